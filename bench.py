@@ -16,9 +16,14 @@ accepted matches land in caller-owned page-locked host buffers, the pairs of a s
 to back with one synchronisation per step (fm_match_accepted_async); N > 1:
 they stay on the device as packed 12-byte rows (fm_match_accepted_dev) and go straight into
 the RCCL all-gather, overlapped with the next pair's kernels.
-Prints ONE JSON line (rank 0).  Beside the headline it carries legs for the other BASELINE
-configs: `classic_ratio_match` and `self_2nn` (configs[1] read literally / Metric_Cache build),
-`expand_c3` (configs[2]), `expand_c4` (configs[3]), `float32_route` (configs[4]).
+Prints ONE JSON line (rank 0).  A plain run measures the headline alone: set-up, warm-up, the
+timed steps, the line.  With --full the line also carries legs for the other BASELINE configs:
+`classic_ratio_match` and `self_2nn` (configs[1] read literally / Metric_Cache build),
+`expand_c3` (configs[2]), `expand_c4` (configs[3]), `float32_route` (configs[4]), plus the CPU
+baselines with the oracle self-check (N = 1) and the collective's cost and the train-sharded
+mode (N > 1); --no-legs / --no-cpu-baseline leave parts of that out again.
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy
+(dump_step_outputs); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -210,6 +215,44 @@ def verify_against_oracle(ctx, Q, T, selfdist, keep, timed_rows, pair0):
         got, scope = ctx.match_accepted(qb, tb, TAU), "fresh call on the first %d query rows of pair 0 x all target rows" % s
     ok = all(len(a) == len(b) and np.array_equal(np.asarray(a).view(np.uint8), np.asarray(b).view(np.uint8)) for a, b in zip(got, want))
     return bool(ok), scope, int(len(want[0]))
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_step_outputs(dirname, counts, rows):
+    """--dump-outputs: what one timed step handed its caller, as DIR/<name>.npy (float32 / float64; indices exact).
+    N = 1: counts = accepted rows per pair, rows = per pair the (query index, train index, distance, ratio) buffers that
+    fm_match_accepted_batch filled; N > 1: counts int64[world, (pairs)] and rows int32[world, (pairs), capacity, 3]
+    (query index, train index, float32 distance bits) as the all-gather left them.  The accepted rows of all pairs are
+    concatenated in order and accepted_counts.npy splits them; should they exceed DUMP_MAX_BYTES, the same fixed, seeded
+    sample of rows is taken from every column and sample_rows.npy holds its row numbers."""
+    counts = np.asarray(counts, dtype=np.int64)
+    if isinstance(rows, np.ndarray):
+        flat = rows.reshape(-1, rows.shape[-2], 3)
+        r = np.concatenate([flat[i, :c] for i, c in enumerate(counts.reshape(-1))])
+        cols = {"query_idx": r[:, 0].astype(np.float64), "train_idx": r[:, 1].astype(np.float64),
+                "distance": np.ascontiguousarray(r[:, 2]).view(np.float32)}
+    else:
+        names = ("query_idx", "train_idx", "distance", "ratio")
+        cols = {name: np.concatenate([bufs[k][:c] for bufs, c in zip(rows, counts)]) for k, name in enumerate(names)}
+        cols["query_idx"] = cols["query_idx"].astype(np.float64)
+        cols["train_idx"] = cols["train_idx"].astype(np.float64)
+    n = len(cols["query_idx"])
+    row_bytes = sum(a.itemsize for a in cols.values())
+    os.makedirs(dirname, exist_ok=True)
+    sample = os.path.join(dirname, "sample_rows.npy")
+    room = DUMP_MAX_BYTES - counts.size * 8 - 1024                  # (1024: the .npy headers)
+    if n * row_bytes > room:
+        k = room // (row_bytes + 8)
+        keep = np.sort(np.random.default_rng(SEED).choice(n, size=k, replace=False))
+        cols = {name: a[keep] for name, a in cols.items()}
+        cols["sample_rows"] = keep.astype(np.float64)
+    elif os.path.exists(sample):
+        os.remove(sample)
+    cols["accepted_counts"] = counts.astype(np.float64)
+    for name, a in cols.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def derived_pair(Q, T, j, rng):
@@ -621,9 +664,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the legs of the other configs, the CPU baselines + oracle self-check (N = 1), "
+                         "the collective's cost and the train-sharded mode (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baselines")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: without the legs of the other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus != world:
@@ -662,7 +711,8 @@ def main():
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
     dev = torch.device("cuda", local_rank) if backend == "nccl" else "cpu"
-    legs = not args.no_legs
+    legs = args.full and not args.no_legs
+    cpu_check = args.full and not args.no_cpu_baseline and world == 1
 
     # Steps are pipelined two deep: step i + 1 is enqueued before the host waits for step i (fm_mark / fm_wait, two
     # output sets), so a step's twelve pairs share ONE distance-kernel launch -- its small kernels run beside the next
@@ -687,7 +737,7 @@ def main():
         selfdist = ctx.self_dist(qb)                    # Metric_Cache build (once per query image)
         if j == 0:
             selfdist0 = selfdist
-        if j == 1 or (j == 0 and PAIRS_PER_STEP == 1):  # timed on a later run (the first pays module load)
+        if args.full and (j == 1 or (j == 0 and PAIRS_PER_STEP == 1)):  # timed on a later run (the first pays module load)
             ctx.reset_stats()
             t0 = time.perf_counter()
             ctx.self_dist(qb)
@@ -775,14 +825,21 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     npass = 0
+    gathered = None
     for _ in range(args.steps):
         npass = step()
     npass = finish_steps()                                  # the last step's results, still inside the timed region
     if gatherer is not None:
-        gatherer.finish()
+        gathered = gatherer.finish()
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                     # (before anything below reuses the output buffers)
+        if world == 1:
+            s_last = (pipe["i"] - 1) % 2
+            dump_step_outputs(args.dump_outputs, [int(c[0]) for c in counts_sets[s_last]], outbufs_sets[s_last])
+        else:
+            dump_step_outputs(args.dump_outputs, gathered[0].cpu().numpy(), gathered[1].cpu().numpy())
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -796,7 +853,7 @@ def main():
     # N > 1: what the collective is and what it costs, so that a 1 -> 8 curve explains itself.  Measured once, OUTSIDE
     # the timed region: the same steps with and without the all-gather (same kernels, same pipeline).
     collective = None
-    if world > 1:
+    if world > 1 and args.full:
         ones = torch.ones(1, dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         ksteps = max(2, min(args.steps, 6))
@@ -831,7 +888,7 @@ def main():
     qb, tb = banks[0]
     # pair 0's accepted rows as the timed batch left them (output set 0), kept for the self-check below
     timed_rows0 = None
-    if world == 1 and use_async:
+    if cpu_check and use_async:
         m0 = int(counts_sets[0][0][0])
         timed_rows0 = tuple(a[:m0].copy() for a in outbufs[0])
 
@@ -855,51 +912,53 @@ def main():
     # and, for the kernel's own rate, the mean of ten back-to-back calls.  r05: the sweep is TRIANGULAR (d(i, j) = d(j, i):
     # every tile above the diagonal is computed once and serves both of its rows), so the matrix cores evaluate about half
     # of the n x n pairs the caller gets -- both figures are reported, the fraction of the MFMA roof over the EVALUATED ones.
-    from fastmatch_amd import _ffi
-    tri_table, _, tri_stages = _ffi.self_dist_plan(((NQ + 127) // 128) * 128)
-    evaluated = float((tri_table[:, 2] - tri_table[:, 1]).sum()) * 128.0 * 512.0       # stages x rows per stage x output rows per workgroup
-    tri_on = ctx.get_option("self_tri") == 1 and NQ >= 32768 - 127
-    if not tri_on:
-        evaluated = float(NQ) * NQ
-    self2 = {"pairs_per_s": float(NQ) * NQ / (self_kernel_ms * 1e-3), "kernel_ms": self_kernel_ms, "wall_s": self_s,
-             "kernel": ("fm::rowreduce_tri_kernel<1> (K1's top-1 body, triangular: launch A = the masked diagonal blocks, launch B = the "
-                        "rest, both directions of every tile; %d stages per workgroup)" % tri_stages) if tri_on else
-                       "fm::rowreduce_kernel<4,1,true,8,3,1,true> (K1's top-1 kernel, diagonal masked)",
-             "distance_evaluations": evaluated, "evaluated_fraction_of_n_squared": evaluated / (float(NQ) * NQ),
-             "note": "Metric_Cache build, 100k x 100k self distances = min over j != i (the second entry of the self 2-NN), outside the "
-                     "timed region; kernel_ms = one call during set-up, kernel_ms_steady = mean of 10 back-to-back calls; pairs_per_s "
-                     "counts the n x n pairs the caller asked for, frac_int8_mfma_peak_steady the distance evaluations the kernel made"}
-    if rank == 0 and legs:
-        ctx.self_dist(qb)
-        ctx.reset_stats()
-        for _ in range(10):
-            ctx.self_dist(qb)
-        s2 = ctx.stats()
-        self2["kernel_ms_steady"] = s2["kernel_ms"] / max(s2["kernel_launches"], 1)
-        self2["pairs_per_s_steady"] = float(NQ) * NQ / (self2["kernel_ms_steady"] * 1e-3)
-        self2["frac_int8_mfma_peak_steady"] = evaluated * OPS_PER_PAIR / (self2["kernel_ms_steady"] * 1e-3) / (INT8_DENSE_PEAK_TOPS * 1e12)
-        if tri_on:                                           # the masked full sweep of r04 beside it, same box, same process
-            ctx.set_option("self_tri", 0)
+    self2 = None
+    if args.full:
+        from fastmatch_amd import _ffi
+        tri_table, _, tri_stages = _ffi.self_dist_plan(((NQ + 127) // 128) * 128)
+        evaluated = float((tri_table[:, 2] - tri_table[:, 1]).sum()) * 128.0 * 512.0       # stages x rows per stage x output rows per workgroup
+        tri_on = ctx.get_option("self_tri") == 1 and NQ >= 32768 - 127
+        if not tri_on:
+            evaluated = float(NQ) * NQ
+        self2 = {"pairs_per_s": float(NQ) * NQ / (self_kernel_ms * 1e-3), "kernel_ms": self_kernel_ms, "wall_s": self_s,
+                 "kernel": ("fm::rowreduce_tri_kernel<1> (K1's top-1 body, triangular: launch A = the masked diagonal blocks, launch B = the "
+                            "rest, both directions of every tile; %d stages per workgroup)" % tri_stages) if tri_on else
+                           "fm::rowreduce_kernel<4,1,true,8,3,1,true> (K1's top-1 kernel, diagonal masked)",
+                 "distance_evaluations": evaluated, "evaluated_fraction_of_n_squared": evaluated / (float(NQ) * NQ),
+                 "note": "Metric_Cache build, 100k x 100k self distances = min over j != i (the second entry of the self 2-NN), outside the "
+                         "timed region; kernel_ms = one call during set-up, kernel_ms_steady = mean of 10 back-to-back calls; pairs_per_s "
+                         "counts the n x n pairs the caller asked for, frac_int8_mfma_peak_steady the distance evaluations the kernel made"}
+        if rank == 0 and legs:
             ctx.self_dist(qb)
             ctx.reset_stats()
             for _ in range(10):
                 ctx.self_dist(qb)
-            s3 = ctx.stats()
-            ctx.set_option("self_tri", 1)
-            self2["kernel_ms_steady_full_sweep"] = s3["kernel_ms"] / max(s3["kernel_launches"], 1)
-        if PAIRS_PER_STEP > 1:                               # the way a dataset's Metric_Caches are built: all query banks in ONE call
-            qbs = [q for q, _ in banks]                      # (two launches for all of them; the same values are attached again)
-            ctx.self_dist_batch(qbs, want_host=False)
-            ctx.sync()                                       # (the call is enqueue-only: its events are read at the next sync)
-            ctx.reset_stats()
-            t0 = time.perf_counter()
-            for _ in range(5):
+            s2 = ctx.stats()
+            self2["kernel_ms_steady"] = s2["kernel_ms"] / max(s2["kernel_launches"], 1)
+            self2["pairs_per_s_steady"] = float(NQ) * NQ / (self2["kernel_ms_steady"] * 1e-3)
+            self2["frac_int8_mfma_peak_steady"] = evaluated * OPS_PER_PAIR / (self2["kernel_ms_steady"] * 1e-3) / (INT8_DENSE_PEAK_TOPS * 1e12)
+            if tri_on:                                           # the masked full sweep of r04 beside it, same box, same process
+                ctx.set_option("self_tri", 0)
+                ctx.self_dist(qb)
+                ctx.reset_stats()
+                for _ in range(10):
+                    ctx.self_dist(qb)
+                s3 = ctx.stats()
+                ctx.set_option("self_tri", 1)
+                self2["kernel_ms_steady_full_sweep"] = s3["kernel_ms"] / max(s3["kernel_launches"], 1)
+            if PAIRS_PER_STEP > 1:                               # the way a dataset's Metric_Caches are built: all query banks in ONE call
+                qbs = [q for q, _ in banks]                      # (two launches for all of them; the same values are attached again)
                 ctx.self_dist_batch(qbs, want_host=False)
-            ctx.sync()
-            self2["ms_per_bank_in_a_batch"] = (time.perf_counter() - t0) * 1e3 / (5.0 * len(qbs))
-            s4 = ctx.stats()
-            self2["kernel_ms_steady_per_bank_in_a_batch"] = s4["kernel_ms"] / max(s4["kernel_launches"], 1) / len(qbs)
-            self2["banks_per_batch_call"] = len(qbs)
+                ctx.sync()                                       # (the call is enqueue-only: its events are read at the next sync)
+                ctx.reset_stats()
+                t0 = time.perf_counter()
+                for _ in range(5):
+                    ctx.self_dist_batch(qbs, want_host=False)
+                ctx.sync()
+                self2["ms_per_bank_in_a_batch"] = (time.perf_counter() - t0) * 1e3 / (5.0 * len(qbs))
+                s4 = ctx.stats()
+                self2["kernel_ms_steady_per_bank_in_a_batch"] = s4["kernel_ms"] / max(s4["kernel_launches"], 1) / len(qbs)
+                self2["banks_per_batch_call"] = len(qbs)
 
     # ONE configs[1] call, the way a caller without a batch makes it: fm_match_accepted (K1 + election +
     # ratio test + compaction into page-locked buffers) and its synchronisation, 20 repetitions.
@@ -1009,7 +1068,8 @@ def main():
     if legs and os.environ.get("FM_BENCH_C4", "1") != "0":
         c4 = leg_expand_c4(ctx, rank, world, dev, backend)
     # N > 1: the OTHER multi-GPU mode of SURVEY.md 8(e), un-timed, so that a multi-GPU record covers both halves
-    tsh = leg_train_sharded(ctx, rank, world, dev, backend) if world > 1 and os.environ.get("FM_BENCH_TRAIN_SHARDED", "1") != "0" else None
+    tsh = leg_train_sharded(ctx, rank, world, dev, backend) if world > 1 and args.full and \
+        os.environ.get("FM_BENCH_TRAIN_SHARDED", "1") != "0" else None
 
     if rank == 0:
         pairs_per_step = float(NQ) * NT * PAIRS_PER_STEP
@@ -1095,9 +1155,10 @@ def main():
             "float32_route": f32,
             "call_ms": call_ms,
             "device": ctx.device_name(),
+            "full": bool(args.full),
         }
         verified = None
-        if world == 1 and not args.no_cpu_baseline:
+        if cpu_check:
             keep = {}
             out["cpu_baseline"] = cpu_baseline(Q, T, keep=keep)
             try:

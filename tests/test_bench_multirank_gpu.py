@@ -19,7 +19,7 @@ def _bench(extra_env, *args):
     env.update({"FM_BENCH_NQ": "33000", "FM_BENCH_NT": "33000", "FM_BENCH_PAIRS": "3", "FM_BENCH_C3": "0", "FM_BENCH_F32": "0",
                 "FM_BENCH_FRESH": "0", "FM_BENCH_C4_PAIRS": "4", "MASTER_ADDR": "127.0.0.1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     env.update(extra_env)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + list(args),
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"] + list(args),
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]

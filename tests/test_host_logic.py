@@ -325,3 +325,36 @@ def test_bench_cpu_baselines_follow_the_containers_cpu_quota(monkeypatch):
     assert bench.host_cpu_allowance() == (limit, None)
     monkeypatch.setattr(builtins, "open", fake({}))
     assert bench.host_cpu_allowance() == (limit, None)
+
+
+def test_bench_dump_outputs_layout_and_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the accepted rows of a step's pairs, concatenated in pair order, as float32 / float64 .npy
+    files with exact indices; above the size cap, the same seeded sample of rows from every column."""
+    import bench
+    rng = np.random.default_rng(3)
+    bufs = [(rng.integers(0, 100000, 9).astype(np.int32), rng.integers(0, 100000, 9).astype(np.int32),
+             rng.random(9).astype(np.float32), rng.random(9)) for _ in range(3)]
+    bench.dump_step_outputs(str(tmp_path / "one"), [4, 0, 9], bufs)
+    got = {f[:-4]: np.load(str(tmp_path / "one" / f)) for f in os.listdir(str(tmp_path / "one"))}
+    assert sorted(got) == ["accepted_counts", "distance", "query_idx", "ratio", "train_idx"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["accepted_counts"].tolist() == [4, 0, 9]
+    for k, name in enumerate(("query_idx", "train_idx", "distance", "ratio")):
+        assert np.array_equal(got[name], np.concatenate([bufs[0][k][:4], bufs[2][k]]))
+    # N > 1: rows [world, pairs, capacity, 3] of (query, train, distance bits) as gathered
+    rows = rng.integers(0, 100000, (2, 3, 7, 3)).astype(np.int32)
+    rows[..., 2] = rng.random((2, 3, 7)).astype(np.float32).view(np.int32)
+    counts = np.array([[1, 2, 3], [0, 7, 1]])
+    want = np.concatenate([rows[w, p, :counts[w, p]] for w in range(2) for p in range(3)])
+    bench.dump_step_outputs(str(tmp_path / "two"), counts, rows)
+    assert np.array_equal(np.load(str(tmp_path / "two" / "query_idx.npy")), want[:, 0])
+    assert np.array_equal(np.load(str(tmp_path / "two" / "distance.npy")).view(np.int32), want[:, 2])
+    assert np.load(str(tmp_path / "two" / "accepted_counts.npy")).shape == (2, 3)
+    # the cap: a fixed sample of rows, the same rows in every column, within the budget
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1024 + 6 * 8 + 5 * 28)
+    for d in ("s1", "s2"):
+        bench.dump_step_outputs(str(tmp_path / d), counts, rows)
+    keep = np.load(str(tmp_path / "s1" / "sample_rows.npy")).astype(np.int64)
+    assert len(keep) == 5 and np.array_equal(keep, np.load(str(tmp_path / "s2" / "sample_rows.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "train_idx.npy")), want[keep, 1])
+    assert sum(os.path.getsize(str(tmp_path / "s1" / f)) for f in os.listdir(str(tmp_path / "s1"))) <= bench.DUMP_MAX_BYTES
