@@ -38,7 +38,7 @@ class fm_stats_ex(ctypes.Structure):
                 ("bytes_moved", ctypes.c_int64)]
 
 
-FM_ABI_VERSION = 8          # include/fastmatch_hip.h: the revision this binding was written against
+FM_ABI_VERSION = 9          # include/fastmatch_hip.h: the revision this binding was written against
 
 
 class fm_expand_desc(ctypes.Structure):
@@ -101,6 +101,7 @@ SYMBOLS = {
     "fm_self_dist_batch": (_INT, [_P, ctypes.c_int32, _P, _P]),
     "fm_knn2": (_INT, [_P, _P, _P, _P, _P]),
     "fm_knn": (_INT, [_P, _P, _P, ctypes.c_int32, _P, _P]),
+    "fm_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
     "fm_xcheck1_keys": (_INT, [_P, _P, _P, _I64, _P]),
     "fm_xcheck1_keys_dev": (_INT, [_P, _P, _P, _I64, _P]),
     "fm_knn2_ratio": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
@@ -484,7 +485,8 @@ class Context(object):
     def set_option(self, name, value):
         """Per-context tuning / batch shape (fm_ctx_set_option): "batch_group", "batch_tail", "nsplit", "nb",
         "nw", "nbuf", "prio", "glds", "coop", "f32_filter", "f32_nw", "f32_nsplit", "f32_fused", "f32_lpc", "f32_bound_every",
-        "async_time_every", "k1_order", "bound_every", "self_tri", "tri_stages", "refill_grid", "expand_big", "expand_huge", "expand_delegate", "expand_grow", "expand_prof".  Results never depend on them."""
+        "async_time_every", "k1_order", "bound_every", "self_tri", "tri_stages", "refill_grid", "expand_big", "expand_huge", "expand_delegate", "expand_grow", "expand_prof",
+        "radius_ws_bytes".  Results never depend on them."""
         self._check(self.lib.fm_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def get_option(self, name):
@@ -580,6 +582,34 @@ class Context(object):
         dist = np.empty((q.n, int(k)), dtype=np.float32)
         self._check(self.lib.fm_knn(self.handle, q.handle, t.handle, int(k), _ptr(idx), _ptr(dist)))
         return idx, dist
+
+    def radius_match(self, q, t, r):
+        """``fm_radius_match``: every train row with distance < r per query row -- cv2's radiusMatch with compactResult
+        False.  ``r`` is a scalar or a float32 [nq] array (one radius per query row).  Returns (offsets int64[nq + 1],
+        idx int32[n], dist float32[n]): row i's list is idx / dist[offsets[i]:offsets[i + 1]], ascending (distance, index).
+        A counts call sizes the arrays, a second call fills them."""
+        nq = q.n
+        if np.ndim(r) == 0:
+            rad, r_all = None, float(np.float32(r))
+        else:
+            rad = np.ascontiguousarray(r, dtype=np.float32).reshape(-1)
+            if rad.shape[0] != nq:
+                raise ValueError("radius_match: %d radii for %d query rows" % (rad.shape[0], nq))
+            r_all = 0.0
+        rp = _ptr(rad) if rad is not None and nq > 0 else None
+        offsets = np.zeros(nq + 1, dtype=np.int64)
+        total = _I64(0)
+        self._check(self.lib.fm_radius_match(self.handle, q.handle, t.handle, rp, r_all, 0, _ptr(offsets), None, None,
+                                             ctypes.byref(total)))
+        n = int(total.value)
+        idx = np.empty(n, dtype=np.int32)
+        dist = np.empty(n, dtype=np.float32)
+        if n > 0:
+            self._check(self.lib.fm_radius_match(self.handle, q.handle, t.handle, rp, r_all, n, _ptr(offsets), _ptr(idx),
+                                                 _ptr(dist), ctypes.byref(total)))
+            if int(total.value) != n:
+                raise FastMatchHipError("fm_radius_match: %d entries on the second call, %d on the first" % (total.value, n))
+        return offsets, idx, dist
 
     def self_dist(self, bank):
         out = np.empty(bank.n, dtype=np.float64)

@@ -265,6 +265,7 @@ static const OptionDef kOptions[] = {
     {"self_tri", &Tuning::self_tri, 0, 2, "FM_SELF_TRI"}, {"tri_stages", &Tuning::tri_stages, 0, 4096, "FM_TRI_STAGES"},
     {"expand_big", &Tuning::expand_big, 0, 1, nullptr}, {"expand_huge", &Tuning::expand_huge, 0, 1, nullptr}, {"expand_delegate", &Tuning::expand_delegate, 0, 1 << 30, "FM_EXPAND_DELEGATE"}, {"expand_grow", &Tuning::expand_grow, 0, 4, nullptr}, {"expand_prof", &Tuning::expand_prof, 0, 1, "FM_EXPAND_PROF"},
     {"delegated_rounds", &Tuning::delegated_rounds, 0, 0, nullptr},       // a counter: set to 0, read
+    {"radius_ws_bytes", &Tuning::radius_ws_bytes, 1 << 16, 0x7fffffff, nullptr},
 };
 
 extern "C" int fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value)
@@ -389,6 +390,7 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx)
     if (ctx->ws_partial) (void)hipFree(ctx->ws_partial);
     if (ctx->ws_out) (void)hipFree(ctx->ws_out);
     if (ctx->ws_in) (void)hipFree(ctx->ws_in);
+    for (void* w : {ctx->ws_rrows, ctx->ws_rkeys, ctx->ws_rtmp}) if (w) (void)hipFree(w);
     if (ctx->h_scratch) (void)hipHostFree(ctx->h_scratch);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);

@@ -732,6 +732,19 @@ extern "C" int fm_knn(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k
     return cs.finish();
 }
 
+// radiusMatch(q, t, maxDistance) (K10, radius.hip): cv2.BFMatcher(NORM_L2).radiusMatch with compactResult = False.
+extern "C" int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* radius, float radius_all, int64_t cap,
+                               int64_t* offsets, int32_t* idx, float* dist, int64_t* n_total)
+{
+    int rc = check_pair(ctx, q, t, "fm_radius_match");
+    if (rc != FM_OK) return rc;
+    if (cap < 0) return fail(ctx, FM_EINVAL, "fm_radius_match: cap is negative");
+    if (!offsets) return fail(ctx, FM_EINVAL, "fm_radius_match: offsets is NULL");
+    if (cap > 0 && (!idx || !dist)) return fail(ctx, FM_EINVAL, "fm_radius_match: idx / dist is NULL with cap > 0");
+    if (q->n > 0 && t->n > 0 && q->kind != t->kind) return fail(ctx, FM_EINVAL, "fm_radius_match: query/train kind mismatch");
+    return radius_match(ctx, *q, *t, radius, radius_all, cap, offsets, idx, dist, n_total);
+}
+
 extern "C" int fm_knn2_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                              int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
 {

@@ -29,6 +29,10 @@ struct fm_ctx {
     void*  ws_partial = nullptr; size_t ws_partial_bytes = 0;
     void*  ws_out = nullptr;     size_t ws_out_bytes = 0;
     void*  ws_in = nullptr;      size_t ws_in_bytes = 0;
+    // K10 (radius.hip): per-row arrays, the candidate keys of one query chunk, rocPRIM's temporary storage
+    void*  ws_rrows = nullptr;   size_t ws_rrows_bytes = 0;
+    void*  ws_rkeys = nullptr;   size_t ws_rkeys_bytes = 0;
+    void*  ws_rtmp = nullptr;    size_t ws_rtmp_bytes = 0;
     // configuration: fm_ctx_set_option (the FM_* environment variables seed it at creation)
     fm::Tuning tune;
     int* d_counters = nullptr;   // device words of the fp16 filter (layout: fm_internal.h, launch_filter)
@@ -129,6 +133,9 @@ int check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who)
 // Planes and scale terms of a (query = reduced, train = output rows) pair of float32 banks for x1_round_f32.
 void fill_round_f32(fm::RoundF32* r, const fm::Bank& q, const fm::Bank& t);
 // One expansion round's cross-checked 1-NN on the whole GPU (K7's delegated cross-check, api_match.hip).
+// K10: radiusMatch (radius.hip); arguments checked by fm_radius_match (api_match.hip)
+int radius_match(fm_ctx* ctx, const fm::Bank& q, const fm::Bank& t, const float* radius, float radius_all, int64_t cap,
+                 int64_t* offsets, int32_t* idx, float* dist, int64_t* n_total);
 int round_xcheck_dense(fm_ctx* ctx, const fm::Bank& q, const int32_t* d_rows, int64_t nq, const fm::Bank& t, int64_t t0, int64_t nt,
                        unsigned long long* d_qbest);
 }

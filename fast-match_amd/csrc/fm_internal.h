@@ -91,6 +91,8 @@ struct Tuning {
     int tri_stages = 0;               // ... stages (128 rows) per slice of the triangular sweep (0 = plan_tri's search)
     int k1_order = 0;                 // K1: workgroup -> (chunk, split) mapping (rowreduce.hip, map_block): 0 split major,
                                       // 1 an XCD owns output chunks, 2 an XCD owns a contiguous share of the split-major order
+    int radius_ws_bytes = 1 << 30;    // K10: device bytes for the candidate keys of one query chunk (radius.hip); a single
+                                      // query row whose list needs more still runs, in a chunk of its own
 };
 
 // ---- K1: row-reduce kernel launcher ---------------------------------------------------

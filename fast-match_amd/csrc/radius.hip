@@ -1,0 +1,603 @@
+// K10 -- radiusMatch: cv2.BFMatcher(NORM_L2).radiusMatch(q, t, maxDistance), compactResult = False.  Every train row j
+// with dist(i, j) < r_i, per query row i, ordered by (float32 bits of the distance, train index).
+//   dist: the bits fm_knn2 returns -- integer route sqrtf((float)d2) of the exact int32 d2, float32 route K5's chain
+//   (s = fmaf(v, v, s), k ascending, then sqrtf); r_i = float32(maxDistance) or the caller's per-row radius; r <= 0 or
+//   NaN: no entries, r = +inf: every train row.
+//
+//   radius_limits_kernel  per query row: integer route D_i = the largest d2 with sqrtf((float)d2) < r_i (sqrt_bits is
+//                         monotone, so "d2 <= D_i" is the exact test; from 4 197 200 on two d2 share one root, which
+//                         the device search over sqrtf itself gets right); float32 route the fp16 filter's threshold
+//                         A <= r_i^2 + M (M = K8's margin, filter_f16.hip) in the MFMA's accumulator units.
+//   radius_*_kernel<FILL> the distance sweep on the matrix cores -- integer route v_mfma_i32_16x16x64_i8 on the
+//                         bank's int8 rows, float32 route v_mfma_f32_16x16x32_f16 on its scaled fp16 rows -- whose
+//                         epilogue is the threshold test: FILL = false counts the hits of every query row, FILL = true
+//                         (after an exclusive scan of the counts) recomputes the tiles and writes 64-bit keys into the
+//                         row's segment (integer route (dist bits << 32) | train row; float32 route (query row << 32) |
+//                         train row, a candidate).
+//   radius_rescore_kernel float32 route: the exact chain per candidate; a candidate at or beyond r_i becomes ~0.
+//   sorting               per segment: <= kRSortThread keys one thread, <= kRSortLds one workgroup (bitonic in LDS),
+//                         longer ones rocPRIM's segmented radix sort (off the hot path: r = inf against large banks).
+//   radius_compact_kernel sorted keys -> train index / distance at the row's final offset.
+// Query rows go in chunks whose candidates fit in the option "radius_ws_bytes" (24 bytes per candidate).
+// Geometry of the sweeps: a workgroup = 4 waves, a wave = 4 blocks of 16 query rows (the MFMA's N, held in VGPRs for the
+// whole sweep), the train rows (M) stream through LDS 64 at a time, rows padded by 16 bytes against bank conflicts.
+// grid = (query groups of 256 rows, splits of the train range).
+#include "ctx_internal.h"
+#include <algorithm>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+
+namespace fm {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef _Float16 rv8h __attribute__((ext_vector_type(8)));
+typedef float rv4f __attribute__((ext_vector_type(4)));
+
+constexpr int kRStage = 64;                // train rows per LDS stage
+constexpr int kRNB = 4;                    // blocks of 16 query rows per wave
+constexpr int kRWaves = 4;
+constexpr int kRQPerWG = 16 * kRNB * kRWaves;
+constexpr int kRRowI8 = kDim + 16;         // LDS row pitch (bytes), int8 rows
+constexpr int kRRowH = 2 * kDim + 16;      // ... fp16 rows
+constexpr int kRSortThread = 16;
+constexpr int kRSortLds = 2048;
+constexpr float kREps = 1.1f / 1024.0f;    // K8's margin: |A - D| <= eps (|c|^2 + max |m|^2) (filter_f16.hip)
+
+struct RSweep {
+    const int8_t* qrows; const int32_t* qnorm;      // integer route (rows of this launch's first query row on)
+    const int8_t* trows; const int32_t* tnorm;
+    const uint16_t* qrowsh; const float* qnormf;    // float32 route
+    const uint16_t* trowsh; const float* tnormf;
+    float cq, ct;              // float32 route: stored |q|^2, |t|^2 -> accumulator units 2^(kq + kt)
+    int all;                   // float32 route without filter planes: every pair is a candidate
+    int nq, nt, per;           // query rows of the launch, train rows, train rows per split (a multiple of kRStage)
+    const int* lim;            // integer route: D_i (-1: none)
+    const float* thr;          // float32 route: threshold on A in accumulator units
+    unsigned* cnt;             // FILL = false: hit counts; FILL = true: cursors (zeroed)
+    const int64_t* off;        // FILL: segment offsets of the launch's query rows, minus `base`
+    int64_t base;
+    unsigned long long* keys;
+};
+
+// Hits of one lane for one query block in a stage (mask over 16 candidates: tile tt, register r -> bit 4 tt + r) into the
+// row's segment: the four lanes of one query row (j, j + 16, j + 32, j + 48) take one cursor increment together.
+__device__ __forceinline__ void r_emit(const RSweep& p, unsigned mask, const unsigned (&hi)[16], int q, bool live, int base, int lane)
+{
+    const int n = __popc(mask);
+    if (!__any(n != 0)) return;
+    const int j = lane & 15, g = lane >> 4;
+    const int n0 = __shfl(n, j), n1 = __shfl(n, j + 16), n2 = __shfl(n, j + 32), n3 = __shfl(n, j + 48);
+    const int tot = n0 + n1 + n2 + n3;
+    const int pre = (g > 0 ? n0 : 0) + (g > 1 ? n1 : 0) + (g > 2 ? n2 : 0);
+    unsigned b0 = 0;
+    if (g == 0 && live && tot > 0) b0 = atomicAdd(&p.cnt[q], (unsigned)tot);
+    b0 = __shfl(b0, j);
+    if (n == 0) return;
+    // (the fill recomputes what the count sweep counted, bit for bit; the segment's end is checked all the same)
+    const int64_t s0 = p.off[q] - p.base, s1 = p.off[q + 1] - p.base;
+    int64_t at = s0 + b0 + pre;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        if (mask & (1u << c)) {
+            const unsigned row = (unsigned)(base + 16 * (c >> 2) + 4 * g + (c & 3));
+            if (at < s1) p.keys[at] = ((unsigned long long)hi[c] << 32) | row;
+            ++at;
+        }
+    }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256)
+void radius_i8_kernel(RSweep p)
+{
+    __shared__ __attribute__((aligned(16))) int8_t srow[kRStage * kRRowI8];
+    __shared__ __attribute__((aligned(16))) int snorm[kRStage];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
+    const int qw = blockIdx.x * kRQPerWG + wave * 16 * kRNB;
+    v4i bq[kRNB][2];
+    int qn[kRNB], lim[kRNB];
+    unsigned count[kRNB];
+#pragma unroll
+    for (int b = 0; b < kRNB; ++b) {
+        const int q = qw + 16 * b + j;
+        const bool live = q < p.nq;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            bq[b][h] = live ? *(const v4i*)(p.qrows + (size_t)q * kDim + 64 * h + 16 * g) : v4i{0, 0, 0, 0};
+        qn[b] = live ? p.qnorm[q] : 0;
+        lim[b] = live ? p.lim[q] : -1;
+        count[b] = 0;
+    }
+    const int t0 = blockIdx.y * p.per, t1 = min(p.nt, t0 + p.per);
+    for (int base = t0; base < t1; base += kRStage) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {       // 64 rows x 8 pieces of 16 B (rows < n_pad: base % 64 == 0, n_pad % 128 == 0)
+            const int piece = tid + 256 * i, r = piece >> 3, c = piece & 7;
+            *(v4i*)(srow + r * kRRowI8 + 16 * c) = *(const v4i*)(p.trows + (size_t)(base + r) * kDim + 16 * c);
+        }
+        if (tid < kRStage) snorm[tid] = p.tnorm[base + tid];
+        __syncthreads();
+        v4i a[4][2], tn[4];
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) a[tt][h] = *(const v4i*)(srow + (16 * tt + j) * kRRowI8 + 64 * h + 16 * g);
+            tn[tt] = *(const v4i*)(snorm + 16 * tt + 4 * g);
+        }
+        const int rowlim = t1 - base - 4 * g;       // register r of tile tt is a real train row iff 16 tt + r < rowlim
+#pragma unroll
+        for (int b = 0; b < kRNB; ++b) {
+            unsigned mask = 0;
+            unsigned hi[16];
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) {
+                v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[tt][0], bq[b][0], v4i{0, 0, 0, 0}, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[tt][1], bq[b][1], acc, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int d2 = qn[b] + tn[tt][r] - 2 * acc[r];
+                    hi[4 * tt + r] = FILL ? sqrt_bits((unsigned)d2) : 0u;
+                    mask |= (d2 <= lim[b] && 16 * tt + r < rowlim) ? (1u << (4 * tt + r)) : 0u;
+                }
+            }
+            if constexpr (FILL) r_emit(p, mask, hi, qw + 16 * b + j, qw + 16 * b + j < p.nq, base, lane);
+            else count[b] += __popc(mask);
+        }
+    }
+    if constexpr (!FILL) {
+#pragma unroll
+        for (int b = 0; b < kRNB; ++b) {
+            unsigned c = count[b];
+            c += __shfl_xor(c, 16);
+            c += __shfl_xor(c, 32);
+            const int q = qw + 16 * b + j;
+            if (g == 0 && q < p.nq && c) atomicAdd(&p.cnt[q], c);
+        }
+    }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256)
+void radius_f16_kernel(RSweep p)
+{
+    __shared__ __attribute__((aligned(16))) char srow[kRStage * kRRowH];
+    __shared__ __attribute__((aligned(16))) float snorm[kRStage];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
+    const int qw = blockIdx.x * kRQPerWG + wave * 16 * kRNB;
+    const bool all = p.all != 0;
+    rv8h bh[kRNB][4];
+    float qn[kRNB], thr[kRNB];
+    unsigned count[kRNB];
+#pragma unroll
+    for (int b = 0; b < kRNB; ++b) {
+        const int q = qw + 16 * b + j;
+        const bool live = q < p.nq;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const v4i h = (live && !all) ? *(const v4i*)(p.qrowsh + (size_t)q * kDim + 32 * s + 8 * g) : v4i{0, 0, 0, 0};
+            bh[b][s] = __builtin_bit_cast(rv8h, h);
+        }
+        qn[b] = (live && !all) ? p.qnormf[q] * p.cq : 0.f;
+        thr[b] = live ? p.thr[q] : -INFINITY;
+        count[b] = 0;
+    }
+    unsigned hi[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) hi[c] = 0u;
+    const int t0 = blockIdx.y * p.per, t1 = min(p.nt, t0 + p.per);
+    for (int base = t0; base < t1; base += kRStage) {
+        if (!all) {
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {   // 64 rows x 16 pieces of 16 B
+                const int piece = tid + 256 * i, r = piece >> 4, c = piece & 15;
+                *(v4i*)(srow + r * kRRowH + 16 * c) = *(const v4i*)(p.trowsh + (size_t)(base + r) * kDim + 8 * c);
+            }
+            if (tid < kRStage) snorm[tid] = p.tnormf[base + tid] * p.ct;
+            __syncthreads();
+        }
+        const int rowlim = t1 - base - 4 * g;
+        unsigned mask[kRNB];
+#pragma unroll
+        for (int b = 0; b < kRNB; ++b) mask[b] = 0;
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+            rv8h a[4];
+            rv4f tn = rv4f{0.f, 0.f, 0.f, 0.f};
+            if (!all) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) a[s] = __builtin_bit_cast(rv8h, *(const v4i*)(srow + (16 * tt + j) * kRRowH + 64 * s + 16 * g));
+                tn = *(const rv4f*)(snorm + 16 * tt + 4 * g);
+            }
+#pragma unroll
+            for (int b = 0; b < kRNB; ++b) {
+                rv4f acc = rv4f{0.f, 0.f, 0.f, 0.f};
+                if (!all) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[s], bh[b][s], acc, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float A = qn[b] + tn[r] - 2.f * acc[r];     // (all: 0, against a threshold of +-inf)
+                    mask[b] |= (A <= thr[b] && 16 * tt + r < rowlim) ? (1u << (4 * tt + r)) : 0u;
+                }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < kRNB; ++b) {
+            const int q = qw + 16 * b + j;
+            if constexpr (FILL) {
+#pragma unroll
+                for (int c = 0; c < 16; ++c) hi[c] = (unsigned)q;
+                r_emit(p, mask[b], hi, q, q < p.nq, base, lane);
+            } else {
+                count[b] += __popc(mask[b]);
+            }
+        }
+    }
+    if constexpr (!FILL) {
+#pragma unroll
+        for (int b = 0; b < kRNB; ++b) {
+            unsigned c = count[b];
+            c += __shfl_xor(c, 16);
+            c += __shfl_xor(c, 32);
+            const int q = qw + 16 * b + j;
+            if (g == 0 && q < p.nq && c) atomicAdd(&p.cnt[q], c);
+        }
+    }
+}
+
+// Per query row: the radius and what the sweep compares against (see the file comment).
+__global__ void radius_limits_kernel(const float* __restrict__ radius, float radius_all, int nq, int f32, int all,
+                                     const float* __restrict__ qnormf, float cq, double unit, float nt_max,
+                                     int* __restrict__ lim, float* __restrict__ thr, float* __restrict__ rr)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    const float r = radius ? radius[i] : radius_all;
+    rr[i] = r;
+    if (!f32) {
+        int D = -1;
+        if (r > 4096.f) D = 0x7fffffff;                  // beyond every d2 of two 128-byte rows (<= 128 * 255^2)
+        else if (r > 0.f) {
+            unsigned h = (unsigned)((double)r * (double)r) + 8u;
+            while (h > 0u && !(sqrtf((float)h) < r)) --h;
+            D = (sqrtf((float)h) < r) ? (int)h : -1;
+        }
+        lim[i] = D;
+    } else {
+        float T;
+        if (!(r > 0.f)) T = -INFINITY;
+        else if (all || __builtin_isinf(r)) T = INFINITY;
+        else {
+            const double r2 = (double)r * (double)r * unit;
+            const double M = (double)kREps * ((double)qnormf[i] * cq + nt_max);
+            T = (float)((r2 + M) * (1.0 + 1.0 / 1048576.0));    // (+ 2^-20: the roundings of r^2 and of the epilogue's A)
+        }
+        thr[i] = T;
+    }
+}
+
+// Float32 route: the exact chain for every candidate key (query row << 32 | train row) of the chunk.
+__global__ __launch_bounds__(256)
+void radius_rescore_kernel(unsigned long long* __restrict__ keys, int64_t n, const float* __restrict__ qrowsf,
+                           const float* __restrict__ trowsf, const float* __restrict__ rr, unsigned* __restrict__ fcnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long k = keys[i];
+    const unsigned q = (unsigned)(k >> 32), t = (unsigned)k;
+    const float4* a = (const float4*)(qrowsf + (size_t)q * kDim);
+    const float4* b = (const float4*)(trowsf + (size_t)t * kDim);
+    float s = 0.f;
+    for (int k4 = 0; k4 < kDim / 4; ++k4) {
+        const float4 x = a[k4], y = b[k4];
+        float v;
+        v = x.x - y.x; s = __builtin_fmaf(v, v, s);
+        v = x.y - y.y; s = __builtin_fmaf(v, v, s);
+        v = x.z - y.z; s = __builtin_fmaf(v, v, s);
+        v = x.w - y.w; s = __builtin_fmaf(v, v, s);
+    }
+    const float d = sqrtf(s);
+    const bool keep = d < rr[q];
+    keys[i] = keep ? (((unsigned long long)__float_as_uint(d) << 32) | t) : ~0ull;
+    if (keep) atomicAdd(&fcnt[q], 1u);
+}
+
+// Segments of at most kRSortThread keys: one thread each, insertion sort.
+__global__ __launch_bounds__(256)
+void radius_sort_thread_kernel(unsigned long long* __restrict__ keys, const int64_t* __restrict__ off, int64_t base, int nrows)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nrows) return;
+    const int64_t b = off[i] - base, len = off[i + 1] - off[i];
+    if (len < 2 || len > kRSortThread) return;
+    unsigned long long* s = keys + b;
+    for (int64_t x = 1; x < len; ++x) {
+        const unsigned long long v = s[x];
+        int64_t y = x - 1;
+        while (y >= 0 && s[y] > v) { s[y + 1] = s[y]; --y; }
+        s[y + 1] = v;
+    }
+}
+
+// Segments of kRSortThread + 1 .. kRSortLds keys: one workgroup each (rows[] lists them), bitonic sort in LDS.
+__global__ __launch_bounds__(256)
+void radius_sort_lds_kernel(unsigned long long* __restrict__ keys, const int64_t* __restrict__ off, int64_t base,
+                            const int* __restrict__ rows)
+{
+    __shared__ unsigned long long s[kRSortLds];
+    const int i = rows[blockIdx.x], tid = threadIdx.x;
+    const int64_t b = off[i] - base;
+    const int len = (int)(off[i + 1] - off[i]);
+    int n = 2;
+    while (n < len) n <<= 1;
+    for (int x = tid; x < n; x += 256) s[x] = x < len ? keys[b + x] : ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= n; k <<= 1)
+        for (int m = k >> 1; m > 0; m >>= 1) {
+            for (int x = tid; x < n; x += 256) {
+                const int y = x ^ m;
+                if (y > x) {
+                    const unsigned long long u = s[x], v = s[y];
+                    if ((u > v) == ((x & k) == 0)) { s[x] = v; s[y] = u; }
+                }
+            }
+            __syncthreads();
+        }
+    for (int x = tid; x < len; x += 256) keys[b + x] = s[x];
+}
+
+// The long segments back from rocPRIM's output buffer.
+__global__ __launch_bounds__(256)
+void radius_copy_back_kernel(unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ sorted,
+                             const int64_t* __restrict__ beg, const int64_t* __restrict__ end)
+{
+    const int64_t b = beg[blockIdx.x], e = end[blockIdx.x];
+    for (int64_t x = b + threadIdx.x; x < e; x += 256) keys[x] = sorted[x];
+}
+
+// One wave per row: the first n sorted keys of the row's segment -> train index / distance at its output offset.
+__global__ __launch_bounds__(256)
+void radius_compact_kernel(const unsigned long long* __restrict__ keys, const int64_t* __restrict__ src_off, int64_t src_base,
+                           const int64_t* __restrict__ dst_off, int64_t dst_base, int nrows,
+                           int32_t* __restrict__ idx, float* __restrict__ dist)
+{
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= nrows) return;
+    const unsigned long long* s = keys + (src_off[row] - src_base);
+    const int64_t d = dst_off[row] - dst_base, n = dst_off[row + 1] - dst_off[row];
+    for (int64_t x = lane; x < n; x += 64) {
+        const unsigned long long k = s[x];
+        idx[d + x] = (int32_t)(unsigned)k;
+        dist[d + x] = __uint_as_float((unsigned)(k >> 32));
+    }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+static int r_splits(int64_t nq, int64_t nt)
+{
+    // ~2048 workgroups on the chip, a split of at least 1024 train rows
+    const int64_t qg = (nq + kRQPerWG - 1) / kRQPerWG;
+    int64_t s = (2048 + qg - 1) / qg;
+    if (s > (nt + 1023) / 1024) s = (nt + 1023) / 1024;
+    if (s < 1) s = 1;
+    if (s > 65535) s = 65535;
+    return (int)s;
+}
+
+static hipError_t r_sweep(const RSweep& base, bool f32, bool fill, int64_t q0, int64_t nq, hipStream_t stream)
+{
+    RSweep p = base;
+    p.nq = (int)nq;
+    if (f32) { if (!p.all) { p.qrowsh += q0 * kDim; p.qnormf += q0; } p.thr += q0; }
+    else     { p.qrows += q0 * kDim; p.qnorm += q0; p.lim += q0; }
+    if (fill) p.off += q0;
+    else p.cnt += q0;
+    const int ns = r_splits(nq, p.nt);
+    int per = (p.nt + ns - 1) / ns;
+    p.per = (per + kRStage - 1) / kRStage * kRStage;
+    const dim3 grid((unsigned)((nq + kRQPerWG - 1) / kRQPerWG), (unsigned)ns);
+    if (f32) {
+        if (fill) hipLaunchKernelGGL(radius_f16_kernel<true>, grid, dim3(256), 0, stream, p);
+        else      hipLaunchKernelGGL(radius_f16_kernel<false>, grid, dim3(256), 0, stream, p);
+    } else {
+        if (fill) hipLaunchKernelGGL(radius_i8_kernel<true>, grid, dim3(256), 0, stream, p);
+        else      hipLaunchKernelGGL(radius_i8_kernel<false>, grid, dim3(256), 0, stream, p);
+    }
+    return hipGetLastError();
+}
+
+static int r_tmp(fm_ctx* ctx, size_t need) { return ws_ensure(ctx, &ctx->ws_rtmp, &ctx->ws_rtmp_bytes, need + 256); }
+
+// offsets[0 .. n] = exclusive scan of counts[0 .. n] (counts[n] = 0) on the device
+static int r_scan(fm_ctx* ctx, const unsigned* counts, int64_t* offsets, int64_t n)
+{
+    size_t bytes = 0;
+    HIP_TRY(ctx, rocprim::exclusive_scan(nullptr, bytes, counts, offsets, (int64_t)0, (size_t)(n + 1), rocprim::plus<int64_t>(), ctx->stream));
+    int rc = r_tmp(ctx, bytes);
+    if (rc != FM_OK) return rc;
+    HIP_TRY(ctx, rocprim::exclusive_scan(ctx->ws_rtmp, bytes, counts, offsets, (int64_t)0, (size_t)(n + 1), rocprim::plus<int64_t>(), ctx->stream));
+    return FM_OK;
+}
+
+static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Sorts the segments [h_off[r] - c0, h_off[r + 1] - c0) of rows r0 .. r1 of the chunk's keys (d_off: the same offsets on the
+// device, from row r0 on).
+static int r_sort(fm_ctx* ctx, unsigned long long* keys, unsigned long long* alt, int64_t nkeys, const int64_t* h_off,
+                  const int64_t* d_off, int64_t r0, int64_t r1, int* d_rows, int64_t* d_beg, int64_t* d_end)
+{
+    const int64_t c0 = h_off[r0], nr = r1 - r0;
+    hipLaunchKernelGGL(radius_sort_thread_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, ctx->stream, keys, d_off, c0, (int)nr);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<int> mid;
+    std::vector<int64_t> beg, end;
+    for (int64_t r = r0; r < r1; ++r) {
+        const int64_t len = h_off[r + 1] - h_off[r];
+        if (len > kRSortLds) { beg.push_back(h_off[r] - c0); end.push_back(h_off[r + 1] - c0); }
+        else if (len > kRSortThread) mid.push_back((int)(r - r0));
+    }
+    if (!mid.empty()) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_rows, mid.data(), mid.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(radius_sort_lds_kernel, dim3((unsigned)mid.size()), dim3(256), 0, ctx->stream, keys, d_off, c0, (const int*)d_rows);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (!beg.empty()) {
+        const size_t nb = beg.size();
+        HIP_TRY(ctx, hipMemcpyAsync(d_beg, beg.data(), nb * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_end, end.data(), nb * 8, hipMemcpyHostToDevice, ctx->stream));
+        size_t bytes = 0;
+        HIP_TRY(ctx, rocprim::segmented_radix_sort_keys(nullptr, bytes, keys, alt, (unsigned)nkeys, (unsigned)nb, d_beg, d_end,
+                                                         0, 64, ctx->stream));
+        int rc = r_tmp(ctx, bytes);
+        if (rc != FM_OK) return rc;
+        HIP_TRY(ctx, rocprim::segmented_radix_sort_keys(ctx->ws_rtmp, bytes, keys, alt, (unsigned)nkeys, (unsigned)nb, d_beg, d_end,
+                                                         0, 64, ctx->stream));
+        hipLaunchKernelGGL(radius_copy_back_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, keys, (const unsigned long long*)alt,
+                           (const int64_t*)d_beg, (const int64_t*)d_end);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    // (the host vectors above were handed to hipMemcpyAsync from pageable memory: staged before the call returns)
+    return FM_OK;
+}
+
+int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const float* radius, float radius_all, int64_t cap,
+                 int64_t* offsets, int32_t* idx, float* dist, int64_t* n_total)
+{
+    const int64_t nq = q.n, nt = t.n;
+    if (nq == 0 || nt == 0 || (!radius && !(radius_all > 0.f))) {       // (NaN and r <= 0 included: no entries)
+        for (int64_t i = 0; i <= nq; ++i) offsets[i] = 0;
+        if (n_total) *n_total = 0;
+        return FM_OK;
+    }
+    if (nt > 0x7fffffff || nq > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, "fm_radius_match: more than 2^31 - 1 rows in a bank");
+    const bool f32 = q.kind == FM_BANK_F32;
+    const bool all = f32 && !filter_usable(q, t);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    CallScope cs(ctx);
+    // per-row arrays: radius | limit | threshold | exact radius | counts [nq+1] | offsets [nq+1] | cursors [nq+1] |
+    // final counts [nq+1] | final offsets [nq+1] | sort row list | long-segment begins | ends
+    const size_t b4 = al256((size_t)(nq + 1) * 4), b8 = al256((size_t)(nq + 1) * 8);
+    int rc = ws_ensure(ctx, &ctx->ws_rrows, &ctx->ws_rrows_bytes, 9 * b4 + 4 * b8);
+    if (rc != FM_OK) return rc;
+    char* w = (char*)ctx->ws_rrows;
+    float* d_rad = (float*)w;            w += b4;
+    int* d_lim = (int*)w;                w += b4;
+    float* d_thr = (float*)w;            w += b4;
+    float* d_rr = (float*)w;             w += b4;
+    unsigned* d_cnt = (unsigned*)w;      w += b4;
+    unsigned* d_cur = (unsigned*)w;      w += b4;
+    unsigned* d_fcnt = (unsigned*)w;     w += b4;
+    int* d_rows = (int*)w;               w += b4;
+    w += b4;
+    int64_t* d_off = (int64_t*)w;        w += b8;
+    int64_t* d_foff = (int64_t*)w;       w += b8;
+    int64_t* d_beg = (int64_t*)w;        w += b8;
+    int64_t* d_end = (int64_t*)w;
+    if (radius) HIP_TRY(ctx, hipMemcpyAsync(d_rad, radius, (size_t)nq * 4, hipMemcpyHostToDevice, ctx->stream));
+    const int dk = q.kscale - t.kscale;
+    const float cq = f32 && !all ? ldexpf(1.f, -dk) : 1.f, ct = f32 && !all ? ldexpf(1.f, dk) : 1.f;
+    const double unit = f32 && !all ? ldexp(1.0, q.kscale + t.kscale) : 1.0;
+    hipLaunchKernelGGL(radius_limits_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
+                       radius ? (const float*)d_rad : (const float*)nullptr, radius_all, (int)nq, f32 ? 1 : 0, all ? 1 : 0,
+                       (const float*)(f32 && !all ? q.normf : nullptr), cq, unit, f32 && !all ? t.nm_max * ct : 0.f, d_lim, d_thr, d_rr);
+    HIP_TRY(ctx, hipGetLastError());
+
+    RSweep sw{};
+    sw.qrows = q.rows8; sw.qnorm = q.norm; sw.trows = t.rows8; sw.tnorm = t.norm;
+    sw.qrowsh = q.rowsh; sw.qnormf = q.normf; sw.trowsh = t.rowsh; sw.tnormf = t.normf;
+    sw.cq = cq; sw.ct = ct; sw.all = all ? 1 : 0;
+    sw.nt = (int)nt; sw.lim = d_lim; sw.thr = d_thr;
+    // 1. counts (candidates on the float32 route), 2. their exclusive scan
+    HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, (size_t)(nq + 1) * 4, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+    sw.cnt = d_cnt;
+    HIP_TRY(ctx, r_sweep(sw, f32, false, 0, nq, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+    ctx->kernel_timed = true;
+    ctx->pending_pairs += nq * nt;
+    ctx->pending_bytes += bank_bytes(&q) + bank_bytes(&t);
+    if ((rc = r_scan(ctx, d_cnt, d_off, nq)) != FM_OK) return rc;
+    std::vector<int64_t> h_off((size_t)nq + 1);
+    HIP_TRY(ctx, hipMemcpyAsync(h_off.data(), d_off, (size_t)(nq + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+    // rows whose candidates are processed: the integer route's counts are final, so only the rows that fit in cap
+    int64_t rows_done = nq;
+    if (!f32) {
+        for (int64_t i = 0; i <= nq; ++i) offsets[i] = h_off[i];
+        if (n_total) *n_total = h_off[nq];
+        rows_done = (int64_t)(std::upper_bound(h_off.begin(), h_off.end(), cap) - h_off.begin()) - 1;
+        if (rows_done <= 0) return cs.finish();
+    }
+    // 3. chunks of query rows whose candidates fit the budget (24 B each: keys, rocPRIM's output, idx + dist)
+    int64_t cmax = (int64_t)ctx->tune.radius_ws_bytes / 24;
+    for (int64_t i = 0; i < rows_done; ++i) cmax = std::max(cmax, h_off[i + 1] - h_off[i]);
+    int64_t final_total = 0;      // float32 route: entries of the rows before the chunk
+    bool open = true;             // ... every row so far fitted in cap
+    std::vector<int64_t> h_foff;
+    for (int64_t r0 = 0; r0 < rows_done;) {
+        int64_t r1 = r0 + 1;
+        while (r1 < rows_done && h_off[r1 + 1] - h_off[r0] <= cmax) ++r1;
+        const int64_t c0 = h_off[r0], nc = h_off[r1] - c0, nr = r1 - r0;
+        if (nc == 0) {
+            if (f32) for (int64_t r = r0; r < r1; ++r) offsets[r] = final_total;
+            r0 = r1;
+            continue;
+        }
+        const size_t kb = al256((size_t)nc * 8);
+        if ((rc = ws_ensure(ctx, &ctx->ws_rkeys, &ctx->ws_rkeys_bytes, 3 * kb)) != FM_OK) return rc;
+        unsigned long long* keys = (unsigned long long*)ctx->ws_rkeys;
+        unsigned long long* alt = (unsigned long long*)((char*)ctx->ws_rkeys + kb);
+        int32_t* d_idx = (int32_t*)((char*)ctx->ws_rkeys + 2 * kb);
+        float* d_dist = (float*)((char*)d_idx + (size_t)nc * 4);
+        HIP_TRY(ctx, hipMemsetAsync(d_cur, 0, (size_t)nr * 4, ctx->stream));
+        sw.cnt = d_cur; sw.off = d_off; sw.base = c0; sw.keys = keys;
+        HIP_TRY(ctx, r_sweep(sw, f32, true, r0, nr, ctx->stream));
+        if (f32) {
+            HIP_TRY(ctx, hipMemsetAsync(d_fcnt, 0, (size_t)(nr + 1) * 4, ctx->stream));
+            hipLaunchKernelGGL(radius_rescore_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ctx->stream, keys, nc,
+                               (const float*)(q.rowsf + (size_t)r0 * kDim), (const float*)t.rowsf, (const float*)(d_rr + r0), d_fcnt);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if ((rc = r_sort(ctx, keys, alt, nc, h_off.data(), d_off + r0, r0, r1, d_rows, d_beg, d_end)) != FM_OK) return rc;
+        if (!f32) {
+            hipLaunchKernelGGL(radius_compact_kernel, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys,
+                               (const int64_t*)(d_off + r0), c0, (const int64_t*)(d_off + r0), c0, (int)nr, d_idx, d_dist);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipMemcpyAsync(idx + c0, d_idx, (size_t)nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(dist + c0, d_dist, (size_t)nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        } else {
+            if ((rc = r_scan(ctx, d_fcnt, d_foff, nr)) != FM_OK) return rc;
+            hipLaunchKernelGGL(radius_compact_kernel, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys,
+                               (const int64_t*)(d_off + r0), c0, (const int64_t*)d_foff, (int64_t)0, (int)nr, d_idx, d_dist);
+            HIP_TRY(ctx, hipGetLastError());
+            h_foff.resize((size_t)nr + 1);
+            HIP_TRY(ctx, hipMemcpyAsync(h_foff.data(), d_foff, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            int64_t fit = 0;             // rows of the chunk whose whole lists fit in cap
+            for (int64_t r = 0; r < nr; ++r) {
+                offsets[r0 + r] = final_total + h_foff[r];
+                if (open && final_total + h_foff[r + 1] <= cap) fit = r + 1;
+            }
+            if (open && fit > 0 && h_foff[fit] > 0) {
+                HIP_TRY(ctx, hipMemcpyAsync(idx + final_total, d_idx, (size_t)h_foff[fit] * 4, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(dist + final_total, d_dist, (size_t)h_foff[fit] * 4, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            }
+            if (fit < nr) open = false;
+            final_total += h_foff[nr];
+        }
+        r0 = r1;
+    }
+    if (f32) {
+        offsets[nq] = final_total;
+        if (n_total) *n_total = final_total;
+    }
+    return cs.finish();
+}
+
+}  // namespace fm

@@ -9,11 +9,15 @@ Mirrors ``matchutil.py`` of the reference:
   reference's FLANN index is randomized and approximate; the exact brute-force k-NN it
   approximates is returned instead, so results are
   deterministic.
+* ``bf_radius_match(dt1, dt2, maxDistance, options={})`` -- ``cv2.BFMatcher(cv2.NORM_L2)
+  .radiusMatch(dt1, dt2, maxDistance)`` (compactResult False; the reference has no call
+  site): every train row with distance < maxDistance, one list per query row ascending
+  by (distance, train index).  ``maxDistance`` may also be one radius per query row.
 * ``sift / get_features / get_keypoints``     -- reference ``matchutil.py:22-36``; SIFT
   stays in OpenCV on the host and needs ``cv2``.
 
 The return value is the same shape OpenCV gives: a list with one inner list per query
-row holding up to ``k`` ``DMatch`` objects (attributes ``queryIdx, trainIdx, imgIdx,
+row holding up to ``k`` ``DMatch`` objects (any number for ``bf_radius_match``) (attributes ``queryIdx, trainIdx, imgIdx,
 distance``).  ``*_arrays`` variants return NumPy arrays and skip the Python objects.
 Errors (dtype/width mismatch, unsupported k) raise ``FastMatchHipError``/``ValueError``
 where cv2 would raise ``cv2.error``.  There is no CPU fallback.
@@ -155,6 +159,27 @@ def ratio_match_arrays(dt1, dt2, tau, options={}):
             qb.close()
         if t_tmp:
             tb.close()
+
+
+def bf_radius_match_arrays(dt1, dt2, maxDistance, options={}):
+    """Array form of :func:`bf_radius_match`: ``(offsets int64[nq + 1], idx int32[n], dist float32[n])``; query row i's
+    list is ``idx[offsets[i]:offsets[i + 1]]`` / ``dist[...]``.  ``maxDistance`` is a scalar (float32, as the cv2 binding
+    passes it) or an array of one radius per query row."""
+    ctx = _context(options)
+    qb, q_tmp, tb, t_tmp = _as_bank_pair(ctx, dt1, dt2)
+    try:
+        return ctx.radius_match(qb, tb, maxDistance)
+    finally:
+        if q_tmp:
+            qb.close()
+        if t_tmp:
+            tb.close()
+
+
+def bf_radius_match(dt1, dt2, maxDistance, options={}):
+    """ cv2.BFMatcher(NORM_L2).radiusMatch(dt1, dt2, maxDistance): a list of DMatch lists, one per query row """
+    off, idx, dist = bf_radius_match_arrays(dt1, dt2, maxDistance, options=options)
+    return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
 
 
 # ---- SIFT stays in OpenCV on the host -------------------------------------------------

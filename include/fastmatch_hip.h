@@ -44,9 +44,9 @@ typedef struct fm_bank fm_bank;
  * fm_expand_desc gained the trailing `lazy`; revision 7, r05: additions -- fm_self_dist_plan, fm_bank_create_f32_cap,
  * fm_bank_append_f32, fm_expand_set_log / _log_counts / _fetch_log -- and fm_expand_run_lazy refuses to resume a run
  * that did not park; revision 8, r06: additions -- fm_knn, the option "f32_bound_every" -- and rounds[i][5] of the
- * per-round log may be -2).  A binding
+ * per-round log may be -2; revision 9: additions -- fm_radius_match, the option "radius_ws_bytes").  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.            */
-#define FM_ABI_VERSION 8
+#define FM_ABI_VERSION 9
 int  fm_abi_version(void);
 
 typedef struct fm_stats {
@@ -107,6 +107,8 @@ int  fm_ctx_destroy(fm_ctx* ctx);
  *   "expand_grow"  0..4   K7: how often a run that fills its pending stack / result list / hash table is
  *                         repeated in a run state four times as large (2; r05: counted per array)
  *   "expand_prof"  0|1    K7: per-phase timers of the first pair of a launch on stderr
+ *   "radius_ws_bytes" 65536..2^31-1  fm_radius_match: device bytes for the candidates of one chunk of query rows (2^30;
+ *                         24 bytes per candidate); a row whose own list needs more runs in a chunk of its own
  * Unknown names and out-of-range values return FM_EINVAL.                                          */
 int  fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value);
 int  fm_ctx_get_option(fm_ctx* ctx, const char* name, int64_t* value);
@@ -179,6 +181,25 @@ int  fm_knn2(fm_ctx* ctx, const fm_bank* q, const fm_bank* t,
  * 100k x 100k uint8 rows); k > 8: FM_EUNSUPPORTED.                                                           */
 int  fm_knn(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k,
             int32_t* idx /*[nq*k]*/, float* dist /*[nq*k]*/);
+
+/* ---- K10: radiusMatch ---------------------------------------------------------------------------------------------
+ * cv2.BFMatcher(cv2.NORM_L2).radiusMatch(q, t, maxDistance) with compactResult = False: every train row closer than a
+ * distance, one list per query row (empty lists included).  The reference has no call site; it is the one-to-many form
+ * of Fast-Match's acceptance test d(q, t) < tau * selfdist(q), a radius per query row.
+ *   r_i = radius[i] (radius != NULL) or radius_all -- float32(maxDistance), what the cv2 binding passes.
+ *   Train row j is in row i's list iff dist(i, j) < r_i, a strict float32 compare; dist is the value fm_knn2 returns
+ *   (integer route sqrtf((float)d2) of the exact int32 d2, float32 route K5's chain s = fmaf(v, v, s), k ascending,
+ *   then sqrtf).  r <= 0 or NaN: an empty list; r = +inf: every train row.  nq = 0 and nt = 0 are valid.
+ *   A list ascends by (distance bits, train index): OpenCV sorts by distance with an unstable std::sort, so any order
+ *   of ties is OpenCV-legal; this one is deterministic.
+ * Output: offsets[0 .. nq] always written (offsets[nq] = *n_total, the number of entries; n_total may be NULL);
+ * idx / dist[0 .. offsets[m]) written for the longest prefix of rows m whose whole lists fit in cap (cap = 0: counts
+ * only, idx / dist may be NULL).  A caller sizes its arrays with a counts call and repeats it with cap = *n_total.
+ * Integer route: v_mfma_i32_16x16x64_i8 sweep against the per-row limit D_i = the largest d2 with sqrtf(d2) < r_i;
+ * float32 route: an fp16-MFMA filter within K8's margin, then the exact chain for the candidates (radius.hip).        */
+int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* radius /*[nq] or NULL*/,
+                    float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* idx, float* dist,
+                    int64_t* n_total);
 
 /* Classic Ratio-Match in one call: knnMatch(q, t, k=2) then ratio = m[0].distance /
  * m[1].distance (float64) and ratio < tau  -- Classic Matching.ipynb cell 3 (JSON 59-72), the
