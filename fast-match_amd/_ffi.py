@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libfastmatch_hip.so")
 
 FM_BANK_I8 = 1
 FM_BANK_F32 = 2
+FM_BANK_BIN = 3             # binary descriptors (Context.bank_binary): NORM_HAMMING
 
 
 class FastMatchHipError(RuntimeError):
@@ -38,7 +39,7 @@ class fm_stats_ex(ctypes.Structure):
                 ("bytes_moved", ctypes.c_int64)]
 
 
-FM_ABI_VERSION = 9          # include/fastmatch_hip.h: the revision this binding was written against
+FM_ABI_VERSION = 10         # include/fastmatch_hip.h: the revision this binding was written against
 
 
 class fm_expand_desc(ctypes.Structure):
@@ -83,6 +84,7 @@ SYMBOLS = {
     "fm_bank_create_u8": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
     "fm_bank_create_f32": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
     "fm_bank_create_f32_route": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
+    "fm_bank_create_bin": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
     "fm_bank_destroy": (_INT, [_P, _P]),
     "fm_bank_info": (_INT, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_INT), ctypes.POINTER(_INT)]),
     "fm_bank_set_selfdist": (_INT, [_P, _P, _P]),
@@ -526,6 +528,21 @@ class Context(object):
         else:
             a = np.ascontiguousarray(a, dtype=np.float32)
             self._check(self.lib.fm_bank_create_f32(self.handle, _ptr(a), a.shape[0], a.shape[1], ctypes.byref(h)))
+        n, dim, kind = _I64(), _INT(), _INT()
+        self._check(self.lib.fm_bank_info(h, ctypes.byref(n), ctypes.byref(dim), ctypes.byref(kind)))
+        return Bank(self, h, n.value, dim.value, kind.value)
+
+    def bank_binary(self, rows):
+        """Upload binary descriptors (ORB, BRIEF, BRISK, FREAK, AKAZE): uint8 [n, bytes], 1 <= bytes <= 64, for NORM_HAMMING
+        (``fm_bank_create_bin``; kind ``FM_BANK_BIN``).  knn2 / knn / xcheck1 / knn2_ratio take a pair of such banks."""
+        a = np.asarray(rows)
+        if a.ndim != 2:
+            raise ValueError("descriptor bank must be 2-D [n, bytes]")
+        if a.dtype != np.uint8:
+            raise ValueError("binary descriptors must be uint8 (cv2 asserts CV_8U for NORM_HAMMING), got %s" % a.dtype)
+        a = np.ascontiguousarray(a)
+        h = _P()
+        self._check(self.lib.fm_bank_create_bin(self.handle, _ptr(a) if a.shape[0] else None, a.shape[0], a.shape[1], ctypes.byref(h)))
         n, dim, kind = _I64(), _INT(), _INT()
         self._check(self.lib.fm_bank_info(h, ctypes.byref(n), ctypes.byref(dim), ctypes.byref(kind)))
         return Bank(self, h, n.value, dim.value, kind.value)

@@ -646,7 +646,9 @@ static void bank_free(Bank* b)
     if (b->auxf) (void)hipFree(b->auxf);
     if (b->selfdist) (void)hipFree(b->selfdist);
     if (b->stage) (void)hipFree(b->stage);
-    b->stage = nullptr;
+    if (b->rowsb) (void)hipFree(b->rowsb);
+    if (b->rows4) (void)hipFree(b->rows4);
+    b->stage = nullptr; b->rowsb = nullptr; b->rows4 = nullptr;
     b->rows8 = nullptr; b->norm = nullptr; b->aux = nullptr; b->rowsf = nullptr; b->selfdist = nullptr;
     b->rowsh = nullptr; b->normf = nullptr; b->auxf = nullptr;
 }
@@ -792,6 +794,7 @@ extern "C" int fm_bank_create_u8_cap(fm_ctx* ctx, const uint8_t* rows, int64_t n
 extern "C" int fm_bank_append_u8(fm_ctx* ctx, fm_bank* bank, const uint8_t* rows, int64_t n, int64_t* first_row)
 {
     if (!ctx || !bank) return fail(ctx, FM_EINVAL, "fm_bank_append_u8: NULL argument");
+    if (int rc = refuse_bin(ctx, bank, "fm_bank_append_u8")) return rc;
     if (bank->kind != FM_BANK_I8 || !bank->rows8) return fail(ctx, FM_EINVAL, "fm_bank_append_u8: not an integer-route bank");
     if (n < 0 || (n > 0 && !rows)) return fail(ctx, FM_EINVAL, "fm_bank_append_u8: bad rows / n");
     const int64_t off = ((bank->n + kTileRows - 1) / kTileRows) * kTileRows;
@@ -889,6 +892,7 @@ extern "C" int fm_bank_create_f32_cap(fm_ctx* ctx, int dim, int64_t capacity, co
 extern "C" int fm_bank_append_f32(fm_ctx* ctx, fm_bank* bank, const float* rows, int64_t n, int64_t* first_row)
 {
     if (!ctx || !bank) return fail(ctx, FM_EINVAL, "fm_bank_append_f32: NULL argument");
+    if (int rc = refuse_bin(ctx, bank, "fm_bank_append_f32")) return rc;
     if (bank->kind != FM_BANK_F32 || !bank->rowsf || !bank->rowsh || bank->cap_pad <= 0)
         return fail(ctx, FM_EINVAL, "fm_bank_append_f32: not a float32-route bank with capacity (fm_bank_create_f32_cap)");
     if (n < 0 || (n > 0 && !rows)) return fail(ctx, FM_EINVAL, "fm_bank_append_f32: bad rows / n");
@@ -933,6 +937,43 @@ extern "C" int fm_bank_append_f32(fm_ctx* ctx, fm_bank* bank, const float* rows,
     return FM_OK;
 }
 
+// K11: a binary bank -- [n][bytes] packed rows, 1 <= bytes <= 64 -- for NORM_HAMMING (hamming.hip).
+extern "C" int fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows, int64_t n, int bytes, fm_bank** out)
+{
+    if (!ctx) return fail(nullptr, FM_EINVAL, "fm_bank_create_bin: ctx is NULL");
+    if (!out) return fail(ctx, FM_EINVAL, "fm_bank_create_bin: bank out pointer is NULL");
+    *out = nullptr;
+    if (n < 0 || bytes < 1 || (n > 0 && !rows)) return fail(ctx, FM_EINVAL, "fm_bank_create_bin: bad rows/n/bytes");
+    if (bytes > 64) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_bin: binary rows of more than 64 bytes (512 bits) are not supported");
+    if (n > (int64_t)INT32_MAX - 2 * kStageRows) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_bin: n too large");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    fm_bank* b = new (std::nothrow) fm_bank();
+    if (!b) return fail(ctx, FM_ENOMEM, "fm_bank_create_bin: out of host memory");
+    b->kind = FM_BANK_BIN;
+    b->n = n;
+    b->dim = bytes;
+    b->ksteps = (bytes + 15) / 16;
+    b->n_pad = ((n + kStageRows - 1) / kStageRows) * kStageRows;
+    if (b->n_pad == 0) b->n_pad = kStageRows;
+    b->cap_pad = b->n_pad;
+    auto bail = [&](hipError_t e, const char* what) {
+        (void)hipGetLastError();
+        bank_free(b); delete b;
+        return fail(ctx, e == hipErrorOutOfMemory ? FM_ENOMEM : FM_EDEVICE, std::string("fm_bank_create_bin: ") + what + ": " + hipGetErrorString(e));
+    };
+    hipError_t e;
+    if ((e = hipMalloc((void**)&b->rowsb, (size_t)b->n_pad * b->ksteps * 16)) != hipSuccess) return bail(e, "packed rows");
+    if ((e = hipMalloc((void**)&b->rows4, (size_t)b->n_pad * b->ksteps * 64)) != hipSuccess) return bail(e, "FP4 rows");
+    const size_t src_bytes = (size_t)n * bytes;
+    int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, src_bytes + 64);
+    if (rc != FM_OK) { bank_free(b); delete b; return rc; }
+    if (src_bytes && (e = hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return bail(e, "upload");
+    if ((e = launch_hamming_prep((const uint8_t*)ctx->ws_in, n, bytes, *b, ctx->stream)) != hipSuccess) return bail(e, "prepare");
+    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "prepare");
+    *out = b;
+    return FM_OK;
+}
+
 extern "C" int fm_bank_create_f32(fm_ctx* ctx, const float* rows, int64_t n, int dim, fm_bank** bank)
 {
     return bank_create(ctx, rows, n, dim, true, bank);
@@ -948,6 +989,7 @@ extern "C" int fm_bank_create_f32_route(fm_ctx* ctx, const float* rows, int64_t 
 extern "C" int fm_bank_refill_u8_async(fm_ctx* ctx, fm_bank* bank, const uint8_t* rows, int64_t n)
 {
     if (!ctx || !bank) return fail(ctx, FM_EINVAL, "fm_bank_refill_u8_async: NULL argument");
+    if (int rc = refuse_bin(ctx, bank, "fm_bank_refill_u8_async")) return rc;
     if (bank->kind != FM_BANK_I8 || !bank->rows8) return fail(ctx, FM_EINVAL, "fm_bank_refill_u8_async: not an integer-route bank");
     if (n < 0 || (n > 0 && !rows)) return fail(ctx, FM_EINVAL, "fm_bank_refill_u8_async: bad rows / n");
     int64_t n_pad = ((n + kStageRows - 1) / kStageRows) * kStageRows;
@@ -1015,6 +1057,7 @@ extern "C" int fm_bank_info(const fm_bank* bank, int64_t* n, int* dim, int* kind
 extern "C" int fm_bank_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* selfdist)
 {
     if (!ctx || !bank) return fail(ctx, FM_EINVAL, "fm_bank_set_selfdist: NULL argument");
+    if (int rc = refuse_bin(ctx, bank, "fm_bank_set_selfdist")) return rc;
     if (bank->n > 0 && !selfdist) return fail(ctx, FM_EINVAL, "fm_bank_set_selfdist: selfdist is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!bank->selfdist) HIP_TRY(ctx, hipMalloc((void**)&bank->selfdist, (size_t)(bank->cap_pad > 0 ? bank->cap_pad : 1) * 8));
@@ -1025,11 +1068,22 @@ extern "C" int fm_bank_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* se
     return FM_OK;
 }
 
-int fm::check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who)
+int fm::refuse_bin(fm_ctx* ctx, const fm_bank* b, const char* who)
+{
+    if (!b || b->kind != FM_BANK_BIN) return FM_OK;
+    return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": binary banks (FM_BANK_BIN, NORM_HAMMING) are served by fm_knn2, fm_knn, "
+                                      "fm_xcheck1 and fm_knn2_ratio only");
+}
+
+int fm::check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who, bool bin_ok)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
     if (!q || !t) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
     if (q->dim != t->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": query/train dim mismatch");
+    // (binary against non-binary is refused even for an empty bank: its rows would go to the L2 kernels)
+    if ((q->kind == FM_BANK_BIN) != (t->kind == FM_BANK_BIN))
+        return fail(ctx, FM_EINVAL, std::string(who) + ": query/train kind mismatch (one bank is binary, FM_BANK_BIN, the other is not)");
+    if (!bin_ok && q->kind == FM_BANK_BIN) return refuse_bin(ctx, q, who);
     if (q->kind != t->kind && q->n > 0 && t->n > 0)      // (an empty bank has no kind of its own)
         return fail(ctx, FM_EINVAL, std::string(who) + ": query/train kind mismatch (one bank is integer-valued, the other is not)");
     return FM_OK;

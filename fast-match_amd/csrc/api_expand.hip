@@ -187,6 +187,8 @@ extern "C" int fm_expand_create(fm_ctx* ctx, const fm_expand_desc* d, fm_expand*
     if (!d || !out) return fail(ctx, FM_EINVAL, "fm_expand_create: NULL argument");
     *out = nullptr;
     if (!d->query || !d->target) return fail(ctx, FM_EINVAL, "fm_expand_create: NULL bank");
+    if (int rc = refuse_bin(ctx, d->query, "fm_expand_create")) return rc;
+    if (int rc = refuse_bin(ctx, d->target, "fm_expand_create")) return rc;
     if (d->query->kind != d->target->kind)
         return fail(ctx, FM_EINVAL, "fm_expand_create: query/target kind mismatch");
     const bool f32 = d->query->kind == FM_BANK_F32;

@@ -622,6 +622,26 @@ int fm::round_xcheck_dense(fm_ctx* ctx, const Bank& q, const int32_t* d_rows, in
 // ---------------------------------------------------------------------------------------
 // K2 entry points
 // ---------------------------------------------------------------------------------------
+// K11: 2-NN of a binary pair (hamming.hip) -- the top-2 sweep on the FP4 matrix cores, merged by knn2_merge_kernel on the
+// float32-route layout (the partial keys carry the float32 bits of the integer Hamming distance: exact, no root ties).
+static int knn2_bin_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* d_idx, float* d_dist)
+{
+    const int64_t nq = q->n;
+    const HamPlan hp = plan_hamming(q->n_pad, t->n_pad);
+    int rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, hp.partial_bytes(2) + 64);
+    if (rc != FM_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+    HIP_TRY(ctx, launch_hamming(*q, *t, 2, hp, (unsigned long long*)ctx->ws_partial, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+    ctx->kernel_timed = true;
+    ctx->pending_pairs += nq * t->n;
+    ctx->pending_bytes += bank_bytes(q) + bank_bytes(t);
+    hipLaunchKernelGGL(knn2_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const unsigned long long*)ctx->ws_partial, hp.nsplit, hp.ncols_alloc, nq, d_idx, d_dist, 1, (unsigned*)nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    return FM_OK;
+}
+
 // Device-side knn2 into d_idx/d_dist (device pointers).
 static int knn2_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* d_idx, float* d_dist)
 {
@@ -634,6 +654,7 @@ static int knn2_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t*
         HIP_TRY(ctx, hipGetLastError());
         return FM_OK;
     }
+    if (q->kind == FM_BANK_BIN) return knn2_bin_device(ctx, q, t, d_idx, d_dist);
     RowReducePlan pl;
     int rc;
     if (f32) {
@@ -670,7 +691,7 @@ static int knn2_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t*
 
 extern "C" int fm_knn2(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* idx, float* dist)
 {
-    int rc = check_pair(ctx, q, t, "fm_knn2");
+    int rc = check_pair(ctx, q, t, "fm_knn2", true);
     if (rc != FM_OK) return rc;
     const int64_t nq = q->n;
     if (nq > 0 && (!idx || !dist)) return fail(ctx, FM_EINVAL, "fm_knn2: output pointer is NULL");
@@ -689,7 +710,7 @@ extern "C" int fm_knn2(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t*
 // knnMatch(dt1, dt2, k) for any k the signature of the reference's bf_match / flann_match admits (matchutil.py:39-43, 46-67).
 extern "C" int fm_knn(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k, int32_t* idx, float* dist)
 {
-    int rc = check_pair(ctx, q, t, "fm_knn");
+    int rc = check_pair(ctx, q, t, "fm_knn", true);
     if (rc != FM_OK) return rc;
     if (k < 1) return fail(ctx, FM_EINVAL, "fm_knn: k must be at least 1");
     if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_knn: k above 8 is not built (cv2.BFMatcher.knnMatch takes any k; the reference calls it with 1 and 2)");
@@ -722,7 +743,10 @@ extern "C" int fm_knn(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k
     }
     if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, knnk_partial_bytes(nq, t->n, k) + 64)) != FM_OK) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-    HIP_TRY(ctx, launch_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
+    if (q->kind == FM_BANK_BIN)
+        HIP_TRY(ctx, launch_hamming_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
+    else
+        HIP_TRY(ctx, launch_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
     ctx->kernel_timed = true;
     ctx->pending_pairs += nq * t->n;
@@ -748,7 +772,7 @@ extern "C" int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
 extern "C" int fm_knn2_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                              int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
 {
-    int rc = check_pair(ctx, q, t, "fm_knn2_ratio");
+    int rc = check_pair(ctx, q, t, "fm_knn2_ratio", true);
     if (rc != FM_OK) return rc;
     if (n_accepted) *n_accepted = 0;
     const int64_t nq = q->n;
@@ -986,6 +1010,7 @@ extern "C" int fm_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks,
     if (!banks) return fail(ctx, FM_EINVAL, "fm_self_dist_batch: banks is NULL");
     for (int i = 0; i < n; ++i) {
         if (!banks[i]) return fail(ctx, FM_EINVAL, "fm_self_dist_batch: bank is NULL");
+        if (int rc = refuse_bin(ctx, banks[i], "fm_self_dist_batch")) return rc;
         for (int j = 0; j < i; ++j) if (banks[j] == banks[i]) return fail(ctx, FM_EINVAL, "fm_self_dist_batch: a bank is listed twice");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1325,6 +1350,7 @@ extern "C" int fm_xcheck1_keys(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
 
 extern "C" int fm_xcheck1_keys_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int64_t t_offset, uint64_t* d_keys)
 {
+    if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return check_pair(ctx, q, t, "fm_xcheck1_keys_dev");
     if (ctx && d_keys) {
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, d_keys) != hipSuccess || at.type != hipMemoryTypeDevice) {
@@ -1377,8 +1403,49 @@ static int xcheck1_keys_common(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
     return cs.finish();
 }
 
+// K11 crossCheck of a binary pair: the reverse top-1 sweep (output rows = train rows, reduced over the query rows) on the FP4
+// matrix cores, then the election and decode of the L2 routes on the float32-route key layout (high word = float32 bits of h).
+static int xcheck1_bin(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* tidx, float* dist)
+{
+    int rc = check_pair(ctx, q, t, "fm_xcheck1", true);
+    if (rc != FM_OK) return rc;
+    const int64_t nq = q->n, nt = t->n;
+    if (nq == 0) return FM_OK;
+    if (!tidx || !dist) return fail(ctx, FM_EINVAL, "fm_xcheck1: output pointer is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // qbest u64[nq] | tidx i32[nq] | dist f32[nq]
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, (size_t)nq * 16 + 64)) != FM_OK) return rc;
+    unsigned long long* d_qbest = (unsigned long long*)ctx->ws_out;
+    int32_t* d_tidx = (int32_t*)((char*)ctx->ws_out + (size_t)nq * 8);
+    float* d_dist = (float*)((char*)ctx->ws_out + (size_t)nq * 12);
+    const HamPlan hp = plan_hamming(t->n_pad, q->n_pad);
+    if (nt > 0 && (rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, hp.partial_bytes(1) + 64)) != FM_OK) return rc;
+    CallScope cs(ctx);
+    HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)nq * 8, ctx->stream));
+    if (nt > 0) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+        HIP_TRY(ctx, launch_hamming(*t, *q, 1, hp, (unsigned long long*)ctx->ws_partial, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+        ctx->kernel_timed = true;
+        ctx->pending_pairs += nq * nt;
+        ctx->pending_bytes += bank_bytes(q) + bank_bytes(t);
+        hipLaunchKernelGGL(xcheck_scatter_kernel, dim3((unsigned)((nt * 4 + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const unsigned long long*)ctx->ws_partial, hp.nsplit, hp.ncols_alloc, nt, d_qbest, 0u, 1, (int*)nullptr,
+                           (unsigned*)nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const unsigned long long*)d_qbest, nq, (const double*)nullptr, 0.0, d_tidx, d_dist, (double*)nullptr,
+                       (uint8_t*)nullptr, (unsigned long long*)nullptr, (int*)nullptr, (unsigned long long*)nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, d2h(ctx, tidx, d_tidx, (size_t)nq * 4));
+    HIP_TRY(ctx, d2h(ctx, dist, d_dist, (size_t)nq * 4));
+    return cs.finish();
+}
+
 extern "C" int fm_xcheck1(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* tidx, float* dist)
 {
+    if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return xcheck1_bin(ctx, q, t, tidx, dist);
     return xcheck_common(ctx, q, t, false, 0.0, tidx, dist, nullptr, nullptr, nullptr, "fm_xcheck1");
 }
 
@@ -1429,6 +1496,8 @@ extern "C" int fm_match_accepted_dev_batch(fm_ctx* ctx, int32_t n, const fm_bank
                                            int64_t cap, int32_t* d_rows, int64_t* d_counts, int64_t* h_counts, void* consumer_stream)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, "fm_match_accepted_dev_batch: ctx is NULL");
+    for (int i = 0; q && t && i < n; ++i)
+        if (q[i] && t[i] && (q[i]->kind == FM_BANK_BIN || t[i]->kind == FM_BANK_BIN)) return check_pair(ctx, q[i], t[i], "fm_match_accepted_dev_batch");
     if (n > 0) {
         if (!d_rows || !d_counts) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_batch: device output pointer is NULL");
         hipPointerAttribute_t at;
@@ -1606,6 +1675,7 @@ extern "C" int fm_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_ban
                                      int32_t* d_rows, int64_t* d_count, int64_t* n_accepted)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, "fm_match_accepted_dev: ctx is NULL");
+    if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return check_pair(ctx, q, t, "fm_match_accepted_dev");
     if (cap < 0) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev: cap < 0");
     if (!d_rows || !d_count) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev: device output pointer is NULL");
     hipPointerAttribute_t at;
@@ -1623,6 +1693,7 @@ extern "C" int fm_match_accepted_dev_async(fm_ctx* ctx, const fm_bank* q, const 
                                            int32_t* d_rows, int64_t* d_count, int64_t* h_count, void* consumer_stream)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, "fm_match_accepted_dev_async: ctx is NULL");
+    if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return check_pair(ctx, q, t, "fm_match_accepted_dev_async");
     if (cap < 0) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_async: cap < 0");
     if (!d_rows || !d_count) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_async: device output pointer is NULL");
     hipPointerAttribute_t at;

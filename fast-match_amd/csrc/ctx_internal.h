@@ -87,8 +87,13 @@ struct fm_ctx {
 };
 
 namespace fm {
-// Algorithmic bytes of a bank in a distance-kernel launch: every row read once (128 B int8, 512 B float32).
-static inline int64_t bank_bytes(const fm::Bank* b) { return b ? b->n * (b->kind == FM_BANK_F32 ? 512 : 128) : 0; }
+// Algorithmic bytes of a bank in a distance-kernel launch: every row read once (128 B int8, 512 B float32, the packed row
+// width of a binary bank).
+static inline int64_t bank_bytes(const fm::Bank* b)
+{
+    if (!b) return 0;
+    return b->n * (b->kind == FM_BANK_BIN ? b->dim : b->kind == FM_BANK_F32 ? 512 : 128);
+}
 }
 
 namespace fm {      // (internal helpers live in the library's namespace: a host program may have a `fail` of its own)
@@ -129,7 +134,11 @@ hipError_t d2h(fm_ctx* ctx, void* dst, const void* src, size_t bytes);
 int drain_pending(fm_ctx* ctx);
 // Everything enqueued on the context -- its own stream and the tail streams the async entry points use.
 void sync_all_streams(fm_ctx* ctx);
-int check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who);
+// bin_ok: the entry point serves binary (FM_BANK_BIN) pairs; the others refuse them with FM_EUNSUPPORTED.  A binary bank
+// paired with a non-binary one is FM_EINVAL, empty banks included.
+int check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who, bool bin_ok = false);
+// FM_EUNSUPPORTED for a binary bank at an entry point that takes one bank (FM_OK otherwise)
+int refuse_bin(fm_ctx* ctx, const fm_bank* b, const char* who);
 // Planes and scale terms of a (query = reduced, train = output rows) pair of float32 banks for x1_round_f32.
 void fill_round_f32(fm::RoundF32* r, const fm::Bank& q, const fm::Bank& t);
 // One expansion round's cross-checked 1-NN on the whole GPU (K7's delegated cross-check, api_match.hip).

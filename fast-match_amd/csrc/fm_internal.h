@@ -28,7 +28,7 @@ constexpr int kAuxPerTile = 64;
 constexpr int kPadCinit   = -(1 << 25);
 
 struct Bank {
-    int      kind   = 0;       // FM_BANK_I8 / FM_BANK_F32
+    int      kind   = 0;       // FM_BANK_I8 / FM_BANK_F32 / FM_BANK_BIN
     int64_t  n      = 0;
     int      dim    = 0;
     int64_t  n_pad  = 0;       // multiple of kStageRows (>= kStageRows so empty banks stage)
@@ -47,6 +47,10 @@ struct Bank {
     int      kscale = 0;       // largest scaled magnitude lies in [2^13, 2^14)
     bool     filt_ok = false;  // every value is finite
     double*  selfdist = nullptr;
+    // FM_BANK_BIN (K11, hamming.hip): dim = bytes per row (1 .. 64), ksteps = ceil(dim / 16) MFMA K steps of 128 bits
+    int      ksteps = 0;
+    uint8_t* rowsb  = nullptr; // [n_pad][16 ksteps] packed rows, zero padded
+    uint8_t* rows4  = nullptr; // [n_pad][64 ksteps] FP4 image: bit 1 -> +1, bit 0 -> -1, padding 0
 };
 
 // OpenCV orders candidates by the float32 root of d2; the integer route orders by d2, which is the same
@@ -178,6 +182,23 @@ hipError_t launch_filter_tri(const Bank& bank, const TriPlan& plan, int bound_ev
 // ---- K9: exact k-NN lists for k up to 8 on the vector ALUs (knn_k.hip; the reference's own calls -- k = 1, 2 -- stay on K1 / K8)
 size_t knnk_partial_bytes(int64_t nq, int64_t nt, int k);
 hipError_t launch_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream);
+int knnk_splits(int64_t nq, int64_t nt);
+// merge of the per-split lists (keys: float32 distance bits << 32 | row) into idx / dist [nq][k]
+hipError_t launch_knnk_merge(const unsigned long long* partial, int nsplit, int nq, int k, int32_t* d_idx, float* d_dist, hipStream_t stream);
+
+// ---- K11: Hamming distance of binary banks (hamming.hip) --------------------------------------------------------------------
+// Top-KTOP (1 or 2) of every row of `cols` over the rows of `red` on the FP4 matrix cores; per split of the reduction range
+// the keys (float32 bits of h << 32 | row of red), ascending, at partial[(split * ncols_alloc + c) * KTOP + k].
+struct HamPlan {
+    int nchunks = 0, ncols_alloc = 0, nstages = 0, nsplit = 0, stages_per_split = 0;
+    size_t partial_bytes(int ktop) const { return (size_t)nsplit * ncols_alloc * ktop * 8; }
+};
+HamPlan plan_hamming(int64_t ncols_pad, int64_t nred_pad);
+hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const HamPlan& plan, unsigned long long* partial, hipStream_t stream);
+// packed rows + FP4 image of n uploaded [n][bytes] rows (b.n_pad, b.ksteps, b.rowsb, b.rows4 set by the caller)
+hipError_t launch_hamming_prep(const uint8_t* d_src, int64_t n, int bytes, const Bank& b, hipStream_t stream);
+// k-NN lists for 1 <= k <= 8 on the vector ALUs (partial: knnk_partial_bytes)
+hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream);
 
 // ---- K4: one workgroup per expansion round (rounds.hip) --------------------------------
 hipError_t launch_rounds(const Bank& q, const Bank& t, const int32_t* d_q_rows, const int64_t* d_q_off,

@@ -15,20 +15,6 @@ namespace fm {
 constexpr int kKnnStage = 64;          // train rows per LDS stage
 
 template <int K>
-__device__ __forceinline__ void knnk_insert(unsigned long long (&keys)[K], unsigned long long key)
-{
-    // strict: an equal key cannot occur (indices differ); a later row never displaces an earlier one at equal distance
-    // because its index is larger
-#pragma unroll
-    for (int i = K - 1; i >= 0; --i) {
-        const unsigned long long prev = i > 0 ? keys[i - 1] : 0ull;
-        const bool here = key < keys[i] && (i == 0 || !(key < prev));
-        const bool shift = i > 0 && key < prev;
-        keys[i] = shift ? prev : (here ? key : keys[i]);
-    }
-}
-
-template <int K>
 __global__ __launch_bounds__(256)
 void knnk_i8_kernel(const int8_t* __restrict__ qrows, const int32_t* __restrict__ qnorm, int nq,
                     const int8_t* __restrict__ trows, const int32_t* __restrict__ tnorm, int nt, int rows_per_split,
@@ -162,6 +148,20 @@ void knnk_merge_kernel(const unsigned long long* __restrict__ partial, int nspli
         idx[(size_t)q * K + i] = has ? (int32_t)(unsigned)keys[i] : -1;
         dist[(size_t)q * K + i] = has ? __uint_as_float((unsigned)(keys[i] >> 32)) : INFINITY;
     }
+}
+
+// K11's vector-ALU lists (hamming.hip) use the same key format and this merge
+hipError_t launch_knnk_merge(const unsigned long long* partial, int nsplit, int nq, int k, int32_t* d_idx, float* d_dist, hipStream_t stream)
+{
+    const dim3 mgrid((unsigned)((nq + 255) / 256));
+#define FM_KNNM(K_)                                                                                                       \
+    case K_: hipLaunchKernelGGL((knnk_merge_kernel<K_>), mgrid, dim3(256), 0, stream, partial, nsplit, nq, d_idx, d_dist); break;
+    switch (k) {
+        FM_KNNM(1) FM_KNNM(2) FM_KNNM(3) FM_KNNM(4) FM_KNNM(5) FM_KNNM(6) FM_KNNM(7) FM_KNNM(8)
+        default: return hipErrorInvalidValue;
+    }
+#undef FM_KNNM
+    return hipGetLastError();
 }
 
 int knnk_splits(int64_t nq, int64_t nt)

@@ -231,4 +231,18 @@ __device__ __forceinline__ bool better(int ah, int ai, int bh_, int bi_)
     return ah > bh_ || (ah == bh_ && ai < bi_);
 }
 
+// Strict insertion of a 64-bit key (distance bits << 32 | row) into an ascending list of K (K9, K11): an equal key cannot
+// occur (indices differ); a later row never displaces an earlier one at equal distance because its index is larger.
+template <int K>
+__device__ __forceinline__ void knnk_insert(unsigned long long (&keys)[K], unsigned long long key)
+{
+#pragma unroll
+    for (int i = K - 1; i >= 0; --i) {
+        const unsigned long long prev = i > 0 ? keys[i - 1] : 0ull;
+        const bool here = key < keys[i] && (i == 0 || !(key < prev));
+        const bool shift = i > 0 && key < prev;
+        keys[i] = shift ? prev : (here ? key : keys[i]);
+    }
+}
+
 }  // namespace fm

@@ -13,6 +13,12 @@ Mirrors ``matchutil.py`` of the reference:
   .radiusMatch(dt1, dt2, maxDistance)`` (compactResult False; the reference has no call
   site): every train row with distance < maxDistance, one list per query row ascending
   by (distance, train index).  ``maxDistance`` may also be one radius per query row.
+* ``options["normType"]``: ``NORM_L2`` (4, the default) or ``NORM_HAMMING`` (6) -- cv2's values.  With
+  ``NORM_HAMMING`` the descriptors are binary (ORB, BRIEF, BRISK, FREAK, AKAZE: uint8 rows of 1 .. 64 bytes,
+  ``Context.bank_binary``) and the distance is the bit count of ``q XOR t`` (``cv2.BFMatcher(cv2.NORM_HAMMING,
+  crossCheck)``); ``bf_match``, ``flann_match`` and ``ratio_match_arrays`` honour it, ``bf_radius_match`` does not
+  (``ValueError``), nor does anything else take ``NORM_HAMMING2``.  Without ``normType`` every array is an L2 bank,
+  a uint8 [n, 32] array included.
 * ``sift / get_features / get_keypoints``     -- reference ``matchutil.py:22-36``; SIFT
   stays in OpenCV on the host and needs ``cv2``.
 
@@ -25,6 +31,9 @@ where cv2 would raise ``cv2.error``.  There is no CPU fallback.
 import numpy as np
 
 from . import _ffi
+
+NORM_L2 = 4             # cv2.NORM_L2
+NORM_HAMMING = 6        # cv2.NORM_HAMMING
 
 
 class DMatch(object):
@@ -56,6 +65,37 @@ def _as_bank(ctx, d):
     if a.ndim != 2:
         raise ValueError("descriptors must be a 2-D [n, dim] array")
     return ctx.bank(a), True
+
+
+def _norm_type(options, dt1, dt2):
+    """options["normType"], checked against the operands BEFORE anything is uploaded (cv2 asserts the same in its matcher)."""
+    norm = options.get("normType", NORM_L2) if options else NORM_L2
+    if norm not in (NORM_L2, NORM_HAMMING):
+        raise ValueError("normType %r: the HIP path builds NORM_L2 (4) and NORM_HAMMING (6) only%s"
+                         % (norm, " (NORM_HAMMING2 is not built)" if norm == 7 else ""))
+    for d in (dt1, dt2):
+        if isinstance(d, _ffi.Bank):
+            if (d.kind == _ffi.FM_BANK_BIN) != (norm == NORM_HAMMING):
+                raise ValueError("a binary bank (Context.bank_binary) goes with normType NORM_HAMMING, and only it"
+                                 if d.kind == _ffi.FM_BANK_BIN else "NORM_HAMMING needs binary banks (Context.bank_binary)")
+        elif norm == NORM_HAMMING and np.asarray(d).dtype != np.uint8:
+            raise ValueError("NORM_HAMMING needs uint8 descriptors (cv2 asserts CV_8U), got %s" % np.asarray(d).dtype)
+    return norm
+
+
+def _bank_pair(ctx, dt1, dt2, norm):
+    if norm != NORM_HAMMING:
+        return _as_bank_pair(ctx, dt1, dt2)
+    banks = []
+    try:
+        for d in (dt1, dt2):
+            banks.append((d, False) if isinstance(d, _ffi.Bank) else (ctx.bank_binary(np.asarray(d)), True))
+    except Exception:
+        for b, tmp in banks:
+            if tmp:
+                b.close()
+        raise
+    return banks[0][0], banks[0][1], banks[1][0], banks[1][1]
 
 
 def _as_bank_pair(ctx, dt1, dt2):
@@ -96,8 +136,9 @@ def bf_match_arrays(dt1, dt2, k=1, options={}):
         # cv2.BFMatcher.knnMatch takes any k; the reference calls k = 1 and 2 (fastmatch.pyx:122-123, 161-162, cache.pyx:250)
         raise ValueError("bf_match: k = %d: the HIP path builds k-NN lists up to k = 8 (FM_EUNSUPPORTED beyond)" % k)
     crossCheck = k == 1 and options.get("crossCheck", False) == True   # noqa: E712  (reference semantics)
+    norm = _norm_type(options, dt1, dt2)
     ctx = _context(options)
-    qb, q_tmp, tb, t_tmp = _as_bank_pair(ctx, dt1, dt2)
+    qb, q_tmp, tb, t_tmp = _bank_pair(ctx, dt1, dt2, norm)
     try:
         if crossCheck:
             return ctx.xcheck1(qb, tb)
@@ -127,7 +168,7 @@ def matches_from_arrays(idx, dist):
 
 
 def bf_match(dt1, dt2, k=1, options={}):
-    """ Use the HIP brute-force matcher with OpenCV BFMatcher(NORM_L2) semantics """
+    """ Use the HIP brute-force matcher with OpenCV BFMatcher(normType) semantics (NORM_L2 unless options say NORM_HAMMING) """
     idx, dist = bf_match_arrays(dt1, dt2, k=k, options=options)
     return matches_from_arrays(idx, dist)
 
@@ -150,8 +191,9 @@ def ratio_match_arrays(dt1, dt2, tau, options={}):
     """Classic Ratio-Match (the reference's baseline, ``Classic Matching.ipynb`` cell 3):
     brute-force 2-NN then ``m[0].distance / m[1].distance < tau`` in float64, on the device.
     Returns (query idx, train idx, distance, ratio) of the accepted matches, ascending query."""
+    norm = _norm_type(options, dt1, dt2)
     ctx = _context(options)
-    qb, q_tmp, tb, t_tmp = _as_bank_pair(ctx, dt1, dt2)
+    qb, q_tmp, tb, t_tmp = _bank_pair(ctx, dt1, dt2, norm)
     try:
         return ctx.knn2_ratio(qb, tb, tau)
     finally:
@@ -165,6 +207,8 @@ def bf_radius_match_arrays(dt1, dt2, maxDistance, options={}):
     """Array form of :func:`bf_radius_match`: ``(offsets int64[nq + 1], idx int32[n], dist float32[n])``; query row i's
     list is ``idx[offsets[i]:offsets[i + 1]]`` / ``dist[...]``.  ``maxDistance`` is a scalar (float32, as the cv2 binding
     passes it) or an array of one radius per query row."""
+    if _norm_type(options, dt1, dt2) == NORM_HAMMING:
+        raise ValueError("bf_radius_match: radiusMatch with NORM_HAMMING is not built (NORM_L2 only)")
     ctx = _context(options)
     qb, q_tmp, tb, t_tmp = _as_bank_pair(ctx, dt1, dt2)
     try:

@@ -35,6 +35,7 @@ extern "C" {
 #define FM_NO_STREAM ((void*)(intptr_t)-1)   /* "no consumer stream" (NULL is the null stream) */
 #define FM_BANK_I8   1       /* uint8 / integer-valued float32 rows: exact int8-MFMA route    */
 #define FM_BANK_F32  2       /* general float32 rows: fp32 fma-chain route                    */
+#define FM_BANK_BIN  3       /* binary descriptors (fm_bank_create_bin): Hamming distance, K11 */
 
 typedef struct fm_ctx  fm_ctx;
 typedef struct fm_bank fm_bank;
@@ -44,9 +45,10 @@ typedef struct fm_bank fm_bank;
  * fm_expand_desc gained the trailing `lazy`; revision 7, r05: additions -- fm_self_dist_plan, fm_bank_create_f32_cap,
  * fm_bank_append_f32, fm_expand_set_log / _log_counts / _fetch_log -- and fm_expand_run_lazy refuses to resume a run
  * that did not park; revision 8, r06: additions -- fm_knn, the option "f32_bound_every" -- and rounds[i][5] of the
- * per-round log may be -2; revision 9: additions -- fm_radius_match, the option "radius_ws_bytes").  A binding
+ * per-round log may be -2; revision 9: additions -- fm_radius_match, the option "radius_ws_bytes"; revision 10: additions --
+ * FM_BANK_BIN, fm_bank_create_bin).  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.            */
-#define FM_ABI_VERSION 9
+#define FM_ABI_VERSION 10
 int  fm_abi_version(void);
 
 typedef struct fm_stats {
@@ -59,7 +61,7 @@ typedef struct fm_stats {
 
 /* fm_stats plus what later revisions add; struct_bytes = sizeof(fm_stats_ex) of the library that filled it.
  * bytes_moved = ALGORITHMIC bytes of the distance-kernel launches in kernel_ms: every bank row of a launch read
- * once (128 B per integer-route row, 512 B per float32 row) -- the numerator of an HBM-roofline fraction; the
+ * once (128 B per integer-route row, 512 B per float32 row, the packed width of a binary row) -- the numerator of an HBM-roofline fraction; the
  * bytes a launch really fetched come from the PMC counters (profiles/).                                       */
 typedef struct fm_stats_ex {
     int64_t  struct_bytes;
@@ -148,6 +150,24 @@ int  fm_bank_create_f32(fm_ctx* ctx, const float*   rows, int64_t n, int dim, fm
  * 0..255: for banks that must pair with a non-integer bank (e.g. one Grid_Cache cell of a
  * RootSIFT image whose values are all 0 or 1).  Distances are the same numbers either way.  */
 int  fm_bank_create_f32_route(fm_ctx* ctx, const float* rows, int64_t n, int dim, fm_bank** bank);
+/* ---- K11: binary descriptors, NORM_HAMMING -------------------------------------------------------------------------------
+ * cv2.BFMatcher(cv2.NORM_HAMMING[, crossCheck]) on ORB / BRIEF / BRISK / FREAK / AKAZE rows: the reference matches SIFT only but
+ * names the detector as an argument (get_features(data, feature_type), matchutil.py:31).  A binary bank holds n packed rows of
+ * `bytes` bytes, 1 <= bytes <= 64 (0 or negative: FM_EINVAL; > 64: FM_EUNSUPPORTED); n may be 0; fm_bank_info reports
+ * dim = bytes, kind = FM_BANK_BIN.  Contract (cv::batchDistance, dtype CV_32S): h(q, t) = popcount(q XOR t), dist = (float)h, exact.
+ *   fm_knn2, fm_knn (1 <= k <= 8; k > 8 FM_EUNSUPPORTED): lists ascend by (h, train index) -- the earlier train row wins a tie;
+ *     idx -1 / dist +inf where t has fewer than k rows.
+ *   fm_xcheck1: every train row elects its nearest query row (strict <: the lowest query index on ties); each query keeps the
+ *     closest electing train row (strict <, ascending train order); a query nobody elects gets -1 / +inf.
+ *   fm_knn2_ratio: the classic ratio match as for L2, d0 / d1 < tau in float64, d1 == 0 rejected (frequent: duplicate rows).
+ * k = 1, 2 and crossCheck run on the matrix cores: every bit an FP4 value +1 / -1 (padding 0), the dot product of two rows is
+ * W - 2 h, exact in the f32 accumulator of v_mfma_scale_f32_16x16x128_f8f6f4 (hamming.hip); k = 3 .. 8: vector ALUs (XOR +
+ * popcount).  Every other entry point that takes a bank refuses a binary one with FM_EUNSUPPORTED before any kernel reads it:
+ * fm_radius_match, fm_self_dist(_batch), fm_bank_set_selfdist, fm_match_ratio, fm_match_accepted*, fm_xcheck1_keys*,
+ * fm_xcheck1_batched, fm_bank_refill_u8_async, fm_bank_append_*, fm_expand_create.  A binary bank paired with a non-binary one
+ * is FM_EINVAL, even when one of them is empty.  Not built: NORM_HAMMING2, Hamming radiusMatch, binary descriptors in the
+ * Fast-Match loop itself (self distances, fm_expand_*, batches, sharded keys), k > 8.                                    */
+int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t n, int bytes, fm_bank** bank);
 int  fm_bank_destroy(fm_ctx* ctx, fm_bank* bank);
 int  fm_bank_info(const fm_bank* bank, int64_t* n, int* dim, int* kind);
 /* Attach per-row self distances (Metric_Cache.*["distances"], float64, cache.pyx:252,273)
