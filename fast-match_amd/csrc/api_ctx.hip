@@ -356,6 +356,7 @@ extern "C" int fm_ctx_create(int device_id, fm_ctx** out)
     ctx->dbg_f32 = getenv("FM_F32_DEBUG") != nullptr;
     ctx->dbg_expand = getenv("FM_EXPAND_DEBUG") != nullptr;
     ctx->dbg_park = ctx->dbg_expand && getenv("FM_PARK_PROF") != nullptr;
+    if (hipMalloc((void**)&ctx->d_cut, kRRBatchMax * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); ctx->d_cut = nullptr; }
     if (hipMalloc((void**)&ctx->d_counters, filter_flag_bytes()) != hipSuccess || hipMemset(ctx->d_counters, 0, filter_flag_bytes()) != hipSuccess) {
         (void)hipGetLastError();
         ctx->d_counters = nullptr;
@@ -394,6 +395,7 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx)
     if (ctx->h_scratch) (void)hipHostFree(ctx->h_scratch);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
+    if (ctx->d_cut) (void)hipFree(ctx->d_cut);
     if (ctx->ev_call0) (void)hipEventDestroy(ctx->ev_call0);
     if (ctx->ev_call1) (void)hipEventDestroy(ctx->ev_call1);
     if (ctx->ev_k0) (void)hipEventDestroy(ctx->ev_k0);
@@ -650,6 +652,7 @@ static void bank_free(Bank* b)
     if (b->rows4) (void)hipFree(b->rows4);
     b->stage = nullptr; b->rowsb = nullptr; b->rows4 = nullptr;
     b->rows8 = nullptr; b->norm = nullptr; b->aux = nullptr; b->rowsf = nullptr; b->selfdist = nullptr;
+    b->sdmax = nullptr; b->sdmax_rows = -1;
     b->rowsh = nullptr; b->normf = nullptr; b->auxf = nullptr;
 }
 
@@ -1060,11 +1063,22 @@ extern "C" int fm_bank_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* se
     if (int rc = refuse_bin(ctx, bank, "fm_bank_set_selfdist")) return rc;
     if (bank->n > 0 && !selfdist) return fail(ctx, FM_EINVAL, "fm_bank_set_selfdist: selfdist is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!bank->selfdist) HIP_TRY(ctx, hipMalloc((void**)&bank->selfdist, (size_t)(bank->cap_pad > 0 ? bank->cap_pad : 1) * 8));
-    if (bank->n > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(bank->selfdist, selfdist, (size_t)bank->n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    int rc;
+    if ((rc = bank_selfdist_alloc(ctx, bank)) != FM_OK) return rc;
+    bank->sdmax_rows = -1;
+    if (bank->n > 0) HIP_TRY(ctx, hipMemcpyAsync(bank->selfdist, selfdist, (size_t)bank->n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = enqueue_selfdist_max(ctx, bank, ctx->stream)) != FM_OK) return rc;
+    if (bank->n > 0) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return FM_OK;
+}
+
+int fm::bank_selfdist_alloc(fm_ctx* ctx, fm_bank* b)
+{
+    if (b->selfdist) return FM_OK;
+    const size_t cap = (size_t)(b->cap_pad > 0 ? b->cap_pad : 1);
+    HIP_TRY(ctx, hipMalloc((void**)&b->selfdist, cap * 8 + 8));
+    b->sdmax = (unsigned long long*)(b->selfdist + cap);
+    b->sdmax_rows = -1;
     return FM_OK;
 }
 

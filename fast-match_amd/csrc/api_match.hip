@@ -339,6 +339,76 @@ __global__ void selfdist_from_knn_kernel(const float* __restrict__ dist2, int64_
     if (i < n) out[i] = (double)dist2[2 * i + 1];
 }
 
+// Bank::sdmax: the maximum of the self distances' bit patterns (>= 0 for every value that allows a ratio cut, so the
+// unsigned order of the patterns is the order of the values; inf, NaN and sign bits land at or above +inf's pattern,
+// which ratio_cut_d2 reads as "no cut").  *out is 0 on entry.
+__global__ __launch_bounds__(256)
+void selfdist_max_kernel(const double* __restrict__ sd, int64_t n, unsigned long long* __restrict__ out)
+{
+    unsigned long long m = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(sd[i]);
+        m = b > m ? b : m;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long x = __shfl_xor(m, o);
+        m = x > m ? x : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(out, m);
+}
+
+int fm::enqueue_selfdist_max(fm_ctx* ctx, fm_bank* b, hipStream_t stream)
+{
+    if (!b->sdmax) return FM_OK;
+    HIP_TRY(ctx, hipMemsetAsync(b->sdmax, 0, 8, stream));
+    if (b->n > 0) {
+        const int64_t blocks = (b->n + 255) / 256;
+        hipLaunchKernelGGL(selfdist_max_kernel, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(256), 0, stream,
+                           (const double*)b->selfdist, b->n, b->sdmax);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    b->sdmax_rows = b->n;
+    return FM_OK;
+}
+
+// D* of the ratio test (ratio_cut.h) for the pairs of one K1 launch, from their query banks' largest self distances:
+// out[i] for every pair with sdmax[i] != null.
+struct CutArgs {
+    const unsigned long long* sdmax[kRRBatchMax];
+    unsigned* out;
+    double tau;
+    int n;
+};
+
+__global__ void ratio_cut_kernel(CutArgs a)
+{
+    const int i = threadIdx.x;
+    if (i < a.n && a.sdmax[i]) a.out[i] = ratio_cut_d2(__longlong_as_double((long long)*a.sdmax[i]), a.tau);
+}
+
+// The accepted-only calls: the cut words of pairs (q[i], -) into ctx->d_cut, enqueued on ctx->stream in front of their K1
+// (which reads them on the same stream).  cut[i] = null for a pair without one: a query bank whose self distances were not
+// reduced for all of its current rows (a refill to more rows than they were computed for), or no device words.
+static int enqueue_ratio_cut(fm_ctx* ctx, int n, const fm_bank* const* q, double tau, const unsigned** cut)
+{
+    CutArgs a{};
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const fm_bank* b = q[i];
+        const bool ok = ctx->d_cut && b->kind == FM_BANK_I8 && b->sdmax && b->sdmax_rows >= b->n;
+        a.sdmax[i] = ok ? b->sdmax : nullptr;
+        cut[i] = ok ? ctx->d_cut + i : nullptr;
+        any = any || ok;
+    }
+    if (!any) return FM_OK;
+    a.out = ctx->d_cut;
+    a.tau = tau;
+    a.n = n;
+    hipLaunchKernelGGL(ratio_cut_kernel, dim3(1), dim3(64), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return FM_OK;
+}
+
 struct SelfMerge {
     const unsigned long long* partial[kRRBatchMax];
     double* out[kRRBatchMax];
@@ -1017,15 +1087,21 @@ extern "C" int fm_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks,
     std::vector<double*> d_out((size_t)n, nullptr);
     std::vector<const fm_bank*> cb((size_t)n, nullptr);
     bool any_out = false;
+    int rc;
     for (int i = 0; i < n; ++i) {
         fm_bank* b = banks[i];
         // (the first attachment allocates; a refilled bank keeps its array: fm_bank_refill_u8_async keeps the capacity)
-        if (!b->selfdist) HIP_TRY(ctx, hipMalloc((void**)&b->selfdist, (size_t)(b->cap_pad > 0 ? b->cap_pad : 1) * 8));
+        if ((rc = bank_selfdist_alloc(ctx, b)) != FM_OK) return rc;
+        b->sdmax_rows = -1;           // (until the largest of the new values is known: no ratio cut)
         d_out[(size_t)i] = b->selfdist;
         cb[(size_t)i] = b;
         any_out = any_out || (out && out[i] && b->n > 0);
     }
-    int rc;
+    // the largest self distance of every bank, behind the sweeps on the same stream
+    auto reduce_max = [&]() {
+        for (int i = 0; i < n; ++i) if (int e = enqueue_selfdist_max(ctx, banks[i], ctx->stream)) return e;
+        return (int)FM_OK;
+    };
     if (!any_out) {
         // enqueue only: accounted at the next fm_sync like the other asynchronous calls
         fm_ctx::PendingTimer tm;
@@ -1036,6 +1112,7 @@ extern "C" int fm_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks,
         HIP_TRY(ctx, hipEventRecord(tm.k0, ctx->stream));
         rc = selfdist_device(ctx, n, cb.data(), d_out.data(), false);
         HIP_TRY(ctx, hipEventRecord(tm.k1, ctx->stream));
+        if (rc == FM_OK) rc = reduce_max();
         HIP_TRY(ctx, hipEventRecord(tm.c1, ctx->stream));
         tm.timed = rc == FM_OK && ctx->pending_pairs > 0;
         tm.call_timed = true;
@@ -1048,6 +1125,7 @@ extern "C" int fm_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks,
     }
     CallScope cs(ctx);
     if ((rc = selfdist_device(ctx, n, cb.data(), d_out.data(), true)) != FM_OK) return rc;
+    if ((rc = reduce_max()) != FM_OK) return rc;
     for (int i = 0; i < n; ++i)
         if (out[i] && banks[i]->n > 0) HIP_TRY(ctx, d2h(ctx, out[i], d_out[(size_t)i], (size_t)banks[i]->n * 8));
     return cs.finish();
@@ -1228,10 +1306,12 @@ static int xcheck_common(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, bool w
         const bool timed_call = time_every > 0 && (ctx->async_calls++ % time_every) == 0;
         tm.timed = tm.timed && timed_call;
         tm.call_timed = timed_call;
+        const unsigned* cut = nullptr;
+        if (nt > 0 && compact && (rc = enqueue_ratio_cut(ctx, 1, &q, tau, &cut)) != FM_OK) return rc;
         if (timed_call) HIP_TRY(ctx, hipEventRecord(tm.k0, ctx->stream));
         if (nt > 0)
             HIP_TRY(ctx, launch_rowreduce(*t, *q, 1, pl, (unsigned long long*)sl.ws, coop ? (int*)((char*)sl.ws + L.pbytes) : nullptr,
-                                          (ctx->tune.glds != 0), ctx->stream));
+                                          (ctx->tune.glds != 0), ctx->stream, cut));
         // (untimed calls hand over through the slot's own event, created without timing)
         hipEvent_t handover = timed_call ? tm.k1 : sl.k_done;
         HIP_TRY(ctx, hipEventRecord(handover, ctx->stream));
@@ -1255,8 +1335,11 @@ static int xcheck_common(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, bool w
         if (f32) {
             if ((rc = rowreduce_f32_route(ctx, t, q, 1, &pl)) != FM_OK) return rc;
         } else {
+            // (accepted-only: only rows that pass the ratio test are reported -- K1 may drop what cannot pass)
+            const unsigned* cut = nullptr;
+            if (compact && with_ratio && (rc = enqueue_ratio_cut(ctx, 1, &q, tau, &cut)) != FM_OK) return rc;
             HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-            HIP_TRY(ctx, launch_rowreduce(*t, *q, 1, pl, (unsigned long long*)ctx->ws_partial, d_bound, (ctx->tune.glds != 0), ctx->stream));
+            HIP_TRY(ctx, launch_rowreduce(*t, *q, 1, pl, (unsigned long long*)ctx->ws_partial, d_bound, (ctx->tune.glds != 0), ctx->stream, cut));
             HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
         }
         ctx->kernel_timed = true;
@@ -1639,8 +1722,10 @@ static int batch_common(fm_ctx* ctx, int32_t n, const fm_bank* const* q, const f
             tm.pairs += q[k]->n * t[k]->n;
             tm.bytes += bank_bytes(q[k]) + bank_bytes(t[k]);
         }
+        const unsigned* cut[kRRBatchMax];
+        if ((rc = enqueue_ratio_cut(ctx, g, q + i, tau, cut)) != FM_OK) { ctx->timer_pool.push_back(tm); return rc; }
         HIP_TRY(ctx, hipEventRecord(tm.k0, ctx->stream));
-        HIP_TRY(ctx, launch_rowreduce_batch(g, cols, red, pls, part, bnd, ctx->stream));
+        HIP_TRY(ctx, launch_rowreduce_batch(g, cols, red, pls, part, bnd, ctx->stream, false, cut));
         HIP_TRY(ctx, hipEventRecord(tm.k1, ctx->stream));
         for (int j = 0; j < g; ++j) {
             const int k = i + j;

@@ -36,6 +36,8 @@ struct fm_ctx {
     // configuration: fm_ctx_set_option (the FM_* environment variables seed it at creation)
     fm::Tuning tune;
     int* d_counters = nullptr;   // device words of the fp16 filter (layout: fm_internal.h, launch_filter)
+    unsigned* d_cut = nullptr;   // [kRRBatchMax] D* of the ratio test per pair of the next K1 launch (ratio_cut.h; on `stream`
+                                 // only: ratio_cut_kernel writes it in front of the K1 that reads it); null: no cut
     int64_t filter_launches = 0;
     unsigned long long* h_scratch = nullptr;   // pinned host words the kernels can write (counts)
     // page-locked staging for results that go to pageable caller memory (d2h below)
@@ -145,6 +147,10 @@ void fill_round_f32(fm::RoundF32* r, const fm::Bank& q, const fm::Bank& t);
 // K10: radiusMatch (radius.hip); arguments checked by fm_radius_match (api_match.hip)
 int radius_match(fm_ctx* ctx, const fm::Bank& q, const fm::Bank& t, const float* radius, float radius_all, int64_t cap,
                  int64_t* offsets, int32_t* idx, float* dist, int64_t* n_total);
+// A bank's self distances, and its largest one (Bank::sdmax), in place: the array is allocated once, the word behind it.
+int bank_selfdist_alloc(fm_ctx* ctx, fm_bank* b);
+// Bank::sdmax of the rows [0, n) of b->selfdist, enqueued on `stream` (sets sdmax_rows).
+int enqueue_selfdist_max(fm_ctx* ctx, fm_bank* b, hipStream_t stream);
 int round_xcheck_dense(fm_ctx* ctx, const fm::Bank& q, const int32_t* d_rows, int64_t nq, const fm::Bank& t, int64_t t0, int64_t nt,
                        unsigned long long* d_qbest);
 }

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "../../include/fastmatch_hip.h"
+#include "ratio_cut.h"
 
 namespace fm {
 
@@ -47,6 +48,11 @@ struct Bank {
     int      kscale = 0;       // largest scaled magnitude lies in [2^13, 2^14)
     bool     filt_ok = false;  // every value is finite
     double*  selfdist = nullptr;
+    // the largest self distance, as the bits of the double (the maximum of the bit patterns: a pattern at or above +inf's --
+    // inf, NaN, a sign bit -- means no ratio cut, ratio_cut.h); a device word behind selfdist[cap], valid for the rows
+    // [0, sdmax_rows) of the array (fm_bank_set_selfdist, fm_self_dist_batch; -1: none)
+    unsigned long long* sdmax = nullptr;
+    int64_t  sdmax_rows = -1;
     // FM_BANK_BIN (K11, hamming.hip): dim = bytes per row (1 .. 64), ksteps = ceil(dim / 16) MFMA K steps of 128 bits
     int      ksteps = 0;
     uint8_t* rowsb  = nullptr; // [n_pad][16 ksteps] packed rows, zero padded
@@ -119,8 +125,11 @@ struct RowReducePlan {
     size_t bound_bytes() const { return (size_t)ncols_alloc * 4 * 2; }   // (top-2 launches keep two arrays)
 };
 RowReducePlan plan_rowreduce(int64_t ncols_pad, int64_t nred_pad, const Tuning& tn);
+// cut (top-1 only): device word D* of the ratio test (ratio_cut.h); candidates at d2 >= D* may be dropped (their rows may
+// then keep the empty key).  Only the accepted-only calls pass one: every reported row there passes the test.
 hipError_t launch_rowreduce(const Bank& cols, const Bank& red, int ktop, const RowReducePlan& plan,
-                            unsigned long long* partial, int* bound, bool use_glds, hipStream_t stream);
+                            unsigned long long* partial, int* bound, bool use_glds, hipStream_t stream,
+                            const unsigned* cut = nullptr);
 int rowreduce_grid(const RowReducePlan& plan);      // workgroups per bank pair (padded under orders 1 and 2)
 // fm_self_dist: top-1 of every row over the OTHER rows of its own bank (masked diagonal)
 RowReducePlan plan_rowreduce_self(int64_t n_pad, const Tuning& tn);
@@ -213,7 +222,8 @@ hipError_t launch_rounds_f32(const RoundF32& rf, const double* q_selfdist, const
 // ---- K7: device-resident expansion loop (expand.hip) ------------------------------------
 constexpr int kRRBatchMax = 16;           // bank pairs per batched row-reduce launch
 hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
-                                  unsigned long long* const* partial, int* const* bound, hipStream_t stream, bool self = false);
+                                  unsigned long long* const* partial, int* const* bound, hipStream_t stream, bool self = false,
+                                  const unsigned* const* cut = nullptr);      // (cut[i]: as launch_rowreduce's, per pair; not for self)
 hipError_t launch_expand(const void* d_pairs, int n_pairs, bool f32, int tier, hipStream_t stream);   // all pairs of one kind / capacity tier (expand.hip)
 int expand_cand_cap();
 int expand_cand_cap_big();

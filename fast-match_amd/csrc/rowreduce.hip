@@ -76,6 +76,7 @@ struct RRParams {
 #endif
     int            tri_first;     // TRI kernels: workgroup bid of a launch is entry tri_first + bid of the bank's workgroup list
     int            tri_S;         // ... whose entries follow from (nchunks, nstages, tri_S) by arithmetic: tri_entry below
+    const unsigned* cut;          // top-1 sweeps of the accepted-only calls: device word D* of the ratio test (ratio_cut.h), null = none
 };
 
 // (tri_entry -- entry e of the triangular sweep's workgroup list -- is in tile_ops.h: filter_f16.hip's float32 form shares it)
@@ -394,6 +395,22 @@ __device__ __forceinline__ void rowreduce_body(const RRParams& p, const int bid,
         gnext[j] = (p.bound && n < p.ncols_alloc)
             ? __hip_atomic_load(bound_thr + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : INT32_MIN;
     }
+    // Ratio cut (the accepted-only calls, ratio_cut.h): no candidate at d2 >= D* can be accepted, so a row's exact path may
+    // start at hi >= |c|^2 + 2 - D* (d2 <= D* - 1) -- acc >= floor of half that, the floor convention of the published bounds.
+    // A row that never reaches it keeps the empty key, which the election skips.  (Loaded here, beside the bound loads, and
+    // folded in behind the prefetch: the wait for these loads is then one the first hand-over makes anyway.)
+    int seed[NC];
+    if constexpr (KTOP == 1 && !SELF && !TRI) {
+        if (p.cut) {
+            const long long dcut = *p.cut;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                const int n = cb + 16 * j + c16;
+                const long long h = ((long long)(n < p.ncols_pad ? p.col_norm[n] : 0) + 2 - dcut) >> 1;
+                seed[j] = h < (long long)INT32_MIN ? INT32_MIN : (int)h;
+            }
+        }
+    }
     // TRI: the refreshed bounds travel by LDS-DMA into kTriGn (no loop-carried register has a load in flight: the compiler
     // moved such registers between the copies of the unrolled stage loop in front of the wait, tests/test_isa_hazards.py);
     // the words read here apply at once
@@ -421,6 +438,13 @@ __device__ __forceinline__ void rowreduce_body(const RRParams& p, const int bid,
         if (st0 < st1) issue_stage<GLDS, NW>(p, st0, smem, wave, lane);
         if constexpr (NBUF == 3) {
             if (st0 + 1 < st1) issue_stage<GLDS, NW>(p, st0 + 1, smem + kStride, wave, lane);
+        }
+    }
+
+    if constexpr (KTOP == 1 && !SELF && !TRI) {
+        if (p.cut) {
+#pragma unroll
+            for (int j = 0; j < NC; ++j) thr[j] = max(thr[j], seed[j]);
         }
     }
 
@@ -1012,6 +1036,7 @@ static void fill_params(RRParams& p, const Bank& cols, const Bank& red, const Ro
     p.partial = partial;
     p.order = plan.order;
     p.bound_mask = plan.bound_every > 1 ? plan.bound_every - 1 : 0;
+    p.cut = nullptr;
 }
 
 int rowreduce_grid(const RowReducePlan& plan) { return blocks_per_pair(plan.nchunks, plan.nsplit, plan.order); }
@@ -1029,7 +1054,8 @@ RowReducePlan plan_rowreduce_self(int64_t n_pad, const Tuning& tn)
 // Top-1 row-reduce of n <= kRRBatchMax bank pairs in one launch, pair i under plans[i] (any sizes; every plan in the shape the
 // batched kernel is built for: 4 blocks per wave, 8 waves).
 hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
-                                  unsigned long long* const* partial, int* const* bound, hipStream_t stream, bool self)
+                                  unsigned long long* const* partial, int* const* bound, hipStream_t stream, bool self,
+                                  const unsigned* const* cut)
 {
     if (n < 1 || n > kRRBatchMax) return hipErrorInvalidValue;
     RRBatch b;
@@ -1037,6 +1063,7 @@ hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* co
     for (int i = 0; i < n; ++i) {
         if (plans[i].nb != 4 || plans[i].nw != 8) return hipErrorInvalidValue;
         fill_params(b.p[i], *cols[i], *red[i], plans[i], partial[i], bound[i]);
+        if (cut && !self) b.p[i].cut = cut[i];
         b.first_block[i] = (int)total;
         total += rowreduce_grid(plans[i]);
     }
@@ -1063,10 +1090,11 @@ hipError_t launch_rowreduce_self(const Bank& bank, const RowReducePlan& plan, un
 }
 
 hipError_t launch_rowreduce(const Bank& cols, const Bank& red, int ktop, const RowReducePlan& plan,
-                            unsigned long long* partial, int* bound, bool use_glds, hipStream_t stream)
+                            unsigned long long* partial, int* bound, bool use_glds, hipStream_t stream, const unsigned* cut)
 {
     RRParams p;
     fill_params(p, cols, red, plan, partial, bound);
+    if (ktop == 1) p.cut = cut;
     const int grid = rowreduce_grid(plan);
     return ktop == 1 ? launch_k<1>(p, grid, plan.nb, plan.nw, use_glds, plan.nbuf, plan.prio != 0, stream)
                      : launch_k<2>(p, grid, plan.nb, plan.nw, use_glds, plan.nbuf, plan.prio != 0, stream);
