@@ -43,3 +43,15 @@ taus = [0.5, 0.6, 0.7, 0.8, 0.9]
 per_tau = fastmatch.match(query_cache, target_img, {})(taus)
 print("matches per threshold:", dict(zip(taus, (len(m) for m in per_tau))))
 assert [m[0] for m in per_tau[2]] == [m[0] for m in matches]
+
+# Retrieval: which image of a database does a query match?  cv2.BFMatcher's train collection (add / train) on the device:
+# one call searches all images, and the per-image ratio test votes for the image that holds the query's object.
+from fastmatch_amd import matchutil                                # noqa: E402
+rng = np.random.default_rng(3)
+database = [synth.synth_sift(1500, rng) for _ in range(20)]       # twenty unrelated images ...
+database[13][:400] = q["descriptors"][:400]                        # ... one of them sees a part of the query image
+matcher = matchutil.BFMatcher(matchutil.NORM_L2)
+matcher.add(database)
+votes = matcher.votes(q["descriptors"], 0.8, mode=1)               # query rows passing Lowe's test inside each image
+print("retrieval: image %d wins with %d votes (runner-up %d)" % (votes.argmax(), votes.max(), np.sort(votes)[-2]))
+assert votes.argmax() == 13 and matcher.match(q["descriptors"][:400])[0].imgIdx == 13

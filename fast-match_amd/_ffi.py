@@ -39,7 +39,7 @@ class fm_stats_ex(ctypes.Structure):
                 ("bytes_moved", ctypes.c_int64)]
 
 
-FM_ABI_VERSION = 10         # include/fastmatch_hip.h: the revision this binding was written against
+FM_ABI_VERSION = 11         # include/fastmatch_hip.h: the revision this binding was written against
 
 
 class fm_expand_desc(ctypes.Structure):
@@ -137,6 +137,20 @@ SYMBOLS = {
     "fm_comm_destroy": (_INT, [_P]),
     "fm_gather_matches": (_INT, [_P, _P, _P, _I64, _P, _P, _INT]),
     "fm_gather_matches_counted": (_INT, [_P, _P, _P, _I64, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_collection_create": (_INT, [_P, ctypes.POINTER(_P)]),
+    "fm_collection_destroy": (_INT, [_P, _P]),
+    "fm_collection_clear": (_INT, [_P, _P]),
+    "fm_collection_add_u8": (_INT, [_P, _P, _P, _I64, _INT, ctypes.POINTER(_I32)]),
+    "fm_collection_add_f32": (_INT, [_P, _P, _P, _I64, _INT, ctypes.POINTER(_I32)]),
+    "fm_collection_add_bin": (_INT, [_P, _P, _P, _I64, _INT, ctypes.POINTER(_I32)]),
+    "fm_collection_train": (_INT, [_P, _P]),
+    "fm_collection_info": (_INT, [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I64), ctypes.POINTER(_INT), ctypes.POINTER(_INT)]),
+    "fm_collection_image_rows": (_INT, [_P, _P]),
+    "fm_collection_locate": (_INT, [_P, _I32, _P, _I64, _P, _P]),
+    "fm_collection_knn": (_INT, [_P, _P, _P, _I32, _P, _P, _P]),
+    "fm_collection_knn2_ratio": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_collection_knn2_each": (_INT, [_P, _P, _P, _P, _P]),
+    "fm_collection_votes": (_INT, [_P, _P, _P, ctypes.c_double, _I32, _P]),
 }
 
 _lib = None
@@ -310,6 +324,130 @@ class Bank(object):
     def close(self):
         if self.handle is not None and self.ctx.handle is not None:
             self.ctx.lib.fm_bank_destroy(self.ctx.handle, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def collection_locate(first_row, g):
+    """``fm_collection_locate`` (host code, no context): (image int32[m], row int64[m]) of the logical global rows ``g`` of a
+    collection whose image i starts at ``first_row[i]`` (``first_row[-1]`` = all rows); -1 / -1 for -1 or a row outside."""
+    fr = np.ascontiguousarray(first_row, dtype=np.int64).reshape(-1)
+    gg = np.ascontiguousarray(g, dtype=np.int64).reshape(-1)
+    if fr.shape[0] < 1:
+        raise ValueError("first_row needs n_images + 1 entries")
+    img = np.empty(gg.shape[0], np.int32)
+    loc = np.empty(gg.shape[0], np.int64)
+    lib = load_library()
+    rc = lib.fm_collection_locate(_ptr(fr), fr.shape[0] - 1, _ptr(gg), gg.shape[0], _ptr(img), _ptr(loc))
+    if rc != 0:
+        msg = lib.fm_last_error(None)
+        raise FastMatchHipError("fm_collection_locate failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+    return img, loc
+
+
+class Collection(object):
+    """Train collection (fm_collection): an ordered list of images resident on the device in one set of arrays --
+    ``cv2.BFMatcher.add`` / ``train`` / ``clear``.  A context manager; closes with its context."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.handle = None
+        h = _P()
+        ctx._check(ctx.lib.fm_collection_create(ctx.handle, ctypes.byref(h)))
+        self.handle = h
+        ctx._children.add(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def add(self, rows):
+        """Append one image ([n, dim] uint8, or float32 with integer values in 0 .. 255; n may be 0); returns its index."""
+        a = np.asarray(rows)
+        if a.ndim != 2:
+            raise ValueError("an image's descriptors must be 2-D [n, dim]")
+        i = _I32(-1)
+        if a.dtype == np.uint8:
+            a = np.ascontiguousarray(a)
+            fn = self.ctx.lib.fm_collection_add_u8
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            fn = self.ctx.lib.fm_collection_add_f32
+        self.ctx._check(fn(self.ctx.handle, self.handle, _ptr(a) if a.shape[0] else None, a.shape[0], a.shape[1], ctypes.byref(i)))
+        return int(i.value)
+
+    def add_binary(self, rows):
+        a = np.ascontiguousarray(rows, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError("an image's descriptors must be 2-D [n, bytes]")
+        i = _I32(-1)
+        self.ctx._check(self.ctx.lib.fm_collection_add_bin(self.ctx.handle, self.handle, _ptr(a) if a.shape[0] else None,
+                                                           a.shape[0], a.shape[1], ctypes.byref(i)))
+        return int(i.value)
+
+    def train(self):
+        self.ctx._check(self.ctx.lib.fm_collection_train(self.ctx.handle, self.handle))
+
+    def clear(self):
+        self.ctx._check(self.ctx.lib.fm_collection_clear(self.ctx.handle, self.handle))
+
+    def info(self):
+        """(n_images, n_rows_total, dim, kind)"""
+        ni, nr, dim, kind = _I32(), _I64(), _INT(), _INT()
+        self.ctx._check(self.ctx.lib.fm_collection_info(self.handle, ctypes.byref(ni), ctypes.byref(nr), ctypes.byref(dim), ctypes.byref(kind)))
+        return int(ni.value), int(nr.value), int(dim.value), int(kind.value)
+
+    def image_rows(self):
+        rows = np.zeros(self.info()[0], np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_image_rows(self.handle, _ptr(rows) if rows.shape[0] else None))
+        return rows
+
+    def knn(self, q, k):
+        """``fm_collection_knn``: (img, idx, dist) [nq, k] against the stacked rows of all images."""
+        k = int(k)
+        img = np.empty((q.n, max(k, 0)), np.int32)
+        idx = np.empty((q.n, max(k, 0)), np.int32)
+        dist = np.empty((q.n, max(k, 0)), np.float32)
+        self.ctx._check(self.ctx.lib.fm_collection_knn(self.ctx.handle, self.handle, q.handle, k, _ptr(img), _ptr(idx), _ptr(dist)))
+        return img, idx, dist
+
+    def knn2_ratio(self, q, tau):
+        """``fm_collection_knn2_ratio``: (qidx, img, tidx, dist, ratio) of the accepted matches, ascending query index."""
+        cap = q.n
+        qidx, img, tidx = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.int32)
+        dist, ratio = np.empty(cap, np.float32), np.empty(cap, np.float64)
+        n = _I64(0)
+        self.ctx._check(self.ctx.lib.fm_collection_knn2_ratio(self.ctx.handle, self.handle, q.handle, float(tau), cap, _ptr(qidx),
+                                                              _ptr(img), _ptr(tidx), _ptr(dist), _ptr(ratio), ctypes.byref(n)))
+        m = min(int(n.value), cap)
+        return qidx[:m], img[:m], tidx[:m], dist[:m], ratio[:m]
+
+    def knn2_each(self, q):
+        """``fm_collection_knn2_each``: (idx, dist) [n_images, nq, 2], slot by slot ``Context.knn2(q, image_i)``."""
+        ni = self.info()[0]
+        idx = np.empty((ni, q.n, 2), np.int32)
+        dist = np.empty((ni, q.n, 2), np.float32)
+        self.ctx._check(self.ctx.lib.fm_collection_knn2_each(self.ctx.handle, self.handle, q.handle, _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def votes(self, q, tau, mode=0):
+        """``fm_collection_votes``: int64[n_images] query rows passing the ratio test per image (mode 0: stacked lists, 1: per image)."""
+        v = np.zeros(self.info()[0], np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_votes(self.ctx.handle, self.handle, q.handle, float(tau), int(mode),
+                                                         _ptr(v) if v.shape[0] else None))
+        return v
+
+    def close(self):
+        if self.handle is not None and self.ctx.handle is not None:
+            self.ctx.lib.fm_collection_destroy(self.ctx.handle, self.handle)
         self.handle = None
 
     def __del__(self):
@@ -585,6 +723,10 @@ class Context(object):
         h = _P()
         self._check(self.lib.fm_bank_create_f32_cap(self.handle, int(dim), int(capacity), scale_like.handle, ctypes.byref(h)))
         return Bank(self, h, 0, int(dim), FM_BANK_F32)
+
+    def collection(self):
+        """An empty train collection (``Collection``: add / train / clear, knn / knn2_each / votes against all images)."""
+        return Collection(self)
 
     # -- operators -----------------------------------------------------------------------
     def knn2(self, q, t):

@@ -1,0 +1,1042 @@
+// C-ABI of libfastmatch_hip.so (include/fastmatch_hip.h), part 2b: train collections -- cv2.BFMatcher.add / train / clear and
+// match / knnMatch against all added images (DMatch.imgIdx).
+//
+// Layout.  One integer-route bank (`stack`: rows8 / norm / aux) holds every image; a non-empty image starts on a 128-row
+// stage and its last stage ends in padding rows prepared like any bank's tail (cinit = kPadCinit: the matrix-core sweeps
+// never prefer them to a real row), so
+//   * rows [phys[i], phys[i] + pad128(rows[i])) ARE a bank: the reduced operand of the top-2 sweep for image i alone
+//     (fm_collection_knn2_each), and
+//   * the used part of the allocation is one bank of n = n_pad = `used` rows for the stacked sweep (fm_collection_knn,
+//     _knn2_ratio, _votes mode 0).
+// The kernels that read rows and norms instead of the aux words (K9's vector-ALU lists, the float32-root repair) see a
+// padding row through its norm: a collection writes 2^26 there (a plain bank: 0), which puts the row at d^2 >= 2^26,
+// beyond every real pair (<= 128 * 255^2), with room left in int32.  A padding row can therefore enter a list only
+// where fewer than k real rows exist, always behind them, and the lookup (physical row -> image, row) turns it into
+// -1 / -1 / +inf.  Lookup tables on the device, per 128-row stage: its image and its number of real rows; per image: its
+// first physical row.  Physical order = logical (image, row) order, so keys (distance, physical row) order ties the way
+// OpenCV's per-image insertion does: the earlier image, then the earlier row.
+#include "ctx_internal.h"
+
+#include <algorithm>
+
+using namespace fm;
+
+// The three kinds.  Integer route: as above.  Float32 route (the first float32 image with a value that is not an integer in
+// 0 .. 255 REBUILDS a collection of integer-valued float32 images on the float32 route, on the device, from the int8 rows:
+// nothing is uploaded again): rowsf / rowsh / normf / auxf, the fp16 planes of ALL images on the ONE power-of-two scale
+// chosen at the rebuild (an image that leaves fp16's range under it switches the filter off for the collection: K5
+// alone, same results); a padding row is a padding row of the fp16 planes (auxf = -3.4e38) and holds kCollPadF32 in every
+// float32 dimension, so the exact chain -- K8's rescoring and rescan, K5, K9 -- puts it at ~1.1e19, behind every real
+// row: masked by value, no kernel changed.  Binary: rowsb / rows4; an all-zero FP4 row is at W / 2 from everything, so K11
+// masks by INDEX: its sweep and its vector-ALU kernel take the per-stage real-row table (stage_real).
+constexpr int kCollPadNorm = 1 << 26;
+constexpr float kCollPadF32 = 1.0e18f;           // 128 * (1e18)^2 = 1.28e38 stays finite in float32
+constexpr int kCollFixGrid = 1024;
+
+struct fm_collection {
+    fm_ctx* ctx = nullptr;
+    fm::Bank stack;                       // kind = the collection's; n = n_pad = used rows, cap_pad = allocated rows
+    int dim = 0;                          // 0: no non-empty image yet
+    int src = 0;                          // 1: images came as uint8, 2: as float32, 3: as binary rows (0: none yet)
+    int64_t used = 0, total = 0;          // physical rows in use (a multiple of 128), real rows
+    std::vector<int64_t> rows, phys;      // per image
+    std::vector<int32_t> usq;             // per image: largest |row|^2 (sqrt_tie_possible)
+    int32_t* d_tab = nullptr;             // stage image [nstages] | stage real rows [nstages] | first row [n_images]
+    size_t tab_bytes = 0;
+    bool dirty = true;
+    int64_t nstages() const { return used / kStageRows; }
+    const int32_t* st_img() const { return d_tab; }
+    const int32_t* st_real() const { return d_tab + nstages(); }
+    const int32_t* img_phys() const { return d_tab + 2 * nstages(); }
+};
+
+// ---------------------------------------------------------------------------------------
+// kernels
+// ---------------------------------------------------------------------------------------
+__global__ void coll_pad_norm_kernel(int32_t* __restrict__ norm, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) norm[i] = kCollPadNorm;
+}
+
+struct CollTab { const int32_t* st_img; const int32_t* st_real; const int32_t* img_phys; };
+
+// physical row of the stack -> (image, row inside it); false for a padding row
+__device__ __forceinline__ bool coll_lookup(const CollTab& t, unsigned p, int32_t& img, int32_t& local)
+{
+    const unsigned s = p >> 7;
+    if ((int)(p & 127u) >= t.st_real[s]) return false;
+    img = t.st_img[s];
+    local = (int32_t)(p - (unsigned)t.img_phys[img]);
+    return true;
+}
+
+__device__ __forceinline__ bool coll_real(const CollTab& t, unsigned long long key)
+{
+    return key != ~0ull && (int)((unsigned)key & 127u) < t.st_real[(unsigned)key >> 7];
+}
+
+// One (query bank, reduced bank) slot of a merge launch: the stacked sweep (tab set, one slot) or one image of
+// fm_collection_knn2_each (tab null: rows are the image's own).
+struct CollSlot {
+    const unsigned long long* partial;    // null: the image is empty, every entry -1 / +inf
+    int nsplit, ncols_alloc;
+    unsigned* fix;                        // rows for the float32-root repair (fix[0] = count, rows from fix[4]) or null
+    int64_t out;                          // first output entry of the slot (in units of 2 entries per query row)
+};
+struct CollMerge { CollSlot s[kRRBatchMax]; };
+
+// Top-2 merge of K2's split partials (keys (d2 << 32) | row) as knn2_merge_kernel, with the row lookup fused in;
+// blockIdx.y = slot.  img may be null (per-image lists).
+__global__ __launch_bounds__(256)
+void coll_merge2_kernel(CollMerge m, CollTab tab, int64_t nq, int32_t* __restrict__ img, int32_t* __restrict__ idx,
+                        float* __restrict__ dist, int f32)
+{
+    const CollSlot& sl = m.s[blockIdx.y];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    unsigned long long b0 = ~0ull, b1 = ~0ull;
+    for (int s = 0; s < sl.nsplit; ++s) {
+        const unsigned long long* p = sl.partial + ((size_t)s * sl.ncols_alloc + i) * 2;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            unsigned long long v = p[k];
+            if (tab.st_img && !coll_real(tab, v)) v = ~0ull;
+            if (v < b0) { b1 = b0; b0 = v; }
+            else if (v < b1) { b1 = v; }
+        }
+    }
+    const int64_t o = 2 * (sl.out + i);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const unsigned long long b = k ? b1 : b0;
+        int32_t im = -1, lo = -1;
+        if (b != ~0ull) {
+            if (tab.st_img) (void)coll_lookup(tab, (unsigned)b, im, lo);
+            else { im = 0; lo = (int32_t)(unsigned)b; }
+        }
+        if (img) img[o + k] = im;
+        idx[o + k] = lo;
+        const unsigned hi = (unsigned)(b >> 32);         // integer route: d2; float32 route and binary: the distance's bits
+        dist[o + k] = (b == ~0ull) ? INFINITY : (f32 ? __uint_as_float(hi) : sqrtf((float)hi));
+    }
+    // (the float32 order can differ from the d2 order: see knn2_merge_kernel)
+    if (sl.fix && b1 != ~0ull && (unsigned)(b1 >> 32) >= kSqrtTieMin) {
+        const unsigned e0 = (unsigned)(b0 >> 32), e1 = (unsigned)(b1 >> 32);
+        const bool paired1 = sqrt_ties_up(e1) || sqrt_ties_up(e1 - 1u);
+        const bool paired0 = e0 >= kSqrtTieMin && (sqrt_ties_up(e0) || sqrt_ties_up(e0 - 1u));
+        if (paired0 || paired1) sl.fix[4 + atomicAdd(sl.fix, 1u)] = (unsigned)i;
+    }
+}
+
+// sqrt_fix_kernel<2> (api_match.hip) for a collection: exact rescan of the listed query rows over the reduced rows
+// [0, nred) in OpenCV's (float32 root, row) order; padding rows sit at d2 >= 2^26 behind every real row and are
+// dropped by the lookup.  out = first output entry of the slot, as CollSlot::out.
+__global__ __launch_bounds__(256)
+void coll_sqrt_fix_kernel(const unsigned* __restrict__ fix, const int8_t* __restrict__ col_rows,
+                          const int32_t* __restrict__ col_norm, const int8_t* __restrict__ red_rows,
+                          const int32_t* __restrict__ red_norm, int nred, CollTab tab, int64_t out,
+                          int32_t* __restrict__ img, int32_t* __restrict__ idx, float* __restrict__ dist)
+{
+    __shared__ unsigned long long best[2];
+    const int tid = threadIdx.x;
+    const unsigned n = fix[0];
+    for (unsigned e = blockIdx.x; e < n; e += gridDim.x) {
+        const unsigned c = fix[4 + e];
+        if (tid == 0) { best[0] = ~0ull; best[1] = ~0ull; }
+        __syncthreads();
+        v4i cr[kDim / 16];
+#pragma unroll
+        for (int w = 0; w < kDim / 16; ++w) cr[w] = *(const v4i*)(col_rows + (size_t)c * kDim + 16 * w);
+        const int cn = col_norm[c];
+        unsigned long long k0 = ~0ull, k1 = ~0ull;
+        for (int m = tid; m < nred; m += 256) {
+            int dot = 0;
+#pragma unroll
+            for (int w = 0; w < kDim / 16; ++w) {
+                const v4i y = *(const v4i*)(red_rows + (size_t)m * kDim + 16 * w);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) dot = __builtin_amdgcn_sdot4(cr[w][u], y[u], dot, false);
+            }
+            const unsigned d2 = (unsigned)(cn + red_norm[m] - 2 * dot);
+            const unsigned long long key = ((unsigned long long)sqrt_bits(d2) << 32) | (unsigned)m;
+            if (key < k0) { k1 = k0; k0 = key; }
+            else if (key < k1) k1 = key;
+        }
+        if (k0 != ~0ull) atomicMin(&best[0], k0);
+        __syncthreads();
+        const unsigned long long g0 = best[0];
+        const unsigned long long mine = (k0 == g0) ? k1 : k0;
+        if (mine != ~0ull) atomicMin(&best[1], mine);
+        __syncthreads();
+        if (tid == 0) {
+            const int64_t o = 2 * (out + (int64_t)c);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const unsigned long long g = best[k];
+                int32_t im = -1, lo = -1;
+                bool has = g != ~0ull;
+                if (has) {
+                    if (tab.st_img) has = coll_lookup(tab, (unsigned)g, im, lo);
+                    else { im = 0; lo = (int32_t)(unsigned)g; }
+                }
+                if (img) img[o + k] = has ? im : -1;
+                idx[o + k] = has ? lo : -1;
+                dist[o + k] = has ? __uint_as_float((unsigned)(g >> 32)) : INFINITY;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// k = 3 .. 8: K9 wrote physical rows; one thread per entry looks its (image, row) up.  A padding row (fewer than k real
+// rows in the collection; it sorts behind them) becomes -1 / -1 / +inf.
+__global__ void coll_translate_kernel(CollTab tab, int64_t n, int32_t* __restrict__ img, int32_t* __restrict__ idx,
+                                      float* __restrict__ dist)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t p = idx[i];
+    int32_t im = -1, lo = -1;
+    const bool has = p >= 0 && coll_lookup(tab, (unsigned)p, im, lo);
+    img[i] = has ? im : -1;
+    idx[i] = has ? lo : -1;
+    if (!has) dist[i] = INFINITY;
+}
+
+// first column of [n][2] lists
+__global__ void coll_col0_kernel(const int32_t* __restrict__ a2, const float* __restrict__ d2, const int32_t* __restrict__ b2,
+                                 int64_t n, int32_t* __restrict__ a, float* __restrict__ d, int32_t* __restrict__ b)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    a[i] = a2[2 * i];  d[i] = d2[2 * i];  b[i] = b2[2 * i];
+}
+
+// Rebuild on the float32 route: an image's int8 rows (value XOR 0x80 = the uint8 value) as float32, dims from `dim` on 0.
+__global__ void coll_i8_to_f32_kernel(const int8_t* __restrict__ rows8, int64_t n, int dim, float* __restrict__ rowsf)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * kDim) return;
+    const int k = (int)(i % kDim);
+    rowsf[i] = k < dim ? (float)((int)rows8[i] + 128) : 0.f;
+}
+
+__global__ void coll_fill_f32_kernel(float* __restrict__ p, int64_t n, float v)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// Ordered compaction of the accepted rows (compact_kernel of api_match.hip with the image column): block b sums the
+// counts of the blocks before it, every accepted row writes itself at offset + rank.  Deterministic.
+__global__ __launch_bounds__(256)
+void coll_compact_kernel(const int32_t* __restrict__ img2, const int32_t* __restrict__ tidx, const float* __restrict__ dist,
+                         const double* __restrict__ ratio, const uint8_t* __restrict__ pass, const int* __restrict__ block_counts,
+                         int64_t nq, int64_t cap, int32_t* __restrict__ o_q, int32_t* __restrict__ o_m, int32_t* __restrict__ o_t,
+                         float* __restrict__ o_d, double* __restrict__ o_r, unsigned long long* __restrict__ npass)
+{
+    __shared__ int red[256];
+    __shared__ int wave_cnt[4];
+    const int tid = threadIdx.x;
+    int s = 0;
+    for (int b = tid; b < (int)blockIdx.x; b += 256) s += block_counts[b];
+    red[tid] = s;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+        if (tid < d) red[tid] += red[tid + d];
+        __syncthreads();
+    }
+    const int64_t base = red[0];
+    const int64_t q = (int64_t)blockIdx.x * 256 + tid;
+    const bool p = q < nq && pass[q];
+    const unsigned long long m = __ballot(p);
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int wb = 0;
+    for (int w = 0; w < wave; ++w) wb += wave_cnt[w];
+    if (blockIdx.x == gridDim.x - 1 && tid == 0)
+        *npass = (unsigned long long)(base + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3]);
+    if (p) {
+        const int64_t dst = base + wb + __popcll(m & ((1ull << lane) - 1ull));
+        if (dst < cap) { o_q[dst] = (int32_t)q; o_m[dst] = img2[2 * q]; o_t[dst] = tidx[q]; o_d[dst] = dist[q]; o_r[dst] = ratio[q]; }
+    }
+}
+
+// Votes: query rows whose 2-NN list passes d0 / d1 < tau (float64; a missing or zero second distance fails, as
+// lowe_kernel) counted per image.  Stacked lists (img != null, one list per query row): at the image of the first
+// neighbour; per-image lists [n_images][nq][2] (img null): at the list's own image, blockIdx.y.  Integer atomics: the
+// totals do not depend on the order of the additions.
+__global__ __launch_bounds__(256)
+void coll_votes_kernel(const int32_t* __restrict__ img, const int32_t* __restrict__ idx, const float* __restrict__ dist,
+                       int64_t nq, double tau, unsigned long long* __restrict__ votes)
+{
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t e = 2 * ((int64_t)blockIdx.y * nq + q);
+    bool p = false;
+    int im = (int)blockIdx.y;
+    if (q < nq) {
+        const double r = (idx[e + 1] >= 0) ? (double)dist[e] / (double)dist[e + 1] : NAN;
+        p = r < tau;
+        if (img) im = img[e];
+    }
+    if (img) {
+        if (p) atomicAdd(votes + im, 1ull);
+    } else {
+        const unsigned long long mk = __ballot(p);
+        if ((threadIdx.x & 63) == 0 && mk) atomicAdd(votes + im, (unsigned long long)__popcll(mk));
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// storage
+// ---------------------------------------------------------------------------------------
+// the device arrays of a kind and their bytes per row
+struct CollPlane { void** p; size_t row_bytes; };
+static int coll_planes(fm::Bank& b, CollPlane* pl)
+{
+    int n = 0;
+    if (b.kind == FM_BANK_F32) {
+        pl[n++] = {(void**)&b.rowsf, (size_t)kDim * 4}; pl[n++] = {(void**)&b.rowsh, (size_t)kDim * 2};
+        pl[n++] = {(void**)&b.normf, 4}; pl[n++] = {(void**)&b.auxf, 4};
+    } else if (b.kind == FM_BANK_BIN) {
+        pl[n++] = {(void**)&b.rowsb, (size_t)b.ksteps * 16}; pl[n++] = {(void**)&b.rows4, (size_t)b.ksteps * 64};
+    } else {
+        pl[n++] = {(void**)&b.rows8, (size_t)kDim}; pl[n++] = {(void**)&b.norm, 4};
+        pl[n++] = {(void**)&b.aux, (size_t)kAuxPerTile * 4 / kTileRows};
+    }
+    return n;
+}
+
+static void coll_free_planes(fm::Bank& b)
+{
+    void** all[] = {(void**)&b.rows8, (void**)&b.norm, (void**)&b.aux, (void**)&b.rowsf, (void**)&b.rowsh, (void**)&b.normf,
+                    (void**)&b.auxf, (void**)&b.rowsb, (void**)&b.rows4};
+    for (void** p : all) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    b.cap_pad = 0;
+}
+
+static void coll_free(fm_collection* c)
+{
+    coll_free_planes(c->stack);
+    if (c->d_tab) (void)hipFree(c->d_tab);
+    c->d_tab = nullptr;
+    c->tab_bytes = 0;
+}
+
+static void coll_reset(fm_collection* c)
+{
+    c->dim = 0; c->src = 0; c->used = 0; c->total = 0;
+    c->rows.clear(); c->phys.clear(); c->usq.clear();
+    c->stack.n = 0; c->stack.n_pad = 0; c->stack.usq_max = 0; c->stack.dim = 0;
+    c->stack.nm_max = 0.f; c->stack.kscale = 0; c->stack.filt_ok = false;
+    c->dirty = true;
+}
+
+// Arrays of `kind` for `cap` rows into *nb (its other fields untouched); the first `copy` rows of `from`'s arrays are copied on
+// the device when `from` is of the same kind.
+static int coll_alloc(fm_ctx* ctx, fm::Bank* nb, int64_t cap, fm::Bank* from, int64_t copy)
+{
+    CollPlane np[4], op[4];
+    const int n = coll_planes(*nb, np);
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n && e == hipSuccess; ++i) e = hipMalloc(np[i].p, (size_t)cap * np[i].row_bytes);
+    if (e == hipSuccess && from && copy > 0) {
+        coll_planes(*from, op);
+        for (int i = 0; i < n && e == hipSuccess; ++i)
+            e = hipMemcpyAsync(*np[i].p, *op[i].p, (size_t)copy * np[i].row_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        coll_free_planes(*nb);
+        return fail(ctx, e == hipErrorOutOfMemory ? FM_ENOMEM : FM_EDEVICE, std::string("fm_collection_add: growing the arrays: ") + hipGetErrorString(e));
+    }
+    nb->cap_pad = cap;
+    return FM_OK;
+}
+
+// room for `need` physical rows: new arrays of at least twice the size, the used part copied on the device
+static int coll_reserve(fm_ctx* ctx, fm_collection* c, int64_t need)
+{
+    if (need <= c->stack.cap_pad) return FM_OK;
+    int64_t cap = std::max<int64_t>(need, 2 * c->stack.cap_pad);
+    cap = std::max<int64_t>(cap, 32 * kStageRows);
+    if (cap > (int64_t)INT32_MAX - 2 * kStageRows) cap = need;
+    if (cap > (int64_t)INT32_MAX - 2 * kStageRows) return fail(ctx, FM_EUNSUPPORTED, "fm_collection_add: the collection would exceed 2^31 rows");
+    fm::Bank nb = c->stack;
+    nb.rows8 = nullptr; nb.norm = nullptr; nb.aux = nullptr; nb.rowsf = nullptr; nb.rowsh = nullptr; nb.normf = nullptr; nb.auxf = nullptr;
+    nb.rowsb = nullptr; nb.rows4 = nullptr;
+    int rc = coll_alloc(ctx, &nb, cap, &c->stack, c->used);
+    if (rc != FM_OK) return rc;
+    coll_free_planes(c->stack);
+    c->stack = nb;
+    return FM_OK;
+}
+
+// The stack in another kind (it holds no rows, or the caller fills the new arrays): frees the old arrays.
+static int coll_set_kind(fm_ctx* ctx, fm_collection* c, int kind, int ksteps, int64_t cap)
+{
+    sync_all_streams(ctx);
+    coll_free_planes(c->stack);
+    c->stack.kind = kind;
+    c->stack.ksteps = ksteps;
+    return cap > 0 ? coll_alloc(ctx, &c->stack, cap, nullptr, 0) : FM_OK;
+}
+
+static int coll_check(fm_ctx* ctx, const fm_collection* c, const char* who)
+{
+    if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
+    if (!c) return fail(ctx, FM_EINVAL, std::string(who) + ": collection is NULL");
+    if (c->ctx != ctx) return fail(ctx, FM_EINVAL, std::string(who) + ": the collection belongs to another context");
+    return FM_OK;
+}
+
+extern "C" int fm_collection_create(fm_ctx* ctx, fm_collection** out)
+{
+    if (!ctx) return fail(nullptr, FM_EINVAL, "fm_collection_create: ctx is NULL");
+    if (!out) return fail(ctx, FM_EINVAL, "fm_collection_create: out pointer is NULL");
+    fm_collection* c = new (std::nothrow) fm_collection();
+    if (!c) return fail(ctx, FM_ENOMEM, "fm_collection_create: out of host memory");
+    c->ctx = ctx;
+    c->stack.kind = FM_BANK_I8;
+    *out = c;
+    return FM_OK;
+}
+
+extern "C" int fm_collection_destroy(fm_ctx* ctx, fm_collection* c)
+{
+    if (!c) return FM_OK;
+    int rc = coll_check(ctx, c, "fm_collection_destroy");
+    if (rc != FM_OK) return rc;
+    (void)hipSetDevice(ctx->device);
+    sync_all_streams(ctx);
+    coll_free(c);
+    delete c;
+    return FM_OK;
+}
+
+extern "C" int fm_collection_clear(fm_ctx* ctx, fm_collection* c)
+{
+    int rc = coll_check(ctx, c, "fm_collection_clear");
+    if (rc != FM_OK) return rc;
+    coll_reset(c);            // (the arrays stay: the next images re-use them)
+    return FM_OK;
+}
+
+// fp16 planes of an image's range and the padding rows' far value in rowsf (the planes are prepared while those rows are 0)
+static int coll_f32_finish(fm_ctx* ctx, fm_collection* c, int64_t off, int64_t n, int64_t n_pad)
+{
+    float nmx = 0.f;
+    int rc = bank_f32_range_planes(ctx, c->stack, off, n, n_pad, &nmx);
+    if (rc != FM_OK) return rc;
+    if (nmx > c->stack.nm_max) c->stack.nm_max = nmx;
+    if (n_pad > n) {
+        const int64_t cnt = (n_pad - n) * kDim;
+        hipLaunchKernelGGL(coll_fill_f32_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream,
+                           c->stack.rowsf + (size_t)(off + n) * kDim, cnt, kCollPadF32);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return FM_OK;
+}
+
+static int coll_kscale(float vmax)
+{
+    int ex = 0;
+    if (vmax > 0.f) (void)frexpf(vmax, &ex);
+    return vmax > 0.f ? 14 - ex : 0;
+}
+
+// An integer-route collection of float32 images becomes a float32-route one: float32 rows from the int8 rows, on the device.
+static int coll_rebuild_f32(fm_ctx* ctx, fm_collection* c, float vmax_new, int64_t need)
+{
+    fm::Bank old = c->stack;                       // (keeps the int8 arrays until the float32 ones are filled)
+    fm::Bank nb = fm::Bank();
+    nb.kind = FM_BANK_F32; nb.dim = c->dim; nb.n = nb.n_pad = c->used; nb.usq_max = old.usq_max;
+    int64_t cap = std::max<int64_t>(std::max<int64_t>(need, old.cap_pad), 32 * kStageRows);
+    int rc = coll_alloc(ctx, &nb, cap, nullptr, 0);
+    if (rc != FM_OK) return rc;
+    nb.kscale = coll_kscale(std::max(vmax_new, c->total > 0 ? 255.f : 0.f));
+    nb.filt_ok = true;
+    nb.nm_max = 0.f;
+    c->stack = nb;
+    for (size_t i = 0; i < c->rows.size(); ++i) {
+        const int64_t n = c->rows[i], off = c->phys[i];
+        if (n == 0) continue;
+        const int64_t n_pad = ((n + kStageRows - 1) / kStageRows) * kStageRows;
+        hipError_t e = hipMemsetAsync(nb.rowsf + (size_t)off * kDim, 0, (size_t)n_pad * kDim * 4, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(coll_i8_to_f32_kernel, dim3((unsigned)((n * kDim + 255) / 256)), dim3(256), 0, ctx->stream,
+                               (const int8_t*)(old.rows8 + (size_t)off * kDim), n, c->dim, nb.rowsf + (size_t)off * kDim);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) rc = coll_f32_finish(ctx, c, off, n, n_pad);
+        if (e != hipSuccess || rc != FM_OK) {
+            coll_free_planes(c->stack);
+            c->stack = old;
+            return rc != FM_OK ? rc : fail(ctx, FM_EDEVICE, std::string("fm_collection_add_f32: rebuild on the float32 route: ") + hipGetErrorString(e));
+        }
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    coll_free_planes(old);
+    return FM_OK;
+}
+
+// src: 1 uint8 rows, 2 float32 rows, 3 binary rows (dim = bytes)
+static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, int dim, int src, int32_t* img_idx, const char* who)
+{
+    int rc = coll_check(ctx, c, who);
+    if (rc != FM_OK) return rc;
+    if (n < 0 || dim < 1 || (n > 0 && !rows)) return fail(ctx, FM_EINVAL, std::string(who) + ": bad rows / n / width");
+    if (src == 3 ? dim > 64 : dim > kDim)
+        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + (src == 3 ? ": binary rows of more than 64 bytes are not supported" : ": dim > 128 is not supported"));
+    if (c->rows.size() >= (size_t)INT32_MAX) return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": too many images");
+    if (n > 0 && c->dim != 0) {
+        if (dim != c->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": the image's width differs from the collection's");
+        if (src != c->src) return fail(ctx, FM_EINVAL, std::string(who) + ": uint8, float32 and binary images do not mix in one collection (cv2 raises on the dtype)");
+    }
+    if (n > 0) {
+        const int64_t n_pad = ((n + kStageRows - 1) / kStageRows) * kStageRows;
+        const int64_t off = c->used;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        int usq = 0;
+        if (c->dim == 0) {                       // the first non-empty image fixes the kind's arrays
+            const int kind = src == 3 ? FM_BANK_BIN : FM_BANK_I8;
+            if (c->stack.kind != kind || (kind == FM_BANK_BIN && c->stack.ksteps != (dim + 15) / 16))
+                if ((rc = coll_set_kind(ctx, c, kind, kind == FM_BANK_BIN ? (dim + 15) / 16 : 0, 0)) != FM_OK) return rc;
+        }
+        if (c->stack.kind == FM_BANK_BIN) {
+            if ((rc = coll_reserve(ctx, c, off + n_pad)) != FM_OK) return rc;
+            const size_t src_bytes = (size_t)n * dim;
+            if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, src_bytes + 64)) != FM_OK) return rc;
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
+            fm::Bank v = c->stack;
+            v.n = n; v.n_pad = n_pad;
+            v.rowsb = c->stack.rowsb + (size_t)off * v.ksteps * 16;
+            v.rows4 = c->stack.rows4 + (size_t)off * v.ksteps * 64;
+            HIP_TRY(ctx, launch_hamming_prep((const uint8_t*)ctx->ws_in, n, dim, v, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (ws_in is free for the next upload)
+        } else {
+            bool as_f32 = c->stack.kind == FM_BANK_F32;
+            if (!as_f32) {
+                if ((rc = coll_reserve(ctx, c, off + n_pad)) != FM_OK) return rc;
+                int flags[2] = {0, 0};
+                if ((rc = bank_prep_range(ctx, rows, n, dim, src == 2, c->stack, off, n_pad, flags)) != FM_OK) return rc;
+                usq = flags[1];
+                if (src == 2 && flags[0]) as_f32 = true;          // (the range just written lies behind `used`: not part of anything)
+                else if (n_pad > n) {
+                    hipLaunchKernelGGL(coll_pad_norm_kernel, dim3((unsigned)((n_pad - n + 255) / 256)), dim3(256), 0, ctx->stream,
+                                       c->stack.norm + off + n, (int)(n_pad - n));
+                    HIP_TRY(ctx, hipGetLastError());              // (stream ordered before every sweep: no synchronisation)
+                }
+            }
+            if (as_f32) {
+                // rows first into the workspace's view of them: magnitude and finiteness decide the scale before anything changes
+                if (c->stack.kind != FM_BANK_F32) {
+                    if (c->dim == 0) c->dim = dim;                // (the rebuild converts rows of this width; no rows yet if this is the first)
+                    const float* f = (const float*)rows;
+                    float vmax = 0.f;
+                    for (int64_t i = 0; i < n * dim; ++i) { const float a = fabsf(f[i]); if (a <= 3.0e38f && a > vmax) vmax = a; }
+                    if ((rc = coll_rebuild_f32(ctx, c, vmax, off + n_pad)) != FM_OK) { if (c->total == 0) c->dim = 0; return rc; }
+                }
+                if ((rc = coll_reserve(ctx, c, off + n_pad)) != FM_OK) return rc;
+                float vmax = 0.f; bool finite = true;
+                if ((rc = bank_f32_range_rows(ctx, (const float*)rows, n, dim, c->stack, off, n_pad, &vmax, &finite)) != FM_OK) return rc;
+                if (!finite || !(ldexpf(vmax, c->stack.kscale) < 60000.f)) c->stack.filt_ok = false;   // K5 alone from here on (planes unused)
+                if ((rc = coll_f32_finish(ctx, c, off, n, n_pad)) != FM_OK) return rc;
+            }
+        }
+        if (c->dim == 0) c->dim = dim;
+        if (c->src == 0) c->src = src;
+        c->phys.push_back(off);
+        c->usq.push_back(usq);
+        c->used += n_pad;
+        c->total += n;
+        if (usq > c->stack.usq_max) c->stack.usq_max = usq;
+    } else {
+        c->phys.push_back(c->used);
+        c->usq.push_back(0);
+    }
+    c->rows.push_back(n);
+    c->stack.dim = c->dim;
+    c->stack.n = c->stack.n_pad = c->used;
+    c->dirty = true;
+    if (img_idx) *img_idx = (int32_t)(c->rows.size() - 1);
+    return FM_OK;
+}
+
+extern "C" int fm_collection_add_u8(fm_ctx* ctx, fm_collection* c, const uint8_t* rows, int64_t n, int dim, int32_t* img_idx)
+{
+    return coll_add(ctx, c, rows, n, dim, 1, img_idx, "fm_collection_add_u8");
+}
+
+extern "C" int fm_collection_add_f32(fm_ctx* ctx, fm_collection* c, const float* rows, int64_t n, int dim, int32_t* img_idx)
+{
+    return coll_add(ctx, c, rows, n, dim, 2, img_idx, "fm_collection_add_f32");
+}
+
+extern "C" int fm_collection_add_bin(fm_ctx* ctx, fm_collection* c, const uint8_t* rows, int64_t n, int bytes, int32_t* img_idx)
+{
+    return coll_add(ctx, c, rows, n, bytes, 3, img_idx, "fm_collection_add_bin");
+}
+
+extern "C" int fm_collection_train(fm_ctx* ctx, fm_collection* c)
+{
+    int rc = coll_check(ctx, c, "fm_collection_train");
+    if (rc != FM_OK) return rc;
+    if (!c->dirty) return FM_OK;
+    const int64_t ns = c->nstages(), ni = (int64_t)c->rows.size();
+    std::vector<int32_t> tab((size_t)(2 * ns + ni + 1), 0);
+    for (int64_t i = 0; i < ni; ++i) {
+        tab[(size_t)(2 * ns + i)] = (int32_t)c->phys[(size_t)i];
+        const int64_t s0 = c->phys[(size_t)i] / kStageRows, n = c->rows[(size_t)i];
+        for (int64_t s = 0; s * kStageRows < n; ++s) {
+            tab[(size_t)(s0 + s)] = (int32_t)i;
+            tab[(size_t)(ns + s0 + s)] = (int32_t)std::min<int64_t>(kStageRows, n - s * kStageRows);
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = tab.size() * 4;
+    if (bytes > c->tab_bytes) {
+        sync_all_streams(ctx);
+        if (c->d_tab) (void)hipFree(c->d_tab);
+        c->d_tab = nullptr; c->tab_bytes = 0;
+        const size_t want = bytes * 2;
+        HIP_TRY(ctx, hipMalloc((void**)&c->d_tab, want));
+        c->tab_bytes = want;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(c->d_tab, tab.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    c->dirty = false;
+    return FM_OK;
+}
+
+extern "C" int fm_collection_info(const fm_collection* c, int32_t* n_images, int64_t* n_rows_total, int* dim, int* kind)
+{
+    if (!c) return fail(nullptr, FM_EINVAL, "fm_collection_info: collection is NULL");
+    if (n_images) *n_images = (int32_t)c->rows.size();
+    if (n_rows_total) *n_rows_total = c->total;
+    if (dim) *dim = c->dim;
+    if (kind) *kind = c->dim ? c->stack.kind : 0;
+    return FM_OK;
+}
+
+extern "C" int fm_collection_image_rows(const fm_collection* c, int64_t* rows)
+{
+    if (!c) return fail(nullptr, FM_EINVAL, "fm_collection_image_rows: collection is NULL");
+    if (!rows && !c->rows.empty()) return fail(nullptr, FM_EINVAL, "fm_collection_image_rows: rows is NULL");
+    for (size_t i = 0; i < c->rows.size(); ++i) rows[i] = c->rows[i];
+    return FM_OK;
+}
+
+extern "C" int fm_collection_locate(const int64_t* first_row, int32_t n_images, const int64_t* g, int64_t m, int32_t* img, int64_t* local)
+{
+    if (n_images < 0 || m < 0 || !first_row || (m > 0 && (!g || !img || !local)))
+        return fail(nullptr, FM_EINVAL, "fm_collection_locate: bad arguments");
+    for (int32_t i = 0; i < n_images; ++i)
+        if (first_row[i + 1] < first_row[i]) return fail(nullptr, FM_EINVAL, "fm_collection_locate: first_row does not ascend");
+    for (int64_t j = 0; j < m; ++j) {
+        const int64_t r = g[j];
+        if (r < first_row[0] || r >= first_row[n_images]) { img[j] = -1; local[j] = -1; continue; }
+        // the last image whose first row is <= r (empty images in between share a first row and are skipped)
+        const int64_t* e = std::upper_bound(first_row, first_row + n_images + 1, r);
+        const int32_t i = (int32_t)(e - first_row) - 1;
+        img[j] = i;
+        local[j] = r - first_row[i];
+    }
+    return FM_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// matching
+// ---------------------------------------------------------------------------------------
+static int coll_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const char* who)
+{
+    int rc = coll_check(ctx, c, who);
+    if (rc != FM_OK) return rc;
+    if (!q) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank is NULL");
+    if (c->dim != 0 && q->kind != c->stack.kind)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the query bank is not of the collection's kind (fm_collection_info)");
+    if (c->dim != 0 && q->dim != c->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": the query's width differs from the collection's");
+    return fm_collection_train(ctx, c);
+}
+
+static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline size_t coll_fix_bytes(int64_t rows) { return al256((size_t)rows * 4 + 16); }
+
+// A bank view of image i (rows of the stack's arrays)
+static fm::Bank coll_view(const fm_collection* c, int i)
+{
+    fm::Bank v = fm::Bank();
+    const fm::Bank& s = c->stack;
+    const int64_t n = c->rows[(size_t)i], p0 = c->phys[(size_t)i];
+    v.kind = s.kind; v.n = n; v.dim = c->dim;
+    v.n_pad = v.cap_pad = ((n + kStageRows - 1) / kStageRows) * kStageRows;
+    v.usq_max = c->usq[(size_t)i];
+    if (s.kind == FM_BANK_F32) {
+        v.rowsf = s.rowsf + (size_t)p0 * kDim; v.rowsh = s.rowsh + (size_t)p0 * kDim; v.normf = s.normf + p0; v.auxf = s.auxf + p0;
+        v.kscale = s.kscale; v.filt_ok = s.filt_ok; v.nm_max = s.nm_max;          // (the collection's largest norm: an upper bound)
+    } else if (s.kind == FM_BANK_BIN) {
+        v.ksteps = s.ksteps;
+        v.rowsb = s.rowsb + (size_t)p0 * s.ksteps * 16; v.rows4 = s.rows4 + (size_t)p0 * s.ksteps * 64;
+    } else {
+        v.rows8 = s.rows8 + (size_t)p0 * kDim; v.norm = s.norm + p0; v.aux = s.aux + (p0 / kTileRows) * kAuxPerTile;
+    }
+    return v;
+}
+
+// Top-2 sweep of q over a float32-route or binary bank `t` (the stack with its stage table, or an image's view) and its merge
+// into slot `sl` of the outputs; the keys carry the distance's float32 bits.  Enqueued on the context's stream.
+static int coll_sweep_f32_bin(fm_ctx* ctx, const fm_bank* q, const fm::Bank& t, const int32_t* stage_real, CollTab tab, int64_t out,
+                              int32_t* d_img, int32_t* d_idx, float* d_dist)
+{
+    const int64_t nq = q->n;
+    CollMerge mg{};
+    CollSlot& sl = mg.s[0];
+    sl.out = out; sl.fix = nullptr;
+    int rc;
+    if (t.kind == FM_BANK_BIN) {
+        const HamPlan hp = plan_hamming(q->n_pad, t.n_pad);
+        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, hp.partial_bytes(2) + 64)) != FM_OK) return rc;
+        HIP_TRY(ctx, launch_hamming(*q, t, 2, hp, (unsigned long long*)ctx->ws_partial, ctx->stream, stage_real));
+        sl.nsplit = hp.nsplit; sl.ncols_alloc = hp.ncols_alloc;
+    } else {
+        RowReducePlan pl;
+        if ((rc = rowreduce_f32_route(ctx, q, static_cast<const fm_bank*>(&t), 2, &pl)) != FM_OK) return rc;
+        sl.nsplit = pl.nsplit; sl.ncols_alloc = pl.ncols_alloc;
+    }
+    sl.partial = (const unsigned long long*)ctx->ws_partial;
+    hipLaunchKernelGGL(coll_merge2_kernel, dim3((unsigned)((nq + 255) / 256), 1), dim3(256), 0, ctx->stream, mg, tab, nq, d_img, d_idx, d_dist, 1);
+    HIP_TRY(ctx, hipGetLastError());
+    return FM_OK;
+}
+
+// The stacked 2-NN lists of q on the device: img / idx / dist [nq][2].  ws_partial: partial | bounds | fix list.
+static int coll_knn2_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t* d_img, int32_t* d_idx, float* d_dist)
+{
+    const int64_t nq = q->n;
+    CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
+    CollMerge mg{};
+    CollSlot& sl = mg.s[0];
+    sl.out = 0;
+    if (c->total == 0) {
+        sl.partial = nullptr; sl.nsplit = 0; sl.ncols_alloc = 0; sl.fix = nullptr;
+        hipLaunchKernelGGL(coll_merge2_kernel, dim3((unsigned)((nq + 255) / 256), 1), dim3(256), 0, ctx->stream, mg, CollTab{nullptr, nullptr, nullptr},
+                           nq, d_img, d_idx, d_dist, 0);
+        HIP_TRY(ctx, hipGetLastError());
+        return FM_OK;
+    }
+    const fm::Bank& t = c->stack;
+    ctx->pending_pairs += nq * c->total;
+    if (t.kind != FM_BANK_I8) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+        int rc = coll_sweep_f32_bin(ctx, q, t, c->st_real(), tab, 0, d_img, d_idx, d_dist);
+        if (rc != FM_OK) return rc;
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+        ctx->kernel_timed = true;
+        ctx->pending_bytes += bank_bytes(q) + bank_bytes(static_cast<const fm_bank*>(&t));
+        return FM_OK;
+    }
+    const RowReducePlan pl = plan_rowreduce(q->n_pad, t.n_pad, ctx->tune);
+    const size_t pbytes = al256(pl.partial_bytes(2)), bbytes = al256(pl.bound_bytes());
+    int rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, pbytes + bbytes + coll_fix_bytes(nq));
+    if (rc != FM_OK) return rc;
+    int* d_bound = nullptr;
+    if (ctx->tune.coop != 0 && pl.nsplit > 1) {
+        d_bound = (int*)((char*)ctx->ws_partial + pbytes);
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)d_bound, (int)0x80000000, (size_t)pl.ncols_alloc * 2, ctx->stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+    HIP_TRY(ctx, launch_rowreduce(*q, t, 2, pl, (unsigned long long*)ctx->ws_partial, d_bound, ctx->tune.glds != 0, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+    ctx->kernel_timed = true;
+    ctx->pending_bytes += bank_bytes(q) + c->used * 128;
+    unsigned* d_fix = sqrt_tie_possible(*q, t) ? (unsigned*)((char*)ctx->ws_partial + pbytes + bbytes) : nullptr;
+    if (d_fix) HIP_TRY(ctx, hipMemsetAsync(d_fix, 0, 16, ctx->stream));
+    sl.partial = (const unsigned long long*)ctx->ws_partial; sl.nsplit = pl.nsplit; sl.ncols_alloc = pl.ncols_alloc; sl.fix = d_fix;
+    hipLaunchKernelGGL(coll_merge2_kernel, dim3((unsigned)((nq + 255) / 256), 1), dim3(256), 0, ctx->stream, mg, tab, nq, d_img, d_idx, d_dist, 0);
+    HIP_TRY(ctx, hipGetLastError());
+    if (d_fix) {
+        hipLaunchKernelGGL(coll_sqrt_fix_kernel, dim3(kCollFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)d_fix,
+                           (const int8_t*)q->rows8, (const int32_t*)q->norm, (const int8_t*)t.rows8, (const int32_t*)t.norm, (int)t.n,
+                           tab, (int64_t)0, d_img, d_idx, d_dist);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return FM_OK;
+}
+
+extern "C" int fm_collection_knn(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t k, int32_t* img, int32_t* idx, float* dist)
+{
+    int rc = coll_query_check(ctx, c, q, "fm_collection_knn");
+    if (rc != FM_OK) return rc;
+    if (k < 1) return fail(ctx, FM_EINVAL, "fm_collection_knn: k must be at least 1");
+    if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_collection_knn: k above 8 is not built");
+    const int64_t nq = q->n;
+    if (nq > 0 && (!img || !idx || !dist)) return fail(ctx, FM_EINVAL, "fm_collection_knn: output pointer is NULL");
+    if (nq == 0) return FM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int kk = k < 2 ? 2 : k;
+    const size_t ob = al256((size_t)nq * kk * 4), cb = al256((size_t)nq * 4);
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, 3 * ob + 3 * cb + 64)) != FM_OK) return rc;
+    char* b = (char*)ctx->ws_out;
+    int32_t* d_img = (int32_t*)b; int32_t* d_idx = (int32_t*)(b + ob); float* d_dist = (float*)(b + 2 * ob);
+    int32_t* d_img1 = (int32_t*)(b + 3 * ob); int32_t* d_idx1 = (int32_t*)(b + 3 * ob + cb); float* d_dist1 = (float*)(b + 3 * ob + 2 * cb);
+    CallScope cs(ctx);
+    if (k <= 2 || c->total == 0) {
+        if (k <= 2) {
+            if ((rc = coll_knn2_device(ctx, c, q, d_img, d_idx, d_dist)) != FM_OK) return rc;
+        } else {
+            HIP_TRY(ctx, hipMemsetAsync(d_img, 0xff, (size_t)nq * k * 4, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(d_idx, 0xff, (size_t)nq * k * 4, ctx->stream));
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)d_dist, 0x7f800000, (size_t)nq * k, ctx->stream));
+        }
+        if (k == 1) {
+            hipLaunchKernelGGL(coll_col0_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t*)d_img,
+                               (const float*)d_dist, (const int32_t*)d_idx, nq, d_img1, d_dist1, d_idx1);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, d2h(ctx, img, d_img1, (size_t)nq * 4));
+            HIP_TRY(ctx, d2h(ctx, idx, d_idx1, (size_t)nq * 4));
+            HIP_TRY(ctx, d2h(ctx, dist, d_dist1, (size_t)nq * 4));
+            return cs.finish();
+        }
+    } else {
+        const fm::Bank& t = c->stack;
+        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, knnk_partial_bytes(nq, t.n, k) + 64)) != FM_OK) return rc;
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+        if (t.kind == FM_BANK_BIN)
+            HIP_TRY(ctx, launch_hamming_knnk(*q, t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream, c->st_real()));
+        else
+            HIP_TRY(ctx, launch_knnk(*q, t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+        ctx->kernel_timed = true;
+        ctx->pending_pairs += nq * c->total;
+        ctx->pending_bytes += bank_bytes(q) + bank_bytes(static_cast<const fm_bank*>(&t));
+        hipLaunchKernelGGL(coll_translate_kernel, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, ctx->stream,
+                           CollTab{c->st_img(), c->st_real(), c->img_phys()}, nq * k, d_img, d_idx, d_dist);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, d2h(ctx, img, d_img, (size_t)nq * k * 4));
+    HIP_TRY(ctx, d2h(ctx, idx, d_idx, (size_t)nq * k * 4));
+    HIP_TRY(ctx, d2h(ctx, dist, d_dist, (size_t)nq * k * 4));
+    return cs.finish();
+}
+
+extern "C" int fm_collection_knn2_ratio(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap,
+                                        int32_t* qidx, int32_t* img, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+{
+    int rc = coll_query_check(ctx, c, q, "fm_collection_knn2_ratio");
+    if (rc != FM_OK) return rc;
+    if (n_accepted) *n_accepted = 0;
+    const int64_t nq = q->n;
+    if (nq == 0) return FM_OK;
+    if (cap < 0 || !qidx || !img || !tidx || !dist || !ratio) return fail(ctx, FM_EINVAL, "fm_collection_knn2_ratio: bad output arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int nblk = (int)((nq + 255) / 256);
+    const int64_t ccap = cap < nq ? cap : nq;
+    size_t off = 0;
+    auto carve = [&](size_t b) { size_t o = off; off += al256(b); return o; };
+    const size_t o_m2 = carve((size_t)nq * 8), o_i2 = carve((size_t)nq * 8), o_d2 = carve((size_t)nq * 8);
+    const size_t o_ti = carve((size_t)nq * 4), o_di = carve((size_t)nq * 4), o_ra = carve((size_t)nq * 8);
+    const size_t o_pa = carve((size_t)nq), o_bc = carve((size_t)nblk * 4), o_cnt = carve(16);
+    const size_t o_cq = carve((size_t)ccap * 4), o_ct = carve((size_t)ccap * 4), o_cm = carve((size_t)ccap * 4);
+    const size_t o_cd = carve((size_t)ccap * 4), o_cr = carve((size_t)ccap * 8);
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
+    char* b = (char*)ctx->ws_out;
+    CallScope cs(ctx);
+    if ((rc = coll_knn2_device(ctx, c, q, (int32_t*)(b + o_m2), (int32_t*)(b + o_i2), (float*)(b + o_d2))) != FM_OK) return rc;
+    // the ratio test of fm_knn2_ratio on the row lists, then the ordered compaction with the image column
+    hipLaunchKernelGGL(lowe_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_i2), (const float*)(b + o_d2), nq, tau,
+                       (int32_t*)(b + o_ti), (float*)(b + o_di), (double*)(b + o_ra), (uint8_t*)(b + o_pa), (int*)(b + o_bc));
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(coll_compact_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_m2), (const int32_t*)(b + o_ti),
+                       (const float*)(b + o_di), (const double*)(b + o_ra), (const uint8_t*)(b + o_pa), (const int*)(b + o_bc), nq, ccap,
+                       (int32_t*)(b + o_cq), (int32_t*)(b + o_cm), (int32_t*)(b + o_ct), (float*)(b + o_cd), (double*)(b + o_cr),
+                       (unsigned long long*)(b + o_cnt));
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long cnt = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&cnt, b + o_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t m = (size_t)((int64_t)cnt < ccap ? (int64_t)cnt : ccap);
+    if (m) {
+        HIP_TRY(ctx, d2h(ctx, qidx, b + o_cq, m * 4));
+        HIP_TRY(ctx, d2h(ctx, img, b + o_cm, m * 4));
+        HIP_TRY(ctx, d2h(ctx, tidx, b + o_ct, m * 4));
+        HIP_TRY(ctx, d2h(ctx, dist, b + o_cd, m * 4));
+        HIP_TRY(ctx, d2h(ctx, ratio, b + o_cr, m * 8));
+    }
+    rc = cs.finish();
+    if (rc != FM_OK) return rc;
+    if (n_accepted) *n_accepted = (int64_t)cnt;
+    return FM_OK;
+}
+
+// The per-image 2-NN lists on the device: d_idx / d_dist [n_images][nq][2].  Up to "batch_group" images per launch of the
+// batched top-2 sweep, every image under its own plan in the batched shape (4 blocks per wave, 8 waves, three stage
+// buffers, LDS-DMA staging -- whatever the shape options say: results do not depend on them); one merge launch per sweep
+// launch.  The launches follow each other on the context's stream and share one workspace.
+static int coll_each_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t* d_idx, float* d_dist)
+{
+    const int64_t nq = q->n;
+    const int ni = (int)c->rows.size();
+    if (c->stack.kind != FM_BANK_I8 && c->total > 0) {
+        // float32-route and binary collections: the per-image sweeps (K8 / K5, K11) enqueued back to back, each followed by its
+        // merge -- one stream, one workspace, no host synchronisation between images
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+        for (int i = 0; i < ni; ++i) {
+            const fm_bank v = fm_bank{coll_view(c, i)};
+            int rc;
+            if (v.n == 0) {
+                CollMerge mg{};
+                mg.s[0].out = (int64_t)i * nq;
+                hipLaunchKernelGGL(coll_merge2_kernel, dim3((unsigned)((nq + 255) / 256), 1), dim3(256), 0, ctx->stream, mg,
+                                   CollTab{nullptr, nullptr, nullptr}, nq, (int32_t*)nullptr, d_idx, d_dist, 1);
+                HIP_TRY(ctx, hipGetLastError());
+                continue;
+            }
+            if ((rc = coll_sweep_f32_bin(ctx, q, v, nullptr, CollTab{nullptr, nullptr, nullptr}, (int64_t)i * nq, nullptr, d_idx, d_dist)) != FM_OK)
+                return rc;
+            ctx->pending_pairs += nq * v.n;
+            ctx->pending_bytes += bank_bytes(q) + bank_bytes(&v);
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+        ctx->kernel_timed = true;
+        return FM_OK;
+    }
+    int group = ctx->tune.batch_group;
+    if (group < 1) group = 1;
+    if (group > kRRBatchMax) group = kRRBatchMax;
+    Tuning shaped = ctx->tune;
+    shaped.nb = 4; shaped.nw = 8; shaped.nbuf = 0; shaped.nsplit = 0; shaped.k1_order = 0;
+    // workspace of one launch: per slot partial | bounds | fix list, sized for the largest image
+    int64_t max_pad = kStageRows;
+    for (int i = 0; i < ni; ++i) max_pad = std::max<int64_t>(max_pad, ((c->rows[(size_t)i] + kStageRows - 1) / kStageRows) * kStageRows);
+    const RowReducePlan big = plan_rowreduce(q->n_pad, max_pad, shaped);
+    size_t slot_p = 0;
+    for (int i = 0; i < ni; ++i) {           // (the split count is not monotonic in the image size: take the maximum)
+        if (c->rows[(size_t)i] == 0) continue;
+        const RowReducePlan p = plan_rowreduce(q->n_pad, ((c->rows[(size_t)i] + kStageRows - 1) / kStageRows) * kStageRows, shaped);
+        slot_p = std::max(slot_p, al256(p.partial_bytes(2)));
+    }
+    const size_t slot_b = al256(big.bound_bytes()), slot_f = coll_fix_bytes(nq);
+    const size_t slot = slot_p + slot_b + slot_f;
+    int rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, slot * (size_t)group + 64);
+    if (rc != FM_OK) return rc;
+    bool timed = false;
+    for (int i0 = 0; i0 < ni; i0 += group) {
+        const int g = std::min(group, ni - i0);
+        fm::Bank views[kRRBatchMax];
+        const fm::Bank* cols[kRRBatchMax]; const fm::Bank* red[kRRBatchMax];
+        RowReducePlan plans[kRRBatchMax];
+        unsigned long long* parts[kRRBatchMax]; int* bounds[kRRBatchMax];
+        int slot_of[kRRBatchMax];
+        CollMerge mg{};
+        int nl = 0;
+        for (int j = 0; j < g; ++j) {
+            const int i = i0 + j;
+            const int64_t n = c->rows[(size_t)i];
+            CollSlot& sl = mg.s[j];
+            sl.out = (int64_t)i * nq;
+            sl.partial = nullptr; sl.nsplit = 0; sl.ncols_alloc = 0; sl.fix = nullptr;
+            if (n == 0) continue;
+            char* base = (char*)ctx->ws_partial + slot * (size_t)j;
+            fm::Bank& v = views[nl];
+            v = coll_view(c, i);
+            plans[nl] = plan_rowreduce(q->n_pad, v.n_pad, shaped);
+            cols[nl] = q; red[nl] = &v;
+            parts[nl] = (unsigned long long*)base;
+            bounds[nl] = nullptr;
+            if (ctx->tune.coop != 0 && plans[nl].nsplit > 1) {
+                bounds[nl] = (int*)(base + slot_p);
+                HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)bounds[nl], (int)0x80000000, (size_t)plans[nl].ncols_alloc * 2, ctx->stream));
+            }
+            sl.partial = parts[nl]; sl.nsplit = plans[nl].nsplit; sl.ncols_alloc = plans[nl].ncols_alloc;
+            if (sqrt_tie_possible(*q, v)) {
+                sl.fix = (unsigned*)(base + slot_p + slot_b);
+                HIP_TRY(ctx, hipMemsetAsync(sl.fix, 0, 16, ctx->stream));
+            }
+            slot_of[nl] = j;
+            ctx->pending_pairs += nq * n;
+            ctx->pending_bytes += bank_bytes(q) + v.n * 128;
+            ++nl;
+        }
+        if (nl > 0) {
+            if (!timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+            HIP_TRY(ctx, launch_rowreduce_batch2(nl, cols, red, plans, parts, bounds, ctx->stream));
+            timed = true;
+        }
+        hipLaunchKernelGGL(coll_merge2_kernel, dim3((unsigned)((nq + 255) / 256), (unsigned)g), dim3(256), 0, ctx->stream, mg,
+                           CollTab{nullptr, nullptr, nullptr}, nq, (int32_t*)nullptr, d_idx, d_dist, 0);
+        HIP_TRY(ctx, hipGetLastError());
+        for (int l = 0; l < nl; ++l) {
+            const CollSlot& sl = mg.s[slot_of[l]];
+            if (!sl.fix) continue;
+            hipLaunchKernelGGL(coll_sqrt_fix_kernel, dim3(kCollFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)sl.fix,
+                               (const int8_t*)q->rows8, (const int32_t*)q->norm, (const int8_t*)views[l].rows8, (const int32_t*)views[l].norm,
+                               (int)views[l].n, CollTab{nullptr, nullptr, nullptr}, sl.out, (int32_t*)nullptr, d_idx, d_dist);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    if (timed) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));       // (the sweeps and the merges between them)
+        ctx->kernel_timed = true;
+    }
+    return FM_OK;
+}
+
+extern "C" int fm_collection_knn2_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t* idx, float* dist)
+{
+    int rc = coll_query_check(ctx, c, q, "fm_collection_knn2_each");
+    if (rc != FM_OK) return rc;
+    const int64_t nq = q->n, ni = (int64_t)c->rows.size();
+    if (nq == 0 || ni == 0) return FM_OK;
+    if (!idx || !dist) return fail(ctx, FM_EINVAL, "fm_collection_knn2_each: output pointer is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t ob = al256((size_t)ni * nq * 8);
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, 2 * ob + 64)) != FM_OK) return rc;
+    int32_t* d_idx = (int32_t*)ctx->ws_out;
+    float* d_dist = (float*)((char*)ctx->ws_out + ob);
+    CallScope cs(ctx);
+    if ((rc = coll_each_device(ctx, c, q, d_idx, d_dist)) != FM_OK) return rc;
+    // (copies of up to 128 MB each keep the staging buffer of fm::d2h within bounds)
+    const size_t total = (size_t)ni * nq * 8, piece = (size_t)128 << 20;
+    for (size_t o = 0; o < total; o += piece) {
+        const size_t nb = std::min(piece, total - o);
+        HIP_TRY(ctx, d2h(ctx, (char*)idx + o, (char*)d_idx + o, nb));
+        HIP_TRY(ctx, d2h(ctx, (char*)dist + o, (char*)d_dist + o, nb));
+    }
+    return cs.finish();
+}
+
+extern "C" int fm_collection_votes(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t mode, int64_t* votes)
+{
+    int rc = coll_query_check(ctx, c, q, "fm_collection_votes");
+    if (rc != FM_OK) return rc;
+    if (mode != 0 && mode != 1) return fail(ctx, FM_EINVAL, "fm_collection_votes: mode must be 0 (stacked lists) or 1 (per-image lists)");
+    const int64_t nq = q->n, ni = (int64_t)c->rows.size();
+    if (ni == 0) return FM_OK;
+    if (!votes) return fail(ctx, FM_EINVAL, "fm_collection_votes: votes is NULL");
+    for (int64_t i = 0; i < ni; ++i) votes[i] = 0;
+    if (nq == 0) return FM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t vb = al256((size_t)ni * 8);
+    const size_t lb = al256((size_t)(mode == 0 ? 1 : ni) * nq * 8);
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, vb + 3 * lb + 64)) != FM_OK) return rc;
+    char* b = (char*)ctx->ws_out;
+    unsigned long long* d_votes = (unsigned long long*)b;
+    int32_t* d_idx = (int32_t*)(b + vb); float* d_dist = (float*)(b + vb + lb); int32_t* d_img = (int32_t*)(b + vb + 2 * lb);
+    CallScope cs(ctx);
+    HIP_TRY(ctx, hipMemsetAsync(d_votes, 0, (size_t)ni * 8, ctx->stream));
+    if (mode == 0) {
+        if ((rc = coll_knn2_device(ctx, c, q, d_img, d_idx, d_dist)) != FM_OK) return rc;
+        hipLaunchKernelGGL(coll_votes_kernel, dim3((unsigned)((nq + 255) / 256), 1), dim3(256), 0, ctx->stream, (const int32_t*)d_img,
+                           (const int32_t*)d_idx, (const float*)d_dist, nq, tau, d_votes);
+    } else {
+        if ((rc = coll_each_device(ctx, c, q, d_idx, d_dist)) != FM_OK) return rc;
+        hipLaunchKernelGGL(coll_votes_kernel, dim3((unsigned)((nq + 255) / 256), (unsigned)ni), dim3(256), 0, ctx->stream, (const int32_t*)nullptr,
+                           (const int32_t*)d_idx, (const float*)d_dist, nq, tau, d_votes);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, d2h(ctx, votes, d_votes, (size_t)ni * 8));
+    return cs.finish();
+}

@@ -824,6 +824,31 @@ extern "C" int fm_bank_append_u8(fm_ctx* ctx, fm_bank* bank, const uint8_t* rows
     return FM_OK;
 }
 
+// Rows [off, off + n_pad) of an integer-route bank's arrays (off and n_pad multiples of 128) from n host rows (uint8, or
+// float32 when f32) -- the rows behind the n real ones come out as padding rows.  flags[0]: a float32 value was not an
+// integer in 0 .. 255 (the range then holds no usable rows), flags[1]: the largest |row|^2.  Synchronous.  A train
+// collection (api_collection.hip) places its images with it.
+int fm::bank_prep_range(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f32, Bank& b, int64_t off, int64_t n_pad, int* flags)
+{
+    const size_t src_bytes = (size_t)n * dim * (f32 ? 4 : 1), flag_off = (src_bytes + 15) & ~(size_t)15;
+    int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, flag_off + 32);
+    if (rc != FM_OK) return rc;
+    int* d_flag = (int*)((char*)ctx->ws_in + flag_off);
+    if (src_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 8, ctx->stream));
+    const int64_t ntiles = n_pad / kTileRows;
+    if (f32)
+        hipLaunchKernelGGL(bank_prep_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, (const void*)ctx->ws_in, n, dim,
+                           b.rows8 + (size_t)off * kDim, b.norm + off, b.aux + (off / kTileRows) * kAuxPerTile, d_flag, ntiles);
+    else
+        hipLaunchKernelGGL(bank_prep_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, (const void*)ctx->ws_in, n, dim,
+                           b.rows8 + (size_t)off * kDim, b.norm + off, b.aux + (off / kTileRows) * kAuxPerTile, d_flag, ntiles);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(flags, d_flag, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return FM_OK;
+}
+
 // ---- a float32-route bank that grows (r05: lazy targets with descriptors that are not integer valued) -----------------
 // Rows of the new range: largest magnitude (float bits) in stat[0], stat[1] |= 1 for a value that is not finite.
 __global__ __launch_bounds__(256)
@@ -937,6 +962,47 @@ extern "C" int fm_bank_append_f32(fm_ctx* ctx, fm_bank* bank, const float* rows,
     if (nmx > bank->nm_max) bank->nm_max = nmx;
     bank->n = off + n;
     bank->n_pad = ((bank->n + kStageRows - 1) / kStageRows) * kStageRows;
+    return FM_OK;
+}
+
+// Float32-route rows [off, off + n_pad) of a bank's arrays (train collections): the n host rows into rowsf (zero rows behind
+// them), *vmax = their largest magnitude, *finite = every value is finite.  Then bank_f32_range_planes: the fp16 planes of
+// the range under b.kscale (rows from n on: padding), *nm_max = the largest scaled norm.  Both synchronous.
+int fm::bank_f32_range_rows(fm_ctx* ctx, const float* rows, int64_t n, int dim, Bank& b, int64_t off, int64_t n_pad, float* vmax, bool* finite)
+{
+    const size_t src_bytes = (size_t)n * dim * 4, flag_off = (src_bytes + 15) & ~(size_t)15;
+    int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, flag_off + 32);
+    if (rc != FM_OK) return rc;
+    int* d_flag = (int*)((char*)ctx->ws_in + flag_off);
+    float* dst = b.rowsf + (size_t)off * kDim;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 16, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(dst, 0, (size_t)n_pad * kDim * 4, ctx->stream));
+    hipLaunchKernelGGL(bank_append_f32_kernel, dim3((unsigned)std::min<int64_t>(1024, (n * kDim + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const float*)ctx->ws_in, n, dim, dst, d_flag);
+    HIP_TRY(ctx, hipGetLastError());
+    int stat[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(stat, d_flag, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(vmax, &stat[0], 4);
+    *finite = stat[1] == 0;
+    return FM_OK;
+}
+
+int fm::bank_f32_range_planes(fm_ctx* ctx, Bank& b, int64_t off, int64_t n, int64_t n_pad, float* nm_max)
+{
+    int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, 64);
+    if (rc != FM_OK) return rc;
+    int* d_flag = (int*)ctx->ws_in;
+    HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(bank_prep_f16_kernel, dim3((unsigned)(n_pad / 16)), dim3(256), 0, ctx->stream,
+                       (const float*)(b.rowsf + (size_t)off * kDim), n, n_pad, b.kscale, b.rowsh + (size_t)off * kDim, b.normf + off,
+                       b.auxf + off, d_flag);
+    HIP_TRY(ctx, hipGetLastError());
+    int stat[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(stat, d_flag, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(nm_max, &stat[0], 4);
     return FM_OK;
 }
 

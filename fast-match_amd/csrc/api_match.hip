@@ -489,7 +489,7 @@ static int tri_plan_for(fm_ctx* ctx, int64_t n_pad, TriPlan* out)
 // float32 route: K5 alone, or the fp16 filter (K8) with K5 as its conditional fallback
 // ---------------------------------------------------------------------------------------
 // Leaves the packed keys in ws_partial in `pl`'s layout (K5's plan) either way.
-static int rowreduce_f32_route(fm_ctx* ctx, const fm_bank* cols, const fm_bank* red, int ktop, RowReducePlan* pl_out, bool self = false)
+int rowreduce_f32_route(fm_ctx* ctx, const fm_bank* cols, const fm_bank* red, int ktop, RowReducePlan* pl_out, bool self)
 {
     const RowReducePlan pl = plan_rowreduce_f32(cols->n_pad, red->n_pad, ctx->tune.nsplit);
     *pl_out = pl;

@@ -147,6 +147,10 @@ void fill_round_f32(fm::RoundF32* r, const fm::Bank& q, const fm::Bank& t);
 // K10: radiusMatch (radius.hip); arguments checked by fm_radius_match (api_match.hip)
 int radius_match(fm_ctx* ctx, const fm::Bank& q, const fm::Bank& t, const float* radius, float radius_all, int64_t cap,
                  int64_t* offsets, int32_t* idx, float* dist, int64_t* n_total);
+// Prepared rows of an integer-route bank's arrays from host rows, at a 128-row offset (api_ctx.hip; train collections)
+int bank_prep_range(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f32, Bank& b, int64_t off, int64_t n_pad, int* flags);
+int bank_f32_range_rows(fm_ctx* ctx, const float* rows, int64_t n, int dim, Bank& b, int64_t off, int64_t n_pad, float* vmax, bool* finite);
+int bank_f32_range_planes(fm_ctx* ctx, Bank& b, int64_t off, int64_t n, int64_t n_pad, float* nm_max);
 // A bank's self distances, and its largest one (Bank::sdmax), in place: the array is allocated once, the word behind it.
 int bank_selfdist_alloc(fm_ctx* ctx, fm_bank* b);
 // Bank::sdmax of the rows [0, n) of b->selfdist, enqueued on `stream` (sets sdmax_rows).
@@ -154,6 +158,15 @@ int enqueue_selfdist_max(fm_ctx* ctx, fm_bank* b, hipStream_t stream);
 int round_xcheck_dense(fm_ctx* ctx, const fm::Bank& q, const int32_t* d_rows, int64_t nq, const fm::Bank& t, int64_t t0, int64_t nt,
                        unsigned long long* d_qbest);
 }
+
+// Float32 route of a top-KTOP row-reduce (api_match.hip): K5 alone, or the fp16 filter (K8) with K5 as its conditional fallback;
+// leaves the packed keys in ctx->ws_partial in *pl_out's layout.
+int rowreduce_f32_route(fm_ctx* ctx, const fm_bank* cols, const fm_bank* red, int ktop, fm::RowReducePlan* pl_out, bool self = false);
+// Lowe's ratio test on 2-NN lists (api_match.hip; api_collection.hip runs it on a collection's lists)
+__global__ void lowe_kernel(const int32_t* __restrict__ idx2, const float* __restrict__ dist2, int64_t nq,
+                            double tau, int32_t* __restrict__ tidx, float* __restrict__ dist,
+                            double* __restrict__ ratio, uint8_t* __restrict__ pass,
+                            int* __restrict__ block_counts);
 
 // Brackets one API call: events for total time, stats accounting after the final sync.
 struct CallScope {

@@ -203,11 +203,14 @@ struct HamPlan {
     size_t partial_bytes(int ktop) const { return (size_t)nsplit * ncols_alloc * ktop * 8; }
 };
 HamPlan plan_hamming(int64_t ncols_pad, int64_t nred_pad);
-hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const HamPlan& plan, unsigned long long* partial, hipStream_t stream);
+// stage_real (train collections): real rows per 128-row stage of `red`, an index mask per stage; null = a plain bank
+hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const HamPlan& plan, unsigned long long* partial, hipStream_t stream,
+                          const int* stage_real = nullptr);
 // packed rows + FP4 image of n uploaded [n][bytes] rows (b.n_pad, b.ksteps, b.rowsb, b.rows4 set by the caller)
 hipError_t launch_hamming_prep(const uint8_t* d_src, int64_t n, int bytes, const Bank& b, hipStream_t stream);
 // k-NN lists for 1 <= k <= 8 on the vector ALUs (partial: knnk_partial_bytes)
-hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream);
+hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream,
+                               const int* stage_real = nullptr);
 
 // ---- K4: one workgroup per expansion round (rounds.hip) --------------------------------
 hipError_t launch_rounds(const Bank& q, const Bank& t, const int32_t* d_q_rows, const int64_t* d_q_off,
@@ -224,6 +227,9 @@ constexpr int kRRBatchMax = 16;           // bank pairs per batched row-reduce l
 hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
                                   unsigned long long* const* partial, int* const* bound, hipStream_t stream, bool self = false,
                                   const unsigned* const* cut = nullptr);      // (cut[i]: as launch_rowreduce's, per pair; not for self)
+// top-2 form of the batched launch (fm_collection_knn2_each): bound[i] = pair i's two bound arrays ([2 * ncols_alloc]) or null
+hipError_t launch_rowreduce_batch2(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
+                                   unsigned long long* const* partial, int* const* bound, hipStream_t stream);
 hipError_t launch_expand(const void* d_pairs, int n_pairs, bool f32, int tier, hipStream_t stream);   // all pairs of one kind / capacity tier (expand.hip)
 int expand_cand_cap();
 int expand_cand_cap_big();

@@ -82,8 +82,11 @@ __device__ __forceinline__ unsigned long long ham_key(float dot, int idx, int W)
 template <int KTOP, int KS>
 __global__ __launch_bounds__(256)
 void ham_sweep_kernel(const uint8_t* __restrict__ col4, int ncols, const uint8_t* __restrict__ red4, int nred, int W,
-                      int nchunks, int stages_per_split, int nstages, int ncols_alloc, unsigned long long* __restrict__ partial)
+                      int nchunks, int stages_per_split, int nstages, int ncols_alloc, unsigned long long* __restrict__ partial,
+                      const int* __restrict__ stage_real = nullptr)
 {
+    // stage_real (train collections, api_collection.hip): the reduced bank holds many images, each from a stage of its own;
+    // stage_real[st] = real rows of stage st, the rows behind them are padding -- the index mask of the tail, per stage
     constexpr int RB = KS * 64;             // FP4 bytes per row
     constexpr int LS = RB + 16;             // LDS row stride: the 16 rows of one 16-lane read land on distinct banks
     constexpr int PIECES = kStageRows * RB / 16 / 256;    // 16-byte pieces per thread per stage (2 KS)
@@ -132,7 +135,8 @@ void ham_sweep_kernel(const uint8_t* __restrict__ col4, int ncols, const uint8_t
         const bool more = st + 1 < st1;
         if (more) load(st + 1);
         const int sbase = st * kStageRows;
-        const bool tail = sbase + kStageRows > nred;        // the bank's last stage: rows from nred on are padding
+        const int lim = stage_real ? sbase + stage_real[st] : nred;
+        const bool tail = sbase + kStageRows > lim;         // the bank's (an image's) last stage: rows from lim on are padding
         float m1[kHamNB], m2[kHamNB];
 #pragma unroll
         for (int b = 0; b < kHamNB; ++b) { m1[b] = -INFINITY; m2[b] = -INFINITY; }
@@ -153,7 +157,7 @@ void ham_sweep_kernel(const uint8_t* __restrict__ col4, int ncols, const uint8_t
                     acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(aop[ks], bop[b][ks], acc, 4, 4, 0, 127, 0, 127);
                 if (tail) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[r] = (sbase + 16 * t + 4 * g + r < nred) ? acc[r] : -INFINITY;
+                    for (int r = 0; r < 4; ++r) acc[r] = (sbase + 16 * t + 4 * g + r < lim) ? acc[r] : -INFINITY;
                 }
                 if constexpr (KTOP == 1) {
                     m1[b] = fmaxf(fmaxf(m1[b], acc[0]), acc[1]);
@@ -239,7 +243,8 @@ HamPlan plan_hamming(int64_t ncols_pad, int64_t nred_pad)
     return p;
 }
 
-hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const HamPlan& p, unsigned long long* partial, hipStream_t stream)
+hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const HamPlan& p, unsigned long long* partial, hipStream_t stream,
+                          const int* stage_real)
 {
     if (cols.kind != FM_BANK_BIN || red.kind != FM_BANK_BIN || cols.ksteps != red.ksteps || cols.dim != red.dim) return hipErrorInvalidValue;
     const int W = 8 * cols.dim;
@@ -248,7 +253,7 @@ hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const Ham
     if (ktop == KT_ && cols.ksteps == KS_) {                                                                                   \
         hipLaunchKernelGGL((ham_sweep_kernel<KT_, KS_>), grid, block, 0, stream, (const uint8_t*)cols.rows4, (int)cols.n,     \
                            (const uint8_t*)red.rows4, (int)red.n, W, p.nchunks, p.stages_per_split, p.nstages, p.ncols_alloc,  \
-                           partial);                                                                                           \
+                           partial, stage_real);                                                                                        \
         return hipGetLastError();                                                                                              \
     }
     FM_HAM(1, 1) FM_HAM(1, 2) FM_HAM(1, 3) FM_HAM(1, 4)
@@ -263,7 +268,7 @@ constexpr int kHamKnnStage = 64;          // train rows per LDS stage (64 x at m
 template <int K, int KS>
 __global__ __launch_bounds__(256)
 void ham_knnk_kernel(const uint8_t* __restrict__ qrows, int nq, const uint8_t* __restrict__ trows, int nt, int rows_per_split,
-                     unsigned long long* __restrict__ partial)
+                     unsigned long long* __restrict__ partial, const int* __restrict__ stage_real = nullptr)
 {
     constexpr int WB = KS * 16;            // packed bytes per row (zero padded)
     __shared__ __attribute__((aligned(16))) uint8_t srow[kHamKnnStage * WB];
@@ -285,7 +290,8 @@ void ham_knnk_kernel(const uint8_t* __restrict__ qrows, int nq, const uint8_t* _
             *(v4i*)(srow + r * WB + 16 * c) = *(const v4i*)(trows + (size_t)(base + r) * WB + 16 * c);
         }
         __syncthreads();
-        const int rn = min(kHamKnnStage, t1 - base);
+        int rn = min(kHamKnnStage, t1 - base);
+        if (stage_real) rn = min(rn, stage_real[base >> 7] - (base & 127));      // (a collection's stage: see ham_sweep_kernel)
         for (int r = 0; r < rn; ++r) {
             int h = 0;
 #pragma unroll
@@ -306,7 +312,7 @@ void ham_knnk_kernel(const uint8_t* __restrict__ qrows, int nq, const uint8_t* _
 
 // (partial: knnk_partial_bytes(q.n, t.n, k) bytes -- the split rule of K9)
 hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist,
-                               hipStream_t stream)
+                               hipStream_t stream, const int* stage_real)
 {
     if (k < 1 || k > 8 || q.kind != FM_BANK_BIN || t.kind != FM_BANK_BIN || q.ksteps != t.ksteps || q.n <= 0) return hipErrorInvalidValue;
     const int nq = (int)q.n, nt = (int)t.n;
@@ -319,7 +325,7 @@ hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned lon
 #define FM_HAMK(K_, KS_)                                                                                                       \
     if (k == K_ && q.ksteps == KS_) {                                                                                          \
         hipLaunchKernelGGL((ham_knnk_kernel<K_, KS_>), grid, dim3(256), 0, stream, (const uint8_t*)q.rowsb, nq,               \
-                           (const uint8_t*)t.rowsb, nt, per, partial);                                                         \
+                           (const uint8_t*)t.rowsb, nt, per, partial, stage_real);                                                       \
         launched = true;                                                                                                       \
     }
 #define FM_HAMK4(K_) FM_HAMK(K_, 1) FM_HAMK(K_, 2) FM_HAMK(K_, 3) FM_HAMK(K_, 4)

@@ -1077,6 +1077,29 @@ hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* co
     return hipGetLastError();
 }
 
+// The same for the top-2 sweep (KTOP = 2): n <= kRRBatchMax (query, image) pairs of a train collection in one launch
+// (fm_collection_knn2_each), pair i under plans[i] in the batched shape, bound[i] = its two bound arrays or null.
+hipError_t launch_rowreduce_batch2(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
+                                   unsigned long long* const* partial, int* const* bound, hipStream_t stream)
+{
+    if (n < 1 || n > kRRBatchMax) return hipErrorInvalidValue;
+    RRBatch b;
+    long long total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (plans[i].nb != 4 || plans[i].nw != 8) return hipErrorInvalidValue;
+        fill_params(b.p[i], *cols[i], *red[i], plans[i], partial[i], bound[i]);
+        b.first_block[i] = (int)total;
+        total += rowreduce_grid(plans[i]);
+    }
+    if (total > INT32_MAX) return hipErrorInvalidValue;
+    for (int i = n; i < kRRBatchMax; ++i) b.p[i] = b.p[0];
+    b.first_block[n] = (int)total;
+    for (int i = n + 1; i <= kRRBatchMax; ++i) b.first_block[i] = INT32_MAX;
+    b.n = n;
+    hipLaunchKernelGGL((rowreduce_batch_kernel<4, 2, 8, 3, 1>), dim3((unsigned)total), dim3(64 * 8), 0, stream, b);
+    return hipGetLastError();
+}
+
 // Top-1 of every row of `bank` over the OTHER rows of the same bank (plan from plan_rowreduce_self).
 hipError_t launch_rowreduce_self(const Bank& bank, const RowReducePlan& plan, unsigned long long* partial, int* bound,
                                  bool use_glds, hipStream_t stream)

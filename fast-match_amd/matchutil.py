@@ -19,6 +19,8 @@ Mirrors ``matchutil.py`` of the reference:
   crossCheck)``); ``bf_match``, ``flann_match`` and ``ratio_match_arrays`` honour it, ``bf_radius_match`` does not
   (``ValueError``), nor does anything else take ``NORM_HAMMING2``.  Without ``normType`` every array is an L2 bank,
   a uint8 [n, 32] array included.
+* ``BFMatcher(normType, crossCheck)`` -- cv2's matcher object: ``add`` / ``train`` / ``clear`` build a TRAIN COLLECTION and
+  ``match(query)`` / ``knnMatch(query, k)`` search all of its images at once, filling ``DMatch.imgIdx`` (``fm_collection_*``).
 * ``sift / get_features / get_keypoints``     -- reference ``matchutil.py:22-36``; SIFT
   stays in OpenCV on the host and needs ``cv2``.
 
@@ -224,6 +226,157 @@ def bf_radius_match(dt1, dt2, maxDistance, options={}):
     """ cv2.BFMatcher(NORM_L2).radiusMatch(dt1, dt2, maxDistance): a list of DMatch lists, one per query row """
     off, idx, dist = bf_radius_match_arrays(dt1, dt2, maxDistance, options=options)
     return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
+
+
+class BFMatcher(object):
+    """``cv2.BFMatcher(normType, crossCheck)`` with cv2's method names.  With a train argument ``match`` / ``knnMatch`` /
+    ``radiusMatch`` are :func:`bf_match` / :func:`bf_radius_match`; without one they run against the TRAIN COLLECTION
+    built with ``add([d1, d2, ...])`` (``train()`` uploads it; implicit in the first match; ``clear()`` empties it) and
+    every ``DMatch.imgIdx`` names the image of the hit (``fm_collection_*``: one sweep over all images, the earlier
+    image wins a tie).  NORM_L2 collections hold uint8 or float32 images (float32 images whose values are all integers in
+    0 .. 255 take the exact integer route until the first other image arrives; a float32 QUERY that is not integer valued
+    against such a collection is refused by the library: upload the query's kind of images), NORM_HAMMING collections binary
+    rows.  ``ValueError`` before anything is uploaded: a normType other than 4 / 6, crossCheck on a collection of more than one image
+    (OpenCV asserts there too, as far as SURVEY.md Appendix A recalls), ``radiusMatch`` on a collection.
+    ``knnMatch_arrays`` / ``knnMatchEach_arrays`` / ``votes`` return NumPy arrays."""
+
+    def __init__(self, normType=NORM_L2, crossCheck=False, options={}):
+        if normType not in (NORM_L2, NORM_HAMMING):
+            raise ValueError("normType %r: the HIP path builds NORM_L2 (4) and NORM_HAMMING (6) only" % (normType,))
+        self.normType = normType
+        self.crossCheck = bool(crossCheck)
+        self.options = dict(options)
+        self.options["normType"] = normType
+        self._images = []
+        self._coll = None          # (_ffi.Collection, number of images it holds)
+        self._uploaded = 0
+
+    # -- bookkeeping (host only) ---------------------------------------------------------
+    def add(self, descriptors):
+        imgs = []
+        for d in descriptors:
+            a = np.asarray(d)
+            if a.ndim != 2:
+                raise ValueError("BFMatcher.add: every image's descriptors must be a 2-D [n, dim] array")
+            if self.normType == NORM_HAMMING and a.dtype != np.uint8:
+                raise ValueError("NORM_HAMMING needs uint8 descriptors (cv2 asserts CV_8U), got %s" % a.dtype)
+            for b in self._images + imgs:
+                if a.shape[0] and b.shape[0] and (b.shape[1] != a.shape[1] or (b.dtype == np.uint8) != (a.dtype == np.uint8)):
+                    raise ValueError("BFMatcher.add: images of one collection share a width and a dtype (cv2 raises at match time)")
+            imgs.append(a)
+        self._images.extend(imgs)
+
+    def clear(self):
+        self._images = []
+        self._uploaded = 0
+        if self._coll is not None:
+            self._coll.clear()
+
+    def empty(self):
+        return len(self._images) == 0
+
+    def getTrainDescriptors(self):
+        return list(self._images)
+
+    # -- the collection on the device ------------------------------------------------------
+    def _check_collection(self, who):
+        if self.empty():
+            raise ValueError("%s: no train descriptors (add() some, or pass a train array)" % who)
+
+    def train(self):
+        self._check_collection("BFMatcher.train")
+        ctx = _context(self.options)
+        if self._coll is None or self._coll.handle is None or self._coll.ctx is not ctx:
+            self._coll = ctx.collection()
+            self._uploaded = 0
+        for a in self._images[self._uploaded:]:
+            if self.normType == NORM_HAMMING:
+                self._coll.add_binary(a)
+            else:
+                self._coll.add(a)
+            self._uploaded += 1
+        self._coll.train()
+        return self._coll
+
+    def _query(self, ctx, q):
+        if isinstance(q, _ffi.Bank):
+            return q, False
+        a = np.asarray(q)
+        if a.ndim != 2:
+            raise ValueError("descriptors must be a 2-D [n, dim] array")
+        if self.normType == NORM_HAMMING:
+            return ctx.bank_binary(a), True
+        # (a float32-route collection takes a float32-route query, integer valued or not)
+        return ctx.bank(a, float_route=self._coll.info()[3] == _ffi.FM_BANK_F32 and a.dtype != np.uint8), True
+
+    def knnMatch_arrays(self, queryDescriptors, k):
+        """(img, idx, dist) [nq, k] against the collection: ``imgIdx``, ``trainIdx`` inside that image, distance; -1 / -1 / inf
+        where the collection has fewer than k rows."""
+        k = int(k)
+        if k < 1 or k > 8:
+            raise ValueError("BFMatcher.knnMatch: k = %d: the HIP path builds k-NN lists for 1 <= k <= 8" % k)
+        self._check_collection("BFMatcher.knnMatch")
+        if self.crossCheck and len(self._images) > 1:
+            raise ValueError("BFMatcher: crossCheck has no collection form (more than one train image)")
+        if self.normType == NORM_HAMMING and np.asarray(queryDescriptors).dtype != np.uint8 and not isinstance(queryDescriptors, _ffi.Bank):
+            raise ValueError("NORM_HAMMING needs uint8 descriptors (cv2 asserts CV_8U), got %s" % np.asarray(queryDescriptors).dtype)
+        if self.crossCheck and k == 1:
+            tidx, dist = bf_match_arrays(queryDescriptors, self._images[0], k=1, options=dict(self.options, crossCheck=True))
+            return np.where(tidx >= 0, 0, -1).astype(np.int32)[:, None], tidx[:, None], dist[:, None]
+        coll = self.train()
+        qb, tmp = self._query(coll.ctx, queryDescriptors)
+        try:
+            return coll.knn(qb, k)
+        finally:
+            if tmp:
+                qb.close()
+
+    def knnMatchEach_arrays(self, queryDescriptors):
+        """(idx, dist) [n_images, nq, 2]: the 2-NN lists of the query inside every image separately."""
+        self._check_collection("BFMatcher.knnMatchEach")
+        coll = self.train()
+        qb, tmp = self._query(coll.ctx, queryDescriptors)
+        try:
+            return coll.knn2_each(qb)
+        finally:
+            if tmp:
+                qb.close()
+
+    def votes(self, queryDescriptors, tau, mode=0):
+        """int64[n_images]: query rows that pass the ratio test d0 / d1 < tau per image (mode 0: on the 2-NN lists over all
+        images, counted at the first neighbour's image; 1: on every image's own 2-NN lists)."""
+        self._check_collection("BFMatcher.votes")
+        coll = self.train()
+        qb, tmp = self._query(coll.ctx, queryDescriptors)
+        try:
+            return coll.votes(qb, tau, mode)
+        finally:
+            if tmp:
+                qb.close()
+
+    # -- cv2's matching methods ------------------------------------------------------------
+    def knnMatch(self, queryDescriptors, trainDescriptors=None, k=None):
+        if k is None and trainDescriptors is not None and np.isscalar(trainDescriptors):
+            trainDescriptors, k = None, trainDescriptors          # knnMatch(query, k)
+        if k is None:
+            raise TypeError("knnMatch: k is required")
+        if trainDescriptors is not None:
+            return bf_match(queryDescriptors, trainDescriptors, k=k, options=dict(self.options, crossCheck=self.crossCheck))
+        img, idx, dist = self.knnMatch_arrays(queryDescriptors, k)
+        return [[DMatch(qi, idx[qi, j], dist[qi, j], img[qi, j]) for j in range(idx.shape[1]) if idx[qi, j] >= 0]
+                for qi in range(idx.shape[0])]
+
+    def match(self, queryDescriptors, trainDescriptors=None):
+        return [m[0] for m in self.knnMatch(queryDescriptors, trainDescriptors, k=1) if m]
+
+    def radiusMatch(self, queryDescriptors, trainDescriptors=None, maxDistance=None):
+        if maxDistance is None and trainDescriptors is not None and np.isscalar(trainDescriptors):
+            trainDescriptors, maxDistance = None, trainDescriptors
+        if trainDescriptors is None:
+            raise ValueError("BFMatcher.radiusMatch: radiusMatch on a collection is not built; pass a train array")
+        if maxDistance is None:
+            raise TypeError("radiusMatch: maxDistance is required")
+        return bf_radius_match(queryDescriptors, trainDescriptors, maxDistance, options=self.options)
 
 
 # ---- SIFT stays in OpenCV on the host -------------------------------------------------

@@ -46,9 +46,9 @@ typedef struct fm_bank fm_bank;
  * fm_bank_append_f32, fm_expand_set_log / _log_counts / _fetch_log -- and fm_expand_run_lazy refuses to resume a run
  * that did not park; revision 8, r06: additions -- fm_knn, the option "f32_bound_every" -- and rounds[i][5] of the
  * per-round log may be -2; revision 9: additions -- fm_radius_match, the option "radius_ws_bytes"; revision 10: additions --
- * FM_BANK_BIN, fm_bank_create_bin).  A binding
+ * FM_BANK_BIN, fm_bank_create_bin; revision 11: additions -- fm_collection_*).  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.            */
-#define FM_ABI_VERSION 10
+#define FM_ABI_VERSION 11
 int  fm_abi_version(void);
 
 typedef struct fm_stats {
@@ -220,6 +220,76 @@ int  fm_knn(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k,
 int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* radius /*[nq] or NULL*/,
                     float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* idx, float* dist,
                     int64_t* n_total);
+
+/* ---- train collections: one query against many images ------------------------------------------------------------------
+ * cv2.BFMatcher.add([d1, d2, ...]) / train() / clear() and then match(query) / knnMatch(query, k) against ALL added images,
+ * every hit carrying DMatch.imgIdx.  The reference matches image pairs only (matchutil.py:39-43); "which image of my database
+ * does this query match" is the other ordinary use of a brute-force matcher.  An fm_collection is an ordered list of train
+ * images that live on the device in ONE set of arrays, ready for the sweep kernels: every non-empty image starts on a
+ * 128-row stage and ends in proper padding rows (at most 127 rows lost per image; an empty image takes no rows but still
+ * takes an image index), so an image is a bank view the top-2 sweep can reduce over, and the whole allocation is one bank
+ * for the stacked sweep.  Logical order is (image, row) whatever the physical gaps.
+ *   fm_collection_add_u8 / _add_f32: append one image of host rows (rules of fm_bank_create_u8 / _f32; n may be 0).  The
+ *     first non-empty image fixes the width.  Rows are uploaded at the add; arrays grow by doubling with device-to-device
+ *     copies, so images already resident are never uploaded again.  *img_idx (may be NULL) = the image's index.
+ *     A width that does not fit, or a uint8 image after float32 ones (and the reverse), is FM_EINVAL, collection unchanged.
+ *     The first non-empty image fixes the kind: uint8 rows and float32 rows whose values are all integers in 0 .. 255 take
+ *     the integer route (FM_BANK_I8, fm_bank_create_f32's rule), binary rows FM_BANK_BIN.  The first float32 image with
+ *     another value REBUILDS a collection of float32 images on the float32 route (FM_BANK_F32) at that add, on the device,
+ *     from the resident int8 rows (nothing is uploaded again); from then on fm_collection_info reports FM_BANK_F32 and a
+ *     query must be a float32-route bank (fm_bank_create_f32_route for integer-valued rows).  The fp16 planes of all
+ *     images share the power-of-two scale chosen at the rebuild; an image that leaves fp16's range under it (or is not
+ *     finite) switches the fp16 filter off for the collection (the all-pairs float32 kernel alone: same results).
+ *   fm_collection_add_bin: binary rows of 1 .. 64 bytes (rules of fm_bank_create_bin).
+ *   fm_collection_train: makes the device tables (stage -> image, real rows per stage, first row per image) current;
+ *     implicit in the first match after an add.
+ *   fm_collection_locate: HOST code, no context: (image, row) of logical global rows g (first_row[i] = rows of the images
+ *     before i, first_row[n_images] = all rows); -1, or a row outside [0, first_row[n_images]), gives -1 / -1.
+ * Matching; q is an ordinary bank of the collection's kind (another kind, or another width: FM_EINVAL):
+ *   fm_collection_knn, 1 <= k <= 8 (k > 8: FM_EUNSUPPORTED): fm_knn(q, T, k) for T = the images' rows stacked in image
+ *     order, every hit reported as (img, row inside that image).  Lists ascend by (distance as fm_knn2 returns it, img,
+ *     row): the earlier image wins a tie, as OpenCV's per-image batchDistance(..., update) with strict insertion does.
+ *     -1 / -1 / +inf where the whole collection has fewer than k rows.  k = 1, 2: ONE matrix-core sweep over the whole
+ *     allocation (padding rows never beat a real row), the physical row -> (img, row) lookup fused into the merge kernel
+ *     (a table per 128-row stage: no search; k = 1 is the first column of the top-2 sweep); k = 3 .. 8: the vector-ALU kernel, then a lookup pass over the nq * k
+ *     entries (off the hot path).  The float32-root repair above d^2 = 4 197 200 is included.
+ *   fm_collection_knn2_ratio: fm_knn2_ratio over the stacked rows (the classic ratio match against a database).
+ *   fm_collection_knn2_each: the 2-NN of every query row inside every image SEPARATELY -- what
+ *     `for t in images: knnMatch(q, t, 2)` returns, slot by slot equal to fm_knn2(q, image_i): idx / dist
+ *     [n_images][nq][2].  The form retrieval needs: a ratio test against the whole database compares a match with the
+ *     second view of the same object and rejects it.  Up to "batch_group" images share one launch of the batched top-2
+ *     sweep (a block range and a plan per image, any sizes), one merge launch per sweep launch, no host synchronisation
+ *     between launches, one copy out.
+ *   fm_collection_votes: number of query rows that pass d0 / d1 < tau (float64, d1 == 0 rejected, as fm_knn2_ratio) per
+ *     image; mode 0 = the ratio test of the stacked 2-NN list, counted at the image of the first neighbour; 1 = the
+ *     per-image ratio test of fm_collection_knn2_each.  Float32-route and binary collections serve fm_collection_knn2_each
+ *     and mode 1 by enqueuing the per-image sweeps (K8 / K5, K11) back to back inside the call: no host synchronisation
+ *     between images, one copy out.  Counted on the device (integer atomics: deterministic totals);
+ *     only n_images words come back.
+ * Not built: crossCheck on a collection (OpenCV's batchDistance asserts update == 0 under crossCheck -- recalled, SURVEY.md
+ * Appendix A; neither cv2 nor its source was at hand), radiusMatch, masks, the Fast-Match self-distance test and the
+ * expansion loop on a collection, a batched K8 / K11 per-image sweep, sharding a collection across GPUs, removing single
+ * images, turning an integer-route collection of float32 images into a float32-route one for a non-integer QUERY.                                                                    */
+typedef struct fm_collection fm_collection;
+int  fm_collection_create(fm_ctx* ctx, fm_collection** coll);
+int  fm_collection_destroy(fm_ctx* ctx, fm_collection* coll);
+int  fm_collection_clear(fm_ctx* ctx, fm_collection* coll);
+int  fm_collection_add_u8 (fm_ctx* ctx, fm_collection* coll, const uint8_t* rows, int64_t n, int dim, int32_t* img_idx);
+int  fm_collection_add_f32(fm_ctx* ctx, fm_collection* coll, const float* rows, int64_t n, int dim, int32_t* img_idx);
+int  fm_collection_add_bin(fm_ctx* ctx, fm_collection* coll, const uint8_t* rows, int64_t n, int bytes, int32_t* img_idx);
+int  fm_collection_train(fm_ctx* ctx, fm_collection* coll);
+int  fm_collection_info(const fm_collection* coll, int32_t* n_images, int64_t* n_rows_total, int* dim, int* kind);
+int  fm_collection_image_rows(const fm_collection* coll, int64_t* rows /*[n_images]*/);
+int  fm_collection_locate(const int64_t* first_row /*[n_images + 1]*/, int32_t n_images, const int64_t* g /*[m]*/, int64_t m,
+                          int32_t* img /*[m]*/, int64_t* local /*[m]*/);
+int  fm_collection_knn(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, int32_t k,
+                       int32_t* img /*[nq*k]*/, int32_t* idx /*[nq*k]*/, float* dist /*[nq*k]*/);
+int  fm_collection_knn2_ratio(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
+                              int32_t* qidx, int32_t* img, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted);
+int  fm_collection_knn2_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q,
+                             int32_t* idx /*[n_images][nq][2]*/, float* dist /*[n_images][nq][2]*/);
+int  fm_collection_votes(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int32_t mode,
+                         int64_t* votes /*[n_images]*/);
 
 /* Classic Ratio-Match in one call: knnMatch(q, t, k=2) then ratio = m[0].distance /
  * m[1].distance (float64) and ratio < tau  -- Classic Matching.ipynb cell 3 (JSON 59-72), the
