@@ -31,7 +31,6 @@ using namespace fm;
 // masks by INDEX: its sweep and its vector-ALU kernel take the per-stage real-row table (stage_real).
 constexpr int kCollPadNorm = 1 << 26;
 constexpr float kCollPadF32 = 1.0e18f;           // 128 * (1e18)^2 = 1.28e38 stays finite in float32
-constexpr int kCollFixGrid = 1024;
 
 struct fm_collection {
     fm_ctx* ctx = nullptr;
@@ -464,7 +463,7 @@ static int coll_rebuild_f32(fm_ctx* ctx, fm_collection* c, float vmax_new, int64
     for (size_t i = 0; i < c->rows.size(); ++i) {
         const int64_t n = c->rows[i], off = c->phys[i];
         if (n == 0) continue;
-        const int64_t n_pad = ((n + kStageRows - 1) / kStageRows) * kStageRows;
+        const int64_t n_pad = pad128(n);
         hipError_t e = hipMemsetAsync(nb.rowsf + (size_t)off * kDim, 0, (size_t)n_pad * kDim * 4, ctx->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(coll_i8_to_f32_kernel, dim3((unsigned)((n * kDim + 255) / 256)), dim3(256), 0, ctx->stream,
@@ -497,7 +496,7 @@ static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, 
         if (src != c->src) return fail(ctx, FM_EINVAL, std::string(who) + ": uint8, float32 and binary images do not mix in one collection (cv2 raises on the dtype)");
     }
     if (n > 0) {
-        const int64_t n_pad = ((n + kStageRows - 1) / kStageRows) * kStageRows;
+        const int64_t n_pad = pad128(n);
         const int64_t off = c->used;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         int usq = 0;
@@ -511,10 +510,7 @@ static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, 
             const size_t src_bytes = (size_t)n * dim;
             if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, src_bytes + 64)) != FM_OK) return rc;
             HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
-            fm::Bank v = c->stack;
-            v.n = n; v.n_pad = n_pad;
-            v.rowsb = c->stack.rowsb + (size_t)off * v.ksteps * 16;
-            v.rows4 = c->stack.rows4 + (size_t)off * v.ksteps * 64;
+            const fm::Bank v = bank_rows_view(c->stack, off, n);
             HIP_TRY(ctx, launch_hamming_prep((const uint8_t*)ctx->ws_in, n, dim, v, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (ws_in is free for the next upload)
         } else {
@@ -662,52 +658,24 @@ static int coll_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, con
     return fm_collection_train(ctx, c);
 }
 
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline size_t coll_fix_bytes(int64_t rows) { return al256((size_t)rows * 4 + 16); }
-
-// A bank view of image i (rows of the stack's arrays)
+// A bank view of image i (rows of the stack's arrays; nm_max stays the collection's largest norm: an upper bound)
 static fm::Bank coll_view(const fm_collection* c, int i)
 {
-    fm::Bank v = fm::Bank();
-    const fm::Bank& s = c->stack;
-    const int64_t n = c->rows[(size_t)i], p0 = c->phys[(size_t)i];
-    v.kind = s.kind; v.n = n; v.dim = c->dim;
-    v.n_pad = v.cap_pad = ((n + kStageRows - 1) / kStageRows) * kStageRows;
+    fm::Bank v = bank_rows_view(c->stack, c->phys[(size_t)i], c->rows[(size_t)i]);
     v.usq_max = c->usq[(size_t)i];
-    if (s.kind == FM_BANK_F32) {
-        v.rowsf = s.rowsf + (size_t)p0 * kDim; v.rowsh = s.rowsh + (size_t)p0 * kDim; v.normf = s.normf + p0; v.auxf = s.auxf + p0;
-        v.kscale = s.kscale; v.filt_ok = s.filt_ok; v.nm_max = s.nm_max;          // (the collection's largest norm: an upper bound)
-    } else if (s.kind == FM_BANK_BIN) {
-        v.ksteps = s.ksteps;
-        v.rowsb = s.rowsb + (size_t)p0 * s.ksteps * 16; v.rows4 = s.rows4 + (size_t)p0 * s.ksteps * 64;
-    } else {
-        v.rows8 = s.rows8 + (size_t)p0 * kDim; v.norm = s.norm + p0; v.aux = s.aux + (p0 / kTileRows) * kAuxPerTile;
-    }
     return v;
 }
 
-// Top-2 sweep of q over a float32-route or binary bank `t` (the stack with its stage table, or an image's view) and its merge
-// into slot `sl` of the outputs; the keys carry the distance's float32 bits.  Enqueued on the context's stream.
-static int coll_sweep_f32_bin(fm_ctx* ctx, const fm_bank* q, const fm::Bank& t, const int32_t* stage_real, CollTab tab, int64_t out,
-                              int32_t* d_img, int32_t* d_idx, float* d_dist)
+// One-slot merge of a sweep's partials into the lists from entry `out` on (CollSlot::out); ps = null: no reduced rows, every
+// entry -1 / +inf.
+static int coll_merge_one(fm_ctx* ctx, const PairSweep* ps, CollTab tab, int64_t nq, int64_t out, int32_t* d_img, int32_t* d_idx, float* d_dist)
 {
-    const int64_t nq = q->n;
     CollMerge mg{};
     CollSlot& sl = mg.s[0];
-    sl.out = out; sl.fix = nullptr;
-    int rc;
-    if (t.kind == FM_BANK_BIN) {
-        const HamPlan hp = plan_hamming(q->n_pad, t.n_pad);
-        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, hp.partial_bytes(2) + 64)) != FM_OK) return rc;
-        HIP_TRY(ctx, launch_hamming(*q, t, 2, hp, (unsigned long long*)ctx->ws_partial, ctx->stream, stage_real));
-        sl.nsplit = hp.nsplit; sl.ncols_alloc = hp.ncols_alloc;
-    } else {
-        RowReducePlan pl;
-        if ((rc = rowreduce_f32_route(ctx, q, static_cast<const fm_bank*>(&t), 2, &pl)) != FM_OK) return rc;
-        sl.nsplit = pl.nsplit; sl.ncols_alloc = pl.ncols_alloc;
-    }
-    sl.partial = (const unsigned long long*)ctx->ws_partial;
-    hipLaunchKernelGGL(coll_merge2_kernel, dim3((unsigned)((nq + 255) / 256), 1), dim3(256), 0, ctx->stream, mg, tab, nq, d_img, d_idx, d_dist, 1);
+    sl.out = out;
+    if (ps) { sl.partial = ps->partial; sl.nsplit = ps->nsplit; sl.ncols_alloc = ps->ncols_alloc; sl.fix = ps->fix; }
+    hipLaunchKernelGGL(coll_merge2_kernel, dim3((unsigned)((nq + 255) / 256), 1), dim3(256), 0, ctx->stream, mg, tab, nq, d_img, d_idx, d_dist,
+                       ps ? ps->f32_keys : 0);
     HIP_TRY(ctx, hipGetLastError());
     return FM_OK;
 }
@@ -716,49 +684,26 @@ static int coll_sweep_f32_bin(fm_ctx* ctx, const fm_bank* q, const fm::Bank& t, 
 static int coll_knn2_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t* d_img, int32_t* d_idx, float* d_dist)
 {
     const int64_t nq = q->n;
-    CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
-    CollMerge mg{};
-    CollSlot& sl = mg.s[0];
-    sl.out = 0;
-    if (c->total == 0) {
-        sl.partial = nullptr; sl.nsplit = 0; sl.ncols_alloc = 0; sl.fix = nullptr;
-        hipLaunchKernelGGL(coll_merge2_kernel, dim3((unsigned)((nq + 255) / 256), 1), dim3(256), 0, ctx->stream, mg, CollTab{nullptr, nullptr, nullptr},
-                           nq, d_img, d_idx, d_dist, 0);
-        HIP_TRY(ctx, hipGetLastError());
-        return FM_OK;
-    }
+    const CollTab none{nullptr, nullptr, nullptr};
+    if (c->total == 0) return coll_merge_one(ctx, nullptr, none, nq, 0, d_img, d_idx, d_dist);
+    const CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
     const fm::Bank& t = c->stack;
+    const bool i8 = t.kind == FM_BANK_I8;
+    // (the pairs are the real rows'; the stack's padding rows are swept and read like any bank's)
     ctx->pending_pairs += nq * c->total;
-    if (t.kind != FM_BANK_I8) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-        int rc = coll_sweep_f32_bin(ctx, q, t, c->st_real(), tab, 0, d_img, d_idx, d_dist);
-        if (rc != FM_OK) return rc;
+    ctx->pending_bytes += bank_bytes(q) + bank_bytes(&t);
+    // the float32 route and K11: the bracket takes the merge in
+    PairSweep ps;
+    int rc;
+    if (!i8) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+    if ((rc = sweep_pair(ctx, *q, t, 2, nq, nullptr, i8 ? nullptr : c->st_real(), kSweepNoCount | (i8 ? 0u : kSweepNoEvents), &ps)) != FM_OK) return rc;
+    if ((rc = coll_merge_one(ctx, &ps, tab, nq, 0, d_img, d_idx, d_dist)) != FM_OK) return rc;
+    if (!i8) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
         ctx->kernel_timed = true;
-        ctx->pending_bytes += bank_bytes(q) + bank_bytes(static_cast<const fm_bank*>(&t));
-        return FM_OK;
     }
-    const RowReducePlan pl = plan_rowreduce(q->n_pad, t.n_pad, ctx->tune);
-    const size_t pbytes = al256(pl.partial_bytes(2)), bbytes = al256(pl.bound_bytes());
-    int rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, pbytes + bbytes + coll_fix_bytes(nq));
-    if (rc != FM_OK) return rc;
-    int* d_bound = nullptr;
-    if (ctx->tune.coop != 0 && pl.nsplit > 1) {
-        d_bound = (int*)((char*)ctx->ws_partial + pbytes);
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)d_bound, (int)0x80000000, (size_t)pl.ncols_alloc * 2, ctx->stream));
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-    HIP_TRY(ctx, launch_rowreduce(*q, t, 2, pl, (unsigned long long*)ctx->ws_partial, d_bound, ctx->tune.glds != 0, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
-    ctx->kernel_timed = true;
-    ctx->pending_bytes += bank_bytes(q) + c->used * 128;
-    unsigned* d_fix = sqrt_tie_possible(*q, t) ? (unsigned*)((char*)ctx->ws_partial + pbytes + bbytes) : nullptr;
-    if (d_fix) HIP_TRY(ctx, hipMemsetAsync(d_fix, 0, 16, ctx->stream));
-    sl.partial = (const unsigned long long*)ctx->ws_partial; sl.nsplit = pl.nsplit; sl.ncols_alloc = pl.ncols_alloc; sl.fix = d_fix;
-    hipLaunchKernelGGL(coll_merge2_kernel, dim3((unsigned)((nq + 255) / 256), 1), dim3(256), 0, ctx->stream, mg, tab, nq, d_img, d_idx, d_dist, 0);
-    HIP_TRY(ctx, hipGetLastError());
-    if (d_fix) {
-        hipLaunchKernelGGL(coll_sqrt_fix_kernel, dim3(kCollFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)d_fix,
+    if (ps.fix) {
+        hipLaunchKernelGGL(coll_sqrt_fix_kernel, dim3(kFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)ps.fix,
                            (const int8_t*)q->rows8, (const int32_t*)q->norm, (const int8_t*)t.rows8, (const int32_t*)t.norm, (int)t.n,
                            tab, (int64_t)0, d_img, d_idx, d_dist);
         HIP_TRY(ctx, hipGetLastError());
@@ -777,7 +722,7 @@ extern "C" int fm_collection_knn(fm_ctx* ctx, fm_collection* c, const fm_bank* q
     if (nq == 0) return FM_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int kk = k < 2 ? 2 : k;
-    const size_t ob = al256((size_t)nq * kk * 4), cb = al256((size_t)nq * 4);
+    const size_t ob = align256((size_t)nq * kk * 4), cb = align256((size_t)nq * 4);
     if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, 3 * ob + 3 * cb + 64)) != FM_OK) return rc;
     char* b = (char*)ctx->ws_out;
     int32_t* d_img = (int32_t*)b; int32_t* d_idx = (int32_t*)(b + ob); float* d_dist = (float*)(b + 2 * ob);
@@ -835,12 +780,11 @@ extern "C" int fm_collection_knn2_ratio(fm_ctx* ctx, fm_collection* c, const fm_
     const int nblk = (int)((nq + 255) / 256);
     const int64_t ccap = cap < nq ? cap : nq;
     size_t off = 0;
-    auto carve = [&](size_t b) { size_t o = off; off += al256(b); return o; };
-    const size_t o_m2 = carve((size_t)nq * 8), o_i2 = carve((size_t)nq * 8), o_d2 = carve((size_t)nq * 8);
-    const size_t o_ti = carve((size_t)nq * 4), o_di = carve((size_t)nq * 4), o_ra = carve((size_t)nq * 8);
-    const size_t o_pa = carve((size_t)nq), o_bc = carve((size_t)nblk * 4), o_cnt = carve(16);
-    const size_t o_cq = carve((size_t)ccap * 4), o_ct = carve((size_t)ccap * 4), o_cm = carve((size_t)ccap * 4);
-    const size_t o_cd = carve((size_t)ccap * 4), o_cr = carve((size_t)ccap * 8);
+    const size_t o_m2 = carve(off, (size_t)nq * 8), o_i2 = carve(off, (size_t)nq * 8), o_d2 = carve(off, (size_t)nq * 8);
+    const size_t o_ti = carve(off, (size_t)nq * 4), o_di = carve(off, (size_t)nq * 4), o_ra = carve(off, (size_t)nq * 8);
+    const size_t o_pa = carve(off, (size_t)nq), o_bc = carve(off, (size_t)nblk * 4), o_cnt = carve(off, 16);
+    const size_t o_cq = carve(off, (size_t)ccap * 4), o_ct = carve(off, (size_t)ccap * 4), o_cm = carve(off, (size_t)ccap * 4);
+    const size_t o_cd = carve(off, (size_t)ccap * 4), o_cr = carve(off, (size_t)ccap * 8);
     if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
     char* b = (char*)ctx->ws_out;
     CallScope cs(ctx);
@@ -884,20 +828,12 @@ static int coll_each_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int
         // merge -- one stream, one workspace, no host synchronisation between images
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
         for (int i = 0; i < ni; ++i) {
-            const fm_bank v = fm_bank{coll_view(c, i)};
+            const fm::Bank v = coll_view(c, i);
+            PairSweep ps;
             int rc;
-            if (v.n == 0) {
-                CollMerge mg{};
-                mg.s[0].out = (int64_t)i * nq;
-                hipLaunchKernelGGL(coll_merge2_kernel, dim3((unsigned)((nq + 255) / 256), 1), dim3(256), 0, ctx->stream, mg,
-                                   CollTab{nullptr, nullptr, nullptr}, nq, (int32_t*)nullptr, d_idx, d_dist, 1);
-                HIP_TRY(ctx, hipGetLastError());
-                continue;
-            }
-            if ((rc = coll_sweep_f32_bin(ctx, q, v, nullptr, CollTab{nullptr, nullptr, nullptr}, (int64_t)i * nq, nullptr, d_idx, d_dist)) != FM_OK)
+            if (v.n > 0 && (rc = sweep_pair(ctx, *q, v, 2, 0, nullptr, nullptr, kSweepNoEvents, &ps)) != FM_OK) return rc;
+            if ((rc = coll_merge_one(ctx, v.n > 0 ? &ps : nullptr, CollTab{nullptr, nullptr, nullptr}, nq, (int64_t)i * nq, nullptr, d_idx, d_dist)) != FM_OK)
                 return rc;
-            ctx->pending_pairs += nq * v.n;
-            ctx->pending_bytes += bank_bytes(q) + bank_bytes(&v);
         }
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
         ctx->kernel_timed = true;
@@ -910,15 +846,15 @@ static int coll_each_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int
     shaped.nb = 4; shaped.nw = 8; shaped.nbuf = 0; shaped.nsplit = 0; shaped.k1_order = 0;
     // workspace of one launch: per slot partial | bounds | fix list, sized for the largest image
     int64_t max_pad = kStageRows;
-    for (int i = 0; i < ni; ++i) max_pad = std::max<int64_t>(max_pad, ((c->rows[(size_t)i] + kStageRows - 1) / kStageRows) * kStageRows);
+    for (int i = 0; i < ni; ++i) max_pad = std::max<int64_t>(max_pad, pad128(c->rows[(size_t)i]));
     const RowReducePlan big = plan_rowreduce(q->n_pad, max_pad, shaped);
     size_t slot_p = 0;
     for (int i = 0; i < ni; ++i) {           // (the split count is not monotonic in the image size: take the maximum)
         if (c->rows[(size_t)i] == 0) continue;
-        const RowReducePlan p = plan_rowreduce(q->n_pad, ((c->rows[(size_t)i] + kStageRows - 1) / kStageRows) * kStageRows, shaped);
-        slot_p = std::max(slot_p, al256(p.partial_bytes(2)));
+        const RowReducePlan p = plan_rowreduce(q->n_pad, pad128(c->rows[(size_t)i]), shaped);
+        slot_p = std::max(slot_p, align256(p.partial_bytes(2)));
     }
-    const size_t slot_b = al256(big.bound_bytes()), slot_f = coll_fix_bytes(nq);
+    const size_t slot_b = align256(big.bound_bytes()), slot_f = align256(fix_bytes(nq));
     const size_t slot = slot_p + slot_b + slot_f;
     int rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, slot * (size_t)group + 64);
     if (rc != FM_OK) return rc;
@@ -971,7 +907,7 @@ static int coll_each_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int
         for (int l = 0; l < nl; ++l) {
             const CollSlot& sl = mg.s[slot_of[l]];
             if (!sl.fix) continue;
-            hipLaunchKernelGGL(coll_sqrt_fix_kernel, dim3(kCollFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)sl.fix,
+            hipLaunchKernelGGL(coll_sqrt_fix_kernel, dim3(kFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)sl.fix,
                                (const int8_t*)q->rows8, (const int32_t*)q->norm, (const int8_t*)views[l].rows8, (const int32_t*)views[l].norm,
                                (int)views[l].n, CollTab{nullptr, nullptr, nullptr}, sl.out, (int32_t*)nullptr, d_idx, d_dist);
             HIP_TRY(ctx, hipGetLastError());
@@ -992,7 +928,7 @@ extern "C" int fm_collection_knn2_each(fm_ctx* ctx, fm_collection* c, const fm_b
     if (nq == 0 || ni == 0) return FM_OK;
     if (!idx || !dist) return fail(ctx, FM_EINVAL, "fm_collection_knn2_each: output pointer is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t ob = al256((size_t)ni * nq * 8);
+    const size_t ob = align256((size_t)ni * nq * 8);
     if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, 2 * ob + 64)) != FM_OK) return rc;
     int32_t* d_idx = (int32_t*)ctx->ws_out;
     float* d_dist = (float*)((char*)ctx->ws_out + ob);
@@ -1019,8 +955,8 @@ extern "C" int fm_collection_votes(fm_ctx* ctx, fm_collection* c, const fm_bank*
     for (int64_t i = 0; i < ni; ++i) votes[i] = 0;
     if (nq == 0) return FM_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t vb = al256((size_t)ni * 8);
-    const size_t lb = al256((size_t)(mode == 0 ? 1 : ni) * nq * 8);
+    const size_t vb = align256((size_t)ni * 8);
+    const size_t lb = align256((size_t)(mode == 0 ? 1 : ni) * nq * 8);
     if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, vb + 3 * lb + 64)) != FM_OK) return rc;
     char* b = (char*)ctx->ws_out;
     unsigned long long* d_votes = (unsigned long long*)b;

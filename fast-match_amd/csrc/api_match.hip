@@ -524,27 +524,92 @@ int rowreduce_f32_route(fm_ctx* ctx, const fm_bank* cols, const fm_bank* red, in
 }
 
 // ---------------------------------------------------------------------------------------
+// one bank pair on the context's stream: every synchronous entry point's sweep (ctx_internal.h)
+// ---------------------------------------------------------------------------------------
+int sweep_pair_plan(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, int64_t fix_rows, PairSweep* out)
+{
+    PairSweep ps{};
+    size_t off = 0;
+    if (cols.kind == FM_BANK_BIN) {
+        ps.ham = plan_hamming(cols.n_pad, red.n_pad);
+        ps.nsplit = ps.ham.nsplit; ps.ncols_alloc = ps.ham.ncols_alloc; ps.f32_keys = 1;
+        carve(off, ps.ham.partial_bytes(ktop));
+    } else {
+        ps.rr = plan_rowreduce(cols.n_pad, red.n_pad, ctx->tune);
+        ps.nsplit = ps.rr.nsplit; ps.ncols_alloc = ps.rr.ncols_alloc; ps.f32_keys = 0;
+        carve(off, ps.rr.partial_bytes(ktop));
+    }
+    const bool coop = cols.kind == FM_BANK_I8 && ctx->tune.coop != 0 && ps.nsplit > 1;
+    const bool ties = cols.kind == FM_BANK_I8 && fix_rows > 0 && sqrt_tie_possible(cols, red);
+    const size_t o_bound = coop ? carve(off, ps.rr.bound_bytes()) : 0;
+    const size_t o_fix = ties ? carve(off, fix_bytes(fix_rows)) : 0;
+    int rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, off + 64);
+    if (rc != FM_OK) return rc;
+    ps.partial = (const unsigned long long*)ctx->ws_partial;
+    ps.bound = coop ? (int*)((char*)ctx->ws_partial + o_bound) : nullptr;
+    ps.fix = ties ? (unsigned*)((char*)ctx->ws_partial + o_fix) : nullptr;
+    *out = ps;
+    return FM_OK;
+}
+
+int sweep_pair_run(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, const unsigned* cut, const int* stage_real,
+                   unsigned flags, const PairSweep& ps)
+{
+    const bool events = !(flags & kSweepNoEvents);
+    if (events) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+    if (cols.kind == FM_BANK_BIN)
+        HIP_TRY(ctx, launch_hamming(cols, red, ktop, ps.ham, (unsigned long long*)ctx->ws_partial, ctx->stream, stage_real));
+    else
+        HIP_TRY(ctx, launch_rowreduce(cols, red, ktop, ps.rr, (unsigned long long*)ctx->ws_partial, ps.bound, ctx->tune.glds != 0, ctx->stream, cut));
+    if (events) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+        ctx->kernel_timed = true;
+    }
+    return FM_OK;
+}
+
+int sweep_pair(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, int64_t fix_rows, const unsigned* cut,
+               const int* stage_real, unsigned flags, PairSweep* out)
+{
+    int rc;
+    if (cols.kind == FM_BANK_F32) {
+        // (K5's layout has neither shared bounds nor a tie list behind it, and needs none; the route records ev_k0 / ev_k1 itself)
+        RowReducePlan pl;
+        if ((rc = rowreduce_f32_route(ctx, static_cast<const fm_bank*>(&cols), static_cast<const fm_bank*>(&red), ktop, &pl)) != FM_OK) return rc;
+        *out = PairSweep{};
+        out->partial = (const unsigned long long*)ctx->ws_partial;
+        out->nsplit = pl.nsplit; out->ncols_alloc = pl.ncols_alloc; out->f32_keys = 1;
+        if (!(flags & kSweepNoEvents)) ctx->kernel_timed = true;
+    } else {
+        if ((rc = sweep_pair_plan(ctx, cols, red, ktop, fix_rows, out)) != FM_OK) return rc;
+        if (out->bound && !ablate_keep_bounds())
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)out->bound, (int)0x80000000, (size_t)ktop * out->ncols_alloc, ctx->stream));
+        if (out->fix) HIP_TRY(ctx, hipMemsetAsync(out->fix, 0, 16, ctx->stream));
+        if ((rc = sweep_pair_run(ctx, cols, red, ktop, cut, stage_real, flags, *out)) != FM_OK) return rc;
+    }
+    if (!(flags & kSweepNoCount)) {
+        ctx->pending_pairs += cols.n * red.n;
+        ctx->pending_bytes += bank_bytes(&cols) + bank_bytes(&red);
+    }
+    return FM_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // float32-root ties of the integer route (tile_ops.h: kSqrtTieMin)
 // ---------------------------------------------------------------------------------------
-constexpr int kFixGrid = 1024;                 // workgroups of a sqrt_fix_kernel launch (each walks the list)
-static inline size_t fix_bytes(int64_t rows) { return ((size_t)rows * 4 + 16 + 15) & ~(size_t)15; }
-
-// Election of the cross-check on stream s: per train row the minimum over K1's split partials, scatter-min
-// into qbest; for bank pairs whose norms allow d2 >= kSqrtTieMin, the listed rows are then redone exactly.
-// fix: device words [4 + nt] (only touched for such pairs).
+// Election of the cross-check on stream s: per train row the minimum over the sweep's split partials ([nsplit][ncols_alloc]
+// top-1 keys; f32_keys: PairSweep's), scatter-min into qbest; the rows the scatter lists in fix are then redone exactly.
+// fix: zeroed tie list of nt rows for an integer-route pair whose norms allow d2 >= kSqrtTieMin, else null.
 static int enqueue_election(fm_ctx* ctx, hipStream_t s, const fm_bank* q, const fm_bank* t,
-                            const unsigned long long* partial, const RowReducePlan& pl,
+                            const unsigned long long* partial, int nsplit, int ncols_alloc, int f32_keys,
                             unsigned long long* qbest, unsigned t_offset, int* bound_reset, unsigned* fix)
 {
     const int64_t nt = t->n;
-    const int f32 = q->kind == FM_BANK_F32;
-    const bool guard = !f32 && fix && sqrt_tie_possible(*q, *t);
-    if (guard) HIP_TRY(ctx, hipMemsetAsync(fix, 0, 16, s));
-    const int64_t sthreads = (bound_reset && (int64_t)pl.ncols_alloc > nt * 4) ? (int64_t)pl.ncols_alloc : nt * 4;
+    const int64_t sthreads = (bound_reset && (int64_t)ncols_alloc > nt * 4) ? (int64_t)ncols_alloc : nt * 4;
     hipLaunchKernelGGL(xcheck_scatter_kernel, dim3((unsigned)((sthreads + 255) / 256)), dim3(256), 0, s,
-                       partial, pl.nsplit, pl.ncols_alloc, nt, qbest, t_offset, f32, bound_reset, guard ? fix : (unsigned*)nullptr);
+                       partial, nsplit, ncols_alloc, nt, qbest, t_offset, f32_keys, bound_reset, fix);
     HIP_TRY(ctx, hipGetLastError());
-    if (guard) {
+    if (fix) {
         hipLaunchKernelGGL(sqrt_fix_kernel<1>, dim3(kFixGrid), dim3(256), 0, s, (const unsigned*)fix,
                            (const int8_t*)t->rows8, (const int32_t*)t->norm, (const int8_t*)q->rows8, (const int32_t*)q->norm,
                            (int)q->n, qbest, t_offset, (int32_t*)nullptr, (float*)nullptr);
@@ -623,68 +688,45 @@ int fm::round_xcheck_dense(fm_ctx* ctx, const Bank& q, const int32_t* d_rows, in
                            unsigned long long* d_qbest)
 {
     if (nq <= 0 || nt <= 0) return FM_OK;
-    const int64_t nq_pad = ((nq + kStageRows - 1) / kStageRows) * kStageRows;
+    const int64_t nq_pad = pad128(nq);
+    // the gathered rows as a bank in ws_out, and the cell's rows as a bank of their own: a view into the target bank (rows
+    // past nt are other cells' rows or padding; what the sweep computes for them is never looked at).  The view is the
+    // output side: its aux words are not read, and t0 need not sit on a tile.
+    Bank gq, tv = bank_rows_view(t, t0, nt);
+    tv.aux = nullptr;
+    gq.kind = q.kind; gq.n = nq; gq.dim = q.dim; gq.n_pad = gq.cap_pad = nq_pad;
     size_t off = 0;
-    auto carve = [&](size_t b) { size_t o = off; off += (b + 255) & ~(size_t)255; return o; };
+    int rc;
+    PairSweep ps;
     if (q.kind == FM_BANK_F32) {
         // float32 banks: the gathered rows in the float32 layout, then the float32 route's own cross-check (fp16 filter +
         // exact rescoring, or all pairs for small rounds: rowreduce_f32_route) with the cell's rows as output rows
-        const size_t o_f = carve((size_t)nq_pad * kDim * 4), o_h = carve((size_t)nq_pad * kDim * 2), o_n = carve((size_t)nq_pad * 4),
-                     o_a = carve((size_t)nq_pad * 4);
-        int rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64);
-        if (rc != FM_OK) return rc;
+        const size_t o_f = carve(off, (size_t)nq_pad * kDim * 4), o_h = carve(off, (size_t)nq_pad * kDim * 2),
+                     o_n = carve(off, (size_t)nq_pad * 4), o_a = carve(off, (size_t)nq_pad * 4);
+        if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
         char* b = (char*)ctx->ws_out;
-        fm_bank gq, tv;
-        gq.kind = FM_BANK_F32; gq.n = nq; gq.dim = q.dim; gq.n_pad = nq_pad; gq.cap_pad = nq_pad;
         gq.rowsf = (float*)(b + o_f); gq.rowsh = (uint16_t*)(b + o_h); gq.normf = (float*)(b + o_n); gq.auxf = (float*)(b + o_a);
         gq.nm_max = q.nm_max; gq.kscale = q.kscale; gq.filt_ok = q.filt_ok;
         hipLaunchKernelGGL(gather_rows_f32_kernel, dim3((unsigned)(nq_pad / 16)), dim3(256), 0, ctx->stream, d_rows, nq,
                            (const float*)q.rowsf, (const uint16_t*)q.rowsh, (const float*)q.normf, (const float*)q.auxf,
                            gq.rowsf, gq.rowsh, gq.normf, gq.auxf, d_qbest);
         HIP_TRY(ctx, hipGetLastError());
-        tv.kind = FM_BANK_F32; tv.n = nt; tv.dim = t.dim;
-        tv.n_pad = ((nt + kStageRows - 1) / kStageRows) * kStageRows;
-        const int64_t room = (t.cap_pad > 0 ? t.cap_pad : t.n_pad) - t0;
-        if (tv.n_pad > room) tv.n_pad = room;
-        tv.cap_pad = tv.n_pad;
-        tv.rowsf = t.rowsf + (size_t)t0 * kDim; tv.rowsh = t.rowsh ? t.rowsh + (size_t)t0 * kDim : nullptr;
-        tv.normf = t.normf ? t.normf + t0 : nullptr; tv.auxf = t.auxf ? t.auxf + t0 : nullptr;
-        tv.nm_max = t.nm_max; tv.kscale = t.kscale; tv.filt_ok = t.filt_ok;
-        RowReducePlan pl;
-        if ((rc = rowreduce_f32_route(ctx, &tv, &gq, 1, &pl)) != FM_OK) return rc;
-        const int64_t sthreads = nt * 4;
-        hipLaunchKernelGGL(xcheck_scatter_kernel, dim3((unsigned)((sthreads + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const unsigned long long*)ctx->ws_partial, pl.nsplit, pl.ncols_alloc, nt, d_qbest, 0u, 1, (int*)nullptr, (unsigned*)nullptr);
+        if ((rc = sweep_pair(ctx, tv, gq, 1, 0, nullptr, nullptr, kSweepNoEvents | kSweepNoCount, &ps)) != FM_OK) return rc;
+    } else {
+        const size_t o_rows = carve(off, (size_t)nq_pad * kDim), o_norm = carve(off, (size_t)nq_pad * 4),
+                     o_aux = carve(off, (size_t)(nq_pad / kTileRows) * kAuxPerTile * 4);
+        if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
+        char* b = (char*)ctx->ws_out;
+        gq.rows8 = (int8_t*)(b + o_rows); gq.norm = (int32_t*)(b + o_norm); gq.aux = (int32_t*)(b + o_aux);
+        // (the gather re-arms K1's shared bounds itself: the sweep in its two halves around it)
+        if ((rc = sweep_pair_plan(ctx, tv, gq, 1, 0, &ps)) != FM_OK) return rc;
+        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(nq_pad / kTileRows)), dim3(256), 0, ctx->stream, d_rows, nq,
+                           (const int8_t*)q.rows8, (const int32_t*)q.norm, gq.rows8, gq.norm, gq.aux, d_qbest, ps.bound, (int64_t)ps.ncols_alloc);
         HIP_TRY(ctx, hipGetLastError());
-        return FM_OK;
+        if ((rc = sweep_pair_run(ctx, tv, gq, 1, nullptr, nullptr, kSweepNoEvents, ps)) != FM_OK) return rc;
     }
-    const size_t o_rows = carve((size_t)nq_pad * kDim), o_norm = carve((size_t)nq_pad * 4), o_aux = carve((size_t)(nq_pad / kTileRows) * kAuxPerTile * 4);
-    int rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64);
-    if (rc != FM_OK) return rc;
-    char* b = (char*)ctx->ws_out;
-    Bank gq;
-    gq.kind = FM_BANK_I8; gq.n = nq; gq.dim = q.dim; gq.n_pad = nq_pad; gq.cap_pad = nq_pad;
-    gq.rows8 = (int8_t*)(b + o_rows); gq.norm = (int32_t*)(b + o_norm); gq.aux = (int32_t*)(b + o_aux);
-    // the cell's rows as a bank of their own: a view into the target bank (rows past nt are other cells' rows or padding;
-    // what K1 computes for them is never looked at)
-    Bank tv;
-    tv.kind = FM_BANK_I8; tv.n = nt; tv.dim = t.dim;
-    tv.n_pad = ((nt + kStageRows - 1) / kStageRows) * kStageRows;
-    const int64_t room = (t.cap_pad > 0 ? t.cap_pad : t.n_pad) - t0;
-    if (tv.n_pad > room) tv.n_pad = room;
-    tv.cap_pad = tv.n_pad;
-    tv.rows8 = t.rows8 + (size_t)t0 * kDim; tv.norm = t.norm + t0; tv.aux = nullptr;
-    const RowReducePlan pl = plan_rowreduce(tv.n_pad, gq.n_pad, ctx->tune);
-    const size_t pbytes = (pl.partial_bytes(1) + 255) & ~(size_t)255;
-    if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, pbytes + pl.bound_bytes() + 64)) != FM_OK) return rc;
-    int* d_bound = ((ctx->tune.coop != 0) && pl.nsplit > 1) ? (int*)((char*)ctx->ws_partial + pbytes) : nullptr;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(nq_pad / kTileRows)), dim3(256), 0, ctx->stream, d_rows, nq,
-                       (const int8_t*)q.rows8, (const int32_t*)q.norm, gq.rows8, gq.norm, gq.aux, d_qbest, d_bound, (int64_t)pl.ncols_alloc);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, launch_rowreduce(tv, gq, 1, pl, (unsigned long long*)ctx->ws_partial, d_bound, (ctx->tune.glds != 0), ctx->stream));
-    const int64_t sthreads = nt * 4;
-    hipLaunchKernelGGL(xcheck_scatter_kernel, dim3((unsigned)((sthreads + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long*)ctx->ws_partial, pl.nsplit, pl.ncols_alloc, nt, d_qbest, 0u, 0, (int*)nullptr, (unsigned*)nullptr);
+    hipLaunchKernelGGL(xcheck_scatter_kernel, dim3((unsigned)((nt * 4 + 255) / 256)), dim3(256), 0, ctx->stream,
+                       ps.partial, ps.nsplit, ps.ncols_alloc, nt, d_qbest, 0u, ps.f32_keys, (int*)nullptr, (unsigned*)nullptr);
     HIP_TRY(ctx, hipGetLastError());
     return FM_OK;
 }
@@ -692,66 +734,23 @@ int fm::round_xcheck_dense(fm_ctx* ctx, const Bank& q, const int32_t* d_rows, in
 // ---------------------------------------------------------------------------------------
 // K2 entry points
 // ---------------------------------------------------------------------------------------
-// K11: 2-NN of a binary pair (hamming.hip) -- the top-2 sweep on the FP4 matrix cores, merged by knn2_merge_kernel on the
-// float32-route layout (the partial keys carry the float32 bits of the integer Hamming distance: exact, no root ties).
-static int knn2_bin_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* d_idx, float* d_dist)
-{
-    const int64_t nq = q->n;
-    const HamPlan hp = plan_hamming(q->n_pad, t->n_pad);
-    int rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, hp.partial_bytes(2) + 64);
-    if (rc != FM_OK) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-    HIP_TRY(ctx, launch_hamming(*q, *t, 2, hp, (unsigned long long*)ctx->ws_partial, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
-    ctx->kernel_timed = true;
-    ctx->pending_pairs += nq * t->n;
-    ctx->pending_bytes += bank_bytes(q) + bank_bytes(t);
-    hipLaunchKernelGGL(knn2_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long*)ctx->ws_partial, hp.nsplit, hp.ncols_alloc, nq, d_idx, d_dist, 1, (unsigned*)nullptr);
-    HIP_TRY(ctx, hipGetLastError());
-    return FM_OK;
-}
-
-// Device-side knn2 into d_idx/d_dist (device pointers).
+// Device-side knn2 into d_idx/d_dist (device pointers): the top-2 sweep of the pair's route (K2, K8 / K5, K11 on the FP4
+// matrix cores -- its keys carry the float32 bits of the integer Hamming distance: exact, no root ties), merged by
+// knn2_merge_kernel.
 static int knn2_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* d_idx, float* d_dist)
 {
     const int64_t nq = q->n;
     if (nq == 0) return FM_OK;
-    const int f32 = q->kind == FM_BANK_F32;
-    if (t->n == 0) {                                     // no train rows: every slot is (-1, +inf)
-        hipLaunchKernelGGL(knn2_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const unsigned long long*)nullptr, 0, 0, nq, d_idx, d_dist, f32);
-        HIP_TRY(ctx, hipGetLastError());
-        return FM_OK;
-    }
-    if (q->kind == FM_BANK_BIN) return knn2_bin_device(ctx, q, t, d_idx, d_dist);
-    RowReducePlan pl;
+    PairSweep ps{};                                      // (no train rows: no partials, every slot is (-1, +inf))
+    ps.f32_keys = q->kind == FM_BANK_F32;
     int rc;
-    if (f32) {
-        if ((rc = rowreduce_f32_route(ctx, q, t, 2, &pl)) != FM_OK) return rc;
-    } else {
-        pl = plan_rowreduce(q->n_pad, t->n_pad, ctx->tune);
-        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, pl.partial_bytes(2) + pl.bound_bytes() + fix_bytes(nq))) != FM_OK) return rc;
-        int* d_bound = nullptr;
-        if ((ctx->tune.coop != 0) && pl.nsplit > 1) {
-            d_bound = (int*)((char*)ctx->ws_partial + pl.partial_bytes(2));      // bound1 | bound2 (rowreduce.hip)
-            if (!ablate_keep_bounds()) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)d_bound, (int)0x80000000, (size_t)pl.ncols_alloc * 2, ctx->stream));
-        }
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-        HIP_TRY(ctx, launch_rowreduce(*q, *t, 2, pl, (unsigned long long*)ctx->ws_partial, d_bound, (ctx->tune.glds != 0), ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
-    }
-    ctx->kernel_timed = true;
-    ctx->pending_pairs += nq * t->n;
-    ctx->pending_bytes += bank_bytes(q) + bank_bytes(t);
-    // (output rows whose second best d2 reaches kSqrtTieMin are redone in OpenCV's float32 order)
-    unsigned* d_fix = (!f32 && sqrt_tie_possible(*q, *t)) ? (unsigned*)((char*)ctx->ws_partial + pl.partial_bytes(2) + pl.bound_bytes()) : nullptr;
-    if (d_fix) HIP_TRY(ctx, hipMemsetAsync(d_fix, 0, 16, ctx->stream));
+    // (output rows whose second best d2 reaches kSqrtTieMin are listed in ps.fix and redone in OpenCV's float32 order)
+    if (t->n > 0 && (rc = sweep_pair(ctx, *q, *t, 2, nq, nullptr, nullptr, 0, &ps)) != FM_OK) return rc;
     hipLaunchKernelGGL(knn2_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long*)ctx->ws_partial, pl.nsplit, pl.ncols_alloc, nq, d_idx, d_dist, f32, d_fix);
+                       ps.partial, ps.nsplit, ps.ncols_alloc, nq, d_idx, d_dist, ps.f32_keys, ps.fix);
     HIP_TRY(ctx, hipGetLastError());
-    if (d_fix) {
-        hipLaunchKernelGGL(sqrt_fix_kernel<2>, dim3(kFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)d_fix,
+    if (ps.fix) {
+        hipLaunchKernelGGL(sqrt_fix_kernel<2>, dim3(kFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)ps.fix,
                            (const int8_t*)q->rows8, (const int32_t*)q->norm, (const int8_t*)t->rows8, (const int32_t*)t->norm,
                            (int)t->n, (unsigned long long*)nullptr, 0u, d_idx, d_dist);
         HIP_TRY(ctx, hipGetLastError());
@@ -853,10 +852,9 @@ extern "C" int fm_knn2_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, do
     const int64_t ccap = cap < nq ? cap : nq;
     // knn lists | per-q tidx, dist, ratio, pass | block counts, count | compacted outputs
     size_t off = 0;
-    auto carve = [&](size_t b) { size_t o = off; off += (b + 15) & ~(size_t)15; return o; };
-    const size_t o_i2 = carve((size_t)nq * 8), o_d2 = carve((size_t)nq * 8), o_ti = carve((size_t)nq * 4), o_di = carve((size_t)nq * 4);
-    const size_t o_ra = carve((size_t)nq * 8), o_pa = carve((size_t)nq), o_bc = carve((size_t)nblk * 4), o_cnt = carve(16);
-    const size_t o_cq = carve((size_t)ccap * 4), o_ct = carve((size_t)ccap * 4), o_cd = carve((size_t)ccap * 4), o_cr = carve((size_t)ccap * 8);
+    const size_t o_i2 = carve(off, (size_t)nq * 8, 16), o_d2 = carve(off, (size_t)nq * 8, 16), o_ti = carve(off, (size_t)nq * 4, 16), o_di = carve(off, (size_t)nq * 4, 16);
+    const size_t o_ra = carve(off, (size_t)nq * 8, 16), o_pa = carve(off, (size_t)nq, 16), o_bc = carve(off, (size_t)nblk * 4, 16), o_cnt = carve(off, 16, 16);
+    const size_t o_cq = carve(off, (size_t)ccap * 4, 16), o_ct = carve(off, (size_t)ccap * 4, 16), o_cd = carve(off, (size_t)ccap * 4, 16), o_cr = carve(off, (size_t)ccap * 8, 16);
     if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
     char* b = (char*)ctx->ws_out;
     CallScope cs(ctx);
@@ -1209,7 +1207,9 @@ static int enqueue_tail(fm_ctx* ctx, hipStream_t ts, fm_ctx::AsyncSlot& sl, cons
     uint8_t* s_pass = (uint8_t*)(sb + L.a_pass);
     int* s_bc = (int*)(sb + L.a_bc);
     if (nt > 0) {
-        int rc = enqueue_election(ctx, ts, q, t, s_partial, pl, s_qbest, 0u, s_bound, (unsigned*)(sb + L.a_fix));
+        unsigned* s_fix = sqrt_tie_possible(*q, *t) ? (unsigned*)(sb + L.a_fix) : nullptr;      // (integer-route pairs only get here)
+        if (s_fix) HIP_TRY(ctx, hipMemsetAsync(s_fix, 0, 16, ts));
+        int rc = enqueue_election(ctx, ts, q, t, s_partial, pl.nsplit, pl.ncols_alloc, 0, s_qbest, 0u, s_bound, s_fix);
         if (rc != FM_OK) return rc;
     }
     hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ts,
@@ -1271,22 +1271,15 @@ static int xcheck_common(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, bool w
     uint8_t* d_pass = (uint8_t*)(base + o_pass);
     unsigned long long* d_cnt = (unsigned long long*)(base + o_cnt);
 
-    // reverse NN: output rows = train rows, reduced over the query rows
-    RowReducePlan pl;
-    int* d_bound = nullptr;
-    if (!f32) {
-        pl = plan_rowreduce(t->n_pad, q->n_pad, ctx->tune);
-        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, pl.partial_bytes(1) + pl.bound_bytes() + fix_bytes(nt))) != FM_OK) return rc;
-        if ((ctx->tune.coop != 0) && pl.nsplit > 1) d_bound = (int*)((char*)ctx->ws_partial + pl.partial_bytes(1));
-    }
-
+    if (async_mode && f32) return fail(ctx, FM_EINVAL, std::string(who) + ": needs integer-valued banks");
     if (async_mode) {
+        // (reverse NN: output rows = train rows, reduced over the query rows; the slot owns the sweep's workspace)
+        const RowReducePlan pl = plan_rowreduce(t->n_pad, q->n_pad, ctx->tune);
         // Enqueue and return: outputs (and the count) are page-locked caller memory the compaction
         // kernel writes directly; the events of this call are read at fm_sync.
         void* a_q = pinned_device_alias(c_qidx); void* a_t = pinned_device_alias(tidx);
         void* a_d = pinned_device_alias(dist);   void* a_r = pinned_device_alias(ratio);
         void* a_c = n_pass ? pinned_device_alias(n_pass) : nullptr;
-        if (f32) return fail(ctx, FM_EINVAL, std::string(who) + ": needs integer-valued banks");
         if (to_device ? (n_pass && !a_c) : (!a_q || !a_t || !a_d || !a_r || !a_c))
             return fail(ctx, FM_EINVAL, std::string(who) + ": host outputs must be page-locked (fm_host_alloc)");
         fm_ctx::PendingTimer tm;
@@ -1330,24 +1323,13 @@ static int xcheck_common(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, bool w
     HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)nq * 8, ctx->stream));
     if (!compact) HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
     if (nt > 0) {
-        if (d_bound)
-            if (!ablate_keep_bounds()) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)d_bound, (int)0x80000000, (size_t)pl.ncols_alloc, ctx->stream));
-        if (f32) {
-            if ((rc = rowreduce_f32_route(ctx, t, q, 1, &pl)) != FM_OK) return rc;
-        } else {
-            // (accepted-only: only rows that pass the ratio test are reported -- K1 may drop what cannot pass)
-            const unsigned* cut = nullptr;
-            if (compact && with_ratio && (rc = enqueue_ratio_cut(ctx, 1, &q, tau, &cut)) != FM_OK) return rc;
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-            HIP_TRY(ctx, launch_rowreduce(*t, *q, 1, pl, (unsigned long long*)ctx->ws_partial, d_bound, (ctx->tune.glds != 0), ctx->stream, cut));
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
-        }
-        ctx->kernel_timed = true;
-        ctx->pending_pairs += nq * nt;
-        ctx->pending_bytes += bank_bytes(q) + bank_bytes(t);
-        // (the float32 route's partial layout has no tie list behind it, and needs none)
-        unsigned* d_fix = f32 ? nullptr : (unsigned*)((char*)ctx->ws_partial + pl.partial_bytes(1) + pl.bound_bytes());
-        if ((rc = enqueue_election(ctx, ctx->stream, q, t, (const unsigned long long*)ctx->ws_partial, pl, d_qbest, 0u, nullptr, d_fix)) != FM_OK) return rc;
+        // reverse NN: output rows = train rows, reduced over the query rows
+        // (accepted-only: only rows that pass the ratio test are reported -- K1 may drop what cannot pass)
+        const unsigned* cut = nullptr;
+        if (!f32 && compact && with_ratio && (rc = enqueue_ratio_cut(ctx, 1, &q, tau, &cut)) != FM_OK) return rc;
+        PairSweep ps;
+        if ((rc = sweep_pair(ctx, *t, *q, 1, nt, cut, nullptr, 0, &ps)) != FM_OK) return rc;
+        if ((rc = enqueue_election(ctx, ctx->stream, q, t, ps.partial, ps.nsplit, ps.ncols_alloc, ps.f32_keys, d_qbest, 0u, nullptr, ps.fix)) != FM_OK) return rc;
     }
     hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
                        (const unsigned long long*)d_qbest, nq, with_ratio ? (const double*)q->selfdist : (const double*)nullptr,
@@ -1452,34 +1434,15 @@ static int xcheck1_keys_common(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
     if (nq == 0) return FM_OK;
     if (!keys) return fail(ctx, FM_EINVAL, "fm_xcheck1_keys: output pointer is NULL");
     if (t_offset < 0 || t_offset + nt > (int64_t)UINT32_MAX) return fail(ctx, FM_EINVAL, "fm_xcheck1_keys: t_offset + rows must fit 32 bits");
-    const int f32 = q->kind == FM_BANK_F32;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, (size_t)nq * 8 + 64)) != FM_OK) return rc;
     unsigned long long* d_qbest = (unsigned long long*)ctx->ws_out;
-    RowReducePlan pl;
-    int* d_bound = nullptr;
-    if (!f32) {
-        pl = plan_rowreduce(t->n_pad, q->n_pad, ctx->tune);
-        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, pl.partial_bytes(1) + pl.bound_bytes() + fix_bytes(nt))) != FM_OK) return rc;
-        if ((ctx->tune.coop != 0) && pl.nsplit > 1) d_bound = (int*)((char*)ctx->ws_partial + pl.partial_bytes(1));
-    }
     CallScope cs(ctx);
     HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)nq * 8, ctx->stream));
     if (nt > 0) {
-        if (d_bound)
-            if (!ablate_keep_bounds()) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)d_bound, (int)0x80000000, (size_t)pl.ncols_alloc, ctx->stream));
-        if (f32) {
-            if ((rc = rowreduce_f32_route(ctx, t, q, 1, &pl)) != FM_OK) return rc;
-        } else {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-            HIP_TRY(ctx, launch_rowreduce(*t, *q, 1, pl, (unsigned long long*)ctx->ws_partial, d_bound, (ctx->tune.glds != 0), ctx->stream));
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
-        }
-        ctx->kernel_timed = true;
-        ctx->pending_pairs += nq * nt;
-        ctx->pending_bytes += bank_bytes(q) + bank_bytes(t);
-        unsigned* d_fix = f32 ? nullptr : (unsigned*)((char*)ctx->ws_partial + pl.partial_bytes(1) + pl.bound_bytes());
-        if ((rc = enqueue_election(ctx, ctx->stream, q, t, (const unsigned long long*)ctx->ws_partial, pl, d_qbest, (unsigned)t_offset, nullptr, d_fix)) != FM_OK) return rc;
+        PairSweep ps;
+        if ((rc = sweep_pair(ctx, *t, *q, 1, nt, nullptr, nullptr, 0, &ps)) != FM_OK) return rc;
+        if ((rc = enqueue_election(ctx, ctx->stream, q, t, ps.partial, ps.nsplit, ps.ncols_alloc, ps.f32_keys, d_qbest, (unsigned)t_offset, nullptr, ps.fix)) != FM_OK) return rc;
     }
     if (keys_on_device) HIP_TRY(ctx, hipMemcpyAsync(keys, d_qbest, (size_t)nq * 8, hipMemcpyDeviceToDevice, ctx->stream));
     else HIP_TRY(ctx, d2h(ctx, keys, d_qbest, (size_t)nq * 8));
@@ -1501,21 +1464,12 @@ static int xcheck1_bin(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t*
     unsigned long long* d_qbest = (unsigned long long*)ctx->ws_out;
     int32_t* d_tidx = (int32_t*)((char*)ctx->ws_out + (size_t)nq * 8);
     float* d_dist = (float*)((char*)ctx->ws_out + (size_t)nq * 12);
-    const HamPlan hp = plan_hamming(t->n_pad, q->n_pad);
-    if (nt > 0 && (rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, hp.partial_bytes(1) + 64)) != FM_OK) return rc;
     CallScope cs(ctx);
     HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)nq * 8, ctx->stream));
     if (nt > 0) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-        HIP_TRY(ctx, launch_hamming(*t, *q, 1, hp, (unsigned long long*)ctx->ws_partial, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
-        ctx->kernel_timed = true;
-        ctx->pending_pairs += nq * nt;
-        ctx->pending_bytes += bank_bytes(q) + bank_bytes(t);
-        hipLaunchKernelGGL(xcheck_scatter_kernel, dim3((unsigned)((nt * 4 + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const unsigned long long*)ctx->ws_partial, hp.nsplit, hp.ncols_alloc, nt, d_qbest, 0u, 1, (int*)nullptr,
-                           (unsigned*)nullptr);
-        HIP_TRY(ctx, hipGetLastError());
+        PairSweep ps;
+        if ((rc = sweep_pair(ctx, *t, *q, 1, 0, nullptr, nullptr, 0, &ps)) != FM_OK) return rc;
+        if ((rc = enqueue_election(ctx, ctx->stream, q, t, ps.partial, ps.nsplit, ps.ncols_alloc, ps.f32_keys, d_qbest, 0u, nullptr, nullptr)) != FM_OK) return rc;
     }
     hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
                        (const unsigned long long*)d_qbest, nq, (const double*)nullptr, 0.0, d_tidx, d_dist, (double*)nullptr,

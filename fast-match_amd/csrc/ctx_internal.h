@@ -1,7 +1,7 @@
 // What the translation units behind the C-ABI share: the context object, error plumbing, workspace and
 // device-to-host helpers.  api_ctx.hip (context, options, banks) defines the functions declared here;
-// api_match.hip (2-NN, cross-check, batches, rounds), api_expand.hip (K7 glue) and comm.hip (result gather)
-// use them.  Internal: nothing here is part of include/fastmatch_hip.h.
+// api_match.hip (2-NN, cross-check, batches, rounds), api_collection.hip (train collections), api_expand.hip (K7 glue)
+// and comm.hip (result gather) use them.  Internal: nothing here is part of include/fastmatch_hip.h.
 #pragma once
 #include "fm_internal.h"
 #include "expand_pair.h"
@@ -162,6 +162,38 @@ int round_xcheck_dense(fm_ctx* ctx, const fm::Bank& q, const int32_t* d_rows, in
 // Float32 route of a top-KTOP row-reduce (api_match.hip): K5 alone, or the fp16 filter (K8) with K5 as its conditional fallback;
 // leaves the packed keys in ctx->ws_partial in *pl_out's layout.
 int rowreduce_f32_route(fm_ctx* ctx, const fm_bank* cols, const fm_bank* red, int ktop, fm::RowReducePlan* pl_out, bool self = false);
+
+// ---- one (output bank, reduced bank) pair swept on the context's stream (api_match.hip) ----------------------------------
+// The tie list of the float32-root repair (tile_ops.h: kSqrtTieMin): fix[0] = count, rows from fix[4] on.
+constexpr int kFixGrid = 1024;                 // workgroups of a sqrt_fix_kernel launch (each walks the list)
+static inline size_t fix_bytes(int64_t rows) { return ((size_t)rows * 4 + 16 + 15) & ~(size_t)15; }
+
+// What the small kernels behind a sweep read: the packed keys in ctx->ws_partial, laid out partial | bounds | tie list.
+struct PairSweep {
+    const unsigned long long* partial;   // ctx->ws_partial: [nsplit][ncols_alloc][ktop] keys, ascending per row
+    int nsplit, ncols_alloc;
+    int f32_keys;                        // high word = float32 distance bits (float32 route, binary) or the exact d2 (integer route)
+    unsigned* fix;                       // zeroed tie list of fix_rows rows: integer-route pairs for which sqrt_tie_possible()
+                                         // holds, and only when asked for; else null
+    int* bound;                          // the integer route's shared bounds, [ktop][ncols_alloc] words, or null (one split, "coop" 0)
+    fm::RowReducePlan rr;                // (sweep_pair_run's: the integer route's plan / K11's)
+    fm::HamPlan ham;
+};
+enum : unsigned {
+    kSweepNoEvents = 1u,   // ev_k0 / ev_k1 are the caller's: it brackets several sweeps, or none (rowreduce_f32_route still records its own)
+    kSweepNoCount  = 2u,   // pending_pairs / pending_bytes are the caller's (a collection counts real rows, not the stack's)
+};
+// Top-ktop (1 or 2) of every row of `cols` over the rows of `red` by the route of the banks' kind: K1 / K2, the float32 route
+// (rowreduce_f32_route), K11.  Sizes and carves ws_partial, re-arms the bounds, zeroes the tie list (fix_rows > 0: the rows
+// the caller's merge or election may list), records ev_k0 / ev_k1 around the launch and accounts the pair.
+// cut: launch_rowreduce's (integer route, top-1); stage_real: launch_hamming's.
+int sweep_pair(fm_ctx* ctx, const fm::Bank& cols, const fm::Bank& red, int ktop, int64_t fix_rows, const unsigned* cut,
+               const int* stage_real, unsigned flags, PairSweep* out);
+// The two halves of sweep_pair, for a caller whose own kernel sits between them and fills out->bound itself (the delegated
+// round's gather): plan + workspace, no stream work; then the launch.  Not for the float32 route, which sizes its own.
+int sweep_pair_plan(fm_ctx* ctx, const fm::Bank& cols, const fm::Bank& red, int ktop, int64_t fix_rows, PairSweep* out);
+int sweep_pair_run(fm_ctx* ctx, const fm::Bank& cols, const fm::Bank& red, int ktop, const unsigned* cut, const int* stage_real,
+                   unsigned flags, const PairSweep& ps);
 // Lowe's ratio test on 2-NN lists (api_match.hip; api_collection.hip runs it on a collection's lists)
 __global__ void lowe_kernel(const int32_t* __restrict__ idx2, const float* __restrict__ dist2, int64_t nq,
                             double tau, int32_t* __restrict__ tidx, float* __restrict__ dist,

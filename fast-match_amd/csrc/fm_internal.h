@@ -59,6 +59,41 @@ struct Bank {
     uint8_t* rows4  = nullptr; // [n_pad][64 ksteps] FP4 image: bit 1 -> +1, bit 0 -> -1, padding 0
 };
 
+// rows rounded up to whole 128-row stages
+inline int64_t pad128(int64_t n) { return ((n + kStageRows - 1) / kStageRows) * kStageRows; }
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// Workspace layouts: the offset of a piece of `bytes` bytes behind `off`, which moves on by the bytes rounded up to `align`
+// (a power of two).
+inline size_t carve(size_t& off, size_t bytes, size_t align = 256)
+{
+    const size_t o = off;
+    off += (bytes + align - 1) & ~(align - 1);
+    return o;
+}
+
+// The rows [r0, r0 + n) of a bank's arrays as a bank of their own, for every kind: each plane that exists moves on by r0
+// rows, the scale terms are the bank's (usq_max and nm_max stay upper bounds), n_pad = cap_pad = pad128(n) clipped to the
+// rows the arrays have left.  The aux words exist per 32-row tile: a view that starts inside a tile has none and can only
+// be the output side of an integer sweep, which does not read them.  No self distances: they belong to the whole bank.
+inline Bank bank_rows_view(const Bank& b, int64_t r0, int64_t n)
+{
+    Bank v;
+    v.kind = b.kind; v.n = n; v.dim = b.dim;
+    v.ksteps = b.ksteps; v.kscale = b.kscale; v.filt_ok = b.filt_ok; v.nm_max = b.nm_max; v.usq_max = b.usq_max;
+    const int64_t room = (b.cap_pad > 0 ? b.cap_pad : b.n_pad) - r0;
+    v.n_pad = v.cap_pad = pad128(n) < room ? pad128(n) : room;
+    if (b.rows8) v.rows8 = b.rows8 + (size_t)r0 * kDim;
+    if (b.norm)  v.norm = b.norm + r0;
+    if (b.aux && r0 % kTileRows == 0) v.aux = b.aux + (r0 / kTileRows) * kAuxPerTile;
+    if (b.rowsf) v.rowsf = b.rowsf + (size_t)r0 * kDim;
+    if (b.rowsh) v.rowsh = b.rowsh + (size_t)r0 * kDim;
+    if (b.normf) v.normf = b.normf + r0;
+    if (b.auxf)  v.auxf = b.auxf + r0;
+    if (b.rowsb) v.rowsb = b.rowsb + (size_t)r0 * b.ksteps * 16;
+    if (b.rows4) v.rows4 = b.rows4 + (size_t)r0 * b.ksteps * 64;
+    return v;
+}
+
 // OpenCV orders candidates by the float32 root of d2; the integer route orders by d2, which is the same
 // order unless a d2 reaches 4 197 200, where two integers start to share a float32 root (kSqrtTieMin,
 // tile_ops.h).  Rows are non-negative, so d2(a, b) <= |a|^2 + |b|^2: a bank pair whose largest row
