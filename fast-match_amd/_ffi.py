@@ -19,6 +19,8 @@ LIB_PATH = os.path.join(_HERE, "libfastmatch_hip.so")
 FM_BANK_I8 = 1
 FM_BANK_F32 = 2
 FM_BANK_BIN = 3             # binary descriptors (Context.bank_binary): NORM_HAMMING
+# element types of rows in device memory (Context.bank_from_device)
+FM_DT_U8, FM_DT_F32, FM_DT_F16, FM_DT_BF16, FM_DT_BIN = 1, 2, 3, 4, 5
 
 
 class FastMatchHipError(RuntimeError):
@@ -39,7 +41,7 @@ class fm_stats_ex(ctypes.Structure):
                 ("bytes_moved", ctypes.c_int64)]
 
 
-FM_ABI_VERSION = 11         # include/fastmatch_hip.h: the revision this binding was written against
+FM_ABI_VERSION = 12         # include/fastmatch_hip.h: the revision this binding was written against
 
 
 class fm_expand_desc(ctypes.Structure):
@@ -85,6 +87,10 @@ SYMBOLS = {
     "fm_bank_create_f32": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
     "fm_bank_create_f32_route": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
     "fm_bank_create_bin": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
+    "fm_bank_create_dev": (_INT, [_P, _P, _INT, _I64, _INT, _I64, _INT, _P, ctypes.POINTER(_P)]),
+    "fm_knn_dev": (_INT, [_P, _P, _P, _I32, _P, _P, _P]),
+    "fm_xcheck1_dev": (_INT, [_P, _P, _P, _P, _P, _P]),
+    "fm_knn2_ratio_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
     "fm_bank_destroy": (_INT, [_P, _P]),
     "fm_bank_info": (_INT, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_INT), ctypes.POINTER(_INT)]),
     "fm_bank_set_selfdist": (_INT, [_P, _P, _P]),
@@ -684,6 +690,42 @@ class Context(object):
         n, dim, kind = _I64(), _INT(), _INT()
         self._check(self.lib.fm_bank_info(h, ctypes.byref(n), ctypes.byref(dim), ctypes.byref(kind)))
         return Bank(self, h, n.value, dim.value, kind.value)
+
+    def bank_from_device(self, ptr, dtype, n, dim, pitch=0, float_route=False, stream=None):
+        """A bank from ``n`` rows of ``dim`` elements that are already in device memory (``fm_bank_create_dev``): ``ptr`` =
+        their device address (``tensor.data_ptr()``), ``dtype`` = ``FM_DT_U8`` / ``_F32`` / ``_F16`` / ``_BF16`` / ``_BIN``
+        (binary: dim = bytes per row), ``pitch`` = bytes between rows (0 = dense).  The preparation kernels read the memory in
+        place behind the work ``stream`` (a raw handle, 0 = the null stream; None = the rows are complete) has been given so
+        far; on return the source may be overwritten.  The bank equals the one ``bank`` / ``bank_binary`` builds from the same
+        values on the host."""
+        h = _P()
+        self._check(self.lib.fm_bank_create_dev(self.handle, _P(int(ptr)) if ptr else None, int(dtype), int(n), int(dim), int(pitch),
+                                                1 if float_route else 0, _stream_arg(stream), ctypes.byref(h)))
+        bn, bdim, kind = _I64(), _INT(), _INT()
+        self._check(self.lib.fm_bank_info(h, ctypes.byref(bn), ctypes.byref(bdim), ctypes.byref(kind)))
+        return Bank(self, h, bn.value, bdim.value, kind.value)
+
+    def knn_dev(self, q, t, k, idx_ptr, dist_ptr, consumer_stream=None):
+        """``knn`` with the lists left on the device (``fm_knn_dev``): ``idx_ptr`` / ``dist_ptr`` = device addresses of
+        int32 / float32 [nq, k] buffers; enqueued, no host synchronisation on the integer and binary routes.
+        ``consumer_stream`` as in ``match_accepted_dev_async``."""
+        self._check(self.lib.fm_knn_dev(self.handle, q.handle, t.handle, int(k), _P(int(idx_ptr)) if idx_ptr else None,
+                                        _P(int(dist_ptr)) if dist_ptr else None, _stream_arg(consumer_stream)))
+
+    def xcheck1_dev(self, q, t, tidx_ptr, dist_ptr, consumer_stream=None):
+        """``xcheck1`` with the results left on the device (``fm_xcheck1_dev``): int32 / float32 [nq] buffers."""
+        self._check(self.lib.fm_xcheck1_dev(self.handle, q.handle, t.handle, _P(int(tidx_ptr)) if tidx_ptr else None,
+                                            _P(int(dist_ptr)) if dist_ptr else None, _stream_arg(consumer_stream)))
+
+    def knn2_ratio_dev(self, q, t, tau, rows_ptr, count_ptr, cap, want_count=False, consumer_stream=None):
+        """``knn2_ratio`` with the accepted matches left on the device (``fm_knn2_ratio_dev``): ``rows_ptr`` = device address
+        of an int32 [cap, 3] buffer (query, train, float32 distance bits), ``count_ptr`` of an int64 word that receives
+        min(accepted, cap).  ``want_count``: also return the full number accepted (one host synchronisation); else None."""
+        n = _I64(0)
+        self._check(self.lib.fm_knn2_ratio_dev(self.handle, q.handle, t.handle, float(tau), int(cap),
+                                               _P(int(rows_ptr)) if rows_ptr else None, _P(int(count_ptr)) if count_ptr else None,
+                                               ctypes.byref(n) if want_count else None, _stream_arg(consumer_stream)))
+        return int(n.value) if want_count else None
 
     def bank_gather(self, rows, src_row, float_route=False):
         """The bank ``rows[src_row]`` without building that matrix on the host: the n_src rows are uploaded once and

@@ -19,6 +19,29 @@ int fm::fail(fm_ctx* ctx, int code, const std::string& msg)
     return code;
 }
 
+int fm::wait_for_stream(fm_ctx* ctx, void* s)
+{
+    if (s == FM_NO_STREAM) return FM_OK;
+    hipEvent_t& ev = ctx->ev_foreign[(hipStream_t)s];
+    if (!ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventRecord(ev, (hipStream_t)s));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ev, 0));
+    return FM_OK;
+}
+
+int fm::check_device_ptr(fm_ctx* ctx, const void* p, const char* who, const char* what)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        return fail(ctx, FM_EINVAL, std::string(who) + ": " + what + " must be device memory");
+    }
+    if (at.device != ctx->device)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": " + what + " lives on device " + std::to_string(at.device) +
+                                    ", the context on device " + std::to_string(ctx->device));
+    return FM_OK;
+}
+
 int fm::ws_ensure(fm_ctx* ctx, void** p, size_t* cap, size_t need)
 {
     if (need <= *cap && *p) return FM_OK;
@@ -161,6 +184,160 @@ void bank_prep_kernel(const void* __restrict__ src, int64_t n, int dim,
         if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (tid & 63) == 0 && *(volatile int*)nonint == 0) atomicOr(nonint, 1);
     }
   }
+}
+
+// The second half of bank_prep_kernel for the device-source kernel below: what a thread does with its 16 values uv[]
+// (have[]: the value is inside the row's dim; live: the row is a real one) -- the int8 bytes, the row's norm and aux
+// words, the largest uint8 norm into nonint[1].  (bank_prep_kernel keeps its own copy: it runs beside the distance kernels
+// in a refill, and sharing this function cost it 46 VGPRs.)
+__device__ __forceinline__ void bank_prep_emit(const int (&uv)[16], const bool (&have)[16], bool live, int64_t row, int64_t tile,
+                                               int tid, int8_t* __restrict__ rows8, int32_t* __restrict__ norm,
+                                               int32_t* __restrict__ aux, int* __restrict__ nonint)
+{
+    const int r = tid >> 3, c = tid & 7;
+    unsigned w[4] = {0, 0, 0, 0};
+    int sumsq = 0, usq = 0;
+    if (live) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            unsigned word = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int u = uv[4 * q + b];
+                if (have[4 * q + b]) usq += u * u;
+                const int s = u - FM_ENC_SHIFT;      // 128: == (int8)(u ^ 0x80)
+                sumsq += s * s;
+                word |= (unsigned)(s & 0xff) << (8 * b);
+            }
+            w[q] = word;
+        }
+    }
+    *(uint4*)(rows8 + row * kDim + 16 * c) = make_uint4(w[0], w[1], w[2], w[3]);
+    sumsq += __shfl_xor(sumsq, 1);
+    sumsq += __shfl_xor(sumsq, 2);
+    sumsq += __shfl_xor(sumsq, 4);
+    usq += __shfl_xor(usq, 1);
+    usq += __shfl_xor(usq, 2);
+    usq += __shfl_xor(usq, 4);
+    usq = max(usq, __shfl_xor(usq, 8));
+    usq = max(usq, __shfl_xor(usq, 16));
+    usq = max(usq, __shfl_xor(usq, 32));
+    if ((tid & 63) == 0 && usq > 0) atomicMax(nonint + 1, usq);
+    if (c == 0) {
+        // aux words of the 32-row unit in the accumulator order of v_mfma_i32_16x16x64_i8
+        // (two 16-row tiles; tile row rr sits in lane group rr >> 2, register rr & 3)
+        const int sub = r >> 4, rr = r & 15;
+        const int id = 4 * sub + (rr & 3);
+        int32_t* a = aux + tile * kAuxPerTile + 32 * sub;
+        if (live) {
+            norm[row] = sumsq;
+            a[rr]      = -(sumsq >> 1);
+            a[16 + rr] = ((1 - (sumsq & 1)) << 4) | (15 - id);
+        } else {
+            norm[row] = 0;
+            a[rr]      = kPadCinit;
+            a[16 + rr] = 15 - id;
+        }
+    }
+}
+
+// A float32 value of a row that may take the integer route: its uint8 value, or 128 (0 after the shift) and `bad` raised.
+__device__ __forceinline__ int bank_prep_u8_of(float f, bool& bad)
+{
+    const float fr = rintf(f);
+    const bool ok = (f == fr) && f >= 0.f && f <= 255.f;
+    bad |= !ok;
+    return ok ? (int)fr : 128;
+}
+
+// ---- fm_bank_create_dev: the same preparation from rows that are ALREADY in device memory -------------------------------------
+// The caller's tensor is read in place -- no copy into ws_in -- as rows of `pitch` bytes (a column slice of a wider tensor
+// is a pitched matrix) of uint8, float32, IEEE half or bfloat16 elements; half and bfloat16 widen to float32 in registers,
+// exactly, and then follow the float32 rules.  DT = FM_DT_U8 / _F32 / _F16 / _BF16.
+template <int DT>
+__device__ __forceinline__ float dev_src_elem(const uint8_t* __restrict__ rowp, int k)
+{
+    if constexpr (DT == FM_DT_F32) return ((const float*)rowp)[k];
+    else if constexpr (DT == FM_DT_F16) return (float)((const _Float16*)rowp)[k];
+    else if constexpr (DT == FM_DT_BF16) return __uint_as_float((unsigned)((const uint16_t*)rowp)[k] << 16);
+    else return (float)rowp[k];
+}
+
+// the 16 elements [16 c, 16 c + 16) of a full-width row whose address and pitch are multiples of 16 bytes
+template <int DT>
+__device__ __forceinline__ void dev_src_load16(const uint8_t* __restrict__ rowp, int c, float (&f)[16])
+{
+    if constexpr (DT == FM_DT_F32) {
+        const float4* sp = (const float4*)rowp + 4 * c;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { const float4 v = sp[q]; f[4 * q] = v.x; f[4 * q + 1] = v.y; f[4 * q + 2] = v.z; f[4 * q + 3] = v.w; }
+    } else if constexpr (DT == FM_DT_U8) {
+        const uint4 v = *((const uint4*)rowp + c);
+        const unsigned ww[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 16; ++e) f[e] = (float)((ww[e >> 2] >> (8 * (e & 3))) & 0xffu);
+    } else {
+        const uint4 v0 = *((const uint4*)rowp + 2 * c), v1 = *((const uint4*)rowp + 2 * c + 1);
+        const unsigned ww[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const unsigned h = (ww[e >> 1] >> (16 * (e & 1))) & 0xffffu;
+            if constexpr (DT == FM_DT_F16) f[e] = (float)__builtin_bit_cast(_Float16, (unsigned short)h);
+            else f[e] = __uint_as_float(h << 16);
+        }
+    }
+}
+
+// bank_prep_kernel for a device source: same tiles, same outputs, same flag words.  vec: dim == 128 and the rows sit on
+// 16-byte boundaries (16-byte loads); otherwise element loads.
+template <int DT>
+__global__ __launch_bounds__(256)
+void bank_prep_dev_kernel(const uint8_t* __restrict__ src, int64_t pitch, int vec, int64_t n, int dim,
+                          int8_t* __restrict__ rows8, int32_t* __restrict__ norm,
+                          int32_t* __restrict__ aux, int* __restrict__ nonint, int64_t ntiles)
+{
+    const int tid = threadIdx.x;
+    const int r = tid >> 3, c = tid & 7;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t row = tile * kTileRows + r;
+        bool bad = false;
+        int uv[16];
+        bool have[16];
+        if (row < n) {
+            const uint8_t* rowp = src + row * pitch;
+            float f[16];
+            if (vec) {
+                dev_src_load16<DT>(rowp, c, f);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) have[e] = true;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int k = 16 * c + e;
+                    have[e] = k < dim;
+                    f[e] = k < dim ? dev_src_elem<DT>(rowp, k) : 0.f;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 16; ++e) uv[e] = have[e] ? bank_prep_u8_of(f[e], bad) : FM_ENC_SHIFT;
+        }
+        bank_prep_emit(uv, have, row < n, row, tile, tid, rows8, norm, aux, nonint);
+        if constexpr (DT != FM_DT_U8) {
+            if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (tid & 63) == 0 && *(volatile int*)nonint == 0) atomicOr(nonint, 1);
+        }
+    }
+}
+
+// bank_copy_f32_kernel for a device source: the float32 route's zero-padded [n_pad][128] rows.
+template <int DT>
+__global__ void bank_copy_dev_kernel(const uint8_t* __restrict__ src, int64_t pitch, int64_t n, int dim,
+                                     float* __restrict__ dst, int64_t n_pad)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pad * kDim) return;
+    const int64_t row = i / kDim;
+    const int k = (int)(i % kDim);
+    dst[i] = (row < n && k < dim) ? dev_src_elem<DT>(src + row * pitch, k) : 0.f;
 }
 
 // float32 bank for the general (non-integer) route: zero-padded copy [n_pad][128].
@@ -383,6 +560,8 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx)
     if (ctx->upload) { (void)hipStreamSynchronize(ctx->upload); (void)hipStreamDestroy(ctx->upload); }
     if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
     if (ctx->ev_consumer) (void)hipEventDestroy(ctx->ev_consumer);
+    for (auto& kv : ctx->ev_foreign) (void)hipEventDestroy(kv.second);
+    if (ctx->ev_results) (void)hipEventDestroy(ctx->ev_results);
     for (hipEvent_t ev : ctx->ev_tail_end) if (ev) (void)hipEventDestroy(ev);
     if (ctx->comm) { comm_destroy(ctx->comm); ctx->comm = nullptr; }      // (before the streams it was used on)
     for (hipStream_t ts : ctx->tails) if (ts) (void)hipStreamDestroy(ts);
@@ -656,14 +835,45 @@ static void bank_free(Bank* b)
     b->rowsh = nullptr; b->normf = nullptr; b->auxf = nullptr;
 }
 
+// Source rows that are already in device memory (fm_bank_create_dev): read in place by the *_dev_kernel variants.
+struct DevSrc { const uint8_t* rows; int dtype; int64_t pitch; };
+
+static hipError_t launch_bank_prep_dev(const DevSrc& d, int64_t n, int dim, Bank& b, int* d_flag, int ntiles, hipStream_t stream)
+{
+    const int vec = dim == kDim && (((uintptr_t)d.rows | (uintptr_t)d.pitch) & 15) == 0;
+#define FM_PREP_DEV(DT_)                                                                                                   \
+    case DT_: hipLaunchKernelGGL((bank_prep_dev_kernel<DT_>), dim3(ntiles), dim3(256), 0, stream, d.rows, d.pitch, vec, n, dim, \
+                                 b.rows8, b.norm, b.aux, d_flag, (int64_t)ntiles); break;
+    switch (d.dtype) {
+        FM_PREP_DEV(FM_DT_U8) FM_PREP_DEV(FM_DT_F32) FM_PREP_DEV(FM_DT_F16) FM_PREP_DEV(FM_DT_BF16)
+        default: return hipErrorInvalidValue;
+    }
+#undef FM_PREP_DEV
+    return hipGetLastError();
+}
+
+static hipError_t launch_bank_copy_dev(const DevSrc& d, int64_t n, int dim, Bank& b, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((b.n_pad * kDim + 255) / 256));
+#define FM_COPY_DEV(DT_)                                                                                                   \
+    case DT_: hipLaunchKernelGGL((bank_copy_dev_kernel<DT_>), grid, dim3(256), 0, stream, d.rows, d.pitch, n, dim, b.rowsf, b.n_pad); break;
+    switch (d.dtype) {
+        FM_COPY_DEV(FM_DT_F32) FM_COPY_DEV(FM_DT_F16) FM_COPY_DEV(FM_DT_BF16)
+        default: return hipErrorInvalidValue;
+    }
+#undef FM_COPY_DEV
+    return hipGetLastError();
+}
+
 // map != nullptr: the bank's row i is rows[map[i]] of the n_src source rows (0 <= map[i] < n_src, checked here).
+// dev != nullptr: the rows are dev's (device memory, checked by the caller; `rows` is ignored, f32 = "not uint8").
 static int bank_create(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f32, fm_bank** out, bool keep_f32 = false,
-                       int64_t capacity = 0, const int32_t* map = nullptr, int64_t n_src = 0)
+                       int64_t capacity = 0, const int32_t* map = nullptr, int64_t n_src = 0, const DevSrc* dev = nullptr)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, "fm_bank_create: ctx is NULL");
     if (!out) return fail(ctx, FM_EINVAL, "fm_bank_create: bank out pointer is NULL");
     *out = nullptr;
-    if (n < 0 || dim < 1 || (n > 0 && !rows)) return fail(ctx, FM_EINVAL, "fm_bank_create: bad rows/n/dim");
+    if (n < 0 || dim < 1 || (n > 0 && !rows && !dev)) return fail(ctx, FM_EINVAL, "fm_bank_create: bad rows/n/dim");
     if (map) {
         if (n_src < 0 || n_src > INT32_MAX) return fail(ctx, FM_EINVAL, "fm_bank_create_*_gather: bad n_src");
         for (int64_t i = 0; i < n; ++i)
@@ -686,7 +896,7 @@ static int bank_create(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f
     }
     b->kind = FM_BANK_I8;
     const size_t elt = f32 ? 4 : 1;
-    const size_t src_bytes = (size_t)(map ? n_src : n) * dim * elt;
+    const size_t src_bytes = dev ? 0 : (size_t)(map ? n_src : n) * dim * elt;      // (a device source is not staged)
     int rc = FM_OK;
     auto bail = [&](int code) { bank_free(b); delete b; return code; };
 
@@ -710,7 +920,9 @@ static int bank_create(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f
     if (map && n > 0) BTRY(hipMemcpyAsync((void*)d_map, map, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     BTRY(hipMemsetAsync(d_flag, 0, 8, ctx->stream));
     const int ntiles = (int)(b->cap_pad / kTileRows);
-    if (f32)
+    if (dev)
+        BTRY(launch_bank_prep_dev(*dev, n, dim, *b, d_flag, ntiles, ctx->stream));
+    else if (f32)
         hipLaunchKernelGGL(bank_prep_kernel<true>, dim3(ntiles), dim3(256), 0, ctx->stream,
                            (const void*)ctx->ws_in, n, dim, b->rows8, b->norm, b->aux, d_flag, (int64_t)ntiles, d_map);
     else
@@ -729,8 +941,11 @@ static int bank_create(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f
         (void)hipFree(b->aux); b->aux = nullptr;
         BTRY(hipMalloc((void**)&b->rowsf, (size_t)b->n_pad * kDim * 4));
         const int64_t tot = b->n_pad * kDim;
-        hipLaunchKernelGGL(bank_copy_f32_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const float*)ctx->ws_in, n, dim, b->rowsf, b->n_pad, d_map);
+        if (dev)
+            BTRY(launch_bank_copy_dev(*dev, n, dim, *b, ctx->stream));
+        else
+            hipLaunchKernelGGL(bank_copy_f32_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream,
+                               (const float*)ctx->ws_in, n, dim, b->rowsf, b->n_pad, d_map);
         BTRY(hipGetLastError());
         // rows for the fp16 filter, scaled by the power of two that puts the largest magnitude
         // of the bank in [2^13, 2^14)
@@ -1007,12 +1222,12 @@ int fm::bank_f32_range_planes(fm_ctx* ctx, Bank& b, int64_t off, int64_t n, int6
 }
 
 // K11: a binary bank -- [n][bytes] packed rows, 1 <= bytes <= 64 -- for NORM_HAMMING (hamming.hip).
-extern "C" int fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows, int64_t n, int bytes, fm_bank** out)
+static int bank_create_bin(fm_ctx* ctx, const uint8_t* rows, int64_t n, int bytes, fm_bank** out, const DevSrc* dev = nullptr)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, "fm_bank_create_bin: ctx is NULL");
     if (!out) return fail(ctx, FM_EINVAL, "fm_bank_create_bin: bank out pointer is NULL");
     *out = nullptr;
-    if (n < 0 || bytes < 1 || (n > 0 && !rows)) return fail(ctx, FM_EINVAL, "fm_bank_create_bin: bad rows/n/bytes");
+    if (n < 0 || bytes < 1 || (n > 0 && !rows && !dev)) return fail(ctx, FM_EINVAL, "fm_bank_create_bin: bad rows/n/bytes");
     if (bytes > 64) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_bin: binary rows of more than 64 bytes (512 bits) are not supported");
     if (n > (int64_t)INT32_MAX - 2 * kStageRows) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_bin: n too large");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1033,14 +1248,59 @@ extern "C" int fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows, int64_t n, i
     hipError_t e;
     if ((e = hipMalloc((void**)&b->rowsb, (size_t)b->n_pad * b->ksteps * 16)) != hipSuccess) return bail(e, "packed rows");
     if ((e = hipMalloc((void**)&b->rows4, (size_t)b->n_pad * b->ksteps * 64)) != hipSuccess) return bail(e, "FP4 rows");
-    const size_t src_bytes = (size_t)n * bytes;
-    int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, src_bytes + 64);
-    if (rc != FM_OK) { bank_free(b); delete b; return rc; }
-    if (src_bytes && (e = hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return bail(e, "upload");
-    if ((e = launch_hamming_prep((const uint8_t*)ctx->ws_in, n, bytes, *b, ctx->stream)) != hipSuccess) return bail(e, "prepare");
+    if (dev) {
+        // (device rows: the preparation kernel reads them in place, at the caller's pitch)
+        if ((e = launch_hamming_prep(dev->rows, n, bytes, *b, ctx->stream, dev->pitch)) != hipSuccess) return bail(e, "prepare");
+    } else {
+        const size_t src_bytes = (size_t)n * bytes;
+        int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, src_bytes + 64);
+        if (rc != FM_OK) { bank_free(b); delete b; return rc; }
+        if (src_bytes && (e = hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return bail(e, "upload");
+        if ((e = launch_hamming_prep((const uint8_t*)ctx->ws_in, n, bytes, *b, ctx->stream)) != hipSuccess) return bail(e, "prepare");
+    }
     if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "prepare");
     *out = b;
     return FM_OK;
+}
+
+extern "C" int fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows, int64_t n, int bytes, fm_bank** out)
+{
+    return bank_create_bin(ctx, rows, n, bytes, out);
+}
+
+// A bank from rows that are already in device memory (include/fastmatch_hip.h: "device sources").  The preparation kernels
+// read the caller's memory in place behind an event recorded on producer_stream; every creator synchronises the context's
+// stream before it returns (the flag words come back), so the source is not read after the call.
+extern "C" int fm_bank_create_dev(fm_ctx* ctx, const void* d_rows, int dtype, int64_t n, int dim, int64_t row_pitch_bytes,
+                                  int float_route, void* producer_stream, fm_bank** bank)
+{
+    if (!ctx) return fail(nullptr, FM_EINVAL, "fm_bank_create_dev: ctx is NULL");
+    if (!bank) return fail(ctx, FM_EINVAL, "fm_bank_create_dev: bank out pointer is NULL");
+    *bank = nullptr;
+    if (dtype < FM_DT_U8 || dtype > FM_DT_BIN)
+        return fail(ctx, FM_EINVAL, "fm_bank_create_dev: unknown dtype " + std::to_string(dtype) + " (FM_DT_U8 .. FM_DT_BIN)");
+    if (n < 0 || dim < 1) return fail(ctx, FM_EINVAL, "fm_bank_create_dev: bad n / dim");
+    if (dtype == FM_DT_BIN && dim > 64)
+        return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_dev: binary rows of more than 64 bytes (512 bits) are not supported");
+    if (dim > kDim) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_dev: dim > 128 is not supported");
+    const int64_t elt = dtype == FM_DT_F32 ? 4 : (dtype == FM_DT_F16 || dtype == FM_DT_BF16) ? 2 : 1;
+    const int64_t pitch = row_pitch_bytes == 0 ? dim * elt : row_pitch_bytes;
+    if (pitch < dim * elt)
+        return fail(ctx, FM_EINVAL, "fm_bank_create_dev: row_pitch_bytes " + std::to_string(row_pitch_bytes) + " is below the row size " +
+                                    std::to_string(dim * elt));
+    if (pitch % elt != 0) return fail(ctx, FM_EINVAL, "fm_bank_create_dev: row_pitch_bytes is not a multiple of the element size");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n > 0) {
+        if (!d_rows) return fail(ctx, FM_EINVAL, "fm_bank_create_dev: d_rows is NULL");
+        if ((uintptr_t)d_rows % (uintptr_t)elt != 0) return fail(ctx, FM_EINVAL, "fm_bank_create_dev: d_rows is not aligned to the element size");
+        int rc;
+        if ((rc = check_device_ptr(ctx, d_rows, "fm_bank_create_dev", "d_rows")) != FM_OK) return rc;
+        // the rows are complete once the work producer_stream has been given so far is: no host wait for it
+        if ((rc = wait_for_stream(ctx, producer_stream)) != FM_OK) return rc;
+    }
+    const DevSrc src{(const uint8_t*)d_rows, dtype, pitch};
+    if (dtype == FM_DT_BIN) return bank_create_bin(ctx, nullptr, n, dim, bank, &src);
+    return bank_create(ctx, nullptr, n, dim, dtype != FM_DT_U8, bank, float_route != 0 && dtype != FM_DT_U8, 0, nullptr, 0, &src);
 }
 
 extern "C" int fm_bank_create_f32(fm_ctx* ctx, const float* rows, int64_t n, int dim, fm_bank** bank)

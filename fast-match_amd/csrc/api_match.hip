@@ -736,8 +736,9 @@ int fm::round_xcheck_dense(fm_ctx* ctx, const Bank& q, const int32_t* d_rows, in
 // ---------------------------------------------------------------------------------------
 // Device-side knn2 into d_idx/d_dist (device pointers): the top-2 sweep of the pair's route (K2, K8 / K5, K11 on the FP4
 // matrix cores -- its keys carry the float32 bits of the integer Hamming distance: exact, no root ties), merged by
-// knn2_merge_kernel.
-static int knn2_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* d_idx, float* d_dist)
+// knn2_merge_kernel.  consumer (fm_knn_dev: d_idx / d_dist are the caller's arrays): the stream whose work so far the merge
+// -- the first kernel that writes them -- waits for, behind the sweep.
+static int knn2_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* d_idx, float* d_dist, void* consumer = FM_NO_STREAM)
 {
     const int64_t nq = q->n;
     if (nq == 0) return FM_OK;
@@ -746,6 +747,7 @@ static int knn2_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t*
     int rc;
     // (output rows whose second best d2 reaches kSqrtTieMin are listed in ps.fix and redone in OpenCV's float32 order)
     if (t->n > 0 && (rc = sweep_pair(ctx, *q, *t, 2, nq, nullptr, nullptr, 0, &ps)) != FM_OK) return rc;
+    if ((rc = wait_for_stream(ctx, consumer)) != FM_OK) return rc;
     hipLaunchKernelGGL(knn2_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
                        ps.partial, ps.nsplit, ps.ncols_alloc, nq, d_idx, d_dist, ps.f32_keys, ps.fix);
     HIP_TRY(ctx, hipGetLastError());
@@ -1484,6 +1486,137 @@ extern "C" int fm_xcheck1(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32
 {
     if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return xcheck1_bin(ctx, q, t, tidx, dist);
     return xcheck_common(ctx, q, t, false, 0.0, tidx, dist, nullptr, nullptr, nullptr, "fm_xcheck1");
+}
+
+// ---------------------------------------------------------------------------------------
+// results left in caller-supplied device memory: fm_knn_dev, fm_xcheck1_dev, fm_knn2_ratio_dev
+// ---------------------------------------------------------------------------------------
+// The host forms' pipelines on the context's stream, with the merge / finalize / compaction kernels given the caller's
+// pointers: nothing is copied to the host and nothing waits for the device.  wait_for_stream(consumer) sits in front of
+// the first kernel that writes the caller's arrays (the sweep before it overlaps whatever the consumer stream still does
+// with them), results_written() behind the last.  The calls are not accounted in fm_stats (no synchronisation to read the
+// events at).
+static int results_written(fm_ctx* ctx, void* consumer)
+{
+    if (consumer == FM_NO_STREAM) return FM_OK;
+    if (!ctx->ev_results) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_results, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_results, ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent((hipStream_t)consumer, ctx->ev_results, 0));
+    return FM_OK;
+}
+
+// k = 1: the first column of the top-2 sweep's [n][2] lists
+__global__ void knn_first_col_kernel(const int32_t* __restrict__ idx2, const float* __restrict__ dist2, int64_t n,
+                                     int32_t* __restrict__ idx, float* __restrict__ dist)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { idx[i] = idx2[2 * i]; dist[i] = dist2[2 * i]; }
+}
+
+extern "C" int fm_knn_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k, int32_t* d_idx, float* d_dist, void* consumer_stream)
+{
+    int rc = check_pair(ctx, q, t, "fm_knn_dev", true);
+    if (rc != FM_OK) return rc;
+    if (k < 1) return fail(ctx, FM_EINVAL, "fm_knn_dev: k must be at least 1");
+    if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_knn_dev: k above 8 is not built");
+    const int64_t nq = q->n;
+    if (nq == 0) return FM_OK;
+    if (!d_idx || !d_dist) return fail(ctx, FM_EINVAL, "fm_knn_dev: output pointer is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_ptr(ctx, d_idx, "fm_knn_dev", "d_idx")) != FM_OK || (rc = check_device_ptr(ctx, d_dist, "fm_knn_dev", "d_dist")) != FM_OK) return rc;
+    if (k == 2) {
+        if ((rc = knn2_device(ctx, q, t, d_idx, d_dist, consumer_stream)) != FM_OK) return rc;
+    } else if (k == 1) {
+        if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, (size_t)nq * 16 + 64)) != FM_OK) return rc;
+        int32_t* d_idx2 = (int32_t*)ctx->ws_out;
+        float* d_dist2 = (float*)((char*)ctx->ws_out + (size_t)nq * 8);
+        if ((rc = knn2_device(ctx, q, t, d_idx2, d_dist2)) != FM_OK) return rc;
+        if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+        hipLaunchKernelGGL(knn_first_col_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const int32_t*)d_idx2, (const float*)d_dist2, nq, d_idx, d_dist);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        // K9 / K11's vector-ALU lists: their merge kernel writes [nq][k] as asked for
+        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, knnk_partial_bytes(nq, t->n, k) + 64)) != FM_OK) return rc;
+        if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+        if (t->n == 0)      // (an empty bank has no kind of its own for the list kernels to dispatch on: the merge of no lists, -1 / +inf)
+            HIP_TRY(ctx, launch_knnk_merge((const unsigned long long*)ctx->ws_partial, 0, (int)nq, k, d_idx, d_dist, ctx->stream));
+        else if (q->kind == FM_BANK_BIN)
+            HIP_TRY(ctx, launch_hamming_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
+        else
+            HIP_TRY(ctx, launch_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
+    }
+    return results_written(ctx, consumer_stream);
+}
+
+extern "C" int fm_xcheck1_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* d_tidx, float* d_dist, void* consumer_stream)
+{
+    int rc = check_pair(ctx, q, t, "fm_xcheck1_dev", true);
+    if (rc != FM_OK) return rc;
+    const int64_t nq = q->n, nt = t->n;
+    if (nq == 0) return FM_OK;
+    if (!d_tidx || !d_dist) return fail(ctx, FM_EINVAL, "fm_xcheck1_dev: output pointer is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_ptr(ctx, d_tidx, "fm_xcheck1_dev", "d_tidx")) != FM_OK || (rc = check_device_ptr(ctx, d_dist, "fm_xcheck1_dev", "d_dist")) != FM_OK) return rc;
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, (size_t)nq * 8 + 64)) != FM_OK) return rc;
+    unsigned long long* d_qbest = (unsigned long long*)ctx->ws_out;
+    HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)nq * 8, ctx->stream));
+    if (nt > 0) {
+        // reverse NN: output rows = train rows, reduced over the query rows; then the election (fm_xcheck1's, all three kinds)
+        PairSweep ps;
+        if ((rc = sweep_pair(ctx, *t, *q, 1, nt, nullptr, nullptr, 0, &ps)) != FM_OK) return rc;
+        if ((rc = enqueue_election(ctx, ctx->stream, q, t, ps.partial, ps.nsplit, ps.ncols_alloc, ps.f32_keys, d_qbest, 0u, nullptr, ps.fix)) != FM_OK) return rc;
+    }
+    if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+    hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const unsigned long long*)d_qbest, nq, (const double*)nullptr, 0.0, d_tidx, d_dist, (double*)nullptr,
+                       (uint8_t*)nullptr, (unsigned long long*)nullptr, (int*)nullptr, (unsigned long long*)nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    return results_written(ctx, consumer_stream);
+}
+
+extern "C" int fm_knn2_ratio_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap, int32_t* d_rows,
+                                 int64_t* d_count, int64_t* n_accepted, void* consumer_stream)
+{
+    int rc = check_pair(ctx, q, t, "fm_knn2_ratio_dev", true);
+    if (rc != FM_OK) return rc;
+    if (n_accepted) *n_accepted = 0;
+    if (cap < 0 || !d_count || (cap > 0 && !d_rows)) return fail(ctx, FM_EINVAL, "fm_knn2_ratio_dev: bad output arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_ptr(ctx, d_count, "fm_knn2_ratio_dev", "d_count")) != FM_OK) return rc;
+    if (cap > 0 && (rc = check_device_ptr(ctx, d_rows, "fm_knn2_ratio_dev", "d_rows")) != FM_OK) return rc;
+    const int64_t nq = q->n;
+    if (nq == 0) {
+        if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 8, ctx->stream));
+        return results_written(ctx, consumer_stream);
+    }
+    const int nblk = (int)((nq + 255) / 256);
+    // knn lists | per-q tidx, dist, ratio, pass | block counts, full count
+    size_t off = 0;
+    const size_t o_i2 = carve(off, (size_t)nq * 8, 16), o_d2 = carve(off, (size_t)nq * 8, 16), o_ti = carve(off, (size_t)nq * 4, 16), o_di = carve(off, (size_t)nq * 4, 16);
+    const size_t o_ra = carve(off, (size_t)nq * 8, 16), o_pa = carve(off, (size_t)nq, 16), o_bc = carve(off, (size_t)nblk * 4, 16), o_cnt = carve(off, 16, 16);
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
+    char* b = (char*)ctx->ws_out;
+    if ((rc = knn2_device(ctx, q, t, (int32_t*)(b + o_i2), (float*)(b + o_d2))) != FM_OK) return rc;
+    hipLaunchKernelGGL(lowe_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_i2),
+                       (const float*)(b + o_d2), nq, tau, (int32_t*)(b + o_ti), (float*)(b + o_di), (double*)(b + o_ra),
+                       (uint8_t*)(b + o_pa), (int*)(b + o_bc));
+    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+    // the ordered compaction of fm_knn2_ratio, into the 12-byte rows of fm_match_accepted_dev
+    hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_ti),
+                       (const float*)(b + o_di), (const uint8_t*)(b + o_pa), (const int*)(b + o_bc), nq, cap, d_rows,
+                       (long long*)d_count, (unsigned long long*)(b + o_cnt));
+    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = results_written(ctx, consumer_stream)) != FM_OK) return rc;
+    if (n_accepted) {       // (the one host synchronisation of the integer and binary routes: the caller asked for a host number)
+        unsigned long long cnt = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&cnt, b + o_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        *n_accepted = (int64_t)cnt;
+    }
+    return FM_OK;
 }
 
 extern "C" int fm_match_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t* tidx,

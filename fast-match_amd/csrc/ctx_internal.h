@@ -58,6 +58,12 @@ struct fm_ctx {
     hipStream_t tails[kTails] = {nullptr, nullptr, nullptr};   // fm_match_accepted_batch spreads the pairs' tails over these
     hipStream_t rows_stream = nullptr;      // stream that produced the last device-resident rows (fm_gather_matches follows it)
     hipEvent_t ev_consumer = nullptr;
+    // device sources and device results (fm_bank_create_dev, fm_knn_dev ...), created on first use: "the work this caller's
+    // stream has been given so far" for the context's stream to wait on -- one event per caller stream, so that an event is
+    // only ever re-recorded on the stream it was recorded on before (see ev_tail_end) -- and "the results are written", always
+    // recorded on the context's stream, for the consumer stream to wait on
+    std::map<hipStream_t, hipEvent_t> ev_foreign;
+    hipEvent_t ev_results = nullptr;
     hipEvent_t ev_tail_end[3] = {nullptr, nullptr, nullptr};   // one per tail stream (an event re-recorded on another stream
                                                                // before its waiters ran is not a safe handshake)
     struct AsyncSlot {
@@ -127,6 +133,10 @@ static inline bool ablate_keep_bounds()
 
 namespace fm {
 int ws_ensure(fm_ctx* ctx, void** p, size_t* cap, size_t need);
+// The context's stream waits (on the device) for the work the caller's stream `s` has been given so far; FM_NO_STREAM: nothing.
+int wait_for_stream(fm_ctx* ctx, void* s);
+// p is device memory on the context's device (FM_EINVAL with a message otherwise)
+int check_device_ptr(fm_ctx* ctx, const void* p, const char* who, const char* what);
 // Device-side alias of a page-locked host buffer (fm_host_alloc / hipHostMalloc), or NULL for pageable memory.
 void* pinned_device_alias(const void* host);
 // Device -> caller memory on the context's stream (through a copy kernel and, for pageable destinations, the

@@ -241,8 +241,9 @@ HamPlan plan_hamming(int64_t ncols_pad, int64_t nred_pad);
 // stage_real (train collections): real rows per 128-row stage of `red`, an index mask per stage; null = a plain bank
 hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const HamPlan& plan, unsigned long long* partial, hipStream_t stream,
                           const int* stage_real = nullptr);
-// packed rows + FP4 image of n uploaded [n][bytes] rows (b.n_pad, b.ksteps, b.rowsb, b.rows4 set by the caller)
-hipError_t launch_hamming_prep(const uint8_t* d_src, int64_t n, int bytes, const Bank& b, hipStream_t stream);
+// packed rows + FP4 image of n device rows of `bytes` bytes, `pitch` bytes apart (0 = dense: an uploaded [n][bytes] matrix)
+// (b.n_pad, b.ksteps, b.rowsb, b.rows4 set by the caller)
+hipError_t launch_hamming_prep(const uint8_t* d_src, int64_t n, int bytes, const Bank& b, hipStream_t stream, int64_t pitch = 0);
 // k-NN lists for 1 <= k <= 8 on the vector ALUs (partial: knnk_partial_bytes)
 hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream,
                                const int* stage_real = nullptr);

@@ -39,10 +39,10 @@ constexpr int kHamNW = 4;                 // waves per workgroup
 constexpr int kHamChunk = 16 * kHamNB * kHamNW;    // output rows per workgroup (256)
 
 // ---- bank preparation -----------------------------------------------------------------------------------------------------
-// One thread per (row, byte of the padded packed width wb): packed[row][byte] (0 beyond the row's bytes or rows) and the
+// One thread per (row, byte of the padded packed width wb; source rows `pitch` bytes apart): packed[row][byte] (0 beyond the row's bytes or rows) and the
 // byte's four FP4 bytes: bit j -> nibble j (0x2 for 1, 0xA for 0), padding -> 0.
 __global__ __launch_bounds__(256)
-void ham_prep_kernel(const uint8_t* __restrict__ src, int64_t n, int bytes, int wb, int64_t n_pad,
+void ham_prep_kernel(const uint8_t* __restrict__ src, int64_t pitch, int64_t n, int bytes, int wb, int64_t n_pad,
                      uint8_t* __restrict__ packed, uint32_t* __restrict__ fp4)
 {
     const int64_t total = n_pad * wb;
@@ -50,7 +50,7 @@ void ham_prep_kernel(const uint8_t* __restrict__ src, int64_t n, int bytes, int 
         const int64_t row = i / wb;
         const int c = (int)(i % wb);
         const bool real = row < n && c < bytes;
-        const unsigned v = real ? src[row * bytes + c] : 0u;
+        const unsigned v = real ? src[row * pitch + c] : 0u;
         uint32_t w = 0;
         if (real) {
 #pragma unroll
@@ -61,12 +61,13 @@ void ham_prep_kernel(const uint8_t* __restrict__ src, int64_t n, int bytes, int 
     }
 }
 
-hipError_t launch_hamming_prep(const uint8_t* d_src, int64_t n, int bytes, const Bank& b, hipStream_t stream)
+hipError_t launch_hamming_prep(const uint8_t* d_src, int64_t n, int bytes, const Bank& b, hipStream_t stream, int64_t pitch)
 {
+    if (pitch == 0) pitch = bytes;
     const int wb = b.ksteps * 16;
     const int64_t total = b.n_pad * wb;
     const int64_t grid = std::min<int64_t>(4096, (total + 255) / 256);
-    hipLaunchKernelGGL(ham_prep_kernel, dim3((unsigned)grid), dim3(256), 0, stream, d_src, n, bytes, wb, b.n_pad, b.rowsb,
+    hipLaunchKernelGGL(ham_prep_kernel, dim3((unsigned)grid), dim3(256), 0, stream, d_src, pitch, n, bytes, wb, b.n_pad, b.rowsb,
                        (uint32_t*)b.rows4);
     return hipGetLastError();
 }

@@ -1,0 +1,147 @@
+"""Matching for descriptors that are already on the GPU: CUDA tensors in, CUDA tensors out.
+
+``matchutil`` mirrors the reference, whose descriptors are NumPy arrays from OpenCV on the CPU.  A pipeline whose extractor
+runs on the GPU (a PyTorch-ROCm model) holds its descriptors as device tensors; the functions here hand their memory to the
+library as it is (``fm_bank_create_dev``: the preparation kernels read the tensor in place, rows ``stride(0)`` apart) and
+leave the results in tensors the library's kernels write directly (``fm_knn_dev`` / ``fm_xcheck1_dev`` /
+``fm_knn2_ratio_dev``).  Nothing crosses PCIe.
+
+* ``bank(tensor, *, binary=False, float_route=False, context=None)`` -- a resident ``Bank`` from a 2-D CUDA tensor of dtype
+  uint8, float32, float16 or bfloat16 (``binary``: uint8 rows of 1 .. 64 packed bytes for Hamming distance).  On return the
+  tensor may be overwritten.
+* ``knn(q, t, k)`` -> ``(idx int32 [nq, k], dist float32 [nq, k])``, 1 <= k <= 8.
+* ``mutual_nn(q, t)`` -> ``(tidx int32 [nq], dist float32 [nq])``: the cross-checked 1-NN (-1 / inf: unmatched).
+* ``ratio_match(q, t, tau)`` -> ``(qidx, tidx, dist)`` of the rows whose first / second distance is below ``tau``.
+
+``q`` and ``t`` are ``Bank``s or CUDA tensors (a tensor becomes a bank for the call).  The values are those of
+``Context.knn`` / ``xcheck1`` / ``knn2_ratio`` on banks built from the same numbers on the host, bit for bit.
+
+Streams: ``torch.cuda.current_stream()`` is both the producer of the descriptor tensors and the consumer of the results --
+the library orders its kernels behind the one and the stream behind the other on the device, so no ``synchronize()`` is needed
+on either side (``ratio_match`` reads the accepted count back to size its outputs: one host wait).
+
+``torch`` is imported inside the functions: importing the package does not need it.  A CPU tensor, another dtype or
+another rank raises ``ValueError`` before the library is touched.  Tensors must live on the context's device.
+"""
+from . import _ffi
+
+_DTYPES = {"torch.uint8": _ffi.FM_DT_U8, "torch.float32": _ffi.FM_DT_F32, "torch.float16": _ffi.FM_DT_F16,
+           "torch.bfloat16": _ffi.FM_DT_BF16}
+
+
+def _checked(tensor, binary=False):
+    """(tensor with unit column stride, FM_DT_*) or ValueError -- before anything reaches the library."""
+    import torch
+    if not isinstance(tensor, torch.Tensor):
+        raise ValueError("descriptors must be a torch.Tensor or a resident Bank, got %s" % type(tensor).__name__)
+    if not tensor.is_cuda:
+        raise ValueError("descriptors must be a CUDA tensor (a host array goes to Context.bank / matchutil)")
+    if tensor.dim() != 2:
+        raise ValueError("descriptors must be 2-D [n, dim], got %d-D" % tensor.dim())
+    dt = _DTYPES.get(str(tensor.dtype))
+    if dt is None:
+        raise ValueError("descriptor dtype %s: uint8, float32, float16 or bfloat16 are taken" % tensor.dtype)
+    if binary:
+        if dt != _ffi.FM_DT_U8:
+            raise ValueError("binary descriptors must be uint8 (packed bits), got %s" % tensor.dtype)
+        dt = _ffi.FM_DT_BIN
+    if tensor.shape[1] < 1:
+        raise ValueError("descriptors must have at least one column")
+    # rows may be pitched (a column slice of a wider tensor); elements of a row must be adjacent.  (A one-row or empty
+    # tensor can report any row stride: below the row size it is made dense.)
+    if tensor.stride(1) != 1 or tensor.stride(0) < tensor.shape[1]:
+        tensor = tensor.contiguous()
+    return tensor, dt
+
+
+def _ctx_for(tensor, context):
+    return context if context is not None else _ffi.default_context(tensor.device.index)
+
+
+def bank(tensor, *, binary=False, float_route=False, context=None):
+    """A resident ``Bank`` from a CUDA tensor, read in place behind the current stream's work (module docstring)."""
+    import torch
+    tensor, dt = _checked(tensor, binary)
+    ctx = _ctx_for(tensor, context)
+    n, dim = tensor.shape
+    with torch.cuda.device(tensor.device):
+        stream = torch.cuda.current_stream().cuda_stream
+    return ctx.bank_from_device(tensor.data_ptr() if n else 0, dt, n, dim, tensor.stride(0) * tensor.element_size(),
+                                float_route=float_route, stream=stream)
+
+
+def _pair(q, t):
+    """Both operands as banks of one context; [banks made for this call]."""
+    ctx = next((x.ctx for x in (q, t) if isinstance(x, _ffi.Bank)), None)
+    checked = [x if isinstance(x, _ffi.Bank) else _checked(x) for x in (q, t)]      # (every refusal before any upload)
+    made = []
+    out = []
+    for x in checked:
+        if isinstance(x, _ffi.Bank):
+            out.append(x)
+            continue
+        b = bank(x[0], context=ctx)
+        ctx = b.ctx
+        made.append(b)
+        out.append(b)
+    return out[0], out[1], made
+
+
+def _stream_and_device(ctx):
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    with torch.cuda.device(dev):
+        return torch.cuda.current_stream().cuda_stream, dev
+
+
+def knn(q, t, k):
+    """k nearest train rows of every query row: ``(idx int32 [nq, k], dist float32 [nq, k])`` CUDA tensors, ascending
+    (distance, train index); -1 / inf where ``t`` has fewer than k rows.  1 <= k <= 8."""
+    import torch
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    qb, tb, made = _pair(q, t)
+    try:
+        stream, dev = _stream_and_device(qb.ctx)
+        idx = torch.empty((qb.n, k), dtype=torch.int32, device=dev)
+        dist = torch.empty((qb.n, k), dtype=torch.float32, device=dev)
+        qb.ctx.knn_dev(qb, tb, k, idx.data_ptr() if qb.n else 0, dist.data_ptr() if qb.n else 0, consumer_stream=stream)
+        return idx, dist
+    finally:
+        for b in made:
+            b.close()
+
+
+def mutual_nn(q, t):
+    """Cross-checked 1-NN (``cv2.BFMatcher(..., crossCheck=True)``): ``(tidx int32 [nq], dist float32 [nq])``."""
+    import torch
+    qb, tb, made = _pair(q, t)
+    try:
+        stream, dev = _stream_and_device(qb.ctx)
+        tidx = torch.empty(qb.n, dtype=torch.int32, device=dev)
+        dist = torch.empty(qb.n, dtype=torch.float32, device=dev)
+        qb.ctx.xcheck1_dev(qb, tb, tidx.data_ptr() if qb.n else 0, dist.data_ptr() if qb.n else 0, consumer_stream=stream)
+        return tidx, dist
+    finally:
+        for b in made:
+            b.close()
+
+
+def ratio_match(q, t, tau):
+    """The classic ratio match: ``(qidx int32 [m], tidx int32 [m], dist float32 [m])`` of the query rows whose nearest /
+    second nearest distance is below ``tau`` (float64; a zero second distance is rejected), ascending query index."""
+    import torch
+    qb, tb, made = _pair(q, t)
+    try:
+        stream, dev = _stream_and_device(qb.ctx)
+        cap = qb.n
+        rows = torch.empty((max(cap, 1), 3), dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        m = qb.ctx.knn2_ratio_dev(qb, tb, float(tau), rows.data_ptr(), count.data_ptr(), cap, want_count=True,
+                                  consumer_stream=stream)
+        rows = rows[:min(m, cap)]
+        return rows[:, 0].contiguous(), rows[:, 1].contiguous(), rows[:, 2].contiguous().view(torch.float32)
+    finally:
+        for b in made:
+            b.close()

@@ -46,9 +46,10 @@ typedef struct fm_bank fm_bank;
  * fm_bank_append_f32, fm_expand_set_log / _log_counts / _fetch_log -- and fm_expand_run_lazy refuses to resume a run
  * that did not park; revision 8, r06: additions -- fm_knn, the option "f32_bound_every" -- and rounds[i][5] of the
  * per-round log may be -2; revision 9: additions -- fm_radius_match, the option "radius_ws_bytes"; revision 10: additions --
- * FM_BANK_BIN, fm_bank_create_bin; revision 11: additions -- fm_collection_*).  A binding
+ * FM_BANK_BIN, fm_bank_create_bin; revision 11: additions -- fm_collection_*; revision 12: additions -- FM_DT_*,
+ * fm_bank_create_dev, fm_knn_dev, fm_xcheck1_dev, fm_knn2_ratio_dev).  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.            */
-#define FM_ABI_VERSION 11
+#define FM_ABI_VERSION 12
 int  fm_abi_version(void);
 
 typedef struct fm_stats {
@@ -290,6 +291,64 @@ int  fm_collection_knn2_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q,
                              int32_t* idx /*[n_images][nq][2]*/, float* dist /*[n_images][nq][2]*/);
 int  fm_collection_votes(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int32_t mode,
                          int64_t* votes /*[n_images]*/);
+
+/* ---- descriptors already on the GPU: device sources, device results ---------------------------------------------------------
+ * Every creator above takes a HOST array and every dense matcher call ends in host arrays: the shape of the reference, whose
+ * descriptors come from OpenCV on the CPU (matchutil.py:31-33 get_features -> sift().detectAndCompute; matched at matchutil.py:39-43,
+ * fastmatch.pyx:122-123, 161-162, Classic Matching.ipynb:63).  A pipeline whose extractor runs on the GPU (a PyTorch-ROCm model)
+ * holds them as device tensors and wants the matches as device tensors; these four entry points take and leave them there.
+ *
+ * fm_bank_create_dev: a bank from n rows in DEVICE memory of the context's device (hipPointerGetAttributes: a host pointer or
+ *   another device's memory is FM_EINVAL), rows row_pitch_bytes apart (0 = dense; a column slice of a wider tensor is a pitched
+ *   matrix; below dim * element size, or not a multiple of the element size: FM_EINVAL).  dtype:
+ *     FM_DT_U8   uint8 rows            -> FM_BANK_I8 (fm_bank_create_u8)
+ *     FM_DT_F32  float32 rows          -> fm_bank_create_f32's rule: all values integers in 0 .. 255 -> FM_BANK_I8, else FM_BANK_F32;
+ *                                         float_route != 0: fm_bank_create_f32_route's (FM_BANK_F32 whatever the values)
+ *     FM_DT_F16  IEEE half rows        -> widened to float32 (exact), then as FM_DT_F32
+ *     FM_DT_BF16 bfloat16 rows         -> widened to float32 (exact), then as FM_DT_F32
+ *     FM_DT_BIN  packed binary rows, dim = bytes (1 .. 64; more: FM_EUNSUPPORTED) -> FM_BANK_BIN (fm_bank_create_bin)
+ *   Another dtype is FM_EINVAL, dim > 128 FM_EUNSUPPORTED, n = 0 valid (d_rows is then not looked at).  The preparation kernels
+ *   read the caller's memory IN PLACE (typed, pitched forms of the upload kernels; half and bfloat16 widen in registers): no
+ *   staging copy, nothing crosses PCIe.  CONTRACT: the bank is the one the host creator named above builds from the same values
+ *   (for half / bfloat16: from their float32 values) -- same kind, same device arrays, same fp16 scale, filter and norm terms --
+ *   so every entry point returns the same bits for it.
+ *   Ordering: the kernels wait (on the device) for the work producer_stream has been given so far -- NULL is the null stream,
+ *   FM_NO_STREAM says the rows are complete -- so the caller needs no host synchronisation after producing the rows.  The call
+ *   itself synchronises with the context's stream as the host creators do (the route and scale decisions read flag words back),
+ *   so on return the bank owns its copy and the source is not read again: the caller may overwrite or free it.
+ *
+ * fm_knn_dev, fm_xcheck1_dev, fm_knn2_ratio_dev: fm_knn (1 <= k <= 8), fm_xcheck1 and fm_knn2_ratio with the results written to
+ *   caller-supplied DEVICE memory -- the same values in the same order, for all three bank kinds, by the same kernels: the
+ *   merge / finalize / compaction kernels are handed the caller's pointers (k = 1: one small kernel takes the first column of the
+ *   top-2 lists).  fm_knn2_ratio_dev leaves 12-byte rows {query, train, float32 distance bits} and *d_count = min(accepted, cap)
+ *   as fm_match_accepted_dev does (the ratio is d_rows' distance over the second distance and is not kept); *n_accepted (host,
+ *   may be NULL) = the full number accepted.  Output pointers must be device memory of the context's device (NULL, host memory:
+ *   FM_EINVAL; d_rows may be NULL when cap = 0); nq = 0 and nt = 0 are valid (nq = 0 writes *d_count = 0 and nothing else).
+ *   Ordering is fm_match_accepted_dev_async's: the kernels that write the caller's arrays first wait for the work consumer_stream
+ *   has been given so far (whatever last read these arrays; the sweep in front of them does not wait), and consumer_stream is
+ *   made to wait for the writes; NULL is the null stream, FM_NO_STREAM means no such stream (fm_sync, or any synchronous call on
+ *   the context, completes the work).  Everything is enqueued on the context's stream behind earlier calls.
+ *   Host synchronisation: NONE on the integer and binary routes, except fm_knn2_ratio_dev with n_accepted != NULL (one 8-byte
+ *   read).  The float32 route makes no promise: its fp16-filter / all-pairs decision is taken on the device today, but it may
+ *   come to need the host, and a workspace that has to grow frees the old one, which waits for the device on every route.
+ *   The calls are not accounted in fm_stats.
+ * Not built: device sources for collection adds (fm_collection_add_*), for fm_bank_refill_u8_async and fm_bank_append_*; device
+ *   results for fm_radius_match and fm_self_dist (fm_self_dist_batch attaches them on the device already); an enqueue-only
+ *   float32 route; tensors on another GPU than the context's (copy them over first).                                          */
+#define FM_DT_U8   1
+#define FM_DT_F32  2
+#define FM_DT_F16  3
+#define FM_DT_BF16 4
+#define FM_DT_BIN  5
+int  fm_bank_create_dev(fm_ctx* ctx, const void* d_rows, int dtype, int64_t n, int dim, int64_t row_pitch_bytes /*0 = dense*/,
+                        int float_route, void* producer_stream /*hipStream_t, NULL = null stream, or FM_NO_STREAM*/, fm_bank** bank);
+int  fm_knn_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k, int32_t* d_idx /*device [nq*k]*/,
+                float* d_dist /*device [nq*k]*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_xcheck1_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* d_tidx /*device [nq]*/, float* d_dist /*device [nq]*/,
+                    void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_knn2_ratio_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
+                       int32_t* d_rows /*device [cap][3]*/, int64_t* d_count /*device*/, int64_t* n_accepted /*host, or NULL*/,
+                       void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* Classic Ratio-Match in one call: knnMatch(q, t, k=2) then ratio = m[0].distance /
  * m[1].distance (float64) and ratio < tau  -- Classic Matching.ipynb cell 3 (JSON 59-72), the
