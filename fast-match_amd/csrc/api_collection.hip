@@ -26,11 +26,21 @@ using namespace fm;
 // nothing is uploaded again): rowsf / rowsh / normf / auxf, the fp16 planes of ALL images on the ONE power-of-two scale
 // chosen at the rebuild (an image that leaves fp16's range under it switches the filter off for the collection: K5
 // alone, same results); a padding row is a padding row of the fp16 planes (auxf = -3.4e38) and holds kCollPadF32 in every
-// float32 dimension, so the exact chain -- K8's rescoring and rescan, K5, K9 -- puts it at ~1.1e19, behind every real
-// row: masked by value, no kernel changed.  Binary: rowsb / rows4; an all-zero FP4 row is at W / 2 from everything, so K11
+// float32 dimension, so the exact chain -- K8's rescoring and rescan, K5, K9 -- puts it at >= 9.7e18, behind every real
+// row (<= 3.3e18) as long as no finite magnitude exceeds kCollF32Max, which add and the match calls enforce: masked by
+// value, no kernel changed.  Binary: rowsb / rows4; an all-zero FP4 row is at W / 2 from everything, so K11
 // masks by INDEX: its sweep and its vector-ALU kernel take the per-stage real-row table (stage_real).
 constexpr int kCollPadNorm = 1 << 26;
-constexpr float kCollPadF32 = 1.0e18f;           // 128 * (1e18)^2 = 1.28e38 stays finite in float32
+constexpr float kCollPadF32 = 1.0e18f;           // 128 * (1e18 + kCollF32Max)^2 = 1.7e38 stays finite in float32
+// Masking by value holds while a padding row is farther from every query row than every real row is.  With all finite
+// magnitudes <= L, per dimension |q - pad| >= 1e18 - L and |q - t| <= 2 L, so 3 L < 1e18 suffices (for every width: the
+// dimensions beyond `dim` hold 0 in q and t and 1e18 in a padding row).  L = FM_COLLECTION_F32_MAX = 2^57 = 1.44e17
+// (3 L = 4.3e17).  Images and query banks beyond it are refused (FM_EUNSUPPORTED), never answered differently: at
+// 9e17 a query row is nearer to the padding rows (1.1e18) than to real rows of 1e16 (1.0e19), K5 and K9 would list
+// padding (-> -1 / inf) where the filter path lists real rows.  Non-finite values are outside the limit's reach and
+// harmless: their distances are inf or NaN to real and padding rows alike, and no kernel lists those.
+constexpr float kCollF32Max = 144115188075855872.0f;      // 2^57
+static_assert(3.0 * kCollF32Max < kCollPadF32, "padding rows must stay behind every real row");
 
 struct fm_collection {
     fm_ctx* ctx = nullptr;
@@ -528,13 +538,19 @@ static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, 
                 }
             }
             if (as_f32) {
-                // rows first into the workspace's view of them: magnitude and finiteness decide the scale before anything changes
+                // the largest finite magnitude first: it decides the refusal, and the scale of a rebuild, before anything changes
+                // (what the integer-route attempt wrote lies behind `used`)
+                float hmax = 0.f;
+                {
+                    const float* f = (const float*)rows;
+                    for (int64_t i = 0; i < n * dim; ++i) { const float a = fabsf(f[i]); if (a <= 3.0e38f && a > hmax) hmax = a; }
+                }
+                if (hmax > kCollF32Max)
+                    return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": a finite magnitude above 2^57 (FM_COLLECTION_F32_MAX): a float32 "
+                                                      "collection masks its padding rows by value (1e18) and cannot hold these rows");
                 if (c->stack.kind != FM_BANK_F32) {
                     if (c->dim == 0) c->dim = dim;                // (the rebuild converts rows of this width; no rows yet if this is the first)
-                    const float* f = (const float*)rows;
-                    float vmax = 0.f;
-                    for (int64_t i = 0; i < n * dim; ++i) { const float a = fabsf(f[i]); if (a <= 3.0e38f && a > vmax) vmax = a; }
-                    if ((rc = coll_rebuild_f32(ctx, c, vmax, off + n_pad)) != FM_OK) { if (c->total == 0) c->dim = 0; return rc; }
+                    if ((rc = coll_rebuild_f32(ctx, c, hmax, off + n_pad)) != FM_OK) { if (c->total == 0) c->dim = 0; return rc; }
                 }
                 if ((rc = coll_reserve(ctx, c, off + n_pad)) != FM_OK) return rc;
                 float vmax = 0.f; bool finite = true;
@@ -655,6 +671,9 @@ static int coll_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, con
     if (c->dim != 0 && q->kind != c->stack.kind)
         return fail(ctx, FM_EINVAL, std::string(who) + ": the query bank is not of the collection's kind (fm_collection_info)");
     if (c->dim != 0 && q->dim != c->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": the query's width differs from the collection's");
+    if (c->dim != 0 && c->stack.kind == FM_BANK_F32 && q->vfin_max > kCollF32Max)
+        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": the query bank holds a finite magnitude above 2^57 (FM_COLLECTION_F32_MAX): "
+                                          "a float32 collection masks its padding rows by value (1e18); match image by image with fm_knn");
     return fm_collection_train(ctx, c);
 }
 

@@ -352,7 +352,7 @@ __global__ void bank_copy_f32_kernel(const float* __restrict__ src, int64_t n, i
 }
 
 // fp16 rows, norms and accumulator inits of a float32 bank for the fp16 filter (filter_f16.hip).
-// Pass 1: stat[0] = max |value| (float bits), stat[1] |= 1 if a value is not finite.
+// Pass 1: stat[0] = max finite |value| (float bits), stat[1] |= 1 if a value is not finite.
 __global__ __launch_bounds__(256)
 void bank_absmax_kernel(const float* __restrict__ rowsf, int64_t total, int* __restrict__ stat)
 {
@@ -360,13 +360,14 @@ void bank_absmax_kernel(const float* __restrict__ rowsf, int64_t total, int* __r
     bool bad = false;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const float v = fabsf(rowsf[i]);
-        bad |= !(v <= 3.0e38f);
-        m = fmaxf(m, v);
+        const bool fin = v <= 3.0e38f;
+        bad |= !fin;
+        m = fin ? fmaxf(m, v) : m;                    // the largest FINITE magnitude, whatever else the bank holds
     }
 #pragma unroll
     for (int mask = 1; mask < 64; mask <<= 1) m = fmaxf(m, __shfl_xor(m, mask));
-    if (__builtin_amdgcn_ballot_w64(bad) != 0ull) { if ((threadIdx.x & 63) == 0) atomicOr(stat + 1, 1); }
-    else if ((threadIdx.x & 63) == 0) atomicMax(stat, (int)__float_as_uint(m));     // m >= 0: bit order = value order
+    if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(stat + 1, 1);
+    if ((threadIdx.x & 63) == 0) atomicMax(stat, (int)__float_as_uint(m));          // m >= 0: bit order = value order
 }
 
 // Pass 2: 16 lanes per row, 8 dims per lane; rows scaled by 2^k (exact) and rounded to fp16
@@ -960,6 +961,7 @@ static int bank_create(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f
         BTRY(hipStreamSynchronize(ctx->stream));
         float vmax = 0.f;
         memcpy(&vmax, &stat[0], 4);
+        b->vfin_max = vmax;
         b->filt_ok = stat[1] == 0;
         if (b->filt_ok) {
             int ex = 0;
@@ -1065,7 +1067,7 @@ int fm::bank_prep_range(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool 
 }
 
 // ---- a float32-route bank that grows (r05: lazy targets with descriptors that are not integer valued) -----------------
-// Rows of the new range: largest magnitude (float bits) in stat[0], stat[1] |= 1 for a value that is not finite.
+// Rows of the new range: largest finite magnitude (float bits) in stat[0], stat[1] |= 1 for a value that is not finite.
 __global__ __launch_bounds__(256)
 void bank_append_f32_kernel(const float* __restrict__ src, int64_t n, int dim, float* __restrict__ dst, int* __restrict__ stat)
 {
@@ -1076,13 +1078,14 @@ void bank_append_f32_kernel(const float* __restrict__ src, int64_t n, int dim, f
         const int k = (int)(i % kDim);
         const float v = k < dim ? src[row * dim + k] : 0.f;
         dst[i] = v;
-        bad |= !(fabsf(v) <= 3.0e38f);
-        m = fmaxf(m, fabsf(v));
+        const bool fin = fabsf(v) <= 3.0e38f;
+        bad |= !fin;
+        m = fin ? fmaxf(m, fabsf(v)) : m;
     }
 #pragma unroll
     for (int mask = 1; mask < 64; mask <<= 1) m = fmaxf(m, __shfl_xor(m, mask));
-    if (__builtin_amdgcn_ballot_w64(bad) != 0ull) { if ((threadIdx.x & 63) == 0) atomicOr(stat + 1, 1); }
-    else if ((threadIdx.x & 63) == 0) atomicMax(stat, (int)__float_as_uint(m));
+    if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(stat + 1, 1);
+    if ((threadIdx.x & 63) == 0) atomicMax(stat, (int)__float_as_uint(m));
 }
 
 // An EMPTY float32-route bank with room for `capacity` rows.  The fp16 planes of a bank are scaled by ONE power of two
@@ -1175,13 +1178,14 @@ extern "C" int fm_bank_append_f32(fm_ctx* ctx, fm_bank* bank, const float* rows,
     float nmx = 0.f;
     memcpy(&nmx, &stat[0], 4);
     if (nmx > bank->nm_max) bank->nm_max = nmx;
+    if (vmax > bank->vfin_max) bank->vfin_max = vmax;
     bank->n = off + n;
     bank->n_pad = ((bank->n + kStageRows - 1) / kStageRows) * kStageRows;
     return FM_OK;
 }
 
 // Float32-route rows [off, off + n_pad) of a bank's arrays (train collections): the n host rows into rowsf (zero rows behind
-// them), *vmax = their largest magnitude, *finite = every value is finite.  Then bank_f32_range_planes: the fp16 planes of
+// them), *vmax = their largest finite magnitude, *finite = every value is finite.  Then bank_f32_range_planes: the fp16 planes of
 // the range under b.kscale (rows from n on: padding), *nm_max = the largest scaled norm.  Both synchronous.
 int fm::bank_f32_range_rows(fm_ctx* ctx, const float* rows, int64_t n, int dim, Bank& b, int64_t off, int64_t n_pad, float* vmax, bool* finite)
 {

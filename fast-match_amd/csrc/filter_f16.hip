@@ -52,6 +52,7 @@ constexpr int   kFStageBytes    = kFStageRowBytes + kFStageRows * 4;   // + aux
 constexpr int   kFP             = 4;                             // entries per lane and output row
 constexpr float kFEmpty         = -3.0e38f;                      // acc of an empty entry
 constexpr int   kFMaxRescan     = 256;                           // output rows rescan_kernel can take
+constexpr int   kFScaleMax      = 72;                            // largest bank scale the filter takes (filter_usable)
 
 struct FParams {
     const char*  col_rows;     // fp16 rows of the output rows
@@ -101,6 +102,17 @@ __device__ __forceinline__ float fmax3(float a, float b, float c)
     return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
 }
 __device__ __forceinline__ float funmap(int i) { return __int_as_float(i ^ ((i >> 31) & 0x7fffffff)); }
+
+// The key of an exactly rescored row: (bits of sqrtf(sum), row).  A chain that overflowed (sum = +inf: rows of magnitudes from
+// ~2^59 on) is no candidate -- K5 and cv::batchDistance insert strictly (inf < inf fails), so a row at distance inf is never
+// a match -- and gets no key.  The filter's ranking stays valid beside such rows: their accumulators are finite (scaled
+// units) and say d2 >= 2^128 (1 - 2^-10), behind every row whose chain is finite, within the margin.  (NaN cannot
+// arise: a bank with a non-finite value carries no fp16 planes, and a - b of finite values is never NaN.)
+__device__ __forceinline__ unsigned long long f_key(float sum, unsigned idx)
+{
+    const float d = sqrtf(sum);
+    return d < INFINITY ? (((unsigned long long)__float_as_uint(d) << 32) | idx) : ~0ull;
+}
 
 constexpr int kFAuxBase = 2 * kFStageRowBytes;       // LDS offset of the aux words (512 B per buffer)
 
@@ -591,7 +603,7 @@ void filter_kernel(FParams p)
                         v = a.z - b.z; sum = __builtin_fmaf(v, v, sum);
                         v = a.w - b.w; sum = __builtin_fmaf(v, v, sum);
                     }
-                    const unsigned long long key = ((unsigned long long)__float_as_uint(sqrtf(sum)) << 32) | (unsigned)ei[j][i];
+                    const unsigned long long key = f_key(sum, (unsigned)ei[j][i]);
                     if (key < k0) { k1 = k0; k0 = key; }
                     else if (key < k1) { k1 = key; }
                 }
@@ -683,7 +695,7 @@ void rescore_kernel(RParams p)
                 v = a.z - b.z; sum = __builtin_fmaf(v, v, sum);
                 v = a.w - b.w; sum = __builtin_fmaf(v, v, sum);
             }
-            const unsigned long long key = ((unsigned long long)__float_as_uint(sqrtf(sum)) << 32) | idx;
+            const unsigned long long key = f_key(sum, idx);
             if (key < k0) { k1 = k0; k0 = key; }
             else if (key < k1) { k1 = key; }
         }
@@ -747,7 +759,7 @@ void rescan_kernel(RParams p, int nred)
             v = a.z - b.z; sum = __builtin_fmaf(v, v, sum);
             v = a.w - b.w; sum = __builtin_fmaf(v, v, sum);
         }
-        const unsigned long long key = ((unsigned long long)__float_as_uint(sqrtf(sum)) << 32) | (unsigned)m;
+        const unsigned long long key = f_key(sum, (unsigned)m);
         if (key < k0) { k1 = k0; k0 = key; }
         else if (key < k1) { k1 = key; }
     }
@@ -831,7 +843,7 @@ void tri_rescore_kernel(TParams p)
                 v = a.z - b.z; sum = __builtin_fmaf(v, v, sum);
                 v = a.w - b.w; sum = __builtin_fmaf(v, v, sum);
             }
-            const unsigned long long key = ((unsigned long long)__float_as_uint(sqrtf(sum)) << 32) | idx;
+            const unsigned long long key = f_key(sum, idx);
             k0 = key < k0 ? key : k0;
         }
     }
@@ -911,7 +923,16 @@ bool filter_usable(const Bank& cols, const Bank& red)
 {
     if (!cols.filt_ok || !red.filt_ok || !cols.rowsh || !red.rowsh) return false;
     const int d = cols.kscale - red.kscale;
-    return d >= -40 && d <= 40;
+    if (d < -40 || d > 40) return false;
+    // The value window.  M bounds |A - D| RELATIVE to |c|^2 + max |m|^2, and the exact chain's underflow error is ABSOLUTE:
+    // a product v * v below 2^-126 is rounded to a multiple of 2^-149, up to 2^-150 per step and 128 * 2^-150 = 2^-143
+    // over a row, whatever the rows' size (at 1e-30 every D is 0 while the accumulators still tell the rows apart).  A bank
+    // of scale k has its largest magnitude in [2^(13-k), 2^(14-k)), so max |m|^2 >= 2^(26-2k); for k <= kFScaleMax = 72
+    // that is >= 2^-118 and the underflow error stays below 2^-25 (|c|^2 + max |m|^2), inside the slack of M beside the
+    // 2^-17 + 2^-20 + 2^-21 it already carries.  Beyond it (magnitudes under 2^-59 ~ 1.7e-18) the filter declines and K5
+    // answers.  Both banks must pass: either can be the reduced one.  No upper end: overflow of the chain is not an
+    // error of D but a row without a key (f_key), and the scaled planes do not depend on the magnitude.
+    return cols.kscale <= kFScaleMax && red.kscale <= kFScaleMax;
 }
 
 hipError_t launch_filter(const Bank& cols, const Bank& red, int ktop, const FilterPlan& pl,

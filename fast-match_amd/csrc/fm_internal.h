@@ -47,6 +47,7 @@ struct Bank {
     float    nm_max = 0.f;     // max |scaled row|^2
     int      kscale = 0;       // largest scaled magnitude lies in [2^13, 2^14)
     bool     filt_ok = false;  // every value is finite
+    float    vfin_max = 0.f;   // FM_BANK_F32: largest finite magnitude (a float32 train collection refuses one above 2^57)
     double*  selfdist = nullptr;
     // the largest self distance, as the bits of the double (the maximum of the bit patterns: a pattern at or above +inf's --
     // inf, NaN, a sign bit -- means no ratio cut, ratio_cut.h); a device word behind selfdist[cap], valid for the rows
@@ -79,7 +80,7 @@ inline Bank bank_rows_view(const Bank& b, int64_t r0, int64_t n)
 {
     Bank v;
     v.kind = b.kind; v.n = n; v.dim = b.dim;
-    v.ksteps = b.ksteps; v.kscale = b.kscale; v.filt_ok = b.filt_ok; v.nm_max = b.nm_max; v.usq_max = b.usq_max;
+    v.ksteps = b.ksteps; v.kscale = b.kscale; v.filt_ok = b.filt_ok; v.nm_max = b.nm_max; v.usq_max = b.usq_max; v.vfin_max = b.vfin_max;
     const int64_t room = (b.cap_pad > 0 ? b.cap_pad : b.n_pad) - r0;
     v.n_pad = v.cap_pad = pad128(n) < room ? pad128(n) : room;
     if (b.rows8) v.rows8 = b.rows8 + (size_t)r0 * kDim;

@@ -116,8 +116,11 @@ void knnk_f32_kernel(const float* __restrict__ qrows, int nq, const float* __res
                 v = a.z - b.z; sum = __builtin_fmaf(v, v, sum);
                 v = a.w - b.w; sum = __builtin_fmaf(v, v, sum);
             }
-            const unsigned long long key = ((unsigned long long)__float_as_uint(sqrtf(sum)) << 32) | (unsigned)(base + r);
-            if (key < keys[K - 1]) knnk_insert<K>(keys, key);
+            // (a distance of +inf -- the chain overflowed, or a row holds an inf -- or NaN is no candidate: K5 and OpenCV
+            // insert strictly, d < inf; its bits would otherwise make a key below "none")
+            const float d = sqrtf(sum);
+            const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(base + r);
+            if (d < INFINITY && key < keys[K - 1]) knnk_insert<K>(keys, key);
         }
     }
     if (live) {

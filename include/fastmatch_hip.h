@@ -241,6 +241,11 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  *     query must be a float32-route bank (fm_bank_create_f32_route for integer-valued rows).  The fp16 planes of all
  *     images share the power-of-two scale chosen at the rebuild; an image that leaves fp16's range under it (or is not
  *     finite) switches the fp16 filter off for the collection (the all-pairs float32 kernel alone: same results).
+ *     VALUE LIMIT of a float32-route collection: its padding rows are masked by value (1e18 in every dimension), which
+ *     holds while no finite magnitude exceeds FM_COLLECTION_F32_MAX = 2^57 (~1.44e17; 3 * 2^57 < 1e18).  fm_collection_add_f32
+ *     of an image with a larger finite magnitude is FM_EUNSUPPORTED, collection unchanged; so is every match call below
+ *     for a query bank that holds one (match image by image with fm_knn / fm_knn2, which have no such limit).  Non-finite
+ *     values are not counted (their distances are inf / NaN, never a match); a magnitude of exactly 2^57 is accepted.
  *   fm_collection_add_bin: binary rows of 1 .. 64 bytes (rules of fm_bank_create_bin).
  *   fm_collection_train: makes the device tables (stage -> image, real rows per stage, first row per image) current;
  *     implicit in the first match after an add.
@@ -272,6 +277,7 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  * expansion loop on a collection, a batched K8 / K11 per-image sweep, sharding a collection across GPUs, removing single
  * images, turning an integer-route collection of float32 images into a float32-route one for a non-integer QUERY.                                                                    */
 typedef struct fm_collection fm_collection;
+#define FM_COLLECTION_F32_MAX 144115188075855872.0f   /* 2^57: largest finite magnitude of a float32-route collection and its queries */
 int  fm_collection_create(fm_ctx* ctx, fm_collection** coll);
 int  fm_collection_destroy(fm_ctx* ctx, fm_collection* coll);
 int  fm_collection_clear(fm_ctx* ctx, fm_collection* coll);
