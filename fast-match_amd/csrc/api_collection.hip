@@ -237,40 +237,18 @@ __global__ void coll_fill_f32_kernel(float* __restrict__ p, int64_t n, float v)
     if (i < n) p[i] = v;
 }
 
-// Ordered compaction of the accepted rows (compact_kernel of api_match.hip with the image column): block b sums the
-// counts of the blocks before it, every accepted row writes itself at offset + rank.  Deterministic.
+// Ordered compaction of the accepted rows: compact_kernel (api_match.hip) with the image column.
 __global__ __launch_bounds__(256)
 void coll_compact_kernel(const int32_t* __restrict__ img2, const int32_t* __restrict__ tidx, const float* __restrict__ dist,
                          const double* __restrict__ ratio, const uint8_t* __restrict__ pass, const int* __restrict__ block_counts,
                          int64_t nq, int64_t cap, int32_t* __restrict__ o_q, int32_t* __restrict__ o_m, int32_t* __restrict__ o_t,
                          float* __restrict__ o_d, double* __restrict__ o_r, unsigned long long* __restrict__ npass)
 {
-    __shared__ int red[256];
-    __shared__ int wave_cnt[4];
-    const int tid = threadIdx.x;
-    int s = 0;
-    for (int b = tid; b < (int)blockIdx.x; b += 256) s += block_counts[b];
-    red[tid] = s;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if (tid < d) red[tid] += red[tid + d];
-        __syncthreads();
-    }
-    const int64_t base = red[0];
-    const int64_t q = (int64_t)blockIdx.x * 256 + tid;
-    const bool p = q < nq && pass[q];
-    const unsigned long long m = __ballot(p);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int wb = 0;
-    for (int w = 0; w < wave; ++w) wb += wave_cnt[w];
-    if (blockIdx.x == gridDim.x - 1 && tid == 0)
-        *npass = (unsigned long long)(base + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3]);
-    if (p) {
-        const int64_t dst = base + wb + __popcll(m & ((1ull << lane) - 1ull));
-        if (dst < cap) { o_q[dst] = (int32_t)q; o_m[dst] = img2[2 * q]; o_t[dst] = tidx[q]; o_d[dst] = dist[q]; o_r[dst] = ratio[q]; }
-    }
+    int64_t q, total;
+    bool p;
+    const int64_t dst = compact_slot(block_counts, pass, nq, &q, &p, &total);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *npass = (unsigned long long)total;
+    if (p && dst < cap) { o_q[dst] = (int32_t)q; o_m[dst] = img2[2 * q]; o_t[dst] = tidx[q]; o_d[dst] = dist[q]; o_r[dst] = ratio[q]; }
 }
 
 // Votes: query rows whose 2-NN list passes d0 / d1 < tau (float64; a missing or zero second distance fails, as
@@ -817,21 +795,8 @@ extern "C" int fm_collection_knn2_ratio(fm_ctx* ctx, fm_collection* c, const fm_
                        (int32_t*)(b + o_cq), (int32_t*)(b + o_cm), (int32_t*)(b + o_ct), (float*)(b + o_cd), (double*)(b + o_cr),
                        (unsigned long long*)(b + o_cnt));
     HIP_TRY(ctx, hipGetLastError());
-    unsigned long long cnt = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&cnt, b + o_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t m = (size_t)((int64_t)cnt < ccap ? (int64_t)cnt : ccap);
-    if (m) {
-        HIP_TRY(ctx, d2h(ctx, qidx, b + o_cq, m * 4));
-        HIP_TRY(ctx, d2h(ctx, img, b + o_cm, m * 4));
-        HIP_TRY(ctx, d2h(ctx, tidx, b + o_ct, m * 4));
-        HIP_TRY(ctx, d2h(ctx, dist, b + o_cd, m * 4));
-        HIP_TRY(ctx, d2h(ctx, ratio, b + o_cr, m * 8));
-    }
-    rc = cs.finish();
-    if (rc != FM_OK) return rc;
-    if (n_accepted) *n_accepted = (int64_t)cnt;
-    return FM_OK;
+    return cs.finish_rows((const unsigned long long*)(b + o_cnt), ccap,
+                          {{qidx, b + o_cq, 4}, {img, b + o_cm, 4}, {tidx, b + o_ct, 4}, {dist, b + o_cd, 4}, {ratio, b + o_cr, 8}}, n_accepted);
 }
 
 // The per-image 2-NN lists on the device: d_idx / d_dist [n_images][nq][2].  Up to "batch_group" images per launch of the

@@ -29,14 +29,14 @@ int fm::wait_for_stream(fm_ctx* ctx, void* s)
     return FM_OK;
 }
 
-int fm::check_device_ptr(fm_ctx* ctx, const void* p, const char* who, const char* what)
+int fm::check_device_ptr(fm_ctx* ctx, const void* p, const char* who, const char* what, bool same_device)
 {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice) {
         (void)hipGetLastError();
         return fail(ctx, FM_EINVAL, std::string(who) + ": " + what + " must be device memory");
     }
-    if (at.device != ctx->device)
+    if (same_device && at.device != ctx->device)
         return fail(ctx, FM_EINVAL, std::string(who) + ": " + what + " lives on device " + std::to_string(at.device) +
                                     ", the context on device " + std::to_string(ctx->device));
     return FM_OK;

@@ -2,10 +2,13 @@
 // around K1 --
 //   top-2 merge of the split partials for knnMatch(k = 2), Lowe ratio
 //   cross-check: election (reverse-NN partials -> 64-bit scatter-min), decode + float64 ratio + threshold,
-//   ordered compaction of the accepted matches (host arrays or 12-byte device rows)
+//   ordered compaction of the accepted matches (host arrays or 12-byte device rows; compact_slot, ctx_internal.h)
 //   exact repair of float32-root ties (sqrt_fix_kernel)
-// and the pipelines built from them: synchronous calls, async calls on two streams, batches of pairs that
-// share distance-kernel launches, sharded election keys, per-round launches (K4).
+// and the pipelines built from them.  One pair's sweep is sweep_pair; the tail behind a reverse top-1 sweep is
+//   xcheck_keys_device (fill, sweep, election) -> xcheck1_device (plain decode) | ratio_sync (ratio test, then the delivery
+//   its AcceptedSink names) | ratio_enqueue + enqueue_tail (the same on two streams, nothing waits);
+// batch_common groups pairs that share distance-kernel launches and calls the same functions; sharded election keys and
+// per-round launches (K4) follow.  DESIGN.md section 4 has the table.
 // Reference call sites are cited in the header next to each entry point.
 #include "ctx_internal.h"
 
@@ -171,7 +174,6 @@ __global__ void xcheck_finalize_kernel(const unsigned long long* qbest, int64_t 
                                        int* __restrict__ block_counts,
                                        unsigned long long* qbest_reset = nullptr)
 {
-    __shared__ int wave_cnt[4];
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool p = false;
     if (q < nq) {
@@ -194,16 +196,11 @@ __global__ void xcheck_finalize_kernel(const unsigned long long* qbest, int64_t 
     if (npass && !block_counts) {            // (with block counts the total comes from compact_kernel)
         if ((threadIdx.x & 63) == 0 && m) atomicAdd(npass, (unsigned long long)__popcll(m));
     }
-    if (block_counts) {                      // for the ordered compaction (compact_kernel)
-        if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = __popcll(m);
-        __syncthreads();
-        if (threadIdx.x == 0) block_counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-    }
+    if (block_counts) emit_block_count(m, block_counts);      // for the ordered compaction (compact_kernel)
 }
 
-// Ordered stream compaction of the accepted matches (ascending query index): block b sums
-// the counts of the blocks before it, then every accepted row writes itself at
-// offset + rank.  Deterministic (no atomics).
+// Ordered stream compaction of the accepted matches (ascending query index; compact_slot, ctx_internal.h) into the
+// caller's four arrays.
 __global__ void compact_kernel(const int32_t* __restrict__ tidx, const float* __restrict__ dist,
                                const double* __restrict__ ratio, const uint8_t* __restrict__ pass,
                                const int* __restrict__ block_counts, int64_t nq, int64_t cap,
@@ -211,32 +208,11 @@ __global__ void compact_kernel(const int32_t* __restrict__ tidx, const float* __
                                float* __restrict__ o_d, double* __restrict__ o_r,
                                unsigned long long* __restrict__ npass)
 {
-    __shared__ int red[256];
-    __shared__ int wave_base[4];
-    const int tid = threadIdx.x;
-    int s = 0;
-    for (int b = tid; b < (int)blockIdx.x; b += 256) s += block_counts[b];
-    red[tid] = s;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if (tid < d) red[tid] += red[tid + d];
-        __syncthreads();
-    }
-    const int64_t base = red[0];
-    const int64_t q = (int64_t)blockIdx.x * 256 + tid;
-    const bool p = q < nq && pass[q];
-    const unsigned long long m = __ballot(p);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) wave_base[wave] = __popcll(m);
-    __syncthreads();
-    int wb = 0;
-    for (int w = 0; w < wave; ++w) wb += wave_base[w];
-    if (blockIdx.x == gridDim.x - 1 && tid == 0)       // total = everything before the last block + its own
-        *npass = (unsigned long long)(base + wave_base[0] + wave_base[1] + wave_base[2] + wave_base[3]);
-    if (p) {
-        const int64_t dst = base + wb + __popcll(m & ((1ull << lane) - 1ull));
-        if (dst < cap) { o_q[dst] = (int32_t)q; o_t[dst] = tidx[q]; o_d[dst] = dist[q]; o_r[dst] = ratio[q]; }
-    }
+    int64_t q, total;
+    bool p;
+    const int64_t dst = compact_slot(block_counts, pass, nq, &q, &p, &total);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *npass = (unsigned long long)total;
+    if (p && dst < cap) { o_q[dst] = (int32_t)q; o_t[dst] = tidx[q]; o_d[dst] = dist[q]; o_r[dst] = ratio[q]; }
 }
 
 // Same ordered compaction, but into the 12-byte rows the multi-GPU result gather ships
@@ -247,40 +223,19 @@ __global__ void compact_rows_kernel(const int32_t* __restrict__ tidx, const floa
                                     int64_t nq, int64_t cap, int32_t* __restrict__ o_rows,
                                     long long* __restrict__ o_count, unsigned long long* __restrict__ h_count)
 {
-    __shared__ int red[256];
-    __shared__ int wave_base[4];
-    const int tid = threadIdx.x;
-    int s = 0;
-    for (int b = tid; b < (int)blockIdx.x; b += 256) s += block_counts[b];
-    red[tid] = s;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if (tid < d) red[tid] += red[tid + d];
-        __syncthreads();
-    }
-    const int64_t base = red[0];
-    const int64_t q = (int64_t)blockIdx.x * 256 + tid;
-    const bool p = q < nq && pass[q];
-    const unsigned long long m = __ballot(p);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) wave_base[wave] = __popcll(m);
-    __syncthreads();
-    int wb = 0;
-    for (int w = 0; w < wave; ++w) wb += wave_base[w];
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) {
+    int64_t q, total;
+    bool p;
+    const int64_t dst = compact_slot(block_counts, pass, nq, &q, &p, &total);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
         // the device word counts the rows that are THERE (what a consumer of o_rows may index: the gather ships
         // it next to the rows); the host word keeps the full number of accepted matches
-        const long long tot = (long long)(base + wave_base[0] + wave_base[1] + wave_base[2] + wave_base[3]);
-        *o_count = tot < (long long)cap ? tot : (long long)cap;
-        if (h_count) *h_count = (unsigned long long)tot;
+        *o_count = total < cap ? (long long)total : (long long)cap;
+        if (h_count) *h_count = (unsigned long long)total;
     }
-    if (p) {
-        const int64_t dst = base + wb + __popcll(m & ((1ull << lane) - 1ull));
-        if (dst < cap) {
-            o_rows[3 * dst] = (int32_t)q;
-            o_rows[3 * dst + 1] = tidx[q];
-            o_rows[3 * dst + 2] = (int32_t)__float_as_uint(dist[q]);
-        }
+    if (p && dst < cap) {
+        o_rows[3 * dst] = (int32_t)q;
+        o_rows[3 * dst + 1] = tidx[q];
+        o_rows[3 * dst + 2] = (int32_t)__float_as_uint(dist[q]);
     }
 }
 
@@ -310,7 +265,6 @@ __global__ void lowe_kernel(const int32_t* __restrict__ idx2, const float* __res
                             double* __restrict__ ratio, uint8_t* __restrict__ pass,
                             int* __restrict__ block_counts)
 {
-    __shared__ int wave_cnt[4];
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool p = false;
     if (q < nq) {
@@ -322,10 +276,7 @@ __global__ void lowe_kernel(const int32_t* __restrict__ idx2, const float* __res
         ratio[q] = r;
         pass[q] = p ? 1 : 0;
     }
-    const unsigned long long m = __ballot(p);
-    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    emit_block_count(__ballot(p), block_counts);
 }
 
 // Self distances (cache.pyx:250-252, 271-273: [r[1].distance for r in bf_match(d, d, k = 2)]) from the split partials
@@ -840,6 +791,34 @@ extern "C" int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
     return radius_match(ctx, *q, *t, radius, radius_all, cap, offsets, idx, dist, n_total);
 }
 
+// Classic Ratio-Match up to the compaction, in ws_out: 2-NN lists | per-q tidx, dist, ratio, pass | block counts, count word |
+// `extra` bytes of the caller's own (16-byte aligned, at `rest`).  knn2_device, then lowe_kernel.
+struct LoweWs {
+    int32_t* tidx; float* dist; double* ratio; uint8_t* pass; int* bc;
+    unsigned long long* cnt;
+    char* rest;
+    int nblk;
+};
+
+static int knn2_lowe_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, size_t extra, LoweWs* w)
+{
+    const int64_t nq = q->n;
+    w->nblk = (int)((nq + 255) / 256);
+    size_t off = 0;
+    const size_t o_i2 = carve(off, (size_t)nq * 8, 16), o_d2 = carve(off, (size_t)nq * 8, 16), o_ti = carve(off, (size_t)nq * 4, 16), o_di = carve(off, (size_t)nq * 4, 16);
+    const size_t o_ra = carve(off, (size_t)nq * 8, 16), o_pa = carve(off, (size_t)nq, 16), o_bc = carve(off, (size_t)w->nblk * 4, 16), o_cnt = carve(off, 16, 16);
+    int rc;
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + extra + 64)) != FM_OK) return rc;
+    char* b = (char*)ctx->ws_out;
+    w->tidx = (int32_t*)(b + o_ti); w->dist = (float*)(b + o_di); w->ratio = (double*)(b + o_ra); w->pass = (uint8_t*)(b + o_pa);
+    w->bc = (int*)(b + o_bc); w->cnt = (unsigned long long*)(b + o_cnt); w->rest = b + off;
+    if ((rc = knn2_device(ctx, q, t, (int32_t*)(b + o_i2), (float*)(b + o_d2))) != FM_OK) return rc;
+    hipLaunchKernelGGL(lowe_kernel, dim3((unsigned)w->nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_i2),
+                       (const float*)(b + o_d2), nq, tau, w->tidx, w->dist, w->ratio, w->pass, w->bc);
+    HIP_TRY(ctx, hipGetLastError());
+    return FM_OK;
+}
+
 extern "C" int fm_knn2_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                              int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
 {
@@ -850,40 +829,18 @@ extern "C" int fm_knn2_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, do
     if (nq == 0) return FM_OK;
     if (cap < 0 || !qidx || !tidx || !dist || !ratio) return fail(ctx, FM_EINVAL, "fm_knn2_ratio: bad output arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int nblk = (int)((nq + 255) / 256);
     const int64_t ccap = cap < nq ? cap : nq;
-    // knn lists | per-q tidx, dist, ratio, pass | block counts, count | compacted outputs
-    size_t off = 0;
-    const size_t o_i2 = carve(off, (size_t)nq * 8, 16), o_d2 = carve(off, (size_t)nq * 8, 16), o_ti = carve(off, (size_t)nq * 4, 16), o_di = carve(off, (size_t)nq * 4, 16);
-    const size_t o_ra = carve(off, (size_t)nq * 8, 16), o_pa = carve(off, (size_t)nq, 16), o_bc = carve(off, (size_t)nblk * 4, 16), o_cnt = carve(off, 16, 16);
+    size_t off = 0;         // the compacted outputs
     const size_t o_cq = carve(off, (size_t)ccap * 4, 16), o_ct = carve(off, (size_t)ccap * 4, 16), o_cd = carve(off, (size_t)ccap * 4, 16), o_cr = carve(off, (size_t)ccap * 8, 16);
-    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
-    char* b = (char*)ctx->ws_out;
     CallScope cs(ctx);
-    if ((rc = knn2_device(ctx, q, t, (int32_t*)(b + o_i2), (float*)(b + o_d2))) != FM_OK) return rc;
-    hipLaunchKernelGGL(lowe_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_i2),
-                       (const float*)(b + o_d2), nq, tau, (int32_t*)(b + o_ti), (float*)(b + o_di), (double*)(b + o_ra),
-                       (uint8_t*)(b + o_pa), (int*)(b + o_bc));
+    LoweWs w;
+    if ((rc = knn2_lowe_device(ctx, q, t, tau, off, &w)) != FM_OK) return rc;
+    char* b = w.rest;
+    hipLaunchKernelGGL(compact_kernel, dim3((unsigned)w.nblk), dim3(256), 0, ctx->stream, (const int32_t*)w.tidx, (const float*)w.dist,
+                       (const double*)w.ratio, (const uint8_t*)w.pass, (const int*)w.bc, nq, ccap, (int32_t*)(b + o_cq),
+                       (int32_t*)(b + o_ct), (float*)(b + o_cd), (double*)(b + o_cr), w.cnt);
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(compact_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_ti),
-                       (const float*)(b + o_di), (const double*)(b + o_ra), (const uint8_t*)(b + o_pa), (const int*)(b + o_bc),
-                       nq, ccap, (int32_t*)(b + o_cq), (int32_t*)(b + o_ct), (float*)(b + o_cd), (double*)(b + o_cr),
-                       (unsigned long long*)(b + o_cnt));
-    HIP_TRY(ctx, hipGetLastError());
-    unsigned long long cnt = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&cnt, b + o_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t m = (size_t)((int64_t)cnt < ccap ? (int64_t)cnt : ccap);
-    if (m) {
-        HIP_TRY(ctx, d2h(ctx, qidx, b + o_cq, m * 4));
-        HIP_TRY(ctx, d2h(ctx, tidx, b + o_ct, m * 4));
-        HIP_TRY(ctx, d2h(ctx, dist, b + o_cd, m * 4));
-        HIP_TRY(ctx, d2h(ctx, ratio, b + o_cr, m * 8));
-    }
-    rc = cs.finish();
-    if (rc != FM_OK) return rc;
-    if (n_accepted) *n_accepted = (int64_t)cnt;
-    return FM_OK;
+    return cs.finish_rows(w.cnt, ccap, {{qidx, b + o_cq, 4}, {tidx, b + o_ct, 4}, {dist, b + o_cd, 4}, {ratio, b + o_cr, 8}}, n_accepted);
 }
 
 static int take_timer(fm_ctx* ctx, fm_ctx::PendingTimer* tm);
@@ -1191,14 +1148,83 @@ static int take_timer(fm_ctx* ctx, fm_ctx::PendingTimer* tm)
     return FM_OK;
 }
 
-// The small kernels behind a K1 (election, decode + ratio test, ordered compaction), on stream ts,
-// which must already wait for that K1.  Host outputs (a_* = device aliases of page-locked memory) or,
-// with dev_rows, the 12-byte rows of the result gather.  Leaves the slot's bound[] / qbest[] clean.
-static int enqueue_tail(fm_ctx* ctx, hipStream_t ts, fm_ctx::AsyncSlot& sl, const SlotLayout& L, const fm_bank* q,
-                        const fm_bank* t, int64_t nq, int64_t nt, const RowReducePlan& pl, double tau, int64_t compact_cap,
-                        void* a_q, void* a_t, void* a_d, void* a_r, void* a_c,
-                        int32_t* dev_rows, long long* dev_count, hipStream_t consumer)
+// ---- the tail behind a reverse top-1 sweep: election, decode (+ ratio test), ordered compaction, delivery ---------------
+// Cross-check up to the election on the context's stream, all three bank kinds: d_qbest[q] = (float32 distance bits << 32 |
+// t_offset + train row) of the closest train row that elects q, ~0 if none.  Reverse NN: output rows = train rows, reduced
+// over the query rows.  cut: launch_rowreduce's (enqueue_ratio_cut) or null.
+static int xcheck_keys_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, unsigned t_offset, const unsigned* cut,
+                              unsigned long long* d_qbest)
 {
+    HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)q->n * 8, ctx->stream));
+    if (t->n == 0) return FM_OK;
+    PairSweep ps;
+    int rc = sweep_pair(ctx, *t, *q, 1, t->n, cut, nullptr, 0, &ps);
+    if (rc != FM_OK) return rc;
+    return enqueue_election(ctx, ctx->stream, q, t, ps.partial, ps.nsplit, ps.ncols_alloc, ps.f32_keys, d_qbest, t_offset, nullptr, ps.fix);
+}
+
+// Device-side cross-checked 1-NN into d_tidx / d_dist (device pointers; d_qbest: nq scratch words): the keys, then the plain
+// decode.  consumer (fm_xcheck1_dev: the arrays are the caller's): the stream whose work so far the decode -- the kernel that
+// writes them -- waits for, behind the sweep and the election.
+static int xcheck1_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, unsigned long long* d_qbest, int32_t* d_tidx,
+                          float* d_dist, void* consumer)
+{
+    int rc;
+    if ((rc = xcheck_keys_device(ctx, q, t, 0u, nullptr, d_qbest)) != FM_OK) return rc;
+    if ((rc = wait_for_stream(ctx, consumer)) != FM_OK) return rc;
+    hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)((q->n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const unsigned long long*)d_qbest, q->n, (const double*)nullptr, 0.0, d_tidx, d_dist, (double*)nullptr,
+                       (uint8_t*)nullptr, (unsigned long long*)nullptr, (int*)nullptr, (unsigned long long*)nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    return FM_OK;
+}
+
+// Where the rows of one pair's ratio test go.  Host form: the caller's arrays (cap < 0, fm_match_ratio: one row per query,
+// no qidx; cap >= 0: the accepted rows, compacted); device form: 12-byte rows and their count in caller device memory.
+// n_host: the host word that receives the full number of accepted rows (optional in the device form).
+struct AcceptedSink {
+    int32_t* qidx = nullptr; int32_t* tidx = nullptr; float* dist = nullptr; double* ratio = nullptr;
+    int32_t* dev_rows = nullptr; long long* dev_count = nullptr;
+    int64_t* n_host = nullptr;
+    unsigned long long* count = nullptr;   // aliased(): n_host as a kernel writes it
+    int64_t cap = -1;
+    hipStream_t consumer = kNoStream;      // device form: the stream that reads dev_rows / dev_count
+
+    bool to_device() const { return dev_rows != nullptr; }
+    // The same sink as the kernels see it: every host pointer replaced by its page-locked device alias (null: pageable).
+    AcceptedSink aliased() const
+    {
+        AcceptedSink a = *this;
+        a.qidx = (int32_t*)pinned_device_alias(qidx); a.tidx = (int32_t*)pinned_device_alias(tidx);
+        a.dist = (float*)pinned_device_alias(dist);   a.ratio = (double*)pinned_device_alias(ratio);
+        a.count = (unsigned long long*)pinned_device_alias(n_host);
+        return a;
+    }
+    // (of an aliased sink) a compaction can write everything the caller gave: all five host aliases, or, in the device form,
+    // the count word if there is one
+    bool writable() const { return to_device() ? (!n_host || count) : (qidx && tidx && dist && ratio && count); }
+};
+
+// The argument checks the ratio calls share, in the order the header documents; n_host is zeroed on the way.  A pair without
+// query rows passes: the caller returns.
+static int ratio_call_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const AcceptedSink& out, const char* who)
+{
+    int rc = check_pair(ctx, q, t, who);
+    if (rc != FM_OK) return rc;
+    if (out.n_host) *out.n_host = 0;
+    if (q->n == 0) return FM_OK;
+    if (!out.to_device() && (!out.tidx || !out.dist || (out.cap >= 0 && (!out.qidx || !out.ratio))))
+        return fail(ctx, FM_EINVAL, std::string(who) + ": output pointer is NULL");
+    if (!q->selfdist) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank has no self distances (fm_bank_set_selfdist)");
+    return FM_OK;
+}
+
+// The small kernels behind a K1 (election, decode + ratio test, ordered compaction), on stream ts,
+// which must already wait for that K1.  `al`: the pair's sink, aliased and writable.  Leaves the slot's bound[] / qbest[] clean.
+static int enqueue_tail(fm_ctx* ctx, hipStream_t ts, fm_ctx::AsyncSlot& sl, const SlotLayout& L, const fm_bank* q,
+                        const fm_bank* t, const RowReducePlan& pl, double tau, const AcceptedSink& al)
+{
+    const int64_t nq = q->n, nt = t->n;
     char* sb = (char*)sl.ws;
     unsigned long long* s_partial = (unsigned long long*)sb;
     int* s_bound = (int*)(sb + L.pbytes);
@@ -1217,54 +1243,44 @@ static int enqueue_tail(fm_ctx* ctx, hipStream_t ts, fm_ctx::AsyncSlot& sl, cons
     hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ts,
                        (const unsigned long long*)s_qbest, nq, (const double*)q->selfdist, tau, s_tidx, s_dist, s_ratio,
                        s_pass, (unsigned long long*)nullptr, s_bc, s_qbest);
-    if (dev_rows) {
+    if (al.to_device()) {
         // the rows go to the caller's device buffers, which a consumer stream (the result gather)
         // reads: the compaction waits for what that stream has been given so far (the gather that
         // last read these buffers), and the stream waits for the compaction
-        if (consumer != kNoStream) {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_consumer, consumer));
+        if (al.consumer != kNoStream) {
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_consumer, al.consumer));
             HIP_TRY(ctx, hipStreamWaitEvent(ts, ctx->ev_consumer, 0));
         }
         hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)L.nblk), dim3(256), 0, ts,
                            (const int32_t*)s_tidx, (const float*)s_dist, (const uint8_t*)s_pass,
-                           (const int*)s_bc, nq, compact_cap, dev_rows, dev_count, (unsigned long long*)a_c);
+                           (const int*)s_bc, nq, al.cap, al.dev_rows, al.dev_count, al.count);
     } else {
         hipLaunchKernelGGL(compact_kernel, dim3((unsigned)L.nblk), dim3(256), 0, ts,
                            (const int32_t*)s_tidx, (const float*)s_dist, (const double*)s_ratio, (const uint8_t*)s_pass,
-                           (const int*)s_bc, nq, compact_cap < nq ? compact_cap : nq, (int32_t*)a_q, (int32_t*)a_t,
-                           (float*)a_d, (double*)a_r, (unsigned long long*)a_c);
+                           (const int*)s_bc, nq, al.cap < nq ? al.cap : nq, al.qidx, al.tidx, al.dist, al.ratio, al.count);
     }
     HIP_TRY(ctx, hipGetLastError());
     return FM_OK;
 }
 
-static int xcheck_common(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, bool with_ratio, double tau,
-                         int32_t* tidx, float* dist, double* ratio, uint8_t* pass, int64_t* n_pass,
-                         const char* who, int64_t compact_cap = -1, int32_t* c_qidx = nullptr,
-                         int32_t* dev_rows = nullptr, long long* dev_count = nullptr, bool async_mode = false,
-                         hipStream_t consumer = kNoStream)
+// The synchronous ratio calls (fm_match_ratio, fm_match_accepted, fm_match_accepted_dev, a float32 pair inside a batch): keys,
+// decode + ratio test, then by the sink -- every row and its flag (pass: fm_match_ratio's, optional), the compaction into
+// page-locked caller arrays directly, the compaction into ws_out and the staged delivery, or the device rows.
+static int ratio_sync(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, const AcceptedSink& out, uint8_t* pass, const char* who)
 {
-    const bool compact = compact_cap >= 0;
-    const bool to_device = dev_rows != nullptr;
-    int rc = check_pair(ctx, q, t, who);
-    if (rc != FM_OK) return rc;
-    const int f32 = q->kind == FM_BANK_F32;
-    const int64_t nq = q->n, nt = t->n;
-    if (n_pass) *n_pass = 0;
-    if (nq == 0) return FM_OK;
-    if (!to_device && (!tidx || !dist || (compact && (!c_qidx || !ratio)))) return fail(ctx, FM_EINVAL, std::string(who) + ": output pointer is NULL");
-    if (with_ratio && !q->selfdist) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank has no self distances (fm_bank_set_selfdist)");
+    int rc = ratio_call_check(ctx, q, t, out, who);
+    if (rc != FM_OK || q->n == 0) return rc;
+    const bool compact = out.cap >= 0, to_device = out.to_device();
+    const int64_t nq = q->n;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // outputs: qbest u64[nq] | tidx i32[nq] | dist f32[nq] | ratio f64[nq] | pass u8[nq] | count u64
-    const size_t o_qbest = 0, o_tidx = (size_t)nq * 8, o_dist = o_tidx + (size_t)nq * 4;
-    const size_t o_ratio = (o_dist + (size_t)nq * 4 + 7) & ~(size_t)7, o_pass = o_ratio + (size_t)nq * 8;
-    const size_t o_cnt = (o_pass + (size_t)nq + 15) & ~(size_t)15;
-    // compaction: block counts | compacted qidx, tidx, dist, ratio
+    // qbest u64[nq] | tidx i32[nq] | dist f32[nq] | ratio f64[nq] | pass u8[nq] | count u64 | block counts | compacted qidx, tidx, dist, ratio
     const int nblk = (int)((nq + 255) / 256);
-    const int64_t ccap = (compact && !to_device) ? (compact_cap < nq ? compact_cap : nq) : 0;
-    const size_t o_bc = o_cnt + 16, o_cq = (o_bc + (size_t)nblk * 4 + 15) & ~(size_t)15, o_ct = o_cq + (size_t)ccap * 4;
-    const size_t o_cd = o_ct + (size_t)ccap * 4, o_cr = (o_cd + (size_t)ccap * 4 + 7) & ~(size_t)7;
-    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, o_cr + (size_t)ccap * 8 + 16)) != FM_OK) return rc;
+    const int64_t ccap = (compact && !to_device) ? (out.cap < nq ? out.cap : nq) : 0;
+    size_t off = 0;
+    const size_t o_qbest = carve(off, (size_t)nq * 8, 16), o_tidx = carve(off, (size_t)nq * 4, 16), o_dist = carve(off, (size_t)nq * 4, 16);
+    const size_t o_ratio = carve(off, (size_t)nq * 8, 16), o_pass = carve(off, (size_t)nq, 16), o_cnt = carve(off, 16, 16), o_bc = carve(off, (size_t)nblk * 4, 16);
+    const size_t o_cq = carve(off, (size_t)ccap * 4, 16), o_ct = carve(off, (size_t)ccap * 4, 16), o_cd = carve(off, (size_t)ccap * 4, 16), o_cr = carve(off, (size_t)ccap * 8, 16);
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 16)) != FM_OK) return rc;
     char* base = (char*)ctx->ws_out;
     unsigned long long* d_qbest = (unsigned long long*)(base + o_qbest);
     int32_t* d_tidx = (int32_t*)(base + o_tidx);
@@ -1272,135 +1288,109 @@ static int xcheck_common(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, bool w
     double* d_ratio = (double*)(base + o_ratio);
     uint8_t* d_pass = (uint8_t*)(base + o_pass);
     unsigned long long* d_cnt = (unsigned long long*)(base + o_cnt);
-
-    if (async_mode && f32) return fail(ctx, FM_EINVAL, std::string(who) + ": needs integer-valued banks");
-    if (async_mode) {
-        // (reverse NN: output rows = train rows, reduced over the query rows; the slot owns the sweep's workspace)
-        const RowReducePlan pl = plan_rowreduce(t->n_pad, q->n_pad, ctx->tune);
-        // Enqueue and return: outputs (and the count) are page-locked caller memory the compaction
-        // kernel writes directly; the events of this call are read at fm_sync.
-        void* a_q = pinned_device_alias(c_qidx); void* a_t = pinned_device_alias(tidx);
-        void* a_d = pinned_device_alias(dist);   void* a_r = pinned_device_alias(ratio);
-        void* a_c = n_pass ? pinned_device_alias(n_pass) : nullptr;
-        if (to_device ? (n_pass && !a_c) : (!a_q || !a_t || !a_d || !a_r || !a_c))
-            return fail(ctx, FM_EINVAL, std::string(who) + ": host outputs must be page-locked (fm_host_alloc)");
-        fm_ctx::PendingTimer tm;
-        if ((rc = take_timer(ctx, &tm)) != FM_OK) return rc;
-        tm.timed = nt > 0;
-        tm.pairs = nq * nt;
-        tm.bytes = bank_bytes(q) + bank_bytes(t);
-        fm_ctx::AsyncSlot& sl = ctx->aslot[ctx->aslot_next];
-        ctx->aslot_next ^= 1;
-        const SlotLayout L = slot_layout(nq, nt, pl);
-        if ((rc = slot_prepare(ctx, sl, L, nq, pl, ctx->stream)) != FM_OK) return rc;
-        const bool coop = (ctx->tune.coop != 0) && pl.nsplit > 1;
-        // Every event record is a packet the K1 launches of consecutive calls queue behind; the
-        // start-of-kernel event is therefore taken for every async_time_every-th call only (those
-        // calls are the ones fm_get_stats accounts as timed K1 launches; option async_time_every, default 4).
-        const int time_every = ctx->tune.async_time_every;
-        const bool timed_call = time_every > 0 && (ctx->async_calls++ % time_every) == 0;
-        tm.timed = tm.timed && timed_call;
-        tm.call_timed = timed_call;
-        const unsigned* cut = nullptr;
-        if (nt > 0 && compact && (rc = enqueue_ratio_cut(ctx, 1, &q, tau, &cut)) != FM_OK) return rc;
-        if (timed_call) HIP_TRY(ctx, hipEventRecord(tm.k0, ctx->stream));
-        if (nt > 0)
-            HIP_TRY(ctx, launch_rowreduce(*t, *q, 1, pl, (unsigned long long*)sl.ws, coop ? (int*)((char*)sl.ws + L.pbytes) : nullptr,
-                                          (ctx->tune.glds != 0), ctx->stream, cut));
-        // (untimed calls hand over through the slot's own event, created without timing)
-        hipEvent_t handover = timed_call ? tm.k1 : sl.k_done;
-        HIP_TRY(ctx, hipEventRecord(handover, ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_tail, handover, 0));
-        if ((rc = enqueue_tail(ctx, ctx->stream_tail, sl, L, q, t, nq, nt, pl, tau, compact_cap, a_q, a_t, a_d, a_r, a_c,
-                               to_device ? dev_rows : nullptr, dev_count, consumer)) != FM_OK) return rc;
-        if (timed_call) HIP_TRY(ctx, hipEventRecord(tm.c1, ctx->stream_tail));
-        HIP_TRY(ctx, hipEventRecord(sl.tail_done, ctx->stream_tail));
-        if (to_device && consumer != kNoStream) HIP_TRY(ctx, hipStreamWaitEvent(consumer, sl.tail_done, 0));
-        ctx->rows_stream = to_device ? ctx->stream_tail : ctx->stream;
-        sl.in_use = true;
-        ctx->pending.push_back(tm);
-        return FM_OK;
-    }
+    int* d_bc = (int*)(base + o_bc);
     CallScope cs(ctx);
-    HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)nq * 8, ctx->stream));
-    if (!compact) HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
-    if (nt > 0) {
-        // reverse NN: output rows = train rows, reduced over the query rows
-        // (accepted-only: only rows that pass the ratio test are reported -- K1 may drop what cannot pass)
-        const unsigned* cut = nullptr;
-        if (!f32 && compact && with_ratio && (rc = enqueue_ratio_cut(ctx, 1, &q, tau, &cut)) != FM_OK) return rc;
-        PairSweep ps;
-        if ((rc = sweep_pair(ctx, *t, *q, 1, nt, cut, nullptr, 0, &ps)) != FM_OK) return rc;
-        if ((rc = enqueue_election(ctx, ctx->stream, q, t, ps.partial, ps.nsplit, ps.ncols_alloc, ps.f32_keys, d_qbest, 0u, nullptr, ps.fix)) != FM_OK) return rc;
-    }
-    hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long*)d_qbest, nq, with_ratio ? (const double*)q->selfdist : (const double*)nullptr,
-                       tau, d_tidx, d_dist, with_ratio ? d_ratio : (double*)nullptr,
-                       with_ratio ? d_pass : (uint8_t*)nullptr, with_ratio ? d_cnt : (unsigned long long*)nullptr,
-                       compact ? (int*)(base + o_bc) : (int*)nullptr);
+    if (!compact) HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 8, ctx->stream));      // (a compaction writes the count itself)
+    // (accepted-only: only rows that pass the ratio test are reported -- K1 may drop what cannot pass)
+    const unsigned* cut = nullptr;
+    if (t->n > 0 && q->kind != FM_BANK_F32 && compact && (rc = enqueue_ratio_cut(ctx, 1, &q, tau, &cut)) != FM_OK) return rc;
+    if ((rc = xcheck_keys_device(ctx, q, t, 0u, cut, d_qbest)) != FM_OK) return rc;
+    hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const unsigned long long*)d_qbest, nq,
+                       (const double*)q->selfdist, tau, d_tidx, d_dist, d_ratio, d_pass, d_cnt, compact ? d_bc : (int*)nullptr);
     HIP_TRY(ctx, hipGetLastError());
-    unsigned long long cnt = 0;
-    if (to_device) {
-        ctx->rows_stream = ctx->stream;
-        // accepted matches stay on the device as packed rows (multi-GPU gather input)
-        void* a_c = ctx->h_scratch ? pinned_device_alias(ctx->h_scratch) : nullptr;
-        hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream,
-                           (const int32_t*)d_tidx, (const float*)d_dist, (const uint8_t*)d_pass,
-                           (const int*)(base + o_bc), nq, compact_cap, dev_rows, dev_count, (unsigned long long*)a_c);
-        HIP_TRY(ctx, hipGetLastError());
-        if (!a_c) HIP_TRY(ctx, hipMemcpyAsync(&cnt, dev_count, 8, hipMemcpyDeviceToHost, ctx->stream));
-        rc = cs.finish();
-        if (rc != FM_OK) return rc;
-        if (n_pass) *n_pass = a_c ? (int64_t)ctx->h_scratch[0] : (int64_t)cnt;
-        return FM_OK;
-    }
-    if (compact) {
-        // caller-owned page-locked outputs: the compaction writes them (and the count) directly,
-        // no staging copies and a single synchronisation
-        void* a_q = pinned_device_alias(c_qidx); void* a_t = pinned_device_alias(tidx);
-        void* a_d = pinned_device_alias(dist);   void* a_r = pinned_device_alias(ratio);
-        void* a_c = ctx->h_scratch ? pinned_device_alias(ctx->h_scratch) : nullptr;
-        if (a_q && a_t && a_d && a_r && a_c && compact_cap <= nq) {
-            hipLaunchKernelGGL(compact_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream,
-                               (const int32_t*)d_tidx, (const float*)d_dist, (const double*)d_ratio, (const uint8_t*)d_pass,
-                               (const int*)(base + o_bc), nq, ccap, (int32_t*)a_q, (int32_t*)a_t,
-                               (float*)a_d, (double*)a_r, (unsigned long long*)a_c);
-            HIP_TRY(ctx, hipGetLastError());
-            rc = cs.finish();
-            if (rc != FM_OK) return rc;
-            if (n_pass) *n_pass = (int64_t)ctx->h_scratch[0];
-            return FM_OK;
-        }
-        hipLaunchKernelGGL(compact_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream,
-                           (const int32_t*)d_tidx, (const float*)d_dist, (const double*)d_ratio, (const uint8_t*)d_pass,
-                           (const int*)(base + o_bc), nq, ccap, (int32_t*)(base + o_cq), (int32_t*)(base + o_ct),
-                           (float*)(base + o_cd), (double*)(base + o_cr), d_cnt);
-        HIP_TRY(ctx, hipGetLastError());
-        // the count must be known before the copies can be sized: one tiny synchronous read
-        HIP_TRY(ctx, hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const size_t m = (size_t)((int64_t)cnt < ccap ? (int64_t)cnt : ccap);
-        if (m) {
-            HIP_TRY(ctx, d2h(ctx, c_qidx, base + o_cq, m * 4));
-            HIP_TRY(ctx, d2h(ctx, tidx, base + o_ct, m * 4));
-            HIP_TRY(ctx, d2h(ctx, dist, base + o_cd, m * 4));
-            HIP_TRY(ctx, d2h(ctx, ratio, base + o_cr, m * 8));
-        }
-        rc = cs.finish();
-        if (rc != FM_OK) return rc;
-        if (n_pass) *n_pass = (int64_t)cnt;
-        return FM_OK;
-    }
-    HIP_TRY(ctx, d2h(ctx, tidx, d_tidx, (size_t)nq * 4));
-    HIP_TRY(ctx, d2h(ctx, dist, d_dist, (size_t)nq * 4));
-    if (with_ratio) {
-        if (ratio) HIP_TRY(ctx, d2h(ctx, ratio, d_ratio, (size_t)nq * 8));
+    if (!compact) {
+        unsigned long long cnt = 0;
+        HIP_TRY(ctx, d2h(ctx, out.tidx, d_tidx, (size_t)nq * 4));
+        HIP_TRY(ctx, d2h(ctx, out.dist, d_dist, (size_t)nq * 4));
+        if (out.ratio) HIP_TRY(ctx, d2h(ctx, out.ratio, d_ratio, (size_t)nq * 8));
         if (pass) HIP_TRY(ctx, d2h(ctx, pass, d_pass, (size_t)nq));
         HIP_TRY(ctx, hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = cs.finish()) != FM_OK) return rc;
+        if (out.n_host) *out.n_host = (int64_t)cnt;
+        return FM_OK;
     }
-    rc = cs.finish();
-    if (rc != FM_OK) return rc;
-    if (n_pass) *n_pass = (int64_t)cnt;
+    // the count through the context's page-locked word where there is one: no copy, a single synchronisation
+    unsigned long long* a_c = (unsigned long long*)pinned_device_alias(ctx->h_scratch);
+    if (to_device) {
+        // accepted matches stay on the device as packed rows (multi-GPU gather input)
+        ctx->rows_stream = ctx->stream;
+        unsigned long long cnt = 0;
+        hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)d_tidx, (const float*)d_dist,
+                           (const uint8_t*)d_pass, (const int*)d_bc, nq, out.cap, out.dev_rows, out.dev_count, a_c);
+        HIP_TRY(ctx, hipGetLastError());
+        if (!a_c) HIP_TRY(ctx, hipMemcpyAsync(&cnt, out.dev_count, 8, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = cs.finish()) != FM_OK) return rc;
+        if (out.n_host) *out.n_host = a_c ? (int64_t)ctx->h_scratch[0] : (int64_t)cnt;
+        return FM_OK;
+    }
+    const AcceptedSink al = out.aliased();
+    if (al.qidx && al.tidx && al.dist && al.ratio && a_c && out.cap <= nq) {
+        // caller-owned page-locked outputs: the compaction writes them (and the count) directly, no staging copies
+        hipLaunchKernelGGL(compact_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)d_tidx, (const float*)d_dist,
+                           (const double*)d_ratio, (const uint8_t*)d_pass, (const int*)d_bc, nq, ccap, al.qidx, al.tidx, al.dist, al.ratio, a_c);
+        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = cs.finish()) != FM_OK) return rc;
+        if (out.n_host) *out.n_host = (int64_t)ctx->h_scratch[0];
+        return FM_OK;
+    }
+    hipLaunchKernelGGL(compact_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)d_tidx, (const float*)d_dist,
+                       (const double*)d_ratio, (const uint8_t*)d_pass, (const int*)d_bc, nq, ccap, (int32_t*)(base + o_cq),
+                       (int32_t*)(base + o_ct), (float*)(base + o_cd), (double*)(base + o_cr), d_cnt);
+    HIP_TRY(ctx, hipGetLastError());
+    return cs.finish_rows(d_cnt, ccap, {{out.qidx, base + o_cq, 4}, {out.tidx, base + o_ct, 4}, {out.dist, base + o_cd, 4}, {out.ratio, base + o_cr, 8}},
+                          out.n_host);
+}
+
+// The enqueue-only form of the accepted call (fm_match_accepted_async, fm_match_accepted_dev_async, an odd pair of a batch):
+// K1 on the context's stream into a workspace slot of its own, the tail on stream_tail beside the NEXT call's K1; the
+// compaction writes page-locked caller memory or the device rows, the events of the call are read at fm_sync.
+static int ratio_enqueue(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, const AcceptedSink& out, const char* who)
+{
+    int rc = ratio_call_check(ctx, q, t, out, who);
+    if (rc != FM_OK || q->n == 0) return rc;
+    const int64_t nq = q->n, nt = t->n;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (q->kind == FM_BANK_F32) return fail(ctx, FM_EINVAL, std::string(who) + ": needs integer-valued banks");
+    const AcceptedSink al = out.aliased();
+    if (!al.writable()) return fail(ctx, FM_EINVAL, std::string(who) + ": host outputs must be page-locked (fm_host_alloc)");
+    // (reverse NN: output rows = train rows, reduced over the query rows; the slot owns the sweep's workspace)
+    const RowReducePlan pl = plan_rowreduce(t->n_pad, q->n_pad, ctx->tune);
+    fm_ctx::PendingTimer tm;
+    if ((rc = take_timer(ctx, &tm)) != FM_OK) return rc;
+    tm.pairs = nq * nt;
+    tm.bytes = bank_bytes(q) + bank_bytes(t);
+    fm_ctx::AsyncSlot& sl = ctx->aslot[ctx->aslot_next];
+    ctx->aslot_next ^= 1;
+    const SlotLayout L = slot_layout(nq, nt, pl);
+    const bool coop = (ctx->tune.coop != 0) && pl.nsplit > 1;
+    // Every event record is a packet the K1 launches of consecutive calls queue behind; the
+    // start-of-kernel event is therefore taken for every async_time_every-th call only (those
+    // calls are the ones fm_get_stats accounts as timed K1 launches; option async_time_every, default 4).
+    const int time_every = ctx->tune.async_time_every;
+    const bool timed_call = time_every > 0 && (ctx->async_calls++ % time_every) == 0;
+    tm.timed = nt > 0 && timed_call;
+    tm.call_timed = timed_call;
+    const unsigned* cut = nullptr;
+    if ((rc = slot_prepare(ctx, sl, L, nq, pl, ctx->stream)) != FM_OK ||
+        (nt > 0 && (rc = enqueue_ratio_cut(ctx, 1, &q, tau, &cut)) != FM_OK)) {
+        ctx->timer_pool.push_back(tm);          // (no event of the set is recorded yet: it goes back)
+        return rc;
+    }
+    if (timed_call) HIP_TRY(ctx, hipEventRecord(tm.k0, ctx->stream));
+    if (nt > 0)
+        HIP_TRY(ctx, launch_rowreduce(*t, *q, 1, pl, (unsigned long long*)sl.ws, coop ? (int*)((char*)sl.ws + L.pbytes) : nullptr,
+                                      (ctx->tune.glds != 0), ctx->stream, cut));
+    // (untimed calls hand over through the slot's own event, created without timing)
+    hipEvent_t handover = timed_call ? tm.k1 : sl.k_done;
+    HIP_TRY(ctx, hipEventRecord(handover, ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_tail, handover, 0));
+    if ((rc = enqueue_tail(ctx, ctx->stream_tail, sl, L, q, t, pl, tau, al)) != FM_OK) return rc;
+    if (timed_call) HIP_TRY(ctx, hipEventRecord(tm.c1, ctx->stream_tail));
+    HIP_TRY(ctx, hipEventRecord(sl.tail_done, ctx->stream_tail));
+    if (al.to_device() && al.consumer != kNoStream) HIP_TRY(ctx, hipStreamWaitEvent(al.consumer, sl.tail_done, 0));
+    ctx->rows_stream = al.to_device() ? ctx->stream_tail : ctx->stream;
+    sl.in_use = true;
+    ctx->pending.push_back(tm);
     return FM_OK;
 }
 
@@ -1418,13 +1408,8 @@ extern "C" int fm_xcheck1_keys(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
 extern "C" int fm_xcheck1_keys_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int64_t t_offset, uint64_t* d_keys)
 {
     if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return check_pair(ctx, q, t, "fm_xcheck1_keys_dev");
-    if (ctx && d_keys) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, d_keys) != hipSuccess || at.type != hipMemoryTypeDevice) {
-            (void)hipGetLastError();
-            return fail(ctx, FM_EINVAL, "fm_xcheck1_keys_dev: d_keys must be device memory");
-        }
-    }
+    if (ctx && d_keys)
+        if (int rc = check_device_ptr(ctx, d_keys, "fm_xcheck1_keys_dev", "d_keys", false)) return rc;
     return xcheck1_keys_common(ctx, q, t, t_offset, d_keys, true);
 }
 
@@ -1440,24 +1425,19 @@ static int xcheck1_keys_common(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
     if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, (size_t)nq * 8 + 64)) != FM_OK) return rc;
     unsigned long long* d_qbest = (unsigned long long*)ctx->ws_out;
     CallScope cs(ctx);
-    HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)nq * 8, ctx->stream));
-    if (nt > 0) {
-        PairSweep ps;
-        if ((rc = sweep_pair(ctx, *t, *q, 1, nt, nullptr, nullptr, 0, &ps)) != FM_OK) return rc;
-        if ((rc = enqueue_election(ctx, ctx->stream, q, t, ps.partial, ps.nsplit, ps.ncols_alloc, ps.f32_keys, d_qbest, (unsigned)t_offset, nullptr, ps.fix)) != FM_OK) return rc;
-    }
+    if ((rc = xcheck_keys_device(ctx, q, t, (unsigned)t_offset, nullptr, d_qbest)) != FM_OK) return rc;
     if (keys_on_device) HIP_TRY(ctx, hipMemcpyAsync(keys, d_qbest, (size_t)nq * 8, hipMemcpyDeviceToDevice, ctx->stream));
     else HIP_TRY(ctx, d2h(ctx, keys, d_qbest, (size_t)nq * 8));
     return cs.finish();
 }
 
-// K11 crossCheck of a binary pair: the reverse top-1 sweep (output rows = train rows, reduced over the query rows) on the FP4
-// matrix cores, then the election and decode of the L2 routes on the float32-route key layout (high word = float32 bits of h).
-static int xcheck1_bin(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* tidx, float* dist)
+// crossCheck of BFMatcher for all three bank kinds (binary: K11's reverse top-1 sweep on the FP4 matrix cores; its keys are in the
+// float32-route layout, high word = float32 bits of h).
+extern "C" int fm_xcheck1(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* tidx, float* dist)
 {
     int rc = check_pair(ctx, q, t, "fm_xcheck1", true);
     if (rc != FM_OK) return rc;
-    const int64_t nq = q->n, nt = t->n;
+    const int64_t nq = q->n;
     if (nq == 0) return FM_OK;
     if (!tidx || !dist) return fail(ctx, FM_EINVAL, "fm_xcheck1: output pointer is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1467,25 +1447,10 @@ static int xcheck1_bin(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t*
     int32_t* d_tidx = (int32_t*)((char*)ctx->ws_out + (size_t)nq * 8);
     float* d_dist = (float*)((char*)ctx->ws_out + (size_t)nq * 12);
     CallScope cs(ctx);
-    HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)nq * 8, ctx->stream));
-    if (nt > 0) {
-        PairSweep ps;
-        if ((rc = sweep_pair(ctx, *t, *q, 1, 0, nullptr, nullptr, 0, &ps)) != FM_OK) return rc;
-        if ((rc = enqueue_election(ctx, ctx->stream, q, t, ps.partial, ps.nsplit, ps.ncols_alloc, ps.f32_keys, d_qbest, 0u, nullptr, nullptr)) != FM_OK) return rc;
-    }
-    hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long*)d_qbest, nq, (const double*)nullptr, 0.0, d_tidx, d_dist, (double*)nullptr,
-                       (uint8_t*)nullptr, (unsigned long long*)nullptr, (int*)nullptr, (unsigned long long*)nullptr);
-    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = xcheck1_device(ctx, q, t, d_qbest, d_tidx, d_dist, FM_NO_STREAM)) != FM_OK) return rc;
     HIP_TRY(ctx, d2h(ctx, tidx, d_tidx, (size_t)nq * 4));
     HIP_TRY(ctx, d2h(ctx, dist, d_dist, (size_t)nq * 4));
     return cs.finish();
-}
-
-extern "C" int fm_xcheck1(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* tidx, float* dist)
-{
-    if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return xcheck1_bin(ctx, q, t, tidx, dist);
-    return xcheck_common(ctx, q, t, false, 0.0, tidx, dist, nullptr, nullptr, nullptr, "fm_xcheck1");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1553,25 +1518,13 @@ extern "C" int fm_xcheck1_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, i
 {
     int rc = check_pair(ctx, q, t, "fm_xcheck1_dev", true);
     if (rc != FM_OK) return rc;
-    const int64_t nq = q->n, nt = t->n;
+    const int64_t nq = q->n;
     if (nq == 0) return FM_OK;
     if (!d_tidx || !d_dist) return fail(ctx, FM_EINVAL, "fm_xcheck1_dev: output pointer is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = check_device_ptr(ctx, d_tidx, "fm_xcheck1_dev", "d_tidx")) != FM_OK || (rc = check_device_ptr(ctx, d_dist, "fm_xcheck1_dev", "d_dist")) != FM_OK) return rc;
     if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, (size_t)nq * 8 + 64)) != FM_OK) return rc;
-    unsigned long long* d_qbest = (unsigned long long*)ctx->ws_out;
-    HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)nq * 8, ctx->stream));
-    if (nt > 0) {
-        // reverse NN: output rows = train rows, reduced over the query rows; then the election (fm_xcheck1's, all three kinds)
-        PairSweep ps;
-        if ((rc = sweep_pair(ctx, *t, *q, 1, nt, nullptr, nullptr, 0, &ps)) != FM_OK) return rc;
-        if ((rc = enqueue_election(ctx, ctx->stream, q, t, ps.partial, ps.nsplit, ps.ncols_alloc, ps.f32_keys, d_qbest, 0u, nullptr, ps.fix)) != FM_OK) return rc;
-    }
-    if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
-    hipLaunchKernelGGL(xcheck_finalize_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long*)d_qbest, nq, (const double*)nullptr, 0.0, d_tidx, d_dist, (double*)nullptr,
-                       (uint8_t*)nullptr, (unsigned long long*)nullptr, (int*)nullptr, (unsigned long long*)nullptr);
-    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = xcheck1_device(ctx, q, t, (unsigned long long*)ctx->ws_out, d_tidx, d_dist, consumer_stream)) != FM_OK) return rc;
     return results_written(ctx, consumer_stream);
 }
 
@@ -1591,45 +1544,56 @@ extern "C" int fm_knn2_ratio_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t
         HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 8, ctx->stream));
         return results_written(ctx, consumer_stream);
     }
-    const int nblk = (int)((nq + 255) / 256);
-    // knn lists | per-q tidx, dist, ratio, pass | block counts, full count
-    size_t off = 0;
-    const size_t o_i2 = carve(off, (size_t)nq * 8, 16), o_d2 = carve(off, (size_t)nq * 8, 16), o_ti = carve(off, (size_t)nq * 4, 16), o_di = carve(off, (size_t)nq * 4, 16);
-    const size_t o_ra = carve(off, (size_t)nq * 8, 16), o_pa = carve(off, (size_t)nq, 16), o_bc = carve(off, (size_t)nblk * 4, 16), o_cnt = carve(off, 16, 16);
-    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
-    char* b = (char*)ctx->ws_out;
-    if ((rc = knn2_device(ctx, q, t, (int32_t*)(b + o_i2), (float*)(b + o_d2))) != FM_OK) return rc;
-    hipLaunchKernelGGL(lowe_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_i2),
-                       (const float*)(b + o_d2), nq, tau, (int32_t*)(b + o_ti), (float*)(b + o_di), (double*)(b + o_ra),
-                       (uint8_t*)(b + o_pa), (int*)(b + o_bc));
-    HIP_TRY(ctx, hipGetLastError());
+    LoweWs w;
+    if ((rc = knn2_lowe_device(ctx, q, t, tau, 0, &w)) != FM_OK) return rc;
     if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
-    // the ordered compaction of fm_knn2_ratio, into the 12-byte rows of fm_match_accepted_dev
-    hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_ti),
-                       (const float*)(b + o_di), (const uint8_t*)(b + o_pa), (const int*)(b + o_bc), nq, cap, d_rows,
-                       (long long*)d_count, (unsigned long long*)(b + o_cnt));
+    // the ordered compaction of fm_knn2_ratio, into the 12-byte rows of fm_match_accepted_dev; w.cnt: the full count
+    hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)w.nblk), dim3(256), 0, ctx->stream, (const int32_t*)w.tidx, (const float*)w.dist,
+                       (const uint8_t*)w.pass, (const int*)w.bc, nq, cap, d_rows, (long long*)d_count, w.cnt);
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = results_written(ctx, consumer_stream)) != FM_OK) return rc;
     if (n_accepted) {       // (the one host synchronisation of the integer and binary routes: the caller asked for a host number)
         unsigned long long cnt = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&cnt, b + o_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&cnt, w.cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         *n_accepted = (int64_t)cnt;
     }
     return FM_OK;
 }
 
+// Host sink of the accepted calls: the four arrays, the count word, the capacity
+static AcceptedSink host_sink(int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_host, int64_t cap)
+{
+    AcceptedSink s;
+    s.qidx = qidx; s.tidx = tidx; s.dist = dist; s.ratio = ratio; s.n_host = n_host; s.cap = cap;
+    return s;
+}
+
+static AcceptedSink device_sink(int32_t* d_rows, int64_t* d_count, int64_t* n_host, int64_t cap, void* consumer)
+{
+    AcceptedSink s;
+    s.dev_rows = d_rows; s.dev_count = (long long*)d_count; s.n_host = n_host; s.cap = cap; s.consumer = (hipStream_t)consumer;
+    return s;
+}
+
+// d_rows and d_count are device memory, of any device (fm_match_accepted_dev and its async and batch forms)
+static int check_device_rows(fm_ctx* ctx, const void* d_rows, const void* d_count, const char* who)
+{
+    int rc = check_device_ptr(ctx, d_rows, who, "d_rows", false);
+    return rc != FM_OK ? rc : check_device_ptr(ctx, d_count, who, "d_count", false);
+}
+
 extern "C" int fm_match_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t* tidx,
                               float* dist, double* ratio, uint8_t* pass, int64_t* n_pass)
 {
-    return xcheck_common(ctx, q, t, true, tau, tidx, dist, ratio, pass, n_pass, "fm_match_ratio");
+    return ratio_sync(ctx, q, t, tau, host_sink(nullptr, tidx, dist, ratio, n_pass, -1), pass, "fm_match_ratio");
 }
 
 extern "C" int fm_match_accepted(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                                  int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
 {
     if (cap < 0) return fail(ctx, FM_EINVAL, "fm_match_accepted: cap < 0");
-    return xcheck_common(ctx, q, t, true, tau, tidx, dist, ratio, nullptr, n_accepted, "fm_match_accepted", cap, qidx);
+    return ratio_sync(ctx, q, t, tau, host_sink(qidx, tidx, dist, ratio, n_accepted, cap), nullptr, "fm_match_accepted");
 }
 
 extern "C" int fm_match_accepted_async(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
@@ -1638,8 +1602,7 @@ extern "C" int fm_match_accepted_async(fm_ctx* ctx, const fm_bank* q, const fm_b
     if (cap < 0) return fail(ctx, FM_EINVAL, "fm_match_accepted_async: cap < 0");
     if (!n_accepted) return fail(ctx, FM_EINVAL, "fm_match_accepted_async: n_accepted is NULL");
     if (q && q->n == 0) { *n_accepted = 0; }
-    return xcheck_common(ctx, q, t, true, tau, tidx, dist, ratio, nullptr, n_accepted, "fm_match_accepted_async", cap, qidx,
-                         nullptr, nullptr, true);
+    return ratio_enqueue(ctx, q, t, tau, host_sink(qidx, tidx, dist, ratio, n_accepted, cap), "fm_match_accepted_async");
 }
 
 // n image pairs in one call, enqueued like fm_match_accepted_async; runs of consecutive pairs of one
@@ -1670,12 +1633,7 @@ extern "C" int fm_match_accepted_dev_batch(fm_ctx* ctx, int32_t n, const fm_bank
         if (q[i] && t[i] && (q[i]->kind == FM_BANK_BIN || t[i]->kind == FM_BANK_BIN)) return check_pair(ctx, q[i], t[i], "fm_match_accepted_dev_batch");
     if (n > 0) {
         if (!d_rows || !d_counts) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_batch: device output pointer is NULL");
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, d_rows) != hipSuccess || at.type != hipMemoryTypeDevice ||
-            hipPointerGetAttributes(&at, d_counts) != hipSuccess || at.type != hipMemoryTypeDevice) {
-            (void)hipGetLastError();
-            return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_batch: d_rows / d_counts must be device memory");
-        }
+        if (int rc = check_device_rows(ctx, d_rows, d_counts, "fm_match_accepted_dev_batch")) return rc;
         if (h_counts && !pinned_device_alias(h_counts)) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_batch: h_counts must be page-locked (fm_host_alloc)");
     }
     return batch_common(ctx, n, q, t, tau, cap, nullptr, nullptr, nullptr, nullptr, nullptr, d_rows, d_counts, h_counts,
@@ -1688,6 +1646,11 @@ static int batch_common(fm_ctx* ctx, int32_t n, const fm_bank* const* q, const f
                         int32_t* d_rows, int64_t* d_counts, int64_t* h_counts, hipStream_t consumer)
 {
     const bool to_dev = d_rows != nullptr;
+    // pair k's sink (the consumer stream is fanned in and out around the whole batch, below)
+    auto sink_of = [&](int k) {
+        return to_dev ? device_sink(d_rows + (size_t)k * cap * 3, d_counts + k, h_counts ? h_counts + k : nullptr, cap, FM_NO_STREAM)
+                      : host_sink(qidx[k], tidx[k], dist[k], ratio[k], n_accepted[k], cap);
+    };
     if (n < 0 || cap < 0) return fail(ctx, FM_EINVAL, "fm_match_accepted_batch: n < 0 or cap < 0");
     if (n == 0) return FM_OK;
     if (!q || !t) return fail(ctx, FM_EINVAL, "fm_match_accepted_batch: NULL argument");
@@ -1755,26 +1718,19 @@ static int batch_common(fm_ctx* ctx, int32_t n, const fm_bank* const* q, const f
             // float32-route pairs have no enqueue-only form: they run synchronously, in place (their outputs
             // are complete when the batch call returns; the pairs around them stay asynchronous)
             const bool in_place = q[i]->kind == FM_BANK_F32 && q[i]->n > 0;
-            if (to_dev) {
-                int64_t* hc = h_counts ? h_counts + i : nullptr;
-                if (q[i]->n == 0) {
-                    HIP_TRY(ctx, hipMemsetAsync(d_counts + i, 0, 8, ctx->stream_tail));
-                    if (hc) *hc = 0;
-                } else {
-                    rc = xcheck_common(ctx, q[i], t[i], true, tau, nullptr, nullptr, nullptr, nullptr, hc, "fm_match_accepted_dev_batch",
-                                       cap, nullptr, d_rows + (size_t)i * cap * 3, (long long*)(d_counts + i), !in_place, kNoStream);
-                    if (rc != FM_OK) return rc;
-                }
+            const char* who = to_dev ? "fm_match_accepted_dev_batch" : "fm_match_accepted_batch";
+            const AcceptedSink out = sink_of(i);
+            if (to_dev && q[i]->n == 0) {
+                HIP_TRY(ctx, hipMemsetAsync(d_counts + i, 0, 8, ctx->stream_tail));
+                if (out.n_host) *out.n_host = 0;
             } else {
-                if (q[i]->n == 0) *n_accepted[i] = 0;
-                rc = xcheck_common(ctx, q[i], t[i], true, tau, tidx[i], dist[i], ratio[i], nullptr, n_accepted[i],
-                                   "fm_match_accepted_batch", cap, qidx[i], nullptr, nullptr, !in_place);
+                rc = in_place ? ratio_sync(ctx, q[i], t[i], tau, out, nullptr, who) : ratio_enqueue(ctx, q[i], t[i], tau, out, who);
                 if (rc != FM_OK) return rc;
             }
             ++i;
             continue;
         }
-        void* al[kRRBatchMax][5];
+        AcceptedSink al[kRRBatchMax];
         int slot_of[kRRBatchMax];
         SlotLayout L[kRRBatchMax];
         const Bank* cols[kRRBatchMax]; const Bank* red[kRRBatchMax];
@@ -1784,18 +1740,9 @@ static int batch_common(fm_ctx* ctx, int32_t n, const fm_bank* const* q, const f
         tm.timed = true; tm.call_timed = true; tm.pairs = 0; tm.bytes = 0;
         for (int j = 0; j < g; ++j) {
             const int k = i + j;
-            if (to_dev) {
-                for (int u = 0; u < 4; ++u) al[j][u] = nullptr;
-                al[j][4] = h_counts ? pinned_device_alias(h_counts + k) : nullptr;
-                if (h_counts) h_counts[k] = 0;
-            } else {
-                al[j][0] = pinned_device_alias(qidx[k]); al[j][1] = pinned_device_alias(tidx[k]);
-                al[j][2] = pinned_device_alias(dist[k]); al[j][3] = pinned_device_alias(ratio[k]);
-                al[j][4] = pinned_device_alias(n_accepted[k]);
-                for (int u = 0; u < 5; ++u)
-                    if (!al[j][u]) { ctx->timer_pool.push_back(tm); return fail(ctx, FM_EINVAL, "fm_match_accepted_batch: host outputs must be page-locked (fm_host_alloc)"); }
-                *n_accepted[k] = 0;
-            }
+            al[j] = sink_of(k).aliased();
+            if (!al[j].writable()) { ctx->timer_pool.push_back(tm); return fail(ctx, FM_EINVAL, "fm_match_accepted_batch: host outputs must be page-locked (fm_host_alloc)"); }
+            if (al[j].n_host) *al[j].n_host = 0;
             slot_of[j] = (int)(ctx->bslot_next++ % fm_ctx::kBatchSlots);
             fm_ctx::AsyncSlot& sl = ctx->bslot[(size_t)slot_of[j]];
             if (!sl.tail_done) HIP_TRY(ctx, hipEventCreateWithFlags(&sl.tail_done, hipEventDisableTiming));
@@ -1819,9 +1766,7 @@ static int batch_common(fm_ctx* ctx, int32_t n, const fm_bank* const* q, const f
             hipStream_t ts = ctx->tails[j % fm_ctx::kTails];
             fm_ctx::AsyncSlot& sl = ctx->bslot[(size_t)slot_of[j]];
             HIP_TRY(ctx, hipStreamWaitEvent(ts, tm.k1, 0));
-            if ((rc = enqueue_tail(ctx, ts, sl, L[j], q[k], t[k], q[k]->n, t[k]->n, pls[j], tau, cap, al[j][0], al[j][1], al[j][2], al[j][3],
-                                   al[j][4], to_dev ? d_rows + (size_t)k * cap * 3 : nullptr, (long long*)(to_dev ? d_counts + k : nullptr),
-                                   kNoStream)) != FM_OK) { ctx->pending.push_back(tm); return rc; }     // (events are in flight: drained at fm_sync)
+            if ((rc = enqueue_tail(ctx, ts, sl, L[j], q[k], t[k], pls[j], tau, al[j])) != FM_OK) { ctx->pending.push_back(tm); return rc; }     // (events are in flight: drained at fm_sync)
             HIP_TRY(ctx, hipEventRecord(sl.tail_done, ts));
             sl.in_use = true;
             if (j == g - 1) HIP_TRY(ctx, hipEventRecord(tm.c1, ts));
@@ -1850,15 +1795,9 @@ extern "C" int fm_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_ban
     if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return check_pair(ctx, q, t, "fm_match_accepted_dev");
     if (cap < 0) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev: cap < 0");
     if (!d_rows || !d_count) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev: device output pointer is NULL");
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, d_rows) != hipSuccess || at.type != hipMemoryTypeDevice ||
-        hipPointerGetAttributes(&at, d_count) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return fail(ctx, FM_EINVAL, "fm_match_accepted_dev: d_rows / d_count must be device memory");
-    }
+    if (int rc = check_device_rows(ctx, d_rows, d_count, "fm_match_accepted_dev")) return rc;
     if (q && q->n == 0) HIP_TRY(ctx, hipMemset(d_count, 0, 8));
-    return xcheck_common(ctx, q, t, true, tau, nullptr, nullptr, nullptr, nullptr, n_accepted, "fm_match_accepted_dev",
-                         cap, nullptr, d_rows, (long long*)d_count);
+    return ratio_sync(ctx, q, t, tau, device_sink(d_rows, d_count, n_accepted, cap, FM_NO_STREAM), nullptr, "fm_match_accepted_dev");
 }
 
 extern "C" int fm_match_accepted_dev_async(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
@@ -1868,12 +1807,7 @@ extern "C" int fm_match_accepted_dev_async(fm_ctx* ctx, const fm_bank* q, const 
     if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return check_pair(ctx, q, t, "fm_match_accepted_dev_async");
     if (cap < 0) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_async: cap < 0");
     if (!d_rows || !d_count) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_async: device output pointer is NULL");
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, d_rows) != hipSuccess || at.type != hipMemoryTypeDevice ||
-        hipPointerGetAttributes(&at, d_count) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_async: d_rows / d_count must be device memory");
-    }
+    if (int rc = check_device_rows(ctx, d_rows, d_count, "fm_match_accepted_dev_async")) return rc;
     if (q && q->n == 0) {
         HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 8, ctx->stream_tail));
         if (h_count) *h_count = 0;
@@ -1883,8 +1817,7 @@ extern "C" int fm_match_accepted_dev_async(fm_ctx* ctx, const fm_bank* q, const 
         }
         ctx->rows_stream = ctx->stream_tail;
     }
-    return xcheck_common(ctx, q, t, true, tau, nullptr, nullptr, nullptr, nullptr, h_count, "fm_match_accepted_dev_async",
-                         cap, nullptr, d_rows, (long long*)d_count, true, (hipStream_t)consumer_stream);
+    return ratio_enqueue(ctx, q, t, tau, device_sink(d_rows, d_count, h_count, cap, consumer_stream), "fm_match_accepted_dev_async");
 }
 
 extern "C" int fm_ratio_filter(fm_ctx* ctx, const float* dist, const double* selfdist, const int32_t* qrows,

@@ -11,6 +11,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 #include <map>
@@ -135,8 +136,9 @@ namespace fm {
 int ws_ensure(fm_ctx* ctx, void** p, size_t* cap, size_t need);
 // The context's stream waits (on the device) for the work the caller's stream `s` has been given so far; FM_NO_STREAM: nothing.
 int wait_for_stream(fm_ctx* ctx, void* s);
-// p is device memory on the context's device (FM_EINVAL with a message otherwise)
-int check_device_ptr(fm_ctx* ctx, const void* p, const char* who, const char* what);
+// p is device memory, and (same_device) on the context's device (FM_EINVAL with a message otherwise).  The accepted-rows
+// entry points take any device's memory, as they always have: a peer buffer is a valid destination.
+int check_device_ptr(fm_ctx* ctx, const void* p, const char* who, const char* what, bool same_device = true);
 // Device-side alias of a page-locked host buffer (fm_host_alloc / hipHostMalloc), or NULL for pageable memory.
 void* pinned_device_alias(const void* host);
 // Device -> caller memory on the context's stream (through a copy kernel and, for pageable destinations, the
@@ -210,6 +212,46 @@ __global__ void lowe_kernel(const int32_t* __restrict__ idx2, const float* __res
                             double* __restrict__ ratio, uint8_t* __restrict__ pass,
                             int* __restrict__ block_counts);
 
+// ---- ordered compaction of the accepted rows (compact_kernel, compact_rows_kernel, coll_compact_kernel) ------------------
+// A 256-thread block's count of accepted rows from its ballots `m`, for the compaction behind it (256-thread blocks).
+__device__ __forceinline__ void emit_block_count(unsigned long long m, int* __restrict__ block_counts)
+{
+    __shared__ int wave_cnt[4];
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
+// Row q = this thread's row of pass[0 .. nq), *p: it is accepted, and then its slot in the compacted arrays (ascending row
+// index): block b sums the counts of the blocks before it, every accepted row takes offset + rank.  Deterministic (no
+// atomics).  *total: the accepted rows up to and including this block's -- in the last block, all of them.
+__device__ __forceinline__ int64_t compact_slot(const int* __restrict__ block_counts, const uint8_t* __restrict__ pass, int64_t nq,
+                                                int64_t* q, bool* p, int64_t* total)
+{
+    __shared__ int red[256];
+    __shared__ int wave_cnt[4];
+    const int tid = threadIdx.x;
+    int s = 0;
+    for (int b = tid; b < (int)blockIdx.x; b += 256) s += block_counts[b];
+    red[tid] = s;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+        if (tid < d) red[tid] += red[tid + d];
+        __syncthreads();
+    }
+    const int64_t base = red[0];
+    *q = (int64_t)blockIdx.x * 256 + tid;
+    *p = *q < nq && pass[*q];
+    const unsigned long long m = __ballot(*p);
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int wb = 0;
+    for (int w = 0; w < wave; ++w) wb += wave_cnt[w];
+    *total = base + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    return base + wb + __popcll(m & ((1ull << lane) - 1ull));
+}
+
 // Brackets one API call: events for total time, stats accounting after the final sync.
 struct CallScope {
     fm_ctx* ctx;
@@ -246,6 +288,22 @@ struct CallScope {
             ctx->stats.pairs += ctx->pending_pairs;
             ctx->stats_bytes += ctx->pending_bytes;
         }
+        return FM_OK;
+    }
+    // The end of a call whose compaction left its rows in device arrays (staged delivery): the count decides how much is
+    // copied, so it is read first -- one tiny synchronous read; then m = min(count, cap) elements of every column, finish(),
+    // and the full count for the caller.
+    struct Column { void* dst; const void* src; size_t elem; };
+    int finish_rows(const unsigned long long* d_count, int64_t cap, std::initializer_list<Column> cols, int64_t* n_accepted)
+    {
+        unsigned long long cnt = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&cnt, d_count, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const size_t m = (size_t)((int64_t)cnt < cap ? (int64_t)cnt : cap);
+        if (m) for (const Column& c : cols) HIP_TRY(ctx, fm::d2h(ctx, c.dst, c.src, m * c.elem));
+        const int rc = finish();
+        if (rc != FM_OK) return rc;
+        if (n_accepted) *n_accepted = (int64_t)cnt;
         return FM_OK;
     }
 };
