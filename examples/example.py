@@ -55,3 +55,12 @@ matcher.add(database)
 votes = matcher.votes(q["descriptors"], 0.8, mode=1)               # query rows passing Lowe's test inside each image
 print("retrieval: image %d wins with %d votes (runner-up %d)" % (votes.argmax(), votes.max(), np.sort(votes)[-2]))
 assert votes.argmax() == 13 and matcher.match(q["descriptors"][:400])[0].imgIdx == 13
+
+# Fast-Match's own acceptance test against the database, image by image: (q, t) is kept when t is q's cross-checked nearest
+# neighbour inside the image and dist(q, t) / selfdist(q) < tau.  One call, one list of DMatch per image.
+three = [database[13], database[2], database[7]]
+fm_matcher = matchutil.BFMatcher(matchutil.NORM_L2)
+fm_matcher.add(three)
+per_image = fm_matcher.fastMatchEach(q["descriptors"], 0.7)
+print("fast-match acceptance per image:", [len(l) for l in per_image])
+assert len(per_image[0]) >= 390 > max(len(per_image[1]), len(per_image[2])) and all(d.imgIdx == 0 for d in per_image[0])

@@ -157,6 +157,8 @@ SYMBOLS = {
     "fm_collection_knn2_ratio": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
     "fm_collection_knn2_each": (_INT, [_P, _P, _P, _P, _P]),
     "fm_collection_votes": (_INT, [_P, _P, _P, ctypes.c_double, _I32, _P]),
+    "fm_collection_match_accepted_each": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, _P]),
+    "fm_collection_match_accepted_each_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -451,6 +453,50 @@ class Collection(object):
                                                          _ptr(v) if v.shape[0] else None))
         return v
 
+    def match_accepted_each(self, q, tau, cap=None):
+        """``fm_collection_match_accepted_each``: Fast-Match's accepted-match test of ``q`` (a bank with self distances) inside
+        every image separately -- a list of (qidx, tidx, dist, ratio) per image, slot i equal to
+        ``Context.match_accepted(q, bank(image_i), tau)``; ``tidx`` is the row inside the image.  ``cap`` (default ``q.n``)
+        bounds the rows returned per image."""
+        ni = self.info()[0]
+        cap = q.n if cap is None else int(cap)
+        kept = max(cap, 0)
+        qidx, tidx = np.empty((ni, kept), np.int32), np.empty((ni, kept), np.int32)
+        dist, ratio = np.empty((ni, kept), np.float32), np.empty((ni, kept), np.float64)
+        n = np.zeros(ni, np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_match_accepted_each(
+            self.ctx.handle, self.handle, q.handle, float(tau), cap, _ptr(qidx) if qidx.size else None,
+            _ptr(tidx) if tidx.size else None, _ptr(dist) if dist.size else None, _ptr(ratio) if ratio.size else None,
+            _ptr(n) if ni else None))
+        out = []
+        for i in range(ni):
+            m = min(int(n[i]), kept)
+            out.append((qidx[i, :m], tidx[i, :m], dist[i, :m], ratio[i, :m]))
+        return out
+
+    def accepted_votes(self, q, tau):
+        """int64[n_images]: the number of matches ``match_accepted_each`` accepts per image (its counts-only call, cap = 0:
+        only n_images words come back)."""
+        n = np.zeros(self.info()[0], np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_match_accepted_each(self.ctx.handle, self.handle, q.handle, float(tau), 0,
+                                                                       None, None, None, None, _ptr(n) if n.shape[0] else None))
+        return n
+
+    def match_accepted_each_dev(self, q, tau, rows_ptr, counts_ptr, cap, h_counts=None, consumer_stream=None):
+        """``match_accepted_each`` with device outputs (``fm_collection_match_accepted_each_dev``), as
+        ``Context.match_accepted_dev_batch``: ``rows_ptr`` = device address of an int32 [n_images, cap, 3] block (query, row
+        inside the image, float32 distance bits), ``counts_ptr`` of an int64 [n_images] array that receives min(count, cap);
+        ``h_counts`` = an int64 [n_images] host array for the full counts (the call then synchronises once) or None
+        (enqueued only); ``consumer_stream`` as in ``Context.match_accepted_dev_async``."""
+        ni = self.info()[0]
+        if h_counts is not None and (not isinstance(h_counts, np.ndarray) or h_counts.dtype != np.int64 or h_counts.size < ni
+                                     or not h_counts.flags.c_contiguous):
+            raise ValueError("h_counts must be a contiguous int64 array of n_images words")
+        self.ctx._check(self.ctx.lib.fm_collection_match_accepted_each_dev(
+            self.ctx.handle, self.handle, q.handle, float(tau), int(cap), _P(int(rows_ptr)) if rows_ptr else None,
+            _P(int(counts_ptr)) if counts_ptr else None, _ptr(h_counts) if h_counts is not None else None,
+            _stream_arg(consumer_stream)))
+
     def close(self):
         if self.handle is not None and self.ctx.handle is not None:
             self.ctx.lib.fm_collection_destroy(self.ctx.handle, self.handle)
@@ -632,7 +678,7 @@ class Context(object):
         """Per-context tuning / batch shape (fm_ctx_set_option): "batch_group", "batch_tail", "nsplit", "nb",
         "nw", "nbuf", "prio", "glds", "coop", "f32_filter", "f32_nw", "f32_nsplit", "f32_fused", "f32_lpc", "f32_bound_every",
         "async_time_every", "k1_order", "bound_every", "self_tri", "tri_stages", "refill_grid", "expand_big", "expand_huge", "expand_delegate", "expand_grow", "expand_prof",
-        "radius_ws_bytes".  Results never depend on them."""
+        "radius_ws_bytes", "coll_ws_bytes".  Results never depend on them."""
         self._check(self.lib.fm_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def get_option(self, name):
@@ -767,7 +813,7 @@ class Context(object):
         return Bank(self, h, 0, int(dim), FM_BANK_F32)
 
     def collection(self):
-        """An empty train collection (``Collection``: add / train / clear, knn / knn2_each / votes against all images)."""
+        """An empty train collection (``Collection``: add / train / clear, knn / knn2_each / votes / match_accepted_each against all images)."""
         return Collection(self)
 
     # -- operators -----------------------------------------------------------------------

@@ -15,6 +15,8 @@
 // -1 / -1 / +inf.  Lookup tables on the device, per 128-row stage: its image and its number of real rows; per image: its
 // first physical row.  Physical order = logical (image, row) order, so keys (distance, physical row) order ties the way
 // OpenCV's per-image insertion does: the earlier image, then the earlier row.
+// fm_collection_match_accepted_each (the end of this file) is the first caller that makes the stack the OUTPUT operand of a
+// sweep; what the padding rows do there is written down in front of it.
 #include "ctx_internal.h"
 
 #include <algorithm>
@@ -959,4 +961,345 @@ extern "C" int fm_collection_votes(fm_ctx* ctx, fm_collection* c, const fm_bank*
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, d2h(ctx, votes, d_votes, (size_t)ni * 8));
     return cs.finish();
+}
+
+// ---------------------------------------------------------------------------------------
+// Fast-Match's accepted-match test per image: fm_collection_match_accepted_each
+// ---------------------------------------------------------------------------------------
+// Slot i = fm_match_accepted(q, bank(T_i)): the cross-checked nearest neighbour of q inside image i, kept when
+// (double)dist / selfdist[q] < tau (fastmatch.pyx:122-124, 161-165).
+//
+// Integer route.  Which query row a train row elects does not depend on the image the train row belongs to, so the reverse
+// top-1 sweep runs ONCE over the stack (output rows = the stack's physical rows, reduced over the query rows) and only the
+// second step is per image: a segmented scatter-min into qbest[image][query].
+// The stack as the OUTPUT operand of a sweep (first use), what its padding rows do there:
+//   * an output row is read through rows8 (zero bytes) and norm (2^26) only; the aux words / kPadCinit of a padding row
+//     belong to the REDUCED side and are not read.  Its partial is a valid key with d2 = 2^26 + |q|^2 (no overflow: < 2^27)
+//     that nothing reads as a candidate: the election drops the row by index (st_real, as coll_real does).
+//   * shared bounds ("coop", bound[]): one word per OUTPUT row, read and raised only by the workgroups that sweep that same
+//     row over other splits.  A padding row's word bounds the padding row's own candidates; no real row reads it.
+//   * the ratio cut seeds an output row's threshold from its own norm: a padding row (2^26) starts above every query row's
+//     reach and keeps the empty key, which the election skips anyway.
+// Float32-root ties: a train row whose best d2 >= kSqrtTieMin shares its root with d2 + 1 goes to the tie list and is
+// redone exactly (coll_sqrt_fix1_kernel).  The list exists when sqrt_tie_possible holds for ANY image of the chunk (usq per
+// image, the query's largest norm); a row can reach the listed range only inside an image for which it holds
+// (d2 <= |q|^2 + |t|^2), so the rows listed are those fm_xcheck1 lists image by image.
+// Ratio cut: as ratio_sync (accepted-only: every reported row passes the test).  D* depends on the query bank and tau alone;
+// a candidate at d2 >= D* can win qbest[image][q] only where no acceptable row elected q in that image, and then fails the
+// ratio test: the accepted rows are those of the unseeded sweep.
+// Chunks: qbest and the decode arrays cost 25 bytes per (image, query row).  Beyond the budget (option "coll_ws_bytes"; 0 = a
+// quarter of the free device memory) the images go in chunks of consecutive images -- whose stack rows are one bank view -- ,
+// enqueued back to back on the context's stream into the same arrays; counts and compacted rows of all images are copied
+// out once, at the end.
+// Float32 route: per-image reverse sweeps (K8 / K5) enqueued back to back on the images' bank views, each followed by
+// fm_xcheck1's own election into slot i of the table; the tail is shared.
+
+// Segmented election: xcheck_scatter_kernel over the physical rows [p0, p0 + nrows) of the stack; the key's low word is the
+// row inside its image, the table slot (image - img0, query).
+__global__ void coll_elect_kernel(const unsigned long long* __restrict__ partial, int nsplit, int ncols_alloc, int64_t nrows,
+                                  unsigned p0, CollTab tab, int img0, int64_t nq, unsigned long long* __restrict__ qbest,
+                                  unsigned* __restrict__ fix)
+{
+    // four lanes per physical row, each takes every 4th split
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t t = gid >> 2;
+    const int part = (int)(gid & 3);
+    unsigned long long b = ~0ull;
+    if (t < nrows) {
+        for (int s = part; s < nsplit; s += 4) {
+            const unsigned long long v = partial[(size_t)s * ncols_alloc + t];
+            b = v < b ? v : b;
+        }
+    }
+    unsigned long long o = __shfl_xor(b, 1);
+    b = o < b ? o : b;
+    o = __shfl_xor(b, 2);
+    b = o < b ? o : b;
+    if (t >= nrows || part != 0 || b == ~0ull) return;
+    const unsigned p = p0 + (unsigned)t;
+    int32_t img, local;
+    if (!coll_lookup(tab, p, img, local)) return;          // a padding row of the stack
+    const unsigned q = (unsigned)b;
+    const unsigned hi = (unsigned)(b >> 32);
+    if (fix && hi >= kSqrtTieMin && sqrt_ties_up(hi)) { fix[4 + atomicAdd(fix, 1u)] = p; return; }
+    atomicMin(&qbest[(int64_t)(img - img0) * nq + q], ((unsigned long long)sqrt_bits(hi) << 32) | (unsigned)local);
+}
+
+// sqrt_fix_kernel<1> (api_match.hip) per image: the listed physical rows of the stack elect again, exactly, over all query
+// rows in (float32 root, query row) order; the winner's slot takes (distance bits, row inside the image).
+__global__ __launch_bounds__(256)
+void coll_sqrt_fix1_kernel(const unsigned* __restrict__ fix, const int8_t* __restrict__ stack_rows, const int32_t* __restrict__ stack_norm,
+                           const int8_t* __restrict__ q_rows, const int32_t* __restrict__ q_norm, int nq_rows, CollTab tab, int img0,
+                           int64_t nq, unsigned long long* __restrict__ qbest)
+{
+    __shared__ unsigned long long best;
+    const int tid = threadIdx.x;
+    const unsigned n = fix[0];
+    for (unsigned e = blockIdx.x; e < n; e += gridDim.x) {
+        const unsigned c = fix[4 + e];
+        if (tid == 0) best = ~0ull;
+        __syncthreads();
+        v4i cr[kDim / 16];
+#pragma unroll
+        for (int w = 0; w < kDim / 16; ++w) cr[w] = *(const v4i*)(stack_rows + (size_t)c * kDim + 16 * w);
+        const int cn = stack_norm[c];
+        unsigned long long k0 = ~0ull;
+        for (int m = tid; m < nq_rows; m += 256) {
+            int dot = 0;
+#pragma unroll
+            for (int w = 0; w < kDim / 16; ++w) {
+                const v4i y = *(const v4i*)(q_rows + (size_t)m * kDim + 16 * w);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) dot = __builtin_amdgcn_sdot4(cr[w][u], y[u], dot, false);
+            }
+            const unsigned d2 = (unsigned)(cn + q_norm[m] - 2 * dot);
+            const unsigned long long key = ((unsigned long long)sqrt_bits(d2) << 32) | (unsigned)m;
+            if (key < k0) k0 = key;
+        }
+        if (k0 != ~0ull) atomicMin(&best, k0);
+        __syncthreads();
+        if (tid == 0 && best != ~0ull) {
+            const unsigned long long g0 = best;
+            int32_t img, local;
+            if (coll_lookup(tab, c, img, local))
+                atomicMin(&qbest[(int64_t)(img - img0) * nq + (unsigned)g0], (g0 & 0xffffffff00000000ull) | (unsigned long long)(unsigned)local);
+        }
+        __syncthreads();
+    }
+}
+
+// xcheck_finalize_kernel for a chunk's table, blockIdx.y = image of the chunk: decode, the same float64 division, the flag,
+// and the block counts of the compaction behind it.
+__global__ __launch_bounds__(256)
+void coll_accept_finalize_kernel(const unsigned long long* __restrict__ qbest, int64_t nq, const double* __restrict__ selfdist, double tau,
+                                 int32_t* __restrict__ tidx, float* __restrict__ dist, double* __restrict__ ratio, uint8_t* __restrict__ pass,
+                                 int* __restrict__ block_counts)
+{
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t e = (int64_t)blockIdx.y * nq + q;
+    bool p = false;
+    if (q < nq) {
+        const unsigned long long key = qbest[e];
+        int32_t ti = -1;
+        float d = INFINITY;
+        double r = NAN;
+        if (key != ~0ull) {
+            ti = (int32_t)(unsigned)key;
+            d = __uint_as_float((unsigned)(key >> 32));
+            r = (double)d / selfdist[q];
+            p = r < tau;
+        }
+        tidx[e] = ti;
+        dist[e] = d;
+        ratio[e] = r;
+        pass[e] = p ? 1 : 0;
+    }
+    emit_block_count(__ballot(p), block_counts + (size_t)blockIdx.y * gridDim.x);
+}
+
+// Ordered compaction of image blockIdx.y's accepted rows (compact_slot) into its slot of the outputs, addressed from the
+// chunk's first image: four arrays [.][cap] (o_rows null) or 12-byte rows [.][cap][3] with o_count = the rows that are there;
+// full = the number accepted.  cap = 0: counts only.
+__global__ __launch_bounds__(256)
+void coll_accept_compact_kernel(const int32_t* __restrict__ tidx, const float* __restrict__ dist, const double* __restrict__ ratio,
+                                const uint8_t* __restrict__ pass, const int* __restrict__ block_counts, int64_t nq, int64_t cap,
+                                int32_t* __restrict__ o_q, int32_t* __restrict__ o_t, float* __restrict__ o_d, double* __restrict__ o_r,
+                                int32_t* __restrict__ o_rows, long long* __restrict__ o_count, unsigned long long* __restrict__ full)
+{
+    const int64_t i = blockIdx.y;
+    int64_t q, total;
+    bool p;
+    const int64_t dst = compact_slot(block_counts + (size_t)i * gridDim.x, pass + i * nq, nq, &q, &p, &total);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        full[i] = (unsigned long long)total;
+        if (o_count) o_count[i] = total < cap ? (long long)total : (long long)cap;
+    }
+    if (p && dst < cap) {
+        const int64_t e = i * nq + q, o = i * cap + dst;
+        if (o_rows) {
+            o_rows[3 * o] = (int32_t)q;
+            o_rows[3 * o + 1] = tidx[e];
+            o_rows[3 * o + 2] = (int32_t)__float_as_uint(dist[e]);
+        } else {
+            o_q[o] = (int32_t)q; o_t[o] = tidx[e]; o_d[o] = dist[e]; o_r[o] = ratio[e];
+        }
+    }
+}
+
+constexpr size_t kCollAcceptEntry = 25;            // qbest 8 | tidx 4 | dist 4 | ratio 8 | pass 1 bytes per (image, query row)
+constexpr int kCollAcceptMaxChunk = 65535;         // (blockIdx.y of the tail kernels)
+
+// Host form: qidx / tidx / dist / ratio [n_images][cap], n_accepted [n_images].  Device form (d_counts != null): d_rows
+// [n_images][cap][3], d_counts [n_images], h_counts host [n_images] or null.
+static int coll_accept_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* qidx, int32_t* tidx,
+                            float* dist, double* ratio, int64_t* n_accepted, int32_t* d_rows, int64_t* d_counts, int64_t* h_counts,
+                            void* consumer, bool to_dev, const char* who)
+{
+    int rc = coll_query_check(ctx, c, q, who);
+    if (rc != FM_OK) return rc;
+    if (q->kind == FM_BANK_BIN)
+        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": binary banks carry no self distances: the self-distance test is not built for a binary collection");
+    const int64_t nq = q->n, ni = (int64_t)c->rows.size();
+    if (nq > 0 && !q->selfdist) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank has no self distances (fm_bank_set_selfdist)");
+    if (cap < 0) return fail(ctx, FM_EINVAL, std::string(who) + ": cap < 0");
+    if (ni == 0) return FM_OK;
+    if (to_dev) {
+        if (!d_counts || (cap > 0 && !d_rows)) return fail(ctx, FM_EINVAL, std::string(who) + ": device output pointer is NULL");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if ((rc = check_device_ptr(ctx, d_counts, who, "d_counts", false)) != FM_OK) return rc;
+        if (cap > 0 && (rc = check_device_ptr(ctx, d_rows, who, "d_rows", false)) != FM_OK) return rc;
+    } else {
+        if (!n_accepted) return fail(ctx, FM_EINVAL, std::string(who) + ": n_accepted is NULL");
+        if (nq > 0 && cap > 0 && (!qidx || !tidx || !dist || !ratio)) return fail(ctx, FM_EINVAL, std::string(who) + ": output pointer is NULL");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+    }
+    if (nq == 0) {
+        if (to_dev) {
+            if ((rc = wait_for_stream(ctx, consumer)) != FM_OK) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, (size_t)ni * 8, ctx->stream));
+            if ((rc = results_written(ctx, consumer)) != FM_OK) return rc;
+            ctx->rows_stream = ctx->stream;
+        }
+        int64_t* hc = to_dev ? h_counts : n_accepted;
+        if (hc) for (int64_t i = 0; i < ni; ++i) hc[i] = 0;
+        return FM_OK;
+    }
+    // images per chunk from the budget
+    const int nblk = (int)((nq + 255) / 256);
+    const size_t per = (size_t)nq * kCollAcceptEntry + (size_t)nblk * 4;
+    size_t budget = (size_t)ctx->tune.coll_ws_bytes;
+    if (budget == 0) {
+        budget = (size_t)64 << 20;
+        if ((size_t)ni * per > budget) {              // (asked only where one chunk may not do)
+            size_t f = 0, t = 0;
+            HIP_TRY(ctx, hipMemGetInfo(&f, &t));
+            budget = std::max(budget, f / 4);
+        }
+    }
+    int64_t nc = (int64_t)(budget / per);
+    nc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nc, ni), kCollAcceptMaxChunk));
+    const int64_t ccap = to_dev ? 0 : (cap < nq ? cap : nq);          // rows per image kept in ws_out for the copy out
+    size_t off = 0;
+    const size_t o_full = carve(off, (size_t)ni * 8);
+    const size_t o_qbest = carve(off, (size_t)nc * nq * 8), o_ratio = carve(off, (size_t)nc * nq * 8);
+    const size_t o_tidx = carve(off, (size_t)nc * nq * 4), o_dist = carve(off, (size_t)nc * nq * 4);
+    const size_t o_pass = carve(off, (size_t)nc * nq), o_bc = carve(off, (size_t)nc * nblk * 4);
+    const size_t o_cq = carve(off, (size_t)ni * ccap * 4), o_ct = carve(off, (size_t)ni * ccap * 4), o_cd = carve(off, (size_t)ni * ccap * 4);
+    const size_t o_cr = carve(off, (size_t)ni * ccap * 8);
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
+    char* b = (char*)ctx->ws_out;
+    unsigned long long* d_full = (unsigned long long*)(b + o_full);
+    unsigned long long* d_qbest = (unsigned long long*)(b + o_qbest);
+    const bool i8 = c->stack.kind == FM_BANK_I8;
+    // the chunks' views; the sweep workspace is sized for the largest before anything is enqueued (no reallocation between chunks)
+    auto chunk_view = [&](int64_t i0, int64_t i1) {
+        const int64_t p0 = c->phys[(size_t)i0], p1 = i1 < ni ? c->phys[(size_t)i1] : c->used;
+        fm::Bank v = bank_rows_view(c->stack, p0, p1 - p0);
+        v.usq_max = 0;
+        for (int64_t i = i0; i < i1; ++i) v.usq_max = std::max(v.usq_max, c->usq[(size_t)i]);
+        return v;
+    };
+    if (i8 && c->total > 0) {
+        for (int64_t i0 = 0; i0 < ni; i0 += nc) {
+            const fm::Bank v = chunk_view(i0, std::min(ni, i0 + nc));
+            PairSweep ps;
+            if (v.n > 0 && (rc = sweep_pair_plan(ctx, v, *q, 1, v.n, &ps)) != FM_OK) return rc;
+        }
+    }
+    CallScope cs(ctx);
+    const CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
+    const unsigned* cut = nullptr;
+    if (i8 && c->total > 0 && (rc = enqueue_ratio_cut(ctx, 1, &q, tau, &cut)) != FM_OK) return rc;
+    bool timed = false;
+    for (int64_t i0 = 0; i0 < ni; i0 += nc) {
+        const int64_t i1 = std::min(ni, i0 + nc), g = i1 - i0;
+        HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)g * nq * 8, ctx->stream));
+        if (i8) {
+            const fm::Bank v = chunk_view(i0, i1);
+            if (v.n > 0) {
+                int64_t real = 0;
+                for (int64_t i = i0; i < i1; ++i) real += c->rows[(size_t)i];
+                ctx->pending_pairs += nq * real;
+                ctx->pending_bytes += bank_bytes(q) + real * 128;
+                if (!timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+                timed = true;
+                PairSweep ps;
+                if ((rc = sweep_pair(ctx, v, *q, 1, v.n, cut, nullptr, kSweepNoEvents | kSweepNoCount, &ps)) != FM_OK) return rc;
+                hipLaunchKernelGGL(coll_elect_kernel, dim3((unsigned)((v.n * 4 + 255) / 256)), dim3(256), 0, ctx->stream, ps.partial, ps.nsplit,
+                                   ps.ncols_alloc, v.n, (unsigned)c->phys[(size_t)i0], tab, (int)i0, nq, d_qbest, ps.fix);
+                HIP_TRY(ctx, hipGetLastError());
+                if (ps.fix) {
+                    hipLaunchKernelGGL(coll_sqrt_fix1_kernel, dim3(kFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)ps.fix,
+                                       (const int8_t*)c->stack.rows8, (const int32_t*)c->stack.norm, (const int8_t*)q->rows8,
+                                       (const int32_t*)q->norm, (int)nq, tab, (int)i0, nq, d_qbest);
+                    HIP_TRY(ctx, hipGetLastError());
+                }
+            }
+        } else {
+            for (int64_t i = i0; i < i1; ++i) {
+                const fm::Bank v = coll_view(c, (int)i);
+                if (v.n == 0) continue;
+                PairSweep ps;
+                if ((rc = sweep_pair(ctx, v, *q, 1, 0, nullptr, nullptr, kSweepNoEvents, &ps)) != FM_OK) return rc;
+                timed = true;                    // (the route brackets every sweep itself: the last one's events stand)
+                hipLaunchKernelGGL(xcheck_scatter_kernel, dim3((unsigned)((v.n * 4 + 255) / 256)), dim3(256), 0, ctx->stream, ps.partial,
+                                   ps.nsplit, ps.ncols_alloc, v.n, d_qbest + (i - i0) * nq, 0u, ps.f32_keys, (int*)nullptr, (unsigned*)nullptr);
+                HIP_TRY(ctx, hipGetLastError());
+            }
+        }
+        hipLaunchKernelGGL(coll_accept_finalize_kernel, dim3((unsigned)nblk, (unsigned)g), dim3(256), 0, ctx->stream,
+                           (const unsigned long long*)d_qbest, nq, (const double*)q->selfdist, tau, (int32_t*)(b + o_tidx), (float*)(b + o_dist),
+                           (double*)(b + o_ratio), (uint8_t*)(b + o_pass), (int*)(b + o_bc));
+        HIP_TRY(ctx, hipGetLastError());
+        // (device form: the first compaction is the first kernel that writes the caller's buffers)
+        if (to_dev && i0 == 0 && (rc = wait_for_stream(ctx, consumer)) != FM_OK) return rc;
+        hipLaunchKernelGGL(coll_accept_compact_kernel, dim3((unsigned)nblk, (unsigned)g), dim3(256), 0, ctx->stream,
+                           (const int32_t*)(b + o_tidx), (const float*)(b + o_dist), (const double*)(b + o_ratio), (const uint8_t*)(b + o_pass),
+                           (const int*)(b + o_bc), nq, to_dev ? cap : ccap,
+                           (int32_t*)(b + o_cq) + i0 * ccap, (int32_t*)(b + o_ct) + i0 * ccap, (float*)(b + o_cd) + i0 * ccap,
+                           (double*)(b + o_cr) + i0 * ccap, to_dev && cap > 0 ? d_rows + (size_t)i0 * cap * 3 : (int32_t*)nullptr,
+                           to_dev ? (long long*)d_counts + i0 : (long long*)nullptr, d_full + i0);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (timed) {
+        if (i8) HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));       // (the sweeps, the elections and the tails between them)
+        ctx->kernel_timed = true;
+    }
+    if (to_dev) {
+        if ((rc = results_written(ctx, consumer)) != FM_OK) return rc;
+        ctx->rows_stream = ctx->stream;
+        if (!h_counts) return FM_OK;              // (enqueued: nothing waits for the device)
+        // the caller asked for host numbers: the call's one synchronisation
+        HIP_TRY(ctx, hipMemcpyAsync(h_counts, d_full, (size_t)ni * 8, hipMemcpyDeviceToHost, ctx->stream));
+        return cs.finish();
+    }
+    // the counts decide how much is copied: one small synchronous read, then min(count, cap) rows of every image
+    std::vector<unsigned long long> cnt((size_t)ni);
+    HIP_TRY(ctx, hipMemcpyAsync(cnt.data(), d_full, (size_t)ni * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < ni; ++i) {
+        const size_t m = (size_t)std::min<int64_t>((int64_t)cnt[(size_t)i], ccap);
+        if (m == 0) continue;
+        HIP_TRY(ctx, d2h(ctx, qidx + i * cap, (int32_t*)(b + o_cq) + i * ccap, m * 4));
+        HIP_TRY(ctx, d2h(ctx, tidx + i * cap, (int32_t*)(b + o_ct) + i * ccap, m * 4));
+        HIP_TRY(ctx, d2h(ctx, dist + i * cap, (float*)(b + o_cd) + i * ccap, m * 4));
+        HIP_TRY(ctx, d2h(ctx, ratio + i * cap, (double*)(b + o_cr) + i * ccap, m * 8));
+    }
+    if ((rc = cs.finish()) != FM_OK) return rc;
+    for (int64_t i = 0; i < ni; ++i) n_accepted[i] = (int64_t)cnt[(size_t)i];
+    return FM_OK;
+}
+
+extern "C" int fm_collection_match_accepted_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* qidx,
+                                                 int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+{
+    return coll_accept_each(ctx, c, q, tau, cap, qidx, tidx, dist, ratio, n_accepted, nullptr, nullptr, nullptr, FM_NO_STREAM, false,
+                            "fm_collection_match_accepted_each");
+}
+
+extern "C" int fm_collection_match_accepted_each_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* d_rows,
+                                                     int64_t* d_counts, int64_t* h_counts, void* consumer_stream)
+{
+    return coll_accept_each(ctx, c, q, tau, cap, nullptr, nullptr, nullptr, nullptr, nullptr, d_rows, d_counts, h_counts, consumer_stream, true,
+                            "fm_collection_match_accepted_each_dev");
 }

@@ -444,6 +444,7 @@ static const OptionDef kOptions[] = {
     {"expand_big", &Tuning::expand_big, 0, 1, nullptr}, {"expand_huge", &Tuning::expand_huge, 0, 1, nullptr}, {"expand_delegate", &Tuning::expand_delegate, 0, 1 << 30, "FM_EXPAND_DELEGATE"}, {"expand_grow", &Tuning::expand_grow, 0, 4, nullptr}, {"expand_prof", &Tuning::expand_prof, 0, 1, "FM_EXPAND_PROF"},
     {"delegated_rounds", &Tuning::delegated_rounds, 0, 0, nullptr},       // a counter: set to 0, read
     {"radius_ws_bytes", &Tuning::radius_ws_bytes, 1 << 16, 0x7fffffff, nullptr},
+    {"coll_ws_bytes", &Tuning::coll_ws_bytes, 0, 0x7fffffff, nullptr},
 };
 
 extern "C" int fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value)

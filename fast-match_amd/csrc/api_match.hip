@@ -340,7 +340,7 @@ __global__ void ratio_cut_kernel(CutArgs a)
 // The accepted-only calls: the cut words of pairs (q[i], -) into ctx->d_cut, enqueued on ctx->stream in front of their K1
 // (which reads them on the same stream).  cut[i] = null for a pair without one: a query bank whose self distances were not
 // reduced for all of its current rows (a refill to more rows than they were computed for), or no device words.
-static int enqueue_ratio_cut(fm_ctx* ctx, int n, const fm_bank* const* q, double tau, const unsigned** cut)
+int enqueue_ratio_cut(fm_ctx* ctx, int n, const fm_bank* const* q, double tau, const unsigned** cut)
 {
     CutArgs a{};
     bool any = false;
@@ -1461,7 +1461,7 @@ extern "C" int fm_xcheck1(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32
 // the first kernel that writes the caller's arrays (the sweep before it overlaps whatever the consumer stream still does
 // with them), results_written() behind the last.  The calls are not accounted in fm_stats (no synchronisation to read the
 // events at).
-static int results_written(fm_ctx* ctx, void* consumer)
+int results_written(fm_ctx* ctx, void* consumer)
 {
     if (consumer == FM_NO_STREAM) return FM_OK;
     if (!ctx->ev_results) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_results, hipEventDisableTiming));

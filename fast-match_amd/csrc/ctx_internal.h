@@ -206,6 +206,16 @@ int sweep_pair(fm_ctx* ctx, const fm::Bank& cols, const fm::Bank& red, int ktop,
 int sweep_pair_plan(fm_ctx* ctx, const fm::Bank& cols, const fm::Bank& red, int ktop, int64_t fix_rows, PairSweep* out);
 int sweep_pair_run(fm_ctx* ctx, const fm::Bank& cols, const fm::Bank& red, int ktop, const unsigned* cut, const int* stage_real,
                    unsigned flags, const PairSweep& ps);
+// D* of the ratio test for the pairs (q[i], -) of the next K1 launch on ctx->stream, into ctx->d_cut (api_match.hip); cut[i] = null
+// for a pair without one.
+int enqueue_ratio_cut(fm_ctx* ctx, int n, const fm_bank* const* q, double tau, const unsigned** cut);
+// "The results are written": the consumer stream waits for what the context's stream has been given so far (api_match.hip).
+int results_written(fm_ctx* ctx, void* consumer);
+// Election of the cross-check (api_match.hip): per output row the minimum over the split partials, scatter-min into qbest.
+__global__ void xcheck_scatter_kernel(const unsigned long long* __restrict__ partial, int nsplit,
+                                      int ncols_alloc, int64_t nt,
+                                      unsigned long long* __restrict__ qbest, unsigned t_offset, int f32,
+                                      int* __restrict__ bound_reset, unsigned* __restrict__ fix);
 // Lowe's ratio test on 2-NN lists (api_match.hip; api_collection.hip runs it on a collection's lists)
 __global__ void lowe_kernel(const int32_t* __restrict__ idx2, const float* __restrict__ dist2, int64_t nq,
                             double tau, int32_t* __restrict__ tidx, float* __restrict__ dist,

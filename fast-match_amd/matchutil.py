@@ -238,7 +238,8 @@ class BFMatcher(object):
     against such a collection is refused by the library: upload the query's kind of images), NORM_HAMMING collections binary
     rows.  ``ValueError`` before anything is uploaded: a normType other than 4 / 6, crossCheck on a collection of more than one image
     (OpenCV asserts there too, as far as SURVEY.md Appendix A recalls), ``radiusMatch`` on a collection.
-    ``knnMatch_arrays`` / ``knnMatchEach_arrays`` / ``votes`` return NumPy arrays."""
+    ``knnMatch_arrays`` / ``knnMatchEach_arrays`` / ``votes`` return NumPy arrays.  ``fastMatchEach`` / ``fastMatchEach_arrays``
+    run Fast-Match's self-distance test against every image of the collection (NORM_L2 only)."""
 
     def __init__(self, normType=NORM_L2, crossCheck=False, options={}):
         if normType not in (NORM_L2, NORM_HAMMING):
@@ -353,6 +354,35 @@ class BFMatcher(object):
         finally:
             if tmp:
                 qb.close()
+
+    def fastMatchEach_arrays(self, queryDescriptors, tau):
+        """A list of (qidx, tidx, dist, ratio) per image: Fast-Match's accepted matches of the query inside every image
+        separately (``Collection.match_accepted_each``)."""
+        if self.normType == NORM_HAMMING:
+            raise ValueError("BFMatcher.fastMatchEach: the self-distance test is not built for NORM_HAMMING (binary banks carry no "
+                             "self distances)")
+        self._check_collection("BFMatcher.fastMatchEach")
+        coll = self.train()
+        qb, tmp = self._query(coll.ctx, queryDescriptors)
+        try:
+            if tmp or not qb.has_selfdist:
+                coll.ctx.self_dist_batch([qb], want_host=False)        # attached on the device, nothing comes back
+            return coll.match_accepted_each(qb, tau)
+        finally:
+            if tmp:
+                qb.close()
+
+    def fastMatchEach(self, queryDescriptors, tau):
+        """Fast-Match's accepted-match test against the collection, image by image: one list of ``DMatch`` per added image
+        (``imgIdx`` set), holding the matches (q, t) for which t is the cross-checked nearest neighbour of q INSIDE that image
+        and ``dist(q, t) / selfdist(q) < tau`` -- what ``fastmatch``'s first round accepts for the pair (query, image).  The
+        query's self distances are computed on the device.  The test is cross-checked by definition: the matcher's
+        ``crossCheck`` flag is ignored.  ``ValueError`` for a NORM_HAMMING matcher and for an empty collection, before
+        anything is uploaded."""
+        out = []
+        for i, (qidx, tidx, dist, _) in enumerate(self.fastMatchEach_arrays(queryDescriptors, tau)):
+            out.append([DMatch(int(qidx[j]), int(tidx[j]), dist[j], i) for j in range(qidx.shape[0])])
+        return out
 
     # -- cv2's matching methods ------------------------------------------------------------
     def knnMatch(self, queryDescriptors, trainDescriptors=None, k=None):

@@ -47,7 +47,8 @@ typedef struct fm_bank fm_bank;
  * that did not park; revision 8, r06: additions -- fm_knn, the option "f32_bound_every" -- and rounds[i][5] of the
  * per-round log may be -2; revision 9: additions -- fm_radius_match, the option "radius_ws_bytes"; revision 10: additions --
  * FM_BANK_BIN, fm_bank_create_bin; revision 11: additions -- fm_collection_*; revision 12: additions -- FM_DT_*,
- * fm_bank_create_dev, fm_knn_dev, fm_xcheck1_dev, fm_knn2_ratio_dev).  A binding
+ * fm_bank_create_dev, fm_knn_dev, fm_xcheck1_dev, fm_knn2_ratio_dev; still revision 12, additions only --
+ * fm_collection_match_accepted_each, fm_collection_match_accepted_each_dev, the option "coll_ws_bytes").  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.            */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -112,6 +113,9 @@ int  fm_ctx_destroy(fm_ctx* ctx);
  *   "expand_prof"  0|1    K7: per-phase timers of the first pair of a launch on stderr
  *   "radius_ws_bytes" 65536..2^31-1  fm_radius_match: device bytes for the candidates of one chunk of query rows (2^30;
  *                         24 bytes per candidate); a row whose own list needs more runs in a chunk of its own
+ *   "coll_ws_bytes" 0..2^31-1  fm_collection_match_accepted_each: device bytes for the per-(image, query row) arrays of one
+ *                         chunk of consecutive images (25 bytes per entry; at least one image per chunk); 0 = one chunk up
+ *                         to 64 MiB, beyond that a quarter of the free device memory (0)
  * Unknown names and out-of-range values return FM_EINVAL.                                          */
 int  fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value);
 int  fm_ctx_get_option(fm_ctx* ctx, const char* name, int64_t* value);
@@ -272,10 +276,34 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  *     and mode 1 by enqueuing the per-image sweeps (K8 / K5, K11) back to back inside the call: no host synchronisation
  *     between images, one copy out.  Counted on the device (integer atomics: deterministic totals);
  *     only n_images words come back.
+ *   fm_collection_match_accepted_each: Fast-Match's accepted-match test (fastmatch.pyx:122-124, 161-165) of q against every
+ *     image SEPARATELY: slot i equals, row by row and bit for bit, fm_match_accepted(q, bank(image i), tau, cap) -- every train
+ *     row of image i elects its nearest query row (float32 distance, lowest query index on ties), every query row keeps the
+ *     closest electing train row of image i (lowest row on ties), kept iff (double)dist / selfdist[q] < tau (NaN and inf
+ *     rejected: a query row with self distance 0 is never accepted).  q carries self distances (fm_bank_set_selfdist /
+ *     fm_self_dist_batch).  qidx / tidx / dist / ratio are [n_images][cap], rows ascending in query index, tidx = the row
+ *     inside image i; n_accepted[i] = the FULL count of image i, rows written = min(count, cap).  Images are independent: a
+ *     descriptor present in two images matches in both; an empty image has no rows and keeps its slot.  cap = 0: counts only
+ *     (the row arrays may be NULL) -- the self-distance analogue of fm_collection_votes, only n_images words come back.
+ *     The test divides by the query row's OWN self distance, so a second view of the same object in the database does not
+ *     reject a match the way the stacked d0 / d1 test does.  Integer route: ONE reverse top-1 sweep over the whole
+ *     allocation (a train row's election does not depend on its image), a segmented election into (image, query row), one
+ *     tail launch for all images; the float32-root repair above d^2 = 4 197 200 is included, per image.  Float32 route: the
+ *     per-image sweeps (K8 / K5) enqueued back to back, no host synchronisation between images.  Where the per-(image, query row)
+ *     arrays exceed the option "coll_ws_bytes" the images run in chunks of consecutive images, enqueued back to back, one
+ *     copy out.  Errors, in this order: NULL handles; a query of another kind or width (FM_EINVAL); a binary collection
+ *     (FM_EUNSUPPORTED: a binary bank carries no self distances); a query without self distances (FM_EINVAL); cap < 0
+ *     (FM_EINVAL).  nq = 0 writes zero counts and nothing else; n_images = 0 is valid.
+ *   fm_collection_match_accepted_each_dev: the same with the results left on the device: 12-byte rows {query, train row in
+ *     the image, float32 distance bits} of image i at d_rows + i * cap * 3, d_counts[i] = min(count, cap) (cap = 0: d_rows
+ *     may be NULL).  Enqueued on the context's stream; consumer_stream is ordered against the fills in both directions, as in
+ *     fm_match_accepted_dev_batch.  h_counts (host, any memory, or NULL) receives the full counts; asking for them is the
+ *     call's one host synchronisation.
  * Not built: crossCheck on a collection (OpenCV's batchDistance asserts update == 0 under crossCheck -- recalled, SURVEY.md
- * Appendix A; neither cv2 nor its source was at hand), radiusMatch, masks, the Fast-Match self-distance test and the
- * expansion loop on a collection, a batched K8 / K11 per-image sweep, sharding a collection across GPUs, removing single
- * images, turning an integer-route collection of float32 images into a float32-route one for a non-integer QUERY.                                                                    */
+ * Appendix A; neither cv2 nor its source was at hand), radiusMatch, masks, the expansion loop on a collection, a batched
+ * K8 / K11 (float32 / binary) per-image sweep, binary collections in the self-distance test, sharding a collection across
+ * GPUs, removing single images, turning an integer-route collection of float32 images into a float32-route one for a
+ * non-integer QUERY.                                                                    */
 typedef struct fm_collection fm_collection;
 #define FM_COLLECTION_F32_MAX 144115188075855872.0f   /* 2^57: largest finite magnitude of a float32-route collection and its queries */
 int  fm_collection_create(fm_ctx* ctx, fm_collection** coll);
@@ -297,6 +325,12 @@ int  fm_collection_knn2_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q,
                              int32_t* idx /*[n_images][nq][2]*/, float* dist /*[n_images][nq][2]*/);
 int  fm_collection_votes(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int32_t mode,
                          int64_t* votes /*[n_images]*/);
+int  fm_collection_match_accepted_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
+                                       int32_t* qidx, int32_t* tidx, float* dist, double* ratio /* each [n_images][cap] */,
+                                       int64_t* n_accepted /*[n_images]: the full count per image*/);
+int  fm_collection_match_accepted_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
+                                           int32_t* d_rows /*device [n_images][cap][3]*/, int64_t* d_counts /*device [n_images]*/,
+                                           int64_t* h_counts /*host [n_images] or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* ---- descriptors already on the GPU: device sources, device results ---------------------------------------------------------
  * Every creator above takes a HOST array and every dense matcher call ends in host arrays: the shape of the reference, whose
