@@ -159,6 +159,9 @@ SYMBOLS = {
     "fm_collection_votes": (_INT, [_P, _P, _P, ctypes.c_double, _I32, _P]),
     "fm_collection_match_accepted_each": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, _P]),
     "fm_collection_match_accepted_each_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P]),
+    "fm_collection_add_dev": (_INT, [_P, _P, _P, _INT, _I64, _INT, _I64, _P, ctypes.POINTER(_I32)]),
+    "fm_collection_knn_dev": (_INT, [_P, _P, _P, _I32, _P, _P, _P, _P]),
+    "fm_collection_knn2_ratio_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
 }
 
 _lib = None
@@ -400,6 +403,34 @@ class Collection(object):
         self.ctx._check(self.ctx.lib.fm_collection_add_bin(self.ctx.handle, self.handle, _ptr(a) if a.shape[0] else None,
                                                            a.shape[0], a.shape[1], ctypes.byref(i)))
         return int(i.value)
+
+    def add_from_device(self, ptr, dtype, n, dim, pitch=0, stream=None):
+        """Append one image whose ``n`` rows of ``dim`` elements are already in device memory (``fm_collection_add_dev``);
+        ``ptr`` / ``dtype`` / ``pitch`` / ``stream`` as in ``Context.bank_from_device`` (``FM_DT_BIN``: dim = bytes per row).
+        The collection is the one ``add`` / ``add_binary`` builds from the same values on the host; on return the source may
+        be overwritten.  Returns the image's index."""
+        i = _I32(-1)
+        self.ctx._check(self.ctx.lib.fm_collection_add_dev(self.ctx.handle, self.handle, _P(int(ptr)) if ptr else None, int(dtype),
+                                                           int(n), int(dim), int(pitch), _stream_arg(stream), ctypes.byref(i)))
+        return int(i.value)
+
+    def knn_dev(self, q, k, img_ptr, idx_ptr, dist_ptr, consumer_stream=None):
+        """``knn`` with the lists left on the device (``fm_collection_knn_dev``): device addresses of int32 / int32 / float32
+        [nq, k] buffers; enqueued, ``consumer_stream`` as in ``Context.knn_dev``."""
+        self.ctx._check(self.ctx.lib.fm_collection_knn_dev(
+            self.ctx.handle, self.handle, q.handle, int(k), _P(int(img_ptr)) if img_ptr else None,
+            _P(int(idx_ptr)) if idx_ptr else None, _P(int(dist_ptr)) if dist_ptr else None, _stream_arg(consumer_stream)))
+
+    def knn2_ratio_dev(self, q, tau, rows_ptr, count_ptr, cap, want_count=False, consumer_stream=None):
+        """``knn2_ratio`` with the accepted matches left on the device (``fm_collection_knn2_ratio_dev``): ``rows_ptr`` = device
+        address of an int32 [cap, 4] buffer (query, image, row inside the image, float32 distance bits), ``count_ptr`` of an
+        int64 word that receives min(accepted, cap).  ``want_count``: also return the full number accepted (one host
+        synchronisation); else None."""
+        n = _I64(0)
+        self.ctx._check(self.ctx.lib.fm_collection_knn2_ratio_dev(
+            self.ctx.handle, self.handle, q.handle, float(tau), int(cap), _P(int(rows_ptr)) if rows_ptr else None,
+            _P(int(count_ptr)) if count_ptr else None, ctypes.byref(n) if want_count else None, _stream_arg(consumer_stream)))
+        return int(n.value) if want_count else None
 
     def train(self):
         self.ctx._check(self.ctx.lib.fm_collection_train(self.ctx.handle, self.handle))

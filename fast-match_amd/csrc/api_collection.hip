@@ -253,6 +253,28 @@ void coll_compact_kernel(const int32_t* __restrict__ img2, const int32_t* __rest
     if (p && dst < cap) { o_q[dst] = (int32_t)q; o_m[dst] = img2[2 * q]; o_t[dst] = tidx[q]; o_d[dst] = dist[q]; o_r[dst] = ratio[q]; }
 }
 
+// The same ordered compaction into 16-byte rows {query, image, row inside the image, float32 distance bits} in the caller's
+// device memory (fm_collection_knn2_ratio_dev): compact_rows_kernel (api_match.hip) with the image column.
+__global__ __launch_bounds__(256)
+void coll_compact_rows_kernel(const int32_t* __restrict__ img2, const int32_t* __restrict__ tidx, const float* __restrict__ dist,
+                              const uint8_t* __restrict__ pass, const int* __restrict__ block_counts, int64_t nq, int64_t cap,
+                              int32_t* __restrict__ o_rows, long long* __restrict__ o_count, unsigned long long* __restrict__ full)
+{
+    int64_t q, total;
+    bool p;
+    const int64_t dst = compact_slot(block_counts, pass, nq, &q, &p, &total);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        *o_count = total < cap ? (long long)total : (long long)cap;       // the rows that are THERE; `full` keeps the number accepted
+        *full = (unsigned long long)total;
+    }
+    if (p && dst < cap) {
+        o_rows[4 * dst] = (int32_t)q;
+        o_rows[4 * dst + 1] = img2[2 * q];
+        o_rows[4 * dst + 2] = tidx[q];
+        o_rows[4 * dst + 3] = (int32_t)__float_as_uint(dist[q]);
+    }
+}
+
 // Votes: query rows whose 2-NN list passes d0 / d1 < tau (float64; a missing or zero second distance fails, as
 // lowe_kernel) counted per image.  Stacked lists (img != null, one list per query row): at the image of the first
 // neighbour; per-image lists [n_images][nq][2] (img null): at the list's own image, blockIdx.y.  Integer atomics: the
@@ -472,8 +494,11 @@ static int coll_rebuild_f32(fm_ctx* ctx, fm_collection* c, float vmax_new, int64
     return FM_OK;
 }
 
-// src: 1 uint8 rows, 2 float32 rows, 3 binary rows (dim = bytes)
-static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, int dim, int src, int32_t* img_idx, const char* who)
+// src: 1 uint8 rows, 2 float32 rows, 3 binary rows (dim = bytes).  dev != nullptr (fm_collection_add_dev): the rows are dev's,
+// in device memory, read in place by the device forms of the same preparation steps -- for src 2 as float32, half or
+// bfloat16 elements, widened exactly; `rows` is then dev->rows.
+static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, int dim, int src, int32_t* img_idx, const char* who,
+                    const DevSrc* dev = nullptr)
 {
     int rc = coll_check(ctx, c, who);
     if (rc != FM_OK) return rc;
@@ -497,18 +522,22 @@ static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, 
         }
         if (c->stack.kind == FM_BANK_BIN) {
             if ((rc = coll_reserve(ctx, c, off + n_pad)) != FM_OK) return rc;
-            const size_t src_bytes = (size_t)n * dim;
-            if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, src_bytes + 64)) != FM_OK) return rc;
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
             const fm::Bank v = bank_rows_view(c->stack, off, n);
-            HIP_TRY(ctx, launch_hamming_prep((const uint8_t*)ctx->ws_in, n, dim, v, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (ws_in is free for the next upload)
+            if (dev) {
+                HIP_TRY(ctx, launch_hamming_prep(dev->rows, n, dim, v, ctx->stream, dev->pitch));
+            } else {
+                const size_t src_bytes = (size_t)n * dim;
+                if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, src_bytes + 64)) != FM_OK) return rc;
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
+                HIP_TRY(ctx, launch_hamming_prep((const uint8_t*)ctx->ws_in, n, dim, v, ctx->stream));
+            }
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (ws_in is free for the next upload; a device source is read)
         } else {
             bool as_f32 = c->stack.kind == FM_BANK_F32;
             if (!as_f32) {
                 if ((rc = coll_reserve(ctx, c, off + n_pad)) != FM_OK) return rc;
                 int flags[2] = {0, 0};
-                if ((rc = bank_prep_range(ctx, rows, n, dim, src == 2, c->stack, off, n_pad, flags)) != FM_OK) return rc;
+                if ((rc = bank_prep_range(ctx, rows, n, dim, src == 2, c->stack, off, n_pad, flags, dev)) != FM_OK) return rc;
                 usq = flags[1];
                 if (src == 2 && flags[0]) as_f32 = true;          // (the range just written lies behind `used`: not part of anything)
                 else if (n_pad > n) {
@@ -521,7 +550,9 @@ static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, 
                 // the largest finite magnitude first: it decides the refusal, and the scale of a rebuild, before anything changes
                 // (what the integer-route attempt wrote lies behind `used`)
                 float hmax = 0.f;
-                {
+                if (dev) {
+                    if ((rc = dev_src_absmax(ctx, *dev, n, dim, &hmax)) != FM_OK) return rc;
+                } else {
                     const float* f = (const float*)rows;
                     for (int64_t i = 0; i < n * dim; ++i) { const float a = fabsf(f[i]); if (a <= 3.0e38f && a > hmax) hmax = a; }
                 }
@@ -534,7 +565,7 @@ static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, 
                 }
                 if ((rc = coll_reserve(ctx, c, off + n_pad)) != FM_OK) return rc;
                 float vmax = 0.f; bool finite = true;
-                if ((rc = bank_f32_range_rows(ctx, (const float*)rows, n, dim, c->stack, off, n_pad, &vmax, &finite)) != FM_OK) return rc;
+                if ((rc = bank_f32_range_rows(ctx, (const float*)rows, n, dim, c->stack, off, n_pad, &vmax, &finite, dev)) != FM_OK) return rc;
                 if (!finite || !(ldexpf(vmax, c->stack.kscale) < 60000.f)) c->stack.filt_ok = false;   // K5 alone from here on (planes unused)
                 if ((rc = coll_f32_finish(ctx, c, off, n, n_pad)) != FM_OK) return rc;
             }
@@ -571,6 +602,40 @@ extern "C" int fm_collection_add_f32(fm_ctx* ctx, fm_collection* c, const float*
 extern "C" int fm_collection_add_bin(fm_ctx* ctx, fm_collection* c, const uint8_t* rows, int64_t n, int bytes, int32_t* img_idx)
 {
     return coll_add(ctx, c, rows, n, bytes, 3, img_idx, "fm_collection_add_bin");
+}
+
+// An image from rows that are already in device memory (include/fastmatch_hip.h: "device sources"): fm_bank_create_dev's
+// source rules, then coll_add's collection rules on the device forms of its steps.  Passes over the source: uint8 and
+// binary one; a floating-point image one on the integer route while it stays integer valued (the preparation with its flag
+// words), two on the float32 route (the largest finite magnitude, then the typed copy), three for the image that turns an
+// integer-route collection into a float32-route one (the failed integer attempt, the magnitude, the copy).
+extern "C" int fm_collection_add_dev(fm_ctx* ctx, fm_collection* c, const void* d_rows, int dtype, int64_t n, int dim,
+                                     int64_t row_pitch_bytes, void* producer_stream, int32_t* img_idx)
+{
+    const char* who = "fm_collection_add_dev";
+    int rc = coll_check(ctx, c, who);
+    if (rc != FM_OK) return rc;
+    if (dtype < FM_DT_U8 || dtype > FM_DT_BIN)
+        return fail(ctx, FM_EINVAL, "fm_collection_add_dev: unknown dtype " + std::to_string(dtype) + " (FM_DT_U8 .. FM_DT_BIN)");
+    if (n < 0 || dim < 1) return fail(ctx, FM_EINVAL, "fm_collection_add_dev: bad n / width");
+    if (dtype == FM_DT_BIN ? dim > 64 : dim > kDim)
+        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + (dtype == FM_DT_BIN ? ": binary rows of more than 64 bytes are not supported" : ": dim > 128 is not supported"));
+    const int64_t elt = dtype == FM_DT_F32 ? 4 : (dtype == FM_DT_F16 || dtype == FM_DT_BF16) ? 2 : 1;
+    const int64_t pitch = row_pitch_bytes == 0 ? dim * elt : row_pitch_bytes;
+    if (pitch < dim * elt)
+        return fail(ctx, FM_EINVAL, "fm_collection_add_dev: row_pitch_bytes " + std::to_string(row_pitch_bytes) + " is below the row size " +
+                                    std::to_string(dim * elt));
+    if (pitch % elt != 0) return fail(ctx, FM_EINVAL, "fm_collection_add_dev: row_pitch_bytes is not a multiple of the element size");
+    const int src = dtype == FM_DT_U8 ? 1 : dtype == FM_DT_BIN ? 3 : 2;
+    if (n == 0) return coll_add(ctx, c, nullptr, 0, dim, src, img_idx, who);       // (d_rows is not looked at)
+    if (!d_rows) return fail(ctx, FM_EINVAL, "fm_collection_add_dev: d_rows is NULL");
+    if ((uintptr_t)d_rows % (uintptr_t)elt != 0) return fail(ctx, FM_EINVAL, "fm_collection_add_dev: d_rows is not aligned to the element size");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_ptr(ctx, d_rows, who, "d_rows")) != FM_OK) return rc;
+    // the rows are complete once the work producer_stream has been given so far is: no host wait for it
+    if ((rc = wait_for_stream(ctx, producer_stream)) != FM_OK) return rc;
+    const DevSrc dsrc{(const uint8_t*)d_rows, dtype, pitch};
+    return coll_add(ctx, c, d_rows, n, dim, src, img_idx, who, &dsrc);
 }
 
 extern "C" int fm_collection_train(fm_ctx* ctx, fm_collection* c)
@@ -679,12 +744,18 @@ static int coll_merge_one(fm_ctx* ctx, const PairSweep* ps, CollTab tab, int64_t
     return FM_OK;
 }
 
-// The stacked 2-NN lists of q on the device: img / idx / dist [nq][2].  ws_partial: partial | bounds | fix list.
-static int coll_knn2_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t* d_img, int32_t* d_idx, float* d_dist)
+// The stacked 2-NN lists of q on the device: img / idx / dist [nq][2].  ws_partial: partial | bounds | fix list.  consumer
+// (fm_collection_knn_dev: the arrays are the caller's): the stream whose work so far the merge -- the first kernel that writes
+// them -- waits for, behind the sweep.
+static int coll_knn2_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t* d_img, int32_t* d_idx, float* d_dist,
+                            void* consumer = FM_NO_STREAM)
 {
     const int64_t nq = q->n;
     const CollTab none{nullptr, nullptr, nullptr};
-    if (c->total == 0) return coll_merge_one(ctx, nullptr, none, nq, 0, d_img, d_idx, d_dist);
+    if (c->total == 0) {
+        if (int rc = wait_for_stream(ctx, consumer)) return rc;
+        return coll_merge_one(ctx, nullptr, none, nq, 0, d_img, d_idx, d_dist);
+    }
     const CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
     const fm::Bank& t = c->stack;
     const bool i8 = t.kind == FM_BANK_I8;
@@ -696,6 +767,7 @@ static int coll_knn2_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int
     int rc;
     if (!i8) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
     if ((rc = sweep_pair(ctx, *q, t, 2, nq, nullptr, i8 ? nullptr : c->st_real(), kSweepNoCount | (i8 ? 0u : kSweepNoEvents), &ps)) != FM_OK) return rc;
+    if ((rc = wait_for_stream(ctx, consumer)) != FM_OK) return rc;
     if ((rc = coll_merge_one(ctx, &ps, tab, nq, 0, d_img, d_idx, d_dist)) != FM_OK) return rc;
     if (!i8) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
@@ -799,6 +871,99 @@ extern "C" int fm_collection_knn2_ratio(fm_ctx* ctx, fm_collection* c, const fm_
     HIP_TRY(ctx, hipGetLastError());
     return cs.finish_rows((const unsigned long long*)(b + o_cnt), ccap,
                           {{qidx, b + o_cq, 4}, {img, b + o_cm, 4}, {tidx, b + o_ct, 4}, {dist, b + o_cd, 4}, {ratio, b + o_cr, 8}}, n_accepted);
+}
+
+// fm_collection_knn / fm_collection_knn2_ratio with the results left in caller-supplied device memory: the same pipelines, the
+// merge / lookup / compaction kernels handed the caller's pointers, ordered against consumer_stream as fm_knn_dev and
+// fm_knn2_ratio_dev are (api_match.hip).  Not accounted in fm_stats.
+extern "C" int fm_collection_knn_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t k, int32_t* d_img, int32_t* d_idx,
+                                     float* d_dist, void* consumer_stream)
+{
+    const char* who = "fm_collection_knn_dev";
+    int rc = coll_query_check(ctx, c, q, who);
+    if (rc != FM_OK) return rc;
+    if (k < 1) return fail(ctx, FM_EINVAL, "fm_collection_knn_dev: k must be at least 1");
+    if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_collection_knn_dev: k above 8 is not built");
+    const int64_t nq = q->n;
+    if (nq == 0) return FM_OK;
+    if (!d_img || !d_idx || !d_dist) return fail(ctx, FM_EINVAL, "fm_collection_knn_dev: output pointer is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_ptr(ctx, d_img, who, "d_img")) != FM_OK || (rc = check_device_ptr(ctx, d_idx, who, "d_idx")) != FM_OK ||
+        (rc = check_device_ptr(ctx, d_dist, who, "d_dist")) != FM_OK) return rc;
+    if (k == 2) {
+        if ((rc = coll_knn2_device(ctx, c, q, d_img, d_idx, d_dist, consumer_stream)) != FM_OK) return rc;
+    } else if (k == 1) {
+        const size_t ob = align256((size_t)nq * 8);
+        if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, 3 * ob + 64)) != FM_OK) return rc;
+        char* b = (char*)ctx->ws_out;
+        if ((rc = coll_knn2_device(ctx, c, q, (int32_t*)b, (int32_t*)(b + ob), (float*)(b + 2 * ob))) != FM_OK) return rc;
+        if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+        hipLaunchKernelGGL(coll_col0_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t*)b,
+                           (const float*)(b + 2 * ob), (const int32_t*)(b + ob), nq, d_img, d_dist, d_idx);
+        HIP_TRY(ctx, hipGetLastError());
+    } else if (c->total == 0) {
+        if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(d_img, 0xff, (size_t)nq * k * 4, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_idx, 0xff, (size_t)nq * k * 4, ctx->stream));
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)d_dist, 0x7f800000, (size_t)nq * k, ctx->stream));
+    } else {
+        // K9 / K11's vector-ALU lists: their merge kernel writes the physical rows into the caller's d_idx, the lookup pass
+        // turns them into (image, row) in place
+        const fm::Bank& t = c->stack;
+        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, knnk_partial_bytes(nq, t.n, k) + 64)) != FM_OK) return rc;
+        if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+        if (t.kind == FM_BANK_BIN)
+            HIP_TRY(ctx, launch_hamming_knnk(*q, t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream, c->st_real()));
+        else
+            HIP_TRY(ctx, launch_knnk(*q, t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
+        hipLaunchKernelGGL(coll_translate_kernel, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, ctx->stream,
+                           CollTab{c->st_img(), c->st_real(), c->img_phys()}, nq * k, d_img, d_idx, d_dist);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return results_written(ctx, consumer_stream);
+}
+
+extern "C" int fm_collection_knn2_ratio_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* d_rows,
+                                            int64_t* d_count, int64_t* n_accepted, void* consumer_stream)
+{
+    const char* who = "fm_collection_knn2_ratio_dev";
+    int rc = coll_query_check(ctx, c, q, who);
+    if (rc != FM_OK) return rc;
+    if (n_accepted) *n_accepted = 0;
+    if (cap < 0 || !d_count || (cap > 0 && !d_rows)) return fail(ctx, FM_EINVAL, "fm_collection_knn2_ratio_dev: bad output arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_ptr(ctx, d_count, who, "d_count")) != FM_OK) return rc;
+    if (cap > 0 && (rc = check_device_ptr(ctx, d_rows, who, "d_rows")) != FM_OK) return rc;
+    const int64_t nq = q->n;
+    if (nq == 0) {
+        if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 8, ctx->stream));
+        return results_written(ctx, consumer_stream);
+    }
+    const int nblk = (int)((nq + 255) / 256);
+    size_t off = 0;
+    const size_t o_m2 = carve(off, (size_t)nq * 8), o_i2 = carve(off, (size_t)nq * 8), o_d2 = carve(off, (size_t)nq * 8);
+    const size_t o_ti = carve(off, (size_t)nq * 4), o_di = carve(off, (size_t)nq * 4), o_ra = carve(off, (size_t)nq * 8);
+    const size_t o_pa = carve(off, (size_t)nq), o_bc = carve(off, (size_t)nblk * 4), o_cnt = carve(off, 16);
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
+    char* b = (char*)ctx->ws_out;
+    if ((rc = coll_knn2_device(ctx, c, q, (int32_t*)(b + o_m2), (int32_t*)(b + o_i2), (float*)(b + o_d2))) != FM_OK) return rc;
+    hipLaunchKernelGGL(lowe_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_i2), (const float*)(b + o_d2), nq, tau,
+                       (int32_t*)(b + o_ti), (float*)(b + o_di), (double*)(b + o_ra), (uint8_t*)(b + o_pa), (int*)(b + o_bc));
+    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+    hipLaunchKernelGGL(coll_compact_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_m2),
+                       (const int32_t*)(b + o_ti), (const float*)(b + o_di), (const uint8_t*)(b + o_pa), (const int*)(b + o_bc), nq, cap, d_rows,
+                       (long long*)d_count, (unsigned long long*)(b + o_cnt));
+    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = results_written(ctx, consumer_stream)) != FM_OK) return rc;
+    if (n_accepted) {       // (the one host synchronisation of the integer and binary routes: the caller asked for a host number)
+        unsigned long long cnt = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&cnt, b + o_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        *n_accepted = (int64_t)cnt;
+    }
+    return FM_OK;
 }
 
 // The per-image 2-NN lists on the device: d_idx / d_dist [n_images][nq][2].  Up to "batch_group" images per launch of the

@@ -340,6 +340,24 @@ __global__ void bank_copy_dev_kernel(const uint8_t* __restrict__ src, int64_t pi
     dst[i] = (row < n && k < dim) ? dev_src_elem<DT>(src + row * pitch, k) : 0.f;
 }
 
+// The largest FINITE magnitude of a device source (fm_collection_add_dev: it decides the 2^57 refusal and the scale of a
+// rebuild before anything changes), bank_absmax_kernel's rule on the typed, pitched rows: |v| <= 3.0e38f counts, larger and
+// NaN do not.  One atomic per wave on the bits of the non-negative float (bit order = value order).
+template <int DT>
+__global__ __launch_bounds__(256)
+void dev_src_absmax_kernel(const uint8_t* __restrict__ src, int64_t pitch, int64_t n, int dim, unsigned* __restrict__ out)
+{
+    float m = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * dim; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / dim;
+        const float v = fabsf(dev_src_elem<DT>(src + row * pitch, (int)(i - row * dim)));
+        m = v <= 3.0e38f ? fmaxf(m, v) : m;
+    }
+#pragma unroll
+    for (int mask = 1; mask < 64; mask <<= 1) m = fmaxf(m, __shfl_xor(m, mask));
+    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(out, __float_as_uint(m));
+}
+
 // float32 bank for the general (non-integer) route: zero-padded copy [n_pad][128].
 __global__ void bank_copy_f32_kernel(const float* __restrict__ src, int64_t n, int dim,
                                      float* __restrict__ dst, int64_t n_pad, const int32_t* __restrict__ map)
@@ -837,9 +855,6 @@ static void bank_free(Bank* b)
     b->rowsh = nullptr; b->normf = nullptr; b->auxf = nullptr;
 }
 
-// Source rows that are already in device memory (fm_bank_create_dev): read in place by the *_dev_kernel variants.
-struct DevSrc { const uint8_t* rows; int dtype; int64_t pitch; };
-
 static hipError_t launch_bank_prep_dev(const DevSrc& d, int64_t n, int dim, Bank& b, int* d_flag, int ntiles, hipStream_t stream)
 {
     const int vec = dim == kDim && (((uintptr_t)d.rows | (uintptr_t)d.pitch) & 15) == 0;
@@ -865,6 +880,26 @@ static hipError_t launch_bank_copy_dev(const DevSrc& d, int64_t n, int dim, Bank
     }
 #undef FM_COPY_DEV
     return hipGetLastError();
+}
+
+int fm::dev_src_absmax(fm_ctx* ctx, const DevSrc& d, int64_t n, int dim, float* vmax)
+{
+    int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, 64);
+    if (rc != FM_OK) return rc;
+    unsigned* d_max = (unsigned*)ctx->ws_in;
+    HIP_TRY(ctx, hipMemsetAsync(d_max, 0, 4, ctx->stream));
+    const dim3 grid((unsigned)std::min<int64_t>(1024, (n * dim + 255) / 256));
+#define FM_ABSMAX_DEV(DT_)                                                                                                 \
+    case DT_: hipLaunchKernelGGL((dev_src_absmax_kernel<DT_>), grid, dim3(256), 0, ctx->stream, d.rows, d.pitch, n, dim, d_max); break;
+    switch (d.dtype) {
+        FM_ABSMAX_DEV(FM_DT_F32) FM_ABSMAX_DEV(FM_DT_F16) FM_ABSMAX_DEV(FM_DT_BF16)
+        default: return fail(ctx, FM_EINVAL, "dev_src_absmax: not a floating-point source");
+    }
+#undef FM_ABSMAX_DEV
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(vmax, d_max, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return FM_OK;
 }
 
 // map != nullptr: the bank's row i is rows[map[i]] of the n_src source rows (0 <= map[i] < n_src, checked here).
@@ -1045,17 +1080,22 @@ extern "C" int fm_bank_append_u8(fm_ctx* ctx, fm_bank* bank, const uint8_t* rows
 // Rows [off, off + n_pad) of an integer-route bank's arrays (off and n_pad multiples of 128) from n host rows (uint8, or
 // float32 when f32) -- the rows behind the n real ones come out as padding rows.  flags[0]: a float32 value was not an
 // integer in 0 .. 255 (the range then holds no usable rows), flags[1]: the largest |row|^2.  Synchronous.  A train
-// collection (api_collection.hip) places its images with it.
-int fm::bank_prep_range(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f32, Bank& b, int64_t off, int64_t n_pad, int* flags)
+// collection (api_collection.hip) places its images with it.  dev != nullptr: the rows are dev's, read in place (`rows` and
+// `f32` are ignored; only the flag words live in ws_in).
+int fm::bank_prep_range(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f32, Bank& b, int64_t off, int64_t n_pad, int* flags,
+                        const DevSrc* dev)
 {
-    const size_t src_bytes = (size_t)n * dim * (f32 ? 4 : 1), flag_off = (src_bytes + 15) & ~(size_t)15;
+    const size_t src_bytes = dev ? 0 : (size_t)n * dim * (f32 ? 4 : 1), flag_off = (src_bytes + 15) & ~(size_t)15;
     int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, flag_off + 32);
     if (rc != FM_OK) return rc;
     int* d_flag = (int*)((char*)ctx->ws_in + flag_off);
     if (src_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 8, ctx->stream));
     const int64_t ntiles = n_pad / kTileRows;
-    if (f32)
+    if (dev) {
+        Bank v = bank_rows_view(b, off, n);
+        HIP_TRY(ctx, launch_bank_prep_dev(*dev, n, dim, v, d_flag, (int)ntiles, ctx->stream));
+    } else if (f32)
         hipLaunchKernelGGL(bank_prep_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, (const void*)ctx->ws_in, n, dim,
                            b.rows8 + (size_t)off * kDim, b.norm + off, b.aux + (off / kTileRows) * kAuxPerTile, d_flag, ntiles);
     else
@@ -1187,19 +1227,31 @@ extern "C" int fm_bank_append_f32(fm_ctx* ctx, fm_bank* bank, const float* rows,
 
 // Float32-route rows [off, off + n_pad) of a bank's arrays (train collections): the n host rows into rowsf (zero rows behind
 // them), *vmax = their largest finite magnitude, *finite = every value is finite.  Then bank_f32_range_planes: the fp16 planes of
-// the range under b.kscale (rows from n on: padding), *nm_max = the largest scaled norm.  Both synchronous.
-int fm::bank_f32_range_rows(fm_ctx* ctx, const float* rows, int64_t n, int dim, Bank& b, int64_t off, int64_t n_pad, float* vmax, bool* finite)
+// the range under b.kscale (rows from n on: padding), *nm_max = the largest scaled norm.  Both synchronous.  dev != nullptr:
+// the rows are dev's (float32, half or bfloat16), read in place; `rows` is ignored.
+int fm::bank_f32_range_rows(fm_ctx* ctx, const float* rows, int64_t n, int dim, Bank& b, int64_t off, int64_t n_pad, float* vmax, bool* finite,
+                            const DevSrc* dev)
 {
-    const size_t src_bytes = (size_t)n * dim * 4, flag_off = (src_bytes + 15) & ~(size_t)15;
+    const size_t src_bytes = dev ? 0 : (size_t)n * dim * 4, flag_off = (src_bytes + 15) & ~(size_t)15;
     int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, flag_off + 32);
     if (rc != FM_OK) return rc;
     int* d_flag = (int*)((char*)ctx->ws_in + flag_off);
     float* dst = b.rowsf + (size_t)off * kDim;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 16, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(dst, 0, (size_t)n_pad * kDim * 4, ctx->stream));
-    hipLaunchKernelGGL(bank_append_f32_kernel, dim3((unsigned)std::min<int64_t>(1024, (n * kDim + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const float*)ctx->ws_in, n, dim, dst, d_flag);
+    if (dev) {
+        // the typed, pitched copy writes every row of the range (zeros behind the real rows and dims); the statistics are
+        // bank_absmax_kernel's over the rows just written -- the zeros change neither
+        Bank v = bank_rows_view(b, off, n);
+        v.n_pad = n_pad;
+        HIP_TRY(ctx, launch_bank_copy_dev(*dev, n, dim, v, ctx->stream));
+        hipLaunchKernelGGL(bank_absmax_kernel, dim3((unsigned)std::min<int64_t>(1024, (n * kDim + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const float*)dst, n * kDim, d_flag);
+    } else {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(dst, 0, (size_t)n_pad * kDim * 4, ctx->stream));
+        hipLaunchKernelGGL(bank_append_f32_kernel, dim3((unsigned)std::min<int64_t>(1024, (n * kDim + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const float*)ctx->ws_in, n, dim, dst, d_flag);
+    }
     HIP_TRY(ctx, hipGetLastError());
     int stat[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(stat, d_flag, 8, hipMemcpyDeviceToHost, ctx->stream));

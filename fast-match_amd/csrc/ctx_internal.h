@@ -159,9 +159,17 @@ void fill_round_f32(fm::RoundF32* r, const fm::Bank& q, const fm::Bank& t);
 // K10: radiusMatch (radius.hip); arguments checked by fm_radius_match (api_match.hip)
 int radius_match(fm_ctx* ctx, const fm::Bank& q, const fm::Bank& t, const float* radius, float radius_all, int64_t cap,
                  int64_t* offsets, int32_t* idx, float* dist, int64_t* n_total);
-// Prepared rows of an integer-route bank's arrays from host rows, at a 128-row offset (api_ctx.hip; train collections)
-int bank_prep_range(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f32, Bank& b, int64_t off, int64_t n_pad, int* flags);
-int bank_f32_range_rows(fm_ctx* ctx, const float* rows, int64_t n, int dim, Bank& b, int64_t off, int64_t n_pad, float* vmax, bool* finite);
+// Source rows that are already in device memory (fm_bank_create_dev, fm_collection_add_dev): n rows of FM_DT_* elements,
+// `pitch` bytes apart, read in place by the *_dev_kernel variants of the preparation kernels.
+struct DevSrc { const uint8_t* rows; int dtype; int64_t pitch; };
+// Prepared rows of an integer-route bank's arrays from host rows -- or from dev's rows -- at a 128-row offset (api_ctx.hip;
+// train collections)
+int bank_prep_range(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f32, Bank& b, int64_t off, int64_t n_pad, int* flags,
+                    const DevSrc* dev = nullptr);
+int bank_f32_range_rows(fm_ctx* ctx, const float* rows, int64_t n, int dim, Bank& b, int64_t off, int64_t n_pad, float* vmax, bool* finite,
+                        const DevSrc* dev = nullptr);
+// *vmax = the largest finite magnitude of a float32 / half / bfloat16 device source (0 for none).  Synchronous: four bytes come back.
+int dev_src_absmax(fm_ctx* ctx, const DevSrc& d, int64_t n, int dim, float* vmax);
 int bank_f32_range_planes(fm_ctx* ctx, Bank& b, int64_t off, int64_t n, int64_t n_pad, float* nm_max);
 // A bank's self distances, and its largest one (Bank::sdmax), in place: the array is allocated once, the word behind it.
 int bank_selfdist_alloc(fm_ctx* ctx, fm_bank* b);

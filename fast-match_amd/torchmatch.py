@@ -13,12 +13,21 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
 * ``mutual_nn(q, t)`` -> ``(tidx int32 [nq], dist float32 [nq])``: the cross-checked 1-NN (-1 / inf: unmatched).
 * ``ratio_match(q, t, tau)`` -> ``(qidx, tidx, dist)`` of the rows whose first / second distance is below ``tau``.
 
+* ``Collection(context=None)`` -- a train collection (``cv2.BFMatcher.add`` / ``train``) whose images are CUDA tensors: the
+  retrieval flow extract -> ``add`` to the database -> query -> consume without a copy to the host.  A context manager.
+  ``add(tensor, *, binary=False)`` reads the tensor in place (``fm_collection_add_dev``) and returns the image index;
+  ``knn(q, k)`` -> ``(img, idx, dist)`` [nq, k]; ``ratio_match(q, tau)`` -> ``(qidx, img, tidx, dist)``;
+  ``fast_match_each(q, tau, cap=None)`` -> ``(rows int32 [n_images, cap, 3], counts int64 [n_images])``, the accepted-match
+  test inside every image (``q``: a ``Bank`` carrying self distances, ``Context.self_dist_batch([q], want_host=False)``);
+  ``clear()``, ``close()``, ``info()``.  The collection equals the ``_ffi.Collection`` the same values build on the host.
+
 ``q`` and ``t`` are ``Bank``s or CUDA tensors (a tensor becomes a bank for the call).  The values are those of
 ``Context.knn`` / ``xcheck1`` / ``knn2_ratio`` on banks built from the same numbers on the host, bit for bit.
 
 Streams: ``torch.cuda.current_stream()`` is both the producer of the descriptor tensors and the consumer of the results --
 the library orders its kernels behind the one and the stream behind the other on the device, so no ``synchronize()`` is needed
-on either side (``ratio_match`` reads the accepted count back to size its outputs: one host wait).
+on either side (``ratio_match`` and ``Collection.ratio_match`` read the accepted count back to size their outputs: one host
+wait).
 
 ``torch`` is imported inside the functions: importing the package does not need it.  A CPU tensor, another dtype or
 another rank raises ``ValueError`` before the library is touched.  Tensors must live on the context's device.
@@ -145,3 +154,118 @@ def ratio_match(q, t, tau):
     finally:
         for b in made:
             b.close()
+
+
+class Collection(object):
+    """A train collection fed from CUDA tensors (module docstring).  The library's collection is made with the first call
+    that needs it, on ``context`` or the default context of the first tensor's device."""
+
+    def __init__(self, context=None):
+        self._context = context
+        self._coll = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _collection(self, ctx=None):
+        if self._coll is None:
+            if self._context is None:
+                self._context = ctx if ctx is not None else _ffi.default_context()
+            self._coll = self._context.collection()
+        return self._coll
+
+    def add(self, tensor, *, binary=False):
+        """Append one image ([n, dim] uint8 / float32 / float16 / bfloat16, or ``binary`` uint8 rows of packed bits; n may be
+        0), read in place behind the current stream's work -- pitched rows with unit column stride included.  Returns the
+        image's index.  On return the tensor may be overwritten."""
+        import torch
+        tensor, dt = _checked(tensor, binary)
+        coll = self._collection(_ctx_for(tensor, self._context))
+        n, dim = tensor.shape
+        with torch.cuda.device(tensor.device):
+            stream = torch.cuda.current_stream().cuda_stream
+        return coll.add_from_device(tensor.data_ptr() if n else 0, dt, n, dim, tensor.stride(0) * tensor.element_size(),
+                                    stream=stream)
+
+    def _query(self, q):
+        """(query bank, [banks made for this call]); every refusal before anything reaches the library."""
+        if isinstance(q, _ffi.Bank):
+            self._collection(q.ctx)
+            return q, []
+        t, _ = _checked(q)
+        kind = self._collection(_ctx_for(t, self._context)).info()[3]
+        b = bank(t, binary=kind == _ffi.FM_BANK_BIN, float_route=kind == _ffi.FM_BANK_F32, context=self._context)
+        return b, [b]
+
+    def knn(self, q, k):
+        """The k nearest rows of the stacked images: ``(img int32, idx int32, dist float32)`` [nq, k] CUDA tensors, ``idx`` the
+        row inside image ``img``; ties go to the earlier image; -1 / -1 / inf beyond the collection's rows.  1 <= k <= 8."""
+        import torch
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        qb, made = self._query(q)
+        try:
+            stream, dev = _stream_and_device(qb.ctx)
+            img = torch.empty((qb.n, k), dtype=torch.int32, device=dev)
+            idx = torch.empty((qb.n, k), dtype=torch.int32, device=dev)
+            dist = torch.empty((qb.n, k), dtype=torch.float32, device=dev)
+            p = (lambda t: t.data_ptr()) if qb.n else (lambda t: 0)
+            self._coll.knn_dev(qb, k, p(img), p(idx), p(dist), consumer_stream=stream)
+            return img, idx, dist
+        finally:
+            for b in made:
+                b.close()
+
+    def ratio_match(self, q, tau):
+        """The classic ratio match against the stacked images: ``(qidx, img, tidx int32 [m], dist float32 [m])``, ascending
+        query index.  One host wait (the count sizes the outputs)."""
+        import torch
+        qb, made = self._query(q)
+        try:
+            stream, dev = _stream_and_device(qb.ctx)
+            cap = qb.n
+            rows = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=dev)
+            count = torch.empty(1, dtype=torch.int64, device=dev)
+            m = self._coll.knn2_ratio_dev(qb, float(tau), rows.data_ptr(), count.data_ptr(), cap, want_count=True,
+                                          consumer_stream=stream)
+            rows = rows[:min(m, cap)]
+            return (rows[:, 0].contiguous(), rows[:, 1].contiguous(), rows[:, 2].contiguous(),
+                    rows[:, 3].contiguous().view(torch.float32))
+        finally:
+            for b in made:
+                b.close()
+
+    def fast_match_each(self, q, tau, cap=None):
+        """Fast-Match's accepted-match test of ``q`` inside every image separately, left on the device: ``(rows int32
+        [n_images, cap, 3] = (query, row inside the image, float32 distance bits), counts int64 [n_images] = min(accepted,
+        cap))``; ``cap`` defaults to ``q.n``.  ``q`` is a ``Bank`` that carries self distances; enqueued, no host wait."""
+        import torch
+        if not isinstance(q, _ffi.Bank):
+            raise ValueError("fast_match_each takes a resident Bank that carries self distances (Context.self_dist_batch)")
+        coll = self._collection(q.ctx)
+        ni = coll.info()[0]
+        cap = q.n if cap is None else int(cap)
+        stream, dev = _stream_and_device(q.ctx)
+        rows = torch.empty((ni, max(cap, 0), 3), dtype=torch.int32, device=dev)
+        counts = torch.zeros(ni, dtype=torch.int64, device=dev)
+        coll.match_accepted_each_dev(q, float(tau), rows.data_ptr() if rows.numel() else 0, counts.data_ptr() if ni else 0, cap,
+                                     consumer_stream=stream)
+        return rows, counts
+
+    def clear(self):
+        if self._coll is not None:
+            self._coll.clear()
+
+    def info(self):
+        """(n_images, n_rows_total, dim, kind)"""
+        return self._coll.info() if self._coll is not None else (0, 0, 0, 0)
+
+    def close(self):
+        if self._coll is not None:
+            self._coll.close()
+        self._coll = None

@@ -48,8 +48,9 @@ typedef struct fm_bank fm_bank;
  * per-round log may be -2; revision 9: additions -- fm_radius_match, the option "radius_ws_bytes"; revision 10: additions --
  * FM_BANK_BIN, fm_bank_create_bin; revision 11: additions -- fm_collection_*; revision 12: additions -- FM_DT_*,
  * fm_bank_create_dev, fm_knn_dev, fm_xcheck1_dev, fm_knn2_ratio_dev; still revision 12, additions only --
- * fm_collection_match_accepted_each, fm_collection_match_accepted_each_dev, the option "coll_ws_bytes").  A binding
- * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.            */
+ * fm_collection_match_accepted_each, fm_collection_match_accepted_each_dev, the option "coll_ws_bytes"; still revision 12,
+ * additions only -- fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev).  A binding compares
+ * fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.                      */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
 
@@ -299,6 +300,8 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  *     may be NULL).  Enqueued on the context's stream; consumer_stream is ordered against the fills in both directions, as in
  *     fm_match_accepted_dev_batch.  h_counts (host, any memory, or NULL) receives the full counts; asking for them is the
  *     call's one host synchronisation.
+ *   fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev: images from, and stacked results into, DEVICE
+ *     memory -- described with the other device entry points below ("descriptors already on the GPU").
  * Not built: crossCheck on a collection (OpenCV's batchDistance asserts update == 0 under crossCheck -- recalled, SURVEY.md
  * Appendix A; neither cv2 nor its source was at hand), radiusMatch, masks, the expansion loop on a collection, a batched
  * K8 / K11 (float32 / binary) per-image sweep, binary collections in the self-distance test, sharding a collection across
@@ -372,9 +375,37 @@ int  fm_collection_match_accepted_each_dev(fm_ctx* ctx, fm_collection* coll, con
  *   read).  The float32 route makes no promise: its fp16-filter / all-pairs decision is taken on the device today, but it may
  *   come to need the host, and a workspace that has to grow frees the old one, which waits for the device on every route.
  *   The calls are not accounted in fm_stats.
- * Not built: device sources for collection adds (fm_collection_add_*), for fm_bank_refill_u8_async and fm_bank_append_*; device
- *   results for fm_radius_match and fm_self_dist (fm_self_dist_batch attaches them on the device already); an enqueue-only
- *   float32 route; tensors on another GPU than the context's (copy them over first).                                          */
+ *
+ * fm_collection_add_dev: fm_collection_add_u8 / _f32 / _bin from rows in DEVICE memory.  The source rules are fm_bank_create_dev's
+ *   (device memory of the context's device, pitch, alignment to the element size, n = 0 valid: d_rows is not looked at and the
+ *   image still takes an index); dtype FM_DT_U8 behaves as fm_collection_add_u8, FM_DT_F32 as fm_collection_add_f32, FM_DT_F16 /
+ *   FM_DT_BF16 are widened exactly to float32 in registers and then follow FM_DT_F32, FM_DT_BIN behaves as fm_collection_add_bin
+ *   (dim = bytes).  The collection rules are the host adds', with the same codes: width or kind mixing FM_EINVAL, dim > 128 or
+ *   binary rows over 64 bytes FM_EUNSUPPORTED, the first non-empty image fixes width and kind, the first float32 image with a
+ *   non-integer value rebuilds the collection on the float32 route, a finite magnitude above FM_COLLECTION_F32_MAX is
+ *   FM_EUNSUPPORTED.  Every refusal leaves the collection unchanged.  CONTRACT: the collection is the one the host add of the
+ *   same values would have built (half / bfloat16: of their float32 values) -- same device arrays, kind, fp16 scale, filter
+ *   and norm terms, padding rows -- so every fm_collection_* call returns the same bits; host and device adds may alternate.
+ *   No staging copy: the preparation kernels read the caller's memory in place and write into the collection's arrays at the
+ *   image's first physical row.  The largest finite magnitude of a floating-point image, which the host add finds with a loop
+ *   over the rows, comes from a reduction kernel over the source (four bytes read back).  Passes over the source: one (uint8,
+ *   binary, an integer-valued floating-point image on the integer route), two on the float32 route, three for the image that
+ *   causes the rebuild.  Ordering is fm_bank_create_dev's: the kernels wait on the device for what producer_stream has been
+ *   given so far, the call synchronises with the context's stream (flag words are read back), and on return the source may be
+ *   overwritten or freed.
+ * fm_collection_knn_dev, fm_collection_knn2_ratio_dev: fm_collection_knn (1 <= k <= 8) and fm_collection_knn2_ratio with the
+ *   results written to caller-supplied DEVICE memory: the same values in the same order on all three collection kinds, the
+ *   float32-root repair included, by the same kernels handed the caller's pointers (k = 1: one small kernel takes the first
+ *   column).  fm_collection_knn2_ratio_dev leaves 16-byte rows {query, img, row inside the image, float32 distance bits} and
+ *   *d_count = min(accepted, cap); *n_accepted (host, may be NULL) = the full number accepted.  Pointer checks, stream ordering
+ *   in both directions and host synchronisation are fm_knn_dev's / fm_knn2_ratio_dev's (NULL or host memory: FM_EINVAL; d_rows
+ *   may be NULL when cap = 0; nq = 0 writes *d_count = 0 and nothing else; an empty collection writes -1 / -1 / +inf and a zero
+ *   count; no host synchronisation on the integer and binary routes except n_accepted != NULL -- and the first match after an
+ *   add, which uploads the lookup tables as fm_collection_train does).  Errors in fm_collection_knn's order; k > 8 is
+ *   FM_EUNSUPPORTED, k < 1 FM_EINVAL.  Not accounted in fm_stats.
+ * Not built: device sources for fm_bank_refill_u8_async and fm_bank_append_*; device results for fm_radius_match and
+ *   fm_self_dist (fm_self_dist_batch attaches them on the device already) and for fm_collection_knn2_each / _votes; an
+ *   enqueue-only float32 route; tensors on another GPU than the context's (copy them over first).                          */
 #define FM_DT_U8   1
 #define FM_DT_F32  2
 #define FM_DT_F16  3
@@ -389,6 +420,14 @@ int  fm_xcheck1_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* d_
 int  fm_knn2_ratio_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                        int32_t* d_rows /*device [cap][3]*/, int64_t* d_count /*device*/, int64_t* n_accepted /*host, or NULL*/,
                        void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_add_dev(fm_ctx* ctx, fm_collection* coll, const void* d_rows, int dtype, int64_t n, int dim,
+                           int64_t row_pitch_bytes /*0 = dense*/, void* producer_stream /*hipStream_t, NULL = null stream, or FM_NO_STREAM*/,
+                           int32_t* img_idx);
+int  fm_collection_knn_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, int32_t k, int32_t* d_img /*device [nq*k]*/,
+                           int32_t* d_idx /*device [nq*k]*/, float* d_dist /*device [nq*k]*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_knn2_ratio_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
+                                  int32_t* d_rows /*device [cap][4]*/, int64_t* d_count /*device*/, int64_t* n_accepted /*host, or NULL*/,
+                                  void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* Classic Ratio-Match in one call: knnMatch(q, t, k=2) then ratio = m[0].distance /
  * m[1].distance (float64) and ratio < tau  -- Classic Matching.ipynb cell 3 (JSON 59-72), the
