@@ -162,6 +162,9 @@ SYMBOLS = {
     "fm_collection_add_dev": (_INT, [_P, _P, _P, _INT, _I64, _INT, _I64, _P, ctypes.POINTER(_I32)]),
     "fm_collection_knn_dev": (_INT, [_P, _P, _P, _I32, _P, _P, _P, _P]),
     "fm_collection_knn2_ratio_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
+    "fm_collection_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    "fm_collection_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
 }
 
 _lib = None
@@ -431,6 +434,49 @@ class Collection(object):
             self.ctx.handle, self.handle, q.handle, float(tau), int(cap), _P(int(rows_ptr)) if rows_ptr else None,
             _P(int(count_ptr)) if count_ptr else None, ctypes.byref(n) if want_count else None, _stream_arg(consumer_stream)))
         return int(n.value) if want_count else None
+
+    def radius_match(self, q, r):
+        """``fm_collection_radius_match``: every row of the stacked images with distance < r per query row.  ``r`` is a scalar
+        or a float32 [nq] array.  Returns (offsets int64[nq + 1], img int32[n], idx int32[n], dist float32[n]): row i's list is
+        img / idx / dist[offsets[i]:offsets[i + 1]], ascending (distance, image, row inside the image).  A counts call sizes
+        the arrays, a second call fills them."""
+        nq = q.n
+        if np.ndim(r) == 0:
+            rad, r_all = None, float(np.float32(r))
+        else:
+            rad = np.ascontiguousarray(r, dtype=np.float32).reshape(-1)
+            if rad.shape[0] != nq:
+                raise ValueError("radius_match: %d radii for %d query rows" % (rad.shape[0], nq))
+            r_all = 0.0
+        rp = _ptr(rad) if rad is not None and nq > 0 else None
+        offsets = np.zeros(nq + 1, dtype=np.int64)
+        total = _I64(0)
+        fn = self.ctx.lib.fm_collection_radius_match
+        self.ctx._check(fn(self.ctx.handle, self.handle, q.handle, rp, r_all, 0, _ptr(offsets), None, None, None, ctypes.byref(total)))
+        n = int(total.value)
+        img = np.empty(n, dtype=np.int32)
+        idx = np.empty(n, dtype=np.int32)
+        dist = np.empty(n, dtype=np.float32)
+        if n > 0:
+            self.ctx._check(fn(self.ctx.handle, self.handle, q.handle, rp, r_all, n, _ptr(offsets), _ptr(img), _ptr(idx), _ptr(dist),
+                               ctypes.byref(total)))
+            if int(total.value) != n:
+                raise FastMatchHipError("fm_collection_radius_match: %d entries on the second call, %d on the first" % (total.value, n))
+        return offsets, img, idx, dist
+
+    def radius_match_dev(self, q, radius_ptr, radius_all, cap, offsets_ptr, img_ptr, idx_ptr, dist_ptr, want_total=True,
+                         consumer_stream=None):
+        """``radius_match`` with the radii read from and the lists left in device memory (``fm_collection_radius_match_dev``):
+        ``radius_ptr`` = device address of float32 [nq] radii, or 0 for the scalar ``radius_all``; ``offsets_ptr`` of an int64
+        [nq + 1] buffer; ``img_ptr`` / ``idx_ptr`` / ``dist_ptr`` of int32 / int32 / float32 [cap] buffers (0 with cap = 0).
+        Returns the number of entries (``want_total``) or None.  The call synchronises (the counts plan the chunks);
+        ``consumer_stream`` as in ``Context.knn_dev``."""
+        n = _I64(0)
+        self.ctx._check(self.ctx.lib.fm_collection_radius_match_dev(
+            self.ctx.handle, self.handle, q.handle, _P(int(radius_ptr)) if radius_ptr else None, float(np.float32(radius_all)), int(cap),
+            _P(int(offsets_ptr)) if offsets_ptr else None, _P(int(img_ptr)) if img_ptr else None, _P(int(idx_ptr)) if idx_ptr else None,
+            _P(int(dist_ptr)) if dist_ptr else None, ctypes.byref(n) if want_total else None, _stream_arg(consumer_stream)))
+        return int(n.value) if want_total else None
 
     def train(self):
         self.ctx._check(self.ctx.lib.fm_collection_train(self.ctx.handle, self.handle))
@@ -803,6 +849,19 @@ class Context(object):
                                                _P(int(rows_ptr)) if rows_ptr else None, _P(int(count_ptr)) if count_ptr else None,
                                                ctypes.byref(n) if want_count else None, _stream_arg(consumer_stream)))
         return int(n.value) if want_count else None
+
+    def radius_match_dev(self, q, t, radius_ptr, radius_all, cap, offsets_ptr, idx_ptr, dist_ptr, want_total=True, consumer_stream=None):
+        """``radius_match`` with the radii read from and the lists left in device memory (``fm_radius_match_dev``):
+        ``radius_ptr`` = device address of float32 [nq] radii, or 0 for the scalar ``radius_all``; ``offsets_ptr`` of an int64
+        [nq + 1] buffer; ``idx_ptr`` / ``dist_ptr`` of int32 / float32 [cap] buffers (0 with cap = 0: a counts call).  Returns
+        the number of entries (``want_total``) or None.  The call synchronises (the counts plan the chunks); what it spares
+        is the radii going up and the lists coming down.  ``consumer_stream`` as in ``knn_dev``."""
+        n = _I64(0)
+        self._check(self.lib.fm_radius_match_dev(
+            self.handle, q.handle, t.handle, _P(int(radius_ptr)) if radius_ptr else None, float(np.float32(radius_all)), int(cap),
+            _P(int(offsets_ptr)) if offsets_ptr else None, _P(int(idx_ptr)) if idx_ptr else None,
+            _P(int(dist_ptr)) if dist_ptr else None, ctypes.byref(n) if want_total else None, _stream_arg(consumer_stream)))
+        return int(n.value) if want_total else None
 
     def bank_gather(self, rows, src_row, float_route=False):
         """The bank ``rows[src_row]`` without building that matrix on the host: the n_src rows are uploaded once and

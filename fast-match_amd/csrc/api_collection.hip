@@ -18,6 +18,7 @@
 // fm_collection_match_accepted_each (the end of this file) is the first caller that makes the stack the OUTPUT operand of a
 // sweep; what the padding rows do there is written down in front of it.
 #include "ctx_internal.h"
+#include "coll_tab.h"
 
 #include <algorithm>
 
@@ -70,22 +71,7 @@ __global__ void coll_pad_norm_kernel(int32_t* __restrict__ norm, int n)
     if (i < n) norm[i] = kCollPadNorm;
 }
 
-struct CollTab { const int32_t* st_img; const int32_t* st_real; const int32_t* img_phys; };
-
-// physical row of the stack -> (image, row inside it); false for a padding row
-__device__ __forceinline__ bool coll_lookup(const CollTab& t, unsigned p, int32_t& img, int32_t& local)
-{
-    const unsigned s = p >> 7;
-    if ((int)(p & 127u) >= t.st_real[s]) return false;
-    img = t.st_img[s];
-    local = (int32_t)(p - (unsigned)t.img_phys[img]);
-    return true;
-}
-
-__device__ __forceinline__ bool coll_real(const CollTab& t, unsigned long long key)
-{
-    return key != ~0ull && (int)((unsigned)key & 127u) < t.st_real[(unsigned)key >> 7];
-}
+// (CollTab, coll_lookup, coll_real: coll_tab.h -- K10's compaction shares them)
 
 // One (query bank, reduced bank) slot of a merge launch: the stacked sweep (tab set, one slot) or one image of
 // fm_collection_knn2_each (tab null: rows are the image's own).
@@ -708,12 +694,14 @@ extern "C" int fm_collection_locate(const int64_t* first_row, int32_t n_images, 
 // ---------------------------------------------------------------------------------------
 // matching
 // ---------------------------------------------------------------------------------------
-static int coll_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const char* who)
+// empty_any_kind (the radius calls, as fm_radius_match pairs banks): a query bank without rows has no kind of its own -- the
+// creators make every empty bank an integer-route one, fm_bank_create_f32_route included -- and is not held to the collection's.
+static int coll_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const char* who, bool empty_any_kind = false)
 {
     int rc = coll_check(ctx, c, who);
     if (rc != FM_OK) return rc;
     if (!q) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank is NULL");
-    if (c->dim != 0 && q->kind != c->stack.kind)
+    if (c->dim != 0 && q->kind != c->stack.kind && !(empty_any_kind && q->n == 0))
         return fail(ctx, FM_EINVAL, std::string(who) + ": the query bank is not of the collection's kind (fm_collection_info)");
     if (c->dim != 0 && q->dim != c->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": the query's width differs from the collection's");
     if (c->dim != 0 && c->stack.kind == FM_BANK_F32 && q->vfin_max > kCollF32Max)
@@ -964,6 +952,46 @@ extern "C" int fm_collection_knn2_ratio_dev(fm_ctx* ctx, fm_collection* c, const
         *n_accepted = (int64_t)cnt;
     }
     return FM_OK;
+}
+
+// radiusMatch against the stacked images (K10, radius.hip): the stack is the train bank of ONE sweep whose epilogue masks
+// the padding rows by index (st_real), and the compaction turns a key's physical row into (image, row).  Host arrays, or
+// (dev) the caller's device arrays.
+static int coll_radius(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const float* radius, float radius_all, int64_t cap, int64_t* offsets,
+                       int32_t* img, int32_t* idx, float* dist, int64_t* n_total, bool dev, void* consumer, const char* who)
+{
+    int rc = coll_query_check(ctx, c, q, who, true);
+    if (rc != FM_OK) return rc;
+    if (c->dim != 0 && c->stack.kind == FM_BANK_BIN)
+        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": Hamming radiusMatch is not built (binary collection)");
+    if (cap < 0) return fail(ctx, FM_EINVAL, std::string(who) + ": cap is negative");
+    if (!offsets) return fail(ctx, FM_EINVAL, std::string(who) + ": offsets is NULL");
+    if (cap > 0 && (!img || !idx || !dist)) return fail(ctx, FM_EINVAL, std::string(who) + ": img / idx / dist is NULL with cap > 0");
+    if (dev) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (radius && (rc = check_device_ptr(ctx, radius, who, "d_radius")) != FM_OK) return rc;
+        if ((rc = check_device_ptr(ctx, offsets, who, "d_offsets")) != FM_OK) return rc;
+        if (img && (rc = check_device_ptr(ctx, img, who, "d_img")) != FM_OK) return rc;
+        if (idx && (rc = check_device_ptr(ctx, idx, who, "d_idx")) != FM_OK) return rc;
+        if (dist && (rc = check_device_ptr(ctx, dist, who, "d_dist")) != FM_OK) return rc;
+    }
+    const CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
+    const RadiusArgs a{who, radius, radius_all, cap, offsets, img, idx, dist, n_total, dev, consumer, &tab, c->total};
+    return radius_match(ctx, *q, c->stack, a);
+}
+
+extern "C" int fm_collection_radius_match(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const float* radius, float radius_all, int64_t cap,
+                                          int64_t* offsets, int32_t* img, int32_t* idx, float* dist, int64_t* n_total)
+{
+    return coll_radius(ctx, c, q, radius, radius_all, cap, offsets, img, idx, dist, n_total, false, FM_NO_STREAM, "fm_collection_radius_match");
+}
+
+extern "C" int fm_collection_radius_match_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const float* d_radius, float radius_all,
+                                              int64_t cap, int64_t* d_offsets, int32_t* d_img, int32_t* d_idx, float* d_dist,
+                                              int64_t* n_total, void* consumer_stream)
+{
+    return coll_radius(ctx, c, q, d_radius, radius_all, cap, d_offsets, d_img, d_idx, d_dist, n_total, true, consumer_stream,
+                       "fm_collection_radius_match_dev");
 }
 
 // The per-image 2-NN lists on the device: d_idx / d_dist [n_images][nq][2].  Up to "batch_group" images per launch of the

@@ -788,7 +788,28 @@ extern "C" int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
     if (!offsets) return fail(ctx, FM_EINVAL, "fm_radius_match: offsets is NULL");
     if (cap > 0 && (!idx || !dist)) return fail(ctx, FM_EINVAL, "fm_radius_match: idx / dist is NULL with cap > 0");
     if (q->n > 0 && t->n > 0 && q->kind != t->kind) return fail(ctx, FM_EINVAL, "fm_radius_match: query/train kind mismatch");
-    return radius_match(ctx, *q, *t, radius, radius_all, cap, offsets, idx, dist, n_total);
+    const RadiusArgs a{"fm_radius_match", radius, radius_all, cap, offsets, nullptr, idx, dist, n_total, false, FM_NO_STREAM, nullptr, 0};
+    return radius_match(ctx, *q, *t, a);
+}
+
+// fm_radius_match with the radii read from, and the offsets and lists written to, the caller's device memory (radius.hip).
+extern "C" int fm_radius_match_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* d_radius, float radius_all, int64_t cap,
+                                   int64_t* d_offsets, int32_t* d_idx, float* d_dist, int64_t* n_total, void* consumer_stream)
+{
+    const char* who = "fm_radius_match_dev";
+    int rc = check_pair(ctx, q, t, who);
+    if (rc != FM_OK) return rc;
+    if (cap < 0) return fail(ctx, FM_EINVAL, "fm_radius_match_dev: cap is negative");
+    if (!d_offsets) return fail(ctx, FM_EINVAL, "fm_radius_match_dev: d_offsets is NULL");
+    if (cap > 0 && (!d_idx || !d_dist)) return fail(ctx, FM_EINVAL, "fm_radius_match_dev: d_idx / d_dist is NULL with cap > 0");
+    if (q->n > 0 && t->n > 0 && q->kind != t->kind) return fail(ctx, FM_EINVAL, "fm_radius_match_dev: query/train kind mismatch");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (d_radius && (rc = check_device_ptr(ctx, d_radius, who, "d_radius")) != FM_OK) return rc;
+    if ((rc = check_device_ptr(ctx, d_offsets, who, "d_offsets")) != FM_OK) return rc;
+    if (d_idx && (rc = check_device_ptr(ctx, d_idx, who, "d_idx")) != FM_OK) return rc;
+    if (d_dist && (rc = check_device_ptr(ctx, d_dist, who, "d_dist")) != FM_OK) return rc;
+    const RadiusArgs a{who, d_radius, radius_all, cap, d_offsets, nullptr, d_idx, d_dist, n_total, true, consumer_stream, nullptr, 0};
+    return radius_match(ctx, *q, *t, a);
 }
 
 // Classic Ratio-Match up to the compaction, in ws_out: 2-NN lists | per-q tidx, dist, ratio, pass | block counts, count word |

@@ -156,9 +156,19 @@ int refuse_bin(fm_ctx* ctx, const fm_bank* b, const char* who);
 // Planes and scale terms of a (query = reduced, train = output rows) pair of float32 banks for x1_round_f32.
 void fill_round_f32(fm::RoundF32* r, const fm::Bank& q, const fm::Bank& t);
 // One expansion round's cross-checked 1-NN on the whole GPU (K7's delegated cross-check, api_match.hip).
-// K10: radiusMatch (radius.hip); arguments checked by fm_radius_match (api_match.hip)
-int radius_match(fm_ctx* ctx, const fm::Bank& q, const fm::Bank& t, const float* radius, float radius_all, int64_t cap,
-                 int64_t* offsets, int32_t* idx, float* dist, int64_t* n_total);
+// K10: radiusMatch (radius.hip); arguments checked by the entry points -- fm_radius_match(_dev) (api_match.hip),
+// fm_collection_radius_match(_dev) (api_collection.hip).
+struct CollTab;      // coll_tab.h
+struct RadiusArgs {
+    const char* who;
+    const float* radius; float radius_all;       // per-row radii (host; dev: device memory, read in place) or null
+    int64_t cap;
+    int64_t* offsets; int32_t* img; int32_t* idx; float* dist;    // host arrays; dev: the caller's device arrays (img: collections)
+    int64_t* n_total;                            // host, may be null
+    bool dev; void* consumer;                    // device form, and the stream it is ordered against (FM_NO_STREAM: none)
+    const CollTab* tab; int64_t real_rows;       // t is a collection's stack: its lookup tables and its real rows; null: a plain bank
+};
+int radius_match(fm_ctx* ctx, const fm::Bank& q, const fm::Bank& t, const RadiusArgs& a);
 // Source rows that are already in device memory (fm_bank_create_dev, fm_collection_add_dev): n rows of FM_DT_* elements,
 // `pitch` bytes apart, read in place by the *_dev_kernel variants of the preparation kernels.
 struct DevSrc { const uint8_t* rows; int dtype; int64_t pitch; };

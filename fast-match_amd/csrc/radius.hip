@@ -18,12 +18,24 @@
 //   sorting               per segment: <= kRSortThread keys one thread, <= kRSortLds one workgroup (bitonic in LDS),
 //                         longer ones rocPRIM's segmented radix sort (off the hot path: r = inf against large banks).
 //   radius_compact_kernel sorted keys -> train index / distance at the row's final offset.
-// Query rows go in chunks whose candidates fit in the option "radius_ws_bytes" (24 bytes per candidate).
+// Query rows go in chunks whose candidates fit in the option "radius_ws_bytes" (24 bytes per candidate; 28 against a collection).
+// A train collection (fm_collection_radius_match): the train bank is the collection's stack, which has padding rows behind
+//   EVERY image whose size is no multiple of 128.  Their values would pass (norm 2^26 against D = 0x7fffffff at r = +inf; 1e18
+//   per float32 dimension is finite, and the `all` path filters nothing), so both sweeps mask them by INDEX: RSweep::st_real,
+//   the real rows per 128-row stage, bounds `rowlim` beside the split's end -- one table word per 64-row stage, uniform.
+//   No padding row ever becomes a key; radius_compact_kernel<true> turns a key's physical row into (image, row) with
+//   coll_tab.h's lookup.  Physical order is logical order, so the keys sort as (distance bits, image, row) unchanged.
+// Device forms (fm_radius_match_dev, fm_collection_radius_match_dev): the limits kernel reads the caller's radii in place,
+//   the offsets come from a device copy of the scan (integer route) or radius_offsets_kernel (float32 route, per chunk), the
+//   compaction writes the caller's arrays at the final offsets for the rows that fit in cap.  The host still reads the
+//   counts back (chunk plan, segment sort).
 // Geometry of the sweeps: a workgroup = 4 waves, a wave = 4 blocks of 16 query rows (the MFMA's N, held in VGPRs for the
 // whole sweep), the train rows (M) stream through LDS 64 at a time, rows padded by 16 bytes against bank conflicts.
 // grid = (query groups of 256 rows, splits of the train range).
 #include "ctx_internal.h"
+#include "coll_tab.h"
 #include <algorithm>
+#include <optional>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -57,7 +69,17 @@ struct RSweep {
     const int64_t* off;        // FILL: segment offsets of the launch's query rows, minus `base`
     int64_t base;
     unsigned long long* keys;
+    const int* st_real;        // a train collection's stack: real rows per 128-row stage (padding sits behind EVERY image and is
+                               // masked by index, never by value); null: a plain bank, padding only behind row nt
 };
+
+// Rows of the 64-row stage at `base` that may be reported: up to the split's end t1 and, in a collection's stack, up to the
+// real rows of the 128-row stage the 64 rows lie in (one table word per stage; <= base where the stage's half is padding).
+__device__ __forceinline__ int r_real_end(const RSweep& p, int base, int t1)
+{
+    if (!p.st_real) return t1;
+    return min(t1, (base & ~127) + p.st_real[base >> 7]);
+}
 
 // Hits of one lane for one query block in a stage (mask over 16 candidates: tile tt, register r -> bit 4 tt + r) into the
 // row's segment: the four lanes of one query row (j, j + 16, j + 32, j + 48) take one cursor increment together.
@@ -125,7 +147,7 @@ void radius_i8_kernel(RSweep p)
             for (int h = 0; h < 2; ++h) a[tt][h] = *(const v4i*)(srow + (16 * tt + j) * kRRowI8 + 64 * h + 16 * g);
             tn[tt] = *(const v4i*)(snorm + 16 * tt + 4 * g);
         }
-        const int rowlim = t1 - base - 4 * g;       // register r of tile tt is a real train row iff 16 tt + r < rowlim
+        const int rowlim = r_real_end(p, base, t1) - base - 4 * g;   // register r of tile tt is a real train row iff 16 tt + r < rowlim
 #pragma unroll
         for (int b = 0; b < kRNB; ++b) {
             unsigned mask = 0;
@@ -197,7 +219,7 @@ void radius_f16_kernel(RSweep p)
             if (tid < kRStage) snorm[tid] = p.tnormf[base + tid] * p.ct;
             __syncthreads();
         }
-        const int rowlim = t1 - base - 4 * g;
+        const int rowlim = r_real_end(p, base, t1) - base - 4 * g;
         unsigned mask[kRNB];
 #pragma unroll
         for (int b = 0; b < kRNB; ++b) mask[b] = 0;
@@ -248,7 +270,8 @@ void radius_f16_kernel(RSweep p)
     }
 }
 
-// Per query row: the radius and what the sweep compares against (see the file comment).
+// Per query row: the radius and what the sweep compares against (see the file comment).  `radius` is the staged copy of the
+// host form's array or, in the device forms, the caller's own array read in place.
 __global__ void radius_limits_kernel(const float* __restrict__ radius, float radius_all, int nq, int f32, int all,
                                      const float* __restrict__ qnormf, float cq, double unit, float nt_max,
                                      int* __restrict__ lim, float* __restrict__ thr, float* __restrict__ rr)
@@ -358,21 +381,41 @@ void radius_copy_back_kernel(unsigned long long* __restrict__ keys, const unsign
     for (int64_t x = b + threadIdx.x; x < e; x += 256) keys[x] = sorted[x];
 }
 
-// One wave per row: the first n sorted keys of the row's segment -> train index / distance at its output offset.
+// One wave per row: the first n sorted keys of the row's segment -> train index / distance at its output offset
+// dst_off[row] - dst_base, for the rows whose lists end at or before `limit` there (the device forms write the caller's arrays
+// at the final offsets and stop at the first row that does not fit in cap; the host forms' staging takes every row).
+// COLL: the key's low word is a physical row of the collection's stack, reported as (image, row inside it) -- the sweeps
+// let no padding row through, so the lookup always finds one.
+template <bool COLL>
 __global__ __launch_bounds__(256)
 void radius_compact_kernel(const unsigned long long* __restrict__ keys, const int64_t* __restrict__ src_off, int64_t src_base,
-                           const int64_t* __restrict__ dst_off, int64_t dst_base, int nrows,
-                           int32_t* __restrict__ idx, float* __restrict__ dist)
+                           const int64_t* __restrict__ dst_off, int64_t dst_base, int nrows, int64_t limit, CollTab tab,
+                           int32_t* __restrict__ img, int32_t* __restrict__ idx, float* __restrict__ dist)
 {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= nrows) return;
     const unsigned long long* s = keys + (src_off[row] - src_base);
     const int64_t d = dst_off[row] - dst_base, n = dst_off[row + 1] - dst_off[row];
+    if (d + n > limit) return;
     for (int64_t x = lane; x < n; x += 64) {
         const unsigned long long k = s[x];
-        idx[d + x] = (int32_t)(unsigned)k;
+        if constexpr (COLL) {
+            int32_t im = -1, lo = -1;
+            (void)coll_lookup(tab, (unsigned)k, im, lo);
+            img[d + x] = im;
+            idx[d + x] = lo;
+        } else {
+            idx[d + x] = (int32_t)(unsigned)k;
+        }
         dist[d + x] = __uint_as_float((unsigned)(k >> 32));
     }
+}
+
+// Device forms: out[i] = add + rel[i] (rel null: add) -- a chunk's final offsets into the caller's array.
+__global__ void radius_offsets_kernel(const int64_t* __restrict__ rel, int64_t add, int64_t n, int64_t* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = add + (rel ? rel[i] : 0);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
@@ -463,24 +506,68 @@ static int r_sort(fm_ctx* ctx, unsigned long long* keys, unsigned long long* alt
     return FM_OK;
 }
 
-int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const float* radius, float radius_all, int64_t cap,
-                 int64_t* offsets, int32_t* idx, float* dist, int64_t* n_total)
+static hipError_t r_compact(fm_ctx* ctx, const RadiusArgs& a, const unsigned long long* keys, const int64_t* src_off, int64_t src_base,
+                            const int64_t* dst_off, int64_t dst_base, int64_t nr, int64_t limit, int32_t* img, int32_t* idx, float* dist)
 {
-    const int64_t nq = q.n, nt = t.n;
-    if (nq == 0 || nt == 0 || (!radius && !(radius_all > 0.f))) {       // (NaN and r <= 0 included: no entries)
+    const dim3 grid((unsigned)((nr + 3) / 4));
+    if (a.tab)
+        hipLaunchKernelGGL(radius_compact_kernel<true>, grid, dim3(256), 0, ctx->stream, keys, src_off, src_base, dst_off, dst_base, (int)nr,
+                           limit, *a.tab, img, idx, dist);
+    else
+        hipLaunchKernelGGL(radius_compact_kernel<false>, grid, dim3(256), 0, ctx->stream, keys, src_off, src_base, dst_off, dst_base, (int)nr,
+                           limit, CollTab{nullptr, nullptr, nullptr}, img, idx, dist);
+    return hipGetLastError();
+}
+
+static hipError_t r_offsets(fm_ctx* ctx, const int64_t* rel, int64_t add, int64_t n, int64_t* out)
+{
+    hipLaunchKernelGGL(radius_offsets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, rel, add, n, out);
+    return hipGetLastError();
+}
+
+// The four entry points (RadiusArgs, ctx_internal.h).  t: a plain bank, or (a.tab set) a collection's stack, whose n counts
+// the padding rows behind every image: the sweeps mask them by index, a.real_rows is what the call is accounted with.
+// a.dev: radius / offsets / img / idx / dist are the caller's DEVICE arrays -- the limits kernel reads the radii in place, the
+// offsets are written by a device copy (integer route: the scan) or kernel (float32 route: per chunk), the compaction writes
+// the lists at their final offsets; the host still reads the counts back to plan the chunks and the segment sort.
+int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
+{
+    const int64_t nq = q.n, nt = t.n, cap = a.cap;
+    const int64_t real = a.tab ? a.real_rows : nt;
+    const bool dev = a.dev;
+    const float* radius = a.radius;
+    int64_t* offsets = a.offsets;
+    int rc;
+    // device forms: the context's stream waits for the consumer's work in front of the first kernel that touches a caller array
+    bool waited = false;
+    auto caller_arrays = [&]() -> int {
+        if (!dev || waited) return FM_OK;
+        waited = true;
+        return wait_for_stream(ctx, a.consumer);
+    };
+    if (nq == 0 || real == 0 || (!radius && !(a.radius_all > 0.f))) {       // (NaN and r <= 0 included: no entries)
+        if (dev) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            if ((rc = caller_arrays()) != FM_OK) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(offsets, 0, (size_t)(nq + 1) * 8, ctx->stream));
+            if (a.n_total) *a.n_total = 0;
+            return results_written(ctx, a.consumer);
+        }
         for (int64_t i = 0; i <= nq; ++i) offsets[i] = 0;
-        if (n_total) *n_total = 0;
+        if (a.n_total) *a.n_total = 0;
         return FM_OK;
     }
-    if (nt > 0x7fffffff || nq > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, "fm_radius_match: more than 2^31 - 1 rows in a bank");
+    if (nt > 0x7fffffff || nq > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, std::string(a.who) + ": more than 2^31 - 1 rows in a bank");
     const bool f32 = q.kind == FM_BANK_F32;
     const bool all = f32 && !filter_usable(q, t);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    CallScope cs(ctx);
+    std::optional<CallScope> cs;          // (the device forms are not accounted in fm_stats)
+    if (!dev) cs.emplace(ctx);
+    auto done = [&]() -> int { return dev ? results_written(ctx, a.consumer) : cs->finish(); };
     // per-row arrays: radius | limit | threshold | exact radius | counts [nq+1] | offsets [nq+1] | cursors [nq+1] |
     // final counts [nq+1] | final offsets [nq+1] | sort row list | long-segment begins | ends
     const size_t b4 = al256((size_t)(nq + 1) * 4), b8 = al256((size_t)(nq + 1) * 8);
-    int rc = ws_ensure(ctx, &ctx->ws_rrows, &ctx->ws_rrows_bytes, 9 * b4 + 4 * b8);
+    rc = ws_ensure(ctx, &ctx->ws_rrows, &ctx->ws_rrows_bytes, 9 * b4 + 4 * b8);
     if (rc != FM_OK) return rc;
     char* w = (char*)ctx->ws_rrows;
     float* d_rad = (float*)w;            w += b4;
@@ -496,12 +583,21 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const float* radius,
     int64_t* d_foff = (int64_t*)w;       w += b8;
     int64_t* d_beg = (int64_t*)w;        w += b8;
     int64_t* d_end = (int64_t*)w;
-    if (radius) HIP_TRY(ctx, hipMemcpyAsync(d_rad, radius, (size_t)nq * 4, hipMemcpyHostToDevice, ctx->stream));
+    const float* k_rad = nullptr;         // what the limits kernel reads
+    if (radius && dev) {
+        if ((rc = caller_arrays()) != FM_OK) return rc;
+        k_rad = radius;                   // (in place: no staging copy)
+    } else if (radius) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_rad, radius, (size_t)nq * 4, hipMemcpyHostToDevice, ctx->stream));
+        k_rad = d_rad;
+    }
     const int dk = q.kscale - t.kscale;
     const float cq = f32 && !all ? ldexpf(1.f, -dk) : 1.f, ct = f32 && !all ? ldexpf(1.f, dk) : 1.f;
     const double unit = f32 && !all ? ldexp(1.0, q.kscale + t.kscale) : 1.0;
+    // (a collection's nm_max is the real rows': the planes of an image are made while its padding rows still hold 0, the
+    // far value goes in afterwards -- coll_f32_finish)
     hipLaunchKernelGGL(radius_limits_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
-                       radius ? (const float*)d_rad : (const float*)nullptr, radius_all, (int)nq, f32 ? 1 : 0, all ? 1 : 0,
+                       k_rad, a.radius_all, (int)nq, f32 ? 1 : 0, all ? 1 : 0,
                        (const float*)(f32 && !all ? q.normf : nullptr), cq, unit, f32 && !all ? t.nm_max * ct : 0.f, d_lim, d_thr, d_rr);
     HIP_TRY(ctx, hipGetLastError());
 
@@ -510,15 +606,18 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const float* radius,
     sw.qrowsh = q.rowsh; sw.qnormf = q.normf; sw.trowsh = t.rowsh; sw.tnormf = t.normf;
     sw.cq = cq; sw.ct = ct; sw.all = all ? 1 : 0;
     sw.nt = (int)nt; sw.lim = d_lim; sw.thr = d_thr;
+    sw.st_real = a.tab ? (const int*)a.tab->st_real : nullptr;
     // 1. counts (candidates on the float32 route), 2. their exclusive scan
     HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, (size_t)(nq + 1) * 4, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
     sw.cnt = d_cnt;
     HIP_TRY(ctx, r_sweep(sw, f32, false, 0, nq, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
-    ctx->kernel_timed = true;
-    ctx->pending_pairs += nq * nt;
-    ctx->pending_bytes += bank_bytes(&q) + bank_bytes(&t);
+    if (!dev) {
+        ctx->kernel_timed = true;
+        ctx->pending_pairs += nq * real;
+        ctx->pending_bytes += bank_bytes(&q) + bank_bytes(&t);
+    }
     if ((rc = r_scan(ctx, d_cnt, d_off, nq)) != FM_OK) return rc;
     std::vector<int64_t> h_off((size_t)nq + 1);
     HIP_TRY(ctx, hipMemcpyAsync(h_off.data(), d_off, (size_t)(nq + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -527,13 +626,20 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const float* radius,
     // rows whose candidates are processed: the integer route's counts are final, so only the rows that fit in cap
     int64_t rows_done = nq;
     if (!f32) {
-        for (int64_t i = 0; i <= nq; ++i) offsets[i] = h_off[i];
-        if (n_total) *n_total = h_off[nq];
+        if (dev) {
+            if ((rc = caller_arrays()) != FM_OK) return rc;
+            HIP_TRY(ctx, hipMemcpyAsync(offsets, d_off, (size_t)(nq + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        } else {
+            for (int64_t i = 0; i <= nq; ++i) offsets[i] = h_off[i];
+        }
+        if (a.n_total) *a.n_total = h_off[nq];
         rows_done = (int64_t)(std::upper_bound(h_off.begin(), h_off.end(), cap) - h_off.begin()) - 1;
-        if (rows_done <= 0) return cs.finish();
+        if (rows_done <= 0) return done();
     }
-    // 3. chunks of query rows whose candidates fit the budget (24 B each: keys, rocPRIM's output, idx + dist)
-    int64_t cmax = (int64_t)ctx->tune.radius_ws_bytes / 24;
+    if ((rc = caller_arrays()) != FM_OK) return rc;
+    // 3. chunks of query rows whose candidates fit the budget: 24 B each (keys, rocPRIM's output, idx + dist), 28 B against a
+    // collection (+ img).  The device forms keep the same chunks although they stage no lists.
+    int64_t cmax = (int64_t)ctx->tune.radius_ws_bytes / (a.tab ? 28 : 24);
     for (int64_t i = 0; i < rows_done; ++i) cmax = std::max(cmax, h_off[i + 1] - h_off[i]);
     int64_t final_total = 0;      // float32 route: entries of the rows before the chunk
     bool open = true;             // ... every row so far fitted in cap
@@ -543,16 +649,19 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const float* radius,
         while (r1 < rows_done && h_off[r1 + 1] - h_off[r0] <= cmax) ++r1;
         const int64_t c0 = h_off[r0], nc = h_off[r1] - c0, nr = r1 - r0;
         if (nc == 0) {
-            if (f32) for (int64_t r = r0; r < r1; ++r) offsets[r] = final_total;
+            if (f32 && dev) HIP_TRY(ctx, r_offsets(ctx, nullptr, final_total, nr, offsets + r0));
+            else if (f32) for (int64_t r = r0; r < r1; ++r) offsets[r] = final_total;
             r0 = r1;
             continue;
         }
-        const size_t kb = al256((size_t)nc * 8);
-        if ((rc = ws_ensure(ctx, &ctx->ws_rkeys, &ctx->ws_rkeys_bytes, 3 * kb)) != FM_OK) return rc;
+        const size_t kb = al256((size_t)nc * 8), ob = al256((size_t)nc * 4);
+        if ((rc = ws_ensure(ctx, &ctx->ws_rkeys, &ctx->ws_rkeys_bytes, 2 * kb + (dev ? 0 : 3 * ob))) != FM_OK) return rc;
         unsigned long long* keys = (unsigned long long*)ctx->ws_rkeys;
         unsigned long long* alt = (unsigned long long*)((char*)ctx->ws_rkeys + kb);
-        int32_t* d_idx = (int32_t*)((char*)ctx->ws_rkeys + 2 * kb);
-        float* d_dist = (float*)((char*)d_idx + (size_t)nc * 4);
+        // host forms: the chunk's lists are staged behind the keys and copied out
+        int32_t* s_idx = (int32_t*)((char*)ctx->ws_rkeys + 2 * kb);
+        float* s_dist = (float*)((char*)s_idx + ob);
+        int32_t* s_img = (int32_t*)((char*)s_idx + 2 * ob);
         HIP_TRY(ctx, hipMemsetAsync(d_cur, 0, (size_t)nr * 4, ctx->stream));
         sw.cnt = d_cur; sw.off = d_off; sw.base = c0; sw.keys = keys;
         HIP_TRY(ctx, r_sweep(sw, f32, true, r0, nr, ctx->stream));
@@ -563,29 +672,40 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const float* radius,
             HIP_TRY(ctx, hipGetLastError());
         }
         if ((rc = r_sort(ctx, keys, alt, nc, h_off.data(), d_off + r0, r0, r1, d_rows, d_beg, d_end)) != FM_OK) return rc;
-        if (!f32) {
-            hipLaunchKernelGGL(radius_compact_kernel, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys,
-                               (const int64_t*)(d_off + r0), c0, (const int64_t*)(d_off + r0), c0, (int)nr, d_idx, d_dist);
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipMemcpyAsync(idx + c0, d_idx, (size_t)nc * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(dist + c0, d_dist, (size_t)nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (!f32 && dev) {
+            // (rows_done: every row of the chunk fits in cap; no synchronisation -- the next chunk follows on the stream)
+            HIP_TRY(ctx, r_compact(ctx, a, keys, d_off + r0, c0, d_off + r0, 0, nr, cap, a.img, a.idx, a.dist));
+        } else if (!f32) {
+            HIP_TRY(ctx, r_compact(ctx, a, keys, d_off + r0, c0, d_off + r0, c0, nr, INT64_MAX, s_img, s_idx, s_dist));
+            HIP_TRY(ctx, hipMemcpyAsync(a.idx + c0, s_idx, (size_t)nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(a.dist + c0, s_dist, (size_t)nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+            if (a.tab) HIP_TRY(ctx, hipMemcpyAsync(a.img + c0, s_img, (size_t)nc * 4, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         } else {
             if ((rc = r_scan(ctx, d_fcnt, d_foff, nr)) != FM_OK) return rc;
-            hipLaunchKernelGGL(radius_compact_kernel, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys,
-                               (const int64_t*)(d_off + r0), c0, (const int64_t*)d_foff, (int64_t)0, (int)nr, d_idx, d_dist);
-            HIP_TRY(ctx, hipGetLastError());
+            if (dev) {
+                // the chunk's final offsets and lists from the device side: the entries before the chunk are known (every chunk
+                // ends in the read-back below), and a row is written only while its list ends within cap -- the final
+                // offsets ascend, so the first row that does not fit closes the prefix for this chunk and, through `open`,
+                // for every later one
+                HIP_TRY(ctx, r_offsets(ctx, d_foff, final_total, nr, offsets + r0));
+                HIP_TRY(ctx, r_compact(ctx, a, keys, d_off + r0, c0, d_foff, -final_total, nr, open ? cap : (int64_t)-1, a.img, a.idx, a.dist));
+            } else {
+                HIP_TRY(ctx, r_compact(ctx, a, keys, d_off + r0, c0, d_foff, (int64_t)0, nr, INT64_MAX, s_img, s_idx, s_dist));
+            }
             h_foff.resize((size_t)nr + 1);
             HIP_TRY(ctx, hipMemcpyAsync(h_foff.data(), d_foff, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             int64_t fit = 0;             // rows of the chunk whose whole lists fit in cap
             for (int64_t r = 0; r < nr; ++r) {
-                offsets[r0 + r] = final_total + h_foff[r];
+                if (!dev) offsets[r0 + r] = final_total + h_foff[r];
                 if (open && final_total + h_foff[r + 1] <= cap) fit = r + 1;
             }
-            if (open && fit > 0 && h_foff[fit] > 0) {
-                HIP_TRY(ctx, hipMemcpyAsync(idx + final_total, d_idx, (size_t)h_foff[fit] * 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(dist + final_total, d_dist, (size_t)h_foff[fit] * 4, hipMemcpyDeviceToHost, ctx->stream));
+            if (!dev && open && fit > 0 && h_foff[fit] > 0) {
+                const size_t nb = (size_t)h_foff[fit] * 4;
+                HIP_TRY(ctx, hipMemcpyAsync(a.idx + final_total, s_idx, nb, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(a.dist + final_total, s_dist, nb, hipMemcpyDeviceToHost, ctx->stream));
+                if (a.tab) HIP_TRY(ctx, hipMemcpyAsync(a.img + final_total, s_img, nb, hipMemcpyDeviceToHost, ctx->stream));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             }
             if (fit < nr) open = false;
@@ -594,10 +714,11 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const float* radius,
         r0 = r1;
     }
     if (f32) {
-        offsets[nq] = final_total;
-        if (n_total) *n_total = final_total;
+        if (dev) HIP_TRY(ctx, r_offsets(ctx, nullptr, final_total, 1, offsets + nq));
+        else offsets[nq] = final_total;
+        if (a.n_total) *a.n_total = final_total;
     }
-    return cs.finish();
+    return done();
 }
 
 }  // namespace fm

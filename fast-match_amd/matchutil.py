@@ -403,7 +403,8 @@ class BFMatcher(object):
         if maxDistance is None and trainDescriptors is not None and np.isscalar(trainDescriptors):
             trainDescriptors, maxDistance = None, trainDescriptors
         if trainDescriptors is None:
-            raise ValueError("BFMatcher.radiusMatch: radiusMatch on a collection is not built; pass a train array")
+            raise ValueError("BFMatcher.radiusMatch: radiusMatch on a collection returns arrays, not DMatch lists, for now: "
+                             "Collection.radius_match (_ffi / torchmatch) is the array-form route; or pass a train array")
         if maxDistance is None:
             raise TypeError("radiusMatch: maxDistance is required")
         return bf_radius_match(queryDescriptors, trainDescriptors, maxDistance, options=self.options)

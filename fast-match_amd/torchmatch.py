@@ -12,11 +12,16 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
 * ``knn(q, t, k)`` -> ``(idx int32 [nq, k], dist float32 [nq, k])``, 1 <= k <= 8.
 * ``mutual_nn(q, t)`` -> ``(tidx int32 [nq], dist float32 [nq])``: the cross-checked 1-NN (-1 / inf: unmatched).
 * ``ratio_match(q, t, tau)`` -> ``(qidx, tidx, dist)`` of the rows whose first / second distance is below ``tau``.
+* ``radius_match(q, t, r)`` -> ``(offsets int64 [nq + 1], idx int32 [n], dist float32 [n])``: every train row with distance
+  < r per query row (``cv2.BFMatcher.radiusMatch``), row i's list at ``offsets[i]:offsets[i + 1]``, ascending (distance, index).
+  ``r`` is a Python or NumPy scalar, or a float32 CUDA tensor ``[nq]`` of one radius per query row on the context's device
+  (``tau * selfdist`` as it comes out of a kernel), read in place (``fm_radius_match_dev``).
 
 * ``Collection(context=None)`` -- a train collection (``cv2.BFMatcher.add`` / ``train``) whose images are CUDA tensors: the
   retrieval flow extract -> ``add`` to the database -> query -> consume without a copy to the host.  A context manager.
   ``add(tensor, *, binary=False)`` reads the tensor in place (``fm_collection_add_dev``) and returns the image index;
   ``knn(q, k)`` -> ``(img, idx, dist)`` [nq, k]; ``ratio_match(q, tau)`` -> ``(qidx, img, tidx, dist)``;
+  ``radius_match(q, r)`` -> ``(offsets, img, idx, dist)``, ``r`` as in the module's ``radius_match``;
   ``fast_match_each(q, tau, cap=None)`` -> ``(rows int32 [n_images, cap, 3], counts int64 [n_images])``, the accepted-match
   test inside every image (``q``: a ``Bank`` carrying self distances, ``Context.self_dist_batch([q], want_host=False)``);
   ``clear()``, ``close()``, ``info()``.  The collection equals the ``_ffi.Collection`` the same values build on the host.
@@ -27,11 +32,16 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
 Streams: ``torch.cuda.current_stream()`` is both the producer of the descriptor tensors and the consumer of the results --
 the library orders its kernels behind the one and the stream behind the other on the device, so no ``synchronize()`` is needed
 on either side (``ratio_match`` and ``Collection.ratio_match`` read the accepted count back to size their outputs: one host
-wait).
+wait; ``radius_match`` and ``Collection.radius_match`` likewise wait for the total that sizes theirs -- a counts call, then a
+fill call -- and the library reads the per-row counts back to plan its chunks).  For the radius calls the current stream is
+also the producer of ``r``.
 
 ``torch`` is imported inside the functions: importing the package does not need it.  A CPU tensor, another dtype or
-another rank raises ``ValueError`` before the library is touched.  Tensors must live on the context's device.
+another rank raises ``ValueError`` before the library is touched -- for a radius tensor: a CPU tensor, a dtype other than
+float32, a shape other than ``[nq]``, another device.  Tensors must live on the context's device.
 """
+import numpy as np
+
 from . import _ffi
 
 _DTYPES = {"torch.uint8": _ffi.FM_DT_U8, "torch.float32": _ffi.FM_DT_F32, "torch.float16": _ffi.FM_DT_F16,
@@ -156,6 +166,68 @@ def ratio_match(q, t, tau):
             b.close()
 
 
+def _rows_and_device(q):
+    """(query rows, device index) of a bank or a descriptor tensor -- nothing reaches the library."""
+    if isinstance(q, _ffi.Bank):
+        return q.n, q.ctx.device
+    t, _ = _checked(q)
+    return t.shape[0], t.device.index
+
+
+def _radius(r, nq, device):
+    """(float32 CUDA tensor [nq] or None, scalar radius) or ValueError -- before anything reaches the library."""
+    import torch
+    if not isinstance(r, torch.Tensor):
+        if np.ndim(r) != 0:
+            raise ValueError("a radius per query row must be a float32 CUDA tensor [nq] (a host array goes to Context.radius_match)")
+        return None, float(np.float32(r))
+    if r.dtype != torch.float32:
+        raise ValueError("radius dtype %s: a radius tensor must be float32" % r.dtype)
+    if r.dim() != 1:
+        raise ValueError("a radius tensor must be 1-D [nq], got %d-D" % r.dim())
+    if r.shape[0] != nq:
+        raise ValueError("%d radii for %d query rows" % (r.shape[0], nq))
+    if not r.is_cuda:
+        raise ValueError("a radius tensor must be a CUDA tensor (a host array goes to Context.radius_match)")
+    if device is not None and r.device.index != device:
+        raise ValueError("the radius tensor lives on device %s, the context on device %s" % (r.device.index, device))
+    return r.contiguous(), 0.0
+
+
+def _radius_lists(call, nq, rad, r_all, stream, dev, with_img):
+    """The counts call, then the fill call, of a ``radius_match_dev`` (``call(radius_ptr, radius_all, cap, offsets_ptr, list
+    pointers ...)``): device tensors (offsets, [img,] idx, dist)."""
+    import torch
+    nl = 3 if with_img else 2
+    offsets = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+    rp = rad.data_ptr() if rad is not None and nq else 0
+    total = call(rp, r_all, 0, offsets.data_ptr(), *([0] * nl), consumer_stream=stream)
+    lists = [torch.empty(total, dtype=torch.int32, device=dev) for _ in range(nl - 1)]
+    lists.append(torch.empty(total, dtype=torch.float32, device=dev))
+    if total > 0:
+        again = call(rp, r_all, total, offsets.data_ptr(), *[x.data_ptr() for x in lists], consumer_stream=stream)
+        if again != total:
+            raise _ffi.FastMatchHipError("radius_match: %d entries on the second call, %d on the first" % (again, total))
+    return (offsets,) + tuple(lists)
+
+
+def radius_match(q, t, r):
+    """``cv2.BFMatcher.radiusMatch``: ``(offsets int64 [nq + 1], idx int32 [n], dist float32 [n])`` CUDA tensors, every train
+    row with distance < r per query row, ascending (distance, train index).  ``r``: a scalar, or a float32 CUDA tensor [nq]
+    read in place behind the current stream's work (module docstring).  One host wait for the total."""
+    nq, device = _rows_and_device(q)
+    if not isinstance(t, _ffi.Bank):
+        _checked(t)
+    rad, r_all = _radius(r, nq, device)
+    qb, tb, made = _pair(q, t)
+    try:
+        stream, dev = _stream_and_device(qb.ctx)
+        return _radius_lists(lambda *a, **k: qb.ctx.radius_match_dev(qb, tb, *a, **k), qb.n, rad, r_all, stream, dev, False)
+    finally:
+        for b in made:
+            b.close()
+
+
 class Collection(object):
     """A train collection fed from CUDA tensors (module docstring).  The library's collection is made with the first call
     that needs it, on ``context`` or the default context of the first tensor's device."""
@@ -236,6 +308,21 @@ class Collection(object):
             rows = rows[:min(m, cap)]
             return (rows[:, 0].contiguous(), rows[:, 1].contiguous(), rows[:, 2].contiguous(),
                     rows[:, 3].contiguous().view(torch.float32))
+        finally:
+            for b in made:
+                b.close()
+
+    def radius_match(self, q, r):
+        """Every row of the stacked images with distance < r per query row: ``(offsets int64 [nq + 1], img int32 [n], idx int32
+        [n], dist float32 [n])`` CUDA tensors, row i's list at ``offsets[i]:offsets[i + 1]``, ascending (distance, image, row
+        inside the image).  ``r`` as in the module's ``radius_match``.  One host wait for the total."""
+        nq, device = _rows_and_device(q)
+        rad, r_all = _radius(r, nq, device if self._context is None else self._context.device)
+        qb, made = self._query(q)
+        try:
+            stream, dev = _stream_and_device(qb.ctx)
+            coll = self._coll
+            return _radius_lists(lambda *a, **k: coll.radius_match_dev(qb, *a, **k), qb.n, rad, r_all, stream, dev, True)
         finally:
             for b in made:
                 b.close()

@@ -49,7 +49,8 @@ typedef struct fm_bank fm_bank;
  * FM_BANK_BIN, fm_bank_create_bin; revision 11: additions -- fm_collection_*; revision 12: additions -- FM_DT_*,
  * fm_bank_create_dev, fm_knn_dev, fm_xcheck1_dev, fm_knn2_ratio_dev; still revision 12, additions only --
  * fm_collection_match_accepted_each, fm_collection_match_accepted_each_dev, the option "coll_ws_bytes"; still revision 12,
- * additions only -- fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev).  A binding compares
+ * additions only -- fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev; still revision 12, additions
+ * only -- fm_collection_radius_match, fm_radius_match_dev, fm_collection_radius_match_dev).  A binding compares
  * fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.                      */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -113,7 +114,8 @@ int  fm_ctx_destroy(fm_ctx* ctx);
  *                         repeated in a run state four times as large (2; r05: counted per array)
  *   "expand_prof"  0|1    K7: per-phase timers of the first pair of a launch on stderr
  *   "radius_ws_bytes" 65536..2^31-1  fm_radius_match: device bytes for the candidates of one chunk of query rows (2^30;
- *                         24 bytes per candidate); a row whose own list needs more runs in a chunk of its own
+ *                         24 bytes per candidate, 28 in the collection forms); a row whose own list needs more runs in a
+ *                         chunk of its own
  *   "coll_ws_bytes" 0..2^31-1  fm_collection_match_accepted_each: device bytes for the per-(image, query row) arrays of one
  *                         chunk of consecutive images (25 bytes per entry; at least one image per chunk); 0 = one chunk up
  *                         to 64 MiB, beyond that a quarter of the free device memory (0)
@@ -222,7 +224,9 @@ int  fm_knn(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k,
  * idx / dist[0 .. offsets[m]) written for the longest prefix of rows m whose whole lists fit in cap (cap = 0: counts
  * only, idx / dist may be NULL).  A caller sizes its arrays with a counts call and repeats it with cap = *n_total.
  * Integer route: v_mfma_i32_16x16x64_i8 sweep against the per-row limit D_i = the largest d2 with sqrtf(d2) < r_i;
- * float32 route: an fp16-MFMA filter within K8's margin, then the exact chain for the candidates (radius.hip).        */
+ * float32 route: an fp16-MFMA filter within K8's margin, then the exact chain for the candidates (radius.hip).
+ * fm_collection_radius_match asks the same of a train collection, fm_radius_match_dev / fm_collection_radius_match_dev take the
+ * radii from and leave the lists in device memory: both described below.                                              */
 int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* radius /*[nq] or NULL*/,
                     float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* idx, float* dist,
                     int64_t* n_total);
@@ -300,12 +304,32 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  *     may be NULL).  Enqueued on the context's stream; consumer_stream is ordered against the fills in both directions, as in
  *     fm_match_accepted_dev_batch.  h_counts (host, any memory, or NULL) receives the full counts; asking for them is the
  *     call's one host synchronisation.
- *   fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev: images from, and stacked results into, DEVICE
- *     memory -- described with the other device entry points below ("descriptors already on the GPU").
+ *   fm_collection_radius_match: fm_radius_match(q, T, ...) for T = the images' rows stacked in image order -- every database
+ *     descriptor within r_i of query row i in ONE matrix-core sweep over the whole allocation (place recognition,
+ *     de-duplication, Fast-Match's one-to-many test d(q, t) < tau * selfdist(q)).  Every hit is (img, row inside that image);
+ *     membership is the strict float32 compare dist < r_i on the value fm_collection_knn returns for the pair (float32-root
+ *     behaviour above d^2 = 4 197 200 included).  The radius rules are fm_radius_match's (r <= 0 or NaN: an empty list; +inf:
+ *     every real row; radius[i] overrides radius_all), and so are, word for word, the offsets / cap / counts-only /
+ *     longest-prefix-of-whole-rows rules; img is written beside idx and dist.  A list ascends by (distance bits, img, row):
+ *     physical order in the stack is logical order, so the sort key (distance bits << 32 | physical row) needs no change.
+ *     Empty images keep their index and contribute nothing; an empty collection, nq = 0 and a collection of empty images
+ *     only are valid and give all-zero offsets.  The padding rows behind every image are masked by INDEX in the sweep's
+ *     epilogue, on both routes (the per-stage real-row table; their values -- norm 2^26, 1e18 per float32 dimension -- would
+ *     pass r = +inf), and the physical row -> (img, row) lookup is fused into the compaction.  The option "radius_ws_bytes"
+ *     keeps its meaning; a candidate takes 28 bytes here (24 for a pair: + img).  Errors, in fm_collection_knn's order: NULL
+ *     handles; a query of another kind or width (FM_EINVAL; as in fm_radius_match a query bank with no rows is not held to
+ *     the kind: every creator makes an empty bank an integer-route one); a float32-route query with a finite magnitude above
+ *     FM_COLLECTION_F32_MAX (FM_EUNSUPPORTED); a binary collection (FM_EUNSUPPORTED); cap < 0, offsets NULL, or img / idx /
+ *     dist NULL with cap > 0 (FM_EINVAL).  Accounted in fm_stats like fm_radius_match, pairs = nq * real rows.
+ *   fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev, fm_collection_radius_match_dev: images from,
+ *     and stacked results into, DEVICE memory -- described with the other device entry points below ("descriptors already on
+ *     the GPU").
  * Not built: crossCheck on a collection (OpenCV's batchDistance asserts update == 0 under crossCheck -- recalled, SURVEY.md
- * Appendix A; neither cv2 nor its source was at hand), radiusMatch, masks, the expansion loop on a collection, a batched
- * K8 / K11 (float32 / binary) per-image sweep, binary collections in the self-distance test, sharding a collection across
- * GPUs, removing single images, turning an integer-route collection of float32 images into a float32-route one for a
+ * Appendix A; neither cv2 nor its source was at hand), Hamming radiusMatch (for pairs or collections), radius queries per
+ * image separately (an _each form), skipping the second count sweep of the counts-then-fill pattern, masks,
+ * the expansion loop on a collection, a batched K8 / K11 (float32 / binary) per-image sweep,
+ * binary collections in the self-distance test, sharding a collection across GPUs (radius queries included), removing single
+ * images, turning an integer-route collection of float32 images into a float32-route one for a
  * non-integer QUERY.                                                                    */
 typedef struct fm_collection fm_collection;
 #define FM_COLLECTION_F32_MAX 144115188075855872.0f   /* 2^57: largest finite magnitude of a float32-route collection and its queries */
@@ -328,6 +352,9 @@ int  fm_collection_knn2_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q,
                              int32_t* idx /*[n_images][nq][2]*/, float* dist /*[n_images][nq][2]*/);
 int  fm_collection_votes(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int32_t mode,
                          int64_t* votes /*[n_images]*/);
+int  fm_collection_radius_match(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const float* radius /*host [nq] or NULL*/,
+                                float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* img, int32_t* idx, float* dist,
+                                int64_t* n_total);
 int  fm_collection_match_accepted_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
                                        int32_t* qidx, int32_t* tidx, float* dist, double* ratio /* each [n_images][cap] */,
                                        int64_t* n_accepted /*[n_images]: the full count per image*/);
@@ -403,7 +430,20 @@ int  fm_collection_match_accepted_each_dev(fm_ctx* ctx, fm_collection* coll, con
  *   count; no host synchronisation on the integer and binary routes except n_accepted != NULL -- and the first match after an
  *   add, which uploads the lookup tables as fm_collection_train does).  Errors in fm_collection_knn's order; k > 8 is
  *   FM_EUNSUPPORTED, k < 1 FM_EINVAL.  Not accounted in fm_stats.
- * Not built: device sources for fm_bank_refill_u8_async and fm_bank_append_*; device results for fm_radius_match and
+ * fm_radius_match_dev, fm_collection_radius_match_dev: fm_radius_match and fm_collection_radius_match with everything that is
+ *   per row or per hit in DEVICE memory: the same values in the same order.  d_radius (device float32 [nq], or NULL for
+ *   radius_all) is read in place by the limits kernel -- tau * selfdist computed on the device goes straight in, no staging
+ *   copy; d_offsets[0 .. nq] is always written (a device copy of the scan, or a small kernel per chunk on the float32 route);
+ *   the compaction writes d_idx / d_dist (and d_img) at each row's final offset, for the longest prefix of rows whose whole
+ *   lists fit in cap, and nothing beyond that prefix; *n_total (host, may be NULL) = the number of entries.  d_radius,
+ *   d_offsets and the list pointers must be device memory of the context's device (fm_knn_dev's check; a host pointer is
+ *   FM_EINVAL); the list pointers may be NULL when cap = 0.  Ordering is fm_knn_dev's in both directions: the first kernel
+ *   that reads d_radius or writes a caller array waits on the device for what consumer_stream has been given so far, and
+ *   consumer_stream is made to wait for the writes; FM_NO_STREAM means no such stream.
+ *   Host synchronisation: the call DOES synchronise -- the counts are read back to plan the chunks and the segment sort (per
+ *   chunk on the float32 route), as in the host forms; what it spares is the radii going up and the lists coming down.  The
+ *   other errors are the host forms', in their order.  Not accounted in fm_stats.
+ * Not built: device sources for fm_bank_refill_u8_async and fm_bank_append_*; device results for
  *   fm_self_dist (fm_self_dist_batch attaches them on the device already) and for fm_collection_knn2_each / _votes; an
  *   enqueue-only float32 route; tensors on another GPU than the context's (copy them over first).                          */
 #define FM_DT_U8   1
@@ -428,6 +468,13 @@ int  fm_collection_knn_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, i
 int  fm_collection_knn2_ratio_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
                                   int32_t* d_rows /*device [cap][4]*/, int64_t* d_count /*device*/, int64_t* n_accepted /*host, or NULL*/,
                                   void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_radius_match_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* d_radius /*device [nq] or NULL*/,
+                         float radius_all, int64_t cap, int64_t* d_offsets /*device [nq+1]*/, int32_t* d_idx, float* d_dist,
+                         int64_t* n_total /*host, or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_radius_match_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const float* d_radius /*device [nq] or NULL*/,
+                                    float radius_all, int64_t cap, int64_t* d_offsets /*device [nq+1]*/, int32_t* d_img,
+                                    int32_t* d_idx, float* d_dist, int64_t* n_total /*host, or NULL*/,
+                                    void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* Classic Ratio-Match in one call: knnMatch(q, t, k=2) then ratio = m[0].distance /
  * m[1].distance (float64) and ratio < tau  -- Classic Matching.ipynb cell 3 (JSON 59-72), the
