@@ -159,6 +159,8 @@ SYMBOLS = {
     "fm_collection_votes": (_INT, [_P, _P, _P, ctypes.c_double, _I32, _P]),
     "fm_collection_match_accepted_each": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, _P]),
     "fm_collection_match_accepted_each_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P]),
+    "fm_collection_xcheck1_each": (_INT, [_P, _P, _P, ctypes.c_float, _P, _P, _P]),
+    "fm_collection_xcheck1_each_dev": (_INT, [_P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P]),
     "fm_collection_add_dev": (_INT, [_P, _P, _P, _INT, _I64, _INT, _I64, _P, ctypes.POINTER(_I32)]),
     "fm_collection_knn_dev": (_INT, [_P, _P, _P, _I32, _P, _P, _P, _P]),
     "fm_collection_knn2_ratio_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
@@ -571,6 +573,44 @@ class Collection(object):
             raise ValueError("h_counts must be a contiguous int64 array of n_images words")
         self.ctx._check(self.ctx.lib.fm_collection_match_accepted_each_dev(
             self.ctx.handle, self.handle, q.handle, float(tau), int(cap), _P(int(rows_ptr)) if rows_ptr else None,
+            _P(int(counts_ptr)) if counts_ptr else None, _ptr(h_counts) if h_counts is not None else None,
+            _stream_arg(consumer_stream)))
+
+    def xcheck1_each(self, q, max_dist=float("inf")):
+        """``fm_collection_xcheck1_each``: the cross-checked 1-NN of ``q`` inside every image separately --
+        ``(tidx int32 [n_images, nq], dist float32 [n_images, nq])``, slot i equal to ``Context.xcheck1(q, bank(image_i))``
+        (-1 / inf: unmatched); a match is kept while ``dist < max_dist`` (strict; inf: every match, <= 0 or NaN: none)."""
+        ni = self.info()[0]
+        tidx, dist = np.full((ni, q.n), -1, np.int32), np.full((ni, q.n), np.inf, np.float32)
+        if tidx.size:
+            self.ctx._check(self.ctx.lib.fm_collection_xcheck1_each(self.ctx.handle, self.handle, q.handle, float(max_dist),
+                                                                    _ptr(tidx), _ptr(dist), None))
+        else:       # (nothing to fill: the call still checks the pair)
+            n = np.zeros(ni, np.int64)
+            self.ctx._check(self.ctx.lib.fm_collection_xcheck1_each(self.ctx.handle, self.handle, q.handle, float(max_dist),
+                                                                    None, None, _ptr(n) if ni else None))
+        return tidx, dist
+
+    def mutual_votes(self, q, max_dist=float("inf")):
+        """int64[n_images]: the number of query rows ``xcheck1_each`` matches per image (its counts-only call: only n_images
+        words come back)."""
+        n = np.zeros(self.info()[0], np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_xcheck1_each(self.ctx.handle, self.handle, q.handle, float(max_dist), None, None,
+                                                                _ptr(n) if n.shape[0] else None))
+        return n
+
+    def xcheck1_each_dev(self, q, max_dist, rows_ptr, counts_ptr, cap, h_counts=None, consumer_stream=None):
+        """``xcheck1_each`` with device outputs (``fm_collection_xcheck1_each_dev``); the arguments are those of
+        ``match_accepted_each_dev`` with ``max_dist`` in the place of ``tau``: ``rows_ptr`` = device address of an int32
+        [n_images, cap, 3] block (query, row inside the image, float32 distance bits), ``counts_ptr`` of an int64 [n_images]
+        array that receives min(count, cap); ``h_counts`` = an int64 [n_images] host array for the full counts (the call then
+        synchronises once) or None (enqueued only)."""
+        ni = self.info()[0]
+        if h_counts is not None and (not isinstance(h_counts, np.ndarray) or h_counts.dtype != np.int64 or h_counts.size < ni
+                                     or not h_counts.flags.c_contiguous):
+            raise ValueError("h_counts must be a contiguous int64 array of n_images words")
+        self.ctx._check(self.ctx.lib.fm_collection_xcheck1_each_dev(
+            self.ctx.handle, self.handle, q.handle, float(max_dist), int(cap), _P(int(rows_ptr)) if rows_ptr else None,
             _P(int(counts_ptr)) if counts_ptr else None, _ptr(h_counts) if h_counts is not None else None,
             _stream_arg(consumer_stream)))
 

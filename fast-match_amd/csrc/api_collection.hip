@@ -1185,13 +1185,29 @@ extern "C" int fm_collection_votes(fm_ctx* ctx, fm_collection* c, const fm_bank*
 // enqueued back to back on the context's stream into the same arrays; counts and compacted rows of all images are copied
 // out once, at the end.
 // Float32 route: per-image reverse sweeps (K8 / K5) enqueued back to back on the images' bank views, each followed by
-// fm_xcheck1's own election into slot i of the table; the tail is shared.
+// fm_xcheck1's own election into slot i of the table; the tail is shared.  (One reverse K8 sweep over the stack is not
+// built: every padding output row would put its candidates into the filter's lists.)
+//
+// fm_collection_xcheck1_each is the same table without the ratio test -- cv2.BFMatcher(norm, crossCheck=True).match(q, T_i)
+// image by image, kept while dist < max_dist -- and takes it to binary collections:
+// Binary route.  The election of a train row does not depend on its image here either: ONE reverse K11 sweep per chunk,
+// cols = the chunk's stack view, red = the query bank (stage_real stays null: the reduced side is an ordinary bank whose
+// tail the sweep masks by nred).  The stack as the OUTPUT operand of ham_sweep_kernel (first use), its padding rows:
+//   * an output row is read through rows4 only.  A padding row is an all-zero FP4 row: every dot product is 0, so it sits
+//     at h = W / 2 from every query row and leaves a VALID key (W / 2, the lowest query row) -- no value marks it.
+//   * nothing may read that key as a candidate: the election drops the row by index (coll_lookup: st_real), exactly as
+//     it drops the integer route's.  Output rows share no state in K11 (no bounds, no cut), so a padding row cannot
+//     change a real row's key.
+// The keys' high word already holds the float32 bits of h (an integer <= 512: exact, one root per value), so the election
+// takes them as they are: no sqrt_bits, no tie list.  Ties follow from the key order alone: (h bits, query row) per train
+// row -- the lowest query index --, then (h bits, row inside the image) per (image, query row) -- the lowest row.
 
 // Segmented election: xcheck_scatter_kernel over the physical rows [p0, p0 + nrows) of the stack; the key's low word is the
-// row inside its image, the table slot (image - img0, query).
+// row inside its image, the table slot (image - img0, query).  f32: the keys' high word holds the distance's float32 bits
+// (K11) and is taken as it is; else the exact d2 (integer route: float32 root, tie list).
 __global__ void coll_elect_kernel(const unsigned long long* __restrict__ partial, int nsplit, int ncols_alloc, int64_t nrows,
                                   unsigned p0, CollTab tab, int img0, int64_t nq, unsigned long long* __restrict__ qbest,
-                                  unsigned* __restrict__ fix)
+                                  int f32, unsigned* __restrict__ fix)
 {
     // four lanes per physical row, each takes every 4th split
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1213,9 +1229,12 @@ __global__ void coll_elect_kernel(const unsigned long long* __restrict__ partial
     int32_t img, local;
     if (!coll_lookup(tab, p, img, local)) return;          // a padding row of the stack
     const unsigned q = (unsigned)b;
-    const unsigned hi = (unsigned)(b >> 32);
-    if (fix && hi >= kSqrtTieMin && sqrt_ties_up(hi)) { fix[4 + atomicAdd(fix, 1u)] = p; return; }
-    atomicMin(&qbest[(int64_t)(img - img0) * nq + q], ((unsigned long long)sqrt_bits(hi) << 32) | (unsigned)local);
+    unsigned hi = (unsigned)(b >> 32);
+    if (!f32) {
+        if (fix && hi >= kSqrtTieMin && sqrt_ties_up(hi)) { fix[4 + atomicAdd(fix, 1u)] = p; return; }
+        hi = sqrt_bits(hi);
+    }
+    atomicMin(&qbest[(int64_t)(img - img0) * nq + q], ((unsigned long long)hi << 32) | (unsigned)local);
 }
 
 // sqrt_fix_kernel<1> (api_match.hip) per image: the listed physical rows of the stack elect again, exactly, over all query
@@ -1261,12 +1280,18 @@ void coll_sqrt_fix1_kernel(const unsigned* __restrict__ fix, const int8_t* __res
     }
 }
 
-// xcheck_finalize_kernel for a chunk's table, blockIdx.y = image of the chunk: decode, the same float64 division, the flag,
-// and the block counts of the compaction behind it.
+// The test a decoded entry must pass.  selfdist set: Fast-Match's accepted-match test, (double)dist / selfdist[q] < tau.
+// Null: the plain cross-check under a distance limit, dist < max_dist -- a strict float32 compare on the reported value
+// (+inf keeps every match, a limit <= 0 or NaN none) -- and a dropped entry then reads -1 / +inf in the decode arrays, which
+// are the host form's dense result.
+struct CollKeep { const double* selfdist; double tau; float max_dist; };
+
+// xcheck_finalize_kernel for a chunk's table, blockIdx.y = image of the chunk: decode, the test (the same float64 division),
+// the flag, and the block counts of the compaction behind it.  ratio: null without self distances.
 __global__ __launch_bounds__(256)
-void coll_accept_finalize_kernel(const unsigned long long* __restrict__ qbest, int64_t nq, const double* __restrict__ selfdist, double tau,
-                                 int32_t* __restrict__ tidx, float* __restrict__ dist, double* __restrict__ ratio, uint8_t* __restrict__ pass,
-                                 int* __restrict__ block_counts)
+void coll_each_finalize_kernel(const unsigned long long* __restrict__ qbest, int64_t nq, CollKeep keep,
+                               int32_t* __restrict__ tidx, float* __restrict__ dist, double* __restrict__ ratio, uint8_t* __restrict__ pass,
+                               int* __restrict__ block_counts)
 {
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t e = (int64_t)blockIdx.y * nq + q;
@@ -1279,25 +1304,30 @@ void coll_accept_finalize_kernel(const unsigned long long* __restrict__ qbest, i
         if (key != ~0ull) {
             ti = (int32_t)(unsigned)key;
             d = __uint_as_float((unsigned)(key >> 32));
-            r = (double)d / selfdist[q];
-            p = r < tau;
+            if (keep.selfdist) {
+                r = (double)d / keep.selfdist[q];
+                p = r < keep.tau;
+            } else {
+                p = d < keep.max_dist;
+                if (!p) { ti = -1; d = INFINITY; }
+            }
         }
         tidx[e] = ti;
         dist[e] = d;
-        ratio[e] = r;
+        if (ratio) ratio[e] = r;
         pass[e] = p ? 1 : 0;
     }
     emit_block_count(__ballot(p), block_counts + (size_t)blockIdx.y * gridDim.x);
 }
 
-// Ordered compaction of image blockIdx.y's accepted rows (compact_slot) into its slot of the outputs, addressed from the
+// Ordered compaction of image blockIdx.y's kept rows (compact_slot) into its slot of the outputs, addressed from the
 // chunk's first image: four arrays [.][cap] (o_rows null) or 12-byte rows [.][cap][3] with o_count = the rows that are there;
-// full = the number accepted.  cap = 0: counts only.
+// full = the number kept.  cap = 0: counts only.
 __global__ __launch_bounds__(256)
-void coll_accept_compact_kernel(const int32_t* __restrict__ tidx, const float* __restrict__ dist, const double* __restrict__ ratio,
-                                const uint8_t* __restrict__ pass, const int* __restrict__ block_counts, int64_t nq, int64_t cap,
-                                int32_t* __restrict__ o_q, int32_t* __restrict__ o_t, float* __restrict__ o_d, double* __restrict__ o_r,
-                                int32_t* __restrict__ o_rows, long long* __restrict__ o_count, unsigned long long* __restrict__ full)
+void coll_each_compact_kernel(const int32_t* __restrict__ tidx, const float* __restrict__ dist, const double* __restrict__ ratio,
+                              const uint8_t* __restrict__ pass, const int* __restrict__ block_counts, int64_t nq, int64_t cap,
+                              int32_t* __restrict__ o_q, int32_t* __restrict__ o_t, float* __restrict__ o_d, double* __restrict__ o_r,
+                              int32_t* __restrict__ o_rows, long long* __restrict__ o_count, unsigned long long* __restrict__ full)
 {
     const int64_t i = blockIdx.y;
     int64_t q, total;
@@ -1320,46 +1350,122 @@ void coll_accept_compact_kernel(const int32_t* __restrict__ tidx, const float* _
 }
 
 constexpr size_t kCollAcceptEntry = 25;            // qbest 8 | tidx 4 | dist 4 | ratio 8 | pass 1 bytes per (image, query row)
+constexpr size_t kCollXcheckEntry = 17;            // fm_collection_xcheck1_each: the same without the ratio
 constexpr int kCollAcceptMaxChunk = 65535;         // (blockIdx.y of the tail kernels)
 
-// Host form: qidx / tidx / dist / ratio [n_images][cap], n_accepted [n_images].  Device form (d_counts != null): d_rows
-// [n_images][cap][3], d_counts [n_images], h_counts host [n_images] or null.
-static int coll_accept_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* qidx, int32_t* tidx,
-                            float* dist, double* ratio, int64_t* n_accepted, int32_t* d_rows, int64_t* d_counts, int64_t* h_counts,
-                            void* consumer, bool to_dev, const char* who)
+// The images [i0, i1) as one bank view of the stack (consecutive images are consecutive physical rows)
+static fm::Bank coll_chunk_view(const fm_collection* c, int64_t i0, int64_t i1)
 {
-    int rc = coll_query_check(ctx, c, q, who);
+    const int64_t ni = (int64_t)c->rows.size();
+    const int64_t p0 = c->phys[(size_t)i0], p1 = i1 < ni ? c->phys[(size_t)i1] : c->used;
+    fm::Bank v = bank_rows_view(c->stack, p0, p1 - p0);
+    v.usq_max = 0;
+    for (int64_t i = i0; i < i1; ++i) v.usq_max = std::max(v.usq_max, c->usq[(size_t)i]);
+    return v;
+}
+
+// The front half for the images [i0, i1): d_qbest[image - i0][query row] = (float32 distance bits << 32 | row inside the
+// image) of the closest row of the image that elects the query row, ~0 where none does -- slot by slot the table of
+// fm_xcheck1(q, bank(image)).  Integer and binary routes: one reverse top-1 sweep over the chunk's stack view and the
+// segmented election (the integer route's tie list redone exactly); float32 route: the per-image sweeps, each with
+// fm_xcheck1's own election.  cut: launch_rowreduce's (integer route) or null.  *timed: a sweep was enqueued; on the
+// integer and binary routes ev_k0 is recorded in front of the first one and ev_k1 is the caller's.
+static int coll_qbest_chunk(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int64_t i0, int64_t i1, const unsigned* cut,
+                            unsigned long long* d_qbest, bool* timed)
+{
+    const int64_t nq = q->n;
+    int rc;
+    HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)(i1 - i0) * nq * 8, ctx->stream));
+    if (c->stack.kind == FM_BANK_F32) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const fm::Bank v = coll_view(c, (int)i);
+            if (v.n == 0) continue;
+            PairSweep ps;
+            if ((rc = sweep_pair(ctx, v, *q, 1, 0, nullptr, nullptr, kSweepNoEvents, &ps)) != FM_OK) return rc;
+            *timed = true;                   // (the route brackets every sweep itself: the last one's events stand)
+            hipLaunchKernelGGL(xcheck_scatter_kernel, dim3((unsigned)((v.n * 4 + 255) / 256)), dim3(256), 0, ctx->stream, ps.partial,
+                               ps.nsplit, ps.ncols_alloc, v.n, d_qbest + (i - i0) * nq, 0u, ps.f32_keys, (int*)nullptr, (unsigned*)nullptr);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        return FM_OK;
+    }
+    const fm::Bank v = coll_chunk_view(c, i0, i1);
+    if (v.n == 0) return FM_OK;
+    const CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
+    int64_t real = 0;
+    for (int64_t i = i0; i < i1; ++i) real += c->rows[(size_t)i];
+    ctx->pending_pairs += nq * real;
+    ctx->pending_bytes += bank_bytes(q) + real * (v.kind == FM_BANK_BIN ? v.dim : 128);
+    if (!*timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+    *timed = true;
+    PairSweep ps;
+    if ((rc = sweep_pair(ctx, v, *q, 1, v.n, cut, nullptr, kSweepNoEvents | kSweepNoCount, &ps)) != FM_OK) return rc;
+    hipLaunchKernelGGL(coll_elect_kernel, dim3((unsigned)((v.n * 4 + 255) / 256)), dim3(256), 0, ctx->stream, ps.partial, ps.nsplit,
+                       ps.ncols_alloc, v.n, (unsigned)c->phys[(size_t)i0], tab, (int)i0, nq, d_qbest, ps.f32_keys, ps.fix);
+    HIP_TRY(ctx, hipGetLastError());
+    if (ps.fix) {
+        hipLaunchKernelGGL(coll_sqrt_fix1_kernel, dim3(kFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)ps.fix,
+                           (const int8_t*)c->stack.rows8, (const int32_t*)c->stack.norm, (const int8_t*)q->rows8,
+                           (const int32_t*)q->norm, (int)nq, tab, (int)i0, nq, d_qbest);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return FM_OK;
+}
+
+// What a per-image election call tests and where its rows go.
+struct CollEachArgs {
+    const char* who;
+    bool accept;                     // the accepted-match test (tau, q's self distances); else the cross-check under max_dist
+    double tau; float max_dist;
+    int64_t cap;                     // rows per image of the compacted outputs (the cross-check's host form has none: 0)
+    // host form.  accept: qidx / tidx / dist / ratio [n_images][cap], compacted; else tidx / dist [n_images][nq], dense (both
+    // null: counts only).  counts [n_images]: the full counts.
+    int32_t* qidx; int32_t* tidx; float* dist; double* ratio; int64_t* counts;
+    // device form: d_rows [n_images][cap][3], d_counts [n_images], h_counts host [n_images] or null
+    bool to_dev; int32_t* d_rows; int64_t* d_counts; int64_t* h_counts; void* consumer;
+};
+
+static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const CollEachArgs& a)
+{
+    const std::string who(a.who);
+    // (the cross-check: a query bank without rows is not held to the collection's kind, as in the radius calls -- every
+    // creator makes an empty bank an integer-route one)
+    int rc = coll_query_check(ctx, c, q, a.who, !a.accept);
     if (rc != FM_OK) return rc;
-    if (q->kind == FM_BANK_BIN)
-        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": binary banks carry no self distances: the self-distance test is not built for a binary collection");
-    const int64_t nq = q->n, ni = (int64_t)c->rows.size();
-    if (nq > 0 && !q->selfdist) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank has no self distances (fm_bank_set_selfdist)");
-    if (cap < 0) return fail(ctx, FM_EINVAL, std::string(who) + ": cap < 0");
+    if (a.accept && q->kind == FM_BANK_BIN)
+        return fail(ctx, FM_EUNSUPPORTED, who + ": binary banks carry no self distances: the self-distance test is not built for a binary collection");
+    const int64_t nq = q->n, ni = (int64_t)c->rows.size(), cap = a.cap;
+    if (a.accept && nq > 0 && !q->selfdist) return fail(ctx, FM_EINVAL, who + ": query bank has no self distances (fm_bank_set_selfdist)");
+    if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap < 0");
     if (ni == 0) return FM_OK;
-    if (to_dev) {
-        if (!d_counts || (cap > 0 && !d_rows)) return fail(ctx, FM_EINVAL, std::string(who) + ": device output pointer is NULL");
+    if (a.to_dev) {
+        if (!a.d_counts || (cap > 0 && !a.d_rows)) return fail(ctx, FM_EINVAL, who + ": device output pointer is NULL");
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if ((rc = check_device_ptr(ctx, d_counts, who, "d_counts", false)) != FM_OK) return rc;
-        if (cap > 0 && (rc = check_device_ptr(ctx, d_rows, who, "d_rows", false)) != FM_OK) return rc;
+        if ((rc = check_device_ptr(ctx, a.d_counts, a.who, "d_counts", false)) != FM_OK) return rc;
+        if (cap > 0 && (rc = check_device_ptr(ctx, a.d_rows, a.who, "d_rows", false)) != FM_OK) return rc;
+    } else if (a.accept) {
+        if (!a.counts) return fail(ctx, FM_EINVAL, who + ": n_accepted is NULL");
+        if (nq > 0 && cap > 0 && (!a.qidx || !a.tidx || !a.dist || !a.ratio)) return fail(ctx, FM_EINVAL, who + ": output pointer is NULL");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
     } else {
-        if (!n_accepted) return fail(ctx, FM_EINVAL, std::string(who) + ": n_accepted is NULL");
-        if (nq > 0 && cap > 0 && (!qidx || !tidx || !dist || !ratio)) return fail(ctx, FM_EINVAL, std::string(who) + ": output pointer is NULL");
+        if (!a.tidx != !a.dist) return fail(ctx, FM_EINVAL, who + ": tidx and dist are given together or not at all");
+        if (!a.tidx && !a.counts) return fail(ctx, FM_EINVAL, who + ": every output pointer is NULL");
         HIP_TRY(ctx, hipSetDevice(ctx->device));
     }
     if (nq == 0) {
-        if (to_dev) {
-            if ((rc = wait_for_stream(ctx, consumer)) != FM_OK) return rc;
-            HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, (size_t)ni * 8, ctx->stream));
-            if ((rc = results_written(ctx, consumer)) != FM_OK) return rc;
+        if (a.to_dev) {
+            if ((rc = wait_for_stream(ctx, a.consumer)) != FM_OK) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(a.d_counts, 0, (size_t)ni * 8, ctx->stream));
+            if ((rc = results_written(ctx, a.consumer)) != FM_OK) return rc;
             ctx->rows_stream = ctx->stream;
         }
-        int64_t* hc = to_dev ? h_counts : n_accepted;
+        int64_t* hc = a.to_dev ? a.h_counts : a.counts;
         if (hc) for (int64_t i = 0; i < ni; ++i) hc[i] = 0;
         return FM_OK;
     }
     // images per chunk from the budget
     const int nblk = (int)((nq + 255) / 256);
-    const size_t per = (size_t)nq * kCollAcceptEntry + (size_t)nblk * 4;
+    const size_t per = (size_t)nq * (a.accept ? kCollAcceptEntry : kCollXcheckEntry) + (size_t)nblk * 4;
     size_t budget = (size_t)ctx->tune.coll_ws_bytes;
     if (budget == 0) {
         budget = (size_t)64 << 20;
@@ -1371,10 +1477,11 @@ static int coll_accept_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, dou
     }
     int64_t nc = (int64_t)(budget / per);
     nc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nc, ni), kCollAcceptMaxChunk));
-    const int64_t ccap = to_dev ? 0 : (cap < nq ? cap : nq);          // rows per image kept in ws_out for the copy out
+    const bool columns = a.accept && !a.to_dev;                       // compacted columns kept in ws_out for the copy out
+    const int64_t ccap = columns ? (cap < nq ? cap : nq) : 0;         // ... and their rows per image
     size_t off = 0;
     const size_t o_full = carve(off, (size_t)ni * 8);
-    const size_t o_qbest = carve(off, (size_t)nc * nq * 8), o_ratio = carve(off, (size_t)nc * nq * 8);
+    const size_t o_qbest = carve(off, (size_t)nc * nq * 8), o_ratio = carve(off, a.accept ? (size_t)nc * nq * 8 : 0);
     const size_t o_tidx = carve(off, (size_t)nc * nq * 4), o_dist = carve(off, (size_t)nc * nq * 4);
     const size_t o_pass = carve(off, (size_t)nc * nq), o_bc = carve(off, (size_t)nc * nblk * 4);
     const size_t o_cq = carve(off, (size_t)ni * ccap * 4), o_ct = carve(off, (size_t)ni * ccap * 4), o_cd = carve(off, (size_t)ni * ccap * 4);
@@ -1383,116 +1490,105 @@ static int coll_accept_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, dou
     char* b = (char*)ctx->ws_out;
     unsigned long long* d_full = (unsigned long long*)(b + o_full);
     unsigned long long* d_qbest = (unsigned long long*)(b + o_qbest);
-    const bool i8 = c->stack.kind == FM_BANK_I8;
-    // the chunks' views; the sweep workspace is sized for the largest before anything is enqueued (no reallocation between chunks)
-    auto chunk_view = [&](int64_t i0, int64_t i1) {
-        const int64_t p0 = c->phys[(size_t)i0], p1 = i1 < ni ? c->phys[(size_t)i1] : c->used;
-        fm::Bank v = bank_rows_view(c->stack, p0, p1 - p0);
-        v.usq_max = 0;
-        for (int64_t i = i0; i < i1; ++i) v.usq_max = std::max(v.usq_max, c->usq[(size_t)i]);
-        return v;
-    };
-    if (i8 && c->total > 0) {
+    const bool stacked = c->stack.kind != FM_BANK_F32;      // one sweep per chunk
+    // the sweep workspace is sized for the largest chunk before anything is enqueued (no reallocation between chunks)
+    if (stacked && c->total > 0) {
         for (int64_t i0 = 0; i0 < ni; i0 += nc) {
-            const fm::Bank v = chunk_view(i0, std::min(ni, i0 + nc));
+            const fm::Bank v = coll_chunk_view(c, i0, std::min(ni, i0 + nc));
             PairSweep ps;
             if (v.n > 0 && (rc = sweep_pair_plan(ctx, v, *q, 1, v.n, &ps)) != FM_OK) return rc;
         }
     }
     CallScope cs(ctx);
-    const CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
     const unsigned* cut = nullptr;
-    if (i8 && c->total > 0 && (rc = enqueue_ratio_cut(ctx, 1, &q, tau, &cut)) != FM_OK) return rc;
+    if (a.accept && c->stack.kind == FM_BANK_I8 && c->total > 0 && (rc = enqueue_ratio_cut(ctx, 1, &q, a.tau, &cut)) != FM_OK) return rc;
+    const CollKeep keep{a.accept ? (const double*)q->selfdist : (const double*)nullptr, a.tau, a.max_dist};
     bool timed = false;
     for (int64_t i0 = 0; i0 < ni; i0 += nc) {
         const int64_t i1 = std::min(ni, i0 + nc), g = i1 - i0;
-        HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)g * nq * 8, ctx->stream));
-        if (i8) {
-            const fm::Bank v = chunk_view(i0, i1);
-            if (v.n > 0) {
-                int64_t real = 0;
-                for (int64_t i = i0; i < i1; ++i) real += c->rows[(size_t)i];
-                ctx->pending_pairs += nq * real;
-                ctx->pending_bytes += bank_bytes(q) + real * 128;
-                if (!timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-                timed = true;
-                PairSweep ps;
-                if ((rc = sweep_pair(ctx, v, *q, 1, v.n, cut, nullptr, kSweepNoEvents | kSweepNoCount, &ps)) != FM_OK) return rc;
-                hipLaunchKernelGGL(coll_elect_kernel, dim3((unsigned)((v.n * 4 + 255) / 256)), dim3(256), 0, ctx->stream, ps.partial, ps.nsplit,
-                                   ps.ncols_alloc, v.n, (unsigned)c->phys[(size_t)i0], tab, (int)i0, nq, d_qbest, ps.fix);
-                HIP_TRY(ctx, hipGetLastError());
-                if (ps.fix) {
-                    hipLaunchKernelGGL(coll_sqrt_fix1_kernel, dim3(kFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)ps.fix,
-                                       (const int8_t*)c->stack.rows8, (const int32_t*)c->stack.norm, (const int8_t*)q->rows8,
-                                       (const int32_t*)q->norm, (int)nq, tab, (int)i0, nq, d_qbest);
-                    HIP_TRY(ctx, hipGetLastError());
-                }
-            }
-        } else {
-            for (int64_t i = i0; i < i1; ++i) {
-                const fm::Bank v = coll_view(c, (int)i);
-                if (v.n == 0) continue;
-                PairSweep ps;
-                if ((rc = sweep_pair(ctx, v, *q, 1, 0, nullptr, nullptr, kSweepNoEvents, &ps)) != FM_OK) return rc;
-                timed = true;                    // (the route brackets every sweep itself: the last one's events stand)
-                hipLaunchKernelGGL(xcheck_scatter_kernel, dim3((unsigned)((v.n * 4 + 255) / 256)), dim3(256), 0, ctx->stream, ps.partial,
-                                   ps.nsplit, ps.ncols_alloc, v.n, d_qbest + (i - i0) * nq, 0u, ps.f32_keys, (int*)nullptr, (unsigned*)nullptr);
-                HIP_TRY(ctx, hipGetLastError());
+        if ((rc = coll_qbest_chunk(ctx, c, q, i0, i1, cut, d_qbest, &timed)) != FM_OK) return rc;
+        hipLaunchKernelGGL(coll_each_finalize_kernel, dim3((unsigned)nblk, (unsigned)g), dim3(256), 0, ctx->stream,
+                           (const unsigned long long*)d_qbest, nq, keep, (int32_t*)(b + o_tidx), (float*)(b + o_dist),
+                           a.accept ? (double*)(b + o_ratio) : (double*)nullptr, (uint8_t*)(b + o_pass), (int*)(b + o_bc));
+        HIP_TRY(ctx, hipGetLastError());
+        if (!a.to_dev && !a.accept && a.tidx) {
+            // the dense result of the chunk, before the next chunk decodes into the same arrays (copies of up to 128 MB
+            // each keep the staging buffer of fm::d2h within bounds)
+            const size_t total = (size_t)g * nq * 4, piece = (size_t)128 << 20;
+            for (size_t o = 0; o < total; o += piece) {
+                const size_t nb = std::min(piece, total - o);
+                HIP_TRY(ctx, d2h(ctx, (char*)(a.tidx + i0 * nq) + o, b + o_tidx + o, nb));
+                HIP_TRY(ctx, d2h(ctx, (char*)(a.dist + i0 * nq) + o, b + o_dist + o, nb));
             }
         }
-        hipLaunchKernelGGL(coll_accept_finalize_kernel, dim3((unsigned)nblk, (unsigned)g), dim3(256), 0, ctx->stream,
-                           (const unsigned long long*)d_qbest, nq, (const double*)q->selfdist, tau, (int32_t*)(b + o_tidx), (float*)(b + o_dist),
-                           (double*)(b + o_ratio), (uint8_t*)(b + o_pass), (int*)(b + o_bc));
-        HIP_TRY(ctx, hipGetLastError());
         // (device form: the first compaction is the first kernel that writes the caller's buffers)
-        if (to_dev && i0 == 0 && (rc = wait_for_stream(ctx, consumer)) != FM_OK) return rc;
-        hipLaunchKernelGGL(coll_accept_compact_kernel, dim3((unsigned)nblk, (unsigned)g), dim3(256), 0, ctx->stream,
+        if (a.to_dev && i0 == 0 && (rc = wait_for_stream(ctx, a.consumer)) != FM_OK) return rc;
+        hipLaunchKernelGGL(coll_each_compact_kernel, dim3((unsigned)nblk, (unsigned)g), dim3(256), 0, ctx->stream,
                            (const int32_t*)(b + o_tidx), (const float*)(b + o_dist), (const double*)(b + o_ratio), (const uint8_t*)(b + o_pass),
-                           (const int*)(b + o_bc), nq, to_dev ? cap : ccap,
+                           (const int*)(b + o_bc), nq, a.to_dev ? cap : ccap,
                            (int32_t*)(b + o_cq) + i0 * ccap, (int32_t*)(b + o_ct) + i0 * ccap, (float*)(b + o_cd) + i0 * ccap,
-                           (double*)(b + o_cr) + i0 * ccap, to_dev && cap > 0 ? d_rows + (size_t)i0 * cap * 3 : (int32_t*)nullptr,
-                           to_dev ? (long long*)d_counts + i0 : (long long*)nullptr, d_full + i0);
+                           (double*)(b + o_cr) + i0 * ccap, a.to_dev && cap > 0 ? a.d_rows + (size_t)i0 * cap * 3 : (int32_t*)nullptr,
+                           a.to_dev ? (long long*)a.d_counts + i0 : (long long*)nullptr, d_full + i0);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (timed) {
-        if (i8) HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));       // (the sweeps, the elections and the tails between them)
+        if (stacked) HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));       // (the sweeps, the elections and the tails between them)
         ctx->kernel_timed = true;
     }
-    if (to_dev) {
-        if ((rc = results_written(ctx, consumer)) != FM_OK) return rc;
+    if (a.to_dev) {
+        if ((rc = results_written(ctx, a.consumer)) != FM_OK) return rc;
         ctx->rows_stream = ctx->stream;
-        if (!h_counts) return FM_OK;              // (enqueued: nothing waits for the device)
+        if (!a.h_counts) return FM_OK;            // (enqueued: nothing waits for the device)
         // the caller asked for host numbers: the call's one synchronisation
-        HIP_TRY(ctx, hipMemcpyAsync(h_counts, d_full, (size_t)ni * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(a.h_counts, d_full, (size_t)ni * 8, hipMemcpyDeviceToHost, ctx->stream));
         return cs.finish();
     }
     // the counts decide how much is copied: one small synchronous read, then min(count, cap) rows of every image
     std::vector<unsigned long long> cnt((size_t)ni);
     HIP_TRY(ctx, hipMemcpyAsync(cnt.data(), d_full, (size_t)ni * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t i = 0; i < ni; ++i) {
+    for (int64_t i = 0; columns && i < ni; ++i) {
         const size_t m = (size_t)std::min<int64_t>((int64_t)cnt[(size_t)i], ccap);
         if (m == 0) continue;
-        HIP_TRY(ctx, d2h(ctx, qidx + i * cap, (int32_t*)(b + o_cq) + i * ccap, m * 4));
-        HIP_TRY(ctx, d2h(ctx, tidx + i * cap, (int32_t*)(b + o_ct) + i * ccap, m * 4));
-        HIP_TRY(ctx, d2h(ctx, dist + i * cap, (float*)(b + o_cd) + i * ccap, m * 4));
-        HIP_TRY(ctx, d2h(ctx, ratio + i * cap, (double*)(b + o_cr) + i * ccap, m * 8));
+        HIP_TRY(ctx, d2h(ctx, a.qidx + i * cap, (int32_t*)(b + o_cq) + i * ccap, m * 4));
+        HIP_TRY(ctx, d2h(ctx, a.tidx + i * cap, (int32_t*)(b + o_ct) + i * ccap, m * 4));
+        HIP_TRY(ctx, d2h(ctx, a.dist + i * cap, (float*)(b + o_cd) + i * ccap, m * 4));
+        HIP_TRY(ctx, d2h(ctx, a.ratio + i * cap, (double*)(b + o_cr) + i * ccap, m * 8));
     }
     if ((rc = cs.finish()) != FM_OK) return rc;
-    for (int64_t i = 0; i < ni; ++i) n_accepted[i] = (int64_t)cnt[(size_t)i];
+    if (a.counts) for (int64_t i = 0; i < ni; ++i) a.counts[i] = (int64_t)cnt[(size_t)i];
     return FM_OK;
 }
 
 extern "C" int fm_collection_match_accepted_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* qidx,
                                                  int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
 {
-    return coll_accept_each(ctx, c, q, tau, cap, qidx, tidx, dist, ratio, n_accepted, nullptr, nullptr, nullptr, FM_NO_STREAM, false,
-                            "fm_collection_match_accepted_each");
+    const CollEachArgs a{"fm_collection_match_accepted_each", true, tau, 0.f, cap, qidx, tidx, dist, ratio, n_accepted,
+                         false, nullptr, nullptr, nullptr, FM_NO_STREAM};
+    return coll_elect_each(ctx, c, q, a);
 }
 
 extern "C" int fm_collection_match_accepted_each_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* d_rows,
                                                      int64_t* d_counts, int64_t* h_counts, void* consumer_stream)
 {
-    return coll_accept_each(ctx, c, q, tau, cap, nullptr, nullptr, nullptr, nullptr, nullptr, d_rows, d_counts, h_counts, consumer_stream, true,
-                            "fm_collection_match_accepted_each_dev");
+    const CollEachArgs a{"fm_collection_match_accepted_each_dev", true, tau, 0.f, cap, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         true, d_rows, d_counts, h_counts, consumer_stream};
+    return coll_elect_each(ctx, c, q, a);
+}
+
+// cv2.BFMatcher(norm, crossCheck=True).match(q, T_i) image by image: the same table, kept while dist < max_dist.
+extern "C" int fm_collection_xcheck1_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, float max_dist, int32_t* tidx, float* dist,
+                                          int64_t* n_matched)
+{
+    const CollEachArgs a{"fm_collection_xcheck1_each", false, 0.0, max_dist, 0, nullptr, tidx, dist, nullptr, n_matched,
+                         false, nullptr, nullptr, nullptr, FM_NO_STREAM};
+    return coll_elect_each(ctx, c, q, a);
+}
+
+extern "C" int fm_collection_xcheck1_each_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, float max_dist, int64_t cap, int32_t* d_rows,
+                                              int64_t* d_counts, int64_t* h_counts, void* consumer_stream)
+{
+    const CollEachArgs a{"fm_collection_xcheck1_each_dev", false, 0.0, max_dist, cap, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         true, d_rows, d_counts, h_counts, consumer_stream};
+    return coll_elect_each(ctx, c, q, a);
 }

@@ -139,8 +139,8 @@ struct Tuning {
                                       // 1 an XCD owns output chunks, 2 an XCD owns a contiguous share of the split-major order
     int radius_ws_bytes = 1 << 30;    // K10: device bytes for the candidate keys of one query chunk (radius.hip); a single
                                       // query row whose list needs more still runs, in a chunk of its own
-    int coll_ws_bytes = 0;            // fm_collection_match_accepted_each: device bytes for the per-(image, query row) arrays of one
-                                      // chunk of images (25 per entry); 0 = a quarter of the free device memory
+    int coll_ws_bytes = 0;            // fm_collection_match_accepted_each / _xcheck1_each: device bytes for the per-(image, query row)
+                                      // arrays of one chunk of images (25 / 17 per entry); 0 = a quarter of the free device memory
 };
 
 // ---- K1: row-reduce kernel launcher ---------------------------------------------------

@@ -236,9 +236,11 @@ class BFMatcher(object):
     image wins a tie).  NORM_L2 collections hold uint8 or float32 images (float32 images whose values are all integers in
     0 .. 255 take the exact integer route until the first other image arrives; a float32 QUERY that is not integer valued
     against such a collection is refused by the library: upload the query's kind of images), NORM_HAMMING collections binary
-    rows.  ``ValueError`` before anything is uploaded: a normType other than 4 / 6, crossCheck on a collection of more than one image
+    rows.  ``ValueError`` before anything is uploaded: a normType other than 4 / 6, ``match`` / ``knnMatch`` with crossCheck on a collection of more than one image
     (OpenCV asserts there too, as far as SURVEY.md Appendix A recalls), ``radiusMatch`` on a collection.
-    ``knnMatch_arrays`` / ``knnMatchEach_arrays`` / ``votes`` return NumPy arrays.  ``fastMatchEach`` / ``fastMatchEach_arrays``
+    ``matchEach`` is ``match`` against every image separately -- with crossCheck the mutual nearest neighbours image by image,
+    the collection form crossCheck does have.
+    ``knnMatch_arrays`` / ``knnMatchEach_arrays`` / ``matchEach_arrays`` / ``votes`` return NumPy arrays.  ``fastMatchEach`` / ``fastMatchEach_arrays``
     run Fast-Match's self-distance test against every image of the collection (NORM_L2 only)."""
 
     def __init__(self, normType=NORM_L2, crossCheck=False, options={}):
@@ -318,7 +320,8 @@ class BFMatcher(object):
             raise ValueError("BFMatcher.knnMatch: k = %d: the HIP path builds k-NN lists for 1 <= k <= 8" % k)
         self._check_collection("BFMatcher.knnMatch")
         if self.crossCheck and len(self._images) > 1:
-            raise ValueError("BFMatcher: crossCheck has no collection form (more than one train image)")
+            raise ValueError("BFMatcher: crossCheck has no stacked collection form (more than one train image); matchEach runs it "
+                             "image by image")
         if self.normType == NORM_HAMMING and np.asarray(queryDescriptors).dtype != np.uint8 and not isinstance(queryDescriptors, _ffi.Bank):
             raise ValueError("NORM_HAMMING needs uint8 descriptors (cv2 asserts CV_8U), got %s" % np.asarray(queryDescriptors).dtype)
         if self.crossCheck and k == 1:
@@ -383,6 +386,35 @@ class BFMatcher(object):
         for i, (qidx, tidx, dist, _) in enumerate(self.fastMatchEach_arrays(queryDescriptors, tau)):
             out.append([DMatch(int(qidx[j]), int(tidx[j]), dist[j], i) for j in range(qidx.shape[0])])
         return out
+
+    def matchEach_arrays(self, queryDescriptors):
+        """(tidx int32, dist float32) [n_images, nq]: ``match`` of the query against every image of the collection separately
+        (-1 / inf: no match in that image).  With ``crossCheck`` the mutual nearest neighbours inside every image
+        (``Collection.xcheck1_each``), without it the nearest row of every image (first column of ``Collection.knn2_each``)."""
+        self._check_collection("BFMatcher.matchEach")
+        if self.normType == NORM_HAMMING and not isinstance(queryDescriptors, _ffi.Bank) and np.asarray(queryDescriptors).dtype != np.uint8:
+            raise ValueError("NORM_HAMMING needs uint8 descriptors (cv2 asserts CV_8U), got %s" % np.asarray(queryDescriptors).dtype)
+        if not isinstance(queryDescriptors, _ffi.Bank) and np.asarray(queryDescriptors).ndim != 2:
+            raise ValueError("descriptors must be a 2-D [n, dim] array")
+        coll = self.train()
+        qb, tmp = self._query(coll.ctx, queryDescriptors)
+        try:
+            if self.crossCheck:
+                return coll.xcheck1_each(qb)
+            idx, dist = coll.knn2_each(qb)
+            return np.ascontiguousarray(idx[:, :, 0]), np.ascontiguousarray(dist[:, :, 0])
+        finally:
+            if tmp:
+                qb.close()
+
+    def matchEach(self, queryDescriptors):
+        """``[BFMatcher(normType, crossCheck).match(query, t) for t in images]`` as one call against the collection: one list
+        of ``DMatch`` per added image, ``imgIdx`` set, ascending query index.  NORM_L2 and NORM_HAMMING; with ``crossCheck``
+        one reverse sweep serves all images (``fm_collection_xcheck1_each``).  ``ValueError`` for an empty collection and
+        for a query of the wrong dtype, before anything is uploaded."""
+        tidx, dist = self.matchEach_arrays(queryDescriptors)
+        return [[DMatch(int(qi), int(tidx[i, qi]), dist[i, qi], i) for qi in np.nonzero(tidx[i] >= 0)[0]]
+                for i in range(tidx.shape[0])]
 
     # -- cv2's matching methods ------------------------------------------------------------
     def knnMatch(self, queryDescriptors, trainDescriptors=None, k=None):

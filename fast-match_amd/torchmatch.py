@@ -24,6 +24,9 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
   ``radius_match(q, r)`` -> ``(offsets, img, idx, dist)``, ``r`` as in the module's ``radius_match``;
   ``fast_match_each(q, tau, cap=None)`` -> ``(rows int32 [n_images, cap, 3], counts int64 [n_images])``, the accepted-match
   test inside every image (``q``: a ``Bank`` carrying self distances, ``Context.self_dist_batch([q], want_host=False)``);
+  ``mutual_nn_each(q, max_dist=None, cap=None)`` -> the same two tensors for the cross-checked 1-NN inside every image
+  (``cv2.BFMatcher(norm, crossCheck=True).match(q, image)`` image by image, kept while ``dist < max_dist``), on uint8,
+  float and binary collections alike;
   ``clear()``, ``close()``, ``info()``.  The collection equals the ``_ffi.Collection`` the same values build on the host.
 
 ``q`` and ``t`` are ``Bank``s or CUDA tensors (a tensor becomes a bank for the call).  The values are those of
@@ -343,6 +346,30 @@ class Collection(object):
         coll.match_accepted_each_dev(q, float(tau), rows.data_ptr() if rows.numel() else 0, counts.data_ptr() if ni else 0, cap,
                                      consumer_stream=stream)
         return rows, counts
+
+    def mutual_nn_each(self, q, max_dist=None, cap=None):
+        """Mutual nearest neighbours of ``q`` inside every image separately, left on the device: ``(rows int32 [n_images, cap,
+        3] = (query, row inside the image, float32 distance bits), counts int64 [n_images] = min(matched, cap))``, rows
+        ascending in query index; ``cap`` defaults to the query's rows.  A match is kept while ``dist < max_dist`` (strict
+        float32 compare; None: every match).  ``q`` is a ``Bank`` or a CUDA tensor as ``add`` takes them (packed bits for a
+        binary collection).  Enqueued, no host wait."""
+        import torch
+        if cap is not None and int(cap) < 0:
+            raise ValueError("cap must not be negative")
+        max_dist = float("inf") if max_dist is None else float(np.float32(max_dist))
+        qb, made = self._query(q)
+        try:
+            ni = self._coll.info()[0]
+            cap = qb.n if cap is None else int(cap)
+            stream, dev = _stream_and_device(qb.ctx)
+            rows = torch.empty((ni, cap, 3), dtype=torch.int32, device=dev)
+            counts = torch.zeros(ni, dtype=torch.int64, device=dev)
+            self._coll.xcheck1_each_dev(qb, max_dist, rows.data_ptr() if rows.numel() else 0, counts.data_ptr() if ni else 0, cap,
+                                        consumer_stream=stream)
+            return rows, counts
+        finally:
+            for b in made:
+                b.close()
 
     def clear(self):
         if self._coll is not None:

@@ -50,7 +50,8 @@ typedef struct fm_bank fm_bank;
  * fm_bank_create_dev, fm_knn_dev, fm_xcheck1_dev, fm_knn2_ratio_dev; still revision 12, additions only --
  * fm_collection_match_accepted_each, fm_collection_match_accepted_each_dev, the option "coll_ws_bytes"; still revision 12,
  * additions only -- fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev; still revision 12, additions
- * only -- fm_collection_radius_match, fm_radius_match_dev, fm_collection_radius_match_dev).  A binding compares
+ * only -- fm_collection_radius_match, fm_radius_match_dev, fm_collection_radius_match_dev; still revision 12, additions
+ * only -- fm_collection_xcheck1_each, fm_collection_xcheck1_each_dev).  A binding compares
  * fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.                      */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -116,9 +117,10 @@ int  fm_ctx_destroy(fm_ctx* ctx);
  *   "radius_ws_bytes" 65536..2^31-1  fm_radius_match: device bytes for the candidates of one chunk of query rows (2^30;
  *                         24 bytes per candidate, 28 in the collection forms); a row whose own list needs more runs in a
  *                         chunk of its own
- *   "coll_ws_bytes" 0..2^31-1  fm_collection_match_accepted_each: device bytes for the per-(image, query row) arrays of one
- *                         chunk of consecutive images (25 bytes per entry; at least one image per chunk); 0 = one chunk up
- *                         to 64 MiB, beyond that a quarter of the free device memory (0)
+ *   "coll_ws_bytes" 0..2^31-1  fm_collection_match_accepted_each, fm_collection_xcheck1_each: device bytes for the
+ *                         per-(image, query row) arrays of one chunk of consecutive images (25 bytes per entry in the
+ *                         accepted-match test, 17 in the cross-check, which keeps no ratio; at least one image per
+ *                         chunk); 0 = one chunk up to 64 MiB, beyond that a quarter of the free device memory (0)
  * Unknown names and out-of-range values return FM_EINVAL.                                          */
 int  fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value);
 int  fm_ctx_get_option(fm_ctx* ctx, const char* name, int64_t* value);
@@ -304,6 +306,32 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  *     may be NULL).  Enqueued on the context's stream; consumer_stream is ordered against the fills in both directions, as in
  *     fm_match_accepted_dev_batch.  h_counts (host, any memory, or NULL) receives the full counts; asking for them is the
  *     call's one host synchronisation.
+ *   fm_collection_xcheck1_each: cv2.BFMatcher(norm, crossCheck=True).match(q, image i) for every image in ONE call -- mutual
+ *     nearest neighbours image by image, the matcher of binary (ORB keyframe) and float32 databases, which have no
+ *     self-distance test.  Slot i of tidx / dist [n_images][nq] equals, row by row and bit for bit, fm_xcheck1(q, bank(image
+ *     i)) on all three collection kinds: every train row of image i elects its nearest query row (lowest query index on
+ *     ties), every query row keeps the closest electing row of image i (lowest row on ties), -1 / +inf where none elects it;
+ *     the float32-root repair above d^2 = 4 197 200 is included, per image.  An empty image keeps its slot, all -1 / +inf;
+ *     images are independent: a descriptor present in two images matches in both.  max_dist: a match is kept iff dist <
+ *     max_dist, a strict float32 compare on the reported value -- +inf keeps every match (plain cv2), max_dist <= 0 or NaN
+ *     keeps none; a dropped entry reads -1 / +inf.  n_matched[i] (may be NULL) = the query rows kept in image i; with tidx ==
+ *     dist == NULL only those n_images words come back: mutual-match votes per image (tidx and dist are given together or
+ *     not at all; all three NULL is FM_EINVAL).  Integer route: the front half of fm_collection_match_accepted_each without
+ *     the ratio cut -- one reverse top-1 sweep per chunk, the segmented election, the tie list redone exactly.  Binary
+ *     collections: ONE reverse K11 sweep per chunk with the stack as the output operand; a padding row (an all-zero FP4 row,
+ *     at W / 2 from every query row) leaves a valid key that the election drops by index.  Float32 route: the per-image
+ *     sweeps (K8 / K5) enqueued back to back, each with fm_xcheck1's own election into slot i -- no faster than the loop
+ *     over fm_xcheck1 but for its per-call costs.  Chunks of consecutive images under the option "coll_ws_bytes" as in
+ *     fm_collection_match_accepted_each (17 bytes per (image, query row)).  Errors, in fm_collection_knn's order: NULL
+ *     handles; a query of another kind or width (FM_EINVAL; as in fm_collection_radius_match a query bank with no rows is
+ *     not held to the kind); a float32-route query with a finite magnitude above FM_COLLECTION_F32_MAX (FM_EUNSUPPORTED);
+ *     then the output pointers.  nq = 0 writes zero counts and nothing else; n_images = 0 is valid.
+ *   fm_collection_xcheck1_each_dev: the kept matches left on the device, word for word as
+ *     fm_collection_match_accepted_each_dev leaves its rows: 12-byte rows {query, train row inside the image, float32
+ *     distance bits}, ascending in query index, of image i at d_rows + i * cap * 3; d_counts[i] = min(count, cap) (cap = 0:
+ *     d_rows may be NULL; cap < 0: FM_EINVAL); consumer_stream ordered in both directions; h_counts (host, or NULL) receives
+ *     the full counts and is the call's one host synchronisation -- on the integer and binary routes the call makes no
+ *     other (but for the table upload of the first match after an add).
  *   fm_collection_radius_match: fm_radius_match(q, T, ...) for T = the images' rows stacked in image order -- every database
  *     descriptor within r_i of query row i in ONE matrix-core sweep over the whole allocation (place recognition,
  *     de-duplication, Fast-Match's one-to-many test d(q, t) < tau * selfdist(q)).  Every hit is (img, row inside that image);
@@ -324,8 +352,11 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  *   fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev, fm_collection_radius_match_dev: images from,
  *     and stacked results into, DEVICE memory -- described with the other device entry points below ("descriptors already on
  *     the GPU").
- * Not built: crossCheck on a collection (OpenCV's batchDistance asserts update == 0 under crossCheck -- recalled, SURVEY.md
- * Appendix A; neither cv2 nor its source was at hand), Hamming radiusMatch (for pairs or collections), radius queries per
+ * Not built: the STACKED crossCheck on a collection (it has no meaning: OpenCV's batchDistance asserts update == 0 under
+ * crossCheck -- recalled; neither cv2 nor its source was at hand; the per-image form is built:
+ * fm_collection_xcheck1_each), mutual nearest neighbours combined with the per-image ratio test, a single reverse K8 sweep
+ * over a float32-route stack (its padding output rows would flood the filter's candidate lists: fm_collection_xcheck1_each
+ * and fm_collection_match_accepted_each sweep image by image there), Hamming radiusMatch (for pairs or collections), radius queries per
  * image separately (an _each form), skipping the second count sweep of the counts-then-fill pattern, masks,
  * the expansion loop on a collection, a batched K8 / K11 (float32 / binary) per-image sweep,
  * binary collections in the self-distance test, sharding a collection across GPUs (radius queries included), removing single
@@ -361,6 +392,12 @@ int  fm_collection_match_accepted_each(fm_ctx* ctx, fm_collection* coll, const f
 int  fm_collection_match_accepted_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
                                            int32_t* d_rows /*device [n_images][cap][3]*/, int64_t* d_counts /*device [n_images]*/,
                                            int64_t* h_counts /*host [n_images] or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_xcheck1_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, float max_dist,
+                                int32_t* tidx /*[n_images][nq] or NULL*/, float* dist /*[n_images][nq] or NULL*/,
+                                int64_t* n_matched /*[n_images] or NULL*/);
+int  fm_collection_xcheck1_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, float max_dist, int64_t cap,
+                                    int32_t* d_rows /*device [n_images][cap][3]*/, int64_t* d_counts /*device [n_images]*/,
+                                    int64_t* h_counts /*host [n_images] or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* ---- descriptors already on the GPU: device sources, device results ---------------------------------------------------------
  * Every creator above takes a HOST array and every dense matcher call ends in host arrays: the shape of the reference, whose
