@@ -112,6 +112,8 @@ SYMBOLS = {
     "fm_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
     "fm_xcheck1_keys": (_INT, [_P, _P, _P, _I64, _P]),
     "fm_xcheck1_keys_dev": (_INT, [_P, _P, _P, _I64, _P]),
+    "fm_mutual_ratio": (_INT, [_P, _P, _P, ctypes.c_double, ctypes.c_int32, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_mutual_ratio_dev": (_INT, [_P, _P, _P, ctypes.c_double, ctypes.c_int32, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
     "fm_knn2_ratio": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
     "fm_self_dist": (_INT, [_P, _P, _P]),
     "fm_self_dist_plan": (_INT, [_I64, _I32, _P, _I64, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
@@ -161,6 +163,8 @@ SYMBOLS = {
     "fm_collection_match_accepted_each_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P]),
     "fm_collection_xcheck1_each": (_INT, [_P, _P, _P, ctypes.c_float, _P, _P, _P]),
     "fm_collection_xcheck1_each_dev": (_INT, [_P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P]),
+    "fm_collection_mutual_ratio_each": (_INT, [_P, _P, _P, ctypes.c_double, ctypes.c_int32, _I64, _P, _P, _P, _P, _P]),
+    "fm_collection_mutual_ratio_each_dev": (_INT, [_P, _P, _P, ctypes.c_double, ctypes.c_int32, _I64, _P, _P, _P, _P]),
     "fm_collection_add_dev": (_INT, [_P, _P, _P, _INT, _I64, _INT, _I64, _P, ctypes.POINTER(_I32)]),
     "fm_collection_knn_dev": (_INT, [_P, _P, _P, _I32, _P, _P, _P, _P]),
     "fm_collection_knn2_ratio_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
@@ -611,6 +615,49 @@ class Collection(object):
             raise ValueError("h_counts must be a contiguous int64 array of n_images words")
         self.ctx._check(self.ctx.lib.fm_collection_xcheck1_each_dev(
             self.ctx.handle, self.handle, q.handle, float(max_dist), int(cap), _P(int(rows_ptr)) if rows_ptr else None,
+            _P(int(counts_ptr)) if counts_ptr else None, _ptr(h_counts) if h_counts is not None else None,
+            _stream_arg(consumer_stream)))
+
+    def mutual_ratio_each(self, q, tau, symmetric=False, cap=None):
+        """``fm_collection_mutual_ratio_each``: mutual nearest neighbours + ratio test of ``q`` inside every image separately
+        -- a list of (qidx, tidx, dist, ratio) per image, slot i equal to ``Context.mutual_ratio(q, bank(image_i), tau,
+        symmetric)``; ``tidx`` is the row inside the image.  ``cap`` (default ``q.n``) bounds the rows returned per image."""
+        ni = self.info()[0]
+        cap = q.n if cap is None else int(cap)
+        kept = max(cap, 0)
+        qidx, tidx = np.empty((ni, kept), np.int32), np.empty((ni, kept), np.int32)
+        dist, ratio = np.empty((ni, kept), np.float32), np.empty((ni, kept), np.float64)
+        n = np.zeros(ni, np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_mutual_ratio_each(
+            self.ctx.handle, self.handle, q.handle, float(tau), int(bool(symmetric)), cap, _ptr(qidx) if qidx.size else None,
+            _ptr(tidx) if tidx.size else None, _ptr(dist) if dist.size else None, _ptr(ratio) if ratio.size else None,
+            _ptr(n) if ni else None))
+        out = []
+        for i in range(ni):
+            m = min(int(n[i]), kept)
+            out.append((qidx[i, :m], tidx[i, :m], dist[i, :m], ratio[i, :m]))
+        return out
+
+    def mutual_ratio_votes(self, q, tau, symmetric=False):
+        """int64[n_images]: the number of matches ``mutual_ratio_each`` accepts per image (its counts-only call, cap = 0: only
+        n_images words come back)."""
+        n = np.zeros(self.info()[0], np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_mutual_ratio_each(self.ctx.handle, self.handle, q.handle, float(tau),
+                                                                     int(bool(symmetric)), 0, None, None, None, None,
+                                                                     _ptr(n) if n.shape[0] else None))
+        return n
+
+    def mutual_ratio_each_dev(self, q, tau, symmetric, rows_ptr, counts_ptr, cap, h_counts=None, consumer_stream=None):
+        """``mutual_ratio_each`` with device outputs (``fm_collection_mutual_ratio_each_dev``); rows, counts, ``h_counts`` and
+        ``consumer_stream`` are those of ``xcheck1_each_dev``: ``rows_ptr`` = device address of an int32 [n_images, cap, 3]
+        block (query, row inside the image, float32 distance bits), ``counts_ptr`` of an int64 [n_images] array that receives
+        min(count, cap); ``h_counts`` = an int64 [n_images] host array for the full counts, or None."""
+        ni = self.info()[0]
+        if h_counts is not None and (not isinstance(h_counts, np.ndarray) or h_counts.dtype != np.int64 or h_counts.size < ni
+                                     or not h_counts.flags.c_contiguous):
+            raise ValueError("h_counts must be a contiguous int64 array of n_images words")
+        self.ctx._check(self.ctx.lib.fm_collection_mutual_ratio_each_dev(
+            self.ctx.handle, self.handle, q.handle, float(tau), int(bool(symmetric)), int(cap), _P(int(rows_ptr)) if rows_ptr else None,
             _P(int(counts_ptr)) if counts_ptr else None, _ptr(h_counts) if h_counts is not None else None,
             _stream_arg(consumer_stream)))
 
@@ -1172,6 +1219,39 @@ class Context(object):
                                            _ptr(dist), _ptr(ratio), ctypes.byref(n)))
         m = min(n.value, cap)
         return qidx[:m], tidx[:m], dist[:m], ratio[:m]
+
+    def mutual_ratio(self, q, t, tau, symmetric=False, cap=None):
+        """Mutual nearest neighbours + ratio test (``fm_mutual_ratio``): query row i is kept iff d0 / d1 < tau on its 2-NN list
+        and i is the nearest query row of its first neighbour; ``symmetric``: the reverse 2-NN list passes the ratio test
+        too.  (qidx i32[m], tidx i32[m], dist f32[m] (= d0), ratio f64[m]) ascending in query index; ``ratio`` is the larger of
+        the two ratios in symmetric mode.  ``cap`` (default ``q.n``) bounds the rows returned."""
+        cap = q.n if cap is None else int(cap)
+        kept = max(cap, 0)
+        qidx, tidx, dist, ratio = np.empty(kept, np.int32), np.empty(kept, np.int32), np.empty(kept, np.float32), np.empty(kept, np.float64)
+        n = _I64(0)
+        self._check(self.lib.fm_mutual_ratio(self.handle, q.handle, t.handle, float(tau), int(bool(symmetric)), cap,
+                                             _ptr(qidx) if kept else None, _ptr(tidx) if kept else None, _ptr(dist) if kept else None,
+                                             _ptr(ratio) if kept else None, ctypes.byref(n)))
+        m = min(n.value, kept)
+        return qidx[:m], tidx[:m], dist[:m], ratio[:m]
+
+    def mutual_ratio_count(self, q, t, tau, symmetric=False):
+        """The number of matches ``mutual_ratio`` accepts (its counts-only call, cap = 0)."""
+        n = _I64(0)
+        self._check(self.lib.fm_mutual_ratio(self.handle, q.handle, t.handle, float(tau), int(bool(symmetric)), 0, None, None, None,
+                                             None, ctypes.byref(n)))
+        return int(n.value)
+
+    def mutual_ratio_dev(self, q, t, tau, symmetric, rows_ptr, count_ptr, cap, want_count=False, consumer_stream=None):
+        """``mutual_ratio`` with the accepted matches left on the device (``fm_mutual_ratio_dev``): rows and count as
+        ``knn2_ratio_dev`` leaves them -- ``rows_ptr`` = device address of an int32 [cap, 3] buffer (query, train, float32
+        distance bits), ``count_ptr`` of an int64 word that receives min(accepted, cap).  The call waits once for the
+        candidate count; ``want_count``: also return the full number accepted (else None)."""
+        n = _I64(0)
+        self._check(self.lib.fm_mutual_ratio_dev(self.handle, q.handle, t.handle, float(tau), int(bool(symmetric)), int(cap),
+                                                 _P(int(rows_ptr)) if rows_ptr else None, _P(int(count_ptr)) if count_ptr else None,
+                                                 ctypes.byref(n) if want_count else None, _stream_arg(consumer_stream)))
+        return int(n.value) if want_count else None
 
     def ratio_filter(self, dist, selfdist, tau, qrows=None):
         dist = np.ascontiguousarray(dist, dtype=np.float32)

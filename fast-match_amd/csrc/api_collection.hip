@@ -1592,3 +1592,180 @@ extern "C" int fm_collection_xcheck1_each_dev(fm_ctx* ctx, fm_collection* c, con
                          true, d_rows, d_counts, h_counts, consumer_stream};
     return coll_elect_each(ctx, c, q, a);
 }
+
+// ---------------------------------------------------------------------------------------
+// mutual nearest neighbours + ratio test per image: fm_collection_mutual_ratio_each
+// ---------------------------------------------------------------------------------------
+// Slot i = fm_mutual_ratio(q, bank(T_i)).  The forward lists are fm_collection_knn2_each's (coll_each_device) and Lowe's
+// test runs per (image, query row).  Which query rows a train row is nearest to does not depend on the image it sits in,
+// so the candidates of ALL images -- (image, query row) entries that passed, in entry order, each naming its first
+// neighbour by its physical row of the stack -- go through ONE restricted reverse sweep (mutual_reverse_device: the rows
+// gathered from the stack's planes, chunks of consecutive candidates under "coll_ws_bytes"), one join, and the per-image
+// ordered compaction of the other _each calls (coll_each_compact_kernel).
+// Host form: the accepted rows of ALL images packed back to back in entry order (image, query row) -- the flat rank of the
+// final flags -- so that four copies bring every image's rows down, whatever the number of images.
+__global__ __launch_bounds__(256)
+void coll_mutual_pack_kernel(const int32_t* __restrict__ tidx, const float* __restrict__ dist, const double* __restrict__ ratio,
+                             const uint8_t* __restrict__ pass, const int* __restrict__ block_counts, int64_t nq, int nblk,
+                             int32_t* __restrict__ o_q, int32_t* __restrict__ o_t, float* __restrict__ o_d, double* __restrict__ o_r)
+{
+    const int64_t q = (int64_t)(blockIdx.x % (unsigned)nblk) * 256 + threadIdx.x;
+    const int64_t e = (int64_t)(blockIdx.x / (unsigned)nblk) * nq + q;
+    const bool p = q < nq && pass[e];
+    int64_t total;
+    const int64_t dst = compact_rank(block_counts, (int)blockIdx.x, p, &total);
+    if (p) { o_q[dst] = (int32_t)q; o_t[dst] = tidx[e]; o_d[dst] = dist[e]; o_r[dst] = ratio[e]; }
+}
+
+struct CollMutualArgs {
+    const char* who;
+    double tau; int symmetric; int64_t cap;
+    int32_t* qidx; int32_t* tidx; float* dist; double* ratio; int64_t* counts;          // host form: [n_images][cap], [n_images]
+    bool to_dev; int32_t* d_rows; int64_t* d_counts; int64_t* h_counts; void* consumer;  // device form
+};
+
+static int coll_mutual_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const CollMutualArgs& a)
+{
+    const std::string who(a.who);
+    int rc = coll_query_check(ctx, c, q, a.who, true);
+    if (rc != FM_OK) return rc;
+    const int64_t nq = q->n, ni = (int64_t)c->rows.size(), cap = a.cap;
+    if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap < 0");
+    if (ni == 0) return FM_OK;
+    if (a.to_dev) {
+        if (!a.d_counts || (cap > 0 && !a.d_rows)) return fail(ctx, FM_EINVAL, who + ": device output pointer is NULL");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if ((rc = check_device_ptr(ctx, a.d_counts, a.who, "d_counts", false)) != FM_OK) return rc;
+        if (cap > 0 && (rc = check_device_ptr(ctx, a.d_rows, a.who, "d_rows", false)) != FM_OK) return rc;
+    } else {
+        if (!a.counts) return fail(ctx, FM_EINVAL, who + ": n_accepted is NULL");
+        if (nq > 0 && cap > 0 && (!a.qidx || !a.tidx || !a.dist || !a.ratio)) return fail(ctx, FM_EINVAL, who + ": output pointer is NULL");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+    }
+    if (nq == 0) {
+        if (a.to_dev) {
+            if ((rc = wait_for_stream(ctx, a.consumer)) != FM_OK) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(a.d_counts, 0, (size_t)ni * 8, ctx->stream));
+            if ((rc = results_written(ctx, a.consumer)) != FM_OK) return rc;
+            ctx->rows_stream = ctx->stream;
+        }
+        int64_t* hc = a.to_dev ? a.h_counts : a.counts;
+        if (hc) for (int64_t i = 0; i < ni; ++i) hc[i] = 0;
+        return FM_OK;
+    }
+    const int nblk = (int)((nq + 255) / 256);
+    const int64_t ne = ni * nq, nb = ni * nblk;
+    if (nb > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, who + ": n_images * ceil(nq / 256) exceeds 2^31 - 1");
+    const int64_t pk = (a.to_dev || cap == 0) ? 0 : ne;            // host form: room for the packed rows of all images
+    size_t off = 0;
+    const size_t o_i2 = carve(off, (size_t)ne * 8), o_d2 = carve(off, (size_t)ne * 8), o_tidx = carve(off, (size_t)ne * 4), o_dist = carve(off, (size_t)ne * 4);
+    const size_t o_ratio = carve(off, (size_t)ne * 8), o_pass = carve(off, (size_t)ne), o_pass2 = carve(off, (size_t)ne);
+    const size_t o_bc = carve(off, (size_t)nb * 4), o_bc2 = carve(off, (size_t)nb * 4), o_cnt = carve(off, 16), o_full = carve(off, (size_t)ni * 8);
+    const size_t o_cand = carve(off, (size_t)ne * 4);
+    const size_t o_cq = carve(off, (size_t)pk * 4), o_ct = carve(off, (size_t)pk * 4), o_cd = carve(off, (size_t)pk * 4);
+    const size_t o_cr = carve(off, (size_t)pk * 8);
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
+    char* b = (char*)ctx->ws_out;
+    int32_t* d_tidx = (int32_t*)(b + o_tidx); float* d_dist = (float*)(b + o_dist); double* d_ratio = (double*)(b + o_ratio);
+    const uint8_t* d_pass = (const uint8_t*)(b + o_pass);
+    const int* d_bc = (const int*)(b + o_bc);
+    unsigned long long* d_cnt = (unsigned long long*)(b + o_cnt);
+    unsigned long long* d_full = (unsigned long long*)(b + o_full);
+    CallScope cs(ctx);
+    if ((rc = coll_each_device(ctx, c, q, (int32_t*)(b + o_i2), (float*)(b + o_d2))) != FM_OK) return rc;
+    hipLaunchKernelGGL(lowe_each_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, (const int32_t*)(b + o_i2), (const float*)(b + o_d2), nq, nblk,
+                       a.tau, d_tidx, d_dist, d_ratio, (uint8_t*)(b + o_pass), (int*)(b + o_bc));
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(mutual_cand_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, (const int32_t*)d_tidx, d_pass, d_bc, nq, nblk,
+                       c->total > 0 ? c->img_phys() : (const int32_t*)nullptr, (int32_t*)(b + o_cand), d_cnt);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long n_cand = 0;      // the call's host wait between the two sweeps
+    HIP_TRY(ctx, hipMemcpyAsync(&n_cand, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_cand > 0) {
+        fm::Bank t = c->stack;
+        t.usq_max = 0;
+        for (int64_t i = 0; i < ni; ++i) t.usq_max = std::max(t.usq_max, c->usq[(size_t)i]);
+        size_t budget = (size_t)ctx->tune.coll_ws_bytes;
+        if (budget == 0) budget = kMutualGatherBytes;
+        int32_t* r_idx; float* r_dist;
+        if ((rc = mutual_reverse_device(ctx, t, (const int32_t*)(b + o_cand), (int64_t)n_cand, q, budget, &r_idx, &r_dist)) != FM_OK) return rc;
+        hipLaunchKernelGGL(mutual_join_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, d_pass, d_bc, nq, nblk, (const int32_t*)r_idx,
+                           (const float*)r_dist, a.tau, a.symmetric, d_ratio, (uint8_t*)(b + o_pass2), (int*)(b + o_bc2));
+        HIP_TRY(ctx, hipGetLastError());
+        d_pass = (const uint8_t*)(b + o_pass2);
+        d_bc = (const int*)(b + o_bc2);
+    }
+    // (no candidates: the forward flags are all clear and the same compaction writes the zero counts)
+    if (a.to_dev && (rc = wait_for_stream(ctx, a.consumer)) != FM_OK) return rc;
+    // per-image counts (device form: and the caller's rows) by the per-image ordered compaction of the other _each calls
+    for (int64_t i0 = 0; i0 < ni; i0 += kCollAcceptMaxChunk) {           // (blockIdx.y of the compaction)
+        const int64_t g = std::min<int64_t>(ni - i0, kCollAcceptMaxChunk);
+        hipLaunchKernelGGL(coll_each_compact_kernel, dim3((unsigned)nblk, (unsigned)g), dim3(256), 0, ctx->stream,
+                           (const int32_t*)d_tidx + i0 * nq, (const float*)d_dist + i0 * nq, (const double*)d_ratio + i0 * nq, d_pass + i0 * nq,
+                           d_bc + i0 * nblk, nq, a.to_dev ? cap : 0, (int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, (double*)nullptr,
+                           a.to_dev && cap > 0 ? a.d_rows + (size_t)i0 * cap * 3 : (int32_t*)nullptr,
+                           a.to_dev ? (long long*)a.d_counts + i0 : (long long*)nullptr, d_full + i0);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (a.to_dev) {
+        if ((rc = results_written(ctx, a.consumer)) != FM_OK) return rc;
+        ctx->rows_stream = ctx->stream;
+        if (!a.h_counts) return FM_OK;
+        HIP_TRY(ctx, hipMemcpyAsync(a.h_counts, d_full, (size_t)ni * 8, hipMemcpyDeviceToHost, ctx->stream));
+        return cs.finish();
+    }
+    if (pk > 0) {
+        hipLaunchKernelGGL(coll_mutual_pack_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, (const int32_t*)d_tidx, (const float*)d_dist,
+                           (const double*)d_ratio, d_pass, d_bc, nq, nblk, (int32_t*)(b + o_cq), (int32_t*)(b + o_ct), (float*)(b + o_cd),
+                           (double*)(b + o_cr));
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    // the counts decide how much is copied: one small synchronous read, then the packed rows of all images in four copies
+    std::vector<unsigned long long> cnt((size_t)ni);
+    HIP_TRY(ctx, hipMemcpyAsync(cnt.data(), d_full, (size_t)ni * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    size_t total = 0;
+    for (int64_t i = 0; i < ni; ++i) total += (size_t)cnt[(size_t)i];
+    std::vector<int32_t> hq, ht;
+    std::vector<float> hd;
+    std::vector<double> hr;
+    if (pk > 0 && total > 0) {
+        try { hq.resize(total); ht.resize(total); hd.resize(total); hr.resize(total); }
+        catch (const std::bad_alloc&) { return fail(ctx, FM_ENOMEM, who + ": out of host memory"); }
+        HIP_TRY(ctx, d2h(ctx, hq.data(), b + o_cq, total * 4));
+        HIP_TRY(ctx, d2h(ctx, ht.data(), b + o_ct, total * 4));
+        HIP_TRY(ctx, d2h(ctx, hd.data(), b + o_cd, total * 4));
+        HIP_TRY(ctx, d2h(ctx, hr.data(), b + o_cr, total * 8));
+    }
+    if ((rc = cs.finish()) != FM_OK) return rc;
+    size_t at = 0;
+    for (int64_t i = 0; i < ni; ++i) {
+        const size_t n = (size_t)cnt[(size_t)i], m = std::min<size_t>(n, (size_t)cap);
+        if (pk > 0 && m > 0) {
+            memcpy(a.qidx + i * cap, hq.data() + at, m * 4);
+            memcpy(a.tidx + i * cap, ht.data() + at, m * 4);
+            memcpy(a.dist + i * cap, hd.data() + at, m * 4);
+            memcpy(a.ratio + i * cap, hr.data() + at, m * 8);
+        }
+        at += n;
+        a.counts[i] = (int64_t)n;
+    }
+    return FM_OK;
+}
+
+extern "C" int fm_collection_mutual_ratio_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t symmetric, int64_t cap,
+                                               int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+{
+    const CollMutualArgs a{"fm_collection_mutual_ratio_each", tau, symmetric, cap, qidx, tidx, dist, ratio, n_accepted,
+                           false, nullptr, nullptr, nullptr, FM_NO_STREAM};
+    return coll_mutual_each(ctx, c, q, a);
+}
+
+extern "C" int fm_collection_mutual_ratio_each_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t symmetric, int64_t cap,
+                                                   int32_t* d_rows, int64_t* d_counts, int64_t* h_counts, void* consumer_stream)
+{
+    const CollMutualArgs a{"fm_collection_mutual_ratio_each_dev", tau, symmetric, cap, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           true, d_rows, d_counts, h_counts, consumer_stream};
+    return coll_mutual_each(ctx, c, q, a);
+}

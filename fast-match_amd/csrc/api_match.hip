@@ -12,6 +12,8 @@
 // Reference call sites are cited in the header next to each entry point.
 #include "ctx_internal.h"
 
+#include <algorithm>
+
 using namespace fm;
 
 // ---------------------------------------------------------------------------------------
@@ -1580,6 +1582,235 @@ extern "C" int fm_knn2_ratio_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t
         *n_accepted = (int64_t)cnt;
     }
     return FM_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// mutual nearest neighbours + ratio test: fm_mutual_ratio, fm_mutual_ratio_dev (and, api_collection.hip, the per-image forms)
+// ---------------------------------------------------------------------------------------
+// hloc's "NN-ratio + mutual", kornia's match_smnn, cv2's knnMatch(k = 2) + ratio + crossCheck loop.  One full sweep: the
+// forward 2-NN lists and Lowe's test as fm_knn2_ratio runs them; only the train rows that are the first neighbour of a
+// query row that PASSED are asked for their nearest query rows -- they are gathered into a bank G and fm_knn2(G, q) is a
+// sweep of n_cand x nq pairs, not nt x nq.  The candidate count is read back between the two (the call's host wait).
+// Entry / block / candidate numbering: ctx_internal.h.
+__global__ __launch_bounds__(256)
+void lowe_each_kernel(const int32_t* __restrict__ idx2, const float* __restrict__ dist2, int64_t nq, int nblk,
+                                 double tau, int32_t* __restrict__ tidx, float* __restrict__ dist,
+                                 double* __restrict__ ratio, uint8_t* __restrict__ pass, int* __restrict__ block_counts)
+{
+    const int64_t q = (int64_t)(blockIdx.x % (unsigned)nblk) * 256 + threadIdx.x;
+    const int64_t e = (int64_t)(blockIdx.x / (unsigned)nblk) * nq + q;
+    bool p = false;
+    if (q < nq) {
+        const float d1 = dist2[2 * e], d2 = dist2[2 * e + 1];
+        const double r = (idx2[2 * e + 1] >= 0) ? (double)d1 / (double)d2 : NAN;
+        p = r < tau;
+        tidx[e] = idx2[2 * e];
+        dist[e] = d1;
+        ratio[e] = r;
+        pass[e] = p ? 1 : 0;
+    }
+    emit_block_count(__ballot(p), block_counts);
+}
+
+__global__ __launch_bounds__(256)
+void mutual_cand_kernel(const int32_t* __restrict__ tidx, const uint8_t* __restrict__ pass,
+                        const int* __restrict__ block_counts, int64_t nq, int nblk,
+                        const int32_t* __restrict__ first_row, int32_t* __restrict__ cand_rows,
+                        unsigned long long* __restrict__ n_cand)
+{
+    const int64_t img = blockIdx.x / (unsigned)nblk;
+    const int64_t q = (int64_t)(blockIdx.x % (unsigned)nblk) * 256 + threadIdx.x;
+    const int64_t e = img * nq + q;
+    const bool p = q < nq && pass[e];
+    int64_t total;
+    const int64_t c = compact_rank(block_counts, (int)blockIdx.x, p, &total);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_cand = (unsigned long long)total;
+    if (p) cand_rows[c] = (first_row ? first_row[img] : 0) + tidx[e];
+}
+
+__global__ __launch_bounds__(256)
+void mutual_join_kernel(const uint8_t* __restrict__ pass, const int* __restrict__ block_counts, int64_t nq, int nblk,
+                        const int32_t* __restrict__ r_idx, const float* __restrict__ r_dist, double tau, int symmetric,
+                        double* __restrict__ ratio, uint8_t* __restrict__ pass2, int* __restrict__ block_counts2)
+{
+    const int64_t q = (int64_t)(blockIdx.x % (unsigned)nblk) * 256 + threadIdx.x;
+    const int64_t e = (int64_t)(blockIdx.x / (unsigned)nblk) * nq + q;
+    const bool p = q < nq && pass[e];
+    int64_t total;
+    const int64_t c = compact_rank(block_counts, (int)blockIdx.x, p, &total);
+    bool keep = false;
+    if (p) {
+        keep = r_idx[2 * c] == (int32_t)q;                 // mutual: the train row's nearest query row (lowest index on ties)
+        if (keep && symmetric) {
+            const double r = (r_idx[2 * c + 1] >= 0) ? (double)r_dist[2 * c] / (double)r_dist[2 * c + 1] : NAN;
+            keep = r < tau;
+            if (keep && r > ratio[e]) ratio[e] = r;
+        }
+    }
+    if (q < nq) pass2[e] = keep ? 1 : 0;
+    emit_block_count(__ballot(keep), block_counts2);
+}
+
+// Up to four planes of a bank's rows, moved by 16-byte units (4-byte units for the per-row words); the slots from n up to
+// n_pad take the plane's padding word.
+struct GatherPlane { const char* src; char* dst; int row_bytes; unsigned pad; };
+struct GatherPlanes { GatherPlane p[4]; };
+
+// G's planes from the rows rows[0 .. n) of the source bank's: blockIdx.y = plane, one thread per unit, grid-stride.
+__global__ __launch_bounds__(256)
+void mutual_gather_kernel(const int32_t* __restrict__ rows, int64_t n, int64_t n_pad, GatherPlanes g)
+{
+    const GatherPlane pl = g.p[blockIdx.y];
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    if (pl.row_bytes >= 16) {
+        const int upr = pl.row_bytes >> 4;
+        for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < n_pad * upr; u += stride) {
+            const int64_t slot = u / upr;
+            const int k = (int)(u - slot * upr);
+            uint4 w = make_uint4(pl.pad, pl.pad, pl.pad, pl.pad);
+            if (slot < n) w = *(const uint4*)(pl.src + (int64_t)rows[slot] * pl.row_bytes + 16 * k);
+            *(uint4*)(pl.dst + slot * pl.row_bytes + 16 * k) = w;
+        }
+    } else {
+        for (int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x; slot < n_pad; slot += stride)
+            ((unsigned*)pl.dst)[slot] = slot < n ? ((const unsigned*)pl.src)[rows[slot]] : pl.pad;
+    }
+}
+
+int fm::mutual_reverse_device(fm_ctx* ctx, const Bank& t, const int32_t* cand_rows, int64_t n_cand, const fm_bank* q, size_t budget,
+                              int32_t** r_idx, float** r_dist)
+{
+    int64_t chunk = (int64_t)(budget / mutual_row_bytes(t)) / kStageRows * kStageRows;
+    chunk = std::max<int64_t>(kStageRows, std::min<int64_t>(chunk, pad128(n_cand)));
+    // ws_in: the reverse lists of all candidates | G's planes for one chunk (padding rows as each route's sweeps expect them:
+    // zero rows, norm 0; float32 accumulator init -3.4e38)
+    const float pad_aux = -3.4e38f;
+    unsigned pad_aux_bits;
+    memcpy(&pad_aux_bits, &pad_aux, 4);
+    const size_t rb[3][4] = {{(size_t)kDim, 4, 0, 0}, {(size_t)kDim * 4, (size_t)kDim * 2, 4, 4}, {(size_t)t.ksteps * 16, (size_t)t.ksteps * 64, 0, 0}};
+    const int route = t.kind == FM_BANK_F32 ? 1 : t.kind == FM_BANK_BIN ? 2 : 0;
+    const void* src[3][4] = {{t.rows8, t.norm, nullptr, nullptr}, {t.rowsf, t.rowsh, t.normf, t.auxf}, {t.rowsb, t.rows4, nullptr, nullptr}};
+    size_t off = 0, o_pl[4] = {0, 0, 0, 0};
+    const size_t o_ri = carve(off, (size_t)n_cand * 8), o_rd = carve(off, (size_t)n_cand * 8);
+    int npl = 0;
+    for (; npl < 4 && rb[route][npl]; ++npl) o_pl[npl] = carve(off, (size_t)chunk * rb[route][npl]);
+    int rc;
+    if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, off + 64)) != FM_OK) return rc;
+    char* b = (char*)ctx->ws_in;
+    *r_idx = (int32_t*)(b + o_ri);
+    *r_dist = (float*)(b + o_rd);
+    GatherPlanes gp{};
+    for (int i = 0; i < npl; ++i) gp.p[i] = GatherPlane{(const char*)src[route][i], b + o_pl[i], (int)rb[route][i], 0u};
+    if (route == 1) gp.p[3].pad = pad_aux_bits;
+    fm_bank g;
+    static_cast<Bank&>(g) = bank_rows_view(t, 0, 0);      // kind, width and the scale terms: upper bounds for any subset of t's rows
+    g.rows8 = nullptr; g.norm = nullptr; g.aux = nullptr; g.rowsf = nullptr; g.rowsh = nullptr; g.normf = nullptr; g.auxf = nullptr;
+    g.rowsb = nullptr; g.rows4 = nullptr;
+    if (route == 0) { g.rows8 = (int8_t*)gp.p[0].dst; g.norm = (int32_t*)gp.p[1].dst; }
+    else if (route == 1) { g.rowsf = (float*)gp.p[0].dst; g.rowsh = (uint16_t*)gp.p[1].dst; g.normf = (float*)gp.p[2].dst; g.auxf = (float*)gp.p[3].dst; }
+    else { g.rowsb = (uint8_t*)gp.p[0].dst; g.rows4 = (uint8_t*)gp.p[1].dst; }
+    for (int64_t c0 = 0; c0 < n_cand; c0 += chunk) {
+        g.n = std::min<int64_t>(chunk, n_cand - c0);
+        g.n_pad = g.cap_pad = pad128(g.n);
+        const int64_t units = g.n_pad * (int64_t)(rb[route][0] >> 4);
+        hipLaunchKernelGGL(mutual_gather_kernel, dim3((unsigned)std::min<int64_t>((units + 255) / 256, 16384), (unsigned)npl), dim3(256), 0,
+                           ctx->stream, cand_rows + c0, g.n, g.n_pad, gp);
+        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = knn2_device(ctx, &g, q, *r_idx + 2 * c0, *r_dist + 2 * c0)) != FM_OK) return rc;
+    }
+    return FM_OK;
+}
+
+// Where a pair's accepted rows go: the host arrays (through compacted columns in ws_out) or the caller's device rows.
+struct MutualSink {
+    int32_t* qidx; int32_t* tidx; float* dist; double* ratio;     // host form
+    int32_t* d_rows; int64_t* d_count; void* consumer; bool dev;  // device form
+    int64_t* n_accepted;
+};
+
+static int mutual_ratio_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int symmetric, int64_t cap, const MutualSink& s)
+{
+    const int64_t nq = q->n;
+    const int64_t ccap = s.dev ? 0 : (cap < nq ? cap : nq);
+    const int nblk = (int)((nq + 255) / 256);
+    size_t off = 0;         // behind the forward lists: the candidates' train rows, the join's flags and counts, the compacted outputs
+    const size_t o_cand = carve(off, (size_t)nq * 4, 16), o_p2 = carve(off, (size_t)nq, 16), o_bc2 = carve(off, (size_t)nblk * 4, 16), o_cnt2 = carve(off, 16, 16);
+    const size_t o_cq = carve(off, (size_t)ccap * 4, 16), o_ct = carve(off, (size_t)ccap * 4, 16), o_cd = carve(off, (size_t)ccap * 4, 16), o_cr = carve(off, (size_t)ccap * 8, 16);
+    CallScope cs(ctx);
+    LoweWs w;
+    int rc;
+    if ((rc = knn2_lowe_device(ctx, q, t, tau, off, &w)) != FM_OK) return rc;
+    char* b = w.rest;
+    int32_t* d_cand = (int32_t*)(b + o_cand);
+    const uint8_t* d_pass = w.pass;
+    const int* d_bc = w.bc;
+    unsigned long long* d_cnt = w.cnt;
+    hipLaunchKernelGGL(mutual_cand_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)w.tidx, (const uint8_t*)w.pass,
+                       (const int*)w.bc, nq, nblk, (const int32_t*)nullptr, d_cand, w.cnt);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long n_cand = 0;      // the call's host wait: how many rows the reverse sweep has to answer for
+    HIP_TRY(ctx, hipMemcpyAsync(&n_cand, w.cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_cand > 0) {
+        int32_t* r_idx; float* r_dist;
+        if ((rc = mutual_reverse_device(ctx, *t, d_cand, (int64_t)n_cand, q, kMutualGatherBytes, &r_idx, &r_dist)) != FM_OK) return rc;
+        hipLaunchKernelGGL(mutual_join_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const uint8_t*)w.pass, (const int*)w.bc, nq, nblk,
+                           (const int32_t*)r_idx, (const float*)r_dist, tau, symmetric, w.ratio, (uint8_t*)(b + o_p2), (int*)(b + o_bc2));
+        HIP_TRY(ctx, hipGetLastError());
+        d_pass = (const uint8_t*)(b + o_p2); d_bc = (const int*)(b + o_bc2); d_cnt = (unsigned long long*)(b + o_cnt2);
+    }
+    // (no candidates: the forward flags are all clear, the same compaction writes the zero count)
+    if (s.dev) {
+        if ((rc = wait_for_stream(ctx, s.consumer)) != FM_OK) return rc;
+        hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)w.tidx, (const float*)w.dist,
+                           d_pass, d_bc, nq, cap, s.d_rows, (long long*)s.d_count, d_cnt);
+        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = results_written(ctx, s.consumer)) != FM_OK) return rc;
+        if (s.n_accepted) {
+            unsigned long long cnt = 0;
+            HIP_TRY(ctx, hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            *s.n_accepted = (int64_t)cnt;
+        }
+        return FM_OK;
+    }
+    hipLaunchKernelGGL(compact_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, (const int32_t*)w.tidx, (const float*)w.dist,
+                       (const double*)w.ratio, d_pass, d_bc, nq, ccap, (int32_t*)(b + o_cq), (int32_t*)(b + o_ct), (float*)(b + o_cd),
+                       (double*)(b + o_cr), d_cnt);
+    HIP_TRY(ctx, hipGetLastError());
+    return cs.finish_rows(d_cnt, ccap, {{s.qidx, b + o_cq, 4}, {s.tidx, b + o_ct, 4}, {s.dist, b + o_cd, 4}, {s.ratio, b + o_cr, 8}}, s.n_accepted);
+}
+
+extern "C" int fm_mutual_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t symmetric, int64_t cap,
+                               int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+{
+    int rc = check_pair(ctx, q, t, "fm_mutual_ratio", true);
+    if (rc != FM_OK) return rc;
+    if (n_accepted) *n_accepted = 0;
+    if (q->n == 0) return FM_OK;
+    if (cap < 0 || (cap > 0 && (!qidx || !tidx || !dist || !ratio))) return fail(ctx, FM_EINVAL, "fm_mutual_ratio: bad output arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const MutualSink s{qidx, tidx, dist, ratio, nullptr, nullptr, FM_NO_STREAM, false, n_accepted};
+    return mutual_ratio_pair(ctx, q, t, tau, symmetric, cap, s);
+}
+
+extern "C" int fm_mutual_ratio_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t symmetric, int64_t cap,
+                                   int32_t* d_rows, int64_t* d_count, int64_t* n_accepted, void* consumer_stream)
+{
+    int rc = check_pair(ctx, q, t, "fm_mutual_ratio_dev", true);
+    if (rc != FM_OK) return rc;
+    if (n_accepted) *n_accepted = 0;
+    if (cap < 0 || !d_count || (cap > 0 && !d_rows)) return fail(ctx, FM_EINVAL, "fm_mutual_ratio_dev: bad output arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_ptr(ctx, d_count, "fm_mutual_ratio_dev", "d_count")) != FM_OK) return rc;
+    if (cap > 0 && (rc = check_device_ptr(ctx, d_rows, "fm_mutual_ratio_dev", "d_rows")) != FM_OK) return rc;
+    if (q->n == 0) {
+        if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(d_count, 0, 8, ctx->stream));
+        return results_written(ctx, consumer_stream);
+    }
+    const MutualSink s{nullptr, nullptr, nullptr, nullptr, d_rows, d_count, consumer_stream, true, n_accepted};
+    return mutual_ratio_pair(ctx, q, t, tau, symmetric, cap, s);
 }
 
 // Host sink of the accepted calls: the four arrays, the count word, the capacity

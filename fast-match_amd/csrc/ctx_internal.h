@@ -250,17 +250,16 @@ __device__ __forceinline__ void emit_block_count(unsigned long long m, int* __re
     if (threadIdx.x == 0) block_counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
 }
 
-// Row q = this thread's row of pass[0 .. nq), *p: it is accepted, and then its slot in the compacted arrays (ascending row
-// index): block b sums the counts of the blocks before it, every accepted row takes offset + rank.  Deterministic (no
-// atomics).  *total: the accepted rows up to and including this block's -- in the last block, all of them.
-__device__ __forceinline__ int64_t compact_slot(const int* __restrict__ block_counts, const uint8_t* __restrict__ pass, int64_t nq,
-                                                int64_t* q, bool* p, int64_t* total)
+// The rank of this thread's flag p among the set flags of the blocks 0 .. blk in thread order (this block is number blk of
+// block_counts): block b sums the counts of the blocks before it, every set flag takes offset + rank.  Deterministic (no
+// atomics).  *total: the set flags up to and including this block's -- in the last block, all of them.
+__device__ __forceinline__ int64_t compact_rank(const int* __restrict__ block_counts, int blk, bool p, int64_t* total)
 {
     __shared__ int red[256];
     __shared__ int wave_cnt[4];
     const int tid = threadIdx.x;
     int s = 0;
-    for (int b = tid; b < (int)blockIdx.x; b += 256) s += block_counts[b];
+    for (int b = tid; b < blk; b += 256) s += block_counts[b];
     red[tid] = s;
     __syncthreads();
     for (int d = 128; d > 0; d >>= 1) {
@@ -268,9 +267,7 @@ __device__ __forceinline__ int64_t compact_slot(const int* __restrict__ block_co
         __syncthreads();
     }
     const int64_t base = red[0];
-    *q = (int64_t)blockIdx.x * 256 + tid;
-    *p = *q < nq && pass[*q];
-    const unsigned long long m = __ballot(*p);
+    const unsigned long long m = __ballot(p);
     const int lane = tid & 63, wave = tid >> 6;
     if (lane == 0) wave_cnt[wave] = __popcll(m);
     __syncthreads();
@@ -278,6 +275,53 @@ __device__ __forceinline__ int64_t compact_slot(const int* __restrict__ block_co
     for (int w = 0; w < wave; ++w) wb += wave_cnt[w];
     *total = base + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
     return base + wb + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// Row q = this thread's row of pass[0 .. nq), *p: it is accepted, and then its slot in the compacted arrays (ascending row
+// index): compact_rank under a grid of one block per 256 rows.
+__device__ __forceinline__ int64_t compact_slot(const int* __restrict__ block_counts, const uint8_t* __restrict__ pass, int64_t nq,
+                                                int64_t* q, bool* p, int64_t* total)
+{
+    *q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    *p = *q < nq && pass[*q];
+    return compact_rank(block_counts, (int)blockIdx.x, *p, total);
+}
+
+// ---- mutual nearest neighbours + ratio test (fm_mutual_ratio, fm_collection_mutual_ratio_each; api_match.hip) -----------------
+// The kernels work on entries e = image * nq + query row in one flat grid of n_images * nblk 256-thread blocks (block b:
+// image b / nblk, rows from (b % nblk) * 256; nblk = ceil(nq / 256); a bank pair is one image); block counts are [image][nblk],
+// the layout emit_block_count leaves under such a grid and coll_each_compact_kernel reads.  A CANDIDATE is an entry that
+// passed the forward ratio test; its index is its rank among the passing entries in entry order.
+// Lowe's test on per-image 2-NN lists [n_images][nq][2]: lowe_kernel's rule, word for word, per entry.
+__global__ __launch_bounds__(256) void lowe_each_kernel(const int32_t* __restrict__ idx2, const float* __restrict__ dist2, int64_t nq, int nblk,
+                                 double tau, int32_t* __restrict__ tidx, float* __restrict__ dist,
+                                 double* __restrict__ ratio, uint8_t* __restrict__ pass, int* __restrict__ block_counts);
+// cand_rows[candidate] = the train row whose reverse neighbours decide it: first_row[image] + tidx[entry] (first_row null:
+// tidx itself); *n_cand = the number of candidates.
+__global__ __launch_bounds__(256) void mutual_cand_kernel(const int32_t* __restrict__ tidx, const uint8_t* __restrict__ pass,
+                                   const int* __restrict__ block_counts, int64_t nq, int nblk,
+                                   const int32_t* __restrict__ first_row, int32_t* __restrict__ cand_rows,
+                                   unsigned long long* __restrict__ n_cand);
+// The join: a candidate is kept iff the nearest query row of its train row (r_idx / r_dist [n_cand][2], fm_knn2's lists of the
+// gathered rows over the query bank) is its own and, symmetric != 0, the reverse ratio passes too -- ratio[entry] then
+// becomes the larger of the two.  pass2 / block_counts2: the flags and counts of the final compaction.
+__global__ __launch_bounds__(256) void mutual_join_kernel(const uint8_t* __restrict__ pass, const int* __restrict__ block_counts, int64_t nq, int nblk,
+                                   const int32_t* __restrict__ r_idx, const float* __restrict__ r_dist, double tau, int symmetric,
+                                   double* __restrict__ ratio, uint8_t* __restrict__ pass2, int* __restrict__ block_counts2);
+namespace fm {
+// Bytes of the gathered bank per candidate: every plane the sweeps read on the output side (integer route: rows8 + norm;
+// float32 route: rowsf + rowsh + normf + auxf; binary: rowsb + rows4).
+inline size_t mutual_row_bytes(const Bank& t)
+{
+    return t.kind == FM_BANK_F32 ? (size_t)kDim * 6 + 8 : t.kind == FM_BANK_BIN ? (size_t)t.ksteps * 80 : (size_t)kDim + 4;
+}
+constexpr size_t kMutualGatherBytes = (size_t)1 << 30;     // fm_mutual_ratio's budget for the gathered bank (a collection: "coll_ws_bytes")
+// The reverse 2-NN lists of the candidates on the context's stream: the rows cand_rows[0 .. n_cand) of t's arrays gathered
+// into a bank G in ws_in (in chunks of consecutive candidates of at most `budget` bytes, whole 128-row stages, at least
+// one), then fm_knn2(G, q) -- the top-2 sweep of the pair's route with its float32-root repair -- into *r_idx / *r_dist
+// [n_cand][2], which live in ws_in in front of G.  n_cand > 0, q->n > 0; t supplies planes and scale terms (upper bounds).
+int mutual_reverse_device(fm_ctx* ctx, const Bank& t, const int32_t* cand_rows, int64_t n_cand, const fm_bank* q, size_t budget,
+                          int32_t** r_idx, float** r_dist);
 }
 
 // Brackets one API call: events for total time, stats accounting after the final sync.

@@ -205,6 +205,25 @@ def ratio_match_arrays(dt1, dt2, tau, options={}):
             tb.close()
 
 
+def mutual_ratio_match_arrays(dt1, dt2, tau, symmetric=False, options={}):
+    """Mutual nearest neighbours that also pass the ratio test (hloc's "NN-ratio + mutual", kornia's ``match_smnn``, cv2's
+    ``knnMatch(k=2)`` + ratio + crossCheck loop) in one call, ``fm_mutual_ratio``: query row i is kept iff
+    ``d0 / d1 < tau`` on its 2-NN list and i is the nearest query row of its first neighbour (lowest index on ties);
+    ``symmetric`` also asks the ratio test of that train row's own 2-NN list over the query rows.  ``options["normType"]``:
+    NORM_L2 or NORM_HAMMING.  Returns (query idx, train idx, distance, ratio) ascending in query index; ``ratio`` is the
+    larger of the two ratios in symmetric mode."""
+    norm = _norm_type(options, dt1, dt2)
+    ctx = _context(options)
+    qb, q_tmp, tb, t_tmp = _bank_pair(ctx, dt1, dt2, norm)
+    try:
+        return ctx.mutual_ratio(qb, tb, tau, symmetric)
+    finally:
+        if q_tmp:
+            qb.close()
+        if t_tmp:
+            tb.close()
+
+
 def bf_radius_match_arrays(dt1, dt2, maxDistance, options={}):
     """Array form of :func:`bf_radius_match`: ``(offsets int64[nq + 1], idx int32[n], dist float32[n])``; query row i's
     list is ``idx[offsets[i]:offsets[i + 1]]`` / ``dist[...]``.  ``maxDistance`` is a scalar (float32, as the cv2 binding
@@ -415,6 +434,33 @@ class BFMatcher(object):
         tidx, dist = self.matchEach_arrays(queryDescriptors)
         return [[DMatch(int(qi), int(tidx[i, qi]), dist[i, qi], i) for qi in np.nonzero(tidx[i] >= 0)[0]]
                 for i in range(tidx.shape[0])]
+
+    def mutualRatioMatchEach_arrays(self, queryDescriptors, tau, symmetric=False):
+        """A list of (qidx, tidx, dist, ratio) per image: the mutual nearest neighbours of the query inside every image
+        separately that also pass the ratio test there (``Collection.mutual_ratio_each``; slot i equals
+        ``mutual_ratio_match_arrays(query, image_i, tau, symmetric)``).  NORM_L2 and NORM_HAMMING."""
+        self._check_collection("BFMatcher.mutualRatioMatchEach")
+        if self.normType == NORM_HAMMING and not isinstance(queryDescriptors, _ffi.Bank) and np.asarray(queryDescriptors).dtype != np.uint8:
+            raise ValueError("NORM_HAMMING needs uint8 descriptors (cv2 asserts CV_8U), got %s" % np.asarray(queryDescriptors).dtype)
+        if not isinstance(queryDescriptors, _ffi.Bank) and np.asarray(queryDescriptors).ndim != 2:
+            raise ValueError("descriptors must be a 2-D [n, dim] array")
+        coll = self.train()
+        qb, tmp = self._query(coll.ctx, queryDescriptors)
+        try:
+            return coll.mutual_ratio_each(qb, tau, symmetric)
+        finally:
+            if tmp:
+                qb.close()
+
+    def mutualRatioMatchEach(self, queryDescriptors, tau, symmetric=False):
+        """``knnMatch(k=2)`` + ratio test + crossCheck against every image of the collection separately, as one call: one list
+        of ``DMatch`` per added image, ``imgIdx`` set, ascending query index (``fm_collection_mutual_ratio_each``: one
+        restricted reverse sweep serves all images).  The matcher's ``crossCheck`` flag is ignored: the test is mutual by
+        definition.  ``ValueError`` for an empty collection and for a query of the wrong dtype, before anything is uploaded."""
+        out = []
+        for i, (qidx, tidx, dist, _) in enumerate(self.mutualRatioMatchEach_arrays(queryDescriptors, tau, symmetric)):
+            out.append([DMatch(int(qidx[j]), int(tidx[j]), dist[j], i) for j in range(qidx.shape[0])])
+        return out
 
     # -- cv2's matching methods ------------------------------------------------------------
     def knnMatch(self, queryDescriptors, trainDescriptors=None, k=None):

@@ -12,6 +12,9 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
 * ``knn(q, t, k)`` -> ``(idx int32 [nq, k], dist float32 [nq, k])``, 1 <= k <= 8.
 * ``mutual_nn(q, t)`` -> ``(tidx int32 [nq], dist float32 [nq])``: the cross-checked 1-NN (-1 / inf: unmatched).
 * ``ratio_match(q, t, tau)`` -> ``(qidx, tidx, dist)`` of the rows whose first / second distance is below ``tau``.
+* ``mutual_ratio_match(q, t, tau, symmetric=False)`` -> ``(qidx, tidx, dist)`` of the rows that pass the ratio test AND are the
+  nearest query row of their first neighbour (hloc's "NN-ratio + mutual", kornia's ``match_smnn``); ``symmetric``: the train
+  row's own 2-NN list over the query rows passes the ratio test too (``fm_mutual_ratio_dev``).
 * ``radius_match(q, t, r)`` -> ``(offsets int64 [nq + 1], idx int32 [n], dist float32 [n])``: every train row with distance
   < r per query row (``cv2.BFMatcher.radiusMatch``), row i's list at ``offsets[i]:offsets[i + 1]``, ascending (distance, index).
   ``r`` is a Python or NumPy scalar, or a float32 CUDA tensor ``[nq]`` of one radius per query row on the context's device
@@ -27,6 +30,8 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
   ``mutual_nn_each(q, max_dist=None, cap=None)`` -> the same two tensors for the cross-checked 1-NN inside every image
   (``cv2.BFMatcher(norm, crossCheck=True).match(q, image)`` image by image, kept while ``dist < max_dist``), on uint8,
   float and binary collections alike;
+  ``mutual_ratio_each(q, tau, symmetric=False, cap=None)`` -> the same two tensors for ``mutual_ratio_match`` inside every
+  image (``fm_collection_mutual_ratio_each_dev``: one restricted reverse sweep serves all images);
   ``clear()``, ``close()``, ``info()``.  The collection equals the ``_ffi.Collection`` the same values build on the host.
 
 ``q`` and ``t`` are ``Bank``s or CUDA tensors (a tensor becomes a bank for the call).  The values are those of
@@ -35,7 +40,8 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
 Streams: ``torch.cuda.current_stream()`` is both the producer of the descriptor tensors and the consumer of the results --
 the library orders its kernels behind the one and the stream behind the other on the device, so no ``synchronize()`` is needed
 on either side (``ratio_match`` and ``Collection.ratio_match`` read the accepted count back to size their outputs: one host
-wait; ``radius_match`` and ``Collection.radius_match`` likewise wait for the total that sizes theirs -- a counts call, then a
+wait; ``mutual_ratio_match`` and ``Collection.mutual_ratio_each`` wait once inside the library, for the number of rows that
+passed the ratio test, which sizes the restricted reverse sweep, and ``mutual_ratio_match`` once more for its count; ``radius_match`` and ``Collection.radius_match`` likewise wait for the total that sizes theirs -- a counts call, then a
 fill call -- and the library reads the per-row counts back to plan its chunks).  For the radius calls the current stream is
 also the producer of ``r``.
 
@@ -162,6 +168,27 @@ def ratio_match(q, t, tau):
         count = torch.empty(1, dtype=torch.int64, device=dev)
         m = qb.ctx.knn2_ratio_dev(qb, tb, float(tau), rows.data_ptr(), count.data_ptr(), cap, want_count=True,
                                   consumer_stream=stream)
+        rows = rows[:min(m, cap)]
+        return rows[:, 0].contiguous(), rows[:, 1].contiguous(), rows[:, 2].contiguous().view(torch.float32)
+    finally:
+        for b in made:
+            b.close()
+
+
+def mutual_ratio_match(q, t, tau, symmetric=False):
+    """Mutual nearest neighbours that pass the ratio test: ``(qidx int32 [m], tidx int32 [m], dist float32 [m])`` of the query
+    rows i with d0 / d1 < ``tau`` (float64; a zero second distance is rejected) whose first neighbour's nearest query row is i
+    (lowest index on ties); ``symmetric``: that train row's 2-NN list over the query rows passes the same test.  Ascending
+    query index.  Two host waits: the candidate count inside the library, the accepted count that sizes the outputs."""
+    import torch
+    qb, tb, made = _pair(q, t)
+    try:
+        stream, dev = _stream_and_device(qb.ctx)
+        cap = qb.n
+        rows = torch.empty((max(cap, 1), 3), dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        m = qb.ctx.mutual_ratio_dev(qb, tb, float(tau), bool(symmetric), rows.data_ptr(), count.data_ptr(), cap, want_count=True,
+                                    consumer_stream=stream)
         rows = rows[:min(m, cap)]
         return rows[:, 0].contiguous(), rows[:, 1].contiguous(), rows[:, 2].contiguous().view(torch.float32)
     finally:
@@ -366,6 +393,28 @@ class Collection(object):
             counts = torch.zeros(ni, dtype=torch.int64, device=dev)
             self._coll.xcheck1_each_dev(qb, max_dist, rows.data_ptr() if rows.numel() else 0, counts.data_ptr() if ni else 0, cap,
                                         consumer_stream=stream)
+            return rows, counts
+        finally:
+            for b in made:
+                b.close()
+
+    def mutual_ratio_each(self, q, tau, symmetric=False, cap=None):
+        """``mutual_ratio_match`` of ``q`` inside every image separately, left on the device: ``(rows int32 [n_images, cap, 3] =
+        (query, row inside the image, float32 distance bits), counts int64 [n_images] = min(accepted, cap))``, rows ascending
+        in query index; ``cap`` defaults to the query's rows.  ``q`` is a ``Bank`` or a CUDA tensor as ``add`` takes them.  One
+        host wait inside the library (the candidate count)."""
+        import torch
+        if cap is not None and int(cap) < 0:
+            raise ValueError("cap must not be negative")
+        qb, made = self._query(q)
+        try:
+            ni = self._coll.info()[0]
+            cap = qb.n if cap is None else int(cap)
+            stream, dev = _stream_and_device(qb.ctx)
+            rows = torch.empty((ni, cap, 3), dtype=torch.int32, device=dev)
+            counts = torch.zeros(ni, dtype=torch.int64, device=dev)
+            self._coll.mutual_ratio_each_dev(qb, float(tau), bool(symmetric), rows.data_ptr() if rows.numel() else 0,
+                                             counts.data_ptr() if ni else 0, cap, consumer_stream=stream)
             return rows, counts
         finally:
             for b in made:

@@ -51,7 +51,8 @@ typedef struct fm_bank fm_bank;
  * fm_collection_match_accepted_each, fm_collection_match_accepted_each_dev, the option "coll_ws_bytes"; still revision 12,
  * additions only -- fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev; still revision 12, additions
  * only -- fm_collection_radius_match, fm_radius_match_dev, fm_collection_radius_match_dev; still revision 12, additions
- * only -- fm_collection_xcheck1_each, fm_collection_xcheck1_each_dev).  A binding compares
+ * only -- fm_collection_xcheck1_each, fm_collection_xcheck1_each_dev; still revision 12, additions only -- fm_mutual_ratio,
+ * fm_mutual_ratio_dev, fm_collection_mutual_ratio_each, fm_collection_mutual_ratio_each_dev).  A binding compares
  * fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.                      */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -120,7 +121,11 @@ int  fm_ctx_destroy(fm_ctx* ctx);
  *   "coll_ws_bytes" 0..2^31-1  fm_collection_match_accepted_each, fm_collection_xcheck1_each: device bytes for the
  *                         per-(image, query row) arrays of one chunk of consecutive images (25 bytes per entry in the
  *                         accepted-match test, 17 in the cross-check, which keeps no ratio; at least one image per
- *                         chunk); 0 = one chunk up to 64 MiB, beyond that a quarter of the free device memory (0)
+ *                         chunk); 0 = one chunk up to 64 MiB, beyond that a quarter of the free device memory (0).
+ *                         fm_collection_mutual_ratio_each: device bytes for the gathered train rows of one chunk of
+ *                         consecutive candidates -- 132 bytes per candidate on the integer route, 776 on the float32 route,
+ *                         80 per 16 bytes of row width (rounded up) for binary rows; whole 128-row stages, at least one per
+ *                         chunk; 0 = 2^30
  * Unknown names and out-of-range values return FM_EINVAL.                                          */
 int  fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value);
 int  fm_ctx_get_option(fm_ctx* ctx, const char* name, int64_t* value);
@@ -332,6 +337,27 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  *     d_rows may be NULL; cap < 0: FM_EINVAL); consumer_stream ordered in both directions; h_counts (host, or NULL) receives
  *     the full counts and is the call's one host synchronisation -- on the integer and binary routes the call makes no
  *     other (but for the table upload of the first match after an add).
+ *   fm_collection_mutual_ratio_each: fm_mutual_ratio(q, image i, tau, symmetric) for every image in ONE call -- mutual nearest
+ *     neighbours that also pass the image's own ratio test, the strong per-image test of binary and float32 databases (which
+ *     have no self-distance test).  Slot i of qidx / tidx / dist / ratio [n_images][cap] equals, row by row and bit for bit,
+ *     fm_mutual_ratio(q, bank(image i), ...) on all three collection kinds; n_accepted[i] = the FULL count of image i, rows
+ *     written = min(count, cap); an empty image keeps its slot with count 0; images are independent: a descriptor present in
+ *     two images can match in both.  cap = 0: counts only (the row arrays may be NULL) -- only n_images words come back, the
+ *     mutual-ratio votes per image.  The forward lists are fm_collection_knn2_each's; which query rows a train row is nearest
+ *     to does not depend on the image it sits in, so the candidates of all images -- (image, query row) entries that passed
+ *     the ratio test, each naming its first neighbour by its physical row of the stack -- share ONE restricted reverse sweep,
+ *     fm_knn2 of the gathered rows over the query bank (float32-root repair included), in chunks of consecutive candidates
+ *     under the option "coll_ws_bytes"; then one join and the per-image ordered compaction.  One host wait between the two
+ *     sweeps (the 8-byte candidate count).  Accounted in fm_stats: pairs = nq * real rows + candidates * nq.  Errors, in
+ *     fm_collection_xcheck1_each's order: NULL handles; a query of another kind or width (FM_EINVAL; a query bank with no rows
+ *     is not held to the kind); a float32-route query with a finite magnitude above FM_COLLECTION_F32_MAX (FM_EUNSUPPORTED);
+ *     then the outputs (cap < 0, n_accepted NULL, a row array NULL with cap > 0 and nq > 0: FM_EINVAL).  nq = 0 writes zero
+ *     counts and nothing else; n_images = 0 is valid.
+ *   fm_collection_mutual_ratio_each_dev: the accepted rows left on the device, word for word as fm_collection_xcheck1_each_dev
+ *     leaves its rows: 12-byte rows {query, train row inside the image, float32 distance bits}, ascending in query index, of
+ *     image i at d_rows + i * cap * 3; d_counts[i] = min(count, cap) (cap = 0: d_rows may be NULL; cap < 0: FM_EINVAL);
+ *     consumer_stream ordered in both directions; h_counts (host, or NULL) receives the full counts.  The call waits once for
+ *     the candidate count on every route; asking for h_counts is a second wait.
  *   fm_collection_radius_match: fm_radius_match(q, T, ...) for T = the images' rows stacked in image order -- every database
  *     descriptor within r_i of query row i in ONE matrix-core sweep over the whole allocation (place recognition,
  *     de-duplication, Fast-Match's one-to-many test d(q, t) < tau * selfdist(q)).  Every hit is (img, row inside that image);
@@ -354,7 +380,7 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  *     the GPU").
  * Not built: the STACKED crossCheck on a collection (it has no meaning: OpenCV's batchDistance asserts update == 0 under
  * crossCheck -- recalled; neither cv2 nor its source was at hand; the per-image form is built:
- * fm_collection_xcheck1_each), mutual nearest neighbours combined with the per-image ratio test, a single reverse K8 sweep
+ * fm_collection_xcheck1_each), a single reverse K8 sweep
  * over a float32-route stack (its padding output rows would flood the filter's candidate lists: fm_collection_xcheck1_each
  * and fm_collection_match_accepted_each sweep image by image there), Hamming radiusMatch (for pairs or collections), radius queries per
  * image separately (an _each form), skipping the second count sweep of the counts-then-fill pattern, masks,
@@ -398,6 +424,12 @@ int  fm_collection_xcheck1_each(fm_ctx* ctx, fm_collection* coll, const fm_bank*
 int  fm_collection_xcheck1_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, float max_dist, int64_t cap,
                                     int32_t* d_rows /*device [n_images][cap][3]*/, int64_t* d_counts /*device [n_images]*/,
                                     int64_t* h_counts /*host [n_images] or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_mutual_ratio_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int32_t symmetric, int64_t cap,
+                                     int32_t* qidx, int32_t* tidx, float* dist, double* ratio /* each [n_images][cap] */,
+                                     int64_t* n_accepted /*[n_images]: the full count per image*/);
+int  fm_collection_mutual_ratio_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int32_t symmetric, int64_t cap,
+                                         int32_t* d_rows /*device [n_images][cap][3]*/, int64_t* d_counts /*device [n_images]*/,
+                                         int64_t* h_counts /*host [n_images] or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* ---- descriptors already on the GPU: device sources, device results ---------------------------------------------------------
  * Every creator above takes a HOST array and every dense matcher call ends in host arrays: the shape of the reference, whose
@@ -520,6 +552,34 @@ int  fm_collection_radius_match_dev(fm_ctx* ctx, fm_collection* coll, const fm_b
  * A zero second distance (where the notebook's Python division raises) is rejected.       */
 int  fm_knn2_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                    int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted);
+
+/* Mutual nearest neighbours that also pass the ratio test, in one call: what most pipelines with a GPU extractor run -- hloc's
+ * "NN-ratio + mutual", kornia's match_smnn, the cv2 loop knnMatch(k = 2) + ratio + crossCheck.  With K2 = fm_knn2(q, t) and R2 =
+ * fm_knn2(t, q) (the two nearest QUERY rows of every train row; both ordered by (float32 distance bits, index), the float32-root
+ * repair of the integer route included), query row i with (t0, d0), (t1, d1) = K2[i] is accepted iff
+ *   1. forward ratio: t1 >= 0 and (double)d0 / (double)d1 < tau -- fm_knn2_ratio's rule (a missing second neighbour or 0 / 0
+ *      is rejected; tau = +inf keeps every row whose ratio is a number);
+ *   2. mutual: R2[t0][0] == i -- the nearest query row of t0 is i, the lowest query index winning a tie;
+ *   3. symmetric != 0 only, reverse ratio: with (q0', e0), (q1', e1) = R2[t0], q1' >= 0 and (double)e0 / (double)e1 < tau (a
+ *      query bank of one row accepts nothing in symmetric mode).
+ * The accepted rows come out in ascending query index as qidx, tidx = t0, dist = d0; ratio = the forward ratio, in symmetric
+ * mode the larger of the two (ratio < tau either way); *n_accepted = the full count, rows written = min(count, cap); cap = 0:
+ * the count only (the row arrays may be NULL).  All three bank kinds; nq = 0 and nt = 0 are valid and accept nothing.  Argument
+ * checks are fm_knn2_ratio's, in its order (a binary bank paired with a non-binary one: FM_EINVAL).
+ * ONE full sweep, where fm_knn2_ratio + fm_xcheck1 take two: the mutual test is only needed for the train rows that are the
+ * first neighbour of a query row that already passed the ratio test.  Those rows are gathered into a workspace bank G (every
+ * plane the sweeps read on the output side, padded to whole 128-row stages; duplicates where two query rows share a first
+ * neighbour) and R2 is fm_knn2(G, q): a sweep of n_cand x nq pairs.  The candidate count is read back between the two sweeps:
+ * the call's host wait.  fm_stats: pairs grows by nq * nt + n_cand * nq.
+ * fm_mutual_ratio_dev: the accepted rows in caller DEVICE memory, word for word as fm_knn2_ratio_dev leaves them -- 12-byte rows
+ * {query, train, float32 distance bits}, *d_count = min(accepted, cap), *n_accepted (host, may be NULL) the full count; pointer
+ * checks and stream ordering are fm_knn2_ratio_dev's.  Host synchronisation: ONE on every route, the 8-byte candidate count
+ * (and the one n_accepted != NULL asks for, as in fm_knn2_ratio_dev).  Not accounted in fm_stats.                            */
+int  fm_mutual_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t symmetric, int64_t cap,
+                     int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted);
+int  fm_mutual_ratio_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t symmetric, int64_t cap,
+                         int32_t* d_rows /*device [cap][3]*/, int64_t* d_count /*device*/, int64_t* n_accepted /*host, or NULL*/,
+                         void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* Replaces bf_match(d, d, k=2) + [r[1].distance] (cache.pyx:250-252; exact substitute
  * for the approximate flann_match at cache.pyx:271-273).  selfdist[i] = distance from
