@@ -463,6 +463,7 @@ static const OptionDef kOptions[] = {
     {"delegated_rounds", &Tuning::delegated_rounds, 0, 0, nullptr},       // a counter: set to 0, read
     {"radius_ws_bytes", &Tuning::radius_ws_bytes, 1 << 16, 0x7fffffff, nullptr},
     {"coll_ws_bytes", &Tuning::coll_ws_bytes, 0, 0x7fffffff, nullptr},
+    {"fp6_filter", &Tuning::fp6_filter, 0, 1, nullptr}, {"fp6_cap", &Tuning::fp6_cap, 1, 1 << 24, nullptr},
 };
 
 extern "C" int fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value)
@@ -482,6 +483,18 @@ extern "C" int fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value)
 extern "C" int fm_ctx_get_option(fm_ctx* ctx, const char* name, int64_t* value)
 {
     if (!ctx || !name || !value) return fail(ctx, FM_EINVAL, "fm_ctx_get_option: NULL argument");
+    // read-only: what the last FP6 filter launch left in its words, summed over its pairs (waits for the context's stream)
+    if (strcmp(name, "fp6_records") == 0 || strcmp(name, "fp6_fallbacks") == 0) {
+        unsigned w[2 * kRRBatchMax] = {0};
+        *value = 0;
+        if (ctx->f6.cnt && ctx->f6_last_n > 0) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(w, ctx->f6.cnt, (size_t)ctx->f6_last_n * 8, hipMemcpyDeviceToHost));
+            for (int i = 0; i < ctx->f6_last_n; ++i) *value += name[4] == 'r' ? (int64_t)w[2 * i] : (int64_t)(w[2 * i + 1] != 0);
+        }
+        return FM_OK;
+    }
     for (const OptionDef& o : kOptions)
         if (strcmp(o.name, name) == 0) { *value = ctx->tune.*(o.field); return FM_OK; }
     return fail(ctx, FM_EINVAL, std::string("fm_ctx_get_option: unknown option ") + name);
@@ -590,6 +603,7 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx)
     if (ctx->ws_partial) (void)hipFree(ctx->ws_partial);
     if (ctx->ws_out) (void)hipFree(ctx->ws_out);
     if (ctx->ws_in) (void)hipFree(ctx->ws_in);
+    if (ctx->ws_f6) (void)hipFree(ctx->ws_f6);
     for (void* w : {ctx->ws_rrows, ctx->ws_rkeys, ctx->ws_rtmp}) if (w) (void)hipFree(w);
     if (ctx->h_scratch) (void)hipHostFree(ctx->h_scratch);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
@@ -836,8 +850,32 @@ hipError_t fm::d2h(fm_ctx* ctx, void* dst, const void* src, size_t bytes)
 // ---------------------------------------------------------------------------------------
 // banks
 // ---------------------------------------------------------------------------------------
+// The FP6 plane of an integer-route bank (filter6.hip); without it the accepted-only sweeps of the bank stay on K1.
+static void bank_free6(Bank* b)
+{
+    if (b->rows6) (void)hipFree(b->rows6);
+    if (b->aux6) (void)hipFree(b->aux6);
+    if (b->stat6) (void)hipFree(b->stat6);
+    if (b->max6) (void)hipFree(b->max6);
+    b->rows6 = nullptr; b->aux6 = nullptr; b->stat6 = nullptr; b->max6 = nullptr;
+}
+// Arrays for cap_pad rows and the plane of the current rows, enqueued on `stream`.  Best effort: an allocation that fails
+// leaves the bank without the plane.
+static void bank_plane6(Bank* b, hipStream_t stream)
+{
+    if (b->kind != FM_BANK_I8 || b->dim != kDim || !b->rows8) return;
+    const size_t rows = (size_t)(b->cap_pad > b->n_pad ? b->cap_pad : b->n_pad);
+    if (hipMalloc((void**)&b->rows6, rows * kDim) != hipSuccess || hipMalloc((void**)&b->aux6, rows * 2 * 4) != hipSuccess ||
+        hipMalloc((void**)&b->stat6, rows * 16) != hipSuccess || hipMalloc((void**)&b->max6, 8) != hipSuccess ||
+        launch_prep6(*b, 0, stream) != hipSuccess) {
+        (void)hipGetLastError();
+        bank_free6(b);
+    }
+}
+
 static void bank_free(Bank* b)
 {
+    bank_free6(b);
     if (b->rows8) (void)hipFree(b->rows8);
     if (b->norm) (void)hipFree(b->norm);
     if (b->aux) (void)hipFree(b->aux);
@@ -1013,6 +1051,7 @@ static int bank_create(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f
         }
     }
 #undef BTRY
+    bank_plane6(b, ctx->stream);        // (integer-route banks of dim 128 only)
     *out = b;
     return FM_OK;
 }
@@ -1072,6 +1111,7 @@ extern "C" int fm_bank_append_u8(fm_ctx* ctx, fm_bank* bank, const uint8_t* rows
     HIP_TRY(ctx, hipMemcpyAsync(flags, d_flag, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (flags[1] > bank->usq_max) bank->usq_max = flags[1];
+    bank_free6(bank);       // (the rows between two appends are padding inside the bank: the FP6 plane has no mark for them)
     bank->n = off + n;
     bank->n_pad = ((bank->n + kStageRows - 1) / kStageRows) * kStageRows;
     return FM_OK;
@@ -1397,6 +1437,7 @@ extern "C" int fm_bank_refill_u8_async(fm_ctx* ctx, fm_bank* bank, const uint8_t
     HIP_TRY(ctx, hipGetLastError());
     bank->n = n;
     bank->n_pad = n_pad;
+    if (bank->rows6) HIP_TRY(ctx, launch_prep6(*bank, ctx->tune.refill_grid, ctx->upload));       // (from the new int8 plane, behind it)
     // the largest row norm of the new rows is known on the device only: assume the float32-root guard is needed
     // (an election then launches one extra kernel that finds an empty list, ~5 us beside the next distance kernel)
     bank->usq_max = INT32_MAX / 2;

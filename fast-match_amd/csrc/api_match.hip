@@ -346,6 +346,7 @@ int enqueue_ratio_cut(fm_ctx* ctx, int n, const fm_bank* const* q, double tau, c
 {
     CutArgs a{};
     bool any = false;
+    ctx->cut_tau_ok = tau == tau;
     for (int i = 0; i < n; ++i) {
         const fm_bank* b = q[i];
         const bool ok = ctx->d_cut && b->kind == FM_BANK_I8 && b->sdmax && b->sdmax_rows >= b->n;
@@ -360,6 +361,19 @@ int enqueue_ratio_cut(fm_ctx* ctx, int n, const fm_bank* const* q, double tau, c
     hipLaunchKernelGGL(ratio_cut_kernel, dim3(1), dim3(64), 0, ctx->stream, a);
     HIP_TRY(ctx, hipGetLastError());
     return FM_OK;
+}
+
+const Filter6Ws* filter6_ws(fm_ctx* ctx, int n)
+{
+    if (ctx->tune.fp6_filter == 0 || !ctx->cut_tau_ok || n < 1 || n > kRRBatchMax) return nullptr;
+    const size_t cap = (size_t)ctx->tune.fp6_cap;
+    // (a larger list is a new allocation: hipFree waits for the launches that still read the old one)
+    if (ws_ensure(ctx, &ctx->ws_f6, &ctx->ws_f6_bytes, 256 + (size_t)n * cap * 8) != FM_OK) { (void)hipGetLastError(); return nullptr; }
+    ctx->f6.cnt = (unsigned*)ctx->ws_f6;
+    ctx->f6.rec = (uint2*)((char*)ctx->ws_f6 + 256);
+    ctx->f6.cap = (unsigned)cap;
+    ctx->f6_last_n = n;
+    return &ctx->f6;
 }
 
 struct SelfMerge {
@@ -513,7 +527,8 @@ int sweep_pair_run(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, con
     if (cols.kind == FM_BANK_BIN)
         HIP_TRY(ctx, launch_hamming(cols, red, ktop, ps.ham, (unsigned long long*)ctx->ws_partial, ctx->stream, stage_real));
     else
-        HIP_TRY(ctx, launch_rowreduce(cols, red, ktop, ps.rr, (unsigned long long*)ctx->ws_partial, ps.bound, ctx->tune.glds != 0, ctx->stream, cut));
+        HIP_TRY(ctx, launch_rowreduce(cols, red, ktop, ps.rr, (unsigned long long*)ctx->ws_partial, ps.bound, ctx->tune.glds != 0, ctx->stream, cut,
+                                      (cut && ktop == 1) ? filter6_ws(ctx, 1) : nullptr));
     if (events) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
         ctx->kernel_timed = true;
@@ -1402,7 +1417,7 @@ static int ratio_enqueue(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double
     if (timed_call) HIP_TRY(ctx, hipEventRecord(tm.k0, ctx->stream));
     if (nt > 0)
         HIP_TRY(ctx, launch_rowreduce(*t, *q, 1, pl, (unsigned long long*)sl.ws, coop ? (int*)((char*)sl.ws + L.pbytes) : nullptr,
-                                      (ctx->tune.glds != 0), ctx->stream, cut));
+                                      (ctx->tune.glds != 0), ctx->stream, cut, cut ? filter6_ws(ctx, 1) : nullptr));
     // (untimed calls hand over through the slot's own event, created without timing)
     hipEvent_t handover = timed_call ? tm.k1 : sl.k_done;
     HIP_TRY(ctx, hipEventRecord(handover, ctx->stream));
@@ -2011,7 +2026,7 @@ static int batch_common(fm_ctx* ctx, int32_t n, const fm_bank* const* q, const f
         const unsigned* cut[kRRBatchMax];
         if ((rc = enqueue_ratio_cut(ctx, g, q + i, tau, cut)) != FM_OK) { ctx->timer_pool.push_back(tm); return rc; }
         HIP_TRY(ctx, hipEventRecord(tm.k0, ctx->stream));
-        HIP_TRY(ctx, launch_rowreduce_batch(g, cols, red, pls, part, bnd, ctx->stream, false, cut));
+        HIP_TRY(ctx, launch_rowreduce_batch(g, cols, red, pls, part, bnd, ctx->stream, false, cut, filter6_ws(ctx, g)));
         HIP_TRY(ctx, hipEventRecord(tm.k1, ctx->stream));
         for (int j = 0; j < g; ++j) {
             const int k = i + j;

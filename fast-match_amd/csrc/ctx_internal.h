@@ -39,6 +39,12 @@ struct fm_ctx {
     int* d_counters = nullptr;   // device words of the fp16 filter (layout: fm_internal.h, launch_filter)
     unsigned* d_cut = nullptr;   // [kRRBatchMax] D* of the ratio test per pair of the next K1 launch (ratio_cut.h; on `stream`
                                  // only: ratio_cut_kernel writes it in front of the K1 that reads it); null: no cut
+    // FP6 filter of the accepted-only sweeps (filter6.hip): the record lists and (count, need_k1) words of ONE launch's pairs
+    // -- the filter, its rescoring and the guarded K1 follow each other on `stream`, so consecutive launches share them
+    void*  ws_f6 = nullptr;      size_t ws_f6_bytes = 0;
+    fm::Filter6Ws f6{nullptr, 0, nullptr};
+    bool   cut_tau_ok = false;   // the last enqueue_ratio_cut had a tau that is not NaN
+    int    f6_last_n = 0;        // pairs of the last filter launch (options "fp6_records" / "fp6_fallbacks" read their words)
     int64_t filter_launches = 0;
     unsigned long long* h_scratch = nullptr;   // pinned host words the kernels can write (counts)
     // page-locked staging for results that go to pageable caller memory (d2h below)
@@ -227,6 +233,9 @@ int sweep_pair_run(fm_ctx* ctx, const fm::Bank& cols, const fm::Bank& red, int k
 // D* of the ratio test for the pairs (q[i], -) of the next K1 launch on ctx->stream, into ctx->d_cut (api_match.hip); cut[i] = null
 // for a pair without one.
 int enqueue_ratio_cut(fm_ctx* ctx, int n, const fm_bank* const* q, double tau, const unsigned** cut);
+// The FP6 filter's workspace for the next K1 launch of n pairs on ctx->stream (behind their enqueue_ratio_cut), or null: option
+// "fp6_filter" 0, a NaN tau, no device memory -- K1 then runs as it always has.
+const fm::Filter6Ws* filter6_ws(fm_ctx* ctx, int n);
 // "The results are written": the consumer stream waits for what the context's stream has been given so far (api_match.hip).
 int results_written(fm_ctx* ctx, void* consumer);
 // Election of the cross-check (api_match.hip): per output row the minimum over the split partials, scatter-min into qbest.

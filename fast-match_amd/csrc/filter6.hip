@@ -1,0 +1,369 @@
+// K12 -- the accepted-only sweep as an FP6 matrix-core filter, with exact rescoring of what it keeps.
+//
+// The accepted-only calls hand K1 the ratio test's distance cut D* (ratio_cut.h): only candidates at d2 < D* can reach the
+// output, and on descriptor data those are a few in a million.  K1 still pays the full int8 MFMA rate to find them.  This
+// file sweeps the same (output chunk, split of the streamed bank) grid with K1's staging -- three LDS stage buffers filled by
+// LDS-DMA two stages ahead, the source-side XOR swizzle, the hand-over waits, the s_setprio burst -- but on
+// v_mfma_scale_f32_16x16x128_f8f6f4 with e2m3 operands: one instruction per 16 x 16 x 128 tile instead of two int8 ones,
+// each at half the cycles.  FP6 is lossy, so the sweep is a FILTER with a static per-row threshold that provably keeps
+// every candidate at d2 <= D* - 1 (fp6_filter.h); there are no shared bounds, no atomics on the fast path and no top-K
+// state.  A lane whose 8 candidates of a 32-row unit clear its threshold appends (output row, unit) to the pair's list;
+// rescore6_kernel then computes the exact int32 d2 of each listed row against the unit's 32 streamed rows from the int8
+// plane, as K1 does, and folds (d2 << 32 | row) into slice 0 of the pair's `partial` with a 64-bit atomic minimum -- the key
+// K1 writes and the order the election reduces with (lowest streamed row on ties).  The sweep's workgroups preset their
+// own (split, chunk) piece of `partial` to "none", so the kernels behind it see K1's layout.
+// A list that overflows, or a pair without a finite cut, sets the pair's need_k1 word; the guarded K1 launch behind the
+// rescoring (rowreduce.hip) then redoes such pairs in full.  Nothing waits on the host.
+//
+// Bank plane (Bank::rows6 / aux6 / stat6 / max6, prep6_kernel): the 128 codes of a row as four K-chunks of 32 codes (24
+// bytes) in 32-byte slots -- a row stays 128 bytes, so K1's LDS image and ds_read_b128 pattern carry over; lane (row, g) of a
+// fragment reads slot g, both operands through the same lane -> byte map, so the instruction's k order cancels.
+#include "tile_ops.h"
+#include "fp6_filter.h"
+
+namespace fm {
+
+typedef int   v8i_6 __attribute__((ext_vector_type(8)));
+typedef float v4f_6 __attribute__((ext_vector_type(4)));
+
+#define F6_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
+#define F6_GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
+
+constexpr int kF6NC = 4, kF6NW = 8;                       // blocks of 16 output rows per wave, waves per workgroup (K1's batched shape)
+constexpr int kF6ChunkRows = 16 * kF6NC * kF6NW;          // 512
+constexpr float kF6Never = 3.0e38f;                       // threshold of an output row beyond the bank: no accumulator reaches it
+
+struct F6Params {
+    const uint8_t* col_rows6;
+    const int32_t* col_stat;      // [row][4]: |c|^2, |c^|^2, |c - c^|^2, 0
+    int            ncols;         // real output rows
+    int            ncols_pad;
+    const uint8_t* red_rows6;
+    const float*   red_aux6;      // [stage][256]: accumulator start of the stage's 128 rows, 128 unused words
+    const int32_t* red_max;       // [2]: largest |m|^2, largest |m - m^|^2 of the streamed bank
+    int            nstages, nsplit, nchunks, stages_per_split, ncols_alloc;
+    unsigned long long* partial;  // K1's [nsplit][ncols_alloc] keys
+    const unsigned* cut;          // device word D*
+    uint2*         rec;           // the pair's list: (output row, 32-row unit of the streamed bank)
+    unsigned       cap;
+    unsigned*      cnt;           // [0] records appended (may exceed cap), [1] need_k1
+    // rescoring: the int8 planes
+    const int8_t*  col_rows8;
+    const int32_t* col_norm;
+    const int8_t*  red_rows8;
+    const int32_t* red_norm;
+    int            nred;
+};
+
+struct F6Batch {
+    F6Params p[kRRBatchMax];
+    int      n;
+    int      first_block[kRRBatchMax + 1];
+};
+
+// K1's issue_stage<true, 8>: 128 rows (16 KiB) + 1 KiB of accumulator starts per stage
+__device__ __forceinline__ void f6_issue_stage(const F6Params& p, int stage, char* buf, int wave, int lane)
+{
+    const uint8_t* src_rows = p.red_rows6 + (size_t)stage * kStageRowBytes;
+    const int slot = lane & 7;
+    constexpr int kPieces = 16 / kF6NW;
+#pragma unroll
+    for (int i = 0; i < kPieces; ++i) {
+        const int g   = wave * kPieces + i;
+        const int row = g * 8 + (lane >> 3);
+        const uint8_t* src = src_rows + (unsigned)(row * kDim + 16 * (slot ^ ((row >> 1) & 7)));
+        __builtin_amdgcn_global_load_lds(F6_GLB_PTR(src), F6_LDS_PTR(buf + g * 1024), 16, 0, 0);
+    }
+    if (wave == kF6NW - 1) {
+        const float* src = p.red_aux6 + (size_t)stage * (kStageAuxBytes / 4) + (unsigned)(lane * 4);
+        __builtin_amdgcn_global_load_lds(F6_GLB_PTR(src), F6_LDS_PTR(buf + kStageRowBytes), 16, 0, 0);
+    }
+}
+
+__global__ __launch_bounds__(64 * kF6NW, 4)
+void filter6_kernel(F6Batch b)
+{
+    __shared__ __attribute__((aligned(16))) char smem[3 * kStageBytes];
+    int pair = 0;
+#pragma unroll
+    for (int i = 1; i < kRRBatchMax; ++i) pair += (int)blockIdx.x >= b.first_block[i] ? 1 : 0;
+    const F6Params& p = b.p[pair];
+    const int bid = (int)blockIdx.x - b.first_block[pair];
+
+    const int tid  = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int g    = lane >> 4;
+    const int c16  = lane & 15;
+    const int chunk = bid % p.nchunks, split = bid / p.nchunks;
+    if (split >= p.nsplit) return;
+    const int st0 = split * p.stages_per_split;
+    const int st1 = min(st0 + p.stages_per_split, p.nstages);
+    const int cb  = chunk * kF6ChunkRows + wave * (16 * kF6NC);
+
+    const unsigned dstar = *p.cut;
+    if (dstar == kNoRatioCut) {               // no finite cut (device-side knowledge: the largest self distance): K1 redoes the pair
+        if (tid == 0) p.cnt[1] = 1u;
+        return;
+    }
+    // this workgroup's piece of K1's key array starts empty (the rescoring folds into slice 0 after this kernel)
+    p.partial[(size_t)split * p.ncols_alloc + chunk * kF6ChunkRows + tid] = ~0ull;
+
+    // stationary operand: chunk g (32 codes, 24 of 32 bytes) of this wave's 4 x 16 output rows; thresholds
+    v8i_6 bf[kF6NC];
+    float thr[kF6NC];
+    {
+        const int um = p.red_max[0], em = p.red_max[1];
+        v4i lo[kF6NC], hi[kF6NC], stat[kF6NC];
+#pragma unroll
+        for (int j = 0; j < kF6NC; ++j) {
+            const int n = cb + 16 * j + c16;
+            lo[j] = hi[j] = stat[j] = v4i{0, 0, 0, 0};
+            if (n < p.ncols_pad) {
+                lo[j] = *(const v4i*)(p.col_rows6 + (size_t)n * kDim + 32 * g);
+                hi[j] = *(const v4i*)(p.col_rows6 + (size_t)n * kDim + 32 * g + 16);
+            }
+            if (n < p.ncols) stat[j] = *(const v4i*)(p.col_stat + 4 * (size_t)n);
+        }
+        // (a use of every loaded register in front of the prefetch: the compiler waits for the loads HERE -- with the first
+        // use inside the stage loop its wait is a vmcnt(0) in front of every stage's first MFMA, which drains the LDS-DMA)
+#pragma unroll
+        for (int j = 0; j < kF6NC; ++j) asm volatile("" : "+v"(lo[j]), "+v"(hi[j]), "+v"(stat[j]));
+#pragma unroll
+        for (int j = 0; j < kF6NC; ++j) {
+            const int n = cb + 16 * j + c16;
+            thr[j] = n < p.ncols ? fp6_threshold_acc(fp6_threshold(stat[j][0], stat[j][1], stat[j][2], um, em, dstar)) : kF6Never;
+            bf[j] = v8i_6{lo[j][0], lo[j][1], lo[j][2], lo[j][3], hi[j][0], hi[j][1], 0, 0};
+        }
+    }
+
+    // per-lane LDS offsets of the streamed fragments: the two 16-byte pieces of slot g, swizzled as staged
+    const int sw = (c16 >> 1) & 7;
+    const int aoff0 = c16 * kDim + 16 * ((2 * g) ^ sw), aoff1 = c16 * kDim + 16 * ((2 * g + 1) ^ sw);
+    const int xoff = kStageRowBytes + 16 * g;
+    constexpr int kDmaPerWave = 16 / kF6NW;
+
+    if (st0 < st1) f6_issue_stage(p, st0, smem, wave, lane);
+    if (st0 + 1 < st1) f6_issue_stage(p, st0 + 1, smem + kStageBytes, wave, lane);
+
+    auto stage = [&](auto buf_tag, int st) {
+        constexpr int BUF = decltype(buf_tag)::value;
+        char* buf = smem + BUF * kStageBytes;
+        // stage st's DMA was issued two hand-overs ago; only the DMA of stage st + 1 may still be in flight (a wave that
+        // appended records since has drained its vector memory counter there, which only makes this wait a no-op)
+        if (st + 1 < st1) {
+            if (wave == kF6NW - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kDmaPerWave + 1) : "memory");
+            else                   asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kDmaPerWave) : "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (st + 2 < st1) f6_issue_stage(p, st + 2, smem + ((BUF + 2) % 3) * kStageBytes, wave, lane);
+
+#pragma unroll
+        for (int u = 0; u < kStageRows / kTileRows; ++u) {
+            v4f_6 acc[2][kF6NC];
+            __builtin_amdgcn_s_setprio(2);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const char* rows = buf + (32 * u + 16 * s) * kDim;
+                const v4i a0 = *(const v4i*)(rows + aoff0);
+                const v4i a1 = *(const v4i*)(rows + aoff1);
+                const v4f_6 ci = *(const v4f_6*)(buf + xoff + (32 * u + 16 * s) * 4);
+                const v8i_6 af = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};      // (the last 8 bytes are the slot's padding: not read)
+#pragma unroll
+                for (int j = 0; j < kF6NC; ++j)
+                    acc[s][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf[j], ci, 2, 2, 0, 127, 0, 127);
+            }
+            __builtin_amdgcn_s_setprio(0);
+            float tmax[kF6NC];
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < kF6NC; ++j) {
+                const float m0 = fmaxf(fmaxf(acc[0][j][0], acc[0][j][1]), acc[0][j][2]);
+                const float m1 = fmaxf(fmaxf(acc[0][j][3], acc[1][j][0]), acc[1][j][1]);
+                tmax[j] = fmaxf(fmaxf(fmaxf(acc[1][j][2], acc[1][j][3]), m0), m1);
+                any |= tmax[j] >= thr[j];
+            }
+            if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+                const unsigned unit = (unsigned)(st * (kStageRows / kTileRows) + u);
+#pragma unroll
+                for (int j = 0; j < kF6NC; ++j) {
+                    const bool hit = tmax[j] >= thr[j];
+                    const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+                    if (m == 0ull) continue;
+                    // one atomic per wave: the lowest lane of the ballot reserves the records of all of them
+                    const int first = __builtin_ctzll(m);
+                    unsigned base = 0;
+                    if ((tid & 63) == first) base = atomicAdd(p.cnt, (unsigned)__popcll(m));
+                    base = (unsigned)__builtin_amdgcn_readlane((int)base, first);
+                    const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                    if (hit) {
+                        const unsigned at = base + rank;
+                        if (at < p.cap) p.rec[at] = make_uint2((unsigned)(cb + 16 * j + c16), unit);
+                        else            p.cnt[1] = 1u;
+                    }
+                }
+                // (the hand-over waits count on the LDS-DMA being this wave's newest vector memory operations)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+    };
+
+    for (int st = st0; st < st1; st += 3) {
+        stage(std::integral_constant<int, 0>{}, st);
+        if (st + 1 < st1) stage(std::integral_constant<int, 1>{}, st + 1);
+        if (st + 2 < st1) stage(std::integral_constant<int, 2>{}, st + 2);
+    }
+}
+
+// One wave per record: exact int32 d2 of the output row against the unit's 32 streamed rows (lane l: row l & 31, K-half
+// l >> 5), from the int8 plane and its norms as K1 computes it; the best (d2, row) below D* goes into slice 0 of `partial`.
+__global__ __launch_bounds__(256)
+void rescore6_kernel(F6Batch b)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = (blockIdx.x * 256u + threadIdx.x) >> 6, nwaves = gridDim.x * 4u;
+    for (int pi = 0; pi < b.n; ++pi) {
+        const F6Params& p = b.p[pi];
+        if (p.cnt[1] != 0u) continue;                 // K1 redoes the pair
+        unsigned n = p.cnt[0];
+        n = n < p.cap ? n : p.cap;
+        const unsigned dstar = *p.cut;
+        for (unsigned r = wave; r < n; r += nwaves) {
+            const uint2 rc = p.rec[r];
+            const int c = (int)rc.x;
+            const int m = (int)(rc.y * 32u) + (lane & 31);
+            const int h = lane >> 5;
+            // (m < n_pad of the streamed bank: the unit was staged from it)
+            const int8_t* a = p.col_rows8 + (size_t)c * kDim + 64 * h;
+            const int8_t* y = p.red_rows8 + (size_t)m * kDim + 64 * h;
+            int dot = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const v4i x = *(const v4i*)(a + 16 * w);
+                const v4i z = *(const v4i*)(y + 16 * w);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) dot = __builtin_amdgcn_sdot4(x[k], z[k], dot, false);
+            }
+            dot += __shfl_xor(dot, 32);
+            const unsigned d2 = (unsigned)(p.col_norm[c] + p.red_norm[m] - 2 * dot);
+            unsigned long long key = (m < p.nred && d2 < dstar) ? ((unsigned long long)d2 << 32) | (unsigned)m : ~0ull;
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) {
+                const unsigned long long other = __shfl_xor(key, o);
+                key = other < key ? other : key;
+            }
+            if (lane == 0 && key != ~0ull) atomicMin(p.partial + c, key);
+        }
+    }
+}
+
+// The FP6 plane of the rows [0, n_pad) of an integer-route bank from its int8 plane (rows8 = uint8 ^ 0x80): 4 threads per
+// row, one K-chunk each.  max6 ([2], zeroed by the caller) takes the bank's largest |m|^2 and |m - m^|^2.
+__global__ __launch_bounds__(256)
+void prep6_kernel(const int8_t* __restrict__ rows8, int64_t n, int64_t n_pad, uint8_t* __restrict__ rows6,
+                  float* __restrict__ aux6, int32_t* __restrict__ stat6, int32_t* __restrict__ max6)
+{
+    __shared__ uint8_t code[256];
+    code[threadIdx.x] = (uint8_t)fp6_code((int)threadIdx.x);
+    __syncthreads();
+    const int k = threadIdx.x & 3;
+    int umax = 0, emax = 0;
+    for (int64_t row = (int64_t)blockIdx.x * 64 + (threadIdx.x >> 2); row < n_pad; row += (int64_t)gridDim.x * 64) {
+        unsigned w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int usq = 0, hsq = 0, esq = 0;
+        if (row < n) {
+            const uint4 lo = *(const uint4*)(rows8 + row * kDim + 32 * k), hi = *(const uint4*)(rows8 + row * kDim + 32 * k + 16);
+            const unsigned src[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            unsigned long long bits = 0;       // codes enter at the top of what is left, words leave at the bottom
+            int have = 0, out = 0;
+#pragma unroll
+            for (int i = 0; i < 32; ++i) {
+                const int v = (int)(((src[i >> 2] >> (8 * (i & 3))) & 0xffu) ^ 0x80u);
+                const int cd = code[v], x = fp6_value32(cd);
+                usq += v * v; hsq += x * x; esq += (v - x) * (v - x);
+                bits |= (unsigned long long)cd << have;
+                have += 6;
+                if (have >= 32) { w[out++] = (unsigned)bits; bits >>= 32; have -= 32; }
+            }
+        }
+        *(uint4*)(rows6 + row * kDim + 32 * k)      = make_uint4(w[0], w[1], w[2], w[3]);
+        *(uint4*)(rows6 + row * kDim + 32 * k + 16) = make_uint4(w[4], w[5], w[6], w[7]);
+        usq += __shfl_xor(usq, 1); usq += __shfl_xor(usq, 2);
+        hsq += __shfl_xor(hsq, 1); hsq += __shfl_xor(hsq, 2);
+        esq += __shfl_xor(esq, 1); esq += __shfl_xor(esq, 2);
+        if (k == 0) {
+            *(int4*)(stat6 + 4 * row) = make_int4(usq, hsq, esq, 0);
+            const int64_t st = row / kStageRows, r = row % kStageRows;
+            aux6[st * 256 + r] = row < n ? fp6_acc_init(usq) : kFp6PadInit;
+            aux6[st * 256 + 128 + r] = 0.f;
+        }
+        umax = max(umax, usq);
+        emax = max(emax, esq);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        umax = max(umax, __shfl_xor(umax, o));
+        emax = max(emax, __shfl_xor(emax, o));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (umax > 0) atomicMax(max6, umax);
+        if (emax > 0) atomicMax(max6 + 1, emax);
+    }
+}
+
+hipError_t launch_prep6(const Bank& b, int grid_max, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(b.max6, 0, 8, stream);
+    if (e != hipSuccess) return e;
+    int64_t grid = (b.n_pad + 63) / 64;
+    if (grid_max > 0 && grid > grid_max) grid = grid_max;
+    hipLaunchKernelGGL(prep6_kernel, dim3((unsigned)grid), dim3(256), 0, stream, (const int8_t*)b.rows8, b.n, b.n_pad,
+                       b.rows6, b.aux6, b.stat6, b.max6);
+    return hipGetLastError();
+}
+
+bool filter6_usable(const Bank& cols, const Bank& red)
+{
+    return cols.kind == FM_BANK_I8 && red.kind == FM_BANK_I8 && cols.dim == kDim && red.dim == kDim &&
+           cols.rows6 && red.rows6 && cols.rows8 && red.rows8;
+}
+
+// The filter sweep and the rescoring of n pairs, pair i under plans[i] (K1's batched shape) with the list rec + i * cap and
+// the words cnt + 2 i ([0] count, [1] need_k1, zeroed here).  The guarded K1 launch follows in launch_rowreduce_batch.
+hipError_t launch_filter6(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
+                          unsigned long long* const* partial, const unsigned* const* cut, uint2* rec, unsigned cap,
+                          unsigned* cnt, hipStream_t stream)
+{
+    if (n < 1 || n > kRRBatchMax) return hipErrorInvalidValue;
+    F6Batch b;
+    long long total = 0;
+    for (int i = 0; i < n; ++i) {
+        const RowReducePlan& pl = plans[i];
+        if (pl.nb != kF6NC || pl.nw != kF6NW || !filter6_usable(*cols[i], *red[i]) || !cut[i]) return hipErrorInvalidValue;
+        F6Params& p = b.p[i];
+        p.col_rows6 = cols[i]->rows6;  p.col_stat = cols[i]->stat6;  p.ncols = (int)cols[i]->n;  p.ncols_pad = (int)cols[i]->n_pad;
+        p.red_rows6 = red[i]->rows6;   p.red_aux6 = red[i]->aux6;    p.red_max = red[i]->max6;
+        p.nstages = (int)(red[i]->n_pad / kStageRows);
+        p.nsplit = pl.nsplit;  p.nchunks = pl.nchunks;  p.stages_per_split = pl.stages_per_split;  p.ncols_alloc = pl.ncols_alloc;
+        p.partial = partial[i];  p.cut = cut[i];
+        p.rec = rec + (size_t)i * cap;  p.cap = cap;  p.cnt = cnt + 2 * i;
+        p.col_rows8 = cols[i]->rows8;  p.col_norm = cols[i]->norm;  p.red_rows8 = red[i]->rows8;  p.red_norm = red[i]->norm;
+        p.nred = (int)red[i]->n;
+        b.first_block[i] = (int)total;
+        total += (long long)pl.nchunks * pl.nsplit;
+    }
+    if (total > INT32_MAX) return hipErrorInvalidValue;
+    for (int i = n; i < kRRBatchMax; ++i) b.p[i] = b.p[0];
+    b.first_block[n] = (int)total;
+    for (int i = n + 1; i <= kRRBatchMax; ++i) b.first_block[i] = INT32_MAX;
+    b.n = n;
+    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)n * 8, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(filter6_kernel, dim3((unsigned)total), dim3(64 * kF6NW), 0, stream, b);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(rescore6_kernel, dim3(1024), dim3(256), 0, stream, b);
+    return hipGetLastError();
+}
+
+}  // namespace fm

@@ -58,6 +58,11 @@ struct Bank {
     int      ksteps = 0;
     uint8_t* rowsb  = nullptr; // [n_pad][16 ksteps] packed rows, zero padded
     uint8_t* rows4  = nullptr; // [n_pad][64 ksteps] FP4 image: bit 1 -> +1, bit 0 -> -1, padding 0
+    // FM_BANK_I8 of dim 128, for the FP6 filter of the accepted-only sweep (filter6.hip, fp6_filter.h); all null: K1 only
+    uint8_t* rows6  = nullptr; // [n_pad][128] e2m3 codes of the raw uint8 rows: four K-chunks of 32 codes (24 bytes) in 32-byte slots
+    float*   aux6   = nullptr; // [n_pad / 128][256] accumulator start -floor(|m|^2 / 32) / 64 of a stage's rows (padding -3.4e38), 128 unused words
+    int32_t* stat6  = nullptr; // [n_pad][4] |row|^2, |image|^2, |row - image|^2 (uint8 values), 0
+    int32_t* max6   = nullptr; // [2] device words: the bank's largest |row|^2 and |row - image|^2
 };
 
 // rows rounded up to whole 128-row stages
@@ -139,6 +144,8 @@ struct Tuning {
                                       // 1 an XCD owns output chunks, 2 an XCD owns a contiguous share of the split-major order
     int radius_ws_bytes = 1 << 30;    // K10: device bytes for the candidate keys of one query chunk (radius.hip); a single
                                       // query row whose list needs more still runs, in a chunk of its own
+    int fp6_filter = 1;               // accepted-only sweeps with a ratio cut: 1 = FP6 filter + exact rescoring (filter6.hip), 0 = K1
+    int fp6_cap = 1 << 20;            // ... records per pair of the filter's list; a pair that needs more is redone by K1
     int coll_ws_bytes = 0;            // fm_collection_match_accepted_each / _xcheck1_each: device bytes for the per-(image, query row)
                                       // arrays of one chunk of images (25 / 17 per entry); 0 = a quarter of the free device memory
 };
@@ -165,9 +172,22 @@ struct RowReducePlan {
 RowReducePlan plan_rowreduce(int64_t ncols_pad, int64_t nred_pad, const Tuning& tn);
 // cut (top-1 only): device word D* of the ratio test (ratio_cut.h); candidates at d2 >= D* may be dropped (their rows may
 // then keep the empty key).  Only the accepted-only calls pass one: every reported row there passes the test.
+// f6 (with a cut, top-1): the FP6 filter's workspace; a pair that qualifies (filter6_usable, K1's batched shape) is swept by
+// the filter with exact rescoring and K1 only as its guarded fallback (filter6.hip)
+struct Filter6Ws {
+    uint2*    rec;     // [pairs of a launch][cap] records (output row, 32-row unit of the streamed bank)
+    unsigned  cap;
+    unsigned* cnt;     // [pairs of a launch][2]: records appended (may exceed cap), need_k1
+};
 hipError_t launch_rowreduce(const Bank& cols, const Bank& red, int ktop, const RowReducePlan& plan,
                             unsigned long long* partial, int* bound, bool use_glds, hipStream_t stream,
-                            const unsigned* cut = nullptr);
+                            const unsigned* cut = nullptr, const Filter6Ws* f6 = nullptr);
+// ---- K12: FP6 filter of the accepted-only sweep (filter6.hip) ----
+bool filter6_usable(const Bank& cols, const Bank& red);     // both banks carry the FP6 plane
+hipError_t launch_prep6(const Bank& b, int grid_max, hipStream_t stream);     // the plane of rows [0, n_pad) from rows8 (grid_max 0: no limit)
+hipError_t launch_filter6(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
+                          unsigned long long* const* partial, const unsigned* const* cut, uint2* rec, unsigned cap,
+                          unsigned* cnt, hipStream_t stream);
 int rowreduce_grid(const RowReducePlan& plan);      // workgroups per bank pair (padded under orders 1 and 2)
 // fm_self_dist: top-1 of every row over the OTHER rows of its own bank (masked diagonal)
 RowReducePlan plan_rowreduce_self(int64_t n_pad, const Tuning& tn);
@@ -265,7 +285,8 @@ hipError_t launch_rounds_f32(const RoundF32& rf, const double* q_selfdist, const
 constexpr int kRRBatchMax = 16;           // bank pairs per batched row-reduce launch
 hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
                                   unsigned long long* const* partial, int* const* bound, hipStream_t stream, bool self = false,
-                                  const unsigned* const* cut = nullptr);      // (cut[i]: as launch_rowreduce's, per pair; not for self)
+                                  const unsigned* const* cut = nullptr,       // (cut[i]: as launch_rowreduce's, per pair; not for self)
+                                  const Filter6Ws* f6 = nullptr);             // (with a cut for every pair: launch_rowreduce's)
 // top-2 form of the batched launch (fm_collection_knn2_each): bound[i] = pair i's two bound arrays ([2 * ncols_alloc]) or null
 hipError_t launch_rowreduce_batch2(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
                                    unsigned long long* const* partial, int* const* bound, hipStream_t stream);

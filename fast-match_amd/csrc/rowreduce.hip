@@ -839,6 +839,24 @@ void rowreduce_batch_kernel(RRBatch b)
     rowreduce_body<NC, KTOP, true, NW, NBUF, PRIO, SELF>(p, (int)blockIdx.x - b.first_block[pair], smem);
 }
 
+// K1 as the FP6 filter's fallback (filter6.hip): a fixed grid of at most 512 workgroups walks the block indices of the pairs
+// whose need_k1 word (need[2 pair + 1]) the filter or its rescoring set -- a list that overflowed, a pair without a finite
+// cut -- through the unchanged body.  A workgroup that finds no word set returns at once.
+__global__ __launch_bounds__(64 * 8, 4)
+void rowreduce_guard_kernel(RRBatch b, const unsigned* __restrict__ need)
+{
+    __shared__ __attribute__((aligned(16))) char smem[3 * kStageBytes];
+    for (int pair = 0; pair < b.n; ++pair) {
+        if (need[2 * pair + 1] == 0u) continue;
+        const RRParams p = b.p[pair];
+        const int nblk = b.first_block[pair + 1] - b.first_block[pair];
+        for (int bid = (int)blockIdx.x; bid < nblk; bid += (int)gridDim.x) {
+            rowreduce_body<4, 1, true, 8, 3, 1>(p, bid, smem);
+            __syncthreads();          // (every wave is done with the stage buffers, nothing of this round is in flight)
+        }
+    }
+}
+
 // The triangular self sweep (see kTriNever above): one bank, or up to kRRBatchMax banks of one padded size.
 template <int PRIO>
 __global__ __launch_bounds__(64 * 8, 4)
@@ -1055,7 +1073,7 @@ RowReducePlan plan_rowreduce_self(int64_t n_pad, const Tuning& tn)
 // batched kernel is built for: 4 blocks per wave, 8 waves).
 hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
                                   unsigned long long* const* partial, int* const* bound, hipStream_t stream, bool self,
-                                  const unsigned* const* cut)
+                                  const unsigned* const* cut, const Filter6Ws* f6)
 {
     if (n < 1 || n > kRRBatchMax) return hipErrorInvalidValue;
     RRBatch b;
@@ -1072,6 +1090,16 @@ hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* co
     b.first_block[n] = (int)total;
     for (int i = n + 1; i <= kRRBatchMax; ++i) b.first_block[i] = INT32_MAX;
     b.n = n;
+    // Accepted-only sweeps (every pair carries a cut) of banks with the FP6 plane: the filter sweep and its exact rescoring
+    // write K1's keys (filter6.hip); K1 itself follows as a guarded launch that redoes the pairs the filter gave up on.
+    bool filter = f6 && f6->rec && f6->cnt && f6->cap > 0 && cut && !self;
+    for (int i = 0; i < n && filter; ++i) filter = cut[i] != nullptr && filter6_usable(*cols[i], *red[i]);
+    if (filter) {
+        const hipError_t e = launch_filter6(n, cols, red, plans, partial, cut, f6->rec, f6->cap, f6->cnt, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(rowreduce_guard_kernel, dim3((unsigned)(total < 512 ? total : 512)), dim3(64 * 8), 0, stream, b, (const unsigned*)f6->cnt);
+        return hipGetLastError();
+    }
     if (self) hipLaunchKernelGGL((rowreduce_batch_kernel<4, 1, 8, 3, 1, true>), dim3((unsigned)total), dim3(64 * 8), 0, stream, b);
     else      hipLaunchKernelGGL((rowreduce_batch_kernel<4, 1, 8, 3, 1>), dim3((unsigned)total), dim3(64 * 8), 0, stream, b);
     return hipGetLastError();
@@ -1113,8 +1141,15 @@ hipError_t launch_rowreduce_self(const Bank& bank, const RowReducePlan& plan, un
 }
 
 hipError_t launch_rowreduce(const Bank& cols, const Bank& red, int ktop, const RowReducePlan& plan,
-                            unsigned long long* partial, int* bound, bool use_glds, hipStream_t stream, const unsigned* cut)
+                            unsigned long long* partial, int* bound, bool use_glds, hipStream_t stream, const unsigned* cut,
+                            const Filter6Ws* f6)
 {
+    // (a pair the FP6 filter can take goes through the batched form, a launch of one pair: the same kernel body)
+    if (f6 && ktop == 1 && cut && use_glds && plan.nb == 4 && plan.nw == 8 && plan.order == 0 && nbuf_choice(1, plan.nbuf) == 3 &&
+        filter6_usable(cols, red)) {
+        const Bank* c1 = &cols; const Bank* r1 = &red;
+        return launch_rowreduce_batch(1, &c1, &r1, &plan, &partial, &bound, stream, false, &cut, f6);
+    }
     RRParams p;
     fill_params(p, cols, red, plan, partial, bound);
     if (ktop == 1) p.cut = cut;

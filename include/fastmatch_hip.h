@@ -115,6 +115,13 @@ int  fm_ctx_destroy(fm_ctx* ctx);
  *   "expand_grow"  0..4   K7: how often a run that fills its pending stack / result list / hash table is
  *                         repeated in a run state four times as large (2; r05: counted per array)
  *   "expand_prof"  0|1    K7: per-phase timers of the first pair of a launch on stderr
+ *   "fp6_filter"   0|1    accepted-match calls (fm_match_accepted*, integer-route banks of dim 128 with self distances): 1 = the
+ *                         sweep runs as an FP6 matrix-core filter below the ratio test's distance cut, with exact int8
+ *                         rescoring of what it keeps and K1 as the fallback (1); 0 = K1 always.  Results never differ.
+ *   "fp6_cap"      1..2^24  ... records per image pair the filter may keep (2^20, 8 bytes each); a pair that needs more is
+ *                         redone by K1 on the device, without a host wait
+ *   "fp6_records", "fp6_fallbacks"  COUNTERS, get only (waits for the context's stream): records appended and pairs redone
+ *                         by K1 in the last filter launch, summed over its pairs
  *   "radius_ws_bytes" 65536..2^31-1  fm_radius_match: device bytes for the candidates of one chunk of query rows (2^30;
  *                         24 bytes per candidate, 28 in the collection forms); a row whose own list needs more runs in a
  *                         chunk of its own
