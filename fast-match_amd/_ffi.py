@@ -171,6 +171,18 @@ SYMBOLS = {
     "fm_collection_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
     "fm_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
     "fm_collection_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    # K13: knnMatch under a mask (csrc/masked.hip)
+    "fm_mask_create": (_INT, [_P, _I64, _I64, ctypes.POINTER(_P)]),
+    "fm_mask_create_coll": (_INT, [_P, _I64, _P, ctypes.POINTER(_P)]),
+    "fm_mask_set_u8": (_INT, [_P, _P, _I32, _P, _I64]),
+    "fm_mask_set_dev": (_INT, [_P, _P, _I32, _P, _I64, _P]),
+    "fm_mask_set_all": (_INT, [_P, _P, _I32, _I32]),
+    "fm_mask_destroy": (_INT, [_P, _P]),
+    "fm_mask_info": (_INT, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I32), ctypes.POINTER(_I64)]),
+    "fm_knn_masked": (_INT, [_P, _P, _P, _P, _I32, _P, _P]),
+    "fm_knn_masked_dev": (_INT, [_P, _P, _P, _P, _I32, _P, _P, _P]),
+    "fm_collection_knn_masked": (_INT, [_P, _P, _P, _P, _I32, _P, _P, _P]),
+    "fm_collection_knn_masked_dev": (_INT, [_P, _P, _P, _P, _I32, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -370,6 +382,69 @@ def collection_locate(first_row, g):
     return img, loc
 
 
+class Mask(object):
+    """A match mask (fm_mask): a device-resident bit matrix over (query row, train row) -- cv2's ``mask`` argument of
+    ``knnMatch`` for a bank pair (``Context.mask(nq, nt)``), or one matrix per image of a train collection
+    (``Collection.mask(nq)``: cv2's ``masks``).  New masks forbid everything.  A context manager; closes with its context."""
+
+    def __init__(self, ctx, handle, coll=None):
+        self.ctx, self.handle, self.coll = ctx, handle, coll
+        self.nq, self.nt, self.n_images, self.nbytes = self.info()
+        ctx._children.add(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def info(self):
+        """(nq, real train rows, images -- 0 for a pair mask --, bytes of the bit matrix)"""
+        nq, nt, ni, nb = _I64(), _I64(), _I32(), _I64()
+        self.ctx._check(self.ctx.lib.fm_mask_info(self.handle, ctypes.byref(nq), ctypes.byref(nt), ctypes.byref(ni), ctypes.byref(nb)))
+        return int(nq.value), int(nt.value), int(ni.value), int(nb.value)
+
+    def set(self, rows, img=0):
+        """``fm_mask_set_u8``: ``rows`` = [nq, rows of image ``img``] uint8 / bool, nonzero = the pair may be matched."""
+        a = np.asarray(rows)
+        if a.dtype == np.bool_:
+            a = a.view(np.uint8)
+        if a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError("a mask is a 2-D [nq, nt] uint8 or bool array, got %s %s" % (a.dtype, a.shape))
+        if a.shape[0] != self.nq:
+            raise ValueError("the mask has %d rows, the Mask was made for %d query rows" % (a.shape[0], self.nq))
+        if a.shape[1] and a.strides[1] != 1 or (a.shape[0] > 1 and a.strides[0] < a.shape[1]):
+            a = np.ascontiguousarray(a)
+        pitch = a.strides[0] if a.shape[0] > 1 and a.shape[1] else 0
+        self.ctx._check(self.ctx.lib.fm_mask_set_u8(self.ctx.handle, self.handle, int(img), _ptr(a) if a.size else None, int(pitch)))
+        return self
+
+    def set_dev(self, ptr, img=0, pitch=0, stream=None):
+        """``fm_mask_set_dev``: the same from device memory (``ptr`` = device address of [nq, rows of the image] bytes, ``pitch``
+        bytes between rows, 0 = dense; a ``torch.bool`` tensor is one byte per element); ``stream`` as in
+        ``Context.bank_from_device``.  On return the source may be overwritten."""
+        self.ctx._check(self.ctx.lib.fm_mask_set_dev(self.ctx.handle, self.handle, int(img), _P(int(ptr)) if ptr else None, int(pitch),
+                                                     _stream_arg(stream)))
+        return self
+
+    def set_all(self, value=True, img=0):
+        """``fm_mask_set_all``: every row of image ``img`` permitted (or forbidden) for every query row."""
+        self.ctx._check(self.ctx.lib.fm_mask_set_all(self.ctx.handle, self.handle, int(img), 1 if value else 0))
+        return self
+
+    def close(self):
+        if self.handle is not None and self.ctx.handle is not None:
+            self.ctx.lib.fm_mask_destroy(self.ctx.handle, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Collection(object):
     """Train collection (fm_collection): an ordered list of images resident on the device in one set of arrays --
     ``cv2.BFMatcher.add`` / ``train`` / ``clear``.  A context manager; closes with its context."""
@@ -509,6 +584,31 @@ class Collection(object):
         dist = np.empty((q.n, max(k, 0)), np.float32)
         self.ctx._check(self.ctx.lib.fm_collection_knn(self.ctx.handle, self.handle, q.handle, k, _ptr(img), _ptr(idx), _ptr(dist)))
         return img, idx, dist
+
+    def mask(self, nq):
+        """An all-forbidding ``Mask`` for ``nq`` query rows laid out on this collection's images as they are now
+        (``fm_mask_create_coll``); a later ``add`` / ``clear`` makes it stale."""
+        h = _P()
+        self.ctx._check(self.ctx.lib.fm_mask_create_coll(self.ctx.handle, int(nq), self.handle, ctypes.byref(h)))
+        return Mask(self.ctx, h, self)
+
+    def knn_masked(self, q, mask, k):
+        """``fm_collection_knn_masked``: ``knn`` over the train rows ``mask`` (``Collection.mask``) permits per query row."""
+        k = int(k)
+        img = np.empty((q.n, max(k, 0)), np.int32)
+        idx = np.empty((q.n, max(k, 0)), np.int32)
+        dist = np.empty((q.n, max(k, 0)), np.float32)
+        self.ctx._check(self.ctx.lib.fm_collection_knn_masked(self.ctx.handle, self.handle, q.handle, mask.handle if mask is not None else None,
+                                                              k, _ptr(img), _ptr(idx), _ptr(dist)))
+        return img, idx, dist
+
+    def knn_masked_dev(self, q, mask, k, img_ptr, idx_ptr, dist_ptr, consumer_stream=None):
+        """``knn_masked`` with the lists left on the device (``fm_collection_knn_masked_dev``); pointers and ``consumer_stream``
+        as in ``knn_dev``."""
+        self.ctx._check(self.ctx.lib.fm_collection_knn_masked_dev(
+            self.ctx.handle, self.handle, q.handle, mask.handle if mask is not None else None, int(k),
+            _P(int(img_ptr)) if img_ptr else None, _P(int(idx_ptr)) if idx_ptr else None, _P(int(dist_ptr)) if dist_ptr else None,
+            _stream_arg(consumer_stream)))
 
     def knn2_ratio(self, q, tau):
         """``fm_collection_knn2_ratio``: (qidx, img, tidx, dist, ratio) of the accepted matches, ascending query index."""
@@ -842,7 +942,7 @@ class Context(object):
         """Per-context tuning / batch shape (fm_ctx_set_option): "batch_group", "batch_tail", "nsplit", "nb",
         "nw", "nbuf", "prio", "glds", "coop", "f32_filter", "f32_nw", "f32_nsplit", "f32_fused", "f32_lpc", "f32_bound_every",
         "async_time_every", "k1_order", "bound_every", "self_tri", "tri_stages", "refill_grid", "expand_big", "expand_huge", "expand_delegate", "expand_grow", "expand_prof",
-        "radius_ws_bytes", "coll_ws_bytes", "fp6_filter", "fp6_cap".  Results never depend on them."""
+        "radius_ws_bytes", "coll_ws_bytes", "fp6_filter", "fp6_cap", "masked_mfma", "mask_pack_words".  Results never depend on them."""
         self._check(self.lib.fm_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def get_option(self, name):
@@ -1006,6 +1106,28 @@ class Context(object):
         dist = np.empty((q.n, int(k)), dtype=np.float32)
         self._check(self.lib.fm_knn(self.handle, q.handle, t.handle, int(k), _ptr(idx), _ptr(dist)))
         return idx, dist
+
+    def mask(self, nq, nt):
+        """An all-forbidding ``Mask`` for a bank pair of ``nq`` query and ``nt`` train rows (``fm_mask_create``)."""
+        h = _P()
+        self._check(self.lib.fm_mask_create(self.handle, int(nq), int(nt), ctypes.byref(h)))
+        return Mask(self, h)
+
+    def knn_masked(self, q, t, mask, k):
+        """``fm_knn_masked``: ``knn`` over the train rows ``mask`` (``Context.mask``) permits per query row -- cv2's
+        ``knnMatch(q, t, k, mask)``; -1 / inf where fewer than k rows are permitted."""
+        idx = np.empty((q.n, max(int(k), 0)), dtype=np.int32)
+        dist = np.empty((q.n, max(int(k), 0)), dtype=np.float32)
+        self._check(self.lib.fm_knn_masked(self.handle, q.handle, t.handle, mask.handle if mask is not None else None, int(k),
+                                           _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def knn_masked_dev(self, q, t, mask, k, idx_ptr, dist_ptr, consumer_stream=None):
+        """``knn_masked`` with the lists left on the device (``fm_knn_masked_dev``); pointers and ``consumer_stream`` as in
+        ``knn_dev``."""
+        self._check(self.lib.fm_knn_masked_dev(self.handle, q.handle, t.handle, mask.handle if mask is not None else None, int(k),
+                                               _P(int(idx_ptr)) if idx_ptr else None, _P(int(dist_ptr)) if dist_ptr else None,
+                                               _stream_arg(consumer_stream)))
 
     def radius_match(self, q, t, r):
         """``fm_radius_match``: every train row with distance < r per query row -- cv2's radiusMatch with compactResult

@@ -21,6 +21,7 @@
 #include "coll_tab.h"
 
 #include <algorithm>
+#include <atomic>
 
 using namespace fm;
 
@@ -56,11 +57,18 @@ struct fm_collection {
     int32_t* d_tab = nullptr;             // stage image [nstages] | stage real rows [nstages] | first row [n_images]
     size_t tab_bytes = 0;
     bool dirty = true;
+    uint64_t gen = 0;                     // changes with every add and clear, unique across collections (fm_mask_create_coll remembers it)
     int64_t nstages() const { return used / kStageRows; }
     const int32_t* st_img() const { return d_tab; }
     const int32_t* st_real() const { return d_tab + nstages(); }
     const int32_t* img_phys() const { return d_tab + 2 * nstages(); }
 };
+
+static uint64_t coll_next_gen()
+{
+    static std::atomic<uint64_t> g{0};
+    return ++g;
+}
 
 // ---------------------------------------------------------------------------------------
 // kernels
@@ -329,6 +337,7 @@ static void coll_reset(fm_collection* c)
     c->stack.n = 0; c->stack.n_pad = 0; c->stack.usq_max = 0; c->stack.dim = 0;
     c->stack.nm_max = 0.f; c->stack.kscale = 0; c->stack.filt_ok = false;
     c->dirty = true;
+    c->gen = coll_next_gen();
 }
 
 // Arrays of `kind` for `cap` rows into *nb (its other fields untouched); the first `copy` rows of `from`'s arrays are copied on
@@ -398,6 +407,7 @@ extern "C" int fm_collection_create(fm_ctx* ctx, fm_collection** out)
     if (!c) return fail(ctx, FM_ENOMEM, "fm_collection_create: out of host memory");
     c->ctx = ctx;
     c->stack.kind = FM_BANK_I8;
+    c->gen = coll_next_gen();
     *out = c;
     return FM_OK;
 }
@@ -571,6 +581,7 @@ static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, 
     c->stack.dim = c->dim;
     c->stack.n = c->stack.n_pad = c->used;
     c->dirty = true;
+    c->gen = coll_next_gen();
     if (img_idx) *img_idx = (int32_t)(c->rows.size() - 1);
     return FM_OK;
 }
@@ -908,6 +919,104 @@ extern "C" int fm_collection_knn_dev(fm_ctx* ctx, fm_collection* c, const fm_ban
                            CollTab{c->st_img(), c->st_real(), c->img_phys()}, nq * k, d_img, d_idx, d_dist);
         HIP_TRY(ctx, hipGetLastError());
     }
+    return results_written(ctx, consumer_stream);
+}
+
+// ---- K13: knnMatch(q, k, masks = [...]) (masked.hip) ---------------------------------------------------------------------------
+// The train operand is the stack viewed as one bank; the mask lies on the physical stack and forbids the padding rows behind
+// every image itself, so the masked kernels take no real-row table.  The lists come back as physical rows and the lookup
+// pass of the k >= 3 path (coll_translate_kernel) turns the nq * k entries into (image, row) for every k.
+extern "C" int fm_mask_create_coll(fm_ctx* ctx, int64_t nq, fm_collection* c, fm_mask** mask)
+{
+    int rc = coll_check(ctx, c, "fm_mask_create_coll");
+    if (rc != FM_OK) return rc;
+    if (!mask) return fail(ctx, FM_EINVAL, "fm_mask_create_coll: mask out pointer is NULL");
+    *mask = nullptr;
+    if (nq < 0) return fail(ctx, FM_EINVAL, "fm_mask_create_coll: bad nq");
+    if (nq > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, "fm_mask_create_coll: more than 2^31 - 1 query rows");
+    if ((rc = mask_alloc(ctx, nq, c->rows, c->phys, c->used, "fm_mask_create_coll", mask)) != FM_OK) return rc;
+    (*mask)->coll = c;
+    (*mask)->coll_gen = c->gen;
+    return FM_OK;
+}
+
+// Steps 1 .. 4 of the collection forms' error order (the header).
+static int coll_masked_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const fm_mask* m, int32_t k, const char* who)
+{
+    if (ctx && c && q && !m) return fail(ctx, FM_EINVAL, std::string(who) + ": mask is NULL");
+    int rc = coll_query_check(ctx, c, q, who);
+    if (rc != FM_OK) return rc;
+    if (k < 1) return fail(ctx, FM_EINVAL, std::string(who) + ": k must be at least 1");
+    if (k > 8) return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": k above 8 is not built");
+    if ((rc = mask_check(ctx, m, who)) != FM_OK) return rc;
+    if (!m->coll) return fail(ctx, FM_EINVAL, std::string(who) + ": the mask was made for a bank pair (fm_mask_create); a collection takes fm_mask_create_coll's");
+    if (m->coll != c) return fail(ctx, FM_EINVAL, std::string(who) + ": the mask was made for another collection");
+    if (m->coll_gen != c->gen)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the collection has changed (add or clear) since fm_mask_create_coll: the mask had " +
+                                    std::to_string(m->rows.size()) + " images and " + std::to_string(m->nt) + " rows");
+    if (m->nq != q->n)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the mask has " + std::to_string(m->nq) + " query rows, the query bank " + std::to_string(q->n));
+    return FM_OK;
+}
+
+// The masked lists of q against the stack into d_img / d_idx / d_dist [nq][k] (device memory) on the context's stream.
+static int coll_knn_masked_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const fm_mask* m, int k, int32_t* d_img, int32_t* d_idx, float* d_dist)
+{
+    const int64_t nq = q->n;
+    if (c->total == 0) {
+        HIP_TRY(ctx, hipMemsetAsync(d_img, 0xff, (size_t)nq * k * 4, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_idx, 0xff, (size_t)nq * k * 4, ctx->stream));
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)d_dist, 0x7f800000, (size_t)nq * k, ctx->stream));
+        return FM_OK;
+    }
+    int rc = knn_masked_device(ctx, *q, c->stack, m, k, d_idx, d_dist);
+    if (rc != FM_OK) return rc;
+    hipLaunchKernelGGL(coll_translate_kernel, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, ctx->stream,
+                       CollTab{c->st_img(), c->st_real(), c->img_phys()}, nq * k, d_img, d_idx, d_dist);
+    HIP_TRY(ctx, hipGetLastError());
+    return FM_OK;
+}
+
+extern "C" int fm_collection_knn_masked(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const fm_mask* mask, int32_t k,
+                                        int32_t* img, int32_t* idx, float* dist)
+{
+    int rc = coll_masked_check(ctx, c, q, mask, k, "fm_collection_knn_masked");
+    if (rc != FM_OK) return rc;
+    const int64_t nq = q->n;
+    if (nq > 0 && (!img || !idx || !dist)) return fail(ctx, FM_EINVAL, "fm_collection_knn_masked: output pointer is NULL");
+    if (nq == 0) return FM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t ob = align256((size_t)nq * k * 4);
+    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, 3 * ob + 64)) != FM_OK) return rc;
+    char* b = (char*)ctx->ws_out;
+    int32_t* d_img = (int32_t*)b; int32_t* d_idx = (int32_t*)(b + ob); float* d_dist = (float*)(b + 2 * ob);
+    CallScope cs(ctx);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+    if ((rc = coll_knn_masked_device(ctx, c, q, mask, k, d_img, d_idx, d_dist)) != FM_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+    ctx->kernel_timed = true;
+    ctx->pending_pairs += nq * c->total;
+    ctx->pending_bytes += bank_bytes(q) + bank_bytes(static_cast<const fm_bank*>(&c->stack));
+    HIP_TRY(ctx, d2h(ctx, img, d_img, (size_t)nq * k * 4));
+    HIP_TRY(ctx, d2h(ctx, idx, d_idx, (size_t)nq * k * 4));
+    HIP_TRY(ctx, d2h(ctx, dist, d_dist, (size_t)nq * k * 4));
+    return cs.finish();
+}
+
+extern "C" int fm_collection_knn_masked_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const fm_mask* mask, int32_t k,
+                                            int32_t* d_img, int32_t* d_idx, float* d_dist, void* consumer_stream)
+{
+    const char* who = "fm_collection_knn_masked_dev";
+    int rc = coll_masked_check(ctx, c, q, mask, k, who);
+    if (rc != FM_OK) return rc;
+    const int64_t nq = q->n;
+    if (nq == 0) return FM_OK;
+    if (!d_img || !d_idx || !d_dist) return fail(ctx, FM_EINVAL, "fm_collection_knn_masked_dev: output pointer is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_ptr(ctx, d_img, who, "d_img")) != FM_OK || (rc = check_device_ptr(ctx, d_idx, who, "d_idx")) != FM_OK ||
+        (rc = check_device_ptr(ctx, d_dist, who, "d_dist")) != FM_OK) return rc;
+    if ((rc = wait_for_stream(ctx, consumer_stream)) != FM_OK) return rc;
+    if ((rc = coll_knn_masked_device(ctx, c, q, mask, k, d_img, d_idx, d_dist)) != FM_OK) return rc;
     return results_written(ctx, consumer_stream);
 }
 

@@ -463,6 +463,7 @@ static const OptionDef kOptions[] = {
     {"delegated_rounds", &Tuning::delegated_rounds, 0, 0, nullptr},       // a counter: set to 0, read
     {"radius_ws_bytes", &Tuning::radius_ws_bytes, 1 << 16, 0x7fffffff, nullptr},
     {"coll_ws_bytes", &Tuning::coll_ws_bytes, 0, 0x7fffffff, nullptr},
+    {"masked_mfma", &Tuning::masked_mfma, 0, 1, nullptr}, {"mask_pack_words", &Tuning::mask_pack_words, 64, (1 << 26) - 4, nullptr},
     {"fp6_filter", &Tuning::fp6_filter, 0, 1, nullptr}, {"fp6_cap", &Tuning::fp6_cap, 1, 1 << 24, nullptr},
 };
 

@@ -333,6 +333,34 @@ int mutual_reverse_device(fm_ctx* ctx, const Bank& t, const int32_t* cand_rows, 
                           int32_t** r_idx, float** r_dist);
 }
 
+// ---- K13: k-NN under a mask (masked.hip; the collection forms in api_collection.hip) -----------------------------------------
+// A mask is a device-resident bit matrix [nq][words] of 64-bit words over the PADDED rows of its train operand: a bank
+// (one "image" at row 0) or a collection's physical stack (every image on its own 128-row stages, so an image's bits are
+// whole words).  Bit b of word w of row i set = (query row i, train row 64 w + b) is permitted; the bits of padding rows
+// are 0 always, which is why no masked kernel needs the per-stage real-row table.
+struct fm_collection;
+struct fm_mask {
+    fm_ctx* ctx = nullptr;
+    int64_t nq = 0, nt = 0;                 // query rows; REAL train rows (a collection: of all images)
+    int64_t n_pad = 0, words = 0;           // padded train rows (a collection: the stack's used rows), n_pad / 64
+    unsigned long long* bits = nullptr;
+    size_t bytes = 0;
+    const fm_collection* coll = nullptr;    // a collection's mask: the collection and its state at creation
+    uint64_t coll_gen = 0;
+    std::vector<int64_t> rows, phys;        // per image: real rows, first padded row
+};
+namespace fm {
+// A zeroed mask for images of `rows` real rows at the padded rows `phys` (multiples of 128) of an operand of n_pad rows.
+int mask_alloc(fm_ctx* ctx, int64_t nq, const std::vector<int64_t>& rows, const std::vector<int64_t>& phys, int64_t n_pad,
+               const char* who, fm_mask** out);
+// The masked k-NN lists of q over t (a bank, or a collection's stack) on the context's stream into d_idx / d_dist [nq][k]
+// (rows of t; device memory): the masked MFMA sweep (integer route, k <= 2, option "masked_mfma") or the masked
+// vector-ALU lists, then the merge.  q.n > 0; arguments checked by the entry points.
+int knn_masked_device(fm_ctx* ctx, const Bank& q, const Bank& t, const fm_mask* m, int k, int32_t* d_idx, float* d_dist);
+// The geometry / ownership checks of the masked calls that do not depend on the train operand's type.
+int mask_check(fm_ctx* ctx, const fm_mask* m, const char* who);
+}
+
 // Brackets one API call: events for total time, stats accounting after the final sync.
 struct CallScope {
     fm_ctx* ctx;

@@ -146,6 +146,8 @@ struct Tuning {
                                       // query row whose list needs more still runs, in a chunk of its own
     int fp6_filter = 1;               // accepted-only sweeps with a ratio cut: 1 = FP6 filter + exact rescoring (filter6.hip), 0 = K1
     int fp6_cap = 1 << 20;            // ... records per pair of the filter's list; a pair that needs more is redone by K1
+    int masked_mfma = 1;              // K13: fm_knn_masked on the integer route with k <= 2: 1 = the masked MFMA sweep, 0 = the masked K9 kernel
+    int mask_pack_words = (1 << 26) - 4;  // K13: mask words one launch of the pack / fill kernels covers (64 work-items per word: < 2^32 per launch)
     int coll_ws_bytes = 0;            // fm_collection_match_accepted_each / _xcheck1_each: device bytes for the per-(image, query row)
                                       // arrays of one chunk of images (25 / 17 per entry); 0 = a quarter of the free device memory
 };
@@ -250,6 +252,9 @@ hipError_t launch_filter_tri(const Bank& bank, const TriPlan& plan, int bound_ev
 size_t knnk_partial_bytes(int64_t nq, int64_t nt, int k);
 hipError_t launch_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream);
 int knnk_splits(int64_t nq, int64_t nt);
+// K9 under a bit mask (K13): mask[q][mwords] 64-bit words, bit b of word w = train row 64 w + b is permitted; 1 <= k <= 8
+hipError_t launch_knnk_masked(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist,
+                              hipStream_t stream, const unsigned long long* mask, int64_t mwords);
 // merge of the per-split lists (keys: float32 distance bits << 32 | row) into idx / dist [nq][k]
 hipError_t launch_knnk_merge(const unsigned long long* partial, int nsplit, int nq, int k, int32_t* d_idx, float* d_dist, hipStream_t stream);
 
@@ -268,8 +273,16 @@ hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const Ham
 // (b.n_pad, b.ksteps, b.rowsb, b.rows4 set by the caller)
 hipError_t launch_hamming_prep(const uint8_t* d_src, int64_t n, int bytes, const Bank& b, hipStream_t stream, int64_t pitch = 0);
 // k-NN lists for 1 <= k <= 8 on the vector ALUs (partial: knnk_partial_bytes)
+// mask (K13): the bit mask of fm_knn_masked, [q.n][mwords] words, or null
 hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream,
-                               const int* stage_real = nullptr);
+                               const int* stage_real = nullptr, const unsigned long long* mask = nullptr, int64_t mwords = 0);
+
+// ---- K13: k-NN under a bit mask (masked.hip) ------------------------------------------------------------------------------
+// Integer route, k = 1 or 2, on the matrix cores: the masked top-k of every row of q over the rows of t (t may be a
+// collection's stack: the mask's bits of padding rows are 0), merged into d_idx / d_dist [q.n][k].
+size_t masked_i8_partial_bytes(int64_t nq, int64_t nt, int k);
+hipError_t launch_masked_i8(const Bank& q, const Bank& t, int k, const unsigned long long* mask, int64_t mwords,
+                            unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream);
 
 // ---- K4: one workgroup per expansion round (rounds.hip) --------------------------------
 hipError_t launch_rounds(const Bank& q, const Bank& t, const int32_t* d_q_rows, const int64_t* d_q_off,

@@ -266,10 +266,12 @@ hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const Ham
 // ---- k = 3 .. 8 on the vector ALUs ------------------------------------------------------------------------------------------
 constexpr int kHamKnnStage = 64;          // train rows per LDS stage (64 x at most 64 packed bytes)
 
-template <int K, int KS>
+// MASKED (K13, masked.hip): the thread's word of the bit mask per 64-row stage, one bit per candidate (as knn_k.hip's kernels).
+template <int K, int KS, bool MASKED = false>
 __global__ __launch_bounds__(256)
 void ham_knnk_kernel(const uint8_t* __restrict__ qrows, int nq, const uint8_t* __restrict__ trows, int nt, int rows_per_split,
-                     unsigned long long* __restrict__ partial, const int* __restrict__ stage_real = nullptr)
+                     unsigned long long* __restrict__ partial, const int* __restrict__ stage_real = nullptr,
+                     const unsigned long long* __restrict__ mask = nullptr, int64_t mwords = 0)
 {
     constexpr int WB = KS * 16;            // packed bytes per row (zero padded)
     __shared__ __attribute__((aligned(16))) uint8_t srow[kHamKnnStage * WB];
@@ -293,7 +295,10 @@ void ham_knnk_kernel(const uint8_t* __restrict__ qrows, int nq, const uint8_t* _
         __syncthreads();
         int rn = min(kHamKnnStage, t1 - base);
         if (stage_real) rn = min(rn, stage_real[base >> 7] - (base & 127));      // (a collection's stage: see ham_sweep_kernel)
+        unsigned long long mw = 0ull;
+        if constexpr (MASKED) mw = live ? mask[(size_t)q * mwords + (base >> 6)] : 0ull;
         for (int r = 0; r < rn; ++r) {
+            if constexpr (MASKED) { if (!((mw >> r) & 1ull)) continue; }
             int h = 0;
 #pragma unroll
             for (int c = 0; c < KS; ++c) {
@@ -313,7 +318,7 @@ void ham_knnk_kernel(const uint8_t* __restrict__ qrows, int nq, const uint8_t* _
 
 // (partial: knnk_partial_bytes(q.n, t.n, k) bytes -- the split rule of K9)
 hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist,
-                               hipStream_t stream, const int* stage_real)
+                               hipStream_t stream, const int* stage_real, const unsigned long long* mask, int64_t mwords)
 {
     if (k < 1 || k > 8 || q.kind != FM_BANK_BIN || t.kind != FM_BANK_BIN || q.ksteps != t.ksteps || q.n <= 0) return hipErrorInvalidValue;
     const int nq = (int)q.n, nt = (int)t.n;
@@ -325,8 +330,12 @@ hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned lon
     bool launched = false;
 #define FM_HAMK(K_, KS_)                                                                                                       \
     if (k == K_ && q.ksteps == KS_) {                                                                                          \
-        hipLaunchKernelGGL((ham_knnk_kernel<K_, KS_>), grid, dim3(256), 0, stream, (const uint8_t*)q.rowsb, nq,               \
-                           (const uint8_t*)t.rowsb, nt, per, partial, stage_real);                                                       \
+        if (mask)                                                                                                              \
+            hipLaunchKernelGGL((ham_knnk_kernel<K_, KS_, true>), grid, dim3(256), 0, stream, (const uint8_t*)q.rowsb, nq,      \
+                               (const uint8_t*)t.rowsb, nt, per, partial, stage_real, mask, mwords);                          \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((ham_knnk_kernel<K_, KS_>), grid, dim3(256), 0, stream, (const uint8_t*)q.rowsb, nq,           \
+                               (const uint8_t*)t.rowsb, nt, per, partial, stage_real);                                         \
         launched = true;                                                                                                       \
     }
 #define FM_HAMK4(K_) FM_HAMK(K_, 1) FM_HAMK(K_, 2) FM_HAMK(K_, 3) FM_HAMK(K_, 4)

@@ -8,17 +8,21 @@
 //   K5's chain (s = fmaf(v, v, s), k ascending; dist_f32.hip) -- the same bits fm_knn2 returns for its two columns.
 // partial[(split * nq + q) * K + i] = (distance bits << 32) | train row, ascending, ~0 = none; knnk_merge_kernel merges
 // the splits of the train range.
+// MASKED (K13, masked.hip: fm_knn_masked): a thread reads its query row's word of the bit mask once per 64-row stage and
+// tests one bit per candidate; a forbidden train row never becomes a key.  The unmasked instantiations compile to what
+// they were without the parameter (every masked statement sits under `if constexpr`).  Masked lists exist for K = 1 .. 8.
 #include "tile_ops.h"
 
 namespace fm {
 
 constexpr int kKnnStage = 64;          // train rows per LDS stage
 
-template <int K>
+template <int K, bool MASKED = false>
 __global__ __launch_bounds__(256)
 void knnk_i8_kernel(const int8_t* __restrict__ qrows, const int32_t* __restrict__ qnorm, int nq,
                     const int8_t* __restrict__ trows, const int32_t* __restrict__ tnorm, int nt, int rows_per_split,
-                    unsigned long long* __restrict__ partial)
+                    unsigned long long* __restrict__ partial,
+                    const unsigned long long* __restrict__ mask = nullptr, int64_t mwords = 0)
 {
     __shared__ __attribute__((aligned(16))) int8_t srow[kKnnStage * kDim];
     __shared__ int snorm[kKnnStage];
@@ -47,7 +51,10 @@ void knnk_i8_kernel(const int8_t* __restrict__ qrows, const int32_t* __restrict_
         }
         __syncthreads();
         const int rn = min(kKnnStage, t1 - base);
+        unsigned long long mw = 0ull;              // MASKED: the row's permitted train rows of this stage (base % 64 == 0)
+        if constexpr (MASKED) mw = live ? mask[(size_t)q * mwords + (base >> 6)] : 0ull;
         for (int r = 0; r < rn; ++r) {
+            if constexpr (MASKED) { if (!((mw >> r) & 1ull)) continue; }
             int dot = 0;
 #pragma unroll
             for (int c = 0; c < kDim / 16; ++c) {
@@ -77,10 +84,11 @@ void knnk_i8_kernel(const int8_t* __restrict__ qrows, const int32_t* __restrict_
     }
 }
 
-template <int K>
+template <int K, bool MASKED = false>
 __global__ __launch_bounds__(256)
 void knnk_f32_kernel(const float* __restrict__ qrows, int nq, const float* __restrict__ trows, int nt, int rows_per_split,
-                     unsigned long long* __restrict__ partial)
+                     unsigned long long* __restrict__ partial,
+                     const unsigned long long* __restrict__ mask = nullptr, int64_t mwords = 0)
 {
     constexpr int kStage = 32;                      // 32 rows x 512 B
     __shared__ __attribute__((aligned(16))) float srow[kStage * kDim];
@@ -104,7 +112,10 @@ void knnk_f32_kernel(const float* __restrict__ qrows, int nq, const float* __res
         }
         __syncthreads();
         const int rn = min(kStage, t1 - base);
+        unsigned mw = 0u;                           // MASKED: this stage's half of the row's mask word (base % 32 == 0)
+        if constexpr (MASKED) mw = live ? (unsigned)(mask[(size_t)q * mwords + (base >> 6)] >> (base & 32)) : 0u;
         for (int r = 0; r < rn; ++r) {
+            if constexpr (MASKED) { if (!((mw >> r) & 1u)) continue; }
             float sum = 0.f;
 #pragma unroll
             for (int k4 = 0; k4 < kDim / 4; ++k4) {
@@ -204,6 +215,36 @@ hipError_t launch_knnk(const Bank& q, const Bank& t, int k, unsigned long long* 
     }
 #undef FM_KNNK
     return hipGetLastError();
+}
+
+// The masked instantiations (K13): the same launch shape, splits and merge.
+hipError_t launch_knnk_masked(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist,
+                              hipStream_t stream, const unsigned long long* mask, int64_t mwords)
+{
+    if (k < 1 || k > 8 || q.kind != t.kind || q.n <= 0 || !mask) return hipErrorInvalidValue;
+    const int nq = (int)q.n, nt = (int)t.n;
+    const int nsplit = knnk_splits(q.n, t.n);
+    int per = (nt + nsplit - 1) / nsplit;
+    per = (per + kKnnStage - 1) / kKnnStage * kKnnStage;
+    if (per < kKnnStage) per = kKnnStage;
+    const dim3 grid((unsigned)((nq + 255) / 256), (unsigned)nsplit);
+#define FM_KNNKM(K_)                                                                                                      \
+    case K_:                                                                                                               \
+        if (q.kind == FM_BANK_F32)                                                                                         \
+            hipLaunchKernelGGL((knnk_f32_kernel<K_, true>), grid, dim3(256), 0, stream, (const float*)q.rowsf, nq, (const float*)t.rowsf, nt, per, \
+                               partial, mask, mwords);                                                                     \
+        else                                                                                                               \
+            hipLaunchKernelGGL((knnk_i8_kernel<K_, true>), grid, dim3(256), 0, stream, (const int8_t*)q.rows8, (const int32_t*)q.norm, nq, \
+                               (const int8_t*)t.rows8, (const int32_t*)t.norm, nt, per, partial, mask, mwords);            \
+        break;
+    switch (k) {
+        FM_KNNKM(1) FM_KNNKM(2) FM_KNNKM(3) FM_KNNKM(4) FM_KNNKM(5) FM_KNNKM(6) FM_KNNKM(7) FM_KNNKM(8)
+        default: return hipErrorInvalidValue;
+    }
+#undef FM_KNNKM
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_knnk_merge(partial, nsplit, nq, k, d_idx, d_dist, stream);
 }
 
 }  // namespace fm

@@ -19,6 +19,15 @@ Mirrors ``matchutil.py`` of the reference:
   crossCheck)``); ``bf_match``, ``flann_match`` and ``ratio_match_arrays`` honour it, ``bf_radius_match`` does not
   (``ValueError``), nor does anything else take ``NORM_HAMMING2``.  Without ``normType`` every array is an L2 bank,
   a uint8 [n, 32] array included.
+* ``options["mask"]``: cv2's ``mask`` argument of ``knnMatch`` -- an ``[nq, nt]`` uint8 / bool array, nonzero = the pair
+  (query row, train row) may be matched, or a resident ``_ffi.Mask`` (``Context.mask``).  ``bf_match``,
+  ``bf_match_arrays``, ``flann_match`` and ``flann_match_arrays`` honour it when crossCheck is off: every list is the
+  unmasked list computed over the permitted train rows only (``fm_knn_masked``; -1 / inf, or a shorter DMatch list, where
+  fewer than k rows are permitted).  Its shape is checked before anything is uploaded.  ``ValueError`` naming what is not
+  built: a mask with crossCheck, in ``bf_radius_match``, ``ratio_match_arrays`` and ``mutual_ratio_match_arrays``.
+  ``BFMatcher.knnMatch(query, train=None, k=None, mask=None, masks=None)`` and ``match`` take cv2's keywords: ``mask`` with a
+  train argument, ``masks`` (one entry per added image, ``None`` = everything permitted) against the collection
+  (``fm_collection_knn_masked``).  Calls without a mask go exactly where they went before masks existed.
 * ``BFMatcher(normType, crossCheck)`` -- cv2's matcher object: ``add`` / ``train`` / ``clear`` build a TRAIN COLLECTION and
   ``match(query)`` / ``knnMatch(query, k)`` search all of its images at once, filling ``DMatch.imgIdx`` (``fm_collection_*``).
 * ``sift / get_features / get_keypoints``     -- reference ``matchutil.py:22-36``; SIFT
@@ -124,6 +133,40 @@ def _as_bank_pair(ctx, dt1, dt2):
     return qb, q_tmp, tb, t_tmp
 
 
+def _rows_of(d):
+    return d.n if isinstance(d, _ffi.Bank) else np.asarray(d).shape[0]
+
+
+def _mask_array(m, nq, nt, what):
+    """A host mask as a uint8 [nq, nt] array, or ValueError."""
+    a = np.asarray(m)
+    if a.dtype == np.bool_:
+        a = a.view(np.uint8)
+    if a.dtype != np.uint8:
+        raise ValueError("%s must be uint8 or bool (cv2 asserts CV_8U), got %s" % (what, a.dtype))
+    if a.ndim != 2 or a.shape != (nq, nt):
+        raise ValueError("%s must be [%d, %d] (query rows, train rows), got %s" % (what, nq, nt, a.shape))
+    return a
+
+
+def _mask_option(options, dt1, dt2, who, not_built=None):
+    """options["mask"] checked against the operands BEFORE anything is uploaded: None, a resident Mask, or a uint8 array.
+    not_built: what the caller would have to honour it in -- a ValueError that names it."""
+    m = options.get("mask") if options else None
+    if m is None:
+        return None
+    if not_built:
+        raise ValueError("%s: a mask with %s is not built (masks are honoured by knnMatch / match without crossCheck: "
+                         "bf_match, flann_match, BFMatcher.knnMatch)" % (who, not_built))
+    nq, nt = _rows_of(dt1), _rows_of(dt2)
+    if isinstance(m, _ffi.Mask):
+        if m.n_images != 0 or (m.nq, m.nt) != (nq, nt):
+            raise ValueError("%s: the Mask is for %d x %d rows%s, the operands have %d x %d"
+                             % (who, m.nq, m.nt, " of a collection" if m.n_images else "", nq, nt))
+        return m
+    return _mask_array(m, nq, nt, "%s: options['mask']" % who)
+
+
 def bf_match_arrays(dt1, dt2, k=1, options={}):
     """Array form of :func:`bf_match`.
 
@@ -139,9 +182,15 @@ def bf_match_arrays(dt1, dt2, k=1, options={}):
         raise ValueError("bf_match: k = %d: the HIP path builds k-NN lists up to k = 8 (FM_EUNSUPPORTED beyond)" % k)
     crossCheck = k == 1 and options.get("crossCheck", False) == True   # noqa: E712  (reference semantics)
     norm = _norm_type(options, dt1, dt2)
+    mask = _mask_option(options, dt1, dt2, "bf_match", "crossCheck" if crossCheck else None)
     ctx = _context(options)
     qb, q_tmp, tb, t_tmp = _bank_pair(ctx, dt1, dt2, norm)
     try:
+        if mask is not None:
+            if isinstance(mask, _ffi.Mask):
+                return ctx.knn_masked(qb, tb, mask, k)
+            with ctx.mask(qb.n, tb.n) as mk:
+                return ctx.knn_masked(qb, tb, mk.set(mask), k)
         if crossCheck:
             return ctx.xcheck1(qb, tb)
         if k > 2:
@@ -194,6 +243,7 @@ def ratio_match_arrays(dt1, dt2, tau, options={}):
     brute-force 2-NN then ``m[0].distance / m[1].distance < tau`` in float64, on the device.
     Returns (query idx, train idx, distance, ratio) of the accepted matches, ascending query."""
     norm = _norm_type(options, dt1, dt2)
+    _mask_option(options, dt1, dt2, "ratio_match_arrays", "the ratio test")
     ctx = _context(options)
     qb, q_tmp, tb, t_tmp = _bank_pair(ctx, dt1, dt2, norm)
     try:
@@ -213,6 +263,7 @@ def mutual_ratio_match_arrays(dt1, dt2, tau, symmetric=False, options={}):
     NORM_L2 or NORM_HAMMING.  Returns (query idx, train idx, distance, ratio) ascending in query index; ``ratio`` is the
     larger of the two ratios in symmetric mode."""
     norm = _norm_type(options, dt1, dt2)
+    _mask_option(options, dt1, dt2, "mutual_ratio_match_arrays", "the mutual ratio test")
     ctx = _context(options)
     qb, q_tmp, tb, t_tmp = _bank_pair(ctx, dt1, dt2, norm)
     try:
@@ -230,6 +281,7 @@ def bf_radius_match_arrays(dt1, dt2, maxDistance, options={}):
     passes it) or an array of one radius per query row."""
     if _norm_type(options, dt1, dt2) == NORM_HAMMING:
         raise ValueError("bf_radius_match: radiusMatch with NORM_HAMMING is not built (NORM_L2 only)")
+    _mask_option(options, dt1, dt2, "bf_radius_match", "radiusMatch")
     ctx = _context(options)
     qb, q_tmp, tb, t_tmp = _as_bank_pair(ctx, dt1, dt2)
     try:
@@ -331,9 +383,23 @@ class BFMatcher(object):
         # (a float32-route collection takes a float32-route query, integer valued or not)
         return ctx.bank(a, float_route=self._coll.info()[3] == _ffi.FM_BANK_F32 and a.dtype != np.uint8), True
 
-    def knnMatch_arrays(self, queryDescriptors, k):
+    def _check_masks(self, masks, queryDescriptors):
+        """cv2's ``masks``: one uint8 / bool [nq, rows of the image] array per added image, None = everything -- checked before
+        anything is uploaded.  (A resident ``_ffi.Mask`` of the collection passes as it is.)"""
+        if self.crossCheck:
+            raise ValueError("BFMatcher.knnMatch: masks with crossCheck are not built")
+        if isinstance(masks, _ffi.Mask):
+            return masks
+        masks = list(masks)
+        if len(masks) != len(self._images):
+            raise ValueError("BFMatcher.knnMatch: masks has %d entries, the collection %d images" % (len(masks), len(self._images)))
+        nq = _rows_of(queryDescriptors)
+        return [None if m is None else _mask_array(m, nq, self._images[i].shape[0], "BFMatcher.knnMatch: masks[%d]" % i)
+                for i, m in enumerate(masks)]
+
+    def knnMatch_arrays(self, queryDescriptors, k, masks=None):
         """(img, idx, dist) [nq, k] against the collection: ``imgIdx``, ``trainIdx`` inside that image, distance; -1 / -1 / inf
-        where the collection has fewer than k rows."""
+        where the collection has fewer than k (permitted) rows.  ``masks``: see the module docstring."""
         k = int(k)
         if k < 1 or k > 8:
             raise ValueError("BFMatcher.knnMatch: k = %d: the HIP path builds k-NN lists for 1 <= k <= 8" % k)
@@ -343,12 +409,24 @@ class BFMatcher(object):
                              "image by image")
         if self.normType == NORM_HAMMING and np.asarray(queryDescriptors).dtype != np.uint8 and not isinstance(queryDescriptors, _ffi.Bank):
             raise ValueError("NORM_HAMMING needs uint8 descriptors (cv2 asserts CV_8U), got %s" % np.asarray(queryDescriptors).dtype)
+        if masks is not None:
+            masks = self._check_masks(masks, queryDescriptors)
         if self.crossCheck and k == 1:
             tidx, dist = bf_match_arrays(queryDescriptors, self._images[0], k=1, options=dict(self.options, crossCheck=True))
             return np.where(tidx >= 0, 0, -1).astype(np.int32)[:, None], tidx[:, None], dist[:, None]
         coll = self.train()
         qb, tmp = self._query(coll.ctx, queryDescriptors)
         try:
+            if isinstance(masks, _ffi.Mask):
+                return coll.knn_masked(qb, masks, k)
+            if masks is not None:
+                with coll.mask(qb.n) as mk:
+                    for i, m in enumerate(masks):
+                        if m is None:
+                            mk.set_all(True, img=i)
+                        else:
+                            mk.set(m, img=i)
+                    return coll.knn_masked(qb, mk, k)
             return coll.knn(qb, k)
         finally:
             if tmp:
@@ -463,19 +541,31 @@ class BFMatcher(object):
         return out
 
     # -- cv2's matching methods ------------------------------------------------------------
-    def knnMatch(self, queryDescriptors, trainDescriptors=None, k=None):
+    def knnMatch(self, queryDescriptors, trainDescriptors=None, k=None, mask=None, masks=None):
         if k is None and trainDescriptors is not None and np.isscalar(trainDescriptors):
             trainDescriptors, k = None, trainDescriptors          # knnMatch(query, k)
         if k is None:
             raise TypeError("knnMatch: k is required")
         if trainDescriptors is not None:
-            return bf_match(queryDescriptors, trainDescriptors, k=k, options=dict(self.options, crossCheck=self.crossCheck))
-        img, idx, dist = self.knnMatch_arrays(queryDescriptors, k)
+            if masks is not None:
+                raise ValueError("BFMatcher.knnMatch: masks goes with the train collection; a train argument takes mask")
+            opts = dict(self.options, crossCheck=self.crossCheck)
+            if mask is not None:
+                opts["mask"] = mask
+            return bf_match(queryDescriptors, trainDescriptors, k=k, options=opts)
+        if mask is not None:
+            raise ValueError("BFMatcher.knnMatch: mask goes with a train argument; the train collection takes masks (one per image)")
+        if masks is None:
+            img, idx, dist = self.knnMatch_arrays(queryDescriptors, k)
+        else:
+            img, idx, dist = self.knnMatch_arrays(queryDescriptors, k, masks=masks)
         return [[DMatch(qi, idx[qi, j], dist[qi, j], img[qi, j]) for j in range(idx.shape[1]) if idx[qi, j] >= 0]
                 for qi in range(idx.shape[0])]
 
-    def match(self, queryDescriptors, trainDescriptors=None):
-        return [m[0] for m in self.knnMatch(queryDescriptors, trainDescriptors, k=1) if m]
+    def match(self, queryDescriptors, trainDescriptors=None, mask=None, masks=None):
+        if mask is None and masks is None:
+            return [m[0] for m in self.knnMatch(queryDescriptors, trainDescriptors, k=1) if m]
+        return [m[0] for m in self.knnMatch(queryDescriptors, trainDescriptors, k=1, mask=mask, masks=masks) if m]
 
     def radiusMatch(self, queryDescriptors, trainDescriptors=None, maxDistance=None):
         if maxDistance is None and trainDescriptors is not None and np.isscalar(trainDescriptors):

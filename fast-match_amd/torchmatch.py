@@ -9,7 +9,10 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
 * ``bank(tensor, *, binary=False, float_route=False, context=None)`` -- a resident ``Bank`` from a 2-D CUDA tensor of dtype
   uint8, float32, float16 or bfloat16 (``binary``: uint8 rows of 1 .. 64 packed bytes for Hamming distance).  On return the
   tensor may be overwritten.
-* ``knn(q, t, k)`` -> ``(idx int32 [nq, k], dist float32 [nq, k])``, 1 <= k <= 8.
+* ``knn(q, t, k, mask=None)`` -> ``(idx int32 [nq, k], dist float32 [nq, k])``, 1 <= k <= 8.  ``mask``: a CUDA ``bool`` /
+  ``uint8`` tensor ``[nq, nt]``, nonzero = the pair may be matched (cv2's ``knnMatch(q, t, k, mask)``), or a resident
+  ``_ffi.Mask``; rows may be pitched (a column slice of a wider tensor).  It is packed into the library's bit mask on the
+  device, read in place behind the current stream (``fm_mask_set_dev``): no host copy.
 * ``mutual_nn(q, t)`` -> ``(tidx int32 [nq], dist float32 [nq])``: the cross-checked 1-NN (-1 / inf: unmatched).
 * ``ratio_match(q, t, tau)`` -> ``(qidx, tidx, dist)`` of the rows whose first / second distance is below ``tau``.
 * ``mutual_ratio_match(q, t, tau, symmetric=False)`` -> ``(qidx, tidx, dist)`` of the rows that pass the ratio test AND are the
@@ -23,7 +26,9 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
 * ``Collection(context=None)`` -- a train collection (``cv2.BFMatcher.add`` / ``train``) whose images are CUDA tensors: the
   retrieval flow extract -> ``add`` to the database -> query -> consume without a copy to the host.  A context manager.
   ``add(tensor, *, binary=False)`` reads the tensor in place (``fm_collection_add_dev``) and returns the image index;
-  ``knn(q, k)`` -> ``(img, idx, dist)`` [nq, k]; ``ratio_match(q, tau)`` -> ``(qidx, img, tidx, dist)``;
+  ``knn(q, k, masks=None)`` -> ``(img, idx, dist)`` [nq, k] (``masks``: one CUDA ``bool`` / ``uint8`` tensor ``[nq, rows of the
+  image]`` per added image, ``None`` entries permit everything -- cv2's ``knnMatch(q, k, masks=[...])``; or a resident
+  ``_ffi.Mask`` from ``Collection.mask``); ``ratio_match(q, tau)`` -> ``(qidx, img, tidx, dist)``;
   ``radius_match(q, r)`` -> ``(offsets, img, idx, dist)``, ``r`` as in the module's ``radius_match``;
   ``fast_match_each(q, tau, cap=None)`` -> ``(rows int32 [n_images, cap, 3], counts int64 [n_images])``, the accepted-match
   test inside every image (``q``: a ``Bank`` carrying self distances, ``Context.self_dist_batch([q], want_host=False)``);
@@ -82,6 +87,32 @@ def _checked(tensor, binary=False):
     return tensor, dt
 
 
+def _checked_mask(m, nq, nt, what="mask"):
+    """A mask tensor with unit column stride, viewed as uint8 -- or ValueError, before anything reaches the library."""
+    import torch
+    if not isinstance(m, torch.Tensor):
+        raise ValueError("%s must be a CUDA bool / uint8 tensor or a resident Mask, got %s" % (what, type(m).__name__))
+    if not m.is_cuda:
+        raise ValueError("%s must be a CUDA tensor (a host array goes to Mask.set / matchutil's options['mask'])" % what)
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("%s dtype %s: bool or uint8 are taken" % (what, m.dtype))
+    if m.dim() != 2 or tuple(m.shape) != (nq, nt):
+        raise ValueError("%s must be [%d, %d] (query rows, train rows), got %s" % (what, nq, nt, tuple(m.shape)))
+    if nq and nt and (m.stride(1) != 1 or m.stride(0) < nt):
+        m = m.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def _set_mask(mask, m, img):
+    """One image's bits from a checked tensor, read in place behind the current stream of its device."""
+    import torch
+    if m.shape[0] == 0 or m.shape[1] == 0:
+        return
+    with torch.cuda.device(m.device):
+        stream = torch.cuda.current_stream().cuda_stream
+    mask.set_dev(m.data_ptr(), img=img, pitch=m.stride(0), stream=stream)
+
+
 def _ctx_for(tensor, context):
     return context if context is not None else _ffi.default_context(tensor.device.index)
 
@@ -122,19 +153,31 @@ def _stream_and_device(ctx):
         return torch.cuda.current_stream().cuda_stream, dev
 
 
-def knn(q, t, k):
+def knn(q, t, k, mask=None):
     """k nearest train rows of every query row: ``(idx int32 [nq, k], dist float32 [nq, k])`` CUDA tensors, ascending
-    (distance, train index); -1 / inf where ``t`` has fewer than k rows.  1 <= k <= 8."""
+    (distance, train index); -1 / inf where ``t`` has fewer than k rows.  1 <= k <= 8.  ``mask`` (module docstring): only the
+    pairs it permits are candidates (``fm_knn_masked_dev``)."""
     import torch
     k = int(k)
     if k < 1:
         raise ValueError("k must be at least 1")
+    if mask is not None and not isinstance(mask, _ffi.Mask):
+        nq, nt = (x.n if isinstance(x, _ffi.Bank) else (x.shape[0] if hasattr(x, "shape") and len(x.shape) == 2 else -1) for x in (q, t))
+        mask = _checked_mask(mask, nq, nt)
     qb, tb, made = _pair(q, t)
     try:
         stream, dev = _stream_and_device(qb.ctx)
         idx = torch.empty((qb.n, k), dtype=torch.int32, device=dev)
         dist = torch.empty((qb.n, k), dtype=torch.float32, device=dev)
-        qb.ctx.knn_dev(qb, tb, k, idx.data_ptr() if qb.n else 0, dist.data_ptr() if qb.n else 0, consumer_stream=stream)
+        if mask is None:
+            qb.ctx.knn_dev(qb, tb, k, idx.data_ptr() if qb.n else 0, dist.data_ptr() if qb.n else 0, consumer_stream=stream)
+            return idx, dist
+        mk = mask
+        if not isinstance(mask, _ffi.Mask):
+            mk = qb.ctx.mask(qb.n, tb.n)
+            made.append(mk)
+            _set_mask(mk, mask, 0)
+        qb.ctx.knn_masked_dev(qb, tb, mk, k, idx.data_ptr() if qb.n else 0, dist.data_ptr() if qb.n else 0, consumer_stream=stream)
         return idx, dist
     finally:
         for b in made:
@@ -303,21 +346,49 @@ class Collection(object):
         b = bank(t, binary=kind == _ffi.FM_BANK_BIN, float_route=kind == _ffi.FM_BANK_F32, context=self._context)
         return b, [b]
 
-    def knn(self, q, k):
+    def mask(self, nq):
+        """An all-forbidding ``_ffi.Mask`` for ``nq`` query rows on the images added so far (``Mask.set_dev`` / ``set_all`` per
+        image); a later ``add`` / ``clear`` makes it stale."""
+        return self._collection().mask(nq)
+
+    def _masks(self, masks, nq, made):
+        """``masks`` as a resident Mask of the collection: one tensor per image (None: everything), checked before any is read."""
+        if isinstance(masks, _ffi.Mask):
+            return masks
+        coll = self._collection()
+        rows = coll.image_rows()
+        if len(masks) != rows.shape[0]:
+            raise ValueError("masks has %d entries, the collection %d images" % (len(masks), rows.shape[0]))
+        checked = [None if m is None else _checked_mask(m, nq, int(rows[i]), "masks[%d]" % i) for i, m in enumerate(masks)]
+        mk = coll.mask(nq)
+        made.append(mk)
+        for i, m in enumerate(checked):
+            if m is None:
+                mk.set_all(True, img=i)
+            else:
+                _set_mask(mk, m, i)
+        return mk
+
+    def knn(self, q, k, masks=None):
         """The k nearest rows of the stacked images: ``(img int32, idx int32, dist float32)`` [nq, k] CUDA tensors, ``idx`` the
-        row inside image ``img``; ties go to the earlier image; -1 / -1 / inf beyond the collection's rows.  1 <= k <= 8."""
+        row inside image ``img``; ties go to the earlier image; -1 / -1 / inf beyond the collection's rows.  1 <= k <= 8.
+        ``masks`` (module docstring): only the pairs they permit are candidates (``fm_collection_knn_masked_dev``)."""
         import torch
         k = int(k)
         if k < 1:
             raise ValueError("k must be at least 1")
         qb, made = self._query(q)
         try:
+            mk = self._masks(masks, qb.n, made) if masks is not None else None
             stream, dev = _stream_and_device(qb.ctx)
             img = torch.empty((qb.n, k), dtype=torch.int32, device=dev)
             idx = torch.empty((qb.n, k), dtype=torch.int32, device=dev)
             dist = torch.empty((qb.n, k), dtype=torch.float32, device=dev)
             p = (lambda t: t.data_ptr()) if qb.n else (lambda t: 0)
-            self._coll.knn_dev(qb, k, p(img), p(idx), p(dist), consumer_stream=stream)
+            if mk is None:
+                self._coll.knn_dev(qb, k, p(img), p(idx), p(dist), consumer_stream=stream)
+            else:
+                self._coll.knn_masked_dev(qb, mk, k, p(img), p(idx), p(dist), consumer_stream=stream)
             return img, idx, dist
         finally:
             for b in made:

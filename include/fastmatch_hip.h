@@ -52,7 +52,10 @@ typedef struct fm_bank fm_bank;
  * additions only -- fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev; still revision 12, additions
  * only -- fm_collection_radius_match, fm_radius_match_dev, fm_collection_radius_match_dev; still revision 12, additions
  * only -- fm_collection_xcheck1_each, fm_collection_xcheck1_each_dev; still revision 12, additions only -- fm_mutual_ratio,
- * fm_mutual_ratio_dev, fm_collection_mutual_ratio_each, fm_collection_mutual_ratio_each_dev).  A binding compares
+ * fm_mutual_ratio_dev, fm_collection_mutual_ratio_each, fm_collection_mutual_ratio_each_dev; still revision 12, additions
+ * only -- fm_mask_create, fm_mask_create_coll, fm_mask_set_u8, fm_mask_set_dev, fm_mask_set_all, fm_mask_destroy,
+ * fm_mask_info, fm_knn_masked, fm_knn_masked_dev, fm_collection_knn_masked, fm_collection_knn_masked_dev, the option
+ * "masked_mfma", "mask_pack_words").  A binding compares
  * fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.                      */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -122,6 +125,11 @@ int  fm_ctx_destroy(fm_ctx* ctx);
  *                         redone by K1 on the device, without a host wait
  *   "fp6_records", "fp6_fallbacks"  COUNTERS, get only (waits for the context's stream): records appended and pairs redone
  *                         by K1 in the last filter launch, summed over its pairs
+ *   "masked_mfma"  0|1    fm_knn_masked and its siblings on the integer route with k <= 2: 1 = the masked matrix-core sweep
+ *                         (1), 0 = the masked vector-ALU lists that serve every other k and route.  Results never differ.
+ *   "mask_pack_words" 64..2^26-4  fm_mask_set_u8 / _set_dev / _set_all: mask words one kernel launch covers (2^26 - 4: the
+ *                         packing kernel spends 64 work-items per word and a launch holds fewer than 2^32); larger masks take
+ *                         several launches of whole query rows, at least one row each
  *   "radius_ws_bytes" 65536..2^31-1  fm_radius_match: device bytes for the candidates of one chunk of query rows (2^30;
  *                         24 bytes per candidate, 28 in the collection forms); a row whose own list needs more runs in a
  *                         chunk of its own
@@ -390,7 +398,8 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  * fm_collection_xcheck1_each), a single reverse K8 sweep
  * over a float32-route stack (its padding output rows would flood the filter's candidate lists: fm_collection_xcheck1_each
  * and fm_collection_match_accepted_each sweep image by image there), Hamming radiusMatch (for pairs or collections), radius queries per
- * image separately (an _each form), skipping the second count sweep of the counts-then-fill pattern, masks,
+ * image separately (an _each form), skipping the second count sweep of the counts-then-fill pattern,
+ * masks anywhere but in knnMatch (fm_collection_knn_masked is built; "masks" below lists what is not),
  * the expansion loop on a collection, a batched K8 / K11 (float32 / binary) per-image sweep,
  * binary collections in the self-distance test, sharding a collection across GPUs (radius queries included), removing single
  * images, turning an integer-route collection of float32 images into a float32-route one for a
@@ -551,6 +560,71 @@ int  fm_collection_radius_match_dev(fm_ctx* ctx, fm_collection* coll, const fm_b
                                     float radius_all, int64_t cap, int64_t* d_offsets /*device [nq+1]*/, int32_t* d_img,
                                     int32_t* d_idx, float* d_dist, int64_t* n_total /*host, or NULL*/,
                                     void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+
+/* ---- masks: knnMatch(q, t, k, mask) and knnMatch(q, k, masks = [...]) (K13, csrc/masked.hip) --------------------------------
+ * cv2's mask argument: a CV_8U [nq][nt] matrix, nonzero = the pair (query row, train row) may be matched; for a train
+ * collection one such matrix per added image, an empty entry permitting everything.  (OpenCV's behaviour as RECALLED, not
+ * verified -- neither cv2 nor its source was at hand, as for SURVEY.md Appendix A: a masked-out pair is skipped before the
+ * distance enters the k-NN insertion, so the result is the unmasked algorithm run over the permitted train rows only.)
+ *
+ * fm_mask -- a device-resident BIT matrix, [nq][n_pad / 64] 64-bit words, n_pad the padded row count of the train operand:
+ *   bit b of word w of row i set = (query row i, train row 64 w + b) is permitted; the bits of rows at or beyond the operand's
+ *   real rows are always 0.  (A dense byte mask at 100k x 100k is 10 GB; the bit form is 1.25 GB and is what the kernels read.)
+ *   fm_mask_create(ctx, nq, nt, &mask): an all-zero (everything forbidden) mask for a bank pair whose train bank has nt rows.
+ *   fm_mask_create_coll(ctx, nq, coll, &mask): an all-zero mask laid out on the collection's PHYSICAL stack: every image
+ *     starts on a 128-row stage, so an image's bits are whole words and setting one image never reads or modifies another
+ *     image's words; the padding rows behind every image have bit 0, so the masked sweeps need no real-row table.  The mask
+ *     remembers the collection, its image count and row total; a later add or clear makes it stale (FM_EINVAL at the match).
+ *   fm_mask_set_u8(ctx, mask, img, rows, pitch): the host matrix uint8 [nq][rows of image img], nonzero = permitted, `pitch`
+ *     bytes between rows (0 = dense); img = 0 for a pair mask.  Uploaded in chunks of query rows through a bounded workspace
+ *     (64 MiB) and packed on the device, one wave per word (64 consecutive bytes of a row, one ballot).  Synchronous.
+ *   fm_mask_set_dev(ctx, mask, img, d_rows, pitch, producer_stream): the same from device memory of the context's device, read
+ *     in place (a torch.bool tensor is one byte per element); pointer check and producer-stream ordering are
+ *     fm_bank_create_dev's, and like it the call returns when the source has been read.
+ *   fm_mask_set_all(ctx, mask, img, value): all real rows of one image permitted (value != 0) or forbidden, for every query row.
+ *   fm_mask_info: nq, the real train rows, the image count (0 for a pair mask), the bytes of the bit matrix.
+ *   Errors: a NULL handle, a mask of another context, an image index outside the mask, a NULL source with nq > 0 and a
+ *   non-empty image, a pitch below the row width: FM_EINVAL.  nq = 0, nt = 0 and empty images are valid.
+ *
+ * fm_knn_masked / fm_knn_masked_dev / fm_collection_knn_masked / fm_collection_knn_masked_dev -- the contract:
+ *   row i's list is fm_knn's (fm_collection_knn's) list computed over the PERMITTED train rows of row i only; the distances
+ *   are the same bits fm_knn reports for the pair; lists ascend by (float32 distance bits, train index), strictly -- for a
+ *   collection by (bits, img, row); where fewer than k rows are permitted the tail is -1 / +inf (img -1 too), a row with no
+ *   permitted pair is all -1 / +inf.  1 <= k <= 8 on all three bank kinds.
+ *   Errors, in this order: (1) NULL handles (ctx, banks / collection, mask): FM_EINVAL; (2) check_pair's rules as in fm_knn --
+ *   width or kind mismatch -- or fm_collection_knn's for the collection forms; (3) k < 1: FM_EINVAL, k > 8: FM_EUNSUPPORTED;
+ *   (4) FM_EINVAL with a message that says which: a mask of another context, a mask whose nq differs from the query bank's
+ *   rows or whose train rows differ from the train bank's, a pair mask given to a collection form and the reverse, a mask of
+ *   another collection, a collection that has changed (add or clear) since fm_mask_create_coll; (5) the output pointers
+ *   (NULL with nq > 0: FM_EINVAL; the device forms: fm_knn_dev's pointer checks).
+ *   The device forms order themselves against consumer_stream in both directions as fm_knn_dev does and are not accounted in
+ *   fm_stats; the host forms are accounted like fm_knn (pairs = nq * real train rows).
+ *   Routes: integer route (FM_BANK_I8) with k = 1 or 2: the masked sweep on the MATRIX CORES (v_mfma_i32_16x16x64_i8; one
+ *   8-byte mask word per 16 query rows x 64 train rows and lane; a wave skips the MFMAs of a stage, and of a 16 x 16 tile,
+ *   in which it has no permitted pair).  Everything else -- k = 3 .. 8 on the integer route, every k on the float32 route
+ *   (K5's chain: fm_knn2's bits) and for binary banks -- runs on the VECTOR ALUs, the exact list kernels of fm_knn with one
+ *   mask bit tested per candidate; NOT on the matrix cores.  Candidates are ordered by the float32 root inside the kernels,
+ *   so no float32-root repair pass exists or is needed.
+ * Not built ("masks"): masks on the fp16-filter (K8) and FP4 (K11) matrix-core sweeps (the float32 route and binary banks take
+ *   the vector-ALU kernels for every k), masked crossCheck, masked radiusMatch, masked ratio / mutual-ratio / accepted-match
+ *   calls, masks in the _each forms.                                                                                        */
+typedef struct fm_mask fm_mask;
+int  fm_mask_create(fm_ctx* ctx, int64_t nq, int64_t nt, fm_mask** mask);
+int  fm_mask_create_coll(fm_ctx* ctx, int64_t nq, fm_collection* coll, fm_mask** mask);
+int  fm_mask_set_u8(fm_ctx* ctx, fm_mask* mask, int32_t img, const uint8_t* rows /*[nq][image rows]*/, int64_t pitch /*0 = dense*/);
+int  fm_mask_set_dev(fm_ctx* ctx, fm_mask* mask, int32_t img, const void* d_rows /*device [nq][image rows] bytes*/, int64_t pitch /*0 = dense*/,
+                     void* producer_stream /*hipStream_t, NULL = null stream, or FM_NO_STREAM*/);
+int  fm_mask_set_all(fm_ctx* ctx, fm_mask* mask, int32_t img, int32_t value);
+int  fm_mask_destroy(fm_ctx* ctx, fm_mask* mask);
+int  fm_mask_info(const fm_mask* mask, int64_t* nq, int64_t* nt, int32_t* n_images, int64_t* bytes);
+int  fm_knn_masked(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, int32_t k, int32_t* idx /*[nq*k]*/, float* dist /*[nq*k]*/);
+int  fm_knn_masked_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, int32_t k, int32_t* d_idx /*device [nq*k]*/,
+                       float* d_dist /*device [nq*k]*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_knn_masked(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const fm_mask* mask, int32_t k,
+                              int32_t* img /*[nq*k]*/, int32_t* idx /*[nq*k]*/, float* dist /*[nq*k]*/);
+int  fm_collection_knn_masked_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const fm_mask* mask, int32_t k,
+                                  int32_t* d_img /*device [nq*k]*/, int32_t* d_idx /*device [nq*k]*/, float* d_dist /*device [nq*k]*/,
+                                  void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* Classic Ratio-Match in one call: knnMatch(q, t, k=2) then ratio = m[0].distance /
  * m[1].distance (float64) and ratio < tau  -- Classic Matching.ipynb cell 3 (JSON 59-72), the
