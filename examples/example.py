@@ -64,3 +64,12 @@ fm_matcher.add(three)
 per_image = fm_matcher.fastMatchEach(q["descriptors"], 0.7)
 print("fast-match acceptance per image:", [len(l) for l in per_image])
 assert len(per_image[0]) >= 390 > max(len(per_image[1]), len(per_image[2])) and all(d.imgIdx == 0 for d in per_image[0])
+
+# Wide float descriptors: a learned extractor's 256-D rows (SuperPoint and its kin) go the same way -- a float array of
+# 129 .. 256 columns becomes a wide float bank; k <= 2, crossCheck, the ratio match and the mutual ratio match take it.
+wide_t = rng.standard_normal((2000, 256)).astype(np.float32)
+wide_t /= np.linalg.norm(wide_t, axis=1, keepdims=True)
+wide_q = wide_t[:500] + np.float32(0.01) * rng.standard_normal((500, 256)).astype(np.float32)
+qidx, tidx, dist, ratio = matchutil.mutual_ratio_match_arrays(wide_q, wide_t, 0.8)
+print("256-D pair: %d of 500 query rows matched mutually at ratio 0.8" % len(qidx))
+assert np.array_equal(qidx, tidx) and len(qidx) == 500

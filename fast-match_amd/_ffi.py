@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libfastmatch_hip.so")
 FM_BANK_I8 = 1
 FM_BANK_F32 = 2
 FM_BANK_BIN = 3             # binary descriptors (Context.bank_binary): NORM_HAMMING
+FM_BANK_F32W = 4            # float rows of 129 .. 256 values (Context.bank / bank_from_device make it for every such width)
 # element types of rows in device memory (Context.bank_from_device)
 FM_DT_U8, FM_DT_F32, FM_DT_F16, FM_DT_BF16, FM_DT_BIN = 1, 2, 3, 4, 5
 
@@ -967,7 +968,8 @@ class Context(object):
     # -- banks -------------------------------------------------------------------------
     def bank(self, rows, float_route=False):
         """Upload an [n, dim] uint8 or float32 matrix.  Other dtypes are converted to
-        float32 first (cv2 would reject them).  ``float_route``: keep the float32 route even
+        float32 first (cv2 would reject them).  Float rows of 129 .. 256 values make a wide float bank (``FM_BANK_F32W``:
+        knn with k <= 2, xcheck1, knn2_ratio, mutual_ratio and their device forms), whatever the values.  ``float_route``: keep the float32 route even
         if the values are integers (to pair with a bank that is not integer valued)."""
         a = np.asarray(rows)
         if a.ndim != 2:

@@ -500,7 +500,9 @@ static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, 
     if (rc != FM_OK) return rc;
     if (n < 0 || dim < 1 || (n > 0 && !rows)) return fail(ctx, FM_EINVAL, std::string(who) + ": bad rows / n / width");
     if (src == 3 ? dim > 64 : dim > kDim)
-        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + (src == 3 ? ": binary rows of more than 64 bytes are not supported" : ": dim > 128 is not supported"));
+        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + (src == 3 ? ": binary rows of more than 64 bytes are not supported" :
+                                                                    src == 2 && dim <= kWideDim ? ": dim > 128 is not supported (wide float rows, FM_BANK_F32W, are served for bank pairs only)" :
+                                                                    ": dim > 128 is not supported"));
     if (c->rows.size() >= (size_t)INT32_MAX) return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": too many images");
     if (n > 0 && c->dim != 0) {
         if (dim != c->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": the image's width differs from the collection's");
@@ -616,7 +618,9 @@ extern "C" int fm_collection_add_dev(fm_ctx* ctx, fm_collection* c, const void* 
         return fail(ctx, FM_EINVAL, "fm_collection_add_dev: unknown dtype " + std::to_string(dtype) + " (FM_DT_U8 .. FM_DT_BIN)");
     if (n < 0 || dim < 1) return fail(ctx, FM_EINVAL, "fm_collection_add_dev: bad n / width");
     if (dtype == FM_DT_BIN ? dim > 64 : dim > kDim)
-        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + (dtype == FM_DT_BIN ? ": binary rows of more than 64 bytes are not supported" : ": dim > 128 is not supported"));
+        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + (dtype == FM_DT_BIN ? ": binary rows of more than 64 bytes are not supported" :
+                                                                    dtype != FM_DT_U8 && dim <= kWideDim ? ": dim > 128 is not supported (wide float rows, FM_BANK_F32W, are served for bank pairs only)" :
+                                                                    ": dim > 128 is not supported"));
     const int64_t elt = dtype == FM_DT_F32 ? 4 : (dtype == FM_DT_F16 || dtype == FM_DT_BF16) ? 2 : 1;
     const int64_t pitch = row_pitch_bytes == 0 ? dim * elt : row_pitch_bytes;
     if (pitch < dim * elt)
@@ -712,6 +716,7 @@ static int coll_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, con
     int rc = coll_check(ctx, c, who);
     if (rc != FM_OK) return rc;
     if (!q) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank is NULL");
+    if ((rc = refuse_wide(ctx, q, who)) != FM_OK) return rc;
     if (c->dim != 0 && q->kind != c->stack.kind && !(empty_any_kind && q->n == 0))
         return fail(ctx, FM_EINVAL, std::string(who) + ": the query bank is not of the collection's kind (fm_collection_info)");
     if (c->dim != 0 && q->dim != c->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": the query's width differs from the collection's");

@@ -888,6 +888,9 @@ static void bank_free(Bank* b)
     if (b->stage) (void)hipFree(b->stage);
     if (b->rowsb) (void)hipFree(b->rowsb);
     if (b->rows4) (void)hipFree(b->rows4);
+    if (b->wrows) (void)hipFree(b->wrows);
+    if (b->wrowsh) (void)hipFree(b->wrowsh);
+    b->wrows = nullptr; b->wrowsh = nullptr;
     b->stage = nullptr; b->rowsb = nullptr; b->rows4 = nullptr;
     b->rows8 = nullptr; b->norm = nullptr; b->aux = nullptr; b->rowsf = nullptr; b->selfdist = nullptr;
     b->sdmax = nullptr; b->sdmax_rows = -1;
@@ -941,6 +944,58 @@ int fm::dev_src_absmax(fm_ctx* ctx, const DevSrc& d, int64_t n, int dim, float* 
     return FM_OK;
 }
 
+// K14: a wide float32 bank -- [n][dim] rows, 129 <= dim <= 256 -- whatever the values (wide_f32.hip).  rows: a host float32
+// matrix, staged dense; dev: the caller's device rows, read in place.  Both go through the same two kernels.
+static int bank_create_wide(fm_ctx* ctx, const float* rows, int64_t n, int dim, fm_bank** out, const DevSrc* dev = nullptr)
+{
+    if (n > (int64_t)INT32_MAX - 2 * kStageRows) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create: n too large");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    fm_bank* b = new (std::nothrow) fm_bank();
+    if (!b) return fail(ctx, FM_ENOMEM, "fm_bank_create: out of host memory");
+    b->kind = FM_BANK_F32W;
+    b->n = n;
+    b->dim = dim;
+    b->n_pad = b->cap_pad = n > 0 ? pad128(n) : kStageRows;
+    auto bail = [&](hipError_t e, const char* what) {
+        (void)hipGetLastError();
+        bank_free(b); delete b;
+        return fail(ctx, e == hipErrorOutOfMemory ? FM_ENOMEM : FM_EDEVICE, std::string("fm_bank_create (wide rows): ") + what + ": " + hipGetErrorString(e));
+    };
+    const size_t src_bytes = dev ? 0 : (size_t)n * dim * 4;
+    const size_t flag_off = (src_bytes + 15) & ~(size_t)15;
+    int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, flag_off + 32);
+    if (rc != FM_OK) { bank_free(b); delete b; return rc; }
+    int* d_stat = (int*)((char*)ctx->ws_in + flag_off);
+    hipError_t e;
+    if ((e = hipMalloc((void**)&b->wrows, (size_t)b->n_pad * kWideDim * 4)) != hipSuccess) return bail(e, "rows");
+    if ((e = hipMalloc((void**)&b->wrowsh, (size_t)b->n_pad * kWideDim * 2)) != hipSuccess) return bail(e, "fp16 rows");
+    if ((e = hipMalloc((void**)&b->normf, (size_t)b->n_pad * 4)) != hipSuccess) return bail(e, "norms");
+    if ((e = hipMalloc((void**)&b->auxf, (size_t)b->n_pad * 4)) != hipSuccess) return bail(e, "accumulator inits");
+    if (src_bytes && (e = hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return bail(e, "upload");
+    if ((e = hipMemsetAsync(d_stat, 0, 16, ctx->stream)) != hipSuccess) return bail(e, "fill");
+    if (dev) e = launch_wide_copy(dev->rows, dev->dtype, dev->pitch, n, dim, *b, d_stat, ctx->stream);
+    else     e = launch_wide_copy(ctx->ws_in, FM_DT_F32, (int64_t)dim * 4, n, dim, *b, d_stat, ctx->stream);
+    if (e != hipSuccess) return bail(e, "copy");
+    int stat[2] = {0, 0};
+    if ((e = hipMemcpyAsync(stat, d_stat, 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return bail(e, "copy");
+    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "copy");
+    float vmax = 0.f;
+    memcpy(&vmax, &stat[0], 4);
+    b->vfin_max = vmax;
+    b->filt_ok = stat[1] == 0;
+    int ex = 0;
+    if (vmax > 0.f) (void)frexpf(vmax, &ex);         // vmax = m 2^ex, m in [0.5, 1)
+    b->kscale = vmax > 0.f ? 14 - ex : 0;
+    // (a bank with a value that is not finite keeps its planes, written from the scaled values as they come: the filter
+    // never reads them, filt_ok is false)
+    if ((e = launch_wide_planes(*b, d_stat + 2, ctx->stream)) != hipSuccess) return bail(e, "planes");
+    if ((e = hipMemcpyAsync(stat, d_stat + 2, 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return bail(e, "planes");
+    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "planes");
+    memcpy(&b->nm_max, &stat[0], 4);
+    *out = b;
+    return FM_OK;
+}
+
 // map != nullptr: the bank's row i is rows[map[i]] of the n_src source rows (0 <= map[i] < n_src, checked here).
 // dev != nullptr: the rows are dev's (device memory, checked by the caller; `rows` is ignored, f32 = "not uint8").
 static int bank_create(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f32, fm_bank** out, bool keep_f32 = false,
@@ -955,7 +1010,12 @@ static int bank_create(fm_ctx* ctx, const void* rows, int64_t n, int dim, bool f
         for (int64_t i = 0; i < n; ++i)
             if (map[i] < 0 || map[i] >= n_src) return fail(ctx, FM_EINVAL, "fm_bank_create_*_gather: src_row entry outside [0, n_src)");
     }
-    if (dim > kDim) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create: dim > 128 is not supported");
+    // float rows of 129 .. 256 values: a wide bank (K14), whatever the values; the gather creators, the capacity creators and
+    // uint8 rows stay at 128
+    if (f32 && dim > kDim && dim <= kWideDim && !map && capacity == 0)
+        return bank_create_wide(ctx, (const float*)rows, n, dim, out, dev);
+    if (dim > kDim) return fail(ctx, FM_EUNSUPPORTED, f32 && dim > kWideDim ? "fm_bank_create: dim > 256 is not supported"
+                                                                             : "fm_bank_create: dim > 128 is not supported");
     if (n > (int64_t)INT32_MAX - 2 * kStageRows) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create: n too large");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     fm_bank* b = new (std::nothrow) fm_bank();
@@ -1380,7 +1440,9 @@ extern "C" int fm_bank_create_dev(fm_ctx* ctx, const void* d_rows, int dtype, in
     if (n < 0 || dim < 1) return fail(ctx, FM_EINVAL, "fm_bank_create_dev: bad n / dim");
     if (dtype == FM_DT_BIN && dim > 64)
         return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_dev: binary rows of more than 64 bytes (512 bits) are not supported");
-    if (dim > kDim) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_dev: dim > 128 is not supported");
+    if (dim > (dtype == FM_DT_U8 ? kDim : kWideDim))
+        return fail(ctx, FM_EUNSUPPORTED, dtype == FM_DT_U8 ? "fm_bank_create_dev: dim > 128 is not supported"
+                                                            : "fm_bank_create_dev: dim > 256 is not supported");
     const int64_t elt = dtype == FM_DT_F32 ? 4 : (dtype == FM_DT_F16 || dtype == FM_DT_BF16) ? 2 : 1;
     const int64_t pitch = row_pitch_bytes == 0 ? dim * elt : row_pitch_bytes;
     if (pitch < dim * elt)
@@ -1507,8 +1569,16 @@ int fm::bank_selfdist_alloc(fm_ctx* ctx, fm_bank* b)
     return FM_OK;
 }
 
+int fm::refuse_wide(fm_ctx* ctx, const fm_bank* b, const char* who)
+{
+    if (!b || b->kind != FM_BANK_F32W) return FM_OK;
+    return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": wide float banks (FM_BANK_F32W, 129 .. 256 values per row) are served by fm_knn2, "
+                                          "fm_knn with k <= 2, fm_xcheck1, fm_knn2_ratio, fm_mutual_ratio and their _dev forms only");
+}
+
 int fm::refuse_bin(fm_ctx* ctx, const fm_bank* b, const char* who)
 {
+    if (int rc = refuse_wide(ctx, b, who)) return rc;
     if (!b || b->kind != FM_BANK_BIN) return FM_OK;
     return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": binary banks (FM_BANK_BIN, NORM_HAMMING) are served by fm_knn2, fm_knn, "
                                       "fm_xcheck1 and fm_knn2_ratio only");
@@ -1523,6 +1593,11 @@ int fm::check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* 
     if ((q->kind == FM_BANK_BIN) != (t->kind == FM_BANK_BIN))
         return fail(ctx, FM_EINVAL, std::string(who) + ": query/train kind mismatch (one bank is binary, FM_BANK_BIN, the other is not)");
     if (!bin_ok && q->kind == FM_BANK_BIN) return refuse_bin(ctx, q, who);
+    // (wide banks: the binary rule -- a dim mismatch was refused above, another kind is refused even for an empty bank: the
+    // other routes index 128-wide planes)
+    if ((q->kind == FM_BANK_F32W) != (t->kind == FM_BANK_F32W))
+        return fail(ctx, FM_EINVAL, std::string(who) + ": query/train kind mismatch (one bank is a wide float bank, FM_BANK_F32W, the other is not)");
+    if (!bin_ok && q->kind == FM_BANK_F32W) return refuse_bin(ctx, q, who);
     if (q->kind != t->kind && q->n > 0 && t->n > 0)      // (an empty bank has no kind of its own)
         return fail(ctx, FM_EINVAL, std::string(who) + ": query/train kind mismatch (one bank is integer-valued, the other is not)");
     return FM_OK;

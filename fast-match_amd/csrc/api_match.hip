@@ -490,6 +490,45 @@ int rowreduce_f32_route(fm_ctx* ctx, const fm_bank* cols, const fm_bank* red, in
     return FM_OK;
 }
 
+// Wide float banks (K14, wide_f32.hip), the same way: the exact kernel alone, or the fp16 filter with the exact kernel as its
+// conditional fallback (a record list that overflowed); "f32_filter" decides as above.  ws_partial: partial | records | their
+// scores | per-row bounds | count.
+static int wide_route(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, RowReducePlan* pl_out)
+{
+    const RowReducePlan pl = plan_rowreduce_f32(cols.n_pad, red.n_pad, ctx->tune.nsplit);
+    *pl_out = pl;
+    const bool filter = ctx->tune.f32_filter != 0 && ctx->d_counters && wide_filter_usable(cols, red) &&
+                        (ctx->tune.f32_filter >= 2 || (double)cols.n * (double)red.n >= 4.0e6);
+    unsigned long long* d_part;
+    int rc;
+    if (!filter) {
+        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, pl.partial_bytes(ktop) + 64)) != FM_OK) return rc;
+        d_part = (unsigned long long*)ctx->ws_partial;
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+        HIP_TRY(ctx, launch_wide_exact(cols, red, ktop, pl, d_part, nullptr, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+        return FM_OK;
+    }
+    const WideFilterPlan fp = plan_wide_filter(cols.n_pad, cols.n, red.n_pad, ctx->tune);
+    size_t off = 0;
+    const size_t o_part = carve(off, pl.partial_bytes(ktop)), o_list = carve(off, fp.list_bytes()), o_score = carve(off, fp.list_bytes() / 2),
+                 o_bound = carve(off, (size_t)cols.n_pad * 4), o_cnt = carve(off, 16);
+    if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, off + 64)) != FM_OK) return rc;
+    d_part = (unsigned long long*)((char*)ctx->ws_partial + o_part);
+    unsigned long long* d_cnt = (unsigned long long*)((char*)ctx->ws_partial + o_cnt);
+    HIP_TRY(ctx, hipMemsetAsync(d_part, 0xff, pl.partial_bytes(ktop), ctx->stream));
+    // (the bounds and the count are neighbours: one fill)
+    HIP_TRY(ctx, hipMemsetAsync((char*)ctx->ws_partial + o_bound, 0, o_cnt + 16 - o_bound, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, 8, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+    HIP_TRY(ctx, launch_wide_filter(cols, red, ktop, fp, (uint2*)((char*)ctx->ws_partial + o_list), (float*)((char*)ctx->ws_partial + o_score),
+                                    (unsigned*)((char*)ctx->ws_partial + o_bound), d_cnt, ctx->d_counters, d_part, ctx->stream));
+    HIP_TRY(ctx, launch_wide_exact(cols, red, ktop, pl, d_part, ctx->d_counters, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+    ctx->filter_launches += 1;
+    return FM_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // one bank pair on the context's stream: every synchronous entry point's sweep (ctx_internal.h)
 // ---------------------------------------------------------------------------------------
@@ -544,6 +583,13 @@ int sweep_pair(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, int64_t
         // (K5's layout has neither shared bounds nor a tie list behind it, and needs none; the route records ev_k0 / ev_k1 itself)
         RowReducePlan pl;
         if ((rc = rowreduce_f32_route(ctx, static_cast<const fm_bank*>(&cols), static_cast<const fm_bank*>(&red), ktop, &pl)) != FM_OK) return rc;
+        *out = PairSweep{};
+        out->partial = (const unsigned long long*)ctx->ws_partial;
+        out->nsplit = pl.nsplit; out->ncols_alloc = pl.ncols_alloc; out->f32_keys = 1;
+        if (!(flags & kSweepNoEvents)) ctx->kernel_timed = true;
+    } else if (cols.kind == FM_BANK_F32W) {
+        RowReducePlan pl;
+        if ((rc = wide_route(ctx, cols, red, ktop, &pl)) != FM_OK) return rc;
         *out = PairSweep{};
         out->partial = (const unsigned long long*)ctx->ws_partial;
         out->nsplit = pl.nsplit; out->ncols_alloc = pl.ncols_alloc; out->f32_keys = 1;
@@ -711,7 +757,7 @@ static int knn2_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t*
     const int64_t nq = q->n;
     if (nq == 0) return FM_OK;
     PairSweep ps{};                                      // (no train rows: no partials, every slot is (-1, +inf))
-    ps.f32_keys = q->kind == FM_BANK_F32;
+    ps.f32_keys = q->kind == FM_BANK_F32 || q->kind == FM_BANK_F32W;
     int rc;
     // (output rows whose second best d2 reaches kSqrtTieMin are listed in ps.fix and redone in OpenCV's float32 order)
     if (t->n > 0 && (rc = sweep_pair(ctx, *q, *t, 2, nq, nullptr, nullptr, 0, &ps)) != FM_OK) return rc;
@@ -753,6 +799,7 @@ extern "C" int fm_knn(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k
     if (rc != FM_OK) return rc;
     if (k < 1) return fail(ctx, FM_EINVAL, "fm_knn: k must be at least 1");
     if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_knn: k above 8 is not built (cv2.BFMatcher.knnMatch takes any k; the reference calls it with 1 and 2)");
+    if (k > 2 && q->kind == FM_BANK_F32W) return refuse_bin(ctx, q, "fm_knn with k >= 3");
     const int64_t nq = q->n;
     if (nq > 0 && (!idx || !dist)) return fail(ctx, FM_EINVAL, "fm_knn: output pointer is NULL");
     if (nq == 0) return FM_OK;
@@ -1445,7 +1492,7 @@ extern "C" int fm_xcheck1_keys(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
 
 extern "C" int fm_xcheck1_keys_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int64_t t_offset, uint64_t* d_keys)
 {
-    if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return check_pair(ctx, q, t, "fm_xcheck1_keys_dev");
+    if (q && t && (bin_or_wide(q) || bin_or_wide(t))) return check_pair(ctx, q, t, "fm_xcheck1_keys_dev");
     if (ctx && d_keys)
         if (int rc = check_device_ptr(ctx, d_keys, "fm_xcheck1_keys_dev", "d_keys", false)) return rc;
     return xcheck1_keys_common(ctx, q, t, t_offset, d_keys, true);
@@ -1522,6 +1569,7 @@ extern "C" int fm_knn_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32
     if (rc != FM_OK) return rc;
     if (k < 1) return fail(ctx, FM_EINVAL, "fm_knn_dev: k must be at least 1");
     if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_knn_dev: k above 8 is not built");
+    if (k > 2 && q->kind == FM_BANK_F32W) return refuse_bin(ctx, q, "fm_knn_dev with k >= 3");
     const int64_t nq = q->n;
     if (nq == 0) return FM_OK;
     if (!d_idx || !d_dist) return fail(ctx, FM_EINVAL, "fm_knn_dev: output pointer is NULL");
@@ -1702,9 +1750,11 @@ int fm::mutual_reverse_device(fm_ctx* ctx, const Bank& t, const int32_t* cand_ro
     const float pad_aux = -3.4e38f;
     unsigned pad_aux_bits;
     memcpy(&pad_aux_bits, &pad_aux, 4);
-    const size_t rb[3][4] = {{(size_t)kDim, 4, 0, 0}, {(size_t)kDim * 4, (size_t)kDim * 2, 4, 4}, {(size_t)t.ksteps * 16, (size_t)t.ksteps * 64, 0, 0}};
-    const int route = t.kind == FM_BANK_F32 ? 1 : t.kind == FM_BANK_BIN ? 2 : 0;
-    const void* src[3][4] = {{t.rows8, t.norm, nullptr, nullptr}, {t.rowsf, t.rowsh, t.normf, t.auxf}, {t.rowsb, t.rows4, nullptr, nullptr}};
+    const size_t rb[4][4] = {{(size_t)kDim, 4, 0, 0}, {(size_t)kDim * 4, (size_t)kDim * 2, 4, 4}, {(size_t)t.ksteps * 16, (size_t)t.ksteps * 64, 0, 0},
+                             {(size_t)kWideDim * 4, (size_t)kWideDim * 2, 4, 4}};
+    const int route = t.kind == FM_BANK_F32 ? 1 : t.kind == FM_BANK_BIN ? 2 : t.kind == FM_BANK_F32W ? 3 : 0;
+    const void* src[4][4] = {{t.rows8, t.norm, nullptr, nullptr}, {t.rowsf, t.rowsh, t.normf, t.auxf}, {t.rowsb, t.rows4, nullptr, nullptr},
+                             {t.wrows, t.wrowsh, t.normf, t.auxf}};
     size_t off = 0, o_pl[4] = {0, 0, 0, 0};
     const size_t o_ri = carve(off, (size_t)n_cand * 8), o_rd = carve(off, (size_t)n_cand * 8);
     int npl = 0;
@@ -1716,13 +1766,14 @@ int fm::mutual_reverse_device(fm_ctx* ctx, const Bank& t, const int32_t* cand_ro
     *r_dist = (float*)(b + o_rd);
     GatherPlanes gp{};
     for (int i = 0; i < npl; ++i) gp.p[i] = GatherPlane{(const char*)src[route][i], b + o_pl[i], (int)rb[route][i], 0u};
-    if (route == 1) gp.p[3].pad = pad_aux_bits;
+    if (route == 1 || route == 3) gp.p[3].pad = pad_aux_bits;
     fm_bank g;
     static_cast<Bank&>(g) = bank_rows_view(t, 0, 0);      // kind, width and the scale terms: upper bounds for any subset of t's rows
     g.rows8 = nullptr; g.norm = nullptr; g.aux = nullptr; g.rowsf = nullptr; g.rowsh = nullptr; g.normf = nullptr; g.auxf = nullptr;
-    g.rowsb = nullptr; g.rows4 = nullptr;
+    g.rowsb = nullptr; g.rows4 = nullptr; g.wrows = nullptr; g.wrowsh = nullptr;
     if (route == 0) { g.rows8 = (int8_t*)gp.p[0].dst; g.norm = (int32_t*)gp.p[1].dst; }
     else if (route == 1) { g.rowsf = (float*)gp.p[0].dst; g.rowsh = (uint16_t*)gp.p[1].dst; g.normf = (float*)gp.p[2].dst; g.auxf = (float*)gp.p[3].dst; }
+    else if (route == 3) { g.wrows = (float*)gp.p[0].dst; g.wrowsh = (uint16_t*)gp.p[1].dst; g.normf = (float*)gp.p[2].dst; g.auxf = (float*)gp.p[3].dst; }
     else { g.rowsb = (uint8_t*)gp.p[0].dst; g.rows4 = (uint8_t*)gp.p[1].dst; }
     for (int64_t c0 = 0; c0 < n_cand; c0 += chunk) {
         g.n = std::min<int64_t>(chunk, n_cand - c0);
@@ -1897,7 +1948,7 @@ extern "C" int fm_match_accepted_dev_batch(fm_ctx* ctx, int32_t n, const fm_bank
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, "fm_match_accepted_dev_batch: ctx is NULL");
     for (int i = 0; q && t && i < n; ++i)
-        if (q[i] && t[i] && (q[i]->kind == FM_BANK_BIN || t[i]->kind == FM_BANK_BIN)) return check_pair(ctx, q[i], t[i], "fm_match_accepted_dev_batch");
+        if (q[i] && t[i] && (bin_or_wide(q[i]) || bin_or_wide(t[i]))) return check_pair(ctx, q[i], t[i], "fm_match_accepted_dev_batch");
     if (n > 0) {
         if (!d_rows || !d_counts) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_batch: device output pointer is NULL");
         if (int rc = check_device_rows(ctx, d_rows, d_counts, "fm_match_accepted_dev_batch")) return rc;
@@ -2059,7 +2110,7 @@ extern "C" int fm_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_ban
                                      int32_t* d_rows, int64_t* d_count, int64_t* n_accepted)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, "fm_match_accepted_dev: ctx is NULL");
-    if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return check_pair(ctx, q, t, "fm_match_accepted_dev");
+    if (q && t && (bin_or_wide(q) || bin_or_wide(t))) return check_pair(ctx, q, t, "fm_match_accepted_dev");
     if (cap < 0) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev: cap < 0");
     if (!d_rows || !d_count) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev: device output pointer is NULL");
     if (int rc = check_device_rows(ctx, d_rows, d_count, "fm_match_accepted_dev")) return rc;
@@ -2071,7 +2122,7 @@ extern "C" int fm_match_accepted_dev_async(fm_ctx* ctx, const fm_bank* q, const 
                                            int32_t* d_rows, int64_t* d_count, int64_t* h_count, void* consumer_stream)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, "fm_match_accepted_dev_async: ctx is NULL");
-    if (q && t && (q->kind == FM_BANK_BIN || t->kind == FM_BANK_BIN)) return check_pair(ctx, q, t, "fm_match_accepted_dev_async");
+    if (q && t && (bin_or_wide(q) || bin_or_wide(t))) return check_pair(ctx, q, t, "fm_match_accepted_dev_async");
     if (cap < 0) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_async: cap < 0");
     if (!d_rows || !d_count) return fail(ctx, FM_EINVAL, "fm_match_accepted_dev_async: device output pointer is NULL");
     if (int rc = check_device_rows(ctx, d_rows, d_count, "fm_match_accepted_dev_async")) return rc;

@@ -102,12 +102,12 @@ struct fm_ctx {
 };
 
 namespace fm {
-// Algorithmic bytes of a bank in a distance-kernel launch: every row read once (128 B int8, 512 B float32, the packed row
-// width of a binary bank).
+// Algorithmic bytes of a bank in a distance-kernel launch: every row read once (128 B int8, 512 B float32, 1024 B wide
+// float32, the packed row width of a binary bank).
 static inline int64_t bank_bytes(const fm::Bank* b)
 {
     if (!b) return 0;
-    return b->n * (b->kind == FM_BANK_BIN ? b->dim : b->kind == FM_BANK_F32 ? 512 : 128);
+    return b->n * (b->kind == FM_BANK_BIN ? b->dim : b->kind == FM_BANK_F32W ? 1024 : b->kind == FM_BANK_F32 ? 512 : 128);
 }
 }
 
@@ -155,10 +155,15 @@ int drain_pending(fm_ctx* ctx);
 // Everything enqueued on the context -- its own stream and the tail streams the async entry points use.
 void sync_all_streams(fm_ctx* ctx);
 // bin_ok: the entry point serves binary (FM_BANK_BIN) pairs; the others refuse them with FM_EUNSUPPORTED.  A binary bank
-// paired with a non-binary one is FM_EINVAL, empty banks included.
+// paired with a non-binary one is FM_EINVAL, empty banks included.  Wide float banks (FM_BANK_F32W) follow the same two rules
+// at the same entry points -- the bin_ok ones serve them (fm_knn: k <= 2) -- so every refusal of a wide bank is made here or
+// in refuse_bin.
 int check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who, bool bin_ok = false);
-// FM_EUNSUPPORTED for a binary bank at an entry point that takes one bank (FM_OK otherwise)
+// FM_EUNSUPPORTED for a binary or a wide float bank at an entry point that takes one bank (FM_OK otherwise)
 int refuse_bin(fm_ctx* ctx, const fm_bank* b, const char* who);
+// FM_EUNSUPPORTED for a wide float bank alone: the entry points that do serve binary banks (the collections' query banks)
+int refuse_wide(fm_ctx* ctx, const fm_bank* b, const char* who);
+static inline bool bin_or_wide(const fm_bank* b) { return b->kind == FM_BANK_BIN || b->kind == FM_BANK_F32W; }
 // Planes and scale terms of a (query = reduced, train = output rows) pair of float32 banks for x1_round_f32.
 void fill_round_f32(fm::RoundF32* r, const fm::Bank& q, const fm::Bank& t);
 // One expansion round's cross-checked 1-NN on the whole GPU (K7's delegated cross-check, api_match.hip).
@@ -319,10 +324,10 @@ __global__ __launch_bounds__(256) void mutual_join_kernel(const uint8_t* __restr
                                    double* __restrict__ ratio, uint8_t* __restrict__ pass2, int* __restrict__ block_counts2);
 namespace fm {
 // Bytes of the gathered bank per candidate: every plane the sweeps read on the output side (integer route: rows8 + norm;
-// float32 route: rowsf + rowsh + normf + auxf; binary: rowsb + rows4).
+// float32 route: rowsf + rowsh + normf + auxf; wide float32: wrows + wrowsh + normf + auxf; binary: rowsb + rows4).
 inline size_t mutual_row_bytes(const Bank& t)
 {
-    return t.kind == FM_BANK_F32 ? (size_t)kDim * 6 + 8 : t.kind == FM_BANK_BIN ? (size_t)t.ksteps * 80 : (size_t)kDim + 4;
+    return t.kind == FM_BANK_F32W ? (size_t)kWideDim * 6 + 8 : t.kind == FM_BANK_F32 ? (size_t)kDim * 6 + 8 : t.kind == FM_BANK_BIN ? (size_t)t.ksteps * 80 : (size_t)kDim + 4;
 }
 constexpr size_t kMutualGatherBytes = (size_t)1 << 30;     // fm_mutual_ratio's budget for the gathered bank (a collection: "coll_ws_bytes")
 // The reverse 2-NN lists of the candidates on the context's stream: the rows cand_rows[0 .. n_cand) of t's arrays gathered

@@ -29,7 +29,7 @@ constexpr int kAuxPerTile = 64;
 constexpr int kPadCinit   = -(1 << 25);
 
 struct Bank {
-    int      kind   = 0;       // FM_BANK_I8 / FM_BANK_F32 / FM_BANK_BIN
+    int      kind   = 0;       // FM_BANK_I8 / FM_BANK_F32 / FM_BANK_BIN / FM_BANK_F32W
     int64_t  n      = 0;
     int      dim    = 0;
     int64_t  n_pad  = 0;       // multiple of kStageRows (>= kStageRows so empty banks stage)
@@ -63,6 +63,10 @@ struct Bank {
     float*   aux6   = nullptr; // [n_pad / 128][256] accumulator start -floor(|m|^2 / 32) / 64 of a stage's rows (padding -3.4e38), 128 unused words
     int32_t* stat6  = nullptr; // [n_pad][4] |row|^2, |image|^2, |row - image|^2 (uint8 values), 0
     int32_t* max6   = nullptr; // [2] device words: the bank's largest |row|^2 and |row - image|^2
+    // FM_BANK_F32W (K14, wide_f32.hip): dim = 129 .. 256; normf, auxf, nm_max, kscale, filt_ok and vfin_max as for FM_BANK_F32,
+    // every 128-wide plane null
+    float*    wrows  = nullptr; // [n_pad][256] float32, zero padded
+    uint16_t* wrowsh = nullptr; // [n_pad][256] fp16 of the scaled rows
 };
 
 // rows rounded up to whole 128-row stages
@@ -97,6 +101,8 @@ inline Bank bank_rows_view(const Bank& b, int64_t r0, int64_t n)
     if (b.auxf)  v.auxf = b.auxf + r0;
     if (b.rowsb) v.rowsb = b.rowsb + (size_t)r0 * b.ksteps * 16;
     if (b.rows4) v.rows4 = b.rows4 + (size_t)r0 * b.ksteps * 64;
+    if (b.wrows)  v.wrows = b.wrows + (size_t)r0 * 256;
+    if (b.wrowsh) v.wrowsh = b.wrowsh + (size_t)r0 * 256;
     return v;
 }
 
@@ -276,6 +282,28 @@ hipError_t launch_hamming_prep(const uint8_t* d_src, int64_t n, int bytes, const
 // mask (K13): the bit mask of fm_knn_masked, [q.n][mwords] words, or null
 hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream,
                                const int* stage_real = nullptr, const unsigned long long* mask = nullptr, int64_t mwords = 0);
+
+// ---- K14: wide float32 banks, 129 .. 256 values per row (wide_f32.hip) ------------------------------------------------------
+constexpr int kWideDim = 256;
+// b.wrows from n source rows of FM_DT_F32 / F16 / BF16 elements `pitch` bytes apart (device memory: a staged host matrix or
+// the caller's tensor); stat[0] = largest finite magnitude (float bits), stat[1] = a value is not finite (zeroed by the caller)
+hipError_t launch_wide_copy(const void* src, int dtype, int64_t pitch, int64_t n, int dim, const Bank& b, int* stat, hipStream_t stream);
+// b.wrowsh, normf, auxf from b.wrows and b.kscale; stat[0] = largest |scaled row|^2 (float bits; zeroed by the caller)
+hipError_t launch_wide_planes(const Bank& b, int* stat, hipStream_t stream);
+// K5's kernel at the wide row: plan_rowreduce_f32's plans, K5's keys, K5's run_flag protocol
+hipError_t launch_wide_exact(const Bank& cols, const Bank& red, int ktop, const RowReducePlan& plan, unsigned long long* partial,
+                             const int* run_flag, hipStream_t stream);
+// fp16 matrix-core filter + exact rescoring into split 0 of `partial` (preset to ~0 by the caller, as the 64-bit *cnt, flag[0] and
+// gbound[0 .. cols.n_pad) to 0); flag[0] = 1 afterwards: the record list overflowed and launch_wide_exact must redo the call
+struct WideFilterPlan {
+    int nchunks = 0, ntiles = 0, nsplit = 0, tiles_per_split = 0;
+    unsigned cap = 0;                                    // records of the list
+    size_t list_bytes() const { return (size_t)cap * 8; }       // (and cap * 4 for the records' scores)
+};
+bool wide_filter_usable(const Bank& cols, const Bank& red);
+WideFilterPlan plan_wide_filter(int64_t ncols_pad, int64_t ncols, int64_t nred_pad, const Tuning& tn);
+hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const WideFilterPlan& plan, uint2* list, float* lscore,
+                              unsigned* gbound, unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream);
 
 // ---- K13: k-NN under a bit mask (masked.hip) ------------------------------------------------------------------------------
 // Integer route, k = 1 or 2, on the matrix cores: the masked top-k of every row of q over the rows of t (t may be a

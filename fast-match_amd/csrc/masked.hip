@@ -355,6 +355,7 @@ static int pair_masked_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, co
     if (!q || !t) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
     if (!m) return fail(ctx, FM_EINVAL, std::string(who) + ": mask is NULL");
     int rc = check_pair(ctx, q, t, who, true);
+    if (rc == FM_OK) rc = refuse_wide(ctx, q, who);
     if (rc != FM_OK) return rc;
     if (k < 1) return fail(ctx, FM_EINVAL, std::string(who) + ": k must be at least 1");
     if (k > 8) return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": k above 8 is not built");

@@ -1,0 +1,594 @@
+// K14 -- wide float32 banks (FM_BANK_F32W): rows of 129 .. 256 values.  gfx950 only.
+//
+// The contract is K5's (dist_f32.hip) at the wider row: dist = sqrtf(s), s = fmaf(v_k, v_k, s), v_k = a_k - b_k in float32,
+// k ascending over the real dim -- the oracle's order 1 -- and keys (float32 distance bits << 32 | reduced row) per split of the
+// reduction range in `partial`, so the merge / election / compaction kernels behind a sweep serve wide banks unchanged.
+//
+// Planes of a wide bank (Bank::wrows ...; the 128-wide planes of the other kinds stay null):
+//   wrows  float32 [n_pad][256]  the rows, ZERO PADDED from dim to 256 and from n to n_pad.  The chain may run past dim: a
+//                                padding term is fmaf(+0, +0, s) = s for every s (s starts at +0 and never becomes -0; inf and
+//                                NaN stay what they are), so the kernels stop at dim rounded up to their unroll step, not at dim.
+//   wrowsh fp16    [n_pad][256]  the rows times 2^kscale (K8's rule: the bank's largest finite magnitude lies in [2^13, 2^14)),
+//                                rounded to nearest even
+//   normf  float32 [n_pad]       |scaled row|^2 (summed in float64)
+//   auxf   float32 [n_pad]       -|scaled row|^2 / 2; padding rows -3.4e38
+// Part 1 writes them in two kernels: one pass over the source (host rows staged as a dense float32 matrix, or a device
+// tensor of float32 / half / bfloat16 read in place at its pitch, widened exactly) that leaves wrows and the largest finite
+// magnitude / the "every value is finite" flag, then the scaled planes from wrows.  Host and device creators run the same
+// two kernels on the same values, so they build the same bank bit for bit.
+//
+// Part 2, wide_exact_kernel: K5's tiling (256 threads, 64 x 64 rows per step, 4 x 4 patch per thread, k-major LDS images);
+// the output rows' image holds all 256 k (68 KiB), the reduced rows' is staged in two halves of 128 k (34 KiB) with the
+// accumulators carried across, which keeps the chain's order.  Bound: fp32 VALU, 2 ops per pair-dimension.
+//
+// Part 3, wide_filter_kernel + wide_rescore_kernel: the threshold form (radius_f16_kernel's), with a RUNNING threshold.
+// Every wave keeps two blocks of 16 output rows as the B operand of v_mfma_f32_16x16x32_f16 in registers (KS = ceil(dim / 32)
+// K steps, 4 VGPRs each: 64 VGPRs at 256-D, which is why it is two blocks and not K8's four) and streams the reduced rows'
+// fp16 plane as the A operand straight from memory, one 16-row tile ahead (32 more VGPRs at KS = 8; the four waves of a
+// workgroup read the same tiles, so three of four reads hit the cache; no LDS, no barrier).  A lane holds, per block, the
+// scores s = q.t 2^(kt - kq) - |t'|^2 / 2 of ONE output row against 4 reduced rows of the tile; d2 = |q'|^2 - 2 s in the
+// reduced bank's scale, so a larger score is a nearer row.  It keeps the KTOP best scores it has seen; the KTOP-th best,
+// shared after every tile among the 4 lanes that own the same output row (max: any lane's is a valid bound), is the bound B.
+// A reduced row whose score reaches B - M is appended to one global list of (output row, reduced row) records; every row of
+// the exact top-KTOP is among them (margin below).  Most records are made early in a sweep, against a bound that is
+// still poor; every wave leaves its final bound in gbound[output row] (atomic maximum) and wide_rescore_kernel drops the
+// records whose score lies below that final bound minus M -- the same test against a better bound -- before it runs the
+// exact chain for the rest, one thread per record, and inserts the key into split 0 of `partial` with 64-bit atomic minima -- top-2: the loser of the first
+// slot's minimum goes to the second slot's, which leaves the two smallest keys whatever the order of arrival, because no
+// (output row, reduced row) pair is recorded twice.  A list that overflows (cap records) sets flag[0] and the exact kernel
+// redoes the whole call behind it, K8's protocol (run_flag); the overflow is sticky (64-bit count of reserved slots, a wave
+// stops recording once its reservation fails: wide_push), however many records a call would make; there is no per-row rescan: a row that is hard for the
+// filter only makes the list longer.  Padding rows are excluded by index.
+//
+// Margin.  Scores are compared in the reduced bank's scale; q' = 2^kt q, t' = 2^kt t below.  Sources of |s_fp16 - s_real|:
+//   * operand rounding: both operands carry a relative error <= 2^-11 (fp16 subnormals: an absolute 2^-25 against a bank whose
+//     largest value is >= 2^13, far below everything here), so each product errs by <= (2^-10 + 2^-22) |q'_k t'_k| and the
+//     sum by <= 2^-10 |q'||t'| (1 + 2^-12) <= 2^-11 (|q'|^2 + |t'|^2)(1 + 2^-12), whatever the number of terms;
+//   * the matrix core's float32 accumulation of n <= 256 exact fp16 products: <= n 2^-24 sum |products| <= 2^-16 |q'||t'|;
+//   * -|t'|^2 / 2 rounded to float32 and the final fmaf: 2^-24 (|t'|^2 + |s|).
+// So |s_fp16 - s_real| <= E = 2^-11 (1 + 2^-4) (|q'|^2 + max |t'|^2).  The exact chain's d2 differs from the real d2 by
+// <= n 2^-24 d2 <= 2^-15 (|q'|^2 + |t'|^2), i.e. 2^-16 (...) in score units, and two d2 that share a float32 root differ by
+// 2^-22 relative: both inside the 2^-4 slack as well.  A row x of the exact top-KTOP has s_real(x) >= s_real of the KTOP-th
+// best of ANY KTOP rows, so s_fp16(x) >= B - 2 E.  M = 1.25 * 2^-10 * (|q'|^2 + max |t'|^2) against 2 E = 1.0625 * 2^-10 (...):
+// K8's constant 1.1 enlarged to 1.25 for the terms that grow with n.
+// Banks of different scales: the score is rescaled by 2^(kt - kq) (exact); pairs whose exponents differ by more than 8
+// take the exact kernel.
+#include "fm_internal.h"
+#include <algorithm>
+
+namespace fm {
+
+typedef _Float16 w_v8h __attribute__((ext_vector_type(8)));
+typedef float    w_v4f __attribute__((ext_vector_type(4)));
+
+// ---------------------------------------------------------------------------------------
+// part 1: preparation
+// ---------------------------------------------------------------------------------------
+template <int DT>
+__device__ __forceinline__ float wide_src_elem(const uint8_t* __restrict__ rowp, int k)
+{
+    if constexpr (DT == FM_DT_F32) return ((const float*)rowp)[k];
+    else if constexpr (DT == FM_DT_F16) return (float)((const _Float16*)rowp)[k];
+    else return __uint_as_float((unsigned)((const uint16_t*)rowp)[k] << 16);
+}
+
+// wrows from the source; stat[0] = largest finite magnitude (float bits), stat[1] |= 1 if a value is not finite
+template <int DT>
+__global__ __launch_bounds__(256)
+void wide_copy_kernel(const uint8_t* __restrict__ src, int64_t pitch, int64_t n, int dim, float* __restrict__ dst, int64_t n_pad,
+                      int* __restrict__ stat)
+{
+    float m = 0.f;
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_pad * kWideDim; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i >> 8;
+        const int k = (int)(i & (kWideDim - 1));
+        const float v = (row < n && k < dim) ? wide_src_elem<DT>(src + row * pitch, k) : 0.f;
+        dst[i] = v;
+        const float a = fabsf(v);
+        const bool fin = a <= 3.0e38f;
+        bad |= !fin;
+        m = fin ? fmaxf(m, a) : m;
+    }
+#pragma unroll
+    for (int mask = 1; mask < 64; mask <<= 1) m = fmaxf(m, __shfl_xor(m, mask));
+    if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(stat + 1, 1);
+    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(stat, (int)__float_as_uint(m));
+}
+
+// the scaled planes from wrows: 32 lanes per row, 8 values per lane; stat[0] = largest |scaled row|^2
+__global__ __launch_bounds__(256)
+void wide_planes_kernel(const float* __restrict__ rows, int64_t n, int64_t n_pad, int k, uint16_t* __restrict__ rowsh,
+                        float* __restrict__ normf, float* __restrict__ auxf, int* __restrict__ stat)
+{
+    const int64_t row = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
+    const int c = threadIdx.x & 31;
+    if (row >= n_pad) return;
+    const float4 v0 = *(const float4*)(rows + row * kWideDim + 8 * c);
+    const float4 v1 = *(const float4*)(rows + row * kWideDim + 8 * c + 4);
+    const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    unsigned h[8];
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float x = ldexpf(v[i], k);
+        const _Float16 hx = (_Float16)x;
+        h[i] = (unsigned)__builtin_bit_cast(unsigned short, hx);
+        ss += (double)x * (double)x;
+    }
+    *(uint4*)(rowsh + row * kWideDim + 8 * c) =
+        make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+#pragma unroll
+    for (int mask = 1; mask < 32; mask <<= 1) ss += __shfl_xor(ss, mask);
+    const float nm = (float)ss;
+    if (c == 0) {
+        normf[row] = row < n ? nm : 0.f;
+        auxf[row] = row < n ? -0.5f * nm : -3.4e38f;
+    }
+    float m = (c == 0 && row < n) ? nm : 0.f;
+    m = fmaxf(m, __shfl_xor(m, 32));
+    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(stat, (int)__float_as_uint(m));
+}
+
+hipError_t launch_wide_copy(const void* src, int dtype, int64_t pitch, int64_t n, int dim, const Bank& b, int* stat, hipStream_t stream)
+{
+    const dim3 grid((unsigned)std::min<int64_t>(2048, (b.n_pad * kWideDim + 255) / 256));
+#define FM_WIDE_COPY(DT_)                                                                                                  \
+    case DT_: hipLaunchKernelGGL((wide_copy_kernel<DT_>), grid, dim3(256), 0, stream, (const uint8_t*)src, pitch, n, dim, b.wrows, b.n_pad, stat); break;
+    switch (dtype) {
+        FM_WIDE_COPY(FM_DT_F32) FM_WIDE_COPY(FM_DT_F16) FM_WIDE_COPY(FM_DT_BF16)
+        default: return hipErrorInvalidValue;
+    }
+#undef FM_WIDE_COPY
+    return hipGetLastError();
+}
+
+hipError_t launch_wide_planes(const Bank& b, int* stat, hipStream_t stream)
+{
+    hipLaunchKernelGGL(wide_planes_kernel, dim3((unsigned)(b.n_pad / 8)), dim3(256), 0, stream, (const float*)b.wrows, b.n, b.n_pad, b.kscale,
+                       b.wrowsh, b.normf, b.auxf, stat);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// part 2: the exact all-pairs kernel
+// ---------------------------------------------------------------------------------------
+constexpr int kWTile = 64;                 // rows per block step, both sides
+constexpr int kWLd   = kWTile + 4;         // padded leading dimension (floats) of the k-major images
+constexpr int kWHalf = 128;                // k per staged half of the reduced rows
+
+struct WideExactParams {
+    const float* col_rows;    // [ncols_pad][256]
+    int          ncols_pad;
+    const float* red_rows;    // [nred_pad][256]
+    int          nred;        // real rows
+    int          nsteps;      // ceil(nred_pad / 64)
+    int          nred_pad;
+    int          nsplit;
+    int          steps_per_split;
+    int          ncols_alloc;
+    int          kend;        // dim rounded up to 8 (129 .. 256: the second half's length is kend - 128)
+    unsigned long long* partial;
+    const int*   run_flag;    // null, or: skip the whole launch unless *run_flag != 0
+};
+
+// NK4 float4 per row from column k0 of 64 rows into the k-major image img[k - k0][row]; rows from row_end on read as zeros
+template <int NK4>
+__device__ __forceinline__ void wide_load_kmajor(const float* __restrict__ rows, int row0, int row_end, int k0, float* __restrict__ img, int tid)
+{
+#pragma unroll
+    for (int i = 0; i < NK4 / 4; ++i) {
+        const int f4 = tid + 256 * i;              // 0 .. 64 * NK4 - 1
+        const int r = f4 / NK4, k4 = (f4 % NK4) * 4;
+        const float4 v = (row0 + r < row_end) ? *(const float4*)(rows + (size_t)(row0 + r) * kWideDim + k0 + k4) : float4{0.f, 0.f, 0.f, 0.f};
+        img[(k4 + 0) * kWLd + r] = v.x;
+        img[(k4 + 1) * kWLd + r] = v.y;
+        img[(k4 + 2) * kWLd + r] = v.z;
+        img[(k4 + 3) * kWLd + r] = v.w;
+    }
+}
+
+template <int KTOP>
+__global__ __launch_bounds__(256)
+void wide_exact_kernel(WideExactParams p)
+{
+    __shared__ __attribute__((aligned(16))) float colimg[kWideDim * kWLd];
+    __shared__ __attribute__((aligned(16))) float redimg[kWHalf * kWLd];
+
+    if (p.run_flag) {
+        if (*p.run_flag == 0) return;                 // the filter's result stands
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd((int*)p.run_flag + 2, 1);
+    }
+    const int tid = threadIdx.x;
+    const int tn = tid & 15, tm = tid >> 4;
+    const int split = blockIdx.x % p.nsplit;
+    const int chunk = blockIdx.x / p.nsplit;
+    const int c0 = chunk * kWTile;
+
+    if (c0 < p.ncols_pad) wide_load_kmajor<64>(p.col_rows, c0, p.ncols_pad, 0, colimg, tid);
+
+    float bd[4][KTOP];
+    int   bi[4][KTOP];
+    float thr[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        thr[i] = INFINITY;
+#pragma unroll
+        for (int k = 0; k < KTOP; ++k) { bd[i][k] = INFINITY; bi[i][k] = -1; }
+    }
+
+    const int s0 = split * p.steps_per_split;
+    const int s1 = min(s0 + p.steps_per_split, p.nsteps);
+    for (int st = s0; st < s1; ++st) {
+        float s[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s[i][j] = 0.f;
+        for (int h = 0; h < 2; ++h) {
+            __syncthreads();                                   // previous redimg fully consumed
+            wide_load_kmajor<32>(p.red_rows, st * kWTile, p.nred_pad, h * kWHalf, redimg, tid);
+            __syncthreads();
+            const float* ci = colimg + h * kWHalf * kWLd;
+            const int kn = h == 0 ? kWHalf : p.kend - kWHalf;
+#pragma unroll 8
+            for (int k = 0; k < kn; ++k) {
+                const float4 a = *(const float4*)(ci + k * kWLd + 4 * tn);
+                const float4 b = *(const float4*)(redimg + k * kWLd + 4 * tm);
+                const float av[4] = {a.x, a.y, a.z, a.w};
+                const float bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float v = av[i] - bv[j];
+                        s[i][j] = __builtin_fmaf(v, v, s[i][j]);
+                    }
+            }
+        }
+        const int m0 = st * kWTile + 4 * tm;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float mn = fminf(fminf(s[i][0], s[i][1]), fminf(s[i][2], s[i][3]));
+            if (mn <= thr[i]) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int idx = m0 + j;
+                    if (idx < p.nred && s[i][j] <= thr[i]) {
+                        const float d = sqrtf(s[i][j]);
+                        if (d < bd[i][KTOP - 1]) {            // strict: earlier row wins ties
+                            if constexpr (KTOP == 2) {
+                                if (d < bd[i][0]) { bd[i][1] = bd[i][0]; bi[i][1] = bi[i][0]; bd[i][0] = d; bi[i][0] = idx; }
+                                else              { bd[i][1] = d; bi[i][1] = idx; }
+                            } else {
+                                bd[i][0] = d; bi[i][0] = idx;
+                            }
+                            const float B = bd[i][KTOP - 1];
+                            thr[i] = (B * B) * 1.00000024f;    // d2 > thr  =>  sqrtf(d2) >= B
+                        }
+                    }
+                }
+            }
+        }
+    }
+
+    // merge the 16 threads (tm) that own the same column through LDS (reuse redimg)
+    __syncthreads();
+    float* md = redimg;                                        // [64 cols][16][KTOP]
+    int* mi = (int*)(redimg + kWTile * 16 * KTOP);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < KTOP; ++k) {
+            md[((4 * tn + i) * 16 + tm) * KTOP + k] = bd[i][k];
+            mi[((4 * tn + i) * 16 + tm) * KTOP + k] = bi[i][k];
+        }
+    __syncthreads();
+    if (tid < kWTile) {
+        const int n = c0 + tid;
+        float rd[KTOP]; int ri[KTOP];
+#pragma unroll
+        for (int k = 0; k < KTOP; ++k) { rd[k] = INFINITY; ri[k] = -1; }
+        for (int t = 0; t < 16; ++t)
+#pragma unroll
+            for (int k = 0; k < KTOP; ++k) {
+                const float d = md[(tid * 16 + t) * KTOP + k];
+                const int ix = mi[(tid * 16 + t) * KTOP + k];
+                if (ix < 0) continue;
+                const bool b0 = ri[0] < 0 || d < rd[0] || (d == rd[0] && ix < ri[0]);
+                if constexpr (KTOP == 2) {
+                    const bool b1 = ri[1] < 0 || d < rd[1] || (d == rd[1] && ix < ri[1]);
+                    if (b0) { rd[1] = rd[0]; ri[1] = ri[0]; rd[0] = d; ri[0] = ix; }
+                    else if (b1) { rd[1] = d; ri[1] = ix; }
+                } else {
+                    if (b0) { rd[0] = d; ri[0] = ix; }
+                }
+            }
+        if (n < p.ncols_alloc) {
+            unsigned long long* out = p.partial + ((size_t)split * p.ncols_alloc + n) * KTOP;
+#pragma unroll
+            for (int k = 0; k < KTOP; ++k)
+                out[k] = (ri[k] >= 0 && n < p.ncols_pad)
+                    ? (((unsigned long long)__float_as_uint(rd[k]) << 32) | (unsigned)ri[k]) : ~0ull;
+        }
+    }
+}
+
+hipError_t launch_wide_exact(const Bank& cols, const Bank& red, int ktop, const RowReducePlan& plan, unsigned long long* partial,
+                             const int* run_flag, hipStream_t stream)
+{
+    WideExactParams p;
+    p.run_flag = run_flag;
+    p.col_rows = cols.wrows;
+    p.ncols_pad = (int)cols.n_pad;
+    p.red_rows = red.wrows;
+    p.nred = (int)red.n;
+    p.nsteps = (int)((red.n_pad + kWTile - 1) / kWTile);
+    p.nred_pad = (int)red.n_pad;
+    p.nsplit = plan.nsplit;
+    p.steps_per_split = plan.stages_per_split;
+    p.ncols_alloc = plan.ncols_alloc;
+    p.kend = (cols.dim + 7) & ~7;
+    p.partial = partial;
+    const int grid = plan.nchunks * plan.nsplit;
+    if (ktop == 1) hipLaunchKernelGGL((wide_exact_kernel<1>), dim3(grid), dim3(256), 0, stream, p);
+    else           hipLaunchKernelGGL((wide_exact_kernel<2>), dim3(grid), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// part 3: fp16 matrix-core filter + exact rescoring
+// ---------------------------------------------------------------------------------------
+constexpr int kWFBlocks = 2;                       // blocks of 16 output rows per wave
+constexpr int kWFCols   = 4 * 16 * kWFBlocks;      // output rows per workgroup (4 waves)
+
+struct WideFilterParams {
+    const uint16_t* colh;  const float* colnorm;  int ncols;     // output rows: fp16 plane, |scaled row|^2, real rows
+    const uint16_t* redh;  const float* redaux;   int nred;      // reduced rows: fp16 plane, -|scaled row|^2 / 2, real rows
+    float cscale;          // 2^(kred - kcol): a dot product of the two planes in the reduced bank's scale
+    float nscale;          // 2^(2 (kred - kcol)): the output rows' norms in the reduced bank's scale
+    float red_nm_max;
+    int   ntiles, tiles_per_split, nsplit;
+    uint2* list; float* lscore; unsigned cap; unsigned long long* cnt;    // records (output row, reduced row), their scores, the count
+    unsigned* gbound;      // [ncols_pad] the best bound any wave reached per output row, as ordered bits (wide_fbits)
+};
+
+// float -> unsigned whose order is the floats' (atomicMax on it; 0 lies below every float)
+__device__ __forceinline__ unsigned wide_fbits(float f)
+{
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float wide_bits_f(unsigned k)
+{
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ float wide_margin(float colnorm, float nscale, float red_nm_max)
+{
+    return 1.25f * 0.0009765625f * (colnorm * nscale + red_nm_max);
+}
+
+// The list is handed out in chunks of 64 slots, one atomic per chunk and wave: an atomic per push on the one counter would
+// serialise the whole sweep.  base / used: the wave's current chunk (wave uniform; base kWNoChunk = none yet).  A chunk that
+// cannot take a push is padded with empty records (output row kWNoRecord) and a new one reserved; *cnt counts reserved slots,
+// every one of which below cap is written.  The overflow is STICKY: *cnt is a 64-bit word (2^58 reservations before it could
+// wrap), and a wave whose reservation starts at or beyond cap stops recording for good (base kWFull) -- the call is redone by
+// the exact kernel anyway -- so the count only ever says "more than cap" once it has.
+constexpr unsigned kWNoChunk = 0xffffffffu, kWFull = 0xfffffffeu, kWNoRecord = 0xffffffffu;
+
+__device__ __forceinline__ void wide_pad_chunk(unsigned base, unsigned used, const WideFilterParams& p)
+{
+    const unsigned lane = threadIdx.x & 63;
+    if (base < kWFull && lane >= used && base + lane < p.cap) p.list[base + lane] = make_uint2(kWNoRecord, 0u);
+}
+
+// one record per set lane of `pred`
+__device__ __forceinline__ void wide_push(bool pred, int col, int row, float score, const WideFilterParams& p, unsigned& base, unsigned& used)
+{
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(pred);
+    if (m == 0ull || base == kWFull) return;
+    const unsigned lane = threadIdx.x & 63;
+    const unsigned n = (unsigned)__builtin_popcountll(m);
+    if (base == kWNoChunk || used + n > 64u) {
+        wide_pad_chunk(base, used, p);
+        unsigned nb = 0;
+        if (lane == 0) {
+            const unsigned long long r = atomicAdd(p.cnt, 64ull);
+            nb = r >= p.cap ? kWFull : (unsigned)r;             // (cap <= 2^24, a multiple of 64)
+        }
+        base = (unsigned)__builtin_amdgcn_readfirstlane((int)nb);
+        used = 0;
+        if (base == kWFull) return;
+    }
+    const unsigned at = base + used + (unsigned)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+    if (pred && at < p.cap) { p.list[at] = make_uint2((unsigned)col, (unsigned)row); p.lscore[at] = score; }
+    used += n;
+}
+
+template <int KS, int KTOP>
+__global__ __launch_bounds__(256)
+void wide_filter_kernel(WideFilterParams p)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lr = lane & 15, lg = lane >> 4;
+    const int split = blockIdx.x % p.nsplit;
+    const int c0 = (blockIdx.x / p.nsplit) * kWFCols + wave * 16 * kWFBlocks;
+
+    w_v8h bq[kWFBlocks][KS];
+    float marg[kWFBlocks], bnd[kWFBlocks], best[kWFBlocks][KTOP];
+#pragma unroll
+    for (int b = 0; b < kWFBlocks; ++b) {
+        const int col = c0 + 16 * b + lr;                       // (< the bank's n_pad: a multiple of 128 = kWFCols)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) bq[b][ks] = *(const w_v8h*)(p.colh + (size_t)col * kWideDim + 32 * ks + 8 * lg);
+        marg[b] = wide_margin(p.colnorm[col], p.nscale, p.red_nm_max);
+        bnd[b] = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < KTOP; ++k) best[b][k] = -INFINITY;
+    }
+
+    const int t0 = split * p.tiles_per_split;
+    const int t1 = min(t0 + p.tiles_per_split, p.ntiles);
+    unsigned lbase = kWNoChunk, lused = 0;
+    w_v8h an[KS];
+    if (t0 < t1) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) an[ks] = *(const w_v8h*)(p.redh + (size_t)(t0 * 16 + lr) * kWideDim + 32 * ks + 8 * lg);
+    }
+    for (int t = t0; t < t1; ++t) {
+        w_v8h a[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) a[ks] = an[ks];
+        if (t + 1 < t1) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) an[ks] = *(const w_v8h*)(p.redh + (size_t)((t + 1) * 16 + lr) * kWideDim + 32 * ks + 8 * lg);
+        }
+        const int r0 = t * 16 + 4 * lg;                         // this lane's 4 reduced rows
+        const float4 ax4 = *(const float4*)(p.redaux + r0);
+        const float ax[4] = {ax4.x, ax4.y, ax4.z, ax4.w};
+#pragma unroll
+        for (int b = 0; b < kWFBlocks; ++b) {
+            w_v4f acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[ks], bq[b][ks], acc, 0, 0, 0);
+            const int col = c0 + 16 * b + lr;
+            // the tile's scores first into the lane's best, the bound shared among the 4 lanes of the output row, THEN the
+            // test: a row is recorded against a bound that already knows its own tile
+            float sc[4];
+            bool real[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                sc[r] = __builtin_fmaf(acc[r], p.cscale, ax[r]);
+                real[r] = r0 + r < p.nred && col < p.ncols;
+                if (real[r]) {
+                    if constexpr (KTOP == 2) {
+                        if (sc[r] > best[b][0]) { best[b][1] = best[b][0]; best[b][0] = sc[r]; }
+                        else if (sc[r] > best[b][1]) best[b][1] = sc[r];
+                    } else {
+                        if (sc[r] > best[b][0]) best[b][0] = sc[r];
+                    }
+                }
+            }
+            bnd[b] = fmaxf(bnd[b], best[b][KTOP - 1]);
+            bnd[b] = fmaxf(bnd[b], __shfl_xor(bnd[b], 16));
+            bnd[b] = fmaxf(bnd[b], __shfl_xor(bnd[b], 32));
+#pragma unroll
+            for (int r = 0; r < 4; ++r) wide_push(real[r] && sc[r] >= bnd[b] - marg[b], col, r0 + r, sc[r], p, lbase, lused);
+        }
+    }
+    wide_pad_chunk(lbase, lused, p);
+    // the bound this wave ended with, for the rescoring's second look at the records
+    if (lg == 0) {
+#pragma unroll
+        for (int b = 0; b < kWFBlocks; ++b)
+            if (bnd[b] > -INFINITY) atomicMax(p.gbound + c0 + 16 * b + lr, wide_fbits(bnd[b]));
+    }
+}
+
+struct WideRescoreParams {
+    const float* col_rows; const float* red_rows; int dim;
+    const uint2* list; const float* lscore; unsigned cap; const unsigned long long* cnt;
+    const unsigned* gbound; const float* colnorm; float nscale, red_nm_max;
+    unsigned long long* partial;      // split 0: [ncols_alloc][KTOP]
+    int* flag;                        // [0] = 1: the list overflowed, the exact kernel redoes the call
+};
+
+template <int KTOP>
+__global__ __launch_bounds__(256)
+void wide_rescore_kernel(WideRescoreParams p)
+{
+    const unsigned long long n64 = *p.cnt;
+    const unsigned n = (unsigned)n64;
+    if (n64 > p.cap) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) p.flag[0] = 1;
+        return;
+    }
+    for (unsigned e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
+        const uint2 rec = p.list[e];
+        if (rec.x == kWNoRecord) continue;                      // the padding of a chunk
+        // most records were made against a bound of the sweep's first tiles: the output row's final bound drops them
+        if (p.lscore[e] < wide_bits_f(p.gbound[rec.x]) - wide_margin(p.colnorm[rec.x], p.nscale, p.red_nm_max)) continue;
+        const float4* a = (const float4*)(p.col_rows + (size_t)rec.x * kWideDim);
+        const float4* b = (const float4*)(p.red_rows + (size_t)rec.y * kWideDim);
+        float s = 0.f;
+        const int k4n = (p.dim + 3) >> 2;                       // (zero padding past dim: see the file comment)
+        for (int k4 = 0; k4 < k4n; ++k4) {
+            const float4 x = a[k4], y = b[k4];
+            float v = x.x - y.x; s = __builtin_fmaf(v, v, s);
+            v = x.y - y.y; s = __builtin_fmaf(v, v, s);
+            v = x.z - y.z; s = __builtin_fmaf(v, v, s);
+            v = x.w - y.w; s = __builtin_fmaf(v, v, s);
+        }
+        const float d = sqrtf(s);
+        if (!(d < INFINITY)) continue;                          // K5's rule: an infinite or NaN distance is no candidate
+        const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | rec.y;
+        unsigned long long* out = p.partial + (size_t)rec.x * KTOP;
+        const unsigned long long old = atomicMin(out, key);
+        if constexpr (KTOP == 2) atomicMin(out + 1, old > key ? old : key);
+    }
+}
+
+bool wide_filter_usable(const Bank& cols, const Bank& red)
+{
+    if (!cols.filt_ok || !red.filt_ok || !cols.wrowsh || !red.wrowsh) return false;
+    const int dk = red.kscale - cols.kscale;
+    return dk >= -8 && dk <= 8;
+}
+
+WideFilterPlan plan_wide_filter(int64_t ncols_pad, int64_t ncols, int64_t nred_pad, const Tuning& tn)
+{
+    WideFilterPlan pl;
+    pl.nchunks = (int)((ncols_pad + kWFCols - 1) / kWFCols);
+    pl.ntiles = (int)(nred_pad / 16);
+    // a split starts with an empty bound and records its first tile whole: at least 64 tiles (1024 rows) per split
+    int64_t nsplit = (512 + pl.nchunks - 1) / pl.nchunks;
+    if (nsplit > pl.ntiles / 64) nsplit = pl.ntiles / 64;
+    if (tn.f32_nsplit > 0) nsplit = tn.f32_nsplit;
+    if (nsplit > pl.ntiles) nsplit = pl.ntiles;
+    if (nsplit < 1) nsplit = 1;
+    pl.tiles_per_split = (int)((pl.ntiles + nsplit - 1) / nsplit);
+    pl.nsplit = (pl.ntiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
+    int64_t cap = 256 * ncols;                                  // (a multiple of the chunk)
+    if (cap < (1 << 20)) cap = 1 << 20;
+    if (cap > (1 << 24)) cap = 1 << 24;
+    pl.cap = (unsigned)cap;
+    return pl;
+}
+
+template <int KS, int KTOP>
+static void wide_filter_launch(const WideFilterParams& p, int grid, hipStream_t stream)
+{
+    hipLaunchKernelGGL((wide_filter_kernel<KS, KTOP>), dim3(grid), dim3(256), 0, stream, p);
+}
+
+hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const WideFilterPlan& plan, uint2* list, float* lscore,
+                              unsigned* gbound, unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream)
+{
+    WideFilterParams p;
+    p.colh = cols.wrowsh; p.colnorm = cols.normf; p.ncols = (int)cols.n;
+    p.redh = red.wrowsh; p.redaux = red.auxf; p.nred = (int)red.n;
+    const int dk = red.kscale - cols.kscale;
+    p.cscale = ldexpf(1.f, dk);
+    p.nscale = ldexpf(1.f, 2 * dk);
+    p.red_nm_max = red.nm_max;
+    p.ntiles = plan.ntiles; p.tiles_per_split = plan.tiles_per_split; p.nsplit = plan.nsplit;
+    p.list = list; p.lscore = lscore; p.cap = plan.cap; p.cnt = cnt; p.gbound = gbound;
+    const int grid = plan.nchunks * plan.nsplit;
+    const int ks = (cols.dim + 31) / 32;
+    if (ks < 5 || ks > 8) return hipErrorInvalidValue;
+#define FM_WIDE_F(KS_)                                                                            \
+    case KS_: if (ktop == 1) wide_filter_launch<KS_, 1>(p, grid, stream); else wide_filter_launch<KS_, 2>(p, grid, stream); break;
+    switch (ks) { FM_WIDE_F(5) FM_WIDE_F(6) FM_WIDE_F(7) FM_WIDE_F(8) }
+#undef FM_WIDE_F
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    WideRescoreParams r;
+    r.col_rows = cols.wrows; r.red_rows = red.wrows; r.dim = cols.dim;
+    r.list = list; r.lscore = lscore; r.cap = plan.cap; r.cnt = cnt; r.partial = partial; r.flag = flag;
+    r.gbound = gbound; r.colnorm = cols.normf; r.nscale = p.nscale; r.red_nm_max = red.nm_max;
+    if (ktop == 1) hipLaunchKernelGGL((wide_rescore_kernel<1>), dim3(2048), dim3(256), 0, stream, r);
+    else           hipLaunchKernelGGL((wide_rescore_kernel<2>), dim3(2048), dim3(256), 0, stream, r);
+    return hipGetLastError();
+}
+
+}  // namespace fm

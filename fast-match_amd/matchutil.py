@@ -19,6 +19,10 @@ Mirrors ``matchutil.py`` of the reference:
   crossCheck)``); ``bf_match``, ``flann_match`` and ``ratio_match_arrays`` honour it, ``bf_radius_match`` does not
   (``ValueError``), nor does anything else take ``NORM_HAMMING2``.  Without ``normType`` every array is an L2 bank,
   a uint8 [n, 32] array included.
+* Wide float descriptors -- float arrays of 129 .. 256 values per row, SuperPoint's 256-D rows for one -- go to the
+  library's wide float banks under ``NORM_L2``: ``bf_match`` with k <= 2 and with crossCheck, ``ratio_match_arrays`` and
+  ``mutual_ratio_match_arrays`` take them; ``bf_radius_match``, a mask, k >= 3 and ``BFMatcher.add`` raise ``ValueError``
+  before anything is uploaded.
 * ``options["mask"]``: cv2's ``mask`` argument of ``knnMatch`` -- an ``[nq, nt]`` uint8 / bool array, nonzero = the pair
   (query row, train row) may be matched, or a resident ``_ffi.Mask`` (``Context.mask``).  ``bf_match``,
   ``bf_match_arrays``, ``flann_match`` and ``flann_match_arrays`` honour it when crossCheck is off: every list is the
@@ -137,6 +141,22 @@ def _rows_of(d):
     return d.n if isinstance(d, _ffi.Bank) else np.asarray(d).shape[0]
 
 
+def _is_wide(d):
+    """A wide float operand: a resident FM_BANK_F32W bank, or a float array of more than 128 columns."""
+    if isinstance(d, _ffi.Bank):
+        return d.kind == _ffi.FM_BANK_F32W
+    a = np.asarray(d)
+    return a.ndim == 2 and a.shape[1] > 128 and a.dtype != np.uint8
+
+
+def _refuse_wide(who, what, *operands):
+    """ValueError BEFORE anything is uploaded: wide float descriptors (129 .. 256 values per row) are served by knnMatch with
+    k <= 2, crossCheck, the ratio match and the mutual ratio match only."""
+    if any(_is_wide(d) for d in operands):
+        raise ValueError("%s: %s is not built for wide float descriptors (129 .. 256 values per row: k <= 2, crossCheck, "
+                         "ratio_match_arrays and mutual_ratio_match_arrays are)" % (who, what))
+
+
 def _mask_array(m, nq, nt, what):
     """A host mask as a uint8 [nq, nt] array, or ValueError."""
     a = np.asarray(m)
@@ -183,6 +203,10 @@ def bf_match_arrays(dt1, dt2, k=1, options={}):
     crossCheck = k == 1 and options.get("crossCheck", False) == True   # noqa: E712  (reference semantics)
     norm = _norm_type(options, dt1, dt2)
     mask = _mask_option(options, dt1, dt2, "bf_match", "crossCheck" if crossCheck else None)
+    if mask is not None:
+        _refuse_wide("bf_match", "a mask", dt1, dt2)
+    if k > 2:
+        _refuse_wide("bf_match", "k >= 3", dt1, dt2)
     ctx = _context(options)
     qb, q_tmp, tb, t_tmp = _bank_pair(ctx, dt1, dt2, norm)
     try:
@@ -282,6 +306,7 @@ def bf_radius_match_arrays(dt1, dt2, maxDistance, options={}):
     if _norm_type(options, dt1, dt2) == NORM_HAMMING:
         raise ValueError("bf_radius_match: radiusMatch with NORM_HAMMING is not built (NORM_L2 only)")
     _mask_option(options, dt1, dt2, "bf_radius_match", "radiusMatch")
+    _refuse_wide("bf_radius_match", "radiusMatch", dt1, dt2)
     ctx = _context(options)
     qb, q_tmp, tb, t_tmp = _as_bank_pair(ctx, dt1, dt2)
     try:
@@ -334,6 +359,7 @@ class BFMatcher(object):
                 raise ValueError("BFMatcher.add: every image's descriptors must be a 2-D [n, dim] array")
             if self.normType == NORM_HAMMING and a.dtype != np.uint8:
                 raise ValueError("NORM_HAMMING needs uint8 descriptors (cv2 asserts CV_8U), got %s" % a.dtype)
+            _refuse_wide("BFMatcher.add", "a train collection", a)
             for b in self._images + imgs:
                 if a.shape[0] and b.shape[0] and (b.shape[1] != a.shape[1] or (b.dtype == np.uint8) != (a.dtype == np.uint8)):
                     raise ValueError("BFMatcher.add: images of one collection share a width and a dtype (cv2 raises at match time)")

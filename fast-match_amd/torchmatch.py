@@ -39,6 +39,11 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
   image (``fm_collection_mutual_ratio_each_dev``: one restricted reverse sweep serves all images);
   ``clear()``, ``close()``, ``info()``.  The collection equals the ``_ffi.Collection`` the same values build on the host.
 
+Wide float descriptors -- ``[n, 129 .. 256]`` float32 / float16 / bfloat16 tensors, SuperPoint's 256-D rows for one -- make
+wide float banks (``FM_BANK_F32W``): ``bank``, ``knn`` with k <= 2, ``mutual_nn``, ``ratio_match`` and ``mutual_ratio_match``
+take them; ``radius_match``, a masked or k >= 3 ``knn`` and ``Collection.add`` raise ``ValueError`` before the library is
+touched.
+
 ``q`` and ``t`` are ``Bank``s or CUDA tensors (a tensor becomes a bank for the call).  The values are those of
 ``Context.knn`` / ``xcheck1`` / ``knn2_ratio`` on banks built from the same numbers on the host, bit for bit.
 
@@ -85,6 +90,21 @@ def _checked(tensor, binary=False):
     if tensor.stride(1) != 1 or tensor.stride(0) < tensor.shape[1]:
         tensor = tensor.contiguous()
     return tensor, dt
+
+
+def _refuse_wide(who, what, *operands):
+    """ValueError before the library is touched: wide float descriptors (129 .. 256 values per row -- a resident FM_BANK_F32W
+    bank or a float tensor of that width) are served by ``bank``, ``knn`` with k <= 2, ``mutual_nn``, ``ratio_match`` and
+    ``mutual_ratio_match`` only."""
+    for x in operands:
+        if isinstance(x, _ffi.Bank):
+            wide = x.kind == _ffi.FM_BANK_F32W
+        else:
+            shape = getattr(x, "shape", ())
+            wide = len(shape) == 2 and shape[1] > 128 and str(getattr(x, "dtype", "")) != "torch.uint8"
+        if wide:
+            raise ValueError("%s: %s is not built for wide float descriptors (129 .. 256 values per row: knn with k <= 2, "
+                             "mutual_nn, ratio_match and mutual_ratio_match are)" % (who, what))
 
 
 def _checked_mask(m, nq, nt, what="mask"):
@@ -161,6 +181,10 @@ def knn(q, t, k, mask=None):
     k = int(k)
     if k < 1:
         raise ValueError("k must be at least 1")
+    if mask is not None:
+        _refuse_wide("knn", "a mask", q, t)
+    if k > 2:
+        _refuse_wide("knn", "k >= 3", q, t)
     if mask is not None and not isinstance(mask, _ffi.Mask):
         nq, nt = (x.n if isinstance(x, _ffi.Bank) else (x.shape[0] if hasattr(x, "shape") and len(x.shape) == 2 else -1) for x in (q, t))
         mask = _checked_mask(mask, nq, nt)
@@ -288,6 +312,7 @@ def radius_match(q, t, r):
     """``cv2.BFMatcher.radiusMatch``: ``(offsets int64 [nq + 1], idx int32 [n], dist float32 [n])`` CUDA tensors, every train
     row with distance < r per query row, ascending (distance, train index).  ``r``: a scalar, or a float32 CUDA tensor [nq]
     read in place behind the current stream's work (module docstring).  One host wait for the total."""
+    _refuse_wide("radius_match", "radiusMatch", q, t)
     nq, device = _rows_and_device(q)
     if not isinstance(t, _ffi.Bank):
         _checked(t)
@@ -328,6 +353,8 @@ class Collection(object):
         0), read in place behind the current stream's work -- pitched rows with unit column stride included.  Returns the
         image's index.  On return the tensor may be overwritten."""
         import torch
+        if not binary:
+            _refuse_wide("Collection.add", "a train collection", tensor)
         tensor, dt = _checked(tensor, binary)
         coll = self._collection(_ctx_for(tensor, self._context))
         n, dim = tensor.shape
@@ -338,6 +365,7 @@ class Collection(object):
 
     def _query(self, q):
         """(query bank, [banks made for this call]); every refusal before anything reaches the library."""
+        _refuse_wide("Collection", "a query against a train collection", q)
         if isinstance(q, _ffi.Bank):
             self._collection(q.ctx)
             return q, []

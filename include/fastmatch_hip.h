@@ -36,6 +36,7 @@ extern "C" {
 #define FM_BANK_I8   1       /* uint8 / integer-valued float32 rows: exact int8-MFMA route    */
 #define FM_BANK_F32  2       /* general float32 rows: fp32 fma-chain route                    */
 #define FM_BANK_BIN  3       /* binary descriptors (fm_bank_create_bin): Hamming distance, K11 */
+#define FM_BANK_F32W 4       /* float32 rows of 129 .. 256 values ("wide float banks", K14)    */
 
 typedef struct fm_ctx  fm_ctx;
 typedef struct fm_bank fm_bank;
@@ -55,7 +56,8 @@ typedef struct fm_bank fm_bank;
  * fm_mutual_ratio_dev, fm_collection_mutual_ratio_each, fm_collection_mutual_ratio_each_dev; still revision 12, additions
  * only -- fm_mask_create, fm_mask_create_coll, fm_mask_set_u8, fm_mask_set_dev, fm_mask_set_all, fm_mask_destroy,
  * fm_mask_info, fm_knn_masked, fm_knn_masked_dev, fm_collection_knn_masked, fm_collection_knn_masked_dev, the option
- * "masked_mfma", "mask_pack_words").  A binding compares
+ * "masked_mfma", "mask_pack_words"; still revision 12, additions only -- FM_BANK_F32W: the float creators take
+ * 129 <= dim <= 256).  A binding compares
  * fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.                      */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -198,6 +200,33 @@ int  fm_bank_create_f32_route(fm_ctx* ctx, const float* rows, int64_t n, int dim
  * is FM_EINVAL, even when one of them is empty.  Not built: NORM_HAMMING2, Hamming radiusMatch, binary descriptors in the
  * Fast-Match loop itself (self distances, fm_expand_*, batches, sharded keys), k > 8.                                    */
 int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t n, int bytes, fm_bank** bank);
+/* ---- K14: wide float banks, 129 .. 256 values per row ---------------------------------------------------------------------
+ * The 256-D float descriptors of learned extractors (SuperPoint and its kin).  fm_bank_create_f32, fm_bank_create_f32_route and
+ * fm_bank_create_dev with FM_DT_F32 / FM_DT_F16 / FM_DT_BF16 (half and bfloat16 widened exactly, the source read in place at
+ * its pitch) make a bank of kind FM_BANK_F32W for every 129 <= dim <= 256, WHATEVER the values: integer-valued rows do not go
+ * to the int8 route.  n may be 0 -- the bank is still FM_BANK_F32W -- and fm_bank_info reports the real dim.  dim > 256 is
+ * FM_EUNSUPPORTED; so are uint8 rows wider than 128 (fm_bank_create_u8, FM_DT_U8) and the gather / capacity creators.  A host
+ * and a device creator given the same values build the same bank bit for bit.
+ * Contract: the float32 route's, at the wider row.  dist(q, t) = sqrtf(s), s = fmaf(v_k, v_k, s), v_k = q_k - t_k in float32,
+ * k ascending over the real dim; results are bit-identical to that chain.  Lists ascend by (distance bits, train index), the
+ * lowest index wins a tie, -1 / +inf where there are fewer than k rows, NaN never beats anything.
+ * Served, with the semantics and the argument checks they have on the float32 route: fm_knn2, fm_knn with k = 1, 2, fm_xcheck1,
+ * fm_knn2_ratio, fm_mutual_ratio, and fm_knn_dev (k <= 2), fm_xcheck1_dev, fm_knn2_ratio_dev, fm_mutual_ratio_dev.  A wide
+ * bank paired with a bank of another kind or another dim is FM_EINVAL, even when one of them is empty.
+ * Kernels (wide_f32.hip): an exact all-pairs kernel on the vector ALUs, and an fp16 filter on the matrix cores
+ * (v_mfma_f32_16x16x32_f16, ceil(dim / 32) K steps) whose candidates are rescored with the exact chain; the option "f32_filter"
+ * chooses as on the float32 route (0 exact kernel only, 1 filter from nq * nt >= 4e6, 2 always; banks with a value that is
+ * not finite, or whose scales differ by more than 2^8, take the exact kernel) and never changes a result; "f32_nsplit" sets
+ * the filter's splits; fm_f32_filter_stats counts the wide filter's launches and its whole-call fallbacks too.
+ * A performance cliff to know: the filter keeps its candidates in one list of 256 records per output row (at least 2^20, at most
+ * 2^24 records of 12 bytes: up to 192 MiB of the context's workspace) and has no per-row rescan, so a call in which more
+ * candidates than that lie inside the fp16 margin -- one large cluster of exact or near duplicates is enough, e.g. 2100 copies of a
+ * row against 600 queries next to it -- is redone as a whole by the exact kernel, 7 to 10 times slower; the results are the same.
+ * Every other entry point that takes a bank or a collection refuses a wide bank with FM_EUNSUPPORTED and a message that says
+ * "wide", before any kernel reads it.  Not built for wide float banks: fm_knn / fm_knn_dev with k >= 3, fm_radius_match(_dev),
+ * fm_self_dist(_batch), fm_bank_set_selfdist, fm_match_ratio, fm_match_accepted*, fm_xcheck1_keys*, fm_xcheck1_batched,
+ * fm_knn_masked(_dev), fm_bank_refill_u8_async, fm_bank_append_*, fm_expand_create, and every fm_collection_* call -- a wide
+ * query bank, and fm_collection_add_f32 / fm_collection_add_dev with more than 128 values per row.                          */
 int  fm_bank_destroy(fm_ctx* ctx, fm_bank* bank);
 int  fm_bank_info(const fm_bank* bank, int64_t* n, int* dim, int* kind);
 /* Attach per-row self distances (Metric_Cache.*["distances"], float64, cache.pyx:252,273)
