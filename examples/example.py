@@ -65,6 +65,17 @@ per_image = fm_matcher.fastMatchEach(q["descriptors"], 0.7)
 print("fast-match acceptance per image:", [len(l) for l in per_image])
 assert len(per_image[0]) >= 390 > max(len(per_image[1]), len(per_image[2])) and all(d.imgIdx == 0 for d in per_image[0])
 
+# The match graph of structure from motion and stitching: the images of a set against EACH OTHER, every pair in one call
+# (pairs=None: every a < b; a list of (a, b) runs a sliding window or the pairs a retrieval step chose).
+views = [synth.synth_sift(800, rng) for _ in range(6)]
+views[4][:300] = views[1][100:400]                                 # images 1 and 4 see the same object
+graph = matchutil.BFMatcher(matchutil.NORM_L2)
+graph.add(views)
+edges = graph.matchPairs(ratio=0.8, symmetric=True)                # {(a, b): [DMatch]}, mutual nearest neighbours + ratio test
+best = max(edges, key=lambda ab: len(edges[ab]))
+print("match graph: %d pairs, the strongest edge %s has %d matches" % (len(edges), best, len(edges[best])))
+assert len(edges) == 15 and best == (1, 4) and len(edges[best]) >= 290 and all(d.imgIdx == 4 for d in edges[best])
+
 # Wide float descriptors: a learned extractor's 256-D rows (SuperPoint and its kin) go the same way -- a float array of
 # 129 .. 256 columns becomes a wide float bank; k <= 2, crossCheck, the ratio match and the mutual ratio match take it.
 wide_t = rng.standard_normal((2000, 256)).astype(np.float32)

@@ -166,6 +166,10 @@ SYMBOLS = {
     "fm_collection_xcheck1_each_dev": (_INT, [_P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P]),
     "fm_collection_mutual_ratio_each": (_INT, [_P, _P, _P, ctypes.c_double, ctypes.c_int32, _I64, _P, _P, _P, _P, _P]),
     "fm_collection_mutual_ratio_each_dev": (_INT, [_P, _P, _P, ctypes.c_double, ctypes.c_int32, _I64, _P, _P, _P, _P]),
+    "fm_collection_pairs_mutual_ratio": (_INT, [_P, _P, _P, _I64, ctypes.c_double, ctypes.c_int32, _I64, _P, _P, _P, _P, _P,
+                                                ctypes.POINTER(_I64)]),
+    "fm_collection_pairs_mutual_ratio_dev": (_INT, [_P, _P, _P, _I64, ctypes.c_double, ctypes.c_int32, _I64, _P, _P,
+                                                    ctypes.POINTER(_I64), _P]),
     "fm_collection_add_dev": (_INT, [_P, _P, _P, _INT, _I64, _INT, _I64, _P, ctypes.POINTER(_I32)]),
     "fm_collection_knn_dev": (_INT, [_P, _P, _P, _I32, _P, _P, _P, _P]),
     "fm_collection_knn2_ratio_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
@@ -237,6 +241,31 @@ def load_library():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data
+
+
+def pairs_array(pairs, n_images=None):
+    """A pair list of the match-graph calls as a C-contiguous int32 [n_pairs, 2] array: a sequence of (a, b) image indices or
+    an integer array of that shape.  ``ValueError`` for anything else and, with ``n_images``, for an index outside
+    [0, n_images).  (An empty list still owns storage, so that its address is not NULL: NULL means "every a < b".)"""
+    if isinstance(pairs, np.ndarray) and pairs.dtype == np.int32 and pairs.ndim == 2 and pairs.shape[1] == 2 \
+            and pairs.flags.c_contiguous and pairs.shape[0] > 0:
+        arr = pairs
+    else:
+        try:
+            src = np.asarray(pairs if isinstance(pairs, np.ndarray) else list(pairs))
+        except TypeError:
+            raise ValueError("pairs must be a sequence of (a, b) image indices")
+        if src.size == 0:
+            src = np.zeros((0, 2), np.int32)
+        if src.ndim != 2 or src.shape[1] != 2 or src.dtype.kind not in "iu":
+            raise ValueError("pairs must be a sequence of (a, b) integer image indices, shape [n_pairs, 2]")
+        if src.size and (src.min() < -2 ** 31 or src.max() >= 2 ** 31):
+            raise ValueError("pairs: an image index does not fit int32")
+        arr = np.zeros((max(src.shape[0], 1), 2), np.int32)[:src.shape[0]]
+        arr[...] = src
+    if n_images is not None and arr.size and (arr.min() < 0 or arr.max() >= n_images):
+        raise ValueError("pairs: an image index is outside [0, %d)" % n_images)
+    return arr
 
 
 def self_dist_plan(n_pad, stages=0):
@@ -761,6 +790,62 @@ class Collection(object):
             self.ctx.handle, self.handle, q.handle, float(tau), int(bool(symmetric)), int(cap), _P(int(rows_ptr)) if rows_ptr else None,
             _P(int(counts_ptr)) if counts_ptr else None, _ptr(h_counts) if h_counts is not None else None,
             _stream_arg(consumer_stream)))
+
+    def _pairs(self, pairs):
+        ni = self.info()[0]
+        if pairs is None:
+            return None, ni * (ni - 1) // 2
+        arr = pairs_array(pairs)
+        return arr, arr.shape[0]
+
+    def pairs_mutual_ratio_counts(self, pairs=None, tau=0.8, symmetric=False):
+        """int64[n_pairs + 1]: the offsets of ``pairs_mutual_ratio`` alone (its counts-only call, cap = 0) -- the number of
+        matches of pair p is ``offsets[p + 1] - offsets[p]``, the edge weights of the match graph."""
+        arr, n = self._pairs(pairs)
+        offsets = np.zeros(n + 1, np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_pairs_mutual_ratio(
+            self.ctx.handle, self.handle, _ptr(arr), n, float(tau), int(bool(symmetric)), 0,
+            _ptr(offsets), None, None, None, None, None))
+        return offsets
+
+    def pairs_mutual_ratio(self, pairs=None, tau=0.8, symmetric=False, cap=None):
+        """``fm_collection_pairs_mutual_ratio``: the images of the collection matched against each other.  ``pairs``: a
+        sequence of ordered (a, b) image indices, or None for every a < b in lexicographic order.  A list of (qidx, tidx,
+        dist, ratio) per pair, entry p equal to ``Context.mutual_ratio(bank(image_a), bank(image_b), tau, symmetric)``:
+        ``qidx`` is the row inside image a, ``tidx`` the row inside image b.  ``cap`` None: the counts first, then one fill
+        call of exactly that size; else the rows of the longest prefix of whole pairs that fits are returned and the later
+        pairs come back empty."""
+        arr, n = self._pairs(pairs)
+        if cap is None:
+            cap = int(self.pairs_mutual_ratio_counts(arr if pairs is not None else None, tau, symmetric)[-1])
+        cap = int(cap)
+        kept = max(cap, 0)
+        qidx, tidx = np.empty(kept, np.int32), np.empty(kept, np.int32)
+        dist, ratio = np.empty(kept, np.float32), np.empty(kept, np.float64)
+        offsets = np.zeros(n + 1, np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_pairs_mutual_ratio(
+            self.ctx.handle, self.handle, _ptr(arr), n, float(tau), int(bool(symmetric)), cap,
+            _ptr(offsets), _ptr(qidx) if kept else None, _ptr(tidx) if kept else None, _ptr(dist) if kept else None,
+            _ptr(ratio) if kept else None, None))
+        out = []
+        for p in range(n):
+            lo, hi = int(offsets[p]), int(offsets[p + 1])
+            if hi > kept:
+                lo = hi = 0
+            out.append((qidx[lo:hi], tidx[lo:hi], dist[lo:hi], ratio[lo:hi]))
+        return out
+
+    def pairs_mutual_ratio_dev(self, pairs, tau, symmetric, offsets_ptr, rows_ptr, cap, want_total=False, consumer_stream=None):
+        """``pairs_mutual_ratio`` with device outputs (``fm_collection_pairs_mutual_ratio_dev``): ``offsets_ptr`` = device
+        address of an int64 [n_pairs + 1] array, ``rows_ptr`` of an int32 [cap, 3] block (row in a, row in b, float32
+        distance bits).  Enqueued only; ``want_total``: also return the total number of matches (the call's one host wait)."""
+        arr, n = self._pairs(pairs)
+        total = _I64(0)
+        self.ctx._check(self.ctx.lib.fm_collection_pairs_mutual_ratio_dev(
+            self.ctx.handle, self.handle, _ptr(arr), n, float(tau), int(bool(symmetric)), int(cap),
+            _P(int(offsets_ptr)) if offsets_ptr else None, _P(int(rows_ptr)) if rows_ptr else None,
+            ctypes.byref(total) if want_total else None, _stream_arg(consumer_stream)))
+        return int(total.value) if want_total else None
 
     def close(self):
         if self.handle is not None and self.ctx.handle is not None:

@@ -608,6 +608,8 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx)
     for (void* w : {ctx->ws_rrows, ctx->ws_rkeys, ctx->ws_rtmp}) if (w) (void)hipFree(w);
     if (ctx->h_scratch) (void)hipHostFree(ctx->h_scratch);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
+    if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
+    if (ctx->ev_tab) (void)hipEventDestroy(ctx->ev_tab);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
     if (ctx->d_cut) (void)hipFree(ctx->d_cut);
     if (ctx->ev_call0) (void)hipEventDestroy(ctx->ev_call0);

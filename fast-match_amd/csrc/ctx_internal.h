@@ -47,6 +47,10 @@ struct fm_ctx {
     int    f6_last_n = 0;        // pairs of the last filter launch (options "fp6_records" / "fp6_fallbacks" read their words)
     int64_t filter_launches = 0;
     unsigned long long* h_scratch = nullptr;   // pinned host words the kernels can write (counts)
+    // fm_collection_pairs_mutual_ratio: page-locked image of the call's slot tables and "its upload is done" -- a call that
+    // returns without a host wait (the _dev form) leaves the copy in flight, the next call waits for it before it writes
+    char*  h_tab = nullptr; size_t h_tab_bytes = 0;
+    hipEvent_t ev_tab = nullptr; bool tab_in_flight = false;
     // page-locked staging for results that go to pageable caller memory (d2h below)
     char*  h_stage = nullptr; size_t h_stage_bytes = 0, h_stage_used = 0;
     struct StagedCopy { void* dst; size_t off, bytes; };

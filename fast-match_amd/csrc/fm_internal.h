@@ -155,7 +155,8 @@ struct Tuning {
     int masked_mfma = 1;              // K13: fm_knn_masked on the integer route with k <= 2: 1 = the masked MFMA sweep, 0 = the masked K9 kernel
     int mask_pack_words = (1 << 26) - 4;  // K13: mask words one launch of the pack / fill kernels covers (64 work-items per word: < 2^32 per launch)
     int coll_ws_bytes = 0;            // fm_collection_match_accepted_each / _xcheck1_each: device bytes for the per-(image, query row)
-                                      // arrays of one chunk of images (25 / 17 per entry); 0 = a quarter of the free device memory
+                                      // arrays of one chunk of images (25 / 17 per entry); 0 = a quarter of the free device memory;
+                                      // fm_collection_pairs_mutual_ratio: partials, lists and per-row arrays of one chunk of pairs (0 = 2^30)
 };
 
 // ---- K1: row-reduce kernel launcher ---------------------------------------------------
@@ -331,6 +332,16 @@ hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* co
 // top-2 form of the batched launch (fm_collection_knn2_each): bound[i] = pair i's two bound arrays ([2 * ncols_alloc]) or null
 hipError_t launch_rowreduce_batch2(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
                                    unsigned long long* const* partial, int* const* bound, hipStream_t stream);
+// table-driven form of the batched top-2 launch (fm_collection_pairs_mutual_ratio): any number of slots, descriptors and the
+// prefix array of first workgroups in device memory.  A table of n slots is rowreduce_table_bytes(n) bytes, the same on the
+// host, where it is built -- rowreduce_table_set: slot i under its plan in the batched shape, owning the workgroups from
+// first_wg on; returns how many (> 0; -1: a plan in another shape) -- then _end with the grid -- and on the device, where the
+// caller has copied it before the launch.  Every slot has at least one workgroup.
+size_t rowreduce_table_bytes(int n);
+int rowreduce_table_set(void* h, int n, int i, int first_wg, const Bank& cols, const Bank& red, const RowReducePlan& plan,
+                        unsigned long long* partial, int* bound);
+void rowreduce_table_end(void* h, int n, int total_wg);
+hipError_t launch_rowreduce_table2(const void* d_table, int n, int total_wg, hipStream_t stream);
 hipError_t launch_expand(const void* d_pairs, int n_pairs, bool f32, int tier, hipStream_t stream);   // all pairs of one kind / capacity tier (expand.hip)
 int expand_cand_cap();
 int expand_cand_cap_big();

@@ -1128,6 +1128,47 @@ hipError_t launch_rowreduce_batch2(int n, const Bank* const* cols, const Bank* c
     return hipGetLastError();
 }
 
+// The top-2 sweep of ANY number of (output bank, reduced bank) slots in one launch (fm_collection_pairs_mutual_ratio: two
+// slots per image pair).  RRBatch travels as kernel arguments and ends at kRRBatchMax; here the descriptors and the prefix
+// array of first workgroups live in DEVICE memory: a table of n slots is RRParams[n] followed by int first[n + 1]
+// (first[n] = the grid), built on the host (rowreduce_table_set / _end) and uploaded by the caller.  A workgroup finds its
+// slot by binary search over first[] (table_slot_of, tile_ops.h: blockIdx.x is uniform, the loads are scalar) and reads its
+// descriptor through the slot number made wave-uniform, so the unchanged body addresses from SGPRs as under
+// rowreduce_batch_kernel.
+template <int NC, int KTOP, int NW, int NBUF, int PRIO>
+__global__ __launch_bounds__(64 * NW, 4)
+void rowreduce_table_kernel(const RRParams* __restrict__ tab, const int* __restrict__ first, int n)
+{
+    __shared__ __attribute__((aligned(16))) char smem[NBUF * kStageBytes];
+    const int slot = __builtin_amdgcn_readfirstlane(table_slot_of(first, n, (int)blockIdx.x));
+    const RRParams p = tab[slot];
+    rowreduce_body<NC, KTOP, true, NW, NBUF, PRIO>(p, (int)blockIdx.x - first[slot], smem);
+}
+
+static size_t table_first_off(int n) { return ((size_t)n * sizeof(RRParams) + 15) & ~(size_t)15; }
+size_t rowreduce_table_bytes(int n) { return align256(table_first_off(n) + ((size_t)n + 1) * sizeof(int)); }
+
+int rowreduce_table_set(void* h, int n, int i, int first_wg, const Bank& cols, const Bank& red, const RowReducePlan& plan,
+                        unsigned long long* partial, int* bound)
+{
+    if (plan.nb != 4 || plan.nw != 8 || i < 0 || i >= n) return -1;
+    RRParams& p = ((RRParams*)h)[i];
+    p = RRParams{};
+    fill_params(p, cols, red, plan, partial, bound);
+    ((int*)((char*)h + table_first_off(n)))[i] = first_wg;
+    return rowreduce_grid(plan);
+}
+
+void rowreduce_table_end(void* h, int n, int total_wg) { ((int*)((char*)h + table_first_off(n)))[n] = total_wg; }
+
+hipError_t launch_rowreduce_table2(const void* d_table, int n, int total_wg, hipStream_t stream)
+{
+    if (n < 1 || total_wg < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((rowreduce_table_kernel<4, 2, 8, 3, 1>), dim3((unsigned)total_wg), dim3(64 * 8), 0, stream,
+                       (const RRParams*)d_table, (const int*)((const char*)d_table + table_first_off(n)), n);
+    return hipGetLastError();
+}
+
 // Top-1 of every row of `bank` over the OTHER rows of the same bank (plan from plan_rowreduce_self).
 hipError_t launch_rowreduce_self(const Bank& bank, const RowReducePlan& plan, unsigned long long* partial, int* bound,
                                  bool use_glds, hipStream_t stream)

@@ -231,6 +231,20 @@ __device__ __forceinline__ bool better(int ah, int ai, int bh_, int bi_)
     return ah > bh_ || (ah == bh_ && ai < bi_);
 }
 
+// Flat grids over slots of different sizes (the table-driven sweep of rowreduce.hip, the merge, join and compaction of
+// fm_collection_pairs_mutual_ratio): slot s owns the blocks [first[s], first[s + 1]) of the grid, first[n] = the grid.
+// The slot of block `bid` (< first[n]) by binary search: the last s with first[s] <= bid, so a slot without blocks is never
+// returned.  bid uniform (blockIdx.x): the loads are scalar.
+__device__ __forceinline__ int table_slot_of(const int* __restrict__ first, int n, int bid)
+{
+    int lo = 0, hi = n;             // first[lo] <= bid < first[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= bid) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // Strict insertion of a 64-bit key (distance bits << 32 | row) into an ascending list of K (K9, K11): an equal key cannot
 // occur (indices differ); a later row never displaces an earlier one at equal distance because its index is larger.
 template <int K>

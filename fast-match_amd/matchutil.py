@@ -337,7 +337,8 @@ class BFMatcher(object):
     ``matchEach`` is ``match`` against every image separately -- with crossCheck the mutual nearest neighbours image by image,
     the collection form crossCheck does have.
     ``knnMatch_arrays`` / ``knnMatchEach_arrays`` / ``matchEach_arrays`` / ``votes`` return NumPy arrays.  ``fastMatchEach`` / ``fastMatchEach_arrays``
-    run Fast-Match's self-distance test against every image of the collection (NORM_L2 only)."""
+    run Fast-Match's self-distance test against every image of the collection (NORM_L2 only).  ``matchPairs`` /
+    ``matchPairs_arrays`` match the added images against each other (the match graph), one call for any number of pairs."""
 
     def __init__(self, normType=NORM_L2, crossCheck=False, options={}):
         if normType not in (NORM_L2, NORM_HAMMING):
@@ -564,6 +565,35 @@ class BFMatcher(object):
         out = []
         for i, (qidx, tidx, dist, _) in enumerate(self.mutualRatioMatchEach_arrays(queryDescriptors, tau, symmetric)):
             out.append([DMatch(int(qidx[j]), int(tidx[j]), dist[j], i) for j in range(qidx.shape[0])])
+        return out
+
+    def matchPairs_arrays(self, pairs=None, ratio=0.8, symmetric=False):
+        """The added images matched AGAINST EACH OTHER -- the match graph of structure from motion and stitching (COLMAP's
+        exhaustive / sequential matchers, ``cv2.detail.BestOf2NearestMatcher``): ``(pairs int32 [n_pairs, 2], [(qidx, tidx,
+        dist, ratio) per pair])``.  ``pairs``: ordered (a, b) image indices, None = every a < b in lexicographic order; entry
+        p equals ``mutual_ratio_match_arrays(image_a, image_b, ratio, symmetric)``, ``qidx`` the row inside image a, ``tidx``
+        inside image b (``Collection.pairs_mutual_ratio``: one call, whatever the number of pairs).  NORM_L2 and
+        NORM_HAMMING.  ``ValueError`` before anything is uploaded: a matcher made with ``crossCheck=True`` (the call is mutual
+        by itself), an empty collection, a malformed ``pairs`` (not [n_pairs, 2] integers, an index outside the images)."""
+        if self.crossCheck:
+            raise ValueError("BFMatcher.matchPairs: the call is mutual by itself; make the matcher with crossCheck=False")
+        self._check_collection("BFMatcher.matchPairs")
+        ni = len(self._images)
+        if pairs is None:
+            arr = np.array([(a, b) for a in range(ni) for b in range(a + 1, ni)], np.int32).reshape(-1, 2)
+        else:
+            arr = _ffi.pairs_array(pairs, ni)
+        coll = self.train()
+        return arr, coll.pairs_mutual_ratio(None if pairs is None else arr, ratio, symmetric)
+
+    def matchPairs(self, pairs=None, ratio=0.8, symmetric=False):
+        """``{(a, b): [DMatch]}`` of :meth:`matchPairs_arrays`: ``queryIdx`` is the row inside image a, ``trainIdx`` the row
+        inside image b, ``imgIdx`` = b, ascending ``queryIdx``.  A pair listed more than once keeps one entry (its lists are
+        equal)."""
+        arr, res = self.matchPairs_arrays(pairs, ratio, symmetric)
+        out = {}
+        for (a, b), (qidx, tidx, dist, _) in zip(arr.tolist(), res):
+            out[(a, b)] = [DMatch(int(qidx[j]), int(tidx[j]), dist[j], b) for j in range(qidx.shape[0])]
         return out
 
     # -- cv2's matching methods ------------------------------------------------------------

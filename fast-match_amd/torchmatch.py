@@ -37,6 +37,10 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
   float and binary collections alike;
   ``mutual_ratio_each(q, tau, symmetric=False, cap=None)`` -> the same two tensors for ``mutual_ratio_match`` inside every
   image (``fm_collection_mutual_ratio_each_dev``: one restricted reverse sweep serves all images);
+  ``match_pairs(pairs=None, tau=0.8, symmetric=False, cap=None)`` -> ``(offsets int64 [n_pairs + 1], rows int32 [n, 3])``: the
+  images matched against EACH OTHER, ``mutual_ratio_match(image_a, image_b)`` for every ordered pair (a, b) of ``pairs`` (a
+  host sequence or an int32 CPU tensor; None: every a < b) in one call (``fm_collection_pairs_mutual_ratio_dev``), no host
+  wait unless ``cap`` is None (then one, for the total that sizes ``rows``);
   ``clear()``, ``close()``, ``info()``.  The collection equals the ``_ffi.Collection`` the same values build on the host.
 
 Wide float descriptors -- ``[n, 129 .. 256]`` float32 / float16 / bfloat16 tensors, SuperPoint's 256-D rows for one -- make
@@ -518,6 +522,36 @@ class Collection(object):
         finally:
             for b in made:
                 b.close()
+
+    def match_pairs(self, pairs=None, tau=0.8, symmetric=False, cap=None):
+        """The images of the collection matched against each other (the match graph), left on the device: ``(offsets int64
+        [n_pairs + 1], rows int32 [n, 3] = (row in image a, row in image b, float32 distance bits))``; the rows of pair p =
+        (a, b) are ``rows[offsets[p]:offsets[p + 1]]``, equal to ``mutual_ratio_match(image_a, image_b, tau, symmetric)``.
+        ``pairs``: a host sequence of ordered (a, b) image indices or an int32 CPU tensor [n_pairs, 2]; None: every a < b in
+        lexicographic order.  ``cap`` rows are allocated and the longest prefix of whole pairs that fits is written (the
+        offsets always hold the full counts); enqueued, no host wait.  ``cap`` None: a counts-only call first, whose total
+        is read back (the one host wait), then one fill of exactly that size."""
+        import torch
+        if cap is not None and int(cap) < 0:
+            raise ValueError("cap must not be negative")
+        if pairs is not None:
+            if torch.is_tensor(pairs):
+                if pairs.is_cuda or pairs.dtype != torch.int32:
+                    raise ValueError("pairs must be a host sequence or an int32 CPU tensor [n_pairs, 2]")
+                pairs = pairs.contiguous().numpy()
+            pairs = _ffi.pairs_array(pairs, self.info()[0])
+        coll = self._collection()
+        n = coll.info()[0] * (coll.info()[0] - 1) // 2 if pairs is None else pairs.shape[0]
+        stream, dev = _stream_and_device(coll.ctx)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        if cap is None:
+            cap = coll.pairs_mutual_ratio_dev(pairs, float(tau), bool(symmetric), offsets.data_ptr(), 0, 0, want_total=True,
+                                              consumer_stream=stream)
+        cap = int(cap)
+        rows = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+        coll.pairs_mutual_ratio_dev(pairs, float(tau), bool(symmetric), offsets.data_ptr(), rows.data_ptr() if cap else 0, cap,
+                                    consumer_stream=stream)
+        return offsets, rows
 
     def clear(self):
         if self._coll is not None:

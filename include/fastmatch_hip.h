@@ -57,7 +57,8 @@ typedef struct fm_bank fm_bank;
  * only -- fm_mask_create, fm_mask_create_coll, fm_mask_set_u8, fm_mask_set_dev, fm_mask_set_all, fm_mask_destroy,
  * fm_mask_info, fm_knn_masked, fm_knn_masked_dev, fm_collection_knn_masked, fm_collection_knn_masked_dev, the option
  * "masked_mfma", "mask_pack_words"; still revision 12, additions only -- FM_BANK_F32W: the float creators take
- * 129 <= dim <= 256).  A binding compares
+ * 129 <= dim <= 256; still revision 12, additions only -- fm_collection_pairs_mutual_ratio,
+ * fm_collection_pairs_mutual_ratio_dev).  A binding compares
  * fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.                      */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -142,7 +143,10 @@ int  fm_ctx_destroy(fm_ctx* ctx);
  *                         fm_collection_mutual_ratio_each: device bytes for the gathered train rows of one chunk of
  *                         consecutive candidates -- 132 bytes per candidate on the integer route, 776 on the float32 route,
  *                         80 per 16 bytes of row width (rounded up) for binary rows; whole 128-row stages, at least one per
- *                         chunk; 0 = 2^30
+ *                         chunk; 0 = 2^30.
+ *                         fm_collection_pairs_mutual_ratio: device bytes for the sweep partials, 2-NN lists and per-row arrays
+ *                         of one chunk of consecutive pairs (one table-driven launch per chunk on the integer route; at
+ *                         least one pair per chunk); 0 = 2^30
  * Unknown names and out-of-range values return FM_EINVAL.                                          */
 int  fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value);
 int  fm_ctx_get_option(fm_ctx* ctx, const char* name, int64_t* value);
@@ -402,6 +406,34 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  *     image i at d_rows + i * cap * 3; d_counts[i] = min(count, cap) (cap = 0: d_rows may be NULL; cap < 0: FM_EINVAL);
  *     consumer_stream ordered in both directions; h_counts (host, or NULL) receives the full counts.  The call waits once for
  *     the candidate count on every route; asking for h_counts is a second wait.
+ *   fm_collection_pairs_mutual_ratio: the images of the collection matched AGAINST EACH OTHER -- the match graph of structure
+ *     from motion, panorama stitching and loop closure (COLMAP's exhaustive and sequential matchers,
+ *     cv::detail::BestOf2NearestMatcher, a pair list from a retrieval step) -- in ONE call.  pairs: host [n_pairs][2] image
+ *     indices; pair p = (a, b) is ORDERED and its rows equal, row by row and bit for bit, fm_mutual_ratio(bank(image a),
+ *     bank(image b), tau, symmetric, ...) on integer-route, float32-route and binary collections: qidx = the row inside image
+ *     a, tidx = the row inside image b, dist = d0, ratio = the forward ratio (symmetric != 0: the larger of the two), rows
+ *     ascending in qidx; the float32-root repair above d^2 = 4 197 200 is included, per pair.  a == b is allowed (it equals
+ *     fm_mutual_ratio(v, v)), a pair may appear more than once, (b, a) is another pair than (a, b); empty images keep their
+ *     index and accept nothing.  pairs == NULL: every (i, j) with i < j in lexicographic order; n_pairs must then equal
+ *     n_images (n_images - 1) / 2 (FM_EINVAL otherwise: it guards the caller's array sizes).  The output is packed, by
+ *     fm_radius_match's rules with "pair" for "query row": offsets[0 .. n_pairs] are always written with the FULL counts,
+ *     offsets[n_pairs] = *n_total; rows are written for the longest prefix of whole pairs that fits in cap; cap = 0: counts
+ *     only (the row arrays may be NULL) -- the edge weights of the match graph.  Both images of a pair are resident bank
+ *     views of the stack, so a pair is two full top-2 sweeps (a over b, b over a), a join -- the reverse list of a row's first
+ *     neighbour is a plain lookup: no gather, no candidate count, no host wait between the sweeps -- and an ordered
+ *     compaction without atomics.  Integer route: the sweeps of a whole chunk of pairs are ONE launch of the batched top-2
+ *     kernel whose slot descriptors and prefix array live in device memory (any number of slots; a workgroup finds its slot
+ *     by binary search), followed by ONE merge launch; chunks of consecutive pairs under the option "coll_ws_bytes" are
+ *     enqueued back to back, a running total on the device keeps the offsets global.  Float32-route and binary collections:
+ *     the two per-pair sweeps (K8 / K5, K11) enqueued back to back with no host wait between pairs.  The host form waits
+ *     only for its copy out.  Accounted in fm_stats: pairs grow by 2 rows(a) rows(b) per pair.  Errors, in this order: NULL
+ *     handles or a foreign context; n_pairs < 0, or pairs NULL with another n_pairs (FM_EINVAL); an image index outside
+ *     [0, n_images) (FM_EINVAL, nothing is enqueued); cap < 0, offsets NULL, a row array NULL with cap > 0 (FM_EINVAL).
+ *     n_pairs = 0 and an empty collection are valid.
+ *   fm_collection_pairs_mutual_ratio_dev: the same into DEVICE memory -- d_offsets [n_pairs + 1], 12-byte rows {row in a, row
+ *     in b, float32 distance bits} at d_rows [cap][3] (cap = 0: d_rows may be NULL); consumer_stream ordered in both
+ *     directions as in fm_collection_mutual_ratio_each_dev; n_total (host, or NULL): asking for it is the call's only host
+ *     wait.  Not accounted in fm_stats.
  *   fm_collection_radius_match: fm_radius_match(q, T, ...) for T = the images' rows stacked in image order -- every database
  *     descriptor within r_i of query row i in ONE matrix-core sweep over the whole allocation (place recognition,
  *     de-duplication, Fast-Match's one-to-many test d(q, t) < tau * selfdist(q)).  Every hit is (img, row inside that image);
@@ -432,7 +464,9 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  * the expansion loop on a collection, a batched K8 / K11 (float32 / binary) per-image sweep,
  * binary collections in the self-distance test, sharding a collection across GPUs (radius queries included), removing single
  * images, turning an integer-route collection of float32 images into a float32-route one for a
- * non-integer QUERY.                                                                    */
+ * non-integer QUERY, and for fm_collection_pairs_mutual_ratio: a sweep that computes a pair's tiles once for both
+ * directions (d(i, j) = d(j, i): half the matrix-core work of a pair), sharing sweeps between (a, b) and (b, a) of one
+ * pair list (the two pairs run the same two sweeps).                                     */
 typedef struct fm_collection fm_collection;
 #define FM_COLLECTION_F32_MAX 144115188075855872.0f   /* 2^57: largest finite magnitude of a float32-route collection and its queries */
 int  fm_collection_create(fm_ctx* ctx, fm_collection** coll);
@@ -475,6 +509,13 @@ int  fm_collection_mutual_ratio_each(fm_ctx* ctx, fm_collection* coll, const fm_
 int  fm_collection_mutual_ratio_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int32_t symmetric, int64_t cap,
                                          int32_t* d_rows /*device [n_images][cap][3]*/, int64_t* d_counts /*device [n_images]*/,
                                          int64_t* h_counts /*host [n_images] or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_pairs_mutual_ratio(fm_ctx* ctx, fm_collection* coll, const int32_t* pairs /*host [n_pairs][2] or NULL*/, int64_t n_pairs,
+                                      double tau, int32_t symmetric, int64_t cap, int64_t* offsets /*[n_pairs + 1]*/,
+                                      int32_t* qidx, int32_t* tidx, float* dist, double* ratio /* each [cap] */, int64_t* n_total /*or NULL*/);
+int  fm_collection_pairs_mutual_ratio_dev(fm_ctx* ctx, fm_collection* coll, const int32_t* pairs /*host [n_pairs][2] or NULL*/, int64_t n_pairs,
+                                          double tau, int32_t symmetric, int64_t cap, int64_t* d_offsets /*device [n_pairs + 1]*/,
+                                          int32_t* d_rows /*device [cap][3]*/, int64_t* n_total /*host or NULL*/,
+                                          void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* ---- descriptors already on the GPU: device sources, device results ---------------------------------------------------------
  * Every creator above takes a HOST array and every dense matcher call ends in host arrays: the shape of the reference, whose
