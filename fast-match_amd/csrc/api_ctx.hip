@@ -892,6 +892,8 @@ static void bank_free(Bank* b)
     if (b->rows4) (void)hipFree(b->rows4);
     if (b->wrows) (void)hipFree(b->wrows);
     if (b->wrowsh) (void)hipFree(b->wrowsh);
+    if (b->real_mem) (void)hipFree(b->real_mem);
+    b->real = nullptr; b->real_mem = nullptr;
     b->wrows = nullptr; b->wrowsh = nullptr;
     b->stage = nullptr; b->rowsb = nullptr; b->rows4 = nullptr;
     b->rows8 = nullptr; b->norm = nullptr; b->aux = nullptr; b->rowsf = nullptr; b->selfdist = nullptr;
@@ -1147,6 +1149,49 @@ extern "C" int fm_bank_create_u8_cap(fm_ctx* ctx, const uint8_t* rows, int64_t n
     return bank_create(ctx, rows, n, dim, false, bank, false, capacity);
 }
 
+// ---- the real-row bitmap of a bank that grew with gaps (Bank::real) ------------------------------------------------------
+// Bits [r0, r1) on: one thread per word (r0 < r1; no two launches in flight touch one word -- the appends are synchronous).
+__global__ void bank_real_set_kernel(unsigned long long* __restrict__ real, int64_t r0, int64_t r1)
+{
+    const int64_t w = (r0 >> 6) + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w > ((r1 - 1) >> 6)) return;
+    const int64_t lo = r0 > 64 * w ? r0 - 64 * w : 0, hi = r1 < 64 * (w + 1) ? r1 - 64 * w : 64;
+    const unsigned long long upto_hi = hi >= 64 ? ~0ull : ((1ull << hi) - 1ull), below_lo = (1ull << lo) - 1ull;
+    real[w] |= upto_hi & ~below_lo;
+}
+
+static hipError_t bank_real_set(unsigned long long* real, int64_t r0, int64_t r1, hipStream_t stream)
+{
+    if (r1 <= r0) return hipSuccess;
+    const int64_t words = ((r1 - 1) >> 6) - (r0 >> 6) + 1;
+    hipLaunchKernelGGL(bank_real_set_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, real, r0, r1);
+    return hipGetLastError();
+}
+
+// In front of an append at row `off` (>= bank->n): the append leaves rows [bank->n, off) as padding INSIDE the bank.  The
+// first such gap gives the bank its bitmap, with the rows so far -- all real until now -- marked; a bank that never has a
+// gap never gets one.  Enqueued on the context's stream; bank_real_append marks the new rows once they are in.
+static int bank_real_gap(fm_ctx* ctx, fm_bank* bank, int64_t off)
+{
+    if (bank->real || off == bank->n || bank->n == 0) return FM_OK;
+    const size_t bytes = (size_t)(bank->cap_pad / 64) * 8;
+    if (!bank->real_mem) HIP_TRY(ctx, hipMalloc((void**)&bank->real_mem, bytes));
+    HIP_TRY(ctx, hipMemsetAsync(bank->real_mem, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, bank_real_set(bank->real_mem, 0, bank->n, ctx->stream));
+    bank->real = bank->real_mem;
+    return FM_OK;
+}
+
+// The rows [off, off + n) of an append marked real: enqueued only, in front of the append's own synchronisation (an append
+// of a grown bank stays at the host waits it had).  Bits of rows at or beyond bank->n are never read, so marking before
+// the append is known to have succeeded is harmless.
+static int bank_real_append(fm_ctx* ctx, fm_bank* bank, int64_t off, int64_t n)
+{
+    if (!bank->real) return FM_OK;
+    HIP_TRY(ctx, bank_real_set(bank->real, off, off + n, ctx->stream));
+    return FM_OK;
+}
+
 // Rows appended to a bank created with room for them, at the next multiple of 32 rows (whole MFMA tiles: the rows
 // of the tile an earlier append ended in stay what they are, padding).  Synchronous.
 extern "C" int fm_bank_append_u8(fm_ctx* ctx, fm_bank* bank, const uint8_t* rows, int64_t n, int64_t* first_row)
@@ -1163,6 +1208,7 @@ extern "C" int fm_bank_append_u8(fm_ctx* ctx, fm_bank* bank, const uint8_t* rows
     const size_t src_bytes = (size_t)n * bank->dim, flag_off = (src_bytes + 15) & ~(size_t)15;
     int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, flag_off + 32);
     if (rc != FM_OK) return rc;
+    if ((rc = bank_real_gap(ctx, bank, off)) != FM_OK) return rc;
     int* d_flag = (int*)((char*)ctx->ws_in + flag_off);
     HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 8, ctx->stream));
@@ -1170,6 +1216,7 @@ extern "C" int fm_bank_append_u8(fm_ctx* ctx, fm_bank* bank, const uint8_t* rows
     hipLaunchKernelGGL(bank_prep_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, (const void*)ctx->ws_in, n, bank->dim,
                        bank->rows8 + (size_t)off * kDim, bank->norm + off, bank->aux + (off / kTileRows) * kAuxPerTile, d_flag, ntiles);
     HIP_TRY(ctx, hipGetLastError());
+    if ((rc = bank_real_append(ctx, bank, off, n)) != FM_OK) return rc;
     int flags[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(flags, d_flag, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1294,6 +1341,7 @@ extern "C" int fm_bank_append_f32(fm_ctx* ctx, fm_bank* bank, const float* rows,
     const size_t src_bytes = (size_t)n * bank->dim * 4, flag_off = (src_bytes + 15) & ~(size_t)15;
     int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, flag_off + 32);
     if (rc != FM_OK) return rc;
+    if ((rc = bank_real_gap(ctx, bank, off)) != FM_OK) return rc;     // (a refused append below leaves the marks of the rows so far: harmless)
     int* d_flag = (int*)((char*)ctx->ws_in + flag_off);
     HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 16, ctx->stream));
@@ -1314,6 +1362,7 @@ extern "C" int fm_bank_append_f32(fm_ctx* ctx, fm_bank* bank, const float* rows,
                        (const float*)dst, ok ? n : (int64_t)0, n16, bank->kscale, bank->rowsh + (size_t)off * kDim, bank->normf + off,
                        bank->auxf + off, d_flag + 2);
     HIP_TRY(ctx, hipGetLastError());
+    if (ok && (rc = bank_real_append(ctx, bank, off, n)) != FM_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(stat, d_flag + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (!ok)
@@ -1502,6 +1551,7 @@ extern "C" int fm_bank_refill_u8_async(fm_ctx* ctx, fm_bank* bank, const uint8_t
     HIP_TRY(ctx, hipGetLastError());
     bank->n = n;
     bank->n_pad = n_pad;
+    bank->real = nullptr;           // (the new rows are dense: whatever gaps appends had left are gone; real_mem stays for the next one)
     if (bank->rows6) HIP_TRY(ctx, launch_prep6(*bank, ctx->tune.refill_grid, ctx->upload));       // (from the new int8 plane, behind it)
     // the largest row norm of the new rows is known on the device only: assume the float32-root guard is needed
     // (an election then launches one extra kernel that finds an empty list, ~5 us beside the next distance kernel)

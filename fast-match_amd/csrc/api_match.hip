@@ -74,7 +74,8 @@ void sqrt_fix_kernel(const unsigned* __restrict__ fix, const int8_t* __restrict_
                      const int32_t* __restrict__ col_norm, const int8_t* __restrict__ red_rows,
                      const int32_t* __restrict__ red_norm, int nred,
                      unsigned long long* __restrict__ qbest, unsigned t_offset,
-                     int32_t* __restrict__ idx, float* __restrict__ dist)
+                     int32_t* __restrict__ idx, float* __restrict__ dist,
+                     const unsigned long long* __restrict__ red_real = nullptr)      // a grown reduced bank's real rows (Bank::real)
 {
     __shared__ unsigned long long best[2];
     const int tid = threadIdx.x;
@@ -89,6 +90,7 @@ void sqrt_fix_kernel(const unsigned* __restrict__ fix, const int8_t* __restrict_
         const int cn = col_norm[c];
         unsigned long long k0 = ~0ull, k1 = ~0ull;
         for (int m = tid; m < nred; m += 256) {
+            if (red_real && !real_row(red_real, m)) continue;
             int dot = 0;
 #pragma unroll
             for (int w = 0; w < kDim / 16; ++w) {
@@ -164,6 +166,27 @@ __global__ void xcheck_scatter_kernel(const unsigned long long* __restrict__ par
     // (t_offset: global index of this bank's first row when the train set is sharded over ranks)
     const unsigned long long key = ((unsigned long long)hi << 32) | (unsigned long long)((unsigned)t + t_offset);
     atomicMin(&qbest[q], key);
+}
+
+// A grown train bank in front of the election: its gap rows (padding inside the bank, Bank::real) were output rows of the
+// reverse sweep like any other and hold a key -- their nearest query row.  They elect nobody: their keys become "none" in
+// every split, which xcheck_scatter_kernel skips (and never lists in fix[]).  One thread per (split, 64-row word of the
+// bitmap): only the gap rows are written, a word without gaps costs one load.
+__global__ void xcheck_blank_gaps_kernel(unsigned long long* __restrict__ partial, int nsplit, int ncols_alloc, int64_t nt,
+                                         const unsigned long long* __restrict__ real)
+{
+    const int64_t nwords = (nt + 63) >> 6;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t w = gid % nwords;
+    const int64_t s = gid / nwords;
+    if (s >= nsplit) return;
+    const int64_t rows = nt - 64 * w;                           // rows of this word below nt: 1 .. 64 of them
+    unsigned long long gaps = ~real[w] & (rows >= 64 ? ~0ull : ((1ull << rows) - 1ull));
+    while (gaps) {
+        const int b = __ffsll((long long)gaps) - 1;
+        partial[(size_t)s * ncols_alloc + 64 * w + b] = ~0ull;
+        gaps &= gaps - 1ull;
+    }
 }
 
 // Cross-check step 3 + optional R1: decode qbest (high word = float32 distance bits), ratio = (double)dist / selfdist[q] in float64, pass = ratio < tau
@@ -614,11 +637,19 @@ int sweep_pair(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, int64_t
 // Election of the cross-check on stream s: per train row the minimum over the sweep's split partials ([nsplit][ncols_alloc]
 // top-1 keys; f32_keys: PairSweep's), scatter-min into qbest; the rows the scatter lists in fix are then redone exactly.
 // fix: zeroed tie list of nt rows for an integer-route pair whose norms allow d2 >= kSqrtTieMin, else null.
+// `partial` is the sweep's workspace and read-only here with one exception: for a GROWN train bank (t->real) the election
+// first overwrites the keys of the bank's gap rows with "none" in place (xcheck_blank_gaps_kernel) -- the partials are
+// consumed by this election and nothing reads them afterwards.
 static int enqueue_election(fm_ctx* ctx, hipStream_t s, const fm_bank* q, const fm_bank* t,
                             const unsigned long long* partial, int nsplit, int ncols_alloc, int f32_keys,
                             unsigned long long* qbest, unsigned t_offset, int* bound_reset, unsigned* fix)
 {
     const int64_t nt = t->n;
+    if (t->real && nt > 0 && nsplit > 0) {          // (a grown train bank only: one more small launch, nothing for any other bank)
+        hipLaunchKernelGGL(xcheck_blank_gaps_kernel, dim3((unsigned)((((nt + 63) >> 6) * nsplit + 255) / 256)), dim3(256), 0, s,
+                           const_cast<unsigned long long*>(partial), nsplit, ncols_alloc, nt, (const unsigned long long*)t->real);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     const int64_t sthreads = (bound_reset && (int64_t)ncols_alloc > nt * 4) ? (int64_t)ncols_alloc : nt * 4;
     hipLaunchKernelGGL(xcheck_scatter_kernel, dim3((unsigned)((sthreads + 255) / 256)), dim3(256), 0, s,
                        partial, nsplit, ncols_alloc, nt, qbest, t_offset, f32_keys, bound_reset, fix);
@@ -626,7 +657,7 @@ static int enqueue_election(fm_ctx* ctx, hipStream_t s, const fm_bank* q, const 
     if (fix) {
         hipLaunchKernelGGL(sqrt_fix_kernel<1>, dim3(kFixGrid), dim3(256), 0, s, (const unsigned*)fix,
                            (const int8_t*)t->rows8, (const int32_t*)t->norm, (const int8_t*)q->rows8, (const int32_t*)q->norm,
-                           (int)q->n, qbest, t_offset, (int32_t*)nullptr, (float*)nullptr);
+                           (int)q->n, qbest, t_offset, (int32_t*)nullptr, (float*)nullptr, (const unsigned long long*)q->real);
         HIP_TRY(ctx, hipGetLastError());
     }
     return FM_OK;
@@ -768,7 +799,7 @@ static int knn2_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t*
     if (ps.fix) {
         hipLaunchKernelGGL(sqrt_fix_kernel<2>, dim3(kFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)ps.fix,
                            (const int8_t*)q->rows8, (const int32_t*)q->norm, (const int8_t*)t->rows8, (const int32_t*)t->norm,
-                           (int)t->n, (unsigned long long*)nullptr, 0u, d_idx, d_dist);
+                           (int)t->n, (unsigned long long*)nullptr, 0u, d_idx, d_dist, (const unsigned long long*)t->real);
         HIP_TRY(ctx, hipGetLastError());
     }
     return FM_OK;

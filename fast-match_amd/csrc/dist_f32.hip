@@ -37,6 +37,7 @@ struct F32Params {
     unsigned long long* partial;
     const int*   run_flag;    // null, or: skip the whole launch unless *run_flag != 0
     int          self;        // the banks are one bank: row n is not a candidate for output row n (fm_self_dist)
+    const unsigned long long* red_real;   // a grown reduced bank with padding rows below nred: its real-row bitmap (Bank::real), else null
 };
 
 __device__ __forceinline__ void load_tile_kmajor(const float* __restrict__ rows, int row0, int row_end, float* __restrict__ img, int tid)
@@ -119,7 +120,8 @@ void rowreduce_f32_kernel(F32Params p)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int idx = m0 + j;
-                    if (idx < p.nred && s[i][j] <= thr[i] && !(p.self && idx == c0 + 4 * tn + i)) {
+                    if (idx < p.nred && s[i][j] <= thr[i] && !(p.self && idx == c0 + 4 * tn + i) &&
+                        !(p.red_real && !real_row(p.red_real, idx))) {
                         const float d = sqrtf(s[i][j]);
                         if (d < bd[i][KTOP - 1]) {            // strict: earlier row wins ties
                             if constexpr (KTOP == 2) {
@@ -208,6 +210,7 @@ hipError_t launch_rowreduce_f32(const Bank& cols, const Bank& red, int ktop, con
     F32Params p;
     p.run_flag = run_flag;
     p.self = self ? 1 : 0;
+    p.red_real = red.real;
     p.col_rows = cols.rowsf;
     p.ncols_pad = (int)cols.n_pad;
     p.red_rows = red.rowsf;

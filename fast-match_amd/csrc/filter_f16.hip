@@ -727,11 +727,13 @@ void rescore_kernel(RParams p)
 // scan is split over kFRescanSplit workgroups (thread t of part s takes rows s * chunk + t,
 // + 256, ...), each part leaves its top-2 in the scratch behind the flag words, and the part that
 // arrives last (a ticket per row) merges them: a 10k-row scan takes ~8 us instead of ~120 us.
+// The scan goes over the reduced rows by index, so unlike the filter and the rescoring of its candidates (which a padding
+// row's accumulator start keeps out by value) it has to be told about the gap rows of a grown bank: red_real, null otherwise.
 constexpr int kFRescanSplit = 16;
 
 template <int KTOP>
 __global__ __launch_bounds__(256)
-void rescan_kernel(RParams p, int nred)
+void rescan_kernel(RParams p, int nred, const unsigned long long* __restrict__ red_real)
 {
     __shared__ unsigned long long sk[256 * 2];
     __shared__ int last;
@@ -747,6 +749,7 @@ void rescan_kernel(RParams p, int nred)
     unsigned long long k0 = ~0ull, k1 = ~0ull;
     for (int m = m0 + threadIdx.x; m < m1; m += 256) {
         if (p.self && m == n) continue;
+        if (red_real && !real_row(red_real, m)) continue;     // a gap row of a grown reduced bank (Bank::real): scanned by index here
         const float4* rp = (const float4*)(p.red_rowsf + (size_t)m * kDim);
         float sum = 0.f;
 #pragma unroll 8
@@ -1002,8 +1005,8 @@ hipError_t launch_filter(const Bank& cols, const Bank& red, int ktop, const Filt
     r.self = self ? 1 : 0;
     if (cols.n > 0 && p.fused) {
         // the filter rescored its own entries; only the flagged rows are left
-        if (ktop == 1) hipLaunchKernelGGL((rescan_kernel<1>), dim3(kFMaxRescan * kFRescanSplit), dim3(256), 0, stream, r, (int)red.n);
-        else           hipLaunchKernelGGL((rescan_kernel<2>), dim3(kFMaxRescan * kFRescanSplit), dim3(256), 0, stream, r, (int)red.n);
+        if (ktop == 1) hipLaunchKernelGGL((rescan_kernel<1>), dim3(kFMaxRescan * kFRescanSplit), dim3(256), 0, stream, r, (int)red.n, (const unsigned long long*)red.real);
+        else           hipLaunchKernelGGL((rescan_kernel<2>), dim3(kFMaxRescan * kFRescanSplit), dim3(256), 0, stream, r, (int)red.n, (const unsigned long long*)red.real);
     } else if (cols.n > 0) {
         // lanes per output row: few slots and many rows -> one lane each (every lane of a wave
         // then runs a chain), else 16 or 64 lanes share a row's slots
@@ -1016,7 +1019,7 @@ hipError_t launch_filter(const Bank& cols, const Bank& red, int ktop, const Filt
             if (lpc == 1)       hipLaunchKernelGGL((rescore_kernel<K_, 1>), dim3(rgrid), dim3(256), 0, stream, r);  \
             else if (lpc == 16) hipLaunchKernelGGL((rescore_kernel<K_, 16>), dim3(rgrid), dim3(256), 0, stream, r); \
             else                hipLaunchKernelGGL((rescore_kernel<K_, 64>), dim3(rgrid), dim3(256), 0, stream, r); \
-            hipLaunchKernelGGL((rescan_kernel<K_>), dim3(kFMaxRescan * kFRescanSplit), dim3(256), 0, stream, r, (int)red.n);   \
+            hipLaunchKernelGGL((rescan_kernel<K_>), dim3(kFMaxRescan * kFRescanSplit), dim3(256), 0, stream, r, (int)red.n, (const unsigned long long*)red.real);   \
         } while (0)
         if (ktop == 1) FM_LAUNCH_RESCORE(1); else FM_LAUNCH_RESCORE(2);
 #undef FM_LAUNCH_RESCORE
@@ -1064,7 +1067,7 @@ hipError_t launch_filter_tri(const Bank& bank, const TriPlan& plan, int bound_ev
     r.slots = nullptr;  r.nsplit = 1;  r.ncols_alloc = plan.ncols_alloc;  r.bound = bound;
     r.col_rowsf = bank.rowsf;  r.col_norm = bank.normf;  r.red_rowsf = bank.rowsf;
     r.eps_c = p.eps_c;  r.eps_nm = p.eps_nm;  r.ncols = (int)bank.n;  r.partial = partial;  r.flag = flag;  r.self = 1;
-    hipLaunchKernelGGL((rescan_kernel<1>), dim3(kFMaxRescan * kFRescanSplit), dim3(256), 0, stream, r, (int)bank.n);
+    hipLaunchKernelGGL((rescan_kernel<1>), dim3(kFMaxRescan * kFRescanSplit), dim3(256), 0, stream, r, (int)bank.n, (const unsigned long long*)bank.real);
     return hipGetLastError();
 }
 

@@ -67,7 +67,20 @@ struct Bank {
     // every 128-wide plane null
     float*    wrows  = nullptr; // [n_pad][256] float32, zero padded
     uint16_t* wrowsh = nullptr; // [n_pad][256] fp16 of the scaled rows
+    // A bank that grew by appends (fm_bank_append_u8 / _f32) and has padding rows INSIDE it, below n (an append starts on a
+    // 32-row tile): the bitmap of its real rows, one 64-bit device word per 64 rows of cap_pad (fm_mask's word layout: bit b
+    // of word w = row 64 w + b).  Null for every bank without such gaps -- the kernels that mask padding by index (row < n)
+    // test it only when it is there; the matrix-core sweeps need nothing (a padding row's accumulator start keeps it out).
+    // A view (bank_rows_view) carries none: it is taken of one append's rows.
+    unsigned long long* real = nullptr;
+    unsigned long long* real_mem = nullptr;   // the allocation behind `real` (kept across fm_bank_refill_u8_async, which ends the gaps)
 };
+
+// Is row m a real row under a bank's `real` bitmap (see Bank)?  For the kernels that take it as an optional pointer.
+__device__ __forceinline__ bool real_row(const unsigned long long* __restrict__ real, int m)
+{
+    return (real[m >> 6] >> (m & 63)) & 1ull;
+}
 
 // rows rounded up to whole 128-row stages
 inline int64_t pad128(int64_t n) { return ((n + kStageRows - 1) / kStageRows) * kStageRows; }

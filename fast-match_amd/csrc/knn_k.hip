@@ -11,6 +11,9 @@
 // MASKED (K13, masked.hip: fm_knn_masked): a thread reads its query row's word of the bit mask once per 64-row stage and
 // tests one bit per candidate; a forbidden train row never becomes a key.  The unmasked instantiations compile to what
 // they were without the parameter (every masked statement sits under `if constexpr`).  Masked lists exist for K = 1 .. 8.
+// real (Bank::real, fm_internal.h): the real-row bitmap of a train bank that grew by appends and has padding rows below nt;
+// null for every other bank.  One uniform word per stage; a gap row never becomes a key (masked: the word is ANDed into the
+// mask word, unmasked: a test per candidate that runs only when the pointer is set).
 #include "tile_ops.h"
 
 namespace fm {
@@ -22,7 +25,8 @@ __global__ __launch_bounds__(256)
 void knnk_i8_kernel(const int8_t* __restrict__ qrows, const int32_t* __restrict__ qnorm, int nq,
                     const int8_t* __restrict__ trows, const int32_t* __restrict__ tnorm, int nt, int rows_per_split,
                     unsigned long long* __restrict__ partial,
-                    const unsigned long long* __restrict__ mask = nullptr, int64_t mwords = 0)
+                    const unsigned long long* __restrict__ mask = nullptr, int64_t mwords = 0,
+                    const unsigned long long* __restrict__ real = nullptr)
 {
     __shared__ __attribute__((aligned(16))) int8_t srow[kKnnStage * kDim];
     __shared__ int snorm[kKnnStage];
@@ -53,8 +57,12 @@ void knnk_i8_kernel(const int8_t* __restrict__ qrows, const int32_t* __restrict_
         const int rn = min(kKnnStage, t1 - base);
         unsigned long long mw = 0ull;              // MASKED: the row's permitted train rows of this stage (base % 64 == 0)
         if constexpr (MASKED) mw = live ? mask[(size_t)q * mwords + (base >> 6)] : 0ull;
+        unsigned long long rw = ~0ull;             // a grown train bank: the stage's real rows (uniform; null: every row < nt is real)
+        if (real) rw = real[base >> 6];
+        if constexpr (MASKED) mw &= rw;
         for (int r = 0; r < rn; ++r) {
             if constexpr (MASKED) { if (!((mw >> r) & 1ull)) continue; }
+            else { if (real && !((rw >> r) & 1ull)) continue; }
             int dot = 0;
 #pragma unroll
             for (int c = 0; c < kDim / 16; ++c) {
@@ -88,7 +96,8 @@ template <int K, bool MASKED = false>
 __global__ __launch_bounds__(256)
 void knnk_f32_kernel(const float* __restrict__ qrows, int nq, const float* __restrict__ trows, int nt, int rows_per_split,
                      unsigned long long* __restrict__ partial,
-                     const unsigned long long* __restrict__ mask = nullptr, int64_t mwords = 0)
+                     const unsigned long long* __restrict__ mask = nullptr, int64_t mwords = 0,
+                     const unsigned long long* __restrict__ real = nullptr)
 {
     constexpr int kStage = 32;                      // 32 rows x 512 B
     __shared__ __attribute__((aligned(16))) float srow[kStage * kDim];
@@ -114,8 +123,12 @@ void knnk_f32_kernel(const float* __restrict__ qrows, int nq, const float* __res
         const int rn = min(kStage, t1 - base);
         unsigned mw = 0u;                           // MASKED: this stage's half of the row's mask word (base % 32 == 0)
         if constexpr (MASKED) mw = live ? (unsigned)(mask[(size_t)q * mwords + (base >> 6)] >> (base & 32)) : 0u;
+        unsigned rw = ~0u;                          // a grown train bank: this stage's half of the real-row word (uniform)
+        if (real) rw = (unsigned)(real[base >> 6] >> (base & 32));
+        if constexpr (MASKED) mw &= rw;
         for (int r = 0; r < rn; ++r) {
             if constexpr (MASKED) { if (!((mw >> r) & 1u)) continue; }
+            else { if (real && !((rw >> r) & 1u)) continue; }
             float sum = 0.f;
 #pragma unroll
             for (int k4 = 0; k4 < kDim / 4; ++k4) {
@@ -203,10 +216,12 @@ hipError_t launch_knnk(const Bank& q, const Bank& t, int k, unsigned long long* 
 #define FM_KNNK(K_)                                                                                                       \
     case K_:                                                                                                               \
         if (q.kind == FM_BANK_F32)                                                                                         \
-            hipLaunchKernelGGL((knnk_f32_kernel<K_>), grid, dim3(256), 0, stream, (const float*)q.rowsf, nq, (const float*)t.rowsf, nt, per, partial); \
+            hipLaunchKernelGGL((knnk_f32_kernel<K_>), grid, dim3(256), 0, stream, (const float*)q.rowsf, nq, (const float*)t.rowsf, nt, per, partial, \
+                               (const unsigned long long*)nullptr, (int64_t)0, (const unsigned long long*)t.real); \
         else                                                                                                               \
             hipLaunchKernelGGL((knnk_i8_kernel<K_>), grid, dim3(256), 0, stream, (const int8_t*)q.rows8, (const int32_t*)q.norm, nq,   \
-                               (const int8_t*)t.rows8, (const int32_t*)t.norm, nt, per, partial);                         \
+                               (const int8_t*)t.rows8, (const int32_t*)t.norm, nt, per, partial,                          \
+                               (const unsigned long long*)nullptr, (int64_t)0, (const unsigned long long*)t.real);        \
         hipLaunchKernelGGL((knnk_merge_kernel<K_>), mgrid, dim3(256), 0, stream, (const unsigned long long*)partial, nsplit, nq, d_idx, d_dist); \
         break;
     switch (k) {
@@ -232,10 +247,11 @@ hipError_t launch_knnk_masked(const Bank& q, const Bank& t, int k, unsigned long
     case K_:                                                                                                               \
         if (q.kind == FM_BANK_F32)                                                                                         \
             hipLaunchKernelGGL((knnk_f32_kernel<K_, true>), grid, dim3(256), 0, stream, (const float*)q.rowsf, nq, (const float*)t.rowsf, nt, per, \
-                               partial, mask, mwords);                                                                     \
+                               partial, mask, mwords, (const unsigned long long*)t.real);                                  \
         else                                                                                                               \
             hipLaunchKernelGGL((knnk_i8_kernel<K_, true>), grid, dim3(256), 0, stream, (const int8_t*)q.rows8, (const int32_t*)q.norm, nq, \
-                               (const int8_t*)t.rows8, (const int32_t*)t.norm, nt, per, partial, mask, mwords);            \
+                               (const int8_t*)t.rows8, (const int32_t*)t.norm, nt, per, partial, mask, mwords,             \
+                               (const unsigned long long*)t.real);                                                         \
         break;
     switch (k) {
         FM_KNNKM(1) FM_KNNKM(2) FM_KNNKM(3) FM_KNNKM(4) FM_KNNKM(5) FM_KNNKM(6) FM_KNNKM(7) FM_KNNKM(8)

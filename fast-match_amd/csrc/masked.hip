@@ -9,6 +9,9 @@
 //                         an image starts on a 128-row stage, so its bits are whole words (two per stage) and setting one
 //                         image touches no other image's words -- and the padding behind EVERY image is forbidden by the
 //                         mask itself: the masked kernels need no per-stage real-row table (RSweep::st_real, stage_real).
+//                         The one padding a mask cannot know: the gap rows INSIDE a train bank that grew by appends (a pair
+//                         mask is made from row counts).  The kernels AND the bank's real-row word (Bank::real, the same
+//                         word layout, null for every other bank) into the mask word of each stage.
 //   mask_pack_kernel      one wave per word: 64 consecutive bytes of a source row (host rows staged in chunks of at most
 //                         64 MiB, or the caller's device memory read in place), nonzero = permitted, packed by ballot.
 //   masked_i8_kernel<K>   integer route, k = 1 and 2, on the matrix cores: v_mfma_i32_16x16x64_i8 in radius_i8_kernel's
@@ -108,7 +111,8 @@ template <int K>
 __global__ __launch_bounds__(256)
 void masked_i8_kernel(const int8_t* __restrict__ qrows, const int32_t* __restrict__ qnorm, int nq,
                       const int8_t* __restrict__ trows, const int32_t* __restrict__ tnorm, int nt, int per,
-                      const unsigned long long* __restrict__ mask, int64_t mwords, unsigned long long* __restrict__ partial)
+                      const unsigned long long* __restrict__ mask, int64_t mwords, unsigned long long* __restrict__ partial,
+                      const unsigned long long* __restrict__ real)
 {
     __shared__ __attribute__((aligned(16))) int8_t srow[kMStage * kMRowI8];
     __shared__ __attribute__((aligned(16))) int snorm[kMStage];
@@ -137,6 +141,11 @@ void masked_i8_kernel(const int8_t* __restrict__ qrows, const int32_t* __restric
         unsigned long long mw[kMNB];
 #pragma unroll
         for (int b = 0; b < kMNB; ++b) mw[b] = mrow[b] ? mrow[b][base >> 6] : 0ull;
+        if (real) {         // a grown train bank (Bank::real; uniform): the mask cannot know its gap rows -- forbidden here
+            const unsigned long long rw = real[base >> 6];
+#pragma unroll
+            for (int b = 0; b < kMNB; ++b) mw[b] &= rw;
+        }
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 2; ++i) {       // 64 rows x 8 pieces of 16 B (rows < n_pad: base % 64 == 0, n_pad % 128 == 0)
@@ -228,10 +237,10 @@ hipError_t launch_masked_i8(const Bank& q, const Bank& t, int k, const unsigned 
     const dim3 grid((unsigned)((nq + kMQPerWG - 1) / kMQPerWG), (unsigned)ns);
     if (k == 1)
         hipLaunchKernelGGL(masked_i8_kernel<1>, grid, dim3(256), 0, stream, (const int8_t*)q.rows8, (const int32_t*)q.norm, nq,
-                           (const int8_t*)t.rows8, (const int32_t*)t.norm, nt, per, mask, mwords, partial);
+                           (const int8_t*)t.rows8, (const int32_t*)t.norm, nt, per, mask, mwords, partial, (const unsigned long long*)t.real);
     else
         hipLaunchKernelGGL(masked_i8_kernel<2>, grid, dim3(256), 0, stream, (const int8_t*)q.rows8, (const int32_t*)q.norm, nq,
-                           (const int8_t*)t.rows8, (const int32_t*)t.norm, nt, per, mask, mwords, partial);
+                           (const int8_t*)t.rows8, (const int32_t*)t.norm, nt, per, mask, mwords, partial, (const unsigned long long*)t.real);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_knnk_merge(partial, ns, nq, k, d_idx, d_dist, stream);

@@ -25,6 +25,8 @@
 //   the real rows per 128-row stage, bounds `rowlim` beside the split's end -- one table word per 64-row stage, uniform.
 //   No padding row ever becomes a key; radius_compact_kernel<true> turns a key's physical row into (image, row) with
 //   coll_tab.h's lookup.  Physical order is logical order, so the keys sort as (distance bits, image, row) unchanged.
+// A plain bank that grew by appends has padding rows INSIDE it (Bank::real, fm_internal.h): the integer sweep drops them by
+//   the stage's real-row word (RSweep::real), the float32 route in radius_rescore_kernel -- the fp16 sweep is not touched.
 // Device forms (fm_radius_match_dev, fm_collection_radius_match_dev): the limits kernel reads the caller's radii in place,
 //   the offsets come from a device copy of the scan (integer route) or radius_offsets_kernel (float32 route, per chunk), the
 //   compaction writes the caller's arrays at the final offsets for the rows that fit in cap.  The host still reads the
@@ -71,7 +73,20 @@ struct RSweep {
     unsigned long long* keys;
     const int* st_real;        // a train collection's stack: real rows per 128-row stage (padding sits behind EVERY image and is
                                // masked by index, never by value); null: a plain bank, padding only behind row nt
+    const unsigned long long* real;   // a plain bank that grew by appends and has padding rows below nt: its real-row bitmap
+                                      // (Bank::real, one word per 64-row stage); null: none
 };
+
+// Grown train banks: the 16 candidates of a lane in the stage at `base` (tile tt, register r -> bit 4 tt + r, train row
+// base + 16 tt + 4 g + r) that are real rows.  One uniform 8-byte load per stage.
+__device__ __forceinline__ unsigned r_real_bits(const unsigned long long* __restrict__ real, int base, int g)
+{
+    const unsigned long long rw = real[base >> 6] >> (4 * g);
+    unsigned bits = 0;
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt) bits |= ((unsigned)(rw >> (16 * tt)) & 0xFu) << (4 * tt);
+    return bits;
+}
 
 // Rows of the 64-row stage at `base` that may be reported: up to the split's end t1 and, in a collection's stack, up to the
 // real rows of the 128-row stage the 64 rows lie in (one table word per stage; <= base where the stage's half is padding).
@@ -163,6 +178,7 @@ void radius_i8_kernel(RSweep p)
                     mask |= (d2 <= lim[b] && 16 * tt + r < rowlim) ? (1u << (4 * tt + r)) : 0u;
                 }
             }
+            if (p.real) mask &= r_real_bits(p.real, base, g);         // (uniform branch; a gap row of a grown bank is no hit)
             if constexpr (FILL) r_emit(p, mask, hi, qw + 16 * b + j, qw + 16 * b + j < p.nq, base, lane);
             else count[b] += __popc(mask);
         }
@@ -302,10 +318,13 @@ __global__ void radius_limits_kernel(const float* __restrict__ radius, float rad
     }
 }
 
-// Float32 route: the exact chain for every candidate key (query row << 32 | train row) of the chunk.
+// Float32 route: the exact chain for every candidate key (query row << 32 | train row) of the chunk.  real != null (a
+// grown train bank, Bank::real): the fp16 sweep let the bank's gap rows through as candidates like any row below nt -- they
+// are dropped here, by index, before they can count.
 __global__ __launch_bounds__(256)
 void radius_rescore_kernel(unsigned long long* __restrict__ keys, int64_t n, const float* __restrict__ qrowsf,
-                           const float* __restrict__ trowsf, const float* __restrict__ rr, unsigned* __restrict__ fcnt)
+                           const float* __restrict__ trowsf, const float* __restrict__ rr, unsigned* __restrict__ fcnt,
+                           const unsigned long long* __restrict__ real)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -323,7 +342,7 @@ void radius_rescore_kernel(unsigned long long* __restrict__ keys, int64_t n, con
         v = x.w - y.w; s = __builtin_fmaf(v, v, s);
     }
     const float d = sqrtf(s);
-    const bool keep = d < rr[q];
+    const bool keep = d < rr[q] && !(real && !real_row(real, (int)t));
     keys[i] = keep ? (((unsigned long long)__float_as_uint(d) << 32) | t) : ~0ull;
     if (keep) atomicAdd(&fcnt[q], 1u);
 }
@@ -607,6 +626,7 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
     sw.cq = cq; sw.ct = ct; sw.all = all ? 1 : 0;
     sw.nt = (int)nt; sw.lim = d_lim; sw.thr = d_thr;
     sw.st_real = a.tab ? (const int*)a.tab->st_real : nullptr;
+    sw.real = a.tab ? nullptr : t.real;
     // 1. counts (candidates on the float32 route), 2. their exclusive scan
     HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, (size_t)(nq + 1) * 4, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
@@ -668,7 +688,8 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
         if (f32) {
             HIP_TRY(ctx, hipMemsetAsync(d_fcnt, 0, (size_t)(nr + 1) * 4, ctx->stream));
             hipLaunchKernelGGL(radius_rescore_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ctx->stream, keys, nc,
-                               (const float*)(q.rowsf + (size_t)r0 * kDim), (const float*)t.rowsf, (const float*)(d_rr + r0), d_fcnt);
+                               (const float*)(q.rowsf + (size_t)r0 * kDim), (const float*)t.rowsf, (const float*)(d_rr + r0), d_fcnt,
+                               (const unsigned long long*)sw.real);
             HIP_TRY(ctx, hipGetLastError());
         }
         if ((rc = r_sort(ctx, keys, alt, nc, h_off.data(), d_off + r0, r0, r1, d_rows, d_beg, d_end)) != FM_OK) return rc;

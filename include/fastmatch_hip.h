@@ -977,9 +977,19 @@ int  fm_expand_run(fm_ctx* ctx, int32_t n, fm_expand* const* pairs, const double
  * computes that cell, appends its descriptors to the target bank, registers it and resumes.
  *   fm_bank_create_u8_cap : a bank with room for `capacity` rows (n of them now, possibly 0).
  *   fm_bank_append_u8     : n more rows at the next multiple of 32 rows (*first_row); FM_EINVAL when the capacity is used up.
- *                           The rows skipped in between are padding rows (never a nearest neighbour); a grown bank is meant for
- *                           fm_expand (cells name their own row ranges) -- as the TRAIN side of a dense call they would be
- *                           output rows like any other.
+ *                           The rows skipped in between ("gap rows") are padding rows INSIDE the bank, below its row count;
+ *                           row indices everywhere are the bank's physical rows, gaps included.  A grown bank is meant for
+ *                           fm_expand (cells name their own row ranges), and every dense call takes one too:
+ *                             as the TRAIN side a gap row is never a neighbour, an elected row or a list entry -- fm_knn2,
+ *                             fm_knn (every k), fm_xcheck1(_keys), fm_match_ratio / fm_match_accepted*, fm_knn2_ratio,
+ *                             fm_mutual_ratio, fm_radius_match, fm_knn_masked (whatever the mask says about a gap row: an
+ *                             fm_mask is made from row counts and cannot know the bank's gaps, the call forbids them),
+ *                             fm_self_dist, their _dev forms; the results are those of a fresh bank of the real rows with the
+ *                             indices mapped to physical rows, and no entry point refuses a grown bank for its gaps;
+ *                             as the QUERY side a gap position is an output row like any other: its slot holds a valid index
+ *                             or -1 and is otherwise unspecified (list forms may list it); the real rows' results are
+ *                             unaffected, in both directions of a cross-check.
+ *                           Wide, binary and collection banks take no appends, as before.
  *   fm_expand_set_cell    : cell (= col * rows + row) := rows [first_row, first_row + n_rows) with their full-image positions;
  *                           n_rows = 0 for a cell without features.
  *   fm_expand_run_lazy    : one run in slot 0, from the start (resume = 0) or from where the last launch parked (resume != 0:
