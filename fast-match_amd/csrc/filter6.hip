@@ -2,12 +2,13 @@
 //
 // The accepted-only calls hand K1 the ratio test's distance cut D* (ratio_cut.h): only candidates at d2 < D* can reach the
 // output, and on descriptor data those are a few in a million.  K1 still pays the full int8 MFMA rate to find them.  This
-// file sweeps the same (output chunk, split of the streamed bank) grid with K1's staging -- three LDS stage buffers filled by
-// LDS-DMA two stages ahead, the source-side XOR swizzle, the hand-over waits, the s_setprio burst -- but on
-// v_mfma_scale_f32_16x16x128_f8f6f4 with e2m3 operands: one instruction per 16 x 16 x 128 tile instead of two int8 ones,
-// each at half the cycles.  FP6 is lossy, so the sweep is a FILTER with a static per-row threshold that provably keeps
-// every candidate at d2 <= D* - 1 (fp6_filter.h); there are no shared bounds, no atomics on the fast path and no top-K
-// state.  A lane whose 8 candidates of a 32-row unit clear its threshold appends (output row, unit) to the pair's list;
+// file sweeps K1's splits of the streamed bank, two of K1's 512-row output chunks per workgroup, with K1's staging -- three
+// LDS stage buffers filled by LDS-DMA two stages ahead, the source-side XOR swizzle, the hand-over waits, the s_setprio
+// burst -- but on v_mfma_scale_f32_32x32x64_f8f6f4 with e2m3 operands: a wave holds 128 output rows and multiplies a 32-row
+// unit of the streamed bank against them with 8 instructions.  FP6 is lossy, so the sweep is a FILTER with a static
+// per-row threshold that provably keeps every candidate at d2 <= D* - 1 (fp6_filter.h); there are no shared bounds, no
+// atomics on the fast path and no top-K state.  A lane whose 16 candidates of a 32-row unit (one output row, half of the
+// unit's rows) clear its threshold appends (output row, unit) to the pair's list;
 // rescore6_kernel then computes the exact int32 d2 of each listed row against the unit's 32 streamed rows from the int8
 // plane, as K1 does, and folds (d2 << 32 | row) into slice 0 of the pair's `partial` with a 64-bit atomic minimum -- the key
 // K1 writes and the order the election reduces with (lowest streamed row on ties).  The sweep's workgroups preset their
@@ -16,21 +17,27 @@
 // rescoring (rowreduce.hip) then redoes such pairs in full.  Nothing waits on the host.
 //
 // Bank plane (Bank::rows6 / aux6 / stat6 / max6, prep6_kernel): the 128 codes of a row as four K-chunks of 32 codes (24
-// bytes) in 32-byte slots -- a row stays 128 bytes, so K1's LDS image and ds_read_b128 pattern carry over; lane (row, g) of a
-// fragment reads slot g, both operands through the same lane -> byte map, so the instruction's k order cancels.
+// bytes) in 32-byte slots -- a row stays 128 bytes, so K1's LDS image and its swizzle carry over; lane (row, half) of a
+// fragment reads slot 2 h + half for the instruction of K-half h, both operands through the same lane -> byte map, so the
+// instruction's k order cancels.
 #include "tile_ops.h"
 #include "fp6_filter.h"
 
 namespace fm {
 
-typedef int   v8i_6 __attribute__((ext_vector_type(8)));
-typedef float v4f_6 __attribute__((ext_vector_type(4)));
+typedef int   v8i_6  __attribute__((ext_vector_type(8)));
+typedef int   v2i_6  __attribute__((ext_vector_type(2)));
+typedef float v4f_6  __attribute__((ext_vector_type(4)));
+typedef float v16f_6 __attribute__((ext_vector_type(16)));
 
 #define F6_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define F6_GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
+#define F6_INLINE __attribute__((always_inline))
 
-constexpr int kF6NC = 4, kF6NW = 8;                       // blocks of 16 output rows per wave, waves per workgroup (K1's batched shape)
-constexpr int kF6ChunkRows = 16 * kF6NC * kF6NW;          // 512
+constexpr int kF6NC = 4, kF6NW = 8;                       // blocks of 32 output rows per wave, waves per workgroup
+constexpr int kF6PieceRows = 512;                         // K1's chunk in the batched shape: the granule of the plan and of `partial`
+constexpr int kF6ChunkRows = 32 * kF6NC * kF6NW;          // 1024: two of K1's chunks per workgroup
+constexpr int kF6Units = kStageRows / kTileRows;          // 32-row units per stage: 4
 constexpr float kF6Never = 3.0e38f;                       // threshold of an output row beyond the bank: no accumulator reaches it
 
 struct F6Params {
@@ -62,9 +69,9 @@ struct F6Batch {
 };
 
 // K1's issue_stage<true, 8>: 128 rows (16 KiB) + 1 KiB of accumulator starts per stage
-__device__ __forceinline__ void f6_issue_stage(const F6Params& p, int stage, char* buf, int wave, int lane)
+__device__ __forceinline__ void f6_issue_stage(const uint8_t* red_rows6, const float* red_aux6, int stage, char* buf, int wave, int lane)
 {
-    const uint8_t* src_rows = p.red_rows6 + (size_t)stage * kStageRowBytes;
+    const uint8_t* src_rows = red_rows6 + (size_t)stage * kStageRowBytes;
     const int slot = lane & 7;
     constexpr int kPieces = 16 / kF6NW;
 #pragma unroll
@@ -75,12 +82,36 @@ __device__ __forceinline__ void f6_issue_stage(const F6Params& p, int stage, cha
         __builtin_amdgcn_global_load_lds(F6_GLB_PTR(src), F6_LDS_PTR(buf + g * 1024), 16, 0, 0);
     }
     if (wave == kF6NW - 1) {
-        const float* src = p.red_aux6 + (size_t)stage * (kStageAuxBytes / 4) + (unsigned)(lane * 4);
+        const float* src = red_aux6 + (size_t)stage * (kStageAuxBytes / 4) + (unsigned)(lane * 4);
         __builtin_amdgcn_global_load_lds(F6_GLB_PTR(src), F6_LDS_PTR(buf + kStageRowBytes), 16, 0, 0);
     }
 }
 
-__global__ __launch_bounds__(64 * kF6NW, 4)
+// One 32-row unit of the streamed bank as a lane reads it: per K-half h the two 16-byte pieces of slot 2 h + (lane >> 5) of
+// row lane & 31 (the last 8 bytes are the slot's padding: the 6-register operand ends in front of them), and the accumulator
+// starts of the lane's 16 rows in the 32 x 32 C layout -- register r holds streamed row (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
+struct F6Unit {
+    v8i_6  a[2];      // (registers 6 and 7 are never written: the operand is the first six)
+    v16f_6 c;
+};
+
+__device__ __forceinline__ float f6_max16(const v16f_6& a)
+{
+    const float m0 = fmaxf(fmaxf(a[0], a[1]), a[2]);
+    const float m1 = fmaxf(fmaxf(a[3], a[4]), a[5]);
+    const float m2 = fmaxf(fmaxf(a[6], a[7]), a[8]);
+    const float m3 = fmaxf(fmaxf(a[9], a[10]), a[11]);
+    const float m4 = fmaxf(fmaxf(a[12], a[13]), a[14]);
+    const float m5 = fmaxf(fmaxf(m0, m1), m2);
+    const float m6 = fmaxf(fmaxf(m3, m4), a[15]);
+    return fmaxf(m5, m6);
+}
+
+// The sweep on v_mfma_scale_f32_32x32x64_f8f6f4: a wave owns 128 output rows (4 blocks of 32, the stationary B operand: 48
+// registers) and multiplies every 32-row unit of the streamed bank against them with 8 instructions, two per block chained
+// along K.  The reads of a unit are issued one unit ahead into a second register set, across the stage hand-over too: a
+// wave enters the barrier with the last unit of the stage it leaves in registers and multiplies it behind the barrier.
+__global__ __launch_bounds__(64 * kF6NW, 2)
 void filter6_kernel(F6Batch b)
 {
     __shared__ __attribute__((aligned(16))) char smem[3 * kStageBytes];
@@ -93,62 +124,94 @@ void filter6_kernel(F6Batch b)
     const int tid  = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-    const int g    = lane >> 4;
-    const int c16  = lane & 15;
-    const int chunk = bid % p.nchunks, split = bid / p.nchunks;
-    if (split >= p.nsplit) return;
-    const int st0 = split * p.stages_per_split;
-    const int st1 = min(st0 + p.stages_per_split, p.nstages);
-    const int cb  = chunk * kF6ChunkRows + wave * (16 * kF6NC);
+    const int r32  = lane & 31;
+    const int hs   = lane >> 5;
+    // everything the loop uses, once: a field read through `p` inside the loop is a scalar load of the kernel argument there
+    const int nsplit = p.nsplit, nstages = p.nstages, per = p.stages_per_split, ncols = p.ncols, ncols_pad = p.ncols_pad;
+    const int ncols_alloc = p.ncols_alloc;
+    const int nch = (p.nchunks + 1) >> 1;
+    const uint8_t* const red_rows6 = p.red_rows6;
+    const float* const red_aux6 = p.red_aux6;
+    uint2* const rec = p.rec;
+    unsigned* const cnt = p.cnt;
+    const unsigned cap = p.cap;
+    const int chunk = bid % nch, split = bid / nch;
+    if (split >= nsplit) return;
+    const int st0 = split * per;
+    const int st1 = min(st0 + per, nstages);
+    const int cb  = chunk * kF6ChunkRows + wave * (32 * kF6NC);
 
     const unsigned dstar = *p.cut;
     if (dstar == kNoRatioCut) {               // no finite cut (device-side knowledge: the largest self distance): K1 redoes the pair
-        if (tid == 0) p.cnt[1] = 1u;
+        if (tid == 0) cnt[1] = 1u;
         return;
     }
-    // this workgroup's piece of K1's key array starts empty (the rescoring folds into slice 0 after this kernel)
-    p.partial[(size_t)split * p.ncols_alloc + chunk * kF6ChunkRows + tid] = ~0ull;
+    // this workgroup's pieces of K1's key array start empty (the rescoring folds into slice 0 after this kernel); an odd
+    // number of K1 chunks leaves the last workgroup's second piece outside the array
+    {
+        unsigned long long* mine = p.partial + (size_t)split * ncols_alloc + chunk * kF6ChunkRows;
+        mine[tid] = ~0ull;
+        if (chunk * kF6ChunkRows + kF6PieceRows < ncols_alloc) mine[kF6PieceRows + tid] = ~0ull;
+    }
 
-    // stationary operand: chunk g (32 codes, 24 of 32 bytes) of this wave's 4 x 16 output rows; thresholds
-    v8i_6 bf[kF6NC];
+    // stationary operand: per block j and K-half h, slot 2 h + (lane >> 5) (32 codes, 24 of 32 bytes) of output row
+    // cb + 32 j + (lane & 31); one threshold per lane and block
+    v8i_6 bf[kF6NC][2];
     float thr[kF6NC];
     {
         const int um = p.red_max[0], em = p.red_max[1];
-        v4i lo[kF6NC], hi[kF6NC], stat[kF6NC];
+        v4i lo[kF6NC][2], stat[kF6NC];
+        v2i_6 hi[kF6NC][2];
 #pragma unroll
         for (int j = 0; j < kF6NC; ++j) {
-            const int n = cb + 16 * j + c16;
-            lo[j] = hi[j] = stat[j] = v4i{0, 0, 0, 0};
-            if (n < p.ncols_pad) {
-                lo[j] = *(const v4i*)(p.col_rows6 + (size_t)n * kDim + 32 * g);
-                hi[j] = *(const v4i*)(p.col_rows6 + (size_t)n * kDim + 32 * g + 16);
+            const int n = cb + 32 * j + r32;
+            stat[j] = v4i{0, 0, 0, 0};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                lo[j][h] = v4i{0, 0, 0, 0};
+                hi[j][h] = v2i_6{0, 0};
+                if (n < ncols_pad) {
+                    const uint8_t* src = p.col_rows6 + (size_t)n * kDim + 32 * (2 * h + hs);
+                    lo[j][h] = *(const v4i*)src;
+                    hi[j][h] = *(const v2i_6*)(src + 16);
+                }
             }
-            if (n < p.ncols) stat[j] = *(const v4i*)(p.col_stat + 4 * (size_t)n);
+            if (n < ncols) stat[j] = *(const v4i*)(p.col_stat + 4 * (size_t)n);
         }
         // (a use of every loaded register in front of the prefetch: the compiler waits for the loads HERE -- with the first
         // use inside the stage loop its wait is a vmcnt(0) in front of every stage's first MFMA, which drains the LDS-DMA)
 #pragma unroll
-        for (int j = 0; j < kF6NC; ++j) asm volatile("" : "+v"(lo[j]), "+v"(hi[j]), "+v"(stat[j]));
+        for (int j = 0; j < kF6NC; ++j)
+            asm volatile("" : "+v"(lo[j][0]), "+v"(hi[j][0]), "+v"(lo[j][1]), "+v"(hi[j][1]), "+v"(stat[j]));
 #pragma unroll
         for (int j = 0; j < kF6NC; ++j) {
-            const int n = cb + 16 * j + c16;
-            thr[j] = n < p.ncols ? fp6_threshold_acc(fp6_threshold(stat[j][0], stat[j][1], stat[j][2], um, em, dstar)) : kF6Never;
-            bf[j] = v8i_6{lo[j][0], lo[j][1], lo[j][2], lo[j][3], hi[j][0], hi[j][1], 0, 0};
+            const int n = cb + 32 * j + r32;
+            thr[j] = n < ncols ? fp6_threshold_acc(fp6_threshold(stat[j][0], stat[j][1], stat[j][2], um, em, dstar)) : kF6Never;
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                bf[j][h] = v8i_6{lo[j][h][0], lo[j][h][1], lo[j][h][2], lo[j][h][3], hi[j][h][0], hi[j][h][1], 0, 0};
         }
     }
 
-    // per-lane LDS offsets of the streamed fragments: the two 16-byte pieces of slot g, swizzled as staged
-    const int sw = (c16 >> 1) & 7;
-    const int aoff0 = c16 * kDim + 16 * ((2 * g) ^ sw), aoff1 = c16 * kDim + 16 * ((2 * g + 1) ^ sw);
-    const int xoff = kStageRowBytes + 16 * g;
+    // per-lane LDS offsets of the streamed fragments (the two 16-byte pieces of slot 2 h + hs, swizzled as staged) and of
+    // the lane's accumulator starts
+    const int sw = (r32 >> 1) & 7;
+    int aoff0[2], aoff1[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        aoff0[h] = r32 * kDim + 16 * ((2 * (2 * h + hs)) ^ sw);
+        aoff1[h] = r32 * kDim + 16 * ((2 * (2 * h + hs) + 1) ^ sw);
+    }
+    const int xoff = kStageRowBytes + 16 * hs;
     constexpr int kDmaPerWave = 16 / kF6NW;
 
-    if (st0 < st1) f6_issue_stage(p, st0, smem, wave, lane);
-    if (st0 + 1 < st1) f6_issue_stage(p, st0 + 1, smem + kStageBytes, wave, lane);
+    if (st0 < st1) f6_issue_stage(red_rows6, red_aux6, st0, smem, wave, lane);
+    if (st0 + 1 < st1) f6_issue_stage(red_rows6, red_aux6, st0 + 1, smem + kStageBytes, wave, lane);
 
-    auto stage = [&](auto buf_tag, int st) {
+    // stage st becomes readable in buffer BUF; the DMA of stage st + 2 goes where stage st - 1 was (every wave has the whole
+    // of that stage in registers or behind it: its reads are waited for in front of the barrier)
+    auto hand_over = [&](auto buf_tag, int st) F6_INLINE {
         constexpr int BUF = decltype(buf_tag)::value;
-        char* buf = smem + BUF * kStageBytes;
         // stage st's DMA was issued two hand-overs ago; only the DMA of stage st + 1 may still be in flight (a wave that
         // appended records since has drained its vector memory counter there, which only makes this wait a no-op)
         if (st + 1 < st1) {
@@ -158,63 +221,100 @@ void filter6_kernel(F6Batch b)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (st + 2 < st1) f6_issue_stage(p, st + 2, smem + ((BUF + 2) % 3) * kStageBytes, wave, lane);
+        if (st + 2 < st1) f6_issue_stage(red_rows6, red_aux6, st + 2, smem + ((BUF + 2) % 3) * kStageBytes, wave, lane);
+    };
 
+    auto read_unit = [&](F6Unit& x, const char* buf, int u) F6_INLINE {
+        const char* rows = buf + 32 * u * kDim;
 #pragma unroll
-        for (int u = 0; u < kStageRows / kTileRows; ++u) {
-            v4f_6 acc[2][kF6NC];
-            __builtin_amdgcn_s_setprio(2);
+        for (int h = 0; h < 2; ++h) {
+            const v4i   lo = *(const v4i*)(rows + aoff0[h]);
+            const v2i_6 hi = *(const v2i_6*)(rows + aoff1[h]);       // the 8 real bytes of the second piece
+            x.a[h] = __builtin_shufflevector(__builtin_shufflevector(lo, lo, 0, 1, 2, 3, -1, -1, -1, -1),
+                                             __builtin_shufflevector(hi, hi, 0, 1, -1, -1, -1, -1, -1, -1), 0, 1, 2, 3, 8, 9, -1, -1);
+        }
+        v4f_6 c[4];
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const char* rows = buf + (32 * u + 16 * s) * kDim;
-                const v4i a0 = *(const v4i*)(rows + aoff0);
-                const v4i a1 = *(const v4i*)(rows + aoff1);
-                const v4f_6 ci = *(const v4f_6*)(buf + xoff + (32 * u + 16 * s) * 4);
-                const v8i_6 af = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};      // (the last 8 bytes are the slot's padding: not read)
+        for (int q = 0; q < 4; ++q) c[q] = *(const v4f_6*)(buf + xoff + (32 * u + 8 * q) * 4);
+        x.c = v16f_6{c[0][0], c[0][1], c[0][2], c[0][3], c[1][0], c[1][1], c[1][2], c[1][3],
+                     c[2][0], c[2][1], c[2][2], c[2][3], c[3][0], c[3][1], c[3][2], c[3][3]};
+    };
+
+    // The 8 instructions of one unit, the reads of the next one (`next`) behind them, then the unit's epilogue.  The compiler
+    // cannot count LDS reads while an LDS-DMA is in flight -- its wait in front of the first instruction is lgkmcnt(0) -- so
+    // the reads of the next unit must not be issued before that wait: the scheduling barrier keeps them behind the
+    // instructions, where they have this unit's epilogue and the other wave's instructions to land in.
+    auto multiply = [&](const F6Unit& x, unsigned unit, F6Unit& y, const char* ybuf, auto yu_tag) F6_INLINE {
+        v16f_6 acc[kF6NC];
+        __builtin_amdgcn_s_setprio(2);
+        // K-half major: the two instructions of a block are four apart
 #pragma unroll
-                for (int j = 0; j < kF6NC; ++j)
-                    acc[s][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf[j], ci, 2, 2, 0, 127, 0, 127);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            float tmax[kF6NC];
-            bool any = false;
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int j = 0; j < kF6NC; ++j)
+                acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(x.a[h], bf[j][h], h == 0 ? x.c : acc[j], 2, 2, 0, 127, 0, 127);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (decltype(yu_tag)::value >= 0) read_unit(y, ybuf, decltype(yu_tag)::value);
+        __builtin_amdgcn_s_setprio(0);
+        float tmax[kF6NC];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < kF6NC; ++j) {
+            tmax[j] = f6_max16(acc[j]);
+            any |= tmax[j] >= thr[j];
+        }
+        if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+            // (both halves of the wave hold candidates of an output row: a row may be listed twice for a unit, which the
+            // rescoring's atomic minimum does not mind)
 #pragma unroll
             for (int j = 0; j < kF6NC; ++j) {
-                const float m0 = fmaxf(fmaxf(acc[0][j][0], acc[0][j][1]), acc[0][j][2]);
-                const float m1 = fmaxf(fmaxf(acc[0][j][3], acc[1][j][0]), acc[1][j][1]);
-                tmax[j] = fmaxf(fmaxf(fmaxf(acc[1][j][2], acc[1][j][3]), m0), m1);
-                any |= tmax[j] >= thr[j];
-            }
-            if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
-                const unsigned unit = (unsigned)(st * (kStageRows / kTileRows) + u);
-#pragma unroll
-                for (int j = 0; j < kF6NC; ++j) {
-                    const bool hit = tmax[j] >= thr[j];
-                    const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-                    if (m == 0ull) continue;
-                    // one atomic per wave: the lowest lane of the ballot reserves the records of all of them
-                    const int first = __builtin_ctzll(m);
-                    unsigned base = 0;
-                    if ((tid & 63) == first) base = atomicAdd(p.cnt, (unsigned)__popcll(m));
-                    base = (unsigned)__builtin_amdgcn_readlane((int)base, first);
-                    const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                    if (hit) {
-                        const unsigned at = base + rank;
-                        if (at < p.cap) p.rec[at] = make_uint2((unsigned)(cb + 16 * j + c16), unit);
-                        else            p.cnt[1] = 1u;
-                    }
+                const bool hit = tmax[j] >= thr[j];
+                const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+                if (m == 0ull) continue;
+                // one atomic per wave: the lowest lane of the ballot reserves the records of all of them
+                const int first = __builtin_ctzll(m);
+                unsigned base = 0;
+                if (lane == first) base = atomicAdd(cnt, (unsigned)__popcll(m));
+                base = (unsigned)__builtin_amdgcn_readlane((int)base, first);
+                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                if (hit) {
+                    const unsigned at = base + rank;
+                    if (at < cap) rec[at] = make_uint2((unsigned)(cb + 32 * j + r32), unit);
+                    else          cnt[1] = 1u;
                 }
-                // (the hand-over waits count on the LDS-DMA being this wave's newest vector memory operations)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
+            // (the hand-over waits count on the LDS-DMA being this wave's newest vector memory operations)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
     };
 
+    // The two register sets: even and odd units of a stage.  The last unit of a stage is multiplied behind the NEXT hand-over,
+    // so a wave enters the barrier with that unit's reads issued a unit earlier and leaves it with work in registers; in
+    // front of the first stage its place is taken by a unit of padding rows (below every threshold).
+    F6Unit ua, ub;
+    ub.a[0] = ub.a[1] = v8i_6{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ub.c[r] = kFp6PadInit;
+    std::integral_constant<int, 0> u0;  std::integral_constant<int, 1> u1;  std::integral_constant<int, 2> u2;
+    std::integral_constant<int, 3> u3;  std::integral_constant<int, -1> none;
+    auto stage = [&](auto buf_tag, int st) F6_INLINE {
+        constexpr int BUF = decltype(buf_tag)::value;
+        const char* buf = smem + BUF * kStageBytes;
+        const unsigned unit0 = (unsigned)(st * kF6Units);
+        hand_over(buf_tag, st);
+        multiply(ub, unit0 - 1, ua, buf, u0);
+        multiply(ua, unit0,     ub, buf, u1);
+        multiply(ub, unit0 + 1, ua, buf, u2);
+        multiply(ua, unit0 + 2, ub, buf, u3);
+    };
+
+    if (st0 >= st1) return;
     for (int st = st0; st < st1; st += 3) {
         stage(std::integral_constant<int, 0>{}, st);
         if (st + 1 < st1) stage(std::integral_constant<int, 1>{}, st + 1);
         if (st + 2 < st1) stage(std::integral_constant<int, 2>{}, st + 2);
     }
+    multiply(ub, (unsigned)(st1 * kF6Units) - 1u, ua, smem, none);
 }
 
 // One wave per record: exact int32 d2 of the output row against the unit's 32 streamed rows (lane l: row l & 31, K-half
@@ -340,7 +440,7 @@ hipError_t launch_filter6(int n, const Bank* const* cols, const Bank* const* red
     long long total = 0;
     for (int i = 0; i < n; ++i) {
         const RowReducePlan& pl = plans[i];
-        if (pl.nb != kF6NC || pl.nw != kF6NW || !filter6_usable(*cols[i], *red[i]) || !cut[i]) return hipErrorInvalidValue;
+        if (pl.nb != 4 || pl.nw != 8 || !filter6_usable(*cols[i], *red[i]) || !cut[i]) return hipErrorInvalidValue;
         F6Params& p = b.p[i];
         p.col_rows6 = cols[i]->rows6;  p.col_stat = cols[i]->stat6;  p.ncols = (int)cols[i]->n;  p.ncols_pad = (int)cols[i]->n_pad;
         p.red_rows6 = red[i]->rows6;   p.red_aux6 = red[i]->aux6;    p.red_max = red[i]->max6;
@@ -351,7 +451,7 @@ hipError_t launch_filter6(int n, const Bank* const* cols, const Bank* const* red
         p.col_rows8 = cols[i]->rows8;  p.col_norm = cols[i]->norm;  p.red_rows8 = red[i]->rows8;  p.red_norm = red[i]->norm;
         p.nred = (int)red[i]->n;
         b.first_block[i] = (int)total;
-        total += (long long)pl.nchunks * pl.nsplit;
+        total += (long long)((pl.nchunks + 1) / 2) * pl.nsplit;      // a workgroup takes two of K1's chunks
     }
     if (total > INT32_MAX) return hipErrorInvalidValue;
     for (int i = n; i < kRRBatchMax; ++i) b.p[i] = b.p[0];
