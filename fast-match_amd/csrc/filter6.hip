@@ -8,7 +8,8 @@
 // unit of the streamed bank against them with 8 instructions.  FP6 is lossy, so the sweep is a FILTER with a static
 // per-row threshold that provably keeps every candidate at d2 <= D* - 1 (fp6_filter.h); there are no shared bounds, no
 // atomics on the fast path and no top-K state.  A lane whose 16 candidates of a 32-row unit (one output row, half of the
-// unit's rows) clear its threshold appends (output row, unit) to the pair's list;
+// unit's rows) clear its threshold writes (output row, unit) to its wave's list in LDS, which the wave copies to the pair's
+// list when it is full and when its sweep ends;
 // rescore6_kernel then computes the exact int32 d2 of each listed row against the unit's 32 streamed rows from the int8
 // plane, as K1 does, and folds (d2 << 32 | row) into slice 0 of the pair's `partial` with a 64-bit atomic minimum -- the key
 // K1 writes and the order the election reduces with (lowest streamed row on ties).  The sweep's workgroups preset their
@@ -39,6 +40,9 @@ constexpr int kF6PieceRows = 512;                         // K1's chunk in the b
 constexpr int kF6ChunkRows = 32 * kF6NC * kF6NW;          // 1024: two of K1's chunks per workgroup
 constexpr int kF6Units = kStageRows / kTileRows;          // 32-row units per stage: 4
 constexpr float kF6Never = 3.0e38f;                       // threshold of an output row beyond the bank: no accumulator reaches it
+constexpr int kF6HitSlots = 128;                          // records of a wave's private list in LDS (one block's ballot delivers <= 64)
+static_assert(kF6HitSlots >= 64 && kF6HitSlots % 64 == 0, "a block's ballot must fit an empty list; the flush copies 64 at a time");
+static_assert(3 * kStageBytes + kF6NW * kF6HitSlots * 8 <= 65536, "the kernel's static LDS");
 
 struct F6Params {
     const uint8_t* col_rows6;
@@ -114,7 +118,7 @@ __device__ __forceinline__ float f6_max16(const v16f_6& a)
 __global__ __launch_bounds__(64 * kF6NW, 2)
 void filter6_kernel(F6Batch b)
 {
-    __shared__ __attribute__((aligned(16))) char smem[3 * kStageBytes];
+    __shared__ __attribute__((aligned(16))) char smem[3 * kStageBytes + kF6NW * kF6HitSlots * 8];
     int pair = 0;
 #pragma unroll
     for (int i = 1; i < kRRBatchMax; ++i) pair += (int)blockIdx.x >= b.first_block[i] ? 1 : 0;
@@ -135,7 +139,9 @@ void filter6_kernel(F6Batch b)
     uint2* const rec = p.rec;
     unsigned* const cnt = p.cnt;
     const unsigned cap = p.cap;
-    const int chunk = bid % nch, split = bid / nch;
+    // (uniform, but the quotient comes out of the vector unit: left there, the stage counter and the DMA addresses of every
+    // hand-over follow it into vector registers)
+    const int split = __builtin_amdgcn_readfirstlane(bid / nch), chunk = bid - split * nch;
     if (split >= nsplit) return;
     const int st0 = split * per;
     const int st1 = min(st0 + per, nstages);
@@ -213,7 +219,7 @@ void filter6_kernel(F6Batch b)
     auto hand_over = [&](auto buf_tag, int st) F6_INLINE {
         constexpr int BUF = decltype(buf_tag)::value;
         // stage st's DMA was issued two hand-overs ago; only the DMA of stage st + 1 may still be in flight (a wave that
-        // appended records since has drained its vector memory counter there, which only makes this wait a no-op)
+        // flushed its records since has drained its vector memory counter there, which only makes this wait a no-op)
         if (st + 1 < st1) {
             if (wave == kF6NW - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kDmaPerWave + 1) : "memory");
             else                   asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kDmaPerWave) : "memory");
@@ -238,6 +244,32 @@ void filter6_kernel(F6Batch b)
         for (int q = 0; q < 4; ++q) c[q] = *(const v4f_6*)(buf + xoff + (32 * u + 8 * q) * 4);
         x.c = v16f_6{c[0][0], c[0][1], c[0][2], c[0][3], c[1][0], c[1][1], c[1][2], c[1][3],
                      c[2][0], c[2][1], c[2][2], c[2][3], c[3][0], c[3][1], c[3][2], c[3][3]};
+    };
+
+    // A wave's records wait in a private list in LDS behind the stage buffers until the list is full or the sweep ends:
+    // nothing reads them before the kernel has ended (the rescoring folds with an atomic minimum, in any order), and a
+    // global atomic inside the loop makes the wave, and at the next barrier the workgroup, wait for an L2 round trip.
+    // `nrec`, the list's fill, is wave-uniform.  The flush reserves the records on the pair's counter with one atomic,
+    // copies them out and drains the vector memory counter: the hand-over waits count on the LDS-DMA being this wave's
+    // newest vector memory operations.  No barrier: only this wave touches its list.
+    const uint2* const hits = (const uint2*)(smem + 3 * kStageBytes) + wave * kF6HitSlots;
+    const unsigned hits_lds = (unsigned)(uintptr_t)F6_LDS_PTR(hits);
+    unsigned nrec = 0;
+    auto flush = [&]() F6_INLINE {
+        unsigned base = 0;
+        if (lane == 0) base = atomicAdd(cnt, nrec);
+        base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+#pragma unroll
+        for (int k = 0; k < kF6HitSlots / 64; ++k) {
+            const unsigned i = (unsigned)(64 * k + lane);
+            if (i < nrec) {
+                const uint2 r = hits[i];
+                if (base + i < cap) rec[base + i] = r;
+                else                cnt[1] = 1u;
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        nrec = 0;
     };
 
     // The 8 instructions of one unit, the reads of the next one (`next`) behind them, then the unit's epilogue.  The compiler
@@ -271,20 +303,17 @@ void filter6_kernel(F6Batch b)
                 const bool hit = tmax[j] >= thr[j];
                 const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
                 if (m == 0ull) continue;
-                // one atomic per wave: the lowest lane of the ballot reserves the records of all of them
-                const int first = __builtin_ctzll(m);
-                unsigned base = 0;
-                if (lane == first) base = atomicAdd(cnt, (unsigned)__popcll(m));
-                base = (unsigned)__builtin_amdgcn_readlane((int)base, first);
+                const unsigned pc = (unsigned)__popcll(m);
+                if (nrec + pc > (unsigned)kF6HitSlots) flush();
                 const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                // (LDS only: the hand-over's lgkmcnt(0) covers the write, which touches no stage buffer.  As a statement of
+                // its own: in front of a store to LDS the compiler waits for vmcnt(0), the LDS-DMA being a pending LDS write)
                 if (hit) {
-                    const unsigned at = base + rank;
-                    if (at < cap) rec[at] = make_uint2((unsigned)(cb + 32 * j + r32), unit);
-                    else          cnt[1] = 1u;
+                    const unsigned long long r = ((unsigned long long)unit << 32) | (unsigned)(cb + 32 * j + r32);
+                    asm volatile("ds_write_b64 %0, %1" :: "v"(hits_lds + 8u * (nrec + rank)), "v"(r) : "memory");
                 }
+                nrec += pc;
             }
-            // (the hand-over waits count on the LDS-DMA being this wave's newest vector memory operations)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
     };
 
@@ -315,6 +344,7 @@ void filter6_kernel(F6Batch b)
         if (st + 2 < st1) stage(std::integral_constant<int, 2>{}, st + 2);
     }
     multiply(ub, (unsigned)(st1 * kF6Units) - 1u, ua, smem, none);
+    if (nrec != 0u) flush();
 }
 
 // One wave per record: exact int32 d2 of the output row against the unit's 32 streamed rows (lane l: row l & 31, K-half
