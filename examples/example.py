@@ -84,3 +84,11 @@ wide_q = wide_t[:500] + np.float32(0.01) * rng.standard_normal((500, 256)).astyp
 qidx, tidx, dist, ratio = matchutil.mutual_ratio_match_arrays(wide_q, wide_t, 0.8)
 print("256-D pair: %d of 500 query rows matched mutually at ratio 0.8" % len(qidx))
 assert np.array_equal(qidx, tidx) and len(qidx) == 500
+
+# ... and so does their match graph: wide images enter a collection through add_wide, matchPairs is the call it was.
+wide_views = [wide_t[300 * i:300 * i + 400].copy() for i in range(4)]      # neighbouring views share 100 rows
+wide_graph = matchutil.BFMatcher(matchutil.NORM_L2)
+wide_graph.add_wide(wide_views)
+wide_edges = wide_graph.matchPairs(ratio=0.8, symmetric=True)
+print("256-D match graph: %d pairs, (0, 1) has %d matches, (0, 2) has %d" % (len(wide_edges), len(wide_edges[(0, 1)]), len(wide_edges[(0, 2)])))
+assert len(wide_edges) == 6 and len(wide_edges[(0, 1)]) == 100 and len(wide_edges[(0, 2)]) == 0

@@ -171,6 +171,9 @@ SYMBOLS = {
     "fm_collection_pairs_mutual_ratio_dev": (_INT, [_P, _P, _P, _I64, ctypes.c_double, ctypes.c_int32, _I64, _P, _P,
                                                     ctypes.POINTER(_I64), _P]),
     "fm_collection_add_dev": (_INT, [_P, _P, _P, _INT, _I64, _INT, _I64, _P, ctypes.POINTER(_I32)]),
+    # wide collections (K14): images of 129 .. 256 float values per row, served by fm_collection_pairs_mutual_ratio(_dev)
+    "fm_collection_add_wide": (_INT, [_P, _P, _P, _I64, _INT, ctypes.POINTER(_I32)]),
+    "fm_collection_add_wide_dev": (_INT, [_P, _P, _P, _INT, _I64, _INT, _I64, _P, ctypes.POINTER(_I32)]),
     "fm_collection_knn_dev": (_INT, [_P, _P, _P, _I32, _P, _P, _P, _P]),
     "fm_collection_knn2_ratio_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
     "fm_collection_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
@@ -526,6 +529,27 @@ class Collection(object):
         i = _I32(-1)
         self.ctx._check(self.ctx.lib.fm_collection_add_dev(self.ctx.handle, self.handle, _P(int(ptr)) if ptr else None, int(dtype),
                                                            int(n), int(dim), int(pitch), _stream_arg(stream), ctypes.byref(i)))
+        return int(i.value)
+
+    def add_wide(self, rows):
+        """Append one WIDE image ([n, dim] float32, 129 <= dim <= 256, any values; n may be 0) -- ``fm_collection_add_wide``.
+        The first one makes the collection a wide one (kind ``FM_BANK_F32W``): it takes no other images and serves ``info``,
+        ``image_rows``, ``train``, ``clear`` and the ``pairs_mutual_ratio*`` calls.  Returns the image's index."""
+        a = np.ascontiguousarray(rows, dtype=np.float32)
+        if a.ndim != 2:
+            raise ValueError("an image's descriptors must be 2-D [n, dim]")
+        i = _I32(-1)
+        self.ctx._check(self.ctx.lib.fm_collection_add_wide(self.ctx.handle, self.handle, _ptr(a) if a.shape[0] else None, a.shape[0],
+                                                            a.shape[1], ctypes.byref(i)))
+        return int(i.value)
+
+    def add_wide_from_device(self, ptr, dtype, n, dim, pitch=0, stream=None):
+        """``add_wide`` from rows in device memory (``fm_collection_add_wide_dev``): ``FM_DT_F32`` / ``FM_DT_F16`` /
+        ``FM_DT_BF16`` elements, otherwise as ``add_from_device``.  The collection is the one ``add_wide`` builds from the same
+        (widened) values."""
+        i = _I32(-1)
+        self.ctx._check(self.ctx.lib.fm_collection_add_wide_dev(self.ctx.handle, self.handle, _P(int(ptr)) if ptr else None, int(dtype),
+                                                                int(n), int(dim), int(pitch), _stream_arg(stream), ctypes.byref(i)))
         return int(i.value)
 
     def knn_dev(self, q, k, img_ptr, idx_ptr, dist_ptr, consumer_stream=None):

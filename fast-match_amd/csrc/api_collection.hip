@@ -34,6 +34,8 @@ using namespace fm;
 // row (<= 3.3e18) as long as no finite magnitude exceeds kCollF32Max, which add and the match calls enforce: masked by
 // value, no kernel changed.  Binary: rowsb / rows4; an all-zero FP4 row is at W / 2 from everything, so K11
 // masks by INDEX: its sweep and its vector-ALU kernel take the per-stage real-row table (stage_real).
+// A fourth kind, wide (FM_BANK_F32W, fm_collection_add_wide: coll_add_wide below), masks by INDEX as well and serves the
+// match graph alone (fm_collection_pairs_mutual_ratio); every call that takes a query bank refuses it (coll_refuse_wide).
 constexpr int kCollPadNorm = 1 << 26;
 constexpr float kCollPadF32 = 1.0e18f;           // 128 * (1e18 + kCollF32Max)^2 = 1.7e38 stays finite in float32
 // Masking by value holds while a padding row is farther from every query row than every real row is.  With all finite
@@ -50,7 +52,9 @@ struct fm_collection {
     fm_ctx* ctx = nullptr;
     fm::Bank stack;                       // kind = the collection's; n = n_pad = used rows, cap_pad = allocated rows
     int dim = 0;                          // 0: no non-empty image yet
-    int src = 0;                          // 1: images came as uint8, 2: as float32, 3: as binary rows (0: none yet)
+    int src = 0;                          // 1: images came as uint8, 2: as float32, 3: as binary rows, 4: as wide rows (0: none yet)
+    float wvmax = 0.f;                    // wide: the largest finite magnitude added so far
+    bool wscale = false;                  // wide: stack.kscale was chosen (from the first magnitude above 0)
     int64_t used = 0, total = 0;          // physical rows in use (a multiple of 128), real rows
     std::vector<int64_t> rows, phys;      // per image
     std::vector<int32_t> usq;             // per image: largest |row|^2 (sqrt_tie_possible)
@@ -305,6 +309,9 @@ static int coll_planes(fm::Bank& b, CollPlane* pl)
     if (b.kind == FM_BANK_F32) {
         pl[n++] = {(void**)&b.rowsf, (size_t)kDim * 4}; pl[n++] = {(void**)&b.rowsh, (size_t)kDim * 2};
         pl[n++] = {(void**)&b.normf, 4}; pl[n++] = {(void**)&b.auxf, 4};
+    } else if (b.kind == FM_BANK_F32W) {
+        pl[n++] = {(void**)&b.wrows, (size_t)kWideDim * 4}; pl[n++] = {(void**)&b.wrowsh, (size_t)kWideDim * 2};
+        pl[n++] = {(void**)&b.normf, 4}; pl[n++] = {(void**)&b.auxf, 4};
     } else if (b.kind == FM_BANK_BIN) {
         pl[n++] = {(void**)&b.rowsb, (size_t)b.ksteps * 16}; pl[n++] = {(void**)&b.rows4, (size_t)b.ksteps * 64};
     } else {
@@ -317,7 +324,7 @@ static int coll_planes(fm::Bank& b, CollPlane* pl)
 static void coll_free_planes(fm::Bank& b)
 {
     void** all[] = {(void**)&b.rows8, (void**)&b.norm, (void**)&b.aux, (void**)&b.rowsf, (void**)&b.rowsh, (void**)&b.normf,
-                    (void**)&b.auxf, (void**)&b.rowsb, (void**)&b.rows4};
+                    (void**)&b.auxf, (void**)&b.rowsb, (void**)&b.rows4, (void**)&b.wrows, (void**)&b.wrowsh};
     for (void** p : all) { if (*p) (void)hipFree(*p); *p = nullptr; }
     b.cap_pad = 0;
 }
@@ -333,6 +340,7 @@ static void coll_free(fm_collection* c)
 static void coll_reset(fm_collection* c)
 {
     c->dim = 0; c->src = 0; c->used = 0; c->total = 0;
+    c->wvmax = 0.f; c->wscale = false;
     c->rows.clear(); c->phys.clear(); c->usq.clear();
     c->stack.n = 0; c->stack.n_pad = 0; c->stack.usq_max = 0; c->stack.dim = 0;
     c->stack.nm_max = 0.f; c->stack.kscale = 0; c->stack.filt_ok = false;
@@ -373,7 +381,7 @@ static int coll_reserve(fm_ctx* ctx, fm_collection* c, int64_t need)
     if (cap > (int64_t)INT32_MAX - 2 * kStageRows) return fail(ctx, FM_EUNSUPPORTED, "fm_collection_add: the collection would exceed 2^31 rows");
     fm::Bank nb = c->stack;
     nb.rows8 = nullptr; nb.norm = nullptr; nb.aux = nullptr; nb.rowsf = nullptr; nb.rowsh = nullptr; nb.normf = nullptr; nb.auxf = nullptr;
-    nb.rowsb = nullptr; nb.rows4 = nullptr;
+    nb.rowsb = nullptr; nb.rows4 = nullptr; nb.wrows = nullptr; nb.wrowsh = nullptr;
     int rc = coll_alloc(ctx, &nb, cap, &c->stack, c->used);
     if (rc != FM_OK) return rc;
     coll_free_planes(c->stack);
@@ -501,9 +509,11 @@ static int coll_add(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, 
     if (n < 0 || dim < 1 || (n > 0 && !rows)) return fail(ctx, FM_EINVAL, std::string(who) + ": bad rows / n / width");
     if (src == 3 ? dim > 64 : dim > kDim)
         return fail(ctx, FM_EUNSUPPORTED, std::string(who) + (src == 3 ? ": binary rows of more than 64 bytes are not supported" :
-                                                                    src == 2 && dim <= kWideDim ? ": dim > 128 is not supported (wide float rows, FM_BANK_F32W, are served for bank pairs only)" :
+                                                                    src == 2 && dim <= kWideDim ? ": dim > 128 is not supported (wide float rows, FM_BANK_F32W, enter a collection through fm_collection_add_wide)" :
                                                                     ": dim > 128 is not supported"));
     if (c->rows.size() >= (size_t)INT32_MAX) return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": too many images");
+    if (c->src == 4)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the collection holds wide float images (fm_collection_add_wide); wide and other images do not mix in one collection");
     if (n > 0 && c->dim != 0) {
         if (dim != c->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": the image's width differs from the collection's");
         if (src != c->src) return fail(ctx, FM_EINVAL, std::string(who) + ": uint8, float32 and binary images do not mix in one collection (cv2 raises on the dtype)");
@@ -619,7 +629,7 @@ extern "C" int fm_collection_add_dev(fm_ctx* ctx, fm_collection* c, const void* 
     if (n < 0 || dim < 1) return fail(ctx, FM_EINVAL, "fm_collection_add_dev: bad n / width");
     if (dtype == FM_DT_BIN ? dim > 64 : dim > kDim)
         return fail(ctx, FM_EUNSUPPORTED, std::string(who) + (dtype == FM_DT_BIN ? ": binary rows of more than 64 bytes are not supported" :
-                                                                    dtype != FM_DT_U8 && dim <= kWideDim ? ": dim > 128 is not supported (wide float rows, FM_BANK_F32W, are served for bank pairs only)" :
+                                                                    dtype != FM_DT_U8 && dim <= kWideDim ? ": dim > 128 is not supported (wide float rows, FM_BANK_F32W, enter a collection through fm_collection_add_wide)" :
                                                                     ": dim > 128 is not supported"));
     const int64_t elt = dtype == FM_DT_F32 ? 4 : (dtype == FM_DT_F16 || dtype == FM_DT_BF16) ? 2 : 1;
     const int64_t pitch = row_pitch_bytes == 0 ? dim * elt : row_pitch_bytes;
@@ -637,6 +647,139 @@ extern "C" int fm_collection_add_dev(fm_ctx* ctx, fm_collection* c, const void* 
     if ((rc = wait_for_stream(ctx, producer_stream)) != FM_OK) return rc;
     const DevSrc dsrc{(const uint8_t*)d_rows, dtype, pitch};
     return coll_add(ctx, c, d_rows, n, dim, src, img_idx, who, &dsrc);
+}
+
+// ---- wide collections: images of 129 .. 256 float values per row (K14, wide_f32.hip) ------------------------------------------
+// The stack is a FM_BANK_F32W bank (wrows / wrowsh / normf / auxf); an image starts on a 128-row stage, so coll_view(c, i) is a
+// wide bank view: wide_copy_kernel writes its rows (zero padded to 256 values and to the stage's end) and wide_planes_kernel
+// its scaled planes, the two kernels of fm_bank_create_f32 on the same values -- host and device adds build the same bytes.
+// Padding rows are excluded by INDEX in every wide kernel, so any value is accepted: there is no FM_COLLECTION_F32_MAX here.
+// One fp16 scale for the whole stack (both views of a pair share it): K8's rule on the running largest finite magnitude.  An
+// add that lifts the maximum beyond the scale's range rewrites wrowsh / normf / auxf of every image from wrows on the device
+// (nothing is uploaded again); the scale never goes back down.  stack.nm_max is the stack's largest scaled squared norm: the
+// filter's margin takes it for every view (wide_f32.hip, part 4).  A value that is not finite switches the filter off for the
+// collection (stack.filt_ok): the exact kernel alone, same results.
+static int coll_add_wide(fm_ctx* ctx, fm_collection* c, const void* rows, int64_t n, int dim, int32_t* img_idx, const char* who,
+                         const DevSrc* dev = nullptr)
+{
+    int rc = coll_check(ctx, c, who);
+    if (rc != FM_OK) return rc;
+    if (n < 0 || (n > 0 && !rows)) return fail(ctx, FM_EINVAL, std::string(who) + ": bad rows / n");
+    if (dim <= kDim)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": wide rows have 129 .. 256 values; rows of up to 128 go to fm_collection_add_f32 / fm_collection_add_dev");
+    if (dim > kWideDim) return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": dim > 256 is not supported");
+    if (c->rows.size() >= (size_t)INT32_MAX) return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": too many images");
+    if (c->src != 4 && !c->rows.empty())
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the collection holds images of another kind; wide and other images do not mix in one collection");
+    if (c->src == 4 && dim != c->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": the image's width differs from the collection's");
+    if (c->used + pad128(n) > (int64_t)INT32_MAX - 2 * kStageRows) return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": the collection would exceed 2^31 rows");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool first = c->src != 4;
+    if (first && c->stack.kind != FM_BANK_F32W && (rc = coll_set_kind(ctx, c, FM_BANK_F32W, 0, 0)) != FM_OK) return rc;
+    float vmax_run = first ? 0.f : c->wvmax, nm_max = first ? 0.f : c->stack.nm_max;
+    bool scaled = first ? false : c->wscale, filt_ok = first ? true : c->stack.filt_ok;
+    int kscale = first ? 0 : c->stack.kscale;
+    if (n > 0) {
+        const int64_t n_pad = pad128(n), off = c->used;
+        c->stack.dim = dim;
+        if ((rc = coll_reserve(ctx, c, off + n_pad)) != FM_OK) return rc;
+        const size_t src_bytes = dev ? 0 : (size_t)n * dim * 4;
+        const size_t flag_off = (src_bytes + 15) & ~(size_t)15;
+        if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, flag_off + 32)) != FM_OK) return rc;
+        int* d_stat = (int*)((char*)ctx->ws_in + flag_off);
+        fm::Bank v = bank_rows_view(c->stack, off, n);
+        if (src_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_stat, 0, 16, ctx->stream));
+        if (dev) HIP_TRY(ctx, launch_wide_copy(dev->rows, dev->dtype, dev->pitch, n, dim, v, d_stat, ctx->stream));
+        else     HIP_TRY(ctx, launch_wide_copy(ctx->ws_in, FM_DT_F32, (int64_t)dim * 4, n, dim, v, d_stat, ctx->stream));
+        int stat[2] = {0, 0};
+        HIP_TRY(ctx, hipMemcpyAsync(stat, d_stat, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        float vmax = 0.f;
+        memcpy(&vmax, &stat[0], 4);
+        if (stat[1] != 0) filt_ok = false;
+        if (vmax > vmax_run) vmax_run = vmax;
+        // the scale: chosen at the first magnitude above 0 (all-zero rows have the same planes under every scale), lowered --
+        // never raised -- when the running maximum leaves its range
+        bool rescale = false;
+        const int want = coll_kscale(vmax_run);
+        if (!scaled) { if (vmax_run > 0.f) { kscale = want; scaled = true; } }
+        else if (want < kscale) { kscale = want; rescale = true; }
+        v.kscale = kscale;
+        HIP_TRY(ctx, launch_wide_planes(v, d_stat + 2, ctx->stream));
+        if (rescale) {
+            for (size_t i = 0; i < c->rows.size(); ++i) {
+                if (c->rows[i] == 0) continue;
+                fm::Bank w = bank_rows_view(c->stack, c->phys[i], c->rows[i]);
+                w.kscale = kscale;
+                HIP_TRY(ctx, launch_wide_planes(w, d_stat + 2, ctx->stream));
+            }
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(stat, d_stat + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        float nmx = 0.f;
+        memcpy(&nmx, &stat[0], 4);
+        nm_max = rescale ? nmx : std::max(nm_max, nmx);
+        c->phys.push_back(off);
+        c->used += n_pad;
+        c->total += n;
+    } else {
+        c->phys.push_back(c->used);
+    }
+    c->usq.push_back(0);
+    c->rows.push_back(n);
+    c->src = 4;
+    c->dim = dim;
+    c->wvmax = vmax_run; c->wscale = scaled;
+    c->stack.kscale = kscale; c->stack.nm_max = nm_max; c->stack.filt_ok = filt_ok; c->stack.vfin_max = vmax_run;
+    c->stack.dim = dim;
+    c->stack.n = c->stack.n_pad = c->used;
+    c->dirty = true;
+    c->gen = coll_next_gen();
+    if (img_idx) *img_idx = (int32_t)(c->rows.size() - 1);
+    return FM_OK;
+}
+
+extern "C" int fm_collection_add_wide(fm_ctx* ctx, fm_collection* c, const float* rows, int64_t n, int dim, int32_t* img_idx)
+{
+    return coll_add_wide(ctx, c, rows, n, dim, img_idx, "fm_collection_add_wide");
+}
+
+// fm_collection_add_dev's source rules, then coll_add_wide on the caller's rows: one pass over the source (the typed copy).
+extern "C" int fm_collection_add_wide_dev(fm_ctx* ctx, fm_collection* c, const void* d_rows, int dtype, int64_t n, int dim,
+                                          int64_t row_pitch_bytes, void* producer_stream, int32_t* img_idx)
+{
+    const char* who = "fm_collection_add_wide_dev";
+    int rc = coll_check(ctx, c, who);
+    if (rc != FM_OK) return rc;
+    if (dtype != FM_DT_F32 && dtype != FM_DT_F16 && dtype != FM_DT_BF16)
+        return fail(ctx, FM_EINVAL, "fm_collection_add_wide_dev: dtype " + std::to_string(dtype) + " is not FM_DT_F32, FM_DT_F16 or FM_DT_BF16");
+    if (n < 0) return fail(ctx, FM_EINVAL, "fm_collection_add_wide_dev: bad n");
+    if (dim <= kDim || dim > kWideDim || n == 0) return coll_add_wide(ctx, c, nullptr, n > 0 ? 0 : n, dim, img_idx, who);   // (d_rows is not looked at)
+    const int64_t elt = dtype == FM_DT_F32 ? 4 : 2;
+    const int64_t pitch = row_pitch_bytes == 0 ? dim * elt : row_pitch_bytes;
+    if (pitch < dim * elt)
+        return fail(ctx, FM_EINVAL, "fm_collection_add_wide_dev: row_pitch_bytes " + std::to_string(row_pitch_bytes) + " is below the row size " +
+                                    std::to_string(dim * elt));
+    if (pitch % elt != 0) return fail(ctx, FM_EINVAL, "fm_collection_add_wide_dev: row_pitch_bytes is not a multiple of the element size");
+    if (!d_rows) return fail(ctx, FM_EINVAL, "fm_collection_add_wide_dev: d_rows is NULL");
+    if ((uintptr_t)d_rows % (uintptr_t)elt != 0) return fail(ctx, FM_EINVAL, "fm_collection_add_wide_dev: d_rows is not aligned to the element size");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_ptr(ctx, d_rows, who, "d_rows")) != FM_OK) return rc;
+    // the rows are complete once the work producer_stream has been given so far is: no host wait for it
+    if ((rc = wait_for_stream(ctx, producer_stream)) != FM_OK) return rc;
+    const DevSrc dsrc{(const uint8_t*)d_rows, dtype, pitch};
+    return coll_add_wide(ctx, c, d_rows, n, dim, img_idx, who, &dsrc);
+}
+
+static bool coll_is_wide(const fm_collection* c) { return c->src == 4; }
+
+// the calls that are not built for a wide collection (include/fastmatch_hip.h, K14)
+static int coll_refuse_wide(fm_ctx* ctx, const fm_collection* c, const char* who)
+{
+    if (!coll_is_wide(c)) return FM_OK;
+    return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": a wide collection (fm_collection_add_wide, FM_BANK_F32W) is served by "
+                                      "fm_collection_pairs_mutual_ratio(_dev) only");
 }
 
 extern "C" int fm_collection_train(fm_ctx* ctx, fm_collection* c)
@@ -716,6 +859,7 @@ static int coll_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, con
     int rc = coll_check(ctx, c, who);
     if (rc != FM_OK) return rc;
     if (!q) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank is NULL");
+    if ((rc = coll_refuse_wide(ctx, c, who)) != FM_OK) return rc;
     if ((rc = refuse_wide(ctx, q, who)) != FM_OK) return rc;
     if (c->dim != 0 && q->kind != c->stack.kind && !(empty_any_kind && q->n == 0))
         return fail(ctx, FM_EINVAL, std::string(who) + ": the query bank is not of the collection's kind (fm_collection_info)");
@@ -937,6 +1081,7 @@ extern "C" int fm_mask_create_coll(fm_ctx* ctx, int64_t nq, fm_collection* c, fm
     if (rc != FM_OK) return rc;
     if (!mask) return fail(ctx, FM_EINVAL, "fm_mask_create_coll: mask out pointer is NULL");
     *mask = nullptr;
+    if ((rc = coll_refuse_wide(ctx, c, "fm_mask_create_coll")) != FM_OK) return rc;
     if (nq < 0) return fail(ctx, FM_EINVAL, "fm_mask_create_coll: bad nq");
     if (nq > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, "fm_mask_create_coll: more than 2^31 - 1 query rows");
     if ((rc = mask_alloc(ctx, nq, c->rows, c->phys, c->used, "fm_mask_create_coll", mask)) != FM_OK) return rc;
@@ -1947,6 +2092,35 @@ void coll_pairs_merge_kernel(const PairsMergeSlot* __restrict__ slots, const int
     }
 }
 
+// The same for a wide chunk (wide_f32.hip, part 4): keys (float32 distance bits << 32 | row inside the reduced image), one
+// split, no tie list -- the key order IS the (distance, row) order.
+__global__ __launch_bounds__(256)
+void coll_pairs_merge_f32_kernel(const PairsMergeSlot* __restrict__ slots, const int* __restrict__ blk0, int n,
+                                 int32_t* __restrict__ idx, float* __restrict__ dist)
+{
+    const int s = table_slot_of(blk0, n, (int)blockIdx.x);
+    const PairsMergeSlot sl = slots[s];
+    const int64_t i = (int64_t)((int)blockIdx.x - blk0[s]) * 256 + threadIdx.x;
+    if (i >= sl.nrows) return;
+    unsigned long long b0 = ~0ull, b1 = ~0ull;
+    for (int sp = 0; sp < sl.nsplit; ++sp) {
+        const unsigned long long* p = sl.partial + ((size_t)sp * sl.ncols_alloc + i) * 2;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const unsigned long long v = p[k];
+            if (v < b0) { b1 = b0; b0 = v; }
+            else if (v < b1) { b1 = v; }
+        }
+    }
+    const int64_t o = 2 * (sl.out + i);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const unsigned long long b = k ? b1 : b0;
+        idx[o + k] = (b == ~0ull) ? -1 : (int32_t)(unsigned)b;
+        dist[o + k] = (b == ~0ull) ? INFINITY : __uint_as_float((unsigned)(b >> 32));
+    }
+}
+
 // The join of a chunk's pairs: lowe_each_kernel's forward test and mutual_join_kernel's two rules, word for word, with the
 // reverse list of the first neighbour looked up in place.  Block b: pair table_slot_of(pblk0, n, b), rows of a from
 // (b - pblk0[pair]) * 256.
@@ -2069,6 +2243,10 @@ struct PairsChunk {
     int64_t jblocks = 0, entries = 0, lists = 0;      // blocks and per-row entries of the join, list entries
     size_t part = 0, bound = 0, fix = 0;   // bytes of the slots' partials, shared bounds and tie lists (integer route)
     size_t o_rr = 0, o_ms = 0, o_mb = 0, o_js = 0, o_jb = 0;     // offsets in the table image
+    // wide collections: the chunk's output-row space (every slot pad128 of its rows), 2 sum rows(a) rows(b), the route, the
+    // record list's size, the filter's grid, and the slot table | first workgroups | first rows in the table image
+    int64_t wrows = 0; double work = 0; bool filt = false; unsigned cap = 0; int fwg = 0;
+    size_t o_ws = 0, o_ww = 0, o_wr = 0;
 };
 
 static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs, int64_t n_pairs, const CollPairsArgs& a)
@@ -2116,7 +2294,13 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
             pairs = all.data();
         }
     } catch (const std::bad_alloc&) { return fail(ctx, FM_ENOMEM, who + ": out of host memory"); }
-    const bool i8 = c->stack.kind == FM_BANK_I8;
+    const bool i8 = c->stack.kind == FM_BANK_I8 && !coll_is_wide(c);
+    // Wide collections (wide_f32.hip, part 4): a chunk's slots lie side by side in one output-row space, swept by ONE filter
+    // launch + ONE rescoring + ONE guarded exact launch (or the exact launch alone) and merged by one launch, whatever the
+    // number of pairs.  ws_partial: partial [rows][2] | count | bounds [rows] | records | their scores, of one chunk.
+    const bool wide = coll_is_wide(c);
+    const bool wide_filter_on = wide && ctx->tune.f32_filter != 0 && ctx->d_counters && c->stack.filt_ok && c->stack.wrowsh;
+    size_t max_cap = 0;
     auto live = [&](int64_t p) { return c->rows[(size_t)pairs[2 * p]] > 0 && c->rows[(size_t)pairs[2 * p + 1]] > 0; };
     // Plans of the integer route: the batched shape, every slot under the plan of its own sizes.  Splits exist to fill the
     // chip from ONE pair; a call whose slots fill it without them takes one split per slot (no shared bounds, the smallest
@@ -2157,6 +2341,19 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
                 ch.o_ms = carve(tab_bytes, (size_t)ch.nslots * sizeof(PairsMergeSlot));
                 ch.o_mb = carve(tab_bytes, ((size_t)ch.nslots + 1) * 4);
             }
+            if (wide && ch.nslots > 0) {
+                ch.o_ws = carve(tab_bytes, (size_t)ch.nslots * sizeof(WideSlot));
+                ch.o_ww = carve(tab_bytes, ((size_t)ch.nslots + 1) * 4);
+                ch.o_wr = carve(tab_bytes, ((size_t)ch.nslots + 1) * 4);
+                ch.o_ms = carve(tab_bytes, (size_t)ch.nslots * sizeof(PairsMergeSlot));
+                ch.o_mb = carve(tab_bytes, ((size_t)ch.nslots + 1) * 4);
+                // wide_route's rule on the chunk's work; the list: 256 records per output row, plan_wide_filter's figure
+                ch.filt = wide_filter_on && (ctx->tune.f32_filter >= 2 || ch.work >= 4.0e6);
+                if (ch.filt) {
+                    ch.cap = (unsigned)std::min<int64_t>(std::max<int64_t>(256 * ch.lists, 1 << 20), (int64_t)1 << 28);
+                    max_cap = std::max<size_t>(max_cap, ch.cap);
+                }
+            }
             ch.o_js = carve(tab_bytes, (size_t)np * sizeof(PairsJoinSlot));
             ch.o_jb = carve(tab_bytes, ((size_t)np + 1) * 4);
             max_part = std::max(max_part, ch.part); max_bound = std::max(max_bound, ch.bound); max_fix = std::max(max_fix, ch.fix);
@@ -2179,18 +2376,27 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
                     wg = (int64_t)rowreduce_grid(f.pl) + rowreduce_grid(r.pl);
                     mb = (ra + 255) / 256 + (rb + 255) / 256;
                 }
+                if (wide) {
+                    const int64_t pr = pad128(ra) + pad128(rb);
+                    part = (size_t)pr * 16; bound = (size_t)pr * 4; fix = wide_filter_on ? (size_t)(ra + rb) * 256 * 12 : 0;
+                    wg = pr / kStageRows;
+                    mb = (ra + 255) / 256 + (rb + 255) / 256;
+                }
                 jb = (ra + 255) / 256;
                 need = part + bound + fix + (size_t)(ra + rb) * 16 + (size_t)ra * 17 + (size_t)jb * 12;
             }
             // (the grids are int32, the tables count slots in int32)
             const bool full = ch.p0 < p && (used + need > budget || ch.wg + wg > 0x7fffffff || ch.jblocks + jb > 0x7fffffff ||
-                                            ch.mblocks + mb > 0x7fffffff || ch.nslots + 2 > (1 << 24));
+                                            ch.mblocks + mb > 0x7fffffff || ch.nslots + 2 > (1 << 24) ||
+                                            (wide && ch.wrows + wg * kStageRows > 0x3fffffff));
             if (full) close(p);
             if (wg > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, who + ": one pair needs more than 2^31 - 1 workgroups");
+            if (wide && wg * kStageRows > 0x3fffffff) return fail(ctx, FM_EUNSUPPORTED, who + ": one pair of a wide collection has more than 2^30 rows");
             used += need;
             if (ra > 0 && rb > 0) {
                 ch.nslots += 2; ch.wg += wg; ch.mblocks += mb; ch.jblocks += jb; ch.entries += ra; ch.lists += ra + rb;
-                ch.part += part; ch.bound += bound; ch.fix += fix;
+                ch.part += part; ch.bound += bound; ch.fix += wide ? 0 : fix;
+                if (wide) { ch.wrows += wg * kStageRows; ch.work += 2.0 * (double)ra * (double)rb; }
                 sum_entries += ra;
             }
         }
@@ -2207,6 +2413,9 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
     const size_t o_cq = carve(off, (size_t)ccap * 4), o_ct = carve(off, (size_t)ccap * 4), o_cd = carve(off, (size_t)ccap * 4), o_cr = carve(off, (size_t)ccap * 8);
     if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
     if (i8 && max_part > 0 && (rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, max_part + max_bound + max_fix + 64)) != FM_OK) return rc;
+    max_part = align256(max_part); max_bound = align256(max_bound);
+    const size_t w_cnt = max_part, w_bound = w_cnt + 256, w_list = w_bound + max_bound, w_score = w_list + align256(max_cap * 8);
+    if (wide && max_part > 0 && (rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, w_score + align256(max_cap * 4) + 64)) != FM_OK) return rc;
     if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, tab_bytes + 64)) != FM_OK) return rc;
     if (ctx->tab_in_flight) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_tab)); ctx->tab_in_flight = false; }
     if (!ctx->ev_tab) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming));
@@ -2225,8 +2434,14 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
     struct FixJob { size_t chunk; unsigned* fix; int ia, ib; int64_t out; };
     std::vector<FixJob> fixes;
     for (size_t k = 0; k < chunks.size(); ++k) {
-        const PairsChunk& ch = chunks[k];
+        PairsChunk& ch = chunks[k];
         const int np = (int)(ch.p1 - ch.p0);
+        WideSlot* wsl = (WideSlot*)(h + ch.o_ws);
+        int* ww0 = (int*)(h + ch.o_ww);
+        int* wr0 = (int*)(h + ch.o_wr);
+        int wrow = 0;
+        // a chunk whose slots fill the chip without splits takes one split per slot
+        const bool one_split = ch.wg >= 512 && ctx->tune.f32_nsplit == 0;
         PairsMergeSlot* ms = (PairsMergeSlot*)(h + ch.o_ms);
         int* mb0 = (int*)(h + ch.o_mb);
         PairsJoinSlot* js = (PairsJoinSlot*)(h + ch.o_js);
@@ -2261,8 +2476,28 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
                 wg += g; mb += (int)((vo.n + 255) / 256);
                 ++slot;
             }
+            for (int dir = 0; wide && dir < 2; ++dir) {
+                const int io = dir ? ib : ia, ir = dir ? ia : ib;
+                const int64_t no = c->rows[(size_t)io], nr = c->rows[(size_t)ir];
+                WideSlot& w = wsl[slot];
+                w.col0 = (int)c->phys[(size_t)io]; w.ncols = (int)no;
+                w.red0 = (int)c->phys[(size_t)ir]; w.nred = (int)nr;
+                const WideFilterPlan fp = plan_wide_filter(pad128(no), no, pad128(nr), ctx->tune);
+                w.ntiles = fp.ntiles;
+                w.nsplit = one_split ? 1 : fp.nsplit;
+                w.tiles_per_split = one_split ? fp.ntiles : fp.tiles_per_split;
+                w.row0 = wrow;
+                ww0[slot] = wg; wr0[slot] = wrow;
+                PairsMergeSlot& m = ms[slot];
+                m.partial = (unsigned long long*)wp + (size_t)wrow * 2; m.fix = nullptr; m.out = dir ? s.rev : s.fwd;
+                m.nsplit = 1; m.ncols_alloc = (int)pad128(no); m.nrows = (int)no; m.pad_ = 0;
+                mb0[slot] = mb;
+                wg += fp.nchunks * w.nsplit; wrow += (int)pad128(no); mb += (int)((no + 255) / 256);
+                ++slot;
+            }
             list += ra + rb; entry += ra; jb += (int)((ra + 255) / 256);
         }
+        if (wide && ch.nslots > 0) { ww0[ch.nslots] = wg; wr0[ch.nslots] = wrow; mb0[ch.nslots] = mb; ch.fwg = wg; }
         jb0[np] = jb;
         if (i8 && ch.nslots > 0) { rowreduce_table_end(h + ch.o_rr, ch.nslots, wg); mb0[ch.nslots] = mb; }
     }
@@ -2274,7 +2509,7 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
         if (!live(p)) continue;
         const int64_t ra = c->rows[(size_t)pairs[2 * p]], rb = c->rows[(size_t)pairs[2 * p + 1]];
         ctx->pending_pairs += 2 * ra * rb;
-        ctx->pending_bytes += 2 * (ra + rb) * (i8 ? 128 : c->stack.kind == FM_BANK_BIN ? c->stack.dim : 512);
+        ctx->pending_bytes += 2 * (ra + rb) * (i8 ? 128 : wide ? 1024 : c->stack.kind == FM_BANK_BIN ? c->stack.dim : 512);
     }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, h, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_tab, ctx->stream));
@@ -2302,6 +2537,25 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
                                    (int)vr.n, CollTab{nullptr, nullptr, nullptr}, fj.out, (int32_t*)nullptr, l_idx, l_dist);
                 HIP_TRY(ctx, hipGetLastError());
             }
+        } else if (ch.nslots > 0 && wide) {
+            unsigned long long* part = (unsigned long long*)wp;
+            const WideTableLaunch tl{(const WideSlot*)(d + ch.o_ws), (const int*)(d + ch.o_ww), (const int*)(d + ch.o_wr), ch.nslots, ch.fwg, ch.wrows};
+            if (!timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+            timed = true;
+            if (ch.filt) {
+                HIP_TRY(ctx, hipMemsetAsync(part, 0xff, (size_t)ch.wrows * 16, ctx->stream));
+                HIP_TRY(ctx, hipMemsetAsync(wp + w_cnt, 0, 256 + (size_t)ch.wrows * 4, ctx->stream));     // (the count and the bounds are neighbours)
+                HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, 8, ctx->stream));
+                HIP_TRY(ctx, launch_wide_filter_table(c->stack, tl, ch.cap, (uint2*)(wp + w_list), (float*)(wp + w_score), (unsigned*)(wp + w_bound),
+                                                      (unsigned long long*)(wp + w_cnt), ctx->d_counters, part, ctx->stream));
+                HIP_TRY(ctx, launch_wide_exact_table(c->stack, tl, part, ctx->d_counters, ctx->stream));
+                ctx->filter_launches += 1;
+            } else {
+                HIP_TRY(ctx, launch_wide_exact_table(c->stack, tl, part, nullptr, ctx->stream));
+            }
+            hipLaunchKernelGGL(coll_pairs_merge_f32_kernel, dim3((unsigned)ch.mblocks), dim3(256), 0, ctx->stream,
+                               (const PairsMergeSlot*)(d + ch.o_ms), (const int*)(d + ch.o_mb), ch.nslots, l_idx, l_dist);
+            HIP_TRY(ctx, hipGetLastError());
         } else if (ch.nslots > 0) {
             // float32 route, binary: the pair's two sweeps by the existing route, each followed by its one-slot merge
             const PairsJoinSlot* js = (const PairsJoinSlot*)(h + ch.o_js);

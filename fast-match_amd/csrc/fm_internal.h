@@ -318,6 +318,29 @@ bool wide_filter_usable(const Bank& cols, const Bank& red);
 WideFilterPlan plan_wide_filter(int64_t ncols_pad, int64_t ncols, int64_t nred_pad, const Tuning& tn);
 hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const WideFilterPlan& plan, uint2* list, float* lscore,
                               unsigned* gbound, unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream);
+// Table forms (top-2) for a chunk of image pairs of one wide stack (fm_collection_pairs_mutual_ratio): a slot is one direction
+// of one pair, both operands views of `stack` that start on a 128-row stage.  The slots lie side by side in the chunk's
+// output-row space -- slot s owns [row0, row0 + pad128(ncols)) -- which indexes gbound, partial [rows][2] and the records.
+struct WideSlot {
+    int col0, ncols;                        // output rows: first physical row of the stack, real rows (>= 1)
+    int red0, nred;                         // reduced rows: the same
+    int ntiles, tiles_per_split, nsplit;    // the filter's shape for this slot (plan_wide_filter's fields)
+    int row0;                               // the slot's first row in the chunk's output-row space (a multiple of 128)
+};
+struct WideTableLaunch {
+    const WideSlot* d_slots;                // [n]
+    const int* d_wg0;                       // [n + 1] first workgroup of each slot in the filter's grid (nchunks * nsplit each), then the total
+    const int* d_rowp;                      // [n + 1] row0 of each slot, then the chunk's rows
+    int n, fwg;                             // slots, the filter's grid
+    int64_t rows;                           // the chunk's rows (a multiple of 128)
+};
+// the filter and the rescoring into `partial` (preset to ~0, *cnt, flag[0] and gbound[0 .. rows) to 0); flag[0] = 1 afterwards:
+// the chunk's list (cap records, a multiple of 64) overflowed and launch_wide_exact_table must redo the chunk
+hipError_t launch_wide_filter_table(const Bank& stack, const WideTableLaunch& tl, unsigned cap, uint2* list, float* lscore, unsigned* gbound,
+                                    unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream);
+// the exact kernel over the same table, one split per slot, under K5's run_flag protocol; writes every row of `partial`
+hipError_t launch_wide_exact_table(const Bank& stack, const WideTableLaunch& tl, unsigned long long* partial, const int* run_flag,
+                                   hipStream_t stream);
 
 // ---- K13: k-NN under a bit mask (masked.hip) ------------------------------------------------------------------------------
 // Integer route, k = 1 or 2, on the matrix cores: the masked top-k of every row of q over the rows of t (t may be a

@@ -53,7 +53,13 @@
 // K8's constant 1.1 enlarged to 1.25 for the terms that grow with n.
 // Banks of different scales: the score is rescaled by 2^(kt - kq) (exact); pairs whose exponents differ by more than 8
 // take the exact kernel.
-#include "fm_internal.h"
+// A view of a wide collection's stack (part 4) uses the STACK's largest scaled squared norm for max |t'|^2 and the stack's one
+// scale: the derivation above holds for such a view exactly as for a bank, its "largest value >= 2^13" step included,
+// because the stack's scale follows the stack's largest finite magnitude and is never lowered.
+//
+// Part 4, the table forms of the three kernels: the bodies of parts 2 and 3 (wide_exact_body, wide_filter_body) over a table
+// of slots in device memory, one launch per chunk of image pairs (fm_collection_pairs_mutual_ratio).
+#include "tile_ops.h"
 #include <algorithm>
 
 namespace fm {
@@ -188,21 +194,13 @@ __device__ __forceinline__ void wide_load_kmajor(const float* __restrict__ rows,
     }
 }
 
+// The body of the exact kernels: 64 output rows (`chunk`) of p's output bank against split `split` of its reduced rows.  The
+// bank-pair kernel and the table kernel (part 4) differ only in where p, chunk and split come from.
 template <int KTOP>
-__global__ __launch_bounds__(256)
-void wide_exact_kernel(WideExactParams p)
+__device__ __forceinline__ void wide_exact_body(const WideExactParams& p, int chunk, int split, float* __restrict__ colimg, float* __restrict__ redimg)
 {
-    __shared__ __attribute__((aligned(16))) float colimg[kWideDim * kWLd];
-    __shared__ __attribute__((aligned(16))) float redimg[kWHalf * kWLd];
-
-    if (p.run_flag) {
-        if (*p.run_flag == 0) return;                 // the filter's result stands
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd((int*)p.run_flag + 2, 1);
-    }
     const int tid = threadIdx.x;
     const int tn = tid & 15, tm = tid >> 4;
-    const int split = blockIdx.x % p.nsplit;
-    const int chunk = blockIdx.x / p.nsplit;
     const int c0 = chunk * kWTile;
 
     if (c0 < p.ncols_pad) wide_load_kmajor<64>(p.col_rows, c0, p.ncols_pad, 0, colimg, tid);
@@ -314,6 +312,20 @@ void wide_exact_kernel(WideExactParams p)
     }
 }
 
+template <int KTOP>
+__global__ __launch_bounds__(256)
+void wide_exact_kernel(WideExactParams p)
+{
+    __shared__ __attribute__((aligned(16))) float colimg[kWideDim * kWLd];
+    __shared__ __attribute__((aligned(16))) float redimg[kWHalf * kWLd];
+
+    if (p.run_flag) {
+        if (*p.run_flag == 0) return;                 // the filter's result stands
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd((int*)p.run_flag + 2, 1);
+    }
+    wide_exact_body<KTOP>(p, (int)(blockIdx.x / p.nsplit), (int)(blockIdx.x % p.nsplit), colimg, redimg);
+}
+
 hipError_t launch_wide_exact(const Bank& cols, const Bank& red, int ktop, const RowReducePlan& plan, unsigned long long* partial,
                              const int* run_flag, hipStream_t stream)
 {
@@ -405,14 +417,15 @@ __device__ __forceinline__ void wide_push(bool pred, int col, int row, float sco
     used += n;
 }
 
+// The body of the filter kernels: the 128 output rows `blk` of p's output bank against split `split` of its reduced rows.
+// rowbase: where the output bank's row 0 lies in the row space of gbound and of the records (0 for a bank pair; a slot's
+// first row in its chunk for the table kernel, part 4).
 template <int KS, int KTOP>
-__global__ __launch_bounds__(256)
-void wide_filter_kernel(WideFilterParams p)
+__device__ __forceinline__ void wide_filter_body(const WideFilterParams& p, int blk, int split, int rowbase)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 15, lg = lane >> 4;
-    const int split = blockIdx.x % p.nsplit;
-    const int c0 = (blockIdx.x / p.nsplit) * kWFCols + wave * 16 * kWFBlocks;
+    const int c0 = blk * kWFCols + wave * 16 * kWFBlocks;
 
     w_v8h bq[kWFBlocks][KS];
     float marg[kWFBlocks], bnd[kWFBlocks], best[kWFBlocks][KTOP];
@@ -473,7 +486,7 @@ void wide_filter_kernel(WideFilterParams p)
             bnd[b] = fmaxf(bnd[b], __shfl_xor(bnd[b], 16));
             bnd[b] = fmaxf(bnd[b], __shfl_xor(bnd[b], 32));
 #pragma unroll
-            for (int r = 0; r < 4; ++r) wide_push(real[r] && sc[r] >= bnd[b] - marg[b], col, r0 + r, sc[r], p, lbase, lused);
+            for (int r = 0; r < 4; ++r) wide_push(real[r] && sc[r] >= bnd[b] - marg[b], rowbase + col, r0 + r, sc[r], p, lbase, lused);
         }
     }
     wide_pad_chunk(lbase, lused, p);
@@ -481,8 +494,15 @@ void wide_filter_kernel(WideFilterParams p)
     if (lg == 0) {
 #pragma unroll
         for (int b = 0; b < kWFBlocks; ++b)
-            if (bnd[b] > -INFINITY) atomicMax(p.gbound + c0 + 16 * b + lr, wide_fbits(bnd[b]));
+            if (bnd[b] > -INFINITY) atomicMax(p.gbound + rowbase + c0 + 16 * b + lr, wide_fbits(bnd[b]));
     }
+}
+
+template <int KS, int KTOP>
+__global__ __launch_bounds__(256)
+void wide_filter_kernel(WideFilterParams p)
+{
+    wide_filter_body<KS, KTOP>(p, (int)(blockIdx.x / p.nsplit), (int)(blockIdx.x % p.nsplit), 0);
 }
 
 struct WideRescoreParams {
@@ -588,6 +608,160 @@ hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const
     r.gbound = gbound; r.colnorm = cols.normf; r.nscale = p.nscale; r.red_nm_max = red.nm_max;
     if (ktop == 1) hipLaunchKernelGGL((wide_rescore_kernel<1>), dim3(2048), dim3(256), 0, stream, r);
     else           hipLaunchKernelGGL((wide_rescore_kernel<2>), dim3(2048), dim3(256), 0, stream, r);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// part 4: the table forms (fm_collection_pairs_mutual_ratio on a wide collection)
+// ---------------------------------------------------------------------------------------
+// A chunk of image pairs of ONE stack (a wide collection: every image a bank view that starts on a 128-row stage) in one
+// launch per step.  A slot (WideSlot) is one direction of one pair; the slots of a chunk lie side by side in the chunk's
+// output-row space (slot s owns the rows [row0, row0 + pad128(ncols))), which indexes gbound, partial and the records'
+// output rows, so ONE record list, ONE 64-bit count and ONE overflow flag serve the chunk: reservation, padding and the
+// sticky overflow are wide_push's, unchanged.  A record is (chunk row, row INSIDE the reduced image): the key the rescoring
+// inserts carries the row the caller sees.  The grids are flat; a workgroup finds its slot with table_slot_of over a prefix
+// array in device memory (the filter: first workgroups, one entry more than slots; the exact kernel and the rescoring: the
+// first rows, which ascend the same way).
+// Both operands of every slot are views of the one stack, so they share its scale (cscale = nscale = 1) and the margin takes
+// the STACK's largest scaled squared norm for max |t'|^2: an upper bound of the image's, so 2 E <= M holds as derived in the
+// file comment, and the stack's largest scaled value lies in [2^13, 2^14) or above whichever image is swept (the scale only
+// ever follows the running maximum upwards), which is all the fp16-subnormal step asks: the derivation holds for a view
+// exactly as for a bank.
+struct WideTableParams {
+    const WideSlot* slots; const int* wg0; const int* rowp; int n;        // the chunk's table
+    const float* rows; const uint16_t* rowsh; const float* normf; const float* auxf;   // the stack's planes
+    float nm_max; int dim;
+    uint2* list; float* lscore; unsigned cap; unsigned long long* cnt; unsigned* gbound;
+    unsigned long long* partial;      // [chunk rows][KTOP]
+    int* flag;                        // the rescoring: [0] = 1, the list overflowed
+    const int* run_flag;              // the exact kernel: null, or skip unless *run_flag != 0 (runs counted in run_flag[2])
+};
+
+template <int KS, int KTOP>
+__global__ __launch_bounds__(256)
+void wide_filter_table_kernel(WideTableParams t)
+{
+    const int s = table_slot_of(t.wg0, t.n, (int)blockIdx.x);
+    const WideSlot sl = t.slots[s];
+    const int local = (int)blockIdx.x - t.wg0[s];
+    WideFilterParams p;
+    p.colh = t.rowsh + (size_t)sl.col0 * kWideDim; p.colnorm = t.normf + sl.col0; p.ncols = sl.ncols;
+    p.redh = t.rowsh + (size_t)sl.red0 * kWideDim; p.redaux = t.auxf + sl.red0; p.nred = sl.nred;
+    p.cscale = 1.f; p.nscale = 1.f; p.red_nm_max = t.nm_max;
+    p.ntiles = sl.ntiles; p.tiles_per_split = sl.tiles_per_split; p.nsplit = sl.nsplit;
+    p.list = t.list; p.lscore = t.lscore; p.cap = t.cap; p.cnt = t.cnt; p.gbound = t.gbound;
+    wide_filter_body<KS, KTOP>(p, local / sl.nsplit, local % sl.nsplit, sl.row0);
+}
+
+template <int KTOP>
+__global__ __launch_bounds__(256)
+void wide_rescore_table_kernel(WideTableParams t)
+{
+    const unsigned long long n64 = *t.cnt;
+    const unsigned n = (unsigned)n64;
+    if (n64 > t.cap) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) t.flag[0] = 1;
+        return;
+    }
+    for (unsigned e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
+        const uint2 rec = t.list[e];
+        if (rec.x == kWNoRecord) continue;                      // the padding of a chunk of the list
+        const int s = table_slot_of(t.rowp, t.n, (int)rec.x);
+        const WideSlot sl = t.slots[s];
+        const size_t col = (size_t)sl.col0 + (rec.x - (unsigned)sl.row0), red = (size_t)sl.red0 + rec.y;
+        if (t.lscore[e] < wide_bits_f(t.gbound[rec.x]) - wide_margin(t.normf[col], 1.f, t.nm_max)) continue;
+        const float4* a = (const float4*)(t.rows + col * kWideDim);
+        const float4* b = (const float4*)(t.rows + red * kWideDim);
+        float s2 = 0.f;
+        const int k4n = (t.dim + 3) >> 2;                       // (zero padding past dim: see the file comment)
+        for (int k4 = 0; k4 < k4n; ++k4) {
+            const float4 x = a[k4], y = b[k4];
+            float v = x.x - y.x; s2 = __builtin_fmaf(v, v, s2);
+            v = x.y - y.y; s2 = __builtin_fmaf(v, v, s2);
+            v = x.z - y.z; s2 = __builtin_fmaf(v, v, s2);
+            v = x.w - y.w; s2 = __builtin_fmaf(v, v, s2);
+        }
+        const float d = sqrtf(s2);
+        if (!(d < INFINITY)) continue;                          // K5's rule: an infinite or NaN distance is no candidate
+        const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | rec.y;
+        unsigned long long* out = t.partial + (size_t)rec.x * KTOP;
+        const unsigned long long old = atomicMin(out, key);
+        if constexpr (KTOP == 2) atomicMin(out + 1, old > key ? old : key);
+    }
+}
+
+// Workgroup b: the 64 chunk rows from 64 b on, the whole reduced image of their slot (one split).
+template <int KTOP>
+__global__ __launch_bounds__(256)
+void wide_exact_table_kernel(WideTableParams t)
+{
+    __shared__ __attribute__((aligned(16))) float colimg[kWideDim * kWLd];
+    __shared__ __attribute__((aligned(16))) float redimg[kWHalf * kWLd];
+
+    if (t.run_flag) {
+        if (*t.run_flag == 0) return;                 // the filter's result stands
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd((int*)t.run_flag + 2, 1);
+    }
+    const int row = (int)blockIdx.x * kWTile;
+    const int s = table_slot_of(t.rowp, t.n, row);
+    const WideSlot sl = t.slots[s];
+    WideExactParams p;
+    p.col_rows = t.rows + (size_t)sl.col0 * kWideDim;
+    p.ncols_pad = (sl.ncols + kStageRows - 1) / kStageRows * kStageRows;
+    p.red_rows = t.rows + (size_t)sl.red0 * kWideDim;
+    p.nred = sl.nred;
+    p.nred_pad = (sl.nred + kStageRows - 1) / kStageRows * kStageRows;
+    p.nsteps = p.nred_pad / kWTile;
+    p.nsplit = 1;
+    p.steps_per_split = p.nsteps;
+    p.ncols_alloc = p.ncols_pad;
+    p.kend = (t.dim + 7) & ~7;
+    p.partial = t.partial + (size_t)sl.row0 * KTOP;
+    p.run_flag = nullptr;
+    wide_exact_body<KTOP>(p, (row - sl.row0) / kWTile, 0, colimg, redimg);
+}
+
+static WideTableParams wide_table_params(const Bank& stack, const WideTableLaunch& tl)
+{
+    WideTableParams t{};
+    t.slots = tl.d_slots; t.wg0 = tl.d_wg0; t.rowp = tl.d_rowp; t.n = tl.n;
+    t.rows = stack.wrows; t.rowsh = stack.wrowsh; t.normf = stack.normf; t.auxf = stack.auxf;
+    t.nm_max = stack.nm_max; t.dim = stack.dim;
+    return t;
+}
+
+template <int KS>
+static void wide_filter_table_launch(const WideTableParams& t, int grid, hipStream_t stream)
+{
+    hipLaunchKernelGGL((wide_filter_table_kernel<KS, 2>), dim3(grid), dim3(256), 0, stream, t);
+}
+
+hipError_t launch_wide_filter_table(const Bank& stack, const WideTableLaunch& tl, unsigned cap, uint2* list, float* lscore, unsigned* gbound,
+                                    unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream)
+{
+    WideTableParams t = wide_table_params(stack, tl);
+    t.list = list; t.lscore = lscore; t.cap = cap; t.cnt = cnt; t.gbound = gbound; t.partial = partial; t.flag = flag;
+    const int ks = (stack.dim + 31) / 32;
+    if (ks < 5 || ks > 8 || tl.n < 1 || tl.fwg < 1) return hipErrorInvalidValue;
+    switch (ks) {
+        case 5: wide_filter_table_launch<5>(t, tl.fwg, stream); break;
+        case 6: wide_filter_table_launch<6>(t, tl.fwg, stream); break;
+        case 7: wide_filter_table_launch<7>(t, tl.fwg, stream); break;
+        default: wide_filter_table_launch<8>(t, tl.fwg, stream); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((wide_rescore_table_kernel<2>), dim3(2048), dim3(256), 0, stream, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_wide_exact_table(const Bank& stack, const WideTableLaunch& tl, unsigned long long* partial, const int* run_flag,
+                                   hipStream_t stream)
+{
+    WideTableParams t = wide_table_params(stack, tl);
+    t.partial = partial; t.run_flag = run_flag;
+    if (tl.n < 1 || tl.rows < kWTile) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((wide_exact_table_kernel<2>), dim3((unsigned)(tl.rows / kWTile)), dim3(256), 0, stream, t);
     return hipGetLastError();
 }
 

@@ -22,7 +22,8 @@ Mirrors ``matchutil.py`` of the reference:
 * Wide float descriptors -- float arrays of 129 .. 256 values per row, SuperPoint's 256-D rows for one -- go to the
   library's wide float banks under ``NORM_L2``: ``bf_match`` with k <= 2 and with crossCheck, ``ratio_match_arrays`` and
   ``mutual_ratio_match_arrays`` take them; ``bf_radius_match``, a mask, k >= 3 and ``BFMatcher.add`` raise ``ValueError``
-  before anything is uploaded.
+  before anything is uploaded.  ``BFMatcher.add_wide`` adds wide images to a collection of their own, whose match graph
+  ``matchPairs`` / ``matchPairs_arrays`` computes (``fm_collection_add_wide``).
 * ``options["mask"]``: cv2's ``mask`` argument of ``knnMatch`` -- an ``[nq, nt]`` uint8 / bool array, nonzero = the pair
   (query row, train row) may be matched, or a resident ``_ffi.Mask`` (``Context.mask``).  ``bf_match``,
   ``bf_match_arrays``, ``flann_match`` and ``flann_match_arrays`` honour it when crossCheck is off: every list is the
@@ -350,9 +351,12 @@ class BFMatcher(object):
         self._images = []
         self._coll = None          # (_ffi.Collection, number of images it holds)
         self._uploaded = 0
+        self._wide = False         # the images came through add_wide: matchPairs is what the collection serves
 
     # -- bookkeeping (host only) ---------------------------------------------------------
     def add(self, descriptors):
+        if self._wide:
+            raise ValueError("BFMatcher.add: the collection holds wide float images (add_wide); wide and other images do not mix")
         imgs = []
         for d in descriptors:
             a = np.asarray(d)
@@ -360,16 +364,42 @@ class BFMatcher(object):
                 raise ValueError("BFMatcher.add: every image's descriptors must be a 2-D [n, dim] array")
             if self.normType == NORM_HAMMING and a.dtype != np.uint8:
                 raise ValueError("NORM_HAMMING needs uint8 descriptors (cv2 asserts CV_8U), got %s" % a.dtype)
-            _refuse_wide("BFMatcher.add", "a train collection", a)
+            _refuse_wide("BFMatcher.add", "a train collection (wide float images go in through add_wide)", a)
             for b in self._images + imgs:
                 if a.shape[0] and b.shape[0] and (b.shape[1] != a.shape[1] or (b.dtype == np.uint8) != (a.dtype == np.uint8)):
                     raise ValueError("BFMatcher.add: images of one collection share a width and a dtype (cv2 raises at match time)")
             imgs.append(a)
         self._images.extend(imgs)
 
+    def add_wide(self, descriptors):
+        """``add`` for WIDE float images: every entry a [n, dim] float array with 129 <= dim <= 256 (learned 256-D descriptors;
+        n may be 0), one width per collection, NORM_L2.  A collection takes either ``add`` or ``add_wide`` images; a wide one
+        (``fm_collection_add_wide``) serves ``matchPairs`` / ``matchPairs_arrays``, and every other collection method raises
+        ``ValueError`` before anything is uploaded."""
+        if self.normType != NORM_L2:
+            raise ValueError("BFMatcher.add_wide: wide float images are NORM_L2 descriptors")
+        if self._images and not self._wide:
+            raise ValueError("BFMatcher.add_wide: the collection holds images of another kind; wide and other images do not mix")
+        imgs = []
+        for d in descriptors:
+            a = np.asarray(d)
+            if a.ndim != 2:
+                raise ValueError("BFMatcher.add_wide: every image's descriptors must be a 2-D [n, dim] array")
+            if a.dtype == np.uint8 or not 129 <= a.shape[1] <= 256:
+                raise ValueError("BFMatcher.add_wide: wide images are float arrays of 129 .. 256 values per row, got %s [%d, %d]"
+                                 % (a.dtype, a.shape[0], a.shape[1]))
+            for b in self._images + imgs:
+                if b.shape[1] != a.shape[1]:
+                    raise ValueError("BFMatcher.add_wide: the images of one collection share a width")
+            imgs.append(np.ascontiguousarray(a, dtype=np.float32))
+        self._images.extend(imgs)
+        if imgs:
+            self._wide = True
+
     def clear(self):
         self._images = []
         self._uploaded = 0
+        self._wide = False
         if self._coll is not None:
             self._coll.clear()
 
@@ -383,6 +413,9 @@ class BFMatcher(object):
     def _check_collection(self, who):
         if self.empty():
             raise ValueError("%s: no train descriptors (add() some, or pass a train array)" % who)
+        if self._wide and who not in ("BFMatcher.train", "BFMatcher.matchPairs"):
+            raise ValueError("%s is not built for a wide collection (images of 129 .. 256 values per row, add_wide): "
+                             "matchPairs and matchPairs_arrays are" % who)
 
     def train(self):
         self._check_collection("BFMatcher.train")
@@ -393,6 +426,8 @@ class BFMatcher(object):
         for a in self._images[self._uploaded:]:
             if self.normType == NORM_HAMMING:
                 self._coll.add_binary(a)
+            elif self._wide:
+                self._coll.add_wide(a)
             else:
                 self._coll.add(a)
             self._uploaded += 1

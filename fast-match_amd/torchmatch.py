@@ -46,7 +46,8 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
 Wide float descriptors -- ``[n, 129 .. 256]`` float32 / float16 / bfloat16 tensors, SuperPoint's 256-D rows for one -- make
 wide float banks (``FM_BANK_F32W``): ``bank``, ``knn`` with k <= 2, ``mutual_nn``, ``ratio_match`` and ``mutual_ratio_match``
 take them; ``radius_match``, a masked or k >= 3 ``knn`` and ``Collection.add`` raise ``ValueError`` before the library is
-touched.
+touched.  Their match graph: ``Collection.add_wide(tensor)`` (``fm_collection_add_wide_dev``) makes a WIDE collection, which
+takes no other images and serves ``match_pairs``, ``info``, ``clear`` and ``close``; its other methods raise ``ValueError``.
 
 ``q`` and ``t`` are ``Bank``s or CUDA tensors (a tensor becomes a bank for the call).  The values are those of
 ``Context.knn`` / ``xcheck1`` / ``knn2_ratio`` on banks built from the same numbers on the host, bit for bit.
@@ -337,6 +338,7 @@ class Collection(object):
     def __init__(self, context=None):
         self._context = context
         self._coll = None
+        self._wide = False          # images came through add_wide: match_pairs is what the collection serves
 
     def __enter__(self):
         return self
@@ -344,6 +346,12 @@ class Collection(object):
     def __exit__(self, *exc):
         self.close()
         return False
+
+    def _refuse_wide_collection(self, who):
+        """ValueError before the library is touched: a wide collection (``add_wide``) is served by ``match_pairs`` only."""
+        if self._wide:
+            raise ValueError("Collection.%s is not built for a wide collection (images of 129 .. 256 values per row, add_wide): "
+                             "match_pairs, info and clear are" % who)
 
     def _collection(self, ctx=None):
         if self._coll is None:
@@ -357,8 +365,9 @@ class Collection(object):
         0), read in place behind the current stream's work -- pitched rows with unit column stride included.  Returns the
         image's index.  On return the tensor may be overwritten."""
         import torch
+        self._refuse_wide_collection("add")
         if not binary:
-            _refuse_wide("Collection.add", "a train collection", tensor)
+            _refuse_wide("Collection.add", "a train collection (wide float images go in through add_wide)", tensor)
         tensor, dt = _checked(tensor, binary)
         coll = self._collection(_ctx_for(tensor, self._context))
         n, dim = tensor.shape
@@ -367,8 +376,32 @@ class Collection(object):
         return coll.add_from_device(tensor.data_ptr() if n else 0, dt, n, dim, tensor.stride(0) * tensor.element_size(),
                                     stream=stream)
 
+    def add_wide(self, tensor):
+        """Append one WIDE image ([n, dim] float32 / float16 / bfloat16 with 129 <= dim <= 256; n may be 0), read in place as
+        ``add`` reads its tensor (``fm_collection_add_wide_dev``).  The first ``add_wide`` makes the collection a wide one
+        (``FM_BANK_F32W``): it takes no other images and serves ``match_pairs``, ``info`` and ``clear``.  Returns the image's
+        index."""
+        import torch
+        tensor, dt = _checked(tensor)
+        if dt == _ffi.FM_DT_U8:
+            raise ValueError("Collection.add_wide: wide images are float32, float16 or bfloat16, got %s" % tensor.dtype)
+        if not 129 <= tensor.shape[1] <= 256:
+            raise ValueError("Collection.add_wide: wide images have 129 .. 256 values per row, got %d (rows of up to 128 go "
+                             "to add)" % tensor.shape[1])
+        if not self._wide and self.info()[0] > 0:
+            raise ValueError("Collection.add_wide: the collection holds images of another kind; wide and other images do not mix")
+        coll = self._collection(_ctx_for(tensor, self._context))
+        n, dim = tensor.shape
+        with torch.cuda.device(tensor.device):
+            stream = torch.cuda.current_stream().cuda_stream
+        i = coll.add_wide_from_device(tensor.data_ptr() if n else 0, dt, n, dim, tensor.stride(0) * tensor.element_size(),
+                                      stream=stream)
+        self._wide = True
+        return i
+
     def _query(self, q):
         """(query bank, [banks made for this call]); every refusal before anything reaches the library."""
+        self._refuse_wide_collection("knn / ratio_match / radius_match / *_each")
         _refuse_wide("Collection", "a query against a train collection", q)
         if isinstance(q, _ffi.Bank):
             self._collection(q.ctx)
@@ -381,6 +414,7 @@ class Collection(object):
     def mask(self, nq):
         """An all-forbidding ``_ffi.Mask`` for ``nq`` query rows on the images added so far (``Mask.set_dev`` / ``set_all`` per
         image); a later ``add`` / ``clear`` makes it stale."""
+        self._refuse_wide_collection("mask")
         return self._collection().mask(nq)
 
     def _masks(self, masks, nq, made):
@@ -406,6 +440,7 @@ class Collection(object):
         row inside image ``img``; ties go to the earlier image; -1 / -1 / inf beyond the collection's rows.  1 <= k <= 8.
         ``masks`` (module docstring): only the pairs they permit are candidates (``fm_collection_knn_masked_dev``)."""
         import torch
+        self._refuse_wide_collection("knn")
         k = int(k)
         if k < 1:
             raise ValueError("k must be at least 1")
@@ -430,6 +465,7 @@ class Collection(object):
         """The classic ratio match against the stacked images: ``(qidx, img, tidx int32 [m], dist float32 [m])``, ascending
         query index.  One host wait (the count sizes the outputs)."""
         import torch
+        self._refuse_wide_collection("ratio_match")
         qb, made = self._query(q)
         try:
             stream, dev = _stream_and_device(qb.ctx)
@@ -449,6 +485,7 @@ class Collection(object):
         """Every row of the stacked images with distance < r per query row: ``(offsets int64 [nq + 1], img int32 [n], idx int32
         [n], dist float32 [n])`` CUDA tensors, row i's list at ``offsets[i]:offsets[i + 1]``, ascending (distance, image, row
         inside the image).  ``r`` as in the module's ``radius_match``.  One host wait for the total."""
+        self._refuse_wide_collection("radius_match")
         nq, device = _rows_and_device(q)
         rad, r_all = _radius(r, nq, device if self._context is None else self._context.device)
         qb, made = self._query(q)
@@ -465,6 +502,7 @@ class Collection(object):
         [n_images, cap, 3] = (query, row inside the image, float32 distance bits), counts int64 [n_images] = min(accepted,
         cap))``; ``cap`` defaults to ``q.n``.  ``q`` is a ``Bank`` that carries self distances; enqueued, no host wait."""
         import torch
+        self._refuse_wide_collection("fast_match_each")
         if not isinstance(q, _ffi.Bank):
             raise ValueError("fast_match_each takes a resident Bank that carries self distances (Context.self_dist_batch)")
         coll = self._collection(q.ctx)
@@ -484,6 +522,7 @@ class Collection(object):
         float32 compare; None: every match).  ``q`` is a ``Bank`` or a CUDA tensor as ``add`` takes them (packed bits for a
         binary collection).  Enqueued, no host wait."""
         import torch
+        self._refuse_wide_collection("mutual_nn_each")
         if cap is not None and int(cap) < 0:
             raise ValueError("cap must not be negative")
         max_dist = float("inf") if max_dist is None else float(np.float32(max_dist))
@@ -507,6 +546,7 @@ class Collection(object):
         in query index; ``cap`` defaults to the query's rows.  ``q`` is a ``Bank`` or a CUDA tensor as ``add`` takes them.  One
         host wait inside the library (the candidate count)."""
         import torch
+        self._refuse_wide_collection("mutual_ratio_each")
         if cap is not None and int(cap) < 0:
             raise ValueError("cap must not be negative")
         qb, made = self._query(q)
@@ -556,6 +596,7 @@ class Collection(object):
     def clear(self):
         if self._coll is not None:
             self._coll.clear()
+        self._wide = False
 
     def info(self):
         """(n_images, n_rows_total, dim, kind)"""

@@ -58,7 +58,8 @@ typedef struct fm_bank fm_bank;
  * fm_mask_info, fm_knn_masked, fm_knn_masked_dev, fm_collection_knn_masked, fm_collection_knn_masked_dev, the option
  * "masked_mfma", "mask_pack_words"; still revision 12, additions only -- FM_BANK_F32W: the float creators take
  * 129 <= dim <= 256; still revision 12, additions only -- fm_collection_pairs_mutual_ratio,
- * fm_collection_pairs_mutual_ratio_dev).  A binding compares
+ * fm_collection_pairs_mutual_ratio_dev; still revision 12, additions only -- fm_collection_add_wide,
+ * fm_collection_add_wide_dev).  A binding compares
  * fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.                      */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -146,7 +147,9 @@ int  fm_ctx_destroy(fm_ctx* ctx);
  *                         chunk; 0 = 2^30.
  *                         fm_collection_pairs_mutual_ratio: device bytes for the sweep partials, 2-NN lists and per-row arrays
  *                         of one chunk of consecutive pairs (one table-driven launch per chunk on the integer route; at
- *                         least one pair per chunk); 0 = 2^30
+ *                         least one pair per chunk); 0 = 2^30.  A pair (a, b) of a wide collection counts 20 bytes per row of
+ *                         pad128(rows(a)) + pad128(rows(b)) (partials and bounds), 3088 per row of rows(a) + rows(b) (256 records
+ *                         of 12 bytes, the 2-NN lists) and 17 per row of a: 12.5 MB for two images of 2000 rows
  * Unknown names and out-of-range values return FM_EINVAL.                                          */
 int  fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value);
 int  fm_ctx_get_option(fm_ctx* ctx, const char* name, int64_t* value);
@@ -230,7 +233,40 @@ int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t
  * "wide", before any kernel reads it.  Not built for wide float banks: fm_knn / fm_knn_dev with k >= 3, fm_radius_match(_dev),
  * fm_self_dist(_batch), fm_bank_set_selfdist, fm_match_ratio, fm_match_accepted*, fm_xcheck1_keys*, fm_xcheck1_batched,
  * fm_knn_masked(_dev), fm_bank_refill_u8_async, fm_bank_append_*, fm_expand_create, and every fm_collection_* call -- a wide
- * query bank, and fm_collection_add_f32 / fm_collection_add_dev with more than 128 values per row.                          */
+ * query bank, and fm_collection_add_f32 / fm_collection_add_dev with more than 128 values per row.
+ * Wide COLLECTIONS: wide images enter a collection through entry points of their own, fm_collection_add_wide (host float32
+ * rows) and fm_collection_add_wide_dev (device rows of FM_DT_F32 / FM_DT_F16 / FM_DT_BF16, widened exactly; source, pitch,
+ * alignment, ordering and synchronisation rules are fm_collection_add_dev's).  129 <= dim <= 256; dim <= 128 is FM_EINVAL (such
+ * rows go to fm_collection_add_f32), dim > 256 FM_EUNSUPPORTED, another dtype FM_EINVAL.  The first successful wide add fixes
+ * the collection's kind, FM_BANK_F32W, and its width, even with n = 0 (as the wide bank creators do); a wide add to a
+ * collection on which any other add has succeeded is FM_EINVAL, and so is any other add to a wide collection, and another
+ * width; every refusal leaves the collection unchanged; fm_collection_clear resets kind and width.  Any values are accepted:
+ * there is no FM_COLLECTION_F32_MAX limit, because the padding rows behind an image are excluded by index, never by value; a
+ * value that is not finite switches the fp16 filter off for the collection and changes no result.  Host and device adds of
+ * the same values build the same collection bit for bit (half and bfloat16: of their widened float32 values) and may
+ * alternate.  The stack keeps ONE fp16 scale, K8's rule on the largest finite magnitude added so far: an add that lifts the
+ * maximum out of the scale's range rewrites the fp16 plane and the norm terms of every image on the device from the float32
+ * rows (nothing is uploaded again); the scale is never lowered again.
+ * Served on a wide collection: fm_collection_info (kind FM_BANK_F32W, the real dim), fm_collection_image_rows,
+ * fm_collection_train, fm_collection_clear, fm_collection_destroy, and fm_collection_pairs_mutual_ratio(_dev) with its
+ * contract word for word: pair (a, b) equals, row by row and bit for bit, fm_mutual_ratio on banks made by fm_bank_create_f32
+ * from the same values; the ordered-pair rule, a == b, repeated pairs, pairs == NULL, the packed output, cap, counts only, the
+ * error order and the _dev stream rules are unchanged.  There the slots (one direction of one pair) of a whole chunk of pairs
+ * lie side by side in one output-row space and run through table forms of the wide kernels -- ONE filter launch, ONE
+ * rescoring launch, ONE guarded exact launch and ONE merge launch per chunk, whatever the number of pairs; a workgroup finds
+ * its slot by binary search in a prefix array in device memory -- then the join, scan and compaction of the other kinds.  The
+ * option "f32_filter" chooses per CHUNK as it does per call for a bank pair (0: the exact kernel alone; 1: the filter from
+ * 2 * sum rows(a) rows(b) >= 4e6 over the chunk's pairs; 2: always) and never changes a result; a slot takes one split when
+ * the chunk's slots fill the chip without splits (512 workgroups), else the bank-pair rule for its own size.
+ * fm_f32_filter_stats counts one launch per filtered chunk and one fallback per chunk redone.  The cliff above is PER CHUNK
+ * here: a chunk shares one list of 256 records per output row (at least 2^20 records), so one pair whose candidates overflow
+ * it -- a cluster of duplicates -- sends the whole chunk, not the whole call, to the exact kernel; a smaller "coll_ws_bytes"
+ * bounds what one such pair can cost.
+ * Not built for wide collections: every other fm_collection_* call -- fm_collection_knn(_dev), fm_collection_knn2_ratio(_dev),
+ * fm_collection_knn2_each, fm_collection_votes, fm_collection_knn_masked(_dev), fm_collection_radius_match(_dev),
+ * fm_collection_match_accepted_each(_dev), fm_collection_xcheck1_each(_dev), fm_collection_mutual_ratio_each(_dev) -- and
+ * fm_mask_create_coll: FM_EUNSUPPORTED with a message that says "wide", straight after the NULL-handle checks.  Also not
+ * built: k >= 3, LDS staging of the streamed operand, computing a pair's tiles once for both directions.             */
 int  fm_bank_destroy(fm_ctx* ctx, fm_bank* bank);
 int  fm_bank_info(const fm_bank* bank, int64_t* n, int* dim, int* kind);
 /* Attach per-row self distances (Metric_Cache.*["distances"], float64, cache.pyx:252,273)
@@ -475,6 +511,10 @@ int  fm_collection_clear(fm_ctx* ctx, fm_collection* coll);
 int  fm_collection_add_u8 (fm_ctx* ctx, fm_collection* coll, const uint8_t* rows, int64_t n, int dim, int32_t* img_idx);
 int  fm_collection_add_f32(fm_ctx* ctx, fm_collection* coll, const float* rows, int64_t n, int dim, int32_t* img_idx);
 int  fm_collection_add_bin(fm_ctx* ctx, fm_collection* coll, const uint8_t* rows, int64_t n, int bytes, int32_t* img_idx);
+/* wide images, 129 <= dim <= 256 ("K14: wide float banks" above, Wide COLLECTIONS) */
+int  fm_collection_add_wide(fm_ctx* ctx, fm_collection* coll, const float* rows, int64_t n, int dim, int32_t* img_idx);
+int  fm_collection_add_wide_dev(fm_ctx* ctx, fm_collection* coll, const void* d_rows, int dtype /*FM_DT_F32 | F16 | BF16*/, int64_t n, int dim,
+                                int64_t row_pitch_bytes, void* producer_stream, int32_t* img_idx);
 int  fm_collection_train(fm_ctx* ctx, fm_collection* coll);
 int  fm_collection_info(const fm_collection* coll, int32_t* n_images, int64_t* n_rows_total, int* dim, int* kind);
 int  fm_collection_image_rows(const fm_collection* coll, int64_t* rows /*[n_images]*/);

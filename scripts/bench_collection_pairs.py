@@ -1,14 +1,16 @@
 """Times the match graph of a train collection -- ONE fm_collection_pairs_mutual_ratio call -- against what it replaces: the
 loop of fm_mutual_ratio over banks created beforehand, one call per pair (that path is untouched by the match graph, so it is
 the parent commit's).  100 images x 2 000 rows on the three routes (uint8 in SIFT range, float32 with the fp16 filter,
-32-byte binary); the exhaustive pair set (4 950 pairs) and a window of 5 (every i < j <= i + 5).
+32-byte binary); the exhaustive pair set (4 950 pairs) and a window of 5 (every i < j <= i + 5).  --routes wide: the same for a
+WIDE collection (unit-norm 256-D float rows, fm_collection_add_wide) against the loop of fm_mutual_ratio on wide banks
+(profiles/wide_collection_pairs.jsonl holds a recorded run).
 
 The answers are compared bit for bit first.  Then the two alternate in one process and the medians of fm_stats' total_ms
 (HIP-event time of the calls, the loop's summed over its calls) are reported, with the wall-clock medians beside them (the
 loop's host time between its calls is in the wall clock only).  One JSON line per (route, pair set) on stdout and, with --out,
 appended to that file (profiles/collection_pairs.jsonl holds a recorded run).
 
-    python scripts/bench_collection_pairs.py [--images 100] [--rows 2000] [--reps 11] [--routes u8,f32,bin32] [--out FILE]
+    python scripts/bench_collection_pairs.py [--images 100] [--rows 2000] [--reps 11] [--routes u8,f32,bin32,wide] [--out FILE]
 """
 import argparse
 import json
@@ -33,6 +35,15 @@ def _images(route, n_images, rows, seed):
         for im in images:
             src = pool[rng.choice(pool.shape[0], shared, replace=False)]
             im[:shared] = np.clip(src.astype(np.int32) + rng.integers(-4, 5, src.shape), 0, 255).astype(np.uint8)
+        return images
+    if route == "wide":
+        def unit(x):
+            return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+        pool = unit(rng.normal(0.0, 1.0, (4 * rows, 256)))
+        images = [unit(rng.normal(0.0, 1.0, (rows, 256))) for _ in range(n_images)]
+        for im in images:
+            src = pool[rng.choice(pool.shape[0], shared, replace=False)]
+            im[:shared] = unit(src + rng.normal(0.0, 0.02 / 16.0, src.shape))
         return images
     if route == "f32":
         pool = rng.normal(0.0, 1.0, (4 * rows, 128)).astype(np.float32)
@@ -81,13 +92,13 @@ def main():
             ("window5", [(i, j) for i in range(ni) for j in range(i + 1, min(ni, i + 6))], None))
     for route in a.routes.split(","):
         images = _images(route, ni, a.rows, 21)
-        binary, fr = route == "bin32", route == "f32"
+        binary, fr, wide = route == "bin32", route == "f32", route == "wide"
         coll = ctx.collection()
         banks = []
         for im in images:
-            coll.add_binary(im) if binary else coll.add(im)
+            coll.add_wide(im) if wide else coll.add_binary(im) if binary else coll.add(im)
             banks.append(ctx.bank_binary(im) if binary else ctx.bank(im, float_route=fr))
-        ctx.set_option("f32_filter", 2 if fr else 1)
+        ctx.set_option("f32_filter", 2 if fr else 1)       # (wide: the default rule takes the filter on both sides at these sizes)
         for name, pairs, implied in sets:
             plist = implied if pairs is None else pairs
 
@@ -120,6 +131,12 @@ def main():
                    "one_call_wall_ms": med(w_one), "loop_wall_ms": med(w_loop), "counts_only_wall_ms": med(w_cnt),
                    "speedup_total_ms": med(t_loop) / med(t_one), "speedup_wall": med(w_loop) / med(w_one),
                    "pairs_per_s_one_call": 2.0 * len(plist) * a.rows * a.rows / (med(t_one) * 1e-3), "device": ctx.device_name()}
+            if wide:
+                l0, f0 = ctx.f32_filter_stats()
+                counts()
+                l1, f1 = ctx.f32_filter_stats()
+                rec["chunks_filtered_per_call"], rec["chunks_redone_per_call"] = l1 - l0, f1 - f0
+                rec["t_one_ms"], rec["t_loop_ms"] = t_one, t_loop
             line = json.dumps(rec)
             print(line, flush=True)
             if a.out:
