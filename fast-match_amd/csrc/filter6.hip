@@ -8,9 +8,9 @@
 // unit of the streamed bank against them with 8 instructions.  FP6 is lossy, so the sweep is a FILTER with a static
 // per-row threshold that provably keeps every candidate at d2 <= D* - 1 (fp6_filter.h); there are no shared bounds, no
 // atomics on the fast path and no top-K state.  A lane whose 16 candidates of a 32-row unit (one output row, half of the
-// unit's rows) clear its threshold writes (output row, unit) to its wave's list in LDS, which the wave copies to the pair's
-// list when it is full and when its sweep ends;
-// rescore6_kernel then computes the exact int32 d2 of each listed row against the unit's 32 streamed rows from the int8
+// unit's rows) clear its threshold writes (output row, unit, half) to its wave's list in LDS, which the wave copies to the
+// pair's list when it is full and when its sweep ends;
+// rescore6_kernel then computes the exact int32 d2 of each listed row against those 16 streamed rows from the int8
 // plane, as K1 does, and folds (d2 << 32 | row) into slice 0 of the pair's `partial` with a 64-bit atomic minimum -- the key
 // K1 writes and the order the election reduces with (lowest streamed row on ties).  The sweep's workgroups preset their
 // own (split, chunk) piece of `partial` to "none", so the kernels behind it see K1's layout.
@@ -55,7 +55,7 @@ struct F6Params {
     int            nstages, nsplit, nchunks, stages_per_split, ncols_alloc;
     unsigned long long* partial;  // K1's [nsplit][ncols_alloc] keys
     const unsigned* cut;          // device word D*
-    uint2*         rec;           // the pair's list: (output row, 32-row unit of the streamed bank)
+    uint2*         rec;           // the pair's list: (output row, 32-row unit of the streamed bank | half of the unit << 31)
     unsigned       cap;
     unsigned*      cnt;           // [0] records appended (may exceed cap), [1] need_k1
     // rescoring: the int8 planes
@@ -164,31 +164,51 @@ void filter6_kernel(F6Batch b)
     // cb + 32 j + (lane & 31); one threshold per lane and block
     v8i_6 bf[kF6NC][2];
     float thr[kF6NC];
+    constexpr int kDmaPerWave = 16 / kF6NW;
     {
         const int um = p.red_max[0], em = p.red_max[1];
         v4i lo[kF6NC][2], stat[kF6NC];
         v2i_6 hi[kF6NC][2];
+        // The loads as asm statements, unconditional (a lane beyond the bank reads its last row and drops it below), for
+        // two reasons.  Behind a condition each load is waited for where its branch ends, one round trip after the other.
+        // And with LDS-DMA in flight the compiler's own wait at the first use of a loaded register is vmcnt(0), which
+        // would drain the DMA issued below: it does not know of these loads, and the counted wait below is ours.
 #pragma unroll
         for (int j = 0; j < kF6NC; ++j) {
-            const int n = cb + 32 * j + r32;
-            stat[j] = v4i{0, 0, 0, 0};
+            const int n = min(cb + 32 * j + r32, ncols_pad - 1);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                lo[j][h] = v4i{0, 0, 0, 0};
-                hi[j][h] = v2i_6{0, 0};
-                if (n < ncols_pad) {
-                    const uint8_t* src = p.col_rows6 + (size_t)n * kDim + 32 * (2 * h + hs);
-                    lo[j][h] = *(const v4i*)src;
-                    hi[j][h] = *(const v2i_6*)(src + 16);
-                }
+                const uint8_t* src = p.col_rows6 + (size_t)n * kDim + 32 * (2 * h + hs);
+                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(lo[j][h]) : "v"(src) : "memory");
+                asm volatile("global_load_dwordx2 %0, %1, off offset:16" : "=v"(hi[j][h]) : "v"(src) : "memory");
             }
-            if (n < ncols) stat[j] = *(const v4i*)(p.col_stat + 4 * (size_t)n);
+            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(stat[j]) : "v"(p.col_stat + 4 * (size_t)n) : "memory");
         }
-        // (a use of every loaded register in front of the prefetch: the compiler waits for the loads HERE -- with the first
-        // use inside the stage loop its wait is a vmcnt(0) in front of every stage's first MFMA, which drains the LDS-DMA)
+        // The first two stages' LDS-DMA are issued HERE, behind the operand loads, and fly under the threshold arithmetic
+        // below.  They are this wave's newest vector memory operations (wave 7 issues one more per stage) and reads return
+        // in order, so the loads have landed at a counted vmcnt; the stage loop's hand-over waits count on the same order.
+        // (The presets of `partial` above are older stores: they can only make the wait longer.)
+        const int nfirst = min(st1 - st0, 2);
+        if (nfirst > 0) f6_issue_stage(red_rows6, red_aux6, st0, smem, wave, lane);
+        if (nfirst > 1) f6_issue_stage(red_rows6, red_aux6, st0 + 1, smem + kStageBytes, wave, lane);
+        if (nfirst > 1) {
+            if (wave == kF6NW - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * (kDmaPerWave + 1)) : "memory");
+            else                   asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * kDmaPerWave) : "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        // (no loaded register is read in front of this statement, which stands behind the wait: every later use goes
+        // through it.  It is also the use in front of the stage loop: with the first use inside the loop the operand would
+        // be assembled there)
 #pragma unroll
         for (int j = 0; j < kF6NC; ++j)
             asm volatile("" : "+v"(lo[j][0]), "+v"(hi[j][0]), "+v"(lo[j][1]), "+v"(hi[j][1]), "+v"(stat[j]));
+#pragma unroll
+        for (int j = 0; j < kF6NC; ++j)
+            if (cb + 32 * j + r32 >= ncols_pad) {
+                lo[j][0] = lo[j][1] = v4i{0, 0, 0, 0};
+                hi[j][0] = hi[j][1] = v2i_6{0, 0};
+            }
 #pragma unroll
         for (int j = 0; j < kF6NC; ++j) {
             const int n = cb + 32 * j + r32;
@@ -209,10 +229,6 @@ void filter6_kernel(F6Batch b)
         aoff1[h] = r32 * kDim + 16 * ((2 * (2 * h + hs) + 1) ^ sw);
     }
     const int xoff = kStageRowBytes + 16 * hs;
-    constexpr int kDmaPerWave = 16 / kF6NW;
-
-    if (st0 < st1) f6_issue_stage(red_rows6, red_aux6, st0, smem, wave, lane);
-    if (st0 + 1 < st1) f6_issue_stage(red_rows6, red_aux6, st0 + 1, smem + kStageBytes, wave, lane);
 
     // stage st becomes readable in buffer BUF; the DMA of stage st + 2 goes where stage st - 1 was (every wave has the whole
     // of that stage in registers or behind it: its reads are waited for in front of the barrier)
@@ -309,7 +325,8 @@ void filter6_kernel(F6Batch b)
                 // (LDS only: the hand-over's lgkmcnt(0) covers the write, which touches no stage buffer.  As a statement of
                 // its own: in front of a store to LDS the compiler waits for vmcnt(0), the LDS-DMA being a pending LDS write)
                 if (hit) {
-                    const unsigned long long r = ((unsigned long long)unit << 32) | (unsigned)(cb + 32 * j + r32);
+                    // (bit 31 of the unit word: which 16 of the unit's rows this lane's accumulators are)
+                    const unsigned long long r = ((unsigned long long)(unit | ((unsigned)hs << 31)) << 32) | (unsigned)(cb + 32 * j + r32);
                     asm volatile("ds_write_b64 %0, %1" :: "v"(hits_lds + 8u * (nrec + rank)), "v"(r) : "memory");
                 }
                 nrec += pc;
@@ -347,8 +364,12 @@ void filter6_kernel(F6Batch b)
     if (nrec != 0u) flush();
 }
 
-// One wave per record: exact int32 d2 of the output row against the unit's 32 streamed rows (lane l: row l & 31, K-half
-// l >> 5), from the int8 plane and its norms as K1 computes it; the best (d2, row) below D* goes into slice 0 of `partial`.
+// One wave per record: exact int32 d2 of the output row against the 16 streamed rows whose accumulators the recording lane
+// held -- rows (r & 3) + 8 (r >> 2) + 4 half of the unit, r = 0 .. 15, half = bit 31 of the record's unit word -- from the
+// int8 plane and its norms as K1 computes it (lane l: row r = l & 15, K-quarter l >> 4); the best (d2, row) below D* goes
+// into slice 0 of `partial`.  The other 16 rows of the unit are not read: a candidate among them made its own lane fire, and
+// the launch is bound by the bytes it reads, not by latency (387 076 records of the flagship step x 32 rows are 1.6 GB in
+// 0.26 ms; several records in flight per wave did not shorten it).
 __global__ __launch_bounds__(256)
 void rescore6_kernel(F6Batch b)
 {
@@ -363,24 +384,25 @@ void rescore6_kernel(F6Batch b)
         for (unsigned r = wave; r < n; r += nwaves) {
             const uint2 rc = p.rec[r];
             const int c = (int)rc.x;
-            const int m = (int)(rc.y * 32u) + (lane & 31);
-            const int h = lane >> 5;
+            const int rr = lane & 15, kq = lane >> 4;
+            const int m = (int)((rc.y & 0x7fffffffu) * 32u) + (rr & 3) + 8 * (rr >> 2) + 4 * (int)(rc.y >> 31);
             // (m < n_pad of the streamed bank: the unit was staged from it)
-            const int8_t* a = p.col_rows8 + (size_t)c * kDim + 64 * h;
-            const int8_t* y = p.red_rows8 + (size_t)m * kDim + 64 * h;
+            const int8_t* a = p.col_rows8 + (size_t)c * kDim + 32 * kq;
+            const int8_t* y = p.red_rows8 + (size_t)m * kDim + 32 * kq;
             int dot = 0;
 #pragma unroll
-            for (int w = 0; w < 4; ++w) {
+            for (int w = 0; w < 2; ++w) {
                 const v4i x = *(const v4i*)(a + 16 * w);
                 const v4i z = *(const v4i*)(y + 16 * w);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) dot = __builtin_amdgcn_sdot4(x[k], z[k], dot, false);
             }
+            dot += __shfl_xor(dot, 16);
             dot += __shfl_xor(dot, 32);
             const unsigned d2 = (unsigned)(p.col_norm[c] + p.red_norm[m] - 2 * dot);
             unsigned long long key = (m < p.nred && d2 < dstar) ? ((unsigned long long)d2 << 32) | (unsigned)m : ~0ull;
 #pragma unroll
-            for (int o = 16; o > 0; o >>= 1) {
+            for (int o = 8; o > 0; o >>= 1) {
                 const unsigned long long other = __shfl_xor(key, o);
                 key = other < key ? other : key;
             }
