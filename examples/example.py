@@ -92,3 +92,12 @@ wide_graph.add_wide(wide_views)
 wide_edges = wide_graph.matchPairs(ratio=0.8, symmetric=True)
 print("256-D match graph: %d pairs, (0, 1) has %d matches, (0, 2) has %d" % (len(wide_edges), len(wide_edges[(0, 1)]), len(wide_edges[(0, 2)])))
 assert len(wide_edges) == 6 and len(wide_edges[(0, 1)]) == 100 and len(wide_edges[(0, 2)]) == 0
+
+# Binary descriptors (ORB, 32 bytes): a distance threshold instead of k -- every database row within 40 bits of a query row.
+# Distances are integers and the compare is strict, so "h <= 40" is maxDistance = 40.5.
+orb_db = rng.integers(0, 256, (5000, 32), dtype=np.uint8)
+orb_q = orb_db[:200].copy()
+orb_q[:, 0] ^= 0b10110                                             # the same rows, three bits flipped
+near = matchutil.hamming_radius_match(orb_q, orb_db, 40.5)
+print("ORB radius match: %d of 200 query rows found within 40 bits, %d entries in all" % (sum(bool(l) for l in near), sum(map(len, near))))
+assert all(l and l[0].trainIdx == i and l[0].distance == 3.0 for i, l in enumerate(near))

@@ -179,6 +179,10 @@ SYMBOLS = {
     "fm_collection_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
     "fm_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
     "fm_collection_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    "fm_hamming_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_hamming_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    "fm_collection_hamming_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_collection_hamming_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
     # K13: knnMatch under a mask (csrc/masked.hip)
     "fm_mask_create": (_INT, [_P, _I64, _I64, ctypes.POINTER(_P)]),
     "fm_mask_create_coll": (_INT, [_P, _I64, _P, ctypes.POINTER(_P)]),
@@ -570,7 +574,7 @@ class Collection(object):
             _P(int(count_ptr)) if count_ptr else None, ctypes.byref(n) if want_count else None, _stream_arg(consumer_stream)))
         return int(n.value) if want_count else None
 
-    def radius_match(self, q, r):
+    def radius_match(self, q, r, _name="fm_collection_radius_match"):
         """``fm_collection_radius_match``: every row of the stacked images with distance < r per query row.  ``r`` is a scalar
         or a float32 [nq] array.  Returns (offsets int64[nq + 1], img int32[n], idx int32[n], dist float32[n]): row i's list is
         img / idx / dist[offsets[i]:offsets[i + 1]], ascending (distance, image, row inside the image).  A counts call sizes
@@ -586,7 +590,7 @@ class Collection(object):
         rp = _ptr(rad) if rad is not None and nq > 0 else None
         offsets = np.zeros(nq + 1, dtype=np.int64)
         total = _I64(0)
-        fn = self.ctx.lib.fm_collection_radius_match
+        fn = getattr(self.ctx.lib, _name)
         self.ctx._check(fn(self.ctx.handle, self.handle, q.handle, rp, r_all, 0, _ptr(offsets), None, None, None, ctypes.byref(total)))
         n = int(total.value)
         img = np.empty(n, dtype=np.int32)
@@ -596,18 +600,31 @@ class Collection(object):
             self.ctx._check(fn(self.ctx.handle, self.handle, q.handle, rp, r_all, n, _ptr(offsets), _ptr(img), _ptr(idx), _ptr(dist),
                                ctypes.byref(total)))
             if int(total.value) != n:
-                raise FastMatchHipError("fm_collection_radius_match: %d entries on the second call, %d on the first" % (total.value, n))
+                raise FastMatchHipError("%s: %d entries on the second call, %d on the first" % (_name, total.value, n))
         return offsets, img, idx, dist
 
+    def hamming_radius_match(self, q, r):
+        """``fm_collection_hamming_radius_match``: ``radius_match`` of a binary query against a binary collection -- every
+        row of the stacked images with ``popcount(q XOR t) < r`` (strict, float32; ``h <= H`` is ``r = H + 0.5``), lists
+        ascending (h, image, row inside the image).  Arguments and return value as ``radius_match``."""
+        return self.radius_match(q, r, _name="fm_collection_hamming_radius_match")
+
+    def hamming_radius_match_dev(self, q, radius_ptr, radius_all, cap, offsets_ptr, img_ptr, idx_ptr, dist_ptr, want_total=True,
+                                 consumer_stream=None):
+        """``hamming_radius_match`` with the radii read from and the lists left in device memory
+        (``fm_collection_hamming_radius_match_dev``); arguments as ``radius_match_dev``."""
+        return self.radius_match_dev(q, radius_ptr, radius_all, cap, offsets_ptr, img_ptr, idx_ptr, dist_ptr, want_total,
+                                     consumer_stream, _name="fm_collection_hamming_radius_match_dev")
+
     def radius_match_dev(self, q, radius_ptr, radius_all, cap, offsets_ptr, img_ptr, idx_ptr, dist_ptr, want_total=True,
-                         consumer_stream=None):
+                         consumer_stream=None, _name="fm_collection_radius_match_dev"):
         """``radius_match`` with the radii read from and the lists left in device memory (``fm_collection_radius_match_dev``):
         ``radius_ptr`` = device address of float32 [nq] radii, or 0 for the scalar ``radius_all``; ``offsets_ptr`` of an int64
         [nq + 1] buffer; ``img_ptr`` / ``idx_ptr`` / ``dist_ptr`` of int32 / int32 / float32 [cap] buffers (0 with cap = 0).
         Returns the number of entries (``want_total``) or None.  The call synchronises (the counts plan the chunks);
         ``consumer_stream`` as in ``Context.knn_dev``."""
         n = _I64(0)
-        self.ctx._check(self.ctx.lib.fm_collection_radius_match_dev(
+        self.ctx._check(getattr(self.ctx.lib, _name)(
             self.ctx.handle, self.handle, q.handle, _P(int(radius_ptr)) if radius_ptr else None, float(np.float32(radius_all)), int(cap),
             _P(int(offsets_ptr)) if offsets_ptr else None, _P(int(img_ptr)) if img_ptr else None, _P(int(idx_ptr)) if idx_ptr else None,
             _P(int(dist_ptr)) if dist_ptr else None, ctypes.byref(n) if want_total else None, _stream_arg(consumer_stream)))
@@ -1148,18 +1165,26 @@ class Context(object):
                                                ctypes.byref(n) if want_count else None, _stream_arg(consumer_stream)))
         return int(n.value) if want_count else None
 
-    def radius_match_dev(self, q, t, radius_ptr, radius_all, cap, offsets_ptr, idx_ptr, dist_ptr, want_total=True, consumer_stream=None):
+    def radius_match_dev(self, q, t, radius_ptr, radius_all, cap, offsets_ptr, idx_ptr, dist_ptr, want_total=True, consumer_stream=None,
+                         _name="fm_radius_match_dev"):
         """``radius_match`` with the radii read from and the lists left in device memory (``fm_radius_match_dev``):
         ``radius_ptr`` = device address of float32 [nq] radii, or 0 for the scalar ``radius_all``; ``offsets_ptr`` of an int64
         [nq + 1] buffer; ``idx_ptr`` / ``dist_ptr`` of int32 / float32 [cap] buffers (0 with cap = 0: a counts call).  Returns
         the number of entries (``want_total``) or None.  The call synchronises (the counts plan the chunks); what it spares
         is the radii going up and the lists coming down.  ``consumer_stream`` as in ``knn_dev``."""
         n = _I64(0)
-        self._check(self.lib.fm_radius_match_dev(
+        self._check(getattr(self.lib, _name)(
             self.handle, q.handle, t.handle, _P(int(radius_ptr)) if radius_ptr else None, float(np.float32(radius_all)), int(cap),
             _P(int(offsets_ptr)) if offsets_ptr else None, _P(int(idx_ptr)) if idx_ptr else None,
             _P(int(dist_ptr)) if dist_ptr else None, ctypes.byref(n) if want_total else None, _stream_arg(consumer_stream)))
         return int(n.value) if want_total else None
+
+    def hamming_radius_match_dev(self, q, t, radius_ptr, radius_all, cap, offsets_ptr, idx_ptr, dist_ptr, want_total=True,
+                                 consumer_stream=None):
+        """``hamming_radius_match`` with the radii read from and the lists left in device memory
+        (``fm_hamming_radius_match_dev``); arguments as ``radius_match_dev``."""
+        return self.radius_match_dev(q, t, radius_ptr, radius_all, cap, offsets_ptr, idx_ptr, dist_ptr, want_total, consumer_stream,
+                                     _name="fm_hamming_radius_match_dev")
 
     def bank_gather(self, rows, src_row, float_route=False):
         """The bank ``rows[src_row]`` without building that matrix on the host: the n_src rows are uploaded once and
@@ -1240,7 +1265,13 @@ class Context(object):
                                                _P(int(idx_ptr)) if idx_ptr else None, _P(int(dist_ptr)) if dist_ptr else None,
                                                _stream_arg(consumer_stream)))
 
-    def radius_match(self, q, t, r):
+    def hamming_radius_match(self, q, t, r):
+        """``fm_hamming_radius_match``: ``radius_match`` on two binary banks (``bank_binary``) -- every train row with
+        ``popcount(q XOR t) < r`` per query row (strict, float32: ``h <= H`` is ``r = H + 0.5``), lists ascending (h, index).
+        Arguments and return value as ``radius_match``."""
+        return self.radius_match(q, t, r, _name="fm_hamming_radius_match")
+
+    def radius_match(self, q, t, r, _name="fm_radius_match"):
         """``fm_radius_match``: every train row with distance < r per query row -- cv2's radiusMatch with compactResult
         False.  ``r`` is a scalar or a float32 [nq] array (one radius per query row).  Returns (offsets int64[nq + 1],
         idx int32[n], dist float32[n]): row i's list is idx / dist[offsets[i]:offsets[i + 1]], ascending (distance, index).
@@ -1256,16 +1287,15 @@ class Context(object):
         rp = _ptr(rad) if rad is not None and nq > 0 else None
         offsets = np.zeros(nq + 1, dtype=np.int64)
         total = _I64(0)
-        self._check(self.lib.fm_radius_match(self.handle, q.handle, t.handle, rp, r_all, 0, _ptr(offsets), None, None,
-                                             ctypes.byref(total)))
+        fn = getattr(self.lib, _name)
+        self._check(fn(self.handle, q.handle, t.handle, rp, r_all, 0, _ptr(offsets), None, None, ctypes.byref(total)))
         n = int(total.value)
         idx = np.empty(n, dtype=np.int32)
         dist = np.empty(n, dtype=np.float32)
         if n > 0:
-            self._check(self.lib.fm_radius_match(self.handle, q.handle, t.handle, rp, r_all, n, _ptr(offsets), _ptr(idx),
-                                                 _ptr(dist), ctypes.byref(total)))
+            self._check(fn(self.handle, q.handle, t.handle, rp, r_all, n, _ptr(offsets), _ptr(idx), _ptr(dist), ctypes.byref(total)))
             if int(total.value) != n:
-                raise FastMatchHipError("fm_radius_match: %d entries on the second call, %d on the first" % (total.value, n))
+                raise FastMatchHipError("%s: %d entries on the second call, %d on the first" % (_name, total.value, n))
         return offsets, idx, dist
 
     def self_dist(self, bank):

@@ -1216,13 +1216,19 @@ extern "C" int fm_collection_knn2_ratio_dev(fm_ctx* ctx, fm_collection* c, const
 // radiusMatch against the stacked images (K10, radius.hip): the stack is the train bank of ONE sweep whose epilogue masks
 // the padding rows by index (st_real), and the compaction turns a key's physical row into (image, row).  Host arrays, or
 // (dev) the caller's device arrays.
+// ham: the Hamming entry points (fm_collection_hamming_radius_match(_dev)) -- a binary query against a binary collection;
+// the L2-named ones keep refusing a binary collection.
 static int coll_radius(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const float* radius, float radius_all, int64_t cap, int64_t* offsets,
-                       int32_t* img, int32_t* idx, float* dist, int64_t* n_total, bool dev, void* consumer, const char* who)
+                       int32_t* img, int32_t* idx, float* dist, int64_t* n_total, bool dev, void* consumer, const char* who, bool ham = false)
 {
     int rc = coll_query_check(ctx, c, q, who, true);
     if (rc != FM_OK) return rc;
-    if (c->dim != 0 && c->stack.kind == FM_BANK_BIN)
-        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": Hamming radiusMatch is not built (binary collection)");
+    if (!ham && c->dim != 0 && c->stack.kind == FM_BANK_BIN)
+        return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": Hamming radiusMatch is not built here (binary collection): "
+                                          "fm_collection_hamming_radius_match serves it");
+    if (ham && (q->kind != FM_BANK_BIN || (c->dim != 0 && c->stack.kind != FM_BANK_BIN)))
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the query bank and the collection must be binary (FM_BANK_BIN); "
+                                    "fm_collection_radius_match is the L2 call");
     if (cap < 0) return fail(ctx, FM_EINVAL, std::string(who) + ": cap is negative");
     if (!offsets) return fail(ctx, FM_EINVAL, std::string(who) + ": offsets is NULL");
     if (cap > 0 && (!img || !idx || !dist)) return fail(ctx, FM_EINVAL, std::string(who) + ": img / idx / dist is NULL with cap > 0");
@@ -1251,6 +1257,21 @@ extern "C" int fm_collection_radius_match_dev(fm_ctx* ctx, fm_collection* c, con
 {
     return coll_radius(ctx, c, q, d_radius, radius_all, cap, d_offsets, d_img, d_idx, d_dist, n_total, true, consumer_stream,
                        "fm_collection_radius_match_dev");
+}
+
+extern "C" int fm_collection_hamming_radius_match(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const float* radius, float radius_all,
+                                                  int64_t cap, int64_t* offsets, int32_t* img, int32_t* idx, float* dist, int64_t* n_total)
+{
+    return coll_radius(ctx, c, q, radius, radius_all, cap, offsets, img, idx, dist, n_total, false, FM_NO_STREAM,
+                       "fm_collection_hamming_radius_match", true);
+}
+
+extern "C" int fm_collection_hamming_radius_match_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const float* d_radius, float radius_all,
+                                                      int64_t cap, int64_t* d_offsets, int32_t* d_img, int32_t* d_idx, float* d_dist,
+                                                      int64_t* n_total, void* consumer_stream)
+{
+    return coll_radius(ctx, c, q, d_radius, radius_all, cap, d_offsets, d_img, d_idx, d_dist, n_total, true, consumer_stream,
+                       "fm_collection_hamming_radius_match_dev", true);
 }
 
 // The per-image 2-NN lists on the device: d_idx / d_dist [n_images][nq][2].  Up to "batch_group" images per launch of the

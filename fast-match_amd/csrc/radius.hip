@@ -18,6 +18,9 @@
 //   sorting               per segment: <= kRSortThread keys one thread, <= kRSortLds one workgroup (bitonic in LDS),
 //                         longer ones rocPRIM's segmented radix sort (off the hot path: r = inf against large banks).
 //   radius_compact_kernel sorted keys -> train index / distance at the row's final offset.
+//   radius_ham_kernel     Hamming route (fm_hamming_radius_match and kin, binary banks): K11's FP4 operands and K11's loop with
+//                         the threshold test on the raw dot product W - 2 h (ham_radius.h); FILL keys are (float bits of h << 32)
+//                         | train row, final like the integer route's: everything behind the count sweep is that route's path.
 // Query rows go in chunks whose candidates fit in the option "radius_ws_bytes" (24 bytes per candidate; 28 against a collection).
 // A train collection (fm_collection_radius_match): the train bank is the collection's stack, which has padding rows behind
 //   EVERY image whose size is no multiple of 128.  Their values would pass (norm 2^26 against D = 0x7fffffff at r = +inf; 1e18
@@ -36,6 +39,7 @@
 // grid = (query groups of 256 rows, splits of the train range).
 #include "ctx_internal.h"
 #include "coll_tab.h"
+#include "ham_radius.h"
 #include <algorithm>
 #include <optional>
 #include <rocprim/device/device_scan.hpp>
@@ -46,6 +50,7 @@ namespace fm {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef _Float16 rv8h __attribute__((ext_vector_type(8)));
 typedef float rv4f __attribute__((ext_vector_type(4)));
+typedef int rv8i __attribute__((ext_vector_type(8)));
 
 constexpr int kRStage = 64;                // train rows per LDS stage
 constexpr int kRNB = 4;                    // blocks of 16 query rows per wave
@@ -62,11 +67,13 @@ struct RSweep {
     const int8_t* trows; const int32_t* tnorm;
     const uint16_t* qrowsh; const float* qnormf;    // float32 route
     const uint16_t* trowsh; const float* tnormf;
+    const uint8_t* q4; const uint8_t* t4;           // Hamming route: the banks' FP4 planes (Bank::rows4), 64 ks bytes per row
+    int ks, W;                 // Hamming route: MFMA K steps per row (0: another route), bits per row
     float cq, ct;              // float32 route: stored |q|^2, |t|^2 -> accumulator units 2^(kq + kt)
     int all;                   // float32 route without filter planes: every pair is a candidate
-    int nq, nt, per;           // query rows of the launch, train rows, train rows per split (a multiple of kRStage)
+    int nq, nt, per;           // query rows of the launch, train rows, train rows per split (a multiple of kRStage; Hamming: of 128)
     const int* lim;            // integer route: D_i (-1: none)
-    const float* thr;          // float32 route: threshold on A in accumulator units
+    const float* thr;          // float32 route: threshold on A in accumulator units; Hamming route: the least dot product of a hit
     unsigned* cnt;             // FILL = false: hit counts; FILL = true: cursors (zeroed)
     const int64_t* off;        // FILL: segment offsets of the launch's query rows, minus `base`
     int64_t base;
@@ -286,6 +293,132 @@ void radius_f16_kernel(RSweep p)
     }
 }
 
+// Hamming route (binary banks, K11's operands: hamming.hip): every bit is one FP4 value, +1 or -1, so the dot product of two
+// encoded rows is W - 2 h, exact in the f32 accumulator; a hit is dot >= thr (ham_radius.h), h = (W - dot) / 2.  K11's loop:
+// 128-row stages through two LDS buffers, the next stage prefetched into registers, one barrier per stage, row pitch RB + 16;
+// the 64 query rows of a wave are the B operand, in registers for the whole sweep.  A split is whole stages (p.per rows).
+// Padding rows are all-zero FP4 rows at dot = 0 -- h = W / 2, inside any r > W / 2 -- and are kept out by index: rows from
+// `lim` on (the bank's nt, or the real rows of a collection's stage) never count; only a last, partial stage pays for the test.
+template <bool FILL, int KS>
+__global__ __launch_bounds__(256)
+void radius_ham_kernel(RSweep p)
+{
+    constexpr int RB = KS * 64;             // FP4 bytes per row
+    constexpr int LS = RB + 16;             // LDS row pitch
+    constexpr int PIECES = kStageRows * RB / 16 / 256;    // 16-byte pieces per thread per stage (2 KS)
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2][kStageRows * LS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
+    const int qw = blockIdx.x * kRQPerWG + wave * 16 * kRNB;
+    const int nstages = (p.nt + kStageRows - 1) / kStageRows;
+    const int st0 = blockIdx.y * (p.per / kStageRows), st1 = min(nstages, st0 + p.per / kStageRows);
+
+    rv8i bop[kRNB][KS];
+    float thr[kRNB];
+    unsigned count[kRNB];
+#pragma unroll
+    for (int b = 0; b < kRNB; ++b) {
+        const int q = qw + 16 * b + j;
+        const bool live = q < p.nq;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const v4i x = live ? *(const v4i*)(p.q4 + (size_t)q * RB + 64 * ks + 16 * g) : v4i{0, 0, 0, 0};
+            bop[b][ks] = rv8i{x[0], x[1], x[2], x[3], 0, 0, 0, 0};
+        }
+        thr[b] = live ? p.thr[q] : INFINITY;
+        count[b] = 0;
+    }
+
+    v4i pre[PIECES];
+    auto load = [&](int st) {
+#pragma unroll
+        for (int i = 0; i < PIECES; ++i)      // (whole stages: st < nstages <= n_pad / 128)
+            pre[i] = *(const v4i*)(p.t4 + ((size_t)st * kStageRows) * RB + (size_t)(tid + 256 * i) * 16);
+    };
+    auto store = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < PIECES; ++i) {
+            const int pc = tid + 256 * i;
+            *(v4i*)(&lds[buf][(pc / (RB / 16)) * LS + 16 * (pc % (RB / 16))]) = pre[i];
+        }
+    };
+    if (st0 < st1) { load(st0); store(0); }
+    __syncthreads();
+    for (int st = st0; st < st1; ++st) {
+        const int buf = (st - st0) & 1;
+        const bool more = st + 1 < st1;
+        if (more) load(st + 1);
+        const int sbase = st * kStageRows;
+        const int lim = p.st_real ? sbase + p.st_real[st] : p.nt;       // (uniform: one table word per stage)
+        const bool tail = sbase + kStageRows > lim;
+        const int rowlim = lim - sbase - 4 * g;      // tail: register r of tile t is a real train row iff 16 t + r < rowlim
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {       // r_emit takes the 16 candidates a lane has in 64 rows
+            unsigned mask[kRNB];
+            float dot[FILL ? kRNB : 1][16];
+#pragma unroll
+            for (int b = 0; b < kRNB; ++b) mask[b] = 0;
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) {
+                const int t = 4 * half + tt;
+                rv8i aop[KS];
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    const v4i x = *(const v4i*)(&lds[buf][(16 * t + j) * LS + 64 * ks + 16 * g]);
+                    aop[ks] = rv8i{x[0], x[1], x[2], x[3], 0, 0, 0, 0};
+                }
+#pragma unroll
+                for (int b = 0; b < kRNB; ++b) {
+                    rv4f acc = rv4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks)
+                        acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(aop[ks], bop[b][ks], acc, 4, 4, 0, 127, 0, 127);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        bool hit = acc[r] >= thr[b];
+                        if (tail) hit = hit && 16 * t + r < rowlim;
+                        if constexpr (FILL) {
+                            mask[b] |= hit ? (1u << (4 * tt + r)) : 0u;
+                            dot[b][4 * tt + r] = acc[r];
+                        } else {
+                            count[b] += hit ? 1u : 0u;
+                        }
+                    }
+                }
+            }
+            if constexpr (FILL) {
+#pragma unroll
+                for (int b = 0; b < kRNB; ++b) {
+                    if (!__any(mask[b] != 0)) continue;
+                    unsigned hi[16];
+#pragma unroll
+                    for (int c = 0; c < 16; ++c) hi[c] = __float_as_uint((float)((p.W - (int)dot[b][c]) >> 1));
+                    r_emit(p, mask[b], hi, qw + 16 * b + j, qw + 16 * b + j < p.nq, sbase + 64 * half, lane);
+                }
+            }
+        }
+        if (more) store(buf ^ 1);
+        __syncthreads();
+    }
+    if constexpr (!FILL) {
+#pragma unroll
+        for (int b = 0; b < kRNB; ++b) {
+            unsigned c = count[b];
+            c += __shfl_xor(c, 16);
+            c += __shfl_xor(c, 32);
+            const int q = qw + 16 * b + j;
+            if (g == 0 && q < p.nq && c) atomicAdd(&p.cnt[q], c);
+        }
+    }
+}
+
+// Hamming route: the least dot product of a hit per query row (ham_radius.h).
+__global__ void radius_ham_limits_kernel(const float* __restrict__ radius, float radius_all, int nq, int W, float* __restrict__ thr)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    thr[i] = ham_radius_dot_min(ham_radius_limit(radius ? radius[i] : radius_all, W), W);
+}
+
 // Per query row: the radius and what the sweep compares against (see the file comment).  `radius` is the staged copy of the
 // host form's array or, in the device forms, the caller's own array read in place.
 __global__ void radius_limits_kernel(const float* __restrict__ radius, float radius_all, int nq, int f32, int all,
@@ -449,10 +582,41 @@ static int r_splits(int64_t nq, int64_t nt)
     return (int)s;
 }
 
+// Hamming route: splits of whole 128-row stages -- ~2048 workgroups on the chip, a split of at least 4 stages (K11's rule,
+// plan_hamming); returns the stages per split.  (Restated in tests/hamming_radius_ref.py.)
+static int r_ham_stages_per_split(int64_t nq, int64_t nt, int* nsplit)
+{
+    const int64_t qg = (nq + kRQPerWG - 1) / kRQPerWG, nstages = (nt + kStageRows - 1) / kStageRows;
+    int64_t ns = (2048 + qg - 1) / qg;
+    if (ns > (nstages + 3) / 4) ns = (nstages + 3) / 4;
+    if (ns < 1) ns = 1;
+    if (ns > 65535) ns = 65535;
+    const int64_t sps = (nstages + ns - 1) / ns;
+    *nsplit = (int)((nstages + sps - 1) / sps);
+    return (int)sps;
+}
+
 static hipError_t r_sweep(const RSweep& base, bool f32, bool fill, int64_t q0, int64_t nq, hipStream_t stream)
 {
     RSweep p = base;
     p.nq = (int)nq;
+    if (p.ks) {
+        p.q4 += q0 * p.ks * 64; p.thr += q0;
+        if (fill) p.off += q0;
+        else p.cnt += q0;
+        int ns = 1;
+        p.per = r_ham_stages_per_split(nq, p.nt, &ns) * kStageRows;
+        const dim3 grid((unsigned)((nq + kRQPerWG - 1) / kRQPerWG), (unsigned)ns);
+#define FM_RHAM(KS_)                                                                                      \
+        if (p.ks == KS_) {                                                                                \
+            if (fill) hipLaunchKernelGGL((radius_ham_kernel<true, KS_>), grid, dim3(256), 0, stream, p);  \
+            else      hipLaunchKernelGGL((radius_ham_kernel<false, KS_>), grid, dim3(256), 0, stream, p); \
+            return hipGetLastError();                                                                     \
+        }
+        FM_RHAM(1) FM_RHAM(2) FM_RHAM(3) FM_RHAM(4)
+#undef FM_RHAM
+        return hipErrorInvalidValue;
+    }
     if (f32) { if (!p.all) { p.qrowsh += q0 * kDim; p.qnormf += q0; } p.thr += q0; }
     else     { p.qrows += q0 * kDim; p.qnorm += q0; p.lim += q0; }
     if (fill) p.off += q0;
@@ -578,6 +742,8 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
     }
     if (nt > 0x7fffffff || nq > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, std::string(a.who) + ": more than 2^31 - 1 rows in a bank");
     const bool f32 = q.kind == FM_BANK_F32;
+    const bool ham = q.kind == FM_BANK_BIN;       // (the Hamming entry points: both banks binary, of one width; counts are final,
+                                                  // so everything behind the count sweep is the integer route's path)
     const bool all = f32 && !filter_usable(q, t);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::optional<CallScope> cs;          // (the device forms are not accounted in fm_stats)
@@ -615,14 +781,19 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
     const double unit = f32 && !all ? ldexp(1.0, q.kscale + t.kscale) : 1.0;
     // (a collection's nm_max is the real rows': the planes of an image are made while its padding rows still hold 0, the
     // far value goes in afterwards -- coll_f32_finish)
-    hipLaunchKernelGGL(radius_limits_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
-                       k_rad, a.radius_all, (int)nq, f32 ? 1 : 0, all ? 1 : 0,
-                       (const float*)(f32 && !all ? q.normf : nullptr), cq, unit, f32 && !all ? t.nm_max * ct : 0.f, d_lim, d_thr, d_rr);
+    if (ham)
+        hipLaunchKernelGGL(radius_ham_limits_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
+                           k_rad, a.radius_all, (int)nq, 8 * q.dim, d_thr);
+    else
+        hipLaunchKernelGGL(radius_limits_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
+                           k_rad, a.radius_all, (int)nq, f32 ? 1 : 0, all ? 1 : 0,
+                           (const float*)(f32 && !all ? q.normf : nullptr), cq, unit, f32 && !all ? t.nm_max * ct : 0.f, d_lim, d_thr, d_rr);
     HIP_TRY(ctx, hipGetLastError());
 
     RSweep sw{};
     sw.qrows = q.rows8; sw.qnorm = q.norm; sw.trows = t.rows8; sw.tnorm = t.norm;
     sw.qrowsh = q.rowsh; sw.qnormf = q.normf; sw.trowsh = t.rowsh; sw.tnormf = t.normf;
+    sw.q4 = q.rows4; sw.t4 = t.rows4; sw.ks = ham ? q.ksteps : 0; sw.W = 8 * q.dim;
     sw.cq = cq; sw.ct = ct; sw.all = all ? 1 : 0;
     sw.nt = (int)nt; sw.lim = d_lim; sw.thr = d_thr;
     sw.st_real = a.tab ? (const int*)a.tab->st_real : nullptr;

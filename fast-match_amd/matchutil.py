@@ -13,11 +13,15 @@ Mirrors ``matchutil.py`` of the reference:
   .radiusMatch(dt1, dt2, maxDistance)`` (compactResult False; the reference has no call
   site): every train row with distance < maxDistance, one list per query row ascending
   by (distance, train index).  ``maxDistance`` may also be one radius per query row.
+* ``hamming_radius_match(dt1, dt2, maxDistance, options={})`` / ``hamming_radius_match_arrays`` --
+  ``cv2.BFMatcher(cv2.NORM_HAMMING).radiusMatch`` on binary descriptors (uint8 rows of 1 .. 64 bytes, or resident binary
+  banks): every train row with ``popcount(q XOR t) < maxDistance`` (strict, float32: ``h <= H`` is ``H + 0.5``), one list
+  per query row ascending by (h, train index) (``fm_hamming_radius_match``).  ``bf_radius_match`` stays the NORM_L2 call.
 * ``options["normType"]``: ``NORM_L2`` (4, the default) or ``NORM_HAMMING`` (6) -- cv2's values.  With
   ``NORM_HAMMING`` the descriptors are binary (ORB, BRIEF, BRISK, FREAK, AKAZE: uint8 rows of 1 .. 64 bytes,
   ``Context.bank_binary``) and the distance is the bit count of ``q XOR t`` (``cv2.BFMatcher(cv2.NORM_HAMMING,
   crossCheck)``); ``bf_match``, ``flann_match`` and ``ratio_match_arrays`` honour it, ``bf_radius_match`` does not
-  (``ValueError``), nor does anything else take ``NORM_HAMMING2``.  Without ``normType`` every array is an L2 bank,
+  (``ValueError``: ``hamming_radius_match`` is the call), nor does anything else take ``NORM_HAMMING2``.  Without ``normType`` every array is an L2 bank,
   a uint8 [n, 32] array included.
 * Wide float descriptors -- float arrays of 129 .. 256 values per row, SuperPoint's 256-D rows for one -- go to the
   library's wide float banks under ``NORM_L2``: ``bf_match`` with k <= 2 and with crossCheck, ``ratio_match_arrays`` and
@@ -305,7 +309,7 @@ def bf_radius_match_arrays(dt1, dt2, maxDistance, options={}):
     list is ``idx[offsets[i]:offsets[i + 1]]`` / ``dist[...]``.  ``maxDistance`` is a scalar (float32, as the cv2 binding
     passes it) or an array of one radius per query row."""
     if _norm_type(options, dt1, dt2) == NORM_HAMMING:
-        raise ValueError("bf_radius_match: radiusMatch with NORM_HAMMING is not built (NORM_L2 only)")
+        raise ValueError("bf_radius_match: radiusMatch with NORM_HAMMING is not built here (NORM_L2 only): hamming_radius_match is the call")
     _mask_option(options, dt1, dt2, "bf_radius_match", "radiusMatch")
     _refuse_wide("bf_radius_match", "radiusMatch", dt1, dt2)
     ctx = _context(options)
@@ -322,6 +326,54 @@ def bf_radius_match_arrays(dt1, dt2, maxDistance, options={}):
 def bf_radius_match(dt1, dt2, maxDistance, options={}):
     """ cv2.BFMatcher(NORM_L2).radiusMatch(dt1, dt2, maxDistance): a list of DMatch lists, one per query row """
     off, idx, dist = bf_radius_match_arrays(dt1, dt2, maxDistance, options=options)
+    return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
+
+
+def _binary_operand(d):
+    """A resident binary bank, or a uint8 [n, 1 .. 64] array -- ValueError before anything is uploaded.  Returns (operand, bytes, rows)."""
+    if isinstance(d, _ffi.Bank):
+        if d.kind != _ffi.FM_BANK_BIN:
+            raise ValueError("hamming_radius_match takes binary banks (Context.bank_binary); bf_radius_match is the NORM_L2 call")
+        return d, d.dim, d.n
+    a = np.asarray(d)
+    if a.ndim != 2:
+        raise ValueError("descriptors must be a 2-D [n, bytes] array")
+    if a.dtype != np.uint8:
+        raise ValueError("hamming_radius_match needs uint8 descriptors (cv2 asserts CV_8U for NORM_HAMMING), got %s" % a.dtype)
+    if not 1 <= a.shape[1] <= 64:
+        raise ValueError("hamming_radius_match: binary descriptors have 1 .. 64 bytes per row, got %d" % a.shape[1])
+    return a, a.shape[1], a.shape[0]
+
+
+def hamming_radius_match_arrays(dt1, dt2, maxDistance, options={}):
+    """``cv2.BFMatcher(cv2.NORM_HAMMING).radiusMatch(dt1, dt2, maxDistance)`` as arrays: ``(offsets int64[nq + 1], idx
+    int32[n], dist float32[n])``; query row i's list is ``idx[offsets[i]:offsets[i + 1]]`` / ``dist[...]``, every train row
+    with ``popcount(q XOR t) < maxDistance`` (a strict float32 compare; distances are integers, so ``h <= H`` is
+    ``maxDistance = H + 0.5``), ascending by (h, train index).  ``dt1`` / ``dt2``: uint8 arrays of 1 .. 64 bytes per row or
+    resident binary banks; ``maxDistance``: a scalar or one radius per query row.  ``ValueError`` before anything is
+    uploaded: another dtype, widths that differ or lie outside 1 .. 64, a ``mask`` option, a wrong number of radii."""
+    q, qw, nq = _binary_operand(dt1)
+    t, tw, _ = _binary_operand(dt2)
+    if qw != tw:
+        raise ValueError("hamming_radius_match: %d bytes per query row, %d per train row" % (qw, tw))
+    if options and options.get("mask") is not None:
+        raise ValueError("hamming_radius_match: a mask is not built for radiusMatch (knnMatch takes one: bf_match)")
+    if np.ndim(maxDistance) != 0 and np.asarray(maxDistance).reshape(-1).shape[0] != nq:
+        raise ValueError("hamming_radius_match: %d radii for %d query rows" % (np.asarray(maxDistance).reshape(-1).shape[0], nq))
+    ctx = _context(options)
+    qb, q_tmp, tb, t_tmp = _bank_pair(ctx, q, t, NORM_HAMMING)
+    try:
+        return ctx.hamming_radius_match(qb, tb, maxDistance)
+    finally:
+        if q_tmp:
+            qb.close()
+        if t_tmp:
+            tb.close()
+
+
+def hamming_radius_match(dt1, dt2, maxDistance, options={}):
+    """ cv2.BFMatcher(NORM_HAMMING).radiusMatch(dt1, dt2, maxDistance): a list of DMatch lists, one per query row """
+    off, idx, dist = hamming_radius_match_arrays(dt1, dt2, maxDistance, options=options)
     return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
 
 

@@ -22,6 +22,10 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
   < r per query row (``cv2.BFMatcher.radiusMatch``), row i's list at ``offsets[i]:offsets[i + 1]``, ascending (distance, index).
   ``r`` is a Python or NumPy scalar, or a float32 CUDA tensor ``[nq]`` of one radius per query row on the context's device
   (``tau * selfdist`` as it comes out of a kernel), read in place (``fm_radius_match_dev``).
+* ``hamming_radius_match(q, t, r)`` -> the same three tensors for BINARY descriptors (uint8 CUDA tensors of 1 .. 64 packed
+  bytes per row, or binary ``Bank``s): every train row with ``popcount(q XOR t) < r`` (strict, float32 -- ``h <= H`` is
+  ``r = H + 0.5``), ascending (h, index); ``r`` as in ``radius_match`` (``fm_hamming_radius_match_dev``).  ``radius_match``
+  itself stays the L2 call.
 
 * ``Collection(context=None)`` -- a train collection (``cv2.BFMatcher.add`` / ``train``) whose images are CUDA tensors: the
   retrieval flow extract -> ``add`` to the database -> query -> consume without a copy to the host.  A context manager.
@@ -30,6 +34,7 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
   image]`` per added image, ``None`` entries permit everything -- cv2's ``knnMatch(q, k, masks=[...])``; or a resident
   ``_ffi.Mask`` from ``Collection.mask``); ``ratio_match(q, tau)`` -> ``(qidx, img, tidx, dist)``;
   ``radius_match(q, r)`` -> ``(offsets, img, idx, dist)``, ``r`` as in the module's ``radius_match``;
+  ``hamming_radius_match(q, r)`` -> the same against a binary collection (``fm_collection_hamming_radius_match_dev``);
   ``fast_match_each(q, tau, cap=None)`` -> ``(rows int32 [n_images, cap, 3], counts int64 [n_images])``, the accepted-match
   test inside every image (``q``: a ``Bank`` carrying self distances, ``Context.self_dist_batch([q], want_host=False)``);
   ``mutual_nn_each(q, max_dist=None, cap=None)`` -> the same two tensors for the cross-checked 1-NN inside every image
@@ -331,6 +336,47 @@ def radius_match(q, t, r):
             b.close()
 
 
+def _binary_operand(who, x):
+    """A binary bank as it is, or a checked uint8 tensor of 1 .. 64 bytes per row -- ValueError before the library is touched."""
+    if isinstance(x, _ffi.Bank):
+        if x.kind != _ffi.FM_BANK_BIN:
+            raise ValueError("%s takes binary banks (bank(tensor, binary=True)); radius_match is the L2 call" % who)
+        return x
+    t, _ = _checked(x, binary=True)
+    if t.shape[1] > 64:
+        raise ValueError("%s: binary descriptors have 1 .. 64 bytes per row, got %d" % (who, t.shape[1]))
+    return t
+
+
+def hamming_radius_match(q, t, r):
+    """``cv2.BFMatcher(NORM_HAMMING).radiusMatch`` on binary descriptors: ``(offsets int64 [nq + 1], idx int32 [n], dist
+    float32 [n])`` CUDA tensors, every train row with ``popcount(q XOR t) < r`` per query row (strict, float32: ``h <= H`` is
+    ``r = H + 0.5``), ascending (h, train index).  ``q`` / ``t``: uint8 CUDA tensors of packed bits or binary ``Bank``s;
+    ``r`` as in ``radius_match``.  One host wait for the total."""
+    who = "hamming_radius_match"
+    ops = [_binary_operand(who, x) for x in (q, t)]
+    widths = [x.dim if isinstance(x, _ffi.Bank) else x.shape[1] for x in ops]
+    if widths[0] != widths[1]:
+        raise ValueError("%s: %d bytes per query row, %d per train row" % (who, widths[0], widths[1]))
+    nq = ops[0].n if isinstance(ops[0], _ffi.Bank) else ops[0].shape[0]
+    ctx = next((x.ctx for x in ops if isinstance(x, _ffi.Bank)), None)
+    rad, r_all = _radius(r, nq, ctx.device if ctx is not None else ops[0].device.index)
+    made, banks = [], []
+    try:
+        for x in ops:
+            if not isinstance(x, _ffi.Bank):
+                x = bank(x, binary=True, context=ctx)
+                ctx = x.ctx
+                made.append(x)
+            banks.append(x)
+        qb, tb = banks
+        stream, dev = _stream_and_device(qb.ctx)
+        return _radius_lists(lambda *a, **k: qb.ctx.hamming_radius_match_dev(qb, tb, *a, **k), qb.n, rad, r_all, stream, dev, False)
+    finally:
+        for b in made:
+            b.close()
+
+
 class Collection(object):
     """A train collection fed from CUDA tensors (module docstring).  The library's collection is made with the first call
     that needs it, on ``context`` or the default context of the first tensor's device."""
@@ -496,6 +542,25 @@ class Collection(object):
         finally:
             for b in made:
                 b.close()
+
+    def hamming_radius_match(self, q, r):
+        """``radius_match`` of binary descriptors against a binary collection (``add(tensor, binary=True)``): every row of the
+        stacked images with ``popcount(q XOR t) < r`` per query row, ``(offsets, img, idx, dist)`` ascending (h, image, row
+        inside the image).  ``q``: a uint8 CUDA tensor of packed bits or a binary ``Bank``; ``r`` as in the module's
+        ``radius_match``.  One host wait for the total."""
+        self._refuse_wide_collection("hamming_radius_match")
+        x = _binary_operand("Collection.hamming_radius_match", q)
+        is_bank = isinstance(x, _ffi.Bank)
+        nq, device = (x.n, x.ctx.device) if is_bank else (x.shape[0], x.device.index)
+        rad, r_all = _radius(r, nq, device if self._context is None else self._context.device)
+        coll = self._collection(x.ctx if is_bank else _ctx_for(x, self._context))
+        qb = x if is_bank else bank(x, binary=True, context=self._context)
+        try:
+            stream, dev = _stream_and_device(qb.ctx)
+            return _radius_lists(lambda *a, **k: coll.hamming_radius_match_dev(qb, *a, **k), qb.n, rad, r_all, stream, dev, True)
+        finally:
+            if not is_bank:
+                qb.close()
 
     def fast_match_each(self, q, tau, cap=None):
         """Fast-Match's accepted-match test of ``q`` inside every image separately, left on the device: ``(rows int32

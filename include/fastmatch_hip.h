@@ -59,7 +59,8 @@ typedef struct fm_bank fm_bank;
  * "masked_mfma", "mask_pack_words"; still revision 12, additions only -- FM_BANK_F32W: the float creators take
  * 129 <= dim <= 256; still revision 12, additions only -- fm_collection_pairs_mutual_ratio,
  * fm_collection_pairs_mutual_ratio_dev; still revision 12, additions only -- fm_collection_add_wide,
- * fm_collection_add_wide_dev).  A binding compares
+ * fm_collection_add_wide_dev; still revision 12, additions only -- fm_hamming_radius_match, fm_hamming_radius_match_dev,
+ * fm_collection_hamming_radius_match, fm_collection_hamming_radius_match_dev).  A binding compares
  * fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.                      */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -201,11 +202,14 @@ int  fm_bank_create_f32_route(fm_ctx* ctx, const float* rows, int64_t n, int dim
  *   fm_knn2_ratio: the classic ratio match as for L2, d0 / d1 < tau in float64, d1 == 0 rejected (frequent: duplicate rows).
  * k = 1, 2 and crossCheck run on the matrix cores: every bit an FP4 value +1 / -1 (padding 0), the dot product of two rows is
  * W - 2 h, exact in the f32 accumulator of v_mfma_scale_f32_16x16x128_f8f6f4 (hamming.hip); k = 3 .. 8: vector ALUs (XOR +
- * popcount).  Every other entry point that takes a bank refuses a binary one with FM_EUNSUPPORTED before any kernel reads it:
- * fm_radius_match, fm_self_dist(_batch), fm_bank_set_selfdist, fm_match_ratio, fm_match_accepted*, fm_xcheck1_keys*,
+ * popcount).
+ *   fm_hamming_radius_match(_dev), fm_collection_hamming_radius_match(_dev): radiusMatch on binary banks -- "Hamming radiusMatch"
+ *     below, behind fm_radius_match.
+ * Every other entry point that takes a bank refuses a binary one with FM_EUNSUPPORTED before any kernel reads it:
+ * fm_radius_match(_dev) (the L2-named radius calls keep refusing: fm_hamming_radius_match is the call), fm_self_dist(_batch), fm_bank_set_selfdist, fm_match_ratio, fm_match_accepted*, fm_xcheck1_keys*,
  * fm_xcheck1_batched, fm_bank_refill_u8_async, fm_bank_append_*, fm_expand_create.  A binary bank paired with a non-binary one
- * is FM_EINVAL, even when one of them is empty.  Not built: NORM_HAMMING2, Hamming radiusMatch, binary descriptors in the
- * Fast-Match loop itself (self distances, fm_expand_*, batches, sharded keys), k > 8.                                    */
+ * is FM_EINVAL, even when one of them is empty.  Not built: NORM_HAMMING2, masked Hamming radius queries, binary descriptors
+ * in the Fast-Match loop itself (self distances, fm_expand_*, batches, sharded keys), k > 8.                                    */
 int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t n, int bytes, fm_bank** bank);
 /* ---- K14: wide float banks, 129 .. 256 values per row ---------------------------------------------------------------------
  * The 256-D float descriptors of learned extractors (SuperPoint and its kin).  fm_bank_create_f32, fm_bank_create_f32_route and
@@ -321,6 +325,27 @@ int  fm_knn(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k,
 int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* radius /*[nq] or NULL*/,
                     float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* idx, float* dist,
                     int64_t* n_total);
+/* ---- Hamming radiusMatch ---------------------------------------------------------------------------------------------
+ * cv2.BFMatcher(cv2.NORM_HAMMING).radiusMatch on two binary banks (FM_BANK_BIN, K11): "every database row within 50 bits of
+ * this one".  fm_radius_match and its kin keep refusing binary banks; these four calls, with the signatures of the four
+ * L2 radius calls, are the ones that serve them.
+ *   h(q, t) = popcount(q XOR t) over the banks' `bytes` bytes, W = 8 * bytes, dist = (float)h, exact (K11's contract).
+ *   r_i = radius[i] (radius != NULL) or radius_all, float32.  Train row j is in row i's list iff (float)h(i, j) < r_i, a STRICT
+ *   float32 compare -- fm_radius_match's rule.  Distances are integers, so an inclusive threshold h <= H is r = H + 0.5f.
+ *   r <= 0 or NaN: an empty list; r = +inf, or any r > W: every real row.  A list ascends by (h, train index).
+ *   offsets / cap / counts-only / longest-prefix-of-whole-rows / *n_total: fm_radius_match's rules, word for word; nq = 0 and
+ *   nt = 0 give all-zero offsets.  No option changes a result; "radius_ws_bytes" keeps its meaning (24 bytes a candidate).
+ * One FP4 matrix-core sweep (radius.hip, radius_ham_kernel): K11's operands and K11's double-buffered 128-row loop with a
+ * threshold epilogue on the raw dot product W - 2 h -- a hit is dot >= W - 2 H_i, H_i the largest integer below r_i
+ * (csrc/ham_radius.h); a count sweep, a scan, a fill sweep that writes (float bits of h << 32 | row) keys, K10's segment sort
+ * and compaction.  Padding rows (all-zero FP4 rows: h = W / 2 from everything, inside any r > W / 2) are kept out by INDEX.
+ * Errors, in this order: NULL handles (check_pair's checks, as in fm_knn2); a bank that is not FM_BANK_BIN (FM_EINVAL, even when it is empty;
+ * fm_radius_match is the L2 call); widths that differ (FM_EINVAL); cap < 0; offsets NULL; idx or dist NULL with cap > 0
+ * (FM_EINVAL).  Accounted in fm_stats like fm_radius_match, pairs = nq * nt.
+ * fm_collection_hamming_radius_match and the _dev forms: with the collections and the device entry points below.          */
+int fm_hamming_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* radius /*[nq] or NULL*/,
+                            float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* idx, float* dist,
+                            int64_t* n_total);
 
 /* ---- train collections: one query against many images ------------------------------------------------------------------
  * cv2.BFMatcher.add([d1, d2, ...]) / train() / clear() and then match(query) / knnMatch(query, k) against ALL added images,
@@ -485,8 +510,17 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  *     keeps its meaning; a candidate takes 28 bytes here (24 for a pair: + img).  Errors, in fm_collection_knn's order: NULL
  *     handles; a query of another kind or width (FM_EINVAL; as in fm_radius_match a query bank with no rows is not held to
  *     the kind: every creator makes an empty bank an integer-route one); a float32-route query with a finite magnitude above
- *     FM_COLLECTION_F32_MAX (FM_EUNSUPPORTED); a binary collection (FM_EUNSUPPORTED); cap < 0, offsets NULL, or img / idx /
+ *     FM_COLLECTION_F32_MAX (FM_EUNSUPPORTED); a binary collection (FM_EUNSUPPORTED: fm_collection_hamming_radius_match serves it); cap < 0, offsets NULL, or img / idx /
  *     dist NULL with cap > 0 (FM_EINVAL).  Accounted in fm_stats like fm_radius_match, pairs = nq * real rows.
+ *   fm_collection_hamming_radius_match: fm_hamming_radius_match(q, T, ...) for T = the stacked rows of a BINARY collection --
+ *     "Hamming radiusMatch" above is the contract ((float)h < r_i strict, r <= 0 or NaN nothing, r = +inf or r > W every real
+ *     row, no option changes a result), fm_collection_radius_match's the output: img beside idx and dist, a list ascends by
+ *     (h, img, row inside the image), the offsets / cap / counts-only / prefix rules word for word; an empty collection, nq = 0
+ *     and a collection of empty images give all-zero offsets.  The padding rows behind every image are all-zero FP4 rows at
+ *     h = W / 2 and WOULD pass any r > W / 2: they are masked by index with the per-stage real-row table, never by value.  A
+ *     candidate takes 28 bytes of "radius_ws_bytes".  Errors: fm_collection_radius_match's handle, kind, width checks (an empty
+ *     collection takes any binary query); then a query bank or a collection that is not binary (FM_EINVAL); then cap < 0,
+ *     offsets NULL, or img / idx / dist NULL with cap > 0 (FM_EINVAL).  Accounted in fm_stats, pairs = nq * real rows.
  *   fm_collection_add_dev, fm_collection_knn_dev, fm_collection_knn2_ratio_dev, fm_collection_radius_match_dev: images from,
  *     and stacked results into, DEVICE memory -- described with the other device entry points below ("descriptors already on
  *     the GPU").
@@ -494,8 +528,10 @@ int fm_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float
  * crossCheck -- recalled; neither cv2 nor its source was at hand; the per-image form is built:
  * fm_collection_xcheck1_each), a single reverse K8 sweep
  * over a float32-route stack (its padding output rows would flood the filter's candidate lists: fm_collection_xcheck1_each
- * and fm_collection_match_accepted_each sweep image by image there), Hamming radiusMatch (for pairs or collections), radius queries per
- * image separately (an _each form), skipping the second count sweep of the counts-then-fill pattern,
+ * and fm_collection_match_accepted_each sweep image by image there), Hamming radiusMatch (for pairs or collections) THROUGH THE
+ * L2-NAMED CALLS -- fm_radius_match(_dev) and fm_collection_radius_match(_dev) keep refusing binary data; fm_hamming_radius_match(_dev)
+ * and fm_collection_hamming_radius_match(_dev) are the entry points that serve it --, NORM_HAMMING2, radius queries per
+ * image separately (an _each form, L2 or Hamming), skipping the second count sweep of the counts-then-fill pattern,
  * masks anywhere but in knnMatch (fm_collection_knn_masked is built; "masks" below lists what is not),
  * the expansion loop on a collection, a batched K8 / K11 (float32 / binary) per-image sweep,
  * binary collections in the self-distance test, sharding a collection across GPUs (radius queries included), removing single
@@ -531,6 +567,9 @@ int  fm_collection_votes(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, dou
 int  fm_collection_radius_match(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const float* radius /*host [nq] or NULL*/,
                                 float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* img, int32_t* idx, float* dist,
                                 int64_t* n_total);
+int  fm_collection_hamming_radius_match(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const float* radius /*host [nq] or NULL*/,
+                                        float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* img, int32_t* idx,
+                                        float* dist, int64_t* n_total);
 int  fm_collection_match_accepted_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
                                        int32_t* qidx, int32_t* tidx, float* dist, double* ratio /* each [n_images][cap] */,
                                        int64_t* n_accepted /*[n_images]: the full count per image*/);
@@ -638,6 +677,10 @@ int  fm_collection_pairs_mutual_ratio_dev(fm_ctx* ctx, fm_collection* coll, cons
  *   Host synchronisation: the call DOES synchronise -- the counts are read back to plan the chunks and the segment sort (per
  *   chunk on the float32 route), as in the host forms; what it spares is the radii going up and the lists coming down.  The
  *   other errors are the host forms', in their order.  Not accounted in fm_stats.
+ * fm_hamming_radius_match_dev, fm_collection_hamming_radius_match_dev: the same device forms of fm_hamming_radius_match and
+ *   fm_collection_hamming_radius_match -- d_radius read in place, d_offsets always written, the lists at their final offsets
+ *   for the rows that fit in cap; pointer checks (after the host forms' errors), stream ordering, *n_total and the host
+ *   synchronisation exactly as in fm_radius_match_dev.  Not accounted in fm_stats.
  * Not built: device sources for fm_bank_refill_u8_async and fm_bank_append_*; device results for
  *   fm_self_dist (fm_self_dist_batch attaches them on the device already) and for fm_collection_knn2_each / _votes; an
  *   enqueue-only float32 route; tensors on another GPU than the context's (copy them over first).                          */
@@ -670,6 +713,13 @@ int  fm_collection_radius_match_dev(fm_ctx* ctx, fm_collection* coll, const fm_b
                                     float radius_all, int64_t cap, int64_t* d_offsets /*device [nq+1]*/, int32_t* d_img,
                                     int32_t* d_idx, float* d_dist, int64_t* n_total /*host, or NULL*/,
                                     void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_hamming_radius_match_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* d_radius /*device [nq] or NULL*/,
+                                 float radius_all, int64_t cap, int64_t* d_offsets /*device [nq+1]*/, int32_t* d_idx, float* d_dist,
+                                 int64_t* n_total /*host, or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_hamming_radius_match_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const float* d_radius /*device [nq] or NULL*/,
+                                            float radius_all, int64_t cap, int64_t* d_offsets /*device [nq+1]*/, int32_t* d_img,
+                                            int32_t* d_idx, float* d_dist, int64_t* n_total /*host, or NULL*/,
+                                            void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* ---- masks: knnMatch(q, t, k, mask) and knnMatch(q, k, masks = [...]) (K13, csrc/masked.hip) --------------------------------
  * cv2's mask argument: a CV_8U [nq][nt] matrix, nonzero = the pair (query row, train row) may be matched; for a train
