@@ -174,6 +174,12 @@ SYMBOLS = {
     # wide collections (K14): images of 129 .. 256 float values per row, served by fm_collection_pairs_mutual_ratio(_dev)
     "fm_collection_add_wide": (_INT, [_P, _P, _P, _I64, _INT, ctypes.POINTER(_I32)]),
     "fm_collection_add_wide_dev": (_INT, [_P, _P, _P, _INT, _I64, _INT, _I64, _P, ctypes.POINTER(_I32)]),
+    # a wide query bank against every image of a wide collection
+    "fm_collection_wide_knn2_each": (_INT, [_P, _P, _P, _P, _P]),
+    "fm_collection_wide_mutual_ratio_each": (_INT, [_P, _P, _P, ctypes.c_double, ctypes.c_int32, _I64, _P, _P, _P, _P, _P,
+                                                    ctypes.POINTER(_I64)]),
+    "fm_collection_wide_mutual_ratio_each_dev": (_INT, [_P, _P, _P, ctypes.c_double, ctypes.c_int32, _I64, _P, _P,
+                                                        ctypes.POINTER(_I64), _P]),
     "fm_collection_knn_dev": (_INT, [_P, _P, _P, _I32, _P, _P, _P, _P]),
     "fm_collection_knn2_ratio_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
     "fm_collection_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
@@ -538,7 +544,8 @@ class Collection(object):
     def add_wide(self, rows):
         """Append one WIDE image ([n, dim] float32, 129 <= dim <= 256, any values; n may be 0) -- ``fm_collection_add_wide``.
         The first one makes the collection a wide one (kind ``FM_BANK_F32W``): it takes no other images and serves ``info``,
-        ``image_rows``, ``train``, ``clear`` and the ``pairs_mutual_ratio*`` calls.  Returns the image's index."""
+        ``image_rows``, ``train``, ``clear``, the ``pairs_mutual_ratio*`` calls and, for a wide query bank, ``wide_knn2_each``
+        and the ``wide_mutual_ratio_each*`` calls.  Returns the image's index."""
         a = np.ascontiguousarray(rows, dtype=np.float32)
         if a.ndim != 2:
             raise ValueError("an image's descriptors must be 2-D [n, dim]")
@@ -884,6 +891,62 @@ class Collection(object):
         total = _I64(0)
         self.ctx._check(self.ctx.lib.fm_collection_pairs_mutual_ratio_dev(
             self.ctx.handle, self.handle, _ptr(arr), n, float(tau), int(bool(symmetric)), int(cap),
+            _P(int(offsets_ptr)) if offsets_ptr else None, _P(int(rows_ptr)) if rows_ptr else None,
+            ctypes.byref(total) if want_total else None, _stream_arg(consumer_stream)))
+        return int(total.value) if want_total else None
+
+    def wide_knn2_each(self, q):
+        """``fm_collection_wide_knn2_each``: a wide query bank against every image of a wide collection -- (idx, dist)
+        [n_images, nq, 2], slot i equal to ``Context.knn2(q, bank(image_i))``."""
+        ni = self.info()[0]
+        idx = np.empty((ni, q.n, 2), np.int32)
+        dist = np.empty((ni, q.n, 2), np.float32)
+        self.ctx._check(self.ctx.lib.fm_collection_wide_knn2_each(self.ctx.handle, self.handle, q.handle,
+                                                                  _ptr(idx) if idx.size else None, _ptr(dist) if dist.size else None))
+        return idx, dist
+
+    def wide_mutual_ratio_each_counts(self, q, tau, symmetric=False):
+        """int64[n_images + 1]: the offsets of ``wide_mutual_ratio_each`` alone (its counts-only call, cap = 0) -- the number
+        of matches of image i is ``offsets[i + 1] - offsets[i]``, the per-image votes."""
+        offsets = np.zeros(self.info()[0] + 1, np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_wide_mutual_ratio_each(
+            self.ctx.handle, self.handle, q.handle, float(tau), int(bool(symmetric)), 0, _ptr(offsets), None, None, None, None, None))
+        return offsets
+
+    def wide_mutual_ratio_each(self, q, tau, symmetric=False, cap=None):
+        """``fm_collection_wide_mutual_ratio_each``: a wide query bank matched against every image of a wide collection,
+        image by image.  A list of (qidx, tidx, dist, ratio) per image, entry i equal to
+        ``Context.mutual_ratio(q, bank(image_i), tau, symmetric)``: ``qidx`` is the query row, ``tidx`` the row inside image
+        i.  ``cap`` None: the counts first, then one fill call of exactly that size; else the rows of the longest prefix of
+        whole images that fits are returned and the later images come back empty."""
+        n = self.info()[0]
+        if cap is None:
+            cap = int(self.wide_mutual_ratio_each_counts(q, tau, symmetric)[-1])
+        cap = int(cap)
+        kept = max(cap, 0)
+        qidx, tidx = np.empty(kept, np.int32), np.empty(kept, np.int32)
+        dist, ratio = np.empty(kept, np.float32), np.empty(kept, np.float64)
+        offsets = np.zeros(n + 1, np.int64)
+        self.ctx._check(self.ctx.lib.fm_collection_wide_mutual_ratio_each(
+            self.ctx.handle, self.handle, q.handle, float(tau), int(bool(symmetric)), cap,
+            _ptr(offsets), _ptr(qidx) if kept else None, _ptr(tidx) if kept else None, _ptr(dist) if kept else None,
+            _ptr(ratio) if kept else None, None))
+        out = []
+        for p in range(n):
+            lo, hi = int(offsets[p]), int(offsets[p + 1])
+            if hi > kept:
+                lo = hi = 0
+            out.append((qidx[lo:hi], tidx[lo:hi], dist[lo:hi], ratio[lo:hi]))
+        return out
+
+    def wide_mutual_ratio_each_dev(self, q, tau, symmetric, offsets_ptr, rows_ptr, cap, want_total=False, consumer_stream=None):
+        """``wide_mutual_ratio_each`` with device outputs (``fm_collection_wide_mutual_ratio_each_dev``): ``offsets_ptr`` =
+        device address of an int64 [n_images + 1] array, ``rows_ptr`` of an int32 [cap, 3] block (query row, row inside the
+        image, float32 distance bits).  Enqueued only; ``want_total``: also return the total number of matches (the call's
+        one host wait)."""
+        total = _I64(0)
+        self.ctx._check(self.ctx.lib.fm_collection_wide_mutual_ratio_each_dev(
+            self.ctx.handle, self.handle, q.handle, float(tau), int(bool(symmetric)), int(cap),
             _P(int(offsets_ptr)) if offsets_ptr else None, _P(int(rows_ptr)) if rows_ptr else None,
             ctypes.byref(total) if want_total else None, _stream_arg(consumer_stream)))
         return int(total.value) if want_total else None

@@ -35,7 +35,9 @@ using namespace fm;
 // value, no kernel changed.  Binary: rowsb / rows4; an all-zero FP4 row is at W / 2 from everything, so K11
 // masks by INDEX: its sweep and its vector-ALU kernel take the per-stage real-row table (stage_real).
 // A fourth kind, wide (FM_BANK_F32W, fm_collection_add_wide: coll_add_wide below), masks by INDEX as well and serves the
-// match graph alone (fm_collection_pairs_mutual_ratio); every call that takes a query bank refuses it (coll_refuse_wide).
+// match graph (fm_collection_pairs_mutual_ratio) and, under names of their own, a wide query bank image by image
+// (fm_collection_wide_mutual_ratio_each, fm_collection_wide_knn2_each: the end of this file); every other call that takes a
+// query bank refuses it (coll_refuse_wide).
 constexpr int kCollPadNorm = 1 << 26;
 constexpr float kCollPadF32 = 1.0e18f;           // 128 * (1e18 + kCollF32Max)^2 = 1.7e38 stays finite in float32
 // Masking by value holds while a padding row is farther from every query row than every real row is.  With all finite
@@ -779,7 +781,8 @@ static int coll_refuse_wide(fm_ctx* ctx, const fm_collection* c, const char* who
 {
     if (!coll_is_wide(c)) return FM_OK;
     return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": a wide collection (fm_collection_add_wide, FM_BANK_F32W) is served by "
-                                      "fm_collection_pairs_mutual_ratio(_dev) only");
+                                      "fm_collection_pairs_mutual_ratio(_dev) and, for a wide query bank, by "
+                                      "fm_collection_wide_mutual_ratio_each(_dev) / fm_collection_wide_knn2_each only");
 }
 
 extern "C" int fm_collection_train(fm_ctx* ctx, fm_collection* c)
@@ -2254,6 +2257,9 @@ struct CollPairsArgs {
     int64_t* offsets; int32_t* qidx; int32_t* tidx; float* dist; double* ratio;     // host form
     bool to_dev; int64_t* d_offsets; int32_t* d_rows; void* consumer;               // device form
     int64_t* n_total;
+    // fm_collection_wide_*_each: "pair" p is (q, image p) -- a is the wide query bank, outside the stack -- for every image;
+    // knn2: the forward slots alone, their merged lists [n_images][nq][2] copied to k_idx / k_dist (host), no join
+    const fm::Bank* q = nullptr; bool knn2 = false; int32_t* k_idx = nullptr; float* k_dist = nullptr;
 };
 
 // One chunk of consecutive pairs [p0, p1): what its kernels cover and where its tables lie in the call's table image.
@@ -2276,15 +2282,20 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
     int rc = coll_check(ctx, c, a.who);
     if (rc != FM_OK) return rc;
     const int64_t ni = (int64_t)c->rows.size(), cap = a.cap;
+    const bool qm = a.q != nullptr;                 // (the caller has checked q and passes pairs = NULL, n_pairs = n_images)
+    const int64_t nq = qm ? a.q->n : 0;
     if (n_pairs < 0) return fail(ctx, FM_EINVAL, who + ": n_pairs < 0");
-    if (!pairs && n_pairs != ni * (ni - 1) / 2)
+    if (!qm && !pairs && n_pairs != ni * (ni - 1) / 2)
         return fail(ctx, FM_EINVAL, who + ": pairs is NULL (every i < j) and n_pairs is not n_images (n_images - 1) / 2");
     if (n_pairs > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, who + ": n_pairs exceeds 2^31 - 1");
     for (int64_t p = 0; pairs && p < n_pairs; ++p)
         if (pairs[2 * p] < 0 || pairs[2 * p] >= ni || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= ni)
             return fail(ctx, FM_EINVAL, who + ": pair " + std::to_string(p) + " names an image outside [0, n_images)");
     if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap is negative");
-    if (a.to_dev) {
+    if (a.knn2) {
+        if (ni * nq > 0 && (!a.k_idx || !a.k_dist)) return fail(ctx, FM_EINVAL, who + ": idx / dist is NULL");
+        if (ni * nq == 0) return FM_OK;
+    } else if (a.to_dev) {
         if (!a.d_offsets) return fail(ctx, FM_EINVAL, who + ": d_offsets is NULL");
         if (cap > 0 && !a.d_rows) return fail(ctx, FM_EINVAL, who + ": d_rows is NULL with cap > 0");
     } else {
@@ -2309,7 +2320,7 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
     // the pairs, in order (NULL: every i < j, lexicographic)
     std::vector<int32_t> all;
     try {
-        if (!pairs) {
+        if (!pairs && !qm) {
             all.reserve((size_t)n_pairs * 2);
             for (int32_t i = 0; i < (int32_t)ni; ++i) for (int32_t j = i + 1; j < (int32_t)ni; ++j) { all.push_back(i); all.push_back(j); }
             pairs = all.data();
@@ -2320,9 +2331,14 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
     // launch + ONE rescoring + ONE guarded exact launch (or the exact launch alone) and merged by one launch, whatever the
     // number of pairs.  ws_partial: partial [rows][2] | count | bounds [rows] | records | their scores, of one chunk.
     const bool wide = coll_is_wide(c);
-    const bool wide_filter_on = wide && ctx->tune.f32_filter != 0 && ctx->d_counters && c->stack.filt_ok && c->stack.wrowsh;
+    const bool wide_filter_on = wide && ctx->tune.f32_filter != 0 && ctx->d_counters && c->stack.filt_ok && c->stack.wrowsh &&
+                                (!qm || wide_filter_usable(*a.q, c->stack));
     size_t max_cap = 0;
-    auto live = [&](int64_t p) { return c->rows[(size_t)pairs[2 * p]] > 0 && c->rows[(size_t)pairs[2 * p + 1]] > 0; };
+    // rows of the pair's two sides: a = the output rows of its forward slot, b = of its reverse slot
+    auto rows_a = [&](int64_t p) { return qm ? nq : c->rows[(size_t)pairs[2 * p]]; };
+    auto rows_b = [&](int64_t p) { return qm ? c->rows[(size_t)p] : c->rows[(size_t)pairs[2 * p + 1]]; };
+    auto live = [&](int64_t p) { return rows_a(p) > 0 && rows_b(p) > 0; };
+    const int ndir = a.knn2 ? 1 : 2;                // sweeps per live pair
     // Plans of the integer route: the batched shape, every slot under the plan of its own sizes.  Splits exist to fill the
     // chip from ONE pair; a call whose slots fill it without them takes one split per slot (no shared bounds, the smallest
     // partials).
@@ -2389,21 +2405,22 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
             size_t need = 0, part = 0, bound = 0, fix = 0;
             int64_t wg = 0, mb = 0, jb = 0, ra = 0, rb = 0;
             if (live(p)) {
-                const int ia = pairs[2 * p], ib = pairs[2 * p + 1];
-                ra = c->rows[(size_t)ia]; rb = c->rows[(size_t)ib];
+                ra = rows_a(p); rb = rows_b(p);
                 if (i8) {
+                    const int ia = pairs[2 * p], ib = pairs[2 * p + 1];
                     const SlotPlan f = slot_plan(ia, ib), r = slot_plan(ib, ia);
                     part = f.part + r.part; bound = f.bound + r.bound; fix = f.fix + r.fix;
                     wg = (int64_t)rowreduce_grid(f.pl) + rowreduce_grid(r.pl);
                     mb = (ra + 255) / 256 + (rb + 255) / 256;
                 }
                 if (wide) {
-                    const int64_t pr = pad128(ra) + pad128(rb);
-                    part = (size_t)pr * 16; bound = (size_t)pr * 4; fix = wide_filter_on ? (size_t)(ra + rb) * 256 * 12 : 0;
+                    const int64_t rr = a.knn2 ? 0 : rb;             // output rows of the reverse slot
+                    const int64_t pr = pad128(ra) + (rr ? pad128(rr) : 0);
+                    part = (size_t)pr * 16; bound = (size_t)pr * 4; fix = wide_filter_on ? (size_t)(ra + rr) * 256 * 12 : 0;
                     wg = pr / kStageRows;
-                    mb = (ra + 255) / 256 + (rb + 255) / 256;
+                    mb = (ra + 255) / 256 + (rr + 255) / 256;
                 }
-                jb = (ra + 255) / 256;
+                jb = a.knn2 ? 0 : (ra + 255) / 256;
                 need = part + bound + fix + (size_t)(ra + rb) * 16 + (size_t)ra * 17 + (size_t)jb * 12;
             }
             // (the grids are int32, the tables count slots in int32)
@@ -2415,10 +2432,11 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
             if (wide && wg * kStageRows > 0x3fffffff) return fail(ctx, FM_EUNSUPPORTED, who + ": one pair of a wide collection has more than 2^30 rows");
             used += need;
             if (ra > 0 && rb > 0) {
-                ch.nslots += 2; ch.wg += wg; ch.mblocks += mb; ch.jblocks += jb; ch.entries += ra; ch.lists += ra + rb;
+                ch.nslots += ndir; ch.wg += wg; ch.mblocks += mb; ch.jblocks += jb; ch.entries += a.knn2 ? 0 : ra;
+                ch.lists += a.knn2 ? ra : ra + rb;
                 ch.part += part; ch.bound += bound; ch.fix += wide ? 0 : fix;
-                if (wide) { ch.wrows += wg * kStageRows; ch.work += 2.0 * (double)ra * (double)rb; }
-                sum_entries += ra;
+                if (wide) { ch.wrows += wg * kStageRows; ch.work += (double)ndir * (double)ra * (double)rb; }
+                sum_entries += a.knn2 ? 0 : ra;
             }
         }
         close(n_pairs);
@@ -2428,6 +2446,7 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
     const int64_t ccap = a.to_dev ? 0 : std::min<int64_t>(cap, sum_entries);
     size_t off = 0;
     const size_t o_off = carve(off, ((size_t)n_pairs + 1) * 8), o_carry = carve(off, 16);
+    if (a.knn2) max_lists = ni * nq;               // the lists ARE the result: every image's, [n_images][nq][2]
     const size_t o_li = carve(off, (size_t)max_lists * 8), o_ld = carve(off, (size_t)max_lists * 8);
     const size_t o_tidx = carve(off, (size_t)max_entries * 4), o_dist = carve(off, (size_t)max_entries * 4), o_ratio = carve(off, (size_t)max_entries * 8);
     const size_t o_pass = carve(off, (size_t)max_entries), o_bc = carve(off, (size_t)max_jblocks * 4), o_bb = carve(off, (size_t)max_jblocks * 8);
@@ -2476,9 +2495,9 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
             s = PairsJoinSlot{};
             jb0[j] = jb;
             if (!live(p)) continue;
-            const int ia = pairs[2 * p], ib = pairs[2 * p + 1];
-            const int64_t ra = c->rows[(size_t)ia], rb = c->rows[(size_t)ib];
-            s.fwd = list; s.rev = list + ra; s.e0 = entry; s.nq = (int32_t)ra; s.nt = (int32_t)rb;
+            const int ia = qm ? -1 : pairs[2 * p], ib = qm ? (int)p : pairs[2 * p + 1];
+            const int64_t ra = rows_a(p), rb = rows_b(p);
+            s.fwd = a.knn2 ? p * nq : list; s.rev = list + ra; s.e0 = entry; s.nq = (int32_t)ra; s.nt = (int32_t)rb;
             for (int dir = 0; i8 && dir < 2; ++dir) {
                 const int io = dir ? ib : ia, ir = dir ? ia : ib;
                 const fm::Bank vo = coll_view(c, io), vr = coll_view(c, ir);
@@ -2497,12 +2516,18 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
                 wg += g; mb += (int)((vo.n + 255) / 256);
                 ++slot;
             }
-            for (int dir = 0; wide && dir < 2; ++dir) {
-                const int io = dir ? ib : ia, ir = dir ? ia : ib;
-                const int64_t no = c->rows[(size_t)io], nr = c->rows[(size_t)ir];
+            for (int dir = 0; wide && dir < ndir; ++dir) {
+                const int io = dir ? ib : ia, ir = dir ? ia : ib;           // (-1: the query bank, whose first row is 0)
+                const int64_t no = dir ? rb : ra, nr = dir ? ra : rb;
                 WideSlot& w = wsl[slot];
-                w.col0 = (int)c->phys[(size_t)io]; w.ncols = (int)no;
-                w.red0 = (int)c->phys[(size_t)ir]; w.nred = (int)nr;
+                w.col0 = io < 0 ? 0 : (int)c->phys[(size_t)io]; w.ncols = (int)no;
+                w.red0 = ir < 0 ? 0 : (int)c->phys[(size_t)ir]; w.nred = (int)nr;
+                // the slot's scale terms (launch_wide_filter's): the stack's scale is read here, at the call -- a later add may
+                // lift it -- the query's was fixed at its creation
+                const int dk = !qm ? 0 : dir ? a.q->kscale - c->stack.kscale : c->stack.kscale - a.q->kscale;      // kred - kcol
+                w.outside = !qm ? 0 : dir ? kWideOutRed : kWideOutCols;
+                w.cscale = ldexpf(1.f, dk); w.nscale = ldexpf(1.f, 2 * dk);
+                w.red_nm_max = (qm && dir) ? a.q->nm_max : c->stack.nm_max;
                 const WideFilterPlan fp = plan_wide_filter(pad128(no), no, pad128(nr), ctx->tune);
                 w.ntiles = fp.ntiles;
                 w.nsplit = one_split ? 1 : fp.nsplit;
@@ -2516,6 +2541,7 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
                 wg += fp.nchunks * w.nsplit; wrow += (int)pad128(no); mb += (int)((no + 255) / 256);
                 ++slot;
             }
+            if (a.knn2) continue;
             list += ra + rb; entry += ra; jb += (int)((ra + 255) / 256);
         }
         if (wide && ch.nslots > 0) { ww0[ch.nslots] = wg; wr0[ch.nslots] = wrow; mb0[ch.nslots] = mb; ch.fwg = wg; }
@@ -2528,14 +2554,23 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
     CallScope cs(ctx);
     for (int64_t p = 0; p < n_pairs; ++p) {
         if (!live(p)) continue;
-        const int64_t ra = c->rows[(size_t)pairs[2 * p]], rb = c->rows[(size_t)pairs[2 * p + 1]];
-        ctx->pending_pairs += 2 * ra * rb;
-        ctx->pending_bytes += 2 * (ra + rb) * (i8 ? 128 : wide ? 1024 : c->stack.kind == FM_BANK_BIN ? c->stack.dim : 512);
+        const int64_t ra = rows_a(p), rb = rows_b(p);
+        ctx->pending_pairs += ndir * ra * rb;
+        ctx->pending_bytes += ndir * (ra + rb) * (i8 ? 128 : wide ? 1024 : c->stack.kind == FM_BANK_BIN ? c->stack.dim : 512);
     }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, h, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_tab, ctx->stream));
     ctx->tab_in_flight = true;
     HIP_TRY(ctx, hipMemsetAsync(d_carry, 0, 16, ctx->stream));
+    if (a.knn2) {
+        // an image without rows keeps its slot: -1 / +inf, fm_knn2's lists over an empty bank
+        bool any_empty = false;
+        for (int64_t p = 0; p < n_pairs && !any_empty; ++p) any_empty = !live(p);
+        if (any_empty) {
+            HIP_TRY(ctx, hipMemsetAsync(l_idx, 0xff, (size_t)ni * nq * 8, ctx->stream));
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)l_dist, 0x7f800000, (size_t)ni * nq * 2, ctx->stream));
+        }
+    }
     bool timed = false;
     size_t next_fix = 0;
     for (size_t k = 0; k < chunks.size(); ++k) {
@@ -2560,7 +2595,7 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
             }
         } else if (ch.nslots > 0 && wide) {
             unsigned long long* part = (unsigned long long*)wp;
-            const WideTableLaunch tl{(const WideSlot*)(d + ch.o_ws), (const int*)(d + ch.o_ww), (const int*)(d + ch.o_wr), ch.nslots, ch.fwg, ch.wrows};
+            const WideTableLaunch tl{(const WideSlot*)(d + ch.o_ws), (const int*)(d + ch.o_ww), (const int*)(d + ch.o_wr), ch.nslots, ch.fwg, ch.wrows, a.q};
             if (!timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
             timed = true;
             if (ch.filt) {
@@ -2594,6 +2629,7 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
                 if ((rc = coll_merge_one(ctx, &ps, none, vb.n, js[j].rev, nullptr, l_idx, l_dist)) != FM_OK) return rc;
             }
         }
+        if (a.knn2) continue;                      // (the merged forward lists are the result)
         if (ch.jblocks > 0) {
             hipLaunchKernelGGL(coll_pairs_join_kernel, dim3((unsigned)ch.jblocks), dim3(256), 0, ctx->stream,
                                (const PairsJoinSlot*)(d + ch.o_js), (const int*)(d + ch.o_jb), np, (const int32_t*)l_idx, (const float*)l_dist,
@@ -2618,6 +2654,16 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
     if (timed) {
         if (c->stack.kind != FM_BANK_F32) HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));   // (the float32 route brackets its sweeps itself)
         ctx->kernel_timed = true;
+    }
+    if (a.knn2) {
+        // (copies of up to 128 MB each keep the staging buffer of fm::d2h within bounds)
+        const size_t total = (size_t)ni * nq * 8, piece = (size_t)128 << 20;
+        for (size_t o = 0; o < total; o += piece) {
+            const size_t nb = std::min(piece, total - o);
+            HIP_TRY(ctx, d2h(ctx, (char*)a.k_idx + o, (char*)l_idx + o, nb));
+            HIP_TRY(ctx, d2h(ctx, (char*)a.k_dist + o, (char*)l_dist + o, nb));
+        }
+        return cs.finish();
     }
     if (a.to_dev) {
         if ((rc = results_written(ctx, a.consumer)) != FM_OK) return rc;
@@ -2666,4 +2712,58 @@ extern "C" int fm_collection_pairs_mutual_ratio_dev(fm_ctx* ctx, fm_collection* 
     const CollPairsArgs a{"fm_collection_pairs_mutual_ratio_dev", tau, symmetric, cap, nullptr, nullptr, nullptr, nullptr, nullptr,
                           true, d_offsets, d_rows, consumer_stream, n_total};
     return coll_pairs_mutual(ctx, c, pairs, n_pairs, a);
+}
+
+// ---------------------------------------------------------------------------------------
+// a wide query bank against every image of a wide collection: fm_collection_wide_mutual_ratio_each, _wide_knn2_each
+// ---------------------------------------------------------------------------------------
+// The match graph's machinery with "pair" p = (q, image p): the forward slot's output rows are the query bank's -- an operand
+// outside the stack, with its own planes and fp16 scale (wide_f32.hip, part 5) -- the reverse slot's reduced rows are.  The
+// chunks, tables, merge, join, scan and compaction are coll_pairs_mutual's (CollPairsArgs::q).
+// The checks in front of it, in the header's order: handles, the collection's kind, the query's kind and width.
+static int coll_wide_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const char* who, const char* narrow)
+{
+    int rc = coll_check(ctx, c, who);
+    if (rc != FM_OK) return rc;
+    if (!q) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank is NULL");
+    if (!c->rows.empty() && !coll_is_wide(c))
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the collection holds images of another kind (not wide ones, fm_collection_add_wide); "
+                                    "it is served by " + narrow);
+    if (q->kind != FM_BANK_F32W)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the query bank is not a wide float bank (FM_BANK_F32W, 129 <= dim <= 256)");
+    if (c->dim != 0 && q->dim != c->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": the query's width differs from the collection's");
+    return FM_OK;
+}
+
+extern "C" int fm_collection_wide_knn2_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t* idx, float* dist)
+{
+    const char* who = "fm_collection_wide_knn2_each";
+    const int rc = coll_wide_query_check(ctx, c, q, who, "fm_collection_knn2_each");
+    if (rc != FM_OK) return rc;
+    CollPairsArgs a{who, 0.0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, FM_NO_STREAM, nullptr};
+    a.q = q; a.knn2 = true; a.k_idx = idx; a.k_dist = dist;
+    return coll_pairs_mutual(ctx, c, nullptr, (int64_t)c->rows.size(), a);
+}
+
+extern "C" int fm_collection_wide_mutual_ratio_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t symmetric, int64_t cap,
+                                                    int64_t* offsets, int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_total)
+{
+    const char* who = "fm_collection_wide_mutual_ratio_each";
+    const int rc = coll_wide_query_check(ctx, c, q, who, "fm_collection_mutual_ratio_each");
+    if (rc != FM_OK) return rc;
+    CollPairsArgs a{who, tau, symmetric, cap, offsets, qidx, tidx, dist, ratio, false, nullptr, nullptr, FM_NO_STREAM, n_total};
+    a.q = q;
+    return coll_pairs_mutual(ctx, c, nullptr, (int64_t)c->rows.size(), a);
+}
+
+extern "C" int fm_collection_wide_mutual_ratio_each_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t symmetric,
+                                                        int64_t cap, int64_t* d_offsets, int32_t* d_rows, int64_t* n_total,
+                                                        void* consumer_stream)
+{
+    const char* who = "fm_collection_wide_mutual_ratio_each_dev";
+    const int rc = coll_wide_query_check(ctx, c, q, who, "fm_collection_mutual_ratio_each");
+    if (rc != FM_OK) return rc;
+    CollPairsArgs a{who, tau, symmetric, cap, nullptr, nullptr, nullptr, nullptr, nullptr, true, d_offsets, d_rows, consumer_stream, n_total};
+    a.q = q;
+    return coll_pairs_mutual(ctx, c, nullptr, (int64_t)c->rows.size(), a);
 }

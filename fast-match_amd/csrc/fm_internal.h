@@ -319,20 +319,27 @@ WideFilterPlan plan_wide_filter(int64_t ncols_pad, int64_t ncols, int64_t nred_p
 hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const WideFilterPlan& plan, uint2* list, float* lscore,
                               unsigned* gbound, unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream);
 // Table forms (top-2) for a chunk of image pairs of one wide stack (fm_collection_pairs_mutual_ratio): a slot is one direction
-// of one pair, both operands views of `stack` that start on a 128-row stage.  The slots lie side by side in the chunk's
+// of one pair, both operands views of `stack` that start on a 128-row stage -- or, with WideTableLaunch::outside, one of them
+// rows of a bank outside the stack (fm_collection_wide_mutual_ratio_each: a query bank).  The slots lie side by side in the chunk's
 // output-row space -- slot s owns [row0, row0 + pad128(ncols)) -- which indexes gbound, partial [rows][2] and the records.
 struct WideSlot {
     int col0, ncols;                        // output rows: first physical row of the stack, real rows (>= 1)
     int red0, nred;                         // reduced rows: the same
     int ntiles, tiles_per_split, nsplit;    // the filter's shape for this slot (plan_wide_filter's fields)
     int row0;                               // the slot's first row in the chunk's output-row space (a multiple of 128)
+    // an operand outside the stack (WideTableLaunch::outside; part 5 of wide_f32.hip): which side it is -- that side's first
+    // row is 0 -- and the slot's scale terms, WideFilterParams' fields of the same names.  Without one: 0, 1, 1, the stack's.
+    int outside;
+    float cscale, nscale, red_nm_max;
 };
+constexpr int kWideOutCols = 1, kWideOutRed = 2;      // WideSlot::outside
 struct WideTableLaunch {
     const WideSlot* d_slots;                // [n]
     const int* d_wg0;                       // [n + 1] first workgroup of each slot in the filter's grid (nchunks * nsplit each), then the total
     const int* d_rowp;                      // [n + 1] row0 of each slot, then the chunk's rows
     int n, fwg;                             // slots, the filter's grid
     int64_t rows;                           // the chunk's rows (a multiple of 128)
+    const Bank* outside = nullptr;          // the bank the slots' `outside` sides are rows of (same dim as the stack), or null
 };
 // the filter and the rescoring into `partial` (preset to ~0, *cnt, flag[0] and gbound[0 .. rows) to 0); flag[0] = 1 afterwards:
 // the chunk's list (cap records, a multiple of 64) overflowed and launch_wide_exact_table must redo the chunk

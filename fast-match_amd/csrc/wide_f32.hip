@@ -56,9 +56,17 @@
 // A view of a wide collection's stack (part 4) uses the STACK's largest scaled squared norm for max |t'|^2 and the stack's one
 // scale: the derivation above holds for such a view exactly as for a bank, its "largest value >= 2^13" step included,
 // because the stack's scale follows the stack's largest finite magnitude and is never lowered.
+// A slot with an operand OUTSIDE the stack (part 5: a query bank against the images of a wide collection) is a bank pair of
+// two scales, slot by slot: the outside bank has the scale of its own largest magnitude, fixed at its creation, the view the
+// stack's, read at the call.  Each slot carries the exact powers of two that put its output rows' planes into its reduced
+// side's scale (cscale, nscale) and its reduced side's largest scaled squared norm -- the stack's for a forward slot (an
+// upper bound of the image's, as above), the outside bank's for a reverse slot -- so every term of E is the one derived
+// above for "Banks of different scales", per slot; a call whose two exponents differ by more than 8 takes the exact kernel.
 //
 // Part 4, the table forms of the three kernels: the bodies of parts 2 and 3 (wide_exact_body, wide_filter_body) over a table
 // of slots in device memory, one launch per chunk of image pairs (fm_collection_pairs_mutual_ratio).
+// Part 5, the table forms with an outside operand (OUT = true): one side of every slot is a bank that is not part of the stack
+// (fm_collection_wide_mutual_ratio_each, fm_collection_wide_knn2_each).
 #include "tile_ops.h"
 #include <algorithm>
 
@@ -627,9 +635,21 @@ hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const
 // file comment, and the stack's largest scaled value lies in [2^13, 2^14) or above whichever image is swept (the scale only
 // ever follows the running maximum upwards), which is all the fp16-subnormal step asks: the derivation holds for a view
 // exactly as for a bank.
+// ---------------------------------------------------------------------------------------
+// part 5: the table forms with an outside operand (a wide query bank against the images of a wide collection)
+// ---------------------------------------------------------------------------------------
+// The same three kernels, instantiated with OUT = true: ONE operand of every slot is a bank outside the stack, with planes,
+// scale and largest norm of its own -- the table parameters carry two plane sets, WideSlot::outside says which side takes the
+// second one (its first row is 0 there), and the slot carries the two exact scale factors and the reduced side's largest
+// scaled squared norm, which feed the filter body, the rescoring's second look and nothing else (the exact chain reads the
+// float32 rows alone).  A forward slot (output rows = the query's, reduced = image i) leaves keys whose low word is the row
+// inside image i, a reverse slot keys whose low word is the query row: the merge, join, scan and compaction behind the sweeps
+// serve unchanged.  All of it derives from the slot, which is the workgroup's (blockIdx.x): base pointers and scales stay in
+// scalar registers; the rescoring finds a record's slot per lane, as part 4's does.
 struct WideTableParams {
     const WideSlot* slots; const int* wg0; const int* rowp; int n;        // the chunk's table
     const float* rows; const uint16_t* rowsh; const float* normf; const float* auxf;   // the stack's planes
+    const float* orows; const uint16_t* orowsh; const float* onormf; const float* oauxf;   // part 5: the outside bank's (else null)
     float nm_max; int dim;
     uint2* list; float* lscore; unsigned cap; unsigned long long* cnt; unsigned* gbound;
     unsigned long long* partial;      // [chunk rows][KTOP]
@@ -637,7 +657,7 @@ struct WideTableParams {
     const int* run_flag;              // the exact kernel: null, or skip unless *run_flag != 0 (runs counted in run_flag[2])
 };
 
-template <int KS, int KTOP>
+template <int KS, int KTOP, bool OUT>
 __global__ __launch_bounds__(256)
 void wide_filter_table_kernel(WideTableParams t)
 {
@@ -645,15 +665,24 @@ void wide_filter_table_kernel(WideTableParams t)
     const WideSlot sl = t.slots[s];
     const int local = (int)blockIdx.x - t.wg0[s];
     WideFilterParams p;
-    p.colh = t.rowsh + (size_t)sl.col0 * kWideDim; p.colnorm = t.normf + sl.col0; p.ncols = sl.ncols;
-    p.redh = t.rowsh + (size_t)sl.red0 * kWideDim; p.redaux = t.auxf + sl.red0; p.nred = sl.nred;
-    p.cscale = 1.f; p.nscale = 1.f; p.red_nm_max = t.nm_max;
+    if constexpr (OUT) {
+        // (the slot is the workgroup's: the choice of a plane set and the slot's scales are scalar values)
+        const bool oc = sl.outside == kWideOutCols, orr = sl.outside == kWideOutRed;
+        p.colh = (oc ? t.orowsh : t.rowsh) + (size_t)sl.col0 * kWideDim; p.colnorm = (oc ? t.onormf : t.normf) + sl.col0;
+        p.redh = (orr ? t.orowsh : t.rowsh) + (size_t)sl.red0 * kWideDim; p.redaux = (orr ? t.oauxf : t.auxf) + sl.red0;
+        p.cscale = sl.cscale; p.nscale = sl.nscale; p.red_nm_max = sl.red_nm_max;
+    } else {
+        p.colh = t.rowsh + (size_t)sl.col0 * kWideDim; p.colnorm = t.normf + sl.col0;
+        p.redh = t.rowsh + (size_t)sl.red0 * kWideDim; p.redaux = t.auxf + sl.red0;
+        p.cscale = 1.f; p.nscale = 1.f; p.red_nm_max = t.nm_max;
+    }
+    p.ncols = sl.ncols; p.nred = sl.nred;
     p.ntiles = sl.ntiles; p.tiles_per_split = sl.tiles_per_split; p.nsplit = sl.nsplit;
     p.list = t.list; p.lscore = t.lscore; p.cap = t.cap; p.cnt = t.cnt; p.gbound = t.gbound;
     wide_filter_body<KS, KTOP>(p, local / sl.nsplit, local % sl.nsplit, sl.row0);
 }
 
-template <int KTOP>
+template <int KTOP, bool OUT>
 __global__ __launch_bounds__(256)
 void wide_rescore_table_kernel(WideTableParams t)
 {
@@ -669,9 +698,17 @@ void wide_rescore_table_kernel(WideTableParams t)
         const int s = table_slot_of(t.rowp, t.n, (int)rec.x);
         const WideSlot sl = t.slots[s];
         const size_t col = (size_t)sl.col0 + (rec.x - (unsigned)sl.row0), red = (size_t)sl.red0 + rec.y;
-        if (t.lscore[e] < wide_bits_f(t.gbound[rec.x]) - wide_margin(t.normf[col], 1.f, t.nm_max)) continue;
-        const float4* a = (const float4*)(t.rows + col * kWideDim);
-        const float4* b = (const float4*)(t.rows + red * kWideDim);
+        const float4* a; const float4* b;
+        if constexpr (OUT) {
+            const bool oc = sl.outside == kWideOutCols, orr = sl.outside == kWideOutRed;
+            if (t.lscore[e] < wide_bits_f(t.gbound[rec.x]) - wide_margin((oc ? t.onormf : t.normf)[col], sl.nscale, sl.red_nm_max)) continue;
+            a = (const float4*)((oc ? t.orows : t.rows) + col * kWideDim);
+            b = (const float4*)((orr ? t.orows : t.rows) + red * kWideDim);
+        } else {
+            if (t.lscore[e] < wide_bits_f(t.gbound[rec.x]) - wide_margin(t.normf[col], 1.f, t.nm_max)) continue;
+            a = (const float4*)(t.rows + col * kWideDim);
+            b = (const float4*)(t.rows + red * kWideDim);
+        }
         float s2 = 0.f;
         const int k4n = (t.dim + 3) >> 2;                       // (zero padding past dim: see the file comment)
         for (int k4 = 0; k4 < k4n; ++k4) {
@@ -691,7 +728,7 @@ void wide_rescore_table_kernel(WideTableParams t)
 }
 
 // Workgroup b: the 64 chunk rows from 64 b on, the whole reduced image of their slot (one split).
-template <int KTOP>
+template <int KTOP, bool OUT>
 __global__ __launch_bounds__(256)
 void wide_exact_table_kernel(WideTableParams t)
 {
@@ -706,9 +743,15 @@ void wide_exact_table_kernel(WideTableParams t)
     const int s = table_slot_of(t.rowp, t.n, row);
     const WideSlot sl = t.slots[s];
     WideExactParams p;
-    p.col_rows = t.rows + (size_t)sl.col0 * kWideDim;
+    const float* crows = t.rows;
+    const float* rrows = t.rows;
+    if constexpr (OUT) {
+        if (sl.outside == kWideOutCols) crows = t.orows;
+        if (sl.outside == kWideOutRed) rrows = t.orows;
+    }
+    p.col_rows = crows + (size_t)sl.col0 * kWideDim;
     p.ncols_pad = (sl.ncols + kStageRows - 1) / kStageRows * kStageRows;
-    p.red_rows = t.rows + (size_t)sl.red0 * kWideDim;
+    p.red_rows = rrows + (size_t)sl.red0 * kWideDim;
     p.nred = sl.nred;
     p.nred_pad = (sl.nred + kStageRows - 1) / kStageRows * kStageRows;
     p.nsteps = p.nred_pad / kWTile;
@@ -726,6 +769,7 @@ static WideTableParams wide_table_params(const Bank& stack, const WideTableLaunc
     WideTableParams t{};
     t.slots = tl.d_slots; t.wg0 = tl.d_wg0; t.rowp = tl.d_rowp; t.n = tl.n;
     t.rows = stack.wrows; t.rowsh = stack.wrowsh; t.normf = stack.normf; t.auxf = stack.auxf;
+    if (tl.outside) { t.orows = tl.outside->wrows; t.orowsh = tl.outside->wrowsh; t.onormf = tl.outside->normf; t.oauxf = tl.outside->auxf; }
     t.nm_max = stack.nm_max; t.dim = stack.dim;
     return t;
 }
@@ -733,7 +777,8 @@ static WideTableParams wide_table_params(const Bank& stack, const WideTableLaunc
 template <int KS>
 static void wide_filter_table_launch(const WideTableParams& t, int grid, hipStream_t stream)
 {
-    hipLaunchKernelGGL((wide_filter_table_kernel<KS, 2>), dim3(grid), dim3(256), 0, stream, t);
+    if (t.orows) hipLaunchKernelGGL((wide_filter_table_kernel<KS, 2, true>), dim3(grid), dim3(256), 0, stream, t);
+    else         hipLaunchKernelGGL((wide_filter_table_kernel<KS, 2, false>), dim3(grid), dim3(256), 0, stream, t);
 }
 
 hipError_t launch_wide_filter_table(const Bank& stack, const WideTableLaunch& tl, unsigned cap, uint2* list, float* lscore, unsigned* gbound,
@@ -751,7 +796,8 @@ hipError_t launch_wide_filter_table(const Bank& stack, const WideTableLaunch& tl
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((wide_rescore_table_kernel<2>), dim3(2048), dim3(256), 0, stream, t);
+    if (t.orows) hipLaunchKernelGGL((wide_rescore_table_kernel<2, true>), dim3(2048), dim3(256), 0, stream, t);
+    else         hipLaunchKernelGGL((wide_rescore_table_kernel<2, false>), dim3(2048), dim3(256), 0, stream, t);
     return hipGetLastError();
 }
 
@@ -761,7 +807,8 @@ hipError_t launch_wide_exact_table(const Bank& stack, const WideTableLaunch& tl,
     WideTableParams t = wide_table_params(stack, tl);
     t.partial = partial; t.run_flag = run_flag;
     if (tl.n < 1 || tl.rows < kWTile) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((wide_exact_table_kernel<2>), dim3((unsigned)(tl.rows / kWTile)), dim3(256), 0, stream, t);
+    if (t.orows) hipLaunchKernelGGL((wide_exact_table_kernel<2, true>), dim3((unsigned)(tl.rows / kWTile)), dim3(256), 0, stream, t);
+    else         hipLaunchKernelGGL((wide_exact_table_kernel<2, false>), dim3((unsigned)(tl.rows / kWTile)), dim3(256), 0, stream, t);
     return hipGetLastError();
 }
 

@@ -27,7 +27,10 @@ Mirrors ``matchutil.py`` of the reference:
   library's wide float banks under ``NORM_L2``: ``bf_match`` with k <= 2 and with crossCheck, ``ratio_match_arrays`` and
   ``mutual_ratio_match_arrays`` take them; ``bf_radius_match``, a mask, k >= 3 and ``BFMatcher.add`` raise ``ValueError``
   before anything is uploaded.  ``BFMatcher.add_wide`` adds wide images to a collection of their own, whose match graph
-  ``matchPairs`` / ``matchPairs_arrays`` computes (``fm_collection_add_wide``).
+  ``matchPairs`` / ``matchPairs_arrays`` computes (``fm_collection_add_wide``).  A wide query against such a collection,
+  image by image, is ``BFMatcher.mutualRatioMatchWideEach`` / ``mutualRatioMatchWideEach_arrays`` (mutual nearest neighbour
+  + ratio per image, the visual-localisation pattern; ``fm_collection_wide_mutual_ratio_each``) and
+  ``knnMatchWideEach_arrays`` (``fm_collection_wide_knn2_each``).
 * ``options["mask"]``: cv2's ``mask`` argument of ``knnMatch`` -- an ``[nq, nt]`` uint8 / bool array, nonzero = the pair
   (query row, train row) may be matched, or a resident ``_ffi.Mask`` (``Context.mask``).  ``bf_match``,
   ``bf_match_arrays``, ``flann_match`` and ``flann_match_arrays`` honour it when crossCheck is off: every list is the
@@ -403,7 +406,7 @@ class BFMatcher(object):
         self._images = []
         self._coll = None          # (_ffi.Collection, number of images it holds)
         self._uploaded = 0
-        self._wide = False         # the images came through add_wide: matchPairs is what the collection serves
+        self._wide = False         # the images came through add_wide: matchPairs and the *WideEach calls are what it serves
 
     # -- bookkeeping (host only) ---------------------------------------------------------
     def add(self, descriptors):
@@ -426,8 +429,9 @@ class BFMatcher(object):
     def add_wide(self, descriptors):
         """``add`` for WIDE float images: every entry a [n, dim] float array with 129 <= dim <= 256 (learned 256-D descriptors;
         n may be 0), one width per collection, NORM_L2.  A collection takes either ``add`` or ``add_wide`` images; a wide one
-        (``fm_collection_add_wide``) serves ``matchPairs`` / ``matchPairs_arrays``, and every other collection method raises
-        ``ValueError`` before anything is uploaded."""
+        (``fm_collection_add_wide``) serves ``matchPairs`` / ``matchPairs_arrays`` and, for a wide query,
+        ``mutualRatioMatchWideEach`` / ``mutualRatioMatchWideEach_arrays`` / ``knnMatchWideEach_arrays``; every other collection
+        method raises ``ValueError`` before anything is uploaded."""
         if self.normType != NORM_L2:
             raise ValueError("BFMatcher.add_wide: wide float images are NORM_L2 descriptors")
         if self._images and not self._wide:
@@ -465,9 +469,11 @@ class BFMatcher(object):
     def _check_collection(self, who):
         if self.empty():
             raise ValueError("%s: no train descriptors (add() some, or pass a train array)" % who)
-        if self._wide and who not in ("BFMatcher.train", "BFMatcher.matchPairs"):
+        if self._wide and who not in ("BFMatcher.train", "BFMatcher.matchPairs", "BFMatcher.mutualRatioMatchWideEach",
+                                      "BFMatcher.knnMatchWideEach"):
             raise ValueError("%s is not built for a wide collection (images of 129 .. 256 values per row, add_wide): "
-                             "matchPairs and matchPairs_arrays are" % who)
+                             "matchPairs, matchPairs_arrays and, for a wide query, mutualRatioMatchWideEach(_arrays) and "
+                             "knnMatchWideEach_arrays are" % who)
 
     def train(self):
         self._check_collection("BFMatcher.train")
@@ -653,6 +659,62 @@ class BFMatcher(object):
         for i, (qidx, tidx, dist, _) in enumerate(self.mutualRatioMatchEach_arrays(queryDescriptors, tau, symmetric)):
             out.append([DMatch(int(qidx[j]), int(tidx[j]), dist[j], i) for j in range(qidx.shape[0])])
         return out
+
+    def _wide_query(self, who, queryDescriptors):
+        """The checks of the wide-query calls, before anything is uploaded: NORM_L2, a wide collection, a float query of the
+        collection's width (or a resident wide bank of it).  Returns the query as it goes to the device."""
+        if self.normType != NORM_L2:
+            raise ValueError("%s: wide float descriptors are NORM_L2 descriptors" % who)
+        self._check_collection(who)
+        if not self._wide:
+            raise ValueError("%s: the collection is not a wide one (add_wide); mutualRatioMatchEach / knnMatchEach_arrays "
+                             "serve the other kinds" % who)
+        dim = self._images[0].shape[1]
+        if isinstance(queryDescriptors, _ffi.Bank):
+            if queryDescriptors.kind != _ffi.FM_BANK_F32W or queryDescriptors.dim != dim:
+                raise ValueError("%s: the query bank is not a wide float bank of the collection's width %d" % (who, dim))
+            return queryDescriptors
+        a = np.asarray(queryDescriptors)
+        if a.ndim != 2 or a.dtype.kind != "f" or a.shape[1] != dim:
+            raise ValueError("%s: the query is a float array [nq, %d] (the collection's width), got %s %s"
+                             % (who, dim, a.dtype, list(a.shape)))
+        return np.ascontiguousarray(a, dtype=np.float32)
+
+    def mutualRatioMatchWideEach_arrays(self, queryDescriptors, tau, symmetric=False):
+        """A wide query ([nq, dim] floats, or a resident wide bank) against every image of a WIDE collection (``add_wide``):
+        a list of (qidx, tidx, dist, ratio) per image, slot i equal to ``mutual_ratio_match_arrays(query, image_i, tau,
+        symmetric)`` (``Collection.wide_mutual_ratio_each``: one call, whatever the number of images).  ``ValueError`` before
+        anything is uploaded: a collection that is not wide, a query that is not a float array of the collection's width,
+        a norm other than NORM_L2."""
+        q = self._wide_query("BFMatcher.mutualRatioMatchWideEach", queryDescriptors)
+        coll = self.train()
+        qb, tmp = (q, False) if isinstance(q, _ffi.Bank) else (coll.ctx.bank(q), True)
+        try:
+            return coll.wide_mutual_ratio_each(qb, tau, symmetric)
+        finally:
+            if tmp:
+                qb.close()
+
+    def mutualRatioMatchWideEach(self, queryDescriptors, tau, symmetric=False):
+        """One list of ``DMatch`` per added image of :meth:`mutualRatioMatchWideEach_arrays`: ``queryIdx`` the query row,
+        ``trainIdx`` the row inside the image, ``imgIdx`` the image, ascending ``queryIdx``."""
+        out = []
+        for i, (qidx, tidx, dist, _) in enumerate(self.mutualRatioMatchWideEach_arrays(queryDescriptors, tau, symmetric)):
+            out.append([DMatch(int(qidx[j]), int(tidx[j]), dist[j], i) for j in range(qidx.shape[0])])
+        return out
+
+    def knnMatchWideEach_arrays(self, queryDescriptors):
+        """(idx int32, dist float32) [n_images, nq, 2]: the two nearest rows of every image of a WIDE collection for every row
+        of a wide query, slot i equal to ``bf_match_arrays(query, image_i, k=2)`` (``Collection.wide_knn2_each``).  The
+        refusals are :meth:`mutualRatioMatchWideEach_arrays`'."""
+        q = self._wide_query("BFMatcher.knnMatchWideEach", queryDescriptors)
+        coll = self.train()
+        qb, tmp = (q, False) if isinstance(q, _ffi.Bank) else (coll.ctx.bank(q), True)
+        try:
+            return coll.wide_knn2_each(qb)
+        finally:
+            if tmp:
+                qb.close()
 
     def matchPairs_arrays(self, pairs=None, ratio=0.8, symmetric=False):
         """The added images matched AGAINST EACH OTHER -- the match graph of structure from motion and stitching (COLMAP's

@@ -53,6 +53,10 @@ wide float banks (``FM_BANK_F32W``): ``bank``, ``knn`` with k <= 2, ``mutual_nn`
 take them; ``radius_match``, a masked or k >= 3 ``knn`` and ``Collection.add`` raise ``ValueError`` before the library is
 touched.  Their match graph: ``Collection.add_wide(tensor)`` (``fm_collection_add_wide_dev``) makes a WIDE collection, which
 takes no other images and serves ``match_pairs``, ``info``, ``clear`` and ``close``; its other methods raise ``ValueError``.
+A wide QUERY against a wide collection, image by image: ``Collection.wide_mutual_ratio_each(q, tau, symmetric=False,
+cap=None)`` -> ``(offsets int64 [n_images + 1], rows int32 [n, 3] = (query row, row inside the image, float32 distance
+bits))``, image i equal to ``mutual_ratio_match(q, image_i)`` (``fm_collection_wide_mutual_ratio_each_dev``; the
+visual-localisation pattern); ``cap`` as in ``match_pairs``.
 
 ``q`` and ``t`` are ``Bank``s or CUDA tensors (a tensor becomes a bank for the call).  The values are those of
 ``Context.knn`` / ``xcheck1`` / ``knn2_ratio`` on banks built from the same numbers on the host, bit for bit.
@@ -394,10 +398,11 @@ class Collection(object):
         return False
 
     def _refuse_wide_collection(self, who):
-        """ValueError before the library is touched: a wide collection (``add_wide``) is served by ``match_pairs`` only."""
+        """ValueError before the library is touched: a wide collection (``add_wide``) is served by ``match_pairs`` and
+        ``wide_mutual_ratio_each`` only."""
         if self._wide:
             raise ValueError("Collection.%s is not built for a wide collection (images of 129 .. 256 values per row, add_wide): "
-                             "match_pairs, info and clear are" % who)
+                             "match_pairs, wide_mutual_ratio_each, info and clear are" % who)
 
     def _collection(self, ctx=None):
         if self._coll is None:
@@ -425,8 +430,8 @@ class Collection(object):
     def add_wide(self, tensor):
         """Append one WIDE image ([n, dim] float32 / float16 / bfloat16 with 129 <= dim <= 256; n may be 0), read in place as
         ``add`` reads its tensor (``fm_collection_add_wide_dev``).  The first ``add_wide`` makes the collection a wide one
-        (``FM_BANK_F32W``): it takes no other images and serves ``match_pairs``, ``info`` and ``clear``.  Returns the image's
-        index."""
+        (``FM_BANK_F32W``): it takes no other images and serves ``match_pairs``, ``wide_mutual_ratio_each``, ``info`` and
+        ``clear``.  Returns the image's index."""
         import torch
         tensor, dt = _checked(tensor)
         if dt == _ffi.FM_DT_U8:
@@ -657,6 +662,47 @@ class Collection(object):
         coll.pairs_mutual_ratio_dev(pairs, float(tau), bool(symmetric), offsets.data_ptr(), rows.data_ptr() if cap else 0, cap,
                                     consumer_stream=stream)
         return offsets, rows
+
+    def wide_mutual_ratio_each(self, q, tau, symmetric=False, cap=None):
+        """A wide query matched against every image of a WIDE collection (``add_wide``), image by image, left on the device:
+        ``(offsets int64 [n_images + 1], rows int32 [n, 3] = (query row, row inside the image, float32 distance bits))``; the
+        rows of image i are ``rows[offsets[i]:offsets[i + 1]]``, equal to ``mutual_ratio_match(q, image_i, tau, symmetric)``.
+        ``q``: a wide ``Bank`` or a CUDA tensor [nq, dim] of float32 / float16 / bfloat16 with 129 <= dim <= 256.  ``cap``
+        exactly as in ``match_pairs``.  ``ValueError`` before the library is touched for a collection that is not wide."""
+        import torch
+        if not self._wide:
+            raise ValueError("Collection.wide_mutual_ratio_each: the collection is not a wide one (add_wide); "
+                             "mutual_ratio_each serves the other kinds")
+        if cap is not None and int(cap) < 0:
+            raise ValueError("cap must not be negative")
+        made = []
+        if isinstance(q, _ffi.Bank):
+            if q.kind != _ffi.FM_BANK_F32W:
+                raise ValueError("Collection.wide_mutual_ratio_each: the query bank is not a wide float bank (FM_BANK_F32W)")
+            qb = q
+        else:
+            t, dt = _checked(q)
+            if dt == _ffi.FM_DT_U8 or not 129 <= t.shape[1] <= 256:
+                raise ValueError("Collection.wide_mutual_ratio_each: the query is a float32 / float16 / bfloat16 tensor of "
+                                 "129 .. 256 values per row, got %s [%d, %d]" % (t.dtype, t.shape[0], t.shape[1]))
+            qb = bank(t, context=self._context)
+            made.append(qb)
+        try:
+            coll = self._collection(qb.ctx)
+            n = coll.info()[0]
+            stream, dev = _stream_and_device(coll.ctx)
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            if cap is None:
+                cap = coll.wide_mutual_ratio_each_dev(qb, float(tau), bool(symmetric), offsets.data_ptr(), 0, 0, want_total=True,
+                                                      consumer_stream=stream)
+            cap = int(cap)
+            rows = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+            coll.wide_mutual_ratio_each_dev(qb, float(tau), bool(symmetric), offsets.data_ptr(), rows.data_ptr() if cap else 0, cap,
+                                            consumer_stream=stream)
+            return offsets, rows
+        finally:
+            for b in made:
+                b.close()
 
     def clear(self):
         if self._coll is not None:

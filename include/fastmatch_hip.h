@@ -60,8 +60,9 @@ typedef struct fm_bank fm_bank;
  * 129 <= dim <= 256; still revision 12, additions only -- fm_collection_pairs_mutual_ratio,
  * fm_collection_pairs_mutual_ratio_dev; still revision 12, additions only -- fm_collection_add_wide,
  * fm_collection_add_wide_dev; still revision 12, additions only -- fm_hamming_radius_match, fm_hamming_radius_match_dev,
- * fm_collection_hamming_radius_match, fm_collection_hamming_radius_match_dev).  A binding compares
- * fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.                      */
+ * fm_collection_hamming_radius_match, fm_collection_hamming_radius_match_dev; still revision 12, additions only --
+ * fm_collection_wide_knn2_each, fm_collection_wide_mutual_ratio_each, fm_collection_wide_mutual_ratio_each_dev).  A binding
+ * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.              */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
 
@@ -270,7 +271,41 @@ int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t
  * fm_collection_knn2_each, fm_collection_votes, fm_collection_knn_masked(_dev), fm_collection_radius_match(_dev),
  * fm_collection_match_accepted_each(_dev), fm_collection_xcheck1_each(_dev), fm_collection_mutual_ratio_each(_dev) -- and
  * fm_mask_create_coll: FM_EUNSUPPORTED with a message that says "wide", straight after the NULL-handle checks.  Also not
- * built: k >= 3, LDS staging of the streamed operand, computing a pair's tiles once for both directions.             */
+ * built: k >= 3, LDS staging of the streamed operand, computing a pair's tiles once for both directions.
+ * Wide QUERIES: a wide query bank is matched against every image of a wide collection, image by image, by entry points of
+ * their own -- the calls listed above keep refusing, and their messages name these: fm_collection_wide_knn2_each,
+ * fm_collection_wide_mutual_ratio_each and fm_collection_wide_mutual_ratio_each_dev (the localisation pattern: one query image
+ * against the N database images that retrieval returned, mutual nearest neighbour + ratio per image).  Slot i of
+ * fm_collection_wide_knn2_each (idx / dist [n_images][nq][2]) equals fm_knn2(q, B_i), and image i of the two mutual calls equals
+ * fm_mutual_ratio(q, B_i, tau, symmetric) row by row and bit for bit, B_i being a bank made by fm_bank_create_f32 from the
+ * values of image i: qidx is the query row, tidx the row inside image i, dist is d0, ratio the forward ratio (symmetric: the
+ * larger of the two), rows ascend in qidx, and every rule of fm_mutual_ratio holds -- tau = +inf, a missing second neighbour,
+ * 0 / 0, the lowest index wins a tie, NaN never beats anything.  Images are independent (a descriptor present in two images can
+ * match in both); an empty image keeps its slot and accepts nothing (knn2: -1 / +inf).  The mutual calls pack their output by
+ * fm_collection_pairs_mutual_ratio's rules with "image" for "pair": offsets[0 .. n_images] always hold the full counts,
+ * offsets[n_images] = *n_total, rows are written for the longest prefix of whole images that fits in cap, cap = 0 is counts
+ * only (the row arrays may be NULL; the counts are the per-image votes); the _dev form writes 12-byte rows {query row, row
+ * inside the image, float32 distance bits}, orders consumer_stream in both directions, waits for the device only when n_total
+ * is asked for and is not accounted in fm_stats; the host mutual form waits only for its copy out and adds 2 nq sum rows_i
+ * pairs to fm_stats, fm_collection_wide_knn2_each nq sum rows_i.  Errors, in this order: NULL handles or a foreign context
+ * (FM_EINVAL); a collection that holds images of another kind (FM_EINVAL, the message names fm_collection_mutual_ratio_each or
+ * fm_collection_knn2_each; a collection on which no add has succeeded is valid and gives offsets[0] = 0); a query that is not
+ * FM_BANK_F32W or whose width is not the collection's (FM_EINVAL, even for an empty query: the wide creators make an empty bank
+ * wide); cap < 0, offsets NULL, a row array NULL with cap > 0 (FM_EINVAL; the _dev form checks that its pointers are device
+ * memory); for fm_collection_wide_knn2_each idx or dist NULL with n_images * nq > 0 (FM_EINVAL).  nq = 0, a collection of empty
+ * images only and n_images = 0 are valid.  Kernels: the table forms above with ONE OPERAND OUTSIDE THE STACK -- a slot is one
+ * direction of one image (forward: the query rows are the output rows, image i the reduced rows; reverse: the other way
+ * round) and carries which side is the query bank, the two exact scale factors between the query's fp16 scale (fixed at its
+ * creation) and the stack's (read at the call) and the reduced side's largest scaled squared norm; ONE filter launch, ONE
+ * rescoring launch, ONE guarded exact launch and ONE merge launch per chunk of consecutive images ("coll_ws_bytes"; per image
+ * pad128(nq) + pad128(rows_i) output rows, 256 records of 12 bytes per output row, at least 2^20 records), no host wait between
+ * the sweeps.  "f32_filter" chooses per chunk and never changes a result: 0 the exact kernel alone, 1 the filter from
+ * 2 nq sum rows_i >= 4e6 over the chunk's images (knn2: nq sum rows_i), 2 always; the exact kernel alone when a value on either
+ * side is not finite or the two scale exponents differ by more than 8; fm_f32_filter_stats counts one launch per filtered chunk
+ * and one fallback per chunk redone (the cliff above, per chunk); "f32_nsplit" keeps its meaning.  Out of scope here: the
+ * stacked forms on a wide collection (knnMatch over all images, knn2_ratio, votes mode 0), xcheck1_each / match_accepted_each
+ * for wide collections, k >= 3, masks, radius queries, sharing one resident copy of the query's B operand across the forward
+ * slots of a chunk, LDS staging of the streamed operand, computing an image's tiles once for both directions.            */
 int  fm_bank_destroy(fm_ctx* ctx, fm_bank* bank);
 int  fm_bank_info(const fm_bank* bank, int64_t* n, int* dim, int* kind);
 /* Attach per-row self distances (Metric_Cache.*["distances"], float64, cache.pyx:252,273)
@@ -595,6 +630,15 @@ int  fm_collection_pairs_mutual_ratio_dev(fm_ctx* ctx, fm_collection* coll, cons
                                           double tau, int32_t symmetric, int64_t cap, int64_t* d_offsets /*device [n_pairs + 1]*/,
                                           int32_t* d_rows /*device [cap][3]*/, int64_t* n_total /*host or NULL*/,
                                           void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+/* a wide query bank against every image of a wide collection ("K14: wide float banks" above, Wide QUERIES) */
+int  fm_collection_wide_knn2_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, int32_t* idx /*[n_images][nq][2]*/,
+                                  float* dist /*[n_images][nq][2]*/);
+int  fm_collection_wide_mutual_ratio_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int32_t symmetric, int64_t cap,
+                                          int64_t* offsets /*[n_images + 1]*/, int32_t* qidx, int32_t* tidx, float* dist,
+                                          double* ratio /* each [cap] */, int64_t* n_total /*or NULL*/);
+int  fm_collection_wide_mutual_ratio_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int32_t symmetric, int64_t cap,
+                                              int64_t* d_offsets /*device [n_images + 1]*/, int32_t* d_rows /*device [cap][3]*/,
+                                              int64_t* n_total /*host or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* ---- descriptors already on the GPU: device sources, device results ---------------------------------------------------------
  * Every creator above takes a HOST array and every dense matcher call ends in host arrays: the shape of the reference, whose
