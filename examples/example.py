@@ -101,3 +101,12 @@ orb_q[:, 0] ^= 0b10110                                             # the same ro
 near = matchutil.hamming_radius_match(orb_q, orb_db, 40.5)
 print("ORB radius match: %d of 200 query rows found within 40 bits, %d entries in all" % (sum(bool(l) for l in near), sum(map(len, near))))
 assert all(l and l[0].trainIdx == i and l[0].distance == 3.0 for i, l in enumerate(near))
+
+# Fast-Match's own test on the same ORB rows: the cross-checked nearest neighbour is accepted while its distance is small
+# beside the query row's distance to its nearest OTHER query row (the Hamming self distance, computed on the device).
+# A query row with a duplicate has self distance 0 and is never accepted: rows 3 and 7 here.
+orb_q[7] = orb_q[3]
+accepted = matchutil.hamming_fast_match(orb_q, orb_db, 0.5)
+print("ORB Fast-Match: %d of 200 query rows accepted at tau 0.5" % len(accepted))
+assert sorted(m.queryIdx for m in accepted) == [i for i in range(200) if i not in (3, 7)]
+assert all(m.trainIdx == m.queryIdx and m.distance == 3.0 for m in accepted)

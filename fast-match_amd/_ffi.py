@@ -189,6 +189,15 @@ SYMBOLS = {
     "fm_hamming_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
     "fm_collection_hamming_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
     "fm_collection_hamming_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    # Hamming Fast-Match: the self-distance test on binary banks (csrc/hamming.hip, ham_self_kernel)
+    "fm_hamming_self_dist": (_INT, [_P, _P, _P]),
+    "fm_hamming_self_dist_batch": (_INT, [_P, ctypes.c_int32, _P, _P]),
+    "fm_hamming_set_selfdist": (_INT, [_P, _P, _P]),
+    "fm_hamming_match_ratio": (_INT, [_P, _P, _P, ctypes.c_double, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_hamming_match_accepted": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_hamming_match_accepted_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_collection_hamming_match_accepted_each": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, _P]),
+    "fm_collection_hamming_match_accepted_each_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P]),
     # K13: knnMatch under a mask (csrc/masked.hip)
     "fm_mask_create": (_INT, [_P, _I64, _I64, ctypes.POINTER(_P)]),
     "fm_mask_create_coll": (_INT, [_P, _I64, _P, ctypes.POINTER(_P)]),
@@ -355,12 +364,16 @@ class Bank(object):
         self.has_selfdist = False
         ctx._children.add(self)           # (a context that is closed first destroys what was made through it)
 
-    def set_selfdist(self, selfdist):
+    def set_selfdist(self, selfdist, _name="fm_bank_set_selfdist"):
         sd = np.ascontiguousarray(selfdist, dtype=np.float64)
         if sd.shape != (self.n,):
             raise ValueError("selfdist must have shape (%d,)" % self.n)
-        self.ctx._check(self.ctx.lib.fm_bank_set_selfdist(self.ctx.handle, self.handle, _ptr(sd)))
+        self.ctx._check(getattr(self.ctx.lib, _name)(self.ctx.handle, self.handle, _ptr(sd)))
         self.has_selfdist = True
+
+    def set_hamming_selfdist(self, selfdist):
+        """``fm_hamming_set_selfdist``: attach Hamming self distances (float64 [n]) to a binary bank."""
+        self.set_selfdist(selfdist, _name="fm_hamming_set_selfdist")
 
     def refill_async(self, rows):
         """A new image's uint8 descriptors into this bank without allocation or host synchronisation
@@ -714,7 +727,17 @@ class Collection(object):
                                                          _ptr(v) if v.shape[0] else None))
         return v
 
-    def match_accepted_each(self, q, tau, cap=None):
+    def hamming_match_accepted_each(self, q, tau, cap=None):
+        """``fm_collection_hamming_match_accepted_each``: ``match_accepted_each`` on a binary collection -- slot i equal to
+        ``Context.hamming_match_accepted(q, bank(image_i), tau)``; ``q`` is a binary bank with Hamming self distances."""
+        return self.match_accepted_each(q, tau, cap, _name="fm_collection_hamming_match_accepted_each")
+
+    def hamming_match_accepted_each_dev(self, q, tau, rows_ptr, counts_ptr, cap, h_counts=None, consumer_stream=None):
+        """``match_accepted_each_dev`` on a binary collection (``fm_collection_hamming_match_accepted_each_dev``)."""
+        return self.match_accepted_each_dev(q, tau, rows_ptr, counts_ptr, cap, h_counts, consumer_stream,
+                                            _name="fm_collection_hamming_match_accepted_each_dev")
+
+    def match_accepted_each(self, q, tau, cap=None, _name="fm_collection_match_accepted_each"):
         """``fm_collection_match_accepted_each``: Fast-Match's accepted-match test of ``q`` (a bank with self distances) inside
         every image separately -- a list of (qidx, tidx, dist, ratio) per image, slot i equal to
         ``Context.match_accepted(q, bank(image_i), tau)``; ``tidx`` is the row inside the image.  ``cap`` (default ``q.n``)
@@ -725,7 +748,7 @@ class Collection(object):
         qidx, tidx = np.empty((ni, kept), np.int32), np.empty((ni, kept), np.int32)
         dist, ratio = np.empty((ni, kept), np.float32), np.empty((ni, kept), np.float64)
         n = np.zeros(ni, np.int64)
-        self.ctx._check(self.ctx.lib.fm_collection_match_accepted_each(
+        self.ctx._check(getattr(self.ctx.lib, _name)(
             self.ctx.handle, self.handle, q.handle, float(tau), cap, _ptr(qidx) if qidx.size else None,
             _ptr(tidx) if tidx.size else None, _ptr(dist) if dist.size else None, _ptr(ratio) if ratio.size else None,
             _ptr(n) if ni else None))
@@ -743,7 +766,8 @@ class Collection(object):
                                                                        None, None, None, None, _ptr(n) if n.shape[0] else None))
         return n
 
-    def match_accepted_each_dev(self, q, tau, rows_ptr, counts_ptr, cap, h_counts=None, consumer_stream=None):
+    def match_accepted_each_dev(self, q, tau, rows_ptr, counts_ptr, cap, h_counts=None, consumer_stream=None,
+                                _name="fm_collection_match_accepted_each_dev"):
         """``match_accepted_each`` with device outputs (``fm_collection_match_accepted_each_dev``), as
         ``Context.match_accepted_dev_batch``: ``rows_ptr`` = device address of an int32 [n_images, cap, 3] block (query, row
         inside the image, float32 distance bits), ``counts_ptr`` of an int64 [n_images] array that receives min(count, cap);
@@ -753,7 +777,7 @@ class Collection(object):
         if h_counts is not None and (not isinstance(h_counts, np.ndarray) or h_counts.dtype != np.int64 or h_counts.size < ni
                                      or not h_counts.flags.c_contiguous):
             raise ValueError("h_counts must be a contiguous int64 array of n_images words")
-        self.ctx._check(self.ctx.lib.fm_collection_match_accepted_each_dev(
+        self.ctx._check(getattr(self.ctx.lib, _name)(
             self.ctx.handle, self.handle, q.handle, float(tau), int(cap), _P(int(rows_ptr)) if rows_ptr else None,
             _P(int(counts_ptr)) if counts_ptr else None, _ptr(h_counts) if h_counts is not None else None,
             _stream_arg(consumer_stream)))
@@ -1361,12 +1385,22 @@ class Context(object):
                 raise FastMatchHipError("%s: %d entries on the second call, %d on the first" % (_name, total.value, n))
         return offsets, idx, dist
 
-    def self_dist(self, bank):
+    def self_dist(self, bank, _name="fm_self_dist"):
         out = np.empty(bank.n, dtype=np.float64)
-        self._check(self.lib.fm_self_dist(self.handle, bank.handle, _ptr(out)))
+        self._check(getattr(self.lib, _name)(self.handle, bank.handle, _ptr(out)))
         return out
 
-    def self_dist_batch(self, banks, want_host=True):
+    def hamming_self_dist(self, bank):
+        """``fm_hamming_self_dist``: float64 [n], row i's Hamming distance to its nearest OTHER row of a binary bank
+        (+inf for a bank of one row, 0 for a row with a duplicate)."""
+        return self.self_dist(bank, _name="fm_hamming_self_dist")
+
+    def hamming_self_dist_batch(self, banks, want_host=True):
+        """``fm_hamming_self_dist_batch``: ``self_dist_batch`` for binary banks -- the Hamming self distances of every bank,
+        attached to it on the device; banks of one K-step count (16 bytes of row width each) share a launch."""
+        return self.self_dist_batch(banks, want_host, _name="fm_hamming_self_dist_batch")
+
+    def self_dist_batch(self, banks, want_host=True, _name="fm_self_dist_batch"):
         """Metric_Cache builds of several images in one call (``fm_self_dist_batch``): the self distances of
         every bank, attached to it on the device; runs of integer banks (of any sizes, r05) share the
         triangular sweep's launches, up to ``batch_group`` banks each.
@@ -1377,7 +1411,7 @@ class Context(object):
         hs = (_P * n)(*[b.handle for b in banks])
         outs = [np.empty(b.n, dtype=np.float64) for b in banks] if want_host else None
         op = (_P * n)(*[_P(o.ctypes.data) if o.shape[0] else None for o in outs]) if want_host else None
-        self._check(self.lib.fm_self_dist_batch(self.handle, n, hs, op))
+        self._check(getattr(self.lib, _name)(self.handle, n, hs, op))
         for b in banks:
             b.has_selfdist = True
         return outs
@@ -1403,7 +1437,20 @@ class Context(object):
         buffer (``tensor.data_ptr()``)."""
         self._check(self.lib.fm_xcheck1_keys_dev(self.handle, q.handle, t.handle, int(t_offset), _P(int(keys_ptr))))
 
-    def match_ratio(self, q, t, tau, out=None):
+    def hamming_match_ratio(self, q, t, tau, out=None):
+        """``match_ratio`` on two binary banks (``fm_hamming_match_ratio``): dist = popcount(q XOR t), the query bank
+        carries Hamming self distances."""
+        return self.match_ratio(q, t, tau, out, _name="fm_hamming_match_ratio")
+
+    def hamming_match_accepted(self, q, t, tau, out=None):
+        """``match_accepted`` on two binary banks (``fm_hamming_match_accepted``)."""
+        return self.match_accepted(q, t, tau, out, _name="fm_hamming_match_accepted")
+
+    def hamming_match_accepted_dev(self, q, t, tau, rows_ptr, count_ptr, cap):
+        """``match_accepted_dev`` on two binary banks (``fm_hamming_match_accepted_dev``)."""
+        return self.match_accepted_dev(q, t, tau, rows_ptr, count_ptr, cap, _name="fm_hamming_match_accepted_dev")
+
+    def match_ratio(self, q, t, tau, out=None, _name="fm_match_ratio"):
         """X1 + R1 fused.  ``out`` = optional (tidx i32[nq], dist f32[nq], ratio f64[nq],
         passed u8[nq]) buffers to fill (e.g. from ``pinned_empty``); then ``passed`` is
         returned as that uint8 array instead of a bool copy."""
@@ -1413,19 +1460,19 @@ class Context(object):
                 if a.dtype != dt or a.shape != (q.n,) or not a.flags.c_contiguous:
                     raise ValueError("out buffers must be contiguous [nq] int32/float32/float64/uint8")
             npass = _I64(0)
-            self._check(self.lib.fm_match_ratio(self.handle, q.handle, t.handle, float(tau), _ptr(tidx),
-                                                _ptr(dist), _ptr(ratio), _ptr(passed), ctypes.byref(npass)))
+            self._check(getattr(self.lib, _name)(self.handle, q.handle, t.handle, float(tau), _ptr(tidx),
+                                                 _ptr(dist), _ptr(ratio), _ptr(passed), ctypes.byref(npass)))
             return tidx, dist, ratio, passed, npass.value
         tidx = np.empty(q.n, dtype=np.int32)
         dist = np.empty(q.n, dtype=np.float32)
         ratio = np.empty(q.n, dtype=np.float64)
         passed = np.empty(q.n, dtype=np.uint8)
         npass = _I64(0)
-        self._check(self.lib.fm_match_ratio(self.handle, q.handle, t.handle, float(tau), _ptr(tidx),
-                                            _ptr(dist), _ptr(ratio), _ptr(passed), ctypes.byref(npass)))
+        self._check(getattr(self.lib, _name)(self.handle, q.handle, t.handle, float(tau), _ptr(tidx),
+                                             _ptr(dist), _ptr(ratio), _ptr(passed), ctypes.byref(npass)))
         return tidx, dist, ratio, passed.astype(bool), npass.value
 
-    def match_accepted(self, q, t, tau, out=None):
+    def match_accepted(self, q, t, tau, out=None, _name="fm_match_accepted"):
         """X1 + R1, returning only the accepted matches in ascending query index:
         (qidx i32[m], tidx i32[m], dist f32[m], ratio f64[m]).  ``out`` = optional buffers
         (qidx, tidx, dist, ratio) of equal capacity (e.g. pinned); views of them are returned."""
@@ -1435,8 +1482,8 @@ class Context(object):
         qidx, tidx, dist, ratio = out
         cap = self._check_accepted_out(out)
         n = _I64(0)
-        self._check(self.lib.fm_match_accepted(self.handle, q.handle, t.handle, float(tau), cap, _ptr(qidx),
-                                               _ptr(tidx), _ptr(dist), _ptr(ratio), ctypes.byref(n)))
+        self._check(getattr(self.lib, _name)(self.handle, q.handle, t.handle, float(tau), cap, _ptr(qidx),
+                                             _ptr(tidx), _ptr(dist), _ptr(ratio), ctypes.byref(n)))
         m = min(n.value, cap)
         return qidx[:m], tidx[:m], dist[:m], ratio[:m]
 
@@ -1509,14 +1556,14 @@ class Context(object):
         arr = lambda vals: (_P * n)(*[_P(int(v)) for v in vals])
         return {"args": (n, arr([q.handle.value for q, _ in pairs]), arr([t.handle.value for _, t in pairs])), "keep": list(pairs)}
 
-    def match_accepted_dev(self, q, t, tau, rows_ptr, count_ptr, cap):
+    def match_accepted_dev(self, q, t, tau, rows_ptr, count_ptr, cap, _name="fm_match_accepted_dev"):
         """X1 + R1 with the accepted matches left on the device: ``rows_ptr`` = device address of
         an int32 [cap, 3] buffer (query index, train index, float32 distance bits), ``count_ptr``
         = device address of an int64 word (e.g. ``tensor.data_ptr()`` of torch tensors on this
         context's device).  Returns the number accepted."""
         n = _I64(0)
-        self._check(self.lib.fm_match_accepted_dev(self.handle, q.handle, t.handle, float(tau), int(cap),
-                                                   _P(int(rows_ptr)), _P(int(count_ptr)), ctypes.byref(n)))
+        self._check(getattr(self.lib, _name)(self.handle, q.handle, t.handle, float(tau), int(cap),
+                                             _P(int(rows_ptr)), _P(int(count_ptr)), ctypes.byref(n)))
         return n.value
 
     def match_accepted_dev_async(self, q, t, tau, rows_ptr, count_ptr, cap, h_count=None, consumer_stream=None):

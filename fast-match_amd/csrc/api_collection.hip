@@ -1706,6 +1706,9 @@ struct CollEachArgs {
     int32_t* qidx; int32_t* tidx; float* dist; double* ratio; int64_t* counts;
     // device form: d_rows [n_images][cap][3], d_counts [n_images], h_counts host [n_images] or null
     bool to_dev; int32_t* d_rows; int64_t* d_counts; int64_t* h_counts; void* consumer;
+    // the Hamming form of the accepted-match test (fm_collection_hamming_match_accepted_each(_dev)): a binary collection and a
+    // binary query bank with Hamming self distances; l2 = the L2 call its refusals name.  Else binary data is refused.
+    bool hamming = false; const char* l2 = nullptr;
 };
 
 static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const CollEachArgs& a)
@@ -1713,12 +1716,23 @@ static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, cons
     const std::string who(a.who);
     // (the cross-check: a query bank without rows is not held to the collection's kind, as in the radius calls -- every
     // creator makes an empty bank an integer-route one)
-    int rc = coll_query_check(ctx, c, q, a.who, !a.accept);
-    if (rc != FM_OK) return rc;
-    if (a.accept && q->kind == FM_BANK_BIN)
-        return fail(ctx, FM_EUNSUPPORTED, who + ": binary banks carry no self distances: the self-distance test is not built for a binary collection");
+    int rc;
+    if (a.hamming) {
+        // (the kinds before coll_query_check's own refusals: a collection or a query bank that is not binary is FM_EINVAL here)
+        if ((rc = coll_check(ctx, c, a.who)) != FM_OK) return rc;
+        if (!q) return fail(ctx, FM_EINVAL, who + ": query bank is NULL");
+        if (q->kind != FM_BANK_BIN || (c->dim != 0 && c->stack.kind != FM_BANK_BIN))
+            return fail(ctx, FM_EINVAL, who + ": the collection and the query bank must be binary (fm_collection_add_bin, fm_bank_create_bin); " +
+                                            a.l2 + " is the L2 call");
+    }
+    if ((rc = coll_query_check(ctx, c, q, a.who, !a.accept)) != FM_OK) return rc;
+    if (a.accept && !a.hamming && q->kind == FM_BANK_BIN)
+        return fail(ctx, FM_EUNSUPPORTED, who + ": binary banks carry no self distances here: fm_collection_hamming_match_accepted_each(_dev) "
+                                                "is the self-distance test of a binary collection");
     const int64_t nq = q->n, ni = (int64_t)c->rows.size(), cap = a.cap;
-    if (a.accept && nq > 0 && !q->selfdist) return fail(ctx, FM_EINVAL, who + ": query bank has no self distances (fm_bank_set_selfdist)");
+    if (a.accept && nq > 0 && !q->selfdist)
+        return fail(ctx, FM_EINVAL, who + ": query bank has no self distances (" +
+                                        (a.hamming ? "fm_hamming_set_selfdist, fm_hamming_self_dist_batch" : "fm_bank_set_selfdist") + ")");
     if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap < 0");
     if (ni == 0) return FM_OK;
     if (a.to_dev) {
@@ -1856,6 +1870,24 @@ extern "C" int fm_collection_match_accepted_each_dev(fm_ctx* ctx, fm_collection*
 {
     const CollEachArgs a{"fm_collection_match_accepted_each_dev", true, tau, 0.f, cap, nullptr, nullptr, nullptr, nullptr, nullptr,
                          true, d_rows, d_counts, h_counts, consumer_stream};
+    return coll_elect_each(ctx, c, q, a);
+}
+
+// The same two calls on a binary collection and a binary query bank that carries Hamming self distances (the header's "Hamming
+// Fast-Match"): coll_qbest_chunk's binary route -- one reverse FP4 sweep per chunk, the segmented election -- and the tail above.
+extern "C" int fm_collection_hamming_match_accepted_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap,
+                                                         int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+{
+    const CollEachArgs a{"fm_collection_hamming_match_accepted_each", true, tau, 0.f, cap, qidx, tidx, dist, ratio, n_accepted,
+                         false, nullptr, nullptr, nullptr, FM_NO_STREAM, true, "fm_collection_match_accepted_each"};
+    return coll_elect_each(ctx, c, q, a);
+}
+
+extern "C" int fm_collection_hamming_match_accepted_each_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap,
+                                                             int32_t* d_rows, int64_t* d_counts, int64_t* h_counts, void* consumer_stream)
+{
+    const CollEachArgs a{"fm_collection_hamming_match_accepted_each_dev", true, tau, 0.f, cap, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         true, d_rows, d_counts, h_counts, consumer_stream, true, "fm_collection_match_accepted_each_dev"};
     return coll_elect_each(ctx, c, q, a);
 }
 

@@ -1633,7 +1633,8 @@ int fm::refuse_bin(fm_ctx* ctx, const fm_bank* b, const char* who)
     if (int rc = refuse_wide(ctx, b, who)) return rc;
     if (!b || b->kind != FM_BANK_BIN) return FM_OK;
     return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": binary banks (FM_BANK_BIN, NORM_HAMMING) are served by fm_knn2, fm_knn, "
-                                      "fm_xcheck1, fm_knn2_ratio and fm_hamming_radius_match only");
+                                      "fm_xcheck1, fm_knn2_ratio, fm_hamming_radius_match and the Hamming Fast-Match calls (fm_hamming_self_dist, "
+                                      "fm_hamming_set_selfdist, fm_hamming_match_ratio, fm_hamming_match_accepted) only");
 }
 
 int fm::check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who, bool bin_ok)

@@ -1247,6 +1247,182 @@ extern "C" int fm_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks,
 }
 
 // ---------------------------------------------------------------------------------------
+// Hamming self distances (hamming.hip: ham_self_kernel, ham_self_merge_kernel)
+// ---------------------------------------------------------------------------------------
+// Self distances of n binary banks on the context's stream, each into d_out[i] (device, [banks[i]->n] float64).  Runs of
+// consecutive non-empty banks of one ksteps go through ONE sweep launch and one merge launch, up to "batch_group" banks
+// (at most kHamSelfMax); every bank under plan_hamming of its own size.  The workgroup tables of all launches are built first
+// and uploaded once (the context's page-locked table buffer), behind the partials in ws_partial, which the launches of the
+// call reuse in stream order.  Enqueue only.  timed: ev_k0 / ev_k1 around the (last) sweep launch.
+static int ham_selfdist_device(fm_ctx* ctx, int n, const fm_bank* const* banks, double* const* d_out, bool timed)
+{
+    struct Group { int first, count, wg0, wgs; };
+    std::vector<Group> groups;
+    std::vector<HamPlan> plans((size_t)n);
+    const int group_max = std::max(1, std::min(ctx->tune.batch_group, kHamSelfMax));
+    size_t max_part = 0;
+    int64_t total_wg = 0;
+    for (int i = 0; i < n;) {
+        if (banks[i]->n == 0) { ++i; continue; }
+        Group g{i, 0, (int)total_wg, 0};
+        size_t part = 0;
+        while (i < n && g.count < group_max && banks[i]->n > 0 && banks[i]->ksteps == banks[g.first]->ksteps) {
+            const HamPlan p = plan_hamming(banks[i]->n_pad, banks[i]->n_pad);
+            plans[(size_t)i] = p;
+            part += (p.partial_bytes(1) + 255) & ~(size_t)255;
+            g.wgs += p.nchunks * p.nsplit;
+            ++g.count; ++i;
+        }
+        total_wg += g.wgs;
+        max_part = std::max(max_part, part);
+        groups.push_back(g);
+    }
+    if (groups.empty()) return FM_OK;
+    if (total_wg > (int64_t)1 << 26) return fail(ctx, FM_EUNSUPPORTED, "fm_hamming_self_dist: more than 2^26 workgroups in one call");
+    const size_t tab_bytes = (size_t)total_wg * 16;
+    int rc;
+    if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, max_part + tab_bytes + 64)) != FM_OK) return rc;
+    if (ctx->tab_in_flight) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_tab)); ctx->tab_in_flight = false; }
+    if (!ctx->ev_tab) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming));
+    if (tab_bytes > ctx->h_tab_bytes) {
+        if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
+        ctx->h_tab = nullptr; ctx->h_tab_bytes = 0;
+        const size_t want = tab_bytes + tab_bytes / 4 + 4096;
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_tab, want, hipHostMallocDefault));
+        ctx->h_tab_bytes = want;
+    }
+    int* tab = (int*)ctx->h_tab;
+    char* d_tab = (char*)ctx->ws_partial + max_part;
+    for (const Group& g : groups) {
+        int* e = tab + (size_t)g.wg0 * 4;
+        for (int j = 0; j < g.count; ++j) {
+            const HamPlan& p = plans[(size_t)(g.first + j)];
+            // (a bank's workgroups in launch_hamming's order: the chunks of a split side by side)
+            for (int s = 0; s < p.nsplit; ++s)
+                for (int c = 0; c < p.nchunks; ++c) { e[0] = j; e[1] = c; e[2] = s; e[3] = 0; e += 4; }
+        }
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_tab, ctx->stream));
+    ctx->tab_in_flight = true;
+    for (const Group& g : groups) {
+        HamSelfArgs a{};
+        size_t at = 0;
+        for (int j = 0; j < g.count; ++j) {
+            const fm_bank* b = banks[g.first + j];
+            HamSelfBank& s = a.b[j];
+            s.rows4 = b->rows4;
+            s.partial = (unsigned long long*)((char*)ctx->ws_partial + at);
+            s.out = d_out[g.first + j];
+            s.n = (int)b->n;
+            s.W = 8 * b->dim;
+            s.plan = plans[(size_t)(g.first + j)];
+            at += (s.plan.partial_bytes(1) + 255) & ~(size_t)255;
+            ctx->pending_pairs += b->n * b->n;
+            ctx->pending_bytes += bank_bytes(b);
+        }
+        if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+        HIP_TRY(ctx, launch_hamming_self(a, g.count, banks[g.first]->ksteps, d_tab + (size_t)g.wg0 * 16, g.wgs, ctx->stream));
+        if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+        ctx->kernel_timed = timed;
+        HIP_TRY(ctx, launch_hamming_self_merge(a, g.count, ctx->stream));
+    }
+    return FM_OK;
+}
+
+// The checks of the Hamming self-distance calls: handles, then a binary bank (l2: the L2 call the message names)
+static int ham_bank_check(fm_ctx* ctx, const fm_bank* b, const char* who, const char* l2)
+{
+    if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
+    if (!b) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
+    if (b->kind != FM_BANK_BIN)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the bank must be binary (FM_BANK_BIN, fm_bank_create_bin); " + l2 + " is the L2 call");
+    return FM_OK;
+}
+
+extern "C" int fm_hamming_self_dist(fm_ctx* ctx, const fm_bank* bank, double* selfdist)
+{
+    int rc = ham_bank_check(ctx, bank, "fm_hamming_self_dist", "fm_self_dist");
+    if (rc != FM_OK) return rc;
+    const int64_t n = bank->n;
+    if (n == 0) return FM_OK;
+    if (!selfdist) return fail(ctx, FM_EINVAL, "fm_hamming_self_dist: output pointer is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, (size_t)n * 8 + 64)) != FM_OK) return rc;
+    double* d_sd = (double*)ctx->ws_in;
+    CallScope cs(ctx);
+    if ((rc = ham_selfdist_device(ctx, 1, &bank, &d_sd, true)) != FM_OK) return rc;
+    HIP_TRY(ctx, d2h(ctx, selfdist, d_sd, (size_t)n * 8));
+    return cs.finish();
+}
+
+extern "C" int fm_hamming_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks, double* const* out)
+{
+    const char* who = "fm_hamming_self_dist_batch";
+    if (!ctx) return fail(nullptr, FM_EINVAL, "fm_hamming_self_dist_batch: ctx is NULL");
+    if (n < 0) return fail(ctx, FM_EINVAL, "fm_hamming_self_dist_batch: n < 0");
+    if (n == 0) return FM_OK;
+    if (!banks) return fail(ctx, FM_EINVAL, "fm_hamming_self_dist_batch: banks is NULL");
+    for (int i = 0; i < n; ++i) {
+        if (int rc = ham_bank_check(ctx, banks[i], who, "fm_self_dist_batch")) return rc;
+        for (int j = 0; j < i; ++j) if (banks[j] == banks[i]) return fail(ctx, FM_EINVAL, "fm_hamming_self_dist_batch: a bank is listed twice");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<double*> d_out((size_t)n, nullptr);
+    std::vector<const fm_bank*> cb((size_t)n, nullptr);
+    bool any_out = false;
+    int rc;
+    for (int i = 0; i < n; ++i) {
+        fm_bank* b = banks[i];
+        if ((rc = bank_selfdist_alloc(ctx, b)) != FM_OK) return rc;
+        b->sdmax_rows = -1;           // (no ratio cut is built on Hamming self distances)
+        d_out[(size_t)i] = b->selfdist;
+        cb[(size_t)i] = b;
+        any_out = any_out || (out && out[i] && b->n > 0);
+    }
+    if (!any_out) {
+        // enqueue only: accounted at the next fm_sync like the other asynchronous calls (fm_self_dist_batch)
+        fm_ctx::PendingTimer tm;
+        if ((rc = take_timer(ctx, &tm)) != FM_OK) return rc;
+        const int64_t before = ctx->pending_pairs, before_b = ctx->pending_bytes;
+        ctx->pending_pairs = 0;
+        ctx->pending_bytes = 0;
+        HIP_TRY(ctx, hipEventRecord(tm.k0, ctx->stream));
+        rc = ham_selfdist_device(ctx, n, cb.data(), d_out.data(), false);
+        HIP_TRY(ctx, hipEventRecord(tm.k1, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(tm.c1, ctx->stream));
+        tm.timed = rc == FM_OK && ctx->pending_pairs > 0;
+        tm.call_timed = true;
+        tm.pairs = ctx->pending_pairs;
+        tm.bytes = ctx->pending_bytes;
+        ctx->pending_pairs = before;
+        ctx->pending_bytes = before_b;
+        ctx->pending.push_back(tm);
+        return rc;
+    }
+    CallScope cs(ctx);
+    if ((rc = ham_selfdist_device(ctx, n, cb.data(), d_out.data(), true)) != FM_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        if (out[i] && banks[i]->n > 0) HIP_TRY(ctx, d2h(ctx, out[i], d_out[(size_t)i], (size_t)banks[i]->n * 8));
+    return cs.finish();
+}
+
+extern "C" int fm_hamming_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* selfdist)
+{
+    int rc = ham_bank_check(ctx, bank, "fm_hamming_set_selfdist", "fm_bank_set_selfdist");
+    if (rc != FM_OK) return rc;
+    if (bank->n > 0 && !selfdist) return fail(ctx, FM_EINVAL, "fm_hamming_set_selfdist: selfdist is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = bank_selfdist_alloc(ctx, bank)) != FM_OK) return rc;
+    bank->sdmax_rows = -1;
+    if (bank->n > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(bank->selfdist, selfdist, (size_t)bank->n * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return FM_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // X1 (+R1) entry points
 // ---------------------------------------------------------------------------------------
 // Workspace of one bank pair in flight (async calls): partial | bound | qbest | tidx | dist | ratio | pass | block counts
@@ -1365,9 +1541,11 @@ struct AcceptedSink {
 
 // The argument checks the ratio calls share, in the order the header documents; n_host is zeroed on the way.  A pair without
 // query rows passes: the caller returns.
-static int ratio_call_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const AcceptedSink& out, const char* who)
+// ham: a binary pair that ham_pair_check (the fm_hamming_* entry points) has passed already -- handles, kinds, widths and the
+// self distances, in the order the header gives for them.
+static int ratio_call_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const AcceptedSink& out, const char* who, bool ham = false)
 {
-    int rc = check_pair(ctx, q, t, who);
+    int rc = ham ? FM_OK : check_pair(ctx, q, t, who);
     if (rc != FM_OK) return rc;
     if (out.n_host) *out.n_host = 0;
     if (q->n == 0) return FM_OK;
@@ -1424,9 +1602,10 @@ static int enqueue_tail(fm_ctx* ctx, hipStream_t ts, fm_ctx::AsyncSlot& sl, cons
 // The synchronous ratio calls (fm_match_ratio, fm_match_accepted, fm_match_accepted_dev, a float32 pair inside a batch): keys,
 // decode + ratio test, then by the sink -- every row and its flag (pass: fm_match_ratio's, optional), the compaction into
 // page-locked caller arrays directly, the compaction into ws_out and the staged delivery, or the device rows.
-static int ratio_sync(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, const AcceptedSink& out, uint8_t* pass, const char* who)
+static int ratio_sync(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, const AcceptedSink& out, uint8_t* pass, const char* who,
+                      bool ham = false)
 {
-    int rc = ratio_call_check(ctx, q, t, out, who);
+    int rc = ratio_call_check(ctx, q, t, out, who, ham);
     if (rc != FM_OK || q->n == 0) return rc;
     const bool compact = out.cap >= 0, to_device = out.to_device();
     const int64_t nq = q->n;
@@ -2189,6 +2368,48 @@ extern "C" int fm_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_ban
     if (int rc = check_device_rows(ctx, d_rows, d_count, "fm_match_accepted_dev")) return rc;
     if (q && q->n == 0) HIP_TRY(ctx, hipMemset(d_count, 0, 8));
     return ratio_sync(ctx, q, t, tau, device_sink(d_rows, d_count, n_accepted, cap, FM_NO_STREAM), nullptr, "fm_match_accepted_dev");
+}
+
+// ---- Hamming Fast-Match: the accepted-match test on binary banks (the header's section of that name) ---------------------
+// Steps 1 .. 4 of the documented error order; the entry points add cap and the NULL outputs, then ratio_sync runs the pair with
+// K11's reverse top-1 sweep (sweep_pair's binary route), the generic election and tail, and no ratio cut (an int8-route device).
+static int ham_pair_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who, const char* l2)
+{
+    if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
+    if (!q || !t) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
+    if (q->kind != FM_BANK_BIN || t->kind != FM_BANK_BIN)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": both banks must be binary (FM_BANK_BIN, fm_bank_create_bin); " + l2 + " is the L2 call");
+    if (q->dim != t->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": query/train width mismatch");
+    if (q->n > 0 && !q->selfdist)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": query bank has no self distances (fm_hamming_set_selfdist, fm_hamming_self_dist_batch)");
+    return FM_OK;
+}
+
+extern "C" int fm_hamming_match_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t* tidx,
+                                      float* dist, double* ratio, uint8_t* pass, int64_t* n_pass)
+{
+    if (int rc = ham_pair_check(ctx, q, t, "fm_hamming_match_ratio", "fm_match_ratio")) return rc;
+    return ratio_sync(ctx, q, t, tau, host_sink(nullptr, tidx, dist, ratio, n_pass, -1), pass, "fm_hamming_match_ratio", true);
+}
+
+extern "C" int fm_hamming_match_accepted(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
+                                         int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+{
+    if (int rc = ham_pair_check(ctx, q, t, "fm_hamming_match_accepted", "fm_match_accepted")) return rc;
+    if (cap < 0) return fail(ctx, FM_EINVAL, "fm_hamming_match_accepted: cap < 0");
+    return ratio_sync(ctx, q, t, tau, host_sink(qidx, tidx, dist, ratio, n_accepted, cap), nullptr, "fm_hamming_match_accepted", true);
+}
+
+extern "C" int fm_hamming_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
+                                             int32_t* d_rows, int64_t* d_count, int64_t* n_accepted)
+{
+    const char* who = "fm_hamming_match_accepted_dev";
+    if (int rc = ham_pair_check(ctx, q, t, who, "fm_match_accepted_dev")) return rc;
+    if (cap < 0) return fail(ctx, FM_EINVAL, "fm_hamming_match_accepted_dev: cap < 0");
+    if (!d_rows || !d_count) return fail(ctx, FM_EINVAL, "fm_hamming_match_accepted_dev: device output pointer is NULL");
+    if (int rc = check_device_rows(ctx, d_rows, d_count, who)) return rc;
+    if (q->n == 0) HIP_TRY(ctx, hipMemset(d_count, 0, 8));
+    return ratio_sync(ctx, q, t, tau, device_sink(d_rows, d_count, n_accepted, cap, FM_NO_STREAM), nullptr, who, true);
 }
 
 extern "C" int fm_match_accepted_dev_async(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,

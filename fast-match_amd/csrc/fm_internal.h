@@ -289,6 +289,21 @@ HamPlan plan_hamming(int64_t ncols_pad, int64_t nred_pad);
 // stage_real (train collections): real rows per 128-row stage of `red`, an index mask per stage; null = a plain bank
 hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const HamPlan& plan, unsigned long long* partial, hipStream_t stream,
                           const int* stage_real = nullptr);
+// Hamming self distances (fm_hamming_self_dist(_batch)): the top-1 sweep of up to kHamSelfMax banks of ONE ksteps against
+// themselves, the diagonal dropped, in one launch.  table (device, int4 per workgroup): {bank of the launch, chunk, split, 0};
+// bank j's keys go to b[j].partial in its plan's layout ([nsplit][ncols_alloc]), every word written.  The merge takes the
+// minimum over the splits and writes b[j].out[i] = (double)h, +inf where no candidate exists (a bank of one row).
+constexpr int kHamSelfMax = 16;
+struct HamSelfBank {
+    const uint8_t* rows4;                // the bank's FP4 image
+    unsigned long long* partial;
+    double* out;                         // [n]
+    int n, W;                            // real rows, bits per row
+    HamPlan plan;                        // plan_hamming(n_pad, n_pad)
+};
+struct HamSelfArgs { HamSelfBank b[kHamSelfMax]; };
+hipError_t launch_hamming_self(const HamSelfArgs& a, int nbanks, int ksteps, const void* d_table, int n_workgroups, hipStream_t stream);
+hipError_t launch_hamming_self_merge(const HamSelfArgs& a, int nbanks, hipStream_t stream);
 // packed rows + FP4 image of n device rows of `bytes` bytes, `pitch` bytes apart (0 = dense: an uploaded [n][bytes] matrix)
 // (b.n_pad, b.ksteps, b.rowsb, b.rows4 set by the caller)
 hipError_t launch_hamming_prep(const uint8_t* d_src, int64_t n, int bytes, const Bank& b, hipStream_t stream, int64_t pitch = 0);

@@ -23,11 +23,15 @@
 // partial[(split * ncols_alloc + c) * KTOP + k] = those keys, ascending, ~0 = none: the layout knn2_merge_kernel and
 // xcheck_scatter_kernel (api_match.hip) read on the float32 route -- the high word is the float32 bits of the distance.
 //
+// Hamming self distances (fm_hamming_self_dist(_batch)): ham_self_kernel, the top-1 sweep of a bank against itself with the
+// diagonal dropped, many banks per launch -- described where it stands, behind launch_hamming.
+//
 // k = 3 .. 8: a vector-ALU kernel in K9's shape (one query row per thread, train rows staged through LDS and read as
 // broadcasts, XOR + popcount on the packed rows, knnk_insert), merged by K9's merge kernel.  Off the hot path.
 #include "tile_ops.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace fm {
 
@@ -263,8 +267,177 @@ hipError_t launch_hamming(const Bank& cols, const Bank& red, int ktop, const Ham
     return hipErrorInvalidValue;
 }
 
+// ---- Hamming self distances: the top-1 sweep of a bank against itself, diagonal dropped ----------------------------------
+// selfdist[i] = min over j != i of h(i, j): fm_knn2(b, b)'s second column, the value only (cache.pyx:250-252 for L2).  The loop
+// is ham_sweep_kernel<1, KS>'s with cols = red = the bank.  In that kernel's lane map acc[r] of tile t is reduced row
+// sbase + 16 t + 4 g + r and the lane's output row is c, so the candidate (i, i) sits in ONE 16 x 16 tile per block b of a wave:
+// the wave's 64 output rows lie in stage 2 chunk + (wave >> 1), tiles 4 (wave & 1) .. + 3.  Only that stage runs the body with
+// the v_cmp / v_cndmask of the diagonal (DIAG); the test is wave-uniform (st, chunk and wave are), every other stage -- all but
+// one per wave -- runs K11's unmasked body.  Padding rows stay excluded by index (tail), as in K11.
+// One launch covers the banks of a Metric_Cache build (many small images): table[workgroup] = {bank, chunk, split, 0}, the
+// banks' arrays and plans in the kernel arguments.  Banks of one KS share a launch; W (bits per row) is per bank.
+// (The loop is restated here and not shared with ham_sweep_kernel, which stays as it was built and measured: its prologue reads
+// launch arguments where this one reads a table entry and a bank record, and its stage body has no second form.)
+template <int KS>
+__global__ __launch_bounds__(256)
+void ham_self_kernel(HamSelfArgs a, const int4* __restrict__ table)
+{
+    constexpr int RB = KS * 64;             // FP4 bytes per row
+    constexpr int LS = RB + 16;             // LDS row stride (ham_sweep_kernel's)
+    constexpr int PIECES = kStageRows * RB / 16 / 256;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2][kStageRows * LS];
+    const int4 e = table[blockIdx.x];
+    const HamSelfBank& bk = a.b[e.x];
+    const uint8_t* __restrict__ rows4 = bk.rows4;
+    const int n = bk.n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
+    const int chunk = e.y, split = e.z;
+    const int st0 = split * bk.plan.stages_per_split, st1 = min(bk.plan.nstages, st0 + bk.plan.stages_per_split);
+    const int diag_stage = 2 * chunk + (wave >> 1);
+
+    v8i_h bop[kHamNB][KS];
+#pragma unroll
+    for (int b = 0; b < kHamNB; ++b) {
+        const int c = chunk * kHamChunk + wave * 16 * kHamNB + 16 * b + (lane & 15);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const v4i x = c < n ? *(const v4i*)(rows4 + (size_t)c * RB + 64 * ks + 16 * g) : v4i{0, 0, 0, 0};
+            bop[b][ks] = v8i_h{x[0], x[1], x[2], x[3], 0, 0, 0, 0};
+        }
+    }
+    float bd0[kHamNB];
+    int bi0[kHamNB];
+#pragma unroll
+    for (int b = 0; b < kHamNB; ++b) { bd0[b] = -INFINITY; bi0[b] = -1; }
+
+    v4i pre[PIECES];
+    auto load = [&](int st) {
+#pragma unroll
+        for (int i = 0; i < PIECES; ++i) {
+            const int p = tid + 256 * i;
+            pre[i] = *(const v4i*)(rows4 + ((size_t)st * kStageRows) * RB + (size_t)p * 16);
+        }
+    };
+    auto store = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < PIECES; ++i) {
+            const int p = tid + 256 * i;
+            const int r = p / (RB / 16), c = p % (RB / 16);
+            *(v4i*)(&lds[buf][r * LS + 16 * c]) = pre[i];
+        }
+    };
+    float m1[kHamNB];
+    // one 128-row stage out of LDS buffer `buf` into m1[]; DIAG: the stage holds this wave's diagonal tiles
+    auto stage = [&](auto diag, int buf, int sbase, bool tail) {
+        constexpr bool DIAG = decltype(diag)::value;
+#pragma unroll
+        for (int t = 0; t < kStageRows / 16; ++t) {
+            v8i_h aop[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const v4i x = *(const v4i*)(&lds[buf][(16 * t + (lane & 15)) * LS + 64 * ks + 16 * g]);
+                aop[ks] = v8i_h{x[0], x[1], x[2], x[3], 0, 0, 0, 0};
+            }
+            const v4f_h cinit = {(31 - 4 * t) * (1.f / 32), (30 - 4 * t) * (1.f / 32), (29 - 4 * t) * (1.f / 32), (28 - 4 * t) * (1.f / 32)};
+#pragma unroll
+            for (int b = 0; b < kHamNB; ++b) {
+                v4f_h acc = cinit;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+                    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(aop[ks], bop[b][ks], acc, 4, 4, 0, 127, 0, 127);
+                if (tail) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[r] = (sbase + 16 * t + 4 * g + r < n) ? acc[r] : -INFINITY;
+                }
+                if constexpr (DIAG) {
+                    // reduced row == output row: 16 t + 4 g + r == 16 (4 (wave & 1) + b) + (lane & 15) inside the stage
+                    const int own = 16 * (4 * (wave & 1) + b - t) + (lane & 15) - 4 * g;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[r] = (own == r) ? -INFINITY : acc[r];
+                }
+                m1[b] = fmaxf(fmaxf(m1[b], acc[0]), acc[1]);
+                m1[b] = fmaxf(fmaxf(m1[b], acc[2]), acc[3]);
+            }
+        }
+    };
+    if (st0 < st1) { load(st0); store(0); }
+    __syncthreads();
+    for (int st = st0; st < st1; ++st) {
+        const int buf = (st - st0) & 1;
+        const bool more = st + 1 < st1;
+        if (more) load(st + 1);
+        const int sbase = st * kStageRows;
+        const bool tail = sbase + kStageRows > n;
+#pragma unroll
+        for (int b = 0; b < kHamNB; ++b) m1[b] = -INFINITY;
+        if (st == diag_stage) stage(std::true_type{}, buf, sbase, tail);
+        else                  stage(std::false_type{}, buf, sbase, tail);
+        // (a stage whose every candidate was dropped leaves -inf, which never passes the strict compare)
+#pragma unroll
+        for (int b = 0; b < kHamNB; ++b) {
+            const float f1 = floorf(m1[b]);
+            const int p1 = 31 - (int)((m1[b] - f1) * 32.f);
+            const int i1 = sbase + 16 * ((p1 >> 2) & 7) + 4 * g + (p1 & 3);
+            const bool up = f1 > bd0[b];
+            bd0[b] = up ? f1 : bd0[b];
+            bi0[b] = up ? i1 : bi0[b];
+        }
+        if (more) store(buf ^ 1);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int b = 0; b < kHamNB; ++b) {
+        unsigned long long k0 = ham_key(bd0[b], bi0[b], bk.W);
+#pragma unroll
+        for (int sh = 16; sh <= 32; sh <<= 1) {
+            const unsigned long long o0 = __shfl_xor(k0, sh);
+            k0 = o0 < k0 ? o0 : k0;
+        }
+        const int c = chunk * kHamChunk + wave * 16 * kHamNB + 16 * b + (lane & 15);
+        if (g == 0) bk.partial[(size_t)split * bk.plan.ncols_alloc + c] = k0;
+    }
+}
+
+// out[i] = (double)h of the smallest key over the splits, +inf where there is none; blockIdx.y = the bank of the launch
+__global__ __launch_bounds__(256)
+void ham_self_merge_kernel(HamSelfArgs a)
+{
+    const HamSelfBank& bk = a.b[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= bk.n) return;
+    unsigned long long k = ~0ull;
+    for (int s = 0; s < bk.plan.nsplit; ++s) {
+        const unsigned long long v = bk.partial[(size_t)s * bk.plan.ncols_alloc + i];
+        k = v < k ? v : k;
+    }
+    bk.out[i] = (k == ~0ull) ? (double)INFINITY : (double)__uint_as_float((unsigned)(k >> 32));
+}
+
+hipError_t launch_hamming_self(const HamSelfArgs& a, int nbanks, int ksteps, const void* d_table, int n_workgroups, hipStream_t stream)
+{
+    if (nbanks < 1 || nbanks > kHamSelfMax || n_workgroups < 1 || !d_table) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)n_workgroups), block(256);
+    switch (ksteps) {
+    case 1: hipLaunchKernelGGL((ham_self_kernel<1>), grid, block, 0, stream, a, (const int4*)d_table); break;
+    case 2: hipLaunchKernelGGL((ham_self_kernel<2>), grid, block, 0, stream, a, (const int4*)d_table); break;
+    case 3: hipLaunchKernelGGL((ham_self_kernel<3>), grid, block, 0, stream, a, (const int4*)d_table); break;
+    case 4: hipLaunchKernelGGL((ham_self_kernel<4>), grid, block, 0, stream, a, (const int4*)d_table); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_hamming_self_merge(const HamSelfArgs& a, int nbanks, hipStream_t stream)
+{
+    int nmax = 0;
+    for (int j = 0; j < nbanks; ++j) nmax = a.b[j].n > nmax ? a.b[j].n : nmax;
+    if (nbanks < 1 || nbanks > kHamSelfMax || nmax < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ham_self_merge_kernel, dim3((unsigned)((nmax + 255) / 256), (unsigned)nbanks), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
 // ---- k = 3 .. 8 on the vector ALUs ------------------------------------------------------------------------------------------
-constexpr int kHamKnnStage = 64;          // train rows per LDS stage (64 x at most 64 packed bytes)
+constexpr int kHamKnnStage = 64;         // train rows per LDS stage (64 x at most 64 packed bytes)
 
 // MASKED (K13, masked.hip): the thread's word of the bit mask per 64-row stage, one bit per candidate (as knn_k.hip's kernels).
 template <int K, int KS, bool MASKED = false>

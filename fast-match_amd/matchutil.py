@@ -17,6 +17,11 @@ Mirrors ``matchutil.py`` of the reference:
   ``cv2.BFMatcher(cv2.NORM_HAMMING).radiusMatch`` on binary descriptors (uint8 rows of 1 .. 64 bytes, or resident binary
   banks): every train row with ``popcount(q XOR t) < maxDistance`` (strict, float32: ``h <= H`` is ``H + 0.5``), one list
   per query row ascending by (h, train index) (``fm_hamming_radius_match``).  ``bf_radius_match`` stays the NORM_L2 call.
+* ``hamming_fast_match(dt1, dt2, tau, options={})`` / ``hamming_fast_match_arrays`` -- Fast-Match's accepted-match test on
+  binary descriptors: the cross-checked nearest neighbour t of q under ``popcount(q XOR t)`` is accepted iff
+  ``dist / selfdist(q) < tau``, ``selfdist(q)`` the Hamming distance from q to its nearest OTHER row of ``dt1``
+  (``fm_hamming_self_dist_batch``, ``fm_hamming_match_accepted``).  Against a collection, image by image:
+  ``BFMatcher(NORM_HAMMING).hammingFastMatchEach`` / ``hammingFastMatchEach_arrays``; ``fastMatchEach`` stays the NORM_L2 call.
 * ``options["normType"]``: ``NORM_L2`` (4, the default) or ``NORM_HAMMING`` (6) -- cv2's values.  With
   ``NORM_HAMMING`` the descriptors are binary (ORB, BRIEF, BRISK, FREAK, AKAZE: uint8 rows of 1 .. 64 bytes,
   ``Context.bank_binary``) and the distance is the bit count of ``q XOR t`` (``cv2.BFMatcher(cv2.NORM_HAMMING,
@@ -380,6 +385,39 @@ def hamming_radius_match(dt1, dt2, maxDistance, options={}):
     return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
 
 
+def hamming_fast_match_arrays(dt1, dt2, tau, options={}):
+    """Fast-Match's accepted-match test on binary descriptors: ``(qidx int32[m], tidx int32[m], dist float32[m], ratio
+    float64[m])``, ascending query index -- the pairs for which t is the cross-checked nearest neighbour of q under
+    ``popcount(q XOR t)`` and ``dist / selfdist(q) < tau``, selfdist(q) the Hamming distance from q to its nearest OTHER row
+    of ``dt1`` (computed on the device unless ``dt1`` is a resident bank that carries its own).  A query row with a duplicate
+    in ``dt1`` (selfdist 0) is never accepted.  ``dt1`` / ``dt2``: uint8 arrays of 1 .. 64 bytes per row or resident binary
+    banks.  ``ValueError`` before anything is uploaded: another dtype, widths that differ or lie outside 1 .. 64."""
+    try:
+        q, qw, _ = _binary_operand(dt1)
+        t, tw, _ = _binary_operand(dt2)
+    except ValueError as e:
+        raise ValueError(str(e).replace("hamming_radius_match", "hamming_fast_match").replace("bf_radius_match", "fastmatch"))
+    if qw != tw:
+        raise ValueError("hamming_fast_match: %d bytes per query row, %d per train row" % (qw, tw))
+    ctx = _context(options)
+    qb, q_tmp, tb, t_tmp = _bank_pair(ctx, q, t, NORM_HAMMING)
+    try:
+        if q_tmp or not qb.has_selfdist:
+            ctx.hamming_self_dist_batch([qb], want_host=False)
+        return ctx.hamming_match_accepted(qb, tb, tau)
+    finally:
+        if q_tmp:
+            qb.close()
+        if t_tmp:
+            tb.close()
+
+
+def hamming_fast_match(dt1, dt2, tau, options={}):
+    """ The accepted matches of hamming_fast_match_arrays as a list of DMatch, ascending query index """
+    qidx, tidx, dist, _ = hamming_fast_match_arrays(dt1, dt2, tau, options=options)
+    return [DMatch(int(qidx[j]), int(tidx[j]), dist[j]) for j in range(qidx.shape[0])]
+
+
 class BFMatcher(object):
     """``cv2.BFMatcher(normType, crossCheck)`` with cv2's method names.  With a train argument ``match`` / ``knnMatch`` /
     ``radiusMatch`` are :func:`bf_match` / :func:`bf_radius_match`; without one they run against the TRAIN COLLECTION
@@ -579,8 +617,8 @@ class BFMatcher(object):
         """A list of (qidx, tidx, dist, ratio) per image: Fast-Match's accepted matches of the query inside every image
         separately (``Collection.match_accepted_each``)."""
         if self.normType == NORM_HAMMING:
-            raise ValueError("BFMatcher.fastMatchEach: the self-distance test is not built for NORM_HAMMING (binary banks carry no "
-                             "self distances)")
+            raise ValueError("BFMatcher.fastMatchEach is the NORM_L2 call: hammingFastMatchEach runs the self-distance test of a "
+                             "NORM_HAMMING matcher")
         self._check_collection("BFMatcher.fastMatchEach")
         coll = self.train()
         qb, tmp = self._query(coll.ctx, queryDescriptors)
@@ -601,6 +639,35 @@ class BFMatcher(object):
         anything is uploaded."""
         out = []
         for i, (qidx, tidx, dist, _) in enumerate(self.fastMatchEach_arrays(queryDescriptors, tau)):
+            out.append([DMatch(int(qidx[j]), int(tidx[j]), dist[j], i) for j in range(qidx.shape[0])])
+        return out
+
+    def hammingFastMatchEach_arrays(self, queryDescriptors, tau):
+        """``fastMatchEach_arrays`` of a NORM_HAMMING matcher: a list of (qidx, tidx, dist, ratio) per image, slot i equal to
+        ``hamming_fast_match_arrays(query, image_i, tau)`` (``Collection.hamming_match_accepted_each``).  ``ValueError`` on a
+        NORM_L2 matcher, another dtype and an empty collection, before anything is uploaded."""
+        if self.normType != NORM_HAMMING:
+            raise ValueError("BFMatcher.hammingFastMatchEach needs a NORM_HAMMING matcher: fastMatchEach is the NORM_L2 call")
+        if not isinstance(queryDescriptors, _ffi.Bank) and np.asarray(queryDescriptors).dtype != np.uint8:
+            raise ValueError("NORM_HAMMING needs uint8 descriptors (cv2 asserts CV_8U), got %s" % np.asarray(queryDescriptors).dtype)
+        self._check_collection("BFMatcher.hammingFastMatchEach")
+        coll = self.train()
+        qb, tmp = self._query(coll.ctx, queryDescriptors)
+        try:
+            if tmp or not qb.has_selfdist:
+                coll.ctx.hamming_self_dist_batch([qb], want_host=False)        # attached on the device, nothing comes back
+            return coll.hamming_match_accepted_each(qb, tau)
+        finally:
+            if tmp:
+                qb.close()
+
+    def hammingFastMatchEach(self, queryDescriptors, tau):
+        """Fast-Match's accepted-match test of a NORM_HAMMING matcher against its collection, image by image: one list of
+        ``DMatch`` per added image (``imgIdx`` set) -- t is the cross-checked nearest neighbour of q inside that image and
+        ``popcount(q XOR t) / selfdist(q) < tau``, selfdist(q) the Hamming distance from q to its nearest OTHER query row
+        (computed on the device).  A query row with a duplicate (selfdist 0) is never accepted."""
+        out = []
+        for i, (qidx, tidx, dist, _) in enumerate(self.hammingFastMatchEach_arrays(queryDescriptors, tau)):
             out.append([DMatch(int(qidx[j]), int(tidx[j]), dist[j], i) for j in range(qidx.shape[0])])
         return out
 

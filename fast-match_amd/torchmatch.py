@@ -26,6 +26,10 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
   bytes per row, or binary ``Bank``s): every train row with ``popcount(q XOR t) < r`` (strict, float32 -- ``h <= H`` is
   ``r = H + 0.5``), ascending (h, index); ``r`` as in ``radius_match`` (``fm_hamming_radius_match_dev``).  ``radius_match``
   itself stays the L2 call.
+* ``hamming_fast_match(q, t, tau)`` -> ``(rows int32 [m, 3], count int64 [1])``: Fast-Match's accepted-match test on binary
+  descriptors -- (query, train row, float32 bits of ``popcount(q XOR t)``) of the cross-checked nearest neighbours with
+  ``dist / selfdist(q) < tau``; the query's Hamming self distances are computed on the device when its bank carries none
+  (``fm_hamming_self_dist_batch``, ``fm_hamming_match_accepted_dev``).
 
 * ``Collection(context=None)`` -- a train collection (``cv2.BFMatcher.add`` / ``train``) whose images are CUDA tensors: the
   retrieval flow extract -> ``add`` to the database -> query -> consume without a copy to the host.  A context manager.
@@ -37,6 +41,8 @@ leave the results in tensors the library's kernels write directly (``fm_knn_dev`
   ``hamming_radius_match(q, r)`` -> the same against a binary collection (``fm_collection_hamming_radius_match_dev``);
   ``fast_match_each(q, tau, cap=None)`` -> ``(rows int32 [n_images, cap, 3], counts int64 [n_images])``, the accepted-match
   test inside every image (``q``: a ``Bank`` carrying self distances, ``Context.self_dist_batch([q], want_host=False)``);
+  ``hamming_fast_match_each(q, tau, cap=None)`` -> the same two tensors on a binary collection (``q``: a binary ``Bank``
+  carrying Hamming self distances, ``Context.hamming_self_dist_batch``);
   ``mutual_nn_each(q, max_dist=None, cap=None)`` -> the same two tensors for the cross-checked 1-NN inside every image
   (``cv2.BFMatcher(norm, crossCheck=True).match(q, image)`` image by image, kept while ``dist < max_dist``), on uint8,
   float and binary collections alike;
@@ -381,6 +387,45 @@ def hamming_radius_match(q, t, r):
             b.close()
 
 
+def hamming_fast_match(q, t, tau):
+    """Fast-Match's accepted-match test on binary descriptors, left on the device: ``(rows int32 [m, 3] = (query, train row,
+    float32 bits of popcount(q XOR t)), count int64 [1])`` CUDA tensors, ascending query index -- t is the cross-checked
+    nearest neighbour of q and ``dist / selfdist(q) < tau``, selfdist(q) the Hamming distance from q to its nearest OTHER
+    query row (a row with a duplicate is never accepted).  ``q`` / ``t``: uint8 CUDA tensors of packed bits or binary
+    ``Bank``s; a query bank that carries no self distances gets them on the device (``fm_hamming_self_dist_batch``).  One host
+    wait, for the count that sizes ``rows``."""
+    import torch
+    who = "hamming_fast_match"
+    ops = [_binary_operand(who, x) for x in (q, t)]
+    widths = [x.dim if isinstance(x, _ffi.Bank) else x.shape[1] for x in ops]
+    if widths[0] != widths[1]:
+        raise ValueError("%s: %d bytes per query row, %d per train row" % (who, widths[0], widths[1]))
+    ctx = next((x.ctx for x in ops if isinstance(x, _ffi.Bank)), None)
+    made, banks = [], []
+    try:
+        for x in ops:
+            if not isinstance(x, _ffi.Bank):
+                x = bank(x, binary=True, context=ctx)
+                ctx = x.ctx
+                made.append(x)
+            banks.append(x)
+        qb, tb = banks
+        if not qb.has_selfdist:
+            qb.ctx.hamming_self_dist_batch([qb], want_host=False)
+        _, dev = _stream_and_device(qb.ctx)
+        cap = qb.n
+        rows = torch.empty((max(cap, 1), 3), dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        # (the call runs on the context's stream and returns when it is done: the fresh tensors must be ours by then)
+        with torch.cuda.device(dev):
+            torch.cuda.current_stream().synchronize()
+        m = qb.ctx.hamming_match_accepted_dev(qb, tb, float(tau), rows.data_ptr(), count.data_ptr(), cap)
+        return rows[:min(m, cap)], count
+    finally:
+        for b in made:
+            b.close()
+
+
 class Collection(object):
     """A train collection fed from CUDA tensors (module docstring).  The library's collection is made with the first call
     that needs it, on ``context`` or the default context of the first tensor's device."""
@@ -583,6 +628,25 @@ class Collection(object):
         counts = torch.zeros(ni, dtype=torch.int64, device=dev)
         coll.match_accepted_each_dev(q, float(tau), rows.data_ptr() if rows.numel() else 0, counts.data_ptr() if ni else 0, cap,
                                      consumer_stream=stream)
+        return rows, counts
+
+    def hamming_fast_match_each(self, q, tau, cap=None):
+        """``fast_match_each`` on a binary collection (``add(tensor, binary=True)``): ``q`` is a binary ``Bank`` that carries
+        Hamming self distances (``Context.hamming_self_dist_batch``); ``(rows, counts)`` as there, the distance bits those of
+        popcount(q XOR t); enqueued, no host wait."""
+        import torch
+        self._refuse_wide_collection("hamming_fast_match_each")
+        if not isinstance(q, _ffi.Bank) or q.kind != _ffi.FM_BANK_BIN:
+            raise ValueError("hamming_fast_match_each takes a resident binary Bank that carries Hamming self distances "
+                             "(Context.hamming_self_dist_batch); fast_match_each is the L2 call")
+        coll = self._collection(q.ctx)
+        ni = coll.info()[0]
+        cap = q.n if cap is None else int(cap)
+        stream, dev = _stream_and_device(q.ctx)
+        rows = torch.empty((ni, max(cap, 0), 3), dtype=torch.int32, device=dev)
+        counts = torch.zeros(ni, dtype=torch.int64, device=dev)
+        coll.hamming_match_accepted_each_dev(q, float(tau), rows.data_ptr() if rows.numel() else 0, counts.data_ptr() if ni else 0,
+                                             cap, consumer_stream=stream)
         return rows, counts
 
     def mutual_nn_each(self, q, max_dist=None, cap=None):

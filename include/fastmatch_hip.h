@@ -61,7 +61,10 @@ typedef struct fm_bank fm_bank;
  * fm_collection_pairs_mutual_ratio_dev; still revision 12, additions only -- fm_collection_add_wide,
  * fm_collection_add_wide_dev; still revision 12, additions only -- fm_hamming_radius_match, fm_hamming_radius_match_dev,
  * fm_collection_hamming_radius_match, fm_collection_hamming_radius_match_dev; still revision 12, additions only --
- * fm_collection_wide_knn2_each, fm_collection_wide_mutual_ratio_each, fm_collection_wide_mutual_ratio_each_dev).  A binding
+ * fm_collection_wide_knn2_each, fm_collection_wide_mutual_ratio_each, fm_collection_wide_mutual_ratio_each_dev; still
+ * revision 12, additions only -- fm_hamming_self_dist, fm_hamming_self_dist_batch, fm_hamming_set_selfdist,
+ * fm_hamming_match_ratio, fm_hamming_match_accepted, fm_hamming_match_accepted_dev,
+ * fm_collection_hamming_match_accepted_each, fm_collection_hamming_match_accepted_each_dev).  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.              */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -206,11 +209,16 @@ int  fm_bank_create_f32_route(fm_ctx* ctx, const float* rows, int64_t n, int dim
  * popcount).
  *   fm_hamming_radius_match(_dev), fm_collection_hamming_radius_match(_dev): radiusMatch on binary banks -- "Hamming radiusMatch"
  *     below, behind fm_radius_match.
+ *   fm_hamming_self_dist(_batch), fm_hamming_set_selfdist, fm_hamming_match_ratio, fm_hamming_match_accepted(_dev),
+ *     fm_collection_hamming_match_accepted_each(_dev): Fast-Match's self-distance test on binary banks -- "Hamming Fast-Match"
+ *     below, behind fm_hamming_radius_match.
  * Every other entry point that takes a bank refuses a binary one with FM_EUNSUPPORTED before any kernel reads it:
- * fm_radius_match(_dev) (the L2-named radius calls keep refusing: fm_hamming_radius_match is the call), fm_self_dist(_batch), fm_bank_set_selfdist, fm_match_ratio, fm_match_accepted*, fm_xcheck1_keys*,
+ * fm_radius_match(_dev) (the L2-named radius calls keep refusing: fm_hamming_radius_match is the call), fm_self_dist(_batch),
+ * fm_bank_set_selfdist, fm_match_ratio, fm_match_accepted* (the L2-named Fast-Match calls keep refusing too: the fm_hamming_*
+ * calls of "Hamming Fast-Match" are the ones that serve binary banks), fm_xcheck1_keys*,
  * fm_xcheck1_batched, fm_bank_refill_u8_async, fm_bank_append_*, fm_expand_create.  A binary bank paired with a non-binary one
- * is FM_EINVAL, even when one of them is empty.  Not built: NORM_HAMMING2, masked Hamming radius queries, binary descriptors
- * in the Fast-Match loop itself (self distances, fm_expand_*, batches, sharded keys), k > 8.                                    */
+ * is FM_EINVAL, even when one of them is empty.  Not built: NORM_HAMMING2, masked Hamming radius queries, the expansion loop
+ * (fm_expand_*) and the async / batch / sharded-key forms of the accepted-match test on binary banks, k > 8.                    */
 int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t n, int bytes, fm_bank** bank);
 /* ---- K14: wide float banks, 129 .. 256 values per row ---------------------------------------------------------------------
  * The 256-D float descriptors of learned extractors (SuperPoint and its kin).  fm_bank_create_f32, fm_bank_create_f32_route and
@@ -382,6 +390,45 @@ int fm_hamming_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, con
                             float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* idx, float* dist,
                             int64_t* n_total);
 
+/* ---- Hamming Fast-Match: the self-distance test on binary banks ----------------------------------------------------------
+ * Fast-Match's accepted-match test -- dist(q, t) / selfdist(q) < tau on the cross-checked 1-NN -- for binary descriptors
+ * (FM_BANK_BIN, K11).  fm_self_dist(_batch), fm_bank_set_selfdist, fm_match_ratio and fm_match_accepted* keep refusing binary
+ * banks; the calls below, with the argument lists of their L2 namesakes, are the ones that serve them.
+ *   selfdist[i] = (double) min over j != i of popcount(row_i XOR row_j), exact: the second column of fm_knn2(b, b), the value
+ *     only.  +inf for a bank of one row; 0 for a row that has a duplicate.
+ *   dist = (float)h(q, t); ratio = (double)dist / selfdist[q] in float64; a row is accepted iff ratio < tau.  So a query row
+ *     with a duplicate (selfdist 0) is never accepted -- d / 0 = +inf for d > 0 and 0 / 0 = NaN, neither is < tau -- and in a
+ *     bank of one query row (selfdist +inf) the ratio is 0, accepted for every tau > 0.
+ *   The cross-check is fm_xcheck1's Hamming contract: strict <, the lowest index wins a tie.
+ *   fm_hamming_self_dist: synchronous, as fm_self_dist.  fm_hamming_self_dist_batch: as fm_self_dist_batch -- the values are
+ *     attached to every bank on the device; with out NULL (or every out[i] NULL) the call only enqueues; a bank listed twice is
+ *     FM_EINVAL.  fm_hamming_set_selfdist attaches the caller's values (fm_bank_set_selfdist's rules).
+ *   fm_hamming_match_ratio / fm_hamming_match_accepted / fm_hamming_match_accepted_dev: outputs, compaction order, cap and
+ *     n_accepted are those of fm_match_ratio / fm_match_accepted / fm_match_accepted_dev, word for word.
+ * One FP4 matrix-core sweep of the bank against itself (hamming.hip, ham_self_kernel): K11's top-1 loop, the diagonal candidate
+ * dropped in the one stage per wave that holds it, every other stage K11's unmasked body; one launch covers up to "batch_group"
+ * banks of one K-step count through a (bank, chunk, split) table in device memory; a merge kernel takes the minimum over the
+ * splits.  Padding rows are kept out by INDEX (an all-zero FP4 row is W / 2 from everything; real neighbours can be farther).
+ * The match calls run the cross-check's sweep, election, ratio test and compaction of the L2 calls, without a ratio cut.
+ * Errors, in this order: NULL handles (and, for the collection forms, a collection of another context): FM_EINVAL; a bank or a
+ * collection that is not binary: FM_EINVAL, the message names the L2 call; widths that differ: FM_EINVAL; a query bank with
+ * rows but without self distances: FM_EINVAL ("no self distances"); cap < 0 and NULL outputs as in the L2 forms.  Empty banks
+ * and empty collections are valid.  fm_stats counts n * n pairs for a self sweep and nq * nt for a match; fm_bank_info is
+ * unchanged.
+ * Not built: a triangular sweep (every tile once, for both directions); an accepted-only Hamming sweep seeded with the ratio
+ * cut; fm_expand_* on binary banks; the async / batch / sharded-key forms (fm_match_accepted_async, _batch, _dev_async,
+ * _dev_batch, fm_xcheck1_keys*) for binary banks; NORM_HAMMING2.
+ * fm_collection_hamming_match_accepted_each(_dev): with the collections below.                                            */
+int fm_hamming_self_dist(fm_ctx* ctx, const fm_bank* bank, double* selfdist /*[n]*/);
+int fm_hamming_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks, double* const* out /*NULL, or [n] of NULL / [n_i]*/);
+int fm_hamming_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* selfdist /*[n]*/);
+int fm_hamming_match_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t* tidx /*[nq]*/,
+                           float* dist /*[nq]*/, double* ratio /*[nq] or NULL*/, uint8_t* pass /*[nq] or NULL*/, int64_t* n_pass);
+int fm_hamming_match_accepted(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
+                              int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted);
+int fm_hamming_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
+                                  int32_t* d_rows /*device [cap][3]*/, int64_t* d_count /*device*/, int64_t* n_accepted);
+
 /* ---- train collections: one query against many images ------------------------------------------------------------------
  * cv2.BFMatcher.add([d1, d2, ...]) / train() / clear() and then match(query) / knnMatch(query, k) against ALL added images,
  * every hit carrying DMatch.imgIdx.  The reference matches image pairs only (matchutil.py:39-43); "which image of my database
@@ -448,8 +495,15 @@ int fm_hamming_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, con
  *     per-image sweeps (K8 / K5) enqueued back to back, no host synchronisation between images.  Where the per-(image, query row)
  *     arrays exceed the option "coll_ws_bytes" the images run in chunks of consecutive images, enqueued back to back, one
  *     copy out.  Errors, in this order: NULL handles; a query of another kind or width (FM_EINVAL); a binary collection
- *     (FM_EUNSUPPORTED: a binary bank carries no self distances); a query without self distances (FM_EINVAL); cap < 0
- *     (FM_EINVAL).  nq = 0 writes zero counts and nothing else; n_images = 0 is valid.
+ *     (FM_EUNSUPPORTED: fm_collection_hamming_match_accepted_each serves it); a query without self distances (FM_EINVAL);
+ *     cap < 0 (FM_EINVAL).  nq = 0 writes zero counts and nothing else; n_images = 0 is valid.
+ *   fm_collection_hamming_match_accepted_each(_dev): the two calls above on a BINARY collection and a binary query bank that
+ *     carries Hamming self distances ("Hamming Fast-Match" above: fm_hamming_self_dist_batch / fm_hamming_set_selfdist): slot i
+ *     equals, row by row and bit for bit, fm_hamming_match_accepted(q, bank(image i), tau, cap).  One reverse FP4 sweep per
+ *     chunk of images and the segmented election of fm_collection_xcheck1_each, then the tail of the L2 form.  Errors, in this
+ *     order: NULL handles or a collection of another context; a collection (when it has rows) or a query bank that is not
+ *     binary (FM_EINVAL: fm_collection_match_accepted_each is the L2 call); widths that differ; a query with rows but without
+ *     self distances; cap < 0 and the NULL outputs of the L2 form.
  *   fm_collection_match_accepted_each_dev: the same with the results left on the device: 12-byte rows {query, train row in
  *     the image, float32 distance bits} of image i at d_rows + i * cap * 3, d_counts[i] = min(count, cap) (cap = 0: d_rows
  *     may be NULL).  Enqueued on the context's stream; consumer_stream is ordered against the fills in both directions, as in
@@ -569,7 +623,8 @@ int fm_hamming_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, con
  * image separately (an _each form, L2 or Hamming), skipping the second count sweep of the counts-then-fill pattern,
  * masks anywhere but in knnMatch (fm_collection_knn_masked is built; "masks" below lists what is not),
  * the expansion loop on a collection, a batched K8 / K11 (float32 / binary) per-image sweep,
- * binary collections in the self-distance test, sharding a collection across GPUs (radius queries included), removing single
+ * binary collections in the self-distance test THROUGH THE L2-NAMED CALLS (fm_collection_hamming_match_accepted_each(_dev)
+ * serve them), sharding a collection across GPUs (radius queries included), removing single
  * images, turning an integer-route collection of float32 images into a float32-route one for a
  * non-integer QUERY, and for fm_collection_pairs_mutual_ratio: a sweep that computes a pair's tiles once for both
  * directions (d(i, j) = d(j, i): half the matrix-core work of a pair), sharing sweeps between (a, b) and (b, a) of one
@@ -611,6 +666,12 @@ int  fm_collection_match_accepted_each(fm_ctx* ctx, fm_collection* coll, const f
 int  fm_collection_match_accepted_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
                                            int32_t* d_rows /*device [n_images][cap][3]*/, int64_t* d_counts /*device [n_images]*/,
                                            int64_t* h_counts /*host [n_images] or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_hamming_match_accepted_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
+                                               int32_t* qidx, int32_t* tidx, float* dist, double* ratio /* each [n_images][cap] */,
+                                               int64_t* n_accepted /*[n_images]: the full count per image*/);
+int  fm_collection_hamming_match_accepted_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
+                                                   int32_t* d_rows /*device [n_images][cap][3]*/, int64_t* d_counts /*device [n_images]*/,
+                                                   int64_t* h_counts /*host [n_images] or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 int  fm_collection_xcheck1_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, float max_dist,
                                 int32_t* tidx /*[n_images][nq] or NULL*/, float* dist /*[n_images][nq] or NULL*/,
                                 int64_t* n_matched /*[n_images] or NULL*/);
