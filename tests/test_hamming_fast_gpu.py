@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 EINVAL, EUNSUPPORTED = -1, -4
 INF = float("inf")
 SIZES = [1, 2, 3, 127, 128, 129, 255, 256, 257, 1300]
-WIDTHS = [1, 16, 17, 32, 61, 64]
+WIDTHS = [1, 16, 17, 32, 33, 40, 48, 61, 64]
 
 
 def _bits(a):

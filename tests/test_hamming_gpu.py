@@ -11,7 +11,7 @@ from fastmatch_amd import matchutil, _ffi
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = [1, 8, 16, 31, 32, 61, 64]
+WIDTHS = [1, 8, 16, 31, 32, 33, 40, 48, 61, 64]
 SHAPES = [(0, 5), (5, 0), (1, 1), (2, 2), (15, 17), (17, 15), (127, 129), (129, 127), (1000, 4099), (4099, 1000)]
 
 

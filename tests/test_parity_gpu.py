@@ -925,7 +925,7 @@ def test_results_do_not_depend_on_the_options():
 
 
 # ---- knnMatch for k > 2 (fm_knn) ---------------------------------------------------------
-@pytest.mark.parametrize("k", [1, 2, 3, 5, 8])
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_bf_match_for_any_k_up_to_8(ctx, k):
     """matchutil.bf_match(dt1, dt2, k) (matchutil.py:39-43: `k` is any int) == oracle.bf_knn on SIFT-like banks, on banks of
     duplicates and ties (lower train index first), in the float32-root tie range, on non-integer float32 banks, and on
