@@ -1156,7 +1156,7 @@ class Context(object):
         """Per-context tuning / batch shape (fm_ctx_set_option): "batch_group", "batch_tail", "nsplit", "nb",
         "nw", "nbuf", "prio", "glds", "coop", "f32_filter", "f32_nw", "f32_nsplit", "f32_fused", "f32_lpc", "f32_bound_every",
         "async_time_every", "k1_order", "bound_every", "self_tri", "tri_stages", "refill_grid", "expand_big", "expand_huge", "expand_delegate", "expand_grow", "expand_prof",
-        "radius_ws_bytes", "coll_ws_bytes", "fp6_filter", "fp6_cap", "masked_mfma", "mask_pack_words".  Results never depend on them."""
+        "radius_ws_bytes", "coll_ws_bytes", "fp6_filter", "fp6_cap", "fp6_nsplit", "masked_mfma", "mask_pack_words".  Results never depend on them."""
         self._check(self.lib.fm_ctx_set_option(self.handle, name.encode(), int(value)))
 
     def get_option(self, name):

@@ -465,6 +465,7 @@ static const OptionDef kOptions[] = {
     {"coll_ws_bytes", &Tuning::coll_ws_bytes, 0, 0x7fffffff, nullptr},
     {"masked_mfma", &Tuning::masked_mfma, 0, 1, nullptr}, {"mask_pack_words", &Tuning::mask_pack_words, 64, (1 << 26) - 4, nullptr},
     {"fp6_filter", &Tuning::fp6_filter, 0, 1, nullptr}, {"fp6_cap", &Tuning::fp6_cap, 1, 1 << 24, nullptr},
+    {"fp6_nsplit", &Tuning::fp6_nsplit, 0, 1 << 20, nullptr},
 };
 
 extern "C" int fm_ctx_set_option(fm_ctx* ctx, const char* name, int64_t value)
@@ -491,6 +492,7 @@ extern "C" int fm_ctx_get_option(fm_ctx* ctx, const char* name, int64_t* value)
         if (ctx->f6.cnt && ctx->f6_last_n > 0) {
             HIP_TRY(ctx, hipSetDevice(ctx->device));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->tails[fm_ctx::kTails - 1]));      // (a batched launch's rescoring and guard)
             HIP_TRY(ctx, hipMemcpy(w, ctx->f6.cnt, (size_t)ctx->f6_last_n * 8, hipMemcpyDeviceToHost));
             for (int i = 0; i < ctx->f6_last_n; ++i) *value += name[4] == 'r' ? (int64_t)w[2 * i] : (int64_t)(w[2 * i + 1] != 0);
         }
@@ -526,6 +528,7 @@ extern "C" int fm_ctx_create(int device_id, fm_ctx** out)
         return fail(nullptr, FM_EDEVICE, std::string("fm_ctx_create: ") + hipGetErrorString(e));
     }
     ctx->devname = std::string(prop.gcnArchName) + " " + prop.name;
+    ctx->ncu = prop.multiProcessorCount;
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
         std::string m = "fm_ctx_create: device is " + ctx->devname + "; this library is built for gfx950 only";
         delete ctx;
@@ -552,6 +555,10 @@ extern "C" int fm_ctx_create(int device_id, fm_ctx** out)
             (e = hipEventCreateWithFlags(&ctx->ev_tail_end[0], hipEventDisableTiming)) != hipSuccess ||
             (e = hipEventCreateWithFlags(&ctx->ev_tail_end[1], hipEventDisableTiming)) != hipSuccess ||
             (e = hipEventCreateWithFlags(&ctx->ev_tail_end[2], hipEventDisableTiming)) != hipSuccess ||
+            (e = hipEventCreateWithFlags(&ctx->ev_f6_sweep[0], hipEventDisableTiming)) != hipSuccess ||
+            (e = hipEventCreateWithFlags(&ctx->ev_f6_sweep[1], hipEventDisableTiming)) != hipSuccess ||
+            (e = hipEventCreateWithFlags(&ctx->ev_f6_done[0], hipEventDisableTiming)) != hipSuccess ||
+            (e = hipEventCreateWithFlags(&ctx->ev_f6_done[1], hipEventDisableTiming)) != hipSuccess ||
             (e = hipEventCreateWithFlags(&ctx->aslot[0].k_done, hipEventDisableTiming)) != hipSuccess ||
             (e = hipEventCreateWithFlags(&ctx->aslot[1].k_done, hipEventDisableTiming)) != hipSuccess) {
             fm_ctx_destroy(ctx);
@@ -567,7 +574,7 @@ extern "C" int fm_ctx_create(int device_id, fm_ctx** out)
     ctx->dbg_f32 = getenv("FM_F32_DEBUG") != nullptr;
     ctx->dbg_expand = getenv("FM_EXPAND_DEBUG") != nullptr;
     ctx->dbg_park = ctx->dbg_expand && getenv("FM_PARK_PROF") != nullptr;
-    if (hipMalloc((void**)&ctx->d_cut, kRRBatchMax * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); ctx->d_cut = nullptr; }
+    if (hipMalloc((void**)&ctx->d_cut, 2 * kRRBatchMax * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); ctx->d_cut = nullptr; }
     if (hipMalloc((void**)&ctx->d_counters, filter_flag_bytes()) != hipSuccess || hipMemset(ctx->d_counters, 0, filter_flag_bytes()) != hipSuccess) {
         (void)hipGetLastError();
         ctx->d_counters = nullptr;
@@ -604,7 +611,9 @@ extern "C" int fm_ctx_destroy(fm_ctx* ctx)
     if (ctx->ws_partial) (void)hipFree(ctx->ws_partial);
     if (ctx->ws_out) (void)hipFree(ctx->ws_out);
     if (ctx->ws_in) (void)hipFree(ctx->ws_in);
-    if (ctx->ws_f6) (void)hipFree(ctx->ws_f6);
+    for (void* w : ctx->ws_f6) if (w) (void)hipFree(w);
+    for (hipEvent_t ev : ctx->ev_f6_sweep) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : ctx->ev_f6_done) if (ev) (void)hipEventDestroy(ev);
     for (void* w : {ctx->ws_rrows, ctx->ws_rkeys, ctx->ws_rtmp}) if (w) (void)hipFree(w);
     if (ctx->h_scratch) (void)hipHostFree(ctx->h_scratch);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);

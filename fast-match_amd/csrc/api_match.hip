@@ -362,23 +362,31 @@ __global__ void ratio_cut_kernel(CutArgs a)
     if (i < a.n && a.sdmax[i]) a.out[i] = ratio_cut_d2(__longlong_as_double((long long)*a.sdmax[i]), a.tau);
 }
 
-// The accepted-only calls: the cut words of pairs (q[i], -) into ctx->d_cut, enqueued on ctx->stream in front of their K1
-// (which reads them on the same stream).  cut[i] = null for a pair without one: a query bank whose self distances were not
+// The accepted-only calls: the cut words of pairs (q[i], -) into the other set of ctx->d_cut than the last call's, enqueued
+// on ctx->stream in front of their K1 (which reads them on the same stream) and behind the rescoring that read that set
+// last, if it ran beside the stream.  cut[i] = null for a pair without one: a query bank whose self distances were not
 // reduced for all of its current rows (a refill to more rows than they were computed for), or no device words.
 int enqueue_ratio_cut(fm_ctx* ctx, int n, const fm_bank* const* q, double tau, const unsigned** cut)
 {
     CutArgs a{};
     bool any = false;
     ctx->cut_tau_ok = tau == tau;
+    const int set = ctx->f6_set ^ 1;
+    unsigned* const words = ctx->d_cut ? ctx->d_cut + set * kRRBatchMax : nullptr;
     for (int i = 0; i < n; ++i) {
         const fm_bank* b = q[i];
-        const bool ok = ctx->d_cut && b->kind == FM_BANK_I8 && b->sdmax && b->sdmax_rows >= b->n;
+        const bool ok = words && b->kind == FM_BANK_I8 && b->sdmax && b->sdmax_rows >= b->n;
         a.sdmax[i] = ok ? b->sdmax : nullptr;
-        cut[i] = ok ? ctx->d_cut + i : nullptr;
+        cut[i] = ok ? words + i : nullptr;
         any = any || ok;
     }
     if (!any) return FM_OK;
-    a.out = ctx->d_cut;
+    ctx->f6_set = set;
+    if (ctx->f6_off_stream[set]) {
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_f6_done[set], 0));
+        ctx->f6_off_stream[set] = false;
+    }
+    a.out = words;
     a.tau = tau;
     a.n = n;
     hipLaunchKernelGGL(ratio_cut_kernel, dim3(1), dim3(64), 0, ctx->stream, a);
@@ -390,11 +398,15 @@ const Filter6Ws* filter6_ws(fm_ctx* ctx, int n)
 {
     if (ctx->tune.fp6_filter == 0 || !ctx->cut_tau_ok || n < 1 || n > kRRBatchMax) return nullptr;
     const size_t cap = (size_t)ctx->tune.fp6_cap;
+    const int set = ctx->f6_set;             // (the cut words' set: its last rescoring is already waited for)
     // (a larger list is a new allocation: hipFree waits for the launches that still read the old one)
-    if (ws_ensure(ctx, &ctx->ws_f6, &ctx->ws_f6_bytes, 256 + (size_t)n * cap * 8) != FM_OK) { (void)hipGetLastError(); return nullptr; }
-    ctx->f6.cnt = (unsigned*)ctx->ws_f6;
-    ctx->f6.rec = (uint2*)((char*)ctx->ws_f6 + 256);
+    if (ws_ensure(ctx, &ctx->ws_f6[set], &ctx->ws_f6_bytes[set], 256 + (size_t)n * cap * 8) != FM_OK) { (void)hipGetLastError(); return nullptr; }
+    ctx->f6.cnt = (unsigned*)ctx->ws_f6[set];
+    ctx->f6.rec = (uint2*)((char*)ctx->ws_f6[set] + 256);
     ctx->f6.cap = (unsigned)cap;
+    ctx->f6.nsplit = ctx->tune.fp6_nsplit > 0 ? ctx->tune.fp6_nsplit : ctx->tune.nsplit > 0 ? -1 : 0;
+    ctx->f6.resident = ctx->ncu > 0 ? ctx->ncu : 256;
+    ctx->f6.side = nullptr;  ctx->f6.ev_sweep = ctx->f6.ev_done = nullptr;
     ctx->f6_last_n = n;
     return &ctx->f6;
 }
@@ -2329,13 +2341,21 @@ static int batch_common(fm_ctx* ctx, int32_t n, const fm_bank* const* q, const f
         const unsigned* cut[kRRBatchMax];
         if ((rc = enqueue_ratio_cut(ctx, g, q + i, tau, cut)) != FM_OK) { ctx->timer_pool.push_back(tm); return rc; }
         HIP_TRY(ctx, hipEventRecord(tm.k0, ctx->stream));
-        HIP_TRY(ctx, launch_rowreduce_batch(g, cols, red, pls, part, bnd, ctx->stream, false, cut, filter6_ws(ctx, g)));
+        // The filter's rescoring and its guarded K1 go to the last tail stream, beside the next launch's sweep; the pairs'
+        // tails then follow the guard's event.  tm.k1 stays on the sweep's stream: with the filter, k0 .. k1 is the sweep alone.
+        const Filter6Ws* f6 = filter6_ws(ctx, g);
+        const int set = ctx->f6_set;
+        if (f6) { ctx->f6.side = ctx->tails[fm_ctx::kTails - 1];  ctx->f6.ev_sweep = ctx->ev_f6_sweep[set];  ctx->f6.ev_done = ctx->ev_f6_done[set]; }
+        bool moved = false;
+        HIP_TRY(ctx, launch_rowreduce_batch(g, cols, red, pls, part, bnd, ctx->stream, false, cut, f6, &moved));
         HIP_TRY(ctx, hipEventRecord(tm.k1, ctx->stream));
+        if (moved) ctx->f6_off_stream[set] = true;
+        hipEvent_t handover = moved ? ctx->ev_f6_done[set] : tm.k1;
         for (int j = 0; j < g; ++j) {
             const int k = i + j;
             hipStream_t ts = ctx->tails[j % fm_ctx::kTails];
             fm_ctx::AsyncSlot& sl = ctx->bslot[(size_t)slot_of[j]];
-            HIP_TRY(ctx, hipStreamWaitEvent(ts, tm.k1, 0));
+            HIP_TRY(ctx, hipStreamWaitEvent(ts, handover, 0));
             if ((rc = enqueue_tail(ctx, ts, sl, L[j], q[k], t[k], pls[j], tau, al[j])) != FM_OK) { ctx->pending.push_back(tm); return rc; }     // (events are in flight: drained at fm_sync)
             HIP_TRY(ctx, hipEventRecord(sl.tail_done, ts));
             sl.in_use = true;

@@ -37,13 +37,20 @@ struct fm_ctx {
     // configuration: fm_ctx_set_option (the FM_* environment variables seed it at creation)
     fm::Tuning tune;
     int* d_counters = nullptr;   // device words of the fp16 filter (layout: fm_internal.h, launch_filter)
-    unsigned* d_cut = nullptr;   // [kRRBatchMax] D* of the ratio test per pair of the next K1 launch (ratio_cut.h; on `stream`
-                                 // only: ratio_cut_kernel writes it in front of the K1 that reads it); null: no cut
-    // FP6 filter of the accepted-only sweeps (filter6.hip): the record lists and (count, need_k1) words of ONE launch's pairs
-    // -- the filter, its rescoring and the guarded K1 follow each other on `stream`, so consecutive launches share them
-    void*  ws_f6 = nullptr;      size_t ws_f6_bytes = 0;
-    fm::Filter6Ws f6{nullptr, 0, nullptr};
+    unsigned* d_cut = nullptr;   // [2][kRRBatchMax] D* of the ratio test per pair of the next K1 launch (ratio_cut.h):
+                                 // ratio_cut_kernel writes set `f6_set` on `stream` in front of the K1 that reads it; null: no cut
+    // FP6 filter of the accepted-only sweeps (filter6.hip): the record lists and (count, need_k1) words of ONE launch's pairs,
+    // twice.  fm_match_accepted_batch moves the rescoring and the guarded K1 of a launch to the last tail stream, beside the
+    // NEXT launch's sweep on `stream`: consecutive launches alternate between the two sets (cut words, lists, counts), and a
+    // launch waits for the rescoring that last used its set (ev_f6_done, recorded on that tail stream only; ev_f6_sweep, "the
+    // sweep is done", on `stream` only).  Every other caller keeps the three kernels on `stream`.
+    void*  ws_f6[2] = {nullptr, nullptr};  size_t ws_f6_bytes[2] = {0, 0};
+    fm::Filter6Ws f6{nullptr, 0, nullptr};      // the set of the last launch
+    int    f6_set = 0;                          // the set the last enqueue_ratio_cut chose
+    hipEvent_t ev_f6_sweep[2] = {nullptr, nullptr}, ev_f6_done[2] = {nullptr, nullptr};
+    bool   f6_off_stream[2] = {false, false};   // the set's last rescoring runs beside `stream`: ev_f6_done[set] orders its next user
     bool   cut_tau_ok = false;   // the last enqueue_ratio_cut had a tau that is not NaN
+    int    ncu = 0;              // the device's CUs (the FP6 filter's split rule counts rounds of them)
     int    f6_last_n = 0;        // pairs of the last filter launch (options "fp6_records" / "fp6_fallbacks" read their words)
     int64_t filter_launches = 0;
     unsigned long long* h_scratch = nullptr;   // pinned host words the kernels can write (counts)

@@ -2,9 +2,11 @@
 //
 // The accepted-only calls hand K1 the ratio test's distance cut D* (ratio_cut.h): only candidates at d2 < D* can reach the
 // output, and on descriptor data those are a few in a million.  K1 still pays the full int8 MFMA rate to find them.  This
-// file sweeps K1's splits of the streamed bank, two of K1's 512-row output chunks per workgroup, with K1's staging -- three
-// LDS stage buffers filled by LDS-DMA two stages ahead, the source-side XOR swizzle, the hand-over waits, the s_setprio
-// burst -- but on v_mfma_scale_f32_32x32x64_f8f6f4 with e2m3 operands: a wave holds 128 output rows and multiplies a 32-row
+// file sweeps splits of the streamed bank -- its own count of them, chosen for the launch as a whole (fp6_plan.h: one
+// workgroup fills a CU, K1's count was tuned for 16 waves per CU) --, two of K1's 512-row output chunks per workgroup, with
+// K1's staging -- three LDS stage buffers filled by LDS-DMA two stages ahead, the source-side XOR swizzle, the hand-over
+// waits, the s_setprio burst -- but on v_mfma_f32_32x32x64_f8f6f4 with e2m3 operands (cbsz:2 blgp:2, the form without
+// scale operands: the builtin with all four scale arguments 0): a wave holds 128 output rows and multiplies a 32-row
 // unit of the streamed bank against them with 8 instructions.  FP6 is lossy, so the sweep is a FILTER with a static
 // per-row threshold that provably keeps every candidate at d2 <= D* - 1 (fp6_filter.h); there are no shared bounds, no
 // atomics on the fast path and no top-K state.  A lane whose 16 candidates of a 32-row unit (one output row, half of the
@@ -12,10 +14,12 @@
 // pair's list when it is full and when its sweep ends;
 // rescore6_kernel then computes the exact int32 d2 of each listed row against those 16 streamed rows from the int8
 // plane, as K1 does, and folds (d2 << 32 | row) into slice 0 of the pair's `partial` with a 64-bit atomic minimum -- the key
-// K1 writes and the order the election reduces with (lowest streamed row on ties).  The sweep's workgroups preset their
-// own (split, chunk) piece of `partial` to "none", so the kernels behind it see K1's layout.
+// K1 writes and the order the election reduces with (lowest streamed row on ties).  The sweep's workgroups preset K1's
+// slices of `partial` for their output rows to "none" (split f of the filter takes slices f, f + nsplit_f, ...), so the
+// kernels behind it see K1's layout.
 // A list that overflows, or a pair without a finite cut, sets the pair's need_k1 word; the guarded K1 launch behind the
-// rescoring (rowreduce.hip) then redoes such pairs in full.  Nothing waits on the host.
+// rescoring (rowreduce.hip) then redoes such pairs in full.  Nothing waits on the host.  The batched call runs the
+// rescoring and the guard on a stream beside the sweep's (Filter6Ws::side), under the next launch's sweep.
 //
 // Bank plane (Bank::rows6 / aux6 / stat6 / max6, prep6_kernel): the 128 codes of a row as four K-chunks of 32 codes (24
 // bytes) in 32-byte slots -- a row stays 128 bytes, so K1's LDS image and its swizzle carry over; lane (row, half) of a
@@ -23,6 +27,7 @@
 // instruction's k order cancels.
 #include "tile_ops.h"
 #include "fp6_filter.h"
+#include "fp6_plan.h"
 
 namespace fm {
 
@@ -52,7 +57,8 @@ struct F6Params {
     const uint8_t* red_rows6;
     const float*   red_aux6;      // [stage][256]: accumulator start of the stage's 128 rows, 128 unused words
     const int32_t* red_max;       // [2]: largest |m|^2, largest |m - m^|^2 of the streamed bank
-    int            nstages, nsplit, nchunks, stages_per_split, ncols_alloc;
+    int            nstages, nsplit, nchunks, stages_per_split, ncols_alloc;      // K1's plan: the layout of `partial`
+    int            nsplit_f, stages_per_split_f;                                 // the filter's own splits of the streamed bank (fp6_plan.h)
     unsigned long long* partial;  // K1's [nsplit][ncols_alloc] keys
     const unsigned* cut;          // device word D*
     uint2*         rec;           // the pair's list: (output row, 32-row unit of the streamed bank | half of the unit << 31)
@@ -111,7 +117,7 @@ __device__ __forceinline__ float f6_max16(const v16f_6& a)
     return fmaxf(m5, m6);
 }
 
-// The sweep on v_mfma_scale_f32_32x32x64_f8f6f4: a wave owns 128 output rows (4 blocks of 32, the stationary B operand: 48
+// The sweep on v_mfma_f32_32x32x64_f8f6f4: a wave owns 128 output rows (4 blocks of 32, the stationary B operand: 48
 // registers) and multiplies every 32-row unit of the streamed bank against them with 8 instructions, two per block chained
 // along K.  The reads of a unit are issued one unit ahead into a second register set, across the stage hand-over too: a
 // wave enters the barrier with the last unit of the stage it leaves in registers and multiplies it behind the barrier.
@@ -131,7 +137,7 @@ void filter6_kernel(F6Batch b)
     const int r32  = lane & 31;
     const int hs   = lane >> 5;
     // everything the loop uses, once: a field read through `p` inside the loop is a scalar load of the kernel argument there
-    const int nsplit = p.nsplit, nstages = p.nstages, per = p.stages_per_split, ncols = p.ncols, ncols_pad = p.ncols_pad;
+    const int nsplit = p.nsplit_f, nstages = p.nstages, per = p.stages_per_split_f, ncols = p.ncols, ncols_pad = p.ncols_pad;
     const int ncols_alloc = p.ncols_alloc;
     const int nch = (p.nchunks + 1) >> 1;
     const uint8_t* const red_rows6 = p.red_rows6;
@@ -152,12 +158,17 @@ void filter6_kernel(F6Batch b)
         if (tid == 0) cnt[1] = 1u;
         return;
     }
-    // this workgroup's pieces of K1's key array start empty (the rescoring folds into slice 0 after this kernel); an odd
-    // number of K1 chunks leaves the last workgroup's second piece outside the array
+    // this workgroup's pieces of K1's key array start empty (the rescoring folds into slice 0 after this kernel): of K1's
+    // slices of its rows -- the election reads them all -- the filter's split f takes s = f, f + nsplit_f, ... below K1's
+    // count (none where f is beyond it); an odd number of K1 chunks leaves the last workgroup's second piece outside the array
     {
-        unsigned long long* mine = p.partial + (size_t)split * ncols_alloc + chunk * kF6ChunkRows;
-        mine[tid] = ~0ull;
-        if (chunk * kF6ChunkRows + kF6PieceRows < ncols_alloc) mine[kF6PieceRows + tid] = ~0ull;
+        const int nslices = p.nsplit;
+        const bool second = chunk * kF6ChunkRows + kF6PieceRows < ncols_alloc;
+        for (int s = split; s < nslices; s += nsplit) {
+            unsigned long long* mine = p.partial + (size_t)s * ncols_alloc + chunk * kF6ChunkRows;
+            mine[tid] = ~0ull;
+            if (second) mine[kF6PieceRows + tid] = ~0ull;
+        }
     }
 
     // stationary operand: per block j and K-half h, slot 2 h + (lane >> 5) (32 codes, 24 of 32 bytes) of output row
@@ -300,7 +311,7 @@ void filter6_kernel(F6Batch b)
         for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int j = 0; j < kF6NC; ++j)
-                acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(x.a[h], bf[j][h], h == 0 ? x.c : acc[j], 2, 2, 0, 127, 0, 127);
+                acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(x.a[h], bf[j][h], h == 0 ? x.c : acc[j], 2, 2, 0, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (decltype(yu_tag)::value >= 0) read_unit(y, ybuf, decltype(yu_tag)::value);
         __builtin_amdgcn_s_setprio(0);
@@ -481,15 +492,20 @@ bool filter6_usable(const Bank& cols, const Bank& red)
            cols.rows6 && red.rows6 && cols.rows8 && red.rows8;
 }
 
-// The filter sweep and the rescoring of n pairs, pair i under plans[i] (K1's batched shape) with the list rec + i * cap and
-// the words cnt + 2 i ([0] count, [1] need_k1, zeroed here).  The guarded K1 launch follows in launch_rowreduce_batch.
+// The filter sweep and the rescoring of n pairs, pair i under plans[i] (K1's batched shape: the layout of its keys) with the
+// list ws.rec + i * ws.cap and the words ws.cnt + 2 i ([0] count, [1] need_k1, zeroed here).  The streamed banks are split
+// by the filter's own rule for the launch as a whole (fp6_plan.h) unless ws.nsplit forces a count or K1's.  The guarded K1
+// launch follows in launch_rowreduce_batch.
 hipError_t launch_filter6(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
-                          unsigned long long* const* partial, const unsigned* const* cut, uint2* rec, unsigned cap,
-                          unsigned* cnt, hipStream_t stream)
+                          unsigned long long* const* partial, const unsigned* const* cut, const Filter6Ws& ws, hipStream_t stream)
 {
     if (n < 1 || n > kRRBatchMax) return hipErrorInvalidValue;
+    uint2* const rec = ws.rec;  const unsigned cap = ws.cap;  unsigned* const cnt = ws.cnt;
     F6Batch b;
     long long total = 0;
+    Fp6PlanPair pp[kRRBatchMax];
+    for (int i = 0; i < n; ++i) pp[i] = Fp6PlanPair{(plans[i].nchunks + 1) / 2, (int)(red[i]->n_pad / kStageRows)};
+    const int L = ws.nsplit == 0 ? fp6_plan_stages(pp, n, ws.resident, kFp6PlanOverhead) : 0;
     for (int i = 0; i < n; ++i) {
         const RowReducePlan& pl = plans[i];
         if (pl.nb != 4 || pl.nw != 8 || !filter6_usable(*cols[i], *red[i]) || !cut[i]) return hipErrorInvalidValue;
@@ -498,12 +514,15 @@ hipError_t launch_filter6(int n, const Bank* const* cols, const Bank* const* red
         p.red_rows6 = red[i]->rows6;   p.red_aux6 = red[i]->aux6;    p.red_max = red[i]->max6;
         p.nstages = (int)(red[i]->n_pad / kStageRows);
         p.nsplit = pl.nsplit;  p.nchunks = pl.nchunks;  p.stages_per_split = pl.stages_per_split;  p.ncols_alloc = pl.ncols_alloc;
+        if (ws.nsplit < 0)      { p.nsplit_f = pl.nsplit;  p.stages_per_split_f = pl.stages_per_split; }
+        else if (ws.nsplit > 0) fp6_plan_split_forced(p.nstages, ws.nsplit, &p.nsplit_f, &p.stages_per_split_f);
+        else                    fp6_plan_split(p.nstages, L, &p.nsplit_f, &p.stages_per_split_f);
         p.partial = partial[i];  p.cut = cut[i];
         p.rec = rec + (size_t)i * cap;  p.cap = cap;  p.cnt = cnt + 2 * i;
         p.col_rows8 = cols[i]->rows8;  p.col_norm = cols[i]->norm;  p.red_rows8 = red[i]->rows8;  p.red_norm = red[i]->norm;
         p.nred = (int)red[i]->n;
         b.first_block[i] = (int)total;
-        total += (long long)((pl.nchunks + 1) / 2) * pl.nsplit;      // a workgroup takes two of K1's chunks
+        total += (long long)((pl.nchunks + 1) / 2) * p.nsplit_f;     // a workgroup takes two of K1's chunks
     }
     if (total > INT32_MAX) return hipErrorInvalidValue;
     for (int i = n; i < kRRBatchMax; ++i) b.p[i] = b.p[0];
@@ -514,7 +533,12 @@ hipError_t launch_filter6(int n, const Bank* const* cols, const Bank* const* red
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(filter6_kernel, dim3((unsigned)total), dim3(64 * kF6NW), 0, stream, b);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(rescore6_kernel, dim3(1024), dim3(256), 0, stream, b);
+    hipStream_t tail = stream;
+    if (ws.side) {          // the rescoring beside whatever follows the sweep on its stream
+        if ((e = hipEventRecord(ws.ev_sweep, stream)) != hipSuccess || (e = hipStreamWaitEvent(ws.side, ws.ev_sweep, 0)) != hipSuccess) return e;
+        tail = ws.side;
+    }
+    hipLaunchKernelGGL(rescore6_kernel, dim3(1024), dim3(256), 0, tail, b);
     return hipGetLastError();
 }
 

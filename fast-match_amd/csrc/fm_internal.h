@@ -165,6 +165,7 @@ struct Tuning {
                                       // query row whose list needs more still runs, in a chunk of its own
     int fp6_filter = 1;               // accepted-only sweeps with a ratio cut: 1 = FP6 filter + exact rescoring (filter6.hip), 0 = K1
     int fp6_cap = 1 << 20;            // ... records per pair of the filter's list; a pair that needs more is redone by K1
+    int fp6_nsplit = 0;               // ... the filter's splits of a streamed bank (0 = fp6_plan.h's rule, or a forced "nsplit")
     int masked_mfma = 1;              // K13: fm_knn_masked on the integer route with k <= 2: 1 = the masked MFMA sweep, 0 = the masked K9 kernel
     int mask_pack_words = (1 << 26) - 4;  // K13: mask words one launch of the pack / fill kernels covers (64 work-items per word: < 2^32 per launch)
     int coll_ws_bytes = 0;            // fm_collection_match_accepted_each / _xcheck1_each: device bytes for the per-(image, query row)
@@ -200,6 +201,13 @@ struct Filter6Ws {
     uint2*    rec;     // [pairs of a launch][cap] records (output row, 32-row unit of the streamed bank)
     unsigned  cap;
     unsigned* cnt;     // [pairs of a launch][2]: records appended (may exceed cap), need_k1
+    int       nsplit = 0;      // the filter's splits of a streamed bank: 0 = its own rule for the launch (fp6_plan.h), > 0 this
+                               // many (option "fp6_nsplit"), < 0 K1's plan (a forced "nsplit" governs both sweeps)
+    int       resident = 256;  // workgroups of the filter the device holds at a time: its CUs
+    // set: the rescoring and the guarded K1 run on `side`, behind ev_sweep (recorded on the sweep's stream behind the filter),
+    // and ev_done is recorded on `side` behind them; null: all three kernels follow each other on the sweep's stream
+    hipStream_t side = nullptr;
+    hipEvent_t  ev_sweep = nullptr, ev_done = nullptr;
 };
 hipError_t launch_rowreduce(const Bank& cols, const Bank& red, int ktop, const RowReducePlan& plan,
                             unsigned long long* partial, int* bound, bool use_glds, hipStream_t stream,
@@ -208,8 +216,7 @@ hipError_t launch_rowreduce(const Bank& cols, const Bank& red, int ktop, const R
 bool filter6_usable(const Bank& cols, const Bank& red);     // both banks carry the FP6 plane
 hipError_t launch_prep6(const Bank& b, int grid_max, hipStream_t stream);     // the plane of rows [0, n_pad) from rows8 (grid_max 0: no limit)
 hipError_t launch_filter6(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
-                          unsigned long long* const* partial, const unsigned* const* cut, uint2* rec, unsigned cap,
-                          unsigned* cnt, hipStream_t stream);
+                          unsigned long long* const* partial, const unsigned* const* cut, const Filter6Ws& ws, hipStream_t stream);
 int rowreduce_grid(const RowReducePlan& plan);      // workgroups per bank pair (padded under orders 1 and 2)
 // fm_self_dist: top-1 of every row over the OTHER rows of its own bank (masked diagonal)
 RowReducePlan plan_rowreduce_self(int64_t n_pad, const Tuning& tn);
@@ -386,7 +393,8 @@ constexpr int kRRBatchMax = 16;           // bank pairs per batched row-reduce l
 hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
                                   unsigned long long* const* partial, int* const* bound, hipStream_t stream, bool self = false,
                                   const unsigned* const* cut = nullptr,       // (cut[i]: as launch_rowreduce's, per pair; not for self)
-                                  const Filter6Ws* f6 = nullptr);             // (with a cut for every pair: launch_rowreduce's)
+                                  const Filter6Ws* f6 = nullptr,              // (with a cut for every pair: launch_rowreduce's)
+                                  bool* off_stream = nullptr);     // out: the keys are complete at f6->ev_done, not on `stream`
 // top-2 form of the batched launch (fm_collection_knn2_each): bound[i] = pair i's two bound arrays ([2 * ncols_alloc]) or null
 hipError_t launch_rowreduce_batch2(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
                                    unsigned long long* const* partial, int* const* bound, hipStream_t stream);

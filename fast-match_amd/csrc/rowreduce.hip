@@ -1073,8 +1073,9 @@ RowReducePlan plan_rowreduce_self(int64_t n_pad, const Tuning& tn)
 // batched kernel is built for: 4 blocks per wave, 8 waves).
 hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* const* red, const RowReducePlan* plans,
                                   unsigned long long* const* partial, int* const* bound, hipStream_t stream, bool self,
-                                  const unsigned* const* cut, const Filter6Ws* f6)
+                                  const unsigned* const* cut, const Filter6Ws* f6, bool* off_stream)
 {
+    if (off_stream) *off_stream = false;
     if (n < 1 || n > kRRBatchMax) return hipErrorInvalidValue;
     RRBatch b;
     long long total = 0;
@@ -1095,10 +1096,16 @@ hipError_t launch_rowreduce_batch(int n, const Bank* const* cols, const Bank* co
     bool filter = f6 && f6->rec && f6->cnt && f6->cap > 0 && cut && !self;
     for (int i = 0; i < n && filter; ++i) filter = cut[i] != nullptr && filter6_usable(*cols[i], *red[i]);
     if (filter) {
-        const hipError_t e = launch_filter6(n, cols, red, plans, partial, cut, f6->rec, f6->cap, f6->cnt, stream);
+        // (behind the rescoring: on the filter's side stream when it has one, and the caller asked where the keys end up)
+        const bool side = off_stream && f6->side && f6->ev_sweep && f6->ev_done;
+        Filter6Ws ws = *f6;
+        if (!side) ws.side = nullptr;
+        hipError_t e = launch_filter6(n, cols, red, plans, partial, cut, ws, stream);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(rowreduce_guard_kernel, dim3((unsigned)(total < 512 ? total : 512)), dim3(64 * 8), 0, stream, b, (const unsigned*)f6->cnt);
-        return hipGetLastError();
+        hipLaunchKernelGGL(rowreduce_guard_kernel, dim3((unsigned)(total < 512 ? total : 512)), dim3(64 * 8), 0, side ? ws.side : stream, b, (const unsigned*)f6->cnt);
+        if ((e = hipGetLastError()) != hipSuccess || !side) return e;
+        *off_stream = true;
+        return hipEventRecord(ws.ev_done, ws.side);
     }
     if (self) hipLaunchKernelGGL((rowreduce_batch_kernel<4, 1, 8, 3, 1, true>), dim3((unsigned)total), dim3(64 * 8), 0, stream, b);
     else      hipLaunchKernelGGL((rowreduce_batch_kernel<4, 1, 8, 3, 1>), dim3((unsigned)total), dim3(64 * 8), 0, stream, b);

@@ -132,6 +132,8 @@ int  fm_ctx_destroy(fm_ctx* ctx);
  *                         rescoring of what it keeps and K1 as the fallback (1); 0 = K1 always.  Results never differ.
  *   "fp6_cap"      1..2^24  ... records per image pair the filter may keep (2^20, 8 bytes each); a pair that needs more is
  *                         redone by K1 on the device, without a host wait
+ *   "fp6_nsplit"   0..2^20  ... slices of the query bank the filter's workgroups sweep (0: chosen per launch from the sizes of
+ *                         all its pairs and the device's CU count; a forced "nsplit" governs the filter too unless this is set)
  *   "fp6_records", "fp6_fallbacks"  COUNTERS, get only (waits for the context's stream): records appended and pairs redone
  *                         by K1 in the last filter launch, summed over its pairs
  *   "masked_mfma"  0|1    fm_knn_masked and its siblings on the integer route with k <= 2: 1 = the masked matrix-core sweep
