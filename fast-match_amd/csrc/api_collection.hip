@@ -15,10 +15,11 @@
 // -1 / -1 / +inf.  Lookup tables on the device, per 128-row stage: its image and its number of real rows; per image: its
 // first physical row.  Physical order = logical (image, row) order, so keys (distance, physical row) order ties the way
 // OpenCV's per-image insertion does: the earlier image, then the earlier row.
-// fm_collection_match_accepted_each (the end of this file) is the first caller that makes the stack the OUTPUT operand of a
+// fm_collection_match_accepted_each (further down) is the first caller that makes the stack the OUTPUT operand of a
 // sweep; what the padding rows do there is written down in front of it.
-#include "ctx_internal.h"
-#include "coll_tab.h"
+// The match graph -- image pairs inside a collection, and a wide query bank image by image -- is a unit of its own,
+// api_pairs.hip; coll_internal.h holds the collection object and what that unit calls here.
+#include "coll_internal.h"
 
 #include <algorithm>
 #include <atomic>
@@ -36,40 +37,8 @@ using namespace fm;
 // masks by INDEX: its sweep and its vector-ALU kernel take the per-stage real-row table (stage_real).
 // A fourth kind, wide (FM_BANK_F32W, fm_collection_add_wide: coll_add_wide below), masks by INDEX as well and serves the
 // match graph (fm_collection_pairs_mutual_ratio) and, under names of their own, a wide query bank image by image
-// (fm_collection_wide_mutual_ratio_each, fm_collection_wide_knn2_each: the end of this file); every other call that takes a
-// query bank refuses it (coll_refuse_wide).
-constexpr int kCollPadNorm = 1 << 26;
-constexpr float kCollPadF32 = 1.0e18f;           // 128 * (1e18 + kCollF32Max)^2 = 1.7e38 stays finite in float32
-// Masking by value holds while a padding row is farther from every query row than every real row is.  With all finite
-// magnitudes <= L, per dimension |q - pad| >= 1e18 - L and |q - t| <= 2 L, so 3 L < 1e18 suffices (for every width: the
-// dimensions beyond `dim` hold 0 in q and t and 1e18 in a padding row).  L = FM_COLLECTION_F32_MAX = 2^57 = 1.44e17
-// (3 L = 4.3e17).  Images and query banks beyond it are refused (FM_EUNSUPPORTED), never answered differently: at
-// 9e17 a query row is nearer to the padding rows (1.1e18) than to real rows of 1e16 (1.0e19), K5 and K9 would list
-// padding (-> -1 / inf) where the filter path lists real rows.  Non-finite values are outside the limit's reach and
-// harmless: their distances are inf or NaN to real and padding rows alike, and no kernel lists those.
-constexpr float kCollF32Max = 144115188075855872.0f;      // 2^57
-static_assert(3.0 * kCollF32Max < kCollPadF32, "padding rows must stay behind every real row");
-
-struct fm_collection {
-    fm_ctx* ctx = nullptr;
-    fm::Bank stack;                       // kind = the collection's; n = n_pad = used rows, cap_pad = allocated rows
-    int dim = 0;                          // 0: no non-empty image yet
-    int src = 0;                          // 1: images came as uint8, 2: as float32, 3: as binary rows, 4: as wide rows (0: none yet)
-    float wvmax = 0.f;                    // wide: the largest finite magnitude added so far
-    bool wscale = false;                  // wide: stack.kscale was chosen (from the first magnitude above 0)
-    int64_t used = 0, total = 0;          // physical rows in use (a multiple of 128), real rows
-    std::vector<int64_t> rows, phys;      // per image
-    std::vector<int32_t> usq;             // per image: largest |row|^2 (sqrt_tie_possible)
-    int32_t* d_tab = nullptr;             // stage image [nstages] | stage real rows [nstages] | first row [n_images]
-    size_t tab_bytes = 0;
-    bool dirty = true;
-    uint64_t gen = 0;                     // changes with every add and clear, unique across collections (fm_mask_create_coll remembers it)
-    int64_t nstages() const { return used / kStageRows; }
-    const int32_t* st_img() const { return d_tab; }
-    const int32_t* st_real() const { return d_tab + nstages(); }
-    const int32_t* img_phys() const { return d_tab + 2 * nstages(); }
-};
-
+// (fm_collection_wide_mutual_ratio_each, fm_collection_wide_knn2_each: api_pairs.hip); every other call that takes a
+// query bank refuses it (coll_refuse_wide).  (kCollPadNorm, kCollPadF32, kCollF32Max: coll_internal.h.)
 static uint64_t coll_next_gen()
 {
     static std::atomic<uint64_t> g{0};
@@ -198,6 +167,15 @@ void coll_sqrt_fix_kernel(const unsigned* __restrict__ fix, const int8_t* __rest
         }
         __syncthreads();
     }
+}
+
+hipError_t launch_coll_sqrt_fix(const unsigned* fix, const int8_t* col_rows, const int32_t* col_norm, const int8_t* red_rows,
+                                const int32_t* red_norm, int nred, CollTab tab, int64_t out, int32_t* img, int32_t* idx, float* dist,
+                                hipStream_t stream)
+{
+    hipLaunchKernelGGL(coll_sqrt_fix_kernel, dim3(kFixGrid), dim3(256), 0, stream, fix, col_rows, col_norm, red_rows, red_norm, nred, tab, out,
+                       img, idx, dist);
+    return hipGetLastError();
 }
 
 // k = 3 .. 8: K9 wrote physical rows; one thread per entry looks its (image, row) up.  A padding row (fewer than k real
@@ -401,7 +379,7 @@ static int coll_set_kind(fm_ctx* ctx, fm_collection* c, int kind, int ksteps, in
     return cap > 0 ? coll_alloc(ctx, &c->stack, cap, nullptr, 0) : FM_OK;
 }
 
-static int coll_check(fm_ctx* ctx, const fm_collection* c, const char* who)
+int coll_check(fm_ctx* ctx, const fm_collection* c, const char* who)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
     if (!c) return fail(ctx, FM_EINVAL, std::string(who) + ": collection is NULL");
@@ -774,8 +752,6 @@ extern "C" int fm_collection_add_wide_dev(fm_ctx* ctx, fm_collection* c, const v
     return coll_add_wide(ctx, c, d_rows, n, dim, img_idx, who, &dsrc);
 }
 
-static bool coll_is_wide(const fm_collection* c) { return c->src == 4; }
-
 // the calls that are not built for a wide collection (include/fastmatch_hip.h, K14)
 static int coll_refuse_wide(fm_ctx* ctx, const fm_collection* c, const char* who)
 {
@@ -873,17 +849,9 @@ static int coll_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, con
     return fm_collection_train(ctx, c);
 }
 
-// A bank view of image i (rows of the stack's arrays; nm_max stays the collection's largest norm: an upper bound)
-static fm::Bank coll_view(const fm_collection* c, int i)
-{
-    fm::Bank v = bank_rows_view(c->stack, c->phys[(size_t)i], c->rows[(size_t)i]);
-    v.usq_max = c->usq[(size_t)i];
-    return v;
-}
-
 // One-slot merge of a sweep's partials into the lists from entry `out` on (CollSlot::out); ps = null: no reduced rows, every
 // entry -1 / +inf.
-static int coll_merge_one(fm_ctx* ctx, const PairSweep* ps, CollTab tab, int64_t nq, int64_t out, int32_t* d_img, int32_t* d_idx, float* d_dist)
+int coll_merge_one(fm_ctx* ctx, const PairSweep* ps, CollTab tab, int64_t nq, int64_t out, int32_t* d_img, int32_t* d_idx, float* d_dist)
 {
     CollMerge mg{};
     CollSlot& sl = mg.s[0];
@@ -1696,6 +1664,32 @@ static int coll_qbest_chunk(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int
 }
 
 // What a per-image election call tests and where its rows go.
+// The device form's output pointers of the _each calls (any device's memory: a peer buffer is a valid destination).
+static int coll_each_dev_check(fm_ctx* ctx, const char* who, const int64_t* d_counts, const int32_t* d_rows, int64_t cap)
+{
+    int rc;
+    if (!d_counts || (cap > 0 && !d_rows)) return fail(ctx, FM_EINVAL, std::string(who) + ": device output pointer is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_ptr(ctx, d_counts, who, "d_counts", false)) != FM_OK) return rc;
+    if (cap > 0 && (rc = check_device_ptr(ctx, d_rows, who, "d_rows", false)) != FM_OK) return rc;
+    return FM_OK;
+}
+
+// An _each call whose query bank has no rows: zero counts for every image.  d_counts (device form, else null) is zeroed on
+// the context's stream behind the consumer's work; h_counts: the host counts, or null.
+static int coll_each_no_rows(fm_ctx* ctx, int64_t ni, int64_t* d_counts, int64_t* h_counts, void* consumer)
+{
+    int rc;
+    if (d_counts) {
+        if ((rc = wait_for_stream(ctx, consumer)) != FM_OK) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, (size_t)ni * 8, ctx->stream));
+        if ((rc = results_written(ctx, consumer)) != FM_OK) return rc;
+        ctx->rows_stream = ctx->stream;
+    }
+    if (h_counts) for (int64_t i = 0; i < ni; ++i) h_counts[i] = 0;
+    return FM_OK;
+}
+
 struct CollEachArgs {
     const char* who;
     bool accept;                     // the accepted-match test (tau, q's self distances); else the cross-check under max_dist
@@ -1736,10 +1730,7 @@ static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, cons
     if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap < 0");
     if (ni == 0) return FM_OK;
     if (a.to_dev) {
-        if (!a.d_counts || (cap > 0 && !a.d_rows)) return fail(ctx, FM_EINVAL, who + ": device output pointer is NULL");
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if ((rc = check_device_ptr(ctx, a.d_counts, a.who, "d_counts", false)) != FM_OK) return rc;
-        if (cap > 0 && (rc = check_device_ptr(ctx, a.d_rows, a.who, "d_rows", false)) != FM_OK) return rc;
+        if ((rc = coll_each_dev_check(ctx, a.who, a.d_counts, a.d_rows, cap)) != FM_OK) return rc;
     } else if (a.accept) {
         if (!a.counts) return fail(ctx, FM_EINVAL, who + ": n_accepted is NULL");
         if (nq > 0 && cap > 0 && (!a.qidx || !a.tidx || !a.dist || !a.ratio)) return fail(ctx, FM_EINVAL, who + ": output pointer is NULL");
@@ -1749,17 +1740,7 @@ static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, cons
         if (!a.tidx && !a.counts) return fail(ctx, FM_EINVAL, who + ": every output pointer is NULL");
         HIP_TRY(ctx, hipSetDevice(ctx->device));
     }
-    if (nq == 0) {
-        if (a.to_dev) {
-            if ((rc = wait_for_stream(ctx, a.consumer)) != FM_OK) return rc;
-            HIP_TRY(ctx, hipMemsetAsync(a.d_counts, 0, (size_t)ni * 8, ctx->stream));
-            if ((rc = results_written(ctx, a.consumer)) != FM_OK) return rc;
-            ctx->rows_stream = ctx->stream;
-        }
-        int64_t* hc = a.to_dev ? a.h_counts : a.counts;
-        if (hc) for (int64_t i = 0; i < ni; ++i) hc[i] = 0;
-        return FM_OK;
-    }
+    if (nq == 0) return coll_each_no_rows(ctx, ni, a.to_dev ? a.d_counts : nullptr, a.to_dev ? a.h_counts : a.counts, a.consumer);
     // images per chunk from the budget
     const int nblk = (int)((nq + 255) / 256);
     const size_t per = (size_t)nq * (a.accept ? kCollAcceptEntry : kCollXcheckEntry) + (size_t)nblk * 4;
@@ -1809,14 +1790,8 @@ static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, cons
                            a.accept ? (double*)(b + o_ratio) : (double*)nullptr, (uint8_t*)(b + o_pass), (int*)(b + o_bc));
         HIP_TRY(ctx, hipGetLastError());
         if (!a.to_dev && !a.accept && a.tidx) {
-            // the dense result of the chunk, before the next chunk decodes into the same arrays (copies of up to 128 MB
-            // each keep the staging buffer of fm::d2h within bounds)
-            const size_t total = (size_t)g * nq * 4, piece = (size_t)128 << 20;
-            for (size_t o = 0; o < total; o += piece) {
-                const size_t nb = std::min(piece, total - o);
-                HIP_TRY(ctx, d2h(ctx, (char*)(a.tidx + i0 * nq) + o, b + o_tidx + o, nb));
-                HIP_TRY(ctx, d2h(ctx, (char*)(a.dist + i0 * nq) + o, b + o_dist + o, nb));
-            }
+            // the dense result of the chunk, before the next chunk decodes into the same arrays
+            HIP_TRY(ctx, d2h_pieces(ctx, (size_t)g * nq, (size_t)32 << 20, {{a.tidx + i0 * nq, b + o_tidx, 4}, {a.dist + i0 * nq, b + o_dist, 4}}));
         }
         // (device form: the first compaction is the first kernel that writes the caller's buffers)
         if (a.to_dev && i0 == 0 && (rc = wait_for_stream(ctx, a.consumer)) != FM_OK) return rc;
@@ -1948,26 +1923,13 @@ static int coll_mutual_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, con
     if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap < 0");
     if (ni == 0) return FM_OK;
     if (a.to_dev) {
-        if (!a.d_counts || (cap > 0 && !a.d_rows)) return fail(ctx, FM_EINVAL, who + ": device output pointer is NULL");
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if ((rc = check_device_ptr(ctx, a.d_counts, a.who, "d_counts", false)) != FM_OK) return rc;
-        if (cap > 0 && (rc = check_device_ptr(ctx, a.d_rows, a.who, "d_rows", false)) != FM_OK) return rc;
+        if ((rc = coll_each_dev_check(ctx, a.who, a.d_counts, a.d_rows, cap)) != FM_OK) return rc;
     } else {
         if (!a.counts) return fail(ctx, FM_EINVAL, who + ": n_accepted is NULL");
         if (nq > 0 && cap > 0 && (!a.qidx || !a.tidx || !a.dist || !a.ratio)) return fail(ctx, FM_EINVAL, who + ": output pointer is NULL");
         HIP_TRY(ctx, hipSetDevice(ctx->device));
     }
-    if (nq == 0) {
-        if (a.to_dev) {
-            if ((rc = wait_for_stream(ctx, a.consumer)) != FM_OK) return rc;
-            HIP_TRY(ctx, hipMemsetAsync(a.d_counts, 0, (size_t)ni * 8, ctx->stream));
-            if ((rc = results_written(ctx, a.consumer)) != FM_OK) return rc;
-            ctx->rows_stream = ctx->stream;
-        }
-        int64_t* hc = a.to_dev ? a.h_counts : a.counts;
-        if (hc) for (int64_t i = 0; i < ni; ++i) hc[i] = 0;
-        return FM_OK;
-    }
+    if (nq == 0) return coll_each_no_rows(ctx, ni, a.to_dev ? a.d_counts : nullptr, a.to_dev ? a.h_counts : a.counts, a.consumer);
     const int nblk = (int)((nq + 255) / 256);
     const int64_t ne = ni * nq, nb = ni * nblk;
     if (nb > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, who + ": n_images * ceil(nq / 256) exceeds 2^31 - 1");
@@ -2083,719 +2045,4 @@ extern "C" int fm_collection_mutual_ratio_each_dev(fm_ctx* ctx, fm_collection* c
     const CollMutualArgs a{"fm_collection_mutual_ratio_each_dev", tau, symmetric, cap, nullptr, nullptr, nullptr, nullptr, nullptr,
                            true, d_rows, d_counts, h_counts, consumer_stream};
     return coll_mutual_each(ctx, c, q, a);
-}
-
-// ---------------------------------------------------------------------------------------
-// image pairs INSIDE a collection (the match graph): fm_collection_pairs_mutual_ratio
-// ---------------------------------------------------------------------------------------
-// Pair p = (a, b), ordered: its rows are fm_mutual_ratio(bank(image a), bank(image b)).  Both images are resident bank views
-// of the stack (coll_view), so a pair is two full top-2 sweeps -- slot 2j: output rows = image a, reduced = image b (the
-// forward lists); slot 2j + 1: the other way round (the reverse lists of ALL rows of b: R2[t0] is a plain lookup, no gather,
-// no candidate count, no host wait) -- then a join (rules 1 to 3 of fm_mutual_ratio from the two lists) and an ordered
-// compaction into the packed output, fm_radius_match's layout with "pair" for "query row".
-// Integer route: the slots of a whole chunk of pairs go through ONE table-driven launch of the batched top-2 kernel
-// (launch_rowreduce_table2: descriptors in device memory) and ONE merge launch over per-slot row blocks; the float32-root
-// repair is the existing per-slot kernel for the slots where sqrt_tie_possible holds.  Float32-route and binary
-// collections: the two sweep_pair calls per pair (K8 / K5, K11), each followed by its one-slot merge, back to back.
-// Every kernel behind the sweeps runs on a FLAT grid with a prefix table in device memory (table_slot_of): blockIdx.y
-// cannot count slots of different sizes.  Chunks: consecutive pairs whose partials, lists and per-row arrays fit the option
-// "coll_ws_bytes" (0 = 2^30), at least one pair, enqueued back to back; a running total in device memory makes the
-// offsets global.  The tables of ALL chunks are built on the host before anything is enqueued and go up in one copy.
-struct PairsMergeSlot {
-    const unsigned long long* partial;    // [nsplit][ncols_alloc][2] keys of the slot's sweep
-    unsigned* fix;                        // tie list (fix[0] = count, rows from fix[4]) or null
-    int64_t out;                          // first entry of the slot's lists
-    int nsplit, ncols_alloc, nrows, pad_;
-};
-struct PairsJoinSlot {
-    int64_t fwd, rev;                     // first list entry of the forward (rows of a) and reverse (rows of b) lists
-    int64_t e0;                           // first entry of the pair in the per-row arrays of the chunk
-    int32_t nq, nt;                       // rows of a (0: the pair accepts nothing and owns no block), rows of b
-};
-
-// coll_merge2_kernel for a chunk's slots: block b belongs to slot table_slot_of(blk0, n, b), rows from (b - blk0[slot]) * 256.
-__global__ __launch_bounds__(256)
-void coll_pairs_merge_kernel(const PairsMergeSlot* __restrict__ slots, const int* __restrict__ blk0, int n,
-                             int32_t* __restrict__ idx, float* __restrict__ dist)
-{
-    const int s = table_slot_of(blk0, n, (int)blockIdx.x);
-    const PairsMergeSlot sl = slots[s];
-    const int64_t i = (int64_t)((int)blockIdx.x - blk0[s]) * 256 + threadIdx.x;
-    if (i >= sl.nrows) return;
-    unsigned long long b0 = ~0ull, b1 = ~0ull;
-    for (int sp = 0; sp < sl.nsplit; ++sp) {
-        const unsigned long long* p = sl.partial + ((size_t)sp * sl.ncols_alloc + i) * 2;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const unsigned long long v = p[k];
-            if (v < b0) { b1 = b0; b0 = v; }
-            else if (v < b1) { b1 = v; }
-        }
-    }
-    const int64_t o = 2 * (sl.out + i);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const unsigned long long b = k ? b1 : b0;
-        idx[o + k] = (b == ~0ull) ? -1 : (int32_t)(unsigned)b;
-        dist[o + k] = (b == ~0ull) ? INFINITY : sqrtf((float)(unsigned)(b >> 32));
-    }
-    // (the float32 order can differ from the d2 order: see knn2_merge_kernel)
-    if (sl.fix && b1 != ~0ull && (unsigned)(b1 >> 32) >= kSqrtTieMin) {
-        const unsigned e0 = (unsigned)(b0 >> 32), e1 = (unsigned)(b1 >> 32);
-        const bool paired1 = sqrt_ties_up(e1) || sqrt_ties_up(e1 - 1u);
-        const bool paired0 = e0 >= kSqrtTieMin && (sqrt_ties_up(e0) || sqrt_ties_up(e0 - 1u));
-        if (paired0 || paired1) sl.fix[4 + atomicAdd(sl.fix, 1u)] = (unsigned)i;
-    }
-}
-
-// The same for a wide chunk (wide_f32.hip, part 4): keys (float32 distance bits << 32 | row inside the reduced image), one
-// split, no tie list -- the key order IS the (distance, row) order.
-__global__ __launch_bounds__(256)
-void coll_pairs_merge_f32_kernel(const PairsMergeSlot* __restrict__ slots, const int* __restrict__ blk0, int n,
-                                 int32_t* __restrict__ idx, float* __restrict__ dist)
-{
-    const int s = table_slot_of(blk0, n, (int)blockIdx.x);
-    const PairsMergeSlot sl = slots[s];
-    const int64_t i = (int64_t)((int)blockIdx.x - blk0[s]) * 256 + threadIdx.x;
-    if (i >= sl.nrows) return;
-    unsigned long long b0 = ~0ull, b1 = ~0ull;
-    for (int sp = 0; sp < sl.nsplit; ++sp) {
-        const unsigned long long* p = sl.partial + ((size_t)sp * sl.ncols_alloc + i) * 2;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const unsigned long long v = p[k];
-            if (v < b0) { b1 = b0; b0 = v; }
-            else if (v < b1) { b1 = v; }
-        }
-    }
-    const int64_t o = 2 * (sl.out + i);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const unsigned long long b = k ? b1 : b0;
-        idx[o + k] = (b == ~0ull) ? -1 : (int32_t)(unsigned)b;
-        dist[o + k] = (b == ~0ull) ? INFINITY : __uint_as_float((unsigned)(b >> 32));
-    }
-}
-
-// The join of a chunk's pairs: lowe_each_kernel's forward test and mutual_join_kernel's two rules, word for word, with the
-// reverse list of the first neighbour looked up in place.  Block b: pair table_slot_of(pblk0, n, b), rows of a from
-// (b - pblk0[pair]) * 256.
-__global__ __launch_bounds__(256)
-void coll_pairs_join_kernel(const PairsJoinSlot* __restrict__ ps, const int* __restrict__ pblk0, int n,
-                            const int32_t* __restrict__ l_idx, const float* __restrict__ l_dist, double tau, int symmetric,
-                            int32_t* __restrict__ tidx, float* __restrict__ dist, double* __restrict__ ratio,
-                            uint8_t* __restrict__ pass, int* __restrict__ block_counts)
-{
-    const int j = table_slot_of(pblk0, n, (int)blockIdx.x);
-    const PairsJoinSlot s = ps[j];
-    const int64_t q = (int64_t)((int)blockIdx.x - pblk0[j]) * 256 + threadIdx.x;
-    bool keep = false;
-    if (q < s.nq) {
-        const int64_t f = 2 * (s.fwd + q);
-        const int32_t t0 = l_idx[f];
-        const float d1 = l_dist[f], d2 = l_dist[f + 1];
-        double r = (l_idx[f + 1] >= 0) ? (double)d1 / (double)d2 : NAN;
-        if (r < tau) {
-            const int64_t g = 2 * (s.rev + t0);
-            keep = l_idx[g] == (int32_t)q;             // mutual: the train row's nearest query row (lowest index on ties)
-            if (keep && symmetric) {
-                const double rr = (l_idx[g + 1] >= 0) ? (double)l_dist[g] / (double)l_dist[g + 1] : NAN;
-                keep = rr < tau;
-                if (keep && rr > r) r = rr;
-            }
-        }
-        const int64_t e = s.e0 + q;
-        tidx[e] = t0;
-        dist[e] = d1;
-        ratio[e] = r;
-        pass[e] = keep ? 1 : 0;
-    }
-    emit_block_count(__ballot(keep), block_counts);
-}
-
-// One workgroup: the exclusive prefix of a chunk's block counts on top of the running total of the chunks before it
-// (block_base, global ranks), the chunk's pair offsets -- offsets points at the chunk's first pair; a pair's offset is the
-// base of its first block, the end for a pair without blocks behind the last one -- and the new running total.  No atomics:
-// the result does not depend on any order of execution.
-__global__ __launch_bounds__(256)
-void coll_pairs_scan_kernel(const int* __restrict__ block_counts, int nblocks, const int* __restrict__ pblk0, int npairs,
-                            long long* carry, long long* block_base, long long* offsets)
-{
-    __shared__ int sc[256];
-    __shared__ long long run;
-    const int tid = threadIdx.x;
-    if (tid == 0) run = *carry;
-    __syncthreads();
-    for (int b0 = 0; b0 < nblocks; b0 += 256) {
-        const int b = b0 + tid;
-        const int v = b < nblocks ? block_counts[b] : 0;
-        sc[tid] = v;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {
-            const int t = tid >= d ? sc[tid - d] : 0;
-            __syncthreads();
-            sc[tid] += t;
-            __syncthreads();
-        }
-        const long long base = run;
-        if (b < nblocks) block_base[b] = base + sc[tid] - v;
-        __syncthreads();
-        if (tid == 255) run = base + sc[255];
-        __syncthreads();
-    }
-    const long long end = run;
-    for (int j = tid; j <= npairs; j += 256) {
-        const int fb = j < npairs ? pblk0[j] : nblocks;
-        offsets[j] = fb < nblocks ? block_base[fb] : end;
-    }
-    if (tid == 0) *carry = end;
-}
-
-// Ordered compaction of a chunk's accepted rows at their global ranks: the rows of a pair are written iff the pair ends
-// within cap (the longest prefix of whole pairs: the offsets ascend).  Four columns (o_rows null) or 12-byte rows.
-__global__ __launch_bounds__(256)
-void coll_pairs_compact_kernel(const PairsJoinSlot* __restrict__ ps, const int* __restrict__ pblk0, int n,
-                               const int32_t* __restrict__ tidx, const float* __restrict__ dist, const double* __restrict__ ratio,
-                               const uint8_t* __restrict__ pass, const long long* __restrict__ block_base,
-                               const long long* __restrict__ offsets, int64_t cap, int32_t* __restrict__ o_q,
-                               int32_t* __restrict__ o_t, float* __restrict__ o_d, double* __restrict__ o_r, int32_t* __restrict__ o_rows)
-{
-    __shared__ int wave_cnt[4];
-    const int j = table_slot_of(pblk0, n, (int)blockIdx.x);
-    const PairsJoinSlot s = ps[j];
-    const int64_t q = (int64_t)((int)blockIdx.x - pblk0[j]) * 256 + threadIdx.x;
-    const bool p = q < s.nq && pass[s.e0 + q];
-    const unsigned long long m = __ballot(p);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int wb = 0;
-    for (int w = 0; w < wave; ++w) wb += wave_cnt[w];
-    if (!p || offsets[j + 1] > cap) return;
-    const int64_t dst = block_base[blockIdx.x] + wb + __popcll(m & ((1ull << lane) - 1ull));
-    const int64_t e = s.e0 + q;
-    if (o_rows) {
-        o_rows[3 * dst] = (int32_t)q;
-        o_rows[3 * dst + 1] = tidx[e];
-        o_rows[3 * dst + 2] = (int32_t)__float_as_uint(dist[e]);
-    } else {
-        o_q[dst] = (int32_t)q; o_t[dst] = tidx[e]; o_d[dst] = dist[e]; o_r[dst] = ratio[e];
-    }
-}
-
-struct CollPairsArgs {
-    const char* who;
-    double tau; int symmetric; int64_t cap;
-    int64_t* offsets; int32_t* qidx; int32_t* tidx; float* dist; double* ratio;     // host form
-    bool to_dev; int64_t* d_offsets; int32_t* d_rows; void* consumer;               // device form
-    int64_t* n_total;
-    // fm_collection_wide_*_each: "pair" p is (q, image p) -- a is the wide query bank, outside the stack -- for every image;
-    // knn2: the forward slots alone, their merged lists [n_images][nq][2] copied to k_idx / k_dist (host), no join
-    const fm::Bank* q = nullptr; bool knn2 = false; int32_t* k_idx = nullptr; float* k_dist = nullptr;
-};
-
-// One chunk of consecutive pairs [p0, p1): what its kernels cover and where its tables lie in the call's table image.
-struct PairsChunk {
-    int64_t p0, p1;
-    int nslots = 0;                        // sweeps (two per pair of non-empty images)
-    int64_t wg = 0, mblocks = 0;           // workgroups of the table sweep, blocks of the merge (integer route)
-    int64_t jblocks = 0, entries = 0, lists = 0;      // blocks and per-row entries of the join, list entries
-    size_t part = 0, bound = 0, fix = 0;   // bytes of the slots' partials, shared bounds and tie lists (integer route)
-    size_t o_rr = 0, o_ms = 0, o_mb = 0, o_js = 0, o_jb = 0;     // offsets in the table image
-    // wide collections: the chunk's output-row space (every slot pad128 of its rows), 2 sum rows(a) rows(b), the route, the
-    // record list's size, the filter's grid, and the slot table | first workgroups | first rows in the table image
-    int64_t wrows = 0; double work = 0; bool filt = false; unsigned cap = 0; int fwg = 0;
-    size_t o_ws = 0, o_ww = 0, o_wr = 0;
-};
-
-static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs, int64_t n_pairs, const CollPairsArgs& a)
-{
-    const std::string who(a.who);
-    int rc = coll_check(ctx, c, a.who);
-    if (rc != FM_OK) return rc;
-    const int64_t ni = (int64_t)c->rows.size(), cap = a.cap;
-    const bool qm = a.q != nullptr;                 // (the caller has checked q and passes pairs = NULL, n_pairs = n_images)
-    const int64_t nq = qm ? a.q->n : 0;
-    if (n_pairs < 0) return fail(ctx, FM_EINVAL, who + ": n_pairs < 0");
-    if (!qm && !pairs && n_pairs != ni * (ni - 1) / 2)
-        return fail(ctx, FM_EINVAL, who + ": pairs is NULL (every i < j) and n_pairs is not n_images (n_images - 1) / 2");
-    if (n_pairs > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, who + ": n_pairs exceeds 2^31 - 1");
-    for (int64_t p = 0; pairs && p < n_pairs; ++p)
-        if (pairs[2 * p] < 0 || pairs[2 * p] >= ni || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= ni)
-            return fail(ctx, FM_EINVAL, who + ": pair " + std::to_string(p) + " names an image outside [0, n_images)");
-    if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap is negative");
-    if (a.knn2) {
-        if (ni * nq > 0 && (!a.k_idx || !a.k_dist)) return fail(ctx, FM_EINVAL, who + ": idx / dist is NULL");
-        if (ni * nq == 0) return FM_OK;
-    } else if (a.to_dev) {
-        if (!a.d_offsets) return fail(ctx, FM_EINVAL, who + ": d_offsets is NULL");
-        if (cap > 0 && !a.d_rows) return fail(ctx, FM_EINVAL, who + ": d_rows is NULL with cap > 0");
-    } else {
-        if (!a.offsets) return fail(ctx, FM_EINVAL, who + ": offsets is NULL");
-        if (cap > 0 && (!a.qidx || !a.tidx || !a.dist || !a.ratio)) return fail(ctx, FM_EINVAL, who + ": qidx / tidx / dist / ratio is NULL with cap > 0");
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (a.to_dev) {
-        if ((rc = check_device_ptr(ctx, a.d_offsets, a.who, "d_offsets")) != FM_OK) return rc;
-        if (cap > 0 && (rc = check_device_ptr(ctx, a.d_rows, a.who, "d_rows")) != FM_OK) return rc;
-    }
-    if (a.n_total) *a.n_total = 0;
-    if (n_pairs == 0) {
-        if (a.to_dev) {
-            if ((rc = wait_for_stream(ctx, a.consumer)) != FM_OK) return rc;
-            HIP_TRY(ctx, hipMemsetAsync(a.d_offsets, 0, 8, ctx->stream));
-            return results_written(ctx, a.consumer);
-        }
-        a.offsets[0] = 0;
-        return FM_OK;
-    }
-    // the pairs, in order (NULL: every i < j, lexicographic)
-    std::vector<int32_t> all;
-    try {
-        if (!pairs && !qm) {
-            all.reserve((size_t)n_pairs * 2);
-            for (int32_t i = 0; i < (int32_t)ni; ++i) for (int32_t j = i + 1; j < (int32_t)ni; ++j) { all.push_back(i); all.push_back(j); }
-            pairs = all.data();
-        }
-    } catch (const std::bad_alloc&) { return fail(ctx, FM_ENOMEM, who + ": out of host memory"); }
-    const bool i8 = c->stack.kind == FM_BANK_I8 && !coll_is_wide(c);
-    // Wide collections (wide_f32.hip, part 4): a chunk's slots lie side by side in one output-row space, swept by ONE filter
-    // launch + ONE rescoring + ONE guarded exact launch (or the exact launch alone) and merged by one launch, whatever the
-    // number of pairs.  ws_partial: partial [rows][2] | count | bounds [rows] | records | their scores, of one chunk.
-    const bool wide = coll_is_wide(c);
-    const bool wide_filter_on = wide && ctx->tune.f32_filter != 0 && ctx->d_counters && c->stack.filt_ok && c->stack.wrowsh &&
-                                (!qm || wide_filter_usable(*a.q, c->stack));
-    size_t max_cap = 0;
-    // rows of the pair's two sides: a = the output rows of its forward slot, b = of its reverse slot
-    auto rows_a = [&](int64_t p) { return qm ? nq : c->rows[(size_t)pairs[2 * p]]; };
-    auto rows_b = [&](int64_t p) { return qm ? c->rows[(size_t)p] : c->rows[(size_t)pairs[2 * p + 1]]; };
-    auto live = [&](int64_t p) { return rows_a(p) > 0 && rows_b(p) > 0; };
-    const int ndir = a.knn2 ? 1 : 2;                // sweeps per live pair
-    // Plans of the integer route: the batched shape, every slot under the plan of its own sizes.  Splits exist to fill the
-    // chip from ONE pair; a call whose slots fill it without them takes one split per slot (no shared bounds, the smallest
-    // partials).
-    Tuning shaped = ctx->tune;
-    shaped.nb = 4; shaped.nw = 8; shaped.nbuf = 0; shaped.nsplit = 0; shaped.k1_order = 0;
-    if (i8) {
-        int64_t wg1 = 0;
-        for (int64_t p = 0; p < n_pairs && wg1 < 2048; ++p)
-            if (live(p)) wg1 += (pad128(c->rows[(size_t)pairs[2 * p]]) + 511) / 512 + (pad128(c->rows[(size_t)pairs[2 * p + 1]]) + 511) / 512;
-        if (wg1 >= 2048) shaped.nsplit = 1;
-    }
-    struct SlotPlan { RowReducePlan pl; size_t part, bound, fix; };
-    auto slot_plan = [&](int ia, int ib) {         // output rows = image ia, reduced = image ib
-        SlotPlan s;
-        const fm::Bank va = coll_view(c, ia), vb = coll_view(c, ib);
-        s.pl = plan_rowreduce(va.n_pad, vb.n_pad, shaped);
-        s.part = align256(s.pl.partial_bytes(2));
-        s.bound = (ctx->tune.coop != 0 && s.pl.nsplit > 1) ? align256(s.pl.bound_bytes()) : 0;
-        s.fix = sqrt_tie_possible(va, vb) ? align256(fix_bytes(va.n)) : 0;
-        return s;
-    };
-    size_t budget = (size_t)ctx->tune.coll_ws_bytes;
-    if (budget == 0) budget = (size_t)1 << 30;
-    // pass 1: the chunks
-    std::vector<PairsChunk> chunks;
-    size_t tab_bytes = 0, max_part = 0, max_bound = 0, max_fix = 0;
-    int64_t max_lists = 0, max_entries = 0, max_jblocks = 0, sum_entries = 0;
-    try {
-        PairsChunk ch{};
-        size_t used = 0;
-        ch.p0 = 0;
-        auto close = [&](int64_t p1) {
-            ch.p1 = p1;
-            const int np = (int)(ch.p1 - ch.p0);
-            if (i8 && ch.nslots > 0) {
-                ch.o_rr = carve(tab_bytes, rowreduce_table_bytes(ch.nslots));
-                ch.o_ms = carve(tab_bytes, (size_t)ch.nslots * sizeof(PairsMergeSlot));
-                ch.o_mb = carve(tab_bytes, ((size_t)ch.nslots + 1) * 4);
-            }
-            if (wide && ch.nslots > 0) {
-                ch.o_ws = carve(tab_bytes, (size_t)ch.nslots * sizeof(WideSlot));
-                ch.o_ww = carve(tab_bytes, ((size_t)ch.nslots + 1) * 4);
-                ch.o_wr = carve(tab_bytes, ((size_t)ch.nslots + 1) * 4);
-                ch.o_ms = carve(tab_bytes, (size_t)ch.nslots * sizeof(PairsMergeSlot));
-                ch.o_mb = carve(tab_bytes, ((size_t)ch.nslots + 1) * 4);
-                // wide_route's rule on the chunk's work; the list: 256 records per output row, plan_wide_filter's figure
-                ch.filt = wide_filter_on && (ctx->tune.f32_filter >= 2 || ch.work >= 4.0e6);
-                if (ch.filt) {
-                    ch.cap = (unsigned)std::min<int64_t>(std::max<int64_t>(256 * ch.lists, 1 << 20), (int64_t)1 << 28);
-                    max_cap = std::max<size_t>(max_cap, ch.cap);
-                }
-            }
-            ch.o_js = carve(tab_bytes, (size_t)np * sizeof(PairsJoinSlot));
-            ch.o_jb = carve(tab_bytes, ((size_t)np + 1) * 4);
-            max_part = std::max(max_part, ch.part); max_bound = std::max(max_bound, ch.bound); max_fix = std::max(max_fix, ch.fix);
-            max_lists = std::max(max_lists, ch.lists); max_entries = std::max(max_entries, ch.entries);
-            max_jblocks = std::max(max_jblocks, ch.jblocks);
-            chunks.push_back(ch);
-            ch = PairsChunk{};
-            ch.p0 = p1;
-            used = 0;
-        };
-        for (int64_t p = 0; p < n_pairs; ++p) {
-            size_t need = 0, part = 0, bound = 0, fix = 0;
-            int64_t wg = 0, mb = 0, jb = 0, ra = 0, rb = 0;
-            if (live(p)) {
-                ra = rows_a(p); rb = rows_b(p);
-                if (i8) {
-                    const int ia = pairs[2 * p], ib = pairs[2 * p + 1];
-                    const SlotPlan f = slot_plan(ia, ib), r = slot_plan(ib, ia);
-                    part = f.part + r.part; bound = f.bound + r.bound; fix = f.fix + r.fix;
-                    wg = (int64_t)rowreduce_grid(f.pl) + rowreduce_grid(r.pl);
-                    mb = (ra + 255) / 256 + (rb + 255) / 256;
-                }
-                if (wide) {
-                    const int64_t rr = a.knn2 ? 0 : rb;             // output rows of the reverse slot
-                    const int64_t pr = pad128(ra) + (rr ? pad128(rr) : 0);
-                    part = (size_t)pr * 16; bound = (size_t)pr * 4; fix = wide_filter_on ? (size_t)(ra + rr) * 256 * 12 : 0;
-                    wg = pr / kStageRows;
-                    mb = (ra + 255) / 256 + (rr + 255) / 256;
-                }
-                jb = a.knn2 ? 0 : (ra + 255) / 256;
-                need = part + bound + fix + (size_t)(ra + rb) * 16 + (size_t)ra * 17 + (size_t)jb * 12;
-            }
-            // (the grids are int32, the tables count slots in int32)
-            const bool full = ch.p0 < p && (used + need > budget || ch.wg + wg > 0x7fffffff || ch.jblocks + jb > 0x7fffffff ||
-                                            ch.mblocks + mb > 0x7fffffff || ch.nslots + 2 > (1 << 24) ||
-                                            (wide && ch.wrows + wg * kStageRows > 0x3fffffff));
-            if (full) close(p);
-            if (wg > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, who + ": one pair needs more than 2^31 - 1 workgroups");
-            if (wide && wg * kStageRows > 0x3fffffff) return fail(ctx, FM_EUNSUPPORTED, who + ": one pair of a wide collection has more than 2^30 rows");
-            used += need;
-            if (ra > 0 && rb > 0) {
-                ch.nslots += ndir; ch.wg += wg; ch.mblocks += mb; ch.jblocks += jb; ch.entries += a.knn2 ? 0 : ra;
-                ch.lists += a.knn2 ? ra : ra + rb;
-                ch.part += part; ch.bound += bound; ch.fix += wide ? 0 : fix;
-                if (wide) { ch.wrows += wg * kStageRows; ch.work += (double)ndir * (double)ra * (double)rb; }
-                sum_entries += a.knn2 ? 0 : ra;
-            }
-        }
-        close(n_pairs);
-    } catch (const std::bad_alloc&) { return fail(ctx, FM_ENOMEM, who + ": out of host memory"); }
-    // workspaces, all before anything is enqueued: ws_out = offsets | carry | lists | per-row arrays | block arrays | packed
-    // columns (host form), ws_partial = partials | bounds | tie lists of one chunk (integer route), ws_in = the tables
-    const int64_t ccap = a.to_dev ? 0 : std::min<int64_t>(cap, sum_entries);
-    size_t off = 0;
-    const size_t o_off = carve(off, ((size_t)n_pairs + 1) * 8), o_carry = carve(off, 16);
-    if (a.knn2) max_lists = ni * nq;               // the lists ARE the result: every image's, [n_images][nq][2]
-    const size_t o_li = carve(off, (size_t)max_lists * 8), o_ld = carve(off, (size_t)max_lists * 8);
-    const size_t o_tidx = carve(off, (size_t)max_entries * 4), o_dist = carve(off, (size_t)max_entries * 4), o_ratio = carve(off, (size_t)max_entries * 8);
-    const size_t o_pass = carve(off, (size_t)max_entries), o_bc = carve(off, (size_t)max_jblocks * 4), o_bb = carve(off, (size_t)max_jblocks * 8);
-    const size_t o_cq = carve(off, (size_t)ccap * 4), o_ct = carve(off, (size_t)ccap * 4), o_cd = carve(off, (size_t)ccap * 4), o_cr = carve(off, (size_t)ccap * 8);
-    if ((rc = ws_ensure(ctx, &ctx->ws_out, &ctx->ws_out_bytes, off + 64)) != FM_OK) return rc;
-    if (i8 && max_part > 0 && (rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, max_part + max_bound + max_fix + 64)) != FM_OK) return rc;
-    max_part = align256(max_part); max_bound = align256(max_bound);
-    const size_t w_cnt = max_part, w_bound = w_cnt + 256, w_list = w_bound + max_bound, w_score = w_list + align256(max_cap * 8);
-    if (wide && max_part > 0 && (rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, w_score + align256(max_cap * 4) + 64)) != FM_OK) return rc;
-    if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, tab_bytes + 64)) != FM_OK) return rc;
-    if (ctx->tab_in_flight) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_tab)); ctx->tab_in_flight = false; }
-    if (!ctx->ev_tab) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming));
-    if (tab_bytes > ctx->h_tab_bytes) {
-        if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
-        ctx->h_tab = nullptr; ctx->h_tab_bytes = 0;
-        const size_t want = tab_bytes + tab_bytes / 4 + 4096;
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_tab, want, hipHostMallocDefault));
-        ctx->h_tab_bytes = want;
-    }
-    char* b = (char*)ctx->ws_out;
-    char* h = ctx->h_tab;
-    const char* d = (const char*)ctx->ws_in;
-    char* wp = (char*)ctx->ws_partial;
-    // pass 2: the tables, now that every address is known
-    struct FixJob { size_t chunk; unsigned* fix; int ia, ib; int64_t out; };
-    std::vector<FixJob> fixes;
-    for (size_t k = 0; k < chunks.size(); ++k) {
-        PairsChunk& ch = chunks[k];
-        const int np = (int)(ch.p1 - ch.p0);
-        WideSlot* wsl = (WideSlot*)(h + ch.o_ws);
-        int* ww0 = (int*)(h + ch.o_ww);
-        int* wr0 = (int*)(h + ch.o_wr);
-        int wrow = 0;
-        // a chunk whose slots fill the chip without splits takes one split per slot
-        const bool one_split = ch.wg >= 512 && ctx->tune.f32_nsplit == 0;
-        PairsMergeSlot* ms = (PairsMergeSlot*)(h + ch.o_ms);
-        int* mb0 = (int*)(h + ch.o_mb);
-        PairsJoinSlot* js = (PairsJoinSlot*)(h + ch.o_js);
-        int* jb0 = (int*)(h + ch.o_jb);
-        int slot = 0, wg = 0, mb = 0, jb = 0;
-        int64_t list = 0, entry = 0;
-        size_t at_p = 0, at_b = max_part, at_f = max_part + max_bound;
-        for (int j = 0; j < np; ++j) {
-            const int64_t p = ch.p0 + j;
-            PairsJoinSlot& s = js[j];
-            s = PairsJoinSlot{};
-            jb0[j] = jb;
-            if (!live(p)) continue;
-            const int ia = qm ? -1 : pairs[2 * p], ib = qm ? (int)p : pairs[2 * p + 1];
-            const int64_t ra = rows_a(p), rb = rows_b(p);
-            s.fwd = a.knn2 ? p * nq : list; s.rev = list + ra; s.e0 = entry; s.nq = (int32_t)ra; s.nt = (int32_t)rb;
-            for (int dir = 0; i8 && dir < 2; ++dir) {
-                const int io = dir ? ib : ia, ir = dir ? ia : ib;
-                const fm::Bank vo = coll_view(c, io), vr = coll_view(c, ir);
-                const SlotPlan sp = slot_plan(io, ir);
-                unsigned long long* part = (unsigned long long*)(wp + at_p);
-                int* bound = sp.bound ? (int*)(wp + at_b) : nullptr;
-                unsigned* fix = sp.fix ? (unsigned*)(wp + at_f) : nullptr;
-                at_p += sp.part; at_b += sp.bound; at_f += sp.fix;
-                const int g = rowreduce_table_set(h + ch.o_rr, ch.nslots, slot, wg, vo, vr, sp.pl, part, bound);
-                if (g < 1) return fail(ctx, FM_EDEVICE, who + ": internal: a slot's plan is not in the batched shape");
-                PairsMergeSlot& m = ms[slot];
-                m.partial = part; m.fix = fix; m.out = dir ? s.rev : s.fwd;
-                m.nsplit = sp.pl.nsplit; m.ncols_alloc = sp.pl.ncols_alloc; m.nrows = (int)vo.n; m.pad_ = 0;
-                mb0[slot] = mb;
-                if (fix) fixes.push_back(FixJob{k, fix, io, ir, m.out});
-                wg += g; mb += (int)((vo.n + 255) / 256);
-                ++slot;
-            }
-            for (int dir = 0; wide && dir < ndir; ++dir) {
-                const int io = dir ? ib : ia, ir = dir ? ia : ib;           // (-1: the query bank, whose first row is 0)
-                const int64_t no = dir ? rb : ra, nr = dir ? ra : rb;
-                WideSlot& w = wsl[slot];
-                w.col0 = io < 0 ? 0 : (int)c->phys[(size_t)io]; w.ncols = (int)no;
-                w.red0 = ir < 0 ? 0 : (int)c->phys[(size_t)ir]; w.nred = (int)nr;
-                // the slot's scale terms (launch_wide_filter's): the stack's scale is read here, at the call -- a later add may
-                // lift it -- the query's was fixed at its creation
-                const int dk = !qm ? 0 : dir ? a.q->kscale - c->stack.kscale : c->stack.kscale - a.q->kscale;      // kred - kcol
-                w.outside = !qm ? 0 : dir ? kWideOutRed : kWideOutCols;
-                w.cscale = ldexpf(1.f, dk); w.nscale = ldexpf(1.f, 2 * dk);
-                w.red_nm_max = (qm && dir) ? a.q->nm_max : c->stack.nm_max;
-                const WideFilterPlan fp = plan_wide_filter(pad128(no), no, pad128(nr), ctx->tune);
-                w.ntiles = fp.ntiles;
-                w.nsplit = one_split ? 1 : fp.nsplit;
-                w.tiles_per_split = one_split ? fp.ntiles : fp.tiles_per_split;
-                w.row0 = wrow;
-                ww0[slot] = wg; wr0[slot] = wrow;
-                PairsMergeSlot& m = ms[slot];
-                m.partial = (unsigned long long*)wp + (size_t)wrow * 2; m.fix = nullptr; m.out = dir ? s.rev : s.fwd;
-                m.nsplit = 1; m.ncols_alloc = (int)pad128(no); m.nrows = (int)no; m.pad_ = 0;
-                mb0[slot] = mb;
-                wg += fp.nchunks * w.nsplit; wrow += (int)pad128(no); mb += (int)((no + 255) / 256);
-                ++slot;
-            }
-            if (a.knn2) continue;
-            list += ra + rb; entry += ra; jb += (int)((ra + 255) / 256);
-        }
-        if (wide && ch.nslots > 0) { ww0[ch.nslots] = wg; wr0[ch.nslots] = wrow; mb0[ch.nslots] = mb; ch.fwg = wg; }
-        jb0[np] = jb;
-        if (i8 && ch.nslots > 0) { rowreduce_table_end(h + ch.o_rr, ch.nslots, wg); mb0[ch.nslots] = mb; }
-    }
-    long long* d_off = a.to_dev ? (long long*)a.d_offsets : (long long*)(b + o_off);
-    long long* d_carry = (long long*)(b + o_carry);
-    int32_t* l_idx = (int32_t*)(b + o_li); float* l_dist = (float*)(b + o_ld);
-    CallScope cs(ctx);
-    for (int64_t p = 0; p < n_pairs; ++p) {
-        if (!live(p)) continue;
-        const int64_t ra = rows_a(p), rb = rows_b(p);
-        ctx->pending_pairs += ndir * ra * rb;
-        ctx->pending_bytes += ndir * (ra + rb) * (i8 ? 128 : wide ? 1024 : c->stack.kind == FM_BANK_BIN ? c->stack.dim : 512);
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, h, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_tab, ctx->stream));
-    ctx->tab_in_flight = true;
-    HIP_TRY(ctx, hipMemsetAsync(d_carry, 0, 16, ctx->stream));
-    if (a.knn2) {
-        // an image without rows keeps its slot: -1 / +inf, fm_knn2's lists over an empty bank
-        bool any_empty = false;
-        for (int64_t p = 0; p < n_pairs && !any_empty; ++p) any_empty = !live(p);
-        if (any_empty) {
-            HIP_TRY(ctx, hipMemsetAsync(l_idx, 0xff, (size_t)ni * nq * 8, ctx->stream));
-            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)l_dist, 0x7f800000, (size_t)ni * nq * 2, ctx->stream));
-        }
-    }
-    bool timed = false;
-    size_t next_fix = 0;
-    for (size_t k = 0; k < chunks.size(); ++k) {
-        const PairsChunk& ch = chunks[k];
-        const int np = (int)(ch.p1 - ch.p0);
-        if (ch.nslots > 0 && i8) {
-            if (ch.bound) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(wp + max_part), (int)0x80000000, ch.bound / 4, ctx->stream));
-            if (ch.fix) HIP_TRY(ctx, hipMemsetAsync(wp + max_part + max_bound, 0, ch.fix, ctx->stream));
-            if (!timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-            timed = true;
-            HIP_TRY(ctx, launch_rowreduce_table2(d + ch.o_rr, ch.nslots, (int)ch.wg, ctx->stream));
-            hipLaunchKernelGGL(coll_pairs_merge_kernel, dim3((unsigned)ch.mblocks), dim3(256), 0, ctx->stream,
-                               (const PairsMergeSlot*)(d + ch.o_ms), (const int*)(d + ch.o_mb), ch.nslots, l_idx, l_dist);
-            HIP_TRY(ctx, hipGetLastError());
-            for (; next_fix < fixes.size() && fixes[next_fix].chunk == k; ++next_fix) {
-                const FixJob& fj = fixes[next_fix];
-                const fm::Bank vo = coll_view(c, fj.ia), vr = coll_view(c, fj.ib);
-                hipLaunchKernelGGL(coll_sqrt_fix_kernel, dim3(kFixGrid), dim3(256), 0, ctx->stream, (const unsigned*)fj.fix,
-                                   (const int8_t*)vo.rows8, (const int32_t*)vo.norm, (const int8_t*)vr.rows8, (const int32_t*)vr.norm,
-                                   (int)vr.n, CollTab{nullptr, nullptr, nullptr}, fj.out, (int32_t*)nullptr, l_idx, l_dist);
-                HIP_TRY(ctx, hipGetLastError());
-            }
-        } else if (ch.nslots > 0 && wide) {
-            unsigned long long* part = (unsigned long long*)wp;
-            const WideTableLaunch tl{(const WideSlot*)(d + ch.o_ws), (const int*)(d + ch.o_ww), (const int*)(d + ch.o_wr), ch.nslots, ch.fwg, ch.wrows, a.q};
-            if (!timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-            timed = true;
-            if (ch.filt) {
-                HIP_TRY(ctx, hipMemsetAsync(part, 0xff, (size_t)ch.wrows * 16, ctx->stream));
-                HIP_TRY(ctx, hipMemsetAsync(wp + w_cnt, 0, 256 + (size_t)ch.wrows * 4, ctx->stream));     // (the count and the bounds are neighbours)
-                HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, 8, ctx->stream));
-                HIP_TRY(ctx, launch_wide_filter_table(c->stack, tl, ch.cap, (uint2*)(wp + w_list), (float*)(wp + w_score), (unsigned*)(wp + w_bound),
-                                                      (unsigned long long*)(wp + w_cnt), ctx->d_counters, part, ctx->stream));
-                HIP_TRY(ctx, launch_wide_exact_table(c->stack, tl, part, ctx->d_counters, ctx->stream));
-                ctx->filter_launches += 1;
-            } else {
-                HIP_TRY(ctx, launch_wide_exact_table(c->stack, tl, part, nullptr, ctx->stream));
-            }
-            hipLaunchKernelGGL(coll_pairs_merge_f32_kernel, dim3((unsigned)ch.mblocks), dim3(256), 0, ctx->stream,
-                               (const PairsMergeSlot*)(d + ch.o_ms), (const int*)(d + ch.o_mb), ch.nslots, l_idx, l_dist);
-            HIP_TRY(ctx, hipGetLastError());
-        } else if (ch.nslots > 0) {
-            // float32 route, binary: the pair's two sweeps by the existing route, each followed by its one-slot merge
-            const PairsJoinSlot* js = (const PairsJoinSlot*)(h + ch.o_js);
-            if (!timed && c->stack.kind == FM_BANK_BIN) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-            timed = true;
-            for (int j = 0; j < np; ++j) {
-                const int64_t p = ch.p0 + j;
-                if (!live(p)) continue;
-                const fm::Bank va = coll_view(c, pairs[2 * p]), vb = coll_view(c, pairs[2 * p + 1]);
-                const CollTab none{nullptr, nullptr, nullptr};
-                PairSweep ps;
-                if ((rc = sweep_pair(ctx, va, vb, 2, 0, nullptr, nullptr, kSweepNoEvents | kSweepNoCount, &ps)) != FM_OK) return rc;
-                if ((rc = coll_merge_one(ctx, &ps, none, va.n, js[j].fwd, nullptr, l_idx, l_dist)) != FM_OK) return rc;
-                if ((rc = sweep_pair(ctx, vb, va, 2, 0, nullptr, nullptr, kSweepNoEvents | kSweepNoCount, &ps)) != FM_OK) return rc;
-                if ((rc = coll_merge_one(ctx, &ps, none, vb.n, js[j].rev, nullptr, l_idx, l_dist)) != FM_OK) return rc;
-            }
-        }
-        if (a.knn2) continue;                      // (the merged forward lists are the result)
-        if (ch.jblocks > 0) {
-            hipLaunchKernelGGL(coll_pairs_join_kernel, dim3((unsigned)ch.jblocks), dim3(256), 0, ctx->stream,
-                               (const PairsJoinSlot*)(d + ch.o_js), (const int*)(d + ch.o_jb), np, (const int32_t*)l_idx, (const float*)l_dist,
-                               a.tau, a.symmetric, (int32_t*)(b + o_tidx), (float*)(b + o_dist), (double*)(b + o_ratio),
-                               (uint8_t*)(b + o_pass), (int*)(b + o_bc));
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        // (device form: the first scan is the first kernel that writes the caller's buffers)
-        if (a.to_dev && k == 0 && (rc = wait_for_stream(ctx, a.consumer)) != FM_OK) return rc;
-        hipLaunchKernelGGL(coll_pairs_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, (const int*)(b + o_bc), (int)ch.jblocks,
-                           (const int*)(d + ch.o_jb), np, d_carry, (long long*)(b + o_bb), d_off + ch.p0);
-        HIP_TRY(ctx, hipGetLastError());
-        if (ch.jblocks > 0 && cap > 0) {
-            hipLaunchKernelGGL(coll_pairs_compact_kernel, dim3((unsigned)ch.jblocks), dim3(256), 0, ctx->stream,
-                               (const PairsJoinSlot*)(d + ch.o_js), (const int*)(d + ch.o_jb), np, (const int32_t*)(b + o_tidx),
-                               (const float*)(b + o_dist), (const double*)(b + o_ratio), (const uint8_t*)(b + o_pass),
-                               (const long long*)(b + o_bb), (const long long*)(d_off + ch.p0), cap, (int32_t*)(b + o_cq),
-                               (int32_t*)(b + o_ct), (float*)(b + o_cd), (double*)(b + o_cr), a.to_dev ? a.d_rows : (int32_t*)nullptr);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-    }
-    if (timed) {
-        if (c->stack.kind != FM_BANK_F32) HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));   // (the float32 route brackets its sweeps itself)
-        ctx->kernel_timed = true;
-    }
-    if (a.knn2) {
-        // (copies of up to 128 MB each keep the staging buffer of fm::d2h within bounds)
-        const size_t total = (size_t)ni * nq * 8, piece = (size_t)128 << 20;
-        for (size_t o = 0; o < total; o += piece) {
-            const size_t nb = std::min(piece, total - o);
-            HIP_TRY(ctx, d2h(ctx, (char*)a.k_idx + o, (char*)l_idx + o, nb));
-            HIP_TRY(ctx, d2h(ctx, (char*)a.k_dist + o, (char*)l_dist + o, nb));
-        }
-        return cs.finish();
-    }
-    if (a.to_dev) {
-        if ((rc = results_written(ctx, a.consumer)) != FM_OK) return rc;
-        ctx->rows_stream = ctx->stream;
-        if (!a.n_total) return FM_OK;              // (enqueued: nothing waits for the device)
-        long long total = 0;                       // the caller asked for a host number: the call's one synchronisation
-        HIP_TRY(ctx, hipMemcpyAsync(&total, d_carry, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        *a.n_total = (int64_t)total;
-        return FM_OK;
-    }
-    // the offsets decide how much is copied: they come down first, then the rows of the longest prefix of whole pairs
-    std::vector<long long> ho;
-    try { ho.resize((size_t)n_pairs + 1); } catch (const std::bad_alloc&) { return fail(ctx, FM_ENOMEM, who + ": out of host memory"); }
-    HIP_TRY(ctx, hipMemcpyAsync(ho.data(), d_off, ((size_t)n_pairs + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    size_t m = 0;
-    if (cap > 0) m = (size_t)*(std::upper_bound(ho.begin(), ho.end(), (long long)cap) - 1);
-    const size_t piece = (size_t)32 << 20;           // (rows per copy: the staging buffer of fm::d2h stays within bounds)
-    for (size_t o = 0; o < m; o += piece) {
-        const size_t nb = std::min(piece, m - o);
-        HIP_TRY(ctx, d2h(ctx, a.qidx + o, (int32_t*)(b + o_cq) + o, nb * 4));
-        HIP_TRY(ctx, d2h(ctx, a.tidx + o, (int32_t*)(b + o_ct) + o, nb * 4));
-        HIP_TRY(ctx, d2h(ctx, a.dist + o, (float*)(b + o_cd) + o, nb * 4));
-        HIP_TRY(ctx, d2h(ctx, a.ratio + o, (double*)(b + o_cr) + o, nb * 8));
-    }
-    if ((rc = cs.finish()) != FM_OK) return rc;
-    for (int64_t p = 0; p <= n_pairs; ++p) a.offsets[p] = (int64_t)ho[(size_t)p];
-    if (a.n_total) *a.n_total = (int64_t)ho[(size_t)n_pairs];
-    return FM_OK;
-}
-
-extern "C" int fm_collection_pairs_mutual_ratio(fm_ctx* ctx, fm_collection* c, const int32_t* pairs, int64_t n_pairs, double tau,
-                                                int32_t symmetric, int64_t cap, int64_t* offsets, int32_t* qidx, int32_t* tidx,
-                                                float* dist, double* ratio, int64_t* n_total)
-{
-    const CollPairsArgs a{"fm_collection_pairs_mutual_ratio", tau, symmetric, cap, offsets, qidx, tidx, dist, ratio,
-                          false, nullptr, nullptr, FM_NO_STREAM, n_total};
-    return coll_pairs_mutual(ctx, c, pairs, n_pairs, a);
-}
-
-extern "C" int fm_collection_pairs_mutual_ratio_dev(fm_ctx* ctx, fm_collection* c, const int32_t* pairs, int64_t n_pairs, double tau,
-                                                    int32_t symmetric, int64_t cap, int64_t* d_offsets, int32_t* d_rows,
-                                                    int64_t* n_total, void* consumer_stream)
-{
-    const CollPairsArgs a{"fm_collection_pairs_mutual_ratio_dev", tau, symmetric, cap, nullptr, nullptr, nullptr, nullptr, nullptr,
-                          true, d_offsets, d_rows, consumer_stream, n_total};
-    return coll_pairs_mutual(ctx, c, pairs, n_pairs, a);
-}
-
-// ---------------------------------------------------------------------------------------
-// a wide query bank against every image of a wide collection: fm_collection_wide_mutual_ratio_each, _wide_knn2_each
-// ---------------------------------------------------------------------------------------
-// The match graph's machinery with "pair" p = (q, image p): the forward slot's output rows are the query bank's -- an operand
-// outside the stack, with its own planes and fp16 scale (wide_f32.hip, part 5) -- the reverse slot's reduced rows are.  The
-// chunks, tables, merge, join, scan and compaction are coll_pairs_mutual's (CollPairsArgs::q).
-// The checks in front of it, in the header's order: handles, the collection's kind, the query's kind and width.
-static int coll_wide_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const char* who, const char* narrow)
-{
-    int rc = coll_check(ctx, c, who);
-    if (rc != FM_OK) return rc;
-    if (!q) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank is NULL");
-    if (!c->rows.empty() && !coll_is_wide(c))
-        return fail(ctx, FM_EINVAL, std::string(who) + ": the collection holds images of another kind (not wide ones, fm_collection_add_wide); "
-                                    "it is served by " + narrow);
-    if (q->kind != FM_BANK_F32W)
-        return fail(ctx, FM_EINVAL, std::string(who) + ": the query bank is not a wide float bank (FM_BANK_F32W, 129 <= dim <= 256)");
-    if (c->dim != 0 && q->dim != c->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": the query's width differs from the collection's");
-    return FM_OK;
-}
-
-extern "C" int fm_collection_wide_knn2_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t* idx, float* dist)
-{
-    const char* who = "fm_collection_wide_knn2_each";
-    const int rc = coll_wide_query_check(ctx, c, q, who, "fm_collection_knn2_each");
-    if (rc != FM_OK) return rc;
-    CollPairsArgs a{who, 0.0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, FM_NO_STREAM, nullptr};
-    a.q = q; a.knn2 = true; a.k_idx = idx; a.k_dist = dist;
-    return coll_pairs_mutual(ctx, c, nullptr, (int64_t)c->rows.size(), a);
-}
-
-extern "C" int fm_collection_wide_mutual_ratio_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t symmetric, int64_t cap,
-                                                    int64_t* offsets, int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_total)
-{
-    const char* who = "fm_collection_wide_mutual_ratio_each";
-    const int rc = coll_wide_query_check(ctx, c, q, who, "fm_collection_mutual_ratio_each");
-    if (rc != FM_OK) return rc;
-    CollPairsArgs a{who, tau, symmetric, cap, offsets, qidx, tidx, dist, ratio, false, nullptr, nullptr, FM_NO_STREAM, n_total};
-    a.q = q;
-    return coll_pairs_mutual(ctx, c, nullptr, (int64_t)c->rows.size(), a);
-}
-
-extern "C" int fm_collection_wide_mutual_ratio_each_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t symmetric,
-                                                        int64_t cap, int64_t* d_offsets, int32_t* d_rows, int64_t* n_total,
-                                                        void* consumer_stream)
-{
-    const char* who = "fm_collection_wide_mutual_ratio_each_dev";
-    const int rc = coll_wide_query_check(ctx, c, q, who, "fm_collection_mutual_ratio_each");
-    if (rc != FM_OK) return rc;
-    CollPairsArgs a{who, tau, symmetric, cap, nullptr, nullptr, nullptr, nullptr, nullptr, true, d_offsets, d_rows, consumer_stream, n_total};
-    a.q = q;
-    return coll_pairs_mutual(ctx, c, nullptr, (int64_t)c->rows.size(), a);
 }

@@ -1,6 +1,6 @@
 // What the translation units behind the C-ABI share: the context object, error plumbing, workspace and
 // device-to-host helpers.  api_ctx.hip (context, options, banks) defines the functions declared here;
-// api_match.hip (2-NN, cross-check, batches, rounds), api_collection.hip (train collections), api_expand.hip (K7 glue)
+// api_match.hip (2-NN, cross-check, batches, rounds), api_collection.hip and api_pairs.hip (train collections), api_expand.hip (K7 glue)
 // and comm.hip (result gather) use them.  Internal: nothing here is part of include/fastmatch_hip.h.
 #pragma once
 #include "fm_internal.h"
@@ -161,6 +161,20 @@ void* pinned_device_alias(const void* host);
 // Device -> caller memory on the context's stream (through a copy kernel and, for pageable destinations, the
 // context's page-locked staging buffer: moved to the caller by CallScope::finish()).
 hipError_t d2h(fm_ctx* ctx, void* dst, const void* src, size_t bytes);
+// The elements [0, n) of several columns (elem bytes per element each), copied down `piece` elements at a time, column after
+// column: d2h's staging buffer grows to the largest single copy, so a large result comes down in pieces.
+struct D2hColumn { void* dst; const void* src; size_t elem; };
+inline hipError_t d2h_pieces(fm_ctx* ctx, size_t n, size_t piece, std::initializer_list<D2hColumn> cols)
+{
+    for (size_t o = 0; o < n; o += piece) {
+        const size_t m = n - o < piece ? n - o : piece;
+        for (const D2hColumn& c : cols) {
+            const hipError_t e = d2h(ctx, (char*)c.dst + o * c.elem, (const char*)c.src + o * c.elem, m * c.elem);
+            if (e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
 // Account the calls that were enqueued without a synchronisation; the streams must be idle.
 int drain_pending(fm_ctx* ctx);
 // Everything enqueued on the context -- its own stream and the tail streams the async entry points use.
