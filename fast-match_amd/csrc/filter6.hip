@@ -9,7 +9,9 @@
 // scale operands: the builtin with all four scale arguments 0): a wave holds 128 output rows and multiplies a 32-row
 // unit of the streamed bank against them with 8 instructions.  FP6 is lossy, so the sweep is a FILTER with a static
 // per-row threshold that provably keeps every candidate at d2 <= D* - 1 (fp6_filter.h); there are no shared bounds, no
-// atomics on the fast path and no top-K state.  A lane whose 16 candidates of a 32-row unit (one output row, half of the
+// atomics on the fast path and no top-K state.  The accumulators start at zero; the rows' start values -|m|^2 / 2 (the 1 KiB
+// behind a stage's rows in the plane, staged into a ring of four slots beside the stage buffers) are read only by a block
+// that passes a screen against thr - (the stage's largest start), which is then tested exactly.  A lane whose 16 candidates of a 32-row unit (one output row, half of the
 // unit's rows) clear its threshold writes (output row, unit, half) to its wave's list in LDS, which the wave copies to the
 // pair's list when it is full and when its sweep ends;
 // rescore6_kernel then computes the exact int32 d2 of each listed row against those 16 streamed rows from the int8
@@ -44,10 +46,15 @@ constexpr int kF6NC = 4, kF6NW = 8;                       // blocks of 32 output
 constexpr int kF6PieceRows = 512;                         // K1's chunk in the batched shape: the granule of the plan and of `partial`
 constexpr int kF6ChunkRows = 32 * kF6NC * kF6NW;          // 1024: two of K1's chunks per workgroup
 constexpr int kF6Units = kStageRows / kTileRows;          // 32-row units per stage: 4
-constexpr float kF6Never = 3.0e38f;                       // threshold of an output row beyond the bank: no accumulator reaches it
 constexpr int kF6HitSlots = 128;                          // records of a wave's private list in LDS (one block's ballot delivers <= 64)
 static_assert(kF6HitSlots >= 64 && kF6HitSlots % 64 == 0, "a block's ballot must fit an empty list; the flush copies 64 at a time");
-static_assert(3 * kStageBytes + kF6NW * kF6HitSlots * 8 <= 65536, "the kernel's static LDS");
+// static LDS: three stage buffers of rows alone, a ring of four stages' accumulator starts, the waves' lists
+constexpr int kF6RingSlots = 4;
+constexpr int kF6RingOff = 3 * kStageRowBytes;
+constexpr int kF6HitsOff = kF6RingOff + kF6RingSlots * kStageAuxBytes;
+constexpr int kF6LdsBytes = kF6HitsOff + kF6NW * kF6HitSlots * 8;
+constexpr int kF6SmaxWord = kStageRows;                   // aux6[stage][128]: the largest start among the stage's real rows
+static_assert(kF6LdsBytes == 61440 && kF6LdsBytes <= 65536, "the kernel's static LDS");
 
 struct F6Params {
     const uint8_t* col_rows6;
@@ -55,7 +62,7 @@ struct F6Params {
     int            ncols;         // real output rows
     int            ncols_pad;
     const uint8_t* red_rows6;
-    const float*   red_aux6;      // [stage][256]: accumulator start of the stage's 128 rows, 128 unused words
+    const float*   red_aux6;      // [stage][256]: accumulator start of the stage's 128 rows, their maximum, 127 unused words
     const int32_t* red_max;       // [2]: largest |m|^2, largest |m - m^|^2 of the streamed bank
     int            nstages, nsplit, nchunks, stages_per_split, ncols_alloc;      // K1's plan: the layout of `partial`
     int            nsplit_f, stages_per_split_f;                                 // the filter's own splits of the streamed bank (fp6_plan.h)
@@ -78,8 +85,9 @@ struct F6Batch {
     int      first_block[kRRBatchMax + 1];
 };
 
-// K1's issue_stage<true, 8>: 128 rows (16 KiB) + 1 KiB of accumulator starts per stage
-__device__ __forceinline__ void f6_issue_stage(const uint8_t* red_rows6, const float* red_aux6, int stage, char* buf, int wave, int lane)
+// K1's issue_stage<true, 8>: 128 rows (16 KiB) into a stage buffer, the stage's 1 KiB of accumulator starts into `aux`, its
+// slot of the ring
+__device__ __forceinline__ void f6_issue_stage(const uint8_t* red_rows6, const float* red_aux6, int stage, char* buf, char* aux, int wave, int lane)
 {
     const uint8_t* src_rows = red_rows6 + (size_t)stage * kStageRowBytes;
     const int slot = lane & 7;
@@ -93,16 +101,16 @@ __device__ __forceinline__ void f6_issue_stage(const uint8_t* red_rows6, const f
     }
     if (wave == kF6NW - 1) {
         const float* src = red_aux6 + (size_t)stage * (kStageAuxBytes / 4) + (unsigned)(lane * 4);
-        __builtin_amdgcn_global_load_lds(F6_GLB_PTR(src), F6_LDS_PTR(buf + kStageRowBytes), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(F6_GLB_PTR(src), F6_LDS_PTR(aux), 16, 0, 0);
     }
 }
 
 // One 32-row unit of the streamed bank as a lane reads it: per K-half h the two 16-byte pieces of slot 2 h + (lane >> 5) of
-// row lane & 31 (the last 8 bytes are the slot's padding: the 6-register operand ends in front of them), and the accumulator
-// starts of the lane's 16 rows in the 32 x 32 C layout -- register r holds streamed row (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
+// row lane & 31 (the last 8 bytes are the slot's padding: the 6-register operand ends in front of them).  The accumulator
+// starts of the lane's 16 rows -- in the 32 x 32 C layout register r holds streamed row (r & 3) + 8 (r >> 2) + 4 (lane >> 5) --
+// are not part of it: they are read where a block passes the screen (below).
 struct F6Unit {
     v8i_6  a[2];      // (registers 6 and 7 are never written: the operand is the first six)
-    v16f_6 c;
 };
 
 __device__ __forceinline__ float f6_max16(const v16f_6& a)
@@ -124,7 +132,7 @@ __device__ __forceinline__ float f6_max16(const v16f_6& a)
 __global__ __launch_bounds__(64 * kF6NW, 2)
 void filter6_kernel(F6Batch b)
 {
-    __shared__ __attribute__((aligned(16))) char smem[3 * kStageBytes + kF6NW * kF6HitSlots * 8];
+    __shared__ __attribute__((aligned(16))) char smem[kF6LdsBytes];
     int pair = 0;
 #pragma unroll
     for (int i = 1; i < kRRBatchMax; ++i) pair += (int)blockIdx.x >= b.first_block[i] ? 1 : 0;
@@ -200,8 +208,8 @@ void filter6_kernel(F6Batch b)
         // in order, so the loads have landed at a counted vmcnt; the stage loop's hand-over waits count on the same order.
         // (The presets of `partial` above are older stores: they can only make the wait longer.)
         const int nfirst = min(st1 - st0, 2);
-        if (nfirst > 0) f6_issue_stage(red_rows6, red_aux6, st0, smem, wave, lane);
-        if (nfirst > 1) f6_issue_stage(red_rows6, red_aux6, st0 + 1, smem + kStageBytes, wave, lane);
+        if (nfirst > 0) f6_issue_stage(red_rows6, red_aux6, st0, smem, smem + kF6RingOff + (st0 & 3) * kStageAuxBytes, wave, lane);
+        if (nfirst > 1) f6_issue_stage(red_rows6, red_aux6, st0 + 1, smem + kStageRowBytes, smem + kF6RingOff + ((st0 + 1) & 3) * kStageAuxBytes, wave, lane);
         if (nfirst > 1) {
             if (wave == kF6NW - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * (kDmaPerWave + 1)) : "memory");
             else                   asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * kDmaPerWave) : "memory");
@@ -230,8 +238,7 @@ void filter6_kernel(F6Batch b)
         }
     }
 
-    // per-lane LDS offsets of the streamed fragments (the two 16-byte pieces of slot 2 h + hs, swizzled as staged) and of
-    // the lane's accumulator starts
+    // per-lane LDS offsets of the streamed fragments (the two 16-byte pieces of slot 2 h + hs, swizzled as staged)
     const int sw = (r32 >> 1) & 7;
     int aoff0[2], aoff1[2];
 #pragma unroll
@@ -239,10 +246,12 @@ void filter6_kernel(F6Batch b)
         aoff0[h] = r32 * kDim + 16 * ((2 * (2 * h + hs)) ^ sw);
         aoff1[h] = r32 * kDim + 16 * ((2 * (2 * h + hs) + 1) ^ sw);
     }
-    const int xoff = kStageRowBytes + 16 * hs;
 
     // stage st becomes readable in buffer BUF; the DMA of stage st + 2 goes where stage st - 1 was (every wave has the whole
-    // of that stage in registers or behind it: its reads are waited for in front of the barrier)
+    // of that stage in registers or behind it: its reads are waited for in front of the barrier).  The starts go to slot
+    // stage & 3 of a ring of FOUR: the last unit of stage st - 1 is multiplied behind this hand-over and may still read its
+    // starts, and the slot the DMA of stage st + 2 takes is that of stage st - 2, whose last unit every wave finished in
+    // front of this barrier.
     auto hand_over = [&](auto buf_tag, int st) F6_INLINE {
         constexpr int BUF = decltype(buf_tag)::value;
         // stage st's DMA was issued two hand-overs ago; only the DMA of stage st + 1 may still be in flight (a wave that
@@ -254,7 +263,8 @@ void filter6_kernel(F6Batch b)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (st + 2 < st1) f6_issue_stage(red_rows6, red_aux6, st + 2, smem + ((BUF + 2) % 3) * kStageBytes, wave, lane);
+        if (st + 2 < st1)
+            f6_issue_stage(red_rows6, red_aux6, st + 2, smem + ((BUF + 2) % 3) * kStageRowBytes, smem + kF6RingOff + ((st + 2) & 3) * kStageAuxBytes, wave, lane);
     };
 
     auto read_unit = [&](F6Unit& x, const char* buf, int u) F6_INLINE {
@@ -266,11 +276,6 @@ void filter6_kernel(F6Batch b)
             x.a[h] = __builtin_shufflevector(__builtin_shufflevector(lo, lo, 0, 1, 2, 3, -1, -1, -1, -1),
                                              __builtin_shufflevector(hi, hi, 0, 1, -1, -1, -1, -1, -1, -1), 0, 1, 2, 3, 8, 9, -1, -1);
         }
-        v4f_6 c[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) c[q] = *(const v4f_6*)(buf + xoff + (32 * u + 8 * q) * 4);
-        x.c = v16f_6{c[0][0], c[0][1], c[0][2], c[0][3], c[1][0], c[1][1], c[1][2], c[1][3],
-                     c[2][0], c[2][1], c[2][2], c[2][3], c[3][0], c[3][1], c[3][2], c[3][3]};
     };
 
     // A wave's records wait in a private list in LDS behind the stage buffers until the list is full or the sweep ends:
@@ -279,7 +284,7 @@ void filter6_kernel(F6Batch b)
     // `nrec`, the list's fill, is wave-uniform.  The flush reserves the records on the pair's counter with one atomic,
     // copies them out and drains the vector memory counter: the hand-over waits count on the LDS-DMA being this wave's
     // newest vector memory operations.  No barrier: only this wave touches its list.
-    const uint2* const hits = (const uint2*)(smem + 3 * kStageBytes) + wave * kF6HitSlots;
+    const uint2* const hits = (const uint2*)(smem + kF6HitsOff) + wave * kF6HitSlots;
     const unsigned hits_lds = (unsigned)(uintptr_t)F6_LDS_PTR(hits);
     unsigned nrec = 0;
     auto flush = [&]() F6_INLINE {
@@ -303,31 +308,56 @@ void filter6_kernel(F6Batch b)
     // cannot count LDS reads while an LDS-DMA is in flight -- its wait in front of the first instruction is lgkmcnt(0) -- so
     // the reads of the next unit must not be issued before that wait: the scheduling barrier keeps them behind the
     // instructions, where they have this unit's epilogue and the other wave's instructions to land in.
-    auto multiply = [&](const F6Unit& x, unsigned unit, F6Unit& y, const char* ybuf, auto yu_tag) F6_INLINE {
+    //
+    // The accumulators start at ZERO (the instruction's inline constant: no C operand is read for the first K-half), so a
+    // block's maximum lacks the rows' start values.  It is screened against thr_s[j] = thr[j] - (the largest start of the
+    // unit's STAGE), rounded down (fp6_filter.h): nothing the exact test keeps fails that.  Only where a lane of the wave
+    // passes the screen does a block read the lane's 16 starts -- slot (stage & 3) of the ring, `xs` the byte offset of the
+    // unit's 32 starts in the kernel's LDS -- and repeat the test on acc + start, which is the accumulator a start value in
+    // the C operand would have given, bit for bit (every partial sum is exact).  `smax_tag`: the wave reads the largest start
+    // of the stage at ring offset `smax_off` beside the next unit's reads and moves thr_s to it behind this unit's test --
+    // the first unit behind a hand-over is the last one of the stage before and is screened against that stage's value.
+    float thr_s[kF6NC];
+#pragma unroll
+    for (int j = 0; j < kF6NC; ++j) thr_s[j] = kF6Never;
+    auto multiply = [&](const F6Unit& x, unsigned unit, int xs, F6Unit& y, const char* ybuf, auto yu_tag, auto smax_tag, int smax_off) F6_INLINE {
         v16f_6 acc[kF6NC];
+        const v16f_6 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         __builtin_amdgcn_s_setprio(2);
         // K-half major: the two instructions of a block are four apart
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int j = 0; j < kF6NC; ++j)
-                acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(x.a[h], bf[j][h], h == 0 ? x.c : acc[j], 2, 2, 0, 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(x.a[h], bf[j][h], h == 0 ? zero : acc[j], 2, 2, 0, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (decltype(yu_tag)::value >= 0) read_unit(y, ybuf, decltype(yu_tag)::value);
+        float smax = 0.f;
+        if constexpr (decltype(smax_tag)::value) smax = *(const float*)(smem + smax_off);
         __builtin_amdgcn_s_setprio(0);
         float tmax[kF6NC];
         bool any = false;
 #pragma unroll
         for (int j = 0; j < kF6NC; ++j) {
             tmax[j] = f6_max16(acc[j]);
-            any |= tmax[j] >= thr[j];
+            any |= tmax[j] >= thr_s[j];
         }
         if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
             // (both halves of the wave hold candidates of an output row: a row may be listed twice for a unit, which the
             // rescoring's atomic minimum does not mind)
 #pragma unroll
             for (int j = 0; j < kF6NC; ++j) {
-                const bool hit = tmax[j] >= thr[j];
+                if (__builtin_amdgcn_ballot_w64(tmax[j] >= thr_s[j]) == 0ull) continue;
+                // the lane's 16 starts: rows (r & 3) + 8 (r >> 2) + 4 hs of the unit, four 16-byte reads (two addresses per
+                // wave: broadcasts)
+                float emax = kFp6PadInit;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const v4f_6 s = *(const v4f_6*)(smem + xs + 16 * hs + 32 * q);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) emax = fmaxf(emax, acc[j][4 * q + k] + s[k]);
+                }
+                const bool hit = emax >= thr[j];
                 const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
                 if (m == 0ull) continue;
                 const unsigned pc = (unsigned)__popcll(m);
@@ -343,26 +373,31 @@ void filter6_kernel(F6Batch b)
                 nrec += pc;
             }
         }
+        if constexpr (decltype(smax_tag)::value) {
+#pragma unroll
+            for (int j = 0; j < kF6NC; ++j) thr_s[j] = fp6_screen_threshold(thr[j], smax);
+        }
     };
 
     // The two register sets: even and odd units of a stage.  The last unit of a stage is multiplied behind the NEXT hand-over,
     // so a wave enters the barrier with that unit's reads issued a unit earlier and leaves it with work in registers; in
-    // front of the first stage its place is taken by a unit of padding rows (below every threshold).
+    // front of the first stage its place is taken by a unit of zero codes, screened against "never" (thr_s above).
     F6Unit ua, ub;
     ub.a[0] = ub.a[1] = v8i_6{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ub.c[r] = kFp6PadInit;
     std::integral_constant<int, 0> u0;  std::integral_constant<int, 1> u1;  std::integral_constant<int, 2> u2;
     std::integral_constant<int, 3> u3;  std::integral_constant<int, -1> none;
+    std::true_type with_smax;  std::false_type no_smax;
     auto stage = [&](auto buf_tag, int st) F6_INLINE {
         constexpr int BUF = decltype(buf_tag)::value;
-        const char* buf = smem + BUF * kStageBytes;
+        const char* buf = smem + BUF * kStageRowBytes;
         const unsigned unit0 = (unsigned)(st * kF6Units);
+        // the starts of this stage's units and of the unit carried in from the stage before
+        const int xs = kF6RingOff + (st & 3) * kStageAuxBytes, xs_prev = kF6RingOff + ((st - 1) & 3) * kStageAuxBytes + 3 * 128;
         hand_over(buf_tag, st);
-        multiply(ub, unit0 - 1, ua, buf, u0);
-        multiply(ua, unit0,     ub, buf, u1);
-        multiply(ub, unit0 + 1, ua, buf, u2);
-        multiply(ua, unit0 + 2, ub, buf, u3);
+        multiply(ub, unit0 - 1, xs_prev,  ua, buf, u0, with_smax, xs + 4 * kF6SmaxWord);
+        multiply(ua, unit0,     xs,       ub, buf, u1, no_smax, 0);
+        multiply(ub, unit0 + 1, xs + 128, ua, buf, u2, no_smax, 0);
+        multiply(ua, unit0 + 2, xs + 256, ub, buf, u3, no_smax, 0);
     };
 
     if (st0 >= st1) return;
@@ -371,7 +406,7 @@ void filter6_kernel(F6Batch b)
         if (st + 1 < st1) stage(std::integral_constant<int, 1>{}, st + 1);
         if (st + 2 < st1) stage(std::integral_constant<int, 2>{}, st + 2);
     }
-    multiply(ub, (unsigned)(st1 * kF6Units) - 1u, ua, smem, none);
+    multiply(ub, (unsigned)(st1 * kF6Units) - 1u, kF6RingOff + ((st1 - 1) & 3) * kStageAuxBytes + 3 * 128, ua, smem, none, no_smax, 0);
     if (nrec != 0u) flush();
 }
 
@@ -423,7 +458,8 @@ void rescore6_kernel(F6Batch b)
 }
 
 // The FP6 plane of the rows [0, n_pad) of an integer-route bank from its int8 plane (rows8 = uint8 ^ 0x80): 4 threads per
-// row, one K-chunk each.  max6 ([2], zeroed by the caller) takes the bank's largest |m|^2 and |m - m^|^2.
+// row, one K-chunk each, a workgroup per 128-row stage.  aux6[stage][128] takes the largest accumulator start among the
+// stage's real rows (kFp6PadInit where it has none): the sweep's screen (fp6_screen_threshold).  max6 ([2], zeroed by the caller) takes the bank's largest |m|^2 and |m - m^|^2.
 __global__ __launch_bounds__(256)
 void prep6_kernel(const int8_t* __restrict__ rows8, int64_t n, int64_t n_pad, uint8_t* __restrict__ rows6,
                   float* __restrict__ aux6, int32_t* __restrict__ stat6, int32_t* __restrict__ max6)
@@ -431,9 +467,16 @@ void prep6_kernel(const int8_t* __restrict__ rows8, int64_t n, int64_t n_pad, ui
     __shared__ uint8_t code[256];
     code[threadIdx.x] = (uint8_t)fp6_code((int)threadIdx.x);
     __syncthreads();
+    __shared__ int stage_min[4];
     const int k = threadIdx.x & 3;
     int umax = 0, emax = 0;
-    for (int64_t row = (int64_t)blockIdx.x * 64 + (threadIdx.x >> 2); row < n_pad; row += (int64_t)gridDim.x * 64) {
+    // a workgroup takes whole stages, 64 rows at a time (n_pad is a multiple of the stage), and leaves the largest start of
+    // the stage's real rows -- the start of their least |m|^2 -- in the word behind the stage's starts
+    int smin = INT32_MAX;
+    for (int64_t i = 0; ; ++i) {
+        const int64_t st = (i >> 1) * gridDim.x + blockIdx.x;
+        if (st >= n_pad / kStageRows) break;
+        const int64_t row = st * kStageRows + (i & 1) * 64 + (threadIdx.x >> 2);
         unsigned w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int usq = 0, hsq = 0, esq = 0;
         if (row < n) {
@@ -458,12 +501,24 @@ void prep6_kernel(const int8_t* __restrict__ rows8, int64_t n, int64_t n_pad, ui
         esq += __shfl_xor(esq, 1); esq += __shfl_xor(esq, 2);
         if (k == 0) {
             *(int4*)(stat6 + 4 * row) = make_int4(usq, hsq, esq, 0);
-            const int64_t st = row / kStageRows, r = row % kStageRows;
+            const int64_t r = row % kStageRows;
             aux6[st * 256 + r] = row < n ? fp6_acc_init(usq) : kFp6PadInit;
-            aux6[st * 256 + 128 + r] = 0.f;
+            if (r != 0) aux6[st * 256 + kStageRows + r] = 0.f;
         }
         umax = max(umax, usq);
         emax = max(emax, esq);
+        if (row < n) smin = min(smin, usq);
+        if (i & 1) {           // (the trip count is the workgroup's: every thread is here)
+            for (int o = 32; o > 0; o >>= 1) smin = min(smin, __shfl_xor(smin, o));
+            if ((threadIdx.x & 63) == 0) stage_min[threadIdx.x >> 6] = smin;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const int m = min(min(stage_min[0], stage_min[1]), min(stage_min[2], stage_min[3]));
+                aux6[st * 256 + kStageRows] = m != INT32_MAX ? fp6_acc_init(m) : kFp6PadInit;
+            }
+            __syncthreads();
+            smin = INT32_MAX;
+        }
     }
     for (int o = 32; o > 0; o >>= 1) {
         umax = max(umax, __shfl_xor(umax, o));
@@ -479,7 +534,7 @@ hipError_t launch_prep6(const Bank& b, int grid_max, hipStream_t stream)
 {
     hipError_t e = hipMemsetAsync(b.max6, 0, 8, stream);
     if (e != hipSuccess) return e;
-    int64_t grid = (b.n_pad + 63) / 64;
+    int64_t grid = b.n_pad / kStageRows;            // a workgroup per stage
     if (grid_max > 0 && grid > grid_max) grid = grid_max;
     hipLaunchKernelGGL(prep6_kernel, dim3((unsigned)grid), dim3(256), 0, stream, (const int8_t*)b.rows8, b.n, b.n_pad,
                        b.rows6, b.aux6, b.stat6, b.max6);

@@ -60,7 +60,7 @@ struct Bank {
     uint8_t* rows4  = nullptr; // [n_pad][64 ksteps] FP4 image: bit 1 -> +1, bit 0 -> -1, padding 0
     // FM_BANK_I8 of dim 128, for the FP6 filter of the accepted-only sweep (filter6.hip, fp6_filter.h); all null: K1 only
     uint8_t* rows6  = nullptr; // [n_pad][128] e2m3 codes of the raw uint8 rows: four K-chunks of 32 codes (24 bytes) in 32-byte slots
-    float*   aux6   = nullptr; // [n_pad / 128][256] accumulator start -floor(|m|^2 / 32) / 64 of a stage's rows (padding -3.4e38), 128 unused words
+    float*   aux6   = nullptr; // [n_pad / 128][256] accumulator start -floor(|m|^2 / 32) / 64 of a stage's rows (padding -3.4e38), the largest start among its real rows, 127 unused words
     int32_t* stat6  = nullptr; // [n_pad][4] |row|^2, |image|^2, |row - image|^2 (uint8 values), 0
     int32_t* max6   = nullptr; // [2] device words: the bank's largest |row|^2 and |row - image|^2
     // FM_BANK_F32W (K14, wide_f32.hip): dim = 129 .. 256; normf, auxf, nm_max, kscale, filt_ok and vfin_max as for FM_BANK_F32,

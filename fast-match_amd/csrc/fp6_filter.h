@@ -14,7 +14,9 @@
 // partial sum is an integer number of steps of magnitude below 2^20 < 2^24: float32 holds each of them exactly whatever the
 // order of the additions.  One step is 1024 / 64 = 16 units of c^.m^; the start value rounds |m|^2 / 2 DOWN to a step, so
 // the accumulator is never below (c^.m^ - |m|^2 / 2) / 1024 and the test  acc >= T_c / 1024  (threshold rounded down to a
-// float) keeps every candidate the inequality above keeps.
+// float) keeps every candidate the inequality above keeps.  The sweep adds the start value LAST, and only where a block
+// passes a screen that needs no start (fp6_screen_threshold below): products summed from zero are the same integers of steps,
+// so acc + start is the same float32, bit for bit.
 // Plain arithmetic only, no HIP types: the host test compiles it on its own (tests/test_fp6_filter.py).
 #pragma once
 #include "ratio_cut.h"
@@ -44,6 +46,7 @@ FM_HD inline int fp6_code(int v)
 // accumulator start of a streamed row with squared norm usq (raw uint8 values): -floor(usq / 32) steps of 1/64
 FM_HD inline float fp6_acc_init(int usq) { return -(float)(usq >> 5) * (1.0f / 64.0f); }
 constexpr float kFp6PadInit = -3.4e38f;        // padding rows: below every threshold
+constexpr float kF6Never = 3.0e38f;            // threshold of an output row beyond the bank: no accumulator reaches it
 
 // E_c of an output row (squared norms of its image and of its error) against a streamed bank (largest squared row norm,
 // largest squared error norm), rounded UP: the float64 roots and products are correct to 1 part in 2^50, the margin is 2^-20
@@ -67,6 +70,36 @@ FM_HD inline float fp6_threshold_acc(double t)
     float f = (float)x;
     if ((double)f > x) f = nextafterf(f, -INFINITY);
     return f;
+}
+
+// The sweep's screen (filter6.hip).  Its accumulators start at zero, so they lack the streamed row's start value; a block
+// is first tested against  thr_s = thr - smax, smax the LARGEST start among the real rows of the streamed stage (the word
+// prep6_kernel leaves behind the stage's starts; kFp6PadInit for a stage without a real row).  With start(m) <= smax:
+//   acc + start(m) >= thr   =>   acc >= thr - start(m) >= thr - smax >= thr_s       (acc + start(m) is exact, see above)
+// so a lane that the exact test keeps always passes the screen, provided thr_s is rounded DOWN: the largest float32 not
+// above thr - smax.  The operands are finite and never both huge with one sign except Never - PadInit, which rounds down to
+// the largest finite float: no infinity, no NaN.  On the device the subtraction runs under the round-down mode; on the host
+// the rounding error of the nearest result is recovered exactly (Knuth's two-sum) and a result above the difference steps down.
+FM_HD inline float fp6_screen_threshold(float thr, float smax)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (bits 1:0 of the MODE register: the float32 rounding, 2 = towards -infinity, 0 = nearest even, the kernel's own.  One
+    // statement, so that nothing else runs under the mode; two writes of one hardware register stand two states apart)
+    float d;
+    asm("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 2\n\t"
+        "v_sub_f32 %0, %1, %2\n\t"
+        "s_nop 1\n\t"
+        "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\t"
+        "s_nop 1" : "=v"(d) : "v"(thr), "v"(smax));
+    return d;
+#else
+    const volatile float s = thr - smax;
+    if (isinf(s)) return s > 0.f ? 3.402823466e38f : s;
+    const volatile float bb = s - thr;
+    const volatile float ra = thr - (s - bb), rb = -smax - bb;
+    const float err = ra + rb;                  // thr - smax = s + err exactly
+    return err < 0.f ? nextafterf(s, -INFINITY) : s;
+#endif
 }
 
 }  // namespace fm
