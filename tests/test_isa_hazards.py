@@ -4,41 +4,14 @@ its own wait would also drain the newest LDS-DMA).  The hand-written s_waitcnt v
 hand-over covers the load only if nothing touches the destination VGPR in between -- a copy, a spill or a
 re-allocation inserted by a future compiler would read or clobber a value that has not landed.  This test
 reads the generated ISA and checks exactly that, for every kernel that uses the construct."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+from isa_read import _regs, have_hipcc, isa as _isa, kernels as _kernels
 
 
-def _regs(operand_text):
-    """VGPR numbers mentioned in an operand string: v12, v[34:37]."""
-    out = set()
-    for a, b in re.findall(r"\bv\[(\d+):(\d+)\]", operand_text):
-        out.update(range(int(a), int(b) + 1))
-    out.update(int(x) for x in re.findall(r"\bv(\d+)\b", operand_text))
-    return out
-
-
-_ASM = {}
-
-
-def _isa(unit, tmp_path_factory):
-    """Device ISA of csrc/<unit>.hip (compiled once per test session)."""
-    if unit not in _ASM:
-        asm = str(tmp_path_factory.mktemp("isa") / (unit + ".s"))
-        subprocess.check_call([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                               os.path.join(ROOT, "fast-match_amd", "csrc", unit + ".hip"), "-o", asm],
-                              stderr=subprocess.DEVNULL)
-        _ASM[unit] = open(asm).read()
-    return _ASM[unit]
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+@pytest.mark.skipif(not have_hipcc(), reason="no hipcc")
 @pytest.mark.parametrize("unit", ["rowreduce", "filter_f16"])
 def test_lds_dma_through_inline_asm_sets_m0_itself(unit, tmp_path_factory):
     """The LDS-DMA helpers written as inline asm (rowreduce.hip lds_dma_16 / lds_dma_4, filter_f16.hip f_lds_dma_16) load M0
@@ -48,26 +21,14 @@ def test_lds_dma_through_inline_asm_sets_m0_itself(unit, tmp_path_factory):
     holds a compiler-generated user of M0 (the builtin's global_load_lds, whose M0 set-up the compiler may hoist or reuse
     across our statements).  This reads the generated ISA and checks both, kernel by kernel."""
     text = _isa(unit, tmp_path_factory)
-    kernels = re.split(r"\n(?=_ZN2fm\w+:)", text)
     asm_kernels = 0
-    for k in kernels:
-        name = k.split(":", 1)[0]
-        if not name.startswith("_ZN2fm"):
-            continue
-        lines = [l.strip() for l in k.split("s_endpgm")[0].splitlines()]
-        in_asm, block = False, []
+    for k in _kernels(text, first_exit=True):
+        name = k.name
+        block_of = {i: b for b in k.blocks for i, _ in b.insns}
         asm_form, compiler_form = 0, 0
-        for l in lines:
-            if "ASMSTART" in l:
-                in_asm, block = True, []
-                continue
-            if "ASMEND" in l:
-                in_asm = False
-                continue
-            if not l or l.startswith((";", ".", "//")):
-                continue
-            if in_asm:
-                block.append(l)
+        for i, l in k.insns:
+            in_asm = i in k.in_asm
+            block = [t for j, t in block_of[i].insns if j <= i] if in_asm else []     # the statement up to this instruction
             if l.startswith("global_load_lds_dword"):
                 if in_asm:
                     asm_form += 1
@@ -83,18 +44,15 @@ def test_lds_dma_through_inline_asm_sets_m0_itself(unit, tmp_path_factory):
     assert asm_kernels >= 3
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+@pytest.mark.skipif(not have_hipcc(), reason="no hipcc")
 def test_untracked_bound_loads_are_not_touched_before_their_wait(tmp_path_factory):
     text = _isa("rowreduce", tmp_path_factory)
-    kernels = re.split(r"\n(?=_ZN2fm\w+:)", text)
     checked = 0
-    for k in kernels:
-        name = k.split(":", 1)[0]
-        if not name.startswith("_ZN2fm") or "sc1" not in k:
+    for k in _kernels(text, first_exit=True):
+        name = k.name
+        if "sc1" not in k.text:
             continue
-        body = k.split(".end_amdhsa_kernel")[0] if ".end_amdhsa_kernel" in k else k
-        lines = [l.strip() for l in body.split("s_endpgm")[0].splitlines()]
-        insns = [(i, l) for i, l in enumerate(lines) if l and not l.startswith((";", ".", "//"))]
+        lines, insns = k.lines, k.insns
         # (only the inline-asm loads: the compiler tracks its own relaxed atomic loads, which look the same)
         loads = [(n, i, l) for n, (i, l) in enumerate(insns)
                  if re.match(r"global_load_dword v\d+, .*\bsc1\b", l) and i > 0 and "ASMSTART" in lines[i - 1]]
@@ -104,11 +62,7 @@ def test_untracked_bound_loads_are_not_touched_before_their_wait(tmp_path_factor
         waits = [n for n, (i, l) in enumerate(insns) if l.startswith("s_waitcnt vmcnt(") and i > 0 and "ASMSTART" in lines[i - 1]]
         assert waits, name
         # loop: the label in front of the first hand-over wait, and the last branch back to it
-        label_line = {}
-        for i, l in enumerate(lines):                        # ".LBB0_39:      ; in Loop: Header=..."
-            m = re.match(r"(\.LBB\d+_\d+):", l)
-            if m:
-                label_line[m.group(1)] = i
+        label_line = k.label_line
         first_wait_line = insns[waits[0]][0]
         header = max((i, name_) for name_, i in label_line.items() if i < first_wait_line)[1]
         back = [n for n, (i, l) in enumerate(insns) if l.startswith(("s_cbranch", "s_branch")) and l.split()[-1] == header]
