@@ -5,9 +5,10 @@
 // file sweeps splits of the streamed bank -- its own count of them, chosen for the launch as a whole (fp6_plan.h: one
 // workgroup fills a CU, K1's count was tuned for 16 waves per CU) --, two of K1's 512-row output chunks per workgroup, with
 // K1's staging -- three LDS stage buffers filled by LDS-DMA two stages ahead, the source-side XOR swizzle, the hand-over
-// waits, the s_setprio burst -- but on v_mfma_f32_32x32x64_f8f6f4 with e2m3 operands (cbsz:2 blgp:2, the form without
+// waits -- but on v_mfma_f32_32x32x64_f8f6f4 with e2m3 operands (cbsz:2 blgp:2, the form without
 // scale operands: the builtin with all four scale arguments 0): a wave holds 128 output rows and multiplies a 32-row
-// unit of the streamed bank against them with 8 instructions.  FP6 is lossy, so the sweep is a FILTER with a static
+// unit of the streamed bank against them with 8 instructions, in two halves of four with the max trees of the half
+// before between them (no priority flips: there is no burst and no epilogue to tell apart).  FP6 is lossy, so the sweep is a FILTER with a static
 // per-row threshold that provably keeps every candidate at d2 <= D* - 1 (fp6_filter.h); there are no shared bounds, no
 // atomics on the fast path and no top-K state.  The accumulators start at zero; the rows' start values -|m|^2 / 2 (the 1 KiB
 // behind a stage's rows in the plane, staged into a ring of four slots beside the stage buffers) are read only by a block
@@ -41,6 +42,8 @@ typedef float v16f_6 __attribute__((ext_vector_type(16)));
 #define F6_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define F6_GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define F6_INLINE __attribute__((always_inline))
+// the scheduler's order inside a basic block: one matrix instruction, then N vector instructions (masks 0x8, 0x2)
+#define F6_MFMA_THEN_VALU(N) do { __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x2, N, 0); } while (0)
 
 constexpr int kF6NC = 4, kF6NW = 8;                       // blocks of 32 output rows per wave, waves per workgroup
 constexpr int kF6PieceRows = 512;                         // K1's chunk in the batched shape: the granule of the plan and of `partial`
@@ -86,23 +89,20 @@ struct F6Batch {
 };
 
 // K1's issue_stage<true, 8>: 128 rows (16 KiB) into a stage buffer, the stage's 1 KiB of accumulator starts into `aux`, its
-// slot of the ring
-__device__ __forceinline__ void f6_issue_stage(const uint8_t* red_rows6, const float* red_aux6, int stage, char* buf, char* aux, int wave, int lane)
+// slot of the ring.  `wave` is the wave's number in a scalar register, so that the source and the LDS address of a piece are
+// scalar too; `off` is the lane's byte offset in a piece.  A wave's pieces are wave, wave + 8: 64 rows apart, they have one
+// swizzle and share `off`.  `last` (the last wave: it also brings the starts) is a lane value: that DMA stands under EXEC.
+__device__ __forceinline__ void f6_issue_stage(const uint8_t* red_rows6, const float* red_aux6, int stage, char* buf, char* aux, int wave, bool last,
+                                               unsigned off, unsigned aux_off)
 {
     const uint8_t* src_rows = red_rows6 + (size_t)stage * kStageRowBytes;
-    const int slot = lane & 7;
     constexpr int kPieces = 16 / kF6NW;
 #pragma unroll
     for (int i = 0; i < kPieces; ++i) {
-        const int g   = wave * kPieces + i;
-        const int row = g * 8 + (lane >> 3);
-        const uint8_t* src = src_rows + (unsigned)(row * kDim + 16 * (slot ^ ((row >> 1) & 7)));
-        __builtin_amdgcn_global_load_lds(F6_GLB_PTR(src), F6_LDS_PTR(buf + g * 1024), 16, 0, 0);
+        const int g = wave + kF6NW * i;
+        __builtin_amdgcn_global_load_lds(F6_GLB_PTR(src_rows + g * 1024 + off), F6_LDS_PTR(buf + g * 1024), 16, 0, 0);
     }
-    if (wave == kF6NW - 1) {
-        const float* src = red_aux6 + (size_t)stage * (kStageAuxBytes / 4) + (unsigned)(lane * 4);
-        __builtin_amdgcn_global_load_lds(F6_GLB_PTR(src), F6_LDS_PTR(aux), 16, 0, 0);
-    }
+    if (last) __builtin_amdgcn_global_load_lds(F6_GLB_PTR((const char*)(red_aux6 + (size_t)stage * (kStageAuxBytes / 4)) + aux_off), F6_LDS_PTR(aux), 16, 0, 0);
 }
 
 // One 32-row unit of the streamed bank as a lane reads it: per K-half h the two 16-byte pieces of slot 2 h + (lane >> 5) of
@@ -125,6 +125,18 @@ __device__ __forceinline__ float f6_max16(const v16f_6& a)
     return fmaxf(m5, m6);
 }
 
+// thr_s of two blocks from the stage's largest start (wave-uniform, in a scalar register): fp6_screen_threshold twice under
+// one change of the rounding mode (bits 1:0 of the MODE register, 2 = towards -infinity; fp6_filter.h)
+__device__ __forceinline__ void f6_screen2(float& s0, float& s1, float t0, float t1, float smax)
+{
+    asm("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 2\n\t"
+        "v_subrev_f32 %0, %4, %2\n\t"
+        "v_subrev_f32 %1, %4, %3\n\t"
+        "s_nop 1\n\t"
+        "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\t"
+        "s_nop 1" : "=&v"(s0), "=&v"(s1) : "v"(t0), "v"(t1), "s"(smax));
+}
+
 // The sweep on v_mfma_f32_32x32x64_f8f6f4: a wave owns 128 output rows (4 blocks of 32, the stationary B operand: 48
 // registers) and multiplies every 32-row unit of the streamed bank against them with 8 instructions, two per block chained
 // along K.  The reads of a unit are issued one unit ahead into a second register set, across the stage hand-over too: a
@@ -141,7 +153,13 @@ void filter6_kernel(F6Batch b)
 
     const int tid  = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = tid >> 6;
+    // (the wave's number twice: in a scalar register for every address made of it, as a lane value for the conditions on it)
+    const int wave_v = tid >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(wave_v);
+    // a lane's place in a 1 KiB piece of the LDS-DMA: row lane >> 3 of the piece's 8, 16-byte slot lane & 7, swizzled by the
+    // row's number in the stage (the piece's first row is a multiple of 8, and a wave's pieces are 64 rows apart)
+    const unsigned dma_off = (unsigned)((lane >> 3) * kDim + 16 * ((lane & 7) ^ ((((wave & 1) * 8 + (lane >> 3)) >> 1) & 7)));
+    const unsigned dma_aux_off = (unsigned)(lane * 16);
     const int r32  = lane & 31;
     const int hs   = lane >> 5;
     // everything the loop uses, once: a field read through `p` inside the loop is a scalar load of the kernel argument there
@@ -208,10 +226,10 @@ void filter6_kernel(F6Batch b)
         // in order, so the loads have landed at a counted vmcnt; the stage loop's hand-over waits count on the same order.
         // (The presets of `partial` above are older stores: they can only make the wait longer.)
         const int nfirst = min(st1 - st0, 2);
-        if (nfirst > 0) f6_issue_stage(red_rows6, red_aux6, st0, smem, smem + kF6RingOff + (st0 & 3) * kStageAuxBytes, wave, lane);
-        if (nfirst > 1) f6_issue_stage(red_rows6, red_aux6, st0 + 1, smem + kStageRowBytes, smem + kF6RingOff + ((st0 + 1) & 3) * kStageAuxBytes, wave, lane);
+        if (nfirst > 0) f6_issue_stage(red_rows6, red_aux6, st0, smem, smem + kF6RingOff + (st0 & 3) * kStageAuxBytes, wave, wave_v == kF6NW - 1, dma_off, dma_aux_off);
+        if (nfirst > 1) f6_issue_stage(red_rows6, red_aux6, st0 + 1, smem + kStageRowBytes, smem + kF6RingOff + ((st0 + 1) & 3) * kStageAuxBytes, wave, wave_v == kF6NW - 1, dma_off, dma_aux_off);
         if (nfirst > 1) {
-            if (wave == kF6NW - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * (kDmaPerWave + 1)) : "memory");
+            if (wave_v == kF6NW - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * (kDmaPerWave + 1)) : "memory");
             else                   asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * kDmaPerWave) : "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -257,14 +275,14 @@ void filter6_kernel(F6Batch b)
         // stage st's DMA was issued two hand-overs ago; only the DMA of stage st + 1 may still be in flight (a wave that
         // flushed its records since has drained its vector memory counter there, which only makes this wait a no-op)
         if (st + 1 < st1) {
-            if (wave == kF6NW - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kDmaPerWave + 1) : "memory");
+            if (wave_v == kF6NW - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kDmaPerWave + 1) : "memory");
             else                   asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kDmaPerWave) : "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if (st + 2 < st1)
-            f6_issue_stage(red_rows6, red_aux6, st + 2, smem + ((BUF + 2) % 3) * kStageRowBytes, smem + kF6RingOff + ((st + 2) & 3) * kStageAuxBytes, wave, lane);
+            f6_issue_stage(red_rows6, red_aux6, st + 2, smem + ((BUF + 2) % 3) * kStageRowBytes, smem + kF6RingOff + ((st + 2) & 3) * kStageAuxBytes, wave, wave_v == kF6NW - 1, dma_off, dma_aux_off);
     };
 
     auto read_unit = [&](F6Unit& x, const char* buf, int u) F6_INLINE {
@@ -284,10 +302,18 @@ void filter6_kernel(F6Batch b)
     // `nrec`, the list's fill, is wave-uniform.  The flush reserves the records on the pair's counter with one atomic,
     // copies them out and drains the vector memory counter: the hand-over waits count on the LDS-DMA being this wave's
     // newest vector memory operations.  No barrier: only this wave touches its list.
+    // The lane's number where the cold paths need it (hit path, flush): two instructions there instead of lane constants
+    // (lane half, row of the block, output row) that would hold registers across the whole loop.  (volatile: not hoisted)
+    auto lane_id = [&]() F6_INLINE {
+        unsigned l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        return l;
+    };
     const uint2* const hits = (const uint2*)(smem + kF6HitsOff) + wave * kF6HitSlots;
     const unsigned hits_lds = (unsigned)(uintptr_t)F6_LDS_PTR(hits);
     unsigned nrec = 0;
     auto flush = [&]() F6_INLINE {
+        const unsigned lane = lane_id();
         unsigned base = 0;
         if (lane == 0) base = atomicAdd(cnt, nrec);
         base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
@@ -304,100 +330,129 @@ void filter6_kernel(F6Batch b)
         nrec = 0;
     };
 
-    // The 8 instructions of one unit, the reads of the next one (`next`) behind them, then the unit's epilogue.  The compiler
-    // cannot count LDS reads while an LDS-DMA is in flight -- its wait in front of the first instruction is lgkmcnt(0) -- so
-    // the reads of the next unit must not be issued before that wait: the scheduling barrier keeps them behind the
-    // instructions, where they have this unit's epilogue and the other wave's instructions to land in.
-    //
     // The accumulators start at ZERO (the instruction's inline constant: no C operand is read for the first K-half), so a
     // block's maximum lacks the rows' start values.  It is screened against thr_s[j] = thr[j] - (the largest start of the
     // unit's STAGE), rounded down (fp6_filter.h): nothing the exact test keeps fails that.  Only where a lane of the wave
-    // passes the screen does a block read the lane's 16 starts -- slot (stage & 3) of the ring, `xs` the byte offset of the
-    // unit's 32 starts in the kernel's LDS -- and repeat the test on acc + start, which is the accumulator a start value in
-    // the C operand would have given, bit for bit (every partial sum is exact).  `smax_tag`: the wave reads the largest start
-    // of the stage at ring offset `smax_off` beside the next unit's reads and moves thr_s to it behind this unit's test --
-    // the first unit behind a hand-over is the last one of the stage before and is screened against that stage's value.
+    // passes the screen (`pass`, the wave's ballot) does a block read the lane's 16 starts -- slot (stage & 3) of the ring,
+    // `xs` the byte offset of the unit's 32 starts in the kernel's LDS -- and repeat the test on acc + start, which is the
+    // accumulator a start value in the C operand would have given, bit for bit (every partial sum is exact).
+    // (both halves of the wave hold candidates of an output row: a row may be listed twice for a unit, which the
+    // rescoring's atomic minimum does not mind)
+    v16f_6 acc[kF6NC];
+#pragma unroll
+    for (int j = 0; j < kF6NC; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = kFp6PadInit;
+    auto test_block = [&](auto j_tag, unsigned long long pass, unsigned unit, int xs) F6_INLINE {
+        constexpr int j = decltype(j_tag)::value;
+        if (pass == 0ull) return;
+        const unsigned l = lane_id(), hs = l >> 5;
+        // the lane's 16 starts: rows (r & 3) + 8 (r >> 2) + 4 hs of the unit, four 16-byte reads (two addresses per
+        // wave: broadcasts)
+        float emax = kFp6PadInit;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const v4f_6 s = *(const v4f_6*)(smem + xs + 16 * hs + 32 * q);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) emax = fmaxf(emax, acc[j][4 * q + k] + s[k]);
+        }
+        const bool hit = emax >= thr[j];
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+        if (m == 0ull) return;
+        const unsigned pc = (unsigned)__popcll(m);
+        if (nrec + pc > (unsigned)kF6HitSlots) flush();
+        const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        // (LDS only: the hand-over's lgkmcnt(0) covers the write, which touches no stage buffer.  As a statement of
+        // its own: in front of a store to LDS the compiler waits for vmcnt(0), the LDS-DMA being a pending LDS write)
+        if (hit) {
+            // (bit 31 of the unit word: which 16 of the unit's rows this lane's accumulators are)
+            const unsigned long long r = ((unsigned long long)(unit | (hs << 31)) << 32) | (unsigned)(cb + 32 * j + (l & 31));
+            asm volatile("ds_write_b64 %0, %1" :: "v"(hits_lds + 8u * (nrec + rank)), "v"(r) : "memory");
+        }
+        nrec += pc;
+    };
+
     float thr_s[kF6NC];
 #pragma unroll
     for (int j = 0; j < kF6NC; ++j) thr_s[j] = kF6Never;
-    auto multiply = [&](const F6Unit& x, unsigned unit, int xs, F6Unit& y, const char* ybuf, auto yu_tag, auto smax_tag, int smax_off) F6_INLINE {
-        v16f_6 acc[kF6NC];
+    float smax = 0.f;
+    std::integral_constant<int, 0> b0;  std::integral_constant<int, 1> b1;  std::integral_constant<int, 2> b2;
+    std::integral_constant<int, 3> b3;
+
+    // One unit in two halves, each one basic block of four instructions that ends in its own branch.  The max trees and
+    // compares stand BETWEEN a half's matrix instructions, on accumulators those do not write: a wave's own vector
+    // instructions issue beside its matrix instruction in flight, while behind a burst of eight they waited for the
+    // SIMD's other wave.  Half 1 multiplies blocks 0, 1 of unit `unit` and tests blocks 2, 3 of the unit before it
+    // (`punit`, starts at `pxs`), whose accumulators half 2 then overwrites; half 2 multiplies blocks 2, 3 and tests blocks
+    // 0, 1 of `unit`, with the reads of the next unit (`y`) among them.  The compiler cannot count LDS reads while an
+    // LDS-DMA is in flight -- its wait in front of a unit's first instruction is lgkmcnt(0) -- so those reads stay behind
+    // that wait; they have the rest of half 2 to land.
+    // thr_s is a STAGE's value and a unit's blocks are tested at two times.  The first unit behind a hand-over is the last
+    // one of the stage before: its blocks 0, 1 are tested in that multiply's half 2 and its blocks 2, 3 in half 1 of the
+    // next.  `smax_tag`: the wave reads the stage's largest start at ring offset `smax_off` beside the next unit's reads and
+    // moves thr_s[0], thr_s[1] to it behind this unit's second test; `late_tag`: thr_s[2], thr_s[3] follow behind the first
+    // test of this multiply.
+    auto multiply = [&](const F6Unit& x, unsigned unit, int xs, unsigned punit, int pxs, F6Unit& y, const char* ybuf, auto yu_tag,
+                        auto smax_tag, auto late_tag, int smax_off) F6_INLINE {
         const v16f_6 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        __builtin_amdgcn_s_setprio(2);
-        // K-half major: the two instructions of a block are four apart
+        // K-half major: the two instructions of a block are two apart
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int j = 0; j < kF6NC; ++j)
+            for (int j = 0; j < 2; ++j)
                 acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(x.a[h], bf[j][h], h == 0 ? zero : acc[j], 2, 2, 0, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (decltype(yu_tag)::value >= 0) read_unit(y, ybuf, decltype(yu_tag)::value);
-        float smax = 0.f;
-        if constexpr (decltype(smax_tag)::value) smax = *(const float*)(smem + smax_off);
-        __builtin_amdgcn_s_setprio(0);
-        float tmax[kF6NC];
-        bool any = false;
-#pragma unroll
-        for (int j = 0; j < kF6NC; ++j) {
-            tmax[j] = f6_max16(acc[j]);
-            any |= tmax[j] >= thr_s[j];
+        const unsigned long long p2 = __builtin_amdgcn_ballot_w64(f6_max16(acc[2]) >= thr_s[2]);
+        const unsigned long long p3 = __builtin_amdgcn_ballot_w64(f6_max16(acc[3]) >= thr_s[3]);
+        F6_MFMA_THEN_VALU(5); F6_MFMA_THEN_VALU(5); F6_MFMA_THEN_VALU(5); F6_MFMA_THEN_VALU(3);
+        if ((p2 | p3) != 0ull) {
+            test_block(b2, p2, punit, pxs);
+            test_block(b3, p3, punit, pxs);
         }
-        if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
-            // (both halves of the wave hold candidates of an output row: a row may be listed twice for a unit, which the
-            // rescoring's atomic minimum does not mind)
+        if constexpr (decltype(late_tag)::value) f6_screen2(thr_s[2], thr_s[3], thr[2], thr[3], smax);
 #pragma unroll
-            for (int j = 0; j < kF6NC; ++j) {
-                if (__builtin_amdgcn_ballot_w64(tmax[j] >= thr_s[j]) == 0ull) continue;
-                // the lane's 16 starts: rows (r & 3) + 8 (r >> 2) + 4 hs of the unit, four 16-byte reads (two addresses per
-                // wave: broadcasts)
-                float emax = kFp6PadInit;
+        for (int h = 0; h < 2; ++h)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const v4f_6 s = *(const v4f_6*)(smem + xs + 16 * hs + 32 * q);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) emax = fmaxf(emax, acc[j][4 * q + k] + s[k]);
-                }
-                const bool hit = emax >= thr[j];
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-                if (m == 0ull) continue;
-                const unsigned pc = (unsigned)__popcll(m);
-                if (nrec + pc > (unsigned)kF6HitSlots) flush();
-                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                // (LDS only: the hand-over's lgkmcnt(0) covers the write, which touches no stage buffer.  As a statement of
-                // its own: in front of a store to LDS the compiler waits for vmcnt(0), the LDS-DMA being a pending LDS write)
-                if (hit) {
-                    // (bit 31 of the unit word: which 16 of the unit's rows this lane's accumulators are)
-                    const unsigned long long r = ((unsigned long long)(unit | ((unsigned)hs << 31)) << 32) | (unsigned)(cb + 32 * j + r32);
-                    asm volatile("ds_write_b64 %0, %1" :: "v"(hits_lds + 8u * (nrec + rank)), "v"(r) : "memory");
-                }
-                nrec += pc;
-            }
+            for (int j = 2; j < 4; ++j)
+                acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(x.a[h], bf[j][h], h == 0 ? zero : acc[j], 2, 2, 0, 0, 0, 0);
+        if constexpr (decltype(yu_tag)::value >= 0) read_unit(y, ybuf, decltype(yu_tag)::value);
+        float sm = 0.f;
+        if constexpr (decltype(smax_tag)::value) sm = *(const float*)(smem + smax_off);
+        const unsigned long long p0 = __builtin_amdgcn_ballot_w64(f6_max16(acc[0]) >= thr_s[0]);
+        const unsigned long long p1 = __builtin_amdgcn_ballot_w64(f6_max16(acc[1]) >= thr_s[1]);
+        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x2, 5, 0);
+        F6_MFMA_THEN_VALU(5); F6_MFMA_THEN_VALU(5); F6_MFMA_THEN_VALU(3);
+        if ((p0 | p1) != 0ull) {
+            test_block(b0, p0, unit, xs);
+            test_block(b1, p1, unit, xs);
         }
         if constexpr (decltype(smax_tag)::value) {
-#pragma unroll
-            for (int j = 0; j < kF6NC; ++j) thr_s[j] = fp6_screen_threshold(thr[j], smax);
+            smax = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sm)));
+            f6_screen2(thr_s[0], thr_s[1], thr[0], thr[1], smax);
         }
     };
 
     // The two register sets: even and odd units of a stage.  The last unit of a stage is multiplied behind the NEXT hand-over,
     // so a wave enters the barrier with that unit's reads issued a unit earlier and leaves it with work in registers; in
-    // front of the first stage its place is taken by a unit of zero codes, screened against "never" (thr_s above).
+    // front of the first stage its place is taken by a unit of zero codes, screened against "never" (thr_s above), and the
+    // first test of all finds the accumulators' preset values, which "never" holds back as well.
     F6Unit ua, ub;
     ub.a[0] = ub.a[1] = v8i_6{0, 0, 0, 0, 0, 0, 0, 0};
     std::integral_constant<int, 0> u0;  std::integral_constant<int, 1> u1;  std::integral_constant<int, 2> u2;
     std::integral_constant<int, 3> u3;  std::integral_constant<int, -1> none;
-    std::true_type with_smax;  std::false_type no_smax;
+    std::true_type yes;  std::false_type no;
     auto stage = [&](auto buf_tag, int st) F6_INLINE {
         constexpr int BUF = decltype(buf_tag)::value;
         const char* buf = smem + BUF * kStageRowBytes;
         const unsigned unit0 = (unsigned)(st * kF6Units);
-        // the starts of this stage's units and of the unit carried in from the stage before
-        const int xs = kF6RingOff + (st & 3) * kStageAuxBytes, xs_prev = kF6RingOff + ((st - 1) & 3) * kStageAuxBytes + 3 * 128;
+        // the starts of this stage's units and of the stage before: its unit 2 is tested in the first half behind the
+        // hand-over, its unit 3, carried in, in the two halves after that -- the slot is intact until the next hand-over
+        const int xs = kF6RingOff + (st & 3) * kStageAuxBytes, xp = kF6RingOff + ((st - 1) & 3) * kStageAuxBytes;
         hand_over(buf_tag, st);
-        multiply(ub, unit0 - 1, xs_prev,  ua, buf, u0, with_smax, xs + 4 * kF6SmaxWord);
-        multiply(ua, unit0,     xs,       ub, buf, u1, no_smax, 0);
-        multiply(ub, unit0 + 1, xs + 128, ua, buf, u2, no_smax, 0);
-        multiply(ua, unit0 + 2, xs + 256, ub, buf, u3, no_smax, 0);
+        multiply(ub, unit0 - 1, xp + 384, unit0 - 2, xp + 256, ua, buf, u0, yes, no, xs + 4 * kF6SmaxWord);
+        multiply(ua, unit0,     xs,       unit0 - 1, xp + 384, ub, buf, u1, no, yes, 0);
+        multiply(ub, unit0 + 1, xs + 128, unit0,     xs,       ua, buf, u2, no, no, 0);
+        multiply(ua, unit0 + 2, xs + 256, unit0 + 1, xs + 128, ub, buf, u3, no, no, 0);
     };
 
     if (st0 >= st1) return;
@@ -406,7 +461,16 @@ void filter6_kernel(F6Batch b)
         if (st + 1 < st1) stage(std::integral_constant<int, 1>{}, st + 1);
         if (st + 2 < st1) stage(std::integral_constant<int, 2>{}, st + 2);
     }
-    multiply(ub, (unsigned)(st1 * kF6Units) - 1u, kF6RingOff + ((st1 - 1) & 3) * kStageAuxBytes + 3 * 128, ua, smem, none, no_smax, 0);
+    {
+        const unsigned last = (unsigned)(st1 * kF6Units) - 1u;
+        const int xl = kF6RingOff + ((st1 - 1) & 3) * kStageAuxBytes;
+        multiply(ub, last, xl + 384, last - 1u, xl + 256, ua, smem, none, no, no, 0);
+        // the drain: blocks 2, 3 of the last unit
+        const unsigned long long p2 = __builtin_amdgcn_ballot_w64(f6_max16(acc[2]) >= thr_s[2]);
+        const unsigned long long p3 = __builtin_amdgcn_ballot_w64(f6_max16(acc[3]) >= thr_s[3]);
+        test_block(b2, p2, last, xl + 384);
+        test_block(b3, p3, last, xl + 384);
+    }
     if (nrec != 0u) flush();
 }
 
