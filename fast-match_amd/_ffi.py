@@ -198,6 +198,14 @@ SYMBOLS = {
     "fm_hamming_match_accepted_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64)]),
     "fm_collection_hamming_match_accepted_each": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, _P]),
     "fm_collection_hamming_match_accepted_each_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P]),
+    "fm_wide_self_dist": (_INT, [_P, _P, _P]),
+    "fm_wide_self_dist_batch": (_INT, [_P, ctypes.c_int32, _P, _P]),
+    "fm_wide_set_selfdist": (_INT, [_P, _P, _P]),
+    "fm_wide_match_ratio": (_INT, [_P, _P, _P, ctypes.c_double, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_wide_match_accepted": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_wide_match_accepted_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_collection_wide_match_accepted_each": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, _P]),
+    "fm_collection_wide_match_accepted_each_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P]),
     # K13: knnMatch under a mask (csrc/masked.hip)
     "fm_mask_create": (_INT, [_P, _I64, _I64, ctypes.POINTER(_P)]),
     "fm_mask_create_coll": (_INT, [_P, _I64, _P, ctypes.POINTER(_P)]),
@@ -374,6 +382,10 @@ class Bank(object):
     def set_hamming_selfdist(self, selfdist):
         """``fm_hamming_set_selfdist``: attach Hamming self distances (float64 [n]) to a binary bank."""
         self.set_selfdist(selfdist, _name="fm_hamming_set_selfdist")
+
+    def set_wide_selfdist(self, selfdist):
+        """``fm_wide_set_selfdist``: attach self distances (float64 [n]) to a wide float bank (FM_BANK_F32W)."""
+        self.set_selfdist(selfdist, _name="fm_wide_set_selfdist")
 
     def refill_async(self, rows):
         """A new image's uint8 descriptors into this bank without allocation or host synchronisation
@@ -736,6 +748,16 @@ class Collection(object):
         """``match_accepted_each_dev`` on a binary collection (``fm_collection_hamming_match_accepted_each_dev``)."""
         return self.match_accepted_each_dev(q, tau, rows_ptr, counts_ptr, cap, h_counts, consumer_stream,
                                             _name="fm_collection_hamming_match_accepted_each_dev")
+
+    def wide_match_accepted_each(self, q, tau, cap=None):
+        """``fm_collection_wide_match_accepted_each``: ``match_accepted_each`` on a wide collection -- slot i equal to
+        ``Context.wide_match_accepted(q, bank(image_i), tau)``; ``q`` is a wide float bank with wide self distances."""
+        return self.match_accepted_each(q, tau, cap, _name="fm_collection_wide_match_accepted_each")
+
+    def wide_match_accepted_each_dev(self, q, tau, rows_ptr, counts_ptr, cap, h_counts=None, consumer_stream=None):
+        """``match_accepted_each_dev`` on a wide collection (``fm_collection_wide_match_accepted_each_dev``)."""
+        return self.match_accepted_each_dev(q, tau, rows_ptr, counts_ptr, cap, h_counts, consumer_stream,
+                                            _name="fm_collection_wide_match_accepted_each_dev")
 
     def match_accepted_each(self, q, tau, cap=None, _name="fm_collection_match_accepted_each"):
         """``fm_collection_match_accepted_each``: Fast-Match's accepted-match test of ``q`` (a bank with self distances) inside
@@ -1400,6 +1422,16 @@ class Context(object):
         attached to it on the device; banks of one K-step count (16 bytes of row width each) share a launch."""
         return self.self_dist_batch(banks, want_host, _name="fm_hamming_self_dist_batch")
 
+    def wide_self_dist(self, bank):
+        """``fm_wide_self_dist``: float64 [n], row i's distance (K14's exact float32 chain) to its nearest OTHER row of a wide
+        float bank; +inf for a bank of one row or a row that holds a NaN, 0 for a row with an exact duplicate."""
+        return self.self_dist(bank, _name="fm_wide_self_dist")
+
+    def wide_self_dist_batch(self, banks, want_host=True):
+        """``fm_wide_self_dist_batch``: ``self_dist_batch`` for wide float banks -- the self distances of every bank, attached
+        to it on the device; ``want_host=False`` only enqueues."""
+        return self.self_dist_batch(banks, want_host, _name="fm_wide_self_dist_batch")
+
     def self_dist_batch(self, banks, want_host=True, _name="fm_self_dist_batch"):
         """Metric_Cache builds of several images in one call (``fm_self_dist_batch``): the self distances of
         every bank, attached to it on the device; runs of integer banks (of any sizes, r05) share the
@@ -1449,6 +1481,18 @@ class Context(object):
     def hamming_match_accepted_dev(self, q, t, tau, rows_ptr, count_ptr, cap):
         """``match_accepted_dev`` on two binary banks (``fm_hamming_match_accepted_dev``)."""
         return self.match_accepted_dev(q, t, tau, rows_ptr, count_ptr, cap, _name="fm_hamming_match_accepted_dev")
+
+    def wide_match_ratio(self, q, t, tau, out=None):
+        """``match_ratio`` on two wide float banks (``fm_wide_match_ratio``): the query bank carries wide self distances."""
+        return self.match_ratio(q, t, tau, out, _name="fm_wide_match_ratio")
+
+    def wide_match_accepted(self, q, t, tau, out=None):
+        """``match_accepted`` on two wide float banks (``fm_wide_match_accepted``)."""
+        return self.match_accepted(q, t, tau, out, _name="fm_wide_match_accepted")
+
+    def wide_match_accepted_dev(self, q, t, tau, rows_ptr, count_ptr, cap):
+        """``match_accepted_dev`` on two wide float banks (``fm_wide_match_accepted_dev``)."""
+        return self.match_accepted_dev(q, t, tau, rows_ptr, count_ptr, cap, _name="fm_wide_match_accepted_dev")
 
     def match_ratio(self, q, t, tau, out=None, _name="fm_match_ratio"):
         """X1 + R1 fused.  ``out`` = optional (tidx i32[nq], dist f32[nq], ratio f64[nq],

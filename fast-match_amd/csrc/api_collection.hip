@@ -37,8 +37,8 @@ using namespace fm;
 // masks by INDEX: its sweep and its vector-ALU kernel take the per-stage real-row table (stage_real).
 // A fourth kind, wide (FM_BANK_F32W, fm_collection_add_wide: coll_add_wide below), masks by INDEX as well and serves the
 // match graph (fm_collection_pairs_mutual_ratio) and, under names of their own, a wide query bank image by image
-// (fm_collection_wide_mutual_ratio_each, fm_collection_wide_knn2_each: api_pairs.hip); every other call that takes a
-// query bank refuses it (coll_refuse_wide).  (kCollPadNorm, kCollPadF32, kCollF32Max: coll_internal.h.)
+// (fm_collection_wide_mutual_ratio_each, fm_collection_wide_knn2_each: api_pairs.hip; fm_collection_wide_match_accepted_each:
+// coll_elect_each's wide form below); every other call that takes a query bank refuses it (coll_refuse_wide).  (kCollPadNorm, kCollPadF32, kCollF32Max: coll_internal.h.)
 static uint64_t coll_next_gen()
 {
     static std::atomic<uint64_t> g{0};
@@ -758,7 +758,8 @@ static int coll_refuse_wide(fm_ctx* ctx, const fm_collection* c, const char* who
     if (!coll_is_wide(c)) return FM_OK;
     return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": a wide collection (fm_collection_add_wide, FM_BANK_F32W) is served by "
                                       "fm_collection_pairs_mutual_ratio(_dev) and, for a wide query bank, by "
-                                      "fm_collection_wide_mutual_ratio_each(_dev) / fm_collection_wide_knn2_each only");
+                                      "fm_collection_wide_mutual_ratio_each(_dev) / fm_collection_wide_knn2_each / "
+                                      "fm_collection_wide_match_accepted_each(_dev) only");
 }
 
 extern "C" int fm_collection_train(fm_ctx* ctx, fm_collection* c)
@@ -1615,6 +1616,156 @@ static fm::Bank coll_chunk_view(const fm_collection* c, int64_t i0, int64_t i1)
     return v;
 }
 
+// ---- wide collections: a chunk's reverse top-1 sweeps through the table kernels (wide_f32.hip, part 5, KTOP = 1) -----------
+// fm_collection_wide_match_accepted_each.  The images of a chunk are swept in GROUPS of consecutive images: the non-empty
+// images of a group are the slots of ONE table -- reverse slots alone: output rows = the image's rows (a view of the stack),
+// reduced rows = the query bank, the operand outside the stack -- side by side in the group's output-row space, swept by one
+// filter launch, one rescoring launch and one guarded exact launch (or the exact launch alone; wide_route's rule on the
+// group's work), then ONE segmented election: every image row's key (float32 distance bits << 32 | query row) scatter-mins
+// (distance bits << 32 | row inside the image) into qbest[image][query row] -- xcheck_scatter_kernel's election, image by
+// image, so the table is fm_wide_match_accepted(q, bank(image))'s.  A group ends with the chunk, or before the image that
+// would lift its real rows past kWideEachGroupRows: the group's record list holds 256 records per output row (at least 2^20),
+// and that bounds it at 2^26 records (768 MiB of the context's workspace) whatever "coll_ws_bytes" lets a chunk hold.
+constexpr int64_t kWideEachGroupRows = (int64_t)1 << 18;
+
+struct WideEachGroup {
+    int64_t i0 = 0, i1 = 0;                 // the images
+    int nslots = 0, fwg = 0;                // non-empty images, the filter's grid
+    int64_t rows = 0, real = 0;             // the output-row space (a multiple of 128), real rows
+    bool filt = false; unsigned cap = 0;    // the route, the record list's size
+    size_t o_slots = 0, o_wg0 = 0, o_rowp = 0, o_img = 0;       // WideSlot [n] | first workgroups [n + 1] | first rows [n + 1] | image - the chunk's first [n]
+};
+struct WideEachPlan {
+    std::vector<WideEachGroup> groups;
+    std::vector<char> tab;                  // the call's table image
+    size_t w_cnt = 0, w_bound = 0, w_list = 0, w_score = 0;     // ws_partial: partial [rows] | count | bounds [rows] | records | their scores
+};
+
+__global__ __launch_bounds__(256)
+void coll_wide_elect_kernel(const unsigned long long* __restrict__ partial, const WideSlot* __restrict__ slots, const int* __restrict__ rowp,
+                            const int* __restrict__ img, int nslots, int rows, int64_t nq, unsigned long long* __restrict__ qbest)
+{
+    const int r = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (r >= rows) return;
+    const unsigned long long key = partial[r];
+    if (key == ~0ull) return;
+    const int s = table_slot_of(rowp, nslots, r);
+    const int local = r - rowp[s];
+    if (local >= slots[s].ncols) return;                   // a padding row behind the image
+    atomicMin(&qbest[(int64_t)img[s] * nq + (unsigned)key], (key & 0xffffffff00000000ull) | (unsigned long long)(unsigned)local);
+}
+
+// The groups of every chunk of nc images, their tables (uploaded once, into ws_in) and ws_partial for the largest group: all
+// before anything is enqueued.
+static int coll_wide_each_plan(fm_ctx* ctx, const fm_collection* c, const fm_bank* q, int64_t nc, const char* who, WideEachPlan* pl)
+{
+    const int64_t ni = (int64_t)c->rows.size(), nq = q->n;
+    const fm::Bank& stack = c->stack;
+    const bool filter_on = ctx->tune.f32_filter != 0 && ctx->d_counters && stack.filt_ok && stack.wrowsh && wide_filter_usable(*q, stack);
+    const int dk = q->kscale - stack.kscale;                // kred - kcol: the reduced side is the query bank (launch_wide_filter's terms)
+    int64_t max_rows = 0;
+    size_t max_cap = 0;
+    try {
+        auto put = [&](const void* src, size_t bytes) {
+            const size_t at = pl->tab.size();
+            pl->tab.resize(at + align256(bytes));
+            memcpy(pl->tab.data() + at, src, bytes);
+            return at;
+        };
+        for (int64_t c0 = 0; c0 < ni; c0 += nc) {
+            const int64_t c1 = std::min(ni, c0 + nc);
+            for (int64_t i = c0; i < c1;) {
+                WideEachGroup g;
+                g.i0 = i;
+                while (i < c1 && (g.real == 0 || g.real + c->rows[(size_t)i] <= kWideEachGroupRows)) {
+                    const int64_t n = c->rows[(size_t)i++];
+                    if (n > 0) { g.real += n; g.rows += pad128(n); ++g.nslots; }
+                }
+                g.i1 = i;
+                if (g.rows > ((int64_t)1 << 30)) return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": one image of a wide collection has more than 2^30 rows");
+                if (g.nslots > 0) {
+                    // a group whose slots fill the chip without splits takes one split per slot (the match graph's rule)
+                    const bool one_split = g.rows / kStageRows >= 512 && ctx->tune.f32_nsplit == 0;
+                    std::vector<WideSlot> sl;
+                    std::vector<int> wg0, rowp, img;
+                    int wrow = 0, wg = 0;
+                    for (int64_t j = g.i0; j < g.i1; ++j) {
+                        const int64_t n = c->rows[(size_t)j];
+                        if (n == 0) continue;
+                        WideSlot w{};
+                        w.col0 = (int)c->phys[(size_t)j]; w.ncols = (int)n;
+                        w.red0 = 0; w.nred = (int)nq;
+                        w.outside = kWideOutRed;
+                        w.cscale = ldexpf(1.f, dk); w.nscale = ldexpf(1.f, 2 * dk); w.red_nm_max = q->nm_max;
+                        const WideFilterPlan fp = plan_wide_filter(pad128(n), n, pad128(nq), ctx->tune);
+                        w.ntiles = fp.ntiles;
+                        w.nsplit = one_split ? 1 : fp.nsplit;
+                        w.tiles_per_split = one_split ? fp.ntiles : fp.tiles_per_split;
+                        w.row0 = wrow;
+                        sl.push_back(w); wg0.push_back(wg); rowp.push_back(wrow); img.push_back((int)(j - c0));
+                        wg += fp.nchunks * w.nsplit;
+                        wrow += (int)pad128(n);
+                    }
+                    wg0.push_back(wg); rowp.push_back(wrow);
+                    g.fwg = wg;
+                    g.filt = filter_on && (ctx->tune.f32_filter >= 2 || (double)nq * (double)g.real >= 4.0e6);
+                    if (g.filt) g.cap = (unsigned)std::min<int64_t>(std::max<int64_t>(256 * g.real, 1 << 20), (int64_t)1 << 26);
+                    g.o_slots = put(sl.data(), sl.size() * sizeof(WideSlot));
+                    g.o_wg0 = put(wg0.data(), wg0.size() * 4);
+                    g.o_rowp = put(rowp.data(), rowp.size() * 4);
+                    g.o_img = put(img.data(), img.size() * 4);
+                    max_rows = std::max(max_rows, g.rows);
+                    max_cap = std::max<size_t>(max_cap, g.cap);
+                }
+                pl->groups.push_back(g);
+            }
+        }
+    } catch (const std::bad_alloc&) { return fail(ctx, FM_ENOMEM, std::string(who) + ": out of host memory"); }
+    if (max_rows == 0) return FM_OK;
+    int rc;
+    pl->w_cnt = align256((size_t)max_rows * 8); pl->w_bound = pl->w_cnt + 256; pl->w_list = pl->w_bound + align256((size_t)max_rows * 4);
+    pl->w_score = pl->w_list + align256(max_cap * 8);
+    if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, pl->w_score + align256(max_cap * 4) + 64)) != FM_OK) return rc;
+    const size_t tab_bytes = pl->tab.size();
+    if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, tab_bytes + 64)) != FM_OK) return rc;
+    if ((rc = table_host(ctx, tab_bytes)) != FM_OK) return rc;
+    memcpy(ctx->h_tab, pl->tab.data(), tab_bytes);
+    return table_upload(ctx, ctx->ws_in, tab_bytes);
+}
+
+// The groups of the chunk [i0, i1) into d_qbest [image - i0][query row] (preset to ~0).
+static int coll_wide_qbest_groups(fm_ctx* ctx, const fm_collection* c, const fm_bank* q, const WideEachPlan& pl, int64_t i0, int64_t i1,
+                                  unsigned long long* d_qbest, bool* timed)
+{
+    const int64_t nq = q->n;
+    char* wp = (char*)ctx->ws_partial;
+    const char* d = (const char*)ctx->ws_in;
+    for (const WideEachGroup& g : pl.groups) {
+        if (g.i0 < i0 || g.i1 > i1 || g.nslots == 0) continue;
+        ctx->pending_pairs += nq * g.real;
+        ctx->pending_bytes += (nq + g.real) * 1024;
+        if (!*timed) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+        *timed = true;
+        const WideTableLaunch tl{(const WideSlot*)(d + g.o_slots), (const int*)(d + g.o_wg0), (const int*)(d + g.o_rowp), g.nslots, g.fwg, g.rows, q};
+        unsigned long long* part = (unsigned long long*)wp;
+        if (g.filt) {
+            HIP_TRY(ctx, hipMemsetAsync(part, 0xff, (size_t)g.rows * 8, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(wp + pl.w_cnt, 0, 256 + (size_t)g.rows * 4, ctx->stream));      // (the count and the bounds are neighbours)
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, 8, ctx->stream));
+            HIP_TRY(ctx, launch_wide_filter_table(c->stack, tl, g.cap, (uint2*)(wp + pl.w_list), (float*)(wp + pl.w_score), (unsigned*)(wp + pl.w_bound),
+                                                  (unsigned long long*)(wp + pl.w_cnt), ctx->d_counters, part, ctx->stream, 1));
+            HIP_TRY(ctx, launch_wide_exact_table(c->stack, tl, part, ctx->d_counters, ctx->stream, 1));
+            ctx->filter_launches += 1;
+        } else {
+            HIP_TRY(ctx, launch_wide_exact_table(c->stack, tl, part, nullptr, ctx->stream, 1));
+        }
+        hipLaunchKernelGGL(coll_wide_elect_kernel, dim3((unsigned)((g.rows + 255) / 256)), dim3(256), 0, ctx->stream, (const unsigned long long*)part,
+                           tl.d_slots, tl.d_rowp, (const int*)(d + g.o_img), g.nslots, (int)g.rows, nq, d_qbest);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return FM_OK;
+}
+
 // The front half for the images [i0, i1): d_qbest[image - i0][query row] = (float32 distance bits << 32 | row inside the
 // image) of the closest row of the image that elects the query row, ~0 where none does -- slot by slot the table of
 // fm_xcheck1(q, bank(image)).  Integer and binary routes: one reverse top-1 sweep over the chunk's stack view and the
@@ -1622,11 +1773,12 @@ static fm::Bank coll_chunk_view(const fm_collection* c, int64_t i0, int64_t i1)
 // fm_xcheck1's own election.  cut: launch_rowreduce's (integer route) or null.  *timed: a sweep was enqueued; on the
 // integer and binary routes ev_k0 is recorded in front of the first one and ev_k1 is the caller's.
 static int coll_qbest_chunk(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int64_t i0, int64_t i1, const unsigned* cut,
-                            unsigned long long* d_qbest, bool* timed)
+                            unsigned long long* d_qbest, bool* timed, const WideEachPlan* wide = nullptr)
 {
     const int64_t nq = q->n;
     int rc;
     HIP_TRY(ctx, hipMemsetAsync(d_qbest, 0xff, (size_t)(i1 - i0) * nq * 8, ctx->stream));
+    if (c->stack.kind == FM_BANK_F32W) return coll_wide_qbest_groups(ctx, c, q, *wide, i0, i1, d_qbest, timed);
     if (c->stack.kind == FM_BANK_F32) {
         for (int64_t i = i0; i < i1; ++i) {
             const fm::Bank v = coll_view(c, (int)i);
@@ -1703,6 +1855,9 @@ struct CollEachArgs {
     // the Hamming form of the accepted-match test (fm_collection_hamming_match_accepted_each(_dev)): a binary collection and a
     // binary query bank with Hamming self distances; l2 = the L2 call its refusals name.  Else binary data is refused.
     bool hamming = false; const char* l2 = nullptr;
+    // the wide form (fm_collection_wide_match_accepted_each(_dev)): a wide collection and a wide query bank with wide self
+    // distances; l2 / ham = the calls its refusals name
+    bool wide = false; const char* ham = nullptr;
 };
 
 static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const CollEachArgs& a)
@@ -1719,14 +1874,25 @@ static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, cons
             return fail(ctx, FM_EINVAL, who + ": the collection and the query bank must be binary (fm_collection_add_bin, fm_bank_create_bin); " +
                                             a.l2 + " is the L2 call");
     }
-    if ((rc = coll_query_check(ctx, c, q, a.who, !a.accept)) != FM_OK) return rc;
+    if (a.wide) {
+        // (the header's order: handles, the kinds, the widths; coll_query_check refuses wide data and is not asked)
+        if ((rc = coll_check(ctx, c, a.who)) != FM_OK) return rc;
+        if (!q) return fail(ctx, FM_EINVAL, who + ": query bank is NULL");
+        const bool cbin = c->dim != 0 && c->stack.kind == FM_BANK_BIN && !coll_is_wide(c);
+        if (q->kind != FM_BANK_F32W || (!c->rows.empty() && !coll_is_wide(c)))
+            return fail(ctx, FM_EINVAL, who + ": the collection and the query bank must be wide float (fm_collection_add_wide; FM_BANK_F32W: "
+                                              "fm_bank_create_f32 with 129 .. 256 values per row); " +
+                                              ((q->kind == FM_BANK_BIN || cbin) ? std::string(a.ham) + " is the Hamming call" : std::string(a.l2) + " is the L2 call"));
+        if (c->dim != 0 && q->dim != c->dim) return fail(ctx, FM_EINVAL, who + ": the query's width differs from the collection's");
+    } else if ((rc = coll_query_check(ctx, c, q, a.who, !a.accept)) != FM_OK) return rc;
     if (a.accept && !a.hamming && q->kind == FM_BANK_BIN)
         return fail(ctx, FM_EUNSUPPORTED, who + ": binary banks carry no self distances here: fm_collection_hamming_match_accepted_each(_dev) "
                                                 "is the self-distance test of a binary collection");
     const int64_t nq = q->n, ni = (int64_t)c->rows.size(), cap = a.cap;
     if (a.accept && nq > 0 && !q->selfdist)
         return fail(ctx, FM_EINVAL, who + ": query bank has no self distances (" +
-                                        (a.hamming ? "fm_hamming_set_selfdist, fm_hamming_self_dist_batch" : "fm_bank_set_selfdist") + ")");
+                                        (a.hamming ? "fm_hamming_set_selfdist, fm_hamming_self_dist_batch" :
+                                         a.wide ? "fm_wide_set_selfdist, fm_wide_self_dist_batch" : "fm_bank_set_selfdist") + ")");
     if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap < 0");
     if (ni == 0) return FM_OK;
     if (a.to_dev) {
@@ -1768,9 +1934,12 @@ static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, cons
     char* b = (char*)ctx->ws_out;
     unsigned long long* d_full = (unsigned long long*)(b + o_full);
     unsigned long long* d_qbest = (unsigned long long*)(b + o_qbest);
-    const bool stacked = c->stack.kind != FM_BANK_F32;      // one sweep per chunk
+    const bool wide = c->stack.kind == FM_BANK_F32W;
+    const bool stacked = c->stack.kind != FM_BANK_F32;      // one sweep per chunk (a wide collection: per group of images, through the table kernels)
     // the sweep workspace is sized for the largest chunk before anything is enqueued (no reallocation between chunks)
-    if (stacked && c->total > 0) {
+    WideEachPlan wplan;
+    if (wide && (rc = coll_wide_each_plan(ctx, c, q, nc, a.who, &wplan)) != FM_OK) return rc;
+    if (stacked && !wide && c->total > 0) {
         for (int64_t i0 = 0; i0 < ni; i0 += nc) {
             const fm::Bank v = coll_chunk_view(c, i0, std::min(ni, i0 + nc));
             PairSweep ps;
@@ -1784,7 +1953,7 @@ static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, cons
     bool timed = false;
     for (int64_t i0 = 0; i0 < ni; i0 += nc) {
         const int64_t i1 = std::min(ni, i0 + nc), g = i1 - i0;
-        if ((rc = coll_qbest_chunk(ctx, c, q, i0, i1, cut, d_qbest, &timed)) != FM_OK) return rc;
+        if ((rc = coll_qbest_chunk(ctx, c, q, i0, i1, cut, d_qbest, &timed, &wplan)) != FM_OK) return rc;
         hipLaunchKernelGGL(coll_each_finalize_kernel, dim3((unsigned)nblk, (unsigned)g), dim3(256), 0, ctx->stream,
                            (const unsigned long long*)d_qbest, nq, keep, (int32_t*)(b + o_tidx), (float*)(b + o_dist),
                            a.accept ? (double*)(b + o_ratio) : (double*)nullptr, (uint8_t*)(b + o_pass), (int*)(b + o_bc));
@@ -1863,6 +2032,27 @@ extern "C" int fm_collection_hamming_match_accepted_each_dev(fm_ctx* ctx, fm_col
 {
     const CollEachArgs a{"fm_collection_hamming_match_accepted_each_dev", true, tau, 0.f, cap, nullptr, nullptr, nullptr, nullptr, nullptr,
                          true, d_rows, d_counts, h_counts, consumer_stream, true, "fm_collection_match_accepted_each_dev"};
+    return coll_elect_each(ctx, c, q, a);
+}
+
+// The same two calls on a wide collection and a wide query bank that carries wide self distances (the header's "Wide
+// Fast-Match"): coll_qbest_chunk's wide route -- groups of images through the top-1 table kernels, the segmented election --
+// and the tail above.
+extern "C" int fm_collection_wide_match_accepted_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap,
+                                                      int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+{
+    CollEachArgs a{"fm_collection_wide_match_accepted_each", true, tau, 0.f, cap, qidx, tidx, dist, ratio, n_accepted,
+                   false, nullptr, nullptr, nullptr, FM_NO_STREAM, false, "fm_collection_match_accepted_each"};
+    a.wide = true; a.ham = "fm_collection_hamming_match_accepted_each";
+    return coll_elect_each(ctx, c, q, a);
+}
+
+extern "C" int fm_collection_wide_match_accepted_each_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap,
+                                                          int32_t* d_rows, int64_t* d_counts, int64_t* h_counts, void* consumer_stream)
+{
+    CollEachArgs a{"fm_collection_wide_match_accepted_each_dev", true, tau, 0.f, cap, nullptr, nullptr, nullptr, nullptr, nullptr,
+                   true, d_rows, d_counts, h_counts, consumer_stream, false, "fm_collection_match_accepted_each_dev"};
+    a.wide = true; a.ham = "fm_collection_hamming_match_accepted_each_dev";
     return coll_elect_each(ctx, c, q, a);
 }
 

@@ -1620,6 +1620,28 @@ extern "C" int fm_bank_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* se
     return FM_OK;
 }
 
+int fm::table_host(fm_ctx* ctx, size_t bytes)
+{
+    if (ctx->tab_in_flight) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_tab)); ctx->tab_in_flight = false; }
+    if (!ctx->ev_tab) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming));
+    if (bytes > ctx->h_tab_bytes) {
+        if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
+        ctx->h_tab = nullptr; ctx->h_tab_bytes = 0;
+        const size_t want = bytes + bytes / 4 + 4096;
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_tab, want, hipHostMallocDefault));
+        ctx->h_tab_bytes = want;
+    }
+    return FM_OK;
+}
+
+int fm::table_upload(fm_ctx* ctx, void* dst, size_t bytes)
+{
+    HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->h_tab, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_tab, ctx->stream));
+    ctx->tab_in_flight = true;
+    return FM_OK;
+}
+
 int fm::bank_selfdist_alloc(fm_ctx* ctx, fm_bank* b)
 {
     if (b->selfdist) return FM_OK;
@@ -1634,7 +1656,8 @@ int fm::refuse_wide(fm_ctx* ctx, const fm_bank* b, const char* who)
 {
     if (!b || b->kind != FM_BANK_F32W) return FM_OK;
     return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": wide float banks (FM_BANK_F32W, 129 .. 256 values per row) are served by fm_knn2, "
-                                          "fm_knn with k <= 2, fm_xcheck1, fm_knn2_ratio, fm_mutual_ratio and their _dev forms only");
+                                          "fm_knn with k <= 2, fm_xcheck1, fm_knn2_ratio, fm_mutual_ratio, their _dev forms and the Wide Fast-Match calls (fm_wide_self_dist, "
+                                          "fm_wide_set_selfdist, fm_wide_match_ratio, fm_wide_match_accepted) only");
 }
 
 int fm::refuse_bin(fm_ctx* ctx, const fm_bank* b, const char* who)

@@ -527,8 +527,9 @@ int rowreduce_f32_route(fm_ctx* ctx, const fm_bank* cols, const fm_bank* red, in
 
 // Wide float banks (K14, wide_f32.hip), the same way: the exact kernel alone, or the fp16 filter with the exact kernel as its
 // conditional fallback (a record list that overflowed); "f32_filter" decides as above.  ws_partial: partial | records | their
-// scores | per-row bounds | count.
-static int wide_route(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, RowReducePlan* pl_out)
+// scores | per-row bounds | count.  self (cols and red are one bank, ktop 1): the SELF forms of the three kernels, which drop
+// the diagonal by index -- fm_wide_self_dist's sweep.
+static int wide_route(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, RowReducePlan* pl_out, bool self = false)
 {
     const RowReducePlan pl = plan_rowreduce_f32(cols.n_pad, red.n_pad, ctx->tune.nsplit);
     *pl_out = pl;
@@ -540,7 +541,7 @@ static int wide_route(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, 
         if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, pl.partial_bytes(ktop) + 64)) != FM_OK) return rc;
         d_part = (unsigned long long*)ctx->ws_partial;
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-        HIP_TRY(ctx, launch_wide_exact(cols, red, ktop, pl, d_part, nullptr, ctx->stream));
+        HIP_TRY(ctx, launch_wide_exact(cols, red, ktop, pl, d_part, nullptr, ctx->stream, self));
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
         return FM_OK;
     }
@@ -557,8 +558,8 @@ static int wide_route(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, 
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, 8, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
     HIP_TRY(ctx, launch_wide_filter(cols, red, ktop, fp, (uint2*)((char*)ctx->ws_partial + o_list), (float*)((char*)ctx->ws_partial + o_score),
-                                    (unsigned*)((char*)ctx->ws_partial + o_bound), d_cnt, ctx->d_counters, d_part, ctx->stream));
-    HIP_TRY(ctx, launch_wide_exact(cols, red, ktop, pl, d_part, ctx->d_counters, ctx->stream));
+                                    (unsigned*)((char*)ctx->ws_partial + o_bound), d_cnt, ctx->d_counters, d_part, ctx->stream, self));
+    HIP_TRY(ctx, launch_wide_exact(cols, red, ktop, pl, d_part, ctx->d_counters, ctx->stream, self));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
     ctx->filter_launches += 1;
     return FM_OK;
@@ -1294,15 +1295,7 @@ static int ham_selfdist_device(fm_ctx* ctx, int n, const fm_bank* const* banks, 
     const size_t tab_bytes = (size_t)total_wg * 16;
     int rc;
     if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, max_part + tab_bytes + 64)) != FM_OK) return rc;
-    if (ctx->tab_in_flight) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_tab)); ctx->tab_in_flight = false; }
-    if (!ctx->ev_tab) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming));
-    if (tab_bytes > ctx->h_tab_bytes) {
-        if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
-        ctx->h_tab = nullptr; ctx->h_tab_bytes = 0;
-        const size_t want = tab_bytes + tab_bytes / 4 + 4096;
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_tab, want, hipHostMallocDefault));
-        ctx->h_tab_bytes = want;
-    }
+    if ((rc = table_host(ctx, tab_bytes)) != FM_OK) return rc;
     int* tab = (int*)ctx->h_tab;
     char* d_tab = (char*)ctx->ws_partial + max_part;
     for (const Group& g : groups) {
@@ -1314,9 +1307,7 @@ static int ham_selfdist_device(fm_ctx* ctx, int n, const fm_bank* const* banks, 
                 for (int c = 0; c < p.nchunks; ++c) { e[0] = j; e[1] = c; e[2] = s; e[3] = 0; e += 4; }
         }
     }
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_tab, ctx->stream));
-    ctx->tab_in_flight = true;
+    if ((rc = table_upload(ctx, d_tab, tab_bytes)) != FM_OK) return rc;
     for (const Group& g : groups) {
         HamSelfArgs a{};
         size_t at = 0;
@@ -1342,42 +1333,90 @@ static int ham_selfdist_device(fm_ctx* ctx, int n, const fm_bank* const* banks, 
     return FM_OK;
 }
 
-// The checks of the Hamming self-distance calls: handles, then a binary bank (l2: the L2 call the message names)
-static int ham_bank_check(fm_ctx* ctx, const fm_bank* b, const char* who, const char* l2)
+// ---------------------------------------------------------------------------------------
+// Wide self distances (wide_f32.hip: the SELF forms of the filter, the rescoring and the exact kernel)
+// ---------------------------------------------------------------------------------------
+// Self distances of n wide banks on the context's stream, each into d_out[i] (device, [banks[i]->n] float64): one sweep of
+// the bank over itself per bank (wide_route, self), back to back -- separate banks share no stack, so the table forms do not
+// apply -- and fm_self_dist's merge over the splits (float32-bit keys; no key: +inf).  Enqueue only.
+static int wide_selfdist_device(fm_ctx* ctx, int n, const fm_bank* const* banks, double* const* d_out, bool timed)
 {
-    if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
-    if (!b) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
-    if (b->kind != FM_BANK_BIN)
-        return fail(ctx, FM_EINVAL, std::string(who) + ": the bank must be binary (FM_BANK_BIN, fm_bank_create_bin); " + l2 + " is the L2 call");
+    for (int i = 0; i < n; ++i) {
+        const fm_bank* b = banks[i];
+        if (b->n == 0) continue;
+        RowReducePlan pl;
+        int rc = wide_route(ctx, *b, *b, 1, &pl, true);
+        if (rc != FM_OK) return rc;
+        ctx->kernel_timed = timed;
+        ctx->pending_pairs += b->n * b->n;
+        ctx->pending_bytes += bank_bytes(b);
+        SelfMerge m{};
+        m.partial[0] = (const unsigned long long*)ctx->ws_partial;
+        m.out[0] = d_out[i];
+        hipLaunchKernelGGL(selfdist_merge_kernel, dim3((unsigned)((b->n + 255) / 256), 1), dim3(256), 0, ctx->stream,
+                           m, pl.nsplit, pl.ncols_alloc, b->n, 1);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     return FM_OK;
 }
 
-extern "C" int fm_hamming_self_dist(fm_ctx* ctx, const fm_bank* bank, double* selfdist)
+// The two families of calls under names of their own -- fm_hamming_* on binary banks, fm_wide_* on wide float banks: the kind
+// they serve, how a refusal describes it, the family's self-distance sweep and the calls that attach self distances.
+struct NamedFamily {
+    int kind; const char* one; const char* both;
+    int (*selfdist)(fm_ctx*, int, const fm_bank* const*, double* const*, bool);
+    const char* attach;
+};
+static const NamedFamily kHamFamily{FM_BANK_BIN, "the bank must be binary (FM_BANK_BIN, fm_bank_create_bin)",
+                                    "both banks must be binary (FM_BANK_BIN, fm_bank_create_bin)", ham_selfdist_device,
+                                    "fm_hamming_set_selfdist, fm_hamming_self_dist_batch"};
+static const NamedFamily kWideFamily{FM_BANK_F32W, "the bank must be wide float (FM_BANK_F32W: fm_bank_create_f32 with 129 .. 256 values per row)",
+                                     "both banks must be wide float (FM_BANK_F32W: fm_bank_create_f32 with 129 .. 256 values per row)",
+                                     wide_selfdist_device, "fm_wide_set_selfdist, fm_wide_self_dist_batch"};
+
+// "<l2> is the L2 call", or for the wide family's refusal of a binary bank "<ham> is the Hamming call"
+static std::string named_served_by(const fm_bank* b, const char* l2, const char* ham)
 {
-    int rc = ham_bank_check(ctx, bank, "fm_hamming_self_dist", "fm_self_dist");
+    if (ham && b->kind == FM_BANK_BIN) return std::string(ham) + " is the Hamming call";
+    return std::string(l2) + " is the L2 call";
+}
+
+// The checks of a family's self-distance calls: handles, then a bank of the family's kind (l2 / ham: the calls the message names)
+static int named_bank_check(fm_ctx* ctx, const fm_bank* b, const NamedFamily& f, const char* who, const char* l2, const char* ham = nullptr)
+{
+    if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
+    if (!b) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
+    if (b->kind != f.kind) return fail(ctx, FM_EINVAL, std::string(who) + ": " + f.one + "; " + named_served_by(b, l2, ham));
+    return FM_OK;
+}
+
+static int named_self_dist(fm_ctx* ctx, const fm_bank* bank, double* selfdist, const NamedFamily& f, const char* who, const char* l2, const char* ham = nullptr)
+{
+    int rc = named_bank_check(ctx, bank, f, who, l2, ham);
     if (rc != FM_OK) return rc;
     const int64_t n = bank->n;
     if (n == 0) return FM_OK;
-    if (!selfdist) return fail(ctx, FM_EINVAL, "fm_hamming_self_dist: output pointer is NULL");
+    if (!selfdist) return fail(ctx, FM_EINVAL, std::string(who) + ": output pointer is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, (size_t)n * 8 + 64)) != FM_OK) return rc;
     double* d_sd = (double*)ctx->ws_in;
     CallScope cs(ctx);
-    if ((rc = ham_selfdist_device(ctx, 1, &bank, &d_sd, true)) != FM_OK) return rc;
+    if ((rc = f.selfdist(ctx, 1, &bank, &d_sd, true)) != FM_OK) return rc;
     HIP_TRY(ctx, d2h(ctx, selfdist, d_sd, (size_t)n * 8));
     return cs.finish();
 }
 
-extern "C" int fm_hamming_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks, double* const* out)
+static int named_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks, double* const* out, const NamedFamily& f, const char* who_,
+                                 const char* l2, const char* ham = nullptr)
 {
-    const char* who = "fm_hamming_self_dist_batch";
-    if (!ctx) return fail(nullptr, FM_EINVAL, "fm_hamming_self_dist_batch: ctx is NULL");
-    if (n < 0) return fail(ctx, FM_EINVAL, "fm_hamming_self_dist_batch: n < 0");
+    const std::string who(who_);
+    if (!ctx) return fail(nullptr, FM_EINVAL, who + ": ctx is NULL");
+    if (n < 0) return fail(ctx, FM_EINVAL, who + ": n < 0");
     if (n == 0) return FM_OK;
-    if (!banks) return fail(ctx, FM_EINVAL, "fm_hamming_self_dist_batch: banks is NULL");
+    if (!banks) return fail(ctx, FM_EINVAL, who + ": banks is NULL");
     for (int i = 0; i < n; ++i) {
-        if (int rc = ham_bank_check(ctx, banks[i], who, "fm_self_dist_batch")) return rc;
-        for (int j = 0; j < i; ++j) if (banks[j] == banks[i]) return fail(ctx, FM_EINVAL, "fm_hamming_self_dist_batch: a bank is listed twice");
+        if (int rc = named_bank_check(ctx, banks[i], f, who_, l2, ham)) return rc;
+        for (int j = 0; j < i; ++j) if (banks[j] == banks[i]) return fail(ctx, FM_EINVAL, who + ": a bank is listed twice");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<double*> d_out((size_t)n, nullptr);
@@ -1387,7 +1426,7 @@ extern "C" int fm_hamming_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const
     for (int i = 0; i < n; ++i) {
         fm_bank* b = banks[i];
         if ((rc = bank_selfdist_alloc(ctx, b)) != FM_OK) return rc;
-        b->sdmax_rows = -1;           // (no ratio cut is built on Hamming self distances)
+        b->sdmax_rows = -1;           // (no ratio cut is built on these self distances)
         d_out[(size_t)i] = b->selfdist;
         cb[(size_t)i] = b;
         any_out = any_out || (out && out[i] && b->n > 0);
@@ -1400,7 +1439,7 @@ extern "C" int fm_hamming_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const
         ctx->pending_pairs = 0;
         ctx->pending_bytes = 0;
         HIP_TRY(ctx, hipEventRecord(tm.k0, ctx->stream));
-        rc = ham_selfdist_device(ctx, n, cb.data(), d_out.data(), false);
+        rc = f.selfdist(ctx, n, cb.data(), d_out.data(), false);
         HIP_TRY(ctx, hipEventRecord(tm.k1, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(tm.c1, ctx->stream));
         tm.timed = rc == FM_OK && ctx->pending_pairs > 0;
@@ -1413,17 +1452,18 @@ extern "C" int fm_hamming_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const
         return rc;
     }
     CallScope cs(ctx);
-    if ((rc = ham_selfdist_device(ctx, n, cb.data(), d_out.data(), true)) != FM_OK) return rc;
+    if ((rc = f.selfdist(ctx, n, cb.data(), d_out.data(), true)) != FM_OK) return rc;
     for (int i = 0; i < n; ++i)
         if (out[i] && banks[i]->n > 0) HIP_TRY(ctx, d2h(ctx, out[i], d_out[(size_t)i], (size_t)banks[i]->n * 8));
     return cs.finish();
 }
 
-extern "C" int fm_hamming_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* selfdist)
+static int named_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* selfdist, const NamedFamily& f, const char* who, const char* l2,
+                              const char* ham = nullptr)
 {
-    int rc = ham_bank_check(ctx, bank, "fm_hamming_set_selfdist", "fm_bank_set_selfdist");
+    int rc = named_bank_check(ctx, bank, f, who, l2, ham);
     if (rc != FM_OK) return rc;
-    if (bank->n > 0 && !selfdist) return fail(ctx, FM_EINVAL, "fm_hamming_set_selfdist: selfdist is NULL");
+    if (bank->n > 0 && !selfdist) return fail(ctx, FM_EINVAL, std::string(who) + ": selfdist is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = bank_selfdist_alloc(ctx, bank)) != FM_OK) return rc;
     bank->sdmax_rows = -1;
@@ -1432,6 +1472,36 @@ extern "C" int fm_hamming_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double*
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return FM_OK;
+}
+
+extern "C" int fm_hamming_self_dist(fm_ctx* ctx, const fm_bank* bank, double* selfdist)
+{
+    return named_self_dist(ctx, bank, selfdist, kHamFamily, "fm_hamming_self_dist", "fm_self_dist");
+}
+
+extern "C" int fm_hamming_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks, double* const* out)
+{
+    return named_self_dist_batch(ctx, n, banks, out, kHamFamily, "fm_hamming_self_dist_batch", "fm_self_dist_batch");
+}
+
+extern "C" int fm_hamming_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* selfdist)
+{
+    return named_set_selfdist(ctx, bank, selfdist, kHamFamily, "fm_hamming_set_selfdist", "fm_bank_set_selfdist");
+}
+
+extern "C" int fm_wide_self_dist(fm_ctx* ctx, const fm_bank* bank, double* selfdist)
+{
+    return named_self_dist(ctx, bank, selfdist, kWideFamily, "fm_wide_self_dist", "fm_self_dist", "fm_hamming_self_dist");
+}
+
+extern "C" int fm_wide_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks, double* const* out)
+{
+    return named_self_dist_batch(ctx, n, banks, out, kWideFamily, "fm_wide_self_dist_batch", "fm_self_dist_batch", "fm_hamming_self_dist_batch");
+}
+
+extern "C" int fm_wide_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* selfdist)
+{
+    return named_set_selfdist(ctx, bank, selfdist, kWideFamily, "fm_wide_set_selfdist", "fm_bank_set_selfdist", "fm_hamming_set_selfdist");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1553,11 +1623,11 @@ struct AcceptedSink {
 
 // The argument checks the ratio calls share, in the order the header documents; n_host is zeroed on the way.  A pair without
 // query rows passes: the caller returns.
-// ham: a binary pair that ham_pair_check (the fm_hamming_* entry points) has passed already -- handles, kinds, widths and the
-// self distances, in the order the header gives for them.
-static int ratio_call_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const AcceptedSink& out, const char* who, bool ham = false)
+// named: a binary or a wide pair that named_pair_check (the fm_hamming_* / fm_wide_* entry points) has passed already --
+// handles, kinds, widths and the self distances, in the order the header gives for them.
+static int ratio_call_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const AcceptedSink& out, const char* who, bool named = false)
 {
-    int rc = ham ? FM_OK : check_pair(ctx, q, t, who);
+    int rc = named ? FM_OK : check_pair(ctx, q, t, who);
     if (rc != FM_OK) return rc;
     if (out.n_host) *out.n_host = 0;
     if (q->n == 0) return FM_OK;
@@ -1615,9 +1685,9 @@ static int enqueue_tail(fm_ctx* ctx, hipStream_t ts, fm_ctx::AsyncSlot& sl, cons
 // decode + ratio test, then by the sink -- every row and its flag (pass: fm_match_ratio's, optional), the compaction into
 // page-locked caller arrays directly, the compaction into ws_out and the staged delivery, or the device rows.
 static int ratio_sync(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, const AcceptedSink& out, uint8_t* pass, const char* who,
-                      bool ham = false)
+                      bool named = false)
 {
-    int rc = ratio_call_check(ctx, q, t, out, who, ham);
+    int rc = ratio_call_check(ctx, q, t, out, who, named);
     if (rc != FM_OK || q->n == 0) return rc;
     const bool compact = out.cap >= 0, to_device = out.to_device();
     const int64_t nq = q->n;
@@ -2390,32 +2460,46 @@ extern "C" int fm_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_ban
     return ratio_sync(ctx, q, t, tau, device_sink(d_rows, d_count, n_accepted, cap, FM_NO_STREAM), nullptr, "fm_match_accepted_dev");
 }
 
-// ---- Hamming Fast-Match: the accepted-match test on binary banks (the header's section of that name) ---------------------
+// ---- Hamming and wide Fast-Match: the accepted-match test on binary / wide float banks (the header's sections of those names) -
 // Steps 1 .. 4 of the documented error order; the entry points add cap and the NULL outputs, then ratio_sync runs the pair with
-// K11's reverse top-1 sweep (sweep_pair's binary route), the generic election and tail, and no ratio cut (an int8-route device).
-static int ham_pair_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who, const char* l2)
+// the family's reverse top-1 sweep (sweep_pair's binary route: K11; its wide route: K14 with float32-bit keys), the generic
+// election and tail, and no ratio cut (an int8-route device).
+static int named_pair_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const NamedFamily& f, const char* who, const char* l2,
+                            const char* ham = nullptr)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
     if (!q || !t) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
-    if (q->kind != FM_BANK_BIN || t->kind != FM_BANK_BIN)
-        return fail(ctx, FM_EINVAL, std::string(who) + ": both banks must be binary (FM_BANK_BIN, fm_bank_create_bin); " + l2 + " is the L2 call");
+    if (q->kind != f.kind || t->kind != f.kind)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": " + f.both + "; " + named_served_by(q->kind != f.kind ? q : t, l2, ham));
     if (q->dim != t->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": query/train width mismatch");
     if (q->n > 0 && !q->selfdist)
-        return fail(ctx, FM_EINVAL, std::string(who) + ": query bank has no self distances (fm_hamming_set_selfdist, fm_hamming_self_dist_batch)");
+        return fail(ctx, FM_EINVAL, std::string(who) + ": query bank has no self distances (" + f.attach + ")");
     return FM_OK;
+}
+
+static int named_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap, int32_t* d_rows, int64_t* d_count,
+                                    int64_t* n_accepted, const NamedFamily& f, const char* who_, const char* l2, const char* ham = nullptr)
+{
+    const std::string who(who_);
+    if (int rc = named_pair_check(ctx, q, t, f, who_, l2, ham)) return rc;
+    if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap < 0");
+    if (!d_rows || !d_count) return fail(ctx, FM_EINVAL, who + ": device output pointer is NULL");
+    if (int rc = check_device_rows(ctx, d_rows, d_count, who_)) return rc;
+    if (q->n == 0) HIP_TRY(ctx, hipMemset(d_count, 0, 8));
+    return ratio_sync(ctx, q, t, tau, device_sink(d_rows, d_count, n_accepted, cap, FM_NO_STREAM), nullptr, who_, true);
 }
 
 extern "C" int fm_hamming_match_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t* tidx,
                                       float* dist, double* ratio, uint8_t* pass, int64_t* n_pass)
 {
-    if (int rc = ham_pair_check(ctx, q, t, "fm_hamming_match_ratio", "fm_match_ratio")) return rc;
+    if (int rc = named_pair_check(ctx, q, t, kHamFamily, "fm_hamming_match_ratio", "fm_match_ratio")) return rc;
     return ratio_sync(ctx, q, t, tau, host_sink(nullptr, tidx, dist, ratio, n_pass, -1), pass, "fm_hamming_match_ratio", true);
 }
 
 extern "C" int fm_hamming_match_accepted(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                                          int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
 {
-    if (int rc = ham_pair_check(ctx, q, t, "fm_hamming_match_accepted", "fm_match_accepted")) return rc;
+    if (int rc = named_pair_check(ctx, q, t, kHamFamily, "fm_hamming_match_accepted", "fm_match_accepted")) return rc;
     if (cap < 0) return fail(ctx, FM_EINVAL, "fm_hamming_match_accepted: cap < 0");
     return ratio_sync(ctx, q, t, tau, host_sink(qidx, tidx, dist, ratio, n_accepted, cap), nullptr, "fm_hamming_match_accepted", true);
 }
@@ -2423,13 +2507,30 @@ extern "C" int fm_hamming_match_accepted(fm_ctx* ctx, const fm_bank* q, const fm
 extern "C" int fm_hamming_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                                              int32_t* d_rows, int64_t* d_count, int64_t* n_accepted)
 {
-    const char* who = "fm_hamming_match_accepted_dev";
-    if (int rc = ham_pair_check(ctx, q, t, who, "fm_match_accepted_dev")) return rc;
-    if (cap < 0) return fail(ctx, FM_EINVAL, "fm_hamming_match_accepted_dev: cap < 0");
-    if (!d_rows || !d_count) return fail(ctx, FM_EINVAL, "fm_hamming_match_accepted_dev: device output pointer is NULL");
-    if (int rc = check_device_rows(ctx, d_rows, d_count, who)) return rc;
-    if (q->n == 0) HIP_TRY(ctx, hipMemset(d_count, 0, 8));
-    return ratio_sync(ctx, q, t, tau, device_sink(d_rows, d_count, n_accepted, cap, FM_NO_STREAM), nullptr, who, true);
+    return named_match_accepted_dev(ctx, q, t, tau, cap, d_rows, d_count, n_accepted, kHamFamily, "fm_hamming_match_accepted_dev",
+                                    "fm_match_accepted_dev");
+}
+
+extern "C" int fm_wide_match_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t* tidx,
+                                   float* dist, double* ratio, uint8_t* pass, int64_t* n_pass)
+{
+    if (int rc = named_pair_check(ctx, q, t, kWideFamily, "fm_wide_match_ratio", "fm_match_ratio", "fm_hamming_match_ratio")) return rc;
+    return ratio_sync(ctx, q, t, tau, host_sink(nullptr, tidx, dist, ratio, n_pass, -1), pass, "fm_wide_match_ratio", true);
+}
+
+extern "C" int fm_wide_match_accepted(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
+                                      int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+{
+    if (int rc = named_pair_check(ctx, q, t, kWideFamily, "fm_wide_match_accepted", "fm_match_accepted", "fm_hamming_match_accepted")) return rc;
+    if (cap < 0) return fail(ctx, FM_EINVAL, "fm_wide_match_accepted: cap < 0");
+    return ratio_sync(ctx, q, t, tau, host_sink(qidx, tidx, dist, ratio, n_accepted, cap), nullptr, "fm_wide_match_accepted", true);
+}
+
+extern "C" int fm_wide_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
+                                          int32_t* d_rows, int64_t* d_count, int64_t* n_accepted)
+{
+    return named_match_accepted_dev(ctx, q, t, tau, cap, d_rows, d_count, n_accepted, kWideFamily, "fm_wide_match_accepted_dev",
+                                    "fm_match_accepted_dev", "fm_hamming_match_accepted_dev");
 }
 
 extern "C" int fm_match_accepted_dev_async(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,

@@ -456,15 +456,7 @@ static int pairs_carve(PairsCall& k)
     k.w_cnt = align256(k.max_part); k.w_bound = k.w_cnt + 256; k.w_list = k.w_bound + align256(k.max_bound); k.w_score = k.w_list + align256(k.max_cap * 8);
     if (k.wide && k.max_part > 0 && (rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, k.w_score + align256(k.max_cap * 4) + 64)) != FM_OK) return rc;
     if ((rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, k.tab_bytes + 64)) != FM_OK) return rc;
-    if (ctx->tab_in_flight) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_tab)); ctx->tab_in_flight = false; }
-    if (!ctx->ev_tab) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming));
-    if (k.tab_bytes > ctx->h_tab_bytes) {
-        if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
-        ctx->h_tab = nullptr; ctx->h_tab_bytes = 0;
-        const size_t want = k.tab_bytes + k.tab_bytes / 4 + 4096;
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_tab, want, hipHostMallocDefault));
-        ctx->h_tab_bytes = want;
-    }
+    if ((rc = table_host(ctx, k.tab_bytes)) != FM_OK) return rc;
     k.b = (char*)ctx->ws_out;
     k.h = ctx->h_tab;
     k.d = (const char*)ctx->ws_in;
@@ -616,9 +608,7 @@ static int pairs_upload(PairsCall& k)
         ctx->pending_pairs += k.ndir * ra * rb;
         ctx->pending_bytes += k.ndir * (ra + rb) * (k.i8 ? 128 : k.wide ? 1024 : c->stack.kind == FM_BANK_BIN ? c->stack.dim : 512);
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ws_in, k.h, k.tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_tab, ctx->stream));
-    ctx->tab_in_flight = true;
+    if (int rc = table_upload(ctx, ctx->ws_in, k.tab_bytes)) return rc;
     HIP_TRY(ctx, hipMemsetAsync(k.d_carry, 0, 16, ctx->stream));
     if (k.a.knn2) {
         // an image without rows keeps its slot: -1 / +inf, fm_knn2's lists over an empty bank

@@ -220,6 +220,12 @@ int dev_src_absmax(fm_ctx* ctx, const DevSrc& d, int64_t n, int dim, float* vmax
 int bank_f32_range_planes(fm_ctx* ctx, Bank& b, int64_t off, int64_t n, int64_t n_pad, float* nm_max);
 // A bank's self distances, and its largest one (Bank::sdmax), in place: the array is allocated once, the word behind it.
 int bank_selfdist_alloc(fm_ctx* ctx, fm_bank* b);
+// The context's page-locked table buffer (fm_ctx::h_tab), the one protocol of every call that builds workgroup or slot tables
+// on the host.  table_host: room for `bytes` bytes in it, once the last upload from it has been read (ev_tab): the caller
+// then writes ctx->h_tab.  table_upload: its first `bytes` bytes to `dst` (device memory) on the context's stream; the buffer
+// stays in flight until ev_tab, which the next table_host waits for -- a call may return without a host wait.
+int table_host(fm_ctx* ctx, size_t bytes);
+int table_upload(fm_ctx* ctx, void* dst, size_t bytes);
 // Bank::sdmax of the rows [0, n) of b->selfdist, enqueued on `stream` (sets sdmax_rows).
 int enqueue_selfdist_max(fm_ctx* ctx, fm_bank* b, hipStream_t stream);
 int round_xcheck_dense(fm_ctx* ctx, const fm::Bank& q, const int32_t* d_rows, int64_t nq, const fm::Bank& t, int64_t t0, int64_t nt,

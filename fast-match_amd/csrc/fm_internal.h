@@ -327,8 +327,9 @@ hipError_t launch_wide_copy(const void* src, int dtype, int64_t pitch, int64_t n
 // b.wrowsh, normf, auxf from b.wrows and b.kscale; stat[0] = largest |scaled row|^2 (float bits; zeroed by the caller)
 hipError_t launch_wide_planes(const Bank& b, int* stat, hipStream_t stream);
 // K5's kernel at the wide row: plan_rowreduce_f32's plans, K5's keys, K5's run_flag protocol
+// self (fm_wide_self_dist; cols and red are one bank, ktop 1): row n is no candidate of output row n
 hipError_t launch_wide_exact(const Bank& cols, const Bank& red, int ktop, const RowReducePlan& plan, unsigned long long* partial,
-                             const int* run_flag, hipStream_t stream);
+                             const int* run_flag, hipStream_t stream, bool self = false);
 // fp16 matrix-core filter + exact rescoring into split 0 of `partial` (preset to ~0 by the caller, as the 64-bit *cnt, flag[0] and
 // gbound[0 .. cols.n_pad) to 0); flag[0] = 1 afterwards: the record list overflowed and launch_wide_exact must redo the call
 struct WideFilterPlan {
@@ -339,7 +340,8 @@ struct WideFilterPlan {
 bool wide_filter_usable(const Bank& cols, const Bank& red);
 WideFilterPlan plan_wide_filter(int64_t ncols_pad, int64_t ncols, int64_t nred_pad, const Tuning& tn);
 hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const WideFilterPlan& plan, uint2* list, float* lscore,
-                              unsigned* gbound, unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream);
+                              unsigned* gbound, unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream,
+                              bool self = false);
 // Table forms (top-2) for a chunk of image pairs of one wide stack (fm_collection_pairs_mutual_ratio): a slot is one direction
 // of one pair, both operands views of `stack` that start on a 128-row stage -- or, with WideTableLaunch::outside, one of them
 // rows of a bank outside the stack (fm_collection_wide_mutual_ratio_each: a query bank).  The slots lie side by side in the chunk's
@@ -366,10 +368,11 @@ struct WideTableLaunch {
 // the filter and the rescoring into `partial` (preset to ~0, *cnt, flag[0] and gbound[0 .. rows) to 0); flag[0] = 1 afterwards:
 // the chunk's list (cap records, a multiple of 64) overflowed and launch_wide_exact_table must redo the chunk
 hipError_t launch_wide_filter_table(const Bank& stack, const WideTableLaunch& tl, unsigned cap, uint2* list, float* lscore, unsigned* gbound,
-                                    unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream);
+                                    unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream, int ktop = 2);
 // the exact kernel over the same table, one split per slot, under K5's run_flag protocol; writes every row of `partial`
+// ktop 1 (both launches; needs WideTableLaunch::outside): the top-1 forms, partial [rows] -- fm_collection_wide_match_accepted_each
 hipError_t launch_wide_exact_table(const Bank& stack, const WideTableLaunch& tl, unsigned long long* partial, const int* run_flag,
-                                   hipStream_t stream);
+                                   hipStream_t stream, int ktop = 2);
 
 // ---- K13: k-NN under a bit mask (masked.hip) ------------------------------------------------------------------------------
 // Integer route, k = 1 or 2, on the matrix cores: the masked top-k of every row of q over the rows of t (t may be a

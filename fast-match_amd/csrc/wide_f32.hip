@@ -66,7 +66,12 @@
 // Part 4, the table forms of the three kernels: the bodies of parts 2 and 3 (wide_exact_body, wide_filter_body) over a table
 // of slots in device memory, one launch per chunk of image pairs (fm_collection_pairs_mutual_ratio).
 // Part 5, the table forms with an outside operand (OUT = true): one side of every slot is a bank that is not part of the stack
-// (fm_collection_wide_mutual_ratio_each, fm_collection_wide_knn2_each).
+// (fm_collection_wide_mutual_ratio_each, fm_collection_wide_knn2_each; with KTOP = 1 and reverse slots alone,
+// fm_collection_wide_match_accepted_each).
+// The SELF forms of the bank-pair kernels (fm_wide_self_dist): one sweep of a bank over itself with the diagonal dropped by
+// index (wide_filter_body, wide_rescore_kernel, wide_exact_body).  The margin derivation above is unchanged: the diagonal
+// leaves by index, not by value, so every bound is the KTOP-th best score of real OTHER rows and every row of the exact
+// top-KTOP over the other rows is recorded against it.
 #include "tile_ops.h"
 #include <algorithm>
 
@@ -204,7 +209,12 @@ __device__ __forceinline__ void wide_load_kmajor(const float* __restrict__ rows,
 
 // The body of the exact kernels: 64 output rows (`chunk`) of p's output bank against split `split` of its reduced rows.  The
 // bank-pair kernel and the table kernel (part 4) differ only in where p, chunk and split come from.
-template <int KTOP>
+// SELF (the banks are one bank, fm_wide_self_dist): row n is no candidate of output row n -- dropped by index, like the padding.
+// OWN: an instantiation of its own for the top-1 table kernel (wide_exact_table_kernel<1, true>), nothing else.  With ONE
+// instantiation wide_exact_body<1> inlined into both that kernel and wide_exact_kernel<1>, hipcc compiled the pair kernel to
+// other code than it had (its LDS staging: 2384 -> 2317 instructions, one more VGPR), unmeasured; with two, every kernel that
+// existed before the table form keeps its instruction stream (tests/test_wide_fast_host.py pins them).
+template <int KTOP, bool SELF = false, bool OWN = false>
 __device__ __forceinline__ void wide_exact_body(const WideExactParams& p, int chunk, int split, float* __restrict__ colimg, float* __restrict__ redimg)
 {
     const int tid = threadIdx.x;
@@ -260,7 +270,9 @@ __device__ __forceinline__ void wide_exact_body(const WideExactParams& p, int ch
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int idx = m0 + j;
-                    if (idx < p.nred && s[i][j] <= thr[i]) {
+                    bool cand = idx < p.nred && s[i][j] <= thr[i];
+                    if constexpr (SELF) cand = cand && idx != c0 + 4 * tn + i;
+                    if (cand) {
                         const float d = sqrtf(s[i][j]);
                         if (d < bd[i][KTOP - 1]) {            // strict: earlier row wins ties
                             if constexpr (KTOP == 2) {
@@ -320,7 +332,7 @@ __device__ __forceinline__ void wide_exact_body(const WideExactParams& p, int ch
     }
 }
 
-template <int KTOP>
+template <int KTOP, bool SELF = false>
 __global__ __launch_bounds__(256)
 void wide_exact_kernel(WideExactParams p)
 {
@@ -331,12 +343,13 @@ void wide_exact_kernel(WideExactParams p)
         if (*p.run_flag == 0) return;                 // the filter's result stands
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd((int*)p.run_flag + 2, 1);
     }
-    wide_exact_body<KTOP>(p, (int)(blockIdx.x / p.nsplit), (int)(blockIdx.x % p.nsplit), colimg, redimg);
+    wide_exact_body<KTOP, SELF>(p, (int)(blockIdx.x / p.nsplit), (int)(blockIdx.x % p.nsplit), colimg, redimg);
 }
 
 hipError_t launch_wide_exact(const Bank& cols, const Bank& red, int ktop, const RowReducePlan& plan, unsigned long long* partial,
-                             const int* run_flag, hipStream_t stream)
+                             const int* run_flag, hipStream_t stream, bool self)
 {
+    if (self && (ktop != 1 || cols.wrows != red.wrows)) return hipErrorInvalidValue;
     WideExactParams p;
     p.run_flag = run_flag;
     p.col_rows = cols.wrows;
@@ -351,8 +364,9 @@ hipError_t launch_wide_exact(const Bank& cols, const Bank& red, int ktop, const 
     p.kend = (cols.dim + 7) & ~7;
     p.partial = partial;
     const int grid = plan.nchunks * plan.nsplit;
-    if (ktop == 1) hipLaunchKernelGGL((wide_exact_kernel<1>), dim3(grid), dim3(256), 0, stream, p);
-    else           hipLaunchKernelGGL((wide_exact_kernel<2>), dim3(grid), dim3(256), 0, stream, p);
+    if (self)           hipLaunchKernelGGL((wide_exact_kernel<1, true>), dim3(grid), dim3(256), 0, stream, p);
+    else if (ktop == 1) hipLaunchKernelGGL((wide_exact_kernel<1>), dim3(grid), dim3(256), 0, stream, p);
+    else                hipLaunchKernelGGL((wide_exact_kernel<2>), dim3(grid), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 
@@ -414,7 +428,7 @@ __device__ __forceinline__ void wide_push(bool pred, int col, int row, float sco
         unsigned nb = 0;
         if (lane == 0) {
             const unsigned long long r = atomicAdd(p.cnt, 64ull);
-            nb = r >= p.cap ? kWFull : (unsigned)r;             // (cap <= 2^24, a multiple of 64)
+            nb = r >= p.cap ? kWFull : (unsigned)r;             // (cap is a multiple of 64 and at most 2^28: a slot below it fits 32 bits)
         }
         base = (unsigned)__builtin_amdgcn_readfirstlane((int)nb);
         used = 0;
@@ -425,10 +439,46 @@ __device__ __forceinline__ void wide_push(bool pred, int col, int row, float sco
     used += n;
 }
 
+// One block's tail of a tile: the tile's scores first into the lane's best, the bound shared among the 4 lanes of the output
+// row, THEN the test -- a row is recorded against a bound that already knows its own tile.  MASK: the tile holds the block's
+// diagonal (SELF form); lane (lr, lg) holds it in register lr - 4 lg, and it is no candidate.
+template <int KTOP, bool MASK>
+__device__ __forceinline__ void wide_tile_scores(const w_v4f& acc, const float (&ax)[4], int r0, int col, int lr, int lg, const WideFilterParams& p,
+                                                 int rowbase, float (&best)[KTOP], float& bnd, float marg, unsigned& lbase, unsigned& lused)
+{
+    float sc[4];
+    bool real[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        sc[r] = __builtin_fmaf(acc[r], p.cscale, ax[r]);
+        real[r] = r0 + r < p.nred && col < p.ncols;
+        if constexpr (MASK) real[r] = real[r] && 4 * lg + r != lr;
+        if (real[r]) {
+            if constexpr (KTOP == 2) {
+                if (sc[r] > best[0]) { best[1] = best[0]; best[0] = sc[r]; }
+                else if (sc[r] > best[1]) best[1] = sc[r];
+            } else {
+                if (sc[r] > best[0]) best[0] = sc[r];
+            }
+        }
+    }
+    bnd = fmaxf(bnd, best[KTOP - 1]);
+    bnd = fmaxf(bnd, __shfl_xor(bnd, 16));
+    bnd = fmaxf(bnd, __shfl_xor(bnd, 32));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wide_push(real[r] && sc[r] >= bnd - marg, rowbase + col, r0 + r, sc[r], p, lbase, lused);
+}
+
 // The body of the filter kernels: the 128 output rows `blk` of p's output bank against split `split` of its reduced rows.
 // rowbase: where the output bank's row 0 lies in the row space of gbound and of the records (0 for a bank pair; a slot's
 // first row in its chunk for the table kernel, part 4).
-template <int KS, int KTOP>
+// SELF (the banks are one bank, fm_wide_self_dist; KTOP = 1): reduced row n is no candidate of output row n.  Its score is the
+// row's maximum (d2 = 0), so it must be gone before it can enter best[] -- in the bound it would shut every real neighbour
+// out -- and before it is pushed: it leaves by INDEX, under `real`, with the padding rows.  A block of 16 output rows meets its
+// diagonal in ONE 16-row tile (both start on multiples of 16): tile c0 / 16 + b, where lane (lr, lg) holds it in register
+// r = lr - 4 lg.  Only that tile takes the masked tail (wide_tile_scores<KTOP, true>); every other tile takes the unmasked
+// one, behind a scalar compare of the tile index with the wave's first diagonal tile (read once into a scalar register).
+template <int KS, int KTOP, bool SELF = false>
 __device__ __forceinline__ void wide_filter_body(const WideFilterParams& p, int blk, int split, int rowbase)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -451,6 +501,8 @@ __device__ __forceinline__ void wide_filter_body(const WideFilterParams& p, int 
     const int t0 = split * p.tiles_per_split;
     const int t1 = min(t0 + p.tiles_per_split, p.ntiles);
     unsigned lbase = kWNoChunk, lused = 0;
+    [[maybe_unused]] int dtile = 0;                             // SELF: the tile that holds block 0's diagonal (block b: dtile + b)
+    if constexpr (SELF) dtile = __builtin_amdgcn_readfirstlane(c0 >> 4);
     w_v8h an[KS];
     if (t0 < t1) {
 #pragma unroll
@@ -473,28 +525,34 @@ __device__ __forceinline__ void wide_filter_body(const WideFilterParams& p, int 
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[ks], bq[b][ks], acc, 0, 0, 0);
             const int col = c0 + 16 * b + lr;
-            // the tile's scores first into the lane's best, the bound shared among the 4 lanes of the output row, THEN the
-            // test: a row is recorded against a bound that already knows its own tile
-            float sc[4];
-            bool real[4];
+            if constexpr (SELF) {
+                // (t and dtile are scalar values: one scalar branch per block and tile, and two copies of the tail)
+                if (t == dtile + b) wide_tile_scores<KTOP, true>(acc, ax, r0, col, lr, lg, p, rowbase, best[b], bnd[b], marg[b], lbase, lused);
+                else                wide_tile_scores<KTOP, false>(acc, ax, r0, col, lr, lg, p, rowbase, best[b], bnd[b], marg[b], lbase, lused);
+            } else {
+                // (the same tail, written out: the instantiations without SELF keep the instruction streams they had before
+                // the SELF form existed, which a call of wide_tile_scores here does not give them)
+                float sc[4];
+                bool real[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                sc[r] = __builtin_fmaf(acc[r], p.cscale, ax[r]);
-                real[r] = r0 + r < p.nred && col < p.ncols;
-                if (real[r]) {
-                    if constexpr (KTOP == 2) {
-                        if (sc[r] > best[b][0]) { best[b][1] = best[b][0]; best[b][0] = sc[r]; }
-                        else if (sc[r] > best[b][1]) best[b][1] = sc[r];
-                    } else {
-                        if (sc[r] > best[b][0]) best[b][0] = sc[r];
+                for (int r = 0; r < 4; ++r) {
+                    sc[r] = __builtin_fmaf(acc[r], p.cscale, ax[r]);
+                    real[r] = r0 + r < p.nred && col < p.ncols;
+                    if (real[r]) {
+                        if constexpr (KTOP == 2) {
+                            if (sc[r] > best[b][0]) { best[b][1] = best[b][0]; best[b][0] = sc[r]; }
+                            else if (sc[r] > best[b][1]) best[b][1] = sc[r];
+                        } else {
+                            if (sc[r] > best[b][0]) best[b][0] = sc[r];
+                        }
                     }
                 }
-            }
-            bnd[b] = fmaxf(bnd[b], best[b][KTOP - 1]);
-            bnd[b] = fmaxf(bnd[b], __shfl_xor(bnd[b], 16));
-            bnd[b] = fmaxf(bnd[b], __shfl_xor(bnd[b], 32));
+                bnd[b] = fmaxf(bnd[b], best[b][KTOP - 1]);
+                bnd[b] = fmaxf(bnd[b], __shfl_xor(bnd[b], 16));
+                bnd[b] = fmaxf(bnd[b], __shfl_xor(bnd[b], 32));
 #pragma unroll
-            for (int r = 0; r < 4; ++r) wide_push(real[r] && sc[r] >= bnd[b] - marg[b], rowbase + col, r0 + r, sc[r], p, lbase, lused);
+                for (int r = 0; r < 4; ++r) wide_push(real[r] && sc[r] >= bnd[b] - marg[b], rowbase + col, r0 + r, sc[r], p, lbase, lused);
+            }
         }
     }
     wide_pad_chunk(lbase, lused, p);
@@ -506,11 +564,11 @@ __device__ __forceinline__ void wide_filter_body(const WideFilterParams& p, int 
     }
 }
 
-template <int KS, int KTOP>
+template <int KS, int KTOP, bool SELF = false>
 __global__ __launch_bounds__(256)
 void wide_filter_kernel(WideFilterParams p)
 {
-    wide_filter_body<KS, KTOP>(p, (int)(blockIdx.x / p.nsplit), (int)(blockIdx.x % p.nsplit), 0);
+    wide_filter_body<KS, KTOP, SELF>(p, (int)(blockIdx.x / p.nsplit), (int)(blockIdx.x % p.nsplit), 0);
 }
 
 struct WideRescoreParams {
@@ -521,7 +579,8 @@ struct WideRescoreParams {
     int* flag;                        // [0] = 1: the list overflowed, the exact kernel redoes the call
 };
 
-template <int KTOP>
+// SELF: a record (i, i) is never inserted (the filter's SELF form makes none; the rescoring does not rely on it).
+template <int KTOP, bool SELF = false>
 __global__ __launch_bounds__(256)
 void wide_rescore_kernel(WideRescoreParams p)
 {
@@ -534,6 +593,7 @@ void wide_rescore_kernel(WideRescoreParams p)
     for (unsigned e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
         const uint2 rec = p.list[e];
         if (rec.x == kWNoRecord) continue;                      // the padding of a chunk
+        if constexpr (SELF) { if (rec.x == rec.y) continue; }
         // most records were made against a bound of the sweep's first tiles: the output row's final bound drops them
         if (p.lscore[e] < wide_bits_f(p.gbound[rec.x]) - wide_margin(p.colnorm[rec.x], p.nscale, p.red_nm_max)) continue;
         const float4* a = (const float4*)(p.col_rows + (size_t)rec.x * kWideDim);
@@ -583,15 +643,16 @@ WideFilterPlan plan_wide_filter(int64_t ncols_pad, int64_t ncols, int64_t nred_p
     return pl;
 }
 
-template <int KS, int KTOP>
+template <int KS, int KTOP, bool SELF = false>
 static void wide_filter_launch(const WideFilterParams& p, int grid, hipStream_t stream)
 {
-    hipLaunchKernelGGL((wide_filter_kernel<KS, KTOP>), dim3(grid), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((wide_filter_kernel<KS, KTOP, SELF>), dim3(grid), dim3(256), 0, stream, p);
 }
 
 hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const WideFilterPlan& plan, uint2* list, float* lscore,
-                              unsigned* gbound, unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream)
+                              unsigned* gbound, unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream, bool self)
 {
+    if (self && (ktop != 1 || cols.wrows != red.wrows)) return hipErrorInvalidValue;
     WideFilterParams p;
     p.colh = cols.wrowsh; p.colnorm = cols.normf; p.ncols = (int)cols.n;
     p.redh = red.wrowsh; p.redaux = red.auxf; p.nred = (int)red.n;
@@ -605,7 +666,8 @@ hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const
     const int ks = (cols.dim + 31) / 32;
     if (ks < 5 || ks > 8) return hipErrorInvalidValue;
 #define FM_WIDE_F(KS_)                                                                            \
-    case KS_: if (ktop == 1) wide_filter_launch<KS_, 1>(p, grid, stream); else wide_filter_launch<KS_, 2>(p, grid, stream); break;
+    case KS_: if (self) wide_filter_launch<KS_, 1, true>(p, grid, stream);                        \
+              else if (ktop == 1) wide_filter_launch<KS_, 1>(p, grid, stream); else wide_filter_launch<KS_, 2>(p, grid, stream); break;
     switch (ks) { FM_WIDE_F(5) FM_WIDE_F(6) FM_WIDE_F(7) FM_WIDE_F(8) }
 #undef FM_WIDE_F
     hipError_t e = hipGetLastError();
@@ -614,8 +676,9 @@ hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const
     r.col_rows = cols.wrows; r.red_rows = red.wrows; r.dim = cols.dim;
     r.list = list; r.lscore = lscore; r.cap = plan.cap; r.cnt = cnt; r.partial = partial; r.flag = flag;
     r.gbound = gbound; r.colnorm = cols.normf; r.nscale = p.nscale; r.red_nm_max = red.nm_max;
-    if (ktop == 1) hipLaunchKernelGGL((wide_rescore_kernel<1>), dim3(2048), dim3(256), 0, stream, r);
-    else           hipLaunchKernelGGL((wide_rescore_kernel<2>), dim3(2048), dim3(256), 0, stream, r);
+    if (self)           hipLaunchKernelGGL((wide_rescore_kernel<1, true>), dim3(2048), dim3(256), 0, stream, r);
+    else if (ktop == 1) hipLaunchKernelGGL((wide_rescore_kernel<1>), dim3(2048), dim3(256), 0, stream, r);
+    else                hipLaunchKernelGGL((wide_rescore_kernel<2>), dim3(2048), dim3(256), 0, stream, r);
     return hipGetLastError();
 }
 
@@ -761,7 +824,7 @@ void wide_exact_table_kernel(WideTableParams t)
     p.kend = (t.dim + 7) & ~7;
     p.partial = t.partial + (size_t)sl.row0 * KTOP;
     p.run_flag = nullptr;
-    wide_exact_body<KTOP>(p, (row - sl.row0) / kWTile, 0, colimg, redimg);
+    wide_exact_body<KTOP, false, KTOP == 1>(p, (row - sl.row0) / kWTile, 0, colimg, redimg);
 }
 
 static WideTableParams wide_table_params(const Bank& stack, const WideTableLaunch& tl)
@@ -774,41 +837,45 @@ static WideTableParams wide_table_params(const Bank& stack, const WideTableLaunc
     return t;
 }
 
+// ktop 1: the top-1 table forms with an outside operand (fm_collection_wide_match_accepted_each: reverse slots, partial [rows])
 template <int KS>
-static void wide_filter_table_launch(const WideTableParams& t, int grid, hipStream_t stream)
+static void wide_filter_table_launch(const WideTableParams& t, int ktop, int grid, hipStream_t stream)
 {
-    if (t.orows) hipLaunchKernelGGL((wide_filter_table_kernel<KS, 2, true>), dim3(grid), dim3(256), 0, stream, t);
-    else         hipLaunchKernelGGL((wide_filter_table_kernel<KS, 2, false>), dim3(grid), dim3(256), 0, stream, t);
+    if (ktop == 1)    hipLaunchKernelGGL((wide_filter_table_kernel<KS, 1, true>), dim3(grid), dim3(256), 0, stream, t);
+    else if (t.orows) hipLaunchKernelGGL((wide_filter_table_kernel<KS, 2, true>), dim3(grid), dim3(256), 0, stream, t);
+    else              hipLaunchKernelGGL((wide_filter_table_kernel<KS, 2, false>), dim3(grid), dim3(256), 0, stream, t);
 }
 
 hipError_t launch_wide_filter_table(const Bank& stack, const WideTableLaunch& tl, unsigned cap, uint2* list, float* lscore, unsigned* gbound,
-                                    unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream)
+                                    unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream, int ktop)
 {
     WideTableParams t = wide_table_params(stack, tl);
     t.list = list; t.lscore = lscore; t.cap = cap; t.cnt = cnt; t.gbound = gbound; t.partial = partial; t.flag = flag;
     const int ks = (stack.dim + 31) / 32;
-    if (ks < 5 || ks > 8 || tl.n < 1 || tl.fwg < 1) return hipErrorInvalidValue;
+    if (ks < 5 || ks > 8 || tl.n < 1 || tl.fwg < 1 || (ktop != 2 && (ktop != 1 || !t.orows))) return hipErrorInvalidValue;
     switch (ks) {
-        case 5: wide_filter_table_launch<5>(t, tl.fwg, stream); break;
-        case 6: wide_filter_table_launch<6>(t, tl.fwg, stream); break;
-        case 7: wide_filter_table_launch<7>(t, tl.fwg, stream); break;
-        default: wide_filter_table_launch<8>(t, tl.fwg, stream); break;
+        case 5: wide_filter_table_launch<5>(t, ktop, tl.fwg, stream); break;
+        case 6: wide_filter_table_launch<6>(t, ktop, tl.fwg, stream); break;
+        case 7: wide_filter_table_launch<7>(t, ktop, tl.fwg, stream); break;
+        default: wide_filter_table_launch<8>(t, ktop, tl.fwg, stream); break;
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (t.orows) hipLaunchKernelGGL((wide_rescore_table_kernel<2, true>), dim3(2048), dim3(256), 0, stream, t);
-    else         hipLaunchKernelGGL((wide_rescore_table_kernel<2, false>), dim3(2048), dim3(256), 0, stream, t);
+    if (ktop == 1)    hipLaunchKernelGGL((wide_rescore_table_kernel<1, true>), dim3(2048), dim3(256), 0, stream, t);
+    else if (t.orows) hipLaunchKernelGGL((wide_rescore_table_kernel<2, true>), dim3(2048), dim3(256), 0, stream, t);
+    else              hipLaunchKernelGGL((wide_rescore_table_kernel<2, false>), dim3(2048), dim3(256), 0, stream, t);
     return hipGetLastError();
 }
 
 hipError_t launch_wide_exact_table(const Bank& stack, const WideTableLaunch& tl, unsigned long long* partial, const int* run_flag,
-                                   hipStream_t stream)
+                                   hipStream_t stream, int ktop)
 {
     WideTableParams t = wide_table_params(stack, tl);
     t.partial = partial; t.run_flag = run_flag;
-    if (tl.n < 1 || tl.rows < kWTile) return hipErrorInvalidValue;
-    if (t.orows) hipLaunchKernelGGL((wide_exact_table_kernel<2, true>), dim3((unsigned)(tl.rows / kWTile)), dim3(256), 0, stream, t);
-    else         hipLaunchKernelGGL((wide_exact_table_kernel<2, false>), dim3((unsigned)(tl.rows / kWTile)), dim3(256), 0, stream, t);
+    if (tl.n < 1 || tl.rows < kWTile || (ktop != 2 && (ktop != 1 || !t.orows))) return hipErrorInvalidValue;
+    if (ktop == 1)    hipLaunchKernelGGL((wide_exact_table_kernel<1, true>), dim3((unsigned)(tl.rows / kWTile)), dim3(256), 0, stream, t);
+    else if (t.orows) hipLaunchKernelGGL((wide_exact_table_kernel<2, true>), dim3((unsigned)(tl.rows / kWTile)), dim3(256), 0, stream, t);
+    else              hipLaunchKernelGGL((wide_exact_table_kernel<2, false>), dim3((unsigned)(tl.rows / kWTile)), dim3(256), 0, stream, t);
     return hipGetLastError();
 }
 

@@ -35,7 +35,9 @@ Mirrors ``matchutil.py`` of the reference:
   ``matchPairs`` / ``matchPairs_arrays`` computes (``fm_collection_add_wide``).  A wide query against such a collection,
   image by image, is ``BFMatcher.mutualRatioMatchWideEach`` / ``mutualRatioMatchWideEach_arrays`` (mutual nearest neighbour
   + ratio per image, the visual-localisation pattern; ``fm_collection_wide_mutual_ratio_each``) and
-  ``knnMatchWideEach_arrays`` (``fm_collection_wide_knn2_each``).
+  ``knnMatchWideEach_arrays`` (``fm_collection_wide_knn2_each``).  Fast-Match's self-distance test on wide descriptors:
+  ``wide_fast_match`` / ``wide_fast_match_arrays`` (``fm_wide_self_dist_batch``, ``fm_wide_match_accepted``) and, against a
+  wide collection, ``BFMatcher.wideFastMatchEach`` / ``wideFastMatchEach_arrays``.
 * ``options["mask"]``: cv2's ``mask`` argument of ``knnMatch`` -- an ``[nq, nt]`` uint8 / bool array, nonzero = the pair
   (query row, train row) may be matched, or a resident ``_ffi.Mask`` (``Context.mask``).  ``bf_match``,
   ``bf_match_arrays``, ``flann_match`` and ``flann_match_arrays`` honour it when crossCheck is off: every list is the
@@ -418,6 +420,61 @@ def hamming_fast_match(dt1, dt2, tau, options={}):
     return [DMatch(int(qidx[j]), int(tidx[j]), dist[j]) for j in range(qidx.shape[0])]
 
 
+def _wide_operand(d, who):
+    """A resident wide float bank, or a float32 / float64 [n, 129 .. 256] array -- ValueError before anything is uploaded.
+    Returns (operand as it goes to the device, dim)."""
+    if isinstance(d, _ffi.Bank):
+        if d.kind != _ffi.FM_BANK_F32W:
+            raise ValueError("%s takes wide float banks (FM_BANK_F32W, 129 .. 256 values per row); fastmatch / "
+                             "hamming_fast_match serve the other kinds" % who)
+        return d, d.dim
+    a = np.asarray(d)
+    if a.ndim != 2:
+        raise ValueError("descriptors must be a 2-D [n, dim] array")
+    if a.dtype not in (np.float32, np.float64):
+        raise ValueError("%s needs float32 / float64 descriptors, got %s" % (who, a.dtype))
+    if not 129 <= a.shape[1] <= 256:
+        raise ValueError("%s: wide float descriptors have 129 .. 256 values per row, got %d" % (who, a.shape[1]))
+    return np.ascontiguousarray(a, dtype=np.float32), a.shape[1]
+
+
+def wide_fast_match_arrays(dt1, dt2, tau, options={}):
+    """Fast-Match's accepted-match test on wide float descriptors (129 .. 256 values per row, SuperPoint and its kin):
+    ``(qidx int32[m], tidx int32[m], dist float32[m], ratio float64[m])``, ascending query index -- the pairs for which t is
+    the cross-checked nearest neighbour of q under the L2 distance and ``dist / selfdist(q) < tau``, selfdist(q) the distance
+    from q to its nearest OTHER row of ``dt1`` (computed on the device unless ``dt1`` is a resident bank that carries its
+    own).  A query row with an exact duplicate in ``dt1`` (selfdist 0) is never accepted.  ``dt1`` / ``dt2``: float32 / float64
+    arrays or resident wide banks.  ``ValueError`` before anything is uploaded: another dtype, dims that differ or lie
+    outside 129 .. 256."""
+    q, qw = _wide_operand(dt1, "wide_fast_match")
+    t, tw = _wide_operand(dt2, "wide_fast_match")
+    if qw != tw:
+        raise ValueError("wide_fast_match: %d values per query row, %d per train row" % (qw, tw))
+    ctx = _context(options)
+    qb, q_tmp = (q, False) if isinstance(q, _ffi.Bank) else (ctx.bank(q), True)
+    try:
+        tb, t_tmp = (t, False) if isinstance(t, _ffi.Bank) else (ctx.bank(t), True)
+    except Exception:
+        if q_tmp:
+            qb.close()
+        raise
+    try:
+        if q_tmp or not qb.has_selfdist:
+            ctx.wide_self_dist_batch([qb], want_host=False)
+        return ctx.wide_match_accepted(qb, tb, tau)
+    finally:
+        if q_tmp:
+            qb.close()
+        if t_tmp:
+            tb.close()
+
+
+def wide_fast_match(dt1, dt2, tau, options={}):
+    """ The accepted matches of wide_fast_match_arrays as a list of DMatch, ascending query index """
+    qidx, tidx, dist, _ = wide_fast_match_arrays(dt1, dt2, tau, options=options)
+    return [DMatch(int(qidx[j]), int(tidx[j]), dist[j]) for j in range(qidx.shape[0])]
+
+
 class BFMatcher(object):
     """``cv2.BFMatcher(normType, crossCheck)`` with cv2's method names.  With a train argument ``match`` / ``knnMatch`` /
     ``radiusMatch`` are :func:`bf_match` / :func:`bf_radius_match`; without one they run against the TRAIN COLLECTION
@@ -508,10 +565,10 @@ class BFMatcher(object):
         if self.empty():
             raise ValueError("%s: no train descriptors (add() some, or pass a train array)" % who)
         if self._wide and who not in ("BFMatcher.train", "BFMatcher.matchPairs", "BFMatcher.mutualRatioMatchWideEach",
-                                      "BFMatcher.knnMatchWideEach"):
+                                      "BFMatcher.knnMatchWideEach", "BFMatcher.wideFastMatchEach"):
             raise ValueError("%s is not built for a wide collection (images of 129 .. 256 values per row, add_wide): "
-                             "matchPairs, matchPairs_arrays and, for a wide query, mutualRatioMatchWideEach(_arrays) and "
-                             "knnMatchWideEach_arrays are" % who)
+                             "matchPairs, matchPairs_arrays and, for a wide query, mutualRatioMatchWideEach(_arrays), "
+                             "wideFastMatchEach(_arrays) and knnMatchWideEach_arrays are" % who)
 
     def train(self):
         self._check_collection("BFMatcher.train")
@@ -767,6 +824,31 @@ class BFMatcher(object):
         ``trainIdx`` the row inside the image, ``imgIdx`` the image, ascending ``queryIdx``."""
         out = []
         for i, (qidx, tidx, dist, _) in enumerate(self.mutualRatioMatchWideEach_arrays(queryDescriptors, tau, symmetric)):
+            out.append([DMatch(int(qidx[j]), int(tidx[j]), dist[j], i) for j in range(qidx.shape[0])])
+        return out
+
+    def wideFastMatchEach_arrays(self, queryDescriptors, tau):
+        """``fastMatchEach_arrays`` of a WIDE collection (``add_wide``): a list of (qidx, tidx, dist, ratio) per image, slot i
+        equal to ``wide_fast_match_arrays(query, image_i, tau)`` (``Collection.wide_match_accepted_each``).  The query's self
+        distances are computed on the device unless it is a resident bank that carries them.  The refusals are
+        :meth:`mutualRatioMatchWideEach_arrays`'."""
+        q = self._wide_query("BFMatcher.wideFastMatchEach", queryDescriptors)
+        coll = self.train()
+        qb, tmp = (q, False) if isinstance(q, _ffi.Bank) else (coll.ctx.bank(q), True)
+        try:
+            if tmp or not qb.has_selfdist:
+                coll.ctx.wide_self_dist_batch([qb], want_host=False)          # attached on the device, nothing comes back
+            return coll.wide_match_accepted_each(qb, tau)
+        finally:
+            if tmp:
+                qb.close()
+
+    def wideFastMatchEach(self, queryDescriptors, tau):
+        """Fast-Match's accepted-match test of a wide query against a WIDE collection, image by image: one list of ``DMatch``
+        per added image (``imgIdx`` set) -- t is the cross-checked nearest neighbour of q inside that image and
+        ``dist(q, t) / selfdist(q) < tau``.  A query row with an exact duplicate (selfdist 0) is never accepted."""
+        out = []
+        for i, (qidx, tidx, dist, _) in enumerate(self.wideFastMatchEach_arrays(queryDescriptors, tau)):
             out.append([DMatch(int(qidx[j]), int(tidx[j]), dist[j], i) for j in range(qidx.shape[0])])
         return out
 

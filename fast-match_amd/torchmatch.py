@@ -63,6 +63,10 @@ A wide QUERY against a wide collection, image by image: ``Collection.wide_mutual
 cap=None)`` -> ``(offsets int64 [n_images + 1], rows int32 [n, 3] = (query row, row inside the image, float32 distance
 bits))``, image i equal to ``mutual_ratio_match(q, image_i)`` (``fm_collection_wide_mutual_ratio_each_dev``; the
 visual-localisation pattern); ``cap`` as in ``match_pairs``.
+Fast-Match's self-distance test on wide descriptors: ``wide_fast_match(q, t, tau)`` -> ``(rows int32 [m, 3], count int64
+[1])`` (``fm_wide_self_dist_batch``, ``fm_wide_match_accepted_dev``) and, against a wide collection image by image,
+``Collection.wide_fast_match_each(q, tau, cap=None)`` -> ``(rows int32 [n_images, cap, 3], counts int64 [n_images])``
+(``fm_collection_wide_match_accepted_each_dev``).
 
 ``q`` and ``t`` are ``Bank``s or CUDA tensors (a tensor becomes a bank for the call).  The values are those of
 ``Context.knn`` / ``xcheck1`` / ``knn2_ratio`` on banks built from the same numbers on the host, bit for bit.
@@ -426,6 +430,60 @@ def hamming_fast_match(q, t, tau):
             b.close()
 
 
+def _wide_operand(who, x):
+    """A wide float bank as it is, or a checked float32 / float16 / bfloat16 tensor of 129 .. 256 values per row -- ValueError
+    before the library is touched."""
+    if isinstance(x, _ffi.Bank):
+        if x.kind != _ffi.FM_BANK_F32W:
+            raise ValueError("%s takes wide float banks (FM_BANK_F32W, 129 .. 256 values per row); fast matching of the other "
+                             "kinds goes through Context.match_accepted_dev / hamming_fast_match" % who)
+        return x
+    t, dt = _checked(x)
+    if dt == _ffi.FM_DT_U8 or not 129 <= t.shape[1] <= 256:
+        raise ValueError("%s: wide descriptors are float32 / float16 / bfloat16 tensors of 129 .. 256 values per row, got %s "
+                         "[%d, %d]" % (who, t.dtype, t.shape[0], t.shape[1]))
+    return t
+
+
+def wide_fast_match(q, t, tau):
+    """Fast-Match's accepted-match test on wide float descriptors (129 .. 256 values per row), left on the device: ``(rows
+    int32 [m, 3] = (query, train row, float32 distance bits), count int64 [1])`` CUDA tensors, ascending query index -- t is
+    the cross-checked nearest neighbour of q and ``dist / selfdist(q) < tau``, selfdist(q) the distance from q to its nearest
+    OTHER query row (a row with an exact duplicate is never accepted).  ``q`` / ``t``: float32 / float16 / bfloat16 CUDA
+    tensors (half and bfloat16 widened exactly) or wide ``Bank``s; a query bank that carries no self distances gets them on
+    the device (``fm_wide_self_dist_batch``).  One host wait, for the count that sizes ``rows``."""
+    import torch
+    who = "wide_fast_match"
+    ops = [_wide_operand(who, x) for x in (q, t)]
+    widths = [x.dim if isinstance(x, _ffi.Bank) else x.shape[1] for x in ops]
+    if widths[0] != widths[1]:
+        raise ValueError("%s: %d values per query row, %d per train row" % (who, widths[0], widths[1]))
+    ctx = next((x.ctx for x in ops if isinstance(x, _ffi.Bank)), None)
+    made, banks = [], []
+    try:
+        for x in ops:
+            if not isinstance(x, _ffi.Bank):
+                x = bank(x, context=ctx)
+                ctx = x.ctx
+                made.append(x)
+            banks.append(x)
+        qb, tb = banks
+        if not qb.has_selfdist:
+            qb.ctx.wide_self_dist_batch([qb], want_host=False)
+        _, dev = _stream_and_device(qb.ctx)
+        cap = qb.n
+        rows = torch.empty((max(cap, 1), 3), dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        # (the call runs on the context's stream and returns when it is done: the fresh tensors must be ours by then)
+        with torch.cuda.device(dev):
+            torch.cuda.current_stream().synchronize()
+        m = qb.ctx.wide_match_accepted_dev(qb, tb, float(tau), rows.data_ptr(), count.data_ptr(), cap)
+        return rows[:min(m, cap)], count
+    finally:
+        for b in made:
+            b.close()
+
+
 class Collection(object):
     """A train collection fed from CUDA tensors (module docstring).  The library's collection is made with the first call
     that needs it, on ``context`` or the default context of the first tensor's device."""
@@ -764,6 +822,41 @@ class Collection(object):
             coll.wide_mutual_ratio_each_dev(qb, float(tau), bool(symmetric), offsets.data_ptr(), rows.data_ptr() if cap else 0, cap,
                                             consumer_stream=stream)
             return offsets, rows
+        finally:
+            for b in made:
+                b.close()
+
+    def wide_fast_match_each(self, q, tau, cap=None):
+        """``fast_match_each`` on a WIDE collection (``add_wide``): Fast-Match's accepted-match test of a wide query inside
+        every image separately, left on the device -- ``(rows int32 [n_images, cap, 3] = (query, row inside the image, float32
+        distance bits), counts int64 [n_images] = min(accepted, cap))``, image i equal to ``wide_fast_match(q, image_i, tau)``;
+        ``cap`` defaults to the query's rows.  ``q``: a wide ``Bank`` or a CUDA tensor [nq, dim] of float32 / float16 /
+        bfloat16; self distances it does not carry are computed on the device (``fm_wide_self_dist_batch``).  Enqueued, no host
+        wait.  ``ValueError`` before the library is touched for a collection that is not wide."""
+        import torch
+        if not self._wide:
+            raise ValueError("Collection.wide_fast_match_each: the collection is not a wide one (add_wide); "
+                             "fast_match_each / hamming_fast_match_each serve the other kinds")
+        if cap is not None and int(cap) < 0:
+            raise ValueError("cap must not be negative")
+        x = _wide_operand("Collection.wide_fast_match_each", q)
+        made = []
+        qb = x
+        if not isinstance(x, _ffi.Bank):
+            qb = bank(x, context=self._context)
+            made.append(qb)
+        try:
+            coll = self._collection(qb.ctx)
+            if not qb.has_selfdist:
+                qb.ctx.wide_self_dist_batch([qb], want_host=False)
+            ni = coll.info()[0]
+            cap = qb.n if cap is None else int(cap)
+            stream, dev = _stream_and_device(qb.ctx)
+            rows = torch.empty((ni, max(cap, 0), 3), dtype=torch.int32, device=dev)
+            counts = torch.zeros(ni, dtype=torch.int64, device=dev)
+            coll.wide_match_accepted_each_dev(qb, float(tau), rows.data_ptr() if rows.numel() else 0, counts.data_ptr() if ni else 0,
+                                              cap, consumer_stream=stream)
+            return rows, counts
         finally:
             for b in made:
                 b.close()

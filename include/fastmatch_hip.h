@@ -64,7 +64,9 @@ typedef struct fm_bank fm_bank;
  * fm_collection_wide_knn2_each, fm_collection_wide_mutual_ratio_each, fm_collection_wide_mutual_ratio_each_dev; still
  * revision 12, additions only -- fm_hamming_self_dist, fm_hamming_self_dist_batch, fm_hamming_set_selfdist,
  * fm_hamming_match_ratio, fm_hamming_match_accepted, fm_hamming_match_accepted_dev,
- * fm_collection_hamming_match_accepted_each, fm_collection_hamming_match_accepted_each_dev).  A binding
+ * fm_collection_hamming_match_accepted_each, fm_collection_hamming_match_accepted_each_dev; still revision 12, additions
+ * only -- fm_wide_self_dist, fm_wide_self_dist_batch, fm_wide_set_selfdist, fm_wide_match_ratio, fm_wide_match_accepted,
+ * fm_wide_match_accepted_dev, fm_collection_wide_match_accepted_each, fm_collection_wide_match_accepted_each_dev).  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.              */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -248,7 +250,10 @@ int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t
  * "wide", before any kernel reads it.  Not built for wide float banks: fm_knn / fm_knn_dev with k >= 3, fm_radius_match(_dev),
  * fm_self_dist(_batch), fm_bank_set_selfdist, fm_match_ratio, fm_match_accepted*, fm_xcheck1_keys*, fm_xcheck1_batched,
  * fm_knn_masked(_dev), fm_bank_refill_u8_async, fm_bank_append_*, fm_expand_create, and every fm_collection_* call -- a wide
- * query bank, and fm_collection_add_f32 / fm_collection_add_dev with more than 128 values per row.
+ * query bank, and fm_collection_add_f32 / fm_collection_add_dev with more than 128 values per row.  (Fast-Match's self-distance
+ * test on wide banks comes under names of its own, "Wide Fast-Match" below: fm_wide_self_dist(_batch), fm_wide_set_selfdist,
+ * fm_wide_match_ratio, fm_wide_match_accepted(_dev), fm_collection_wide_match_accepted_each(_dev); the L2-named calls of this
+ * list keep refusing.)
  * Wide COLLECTIONS: wide images enter a collection through entry points of their own, fm_collection_add_wide (host float32
  * rows) and fm_collection_add_wide_dev (device rows of FM_DT_F32 / FM_DT_F16 / FM_DT_BF16, widened exactly; source, pitch,
  * alignment, ordering and synchronisation rules are fm_collection_add_dev's).  129 <= dim <= 256; dim <= 128 is FM_EINVAL (such
@@ -430,6 +435,65 @@ int fm_hamming_match_accepted(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, d
                               int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted);
 int fm_hamming_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                                   int32_t* d_rows /*device [cap][3]*/, int64_t* d_count /*device*/, int64_t* n_accepted);
+
+/* ---- Wide Fast-Match: the self-distance test on wide float banks ---------------------------------------------------------
+ * Fast-Match's accepted-match test -- dist(q, t) / selfdist(q) < tau on the cross-checked 1-NN -- for wide float descriptors
+ * (FM_BANK_F32W, 129 .. 256 values per row, K14).  fm_self_dist(_batch), fm_bank_set_selfdist, fm_match_ratio,
+ * fm_match_accepted* and fm_collection_match_accepted_each(_dev) keep refusing wide banks; the calls below, with the argument
+ * lists of their L2 namesakes, are the ones that serve them.
+ *   selfdist[i] = (double) min over j != i of dist(i, j), dist being K14's exact chain -- sqrtf(s), s = fmaf(v_k, v_k, s),
+ *     k ascending over the real dim; the comparison is strict <, starting from +inf, so a NaN or +inf distance never becomes the
+ *     minimum: fm_self_dist's float32-route definition at the wider row.  +inf for a bank of one row and for a row that holds
+ *     a NaN (or an infinite value); 0 for a row that has an exact duplicate.  For banks whose values are all finite it equals
+ *     the second column of fm_knn2(b, b), the value only.
+ *   The cross-check is fm_xcheck1's wide contract: strict <, the lowest index wins a tie, NaN never beats anything.
+ *   ratio = (double)dist / selfdist[q] in float64; a row is accepted iff ratio < tau.  So a query row with a duplicate
+ *     (selfdist 0) is never accepted -- d / 0 = +inf for d > 0 and 0 / 0 = NaN, neither is < tau -- and in a bank of one query
+ *     row (selfdist +inf) the ratio is 0, accepted for every tau > 0.  There is no ratio cut.
+ *   fm_wide_self_dist: synchronous, as fm_self_dist.  fm_wide_self_dist_batch: as fm_self_dist_batch -- the values are attached
+ *     to every bank on the device; with out NULL (or every out[i] NULL) the call only enqueues; a bank listed twice is
+ *     FM_EINVAL.  It runs one sweep per bank, enqueued back to back: separate banks do not share a stack, so the table forms
+ *     of the wide kernels do not apply.  fm_wide_set_selfdist attaches the caller's values (fm_bank_set_selfdist's rules).
+ *   fm_wide_match_ratio / fm_wide_match_accepted / fm_wide_match_accepted_dev: outputs, compaction order (ascending query
+ *     index), cap and n_accepted / n_pass are those of fm_match_ratio / fm_match_accepted / fm_match_accepted_dev, word for word.
+ *   fm_collection_wide_match_accepted_each(_dev), on a wide collection (fm_collection_add_wide): slot i equals, row by row and
+ *     bit for bit, fm_wide_match_accepted(q, B_i, tau, cap), B_i being a bank made by fm_bank_create_f32 from image i's values.
+ *     The output layouts, cap, d_counts / h_counts, the chunking under "coll_ws_bytes" and the _dev stream rules are
+ *     fm_collection_match_accepted_each(_dev)'s; an empty image keeps its slot and accepts nothing.
+ * Kernels (wide_f32.hip): a SELF form of K14's fp16 filter, of its rescoring and of its exact kernel -- one sweep of the bank
+ * over itself with the diagonal candidate dropped by INDEX, in the one 16-row tile per block of output rows that holds it
+ * (a scalar branch sends every other tile to an unmasked copy of the tile's tail), before it can enter the filter's bound: its score is the row's maximum, and in
+ * the bound it would shut every real neighbour out.  The filter's margin is unchanged, because the diagonal leaves by index
+ * and not by value.  Padding rows stay excluded by index.  "f32_filter" and "f32_nsplit" choose the kernel as for a wide bank
+ * pair (n * n in the place of nq * nt) and never change a result; fm_f32_filter_stats counts the self sweeps' filter launches
+ * and whole-call fallbacks; the cliff described under K14 holds for a self sweep too (a cluster of more than ~1000 exact
+ * duplicates overflows the record list and the exact kernel redoes the sweep).  The match calls run the cross-check's reverse
+ * top-1 sweep of a wide pair, then the election, ratio test and compaction of the L2 calls.  The collection forms use the
+ * table forms of the wide kernels with an operand outside the stack, top-1 and reverse slots alone (output rows = the rows of
+ * image i, reduced rows = q): the non-empty images of a chunk lie side by side in one output-row space and run through ONE
+ * filter launch, ONE rescoring launch and ONE guarded exact launch -- a chunk whose images hold more than 2^18 rows together
+ * is swept in groups of that size, which bounds the record list at 2^26 records -- then a segmented election (every image
+ * row's key scatter-mins into qbest[image][q]), the float64 ratio test against q's self distances and the ordered
+ * compaction of fm_collection_match_accepted_each.  "f32_filter" chooses per group as it does per chunk for the match graph
+ * (1: the filter from nq * rows >= 4e6), and fm_f32_filter_stats counts one launch per filtered group and one fallback per
+ * group redone.
+ * Errors, in this order: NULL handles (and, for the collection forms, a collection of another context): FM_EINVAL; a bank or a
+ * collection that is not wide (FM_BANK_F32W): FM_EINVAL, the message names the L2 or the Hamming call that serves it; dims
+ * that differ: FM_EINVAL; a query bank with rows but without self distances: FM_EINVAL ("no self distances"); cap < 0 and NULL
+ * outputs as in the L2 forms.  Empty banks and empty collections are valid.  fm_stats counts n * n pairs for a self sweep and
+ * nq * nt for a match.
+ * Not built: a triangular sweep (every tile once, for both directions); the async / batch / sharded-key forms
+ * (fm_match_accepted_async, _batch, _dev_async, _dev_batch, fm_xcheck1_keys*) for wide banks; fm_expand_* on wide banks; wide
+ * radiusMatch, masks, k >= 3; a shared launch for fm_wide_self_dist_batch.                                               */
+int fm_wide_self_dist(fm_ctx* ctx, const fm_bank* bank, double* selfdist /*[n]*/);
+int fm_wide_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks, double* const* out /*NULL, or [n] of NULL / [n_i]*/);
+int fm_wide_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* selfdist /*[n]*/);
+int fm_wide_match_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t* tidx /*[nq]*/,
+                        float* dist /*[nq]*/, double* ratio /*[nq] or NULL*/, uint8_t* pass /*[nq] or NULL*/, int64_t* n_pass);
+int fm_wide_match_accepted(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
+                           int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted);
+int fm_wide_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
+                               int32_t* d_rows /*device [cap][3]*/, int64_t* d_count /*device*/, int64_t* n_accepted);
 
 /* ---- train collections: one query against many images ------------------------------------------------------------------
  * cv2.BFMatcher.add([d1, d2, ...]) / train() / clear() and then match(query) / knnMatch(query, k) against ALL added images,
@@ -674,6 +738,13 @@ int  fm_collection_hamming_match_accepted_each(fm_ctx* ctx, fm_collection* coll,
 int  fm_collection_hamming_match_accepted_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
                                                    int32_t* d_rows /*device [n_images][cap][3]*/, int64_t* d_counts /*device [n_images]*/,
                                                    int64_t* h_counts /*host [n_images] or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+/* "Wide Fast-Match" above: the two calls on a wide collection and a wide query bank that carries wide self distances */
+int  fm_collection_wide_match_accepted_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
+                                            int32_t* qidx, int32_t* tidx, float* dist, double* ratio /* each [n_images][cap] */,
+                                            int64_t* n_accepted /*[n_images]: the full count per image*/);
+int  fm_collection_wide_match_accepted_each_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
+                                                int32_t* d_rows /*device [n_images][cap][3]*/, int64_t* d_counts /*device [n_images]*/,
+                                                int64_t* h_counts /*host [n_images] or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 int  fm_collection_xcheck1_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, float max_dist,
                                 int32_t* tidx /*[n_images][nq] or NULL*/, float* dist /*[n_images][nq] or NULL*/,
                                 int64_t* n_matched /*[n_images] or NULL*/);
