@@ -189,6 +189,10 @@ SYMBOLS = {
     "fm_hamming_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
     "fm_collection_hamming_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
     "fm_collection_hamming_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    "fm_wide_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_wide_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    "fm_collection_wide_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_collection_wide_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
     # Hamming Fast-Match: the self-distance test on binary banks (csrc/hamming.hip, ham_self_kernel)
     "fm_hamming_self_dist": (_INT, [_P, _P, _P]),
     "fm_hamming_self_dist_batch": (_INT, [_P, ctypes.c_int32, _P, _P]),
@@ -647,6 +651,19 @@ class Collection(object):
         (``fm_collection_hamming_radius_match_dev``); arguments as ``radius_match_dev``."""
         return self.radius_match_dev(q, radius_ptr, radius_all, cap, offsets_ptr, img_ptr, idx_ptr, dist_ptr, want_total,
                                      consumer_stream, _name="fm_collection_hamming_radius_match_dev")
+
+    def wide_radius_match(self, q, r):
+        """``fm_collection_wide_radius_match``: ``radius_match`` of a wide float query bank (129 .. 256 values per row) against
+        a wide collection (``add_wide``) -- every row of the stacked images with K14's distance < r, lists ascending
+        (distance, image, row inside the image).  Arguments and return value as ``radius_match``."""
+        return self.radius_match(q, r, _name="fm_collection_wide_radius_match")
+
+    def wide_radius_match_dev(self, q, radius_ptr, radius_all, cap, offsets_ptr, img_ptr, idx_ptr, dist_ptr, want_total=True,
+                              consumer_stream=None):
+        """``wide_radius_match`` with the radii read from and the lists left in device memory
+        (``fm_collection_wide_radius_match_dev``); arguments as ``radius_match_dev``."""
+        return self.radius_match_dev(q, radius_ptr, radius_all, cap, offsets_ptr, img_ptr, idx_ptr, dist_ptr, want_total,
+                                     consumer_stream, _name="fm_collection_wide_radius_match_dev")
 
     def radius_match_dev(self, q, radius_ptr, radius_all, cap, offsets_ptr, img_ptr, idx_ptr, dist_ptr, want_total=True,
                          consumer_stream=None, _name="fm_collection_radius_match_dev"):
@@ -1295,6 +1312,13 @@ class Context(object):
         return self.radius_match_dev(q, t, radius_ptr, radius_all, cap, offsets_ptr, idx_ptr, dist_ptr, want_total, consumer_stream,
                                      _name="fm_hamming_radius_match_dev")
 
+    def wide_radius_match_dev(self, q, t, radius_ptr, radius_all, cap, offsets_ptr, idx_ptr, dist_ptr, want_total=True,
+                              consumer_stream=None):
+        """``wide_radius_match`` with the radii read from and the lists left in device memory
+        (``fm_wide_radius_match_dev``); arguments as ``radius_match_dev``."""
+        return self.radius_match_dev(q, t, radius_ptr, radius_all, cap, offsets_ptr, idx_ptr, dist_ptr, want_total, consumer_stream,
+                                     _name="fm_wide_radius_match_dev")
+
     def bank_gather(self, rows, src_row, float_route=False):
         """The bank ``rows[src_row]`` without building that matrix on the host: the n_src rows are uploaded once and
         gathered by the upload kernel (fm_bank_create_*_gather).  dtype handling as ``bank``."""
@@ -1379,6 +1403,12 @@ class Context(object):
         ``popcount(q XOR t) < r`` per query row (strict, float32: ``h <= H`` is ``r = H + 0.5``), lists ascending (h, index).
         Arguments and return value as ``radius_match``."""
         return self.radius_match(q, t, r, _name="fm_hamming_radius_match")
+
+    def wide_radius_match(self, q, t, r):
+        """``fm_wide_radius_match``: ``radius_match`` on two wide float banks (129 .. 256 values per row) -- every train row
+        whose distance (K14's float32 chain over the real dim) is < r per query row, lists ascending (distance bits, index).
+        Arguments and return value as ``radius_match``."""
+        return self.radius_match(q, t, r, _name="fm_wide_radius_match")
 
     def radius_match(self, q, t, r, _name="fm_radius_match"):
         """``fm_radius_match``: every train row with distance < r per query row -- cv2's radiusMatch with compactResult

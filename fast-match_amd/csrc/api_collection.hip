@@ -759,7 +759,7 @@ static int coll_refuse_wide(fm_ctx* ctx, const fm_collection* c, const char* who
     return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": a wide collection (fm_collection_add_wide, FM_BANK_F32W) is served by "
                                       "fm_collection_pairs_mutual_ratio(_dev) and, for a wide query bank, by "
                                       "fm_collection_wide_mutual_ratio_each(_dev) / fm_collection_wide_knn2_each / "
-                                      "fm_collection_wide_match_accepted_each(_dev) only");
+                                      "fm_collection_wide_match_accepted_each(_dev) / fm_collection_wide_radius_match(_dev) only");
 }
 
 extern "C" int fm_collection_train(fm_ctx* ctx, fm_collection* c)
@@ -1244,6 +1244,57 @@ extern "C" int fm_collection_hamming_radius_match_dev(fm_ctx* ctx, fm_collection
 {
     return coll_radius(ctx, c, q, d_radius, radius_all, cap, d_offsets, d_img, d_idx, d_dist, n_total, true, consumer_stream,
                        "fm_collection_hamming_radius_match_dev", true);
+}
+
+// Wide radiusMatch against the stacked images of a WIDE collection (radius.hip, the wide route): the stack is the train bank of
+// one sweep, its padding rows masked by index through the stage table fm_collection_train builds for every kind.  The
+// L2-named calls above keep refusing a wide collection (coll_query_check); these are the ones that serve it.  Checks in the
+// header's order: handles, the kinds (coll_query_check refuses wide data and is not asked), the widths, cap and the outputs.
+// The stack's scale and largest scaled squared norm are read by radius_match at this call: a later add may rewrite them.
+static int coll_wide_radius(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const float* radius, float radius_all, int64_t cap, int64_t* offsets,
+                            int32_t* img, int32_t* idx, float* dist, int64_t* n_total, bool dev, void* consumer, const char* who_)
+{
+    const std::string who(who_);
+    int rc = coll_check(ctx, c, who_);
+    if (rc != FM_OK) return rc;
+    if (!q) return fail(ctx, FM_EINVAL, who + ": query bank is NULL");
+    const bool cbin = c->dim != 0 && c->stack.kind == FM_BANK_BIN && !coll_is_wide(c);
+    if (q->kind != FM_BANK_F32W || (!c->rows.empty() && !coll_is_wide(c)))
+        return fail(ctx, FM_EINVAL, who + ": the collection and the query bank must be wide float (fm_collection_add_wide; FM_BANK_F32W: "
+                                          "fm_bank_create_f32 with 129 .. 256 values per row); " +
+                                          ((q->kind == FM_BANK_BIN || cbin) ? "fm_collection_hamming_radius_match is the Hamming call"
+                                                                            : "fm_collection_radius_match is the L2 call"));
+    if (c->dim != 0 && q->dim != c->dim) return fail(ctx, FM_EINVAL, who + ": the query's width differs from the collection's");
+    if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap is negative");
+    if (!offsets) return fail(ctx, FM_EINVAL, who + ": offsets is NULL");
+    if (cap > 0 && (!img || !idx || !dist)) return fail(ctx, FM_EINVAL, who + ": img / idx / dist is NULL with cap > 0");
+    if (dev) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (radius && (rc = check_device_ptr(ctx, radius, who_, "d_radius")) != FM_OK) return rc;
+        if ((rc = check_device_ptr(ctx, offsets, who_, "d_offsets")) != FM_OK) return rc;
+        if (img && (rc = check_device_ptr(ctx, img, who_, "d_img")) != FM_OK) return rc;
+        if (idx && (rc = check_device_ptr(ctx, idx, who_, "d_idx")) != FM_OK) return rc;
+        if (dist && (rc = check_device_ptr(ctx, dist, who_, "d_dist")) != FM_OK) return rc;
+    }
+    if ((rc = fm_collection_train(ctx, c)) != FM_OK) return rc;
+    const CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
+    const RadiusArgs a{who_, radius, radius_all, cap, offsets, img, idx, dist, n_total, dev, consumer, &tab, c->total};
+    return radius_match(ctx, *q, c->stack, a);
+}
+
+extern "C" int fm_collection_wide_radius_match(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const float* radius, float radius_all,
+                                               int64_t cap, int64_t* offsets, int32_t* img, int32_t* idx, float* dist, int64_t* n_total)
+{
+    return coll_wide_radius(ctx, c, q, radius, radius_all, cap, offsets, img, idx, dist, n_total, false, FM_NO_STREAM,
+                            "fm_collection_wide_radius_match");
+}
+
+extern "C" int fm_collection_wide_radius_match_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const float* d_radius, float radius_all,
+                                                   int64_t cap, int64_t* d_offsets, int32_t* d_img, int32_t* d_idx, float* d_dist,
+                                                   int64_t* n_total, void* consumer_stream)
+{
+    return coll_wide_radius(ctx, c, q, d_radius, radius_all, cap, d_offsets, d_img, d_idx, d_dist, n_total, true, consumer_stream,
+                            "fm_collection_wide_radius_match_dev");
 }
 
 // The per-image 2-NN lists on the device: d_idx / d_dist [n_images][nq][2].  Up to "batch_group" images per launch of the

@@ -962,6 +962,52 @@ extern "C" int fm_hamming_radius_match_dev(fm_ctx* ctx, const fm_bank* q, const 
     return radius_match(ctx, *q, *t, a);
 }
 
+// Wide radiusMatch (radius.hip, the wide route): fm_radius_match's contract with K14's distance on two wide float banks.  The
+// L2-named calls above keep refusing wide banks; these are the entry points that serve them.  Checks in the header's order:
+// handles, the kinds (even of an empty bank), the dims, cap and the output pointers.
+static int wide_radius_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int64_t cap, const void* offsets, const void* idx, const void* dist,
+                             const char* who, const char* pre)
+{
+    if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
+    if (!q || !t) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
+    for (const fm_bank* b : {q, t})
+        if (b->kind != FM_BANK_F32W)
+            return fail(ctx, FM_EINVAL, std::string(who) + ": both banks must be wide float (FM_BANK_F32W: fm_bank_create_f32 with 129 .. 256 "
+                                        "values per row); " + (b->kind == FM_BANK_BIN ? "fm_hamming_radius_match is the Hamming call"
+                                                                                      : "fm_radius_match is the L2 call"));
+    if (q->dim != t->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": query/train dim mismatch");
+    if (cap < 0) return fail(ctx, FM_EINVAL, std::string(who) + ": cap is negative");
+    if (!offsets) return fail(ctx, FM_EINVAL, std::string(who) + ": " + pre + "offsets is NULL");
+    if (cap > 0 && (!idx || !dist)) return fail(ctx, FM_EINVAL, std::string(who) + ": " + pre + "idx / " + pre + "dist is NULL with cap > 0");
+    return FM_OK;
+}
+
+extern "C" int fm_wide_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* radius, float radius_all, int64_t cap,
+                                    int64_t* offsets, int32_t* idx, float* dist, int64_t* n_total)
+{
+    const char* who = "fm_wide_radius_match";
+    int rc = wide_radius_check(ctx, q, t, cap, offsets, idx, dist, who, "");
+    if (rc != FM_OK) return rc;
+    const RadiusArgs a{who, radius, radius_all, cap, offsets, nullptr, idx, dist, n_total, false, FM_NO_STREAM, nullptr, 0};
+    return radius_match(ctx, *q, *t, a);
+}
+
+extern "C" int fm_wide_radius_match_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* d_radius, float radius_all,
+                                        int64_t cap, int64_t* d_offsets, int32_t* d_idx, float* d_dist, int64_t* n_total,
+                                        void* consumer_stream)
+{
+    const char* who = "fm_wide_radius_match_dev";
+    int rc = wide_radius_check(ctx, q, t, cap, d_offsets, d_idx, d_dist, who, "d_");
+    if (rc != FM_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (d_radius && (rc = check_device_ptr(ctx, d_radius, who, "d_radius")) != FM_OK) return rc;
+    if ((rc = check_device_ptr(ctx, d_offsets, who, "d_offsets")) != FM_OK) return rc;
+    if (d_idx && (rc = check_device_ptr(ctx, d_idx, who, "d_idx")) != FM_OK) return rc;
+    if (d_dist && (rc = check_device_ptr(ctx, d_dist, who, "d_dist")) != FM_OK) return rc;
+    const RadiusArgs a{who, d_radius, radius_all, cap, d_offsets, nullptr, d_idx, d_dist, n_total, true, consumer_stream, nullptr, 0};
+    return radius_match(ctx, *q, *t, a);
+}
+
 // Classic Ratio-Match up to the compaction, in ws_out: 2-NN lists | per-q tidx, dist, ratio, pass | block counts, count word |
 // `extra` bytes of the caller's own (16-byte aligned, at `rest`).  knn2_device, then lowe_kernel.
 struct LoweWs {

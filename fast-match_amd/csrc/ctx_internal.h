@@ -194,7 +194,9 @@ void fill_round_f32(fm::RoundF32* r, const fm::Bank& q, const fm::Bank& t);
 // One expansion round's cross-checked 1-NN on the whole GPU (K7's delegated cross-check, api_match.hip).
 // K10: radiusMatch (radius.hip); arguments checked by the entry points -- fm_radius_match(_dev) (api_match.hip),
 // fm_collection_radius_match(_dev) (api_collection.hip), and their Hamming forms fm_hamming_radius_match(_dev),
-// fm_collection_hamming_radius_match(_dev): two binary banks take radius_match's Hamming route.
+// fm_collection_hamming_radius_match(_dev): two binary banks take radius_match's Hamming route; and the wide forms
+// fm_wide_radius_match(_dev), fm_collection_wide_radius_match(_dev): two wide float banks (or a wide query bank and a wide
+// collection's stack) take its wide route.
 struct CollTab;      // coll_tab.h
 struct RadiusArgs {
     const char* who;

@@ -37,6 +37,44 @@
 // Geometry of the sweeps: a workgroup = 4 waves, a wave = 4 blocks of 16 query rows (the MFMA's N, held in VGPRs for the
 // whole sweep), the train rows (M) stream through LDS 64 at a time, rows padded by 16 bytes against bank conflicts.
 // grid = (query groups of 256 rows, splits of the train range).
+//
+// Wide route (fm_wide_radius_match and kin: two FM_BANK_F32W banks, or a wide query bank against a wide collection's stack;
+// K14's planes, wide_f32.hip): the float32 route at 129 .. 256 values per row.  dist is K14's chain over the real dim.
+//   radius_wide_limits_kernel  the threshold on A, with K14's margin (derivation below).
+//   radius_wide_kernel<FILL, KS>  the sweep: v_mfma_f32_16x16x32_f16 on the banks' wrowsh planes (pitch 256 halves, zero padded
+//                         beyond dim: a padding product adds nothing), KS = ceil(dim / 32) = 5 .. 8 K steps, the epilogue
+//                         radius_f16_kernel's -- A = |q'|^2 cq + |t'|^2 ct - 2 acc, a hit is A <= thr[q] -- and r_emit's keys.
+//   radius_wide_rescore_kernel  the exact chain over wrows (pitch 256), to dim rounded up to 4: a padding term is
+//                         fmaf(+0, +0, s) = s; keep = d < rr[q].
+//   Everything else -- scan, chunks, sort tiers, compaction, the device forms' offsets -- is the float32 route's, unchanged.
+// Geometry.  Four blocks of 16 query rows per wave as the B operand would be 4 * KS * 4 = 128 VGPRs at KS = 8, before a single
+//   streamed row is held: a wave keeps TWO blocks (K14's choice: 64 VGPRs at 256-D), a workgroup of 4 waves 128 query rows,
+//   grid = (query groups of 128 rows, splits of the train range).  The streamed rows come STRAIGHT FROM MEMORY, one 16-row
+//   tile ahead in registers (2 * KS * 4 = 64 more VGPRs at KS = 8), as wide_filter_body reads them, and not through LDS:
+//   a 64-row stage at a conflict-free pitch of 2 * 256 + 16 bytes is 33 KiB, so a double buffer (66 KiB) does not fit in
+//   64 KiB of static LDS, and a single buffer puts two barriers and the whole load latency into every stage.  From memory the
+//   four waves of a workgroup read the same tiles (three of four reads hit the cache), a lane's 16-byte pieces are its own MFMA
+//   operands (no transpose, no bank conflict to pad against), there is no barrier, and the load of tile t + 1 is in flight
+//   under the 2 * KS MFMAs and the epilogue of tile t.  This is the loop K14's filter already runs at these widths.
+//   A split is whole 64-row stages (four tiles: r_emit's 16 candidates per lane); rows are read up to the stage's end, which
+//   lies inside the bank's padded rows (n_pad is a multiple of 128).  Padding is masked by index exactly as on the float32
+//   route: r_real_end / st_real for a collection's stack, row < nt for a bank.  Wide banks do not grow: no gap rows.
+// Margin, in the accumulator's (d2) units 2^(kq + kt); q' and t' are the scaled rows.  K14's error terms (wide_f32.hip) are in
+//   score units s = q'.t' - |t'|^2 / 2, and d2 = |q'|^2 - 2 s: they double.
+//   * fp16 operand rounding: <= 2^-11 (1 + 2^-12)(|q'|^2 + |t'|^2) on the dot product, whatever the number of terms, so
+//     <= 2^-10 (1 + 2^-12)(...) on A;
+//   * the matrix core's float32 accumulation of n <= 256 exact fp16 products: <= n 2^-24 sum |products| <= 2^-16 |q'||t'| on
+//     the dot product, <= 2^-16 (|q'|^2 + |t'|^2) on A;
+//   * the norms (float64 sums of the unrounded scaled values, rounded to float32 once), their scaling by exact powers of two and the
+//     epilogue's two float32 operations: a few 2^-24 (|q'|^2 + |t'|^2).
+//   Together |A - d2_real| <= 2^-10 (1 + 2^-4)(|q'|^2 + max |t'|^2).  The exact chain's d2 is within n 2^-24 d2 <=
+//   2^-15 (|q'|^2 + |t'|^2) of the real one (d2 <= 2 (|q'|^2 + |t'|^2)), and sqrtf(d2) < r implies d2 < r^2 (1 + 2^-22).  So a row the
+//   exact chain keeps has A <= r^2 (1 + 2^-22) + (1 + 2^-4 + 2^-5) 2^-10 (...) = r^2 (...) + 1.094 * 2^-10 (...), inside
+//   T = (r^2 unit + M)(1 + 2^-20), M = 1.25 * 2^-10 (|q'|^2 cq + nm_max ct): K14's constant, not K8's 1.1 -- the accumulation
+//   terms grow with the number of products and are twice as large at 256 values.
+//   The `all` path (every pair a candidate, the rescoring decides): a value that is not finite on either side, scale exponents
+//   more than 8 apart (K14's rule), or a bank whose scale is above 2^72 (largest magnitude below 2^-59: filter_usable's value
+//   window -- the exact chain's underflow error is absolute, 256 * 2^-150, and must stay inside the slack of M).
 #include "ctx_internal.h"
 #include "coll_tab.h"
 #include "ham_radius.h"
@@ -61,6 +99,10 @@ constexpr int kRRowH = 2 * kDim + 16;      // ... fp16 rows
 constexpr int kRSortThread = 16;
 constexpr int kRSortLds = 2048;
 constexpr float kREps = 1.1f / 1024.0f;    // K8's margin: |A - D| <= eps (|c|^2 + max |m|^2) (filter_f16.hip)
+constexpr int kRWNB = 2;                   // wide route: blocks of 16 query rows per wave
+constexpr int kRWQPerWG = 16 * kRWNB * kRWaves;
+constexpr float kRWEps = 1.25f / 1024.0f;  // wide route: K14's margin (file comment)
+constexpr int kRWScaleMax = 72;            // wide route: the largest bank scale the sweep takes (filter_f16.hip: kFScaleMax)
 
 struct RSweep {
     const int8_t* qrows; const int32_t* qnorm;      // integer route (rows of this launch's first query row on)
@@ -82,6 +124,8 @@ struct RSweep {
                                // masked by index, never by value); null: a plain bank, padding only behind row nt
     const unsigned long long* real;   // a plain bank that grew by appends and has padding rows below nt: its real-row bitmap
                                       // (Bank::real, one word per 64-row stage); null: none
+    int wks;                   // wide route: MFMA K steps per row, 5 .. 8 (0: another route); the float32 route's fields then
+                               // hold the wide planes (wrowsh at pitch kWideDim, normf)
 };
 
 // Grown train banks: the 16 candidates of a lane in the stage at `base` (tile tt, register r -> bit 4 tt + r, train row
@@ -293,6 +337,104 @@ void radius_f16_kernel(RSweep p)
     }
 }
 
+// Wide route (file comment): the query rows of a wave -- two blocks of 16 -- are the B operand, in registers for the whole
+// sweep; the train rows' fp16 plane comes straight from memory, one 16-row tile ahead (no LDS, no barrier).  A stage is four
+// tiles: the 16 candidates a lane has per block in 64 rows go through r_emit like the float32 route's.  Every tile of a stage
+// is read, also behind the split's end: the stage ends inside the bank's padded rows (base % 64 == 0, n_pad % 128 == 0), and
+// what lies behind t1 or behind a collection's real rows is masked by index.
+template <bool FILL, int KS>
+__global__ __launch_bounds__(256)
+void radius_wide_kernel(RSweep p)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
+    const int qw = blockIdx.x * kRWQPerWG + wave * 16 * kRWNB;
+    const bool all = p.all != 0;
+    rv8h bh[kRWNB][KS];
+    float qn[kRWNB], thr[kRWNB];
+    unsigned count[kRWNB];
+#pragma unroll
+    for (int b = 0; b < kRWNB; ++b) {
+        const int q = qw + 16 * b + j;
+        const bool live = q < p.nq;      // (a chunk may start on any row: the rows behind nq need not lie inside the bank)
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const v4i h = (live && !all) ? *(const v4i*)(p.qrowsh + (size_t)q * kWideDim + 32 * s + 8 * g) : v4i{0, 0, 0, 0};
+            bh[b][s] = __builtin_bit_cast(rv8h, h);
+        }
+        qn[b] = (live && !all) ? p.qnormf[q] * p.cq : 0.f;
+        thr[b] = live ? p.thr[q] : -INFINITY;
+        count[b] = 0;
+    }
+    unsigned hi[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) hi[c] = 0u;
+    const int t0 = blockIdx.y * p.per, t1 = min(p.nt, t0 + p.per);
+    rv8h an[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) an[s] = rv8h{0, 0, 0, 0, 0, 0, 0, 0};
+    if (!all && t0 < t1) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+            an[s] = __builtin_bit_cast(rv8h, *(const v4i*)(p.trowsh + (size_t)(t0 + j) * kWideDim + 32 * s + 8 * g));
+    }
+    for (int base = t0; base < t1; base += kRStage) {
+        const int rowlim = r_real_end(p, base, t1) - base - 4 * g;   // register r of tile tt is a real train row iff 16 tt + r < rowlim
+        const bool more = base + kRStage < t1;
+        unsigned mask[kRWNB];
+#pragma unroll
+        for (int b = 0; b < kRWNB; ++b) mask[b] = 0;
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+            rv8h a[KS];
+            rv4f tn = rv4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < KS; ++s) a[s] = an[s];
+            if (!all) {
+                if (tt < 3 || more) {       // the next tile: of this stage, or the first of the next one
+#pragma unroll
+                    for (int s = 0; s < KS; ++s)
+                        an[s] = __builtin_bit_cast(rv8h, *(const v4i*)(p.trowsh + (size_t)(base + 16 * (tt + 1) + j) * kWideDim + 32 * s + 8 * g));
+                }
+                tn = *(const rv4f*)(p.tnormf + base + 16 * tt + 4 * g) * p.ct;
+            }
+#pragma unroll
+            for (int b = 0; b < kRWNB; ++b) {
+                rv4f acc = rv4f{0.f, 0.f, 0.f, 0.f};
+                if (!all) {
+#pragma unroll
+                    for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[s], bh[b][s], acc, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float A = qn[b] + tn[r] - 2.f * acc[r];     // (all: 0, against a threshold of +-inf)
+                    mask[b] |= (A <= thr[b] && 16 * tt + r < rowlim) ? (1u << (4 * tt + r)) : 0u;
+                }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < kRWNB; ++b) {
+            const int q = qw + 16 * b + j;
+            if constexpr (FILL) {
+#pragma unroll
+                for (int c = 0; c < 16; ++c) hi[c] = (unsigned)q;
+                r_emit(p, mask[b], hi, q, q < p.nq, base, lane);
+            } else {
+                count[b] += __popc(mask[b]);
+            }
+        }
+    }
+    if constexpr (!FILL) {
+#pragma unroll
+        for (int b = 0; b < kRWNB; ++b) {
+            unsigned c = count[b];
+            c += __shfl_xor(c, 16);
+            c += __shfl_xor(c, 32);
+            const int q = qw + 16 * b + j;
+            if (g == 0 && q < p.nq && c) atomicAdd(&p.cnt[q], c);
+        }
+    }
+}
+
 // Hamming route (binary banks, K11's operands: hamming.hip): every bit is one FP4 value, +1 or -1, so the dot product of two
 // encoded rows is W - 2 h, exact in the f32 accumulator; a hit is dot >= thr (ham_radius.h), h = (W - dot) / 2.  K11's loop:
 // 128-row stages through two LDS buffers, the next stage prefetched into registers, one barrier per stage, row pitch RB + 16;
@@ -480,6 +622,55 @@ void radius_rescore_kernel(unsigned long long* __restrict__ keys, int64_t n, con
     if (keep) atomicAdd(&fcnt[q], 1u);
 }
 
+// Wide route: the radius and the sweep's threshold per query row, T = (r^2 unit + M)(1 + 2^-20) with K14's margin
+// M = 1.25 * 2^-10 (|q'|^2 cq + nm_max ct) (file comment); `all`, or r = +inf: every pair is a candidate.
+__global__ void radius_wide_limits_kernel(const float* __restrict__ radius, float radius_all, int nq, int all,
+                                          const float* __restrict__ qnormf, float cq, double unit, float nt_max,
+                                          float* __restrict__ thr, float* __restrict__ rr)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    const float r = radius ? radius[i] : radius_all;
+    rr[i] = r;
+    float T;
+    if (!(r > 0.f)) T = -INFINITY;
+    else if (all || __builtin_isinf(r)) T = INFINITY;
+    else {
+        const double r2 = (double)r * (double)r * unit;
+        const double M = (double)kRWEps * ((double)qnormf[i] * cq + nt_max);
+        T = (float)((r2 + M) * (1.0 + 1.0 / 1048576.0));    // (+ 2^-20: the roundings of r^2 and of the epilogue's A)
+    }
+    thr[i] = T;
+}
+
+// Wide route: the exact chain for every candidate key (query row << 32 | train row) of the chunk over the float32 rows at
+// pitch kWideDim, k4n = ceil(dim / 4) float4 steps (zero padding past dim: fmaf(+0, +0, s) = s).  A NaN or +inf distance is
+// below no radius.
+__global__ __launch_bounds__(256)
+void radius_wide_rescore_kernel(unsigned long long* __restrict__ keys, int64_t n, const float* __restrict__ qrows,
+                                const float* __restrict__ trows, const float* __restrict__ rr, unsigned* __restrict__ fcnt, int k4n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long k = keys[i];
+    const unsigned q = (unsigned)(k >> 32), t = (unsigned)k;
+    const float4* a = (const float4*)(qrows + (size_t)q * kWideDim);
+    const float4* b = (const float4*)(trows + (size_t)t * kWideDim);
+    float s = 0.f;
+    for (int k4 = 0; k4 < k4n; ++k4) {
+        const float4 x = a[k4], y = b[k4];
+        float v;
+        v = x.x - y.x; s = __builtin_fmaf(v, v, s);
+        v = x.y - y.y; s = __builtin_fmaf(v, v, s);
+        v = x.z - y.z; s = __builtin_fmaf(v, v, s);
+        v = x.w - y.w; s = __builtin_fmaf(v, v, s);
+    }
+    const float d = sqrtf(s);
+    const bool keep = d < rr[q];
+    keys[i] = keep ? (((unsigned long long)__float_as_uint(d) << 32) | t) : ~0ull;
+    if (keep) atomicAdd(&fcnt[q], 1u);
+}
+
 // Segments of at most kRSortThread keys: one thread each, insertion sort.
 __global__ __launch_bounds__(256)
 void radius_sort_thread_kernel(unsigned long long* __restrict__ keys, const int64_t* __restrict__ off, int64_t base, int nrows)
@@ -571,10 +762,10 @@ __global__ void radius_offsets_kernel(const int64_t* __restrict__ rel, int64_t a
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-static int r_splits(int64_t nq, int64_t nt)
+static int r_splits(int64_t nq, int64_t nt, int qper = kRQPerWG)
 {
-    // ~2048 workgroups on the chip, a split of at least 1024 train rows
-    const int64_t qg = (nq + kRQPerWG - 1) / kRQPerWG;
+    // ~2048 workgroups on the chip, a split of at least 1024 train rows (qper: query rows per workgroup)
+    const int64_t qg = (nq + qper - 1) / qper;
     int64_t s = (2048 + qg - 1) / qg;
     if (s > (nt + 1023) / 1024) s = (nt + 1023) / 1024;
     if (s < 1) s = 1;
@@ -615,6 +806,26 @@ static hipError_t r_sweep(const RSweep& base, bool f32, bool fill, int64_t q0, i
         }
         FM_RHAM(1) FM_RHAM(2) FM_RHAM(3) FM_RHAM(4)
 #undef FM_RHAM
+        return hipErrorInvalidValue;
+    }
+    if (p.wks) {
+        // wide route: 128 query rows per workgroup, splits of whole 64-row stages
+        if (!p.all) { p.qrowsh += q0 * kWideDim; p.qnormf += q0; }
+        p.thr += q0;
+        if (fill) p.off += q0;
+        else p.cnt += q0;
+        const int ns = r_splits(nq, p.nt, kRWQPerWG);
+        const int per = (p.nt + ns - 1) / ns;
+        p.per = (per + kRStage - 1) / kRStage * kRStage;
+        const dim3 grid((unsigned)((nq + kRWQPerWG - 1) / kRWQPerWG), (unsigned)ns);
+#define FM_RWIDE(KS_)                                                                                      \
+        if (p.wks == KS_) {                                                                                \
+            if (fill) hipLaunchKernelGGL((radius_wide_kernel<true, KS_>), grid, dim3(256), 0, stream, p);  \
+            else      hipLaunchKernelGGL((radius_wide_kernel<false, KS_>), grid, dim3(256), 0, stream, p); \
+            return hipGetLastError();                                                                      \
+        }
+        FM_RWIDE(5) FM_RWIDE(6) FM_RWIDE(7) FM_RWIDE(8)
+#undef FM_RWIDE
         return hipErrorInvalidValue;
     }
     if (f32) { if (!p.all) { p.qrowsh += q0 * kDim; p.qnormf += q0; } p.thr += q0; }
@@ -708,7 +919,7 @@ static hipError_t r_offsets(fm_ctx* ctx, const int64_t* rel, int64_t add, int64_
     return hipGetLastError();
 }
 
-// The four entry points (RadiusArgs, ctx_internal.h).  t: a plain bank, or (a.tab set) a collection's stack, whose n counts
+// The entry points' one driver (RadiusArgs, ctx_internal.h), by the kind of q: the integer, float32, Hamming or wide route.  t: a plain bank, or (a.tab set) a collection's stack, whose n counts
 // the padding rows behind every image: the sweeps mask them by index, a.real_rows is what the call is accounted with.
 // a.dev: radius / offsets / img / idx / dist are the caller's DEVICE arrays -- the limits kernel reads the radii in place, the
 // offsets are written by a device copy (integer route: the scan) or kernel (float32 route: per chunk), the compaction writes
@@ -741,10 +952,13 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
         return FM_OK;
     }
     if (nt > 0x7fffffff || nq > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, std::string(a.who) + ": more than 2^31 - 1 rows in a bank");
-    const bool f32 = q.kind == FM_BANK_F32;
+    const bool wide = q.kind == FM_BANK_F32W;     // (the wide entry points: both operands wide, of one dim; the float32 route's
+                                                  // path with the wide sweep, limits and rescoring kernels)
+    const bool f32 = q.kind == FM_BANK_F32 || wide;
     const bool ham = q.kind == FM_BANK_BIN;       // (the Hamming entry points: both banks binary, of one width; counts are final,
                                                   // so everything behind the count sweep is the integer route's path)
-    const bool all = f32 && !filter_usable(q, t);
+    const bool all = wide ? !(wide_filter_usable(q, t) && q.kscale <= kRWScaleMax && t.kscale <= kRWScaleMax)
+                          : f32 && !filter_usable(q, t);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::optional<CallScope> cs;          // (the device forms are not accounted in fm_stats)
     if (!dev) cs.emplace(ctx);
@@ -784,6 +998,11 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
     if (ham)
         hipLaunchKernelGGL(radius_ham_limits_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
                            k_rad, a.radius_all, (int)nq, 8 * q.dim, d_thr);
+    else if (wide)
+        // (a collection: the stack's scale and largest scaled squared norm as they are NOW -- a later add may rewrite them)
+        hipLaunchKernelGGL(radius_wide_limits_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
+                           k_rad, a.radius_all, (int)nq, all ? 1 : 0, (const float*)(all ? nullptr : q.normf), cq, unit,
+                           all ? 0.f : t.nm_max * ct, d_thr, d_rr);
     else
         hipLaunchKernelGGL(radius_limits_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
                            k_rad, a.radius_all, (int)nq, f32 ? 1 : 0, all ? 1 : 0,
@@ -792,7 +1011,9 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
 
     RSweep sw{};
     sw.qrows = q.rows8; sw.qnorm = q.norm; sw.trows = t.rows8; sw.tnorm = t.norm;
-    sw.qrowsh = q.rowsh; sw.qnormf = q.normf; sw.trowsh = t.rowsh; sw.tnormf = t.normf;
+    sw.qrowsh = wide ? q.wrowsh : q.rowsh; sw.qnormf = q.normf; sw.trowsh = wide ? t.wrowsh : t.rowsh; sw.tnormf = t.normf;
+    sw.wks = wide ? (q.dim + 31) / 32 : 0;
+    if (wide && !all) ctx->filter_launches += 1;      // (fm_f32_filter_stats: a call that ran the fp16 sweep; `all` runs none)
     sw.q4 = q.rows4; sw.t4 = t.rows4; sw.ks = ham ? q.ksteps : 0; sw.W = 8 * q.dim;
     sw.cq = cq; sw.ct = ct; sw.all = all ? 1 : 0;
     sw.nt = (int)nt; sw.lim = d_lim; sw.thr = d_thr;
@@ -856,7 +1077,13 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
         HIP_TRY(ctx, hipMemsetAsync(d_cur, 0, (size_t)nr * 4, ctx->stream));
         sw.cnt = d_cur; sw.off = d_off; sw.base = c0; sw.keys = keys;
         HIP_TRY(ctx, r_sweep(sw, f32, true, r0, nr, ctx->stream));
-        if (f32) {
+        if (wide) {
+            HIP_TRY(ctx, hipMemsetAsync(d_fcnt, 0, (size_t)(nr + 1) * 4, ctx->stream));
+            hipLaunchKernelGGL(radius_wide_rescore_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ctx->stream, keys, nc,
+                               (const float*)(q.wrows + (size_t)r0 * kWideDim), (const float*)t.wrows, (const float*)(d_rr + r0), d_fcnt,
+                               (q.dim + 3) >> 2);
+            HIP_TRY(ctx, hipGetLastError());
+        } else if (f32) {
             HIP_TRY(ctx, hipMemsetAsync(d_fcnt, 0, (size_t)(nr + 1) * 4, ctx->stream));
             hipLaunchKernelGGL(radius_rescore_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ctx->stream, keys, nc,
                                (const float*)(q.rowsf + (size_t)r0 * kDim), (const float*)t.rowsf, (const float*)(d_rr + r0), d_fcnt,

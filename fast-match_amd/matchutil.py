@@ -475,6 +475,46 @@ def wide_fast_match(dt1, dt2, tau, options={}):
     return [DMatch(int(qidx[j]), int(tidx[j]), dist[j]) for j in range(qidx.shape[0])]
 
 
+def wide_radius_match_arrays(dt1, dt2, maxDistance, options={}):
+    """``cv2.BFMatcher(cv2.NORM_L2).radiusMatch(dt1, dt2, maxDistance)`` on wide float descriptors (129 .. 256 values per row,
+    SuperPoint and its kin) as arrays: ``(offsets int64[nq + 1], idx int32[n], dist float32[n])``; query row i's list is
+    ``idx[offsets[i]:offsets[i + 1]]`` / ``dist[...]``, every train row with ``dist < maxDistance`` (a strict float32
+    compare), ascending by (distance, train index).  ``dt1`` / ``dt2``: float32 / float64 arrays or resident wide banks;
+    ``maxDistance``: a scalar or one radius per query row.  ``ValueError`` before anything is uploaded: another dtype (uint8
+    rows included), dims that differ or lie outside 129 .. 256, a ``mask`` option, a wrong number of radii.
+    (``bf_radius_match`` keeps refusing wide descriptors.)"""
+    q, qw = _wide_operand(dt1, "wide_radius_match")
+    t, tw = _wide_operand(dt2, "wide_radius_match")
+    if qw != tw:
+        raise ValueError("wide_radius_match: %d values per query row, %d per train row" % (qw, tw))
+    if options and options.get("mask") is not None:
+        raise ValueError("wide_radius_match: a mask is not built for radiusMatch")
+    nq = _rows_of(q)
+    if np.ndim(maxDistance) != 0 and np.asarray(maxDistance).reshape(-1).shape[0] != nq:
+        raise ValueError("wide_radius_match: %d radii for %d query rows" % (np.asarray(maxDistance).reshape(-1).shape[0], nq))
+    ctx = _context(options)
+    qb, q_tmp = (q, False) if isinstance(q, _ffi.Bank) else (ctx.bank(q), True)
+    try:
+        tb, t_tmp = (t, False) if isinstance(t, _ffi.Bank) else (ctx.bank(t), True)
+    except Exception:
+        if q_tmp:
+            qb.close()
+        raise
+    try:
+        return ctx.wide_radius_match(qb, tb, maxDistance)
+    finally:
+        if q_tmp:
+            qb.close()
+        if t_tmp:
+            tb.close()
+
+
+def wide_radius_match(dt1, dt2, maxDistance, options={}):
+    """ radiusMatch on wide float descriptors (wide_radius_match_arrays): a list of DMatch lists, one per query row """
+    off, idx, dist = wide_radius_match_arrays(dt1, dt2, maxDistance, options=options)
+    return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
+
+
 class BFMatcher(object):
     """``cv2.BFMatcher(normType, crossCheck)`` with cv2's method names.  With a train argument ``match`` / ``knnMatch`` /
     ``radiusMatch`` are :func:`bf_match` / :func:`bf_radius_match`; without one they run against the TRAIN COLLECTION

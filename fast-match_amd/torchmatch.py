@@ -484,6 +484,36 @@ def wide_fast_match(q, t, tau):
             b.close()
 
 
+def wide_radius_match(q, t, r):
+    """``cv2.BFMatcher.radiusMatch`` on wide float descriptors (129 .. 256 values per row): ``(offsets int64 [nq + 1], idx int32
+    [n], dist float32 [n])`` CUDA tensors, every train row with distance < r per query row, ascending (distance, train index).
+    ``q`` / ``t``: float32 / float16 / bfloat16 CUDA tensors (half and bfloat16 widened exactly) or wide ``Bank``s; ``r``: a
+    scalar, or a float32 CUDA tensor [nq] read in place behind the current stream's work, as in ``radius_match`` (which keeps
+    refusing wide descriptors).  One host wait for the total."""
+    who = "wide_radius_match"
+    ops = [_wide_operand(who, x) for x in (q, t)]
+    widths = [x.dim if isinstance(x, _ffi.Bank) else x.shape[1] for x in ops]
+    if widths[0] != widths[1]:
+        raise ValueError("%s: %d values per query row, %d per train row" % (who, widths[0], widths[1]))
+    nq = ops[0].n if isinstance(ops[0], _ffi.Bank) else ops[0].shape[0]
+    ctx = next((x.ctx for x in ops if isinstance(x, _ffi.Bank)), None)
+    rad, r_all = _radius(r, nq, ctx.device if ctx is not None else ops[0].device.index)
+    made, banks = [], []
+    try:
+        for x in ops:
+            if not isinstance(x, _ffi.Bank):
+                x = bank(x, context=ctx)
+                ctx = x.ctx
+                made.append(x)
+            banks.append(x)
+        qb, tb = banks
+        stream, dev = _stream_and_device(qb.ctx)
+        return _radius_lists(lambda *a, **k: qb.ctx.wide_radius_match_dev(qb, tb, *a, **k), qb.n, rad, r_all, stream, dev, False)
+    finally:
+        for b in made:
+            b.close()
+
+
 class Collection(object):
     """A train collection fed from CUDA tensors (module docstring).  The library's collection is made with the first call
     that needs it, on ``context`` or the default context of the first tensor's device."""
@@ -860,6 +890,28 @@ class Collection(object):
         finally:
             for b in made:
                 b.close()
+
+    def wide_radius_match(self, q, r):
+        """``radius_match`` on a WIDE collection (``add_wide``): every row of the stacked images with distance < r per query
+        row, ``(offsets int64 [nq + 1], img int32 [n], idx int32 [n], dist float32 [n])`` CUDA tensors, ascending (distance,
+        image, row inside the image).  ``q``: a wide ``Bank`` or a CUDA tensor [nq, dim] of float32 / float16 / bfloat16 with
+        129 <= dim <= 256; ``r`` as in the module's ``radius_match``.  One host wait for the total.  ``ValueError`` before the
+        library is touched for a collection that is not wide."""
+        if not self._wide:
+            raise ValueError("Collection.wide_radius_match: the collection is not a wide one (add_wide); "
+                             "radius_match / hamming_radius_match serve the other kinds")
+        x = _wide_operand("Collection.wide_radius_match", q)
+        is_bank = isinstance(x, _ffi.Bank)
+        nq, device = (x.n, x.ctx.device) if is_bank else (x.shape[0], x.device.index)
+        rad, r_all = _radius(r, nq, device if self._context is None else self._context.device)
+        coll = self._collection(x.ctx if is_bank else _ctx_for(x, self._context))
+        qb = x if is_bank else bank(x, context=self._context)
+        try:
+            stream, dev = _stream_and_device(qb.ctx)
+            return _radius_lists(lambda *a, **k: coll.wide_radius_match_dev(qb, *a, **k), qb.n, rad, r_all, stream, dev, True)
+        finally:
+            if not is_bank:
+                qb.close()
 
     def clear(self):
         if self._coll is not None:

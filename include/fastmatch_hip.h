@@ -66,7 +66,9 @@ typedef struct fm_bank fm_bank;
  * fm_hamming_match_ratio, fm_hamming_match_accepted, fm_hamming_match_accepted_dev,
  * fm_collection_hamming_match_accepted_each, fm_collection_hamming_match_accepted_each_dev; still revision 12, additions
  * only -- fm_wide_self_dist, fm_wide_self_dist_batch, fm_wide_set_selfdist, fm_wide_match_ratio, fm_wide_match_accepted,
- * fm_wide_match_accepted_dev, fm_collection_wide_match_accepted_each, fm_collection_wide_match_accepted_each_dev).  A binding
+ * fm_wide_match_accepted_dev, fm_collection_wide_match_accepted_each, fm_collection_wide_match_accepted_each_dev; still
+ * revision 12, additions only -- fm_wide_radius_match, fm_wide_radius_match_dev, fm_collection_wide_radius_match,
+ * fm_collection_wide_radius_match_dev).  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.              */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -253,7 +255,9 @@ int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t
  * query bank, and fm_collection_add_f32 / fm_collection_add_dev with more than 128 values per row.  (Fast-Match's self-distance
  * test on wide banks comes under names of its own, "Wide Fast-Match" below: fm_wide_self_dist(_batch), fm_wide_set_selfdist,
  * fm_wide_match_ratio, fm_wide_match_accepted(_dev), fm_collection_wide_match_accepted_each(_dev); the L2-named calls of this
- * list keep refusing.)
+ * list keep refusing.)  (Radius queries on wide banks come under names of their own as well, "Wide radiusMatch" below:
+ * fm_wide_radius_match(_dev), and fm_collection_wide_radius_match(_dev) for a wide collection; fm_radius_match(_dev) keeps
+ * refusing.)
  * Wide COLLECTIONS: wide images enter a collection through entry points of their own, fm_collection_add_wide (host float32
  * rows) and fm_collection_add_wide_dev (device rows of FM_DT_F32 / FM_DT_F16 / FM_DT_BF16, widened exactly; source, pitch,
  * alignment, ordering and synchronisation rules are fm_collection_add_dev's).  129 <= dim <= 256; dim <= 128 is FM_EINVAL (such
@@ -286,7 +290,9 @@ int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t
  * fm_collection_knn2_each, fm_collection_votes, fm_collection_knn_masked(_dev), fm_collection_radius_match(_dev),
  * fm_collection_match_accepted_each(_dev), fm_collection_xcheck1_each(_dev), fm_collection_mutual_ratio_each(_dev) -- and
  * fm_mask_create_coll: FM_EUNSUPPORTED with a message that says "wide", straight after the NULL-handle checks.  Also not
- * built: k >= 3, LDS staging of the streamed operand, computing a pair's tiles once for both directions.
+ * built: k >= 3, LDS staging of the streamed operand, computing a pair's tiles once for both directions.  (Radius queries
+ * against a wide collection come under names of their own, "Wide radiusMatch" below: fm_collection_wide_radius_match(_dev);
+ * fm_collection_radius_match(_dev) keeps refusing.)
  * Wide QUERIES: a wide query bank is matched against every image of a wide collection, image by image, by entry points of
  * their own -- the calls listed above keep refusing, and their messages name these: fm_collection_wide_knn2_each,
  * fm_collection_wide_mutual_ratio_each and fm_collection_wide_mutual_ratio_each_dev (the localisation pattern: one query image
@@ -320,7 +326,9 @@ int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t
  * and one fallback per chunk redone (the cliff above, per chunk); "f32_nsplit" keeps its meaning.  Out of scope here: the
  * stacked forms on a wide collection (knnMatch over all images, knn2_ratio, votes mode 0), xcheck1_each / match_accepted_each
  * for wide collections, k >= 3, masks, radius queries, sharing one resident copy of the query's B operand across the forward
- * slots of a chunk, LDS staging of the streamed operand, computing an image's tiles once for both directions.            */
+ * slots of a chunk, LDS staging of the streamed operand, computing an image's tiles once for both directions.  (Radius
+ * queries of a wide query bank against the STACKED images of a wide collection now come under a name of their own:
+ * fm_collection_wide_radius_match(_dev), "Wide radiusMatch" below.)                                                      */
 int  fm_bank_destroy(fm_ctx* ctx, fm_bank* bank);
 int  fm_bank_info(const fm_bank* bank, int64_t* n, int* dim, int* kind);
 /* Attach per-row self distances (Metric_Cache.*["distances"], float64, cache.pyx:252,273)
@@ -484,7 +492,8 @@ int fm_hamming_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* 
  * nq * nt for a match.
  * Not built: a triangular sweep (every tile once, for both directions); the async / batch / sharded-key forms
  * (fm_match_accepted_async, _batch, _dev_async, _dev_batch, fm_xcheck1_keys*) for wide banks; fm_expand_* on wide banks; wide
- * radiusMatch, masks, k >= 3; a shared launch for fm_wide_self_dist_batch.                                               */
+ * radiusMatch, masks, k >= 3; a shared launch for fm_wide_self_dist_batch.  (radiusMatch on wide banks has since come under
+ * names of its own: "Wide radiusMatch" below.)                                                                           */
 int fm_wide_self_dist(fm_ctx* ctx, const fm_bank* bank, double* selfdist /*[n]*/);
 int fm_wide_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks, double* const* out /*NULL, or [n] of NULL / [n_i]*/);
 int fm_wide_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* selfdist /*[n]*/);
@@ -494,6 +503,49 @@ int fm_wide_match_accepted(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, doub
                            int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted);
 int fm_wide_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                                int32_t* d_rows /*device [cap][3]*/, int64_t* d_count /*device*/, int64_t* n_accepted);
+
+/* ---- Wide radiusMatch: every neighbour closer than a distance, on wide float banks ---------------------------------------
+ * cv2.BFMatcher(cv2.NORM_L2).radiusMatch for wide float descriptors (FM_BANK_F32W, 129 .. 256 values per row, K14): for
+ * unit-norm learned descriptors "keep every neighbour closer than a fixed distance" (SuperPoint's nn_thresh = 0.7) is the usual
+ * acceptance test.  fm_radius_match(_dev) and fm_collection_radius_match(_dev) keep refusing wide banks and wide collections
+ * (FM_EUNSUPPORTED, a message that says "wide"); the four calls here, with the argument lists of their L2 namesakes word for
+ * word, are the ones that serve them: fm_wide_radius_match, fm_wide_radius_match_dev, fm_collection_wide_radius_match,
+ * fm_collection_wide_radius_match_dev (the collection forms are declared with the collections below, the _dev forms' stream
+ * rules are described with the device entry points).
+ *   fm_radius_match's contract applies word for word, with K14's distance: dist(q, t) = sqrtf(s), s = fmaf(v_k, v_k, s),
+ *   v_k = q_k - t_k in float32, k ascending over the real dim.  r_i = radius[i] (radius != NULL) or radius_all.  Train row j is
+ *   in row i's list iff dist(i, j) < r_i, a strict float32 compare on the bits fm_knn2 returns for a wide pair.  A NaN or +inf
+ *   distance is never listed, not even at r = +inf; r <= 0 or NaN gives an empty list.  A list ascends by (distance bits, train
+ *   index) -- against a collection by (distance bits, image, row).  offsets[0 .. nq], cap, counts only (cap = 0), the longest
+ *   prefix of whole rows and *n_total are fm_radius_match's rules; nq = 0 and nt = 0 are valid.  No option changes a result;
+ *   "radius_ws_bytes" keeps its meaning (24 bytes a candidate, 28 against a collection).
+ *   fm_collection_wide_radius_match(q, coll): fm_wide_radius_match(q, T) for T = the rows of a WIDE collection
+ *   (fm_collection_add_wide) stacked in image order, every entry reported as (img, idx inside the image) --
+ *   fm_collection_radius_match's output rules.  The padding rows behind every image are kept out by INDEX.  The stack's fp16
+ *   scale and largest scaled squared norm are read at the call: a later add may rewrite them.
+ * Kernels (radius.hip, the wide route of K10): a threshold sweep on the matrix cores -- radius_wide_kernel,
+ * v_mfma_f32_16x16x32_f16 on the banks' scaled fp16 planes, ceil(dim / 32) = 5 .. 8 K steps, two blocks of 16 query rows per
+ * wave as the B operand, the train rows streamed from memory one 16-row tile ahead -- run twice (count, scan, fill); a
+ * candidate is a pair with A = |q'|^2 + |t'|^2 - 2 q'.t' <= (r_i^2 + M)(1 + 2^-20) in the accumulator's units, M = 1.25 * 2^-10
+ * (|q'|^2 + max |t'|^2), K14's margin; every candidate is then rescored with the exact chain (radius_wide_rescore_kernel) and
+ * kept iff dist < r_i; K10's segment sort and compaction follow unchanged.  When a value on either side is not finite, when
+ * the two scale exponents differ by more than 8, or when a bank's largest magnitude lies below 2^-59, every pair is a candidate
+ * and the exact chain alone decides: same results.  fm_f32_filter_stats counts one launch per call that ran the fp16 sweep
+ * (none for a call on the all-pairs path); there is no fallback to count.
+ * Errors, in this order: NULL handles, or for the collection forms a collection of another context (FM_EINVAL); a bank or a
+ * collection that is not FM_BANK_F32W (FM_EINVAL, even when it is empty: the wide creators make an empty bank wide; the
+ * message names fm_radius_match or fm_hamming_radius_match as the call that serves it; a collection on which no add has
+ * succeeded is valid and gives all-zero offsets); dims that differ (FM_EINVAL); cap < 0, offsets NULL, or idx / dist (img, for
+ * the collection forms) NULL with cap > 0 (FM_EINVAL); for the _dev forms the device-pointer checks of fm_radius_match_dev.
+ * Accounted in fm_stats like fm_radius_match: the host forms add nq * real rows pairs, the _dev forms are not accounted.
+ * Not built: masks; compactResult = True; one sweep that counts and fills in a single pass; k >= 3 and the stacked knn forms
+ * on a wide collection.                                                                                                  */
+int fm_wide_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* radius /*[nq] or NULL*/,
+                         float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* idx, float* dist,
+                         int64_t* n_total);
+int fm_wide_radius_match_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* d_radius /*device [nq] or NULL*/,
+                             float radius_all, int64_t cap, int64_t* d_offsets /*device [nq+1]*/, int32_t* d_idx, float* d_dist,
+                             int64_t* n_total /*host, or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* ---- train collections: one query against many images ------------------------------------------------------------------
  * cv2.BFMatcher.add([d1, d2, ...]) / train() / clear() and then match(query) / knnMatch(query, k) against ALL added images,
@@ -726,6 +778,10 @@ int  fm_collection_radius_match(fm_ctx* ctx, fm_collection* coll, const fm_bank*
 int  fm_collection_hamming_radius_match(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const float* radius /*host [nq] or NULL*/,
                                         float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* img, int32_t* idx,
                                         float* dist, int64_t* n_total);
+/* (a wide collection: "Wide radiusMatch" above) */
+int  fm_collection_wide_radius_match(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const float* radius /*host [nq] or NULL*/,
+                                     float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* img, int32_t* idx,
+                                     float* dist, int64_t* n_total);
 int  fm_collection_match_accepted_each(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
                                        int32_t* qidx, int32_t* tidx, float* dist, double* ratio /* each [n_images][cap] */,
                                        int64_t* n_accepted /*[n_images]: the full count per image*/);
@@ -859,6 +915,10 @@ int  fm_collection_wide_mutual_ratio_each_dev(fm_ctx* ctx, fm_collection* coll, 
  *   fm_collection_hamming_radius_match -- d_radius read in place, d_offsets always written, the lists at their final offsets
  *   for the rows that fit in cap; pointer checks (after the host forms' errors), stream ordering, *n_total and the host
  *   synchronisation exactly as in fm_radius_match_dev.  Not accounted in fm_stats.
+ * fm_wide_radius_match_dev, fm_collection_wide_radius_match_dev: the same device forms of fm_wide_radius_match and
+ *   fm_collection_wide_radius_match ("Wide radiusMatch" above) -- pointer checks (after the host forms' errors), stream
+ *   ordering, d_offsets written per chunk, *n_total and the host synchronisation as on fm_radius_match_dev's float32 route.
+ *   Not accounted in fm_stats.
  * Not built: device sources for fm_bank_refill_u8_async and fm_bank_append_*; device results for
  *   fm_self_dist (fm_self_dist_batch attaches them on the device already) and for fm_collection_knn2_each / _votes; an
  *   enqueue-only float32 route; tensors on another GPU than the context's (copy them over first).                          */
@@ -898,6 +958,11 @@ int  fm_collection_hamming_radius_match_dev(fm_ctx* ctx, fm_collection* coll, co
                                             float radius_all, int64_t cap, int64_t* d_offsets /*device [nq+1]*/, int32_t* d_img,
                                             int32_t* d_idx, float* d_dist, int64_t* n_total /*host, or NULL*/,
                                             void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+/* (wide banks and wide collections, "Wide radiusMatch" above: fm_wide_radius_match_dev is declared there) */
+int  fm_collection_wide_radius_match_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const float* d_radius /*device [nq] or NULL*/,
+                                         float radius_all, int64_t cap, int64_t* d_offsets /*device [nq+1]*/, int32_t* d_img,
+                                         int32_t* d_idx, float* d_dist, int64_t* n_total /*host, or NULL*/,
+                                         void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* ---- masks: knnMatch(q, t, k, mask) and knnMatch(q, k, masks = [...]) (K13, csrc/masked.hip) --------------------------------
  * cv2's mask argument: a CV_8U [nq][nt] matrix, nonzero = the pair (query row, train row) may be matched; for a train
