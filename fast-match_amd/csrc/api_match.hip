@@ -533,8 +533,13 @@ static int wide_route(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, 
 {
     const RowReducePlan pl = plan_rowreduce_f32(cols.n_pad, red.n_pad, ctx->tune.nsplit);
     *pl_out = pl;
+    const WideFilterPlan fp = plan_wide_filter(cols.n_pad, cols.n, red.n_pad, ctx->tune);
+    // (a split records its first tile whole -- 16 records per output row, fewer only where the reduced bank is shorter than a
+    // tile -- and the list ends at 2^24 records: from 2^20 output rows on it overflows in every call, with one split already,
+    // the filter's sweep is wasted and the exact kernel redoes the call.  Such a call goes to the exact kernel at once.)
     const bool filter = ctx->tune.f32_filter != 0 && ctx->d_counters && wide_filter_usable(cols, red) &&
-                        (ctx->tune.f32_filter >= 2 || (double)cols.n * (double)red.n >= 4.0e6);
+                        (ctx->tune.f32_filter >= 2 || (double)cols.n * (double)red.n >= 4.0e6) &&
+                        cols.n * std::min<int64_t>(16, red.n) <= (int64_t)fp.cap;
     unsigned long long* d_part;
     int rc;
     if (!filter) {
@@ -545,7 +550,6 @@ static int wide_route(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, 
         HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
         return FM_OK;
     }
-    const WideFilterPlan fp = plan_wide_filter(cols.n_pad, cols.n, red.n_pad, ctx->tune);
     size_t off = 0;
     const size_t o_part = carve(off, pl.partial_bytes(ktop)), o_list = carve(off, fp.list_bytes()), o_score = carve(off, fp.list_bytes() / 2),
                  o_bound = carve(off, (size_t)cols.n_pad * 4), o_cnt = carve(off, 16);

@@ -15,6 +15,18 @@
  * (not re-entrant per ctx; distinct ctxs are independent).  All calls are synchronous:
  * host outputs are valid on return.  There is no CPU fallback: without a usable
  * gfx950 device fm_ctx_create fails.
+ *
+ * Sizes.  Row numbers are 32-bit everywhere (idx outputs are int32, the kernels' keys carry a row in 32 bits): a bank holds
+ * at most 2^31 - 257 rows and a train collection at most that many rows in all its images together, padding to 128-row
+ * stages included; the creators and the adds refuse more with FM_EUNSUPPORTED.  BYTE offsets into a bank's arrays are
+ * 64-bit in every kernel, so a bank or a collection may be as large as device memory allows: rows beyond the 2^31- and
+ * 2^32-byte marks of every plane (2^21 / 2^22 rows of a wide bank, 2^22 / 2^23 of a float32-route bank, 2^24 / 2^25 of an
+ * integer-route bank, 2^25 / 2^26 binary rows of 64 bytes) are tested bit for bit (tests/test_big_offset_gpu.py; DESIGN.md,
+ * "Index widths", lists every access).  Two narrower limits come from kernels that spend one work-item per element and
+ * end in FM_EDEVICE (a refused launch), never in a wrong result: a float32-route bank (FM_BANK_F32) is prepared for fewer
+ * than 2^25 rows, and a cross-check elects among fewer than 2^30 train rows.  A wide pair (FM_BANK_F32W) whose OUTPUT side has
+ * 2^20 rows or more takes the exact kernel whatever "f32_filter" says and counts no filter launch: the first tiles alone
+ * would fill the filter's record list (K14 below).
  */
 #ifndef FASTMATCH_HIP_H
 #define FASTMATCH_HIP_H
