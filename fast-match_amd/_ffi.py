@@ -220,6 +220,8 @@ SYMBOLS = {
     "fm_mask_info": (_INT, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I32), ctypes.POINTER(_I64)]),
     "fm_knn_masked": (_INT, [_P, _P, _P, _P, _I32, _P, _P]),
     "fm_knn_masked_dev": (_INT, [_P, _P, _P, _P, _I32, _P, _P, _P]),
+    "fm_wide_knn_masked": (_INT, [_P, _P, _P, _P, _I32, _P, _P]),            # wide float banks (csrc/wide_masked.hip)
+    "fm_wide_knn_masked_dev": (_INT, [_P, _P, _P, _P, _I32, _P, _P, _P]),
     "fm_collection_knn_masked": (_INT, [_P, _P, _P, _P, _I32, _P, _P, _P]),
     "fm_collection_knn_masked_dev": (_INT, [_P, _P, _P, _P, _I32, _P, _P, _P, _P]),
 }
@@ -1397,6 +1399,23 @@ class Context(object):
         self._check(self.lib.fm_knn_masked_dev(self.handle, q.handle, t.handle, mask.handle if mask is not None else None, int(k),
                                                _P(int(idx_ptr)) if idx_ptr else None, _P(int(dist_ptr)) if dist_ptr else None,
                                                _stream_arg(consumer_stream)))
+
+    def wide_knn_masked(self, q, t, mask, k):
+        """``fm_wide_knn_masked``: ``knn_masked`` on two wide float banks (129 .. 256 values per row), k = 1 or 2, on the matrix
+        cores -- ``knn``'s lists for the wide pair over the train rows ``mask`` (``Context.mask``) permits per query row, the same
+        distance bits; -1 / inf where fewer than k rows are permitted.  (``knn_masked`` keeps refusing wide banks.)"""
+        idx = np.empty((q.n, max(int(k), 0)), dtype=np.int32)
+        dist = np.empty((q.n, max(int(k), 0)), dtype=np.float32)
+        self._check(self.lib.fm_wide_knn_masked(self.handle, q.handle, t.handle, mask.handle if mask is not None else None, int(k),
+                                                _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def wide_knn_masked_dev(self, q, t, mask, k, idx_ptr, dist_ptr, consumer_stream=None):
+        """``wide_knn_masked`` with the lists left on the device (``fm_wide_knn_masked_dev``); pointers and ``consumer_stream``
+        as in ``knn_dev``."""
+        self._check(self.lib.fm_wide_knn_masked_dev(self.handle, q.handle, t.handle, mask.handle if mask is not None else None, int(k),
+                                                    _P(int(idx_ptr)) if idx_ptr else None, _P(int(dist_ptr)) if dist_ptr else None,
+                                                    _stream_arg(consumer_stream)))
 
     def hamming_radius_match(self, q, t, r):
         """``fm_hamming_radius_match``: ``radius_match`` on two binary banks (``bank_binary``) -- every train row with

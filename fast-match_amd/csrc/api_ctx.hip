@@ -1657,7 +1657,7 @@ int fm::refuse_wide(fm_ctx* ctx, const fm_bank* b, const char* who)
     if (!b || b->kind != FM_BANK_F32W) return FM_OK;
     return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": wide float banks (FM_BANK_F32W, 129 .. 256 values per row) are served by fm_knn2, "
                                           "fm_knn with k <= 2, fm_xcheck1, fm_knn2_ratio, fm_mutual_ratio, their _dev forms and the Wide Fast-Match calls (fm_wide_self_dist, "
-                                          "fm_wide_set_selfdist, fm_wide_match_ratio, fm_wide_match_accepted) and fm_wide_radius_match(_dev) only");
+                                          "fm_wide_set_selfdist, fm_wide_match_ratio, fm_wide_match_accepted), fm_wide_radius_match(_dev) and fm_wide_knn_masked(_dev) only");
 }
 
 int fm::refuse_bin(fm_ctx* ctx, const fm_bank* b, const char* who)

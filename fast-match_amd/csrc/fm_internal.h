@@ -342,6 +342,20 @@ WideFilterPlan plan_wide_filter(int64_t ncols_pad, int64_t ncols, int64_t nred_p
 hipError_t launch_wide_filter(const Bank& cols, const Bank& red, int ktop, const WideFilterPlan& plan, uint2* list, float* lscore,
                               unsigned* gbound, unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream,
                               bool self = false);
+// launch_wide_filter's second kernel alone: the records of `list` rescored exactly into split 0 of `partial` (the masked filter
+// of wide_masked.hip leaves records in the same form)
+hipError_t launch_wide_rescore(const Bank& cols, const Bank& red, int ktop, unsigned cap, const uint2* list, const float* lscore,
+                               const unsigned* gbound, const unsigned long long* cnt, int* flag, unsigned long long* partial, hipStream_t stream,
+                               bool self = false);
+// ---- K14 under a mask (wide_masked.hip): fm_wide_knn_masked's two sweeps.  mask: fm_mask's words [q.n][mwords], mwords =
+// t.n_pad / 64; partial: [plan.nsplit][q.n][ktop] keys, K9's layout (launch_knnk_merge merges it) ----
+// the masked filter + launch_wide_rescore (presets as for launch_wide_filter); ktop 1 or 2
+hipError_t launch_wide_masked_filter(const Bank& q, const Bank& t, int ktop, const WideFilterPlan& plan, const unsigned long long* mask,
+                                     int64_t mwords, uint2* list, float* lscore, unsigned* gbound, unsigned long long* cnt, int* flag,
+                                     unsigned long long* partial, hipStream_t stream);
+// the masked exact kernel under K5's run_flag protocol; writes every key of `partial`
+hipError_t launch_wide_masked_exact(const Bank& q, const Bank& t, int ktop, const RowReducePlan& plan, const unsigned long long* mask,
+                                    int64_t mwords, unsigned long long* partial, const int* run_flag, hipStream_t stream);
 // Table forms (top-2) for a chunk of image pairs of one wide stack (fm_collection_pairs_mutual_ratio): a slot is one direction
 // of one pair, both operands views of `stack` that start on a 128-row stage -- or, with WideTableLaunch::outside, one of them
 // rows of a bank outside the stack (fm_collection_wide_mutual_ratio_each: a query bank).  The slots lie side by side in the chunk's

@@ -37,7 +37,9 @@ Mirrors ``matchutil.py`` of the reference:
   + ratio per image, the visual-localisation pattern; ``fm_collection_wide_mutual_ratio_each``) and
   ``knnMatchWideEach_arrays`` (``fm_collection_wide_knn2_each``).  Fast-Match's self-distance test on wide descriptors:
   ``wide_fast_match`` / ``wide_fast_match_arrays`` (``fm_wide_self_dist_batch``, ``fm_wide_match_accepted``) and, against a
-  wide collection, ``BFMatcher.wideFastMatchEach`` / ``wideFastMatchEach_arrays``.
+  wide collection, ``BFMatcher.wideFastMatchEach`` / ``wideFastMatchEach_arrays``.  knnMatch under a mask on wide descriptors
+  (guided matching: a window round a predicted position, an epipolar band) is ``wide_bf_match_masked`` /
+  ``wide_bf_match_masked_arrays`` (``fm_wide_knn_masked``, k = 1 or 2); ``bf_match`` keeps refusing the combination.
 * ``options["mask"]``: cv2's ``mask`` argument of ``knnMatch`` -- an ``[nq, nt]`` uint8 / bool array, nonzero = the pair
   (query row, train row) may be matched, or a resident ``_ffi.Mask`` (``Context.mask``).  ``bf_match``,
   ``bf_match_arrays``, ``flann_match`` and ``flann_match_arrays`` honour it when crossCheck is off: every list is the
@@ -513,6 +515,53 @@ def wide_radius_match(dt1, dt2, maxDistance, options={}):
     """ radiusMatch on wide float descriptors (wide_radius_match_arrays): a list of DMatch lists, one per query row """
     off, idx, dist = wide_radius_match_arrays(dt1, dt2, maxDistance, options=options)
     return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
+
+
+def wide_bf_match_masked_arrays(dt1, dt2, mask, k=2, options=None):
+    """``cv2.BFMatcher(cv2.NORM_L2).knnMatch(dt1, dt2, k, mask)`` on wide float descriptors (129 .. 256 values per row) as
+    arrays: ``(idx int32[nq, k], dist float32[nq, k])``, row i the list ``bf_match_arrays(dt1, dt2, k)`` gives computed over
+    the train rows ``mask`` permits for row i only -- the same distance bits, ascending (distance, train index), -1 / inf
+    where fewer than k rows are permitted (``fm_wide_knn_masked``, on the matrix cores).  ``dt1`` / ``dt2``: float32 / float64
+    arrays or resident wide banks; ``mask``: a uint8 / bool ``[nq, nt]`` array, nonzero = the pair may be matched, or a resident
+    ``_ffi.Mask`` (``Context.mask``); k = 1 or 2.  ``ValueError`` before anything is uploaded: another dtype, dims that differ
+    or lie outside 129 .. 256, a mask of another shape or dtype, another k.  (``bf_match`` keeps refusing a mask on wide
+    descriptors.)"""
+    who = "wide_bf_match_masked"
+    q, qw = _wide_operand(dt1, who)
+    t, tw = _wide_operand(dt2, who)
+    if qw != tw:
+        raise ValueError("%s: %d values per query row, %d per train row" % (who, qw, tw))
+    k = int(k)
+    if k < 1 or k > 2:
+        raise ValueError("%s: k = %d: wide float descriptors take k = 1 or 2" % (who, k))
+    if mask is None:
+        raise ValueError("%s: mask is None (bf_match serves wide descriptors without a mask)" % who)
+    mask = _mask_option({"mask": mask}, q, t, who)
+    ctx = _context(options or {})
+    qb, q_tmp = (q, False) if isinstance(q, _ffi.Bank) else (ctx.bank(q), True)
+    try:
+        tb, t_tmp = (t, False) if isinstance(t, _ffi.Bank) else (ctx.bank(t), True)
+    except Exception:
+        if q_tmp:
+            qb.close()
+        raise
+    try:
+        if isinstance(mask, _ffi.Mask):
+            return ctx.wide_knn_masked(qb, tb, mask, k)
+        with ctx.mask(qb.n, tb.n) as mk:
+            return ctx.wide_knn_masked(qb, tb, mk.set(mask), k)
+    finally:
+        if q_tmp:
+            qb.close()
+        if t_tmp:
+            tb.close()
+
+
+def wide_bf_match_masked(dt1, dt2, mask, k=2, options=None):
+    """ knnMatch under a mask on wide float descriptors (wide_bf_match_masked_arrays): bf_match's list of DMatch lists, one per
+    query row, shorter where fewer than k train rows are permitted """
+    idx, dist = wide_bf_match_masked_arrays(dt1, dt2, mask, k=k, options=options)
+    return matches_from_arrays(idx, dist)
 
 
 class BFMatcher(object):

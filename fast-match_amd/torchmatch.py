@@ -67,6 +67,8 @@ Fast-Match's self-distance test on wide descriptors: ``wide_fast_match(q, t, tau
 [1])`` (``fm_wide_self_dist_batch``, ``fm_wide_match_accepted_dev``) and, against a wide collection image by image,
 ``Collection.wide_fast_match_each(q, tau, cap=None)`` -> ``(rows int32 [n_images, cap, 3], counts int64 [n_images])``
 (``fm_collection_wide_match_accepted_each_dev``).
+knnMatch under a mask on wide descriptors: ``wide_knn_masked(q, t, k, mask)`` -> ``(idx int32 [nq, k], dist float32 [nq, k])``,
+k = 1 or 2, ``mask`` as in ``knn`` (``fm_wide_knn_masked_dev``, on the matrix cores); ``knn`` keeps refusing the combination.
 
 ``q`` and ``t`` are ``Bank``s or CUDA tensors (a tensor becomes a bank for the call).  The values are those of
 ``Context.knn`` / ``xcheck1`` / ``knn2_ratio`` on banks built from the same numbers on the host, bit for bit.
@@ -479,6 +481,52 @@ def wide_fast_match(q, t, tau):
             torch.cuda.current_stream().synchronize()
         m = qb.ctx.wide_match_accepted_dev(qb, tb, float(tau), rows.data_ptr(), count.data_ptr(), cap)
         return rows[:min(m, cap)], count
+    finally:
+        for b in made:
+            b.close()
+
+
+def wide_knn_masked(q, t, k, mask):
+    """``knn(q, t, k, mask)`` on wide float descriptors (129 .. 256 values per row), k = 1 or 2, on the matrix cores: ``(idx int32
+    [nq, k], dist float32 [nq, k])`` CUDA tensors, ``knn``'s lists for the pair computed over the train rows ``mask`` permits per
+    query row -- the same distance bits; -1 / inf where fewer than k rows are permitted (``fm_wide_knn_masked_dev``).  ``q`` /
+    ``t``: float32 / float16 / bfloat16 CUDA tensors (half and bfloat16 widened exactly) or wide ``Bank``s; ``mask``: a CUDA
+    ``bool`` / ``uint8`` tensor ``[nq, nt]``, packed on the device behind the current stream (``fm_mask_set_dev``), or a resident
+    ``_ffi.Mask``.  (``knn`` keeps refusing a mask on wide descriptors.)  Every refusal comes before the library is touched."""
+    import torch
+    who = "wide_knn_masked"
+    k = int(k)
+    if k < 1 or k > 2:
+        raise ValueError("%s: k = %d: wide float descriptors take k = 1 or 2" % (who, k))
+    ops = [_wide_operand(who, x) for x in (q, t)]
+    widths = [x.dim if isinstance(x, _ffi.Bank) else x.shape[1] for x in ops]
+    if widths[0] != widths[1]:
+        raise ValueError("%s: %d values per query row, %d per train row" % (who, widths[0], widths[1]))
+    if mask is None:
+        raise ValueError("%s: mask is None (knn serves wide descriptors without a mask)" % who)
+    if not isinstance(mask, _ffi.Mask):
+        nq, nt = (x.n if isinstance(x, _ffi.Bank) else x.shape[0] for x in ops)
+        mask = _checked_mask(mask, nq, nt)
+    ctx = next((x.ctx for x in ops if isinstance(x, _ffi.Bank)), None)
+    made, banks = [], []
+    try:
+        for x in ops:
+            if not isinstance(x, _ffi.Bank):
+                x = bank(x, context=ctx)
+                ctx = x.ctx
+                made.append(x)
+            banks.append(x)
+        qb, tb = banks
+        stream, dev = _stream_and_device(qb.ctx)
+        idx = torch.empty((qb.n, k), dtype=torch.int32, device=dev)
+        dist = torch.empty((qb.n, k), dtype=torch.float32, device=dev)
+        mk = mask
+        if not isinstance(mask, _ffi.Mask):
+            mk = qb.ctx.mask(qb.n, tb.n)
+            made.append(mk)
+            _set_mask(mk, mask, 0)
+        qb.ctx.wide_knn_masked_dev(qb, tb, mk, k, idx.data_ptr() if qb.n else 0, dist.data_ptr() if qb.n else 0, consumer_stream=stream)
+        return idx, dist
     finally:
         for b in made:
             b.close()

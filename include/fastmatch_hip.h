@@ -80,7 +80,7 @@ typedef struct fm_bank fm_bank;
  * only -- fm_wide_self_dist, fm_wide_self_dist_batch, fm_wide_set_selfdist, fm_wide_match_ratio, fm_wide_match_accepted,
  * fm_wide_match_accepted_dev, fm_collection_wide_match_accepted_each, fm_collection_wide_match_accepted_each_dev; still
  * revision 12, additions only -- fm_wide_radius_match, fm_wide_radius_match_dev, fm_collection_wide_radius_match,
- * fm_collection_wide_radius_match_dev).  A binding
+ * fm_collection_wide_radius_match_dev; still revision 12, additions only -- fm_wide_knn_masked, fm_wide_knn_masked_dev).  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.              */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -1040,6 +1040,40 @@ int  fm_collection_knn_masked(fm_ctx* ctx, fm_collection* coll, const fm_bank* q
 int  fm_collection_knn_masked_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const fm_mask* mask, int32_t k,
                                   int32_t* d_img /*device [nq*k]*/, int32_t* d_idx /*device [nq*k]*/, float* d_dist /*device [nq*k]*/,
                                   void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+
+/* ---- Wide knnMatch masks: knnMatch(q, t, k, mask) on wide float banks (K14 under a mask, csrc/wide_masked.hip) ---------------
+ * fm_knn_masked(_dev) above keep refusing wide float banks (FM_BANK_F32W, 129 .. 256 values per row: FM_EUNSUPPORTED with a
+ * message that says "wide"); these two calls serve them, with fm_knn_masked's and fm_knn_masked_dev's argument lists word for
+ * word.  Guided matching of learned descriptors: a window round a predicted position, an epipolar band from a pose prior.
+ * The mask is fm_mask_create(ctx, nq, nt, &mask)'s, unchanged: its geometry does not depend on the bank kind (a wide bank's
+ * padded row count is pad128(n) like every bank's).
+ * Contract: row i's list is the list fm_knn(q, t, k) gives for the wide pair, computed over the PERMITTED train rows of row i
+ *   only.  The distances are the same bits -- K14's chain: sqrtf(s), s = fmaf(v_k, v_k, s), k ascending over the real dim.
+ *   Order: (float32 distance bits, train index), strictly; the lowest permitted index wins a tie.  -1 / +inf where fewer than k
+ *   rows are permitted.  A NaN or +inf distance is never listed.  An all-ones mask reproduces fm_knn bit for bit.  nq = 0,
+ *   nt = 0 and an all-zero mask are valid.  k = 1, 2; k >= 3 is FM_EUNSUPPORTED, as fm_knn answers for wide banks; k < 1 is
+ *   FM_EINVAL.  No option changes a result.
+ * Errors, in this order: (1) NULL handles (ctx, banks, mask): FM_EINVAL; (2) a bank that is not FM_BANK_F32W: FM_EINVAL, even
+ *   when it is empty, with a message that names fm_knn_masked as the call that serves it; dims that differ: FM_EINVAL; (3) k;
+ *   (4) the mask checks of fm_knn_masked, FM_EINVAL with a message that says which: a mask of another context, a mask whose nq
+ *   differs from the query bank's rows or whose train rows differ from the train bank's, a collection's mask; (5) the output
+ *   pointers: fm_knn_masked's check for the host form (NULL with nq > 0), fm_knn_dev's pointer checks for the device form.
+ * Streams and accounting: the device form orders itself against consumer_stream in both directions as fm_knn_masked_dev does
+ *   and is not accounted in fm_stats; the host form is accounted like fm_knn_masked (pairs = nq * real train rows).
+ *   fm_f32_filter_stats counts one launch per filtered call and one fallback per call that is redone.
+ * Routes ("f32_filter" 0 / 1 / 2 and "f32_nsplit" as for every wide sweep): the masked fp16 filter on the MATRIX CORES
+ *   (v_mfma_f32_16x16x32_f16, K14's filter shape) for calls of 4e6 pairs or more ("f32_filter" 2: always) on banks the filter
+ *   can take, then K14's exact rescoring of the recorded pairs; a lane reads the 16 mask bits of its output row and a 16-row
+ *   tile from one 8-byte word per four tiles, a forbidden pair is dropped by INDEX before it can enter a bound, and a wave
+ *   skips the matrix instructions -- and the operand fetch -- of a tile in which it has no permitted pair.  Everything else,
+ *   and a call whose record list overflowed (2^20 records at least; the call is redone: the fallback), takes the masked exact
+ *   kernel: K14's exact tiling on the vector ALUs with one mask bit tested per candidate.
+ * Not built: masks in the wide mutual-ratio, ratio, self-distance, radius and collection calls (fm_mutual_ratio, fm_knn2_ratio,
+ *   fm_wide_self_dist, fm_wide_match_*, fm_wide_radius_match, fm_collection_wide_*); k >= 3; a masked K8 filter for 128-D float
+ *   banks (fm_knn_masked's float32 route stays on the vector ALUs).                                                        */
+int  fm_wide_knn_masked(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, int32_t k, int32_t* idx /*[nq*k]*/, float* dist /*[nq*k]*/);
+int  fm_wide_knn_masked_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, int32_t k, int32_t* d_idx /*device [nq*k]*/,
+                            float* d_dist /*device [nq*k]*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* Classic Ratio-Match in one call: knnMatch(q, t, k=2) then ratio = m[0].distance /
  * m[1].distance (float64) and ratio < tau  -- Classic Matching.ipynb cell 3 (JSON 59-72), the
