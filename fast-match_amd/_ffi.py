@@ -193,6 +193,12 @@ SYMBOLS = {
     "fm_wide_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
     "fm_collection_wide_radius_match": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
     "fm_collection_wide_radius_match_dev": (_INT, [_P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    # Wide stacked knnMatch (csrc/wide_stack.hip): the argument lists of fm_collection_knn(_dev) / _knn2_ratio(_dev) / _votes
+    "fm_collection_wide_knn": (_INT, [_P, _P, _P, _I32, _P, _P, _P]),
+    "fm_collection_wide_knn_dev": (_INT, [_P, _P, _P, _I32, _P, _P, _P, _P]),
+    "fm_collection_wide_knn2_ratio": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_collection_wide_knn2_ratio_dev": (_INT, [_P, _P, _P, ctypes.c_double, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
+    "fm_collection_wide_votes": (_INT, [_P, _P, _P, ctypes.c_double, _I32, _P]),
     # Hamming Fast-Match: the self-distance test on binary banks (csrc/hamming.hip, ham_self_kernel)
     "fm_hamming_self_dist": (_INT, [_P, _P, _P]),
     "fm_hamming_self_dist_batch": (_INT, [_P, ctypes.c_int32, _P, _P]),
@@ -594,23 +600,34 @@ class Collection(object):
                                                                 int(n), int(dim), int(pitch), _stream_arg(stream), ctypes.byref(i)))
         return int(i.value)
 
-    def knn_dev(self, q, k, img_ptr, idx_ptr, dist_ptr, consumer_stream=None):
+    def knn_dev(self, q, k, img_ptr, idx_ptr, dist_ptr, consumer_stream=None, _name="fm_collection_knn_dev"):
         """``knn`` with the lists left on the device (``fm_collection_knn_dev``): device addresses of int32 / int32 / float32
         [nq, k] buffers; enqueued, ``consumer_stream`` as in ``Context.knn_dev``."""
-        self.ctx._check(self.ctx.lib.fm_collection_knn_dev(
+        self.ctx._check(getattr(self.ctx.lib, _name)(
             self.ctx.handle, self.handle, q.handle, int(k), _P(int(img_ptr)) if img_ptr else None,
             _P(int(idx_ptr)) if idx_ptr else None, _P(int(dist_ptr)) if dist_ptr else None, _stream_arg(consumer_stream)))
 
-    def knn2_ratio_dev(self, q, tau, rows_ptr, count_ptr, cap, want_count=False, consumer_stream=None):
+    def knn2_ratio_dev(self, q, tau, rows_ptr, count_ptr, cap, want_count=False, consumer_stream=None,
+                       _name="fm_collection_knn2_ratio_dev"):
         """``knn2_ratio`` with the accepted matches left on the device (``fm_collection_knn2_ratio_dev``): ``rows_ptr`` = device
         address of an int32 [cap, 4] buffer (query, image, row inside the image, float32 distance bits), ``count_ptr`` of an
         int64 word that receives min(accepted, cap).  ``want_count``: also return the full number accepted (one host
         synchronisation); else None."""
         n = _I64(0)
-        self.ctx._check(self.ctx.lib.fm_collection_knn2_ratio_dev(
+        self.ctx._check(getattr(self.ctx.lib, _name)(
             self.ctx.handle, self.handle, q.handle, float(tau), int(cap), _P(int(rows_ptr)) if rows_ptr else None,
             _P(int(count_ptr)) if count_ptr else None, ctypes.byref(n) if want_count else None, _stream_arg(consumer_stream)))
         return int(n.value) if want_count else None
+
+    def wide_knn_dev(self, q, k, img_ptr, idx_ptr, dist_ptr, consumer_stream=None):
+        """``wide_knn`` with the lists left on the device (``fm_collection_wide_knn_dev``); arguments as ``knn_dev``."""
+        self.knn_dev(q, k, img_ptr, idx_ptr, dist_ptr, consumer_stream, _name="fm_collection_wide_knn_dev")
+
+    def wide_knn2_ratio_dev(self, q, tau, rows_ptr, count_ptr, cap, want_count=False, consumer_stream=None):
+        """``wide_knn2_ratio`` with the accepted matches left on the device (``fm_collection_wide_knn2_ratio_dev``); arguments
+        and return value as ``knn2_ratio_dev``."""
+        return self.knn2_ratio_dev(q, tau, rows_ptr, count_ptr, cap, want_count, consumer_stream,
+                                   _name="fm_collection_wide_knn2_ratio_dev")
 
     def radius_match(self, q, r, _name="fm_collection_radius_match"):
         """``fm_collection_radius_match``: every row of the stacked images with distance < r per query row.  ``r`` is a scalar
@@ -698,14 +715,20 @@ class Collection(object):
         self.ctx._check(self.ctx.lib.fm_collection_image_rows(self.handle, _ptr(rows) if rows.shape[0] else None))
         return rows
 
-    def knn(self, q, k):
+    def knn(self, q, k, _name="fm_collection_knn"):
         """``fm_collection_knn``: (img, idx, dist) [nq, k] against the stacked rows of all images."""
         k = int(k)
         img = np.empty((q.n, max(k, 0)), np.int32)
         idx = np.empty((q.n, max(k, 0)), np.int32)
         dist = np.empty((q.n, max(k, 0)), np.float32)
-        self.ctx._check(self.ctx.lib.fm_collection_knn(self.ctx.handle, self.handle, q.handle, k, _ptr(img), _ptr(idx), _ptr(dist)))
+        self.ctx._check(getattr(self.ctx.lib, _name)(self.ctx.handle, self.handle, q.handle, k, _ptr(img), _ptr(idx), _ptr(dist)))
         return img, idx, dist
+
+    def wide_knn(self, q, k):
+        """``fm_collection_wide_knn``: ``knn`` of a wide float query bank (129 .. 256 values per row) against the stacked rows
+        of a wide collection (``add_wide``), k = 1, 2: (img, idx, dist) [nq, k], the lists ``Context.knn`` gives for one bank of
+        the images' rows concatenated, every entry as (image, row inside the image)."""
+        return self.knn(q, k, _name="fm_collection_wide_knn")
 
     def mask(self, nq):
         """An all-forbidding ``Mask`` for ``nq`` query rows laid out on this collection's images as they are now
@@ -732,16 +755,21 @@ class Collection(object):
             _P(int(img_ptr)) if img_ptr else None, _P(int(idx_ptr)) if idx_ptr else None, _P(int(dist_ptr)) if dist_ptr else None,
             _stream_arg(consumer_stream)))
 
-    def knn2_ratio(self, q, tau):
+    def knn2_ratio(self, q, tau, _name="fm_collection_knn2_ratio"):
         """``fm_collection_knn2_ratio``: (qidx, img, tidx, dist, ratio) of the accepted matches, ascending query index."""
         cap = q.n
         qidx, img, tidx = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.int32)
         dist, ratio = np.empty(cap, np.float32), np.empty(cap, np.float64)
         n = _I64(0)
-        self.ctx._check(self.ctx.lib.fm_collection_knn2_ratio(self.ctx.handle, self.handle, q.handle, float(tau), cap, _ptr(qidx),
-                                                              _ptr(img), _ptr(tidx), _ptr(dist), _ptr(ratio), ctypes.byref(n)))
+        self.ctx._check(getattr(self.ctx.lib, _name)(self.ctx.handle, self.handle, q.handle, float(tau), cap, _ptr(qidx),
+                                                     _ptr(img), _ptr(tidx), _ptr(dist), _ptr(ratio), ctypes.byref(n)))
         m = min(int(n.value), cap)
         return qidx[:m], img[:m], tidx[:m], dist[:m], ratio[:m]
+
+    def wide_knn2_ratio(self, q, tau):
+        """``fm_collection_wide_knn2_ratio``: ``knn2_ratio`` of a wide query bank against a wide collection -- Lowe's ratio
+        test on the 2-NN lists over ALL images' rows."""
+        return self.knn2_ratio(q, tau, _name="fm_collection_wide_knn2_ratio")
 
     def knn2_each(self, q):
         """``fm_collection_knn2_each``: (idx, dist) [n_images, nq, 2], slot by slot ``Context.knn2(q, image_i)``."""
@@ -751,12 +779,16 @@ class Collection(object):
         self.ctx._check(self.ctx.lib.fm_collection_knn2_each(self.ctx.handle, self.handle, q.handle, _ptr(idx), _ptr(dist)))
         return idx, dist
 
-    def votes(self, q, tau, mode=0):
+    def votes(self, q, tau, mode=0, _name="fm_collection_votes"):
         """``fm_collection_votes``: int64[n_images] query rows passing the ratio test per image (mode 0: stacked lists, 1: per image)."""
         v = np.zeros(self.info()[0], np.int64)
-        self.ctx._check(self.ctx.lib.fm_collection_votes(self.ctx.handle, self.handle, q.handle, float(tau), int(mode),
-                                                         _ptr(v) if v.shape[0] else None))
+        self.ctx._check(getattr(self.ctx.lib, _name)(self.ctx.handle, self.handle, q.handle, float(tau), int(mode),
+                                                     _ptr(v) if v.shape[0] else None))
         return v
+
+    def wide_votes(self, q, tau, mode=0):
+        """``fm_collection_wide_votes``: ``votes`` of a wide query bank against a wide collection."""
+        return self.votes(q, tau, mode, _name="fm_collection_wide_votes")
 
     def hamming_match_accepted_each(self, q, tau, cap=None):
         """``fm_collection_hamming_match_accepted_each``: ``match_accepted_each`` on a binary collection -- slot i equal to

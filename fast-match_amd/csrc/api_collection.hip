@@ -278,6 +278,13 @@ void coll_votes_kernel(const int32_t* __restrict__ img, const int32_t* __restric
     }
 }
 
+hipError_t launch_coll_votes(const int32_t* img, const int32_t* idx, const float* dist, int64_t nq, int64_t ny, double tau,
+                             unsigned long long* votes, hipStream_t stream)
+{
+    hipLaunchKernelGGL(coll_votes_kernel, dim3((unsigned)((nq + 255) / 256), (unsigned)ny), dim3(256), 0, stream, img, idx, dist, nq, tau, votes);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------
 // storage
 // ---------------------------------------------------------------------------------------
@@ -759,7 +766,8 @@ static int coll_refuse_wide(fm_ctx* ctx, const fm_collection* c, const char* who
     return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": a wide collection (fm_collection_add_wide, FM_BANK_F32W) is served by "
                                       "fm_collection_pairs_mutual_ratio(_dev) and, for a wide query bank, by "
                                       "fm_collection_wide_mutual_ratio_each(_dev) / fm_collection_wide_knn2_each / "
-                                      "fm_collection_wide_match_accepted_each(_dev) / fm_collection_wide_radius_match(_dev) only");
+                                      "fm_collection_wide_match_accepted_each(_dev) / fm_collection_wide_radius_match(_dev) / "
+                                      "fm_collection_wide_knn(_dev) / fm_collection_wide_knn2_ratio(_dev) / fm_collection_wide_votes only");
 }
 
 extern "C" int fm_collection_train(fm_ctx* ctx, fm_collection* c)
@@ -864,6 +872,58 @@ int coll_merge_one(fm_ctx* ctx, const PairSweep* ps, CollTab tab, int64_t nq, in
     return FM_OK;
 }
 
+// The stacked 2-NN lists of a wide query bank over a wide collection (K14 over the stack, wide_stack.hip): wide_route's rule
+// (api_match.hip) with the stack as the reduced bank -- "f32_filter" 0 / 1 / 2 and the 4e6 threshold on the REAL pairs,
+// wide_filter_usable, "f32_nsplit", the record cap rule, ws_partial = partial | records | scores | bounds | count, one
+// filter launch counted per filtered call and (by the exact kernel itself, behind run_flag) one fallback per call redone.
+// The stack's scale, largest scaled squared norm and filt_ok are read HERE, at the call: a later add may rewrite them.
+// c->total > 0; the tables are built (fm_collection_train).
+static int coll_wide_knn2_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const CollTab& tab, int32_t* d_img, int32_t* d_idx,
+                                 float* d_dist, void* consumer)
+{
+    const int64_t nq = q->n;
+    const fm::Bank& t = c->stack;
+    ctx->pending_pairs += nq * c->total;
+    ctx->pending_bytes += bank_bytes(q) + bank_bytes(&t);
+    const RowReducePlan pl = plan_rowreduce_f32(q->n_pad, t.n_pad, ctx->tune.nsplit);
+    const WideFilterPlan fp = plan_wide_filter(q->n_pad, nq, t.n_pad, ctx->tune);
+    const bool filter = ctx->tune.f32_filter != 0 && ctx->d_counters && wide_filter_usable(*q, t) &&
+                        (ctx->tune.f32_filter >= 2 || (double)nq * (double)c->total >= 4.0e6) &&
+                        nq * std::min<int64_t>(16, c->total) <= (int64_t)fp.cap;
+    const size_t part = pl.partial_bytes(2);
+    unsigned long long* d_part;
+    int rc;
+    if (!filter) {
+        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, part + 64)) != FM_OK) return rc;
+        d_part = (unsigned long long*)ctx->ws_partial;
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+        HIP_TRY(ctx, launch_wide_stack_exact(*q, t, tab.st_real, pl, d_part, nullptr, ctx->stream));
+    } else {
+        size_t off = 0;
+        const size_t o_part = carve(off, part), o_list = carve(off, fp.list_bytes()), o_score = carve(off, fp.list_bytes() / 2),
+                     o_bound = carve(off, (size_t)q->n_pad * 4), o_cnt = carve(off, 16);
+        if ((rc = ws_ensure(ctx, &ctx->ws_partial, &ctx->ws_partial_bytes, off + 64)) != FM_OK) return rc;
+        char* w = (char*)ctx->ws_partial;
+        d_part = (unsigned long long*)(w + o_part);
+        HIP_TRY(ctx, hipMemsetAsync(d_part, 0xff, part, ctx->stream));
+        // (the bounds and the count are neighbours: one fill)
+        HIP_TRY(ctx, hipMemsetAsync(w + o_bound, 0, o_cnt + 16 - o_bound, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, 8, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+        HIP_TRY(ctx, launch_wide_stack_filter(*q, t, tab.st_real, fp, (uint2*)(w + o_list), (float*)(w + o_score), (unsigned*)(w + o_bound),
+                                              (unsigned long long*)(w + o_cnt), ctx->d_counters, d_part, ctx->stream));
+        HIP_TRY(ctx, launch_wide_stack_exact(*q, t, tab.st_real, pl, d_part, ctx->d_counters, ctx->stream));
+        ctx->filter_launches += 1;
+    }
+    if ((rc = wait_for_stream(ctx, consumer)) != FM_OK) return rc;
+    PairSweep ps{};
+    ps.partial = d_part; ps.nsplit = pl.nsplit; ps.ncols_alloc = pl.ncols_alloc; ps.f32_keys = 1;
+    if ((rc = coll_merge_one(ctx, &ps, tab, nq, 0, d_img, d_idx, d_dist)) != FM_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+    ctx->kernel_timed = true;
+    return FM_OK;
+}
+
 // The stacked 2-NN lists of q on the device: img / idx / dist [nq][2].  ws_partial: partial | bounds | fix list.  consumer
 // (fm_collection_knn_dev: the arrays are the caller's): the stream whose work so far the merge -- the first kernel that writes
 // them -- waits for, behind the sweep.
@@ -878,6 +938,8 @@ static int coll_knn2_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int
     }
     const CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
     const fm::Bank& t = c->stack;
+    // (a wide collection gets here from the fm_collection_wide_* calls alone: the L2-named ones have refused it)
+    if (coll_is_wide(c)) return coll_wide_knn2_device(ctx, c, q, tab, d_img, d_idx, d_dist, consumer);
     const bool i8 = t.kind == FM_BANK_I8;
     // (the pairs are the real rows'; the stack's padding rows are swept and read like any bank's)
     ctx->pending_pairs += nq * c->total;
@@ -902,14 +964,13 @@ static int coll_knn2_device(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int
     return FM_OK;
 }
 
-extern "C" int fm_collection_knn(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t k, int32_t* img, int32_t* idx, float* dist)
+// fm_collection_knn behind its checks of the handles, the kinds and k (1 .. 8; a wide collection: 1, 2) -- shared with
+// fm_collection_wide_knn, whose checks differ and whose sweep coll_knn2_device picks by the collection's kind.
+static int coll_knn_host(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t k, int32_t* img, int32_t* idx, float* dist, const char* who)
 {
-    int rc = coll_query_check(ctx, c, q, "fm_collection_knn");
-    if (rc != FM_OK) return rc;
-    if (k < 1) return fail(ctx, FM_EINVAL, "fm_collection_knn: k must be at least 1");
-    if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_collection_knn: k above 8 is not built");
+    int rc;
     const int64_t nq = q->n;
-    if (nq > 0 && (!img || !idx || !dist)) return fail(ctx, FM_EINVAL, "fm_collection_knn: output pointer is NULL");
+    if (nq > 0 && (!img || !idx || !dist)) return fail(ctx, FM_EINVAL, std::string(who) + ": output pointer is NULL");
     if (nq == 0) return FM_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int kk = k < 2 ? 2 : k;
@@ -958,15 +1019,24 @@ extern "C" int fm_collection_knn(fm_ctx* ctx, fm_collection* c, const fm_bank* q
     return cs.finish();
 }
 
-extern "C" int fm_collection_knn2_ratio(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap,
-                                        int32_t* qidx, int32_t* img, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+extern "C" int fm_collection_knn(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t k, int32_t* img, int32_t* idx, float* dist)
 {
-    int rc = coll_query_check(ctx, c, q, "fm_collection_knn2_ratio");
+    int rc = coll_query_check(ctx, c, q, "fm_collection_knn");
     if (rc != FM_OK) return rc;
+    if (k < 1) return fail(ctx, FM_EINVAL, "fm_collection_knn: k must be at least 1");
+    if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_collection_knn: k above 8 is not built");
+    return coll_knn_host(ctx, c, q, k, img, idx, dist, "fm_collection_knn");
+}
+
+// fm_collection_knn2_ratio behind coll_query_check -- shared with fm_collection_wide_knn2_ratio
+static int coll_knn2_ratio_host(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* qidx, int32_t* img,
+                                int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted, const char* who)
+{
+    int rc;
     if (n_accepted) *n_accepted = 0;
     const int64_t nq = q->n;
     if (nq == 0) return FM_OK;
-    if (cap < 0 || !qidx || !img || !tidx || !dist || !ratio) return fail(ctx, FM_EINVAL, "fm_collection_knn2_ratio: bad output arguments");
+    if (cap < 0 || !qidx || !img || !tidx || !dist || !ratio) return fail(ctx, FM_EINVAL, std::string(who) + ": bad output arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int nblk = (int)((nq + 255) / 256);
     const int64_t ccap = cap < nq ? cap : nq;
@@ -993,20 +1063,25 @@ extern "C" int fm_collection_knn2_ratio(fm_ctx* ctx, fm_collection* c, const fm_
                           {{qidx, b + o_cq, 4}, {img, b + o_cm, 4}, {tidx, b + o_ct, 4}, {dist, b + o_cd, 4}, {ratio, b + o_cr, 8}}, n_accepted);
 }
 
+extern "C" int fm_collection_knn2_ratio(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap,
+                                        int32_t* qidx, int32_t* img, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+{
+    int rc = coll_query_check(ctx, c, q, "fm_collection_knn2_ratio");
+    if (rc != FM_OK) return rc;
+    return coll_knn2_ratio_host(ctx, c, q, tau, cap, qidx, img, tidx, dist, ratio, n_accepted, "fm_collection_knn2_ratio");
+}
+
 // fm_collection_knn / fm_collection_knn2_ratio with the results left in caller-supplied device memory: the same pipelines, the
 // merge / lookup / compaction kernels handed the caller's pointers, ordered against consumer_stream as fm_knn_dev and
 // fm_knn2_ratio_dev are (api_match.hip).  Not accounted in fm_stats.
-extern "C" int fm_collection_knn_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t k, int32_t* d_img, int32_t* d_idx,
-                                     float* d_dist, void* consumer_stream)
+// fm_collection_knn_dev behind its checks of the handles, the kinds and k -- shared with fm_collection_wide_knn_dev
+static int coll_knn_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t k, int32_t* d_img, int32_t* d_idx, float* d_dist,
+                        void* consumer_stream, const char* who)
 {
-    const char* who = "fm_collection_knn_dev";
-    int rc = coll_query_check(ctx, c, q, who);
-    if (rc != FM_OK) return rc;
-    if (k < 1) return fail(ctx, FM_EINVAL, "fm_collection_knn_dev: k must be at least 1");
-    if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_collection_knn_dev: k above 8 is not built");
+    int rc;
     const int64_t nq = q->n;
     if (nq == 0) return FM_OK;
-    if (!d_img || !d_idx || !d_dist) return fail(ctx, FM_EINVAL, "fm_collection_knn_dev: output pointer is NULL");
+    if (!d_img || !d_idx || !d_dist) return fail(ctx, FM_EINVAL, std::string(who) + ": output pointer is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = check_device_ptr(ctx, d_img, who, "d_img")) != FM_OK || (rc = check_device_ptr(ctx, d_idx, who, "d_idx")) != FM_OK ||
         (rc = check_device_ptr(ctx, d_dist, who, "d_dist")) != FM_OK) return rc;
@@ -1041,6 +1116,17 @@ extern "C" int fm_collection_knn_dev(fm_ctx* ctx, fm_collection* c, const fm_ban
         HIP_TRY(ctx, hipGetLastError());
     }
     return results_written(ctx, consumer_stream);
+}
+
+extern "C" int fm_collection_knn_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t k, int32_t* d_img, int32_t* d_idx,
+                                     float* d_dist, void* consumer_stream)
+{
+    const char* who = "fm_collection_knn_dev";
+    int rc = coll_query_check(ctx, c, q, who);
+    if (rc != FM_OK) return rc;
+    if (k < 1) return fail(ctx, FM_EINVAL, "fm_collection_knn_dev: k must be at least 1");
+    if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_collection_knn_dev: k above 8 is not built");
+    return coll_knn_dev(ctx, c, q, k, d_img, d_idx, d_dist, consumer_stream, who);
 }
 
 // ---- K13: knnMatch(q, k, masks = [...]) (masked.hip) ---------------------------------------------------------------------------
@@ -1142,14 +1228,13 @@ extern "C" int fm_collection_knn_masked_dev(fm_ctx* ctx, fm_collection* c, const
     return results_written(ctx, consumer_stream);
 }
 
-extern "C" int fm_collection_knn2_ratio_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* d_rows,
-                                            int64_t* d_count, int64_t* n_accepted, void* consumer_stream)
+// fm_collection_knn2_ratio_dev behind coll_query_check -- shared with fm_collection_wide_knn2_ratio_dev
+static int coll_knn2_ratio_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* d_rows, int64_t* d_count,
+                               int64_t* n_accepted, void* consumer_stream, const char* who)
 {
-    const char* who = "fm_collection_knn2_ratio_dev";
-    int rc = coll_query_check(ctx, c, q, who);
-    if (rc != FM_OK) return rc;
+    int rc;
     if (n_accepted) *n_accepted = 0;
-    if (cap < 0 || !d_count || (cap > 0 && !d_rows)) return fail(ctx, FM_EINVAL, "fm_collection_knn2_ratio_dev: bad output arguments");
+    if (cap < 0 || !d_count || (cap > 0 && !d_rows)) return fail(ctx, FM_EINVAL, std::string(who) + ": bad output arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = check_device_ptr(ctx, d_count, who, "d_count")) != FM_OK) return rc;
     if (cap > 0 && (rc = check_device_ptr(ctx, d_rows, who, "d_rows")) != FM_OK) return rc;
@@ -1183,6 +1268,15 @@ extern "C" int fm_collection_knn2_ratio_dev(fm_ctx* ctx, fm_collection* c, const
         *n_accepted = (int64_t)cnt;
     }
     return FM_OK;
+}
+
+extern "C" int fm_collection_knn2_ratio_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* d_rows,
+                                            int64_t* d_count, int64_t* n_accepted, void* consumer_stream)
+{
+    const char* who = "fm_collection_knn2_ratio_dev";
+    int rc = coll_query_check(ctx, c, q, who);
+    if (rc != FM_OK) return rc;
+    return coll_knn2_ratio_dev(ctx, c, q, tau, cap, d_rows, d_count, n_accepted, consumer_stream, who);
 }
 
 // radiusMatch against the stacked images (K10, radius.hip): the stack is the train bank of ONE sweep whose epilogue masks
@@ -1426,16 +1520,18 @@ extern "C" int fm_collection_knn2_each(fm_ctx* ctx, fm_collection* c, const fm_b
     return cs.finish();
 }
 
-extern "C" int fm_collection_votes(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t mode, int64_t* votes)
+// fm_collection_votes behind its checks of the handles and the kinds -- shared with fm_collection_wide_votes.  A wide
+// collection's per-image lists (mode 1) are those behind fm_collection_wide_knn2_each, counted where they lie (api_pairs.hip).
+static int coll_votes_host(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t mode, int64_t* votes, const char* who)
 {
-    int rc = coll_query_check(ctx, c, q, "fm_collection_votes");
-    if (rc != FM_OK) return rc;
-    if (mode != 0 && mode != 1) return fail(ctx, FM_EINVAL, "fm_collection_votes: mode must be 0 (stacked lists) or 1 (per-image lists)");
+    int rc;
+    if (mode != 0 && mode != 1) return fail(ctx, FM_EINVAL, std::string(who) + ": mode must be 0 (stacked lists) or 1 (per-image lists)");
     const int64_t nq = q->n, ni = (int64_t)c->rows.size();
     if (ni == 0) return FM_OK;
-    if (!votes) return fail(ctx, FM_EINVAL, "fm_collection_votes: votes is NULL");
+    if (!votes) return fail(ctx, FM_EINVAL, std::string(who) + ": votes is NULL");
     for (int64_t i = 0; i < ni; ++i) votes[i] = 0;
     if (nq == 0) return FM_OK;
+    if (mode == 1 && coll_is_wide(c)) return coll_wide_each_votes(ctx, c, q, tau, votes);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t vb = align256((size_t)ni * 8);
     const size_t lb = align256((size_t)(mode == 0 ? 1 : ni) * nq * 8);
@@ -1457,6 +1553,85 @@ extern "C" int fm_collection_votes(fm_ctx* ctx, fm_collection* c, const fm_bank*
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, d2h(ctx, votes, d_votes, (size_t)ni * 8));
     return cs.finish();
+}
+
+extern "C" int fm_collection_votes(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t mode, int64_t* votes)
+{
+    int rc = coll_query_check(ctx, c, q, "fm_collection_votes");
+    if (rc != FM_OK) return rc;
+    return coll_votes_host(ctx, c, q, tau, mode, votes, "fm_collection_votes");
+}
+
+// ---------------------------------------------------------------------------------------
+// Wide stacked knnMatch: fm_collection_wide_knn(_dev), fm_collection_wide_knn2_ratio(_dev), fm_collection_wide_votes
+// ---------------------------------------------------------------------------------------
+// cv2.BFMatcher.add(images) + knnMatch(query, k) against ALL images of a WIDE collection at once: the calls above under names
+// of their own, as every wide feature has come.  The L2-named calls keep refusing a wide collection and a wide query bank
+// (coll_query_check); these run the same pipelines -- merge, ratio test, compaction, votes -- behind K14's sweep over the
+// stack (coll_wide_knn2_device; the kernels and why the bank-pair ones cannot serve: wide_stack.hip).
+// Steps 1 .. 3 of the header's error order: the handles, the kinds, the widths.  Then the tables (fm_collection_train).
+static int coll_wide_stack_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const char* who_, const char* narrow)
+{
+    const std::string who(who_);
+    int rc = coll_check(ctx, c, who_);
+    if (rc != FM_OK) return rc;
+    if (!q) return fail(ctx, FM_EINVAL, who + ": query bank is NULL");
+    if (q->kind != FM_BANK_F32W || (!c->rows.empty() && !coll_is_wide(c)))
+        return fail(ctx, FM_EINVAL, who + ": the collection and the query bank must be wide float (fm_collection_add_wide; FM_BANK_F32W: "
+                                          "fm_bank_create_f32 with 129 .. 256 values per row); " + narrow +
+                                          " is the call that serves the L2 kinds and the binary (Hamming) kind");
+    if (c->dim != 0 && q->dim != c->dim) return fail(ctx, FM_EINVAL, who + ": the query's width differs from the collection's");
+    return fm_collection_train(ctx, c);
+}
+
+static int coll_wide_k_check(fm_ctx* ctx, int32_t k, const char* who)
+{
+    if (k < 1) return fail(ctx, FM_EINVAL, std::string(who) + ": k must be at least 1");
+    if (k > 2) return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": k >= 3 is not built for wide float banks (fm_knn serves them with k <= 2 too)");
+    return FM_OK;
+}
+
+extern "C" int fm_collection_wide_knn(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t k, int32_t* img, int32_t* idx, float* dist)
+{
+    const char* who = "fm_collection_wide_knn";
+    int rc = coll_wide_stack_check(ctx, c, q, who, "fm_collection_knn");
+    if (rc != FM_OK || (rc = coll_wide_k_check(ctx, k, who)) != FM_OK) return rc;
+    return coll_knn_host(ctx, c, q, k, img, idx, dist, who);
+}
+
+extern "C" int fm_collection_wide_knn_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, int32_t k, int32_t* d_img, int32_t* d_idx,
+                                          float* d_dist, void* consumer_stream)
+{
+    const char* who = "fm_collection_wide_knn_dev";
+    int rc = coll_wide_stack_check(ctx, c, q, who, "fm_collection_knn_dev");
+    if (rc != FM_OK || (rc = coll_wide_k_check(ctx, k, who)) != FM_OK) return rc;
+    return coll_knn_dev(ctx, c, q, k, d_img, d_idx, d_dist, consumer_stream, who);
+}
+
+extern "C" int fm_collection_wide_knn2_ratio(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* qidx,
+                                             int32_t* img, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
+{
+    const char* who = "fm_collection_wide_knn2_ratio";
+    int rc = coll_wide_stack_check(ctx, c, q, who, "fm_collection_knn2_ratio");
+    if (rc != FM_OK) return rc;
+    return coll_knn2_ratio_host(ctx, c, q, tau, cap, qidx, img, tidx, dist, ratio, n_accepted, who);
+}
+
+extern "C" int fm_collection_wide_knn2_ratio_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t cap, int32_t* d_rows,
+                                                 int64_t* d_count, int64_t* n_accepted, void* consumer_stream)
+{
+    const char* who = "fm_collection_wide_knn2_ratio_dev";
+    int rc = coll_wide_stack_check(ctx, c, q, who, "fm_collection_knn2_ratio_dev");
+    if (rc != FM_OK) return rc;
+    return coll_knn2_ratio_dev(ctx, c, q, tau, cap, d_rows, d_count, n_accepted, consumer_stream, who);
+}
+
+extern "C" int fm_collection_wide_votes(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t mode, int64_t* votes)
+{
+    const char* who = "fm_collection_wide_votes";
+    int rc = coll_wide_stack_check(ctx, c, q, who, "fm_collection_votes");
+    if (rc != FM_OK) return rc;
+    return coll_votes_host(ctx, c, q, tau, mode, votes, who);
 }
 
 // ---------------------------------------------------------------------------------------

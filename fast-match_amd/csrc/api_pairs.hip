@@ -194,6 +194,9 @@ struct CollPairsArgs {
     // fm_collection_wide_*_each: "pair" p is (q, image p) -- a is the wide query bank, outside the stack -- for every image;
     // knn2: the forward slots alone, their merged lists [n_images][nq][2] copied to k_idx / k_dist (host), no join
     const fm::Bank* q = nullptr; bool knn2 = false; int32_t* k_idx = nullptr; float* k_dist = nullptr;
+    // knn2 with k_votes (fm_collection_wide_votes, mode 1): the lists stay on the device; tau's ratio test on every list,
+    // counted per image into k_votes [n_images] (host)
+    int64_t* k_votes = nullptr;
 };
 
 // One chunk of consecutive pairs [p0, p1): what its kernels cover (PairsSpan) and where its tables lie in the call's table image.
@@ -277,7 +280,7 @@ static int pairs_check(fm_ctx* ctx, fm_collection* c, const int32_t* pairs, int6
     if (cap < 0) return fail(ctx, FM_EINVAL, who + ": cap is negative");
     *done = true;
     if (a.knn2) {
-        if (ni * nq > 0 && (!a.k_idx || !a.k_dist)) return fail(ctx, FM_EINVAL, who + ": idx / dist is NULL");
+        if (!a.k_votes && ni * nq > 0 && (!a.k_idx || !a.k_dist)) return fail(ctx, FM_EINVAL, who + ": idx / dist is NULL");
         if (ni * nq == 0) return FM_OK;
     } else if (a.to_dev) {
         if (!a.d_offsets) return fail(ctx, FM_EINVAL, who + ": d_offsets is NULL");
@@ -740,6 +743,18 @@ static int pairs_deliver_knn2(PairsCall& k, CallScope& cs)
     return cs.finish();
 }
 
+// knn2 with k_votes: the ratio test on the merged lists where they lie, counted per image (coll_votes_kernel's per-image form).
+// The counts take the offsets' place in ws_out ([n_images + 1] words that a knn2 call does not use).
+static int pairs_deliver_votes(PairsCall& k, CallScope& cs)
+{
+    fm_ctx* ctx = k.ctx;
+    unsigned long long* d_votes = (unsigned long long*)(k.b + k.o_off);
+    HIP_TRY(ctx, hipMemsetAsync(d_votes, 0, (size_t)k.ni * 8, ctx->stream));
+    HIP_TRY(ctx, launch_coll_votes(nullptr, k.l_idx, k.l_dist, k.nq, k.ni, k.a.tau, d_votes, ctx->stream));
+    HIP_TRY(ctx, d2h(ctx, k.a.k_votes, d_votes, (size_t)k.ni * 8));
+    return cs.finish();
+}
+
 // Device form: the rows and offsets are in the caller's memory behind "the results are written".
 static int pairs_deliver_dev(PairsCall& k)
 {
@@ -803,7 +818,7 @@ static int coll_pairs_mutual(fm_ctx* ctx, fm_collection* c, const int32_t* pairs
         if (c->stack.kind != FM_BANK_F32) HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));   // (the float32 route brackets its sweeps itself)
         ctx->kernel_timed = true;
     }
-    if (a.knn2) return pairs_deliver_knn2(k, cs);
+    if (a.knn2) return a.k_votes ? pairs_deliver_votes(k, cs) : pairs_deliver_knn2(k, cs);
     if (a.to_dev) return pairs_deliver_dev(k);
     return pairs_deliver_host(k, cs);
 }
@@ -860,6 +875,15 @@ extern "C" int fm_collection_wide_knn2_each(fm_ctx* ctx, fm_collection* c, const
     CollPairsArgs a{"fm_collection_wide_knn2_each", 0.0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, FM_NO_STREAM, nullptr};
     a.knn2 = true; a.k_idx = idx; a.k_dist = dist;
     return coll_wide_each(ctx, c, q, "fm_collection_knn2_each", a);
+}
+
+// fm_collection_wide_votes, mode 1 (api_collection.hip checks the arguments): the sweep above with the lists left on the device,
+// the per-image ratio test counted there.  n_images > 0 and q->n > 0.
+int coll_wide_each_votes(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t* votes)
+{
+    CollPairsArgs a{"fm_collection_wide_votes", tau, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, FM_NO_STREAM, nullptr};
+    a.knn2 = true; a.k_votes = votes;
+    return coll_wide_each(ctx, c, q, "fm_collection_votes", a);
 }
 
 extern "C" int fm_collection_wide_mutual_ratio_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int32_t symmetric, int64_t cap,

@@ -57,3 +57,13 @@ int coll_merge_one(fm_ctx* ctx, const PairSweep* ps, fm::CollTab tab, int64_t nq
 hipError_t launch_coll_sqrt_fix(const unsigned* fix, const int8_t* col_rows, const int32_t* col_norm, const int8_t* red_rows,
                                 const int32_t* red_norm, int nred, fm::CollTab tab, int64_t out, int32_t* img, int32_t* idx, float* dist,
                                 hipStream_t stream);
+// One launch of coll_votes_kernel on `stream`: the ratio test d0 / d1 < tau on 2-NN lists, counted per image into votes.
+// img set: stacked lists [nq][2], counted at the first neighbour's image (ny = 1); img null: per-image lists [ny][nq][2].
+hipError_t launch_coll_votes(const int32_t* img, const int32_t* idx, const float* dist, int64_t nq, int64_t ny, double tau,
+                             unsigned long long* votes, hipStream_t stream);
+
+// ---- api_pairs.hip ---------------------------------------------------------------------------------------------------------
+// fm_collection_wide_votes, mode 1: the per-image 2-NN sweep of fm_collection_wide_knn2_each with the lists left on the device
+// and tau's ratio test counted per image into votes [n_images] (host).  The caller has checked the handles, the kinds and the
+// widths; n_images > 0 and q->n > 0.
+int coll_wide_each_votes(fm_ctx* ctx, fm_collection* c, const fm_bank* q, double tau, int64_t* votes);

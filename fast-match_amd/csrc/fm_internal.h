@@ -356,6 +356,17 @@ hipError_t launch_wide_masked_filter(const Bank& q, const Bank& t, int ktop, con
 // the masked exact kernel under K5's run_flag protocol; writes every key of `partial`
 hipError_t launch_wide_masked_exact(const Bank& q, const Bank& t, int ktop, const RowReducePlan& plan, const unsigned long long* mask,
                                     int64_t mwords, unsigned long long* partial, const int* run_flag, hipStream_t stream);
+// ---- K14 over a wide collection's stack (wide_stack.hip): the top-2 sweeps of fm_collection_wide_knn and its kin.  stack: the
+// collection's stack as one bank (n = n_pad = whole 128-row stages); st_real: the real rows per stage (coll_tab.h), which the
+// kernels test every reduced row against; keys carry PHYSICAL rows.  Plans: plan_wide_filter / plan_rowreduce_f32 over
+// (q.n_pad, stack.n_pad); partial: [plan.nsplit][plan.ncols_alloc][2] ----
+// the stack filter + launch_wide_rescore (presets as for launch_wide_filter)
+hipError_t launch_wide_stack_filter(const Bank& q, const Bank& stack, const int32_t* st_real, const WideFilterPlan& plan, uint2* list,
+                                    float* lscore, unsigned* gbound, unsigned long long* cnt, int* flag, unsigned long long* partial,
+                                    hipStream_t stream);
+// the stack exact kernel under K5's run_flag protocol; writes every key of `partial`
+hipError_t launch_wide_stack_exact(const Bank& q, const Bank& stack, const int32_t* st_real, const RowReducePlan& plan,
+                                   unsigned long long* partial, const int* run_flag, hipStream_t stream);
 // Table forms (top-2) for a chunk of image pairs of one wide stack (fm_collection_pairs_mutual_ratio): a slot is one direction
 // of one pair, both operands views of `stack` that start on a 128-row stage -- or, with WideTableLaunch::outside, one of them
 // rows of a bank outside the stack (fm_collection_wide_mutual_ratio_each: a query bank).  The slots lie side by side in the chunk's

@@ -614,7 +614,8 @@ class BFMatcher(object):
         """``add`` for WIDE float images: every entry a [n, dim] float array with 129 <= dim <= 256 (learned 256-D descriptors;
         n may be 0), one width per collection, NORM_L2.  A collection takes either ``add`` or ``add_wide`` images; a wide one
         (``fm_collection_add_wide``) serves ``matchPairs`` / ``matchPairs_arrays`` and, for a wide query,
-        ``mutualRatioMatchWideEach`` / ``mutualRatioMatchWideEach_arrays`` / ``knnMatchWideEach_arrays``; every other collection
+        ``mutualRatioMatchWideEach`` / ``mutualRatioMatchWideEach_arrays`` / ``knnMatchWideEach_arrays`` and, against all images at
+        once, ``knnMatchWide`` / ``knnMatchWide_arrays`` / ``ratioMatchWide_arrays`` / ``votesWide``; every other collection
         method raises ``ValueError`` before anything is uploaded."""
         if self.normType != NORM_L2:
             raise ValueError("BFMatcher.add_wide: wide float images are NORM_L2 descriptors")
@@ -654,10 +655,12 @@ class BFMatcher(object):
         if self.empty():
             raise ValueError("%s: no train descriptors (add() some, or pass a train array)" % who)
         if self._wide and who not in ("BFMatcher.train", "BFMatcher.matchPairs", "BFMatcher.mutualRatioMatchWideEach",
-                                      "BFMatcher.knnMatchWideEach", "BFMatcher.wideFastMatchEach"):
+                                      "BFMatcher.knnMatchWideEach", "BFMatcher.wideFastMatchEach", "BFMatcher.knnMatchWide",
+                                      "BFMatcher.ratioMatchWide", "BFMatcher.votesWide"):
             raise ValueError("%s is not built for a wide collection (images of 129 .. 256 values per row, add_wide): "
                              "matchPairs, matchPairs_arrays and, for a wide query, mutualRatioMatchWideEach(_arrays), "
-                             "wideFastMatchEach(_arrays) and knnMatchWideEach_arrays are" % who)
+                             "wideFastMatchEach(_arrays), knnMatchWideEach_arrays and, against all images at once, "
+                             "knnMatchWide(_arrays), ratioMatchWide_arrays and votesWide are" % who)
 
     def train(self):
         self._check_collection("BFMatcher.train")
@@ -953,6 +956,48 @@ class BFMatcher(object):
         finally:
             if tmp:
                 qb.close()
+
+    def _wide_stacked(self, who, queryDescriptors, call):
+        """``call(collection, query bank)`` behind :meth:`_wide_query`'s checks: the wide calls against ALL images at once."""
+        q = self._wide_query(who, queryDescriptors)
+        coll = self.train()
+        qb, tmp = (q, False) if isinstance(q, _ffi.Bank) else (coll.ctx.bank(q), True)
+        try:
+            return call(coll, qb)
+        finally:
+            if tmp:
+                qb.close()
+
+    def knnMatchWide_arrays(self, queryDescriptors, k):
+        """(img, idx, dist) [nq, k], k = 1 or 2, of a wide query against ALL images of a WIDE collection (``add_wide``) at once:
+        ``imgIdx``, ``trainIdx`` inside that image, distance -- ``bf_match_arrays(query, the images' rows concatenated, k)``
+        with every hit located; -1 / -1 / inf where the collection has fewer than k rows (``Collection.wide_knn``).
+        ``ValueError`` before anything is uploaded: k outside 1, 2, and :meth:`mutualRatioMatchWideEach_arrays`' refusals."""
+        k = int(k)
+        if k < 1 or k > 2:
+            raise ValueError("BFMatcher.knnMatchWide: k = %d: wide float descriptors get k-NN lists for k = 1, 2" % k)
+        return self._wide_stacked("BFMatcher.knnMatchWide", queryDescriptors, lambda coll, qb: coll.wide_knn(qb, k))
+
+    def knnMatchWide(self, queryDescriptors, k):
+        """``cv2.BFMatcher.knnMatch(query, k)`` against a WIDE collection: one list of up to k ``DMatch`` per query row, nearest
+        first, ``imgIdx`` the image and ``trainIdx`` the row inside it (:meth:`knnMatchWide_arrays`)."""
+        img, idx, dist = self.knnMatchWide_arrays(queryDescriptors, k)
+        return [[DMatch(qi, idx[qi, j], dist[qi, j], img[qi, j]) for j in range(idx.shape[1]) if idx[qi, j] >= 0]
+                for qi in range(idx.shape[0])]
+
+    def ratioMatchWide_arrays(self, queryDescriptors, tau):
+        """(qidx, img, tidx, dist, ratio) of the query rows whose 2-NN list over ALL images of a WIDE collection passes Lowe's
+        test d0 / d1 < tau, ascending ``qidx`` (``Collection.wide_knn2_ratio``).  The refusals are
+        :meth:`mutualRatioMatchWideEach_arrays`'."""
+        return self._wide_stacked("BFMatcher.ratioMatchWide", queryDescriptors, lambda coll, qb: coll.wide_knn2_ratio(qb, tau))
+
+    def votesWide(self, queryDescriptors, tau, mode=0):
+        """:meth:`votes` of a wide query on a WIDE collection: int64[n_images] (``Collection.wide_votes``; mode 0: the test on
+        the lists over all images, counted at the first neighbour's image; 1: on every image's own 2-NN lists).  The refusals
+        are :meth:`mutualRatioMatchWideEach_arrays`', and a mode other than 0, 1."""
+        if mode not in (0, 1):
+            raise ValueError("BFMatcher.votesWide: mode must be 0 (stacked lists) or 1 (per-image lists)")
+        return self._wide_stacked("BFMatcher.votesWide", queryDescriptors, lambda coll, qb: coll.wide_votes(qb, tau, mode))
 
     def matchPairs_arrays(self, pairs=None, ratio=0.8, symmetric=False):
         """The added images matched AGAINST EACH OTHER -- the match graph of structure from motion and stitching (COLMAP's

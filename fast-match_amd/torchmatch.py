@@ -961,6 +961,83 @@ class Collection(object):
             if not is_bank:
                 qb.close()
 
+    def _wide_stacked_query(self, who, q):
+        """The query bank of a wide stacked call and the banks made for it -- ``ValueError`` before the library is touched for a
+        collection that is not wide and for a query that is not a wide operand."""
+        if not self._wide:
+            raise ValueError("Collection.%s: the collection is not a wide one (add_wide); knn / ratio_match serve the other "
+                             "kinds" % who)
+        x = _wide_operand("Collection.%s" % who, q)
+        if isinstance(x, _ffi.Bank):
+            return x, []
+        qb = bank(x, context=self._context)
+        return qb, [qb]
+
+    def wide_knn(self, q, k):
+        """``knn`` on a WIDE collection (``add_wide``): the k nearest rows of ALL images' stacked rows, ``(img int32, idx int32,
+        dist float32)`` [nq, k] CUDA tensors shaped like ``knn``'s -- ``knn(q, the images' rows concatenated, k)`` with every
+        hit located; -1 / -1 / inf beyond the collection's rows.  k = 1, 2.  ``q``: a wide ``Bank`` or a CUDA tensor [nq, dim]
+        of float32 / float16 / bfloat16 with 129 <= dim <= 256.  Enqueued, no host wait (``fm_collection_wide_knn_dev``).
+        ``ValueError`` before the library is touched for a collection that is not wide and for k outside 1, 2."""
+        import torch
+        k = int(k)
+        if k < 1 or k > 2:
+            raise ValueError("Collection.wide_knn: k = %d: wide float descriptors get k-NN lists for k = 1, 2" % k)
+        qb, made = self._wide_stacked_query("wide_knn", q)
+        try:
+            coll = self._collection(qb.ctx)
+            stream, dev = _stream_and_device(qb.ctx)
+            img = torch.empty((qb.n, k), dtype=torch.int32, device=dev)
+            idx = torch.empty((qb.n, k), dtype=torch.int32, device=dev)
+            dist = torch.empty((qb.n, k), dtype=torch.float32, device=dev)
+            p = (lambda t: t.data_ptr()) if qb.n else (lambda t: 0)
+            coll.wide_knn_dev(qb, k, p(img), p(idx), p(dist), consumer_stream=stream)
+            return img, idx, dist
+        finally:
+            for b in made:
+                b.close()
+
+    def wide_ratio_match(self, q, tau):
+        """``ratio_match`` on a WIDE collection: Lowe's test on the 2-NN lists over ALL images' rows, ``(qidx, img, tidx int32
+        [m], dist float32 [m])``, ascending query index (``fm_collection_wide_knn2_ratio_dev``).  ``q`` as in ``wide_knn``.
+        One host wait (the count sizes the outputs)."""
+        import torch
+        qb, made = self._wide_stacked_query("wide_ratio_match", q)
+        try:
+            coll = self._collection(qb.ctx)
+            stream, dev = _stream_and_device(qb.ctx)
+            cap = qb.n
+            rows = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=dev)
+            count = torch.empty(1, dtype=torch.int64, device=dev)
+            m = coll.wide_knn2_ratio_dev(qb, float(tau), rows.data_ptr(), count.data_ptr(), cap, want_count=True,
+                                         consumer_stream=stream)
+            rows = rows[:min(m, cap)]
+            return (rows[:, 0].contiguous(), rows[:, 1].contiguous(), rows[:, 2].contiguous(),
+                    rows[:, 3].contiguous().view(torch.float32))
+        finally:
+            for b in made:
+                b.close()
+
+    def wide_votes(self, q, tau, mode=0):
+        """Query rows that pass the ratio test d0 / d1 < tau per image of a WIDE collection: an int64 [n_images] CUDA tensor
+        (mode 0: the test on the lists over all images, counted at the first neighbour's image; 1: on every image's own 2-NN
+        lists).  ``q`` as in ``wide_knn``.  The library counts on the device and hands the counts to the host
+        (``fm_collection_wide_votes``); they are put back on the query's device: one host wait."""
+        import torch
+        if mode not in (0, 1):
+            raise ValueError("Collection.wide_votes: mode must be 0 (stacked lists) or 1 (per-image lists)")
+        qb, made = self._wide_stacked_query("wide_votes", q)
+        try:
+            coll = self._collection(qb.ctx)
+            _, dev = _stream_and_device(qb.ctx)
+            # (a host-form call: the query's rows must be there when it runs on the context's stream)
+            with torch.cuda.device(dev):
+                torch.cuda.current_stream().synchronize()
+            return torch.from_numpy(coll.wide_votes(qb, float(tau), int(mode))).to(dev)
+        finally:
+            for b in made:
+                b.close()
+
     def clear(self):
         if self._coll is not None:
             self._coll.clear()

@@ -80,7 +80,9 @@ typedef struct fm_bank fm_bank;
  * only -- fm_wide_self_dist, fm_wide_self_dist_batch, fm_wide_set_selfdist, fm_wide_match_ratio, fm_wide_match_accepted,
  * fm_wide_match_accepted_dev, fm_collection_wide_match_accepted_each, fm_collection_wide_match_accepted_each_dev; still
  * revision 12, additions only -- fm_wide_radius_match, fm_wide_radius_match_dev, fm_collection_wide_radius_match,
- * fm_collection_wide_radius_match_dev; still revision 12, additions only -- fm_wide_knn_masked, fm_wide_knn_masked_dev).  A binding
+ * fm_collection_wide_radius_match_dev; still revision 12, additions only -- fm_wide_knn_masked, fm_wide_knn_masked_dev; still
+ * revision 12, additions only -- fm_collection_wide_knn, fm_collection_wide_knn_dev, fm_collection_wide_knn2_ratio,
+ * fm_collection_wide_knn2_ratio_dev, fm_collection_wide_votes).  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.              */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -304,7 +306,9 @@ int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t
  * fm_mask_create_coll: FM_EUNSUPPORTED with a message that says "wide", straight after the NULL-handle checks.  Also not
  * built: k >= 3, LDS staging of the streamed operand, computing a pair's tiles once for both directions.  (Radius queries
  * against a wide collection come under names of their own, "Wide radiusMatch" below: fm_collection_wide_radius_match(_dev);
- * fm_collection_radius_match(_dev) keeps refusing.)
+ * fm_collection_radius_match(_dev) keeps refusing.)  (The stacked knn forms against a wide collection -- knnMatch over all
+ * images, the ratio test on it, votes -- come under names of their own too, "Wide stacked knnMatch" below:
+ * fm_collection_wide_knn(_dev), fm_collection_wide_knn2_ratio(_dev), fm_collection_wide_votes; the calls listed keep refusing.)
  * Wide QUERIES: a wide query bank is matched against every image of a wide collection, image by image, by entry points of
  * their own -- the calls listed above keep refusing, and their messages name these: fm_collection_wide_knn2_each,
  * fm_collection_wide_mutual_ratio_each and fm_collection_wide_mutual_ratio_each_dev (the localisation pattern: one query image
@@ -340,7 +344,8 @@ int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t
  * for wide collections, k >= 3, masks, radius queries, sharing one resident copy of the query's B operand across the forward
  * slots of a chunk, LDS staging of the streamed operand, computing an image's tiles once for both directions.  (Radius
  * queries of a wide query bank against the STACKED images of a wide collection now come under a name of their own:
- * fm_collection_wide_radius_match(_dev), "Wide radiusMatch" below.)                                                      */
+ * fm_collection_wide_radius_match(_dev), "Wide radiusMatch" below; the stacked knn forms under theirs, "Wide stacked
+ * knnMatch" below.)                                                                                                       */
 int  fm_bank_destroy(fm_ctx* ctx, fm_bank* bank);
 int  fm_bank_info(const fm_bank* bank, int64_t* n, int* dim, int* kind);
 /* Attach per-row self distances (Metric_Cache.*["distances"], float64, cache.pyx:252,273)
@@ -551,7 +556,8 @@ int fm_wide_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
  * the collection forms) NULL with cap > 0 (FM_EINVAL); for the _dev forms the device-pointer checks of fm_radius_match_dev.
  * Accounted in fm_stats like fm_radius_match: the host forms add nq * real rows pairs, the _dev forms are not accounted.
  * Not built: masks; compactResult = True; one sweep that counts and fills in a single pass; k >= 3 and the stacked knn forms
- * on a wide collection.                                                                                                  */
+ * on a wide collection.  (The stacked knn forms on a wide collection have since come, k = 1, 2: "Wide stacked knnMatch"
+ * below.)                                                                                                                 */
 int fm_wide_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* radius /*[nq] or NULL*/,
                          float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* idx, float* dist,
                          int64_t* n_total);
@@ -1074,6 +1080,64 @@ int  fm_collection_knn_masked_dev(fm_ctx* ctx, fm_collection* coll, const fm_ban
 int  fm_wide_knn_masked(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, int32_t k, int32_t* idx /*[nq*k]*/, float* dist /*[nq*k]*/);
 int  fm_wide_knn_masked_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, int32_t k, int32_t* d_idx /*device [nq*k]*/,
                             float* d_dist /*device [nq*k]*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+
+/* ---- Wide stacked knnMatch: a wide query against ALL images of a wide collection at once (K14 over the stack, csrc/wide_stack.hip) --
+ * cv2.BFMatcher.add(images) followed by knnMatch(query, k) for wide float descriptors (FM_BANK_F32W, 129 .. 256 values per row):
+ * "which image of my database does this query row match", every hit carrying imgIdx -- retrieval with 256-D learned
+ * descriptors: 2-NN over the whole database, Lowe's ratio against the whole database, votes per image.
+ * fm_collection_knn(_dev), fm_collection_knn2_ratio(_dev) and fm_collection_votes keep refusing a wide collection and a wide
+ * query bank exactly as before; the five calls here, with the argument lists of their L2 namesakes word for word, are the
+ * ones that serve them: fm_collection_wide_knn, fm_collection_wide_knn_dev, fm_collection_wide_knn2_ratio,
+ * fm_collection_wide_knn2_ratio_dev, fm_collection_wide_votes.
+ * Contract.  Let T be the real rows of the images concatenated in image order.
+ *   fm_collection_wide_knn(q, coll, k) equals fm_knn(q, bank(T), k) bit for bit, every entry reported as (img, row inside the
+ *   image).  The distances are K14's chain: sqrtf(s), s = fmaf(v_k, v_k, s), k ascending over the real dim.  Lists ascend
+ *   strictly by (distance bits, img, row).  Where the collection has fewer than k real rows the entry is -1 / -1 / +inf; a NaN
+ *   or +inf distance is never listed.  k = 1, 2; k >= 3 is FM_EUNSUPPORTED, as fm_knn answers for wide banks; k < 1 is
+ *   FM_EINVAL.
+ *   fm_collection_wide_knn2_ratio follows fm_collection_knn2_ratio's rules on that list: float64 d0 / d1 < tau, d1 == 0
+ *   rejected, ascending query index, cap, the full count in *n_accepted (the _dev form: 16-byte rows {query, image, row inside
+ *   the image, float32 distance bits}, *d_count the rows that are there).
+ *   fm_collection_wide_votes mode 0 is the same test counted at the first neighbour's image; mode 1 is the per-image ratio
+ *   test on the lists behind fm_collection_wide_knn2_each (which stay on the device), counted per image.
+ *   Empty images keep their index.  A collection on which no add has succeeded is valid, and so are nq = 0 and a collection of
+ *   empty images only.  No option changes a result.  The stack's fp16 scale and largest scaled squared norm are read at the
+ *   call: a later add may rewrite them.
+ * Routes ("f32_filter" 0 / 1 / 2 and "f32_nsplit" as for every wide sweep): ONE sweep over the whole physical stack.  The
+ *   stack has zero-filled padding rows behind EVERY image (each starts on a 128-row stage), which a bank-pair kernel -- it
+ *   drops padding by index at a bank's end only -- would take for near neighbours (distance |q|: 1.0 for unit-norm rows, nearer
+ *   than almost every real row); so the kernels here read the collection's per-stage table of real rows: a reduced row is real
+ *   iff (row & 127) < real_rows[row >> 7], one uniform table read per 16-row tile, and a padding row leaves by INDEX before it
+ *   can enter a list, a bound or a record.  The fp16 filter on the MATRIX CORES (v_mfma_f32_16x16x32_f16, K14's filter shape;
+ *   a tile without a real row skips its matrix instructions and its operand fetch) for calls of 4e6 real pairs or more
+ *   ("f32_filter" 2: always) on operands the filter can take, then K14's exact rescoring of the recorded pairs; everything
+ *   else -- "f32_filter" 0, a value on either side that is not finite, scale exponents more than 8 apart -- and a call whose
+ *   record list overflowed (256 records per query row, 2^20 at least; the call is redone: the fallback) takes the exact
+ *   kernel, K14's tiling on the vector ALUs with the same table test.  fm_f32_filter_stats counts one launch per filtered call
+ *   and one fallback per call that is redone.  The merge writes (img, row inside the image, distance); the ratio test, the
+ *   compaction and the votes behind it are those of the L2 namesakes.
+ * Errors, in this order: (1) NULL handles, or a collection of another context: FM_EINVAL; (2) a query that is not FM_BANK_F32W
+ *   (even when it is empty: the wide creators make an empty bank wide), or a non-empty collection that is not wide: FM_EINVAL,
+ *   with a message that names the L2-named call that serves it (which serves the binary, Hamming, kind too); (3) widths that
+ *   differ: FM_EINVAL; (4) k, or for the votes the mode (FM_EINVAL unless 0 or 1); (5) the output pointers: the host forms check
+ *   NULL with nq > 0 (votes: with n_images > 0), the _dev forms use fm_collection_knn_dev's and
+ *   fm_collection_knn2_ratio_dev's pointer checks.
+ * Streams and accounting: the _dev forms order themselves against consumer_stream in both directions, like their namesakes,
+ *   and are not accounted in fm_stats; the host forms add nq * real rows pairs (votes mode 1: nq * real rows as well, image by
+ *   image).
+ * Not built: k >= 3; masks on a wide collection (fm_mask_create_coll keeps refusing it); fm_collection_wide_xcheck1_each; a
+ *   stacked sweep shared by several query banks.                                                                          */
+int  fm_collection_wide_knn(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, int32_t k,
+                            int32_t* img /*[nq*k]*/, int32_t* idx /*[nq*k]*/, float* dist /*[nq*k]*/);
+int  fm_collection_wide_knn_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, int32_t k, int32_t* d_img /*device [nq*k]*/,
+                                int32_t* d_idx /*device [nq*k]*/, float* d_dist /*device [nq*k]*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_wide_knn2_ratio(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
+                                   int32_t* qidx, int32_t* img, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted);
+int  fm_collection_wide_knn2_ratio_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int64_t cap,
+                                       int32_t* d_rows /*device [cap][4]*/, int64_t* d_count /*device*/, int64_t* n_accepted /*host, or NULL*/,
+                                       void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_wide_votes(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, double tau, int32_t mode,
+                              int64_t* votes /*[n_images]*/);
 
 /* Classic Ratio-Match in one call: knnMatch(q, t, k=2) then ratio = m[0].distance /
  * m[1].distance (float64) and ratio < tau  -- Classic Matching.ipynb cell 3 (JSON 59-72), the
