@@ -230,6 +230,11 @@ SYMBOLS = {
     "fm_wide_knn_masked_dev": (_INT, [_P, _P, _P, _P, _I32, _P, _P, _P]),
     "fm_collection_knn_masked": (_INT, [_P, _P, _P, _P, _I32, _P, _P, _P]),
     "fm_collection_knn_masked_dev": (_INT, [_P, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    # masked radiusMatch on all four bank kinds (csrc/radius.hip, the masked sweeps): the unmasked lists with `mask` behind the train operand
+    "fm_radius_match_masked": (_INT, [_P, _P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_radius_match_masked_dev": (_INT, [_P, _P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    "fm_collection_radius_match_masked": (_INT, [_P, _P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "fm_collection_radius_match_masked_dev": (_INT, [_P, _P, _P, _P, _P, ctypes.c_float, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
 }
 
 _lib = None
@@ -657,6 +662,47 @@ class Collection(object):
             if int(total.value) != n:
                 raise FastMatchHipError("%s: %d entries on the second call, %d on the first" % (_name, total.value, n))
         return offsets, img, idx, dist
+
+    def radius_match_masked(self, q, mask, r):
+        """``fm_collection_radius_match_masked``: ``radius_match`` (an integer, float32 or binary collection: for a binary one
+        ``hamming_radius_match``) with every entry whose pair ``mask`` (``Collection.mask``) forbids removed; nothing else
+        changes.  Arguments after ``mask`` and the return value as ``radius_match``."""
+        nq = q.n
+        if np.ndim(r) == 0:
+            rad, r_all = None, float(np.float32(r))
+        else:
+            rad = np.ascontiguousarray(r, dtype=np.float32).reshape(-1)
+            if rad.shape[0] != nq:
+                raise ValueError("radius_match_masked: %d radii for %d query rows" % (rad.shape[0], nq))
+            r_all = 0.0
+        rp = _ptr(rad) if rad is not None and nq > 0 else None
+        mh = mask.handle if mask is not None else None
+        offsets = np.zeros(nq + 1, dtype=np.int64)
+        total = _I64(0)
+        fn = self.ctx.lib.fm_collection_radius_match_masked
+        self.ctx._check(fn(self.ctx.handle, self.handle, q.handle, mh, rp, r_all, 0, _ptr(offsets), None, None, None, ctypes.byref(total)))
+        n = int(total.value)
+        img = np.empty(n, dtype=np.int32)
+        idx = np.empty(n, dtype=np.int32)
+        dist = np.empty(n, dtype=np.float32)
+        if n > 0:
+            self.ctx._check(fn(self.ctx.handle, self.handle, q.handle, mh, rp, r_all, n, _ptr(offsets), _ptr(img), _ptr(idx), _ptr(dist),
+                               ctypes.byref(total)))
+            if int(total.value) != n:
+                raise FastMatchHipError("fm_collection_radius_match_masked: %d entries on the second call, %d on the first" % (total.value, n))
+        return offsets, img, idx, dist
+
+    def radius_match_masked_dev(self, q, mask, radius_ptr, radius_all, cap, offsets_ptr, img_ptr, idx_ptr, dist_ptr, want_total=True,
+                                consumer_stream=None):
+        """``radius_match_masked`` with the radii read from and the lists left in device memory
+        (``fm_collection_radius_match_masked_dev``); arguments after ``mask`` as ``radius_match_dev``."""
+        n = _I64(0)
+        self.ctx._check(self.ctx.lib.fm_collection_radius_match_masked_dev(
+            self.ctx.handle, self.handle, q.handle, mask.handle if mask is not None else None,
+            _P(int(radius_ptr)) if radius_ptr else None, float(np.float32(radius_all)), int(cap),
+            _P(int(offsets_ptr)) if offsets_ptr else None, _P(int(img_ptr)) if img_ptr else None, _P(int(idx_ptr)) if idx_ptr else None,
+            _P(int(dist_ptr)) if dist_ptr else None, ctypes.byref(n) if want_total else None, _stream_arg(consumer_stream)))
+        return int(n.value) if want_total else None
 
     def hamming_radius_match(self, q, r):
         """``fm_collection_hamming_radius_match``: ``radius_match`` of a binary query against a binary collection -- every
@@ -1487,6 +1533,45 @@ class Context(object):
             if int(total.value) != n:
                 raise FastMatchHipError("%s: %d entries on the second call, %d on the first" % (_name, total.value, n))
         return offsets, idx, dist
+
+    def radius_match_masked(self, q, t, mask, r):
+        """``fm_radius_match_masked``: ``radius_match`` -- for two binary banks ``hamming_radius_match``, for two wide float banks
+        ``wide_radius_match`` -- with every entry whose pair ``mask`` (``Context.mask``) forbids removed: cv2's
+        radiusMatch(q, t, maxDistance, mask).  Distances, order, radii and the return value are the unmasked call's."""
+        nq = q.n
+        if np.ndim(r) == 0:
+            rad, r_all = None, float(np.float32(r))
+        else:
+            rad = np.ascontiguousarray(r, dtype=np.float32).reshape(-1)
+            if rad.shape[0] != nq:
+                raise ValueError("radius_match_masked: %d radii for %d query rows" % (rad.shape[0], nq))
+            r_all = 0.0
+        rp = _ptr(rad) if rad is not None and nq > 0 else None
+        mh = mask.handle if mask is not None else None
+        offsets = np.zeros(nq + 1, dtype=np.int64)
+        total = _I64(0)
+        fn = self.lib.fm_radius_match_masked
+        self._check(fn(self.handle, q.handle, t.handle, mh, rp, r_all, 0, _ptr(offsets), None, None, ctypes.byref(total)))
+        n = int(total.value)
+        idx = np.empty(n, dtype=np.int32)
+        dist = np.empty(n, dtype=np.float32)
+        if n > 0:
+            self._check(fn(self.handle, q.handle, t.handle, mh, rp, r_all, n, _ptr(offsets), _ptr(idx), _ptr(dist), ctypes.byref(total)))
+            if int(total.value) != n:
+                raise FastMatchHipError("fm_radius_match_masked: %d entries on the second call, %d on the first" % (total.value, n))
+        return offsets, idx, dist
+
+    def radius_match_masked_dev(self, q, t, mask, radius_ptr, radius_all, cap, offsets_ptr, idx_ptr, dist_ptr, want_total=True,
+                                consumer_stream=None):
+        """``radius_match_masked`` with the radii read from and the lists left in device memory (``fm_radius_match_masked_dev``);
+        arguments after ``mask`` as ``radius_match_dev``."""
+        n = _I64(0)
+        self._check(self.lib.fm_radius_match_masked_dev(
+            self.handle, q.handle, t.handle, mask.handle if mask is not None else None,
+            _P(int(radius_ptr)) if radius_ptr else None, float(np.float32(radius_all)), int(cap),
+            _P(int(offsets_ptr)) if offsets_ptr else None, _P(int(idx_ptr)) if idx_ptr else None,
+            _P(int(dist_ptr)) if dist_ptr else None, ctypes.byref(n) if want_total else None, _stream_arg(consumer_stream)))
+        return int(n.value) if want_total else None
 
     def self_dist(self, bank, _name="fm_self_dist"):
         out = np.empty(bank.n, dtype=np.float64)

@@ -1340,6 +1340,59 @@ extern "C" int fm_collection_hamming_radius_match_dev(fm_ctx* ctx, fm_collection
                        "fm_collection_hamming_radius_match_dev", true);
 }
 
+// Masked radiusMatch against the stacked images (radius.hip's masked sweeps): integer, float32 and binary collections under one
+// name, the route chosen by the query bank's kind as radius_match chooses it.  A wide collection is refused by
+// coll_query_check (FM_EUNSUPPORTED; fm_mask_create_coll makes no mask for one either).  Checks in the header's order: handles,
+// the collection and its query, the mask (fm_collection_knn_masked's), cap and the outputs.  The sweeps keep testing st_real
+// beside the mask although the mask's padding bits are 0 already: one uniform table word per stage, and the same code as
+// the unmasked sweeps'.
+static int coll_radius_masked(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const fm_mask* m, const float* radius, float radius_all, int64_t cap,
+                              int64_t* offsets, int32_t* img, int32_t* idx, float* dist, int64_t* n_total, bool dev, void* consumer, const char* who)
+{
+    if (ctx && c && q && !m) return fail(ctx, FM_EINVAL, std::string(who) + ": mask is NULL");
+    int rc = coll_query_check(ctx, c, q, who, true);
+    if (rc != FM_OK) return rc;
+    if ((rc = mask_check(ctx, m, who)) != FM_OK) return rc;
+    if (!m->coll) return fail(ctx, FM_EINVAL, std::string(who) + ": the mask was made for a bank pair (fm_mask_create); a collection takes fm_mask_create_coll's");
+    if (m->coll != c) return fail(ctx, FM_EINVAL, std::string(who) + ": the mask was made for another collection");
+    if (m->coll_gen != c->gen)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the collection has changed (add or clear) since fm_mask_create_coll: the mask had " +
+                                    std::to_string(m->rows.size()) + " images and " + std::to_string(m->nt) + " rows");
+    if (m->nq != q->n)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the mask has " + std::to_string(m->nq) + " query rows, the query bank " + std::to_string(q->n));
+    const char* pre = dev ? "d_" : "";
+    if (cap < 0) return fail(ctx, FM_EINVAL, std::string(who) + ": cap is negative");
+    if (!offsets) return fail(ctx, FM_EINVAL, std::string(who) + ": " + pre + "offsets is NULL");
+    if (cap > 0 && (!img || !idx || !dist)) return fail(ctx, FM_EINVAL, std::string(who) + ": img / idx / dist is NULL with cap > 0");
+    if (dev) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (radius && (rc = check_device_ptr(ctx, radius, who, "d_radius")) != FM_OK) return rc;
+        if ((rc = check_device_ptr(ctx, offsets, who, "d_offsets")) != FM_OK) return rc;
+        if (img && (rc = check_device_ptr(ctx, img, who, "d_img")) != FM_OK) return rc;
+        if (idx && (rc = check_device_ptr(ctx, idx, who, "d_idx")) != FM_OK) return rc;
+        if (dist && (rc = check_device_ptr(ctx, dist, who, "d_dist")) != FM_OK) return rc;
+    }
+    const CollTab tab{c->st_img(), c->st_real(), c->img_phys()};
+    const RadiusArgs a{who, radius, radius_all, cap, offsets, img, idx, dist, n_total, dev, consumer, &tab, c->total, m->bits, m->words};
+    return radius_match(ctx, *q, c->stack, a);
+}
+
+extern "C" int fm_collection_radius_match_masked(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const fm_mask* mask, const float* radius,
+                                                 float radius_all, int64_t cap, int64_t* offsets, int32_t* img, int32_t* idx, float* dist,
+                                                 int64_t* n_total)
+{
+    return coll_radius_masked(ctx, c, q, mask, radius, radius_all, cap, offsets, img, idx, dist, n_total, false, FM_NO_STREAM,
+                              "fm_collection_radius_match_masked");
+}
+
+extern "C" int fm_collection_radius_match_masked_dev(fm_ctx* ctx, fm_collection* c, const fm_bank* q, const fm_mask* mask, const float* d_radius,
+                                                     float radius_all, int64_t cap, int64_t* d_offsets, int32_t* d_img, int32_t* d_idx,
+                                                     float* d_dist, int64_t* n_total, void* consumer_stream)
+{
+    return coll_radius_masked(ctx, c, q, mask, d_radius, radius_all, cap, d_offsets, d_img, d_idx, d_dist, n_total, true, consumer_stream,
+                              "fm_collection_radius_match_masked_dev");
+}
+
 // Wide radiusMatch against the stacked images of a WIDE collection (radius.hip, the wide route): the stack is the train bank of
 // one sweep, its padding rows masked by index through the stage table fm_collection_train builds for every kind.  The
 // L2-named calls above keep refusing a wide collection (coll_query_check); these are the ones that serve it.  Checks in the

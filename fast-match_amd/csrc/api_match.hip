@@ -1012,6 +1012,57 @@ extern "C" int fm_wide_radius_match_dev(fm_ctx* ctx, const fm_bank* q, const fm_
     return radius_match(ctx, *q, *t, a);
 }
 
+// Masked radiusMatch on a bank pair (radius.hip: the masked instantiations of the four sweeps).  One name for every kind of
+// pair -- integer, float32 route, binary (fm_hamming_radius_match's distance and radius rules), wide float
+// (fm_wide_radius_match's) -- chosen by the banks' kind as radius_match chooses its route.  Checks in the header's order:
+// handles, the pair (check_pair, which takes a binary or a wide pair here), the mask, cap and the outputs.
+static int radius_masked_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* m, int64_t cap, const void* offsets,
+                               const void* idx, const void* dist, const char* who, const char* pre)
+{
+    if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
+    if (!q || !t) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
+    if (!m) return fail(ctx, FM_EINVAL, std::string(who) + ": mask is NULL");
+    int rc = check_pair(ctx, q, t, who, true);
+    if (rc != FM_OK) return rc;
+    if ((rc = mask_check(ctx, m, who)) != FM_OK) return rc;
+    if (m->coll) return fail(ctx, FM_EINVAL, std::string(who) + ": the mask was made for a collection (fm_mask_create_coll); a bank pair takes fm_mask_create's");
+    if (m->nq != q->n)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the mask has " + std::to_string(m->nq) + " query rows, the query bank " + std::to_string(q->n));
+    if (m->nt != t->n)
+        return fail(ctx, FM_EINVAL, std::string(who) + ": the mask has " + std::to_string(m->nt) + " train rows, the train bank " + std::to_string(t->n));
+    if (cap < 0) return fail(ctx, FM_EINVAL, std::string(who) + ": cap is negative");
+    if (!offsets) return fail(ctx, FM_EINVAL, std::string(who) + ": " + pre + "offsets is NULL");
+    if (cap > 0 && (!idx || !dist)) return fail(ctx, FM_EINVAL, std::string(who) + ": " + pre + "idx / " + pre + "dist is NULL with cap > 0");
+    return FM_OK;
+}
+
+extern "C" int fm_radius_match_masked(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, const float* radius,
+                                      float radius_all, int64_t cap, int64_t* offsets, int32_t* idx, float* dist, int64_t* n_total)
+{
+    const char* who = "fm_radius_match_masked";
+    int rc = radius_masked_check(ctx, q, t, mask, cap, offsets, idx, dist, who, "");
+    if (rc != FM_OK) return rc;
+    const RadiusArgs a{who, radius, radius_all, cap, offsets, nullptr, idx, dist, n_total, false, FM_NO_STREAM, nullptr, 0, mask->bits, mask->words};
+    return radius_match(ctx, *q, *t, a);
+}
+
+extern "C" int fm_radius_match_masked_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, const float* d_radius,
+                                          float radius_all, int64_t cap, int64_t* d_offsets, int32_t* d_idx, float* d_dist,
+                                          int64_t* n_total, void* consumer_stream)
+{
+    const char* who = "fm_radius_match_masked_dev";
+    int rc = radius_masked_check(ctx, q, t, mask, cap, d_offsets, d_idx, d_dist, who, "d_");
+    if (rc != FM_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (d_radius && (rc = check_device_ptr(ctx, d_radius, who, "d_radius")) != FM_OK) return rc;
+    if ((rc = check_device_ptr(ctx, d_offsets, who, "d_offsets")) != FM_OK) return rc;
+    if (d_idx && (rc = check_device_ptr(ctx, d_idx, who, "d_idx")) != FM_OK) return rc;
+    if (d_dist && (rc = check_device_ptr(ctx, d_dist, who, "d_dist")) != FM_OK) return rc;
+    const RadiusArgs a{who, d_radius, radius_all, cap, d_offsets, nullptr, d_idx, d_dist, n_total, true, consumer_stream, nullptr, 0,
+                       mask->bits, mask->words};
+    return radius_match(ctx, *q, *t, a);
+}
+
 // Classic Ratio-Match up to the compaction, in ws_out: 2-NN lists | per-q tidx, dist, ratio, pass | block counts, count word |
 // `extra` bytes of the caller's own (16-byte aligned, at `rest`).  knn2_device, then lowe_kernel.
 struct LoweWs {

@@ -206,6 +206,8 @@ struct RadiusArgs {
     int64_t* n_total;                            // host, may be null
     bool dev; void* consumer;                    // device form, and the stream it is ordered against (FM_NO_STREAM: none)
     const CollTab* tab; int64_t real_rows;       // t is a collection's stack: its lookup tables and its real rows; null: a plain bank
+    const unsigned long long* mask = nullptr;    // the masked entry points: fm_mask's words [q.n][mwords] over t's padded rows,
+    int64_t mwords = 0;                          // checked against q and t by the caller; null: every pair is permitted
 };
 int radius_match(fm_ctx* ctx, const fm::Bank& q, const fm::Bank& t, const RadiusArgs& a);
 // Source rows that are already in device memory (fm_bank_create_dev, fm_collection_add_dev): n rows of FM_DT_* elements,

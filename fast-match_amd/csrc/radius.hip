@@ -34,6 +34,11 @@
 //   the offsets come from a device copy of the scan (integer route) or radius_offsets_kernel (float32 route, per chunk), the
 //   compaction writes the caller's arrays at the final offsets for the rows that fit in cap.  The host still reads the
 //   counts back (chunk plan, segment sort).
+// Under a mask (fm_radius_match_masked, fm_collection_radius_match_masked and their _dev forms; K13's fm_mask): the four
+//   sweeps live in radius_sweeps.inc, included once unmasked (radius_*_kernel, the code they always were) and once with
+//   MASKED = true (rmask_*_kernel).  A masked sweep ANDs the query row's mask word of the stage into its hit bits in front of
+//   the count and of r_emit, and skips the LDS reads and MFMAs of a stage in which its rows permit nothing (r_mask_word below).
+//   Everything behind the sweeps -- scan, chunks, rescoring, sort, compaction -- sees permitted candidates only and is unchanged.
 // Geometry of the sweeps: a workgroup = 4 waves, a wave = 4 blocks of 16 query rows (the MFMA's N, held in VGPRs for the
 // whole sweep), the train rows (M) stream through LDS 64 at a time, rows padded by 16 bytes against bank conflicts.
 // grid = (query groups of 256 rows, splits of the train range).
@@ -126,17 +131,36 @@ struct RSweep {
                                       // (Bank::real, one word per 64-row stage); null: none
     int wks;                   // wide route: MFMA K steps per row, 5 .. 8 (0: another route); the float32 route's fields then
                                // hold the wide planes (wrowsh at pitch kWideDim, normf)
+    const unsigned long long* mask;   // the masked calls: fm_mask's words of this launch's first query row on ([nq][mwords], one word
+    int64_t mwords;                   // per query row and 64-row stage, padding bits 0); null: none -- the unmasked kernels never read it
 };
 
 // Grown train banks: the 16 candidates of a lane in the stage at `base` (tile tt, register r -> bit 4 tt + r, train row
 // base + 16 tt + 4 g + r) that are real rows.  One uniform 8-byte load per stage.
-__device__ __forceinline__ unsigned r_real_bits(const unsigned long long* __restrict__ real, int base, int g)
+__device__ __forceinline__ unsigned r_word_bits(unsigned long long w, int g)
 {
-    const unsigned long long rw = real[base >> 6] >> (4 * g);
+    const unsigned long long rw = w >> (4 * g);
     unsigned bits = 0;
 #pragma unroll
     for (int tt = 0; tt < 4; ++tt) bits |= ((unsigned)(rw >> (16 * tt)) & 0xFu) << (4 * tt);
     return bits;
+}
+
+__device__ __forceinline__ unsigned r_real_bits(const unsigned long long* __restrict__ real, int base, int g)
+{
+    return r_word_bits(real[base >> 6], g);
+}
+
+// The masked sweeps (MASKED, a compile-time parameter of the bodies below: the unmasked kernels hold none of this).  Query row
+// q's word of the 64-row stage at `base`: the four lanes g of a row read the same 8 bytes; a lane without a query row reads
+// nothing and permits nothing.  The word of stage s + 1 is loaded while stage s is worked on (r_mask_next) and turned into the
+// lane's 16 candidate bits (r_word_bits: the layout of the hit mask) at the top of its own stage -- ahead of the stage's LDS
+// traffic and MFMAs, and one whole stage ahead of its first use.  The bits are ANDed into the hit mask in front of the count
+// and in front of r_emit: the count sweep and the fill sweep read the same words (nothing writes a mask during a call), so
+// the fill finds exactly what the count counted.
+__device__ __forceinline__ unsigned long long r_mask_word(const RSweep& p, int q, int base)
+{
+    return q < p.nq ? p.mask[(size_t)q * (size_t)p.mwords + (size_t)(base >> 6)] : 0ull;
 }
 
 // Rows of the 64-row stage at `base` that may be reported: up to the split's end t1 and, in a collection's stack, up to the
@@ -174,384 +198,16 @@ __device__ __forceinline__ void r_emit(const RSweep& p, unsigned mask, const uns
     }
 }
 
-template <bool FILL>
-__global__ __launch_bounds__(256)
-void radius_i8_kernel(RSweep p)
-{
-    __shared__ __attribute__((aligned(16))) int8_t srow[kRStage * kRRowI8];
-    __shared__ __attribute__((aligned(16))) int snorm[kRStage];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
-    const int qw = blockIdx.x * kRQPerWG + wave * 16 * kRNB;
-    v4i bq[kRNB][2];
-    int qn[kRNB], lim[kRNB];
-    unsigned count[kRNB];
-#pragma unroll
-    for (int b = 0; b < kRNB; ++b) {
-        const int q = qw + 16 * b + j;
-        const bool live = q < p.nq;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            bq[b][h] = live ? *(const v4i*)(p.qrows + (size_t)q * kDim + 64 * h + 16 * g) : v4i{0, 0, 0, 0};
-        qn[b] = live ? p.qnorm[q] : 0;
-        lim[b] = live ? p.lim[q] : -1;
-        count[b] = 0;
-    }
-    const int t0 = blockIdx.y * p.per, t1 = min(p.nt, t0 + p.per);
-    for (int base = t0; base < t1; base += kRStage) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {       // 64 rows x 8 pieces of 16 B (rows < n_pad: base % 64 == 0, n_pad % 128 == 0)
-            const int piece = tid + 256 * i, r = piece >> 3, c = piece & 7;
-            *(v4i*)(srow + r * kRRowI8 + 16 * c) = *(const v4i*)(p.trows + (size_t)(base + r) * kDim + 16 * c);
-        }
-        if (tid < kRStage) snorm[tid] = p.tnorm[base + tid];
-        __syncthreads();
-        v4i a[4][2], tn[4];
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) a[tt][h] = *(const v4i*)(srow + (16 * tt + j) * kRRowI8 + 64 * h + 16 * g);
-            tn[tt] = *(const v4i*)(snorm + 16 * tt + 4 * g);
-        }
-        const int rowlim = r_real_end(p, base, t1) - base - 4 * g;   // register r of tile tt is a real train row iff 16 tt + r < rowlim
-#pragma unroll
-        for (int b = 0; b < kRNB; ++b) {
-            unsigned mask = 0;
-            unsigned hi[16];
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) {
-                v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[tt][0], bq[b][0], v4i{0, 0, 0, 0}, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[tt][1], bq[b][1], acc, 0, 0, 0);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int d2 = qn[b] + tn[tt][r] - 2 * acc[r];
-                    hi[4 * tt + r] = FILL ? sqrt_bits((unsigned)d2) : 0u;
-                    mask |= (d2 <= lim[b] && 16 * tt + r < rowlim) ? (1u << (4 * tt + r)) : 0u;
-                }
-            }
-            if (p.real) mask &= r_real_bits(p.real, base, g);         // (uniform branch; a gap row of a grown bank is no hit)
-            if constexpr (FILL) r_emit(p, mask, hi, qw + 16 * b + j, qw + 16 * b + j < p.nq, base, lane);
-            else count[b] += __popc(mask);
-        }
-    }
-    if constexpr (!FILL) {
-#pragma unroll
-        for (int b = 0; b < kRNB; ++b) {
-            unsigned c = count[b];
-            c += __shfl_xor(c, 16);
-            c += __shfl_xor(c, 32);
-            const int q = qw + 16 * b + j;
-            if (g == 0 && q < p.nq && c) atomicAdd(&p.cnt[q], c);
-        }
-    }
-}
-
-template <bool FILL>
-__global__ __launch_bounds__(256)
-void radius_f16_kernel(RSweep p)
-{
-    __shared__ __attribute__((aligned(16))) char srow[kRStage * kRRowH];
-    __shared__ __attribute__((aligned(16))) float snorm[kRStage];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
-    const int qw = blockIdx.x * kRQPerWG + wave * 16 * kRNB;
-    const bool all = p.all != 0;
-    rv8h bh[kRNB][4];
-    float qn[kRNB], thr[kRNB];
-    unsigned count[kRNB];
-#pragma unroll
-    for (int b = 0; b < kRNB; ++b) {
-        const int q = qw + 16 * b + j;
-        const bool live = q < p.nq;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const v4i h = (live && !all) ? *(const v4i*)(p.qrowsh + (size_t)q * kDim + 32 * s + 8 * g) : v4i{0, 0, 0, 0};
-            bh[b][s] = __builtin_bit_cast(rv8h, h);
-        }
-        qn[b] = (live && !all) ? p.qnormf[q] * p.cq : 0.f;
-        thr[b] = live ? p.thr[q] : -INFINITY;
-        count[b] = 0;
-    }
-    unsigned hi[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) hi[c] = 0u;
-    const int t0 = blockIdx.y * p.per, t1 = min(p.nt, t0 + p.per);
-    for (int base = t0; base < t1; base += kRStage) {
-        if (!all) {
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {   // 64 rows x 16 pieces of 16 B
-                const int piece = tid + 256 * i, r = piece >> 4, c = piece & 15;
-                *(v4i*)(srow + r * kRRowH + 16 * c) = *(const v4i*)(p.trowsh + (size_t)(base + r) * kDim + 8 * c);
-            }
-            if (tid < kRStage) snorm[tid] = p.tnormf[base + tid] * p.ct;
-            __syncthreads();
-        }
-        const int rowlim = r_real_end(p, base, t1) - base - 4 * g;
-        unsigned mask[kRNB];
-#pragma unroll
-        for (int b = 0; b < kRNB; ++b) mask[b] = 0;
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            rv8h a[4];
-            rv4f tn = rv4f{0.f, 0.f, 0.f, 0.f};
-            if (!all) {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) a[s] = __builtin_bit_cast(rv8h, *(const v4i*)(srow + (16 * tt + j) * kRRowH + 64 * s + 16 * g));
-                tn = *(const rv4f*)(snorm + 16 * tt + 4 * g);
-            }
-#pragma unroll
-            for (int b = 0; b < kRNB; ++b) {
-                rv4f acc = rv4f{0.f, 0.f, 0.f, 0.f};
-                if (!all) {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[s], bh[b][s], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float A = qn[b] + tn[r] - 2.f * acc[r];     // (all: 0, against a threshold of +-inf)
-                    mask[b] |= (A <= thr[b] && 16 * tt + r < rowlim) ? (1u << (4 * tt + r)) : 0u;
-                }
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < kRNB; ++b) {
-            const int q = qw + 16 * b + j;
-            if constexpr (FILL) {
-#pragma unroll
-                for (int c = 0; c < 16; ++c) hi[c] = (unsigned)q;
-                r_emit(p, mask[b], hi, q, q < p.nq, base, lane);
-            } else {
-                count[b] += __popc(mask[b]);
-            }
-        }
-    }
-    if constexpr (!FILL) {
-#pragma unroll
-        for (int b = 0; b < kRNB; ++b) {
-            unsigned c = count[b];
-            c += __shfl_xor(c, 16);
-            c += __shfl_xor(c, 32);
-            const int q = qw + 16 * b + j;
-            if (g == 0 && q < p.nq && c) atomicAdd(&p.cnt[q], c);
-        }
-    }
-}
-
-// Wide route (file comment): the query rows of a wave -- two blocks of 16 -- are the B operand, in registers for the whole
-// sweep; the train rows' fp16 plane comes straight from memory, one 16-row tile ahead (no LDS, no barrier).  A stage is four
-// tiles: the 16 candidates a lane has per block in 64 rows go through r_emit like the float32 route's.  Every tile of a stage
-// is read, also behind the split's end: the stage ends inside the bank's padded rows (base % 64 == 0, n_pad % 128 == 0), and
-// what lies behind t1 or behind a collection's real rows is masked by index.
-template <bool FILL, int KS>
-__global__ __launch_bounds__(256)
-void radius_wide_kernel(RSweep p)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
-    const int qw = blockIdx.x * kRWQPerWG + wave * 16 * kRWNB;
-    const bool all = p.all != 0;
-    rv8h bh[kRWNB][KS];
-    float qn[kRWNB], thr[kRWNB];
-    unsigned count[kRWNB];
-#pragma unroll
-    for (int b = 0; b < kRWNB; ++b) {
-        const int q = qw + 16 * b + j;
-        const bool live = q < p.nq;      // (a chunk may start on any row: the rows behind nq need not lie inside the bank)
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const v4i h = (live && !all) ? *(const v4i*)(p.qrowsh + (size_t)q * kWideDim + 32 * s + 8 * g) : v4i{0, 0, 0, 0};
-            bh[b][s] = __builtin_bit_cast(rv8h, h);
-        }
-        qn[b] = (live && !all) ? p.qnormf[q] * p.cq : 0.f;
-        thr[b] = live ? p.thr[q] : -INFINITY;
-        count[b] = 0;
-    }
-    unsigned hi[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) hi[c] = 0u;
-    const int t0 = blockIdx.y * p.per, t1 = min(p.nt, t0 + p.per);
-    rv8h an[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) an[s] = rv8h{0, 0, 0, 0, 0, 0, 0, 0};
-    if (!all && t0 < t1) {
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-            an[s] = __builtin_bit_cast(rv8h, *(const v4i*)(p.trowsh + (size_t)(t0 + j) * kWideDim + 32 * s + 8 * g));
-    }
-    for (int base = t0; base < t1; base += kRStage) {
-        const int rowlim = r_real_end(p, base, t1) - base - 4 * g;   // register r of tile tt is a real train row iff 16 tt + r < rowlim
-        const bool more = base + kRStage < t1;
-        unsigned mask[kRWNB];
-#pragma unroll
-        for (int b = 0; b < kRWNB; ++b) mask[b] = 0;
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            rv8h a[KS];
-            rv4f tn = rv4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < KS; ++s) a[s] = an[s];
-            if (!all) {
-                if (tt < 3 || more) {       // the next tile: of this stage, or the first of the next one
-#pragma unroll
-                    for (int s = 0; s < KS; ++s)
-                        an[s] = __builtin_bit_cast(rv8h, *(const v4i*)(p.trowsh + (size_t)(base + 16 * (tt + 1) + j) * kWideDim + 32 * s + 8 * g));
-                }
-                tn = *(const rv4f*)(p.tnormf + base + 16 * tt + 4 * g) * p.ct;
-            }
-#pragma unroll
-            for (int b = 0; b < kRWNB; ++b) {
-                rv4f acc = rv4f{0.f, 0.f, 0.f, 0.f};
-                if (!all) {
-#pragma unroll
-                    for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[s], bh[b][s], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float A = qn[b] + tn[r] - 2.f * acc[r];     // (all: 0, against a threshold of +-inf)
-                    mask[b] |= (A <= thr[b] && 16 * tt + r < rowlim) ? (1u << (4 * tt + r)) : 0u;
-                }
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < kRWNB; ++b) {
-            const int q = qw + 16 * b + j;
-            if constexpr (FILL) {
-#pragma unroll
-                for (int c = 0; c < 16; ++c) hi[c] = (unsigned)q;
-                r_emit(p, mask[b], hi, q, q < p.nq, base, lane);
-            } else {
-                count[b] += __popc(mask[b]);
-            }
-        }
-    }
-    if constexpr (!FILL) {
-#pragma unroll
-        for (int b = 0; b < kRWNB; ++b) {
-            unsigned c = count[b];
-            c += __shfl_xor(c, 16);
-            c += __shfl_xor(c, 32);
-            const int q = qw + 16 * b + j;
-            if (g == 0 && q < p.nq && c) atomicAdd(&p.cnt[q], c);
-        }
-    }
-}
-
-// Hamming route (binary banks, K11's operands: hamming.hip): every bit is one FP4 value, +1 or -1, so the dot product of two
-// encoded rows is W - 2 h, exact in the f32 accumulator; a hit is dot >= thr (ham_radius.h), h = (W - dot) / 2.  K11's loop:
-// 128-row stages through two LDS buffers, the next stage prefetched into registers, one barrier per stage, row pitch RB + 16;
-// the 64 query rows of a wave are the B operand, in registers for the whole sweep.  A split is whole stages (p.per rows).
-// Padding rows are all-zero FP4 rows at dot = 0 -- h = W / 2, inside any r > W / 2 -- and are kept out by index: rows from
-// `lim` on (the bank's nt, or the real rows of a collection's stage) never count; only a last, partial stage pays for the test.
-template <bool FILL, int KS>
-__global__ __launch_bounds__(256)
-void radius_ham_kernel(RSweep p)
-{
-    constexpr int RB = KS * 64;             // FP4 bytes per row
-    constexpr int LS = RB + 16;             // LDS row pitch
-    constexpr int PIECES = kStageRows * RB / 16 / 256;    // 16-byte pieces per thread per stage (2 KS)
-    __shared__ __attribute__((aligned(16))) uint8_t lds[2][kStageRows * LS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
-    const int qw = blockIdx.x * kRQPerWG + wave * 16 * kRNB;
-    const int nstages = (p.nt + kStageRows - 1) / kStageRows;
-    const int st0 = blockIdx.y * (p.per / kStageRows), st1 = min(nstages, st0 + p.per / kStageRows);
-
-    rv8i bop[kRNB][KS];
-    float thr[kRNB];
-    unsigned count[kRNB];
-#pragma unroll
-    for (int b = 0; b < kRNB; ++b) {
-        const int q = qw + 16 * b + j;
-        const bool live = q < p.nq;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const v4i x = live ? *(const v4i*)(p.q4 + (size_t)q * RB + 64 * ks + 16 * g) : v4i{0, 0, 0, 0};
-            bop[b][ks] = rv8i{x[0], x[1], x[2], x[3], 0, 0, 0, 0};
-        }
-        thr[b] = live ? p.thr[q] : INFINITY;
-        count[b] = 0;
-    }
-
-    v4i pre[PIECES];
-    auto load = [&](int st) {
-#pragma unroll
-        for (int i = 0; i < PIECES; ++i)      // (whole stages: st < nstages <= n_pad / 128)
-            pre[i] = *(const v4i*)(p.t4 + ((size_t)st * kStageRows) * RB + (size_t)(tid + 256 * i) * 16);
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < PIECES; ++i) {
-            const int pc = tid + 256 * i;
-            *(v4i*)(&lds[buf][(pc / (RB / 16)) * LS + 16 * (pc % (RB / 16))]) = pre[i];
-        }
-    };
-    if (st0 < st1) { load(st0); store(0); }
-    __syncthreads();
-    for (int st = st0; st < st1; ++st) {
-        const int buf = (st - st0) & 1;
-        const bool more = st + 1 < st1;
-        if (more) load(st + 1);
-        const int sbase = st * kStageRows;
-        const int lim = p.st_real ? sbase + p.st_real[st] : p.nt;       // (uniform: one table word per stage)
-        const bool tail = sbase + kStageRows > lim;
-        const int rowlim = lim - sbase - 4 * g;      // tail: register r of tile t is a real train row iff 16 t + r < rowlim
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {       // r_emit takes the 16 candidates a lane has in 64 rows
-            unsigned mask[kRNB];
-            float dot[FILL ? kRNB : 1][16];
-#pragma unroll
-            for (int b = 0; b < kRNB; ++b) mask[b] = 0;
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) {
-                const int t = 4 * half + tt;
-                rv8i aop[KS];
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const v4i x = *(const v4i*)(&lds[buf][(16 * t + j) * LS + 64 * ks + 16 * g]);
-                    aop[ks] = rv8i{x[0], x[1], x[2], x[3], 0, 0, 0, 0};
-                }
-#pragma unroll
-                for (int b = 0; b < kRNB; ++b) {
-                    rv4f acc = rv4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int ks = 0; ks < KS; ++ks)
-                        acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(aop[ks], bop[b][ks], acc, 4, 4, 0, 127, 0, 127);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        bool hit = acc[r] >= thr[b];
-                        if (tail) hit = hit && 16 * t + r < rowlim;
-                        if constexpr (FILL) {
-                            mask[b] |= hit ? (1u << (4 * tt + r)) : 0u;
-                            dot[b][4 * tt + r] = acc[r];
-                        } else {
-                            count[b] += hit ? 1u : 0u;
-                        }
-                    }
-                }
-            }
-            if constexpr (FILL) {
-#pragma unroll
-                for (int b = 0; b < kRNB; ++b) {
-                    if (!__any(mask[b] != 0)) continue;
-                    unsigned hi[16];
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) hi[c] = __float_as_uint((float)((p.W - (int)dot[b][c]) >> 1));
-                    r_emit(p, mask[b], hi, qw + 16 * b + j, qw + 16 * b + j < p.nq, sbase + 64 * half, lane);
-                }
-            }
-        }
-        if (more) store(buf ^ 1);
-        __syncthreads();
-    }
-    if constexpr (!FILL) {
-#pragma unroll
-        for (int b = 0; b < kRNB; ++b) {
-            unsigned c = count[b];
-            c += __shfl_xor(c, 16);
-            c += __shfl_xor(c, 32);
-            const int q = qw + 16 * b + j;
-            if (g == 0 && q < p.nq && c) atomicAdd(&p.cnt[q], c);
-        }
-    }
-}
+#define R_SWEEP_MASKED false
+#define R_SWEEP_KERNEL(route) radius_##route##_kernel
+#include "radius_sweeps.inc"
+#undef R_SWEEP_MASKED
+#undef R_SWEEP_KERNEL
+#define R_SWEEP_MASKED true
+#define R_SWEEP_KERNEL(route) rmask_##route##_kernel
+#include "radius_sweeps.inc"
+#undef R_SWEEP_MASKED
+#undef R_SWEEP_KERNEL
 
 // Hamming route: the least dot product of a hit per query row (ham_radius.h).
 __global__ void radius_ham_limits_kernel(const float* __restrict__ radius, float radius_all, int nq, int W, float* __restrict__ thr)
@@ -791,6 +447,8 @@ static hipError_t r_sweep(const RSweep& base, bool f32, bool fill, int64_t q0, i
 {
     RSweep p = base;
     p.nq = (int)nq;
+    const bool masked = p.mask != nullptr;
+    if (masked) p.mask += q0 * p.mwords;
     if (p.ks) {
         p.q4 += q0 * p.ks * 64; p.thr += q0;
         if (fill) p.off += q0;
@@ -800,7 +458,9 @@ static hipError_t r_sweep(const RSweep& base, bool f32, bool fill, int64_t q0, i
         const dim3 grid((unsigned)((nq + kRQPerWG - 1) / kRQPerWG), (unsigned)ns);
 #define FM_RHAM(KS_)                                                                                      \
         if (p.ks == KS_) {                                                                                \
-            if (fill) hipLaunchKernelGGL((radius_ham_kernel<true, KS_>), grid, dim3(256), 0, stream, p);  \
+            if (masked && fill) hipLaunchKernelGGL((rmask_ham_kernel<true, KS_>), grid, dim3(256), 0, stream, p);   \
+            else if (masked)    hipLaunchKernelGGL((rmask_ham_kernel<false, KS_>), grid, dim3(256), 0, stream, p);  \
+            else if (fill) hipLaunchKernelGGL((radius_ham_kernel<true, KS_>), grid, dim3(256), 0, stream, p);  \
             else      hipLaunchKernelGGL((radius_ham_kernel<false, KS_>), grid, dim3(256), 0, stream, p); \
             return hipGetLastError();                                                                     \
         }
@@ -820,7 +480,9 @@ static hipError_t r_sweep(const RSweep& base, bool f32, bool fill, int64_t q0, i
         const dim3 grid((unsigned)((nq + kRWQPerWG - 1) / kRWQPerWG), (unsigned)ns);
 #define FM_RWIDE(KS_)                                                                                      \
         if (p.wks == KS_) {                                                                                \
-            if (fill) hipLaunchKernelGGL((radius_wide_kernel<true, KS_>), grid, dim3(256), 0, stream, p);  \
+            if (masked && fill) hipLaunchKernelGGL((rmask_wide_kernel<true, KS_>), grid, dim3(256), 0, stream, p);   \
+            else if (masked)    hipLaunchKernelGGL((rmask_wide_kernel<false, KS_>), grid, dim3(256), 0, stream, p);  \
+            else if (fill) hipLaunchKernelGGL((radius_wide_kernel<true, KS_>), grid, dim3(256), 0, stream, p);  \
             else      hipLaunchKernelGGL((radius_wide_kernel<false, KS_>), grid, dim3(256), 0, stream, p); \
             return hipGetLastError();                                                                      \
         }
@@ -837,10 +499,14 @@ static hipError_t r_sweep(const RSweep& base, bool f32, bool fill, int64_t q0, i
     p.per = (per + kRStage - 1) / kRStage * kRStage;
     const dim3 grid((unsigned)((nq + kRQPerWG - 1) / kRQPerWG), (unsigned)ns);
     if (f32) {
-        if (fill) hipLaunchKernelGGL(radius_f16_kernel<true>, grid, dim3(256), 0, stream, p);
+        if (masked && fill) hipLaunchKernelGGL(rmask_f16_kernel<true>, grid, dim3(256), 0, stream, p);
+        else if (masked)    hipLaunchKernelGGL(rmask_f16_kernel<false>, grid, dim3(256), 0, stream, p);
+        else if (fill) hipLaunchKernelGGL(radius_f16_kernel<true>, grid, dim3(256), 0, stream, p);
         else      hipLaunchKernelGGL(radius_f16_kernel<false>, grid, dim3(256), 0, stream, p);
     } else {
-        if (fill) hipLaunchKernelGGL(radius_i8_kernel<true>, grid, dim3(256), 0, stream, p);
+        if (masked && fill) hipLaunchKernelGGL(rmask_i8_kernel<true>, grid, dim3(256), 0, stream, p);
+        else if (masked)    hipLaunchKernelGGL(rmask_i8_kernel<false>, grid, dim3(256), 0, stream, p);
+        else if (fill) hipLaunchKernelGGL(radius_i8_kernel<true>, grid, dim3(256), 0, stream, p);
         else      hipLaunchKernelGGL(radius_i8_kernel<false>, grid, dim3(256), 0, stream, p);
     }
     return hipGetLastError();
@@ -952,6 +618,8 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
         return FM_OK;
     }
     if (nt > 0x7fffffff || nq > 0x7fffffff) return fail(ctx, FM_EUNSUPPORTED, std::string(a.who) + ": more than 2^31 - 1 rows in a bank");
+    // (a mask spans the padded train rows, in whole 128-row stages: every word a sweep reads lies inside it)
+    if (a.mask && a.mwords * 64 < ((nt + 127) & ~(int64_t)127)) return fail(ctx, FM_EINVAL, std::string(a.who) + ": the mask does not span the train rows");
     const bool wide = q.kind == FM_BANK_F32W;     // (the wide entry points: both operands wide, of one dim; the float32 route's
                                                   // path with the wide sweep, limits and rescoring kernels)
     const bool f32 = q.kind == FM_BANK_F32 || wide;
@@ -1019,6 +687,7 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
     sw.nt = (int)nt; sw.lim = d_lim; sw.thr = d_thr;
     sw.st_real = a.tab ? (const int*)a.tab->st_real : nullptr;
     sw.real = a.tab ? nullptr : t.real;
+    sw.mask = a.mask; sw.mwords = a.mwords;      // (the masked entry points; r_sweep moves the pointer to a chunk's first row)
     // 1. counts (candidates on the float32 route), 2. their exclusive scan
     HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, (size_t)(nq + 1) * 4, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));

@@ -40,6 +40,11 @@ Mirrors ``matchutil.py`` of the reference:
   wide collection, ``BFMatcher.wideFastMatchEach`` / ``wideFastMatchEach_arrays``.  knnMatch under a mask on wide descriptors
   (guided matching: a window round a predicted position, an epipolar band) is ``wide_bf_match_masked`` /
   ``wide_bf_match_masked_arrays`` (``fm_wide_knn_masked``, k = 1 or 2); ``bf_match`` keeps refusing the combination.
+* radiusMatch under a mask (guided matching: every row within r among the rows of a window or an epipolar band):
+  ``bf_radius_match_masked`` / ``bf_radius_match_masked_arrays`` (``fm_radius_match_masked``: uint8 and float 128-D rows,
+  NORM_HAMMING rows, wide float rows -- the masked threshold sweeps on the matrix cores), and
+  ``BFMatcher.radiusMatch(query, train, maxDistance, mask=None, compactResult=False)``.  ``bf_radius_match`` keeps refusing
+  ``options["mask"]``.
 * ``options["mask"]``: cv2's ``mask`` argument of ``knnMatch`` -- an ``[nq, nt]`` uint8 / bool array, nonzero = the pair
   (query row, train row) may be matched, or a resident ``_ffi.Mask`` (``Context.mask``).  ``bf_match``,
   ``bf_match_arrays``, ``flann_match`` and ``flann_match_arrays`` honour it when crossCheck is off: every list is the
@@ -338,6 +343,61 @@ def bf_radius_match_arrays(dt1, dt2, maxDistance, options={}):
 def bf_radius_match(dt1, dt2, maxDistance, options={}):
     """ cv2.BFMatcher(NORM_L2).radiusMatch(dt1, dt2, maxDistance): a list of DMatch lists, one per query row """
     off, idx, dist = bf_radius_match_arrays(dt1, dt2, maxDistance, options=options)
+    return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
+
+
+def bf_radius_match_masked_arrays(dt1, dt2, maxDistance, mask, options={}):
+    """``cv2.BFMatcher(normType).radiusMatch(dt1, dt2, maxDistance, mask)`` as arrays: ``(offsets int64[nq + 1], idx int32[n],
+    dist float32[n])`` -- the lists of the unmasked call that serves the operands with every entry whose pair ``mask`` forbids
+    removed, nothing else changed (``fm_radius_match_masked``, on the matrix cores for every kind).  The call is chosen by
+    ``options["normType"]`` and the row width: NORM_HAMMING (uint8 rows of 1 .. 64 bytes, or binary banks) is
+    :func:`hamming_radius_match_arrays`'s, float rows of 129 .. 256 values (or wide banks) :func:`wide_radius_match_arrays`'s,
+    everything else :func:`bf_radius_match_arrays`'s.  ``mask``: a uint8 / bool ``[nq, nt]`` array, nonzero = the pair may be
+    listed, or a resident ``_ffi.Mask`` (``Context.mask``).  ``ValueError`` before anything is uploaded: what the unmasked call
+    refuses for the operands, ``mask`` None, a mask of another shape or dtype, a collection's Mask, a wrong number of radii."""
+    who = "bf_radius_match_masked"
+    options = options or {}
+    norm = _norm_type(options, dt1, dt2)
+    wide = norm != NORM_HAMMING and (_is_wide(dt1) or _is_wide(dt2))
+    if norm == NORM_HAMMING:
+        q, qw, _ = _binary_operand(dt1)
+        t, tw, _ = _binary_operand(dt2)
+        if qw != tw:
+            raise ValueError("%s: %d bytes per query row, %d per train row" % (who, qw, tw))
+    elif wide:
+        q, qw = _wide_operand(dt1, who)
+        t, tw = _wide_operand(dt2, who)
+        if qw != tw:
+            raise ValueError("%s: %d values per query row, %d per train row" % (who, qw, tw))
+    else:
+        q, t = dt1, dt2
+        for d in (q, t):
+            if not isinstance(d, _ffi.Bank) and np.asarray(d).ndim != 2:
+                raise ValueError("descriptors must be a 2-D [n, dim] array")
+    if mask is None:
+        raise ValueError("%s: mask is None (bf_radius_match, hamming_radius_match and wide_radius_match are the calls without one)" % who)
+    mask = _mask_option({"mask": mask}, q, t, who)
+    nq = _rows_of(q)
+    if np.ndim(maxDistance) != 0 and np.asarray(maxDistance).reshape(-1).shape[0] != nq:
+        raise ValueError("%s: %d radii for %d query rows" % (who, np.asarray(maxDistance).reshape(-1).shape[0], nq))
+    ctx = _context(options)
+    qb, q_tmp, tb, t_tmp = _bank_pair(ctx, q, t, norm)
+    try:
+        if isinstance(mask, _ffi.Mask):
+            return ctx.radius_match_masked(qb, tb, mask, maxDistance)
+        with ctx.mask(qb.n, tb.n) as mk:
+            return ctx.radius_match_masked(qb, tb, mk.set(mask), maxDistance)
+    finally:
+        if q_tmp:
+            qb.close()
+        if t_tmp:
+            tb.close()
+
+
+def bf_radius_match_masked(dt1, dt2, maxDistance, mask, options={}):
+    """ cv2.BFMatcher(normType).radiusMatch(dt1, dt2, maxDistance, mask): a list of DMatch lists, one per query row (an empty
+    list where the mask permits nothing within maxDistance) """
+    off, idx, dist = bf_radius_match_masked_arrays(dt1, dt2, maxDistance, mask, options=options)
     return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
 
 
@@ -1055,7 +1115,12 @@ class BFMatcher(object):
             return [m[0] for m in self.knnMatch(queryDescriptors, trainDescriptors, k=1) if m]
         return [m[0] for m in self.knnMatch(queryDescriptors, trainDescriptors, k=1, mask=mask, masks=masks) if m]
 
-    def radiusMatch(self, queryDescriptors, trainDescriptors=None, maxDistance=None):
+    def radiusMatch(self, queryDescriptors, trainDescriptors=None, maxDistance=None, mask=None, compactResult=False):
+        """cv2's radiusMatch(query, train, maxDistance, mask, compactResult).  Without ``mask`` and ``compactResult`` the call is
+        what it was before masks existed (:func:`bf_radius_match`).  ``mask``: :func:`bf_radius_match_masked`'s, on every kind of
+        descriptor the matcher's normType takes.  ``compactResult`` = True drops the lists of the query rows whose mask row is
+        entirely zero -- OpenCV's rule as recalled, not verified -- so the result may have fewer than nq lists (every DMatch keeps
+        its queryIdx); without a mask it drops nothing."""
         if maxDistance is None and trainDescriptors is not None and np.isscalar(trainDescriptors):
             trainDescriptors, maxDistance = None, trainDescriptors
         if trainDescriptors is None:
@@ -1063,7 +1128,15 @@ class BFMatcher(object):
                              "Collection.radius_match (_ffi / torchmatch) is the array-form route; or pass a train array")
         if maxDistance is None:
             raise TypeError("radiusMatch: maxDistance is required")
-        return bf_radius_match(queryDescriptors, trainDescriptors, maxDistance, options=self.options)
+        if mask is None:
+            return bf_radius_match(queryDescriptors, trainDescriptors, maxDistance, options=self.options)
+        if compactResult and isinstance(mask, _ffi.Mask):
+            raise ValueError("BFMatcher.radiusMatch: compactResult needs the mask as an array (a resident Mask's rows are on the device)")
+        out = bf_radius_match_masked(queryDescriptors, trainDescriptors, maxDistance, mask, options=self.options)
+        if compactResult:
+            keep = np.asarray(mask).astype(bool).any(axis=1)
+            out = [m for qi, m in enumerate(out) if keep[qi]]
+        return out
 
 
 # ---- SIFT stays in OpenCV on the host -------------------------------------------------

@@ -159,6 +159,27 @@ def _set_mask(mask, m, img):
     mask.set_dev(m.data_ptr(), img=img, pitch=m.stride(0), stream=stream)
 
 
+def _rows_hint(x):
+    return x.n if isinstance(x, _ffi.Bank) else (x.shape[0] if hasattr(x, "shape") and len(x.shape) == 2 else -1)
+
+
+def _pair_mask_checked(mask, q, t):
+    """``mask`` of a pair call before anything is uploaded: None, a resident Mask as it is, or a checked tensor."""
+    if mask is None or isinstance(mask, _ffi.Mask):
+        return mask
+    return _checked_mask(mask, _rows_hint(q), _rows_hint(t))
+
+
+def _pair_mask(mask, qb, tb, made):
+    """The resident Mask of a checked pair mask (a tensor's is made for this call and closed with ``made``)."""
+    if isinstance(mask, _ffi.Mask):
+        return mask
+    mk = qb.ctx.mask(qb.n, tb.n)
+    made.append(mk)
+    _set_mask(mk, mask, 0)
+    return mk
+
+
 def _ctx_for(tensor, context):
     return context if context is not None else _ffi.default_context(tensor.device.index)
 
@@ -334,18 +355,24 @@ def _radius_lists(call, nq, rad, r_all, stream, dev, with_img):
     return (offsets,) + tuple(lists)
 
 
-def radius_match(q, t, r):
+def radius_match(q, t, r, mask=None):
     """``cv2.BFMatcher.radiusMatch``: ``(offsets int64 [nq + 1], idx int32 [n], dist float32 [n])`` CUDA tensors, every train
     row with distance < r per query row, ascending (distance, train index).  ``r``: a scalar, or a float32 CUDA tensor [nq]
-    read in place behind the current stream's work (module docstring).  One host wait for the total."""
+    read in place behind the current stream's work (module docstring).  One host wait for the total.  ``mask`` (a bool / uint8
+    CUDA tensor [nq, nt] or a resident Mask, as in ``knn``): the same lists without the pairs it forbids
+    (``fm_radius_match_masked_dev``)."""
     _refuse_wide("radius_match", "radiusMatch", q, t)
     nq, device = _rows_and_device(q)
     if not isinstance(t, _ffi.Bank):
         _checked(t)
     rad, r_all = _radius(r, nq, device)
+    mask = _pair_mask_checked(mask, q, t)
     qb, tb, made = _pair(q, t)
     try:
         stream, dev = _stream_and_device(qb.ctx)
+        if mask is not None:
+            mk = _pair_mask(mask, qb, tb, made)
+            return _radius_lists(lambda *a, **k: qb.ctx.radius_match_masked_dev(qb, tb, mk, *a, **k), qb.n, rad, r_all, stream, dev, False)
         return _radius_lists(lambda *a, **k: qb.ctx.radius_match_dev(qb, tb, *a, **k), qb.n, rad, r_all, stream, dev, False)
     finally:
         for b in made:
@@ -364,8 +391,9 @@ def _binary_operand(who, x):
     return t
 
 
-def hamming_radius_match(q, t, r):
-    """``cv2.BFMatcher(NORM_HAMMING).radiusMatch`` on binary descriptors: ``(offsets int64 [nq + 1], idx int32 [n], dist
+def hamming_radius_match(q, t, r, mask=None):
+    """``mask`` as in ``radius_match``.
+    ``cv2.BFMatcher(NORM_HAMMING).radiusMatch`` on binary descriptors: ``(offsets int64 [nq + 1], idx int32 [n], dist
     float32 [n])`` CUDA tensors, every train row with ``popcount(q XOR t) < r`` per query row (strict, float32: ``h <= H`` is
     ``r = H + 0.5``), ascending (h, train index).  ``q`` / ``t``: uint8 CUDA tensors of packed bits or binary ``Bank``s;
     ``r`` as in ``radius_match``.  One host wait for the total."""
@@ -377,6 +405,7 @@ def hamming_radius_match(q, t, r):
     nq = ops[0].n if isinstance(ops[0], _ffi.Bank) else ops[0].shape[0]
     ctx = next((x.ctx for x in ops if isinstance(x, _ffi.Bank)), None)
     rad, r_all = _radius(r, nq, ctx.device if ctx is not None else ops[0].device.index)
+    mask = _pair_mask_checked(mask, ops[0], ops[1])
     made, banks = [], []
     try:
         for x in ops:
@@ -387,6 +416,9 @@ def hamming_radius_match(q, t, r):
             banks.append(x)
         qb, tb = banks
         stream, dev = _stream_and_device(qb.ctx)
+        if mask is not None:
+            mk = _pair_mask(mask, qb, tb, made)
+            return _radius_lists(lambda *a, **k: qb.ctx.radius_match_masked_dev(qb, tb, mk, *a, **k), qb.n, rad, r_all, stream, dev, False)
         return _radius_lists(lambda *a, **k: qb.ctx.hamming_radius_match_dev(qb, tb, *a, **k), qb.n, rad, r_all, stream, dev, False)
     finally:
         for b in made:
@@ -532,8 +564,9 @@ def wide_knn_masked(q, t, k, mask):
             b.close()
 
 
-def wide_radius_match(q, t, r):
-    """``cv2.BFMatcher.radiusMatch`` on wide float descriptors (129 .. 256 values per row): ``(offsets int64 [nq + 1], idx int32
+def wide_radius_match(q, t, r, mask=None):
+    """``mask`` as in ``radius_match``.
+    ``cv2.BFMatcher.radiusMatch`` on wide float descriptors (129 .. 256 values per row): ``(offsets int64 [nq + 1], idx int32
     [n], dist float32 [n])`` CUDA tensors, every train row with distance < r per query row, ascending (distance, train index).
     ``q`` / ``t``: float32 / float16 / bfloat16 CUDA tensors (half and bfloat16 widened exactly) or wide ``Bank``s; ``r``: a
     scalar, or a float32 CUDA tensor [nq] read in place behind the current stream's work, as in ``radius_match`` (which keeps
@@ -546,6 +579,7 @@ def wide_radius_match(q, t, r):
     nq = ops[0].n if isinstance(ops[0], _ffi.Bank) else ops[0].shape[0]
     ctx = next((x.ctx for x in ops if isinstance(x, _ffi.Bank)), None)
     rad, r_all = _radius(r, nq, ctx.device if ctx is not None else ops[0].device.index)
+    mask = _pair_mask_checked(mask, ops[0], ops[1])
     made, banks = [], []
     try:
         for x in ops:
@@ -556,6 +590,9 @@ def wide_radius_match(q, t, r):
             banks.append(x)
         qb, tb = banks
         stream, dev = _stream_and_device(qb.ctx)
+        if mask is not None:
+            mk = _pair_mask(mask, qb, tb, made)
+            return _radius_lists(lambda *a, **k: qb.ctx.radius_match_masked_dev(qb, tb, mk, *a, **k), qb.n, rad, r_all, stream, dev, False)
         return _radius_lists(lambda *a, **k: qb.ctx.wide_radius_match_dev(qb, tb, *a, **k), qb.n, rad, r_all, stream, dev, False)
     finally:
         for b in made:
@@ -713,8 +750,10 @@ class Collection(object):
             for b in made:
                 b.close()
 
-    def radius_match(self, q, r):
-        """Every row of the stacked images with distance < r per query row: ``(offsets int64 [nq + 1], img int32 [n], idx int32
+    def radius_match(self, q, r, masks=None):
+        """``masks`` (one tensor per image, None = everything, or a resident Mask from ``mask``; as in ``knn``): the same lists
+        without the pairs they forbid (``fm_collection_radius_match_masked_dev``).
+        Every row of the stacked images with distance < r per query row: ``(offsets int64 [nq + 1], img int32 [n], idx int32
         [n], dist float32 [n])`` CUDA tensors, row i's list at ``offsets[i]:offsets[i + 1]``, ascending (distance, image, row
         inside the image).  ``r`` as in the module's ``radius_match``.  One host wait for the total."""
         self._refuse_wide_collection("radius_match")
@@ -724,13 +763,17 @@ class Collection(object):
         try:
             stream, dev = _stream_and_device(qb.ctx)
             coll = self._coll
+            if masks is not None:
+                mk = self._masks(masks, qb.n, made)
+                return _radius_lists(lambda *a, **k: coll.radius_match_masked_dev(qb, mk, *a, **k), qb.n, rad, r_all, stream, dev, True)
             return _radius_lists(lambda *a, **k: coll.radius_match_dev(qb, *a, **k), qb.n, rad, r_all, stream, dev, True)
         finally:
             for b in made:
                 b.close()
 
-    def hamming_radius_match(self, q, r):
-        """``radius_match`` of binary descriptors against a binary collection (``add(tensor, binary=True)``): every row of the
+    def hamming_radius_match(self, q, r, masks=None):
+        """``masks`` as in ``radius_match``.
+        ``radius_match`` of binary descriptors against a binary collection (``add(tensor, binary=True)``): every row of the
         stacked images with ``popcount(q XOR t) < r`` per query row, ``(offsets, img, idx, dist)`` ascending (h, image, row
         inside the image).  ``q``: a uint8 CUDA tensor of packed bits or a binary ``Bank``; ``r`` as in the module's
         ``radius_match``.  One host wait for the total."""
@@ -741,12 +784,16 @@ class Collection(object):
         rad, r_all = _radius(r, nq, device if self._context is None else self._context.device)
         coll = self._collection(x.ctx if is_bank else _ctx_for(x, self._context))
         qb = x if is_bank else bank(x, binary=True, context=self._context)
+        made = [] if is_bank else [qb]
         try:
             stream, dev = _stream_and_device(qb.ctx)
+            if masks is not None:
+                mk = self._masks(masks, qb.n, made)
+                return _radius_lists(lambda *a, **k: coll.radius_match_masked_dev(qb, mk, *a, **k), qb.n, rad, r_all, stream, dev, True)
             return _radius_lists(lambda *a, **k: coll.hamming_radius_match_dev(qb, *a, **k), qb.n, rad, r_all, stream, dev, True)
         finally:
-            if not is_bank:
-                qb.close()
+            for b in made:
+                b.close()
 
     def fast_match_each(self, q, tau, cap=None):
         """Fast-Match's accepted-match test of ``q`` inside every image separately, left on the device: ``(rows int32

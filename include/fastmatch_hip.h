@@ -82,7 +82,8 @@ typedef struct fm_bank fm_bank;
  * revision 12, additions only -- fm_wide_radius_match, fm_wide_radius_match_dev, fm_collection_wide_radius_match,
  * fm_collection_wide_radius_match_dev; still revision 12, additions only -- fm_wide_knn_masked, fm_wide_knn_masked_dev; still
  * revision 12, additions only -- fm_collection_wide_knn, fm_collection_wide_knn_dev, fm_collection_wide_knn2_ratio,
- * fm_collection_wide_knn2_ratio_dev, fm_collection_wide_votes).  A binding
+ * fm_collection_wide_knn2_ratio_dev, fm_collection_wide_votes; still revision 12, additions only -- fm_radius_match_masked,
+ * fm_radius_match_masked_dev, fm_collection_radius_match_masked, fm_collection_radius_match_masked_dev).  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.              */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -238,7 +239,8 @@ int  fm_bank_create_f32_route(fm_ctx* ctx, const float* rows, int64_t n, int dim
  * calls of "Hamming Fast-Match" are the ones that serve binary banks), fm_xcheck1_keys*,
  * fm_xcheck1_batched, fm_bank_refill_u8_async, fm_bank_append_*, fm_expand_create.  A binary bank paired with a non-binary one
  * is FM_EINVAL, even when one of them is empty.  Not built: NORM_HAMMING2, masked Hamming radius queries, the expansion loop
- * (fm_expand_*) and the async / batch / sharded-key forms of the accepted-match test on binary banks, k > 8.                    */
+ * (fm_expand_*) and the async / batch / sharded-key forms of the accepted-match test on binary banks, k > 8.  (Masked Hamming
+ * radius queries have since come: "Masked radiusMatch" below.)                                                                 */
 int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t n, int bytes, fm_bank** bank);
 /* ---- K14: wide float banks, 129 .. 256 values per row ---------------------------------------------------------------------
  * The 256-D float descriptors of learned extractors (SuperPoint and its kin).  fm_bank_create_f32, fm_bank_create_f32_route and
@@ -510,7 +512,8 @@ int fm_hamming_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* 
  * Not built: a triangular sweep (every tile once, for both directions); the async / batch / sharded-key forms
  * (fm_match_accepted_async, _batch, _dev_async, _dev_batch, fm_xcheck1_keys*) for wide banks; fm_expand_* on wide banks; wide
  * radiusMatch, masks, k >= 3; a shared launch for fm_wide_self_dist_batch.  (radiusMatch on wide banks has since come under
- * names of its own: "Wide radiusMatch" below.)                                                                           */
+ * names of its own: "Wide radiusMatch" below; masks on wide knnMatch and on wide radiusMatch too: "Wide knnMatch masks",
+ * "Masked radiusMatch".)                                                                                                  */
 int fm_wide_self_dist(fm_ctx* ctx, const fm_bank* bank, double* selfdist /*[n]*/);
 int fm_wide_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks, double* const* out /*NULL, or [n] of NULL / [n_i]*/);
 int fm_wide_set_selfdist(fm_ctx* ctx, fm_bank* bank, const double* selfdist /*[n]*/);
@@ -557,7 +560,7 @@ int fm_wide_match_accepted_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
  * Accounted in fm_stats like fm_radius_match: the host forms add nq * real rows pairs, the _dev forms are not accounted.
  * Not built: masks; compactResult = True; one sweep that counts and fills in a single pass; k >= 3 and the stacked knn forms
  * on a wide collection.  (The stacked knn forms on a wide collection have since come, k = 1, 2: "Wide stacked knnMatch"
- * below.)                                                                                                                 */
+ * below; masks on a pair of wide banks have since come: "Masked radiusMatch" below.  A wide collection takes no mask.)     */
 int fm_wide_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const float* radius /*[nq] or NULL*/,
                          float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* idx, float* dist,
                          int64_t* n_total);
@@ -1028,7 +1031,8 @@ int  fm_collection_wide_radius_match_dev(fm_ctx* ctx, fm_collection* coll, const
  *   so no float32-root repair pass exists or is needed.
  * Not built ("masks"): masks on the fp16-filter (K8) and FP4 (K11) matrix-core sweeps (the float32 route and binary banks take
  *   the vector-ALU kernels for every k), masked crossCheck, masked radiusMatch, masked ratio / mutual-ratio / accepted-match
- *   calls, masks in the _each forms.                                                                                        */
+ *   calls, masks in the _each forms.  (Masked radiusMatch has since come, on the matrix cores of all four bank kinds: "Masked
+ *   radiusMatch" below.)                                                                                                    */
 typedef struct fm_mask fm_mask;
 int  fm_mask_create(fm_ctx* ctx, int64_t nq, int64_t nt, fm_mask** mask);
 int  fm_mask_create_coll(fm_ctx* ctx, int64_t nq, fm_collection* coll, fm_mask** mask);
@@ -1080,6 +1084,60 @@ int  fm_collection_knn_masked_dev(fm_ctx* ctx, fm_collection* coll, const fm_ban
 int  fm_wide_knn_masked(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, int32_t k, int32_t* idx /*[nq*k]*/, float* dist /*[nq*k]*/);
 int  fm_wide_knn_masked_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, int32_t k, int32_t* d_idx /*device [nq*k]*/,
                             float* d_dist /*device [nq*k]*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+
+/* ---- Masked radiusMatch: radiusMatch(q, t, maxDistance, mask) on all four bank kinds (K10 under a mask, csrc/radius.hip) ------
+ * cv2.BFMatcher.radiusMatch takes a mask as knnMatch and match do (recalled, not verified, like the mask rules above).
+ * Guided matching: every database row within r of a descriptor AMONG the rows inside a window round a predicted position or
+ * inside an epipolar band -- without sweeping, sorting and reading back the forbidden rows first.
+ * The existing radius calls (fm_radius_match, fm_hamming_radius_match, fm_wide_radius_match, their _dev and collection forms)
+ * keep every refusal they have.  The four calls here are new names and dispatch on the bank kind; each argument list is its
+ * unmasked namesake's with `const fm_mask* mask` behind the train operand:
+ *   fm_radius_match_masked(_dev): FM_BANK_I8 pairs, float32-route pairs, FM_BANK_BIN pairs (distance and radius rules of
+ *     fm_hamming_radius_match) and FM_BANK_F32W pairs (those of fm_wide_radius_match); the mask is fm_mask_create's.
+ *   fm_collection_radius_match_masked(_dev): integer, float32 and binary collections; the mask is fm_mask_create_coll's.  A wide
+ *     collection is FM_EUNSUPPORTED with a message that says "wide" (fm_mask_create_coll keeps refusing one: no such mask exists).
+ * Contract: row i's list is the list the unmasked call returns for the same operands and radii with every entry whose pair
+ *   (i, train row) is forbidden removed -- nothing else changes.  The distance bits, the strict float32 compare dist < r and
+ *   the order (distance bits, train index) -- a collection: (bits, img, row) -- are the unmasked call's.  r <= 0 or NaN: an
+ *   empty list; r = +inf: every permitted real row.  offsets, cap (cap = 0: counts only; the longest prefix of whole rows is
+ *   written) and *n_total follow fm_radius_match's rules unchanged.  An all-ones mask reproduces the unmasked call bit for bit,
+ *   an all-zero mask gives all-zero offsets.  nq = 0 and nt = 0 are valid.  No option changes a result; "radius_ws_bytes" keeps
+ *   its meaning (24 bytes per candidate, 28 against a collection -- of the PERMITTED candidates only).  A train bank that grew by
+ *   appends never lists a gap row, whatever the mask says.
+ * Errors, in this order: (1) NULL handles (ctx, banks / collection, mask): FM_EINVAL; (2) the pair's rules -- width or kind
+ *   mismatch, a binary or wide bank against one that is not: FM_EINVAL -- or fm_collection_radius_match's for the collection
+ *   forms (a wide collection or a wide query bank: FM_EUNSUPPORTED; a query bank not of the collection's kind: FM_EINVAL);
+ *   (3) the mask checks of fm_knn_masked, FM_EINVAL with a message that says which: a mask of another context, a mask whose nq
+ *   differs from the query bank's rows or whose train rows differ from the train bank's, a pair mask given to a collection form
+ *   and the reverse, a mask of another collection, a collection that has changed (add or clear) since fm_mask_create_coll;
+ *   (4) cap < 0, offsets NULL, idx / dist (img) NULL with cap > 0: FM_EINVAL; the _dev forms: fm_radius_match_dev's
+ *   device-pointer checks.  A refused call writes nothing.
+ * Streams and accounting: the device forms follow fm_radius_match_dev -- radii read in place, offsets and lists written to the
+ *   caller's device arrays, ordered against consumer_stream in both directions, not accounted in fm_stats; the host forms are
+ *   accounted like fm_radius_match (pairs = nq * real train rows, whatever the mask permits).
+ * Kernels: the four threshold sweeps of K10 in MASKED instantiations (the mask is a compile-time parameter; the unmasked
+ *   kernels are the code they were): v_mfma_i32_16x16x64_i8, v_mfma_f32_16x16x32_f16 (128-D and wide) and the FP4
+ *   v_mfma_scale_f32_16x16x128_f8f6f4.  Per query row and 64-row stage a lane reads one 8-byte mask word, one stage ahead of its
+ *   use, and ANDs its 16 bits into the sweep's hit bits in front of the count and in front of the key writes -- the count pass
+ *   and the fill pass read the same words.  A wave whose rows permit nothing in a stage skips the stage's operand reads from LDS
+ *   and its MFMAs (per block of 16 query rows too); it still takes part in the stage's load and barriers.  The float32
+ *   route's `all` path (every pair a candidate) takes the mask as well; the rescoring kernels only ever see permitted pairs.
+ * Not built: masks on a wide collection; masked crossCheck, ratio, mutual-ratio and accepted-match calls; compactResult in the
+ *   C ABI (the Python BFMatcher drops the rows itself); a skip of the whole workgroup's stage load, or of the wide sweep's
+ *   streamed operand fetch, where every row forbids a stage.                                                                  */
+int  fm_radius_match_masked(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask, const float* radius /*[nq] or NULL*/,
+                            float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/, int32_t* idx, float* dist, int64_t* n_total);
+int  fm_radius_match_masked_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const fm_mask* mask,
+                                const float* d_radius /*device [nq] or NULL*/, float radius_all, int64_t cap,
+                                int64_t* d_offsets /*device [nq+1]*/, int32_t* d_idx, float* d_dist, int64_t* n_total /*host, or NULL*/,
+                                void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
+int  fm_collection_radius_match_masked(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const fm_mask* mask,
+                                       const float* radius /*[nq] or NULL*/, float radius_all, int64_t cap, int64_t* offsets /*[nq+1]*/,
+                                       int32_t* img, int32_t* idx, float* dist, int64_t* n_total);
+int  fm_collection_radius_match_masked_dev(fm_ctx* ctx, fm_collection* coll, const fm_bank* q, const fm_mask* mask,
+                                           const float* d_radius /*device [nq] or NULL*/, float radius_all, int64_t cap,
+                                           int64_t* d_offsets /*device [nq+1]*/, int32_t* d_img, int32_t* d_idx, float* d_dist,
+                                           int64_t* n_total /*host, or NULL*/, void* consumer_stream /*hipStream_t or FM_NO_STREAM*/);
 
 /* ---- Wide stacked knnMatch: a wide query against ALL images of a wide collection at once (K14 over the stack, csrc/wide_stack.hip) --
  * cv2.BFMatcher.add(images) followed by knnMatch(query, k) for wide float descriptors (FM_BANK_F32W, 129 .. 256 values per row):
