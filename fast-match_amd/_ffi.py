@@ -22,6 +22,8 @@ FM_BANK_BIN = 3             # binary descriptors (Context.bank_binary): NORM_HAM
 FM_BANK_F32W = 4            # float rows of 129 .. 256 values (Context.bank / bank_from_device make it for every such width)
 # element types of rows in device memory (Context.bank_from_device)
 FM_DT_U8, FM_DT_F32, FM_DT_F16, FM_DT_BF16, FM_DT_BIN = 1, 2, 3, 4, 5
+FM_BANK_BIN2 = 5            # binary descriptors of 2-bit cells (Context.bank_binary2): NORM_HAMMING2
+FM_DT_BIN2 = 6              # ... their rows in device memory (Context.bank_from_device; banks only)
 
 
 class FastMatchHipError(RuntimeError):
@@ -88,6 +90,7 @@ SYMBOLS = {
     "fm_bank_create_f32": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
     "fm_bank_create_f32_route": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
     "fm_bank_create_bin": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
+    "fm_bank_create_bin2": (_INT, [_P, _P, _I64, _INT, ctypes.POINTER(_P)]),
     "fm_bank_create_dev": (_INT, [_P, _P, _INT, _I64, _INT, _I64, _INT, _P, ctypes.POINTER(_P)]),
     "fm_knn_dev": (_INT, [_P, _P, _P, _I32, _P, _P, _P]),
     "fm_xcheck1_dev": (_INT, [_P, _P, _P, _P, _P, _P]),
@@ -1331,6 +1334,22 @@ class Context(object):
         a = np.ascontiguousarray(a)
         h = _P()
         self._check(self.lib.fm_bank_create_bin(self.handle, _ptr(a) if a.shape[0] else None, a.shape[0], a.shape[1], ctypes.byref(h)))
+        n, dim, kind = _I64(), _INT(), _INT()
+        self._check(self.lib.fm_bank_info(h, ctypes.byref(n), ctypes.byref(dim), ctypes.byref(kind)))
+        return Bank(self, h, n.value, dim.value, kind.value)
+
+    def bank_binary2(self, rows):
+        """Upload binary descriptors whose elements are 2-bit values (ORB with ``WTA_K`` = 3 or 4): uint8 [n, bytes],
+        1 <= bytes <= 64, for NORM_HAMMING2 (``fm_bank_create_bin2``; kind ``FM_BANK_BIN2``).  knn2 / knn / xcheck1 / knn2_ratio /
+        mutual_ratio, their ``_dev`` forms and hamming_radius_match take a pair of such banks; every other call refuses one."""
+        a = np.asarray(rows)
+        if a.ndim != 2:
+            raise ValueError("descriptor bank must be 2-D [n, bytes]")
+        if a.dtype != np.uint8:
+            raise ValueError("binary descriptors must be uint8 (cv2 asserts CV_8U for NORM_HAMMING2), got %s" % a.dtype)
+        a = np.ascontiguousarray(a)
+        h = _P()
+        self._check(self.lib.fm_bank_create_bin2(self.handle, _ptr(a) if a.shape[0] else None, a.shape[0], a.shape[1], ctypes.byref(h)))
         n, dim, kind = _I64(), _INT(), _INT()
         self._check(self.lib.fm_bank_info(h, ctypes.byref(n), ctypes.byref(dim), ctypes.byref(kind)))
         return Bank(self, h, n.value, dim.value, kind.value)

@@ -611,6 +611,9 @@ extern "C" int fm_collection_add_dev(fm_ctx* ctx, fm_collection* c, const void* 
     const char* who = "fm_collection_add_dev";
     int rc = coll_check(ctx, c, who);
     if (rc != FM_OK) return rc;
+    if (dtype == FM_DT_BIN2)
+        return fail(ctx, FM_EUNSUPPORTED, "fm_collection_add_dev: NORM_HAMMING2 rows (FM_DT_BIN2) are served as bank pairs only (fm_bank_create_dev, "
+                                          "fm_bank_create_bin2); a collection takes none");
     if (dtype < FM_DT_U8 || dtype > FM_DT_BIN)
         return fail(ctx, FM_EINVAL, "fm_collection_add_dev: unknown dtype " + std::to_string(dtype) + " (FM_DT_U8 .. FM_DT_BIN)");
     if (n < 0 || dim < 1) return fail(ctx, FM_EINVAL, "fm_collection_add_dev: bad n / width");
@@ -1405,6 +1408,7 @@ static int coll_wide_radius(fm_ctx* ctx, fm_collection* c, const fm_bank* q, con
     int rc = coll_check(ctx, c, who_);
     if (rc != FM_OK) return rc;
     if (!q) return fail(ctx, FM_EINVAL, who + ": query bank is NULL");
+    if ((rc = refuse_bin2(ctx, q, who_)) != FM_OK) return rc;
     const bool cbin = c->dim != 0 && c->stack.kind == FM_BANK_BIN && !coll_is_wide(c);
     if (q->kind != FM_BANK_F32W || (!c->rows.empty() && !coll_is_wide(c)))
         return fail(ctx, FM_EINVAL, who + ": the collection and the query bank must be wide float (fm_collection_add_wide; FM_BANK_F32W: "
@@ -1629,6 +1633,7 @@ static int coll_wide_stack_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q
     int rc = coll_check(ctx, c, who_);
     if (rc != FM_OK) return rc;
     if (!q) return fail(ctx, FM_EINVAL, who + ": query bank is NULL");
+    if ((rc = refuse_bin2(ctx, q, who_)) != FM_OK) return rc;
     if (q->kind != FM_BANK_F32W || (!c->rows.empty() && !coll_is_wide(c)))
         return fail(ctx, FM_EINVAL, who + ": the collection and the query bank must be wide float (fm_collection_add_wide; FM_BANK_F32W: "
                                           "fm_bank_create_f32 with 129 .. 256 values per row); " + narrow +
@@ -2149,6 +2154,7 @@ static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, cons
         // (the kinds before coll_query_check's own refusals: a collection or a query bank that is not binary is FM_EINVAL here)
         if ((rc = coll_check(ctx, c, a.who)) != FM_OK) return rc;
         if (!q) return fail(ctx, FM_EINVAL, who + ": query bank is NULL");
+        if ((rc = refuse_bin2(ctx, q, a.who)) != FM_OK) return rc;
         if (q->kind != FM_BANK_BIN || (c->dim != 0 && c->stack.kind != FM_BANK_BIN))
             return fail(ctx, FM_EINVAL, who + ": the collection and the query bank must be binary (fm_collection_add_bin, fm_bank_create_bin); " +
                                             a.l2 + " is the L2 call");
@@ -2157,6 +2163,7 @@ static int coll_elect_each(fm_ctx* ctx, fm_collection* c, const fm_bank* q, cons
         // (the header's order: handles, the kinds, the widths; coll_query_check refuses wide data and is not asked)
         if ((rc = coll_check(ctx, c, a.who)) != FM_OK) return rc;
         if (!q) return fail(ctx, FM_EINVAL, who + ": query bank is NULL");
+        if ((rc = refuse_bin2(ctx, q, a.who)) != FM_OK) return rc;
         const bool cbin = c->dim != 0 && c->stack.kind == FM_BANK_BIN && !coll_is_wide(c);
         if (q->kind != FM_BANK_F32W || (!c->rows.empty() && !coll_is_wide(c)))
             return fail(ctx, FM_EINVAL, who + ": the collection and the query bank must be wide float (fm_collection_add_wide; FM_BANK_F32W: "

@@ -1299,6 +1299,7 @@ extern "C" int fm_bank_create_f32_cap(fm_ctx* ctx, int dim, int64_t capacity, co
     *out = nullptr;
     if (dim < 1 || dim > kDim || capacity < 1 || capacity > (int64_t)INT32_MAX - 2 * kStageRows)
         return fail(ctx, FM_EINVAL, "fm_bank_create_f32_cap: bad dim / capacity");
+    if (int rc = refuse_bin2(ctx, scale_like, "fm_bank_create_f32_cap")) return rc;
     if (!scale_like || scale_like->kind != FM_BANK_F32 || !scale_like->filt_ok)
         return fail(ctx, FM_EINVAL, "fm_bank_create_f32_cap: scale_like must be a float32-route bank of finite values");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1439,42 +1440,45 @@ int fm::bank_f32_range_planes(fm_ctx* ctx, Bank& b, int64_t off, int64_t n, int6
     return FM_OK;
 }
 
-// K11: a binary bank -- [n][bytes] packed rows, 1 <= bytes <= 64 -- for NORM_HAMMING (hamming.hip).
-static int bank_create_bin(fm_ctx* ctx, const uint8_t* rows, int64_t n, int bytes, fm_bank** out, const DevSrc* dev = nullptr)
+// K11: a binary bank -- [n][bytes] packed rows, 1 <= bytes <= 64 -- for NORM_HAMMING (hamming.hip) or, kind FM_BANK_BIN2, for
+// NORM_HAMMING2 (K11b, hamming2.hip): the same checks in the same order, the same packed plane, the tetrahedral FP4 image.
+static int bank_create_bin(fm_ctx* ctx, const uint8_t* rows, int64_t n, int bytes, fm_bank** out, const DevSrc* dev = nullptr, int kind = FM_BANK_BIN)
 {
-    if (!ctx) return fail(nullptr, FM_EINVAL, "fm_bank_create_bin: ctx is NULL");
-    if (!out) return fail(ctx, FM_EINVAL, "fm_bank_create_bin: bank out pointer is NULL");
+    const std::string who = kind == FM_BANK_BIN2 ? "fm_bank_create_bin2" : "fm_bank_create_bin";
+    if (!ctx) return fail(nullptr, FM_EINVAL, who + ": ctx is NULL");
+    if (!out) return fail(ctx, FM_EINVAL, who + ": bank out pointer is NULL");
     *out = nullptr;
-    if (n < 0 || bytes < 1 || (n > 0 && !rows && !dev)) return fail(ctx, FM_EINVAL, "fm_bank_create_bin: bad rows/n/bytes");
-    if (bytes > 64) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_bin: binary rows of more than 64 bytes (512 bits) are not supported");
-    if (n > (int64_t)INT32_MAX - 2 * kStageRows) return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_bin: n too large");
+    if (n < 0 || bytes < 1 || (n > 0 && !rows && !dev)) return fail(ctx, FM_EINVAL, who + ": bad rows/n/bytes");
+    if (bytes > 64) return fail(ctx, FM_EUNSUPPORTED, who + ": binary rows of more than 64 bytes (512 bits) are not supported");
+    if (n > (int64_t)INT32_MAX - 2 * kStageRows) return fail(ctx, FM_EUNSUPPORTED, who + ": n too large");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     fm_bank* b = new (std::nothrow) fm_bank();
-    if (!b) return fail(ctx, FM_ENOMEM, "fm_bank_create_bin: out of host memory");
-    b->kind = FM_BANK_BIN;
+    if (!b) return fail(ctx, FM_ENOMEM, who + ": out of host memory");
+    b->kind = kind;
     b->n = n;
     b->dim = bytes;
     b->ksteps = (bytes + 15) / 16;
+    b->ksteps4 = kind == FM_BANK_BIN2 ? ham2_fp4_steps(bytes) : b->ksteps;
     b->n_pad = ((n + kStageRows - 1) / kStageRows) * kStageRows;
     if (b->n_pad == 0) b->n_pad = kStageRows;
     b->cap_pad = b->n_pad;
     auto bail = [&](hipError_t e, const char* what) {
         (void)hipGetLastError();
         bank_free(b); delete b;
-        return fail(ctx, e == hipErrorOutOfMemory ? FM_ENOMEM : FM_EDEVICE, std::string("fm_bank_create_bin: ") + what + ": " + hipGetErrorString(e));
+        return fail(ctx, e == hipErrorOutOfMemory ? FM_ENOMEM : FM_EDEVICE, std::string(who + ": ") + what + ": " + hipGetErrorString(e));
     };
     hipError_t e;
     if ((e = hipMalloc((void**)&b->rowsb, (size_t)b->n_pad * b->ksteps * 16)) != hipSuccess) return bail(e, "packed rows");
-    if ((e = hipMalloc((void**)&b->rows4, (size_t)b->n_pad * b->ksteps * 64)) != hipSuccess) return bail(e, "FP4 rows");
+    if ((e = hipMalloc((void**)&b->rows4, (size_t)b->n_pad * b->ksteps4 * 64)) != hipSuccess) return bail(e, "FP4 rows");
     if (dev) {
         // (device rows: the preparation kernel reads them in place, at the caller's pitch)
-        if ((e = launch_hamming_prep(dev->rows, n, bytes, *b, ctx->stream, dev->pitch)) != hipSuccess) return bail(e, "prepare");
+        if ((e = (kind == FM_BANK_BIN2 ? launch_hamming2_prep : launch_hamming_prep)(dev->rows, n, bytes, *b, ctx->stream, dev->pitch)) != hipSuccess) return bail(e, "prepare");
     } else {
         const size_t src_bytes = (size_t)n * bytes;
         int rc = ws_ensure(ctx, &ctx->ws_in, &ctx->ws_in_bytes, src_bytes + 64);
         if (rc != FM_OK) { bank_free(b); delete b; return rc; }
         if (src_bytes && (e = hipMemcpyAsync(ctx->ws_in, rows, src_bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return bail(e, "upload");
-        if ((e = launch_hamming_prep((const uint8_t*)ctx->ws_in, n, bytes, *b, ctx->stream)) != hipSuccess) return bail(e, "prepare");
+        if ((e = (kind == FM_BANK_BIN2 ? launch_hamming2_prep : launch_hamming_prep)((const uint8_t*)ctx->ws_in, n, bytes, *b, ctx->stream, 0)) != hipSuccess) return bail(e, "prepare");
     }
     if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(e, "prepare");
     *out = b;
@@ -1486,6 +1490,11 @@ extern "C" int fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows, int64_t n, i
     return bank_create_bin(ctx, rows, n, bytes, out);
 }
 
+extern "C" int fm_bank_create_bin2(fm_ctx* ctx, const uint8_t* rows, int64_t n, int bytes, fm_bank** out)
+{
+    return bank_create_bin(ctx, rows, n, bytes, out, nullptr, FM_BANK_BIN2);
+}
+
 // A bank from rows that are already in device memory (include/fastmatch_hip.h: "device sources").  The preparation kernels
 // read the caller's memory in place behind an event recorded on producer_stream; every creator synchronises the context's
 // stream before it returns (the flag words come back), so the source is not read after the call.
@@ -1495,10 +1504,10 @@ extern "C" int fm_bank_create_dev(fm_ctx* ctx, const void* d_rows, int dtype, in
     if (!ctx) return fail(nullptr, FM_EINVAL, "fm_bank_create_dev: ctx is NULL");
     if (!bank) return fail(ctx, FM_EINVAL, "fm_bank_create_dev: bank out pointer is NULL");
     *bank = nullptr;
-    if (dtype < FM_DT_U8 || dtype > FM_DT_BIN)
-        return fail(ctx, FM_EINVAL, "fm_bank_create_dev: unknown dtype " + std::to_string(dtype) + " (FM_DT_U8 .. FM_DT_BIN)");
+    if (dtype < FM_DT_U8 || dtype > FM_DT_BIN2)
+        return fail(ctx, FM_EINVAL, "fm_bank_create_dev: unknown dtype " + std::to_string(dtype) + " (FM_DT_U8 .. FM_DT_BIN2)");
     if (n < 0 || dim < 1) return fail(ctx, FM_EINVAL, "fm_bank_create_dev: bad n / dim");
-    if (dtype == FM_DT_BIN && dim > 64)
+    if ((dtype == FM_DT_BIN || dtype == FM_DT_BIN2) && dim > 64)
         return fail(ctx, FM_EUNSUPPORTED, "fm_bank_create_dev: binary rows of more than 64 bytes (512 bits) are not supported");
     if (dim > (dtype == FM_DT_U8 ? kDim : kWideDim))
         return fail(ctx, FM_EUNSUPPORTED, dtype == FM_DT_U8 ? "fm_bank_create_dev: dim > 128 is not supported"
@@ -1520,6 +1529,7 @@ extern "C" int fm_bank_create_dev(fm_ctx* ctx, const void* d_rows, int dtype, in
     }
     const DevSrc src{(const uint8_t*)d_rows, dtype, pitch};
     if (dtype == FM_DT_BIN) return bank_create_bin(ctx, nullptr, n, dim, bank, &src);
+    if (dtype == FM_DT_BIN2) return bank_create_bin(ctx, nullptr, n, dim, bank, &src, FM_BANK_BIN2);
     return bank_create(ctx, nullptr, n, dim, dtype != FM_DT_U8, bank, float_route != 0 && dtype != FM_DT_U8, 0, nullptr, 0, &src);
 }
 
@@ -1652,8 +1662,16 @@ int fm::bank_selfdist_alloc(fm_ctx* ctx, fm_bank* b)
     return FM_OK;
 }
 
+int fm::refuse_bin2(fm_ctx* ctx, const fm_bank* b, const char* who)
+{
+    if (!b || b->kind != FM_BANK_BIN2) return FM_OK;
+    return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": NORM_HAMMING2 banks (FM_BANK_BIN2, fm_bank_create_bin2) are served by fm_knn2, fm_knn, "
+                                      "fm_xcheck1, fm_knn2_ratio, fm_mutual_ratio, their _dev forms and fm_hamming_radius_match(_dev) only");
+}
+
 int fm::refuse_wide(fm_ctx* ctx, const fm_bank* b, const char* who)
 {
+    if (int rc = refuse_bin2(ctx, b, who)) return rc;
     if (!b || b->kind != FM_BANK_F32W) return FM_OK;
     return fail(ctx, FM_EUNSUPPORTED, std::string(who) + ": wide float banks (FM_BANK_F32W, 129 .. 256 values per row) are served by fm_knn2, "
                                           "fm_knn with k <= 2, fm_xcheck1, fm_knn2_ratio, fm_mutual_ratio, their _dev forms and the Wide Fast-Match calls (fm_wide_self_dist, "
@@ -1669,11 +1687,18 @@ int fm::refuse_bin(fm_ctx* ctx, const fm_bank* b, const char* who)
                                       "fm_hamming_set_selfdist, fm_hamming_match_ratio, fm_hamming_match_accepted) only");
 }
 
-int fm::check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who, bool bin_ok)
+int fm::check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who, bool bin_ok, bool bin2_ok)
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
     if (!q || !t) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
+    // (NORM_HAMMING2: any other kind beside it is refused even for an empty bank -- FM_BANK_BIN of the same width included --
+    // and a pair of them is served only where the entry point says so; both in front of the width check, so that the message
+    // names the norm)
+    if ((q->kind == FM_BANK_BIN2) != (t->kind == FM_BANK_BIN2))
+        return fail(ctx, FM_EINVAL, std::string(who) + ": query/train kind mismatch (one bank is a NORM_HAMMING2 bank, FM_BANK_BIN2, the other is not)");
+    if (q->kind == FM_BANK_BIN2 && !bin2_ok) return refuse_bin2(ctx, q, who);
     if (q->dim != t->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": query/train dim mismatch");
+    if (q->kind == FM_BANK_BIN2) return FM_OK;
     // (binary against non-binary is refused even for an empty bank: its rows would go to the L2 kernels)
     if ((q->kind == FM_BANK_BIN) != (t->kind == FM_BANK_BIN))
         return fail(ctx, FM_EINVAL, std::string(who) + ": query/train kind mismatch (one bank is binary, FM_BANK_BIN, the other is not)");

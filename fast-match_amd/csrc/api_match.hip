@@ -576,7 +576,7 @@ int sweep_pair_plan(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, in
 {
     PairSweep ps{};
     size_t off = 0;
-    if (cols.kind == FM_BANK_BIN) {
+    if (cols.kind == FM_BANK_BIN || cols.kind == FM_BANK_BIN2) {      // (K11b takes K11's plan)
         ps.ham = plan_hamming(cols.n_pad, red.n_pad);
         ps.nsplit = ps.ham.nsplit; ps.ncols_alloc = ps.ham.ncols_alloc; ps.f32_keys = 1;
         carve(off, ps.ham.partial_bytes(ktop));
@@ -605,6 +605,8 @@ int sweep_pair_run(fm_ctx* ctx, const Bank& cols, const Bank& red, int ktop, con
     if (events) HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
     if (cols.kind == FM_BANK_BIN)
         HIP_TRY(ctx, launch_hamming(cols, red, ktop, ps.ham, (unsigned long long*)ctx->ws_partial, ctx->stream, stage_real));
+    else if (cols.kind == FM_BANK_BIN2)
+        HIP_TRY(ctx, launch_hamming2(cols, red, ktop, ps.ham, (unsigned long long*)ctx->ws_partial, ctx->stream, stage_real));
     else
         HIP_TRY(ctx, launch_rowreduce(cols, red, ktop, ps.rr, (unsigned long long*)ctx->ws_partial, ps.bound, ctx->tune.glds != 0, ctx->stream, cut,
                                       (cut && ktop == 1) ? filter6_ws(ctx, 1) : nullptr));
@@ -824,7 +826,7 @@ static int knn2_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t*
 
 extern "C" int fm_knn2(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* idx, float* dist)
 {
-    int rc = check_pair(ctx, q, t, "fm_knn2", true);
+    int rc = check_pair(ctx, q, t, "fm_knn2", true, true);
     if (rc != FM_OK) return rc;
     const int64_t nq = q->n;
     if (nq > 0 && (!idx || !dist)) return fail(ctx, FM_EINVAL, "fm_knn2: output pointer is NULL");
@@ -843,7 +845,7 @@ extern "C" int fm_knn2(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t*
 // knnMatch(dt1, dt2, k) for any k the signature of the reference's bf_match / flann_match admits (matchutil.py:39-43, 46-67).
 extern "C" int fm_knn(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k, int32_t* idx, float* dist)
 {
-    int rc = check_pair(ctx, q, t, "fm_knn", true);
+    int rc = check_pair(ctx, q, t, "fm_knn", true, true);
     if (rc != FM_OK) return rc;
     if (k < 1) return fail(ctx, FM_EINVAL, "fm_knn: k must be at least 1");
     if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_knn: k above 8 is not built (cv2.BFMatcher.knnMatch takes any k; the reference calls it with 1 and 2)");
@@ -879,6 +881,8 @@ extern "C" int fm_knn(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k
     HIP_TRY(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
     if (q->kind == FM_BANK_BIN)
         HIP_TRY(ctx, launch_hamming_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
+    else if (q->kind == FM_BANK_BIN2)
+        HIP_TRY(ctx, launch_hamming2_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
     else
         HIP_TRY(ctx, launch_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
@@ -929,9 +933,10 @@ extern "C" int fm_radius_match_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank*
 static int ham_radius_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int64_t cap, const void* offsets, const void* idx, const void* dist,
                             const char* who, const char* pre)
 {
-    int rc = check_pair(ctx, q, t, who, true);
+    int rc = check_pair(ctx, q, t, who, true, true);
     if (rc != FM_OK) return rc;
-    if (q->kind != FM_BANK_BIN || t->kind != FM_BANK_BIN)
+    // (a NORM_HAMMING2 pair -- check_pair has refused one such bank beside any other kind -- takes the radius against h2)
+    if (!(q->kind == FM_BANK_BIN2 && t->kind == FM_BANK_BIN2) && (q->kind != FM_BANK_BIN || t->kind != FM_BANK_BIN))
         return fail(ctx, FM_EINVAL, std::string(who) + ": both banks must be binary (FM_BANK_BIN, fm_bank_create_bin); fm_radius_match is the L2 call");
     if (q->dim != t->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": query/train width mismatch");       // (check_pair's, restated)
     if (cap < 0) return fail(ctx, FM_EINVAL, std::string(who) + ": cap is negative");
@@ -974,6 +979,8 @@ static int wide_radius_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, in
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
     if (!q || !t) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
+    for (const fm_bank* b : {q, t})
+        if (int rc = refuse_bin2(ctx, b, who)) return rc;
     for (const fm_bank* b : {q, t})
         if (b->kind != FM_BANK_F32W)
             return fail(ctx, FM_EINVAL, std::string(who) + ": both banks must be wide float (FM_BANK_F32W: fm_bank_create_f32 with 129 .. 256 "
@@ -1094,7 +1101,7 @@ static int knn2_lowe_device(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, dou
 extern "C" int fm_knn2_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap,
                              int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
 {
-    int rc = check_pair(ctx, q, t, "fm_knn2_ratio", true);
+    int rc = check_pair(ctx, q, t, "fm_knn2_ratio", true, true);
     if (rc != FM_OK) return rc;
     if (n_accepted) *n_accepted = 0;
     const int64_t nq = q->n;
@@ -1487,6 +1494,7 @@ static int named_bank_check(fm_ctx* ctx, const fm_bank* b, const NamedFamily& f,
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
     if (!b) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
+    if (int rc = refuse_bin2(ctx, b, who)) return rc;
     if (b->kind != f.kind) return fail(ctx, FM_EINVAL, std::string(who) + ": " + f.one + "; " + named_served_by(b, l2, ham));
     return FM_OK;
 }
@@ -1955,7 +1963,7 @@ static int xcheck1_keys_common(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
 // float32-route layout, high word = float32 bits of h).
 extern "C" int fm_xcheck1(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* tidx, float* dist)
 {
-    int rc = check_pair(ctx, q, t, "fm_xcheck1", true);
+    int rc = check_pair(ctx, q, t, "fm_xcheck1", true, true);
     if (rc != FM_OK) return rc;
     const int64_t nq = q->n;
     if (nq == 0) return FM_OK;
@@ -2000,7 +2008,7 @@ __global__ void knn_first_col_kernel(const int32_t* __restrict__ idx2, const flo
 
 extern "C" int fm_knn_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k, int32_t* d_idx, float* d_dist, void* consumer_stream)
 {
-    int rc = check_pair(ctx, q, t, "fm_knn_dev", true);
+    int rc = check_pair(ctx, q, t, "fm_knn_dev", true, true);
     if (rc != FM_OK) return rc;
     if (k < 1) return fail(ctx, FM_EINVAL, "fm_knn_dev: k must be at least 1");
     if (k > 8) return fail(ctx, FM_EUNSUPPORTED, "fm_knn_dev: k above 8 is not built");
@@ -2029,6 +2037,8 @@ extern "C" int fm_knn_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32
             HIP_TRY(ctx, launch_knnk_merge((const unsigned long long*)ctx->ws_partial, 0, (int)nq, k, d_idx, d_dist, ctx->stream));
         else if (q->kind == FM_BANK_BIN)
             HIP_TRY(ctx, launch_hamming_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
+        else if (q->kind == FM_BANK_BIN2)
+            HIP_TRY(ctx, launch_hamming2_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
         else
             HIP_TRY(ctx, launch_knnk(*q, *t, k, (unsigned long long*)ctx->ws_partial, d_idx, d_dist, ctx->stream));
     }
@@ -2037,7 +2047,7 @@ extern "C" int fm_knn_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32
 
 extern "C" int fm_xcheck1_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t* d_tidx, float* d_dist, void* consumer_stream)
 {
-    int rc = check_pair(ctx, q, t, "fm_xcheck1_dev", true);
+    int rc = check_pair(ctx, q, t, "fm_xcheck1_dev", true, true);
     if (rc != FM_OK) return rc;
     const int64_t nq = q->n;
     if (nq == 0) return FM_OK;
@@ -2052,7 +2062,7 @@ extern "C" int fm_xcheck1_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, i
 extern "C" int fm_knn2_ratio_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int64_t cap, int32_t* d_rows,
                                  int64_t* d_count, int64_t* n_accepted, void* consumer_stream)
 {
-    int rc = check_pair(ctx, q, t, "fm_knn2_ratio_dev", true);
+    int rc = check_pair(ctx, q, t, "fm_knn2_ratio_dev", true, true);
     if (rc != FM_OK) return rc;
     if (n_accepted) *n_accepted = 0;
     if (cap < 0 || !d_count || (cap > 0 && !d_rows)) return fail(ctx, FM_EINVAL, "fm_knn2_ratio_dev: bad output arguments");
@@ -2185,9 +2195,9 @@ int fm::mutual_reverse_device(fm_ctx* ctx, const Bank& t, const int32_t* cand_ro
     const float pad_aux = -3.4e38f;
     unsigned pad_aux_bits;
     memcpy(&pad_aux_bits, &pad_aux, 4);
-    const size_t rb[4][4] = {{(size_t)kDim, 4, 0, 0}, {(size_t)kDim * 4, (size_t)kDim * 2, 4, 4}, {(size_t)t.ksteps * 16, (size_t)t.ksteps * 64, 0, 0},
+    const size_t rb[4][4] = {{(size_t)kDim, 4, 0, 0}, {(size_t)kDim * 4, (size_t)kDim * 2, 4, 4}, {(size_t)t.ksteps * 16, (size_t)fp4_steps(t) * 64, 0, 0},
                              {(size_t)kWideDim * 4, (size_t)kWideDim * 2, 4, 4}};
-    const int route = t.kind == FM_BANK_F32 ? 1 : t.kind == FM_BANK_BIN ? 2 : t.kind == FM_BANK_F32W ? 3 : 0;
+    const int route = t.kind == FM_BANK_F32 ? 1 : (t.kind == FM_BANK_BIN || t.kind == FM_BANK_BIN2) ? 2 : t.kind == FM_BANK_F32W ? 3 : 0;
     const void* src[4][4] = {{t.rows8, t.norm, nullptr, nullptr}, {t.rowsf, t.rowsh, t.normf, t.auxf}, {t.rowsb, t.rows4, nullptr, nullptr},
                              {t.wrows, t.wrowsh, t.normf, t.auxf}};
     size_t off = 0, o_pl[4] = {0, 0, 0, 0};
@@ -2285,7 +2295,7 @@ static int mutual_ratio_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, do
 extern "C" int fm_mutual_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t symmetric, int64_t cap,
                                int32_t* qidx, int32_t* tidx, float* dist, double* ratio, int64_t* n_accepted)
 {
-    int rc = check_pair(ctx, q, t, "fm_mutual_ratio", true);
+    int rc = check_pair(ctx, q, t, "fm_mutual_ratio", true, true);
     if (rc != FM_OK) return rc;
     if (n_accepted) *n_accepted = 0;
     if (q->n == 0) return FM_OK;
@@ -2298,7 +2308,7 @@ extern "C" int fm_mutual_ratio(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, 
 extern "C" int fm_mutual_ratio_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, double tau, int32_t symmetric, int64_t cap,
                                    int32_t* d_rows, int64_t* d_count, int64_t* n_accepted, void* consumer_stream)
 {
-    int rc = check_pair(ctx, q, t, "fm_mutual_ratio_dev", true);
+    int rc = check_pair(ctx, q, t, "fm_mutual_ratio_dev", true, true);
     if (rc != FM_OK) return rc;
     if (n_accepted) *n_accepted = 0;
     if (cap < 0 || !d_count || (cap > 0 && !d_rows)) return fail(ctx, FM_EINVAL, "fm_mutual_ratio_dev: bad output arguments");
@@ -2570,6 +2580,8 @@ static int named_pair_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, con
 {
     if (!ctx) return fail(nullptr, FM_EINVAL, std::string(who) + ": ctx is NULL");
     if (!q || !t) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
+    for (const fm_bank* b : {q, t})
+        if (int rc = refuse_bin2(ctx, b, who)) return rc;
     if (q->kind != f.kind || t->kind != f.kind)
         return fail(ctx, FM_EINVAL, std::string(who) + ": " + f.both + "; " + named_served_by(q->kind != f.kind ? q : t, l2, ham));
     if (q->dim != t->dim) return fail(ctx, FM_EINVAL, std::string(who) + ": query/train width mismatch");

@@ -853,6 +853,7 @@ static int coll_wide_query_check(fm_ctx* ctx, fm_collection* c, const fm_bank* q
     int rc = coll_check(ctx, c, who);
     if (rc != FM_OK) return rc;
     if (!q) return fail(ctx, FM_EINVAL, std::string(who) + ": query bank is NULL");
+    if ((rc = refuse_bin2(ctx, q, who)) != FM_OK) return rc;
     if (!c->rows.empty() && !coll_is_wide(c))
         return fail(ctx, FM_EINVAL, std::string(who) + ": the collection holds images of another kind (not wide ones, fm_collection_add_wide); "
                                     "it is served by " + narrow);

@@ -118,7 +118,7 @@ namespace fm {
 static inline int64_t bank_bytes(const fm::Bank* b)
 {
     if (!b) return 0;
-    return b->n * (b->kind == FM_BANK_BIN ? b->dim : b->kind == FM_BANK_F32W ? 1024 : b->kind == FM_BANK_F32 ? 512 : 128);
+    return b->n * (b->kind == FM_BANK_BIN || b->kind == FM_BANK_BIN2 ? b->dim : b->kind == FM_BANK_F32W ? 1024 : b->kind == FM_BANK_F32 ? 512 : 128);
 }
 }
 
@@ -183,12 +183,20 @@ void sync_all_streams(fm_ctx* ctx);
 // paired with a non-binary one is FM_EINVAL, empty banks included.  Wide float banks (FM_BANK_F32W) follow the same two rules
 // at the same entry points -- the bin_ok ones serve them (fm_knn: k <= 2) -- so every refusal of a wide bank is made here or
 // in refuse_bin.
-int check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who, bool bin_ok = false);
+// NORM_HAMMING2 banks (FM_BANK_BIN2, K11b) are refused by DEFAULT: only an entry point that passes bin2_ok serves a pair of
+// them (fm_knn2, fm_knn, fm_xcheck1, fm_knn2_ratio, fm_mutual_ratio, their _dev forms, fm_hamming_radius_match(_dev)); for every
+// other one check_pair returns FM_EUNSUPPORTED with a message that names NORM_HAMMING2, whatever bin_ok says.  Such a bank
+// paired with a bank of any other kind -- FM_BANK_BIN of the same width included -- is FM_EINVAL, empty banks included.
+int check_pair(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, const char* who, bool bin_ok = false, bool bin2_ok = false);
 // FM_EUNSUPPORTED for a binary or a wide float bank at an entry point that takes one bank (FM_OK otherwise)
 int refuse_bin(fm_ctx* ctx, const fm_bank* b, const char* who);
-// FM_EUNSUPPORTED for a wide float bank alone: the entry points that do serve binary banks (the collections' query banks)
+// FM_EUNSUPPORTED for a wide float bank alone: the entry points that do serve binary banks (the collections' query banks).
+// (A NORM_HAMMING2 bank is refused here too -- refuse_bin2 -- so every caller of refuse_wide or refuse_bin turns it away.)
 int refuse_wide(fm_ctx* ctx, const fm_bank* b, const char* who);
-static inline bool bin_or_wide(const fm_bank* b) { return b->kind == FM_BANK_BIN || b->kind == FM_BANK_F32W; }
+// FM_EUNSUPPORTED, naming NORM_HAMMING2, for a FM_BANK_BIN2 bank (FM_OK otherwise): the entry points that do not go through
+// check_pair, refuse_bin or refuse_wide call it in front of their own kind checks
+int refuse_bin2(fm_ctx* ctx, const fm_bank* b, const char* who);
+static inline bool bin_or_wide(const fm_bank* b) { return b->kind == FM_BANK_BIN || b->kind == FM_BANK_BIN2 || b->kind == FM_BANK_F32W; }
 // Planes and scale terms of a (query = reduced, train = output rows) pair of float32 banks for x1_round_f32.
 void fill_round_f32(fm::RoundF32* r, const fm::Bank& q, const fm::Bank& t);
 // One expansion round's cross-checked 1-NN on the whole GPU (K7's delegated cross-check, api_match.hip).
@@ -363,6 +371,7 @@ namespace fm {
 // float32 route: rowsf + rowsh + normf + auxf; wide float32: wrows + wrowsh + normf + auxf; binary: rowsb + rows4).
 inline size_t mutual_row_bytes(const Bank& t)
 {
+    if (t.kind == FM_BANK_BIN2) return (size_t)t.ksteps * 16 + (size_t)fp4_steps(t) * 64;      // (the FP4 plane has its own step count)
     return t.kind == FM_BANK_F32W ? (size_t)kWideDim * 6 + 8 : t.kind == FM_BANK_F32 ? (size_t)kDim * 6 + 8 : t.kind == FM_BANK_BIN ? (size_t)t.ksteps * 80 : (size_t)kDim + 4;
 }
 constexpr size_t kMutualGatherBytes = (size_t)1 << 30;     // fm_mutual_ratio's budget for the gathered bank (a collection: "coll_ws_bytes")

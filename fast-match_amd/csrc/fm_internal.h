@@ -58,6 +58,9 @@ struct Bank {
     int      ksteps = 0;
     uint8_t* rowsb  = nullptr; // [n_pad][16 ksteps] packed rows, zero padded
     uint8_t* rows4  = nullptr; // [n_pad][64 ksteps] FP4 image: bit 1 -> +1, bit 0 -> -1, padding 0
+    // FM_BANK_BIN2 (K11b, hamming2.hip): dim and ksteps (the packed plane's 16-byte pieces) as for FM_BANK_BIN; the FP4 plane is
+    // the tetrahedral image, 12 dim values in ksteps4 = ceil(12 dim / 128) K steps: rows4 is [n_pad][64 ksteps4] (fp4_steps below)
+    int      ksteps4 = 0;
     // FM_BANK_I8 of dim 128, for the FP6 filter of the accepted-only sweep (filter6.hip, fp6_filter.h); all null: K1 only
     uint8_t* rows6  = nullptr; // [n_pad][128] e2m3 codes of the raw uint8 rows: four K-chunks of 32 codes (24 bytes) in 32-byte slots
     float*   aux6   = nullptr; // [n_pad / 128][256] accumulator start -floor(|m|^2 / 32) / 64 of a stage's rows (padding -3.4e38), the largest start among its real rows, 127 unused words
@@ -82,6 +85,9 @@ __device__ __forceinline__ bool real_row(const unsigned long long* __restrict__ 
     return (real[m >> 6] >> (m & 63)) & 1ull;
 }
 
+// K steps (64 bytes each) per row of a binary bank's FP4 plane: the packed pieces for NORM_HAMMING, where the two coincide
+inline int fp4_steps(const Bank& b) { return b.kind == FM_BANK_BIN2 ? b.ksteps4 : b.ksteps; }
+
 // rows rounded up to whole 128-row stages
 inline int64_t pad128(int64_t n) { return ((n + kStageRows - 1) / kStageRows) * kStageRows; }
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -102,7 +108,7 @@ inline Bank bank_rows_view(const Bank& b, int64_t r0, int64_t n)
 {
     Bank v;
     v.kind = b.kind; v.n = n; v.dim = b.dim;
-    v.ksteps = b.ksteps; v.kscale = b.kscale; v.filt_ok = b.filt_ok; v.nm_max = b.nm_max; v.usq_max = b.usq_max; v.vfin_max = b.vfin_max;
+    v.ksteps = b.ksteps; v.ksteps4 = b.ksteps4; v.kscale = b.kscale; v.filt_ok = b.filt_ok; v.nm_max = b.nm_max; v.usq_max = b.usq_max; v.vfin_max = b.vfin_max;
     const int64_t room = (b.cap_pad > 0 ? b.cap_pad : b.n_pad) - r0;
     v.n_pad = v.cap_pad = pad128(n) < room ? pad128(n) : room;
     if (b.rows8) v.rows8 = b.rows8 + (size_t)r0 * kDim;
@@ -113,7 +119,7 @@ inline Bank bank_rows_view(const Bank& b, int64_t r0, int64_t n)
     if (b.normf) v.normf = b.normf + r0;
     if (b.auxf)  v.auxf = b.auxf + r0;
     if (b.rowsb) v.rowsb = b.rowsb + (size_t)r0 * b.ksteps * 16;
-    if (b.rows4) v.rows4 = b.rows4 + (size_t)r0 * b.ksteps * 64;
+    if (b.rows4) v.rows4 = b.rows4 + (size_t)r0 * fp4_steps(b) * 64;
     if (b.wrows)  v.wrows = b.wrows + (size_t)r0 * 256;
     if (b.wrowsh) v.wrowsh = b.wrowsh + (size_t)r0 * 256;
     return v;
@@ -318,6 +324,29 @@ hipError_t launch_hamming_prep(const uint8_t* d_src, int64_t n, int bytes, const
 // mask (K13): the bit mask of fm_knn_masked, [q.n][mwords] words, or null
 hipError_t launch_hamming_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream,
                                const int* stage_real = nullptr, const unsigned long long* mask = nullptr, int64_t mwords = 0);
+
+// ---- K11b: NORM_HAMMING2 on binary banks of 2-bit cells (hamming2.hip) --------------------------------------------------------
+// K11's launchers for FM_BANK_BIN2 pairs: the same plans (plan_hamming), the same key layout, h2 for h.
+inline int ham2_fp4_steps(int bytes) { return (12 * bytes + 127) / 128; }
+// packed rows + tetrahedral FP4 image (b.n_pad, b.ksteps, b.ksteps4, b.rowsb, b.rows4 set by the caller)
+hipError_t launch_hamming2_prep(const uint8_t* d_src, int64_t n, int bytes, const Bank& b, hipStream_t stream, int64_t pitch = 0);
+hipError_t launch_hamming2(const Bank& cols, const Bank& red, int ktop, const HamPlan& plan, unsigned long long* partial, hipStream_t stream,
+                           const int* stage_real = nullptr);
+// k-NN lists for 3 <= k <= 8 on the vector ALUs (partial: knnk_partial_bytes)
+hipError_t launch_hamming2_knnk(const Bank& q, const Bank& t, int k, unsigned long long* partial, int32_t* d_idx, float* d_dist, hipStream_t stream);
+// radiusMatch (radius.hip's r_sweep launches these): thr[i] = the least dot product of a hit of query row i
+// (ham2_radius_dot_min, ham_radius.h)
+hipError_t launch_hamming2_radius_limits(const float* radius, float radius_all, int nq, int P, float* thr, hipStream_t stream);
+struct Ham2RSweep {
+    const uint8_t* q4; const uint8_t* t4;   // the FP4 planes, from this launch's first query row on / the train bank's
+    int ks, P3;                             // FP4 K steps per row (1 .. 6), 3 * cells per row
+    int nq, nt, per;                        // query rows of the launch, train rows, train rows per split (whole 128-row stages)
+    const float* thr;                       // per query row of the launch
+    unsigned* cnt;                          // count sweep: hit counts; fill sweep: cursors (zeroed)
+    const int64_t* off; int64_t base;       // fill sweep: segment offsets of the launch's query rows, minus `base`
+    unsigned long long* keys;               // fill sweep: (float32 bits of h2 << 32 | train row)
+};
+hipError_t launch_hamming2_radius(const Ham2RSweep& p, bool fill, int nsplit, hipStream_t stream);
 
 // ---- K14: wide float32 banks, 129 .. 256 values per row (wide_f32.hip) ------------------------------------------------------
 constexpr int kWideDim = 256;

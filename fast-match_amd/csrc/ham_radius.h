@@ -32,4 +32,11 @@ FM_HR_HD inline float ham_radius_dot_min(int H, int W)
     return H < 0 ? INFINITY : (float)(W - 2 * H);
 }
 
+// NORM_HAMMING2 (hamming2.hip): h2 counts the 2-bit cells that differ, an integer of [0, P], P = 4 * bytes <= 256 cells per row;
+// the limit is ham_radius_limit(r, P), and the tetrahedral FP4 image gives dot = 3 P - 4 h2, so  h2 <= H  <=>  dot >= 3 P - 4 H.
+FM_HR_HD inline float ham2_radius_dot_min(int H, int P)
+{
+    return H < 0 ? INFINITY : (float)(3 * P - 4 * H);
+}
+
 }  // namespace fm

@@ -116,6 +116,8 @@ struct RSweep {
     const uint16_t* trowsh; const float* tnormf;
     const uint8_t* q4; const uint8_t* t4;           // Hamming route: the banks' FP4 planes (Bank::rows4), 64 ks bytes per row
     int ks, W;                 // Hamming route: MFMA K steps per row (0: another route), bits per row
+    int ham2;                  // Hamming route on NORM_HAMMING2 banks (K11b): ks = the tetrahedral image's K steps, 1 .. 6, W = 4 bytes cells
+                               // per row; r_sweep hands the launch to hamming2.hip's radius_ham2_kernel
     float cq, ct;              // float32 route: stored |q|^2, |t|^2 -> accumulator units 2^(kq + kt)
     int all;                   // float32 route without filter planes: every pair is a candidate
     int nq, nt, per;           // query rows of the launch, train rows, train rows per split (a multiple of kRStage; Hamming: of 128)
@@ -449,6 +451,15 @@ static hipError_t r_sweep(const RSweep& base, bool f32, bool fill, int64_t q0, i
     p.nq = (int)nq;
     const bool masked = p.mask != nullptr;
     if (masked) p.mask += q0 * p.mwords;
+    if (p.ham2) {
+        // K11b: the Hamming route's plan and pointers, the sweep of hamming2.hip (no masks, no collections: refused by the entry points)
+        if (masked || p.st_real || p.real) return hipErrorInvalidValue;
+        int ns = 1;
+        const int per = r_ham_stages_per_split(nq, p.nt, &ns) * kStageRows;
+        const Ham2RSweep h{p.q4 + q0 * p.ks * 64, p.t4, p.ks, 3 * p.W, (int)nq, p.nt, per, p.thr + q0, p.cnt + (fill ? 0 : q0),
+                           fill ? p.off + q0 : nullptr, p.base, p.keys};
+        return launch_hamming2_radius(h, fill, ns, stream);
+    }
     if (p.ks) {
         p.q4 += q0 * p.ks * 64; p.thr += q0;
         if (fill) p.off += q0;
@@ -623,7 +634,10 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
     const bool wide = q.kind == FM_BANK_F32W;     // (the wide entry points: both operands wide, of one dim; the float32 route's
                                                   // path with the wide sweep, limits and rescoring kernels)
     const bool f32 = q.kind == FM_BANK_F32 || wide;
-    const bool ham = q.kind == FM_BANK_BIN;       // (the Hamming entry points: both banks binary, of one width; counts are final,
+    const bool ham2 = q.kind == FM_BANK_BIN2;     // (fm_hamming_radius_match(_dev) on a NORM_HAMMING2 pair: the Hamming route with h2 for h)
+    if (ham2 && (t.kind != FM_BANK_BIN2 || a.tab || a.mask || fp4_steps(q) != fp4_steps(t)))
+        return fail(ctx, FM_EUNSUPPORTED, std::string(a.who) + ": NORM_HAMMING2 banks are served as plain, unmasked bank pairs only");
+    const bool ham = q.kind == FM_BANK_BIN || ham2;       // (the Hamming entry points: both banks binary, of one width; counts are final,
                                                   // so everything behind the count sweep is the integer route's path)
     const bool all = wide ? !(wide_filter_usable(q, t) && q.kscale <= kRWScaleMax && t.kscale <= kRWScaleMax)
                           : f32 && !filter_usable(q, t);
@@ -663,7 +677,9 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
     const double unit = f32 && !all ? ldexp(1.0, q.kscale + t.kscale) : 1.0;
     // (a collection's nm_max is the real rows': the planes of an image are made while its padding rows still hold 0, the
     // far value goes in afterwards -- coll_f32_finish)
-    if (ham)
+    if (ham2)
+        HIP_TRY(ctx, launch_hamming2_radius_limits(k_rad, a.radius_all, (int)nq, 4 * q.dim, d_thr, ctx->stream));
+    else if (ham)
         hipLaunchKernelGGL(radius_ham_limits_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
                            k_rad, a.radius_all, (int)nq, 8 * q.dim, d_thr);
     else if (wide)
@@ -682,7 +698,7 @@ int radius_match(fm_ctx* ctx, const Bank& q, const Bank& t, const RadiusArgs& a)
     sw.qrowsh = wide ? q.wrowsh : q.rowsh; sw.qnormf = q.normf; sw.trowsh = wide ? t.wrowsh : t.rowsh; sw.tnormf = t.normf;
     sw.wks = wide ? (q.dim + 31) / 32 : 0;
     if (wide && !all) ctx->filter_launches += 1;      // (fm_f32_filter_stats: a call that ran the fp16 sweep; `all` runs none)
-    sw.q4 = q.rows4; sw.t4 = t.rows4; sw.ks = ham ? q.ksteps : 0; sw.W = 8 * q.dim;
+    sw.q4 = q.rows4; sw.t4 = t.rows4; sw.ks = ham ? fp4_steps(q) : 0; sw.W = ham2 ? 4 * q.dim : 8 * q.dim; sw.ham2 = ham2 ? 1 : 0;
     sw.cq = cq; sw.ct = ct; sw.all = all ? 1 : 0;
     sw.nt = (int)nt; sw.lim = d_lim; sw.thr = d_thr;
     sw.st_real = a.tab ? (const int*)a.tab->st_real : nullptr;

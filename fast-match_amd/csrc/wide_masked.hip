@@ -430,6 +430,8 @@ static int wide_masked_check(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, co
     if (!q || !t) return fail(ctx, FM_EINVAL, std::string(who) + ": bank is NULL");
     if (!m) return fail(ctx, FM_EINVAL, std::string(who) + ": mask is NULL");
     for (const fm_bank* b : {q, t})
+        if (int rc = refuse_bin2(ctx, b, who)) return rc;
+    for (const fm_bank* b : {q, t})
         if (b->kind != FM_BANK_F32W)
             return fail(ctx, FM_EINVAL, std::string(who) + ": both banks must be wide float (FM_BANK_F32W: fm_bank_create_f32 with 129 .. 256 "
                                         "values per row); fm_knn_masked is the call that serves the other kinds");

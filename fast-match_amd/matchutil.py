@@ -28,6 +28,20 @@ Mirrors ``matchutil.py`` of the reference:
   crossCheck)``); ``bf_match``, ``flann_match`` and ``ratio_match_arrays`` honour it, ``bf_radius_match`` does not
   (``ValueError``: ``hamming_radius_match`` is the call), nor does anything else take ``NORM_HAMMING2``.  Without ``normType`` every array is an L2 bank,
   a uint8 [n, 32] array included.
+* ``NORM_HAMMING2`` (7; ORB with ``WTA_K`` = 3 or 4, every descriptor element a 2-bit value) has calls of its own:
+  ``hamming2_match`` / ``hamming2_match_arrays`` (knnMatch, 1 <= k <= 8, crossCheck at k == 1), ``hamming2_ratio_match_arrays``,
+  ``hamming2_mutual_ratio_match_arrays``, ``hamming2_radius_match`` / ``hamming2_radius_match_arrays`` and cv2's factory
+  ``BFMatcher_create(7)``, whose object takes ``match`` / ``knnMatch`` / ``radiusMatch`` with a train argument.  The distance is
+  the number of 2-bit cells (bits 2c, 2c + 1 of a byte) in which two rows differ.  On the matrix cores a cell (a, b) is three
+  FP4 values (s_a, s_b, s_a s_b), s = +-1 -- the vertices of a tetrahedron -- so the dot product of two rows of P = 4 bytes
+  cells is 3 P - 4 h2, exact in float32 (``csrc/hamming2.hip``; 12 bytes values per row, ceil(12 bytes / 128) K steps: 1 .. 10
+  bytes one, .. 21 two, .. 32 three, .. 42 four, .. 53 five, .. 64 six; the sweeps hold two 128-row stages in 20,480 ..
+  102,400 bytes of LDS and 224 .. 400 registers, no scratch: DESIGN.md, K11b, which also has the measured cost beside
+  NORM_HAMMING -- 1.14 x to 1.28 x on the same rows).  Served by the library for two such banks: ``fm_knn2``, ``fm_knn``,
+  ``fm_xcheck1``, ``fm_knn2_ratio``, ``fm_mutual_ratio``, their ``_dev`` forms, ``fm_hamming_radius_match(_dev)``; every other
+  entry point refuses them (``FM_EUNSUPPORTED``).  Not built for this norm, ``ValueError`` before
+  anything is uploaded: ``options["normType"] = 7`` in the other calls, ``BFMatcher(7)``, masks, train collections
+  (``add`` / ``train`` / a call without a train argument), Fast-Match's self-distance test.
 * Wide float descriptors -- float arrays of 129 .. 256 values per row, SuperPoint's 256-D rows for one -- go to the
   library's wide float banks under ``NORM_L2``: ``bf_match`` with k <= 2 and with crossCheck, ``ratio_match_arrays`` and
   ``mutual_ratio_match_arrays`` take them; ``bf_radius_match``, a mask, k >= 3 and ``BFMatcher.add`` raise ``ValueError``
@@ -71,6 +85,7 @@ from . import _ffi
 
 NORM_L2 = 4             # cv2.NORM_L2
 NORM_HAMMING = 6        # cv2.NORM_HAMMING
+NORM_HAMMING2 = 7       # cv2.NORM_HAMMING2 (ORB with WTA_K = 3 or 4): served by the hamming2_* calls and BFMatcher_create(7)
 
 
 class DMatch(object):
@@ -108,9 +123,12 @@ def _norm_type(options, dt1, dt2):
     """options["normType"], checked against the operands BEFORE anything is uploaded (cv2 asserts the same in its matcher)."""
     norm = options.get("normType", NORM_L2) if options else NORM_L2
     if norm not in (NORM_L2, NORM_HAMMING):
-        raise ValueError("normType %r: the HIP path builds NORM_L2 (4) and NORM_HAMMING (6) only%s"
-                         % (norm, " (NORM_HAMMING2 is not built)" if norm == 7 else ""))
+        raise ValueError("normType %r: this call takes NORM_L2 (4) and NORM_HAMMING (6) only%s"
+                         % (norm, " (NORM_HAMMING2 is served by hamming2_match, hamming2_match_arrays, hamming2_ratio_match_arrays, "
+                                  "hamming2_mutual_ratio_match_arrays, hamming2_radius_match and BFMatcher_create(7))" if norm == 7 else ""))
     for d in (dt1, dt2):
+        if isinstance(d, _ffi.Bank) and d.kind == _ffi.FM_BANK_BIN2:
+            raise ValueError("a NORM_HAMMING2 bank (Context.bank_binary2) goes with the hamming2_* calls and BFMatcher_create(7) only")
         if isinstance(d, _ffi.Bank):
             if (d.kind == _ffi.FM_BANK_BIN) != (norm == NORM_HAMMING):
                 raise ValueError("a binary bank (Context.bank_binary) goes with normType NORM_HAMMING, and only it"
@@ -449,6 +467,177 @@ def hamming_radius_match(dt1, dt2, maxDistance, options={}):
     return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
 
 
+# ---- NORM_HAMMING2: binary descriptors of 2-bit cells (ORB with WTA_K = 3 or 4) -----------------------------------------------
+def _binary2_operand(d, who):
+    """A resident NORM_HAMMING2 bank, or a uint8 [n, 1 .. 64] array -- ValueError before anything is uploaded.
+    Returns (operand, bytes, rows)."""
+    if isinstance(d, _ffi.Bank):
+        if d.kind != _ffi.FM_BANK_BIN2:
+            raise ValueError("%s takes NORM_HAMMING2 banks (Context.bank_binary2); a NORM_HAMMING bank (Context.bank_binary) "
+                             "counts bits, not 2-bit cells, and goes to bf_match / hamming_radius_match" % who)
+        return d, d.dim, d.n
+    a = np.asarray(d)
+    if a.ndim != 2:
+        raise ValueError("%s: descriptors must be a 2-D [n, bytes] array" % who)
+    if a.dtype != np.uint8:
+        raise ValueError("%s needs uint8 descriptors (cv2 asserts CV_8U for NORM_HAMMING2), got %s" % (who, a.dtype))
+    if not 1 <= a.shape[1] <= 64:
+        raise ValueError("%s: binary descriptors have 1 .. 64 bytes per row, got %d" % (who, a.shape[1]))
+    return a, a.shape[1], a.shape[0]
+
+
+def _binary2_pair(dt1, dt2, who, options):
+    """Both operands checked -- uint8, 2-D, 1 .. 64 columns, equal widths, no mask -- BEFORE the library is touched."""
+    q, qw, nq = _binary2_operand(dt1, who)
+    t, tw, _ = _binary2_operand(dt2, who)
+    if qw != tw:
+        raise ValueError("%s: %d bytes per query row, %d per train row" % (who, qw, tw))
+    if options and options.get("mask") is not None:
+        raise ValueError("%s: a mask is not built for NORM_HAMMING2" % who)
+    return q, t, nq
+
+
+class _Binary2Banks(object):
+    """The two operands as NORM_HAMMING2 banks for one call (arrays are uploaded and closed again)."""
+    def __init__(self, ctx, q, t):
+        self.own = []
+        try:
+            self.banks = [self._one(ctx, d) for d in (q, t)]
+        except Exception:
+            self.close()
+            raise
+
+    def _one(self, ctx, d):
+        if isinstance(d, _ffi.Bank):
+            return d
+        b = ctx.bank_binary2(d)
+        self.own.append(b)
+        return b
+
+    def close(self):
+        for b in self.own:
+            b.close()
+        self.own = []
+
+    def __enter__(self):
+        return self.banks
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def hamming2_match_arrays(dt1, dt2, k=1, options={}):
+    """``cv2.BFMatcher(cv2.NORM_HAMMING2, crossCheck).knnMatch(dt1, dt2, k)`` as arrays, :func:`bf_match_arrays`' shapes: the
+    distance is the number of 2-bit cells (bits 2c, 2c + 1 of a byte) in which two rows differ, lists ascend by (distance,
+    train index).  crossCheck is honoured at ``k == 1``.  ``dt1`` / ``dt2``: uint8 arrays of 1 .. 64 bytes per row or resident
+    NORM_HAMMING2 banks (``Context.bank_binary2``); 1 <= k <= 8."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("hamming2_match: k must be at least 1")
+    if k > 8:
+        raise ValueError("hamming2_match: k = %d: the HIP path builds k-NN lists up to k = 8" % k)
+    crossCheck = k == 1 and bool(options) and options.get("crossCheck", False) == True   # noqa: E712  (bf_match's rule)
+    q, t, _ = _binary2_pair(dt1, dt2, "hamming2_match", options)
+    ctx = _context(options)
+    with _Binary2Banks(ctx, q, t) as (qb, tb):
+        if crossCheck:
+            return ctx.xcheck1(qb, tb)
+        if k > 2:
+            return ctx.knn(qb, tb, k)
+        idx, dist = ctx.knn2(qb, tb)
+        return idx[:, :k], dist[:, :k]
+
+
+def hamming2_match(dt1, dt2, k=1, options={}):
+    """ cv2.BFMatcher(NORM_HAMMING2[, crossCheck]).knnMatch(dt1, dt2, k): a list of DMatch lists, one per query row """
+    idx, dist = hamming2_match_arrays(dt1, dt2, k=k, options=options)
+    return matches_from_arrays(idx, dist)
+
+
+def hamming2_ratio_match_arrays(dt1, dt2, tau, options={}):
+    """:func:`ratio_match_arrays` under NORM_HAMMING2 (``fm_knn2_ratio`` on two NORM_HAMMING2 banks)."""
+    q, t, _ = _binary2_pair(dt1, dt2, "hamming2_ratio_match_arrays", options)
+    ctx = _context(options)
+    with _Binary2Banks(ctx, q, t) as (qb, tb):
+        return ctx.knn2_ratio(qb, tb, tau)
+
+
+def hamming2_mutual_ratio_match_arrays(dt1, dt2, tau, symmetric=False, options={}):
+    """:func:`mutual_ratio_match_arrays` under NORM_HAMMING2 (``fm_mutual_ratio`` on two NORM_HAMMING2 banks)."""
+    q, t, _ = _binary2_pair(dt1, dt2, "hamming2_mutual_ratio_match_arrays", options)
+    ctx = _context(options)
+    with _Binary2Banks(ctx, q, t) as (qb, tb):
+        return ctx.mutual_ratio(qb, tb, tau, symmetric)
+
+
+def hamming2_radius_match_arrays(dt1, dt2, maxDistance, options={}):
+    """``cv2.BFMatcher(cv2.NORM_HAMMING2).radiusMatch`` as arrays, :func:`hamming_radius_match_arrays`' shapes: every train row
+    whose cell count is < ``maxDistance`` (strict, float32; a radius above 4 * bytes admits every row), ascending by
+    (distance, train index).  ``maxDistance``: a scalar or one radius per query row."""
+    q, t, nq = _binary2_pair(dt1, dt2, "hamming2_radius_match", options)
+    if np.ndim(maxDistance) != 0 and np.asarray(maxDistance).reshape(-1).shape[0] != nq:
+        raise ValueError("hamming2_radius_match: %d radii for %d query rows" % (np.asarray(maxDistance).reshape(-1).shape[0], nq))
+    ctx = _context(options)
+    with _Binary2Banks(ctx, q, t) as (qb, tb):
+        return ctx.hamming_radius_match(qb, tb, maxDistance)
+
+
+def hamming2_radius_match(dt1, dt2, maxDistance, options={}):
+    """ cv2.BFMatcher(NORM_HAMMING2).radiusMatch(dt1, dt2, maxDistance): a list of DMatch lists, one per query row """
+    off, idx, dist = hamming2_radius_match_arrays(dt1, dt2, maxDistance, options=options)
+    return [[DMatch(qi, idx[j], dist[j]) for j in range(off[qi], off[qi + 1])] for qi in range(off.shape[0] - 1)]
+
+
+class Hamming2Matcher(object):
+    """What :func:`BFMatcher_create` returns for NORM_HAMMING2: ``match`` / ``knnMatch`` / ``radiusMatch`` with a train
+    argument.  A train collection (``add`` / ``train`` / a call without a train argument) and masks are not built for this
+    norm: ``ValueError``, before anything is uploaded."""
+
+    def __init__(self, crossCheck=False, options={}):
+        self.normType = NORM_HAMMING2
+        self.crossCheck = bool(crossCheck)
+        self.options = dict(options)
+
+    def add(self, descriptors):
+        raise ValueError("BFMatcher(NORM_HAMMING2).add: a train collection is not built for NORM_HAMMING2; pass a train argument")
+
+    def train(self):
+        raise ValueError("BFMatcher(NORM_HAMMING2).train: a train collection is not built for NORM_HAMMING2; pass a train argument")
+
+    def _checked(self, who, trainDescriptors, mask, masks):
+        if mask is not None or masks is not None:
+            raise ValueError("BFMatcher(NORM_HAMMING2).%s: masks are not built for NORM_HAMMING2" % who)
+        if trainDescriptors is None:
+            raise ValueError("BFMatcher(NORM_HAMMING2).%s: a train collection is not built for NORM_HAMMING2; pass a train argument" % who)
+
+    def knnMatch(self, queryDescriptors, trainDescriptors=None, k=None, mask=None, masks=None):
+        if k is None and trainDescriptors is not None and np.isscalar(trainDescriptors):
+            trainDescriptors, k = None, trainDescriptors          # knnMatch(query, k)
+        self._checked("knnMatch", trainDescriptors, mask, masks)
+        if k is None:
+            raise TypeError("knnMatch: k is required")
+        return hamming2_match(queryDescriptors, trainDescriptors, k=k, options=dict(self.options, crossCheck=self.crossCheck))
+
+    def match(self, queryDescriptors, trainDescriptors=None, mask=None, masks=None):
+        self._checked("match", trainDescriptors, mask, masks)
+        return [m[0] for m in self.knnMatch(queryDescriptors, trainDescriptors, k=1) if m]
+
+    def radiusMatch(self, queryDescriptors, trainDescriptors=None, maxDistance=None, mask=None, compactResult=False):
+        if maxDistance is None and trainDescriptors is not None and np.isscalar(trainDescriptors):
+            trainDescriptors, maxDistance = None, trainDescriptors
+        self._checked("radiusMatch", trainDescriptors, mask, None)
+        if maxDistance is None:
+            raise TypeError("radiusMatch: maxDistance is required")
+        return hamming2_radius_match(queryDescriptors, trainDescriptors, maxDistance, options=self.options)
+
+
+def BFMatcher_create(normType=NORM_L2, crossCheck=False, options={}):
+    """cv2's factory: :class:`BFMatcher` for NORM_L2 (4) and NORM_HAMMING (6), a :class:`Hamming2Matcher` for NORM_HAMMING2 (7)."""
+    if normType == NORM_HAMMING2:
+        return Hamming2Matcher(crossCheck=crossCheck, options=options)
+    return BFMatcher(normType, crossCheck=crossCheck, options=options)
+
+
 def hamming_fast_match_arrays(dt1, dt2, tau, options={}):
     """Fast-Match's accepted-match test on binary descriptors: ``(qidx int32[m], tidx int32[m], dist float32[m], ratio
     float64[m])``, ascending query index -- the pairs for which t is the cross-checked nearest neighbour of q under
@@ -642,7 +831,8 @@ class BFMatcher(object):
 
     def __init__(self, normType=NORM_L2, crossCheck=False, options={}):
         if normType not in (NORM_L2, NORM_HAMMING):
-            raise ValueError("normType %r: the HIP path builds NORM_L2 (4) and NORM_HAMMING (6) only" % (normType,))
+            raise ValueError("normType %r: BFMatcher builds NORM_L2 (4) and NORM_HAMMING (6) only%s"
+                             % (normType, " (NORM_HAMMING2: BFMatcher_create(7) returns the matcher that serves it)" if normType == 7 else ""))
         self.normType = normType
         self.crossCheck = bool(crossCheck)
         self.options = dict(options)

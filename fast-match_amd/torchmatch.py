@@ -6,9 +6,11 @@ library as it is (``fm_bank_create_dev``: the preparation kernels read the tenso
 leave the results in tensors the library's kernels write directly (``fm_knn_dev`` / ``fm_xcheck1_dev`` /
 ``fm_knn2_ratio_dev``).  Nothing crosses PCIe.
 
-* ``bank(tensor, *, binary=False, float_route=False, context=None)`` -- a resident ``Bank`` from a 2-D CUDA tensor of dtype
+* ``bank(tensor, *, binary=False, hamming2=False, float_route=False, context=None)`` -- a resident ``Bank`` from a 2-D CUDA tensor of dtype
   uint8, float32, float16 or bfloat16 (``binary``: uint8 rows of 1 .. 64 packed bytes for Hamming distance).  On return the
-  tensor may be overwritten.
+  tensor may be overwritten.  ``hamming2``: the same rows for NORM_HAMMING2 (ORB with WTA_K = 3 or 4: the distance counts the
+  2-bit cells that differ); ``knn``, ``mutual_nn``, ``ratio_match``, ``mutual_ratio_match`` and ``hamming_radius_match`` take
+  two such resident banks, ``Collection.add``, a collection query and every masked call refuse them with ``ValueError``.
 * ``knn(q, t, k, mask=None)`` -> ``(idx int32 [nq, k], dist float32 [nq, k])``, 1 <= k <= 8.  ``mask``: a CUDA ``bool`` /
   ``uint8`` tensor ``[nq, nt]``, nonzero = the pair may be matched (cv2's ``knnMatch(q, t, k, mask)``), or a resident
   ``_ffi.Mask``; rows may be pitched (a column slice of a wider tensor).  It is packed into the library's bit mask on the
@@ -93,7 +95,7 @@ _DTYPES = {"torch.uint8": _ffi.FM_DT_U8, "torch.float32": _ffi.FM_DT_F32, "torch
            "torch.bfloat16": _ffi.FM_DT_BF16}
 
 
-def _checked(tensor, binary=False):
+def _checked(tensor, binary=False, hamming2=False):
     """(tensor with unit column stride, FM_DT_*) or ValueError -- before anything reaches the library."""
     import torch
     if not isinstance(tensor, torch.Tensor):
@@ -105,10 +107,14 @@ def _checked(tensor, binary=False):
     dt = _DTYPES.get(str(tensor.dtype))
     if dt is None:
         raise ValueError("descriptor dtype %s: uint8, float32, float16 or bfloat16 are taken" % tensor.dtype)
-    if binary:
+    if binary and hamming2:
+        raise ValueError("binary (NORM_HAMMING) and hamming2 (NORM_HAMMING2) are two norms: ask for one")
+    if binary or hamming2:
         if dt != _ffi.FM_DT_U8:
             raise ValueError("binary descriptors must be uint8 (packed bits), got %s" % tensor.dtype)
-        dt = _ffi.FM_DT_BIN
+        if hamming2 and not 1 <= tensor.shape[1] <= 64:
+            raise ValueError("NORM_HAMMING2 descriptors have 1 .. 64 bytes per row, got %d" % tensor.shape[1])
+        dt = _ffi.FM_DT_BIN2 if hamming2 else _ffi.FM_DT_BIN
     if tensor.shape[1] < 1:
         raise ValueError("descriptors must have at least one column")
     # rows may be pitched (a column slice of a wider tensor); elements of a row must be adjacent.  (A one-row or empty
@@ -131,6 +137,14 @@ def _refuse_wide(who, what, *operands):
         if wide:
             raise ValueError("%s: %s is not built for wide float descriptors (129 .. 256 values per row: knn with k <= 2, "
                              "mutual_nn, ratio_match and mutual_ratio_match are)" % (who, what))
+
+
+def _refuse_hamming2(who, what, *operands):
+    """ValueError before the library is touched: a NORM_HAMMING2 bank (``bank(tensor, hamming2=True)``) is served by ``knn``,
+    ``mutual_nn``, ``ratio_match``, ``mutual_ratio_match`` and ``hamming_radius_match`` without a mask, and by nothing else."""
+    if any(isinstance(x, _ffi.Bank) and x.kind == _ffi.FM_BANK_BIN2 for x in operands):
+        raise ValueError("%s: %s is not built for NORM_HAMMING2 banks (knn, mutual_nn, ratio_match, mutual_ratio_match and "
+                         "hamming_radius_match without a mask are)" % (who, what))
 
 
 def _checked_mask(m, nq, nt, what="mask"):
@@ -184,10 +198,11 @@ def _ctx_for(tensor, context):
     return context if context is not None else _ffi.default_context(tensor.device.index)
 
 
-def bank(tensor, *, binary=False, float_route=False, context=None):
-    """A resident ``Bank`` from a CUDA tensor, read in place behind the current stream's work (module docstring)."""
+def bank(tensor, *, binary=False, hamming2=False, float_route=False, context=None):
+    """A resident ``Bank`` from a CUDA tensor, read in place behind the current stream's work (module docstring).
+    ``hamming2``: uint8 rows of 1 .. 64 packed bytes whose elements are 2-bit values, for NORM_HAMMING2 (``FM_DT_BIN2``)."""
     import torch
-    tensor, dt = _checked(tensor, binary)
+    tensor, dt = _checked(tensor, binary, hamming2)
     ctx = _ctx_for(tensor, context)
     n, dim = tensor.shape
     with torch.cuda.device(tensor.device):
@@ -230,6 +245,7 @@ def knn(q, t, k, mask=None):
         raise ValueError("k must be at least 1")
     if mask is not None:
         _refuse_wide("knn", "a mask", q, t)
+        _refuse_hamming2("knn", "a mask", q, t)
     if k > 2:
         _refuse_wide("knn", "k >= 3", q, t)
     if mask is not None and not isinstance(mask, _ffi.Mask):
@@ -362,6 +378,7 @@ def radius_match(q, t, r, mask=None):
     CUDA tensor [nq, nt] or a resident Mask, as in ``knn``): the same lists without the pairs it forbids
     (``fm_radius_match_masked_dev``)."""
     _refuse_wide("radius_match", "radiusMatch", q, t)
+    _refuse_hamming2("radius_match", "the L2 radiusMatch (hamming_radius_match is the call)", q, t)
     nq, device = _rows_and_device(q)
     if not isinstance(t, _ffi.Bank):
         _checked(t)
@@ -379,10 +396,10 @@ def radius_match(q, t, r, mask=None):
             b.close()
 
 
-def _binary_operand(who, x):
+def _binary_operand(who, x, hamming2_ok=False):
     """A binary bank as it is, or a checked uint8 tensor of 1 .. 64 bytes per row -- ValueError before the library is touched."""
     if isinstance(x, _ffi.Bank):
-        if x.kind != _ffi.FM_BANK_BIN:
+        if x.kind != _ffi.FM_BANK_BIN and not (hamming2_ok and x.kind == _ffi.FM_BANK_BIN2):
             raise ValueError("%s takes binary banks (bank(tensor, binary=True)); radius_match is the L2 call" % who)
         return x
     t, _ = _checked(x, binary=True)
@@ -396,9 +413,16 @@ def hamming_radius_match(q, t, r, mask=None):
     ``cv2.BFMatcher(NORM_HAMMING).radiusMatch`` on binary descriptors: ``(offsets int64 [nq + 1], idx int32 [n], dist
     float32 [n])`` CUDA tensors, every train row with ``popcount(q XOR t) < r`` per query row (strict, float32: ``h <= H`` is
     ``r = H + 0.5``), ascending (h, train index).  ``q`` / ``t``: uint8 CUDA tensors of packed bits or binary ``Bank``s;
-    ``r`` as in ``radius_match``.  One host wait for the total."""
+    ``r`` as in ``radius_match``.  One host wait for the total.  Two NORM_HAMMING2 banks (``bank(tensor, hamming2=True)``): the
+    same lists under the cell count of NORM_HAMMING2, without a mask."""
     who = "hamming_radius_match"
-    ops = [_binary_operand(who, x) for x in (q, t)]
+    ops = [_binary_operand(who, x, hamming2_ok=True) for x in (q, t)]
+    if any(isinstance(x, _ffi.Bank) and x.kind == _ffi.FM_BANK_BIN2 for x in ops):
+        # NORM_HAMMING2: two resident banks of that kind (a tensor is a NORM_HAMMING operand), the radius against the cell count
+        if not all(isinstance(x, _ffi.Bank) and x.kind == _ffi.FM_BANK_BIN2 for x in ops):
+            raise ValueError("%s: a NORM_HAMMING2 bank pairs with another NORM_HAMMING2 bank only (bank(tensor, hamming2=True))" % who)
+        if mask is not None:
+            _refuse_hamming2(who, "a mask", *ops)
     widths = [x.dim if isinstance(x, _ffi.Bank) else x.shape[1] for x in ops]
     if widths[0] != widths[1]:
         raise ValueError("%s: %d bytes per query row, %d per train row" % (who, widths[0], widths[1]))
@@ -629,12 +653,14 @@ class Collection(object):
             self._coll = self._context.collection()
         return self._coll
 
-    def add(self, tensor, *, binary=False):
+    def add(self, tensor, *, binary=False, hamming2=False):
         """Append one image ([n, dim] uint8 / float32 / float16 / bfloat16, or ``binary`` uint8 rows of packed bits; n may be
         0), read in place behind the current stream's work -- pitched rows with unit column stride included.  Returns the
         image's index.  On return the tensor may be overwritten."""
         import torch
         self._refuse_wide_collection("add")
+        if hamming2:
+            raise ValueError("Collection.add: a train collection is not built for NORM_HAMMING2 (banks of that norm are matched as pairs)")
         if not binary:
             _refuse_wide("Collection.add", "a train collection (wide float images go in through add_wide)", tensor)
         tensor, dt = _checked(tensor, binary)
@@ -672,6 +698,7 @@ class Collection(object):
         """(query bank, [banks made for this call]); every refusal before anything reaches the library."""
         self._refuse_wide_collection("knn / ratio_match / radius_match / *_each")
         _refuse_wide("Collection", "a query against a train collection", q)
+        _refuse_hamming2("Collection", "a query against a train collection", q)
         if isinstance(q, _ffi.Bank):
             self._collection(q.ctx)
             return q, []

@@ -49,6 +49,7 @@ extern "C" {
 #define FM_BANK_F32  2       /* general float32 rows: fp32 fma-chain route                    */
 #define FM_BANK_BIN  3       /* binary descriptors (fm_bank_create_bin): Hamming distance, K11 */
 #define FM_BANK_F32W 4       /* float32 rows of 129 .. 256 values ("wide float banks", K14)    */
+#define FM_BANK_BIN2 5       /* binary descriptors of 2-bit cells (fm_bank_create_bin2): NORM_HAMMING2, K11b */
 
 typedef struct fm_ctx  fm_ctx;
 typedef struct fm_bank fm_bank;
@@ -83,7 +84,8 @@ typedef struct fm_bank fm_bank;
  * fm_collection_wide_radius_match_dev; still revision 12, additions only -- fm_wide_knn_masked, fm_wide_knn_masked_dev; still
  * revision 12, additions only -- fm_collection_wide_knn, fm_collection_wide_knn_dev, fm_collection_wide_knn2_ratio,
  * fm_collection_wide_knn2_ratio_dev, fm_collection_wide_votes; still revision 12, additions only -- fm_radius_match_masked,
- * fm_radius_match_masked_dev, fm_collection_radius_match_masked, fm_collection_radius_match_masked_dev).  A binding
+ * fm_radius_match_masked_dev, fm_collection_radius_match_masked, fm_collection_radius_match_masked_dev; still revision 12,
+ * additions only -- FM_BANK_BIN2, FM_DT_BIN2, fm_bank_create_bin2).  A binding
  * compares fm_abi_version() with the FM_ABI_VERSION it was written against before its first call.              */
 #define FM_ABI_VERSION 12
 int  fm_abi_version(void);
@@ -240,8 +242,33 @@ int  fm_bank_create_f32_route(fm_ctx* ctx, const float* rows, int64_t n, int dim
  * fm_xcheck1_batched, fm_bank_refill_u8_async, fm_bank_append_*, fm_expand_create.  A binary bank paired with a non-binary one
  * is FM_EINVAL, even when one of them is empty.  Not built: NORM_HAMMING2, masked Hamming radius queries, the expansion loop
  * (fm_expand_*) and the async / batch / sharded-key forms of the accepted-match test on binary banks, k > 8.  (Masked Hamming
- * radius queries have since come: "Masked radiusMatch" below.)                                                                 */
+ * radius queries have since come: "Masked radiusMatch" below.)  (NORM_HAMMING2 has since come, for bank pairs:
+ * "K11b: NORM_HAMMING2" below.)                                                                                                */
 int  fm_bank_create_bin(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t n, int bytes, fm_bank** bank);
+/* ---- K11b: NORM_HAMMING2 ---------------------------------------------------------------------------------------------------
+ * cv2.BFMatcher(cv2.NORM_HAMMING2[, crossCheck]): the norm OpenCV prescribes for ORB with WTA_K = 3 or 4, where every
+ * descriptor element is a 2-bit value.  fm_bank_create_bin2 follows fm_bank_create_bin's rules word for word (1 <= bytes <= 64;
+ * 0 or negative: FM_EINVAL; > 64: FM_EUNSUPPORTED; n may be 0; the errors and their order are the same); fm_bank_info reports
+ * dim = bytes, kind = FM_BANK_BIN2.  fm_bank_create_dev with FM_DT_BIN2 makes the same bank from device rows read in place at
+ * their pitch.  Contract (cv::normHamming with cellSize = 2): h2(q, t) = the number of 2-bit cells of q XOR t that are non-zero,
+ * a cell being bits 2c, 2c + 1 of a byte; dist = (float)h2, exact; P = 4 * bytes cells per row.  Every ordering rule is K11's
+ * with h2 for h: lists ascend by (h2, train index), strict compares, the lowest index wins a tie.
+ * Served, for a pair of FM_BANK_BIN2 banks of one width, under K11's contracts: fm_knn2, fm_knn (1 <= k <= 8), fm_xcheck1,
+ * fm_knn2_ratio, fm_mutual_ratio, fm_knn_dev, fm_xcheck1_dev, fm_knn2_ratio_dev, fm_mutual_ratio_dev and
+ * fm_hamming_radius_match(_dev) (the radius against h2; r > P admits every real row).
+ * k = 1, 2, crossCheck and the radius sweeps run on the matrix cores (hamming2.hip): a cell (a, b) becomes three FP4 values
+ * (s_a, s_b, s_a s_b), s = +1 for a 1 bit and -1 for a 0 bit -- the four vertices of a tetrahedron -- so two equal cells add
+ * +3 to the dot product of two rows and two different ones -1, whether they differ in one bit or both: dot = 3 P - 4 h2, every
+ * partial sum an integer of magnitude <= 768, exact in the f32 accumulator of v_mfma_scale_f32_16x16x128_f8f6f4 in any order.
+ * A row is 12 * bytes FP4 values, ceil(12 * bytes / 128) K steps (a 32-byte ORB row: three).  k = 3 .. 8: vector ALUs, the
+ * population count of (x | x >> 1) & 0x55555555 over the packed rows.
+ * Refused with FM_EUNSUPPORTED and a message that names NORM_HAMMING2, before any kernel reads the bank: every other entry
+ * point that takes a bank, a mask or a collection -- the knn and radius masks (fm_mask_create for such banks included), the
+ * Hamming Fast-Match family (fm_hamming_self_dist(_batch), fm_hamming_set_selfdist, fm_hamming_match_*), the fm_collection_*
+ * calls (fm_collection_add_dev with FM_DT_BIN2 included), every L2-only call, fm_expand_create, the async and batch forms.  A
+ * FM_BANK_BIN2 bank paired with a bank of any other kind is FM_EINVAL, even when one of them is empty -- a NORM_HAMMING bank
+ * (FM_BANK_BIN) of the same width included: the two norms never mix.                                                          */
+int fm_bank_create_bin2(fm_ctx* ctx, const uint8_t* rows /*[n][bytes]*/, int64_t n, int bytes, fm_bank** bank);
 /* ---- K14: wide float banks, 129 .. 256 values per row ---------------------------------------------------------------------
  * The 256-D float descriptors of learned extractors (SuperPoint and its kin).  fm_bank_create_f32, fm_bank_create_f32_route and
  * fm_bank_create_dev with FM_DT_F32 / FM_DT_F16 / FM_DT_BF16 (half and bfloat16 widened exactly, the source read in place at
@@ -451,7 +478,8 @@ int fm_hamming_radius_match(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, con
  * unchanged.
  * Not built: a triangular sweep (every tile once, for both directions); an accepted-only Hamming sweep seeded with the ratio
  * cut; fm_expand_* on binary banks; the async / batch / sharded-key forms (fm_match_accepted_async, _batch, _dev_async,
- * _dev_batch, fm_xcheck1_keys*) for binary banks; NORM_HAMMING2.
+ * _dev_batch, fm_xcheck1_keys*) for binary banks; NORM_HAMMING2.  (NORM_HAMMING2 has since come for knnMatch, crossCheck,
+ * the ratio tests and radiusMatch on bank pairs -- "K11b: NORM_HAMMING2" above -- and stays out of Fast-Match.)
  * fm_collection_hamming_match_accepted_each(_dev): with the collections below.                                            */
 int fm_hamming_self_dist(fm_ctx* ctx, const fm_bank* bank, double* selfdist /*[n]*/);
 int fm_hamming_self_dist_batch(fm_ctx* ctx, int32_t n, fm_bank* const* banks, double* const* out /*NULL, or [n] of NULL / [n_i]*/);
@@ -767,7 +795,8 @@ int fm_wide_radius_match_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, co
  * images, turning an integer-route collection of float32 images into a float32-route one for a
  * non-integer QUERY, and for fm_collection_pairs_mutual_ratio: a sweep that computes a pair's tiles once for both
  * directions (d(i, j) = d(j, i): half the matrix-core work of a pair), sharing sweeps between (a, b) and (b, a) of one
- * pair list (the two pairs run the same two sweeps).                                     */
+ * pair list (the two pairs run the same two sweeps).  (NORM_HAMMING2 has since come for bank pairs -- "K11b: NORM_HAMMING2"
+ * above; a collection still takes no FM_BANK_BIN2 rows and no such query bank: FM_EUNSUPPORTED.)                         */
 typedef struct fm_collection fm_collection;
 #define FM_COLLECTION_F32_MAX 144115188075855872.0f   /* 2^57: largest finite magnitude of a float32-route collection and its queries */
 int  fm_collection_create(fm_ctx* ctx, fm_collection** coll);
@@ -948,6 +977,7 @@ int  fm_collection_wide_mutual_ratio_each_dev(fm_ctx* ctx, fm_collection* coll, 
 #define FM_DT_F16  3
 #define FM_DT_BF16 4
 #define FM_DT_BIN  5
+#define FM_DT_BIN2 6      /* packed binary rows of 2-bit cells, dim = bytes (1 .. 64) -> FM_BANK_BIN2 (fm_bank_create_bin2); banks only */
 int  fm_bank_create_dev(fm_ctx* ctx, const void* d_rows, int dtype, int64_t n, int dim, int64_t row_pitch_bytes /*0 = dense*/,
                         int float_route, void* producer_stream /*hipStream_t, NULL = null stream, or FM_NO_STREAM*/, fm_bank** bank);
 int  fm_knn_dev(fm_ctx* ctx, const fm_bank* q, const fm_bank* t, int32_t k, int32_t* d_idx /*device [nq*k]*/,
